@@ -4,7 +4,11 @@
 and the same-box CPU baseline.
 
 Contract (one JSON line on stdout from rank 0):
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps, writes the last step's output if asked, and prints the headline line.
+``--full`` adds everything else the benchmark measures or checks: parity of the timed batch against the oracle, the
+dominant-kernel roofline, batch-1 latency, the training steps/s of C2 - C5, the other generators' inference and the
+same-box CPU baselines (compact line on stdout, full record in the detail file).
 A "step" is one forward pass of the generator over one resident batch of
 synthetic mel frames (B utterances x F frames, mel ~ N(0,1), random-init weights
 of the V1 architecture, weight norm removed as bin/decode.py does).  N > 1 runs
@@ -669,6 +673,54 @@ def rccl_log_summary(max_lines=6):
             "algo_proto_counts": algos, "large_allreduce": large, "sample_lines": samples}
 
 
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(directory, arrays, seed=0):
+    """``--dump-outputs DIR``: every array as ``DIR/<name>.npy`` in float32.  Should they exceed 64 MiB together, each is
+    replaced by a fixed, seeded sample of its flattened elements (``DIR/<name>_sample.npy``, indices in ascending
+    order), the same for the same shapes, so that two builds can be compared output for output."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    total = sum(t.numel() * 4 for t in arrays.values())
+    for name, t in arrays.items():
+        t = t.detach().float()
+        if total > DUMP_LIMIT_BYTES:
+            k = t.numel() * DUMP_LIMIT_BYTES // total
+            idx = np.sort(np.random.default_rng(seed).integers(0, t.numel(), k))
+            t, name = t.reshape(-1)[torch.from_numpy(idx).to(t.device)], name + "_sample"
+        np.save(os.path.join(directory, name + ".npy"), t.cpu().numpy())
+
+
+def headline(args, world, elapsed, samples_per_step):
+    """The headline measurement: the keys of the bench contract, before anything ``--full`` adds."""
+    value = samples_per_step * world * args.steps / elapsed
+    return {
+        "metric": "HiFi-GAN V1 22.05 kHz generator inference RTF^-1 (audio samples/s)",
+        "value": value,
+        "unit": "samples/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {
+            "workload": f"HiFi-GAN V1 generator forward (configs[2], LJSpeech 22.05 kHz), "
+                        f"{args.batch} utterances x {args.frames} mel frames per GPU per step, fp32, "
+                        f"weight norm removed, random-init weights",
+            "batch_per_gpu": args.batch,
+            "frames": args.frames,
+            "samples_per_step_per_gpu": samples_per_step,
+            "parallelism": f"replicas x{world}",
+        },
+    }
+
+
 COMPACT_LIMIT = 1900  # the driver keeps a 2000-byte tail of stdout: the ONE stdout line must fit inside it
 
 
@@ -719,9 +771,9 @@ def compact_line(out):
     if par:
         line["parity"] = {"max_abs_vs_oracle": float(f"{par['max_abs_vs_oracle']:.3g}"), "tol": par["tolerance"],
                           "ok": par["ok"]}
-    line["train_steps_per_s"] = out.get("train_steps_per_s")
-    line["train_ok"] = out.get("train_ok")
-    line["hip_graph"] = out.get("hip_graph")
+    for key in ("train_steps_per_s", "train_ok", "hip_graph"):  # absent from a plain run's headline
+        if key in out:
+            line[key] = out[key]
     if tr:
         line["train"] = {"config": out.get("train_config"), "batch_per_gpu": tr.get("batch_per_gpu"),
                          "ms_per_step": _r(tr.get("ms_per_step"), 3),
@@ -737,7 +789,8 @@ def compact_line(out):
                                      "exposed_comm_ms_per_exchange": {k: _r(v, 3) for k, v in
                                                                       d.get("exposed_comm_ms_per_exchange", {}).items()},
                                      "rccl": {"nranks": rc.get("nranks"), "large_allreduce": rc.get("large_allreduce")}}
-    line["detail"] = out.get("detail_file")
+    if "detail_file" in out:
+        line["detail"] = out["detail_file"]
     text = json.dumps(line, separators=(",", ":"))
     if len(text) > COMPACT_LIMIT:  # never exceed the tail: drop the optional objects, least important first
         for key in ("detail", "train", "infer_Msps_b16_b1_err", "parity"):
@@ -787,6 +840,11 @@ def main():
     ap.add_argument("--train-warmup", type=int, default=10, help=">= 3 so that the hipGraph capture is not timed")
     ap.add_argument("--no-graph", action="store_true", help="run the training step eagerly (no hipGraph replay)")
     ap.add_argument("--train-batch", type=int, default=0, help="override the C3 batch per GPU (default: the recipe's 16)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline (parity, roofline, latency, training, "
+                         "other configs, CPU baselines); the --no-* options above select within it")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the waveforms of the last timed step (rank 0) as DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -878,6 +936,17 @@ def main():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
+    head = headline(args, world, elapsed, samples_per_step)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"waveform": y})
+    if not args.full:
+        if rank == 0:
+            sys.stdout.flush()
+            os.write(real_stdout, (compact_line(head) + "\n").encode())
+        if world > 1 or force_dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- parity of THIS workload: utterances 0 and B-1 of the timed batch against the oracle
     parity = None
@@ -995,7 +1064,7 @@ def main():
             configs["c4_mbmelgan_inference"] = {"error": f"{type(e).__name__}: {e}"}
 
     if rank == 0:
-        value = samples_per_step * world * args.steps / elapsed
+        value = head["value"]
         train_brief, train_ok = None, None
         if train is not None:
             runs = {main_tag: train, **{k[:2]: v for k, v in configs.items() if k.endswith("_train")}}
@@ -1003,27 +1072,7 @@ def main():
             # False as soon as ANY measured training configuration produced a non-finite loss (or failed to run)
             train_ok = all(v.get("losses_finite", False) for v in runs.values())
         out = {
-            "metric": "HiFi-GAN V1 22.05 kHz generator inference RTF^-1 (audio samples/s)",
-            "value": value,
-            "unit": "samples/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
-            "config": {
-                "workload": f"HiFi-GAN V1 generator forward (configs[2], LJSpeech 22.05 kHz), "
-                            f"{args.batch} utterances x {args.frames} mel frames per GPU per step, fp32, "
-                            f"weight norm removed, random-init weights",
-                "batch_per_gpu": args.batch,
-                "frames": args.frames,
-                "samples_per_step_per_gpu": samples_per_step,
-                "parallelism": f"replicas x{world}",
-            },
+            **head,
             "rtf": 22050.0 / value,
             # the training results in brief, early in the line (the full objects follow under "train" / "configs")
             "train_steps_per_s": train_brief,

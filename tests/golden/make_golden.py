@@ -62,6 +62,25 @@ def hifigan_generator(name, cfg, batch, frames, seed):
     print(name, "y", tuple(y.shape), "std %.4f max %.4f pre-tanh std %.3f" % (y.std().item(), y.abs().max().item(), pre[0].std().item()))
 
 
+def collater(name):
+    """The reference Collater's batches for tests/test_collater.py (same items, options and seeds as the test)."""
+    from parallel_wavegan.bin.train import Collater
+
+    from tests import test_collater as tc
+
+    items = tc.reference_case_items()
+    out = {}
+    for tag, kw, n in tc.REFERENCE_CASES:
+        np.random.seed(5)
+        torch.manual_seed(5)
+        ins, y = Collater(**tc.reference_case_args(kw))([it[:n] for it in items])
+        out[f"{tag}_y"] = y.numpy()
+        for i, t in enumerate(ins):
+            out[f"{tag}_in{i}"] = t.numpy()
+    np.savez_compressed(os.path.join(OUT, f"{name}.npz"), **out)
+    print(name, {k: v.shape for k, v in out.items()})
+
+
 def _load_yaml(name, corpus="ljspeech"):
     import yaml
 
@@ -631,6 +650,7 @@ JOBS = {
     "hifigan_v1_d": lambda: hifigan_discriminator("hifigan_v1_d", 21),
     "losses": lambda: losses("losses", 31),
     "adv_losses": lambda: adv_losses("adv_losses", 33),
+    "collater": lambda: collater("collater"),
     "hifigan_v1_train": lambda: hifigan_train_steps("hifigan_v1_train", 41),
     "c2_train_full": lambda: train_full_shape("c2_train_full", "c2", 171),
     "c3_train_full": lambda: train_full_shape("c3_train_full", "c3", 141),

@@ -168,3 +168,36 @@ def test_compact_line_sheds_optional_objects_rather_than_exceed_the_tail():
 
     rec = json.loads(line)
     assert "roofline" in rec and "cpu_baseline" in rec and "train_steps_per_s" in rec
+
+
+def test_plain_run_line_carries_the_headline_alone():
+    """A plain ``bench.py --gpus 1 --steps K --warmup W`` prints the contract keys and nothing that ``--full`` adds."""
+    import argparse
+    import json
+
+    bench = _bench()
+    args = argparse.Namespace(steps=20, warmup=5, batch=16, frames=800)
+    head = bench.headline(args, 1, 1.25, 16 * 800 * 256)
+    rec = json.loads(bench.compact_line(head))
+    assert set(rec) == {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
+                        "scaling", "vs_baseline", "dtype", "data", "config"}
+    assert (rec["unit"], rec["higher_is_better"], rec["dtype"], rec["steps"]) == ("samples/s", True, "f32", 20)
+    assert rec["ms_per_step"] == 62.5
+    assert rec["value"] == round(16 * 800 * 256 * 20 / 1.25, 1)
+
+
+def test_dump_outputs_writes_float32_and_samples_beyond_the_budget(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+
+    bench = _bench()
+    y = torch.randn(2, 1, 3000, generator=torch.Generator().manual_seed(0), dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "all"), {"waveform": y})
+    a = np.load(tmp_path / "all" / "waveform.npy")
+    assert a.dtype == np.float32 and a.shape == (2, 1, 3000) and np.array_equal(a, y.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4000)  # 1000 of the 6000 elements
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), {"waveform": y})
+    s1, s2 = (np.load(tmp_path / d / "waveform_sample.npy") for d in ("s1", "s2"))
+    assert s1.dtype == np.float32 and s1.shape == (1000,) and np.array_equal(s1, s2)
+    assert np.isin(s1, y.float().numpy()).all() and not (tmp_path / "s1" / "waveform.npy").exists()

@@ -1,4 +1,6 @@
 """CPU: Collater crop algebra (the reference's test-free contract, bin/train.py:711-798)."""
+import os
+
 import numpy as np
 import torch
 
@@ -38,36 +40,55 @@ def test_collater_without_noise_and_length_fix():
     assert cb.shape == (1, 80, 10) and y.shape == (1, 1, 2560)
 
 
-def test_collater_matches_reference_collater():
-    """Same numpy seed -> the same batches as the reference's Collater (bin/train.py:646-896), for the
-    plain, the noise-input (PWG) and the f0/excitation (UHiFiGAN) variants.  Build container only."""
-    import pytest
+# (tag, Collater options, fields per item) of the reference comparison: plain, noise-input (PWG), f0/excitation (UHiFiGAN)
+REFERENCE_CASES = (("plain", dict(), 2), ("noise", dict(use_noise_input=True), 2), ("f0", dict(use_f0_and_excitation=True), 4))
+REFERENCE_HOP = 64
 
-    from oracle import ref_shim
 
-    if not ref_shim.available():
-        pytest.skip("/root/reference is not present")
-    ref_shim.install()
-    from parallel_wavegan.bin.train import Collater as RefCollater
-
+def reference_case_items():
     rng = np.random.default_rng(2)
-    hop = 64
     items = []
     for frames in (50, 33, 90, 41):
-        x, c = _utt(frames, hop, rng)
+        x, c = _utt(frames, REFERENCE_HOP, rng)
         f0 = rng.standard_normal(frames).astype(np.float32)
-        ex = rng.standard_normal((frames, hop)).astype(np.float32)
+        ex = rng.standard_normal((frames, REFERENCE_HOP)).astype(np.float32)
         items.append((x, c, f0, ex))
-    for kw, n in ((dict(), 2), (dict(use_noise_input=True), 2), (dict(use_f0_and_excitation=True), 4)):
-        args = dict(batch_max_steps=32 * hop, hop_size=hop, aux_context_window=2, **kw)
+    return items
+
+
+def reference_case_args(kw):
+    return dict(batch_max_steps=32 * REFERENCE_HOP, hop_size=REFERENCE_HOP, aux_context_window=2, **kw)
+
+
+def test_collater_matches_reference_collater(golden_dir):
+    """Same numpy seed -> the same batches as the reference's Collater (bin/train.py:646-896), for the
+    plain, the noise-input (PWG) and the f0/excitation (UHiFiGAN) variants: the reference's batches are stored in
+    tests/golden/collater.npz (tests/golden/make_golden.py), and where the reference itself is present it is run too."""
+    from oracle import ref_shim
+
+    stored = np.load(os.path.join(golden_dir, "collater.npz"))
+    ref_collater = None
+    if ref_shim.available():
+        ref_shim.install()
+        from parallel_wavegan.bin.train import Collater as ref_collater
+
+    items = reference_case_items()
+    for tag, kw, n in REFERENCE_CASES:
+        args = reference_case_args(kw)
         batch = [it[:n] for it in items]
         np.random.seed(5)
         torch.manual_seed(5)
-        want_in, want_y = RefCollater(**args)(batch)
-        np.random.seed(5)
-        torch.manual_seed(5)
         got_in, got_y = Collater(**args)(batch)
-        assert torch.equal(got_y, want_y)
-        assert len(got_in) == len(want_in)
+        want_in = [torch.from_numpy(stored[f"{tag}_in{i}"]) for i in range(sum(k.startswith(tag + "_in") for k in stored.files))]
+        assert torch.equal(got_y, torch.from_numpy(stored[f"{tag}_y"])), tag
+        assert len(got_in) == len(want_in), tag
         for a, b in zip(got_in, want_in):
-            assert a.shape == b.shape and torch.equal(a, b), kw
+            assert a.shape == b.shape and torch.equal(a, b), tag
+        if ref_collater is not None:
+            np.random.seed(5)
+            torch.manual_seed(5)
+            want_in, want_y = ref_collater(**args)(batch)
+            assert torch.equal(got_y, want_y)
+            assert len(got_in) == len(want_in)
+            for a, b in zip(got_in, want_in):
+                assert a.shape == b.shape and torch.equal(a, b), kw

@@ -112,7 +112,10 @@ def test_style_melgan_oracle_matches_reference_golden():
             sd = synth_for(StyleMelGANGenerator(**cfg), seed, 1.1)
             z = synth.synth_input("z", (2, cfg["in_channels"], 5), seed=seed)
             c = synth.synth_input("c", (2, 80, 20), seed=seed)
-            assert max_abs(torch_cpu.style_melgan_generator(sd, c, z, **cfg), gold[key]) < 1e-5, key
+            # in float64: the float32 golden is up to 6e-6 from the exact result by itself, and a float32 evaluation
+            # adds as much again that depends on the host CPU's kernels (1.2e-5 on some hosts)
+            sd = {k: v.double() for k, v in sd.items()}
+            assert max_abs(torch_cpu.style_melgan_generator(sd, c.double(), z.double(), **cfg), gold[key]) < 1e-5, key
         sd = synth_for(StyleMelGANGenerator(), seed + 1, 0.8)
         y = torch_cpu.style_melgan_generator(sd, synth.synth_input("c", (1, 80, 88), seed=seed + 1),
                                              synth.synth_input("z", (1, 128, 1), seed=seed + 1))

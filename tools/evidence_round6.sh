@@ -10,20 +10,20 @@ cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/prof_r06
 mkdir -p $O
-CMD_FULL="python $R/bench.py --steps 5 --warmup 2 --train-steps 8 --train-warmup 4 --no-cpu-baseline --no-graph --no-extra-configs"
-CMD_INF="python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-graph --no-train --no-latency --no-extra-configs"
+CMD_FULL="python $R/bench.py --full --steps 5 --warmup 2 --train-steps 8 --train-warmup 4 --no-cpu-baseline --no-graph --no-extra-configs"
+CMD_INF="python $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-graph --no-train --no-latency --no-extra-configs"
 PWG_BENCH_DETAIL=prof_r06_full_detail.json rocprofv3 --kernel-trace --stats -d $O/trace -o bench -- $CMD_FULL > $O/trace.log 2>&1
 python $R/tools/rocprof_summary.py $(ls $O/trace/*/*.db $O/trace/*.db 2>/dev/null | head -1) $O/bench_kernel_stats.csv \
-  "rocprofv3 --kernel-trace --stats -- python bench.py --steps 5 --warmup 2 --train-steps 8 --train-warmup 4 --no-cpu-baseline --no-graph --no-extra-configs (eager launches: every kernel its own dispatch; inference B16 x 800 frames: 2 warm-up + 5 timed + 3 event-profiled forwards + 2 latency shapes; C3 and C5 training: 4 warm-up + 8 timed + 1 event-profiled step each)"
+  "rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 5 --warmup 2 --train-steps 8 --train-warmup 4 --no-cpu-baseline --no-graph --no-extra-configs (eager launches: every kernel its own dispatch; inference B16 x 800 frames: 2 warm-up + 5 timed + 3 event-profiled forwards + 2 latency shapes; C3 and C5 training: 4 warm-up + 8 timed + 1 event-profiled step each)"
 PWG_BENCH_DETAIL=prof_r06_infer_detail.json rocprofv3 --kernel-trace --stats -d $O/trace_infer -o bench -- $CMD_INF > $O/trace_infer.log 2>&1
 python $R/tools/rocprof_summary.py $(ls $O/trace_infer/*/*.db $O/trace_infer/*.db 2>/dev/null | head -1) $O/infer_kernel_stats.csv \
-  "rocprofv3 --kernel-trace --stats -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-graph --no-train --no-latency --no-extra-configs (HiFi-GAN V1 inference B16 x 800 frames only: 2 warm-up + 5 timed + 3 event-profiled forwards = 10 x (47 conv + 15 residual-unit + 1 output) launches)"
+  "rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-graph --no-train --no-latency --no-extra-configs (HiFi-GAN V1 inference B16 x 800 frames only: 2 warm-up + 5 timed + 3 event-profiled forwards = 10 x (47 conv + 15 residual-unit + 1 output) launches)"
 cp $R/gpurun_out/prof_r06_infer_detail.json $O/infer_bench.json
 grep "^{\"metric\"" $O/trace_infer.log | tail -1 > $O/infer_bench_line.json
 if [ -z "$NO_PMC" ]; then
 for C in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --pmc $C --kernel-trace --output-format csv -d $O/calib_$C -o p -- $R/tools/probes/pmc_calib_dma.bin 1024 3 > $O/calib_$C.log 2>&1
-  PWG_BENCH_DETAIL=prof_r06_pmc_detail.json rocprofv3 --pmc $C --kernel-trace --output-format csv -d $O/bench_$C -o p -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-graph --no-train --no-latency --no-extra-configs > $O/bench_$C.log 2>&1
+  PWG_BENCH_DETAIL=prof_r06_pmc_detail.json rocprofv3 --pmc $C --kernel-trace --output-format csv -d $O/bench_$C -o p -- python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-graph --no-train --no-latency --no-extra-configs > $O/bench_$C.log 2>&1
 done
 python - <<PY
 import csv, glob, collections, json

@@ -9,8 +9,8 @@ head -40 $O/graph_timeline_c3.txt
 rm -rf $O/tl
 cd $R
 for rep in 1 2; do
-PWG_SPLIT_UNDERFILL=0 timeout 300 python bench.py --no-train --no-cpu-baseline --no-extra-configs --steps 5 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('old', d['lat_ms'], d['value'])" >> $O/lat.txt
-timeout 300 python bench.py --no-train --no-cpu-baseline --no-extra-configs --steps 5 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('new', d['lat_ms'], d['value'])" >> $O/lat.txt
+PWG_SPLIT_UNDERFILL=0 timeout 300 python bench.py --full --no-train --no-cpu-baseline --no-extra-configs --steps 5 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('old', d['lat_ms'], d['value'])" >> $O/lat.txt
+timeout 300 python bench.py --full --no-train --no-cpu-baseline --no-extra-configs --steps 5 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('new', d['lat_ms'], d['value'])" >> $O/lat.txt
 done
 cat $O/lat.txt
 timeout 900 python -m pytest tests/test_hifigan_gpu.py tests/test_conv_ops_gpu.py tests/test_streaming_gpu.py tests/test_graphed_inference_gpu.py -q 2>&1 | tail -3

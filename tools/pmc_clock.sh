@@ -4,7 +4,7 @@
 # rocprofv3 --pmc with --kernel-trace only.  Result: gpurun_out/pmc_clock/clock.json (+ printed table).
 cd /tmp && export TMPDIR=/tmp
 R=/root/repo; O=$R/gpurun_out/pmc_clock; mkdir -p $O
-rocprofv3 --pmc GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O/infer -o p -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-graph --no-train --no-latency --no-extra-configs > $O/infer.log 2>&1
+rocprofv3 --pmc GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O/infer -o p -- python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-graph --no-train --no-latency --no-extra-configs > $O/infer.log 2>&1
 for T in c3 c2; do
   PWG_NO_GRAPH=1 PWG_NO_BRANCH=1 PWG_WAVENET_WGRAD_STREAM=0 rocprofv3 --pmc GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O/$T -o p -- python $R/tools/train_replay.py $T 5 > $O/$T.log 2>&1
 done

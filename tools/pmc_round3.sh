@@ -12,7 +12,7 @@ for C in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --pmc $C --kernel-trace --output-format csv -d $O/calib_$C -o p -- $R/tools/probes/pmc_calib_dma.bin 1024 3 > $O/calib_$C.log 2>&1
   rocprofv3 --pmc $C --kernel-trace --output-format csv -d $O/wn0_$C -o p -- python $R/tools/one_wavenet.py 16 102400 16 0 4 > $O/wn0_$C.log 2>&1
   rocprofv3 --pmc $C --kernel-trace --output-format csv -d $O/wn1_$C -o p -- python $R/tools/one_wavenet.py 6 25600 16 1 6 > $O/wn1_$C.log 2>&1
-  rocprofv3 --pmc $C --kernel-trace --output-format csv -d $O/bench_$C -o p -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-graph --no-train --no-latency --no-extra-configs > $O/bench_$C.log 2>&1
+  rocprofv3 --pmc $C --kernel-trace --output-format csv -d $O/bench_$C -o p -- python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-graph --no-train --no-latency --no-extra-configs > $O/bench_$C.log 2>&1
 done
 python - <<PY
 import csv, glob, collections, json

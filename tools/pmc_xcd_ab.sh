@@ -4,7 +4,7 @@
 cd /tmp && export TMPDIR=/tmp
 R=/root/repo; O=$R/gpurun_out/pmc_xcd; mkdir -p $O
 for MODE in 0 16; do
-  PWG_DBG=$MODE rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/fetch_$MODE -o p -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-graph --no-train --no-latency --no-extra-configs > $O/fetch_$MODE.log 2>&1
+  PWG_DBG=$MODE rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/fetch_$MODE -o p -- python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-graph --no-train --no-latency --no-extra-configs > $O/fetch_$MODE.log 2>&1
 done
 python - <<PY
 import csv, glob, collections, json

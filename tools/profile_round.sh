@@ -7,18 +7,18 @@ R=/root/repo
 O=$R/gpurun_out/prof_$TAG
 mkdir -p $O
 if [ -z "$PMC_ONLY" ]; then
-rocprofv3 --kernel-trace --stats -d $O/trace -o bench -- python $R/bench.py --steps 5 --warmup 2 --train-steps 8 --train-warmup 4 --no-cpu-baseline --no-graph --no-extra-configs > $O/trace.log 2>&1
+rocprofv3 --kernel-trace --stats -d $O/trace -o bench -- python $R/bench.py --full --steps 5 --warmup 2 --train-steps 8 --train-warmup 4 --no-cpu-baseline --no-graph --no-extra-configs > $O/trace.log 2>&1
 fi
-[ -z "$PMC_ONLY" ] && python $R/tools/rocprof_summary.py $(ls $O/trace/*.db | head -1) $O/kernel_stats.csv "rocprofv3 --kernel-trace --stats -- python bench.py --steps 5 --warmup 2 --train-steps 8 --train-warmup 4 --no-cpu-baseline --no-graph --no-extra-configs (eager launches so that every kernel is a separate dispatch; inference B=16x800 frames: 2 warm-up + 5 timed + 3 event-profiled + 2 latency shapes; training B=16x8192: 4 warm-up + 8 timed + 1 event-profiled steps)"
+[ -z "$PMC_ONLY" ] && python $R/tools/rocprof_summary.py $(ls $O/trace/*.db | head -1) $O/kernel_stats.csv "rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 5 --warmup 2 --train-steps 8 --train-warmup 4 --no-cpu-baseline --no-graph --no-extra-configs (eager launches so that every kernel is a separate dispatch; inference B=16x800 frames: 2 warm-up + 5 timed + 3 event-profiled + 2 latency shapes; training B=16x8192: 4 warm-up + 8 timed + 1 event-profiled steps)"
 if [ -z "$PMC_ONLY" ]; then
 # inference-only trace: the conv family's average launch duration here is the one bench.py's `roofline`
 # object must agree with (same workload, eager launches = one dispatch per kernel)
-rocprofv3 --kernel-trace --stats -d $O/trace_infer -o bench -- python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-graph --no-train --no-latency --no-extra-configs > $O/trace_infer.log 2>&1
-python $R/tools/rocprof_summary.py $(ls $O/trace_infer/*.db | head -1) $O/infer_kernel_stats.csv "rocprofv3 --kernel-trace --stats -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-graph --no-train --no-latency (HiFi-GAN V1 inference B=16x800 frames only: 2 warm-up + 5 timed + 3 event-profiled forwards = 10 x 78 conv launches)"
+rocprofv3 --kernel-trace --stats -d $O/trace_infer -o bench -- python $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-graph --no-train --no-latency --no-extra-configs > $O/trace_infer.log 2>&1
+python $R/tools/rocprof_summary.py $(ls $O/trace_infer/*.db | head -1) $O/infer_kernel_stats.csv "rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-graph --no-train --no-latency (HiFi-GAN V1 inference B=16x800 frames only: 2 warm-up + 5 timed + 3 event-profiled forwards = 10 x 78 conv launches)"
 grep "^{\"metric\"" $O/trace_infer.log | tail -1 > $O/infer_bench.json
 fi
 for C in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $C --kernel-trace --output-format csv -d $O/pmc_$C -o p -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-graph --no-train --no-latency --no-extra-configs > $O/pmc_$C.log 2>&1
+  rocprofv3 --pmc $C --kernel-trace --output-format csv -d $O/pmc_$C -o p -- python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-graph --no-train --no-latency --no-extra-configs > $O/pmc_$C.log 2>&1
 done
 python - <<PY
 import csv, glob, collections, json
@@ -41,7 +41,7 @@ PY
 if [ -n "$TRAIN_PMC" ]; then
 for PASS in "FETCH_SIZE" "WRITE_SIZE" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY"; do
   TAGP=$(echo $PASS | cut -d" " -f1)
-  rocprofv3 --pmc $PASS --kernel-trace --output-format csv -d $O/train_pmc_$TAGP -o p -- python $R/bench.py --steps 1 --warmup 1 --train-steps 2 --train-warmup 2 --no-cpu-baseline --no-graph --no-latency --no-extra-configs > $O/train_pmc_$TAGP.log 2>&1
+  rocprofv3 --pmc $PASS --kernel-trace --output-format csv -d $O/train_pmc_$TAGP -o p -- python $R/bench.py --full --steps 1 --warmup 1 --train-steps 2 --train-warmup 2 --no-cpu-baseline --no-graph --no-latency --no-extra-configs > $O/train_pmc_$TAGP.log 2>&1
 done
 python - <<PY
 import csv, glob, collections, json
