@@ -209,6 +209,30 @@ int pwg_conv1d_forward_cfg(const pwg_conv1d_desc* d, const float* x, const float
                            const float* bias, const float* add1, const float* add2, float* y,
                            int32_t tile_config, int32_t use_dma, void* stream);
 
+/* ---- bf16-operand inference (opt-in; csrc/conv1d_bf16.hip) ----
+ * The same fused convolution at the same call sites as pwg_conv1d_forward (layers/residual_block.py:190-196,213-220,
+ * models/hifigan.py:75-81,99-107,143-149: F.conv1d / F.conv_transpose1d under torch.no_grad(), bin/decode.py:158-169),
+ * with bf16 OPERANDS on the gfx950 bf16 MFMA instructions.  Numerical definition:
+ *   1. pre_act is applied to the fp32 input in fp32;  2. the activated input is rounded to bf16 (nearest-even);
+ *   3. the effective fp32 weight (w * scale) is rounded to bf16 once, by the packer;  4. products are accumulated in fp32;
+ *   5. bias, add1, add2, out_mul, out_div, post_act and the stored result are fp32.
+ * Tensors stay fp32 in memory.  Covered: groups == 1, width == 1, zero padding, and either stride-1 Conv1d (any kernel /
+ * dilation whose window fits LDS) or ConvTranspose1d with kernel == 2 * stride; pwg_conv1d_bf16_supported is pure host
+ * logic (no device needed; pwg_last_error names the reason for 0).  Deterministic (no split reduction, no atomics).
+ * Inference only: there is no backward.  `scale` as for pwg_conv1d_pack_weight; the image is
+ * pwg_conv1d_bf16_packed_weight_bytes bytes (0 = unsupported), 16-B aligned.  pwg_conv1d_bf16_forward takes the arguments
+ * of pwg_conv1d_forward in the same order (the workspace is never used and may be NULL / 0).
+ * pwg_conv1d_bf16_forward_cfg (tuning): mfma_shape 32 = 32x32x16, 16 = 16x16x32 at the same output tile.              */
+int pwg_conv1d_bf16_supported(const pwg_conv1d_desc* d);
+size_t pwg_conv1d_bf16_packed_weight_bytes(const pwg_conv1d_desc* d);
+int pwg_conv1d_bf16_pack_weight(const pwg_conv1d_desc* d, const float* w, const float* scale, void* w_packed,
+                                void* stream);
+int pwg_conv1d_bf16_forward(const pwg_conv1d_desc* d, const float* x, const void* w_packed, const float* bias,
+                            const float* add1, const float* add2, float* y, float* workspace, size_t workspace_floats,
+                            void* stream);
+int pwg_conv1d_bf16_forward_cfg(const pwg_conv1d_desc* d, const float* x, const void* w_packed, const float* bias,
+                                const float* add1, const float* add2, float* y, int32_t mfma_shape, void* stream);
+
 /* Diagnostics (host only, no launch, no device needed): the plan pwg_conv1d_forward derives for a descriptor.
  * has_addends: 1 if add1 / add2 will be passed.  out[8]:
  *   out[0] kernel family: 0 = MFMA implicit-GEMM kernel, 1 = grouped 16x16x4 kernel, 2 = single-input-channel

@@ -106,12 +106,13 @@ class PreparedWeights:
     keeps one instance per parameter epoch, so every forward / backward of that epoch -- e.g. D(y) and
     D(G(c)) of a discriminator phase -- shares a single scale + pack + pack launch sequence."""
 
-    __slots__ = ("key", "w", "_scale", "_fwd", "_fwd_desc", "_bwd", "_res", "_stale")
+    __slots__ = ("key", "w", "_scale", "_fwd", "_fwd_desc", "_bwd", "_res", "_bf16", "_stale")
 
     def __init__(self, key, w, scale, fwd=None, fwd_desc=None):
         """``fwd``: the packed forward image, or None with ``fwd_desc`` (any descriptor of the layer) to build it
         on first use -- layers that only run inside a fused multi-layer kernel never need it."""
         self.key, self.w, self._scale, self._fwd, self._fwd_desc, self._bwd, self._res = key, w, scale, fwd, fwd_desc, None, None
+        self._bf16 = None
         self._stale = False  # set by weight_bank.WeightBank when it overwrites the (shared, persistent) images
 
     @property
@@ -141,6 +142,15 @@ class PreparedWeights:
             with torch.no_grad():
                 self._res = ops.resunit_pack_weight(self.w, self._scale)
         return self._res
+
+    def bf16(self):
+        """bf16 MFMA weight image of the opt-in bf16-operand inference mode (csrc/conv1d_bf16.hip), built on first use;
+        it lives and dies with this instance, i.e. with the parameter state the fp32 image is keyed on."""
+        self._check()
+        if self._bf16 is None:
+            with torch.no_grad():
+                self._bf16 = ops.pack_weight_bf16(self._fwd_desc, self.w, self._scale)
+        return self._bf16
 
     def bwd(self, desc):
         self._check()

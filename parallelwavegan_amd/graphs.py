@@ -15,8 +15,9 @@ class GraphedInference:
     The capture records the kernels that read the packed weight images of that moment.  Every call first compares the
     model's *parameter state* -- storage address, torch version counter and the engine's own epoch of every parameter
     and buffer (``ops.param_epoch``: the fused optimizers update through raw pointers), plus the global weight-cache
-    epoch -- with the state at capture time; after ``load_state_dict``, an optimizer step, ``remove_weight_norm`` ...
-    the stale graphs are dropped and the call captures again, so a replay can never synthesise with old weights
+    epoch and every convolution's inference precision -- with the state at capture time; after ``load_state_dict``, an
+    optimizer step, ``remove_weight_norm``, ``set_inference_precision`` ... the stale graphs are dropped and the call
+    captures again, so a replay can never synthesise with old weights
     (VERDICT r04).  :meth:`reset` does the same by hand."""
 
     def __init__(self, model, warmup=2, frozen=False):
@@ -27,11 +28,13 @@ class GraphedInference:
         self.frozen = frozen
         self._graphs = {}
         self._state = None
+        self._convs = None
 
     def reset(self):
         """Drop the captured graphs (parameters changed)."""
         self._graphs = {}
         self._state = None
+        self._convs = None
 
     def _param_state(self):
         from . import ops
@@ -46,6 +49,13 @@ class GraphedInference:
             st.append((t.data_ptr(), ops.tensor_version(t), ops.param_epoch(t)))
         for t in model.buffers():
             st.append((t.data_ptr(), ops.tensor_version(t)))
+        # the inference precision of every convolution: switching it (utils.set_inference_precision) drops the graphs
+        # (the list of convolution modules is taken once: walking the module tree costs as much as the tensors above)
+        if self._convs is None:
+            from .layers.conv import _ConvNd
+
+            self._convs = [m for m in model.modules() if isinstance(m, _ConvNd)]
+        st.append(tuple(m.precision for m in self._convs))
         return st
 
     def _capture(self, inputs):

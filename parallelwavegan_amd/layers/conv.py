@@ -31,6 +31,10 @@ class _ConvNd(torch.nn.Module):
     fold_batch = {"0": False, "1": True}.get(os.environ.get("PWG_FOLD_BATCH", ""), True)
     fold_max_cols = int(os.environ.get("PWG_FOLD_MAX_COLS", 40))  # output columns per item up to which a layer is folded
     fold_min_weight_bytes = 4 << 20  # ... if its weight is at least this large (the launch streams it once per item)
+    # Inference precision of this module: "fp32" (default) or "bf16" -- bf16 OPERANDS on the bf16 MFMA kernel
+    # (csrc/conv1d_bf16.hip), fp32 accumulation, epilogue and tensors; inference only.  Set through
+    # utils.set_inference_precision; a layer the bf16 kernel does not cover stays on the fp32 kernels.
+    precision = "fp32"
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1,
                  bias=True, output_padding=0, pad_mode="zero"):
@@ -204,6 +208,17 @@ class _ConvNd(torch.nn.Module):
             return ops.pack_weight(self.make_desc(1, self._probe_len()), self._w3(self.effective_weight()))
         return self.prepared().fwd
 
+    def packed_weight_bf16(self):
+        """Cached bf16 weight image (bf16-operand inference); keyed like the fp32 image, so ``load_state_dict``, optimizer
+        steps and ``remove_weight_norm`` invalidate both together."""
+        if self.has_spectral_norm and self.training:
+            return ops.pack_weight_bf16(self.make_desc(1, self._probe_len()), self._w3(self.effective_weight()))
+        return self.prepared().bf16()
+
+    def bf16_capable(self):
+        """Does the bf16-operand kernel cover this layer's geometry (host logic, no device needed)?"""
+        return not self.width_mode and ops.conv1d_bf16_supported(self.make_desc(1, self._probe_len()))
+
     @staticmethod
     def _w3(w):
         return w.reshape(w.shape[0], w.shape[1], -1).contiguous()
@@ -265,6 +280,11 @@ class _ConvNd(torch.nn.Module):
         fused = dict(pre_act=pre_act, pre_slope=pre_slope, post_act=post_act, post_slope=post_slope,
                      out_mul=out_mul, out_div=out_div)
         width_mode = self.width_mode or folded > 0
+        if self.precision == "bf16" and self._needs_grad(x, add1, add2):
+            raise RuntimeError(
+                f"{self.__class__.__name__} is in bf16 inference precision, which has no backward pass: run it under "
+                "torch.no_grad() (HiFiGANGenerator.inference(..., precision='bf16') does), or switch back with "
+                "utils.set_inference_precision(model, 'fp32') before training")
         if self._needs_grad(x, add1, add2):
             geom = self.geom()
             if width_mode:
@@ -307,6 +327,9 @@ class _ConvNd(torch.nn.Module):
                 return ops.conv1d_forward(desc, xp, self.packed_weight(),
                                           None if self.bias is None else self.bias.detach(), add1, add2)
             desc = self.make_desc(b, x.shape[-1], **fused)
+            if self.precision == "bf16" and ops.conv1d_bf16_supported(desc):
+                return ops.conv1d_forward_bf16(desc, x.contiguous(), self.packed_weight_bf16(),
+                                               None if self.bias is None else self.bias.detach(), add1, add2)
             return ops.conv1d_forward(desc, x.contiguous(), self.packed_weight(),
                                       None if self.bias is None else self.bias.detach(), add1, add2)
 

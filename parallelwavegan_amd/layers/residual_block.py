@@ -204,6 +204,8 @@ class HiFiGANResidualBlock(torch.nn.Module):
             slope2 = act2.slope
         if conv1.has_spectral_norm or conv1.pad_mode != "zero":
             return None
+        if conv1.precision != "fp32" or (conv2 is not None and conv2.precision != "fp32"):
+            return None  # bf16-operand inference: the unit's convolutions run one by one on csrc/conv1d_bf16.hip
         desc = ops.make_resunit_desc(x.shape[0], x.shape[1], x.shape[2], self.kernel_size, conv1.dilation,
                                      conv2 is not None, act1.slope, slope2, out_div)
         if not ops.resunit_profitable(desc):

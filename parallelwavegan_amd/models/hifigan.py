@@ -4,6 +4,7 @@ Drop-in for ``parallel_wavegan.models.hifigan`` (constructor kwargs, method
 names and state-dict keys follow /root/reference/parallel_wavegan/models/hifigan.py);
 the arithmetic is hand-written HIP behind ``parallelwavegan_amd.ops``.
 """
+import contextlib
 import copy
 import logging
 
@@ -158,13 +159,29 @@ class HiFiGANGenerator(torch.nn.Module):
         self.register_buffer("scale", torch.from_numpy(scale).float())
         logging.info("Successfully registered stats as buffer.")
 
-    def inference(self, c, normalize_before=False):
-        """c: (T, in_channels) tensor/ndarray -> (T * prod(upsample_scales), out_channels)."""
+    def inference(self, c, normalize_before=False, precision=None):
+        """c: (T, in_channels) tensor/ndarray -> (T * prod(upsample_scales), out_channels).
+
+        ``precision``: None = whatever ``utils.set_inference_precision`` set on the model (default fp32); ``"bf16"`` /
+        ``"fp32"`` = this call only (the modules' settings are restored afterwards).  A bf16 call runs under
+        ``torch.no_grad()``: the mode has no backward pass."""
+        if precision is not None:
+            from ..utils.precision import set_inference_precision
+
+            saved = [(m, m.precision) for m in _each_conv(self)]
+            set_inference_precision(self, precision)
+            try:
+                return self.inference(c, normalize_before)
+            finally:
+                for m, p in saved:
+                    m.precision = p
         if not isinstance(c, torch.Tensor):
             c = torch.tensor(c, dtype=torch.float).to(next(self.parameters()).device)
         if normalize_before:
             c = (c - self.mean) / self.scale
-        c = self.forward(c.transpose(1, 0).unsqueeze(0).contiguous())
+        bf16 = any(m.precision == "bf16" for m in _each_conv(self))
+        with torch.no_grad() if bf16 else contextlib.nullcontext():
+            c = self.forward(c.transpose(1, 0).unsqueeze(0).contiguous())
         return c.squeeze(0).transpose(1, 0)
 
 

@@ -194,6 +194,47 @@ def conv1d_forward(desc, x, w_packed, bias=None, add1=None, add2=None, out=None)
     return out
 
 
+def conv1d_bf16_supported(desc):
+    """Does the bf16-operand inference kernel (csrc/conv1d_bf16.hip) cover this descriptor?  Host logic only (no
+    device needed); ``_lib.lib().pwg_last_error()`` names the reason for a False."""
+    return bool(_lib.lib().pwg_conv1d_bf16_supported(ctypes.byref(desc)))
+
+
+def pack_weight_bf16(desc, w, scale=None):
+    """torch-layout fp32 weight (+ optional weight_norm row scale) -> bf16 MFMA weight image (an opaque byte tensor);
+    the effective weight ``w * scale`` is rounded to bf16 here, once."""
+    _require_device(w, scale)
+    n = _lib.lib().pwg_conv1d_bf16_packed_weight_bytes(ctypes.byref(desc))
+    if n == 0:
+        _lib.check(-1, "conv1d_bf16_packed_weight_bytes")
+    out = torch.empty(n, device=w.device, dtype=torch.uint8)
+    _lib.check(_lib.lib().pwg_conv1d_bf16_pack_weight(ctypes.byref(desc), _ptr(w), _ptr(scale), _ptr(out), _stream()),
+               "conv1d_bf16_pack_weight")
+    return out
+
+
+def conv1d_forward_bf16(desc, x, w_packed, bias=None, add1=None, add2=None, out=None, mfma_shape=None):
+    """Fused convolution with bf16 operands and fp32 accumulation / epilogue (inference only).  ``mfma_shape``
+    (tuning): 32 or 16 selects the MFMA instruction explicitly."""
+    _require_device(x, bias, add1, add2, out)
+    if not w_packed.is_cuda or w_packed.dtype != torch.uint8:
+        raise RuntimeError("conv1d_forward_bf16: w_packed must be the device image of pack_weight_bf16")
+    if out is None:
+        out = torch.empty((desc.batch, desc.c_out, desc.t_out), device=x.device, dtype=torch.float32)
+    assert x.numel() == desc.batch * desc.c_in * desc.t_in, (tuple(x.shape), desc.batch, desc.c_in, desc.t_in)
+    assert out.numel() == desc.batch * desc.c_out * desc.t_out
+    for t in (add1, add2):
+        assert t is None or t.numel() == out.numel()
+    if mfma_shape is None:
+        rc = _lib.lib().pwg_conv1d_bf16_forward(ctypes.byref(desc), _ptr(x), _ptr(w_packed), _ptr(bias), _ptr(add1),
+                                                _ptr(add2), _ptr(out), None, 0, _stream())
+    else:
+        rc = _lib.lib().pwg_conv1d_bf16_forward_cfg(ctypes.byref(desc), _ptr(x), _ptr(w_packed), _ptr(bias), _ptr(add1),
+                                                    _ptr(add2), _ptr(out), int(mfma_shape), _stream())
+    _lib.check(rc, "conv1d_forward_bf16")
+    return out
+
+
 def make_resunit_desc(batch, channels, t, kernel, dilation, has_conv2=True, slope1=0.1, slope2=0.1, out_div=1.0):
     return ResUnitDesc(int(batch), int(channels), int(t), int(kernel), int(dilation), int(bool(has_conv2)),
                        float(slope1), float(slope2), float(out_div))

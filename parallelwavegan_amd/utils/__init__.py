@@ -1,1 +1,2 @@
 from .utils import *  # noqa: F401,F403
+from .precision import get_inference_precision, set_inference_precision  # noqa: E402,F401

@@ -1,0 +1,28 @@
+"""Opt-in reduced-precision inference: bf16 operands, fp32 accumulation, fp32 tensors (csrc/conv1d_bf16.hip)."""
+from ..layers.conv import _ConvNd
+
+PRECISIONS = ("fp32", "bf16")
+
+
+def set_inference_precision(model, precision):
+    """Switch every convolution of ``model`` to ``"bf16"`` (bf16-operand MFMA kernel, inference only) or back to
+    ``"fp32"`` (the default).  Module tree, tensor dtypes, state dicts and checkpoints do not change: the mode is an
+    attribute of the convolution modules.  A convolution the bf16 kernel does not cover (grouped, (k, 1) Conv2d,
+    reflect padding, strided) stays at ``"fp32"``.  Returns how many convolutions took the requested mode."""
+    if precision not in PRECISIONS:
+        raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
+    n = 0
+    for m in model.modules():
+        if not isinstance(m, _ConvNd):
+            continue
+        if precision == "bf16" and not m.bf16_capable():
+            m.precision = "fp32"
+            continue
+        m.precision = precision
+        n += 1
+    return n
+
+
+def get_inference_precision(model):
+    """``"bf16"`` if any convolution of ``model`` is in bf16 mode, else ``"fp32"``."""
+    return "bf16" if any(isinstance(m, _ConvNd) and m.precision == "bf16" for m in model.modules()) else "fp32"
