@@ -348,6 +348,33 @@ int pwg_wavenet_pack_weights(const pwg_wavenet_desc* d, const float* w_dil, cons
 int pwg_wavenet_layer_forward(const pwg_wavenet_desc* d, const float* x, const float* c, const float* skips,
                               const float* packed, const float* b_dil, const float* b_skip, const float* b_out,
                               float* x_out, float* skips_out, float* z_out, float* g_out, void* stream);
+/* ---- bf16-operand inference form of the same layer (opt-in; csrc/wavenet_bf16.hip) ----
+ * The definition of the bf16-operand convolution (pwg_conv1d_bf16_*, above) applied to each of the layer's four
+ * convolutions, in ONE launch:
+ *   z         = W_dil (*) bf16(x) + W_aux . bf16(c) + b_dil      (products accumulated in fp32 on the bf16 MFMA)
+ *   g         = bf16(tanh(z[:64]) * sigmoid(z[64:]))              (gate in fp32, then rounded to nearest-even)
+ *   skips_out = (W_skip . g + b_skip + skips) * skip_mul;   x_out = (W_out . g + b_out + x) * out_mul
+ * where W_* are the effective weights (w * scale) rounded to bf16 once, by pwg_wavenet_bf16_pack_weights, and the bias,
+ * the residual x (read in fp32, not from the rounded operand), the running skip sum and every tensor in memory are
+ * fp32.  Geometry: that of pwg_wavenet_layer_supported (PWG.v1 channels, kernel 3, non-causal, any dilation, any t >= 1,
+ * batch 1 .. 65535); pwg_wavenet_bf16_supported is pure host logic (no device needed; pwg_last_error names the reason
+ * for 0).  The image is pwg_wavenet_bf16_packed_weight_bytes bytes (0 = unsupported), 16-B aligned.
+ * pwg_wavenet_bf16_layer_forward takes the arguments of pwg_wavenet_layer_forward in the same order; z_out / g_out
+ * (both or neither, NULL in normal use) receive the fp32 z and the bf16-rounded g (stored as fp32) for stage tests.
+ * x, c 4-B aligned.  Deterministic (no split reduction, no atomics).  Inference only: there is no backward.
+ * pwg_wavenet_bf16_layer_forward_cfg (tuning): mfma_shape 32 = 32x32x16, 16 = 16x16x32 at the same tiles.       */
+int pwg_wavenet_bf16_supported(const pwg_wavenet_desc* d);
+size_t pwg_wavenet_bf16_packed_weight_bytes(const pwg_wavenet_desc* d);
+int pwg_wavenet_bf16_pack_weights(const pwg_wavenet_desc* d, const float* w_dil, const float* scale_dil,
+                                  const float* w_aux, const float* scale_aux, const float* w_skip, const float* scale_skip,
+                                  const float* w_out, const float* scale_out, void* packed, void* stream);
+int pwg_wavenet_bf16_layer_forward(const pwg_wavenet_desc* d, const float* x, const float* c, const float* skips,
+                                   const void* packed, const float* b_dil, const float* b_skip, const float* b_out,
+                                   float* x_out, float* skips_out, float* z_out, float* g_out, void* stream);
+int pwg_wavenet_bf16_layer_forward_cfg(const pwg_wavenet_desc* d, const float* x, const float* c, const float* skips,
+                                       const void* packed, const float* b_dil, const float* b_skip, const float* b_out,
+                                       float* x_out, float* skips_out, float* z_out, float* g_out, int32_t mfma_shape,
+                                       void* stream);
 /* Data path of the layer's backward pass in two launches (the weight gradients use pwg_conv1d_backward_weight*):
  *   gate_backward: dz (batch, 128, t) = d loss / d z from dx_out, ds_out (gradients w.r.t. x_out / skips_out; dx_out
  *     may be NULL) and the saved z -- the two 1x1 data gradients (K = 128), the out_mul / skip_mul scales and the

@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("PWG_KERNEL_LIB") or os.path.join(_HERE, "libpwgkernel
 
 PWG_ACT_NONE, PWG_ACT_LEAKY_RELU, PWG_ACT_TANH, PWG_ACT_RELU = 0, 1, 2, 3
 PWG_PAD_ZERO, PWG_PAD_REFLECT, PWG_PAD_REPLICATE = 0, 1, 2
-ABI_VERSION = 12
+ABI_VERSION = 13
 SPECTRAL_NORM_SCRATCH_FLOATS = 257  # PWG_SPECTRAL_NORM_SCRATCH_FLOATS (include/pwg_kernels.h)
 
 
@@ -172,6 +172,11 @@ SIGNATURES = {
     "pwg_wavenet_packed_weight_floats": (ctypes.c_size_t, [ctypes.POINTER(WaveNetDesc)]),
     "pwg_wavenet_pack_weights": (ctypes.c_int, [ctypes.POINTER(WaveNetDesc)] + [_vp] * 10),
     "pwg_wavenet_layer_forward": (ctypes.c_int, [ctypes.POINTER(WaveNetDesc)] + [_vp] * 12),
+    "pwg_wavenet_bf16_supported": (ctypes.c_int, [ctypes.POINTER(WaveNetDesc)]),
+    "pwg_wavenet_bf16_packed_weight_bytes": (ctypes.c_size_t, [ctypes.POINTER(WaveNetDesc)]),
+    "pwg_wavenet_bf16_pack_weights": (ctypes.c_int, [ctypes.POINTER(WaveNetDesc)] + [_vp] * 10),
+    "pwg_wavenet_bf16_layer_forward": (ctypes.c_int, [ctypes.POINTER(WaveNetDesc)] + [_vp] * 12),
+    "pwg_wavenet_bf16_layer_forward_cfg": (ctypes.c_int, [ctypes.POINTER(WaveNetDesc)] + [_vp] * 11 + [_i32, _vp]),
     "pwg_wavenet_packed_weight_bwd_floats": (ctypes.c_size_t, [ctypes.POINTER(WaveNetDesc)]),
     "pwg_wavenet_pack_weights_bwd": (ctypes.c_int, [ctypes.POINTER(WaveNetDesc)] + [_vp] * 10),
     "pwg_wavenet_gate_backward": (ctypes.c_int, [ctypes.POINTER(WaveNetDesc)] + [_vp] * 7),

@@ -3,6 +3,7 @@ import math
 
 import torch
 
+from .. import _lib
 from .. import functional as Fn
 from .. import ops
 from .activation import FusedActivation
@@ -119,13 +120,94 @@ class WaveNetResidualBlock(torch.nn.Module):
             return False
         return ops.wavenet_layer_supported(self.fused_desc(x.shape[0], x.shape[2]))
 
+    # ---- bf16-operand inference (csrc/wavenet_bf16.hip): the whole layer in one launch, any dilation
+    def _bf16_geometry_reason(self, batch=1, t=1):
+        """None if the fused bf16 layer covers this block at (batch, t), else the reason it does not."""
+        if self.conv1x1_aux is None:
+            return "the block has no aux (conditioning) convolution"
+        if self.use_causal_conv:
+            return "causal layers are not built"
+        if any(cv.has_spectral_norm or cv.pad_mode != "zero" for cv in self.fused_convs()):
+            return "spectral norm or non-zero padding"
+        if self.conv1x1_out.out_channels != self.conv.in_channels:
+            return "out channels differ from the residual channels"
+        if not ops.wavenet_bf16_supported(self.fused_desc(batch, t)):
+            return _lib.lib().pwg_last_error().decode(errors="replace")
+        return None
+
+    def bf16_covered_convs(self):
+        """Convolutions that the fused bf16 layer runs in bf16 although the stand-alone bf16 kernel may not cover them
+        (the dilation-512 dilated convolution): all four when the layer geometry is covered, else none.  Asked by
+        ``utils.set_inference_precision``; host logic only."""
+        return tuple(self.fused_convs()) if self._bf16_geometry_reason() is None else ()
+
+    def fused_image_bf16(self):
+        """bf16 MFMA image of the layer's four weights; keyed like ``fused_image`` (``load_state_dict``, optimizer steps
+        and ``remove_weight_norm`` invalidate both together)."""
+        convs = self.fused_convs()
+        key = tuple(cv._params_key() for cv in convs)
+        if getattr(self, "_fused_bf16_key", None) != key:
+            hs = [cv.prepared() for cv in convs]
+            with torch.no_grad():
+                self._fused_bf16_img = ops.wavenet_bf16_pack_weights(self.fused_desc(1, 64), hs[0].w, hs[0].scale,
+                                                                     hs[1].w, hs[1].scale, hs[2].w, hs[2].scale,
+                                                                     hs[3].w, hs[3].scale)
+            self._fused_bf16_key = key
+        return self._fused_bf16_img
+
+    def _forward_bf16(self, x, c, skips, skip_scale, chain_aux, inplace_skips):
+        """Some convolution of the block is in bf16 mode: the fused bf16 launch when all four are and it covers the
+        call, else the per-convolution path -- where every bf16 convolution must run in bf16 on its own kernel."""
+        convs = [cv for cv in self.fused_convs() if cv is not None]
+        if torch.is_grad_enabled() and (x.requires_grad or (c is not None and c.requires_grad)
+                                        or (skips is not None and skips.requires_grad)
+                                        or any(p.requires_grad for cv in convs for p in cv.parameters())):
+            raise RuntimeError(
+                f"{self.__class__.__name__} is in bf16 inference precision, which has no backward pass: run it under "
+                "torch.no_grad() (ParallelWaveGANGenerator.inference(..., precision='bf16') does), or switch back with "
+                "utils.set_inference_precision(model, 'fp32') before training")
+        all_bf16 = all(cv.precision == "bf16" for cv in convs)
+        reason = None
+        if not all_bf16:
+            reason = "its convolutions are in mixed precision"
+        elif c is None:
+            reason = "no aux input"
+        elif x.dim() != 3 or not x.is_cuda:
+            reason = "the input is not a (B, C, T) device tensor"
+        elif self.dropout > 0.0 and self.training:
+            reason = "dropout in training mode"
+        else:
+            reason = self._bf16_geometry_reason(x.shape[0], x.shape[2])
+        if reason is None:
+            with torch.no_grad():
+                b_d, b_s, b_o = (None if cv.bias is None else cv.bias.detach()
+                                 for cv in (self.conv, self.conv1x1_skip, self.conv1x1_out))
+                x_out, s_out, _, _ = ops.wavenet_bf16_layer_forward(
+                    self.fused_desc(x.shape[0], x.shape[2], skip_scale), x.contiguous(), c.contiguous(), skips,
+                    self.fused_image_bf16(), b_d, b_s, b_o, skips_out=skips if inplace_skips else None)
+            return (x_out, s_out, c) if chain_aux else (x_out, s_out)
+        # per-convolution path: a bf16 convolution the stand-alone kernel cannot take is an error, not an fp32 run
+        t = x.shape[-1]
+        for name, cv in (("conv", self.conv), ("conv1x1_aux", self.conv1x1_aux), ("conv1x1_skip", self.conv1x1_skip),
+                         ("conv1x1_out", self.conv1x1_out)):
+            if cv is not None and cv.precision == "bf16" and not ops.conv1d_bf16_supported(cv.make_desc(x.shape[0], t)):
+                why = _lib.lib().pwg_last_error().decode(errors="replace")
+                raise RuntimeError(f"{self.__class__.__name__}: {name} is in bf16 inference precision, but the fused bf16 "
+                                   f"layer cannot run this call ({reason}) and the bf16 convolution kernel does not cover "
+                                   f"it ({why})")
+        return None
+
     def forward(self, x, c, skips=None, skip_scale=1.0, chain_aux=False, inplace_skips=False):
         """Returns (x_out, skips + s) -- the running skip sum is an addend of the skip conv's epilogue
         (``skip_scale`` is the final ``sqrt(1/layers)`` of the generator, applied by the last block).
         ``inplace_skips``: the no-grad fused path may write the new running sum into ``skips`` itself.
         ``chain_aux``: also return the aux features for the NEXT layer (the same values; on the one-launch autograd
         path an alias whose gradient is chained through the layers' data-gradient epilogues)."""
-        if self._fusable(x, c):
+        if any(cv is not None and cv.precision == "bf16" for cv in self.fused_convs()):
+            out = self._forward_bf16(x, c, skips, skip_scale, chain_aux, inplace_skips)
+            if out is not None:
+                return out
+        elif self._fusable(x, c):
             needs_grad = torch.is_grad_enabled() and (x.requires_grad or c.requires_grad
                                                       or (skips is not None and skips.requires_grad)
                                                       or any(p.requires_grad for p in self.fused_params()))

@@ -10,6 +10,7 @@ from .. import functional as Fn
 from ..layers import upsample
 from ..layers.activation import FusedActivation
 from ..layers.conv import Conv1d as _AnyConv1d
+from ..layers.conv import _ConvNd
 from ..layers.residual_block import Conv1d, Conv1d1x1
 from ..layers.residual_block import WaveNetResidualBlock as ResidualBlock
 from ..layers.upsample import Conv2d as UpsampleConv2d
@@ -119,8 +120,28 @@ class ParallelWaveGANGenerator(torch.nn.Module, _WeightNormMixin):
         self.register_buffer("scale", torch.from_numpy(scale).float())
         logging.info("Successfully registered stats as buffer.")
 
-    def inference(self, c=None, x=None, normalize_before=False):
-        """c: (T', C) mel, x: (T, 1) noise (drawn here if omitted) -> (T, out_channels)."""
+    def inference(self, c=None, x=None, normalize_before=False, precision=None):
+        """c: (T', C) mel, x: (T, 1) noise (drawn here if omitted) -> (T, out_channels).
+
+        ``precision``: None = whatever ``utils.set_inference_precision`` set on the model (default fp32); ``"bf16"`` /
+        ``"fp32"`` = this call only (the modules' settings are restored afterwards).  A bf16 call runs under
+        ``torch.no_grad()``: the mode has no backward pass."""
+        if precision is not None:
+            from ..utils.precision import set_inference_precision
+
+            saved = [(m, m.precision) for m in self.modules() if isinstance(m, _ConvNd)]
+            set_inference_precision(self, precision)
+            try:
+                return self.inference(c, x, normalize_before)
+            finally:
+                for m, p in saved:
+                    m.precision = p
+        if any(isinstance(m, _ConvNd) and m.precision == "bf16" for m in self.modules()):
+            with torch.no_grad():
+                return self._inference(c, x, normalize_before)
+        return self._inference(c, x, normalize_before)
+
+    def _inference(self, c, x, normalize_before):
         dev = next(self.parameters()).device
         if x is not None:
             if not isinstance(x, torch.Tensor):

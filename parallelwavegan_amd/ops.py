@@ -364,6 +364,57 @@ def wavenet_layer_forward(desc, x, c, skips, packed, b_dil, b_skip, b_out, save=
     return x_out, skips_out, z, g
 
 
+def wavenet_bf16_supported(desc):
+    """Does the bf16-operand one-launch layer (csrc/wavenet_bf16.hip) cover this geometry?  Host logic only (no device
+    needed); ``_lib.lib().pwg_last_error()`` names the reason for a False."""
+    return bool(_lib.lib().pwg_wavenet_bf16_supported(ctypes.byref(desc)))
+
+
+def wavenet_bf16_packed_weight_bytes(desc):
+    n = _lib.lib().pwg_wavenet_bf16_packed_weight_bytes(ctypes.byref(desc))
+    if n == 0:
+        _lib.check(-1, "wavenet_bf16_packed_weight_bytes")
+    return n
+
+
+def wavenet_bf16_pack_weights(desc, w_dil, s_dil, w_aux, s_aux, w_skip, s_skip, w_out, s_out):
+    """The four torch-layout fp32 weights of a layer (+ optional weight-norm row scales) -> one bf16 MFMA weight image
+    (an opaque byte tensor); each effective weight ``w * scale`` is rounded to bf16 here, once."""
+    _require_device(w_dil, s_dil, w_aux, s_aux, w_skip, s_skip, w_out, s_out)
+    out = torch.empty(wavenet_bf16_packed_weight_bytes(desc), device=w_dil.device, dtype=torch.uint8)
+    _lib.check(_lib.lib().pwg_wavenet_bf16_pack_weights(ctypes.byref(desc), _ptr(w_dil), _ptr(s_dil), _ptr(w_aux),
+                                                        _ptr(s_aux), _ptr(w_skip), _ptr(s_skip), _ptr(w_out), _ptr(s_out),
+                                                        _ptr(out), _stream()), "wavenet_bf16_pack_weights")
+    return out
+
+
+def wavenet_bf16_layer_forward(desc, x, c, skips, packed, b_dil, b_skip, b_out, save=False, skips_out=None,
+                               mfma_shape=None):
+    """One gated residual layer with bf16 operands (inference only) -> (x_out, skips_out, z, g); ``z`` (fp32) and ``g``
+    (the bf16-rounded gate output, stored as fp32) only with ``save`` (stage tests).  ``skips_out`` may be ``skips``
+    itself.  ``mfma_shape`` (tuning): 32 or 16 selects the MFMA instruction explicitly."""
+    _require_device(x, c, skips, b_dil, b_skip, b_out, skips_out)
+    if not packed.is_cuda or packed.dtype != torch.uint8:
+        raise RuntimeError("wavenet_bf16_layer_forward: packed must be the device image of wavenet_bf16_pack_weights")
+    assert tuple(x.shape) == (desc.batch, desc.residual_channels, desc.t) and x.is_contiguous(), tuple(x.shape)
+    assert tuple(c.shape) == (desc.batch, desc.aux_channels, desc.t) and c.is_contiguous(), tuple(c.shape)
+    for t in (skips, skips_out):
+        assert t is None or (t.shape == x.shape and t.is_contiguous())
+    x_out = torch.empty_like(x)
+    if skips_out is None:
+        skips_out = torch.empty_like(x)
+    z = torch.empty((x.shape[0], desc.gate_channels, x.shape[2]), device=x.device, dtype=torch.float32) if save else None
+    g = torch.empty_like(x) if save else None
+    args = [ctypes.byref(desc), _ptr(x), _ptr(c), _ptr(skips), _ptr(packed), _ptr(b_dil), _ptr(b_skip), _ptr(b_out),
+            _ptr(x_out), _ptr(skips_out), _ptr(z), _ptr(g)]
+    if mfma_shape is None:
+        rc = _lib.lib().pwg_wavenet_bf16_layer_forward(*args, _stream())
+    else:
+        rc = _lib.lib().pwg_wavenet_bf16_layer_forward_cfg(*args, int(mfma_shape), _stream())
+    _lib.check(rc, "wavenet_bf16_layer_forward")
+    return x_out, skips_out, z, g
+
+
 def wavenet_pack_weights_bwd(desc, w_dil, s_dil, w_aux, s_aux, w_skip, s_skip, w_out, s_out):
     """Backward-pass image of a layer (gate / dilated / aux data gradients; folds desc.out_mul and desc.skip_mul)."""
     _require_device(w_dil, s_dil, w_aux, s_aux, w_skip, s_skip, w_out, s_out)

@@ -1,4 +1,5 @@
-"""Opt-in reduced-precision inference: bf16 operands, fp32 accumulation, fp32 tensors (csrc/conv1d_bf16.hip)."""
+"""Opt-in reduced-precision inference: bf16 operands, fp32 accumulation, fp32 tensors (csrc/conv1d_bf16.hip,
+csrc/wavenet_bf16.hip)."""
 from ..layers.conv import _ConvNd
 
 PRECISIONS = ("fp32", "bf16")
@@ -8,14 +9,23 @@ def set_inference_precision(model, precision):
     """Switch every convolution of ``model`` to ``"bf16"`` (bf16-operand MFMA kernel, inference only) or back to
     ``"fp32"`` (the default).  Module tree, tensor dtypes, state dicts and checkpoints do not change: the mode is an
     attribute of the convolution modules.  A convolution the bf16 kernel does not cover (grouped, (k, 1) Conv2d,
-    reflect padding, strided) stays at ``"fp32"``.  Returns how many convolutions took the requested mode."""
+    reflect padding, strided) stays at ``"fp32"``.  Coverage is decided per block where a module runs several
+    convolutions as one fused bf16 launch: a module's ``bf16_covered_convs()`` (the PWG residual block,
+    csrc/wavenet_bf16.hip) names convolutions that launch covers even where the stand-alone kernel does not.  Returns how
+    many convolutions took the requested mode."""
     if precision not in PRECISIONS:
         raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
+    covered = set()
+    if precision == "bf16":
+        for m in model.modules():
+            hook = getattr(m, "bf16_covered_convs", None)
+            if callable(hook):
+                covered.update(id(cv) for cv in hook())
     n = 0
     for m in model.modules():
         if not isinstance(m, _ConvNd):
             continue
-        if precision == "bf16" and not m.bf16_capable():
+        if precision == "bf16" and id(m) not in covered and not m.bf16_capable():
             m.precision = "fp32"
             continue
         m.precision = precision
