@@ -21,13 +21,10 @@
 // Deterministic: one workgroup owns an output tile, no split reduction, no atomics.
 // What bounds it and what was measured on the way: DESIGN.md s9, profiles/bf16_infer.json, bf16_infer_variants.txt.
 #include "common.h"
+#include "bf16_mfma.h"
 
 namespace pwg {
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int KC = 32;       // input channels per staged chunk
 constexpr int ROW = KC + 8;  // bf16 elements per LDS row (80 B)
@@ -133,23 +130,6 @@ __global__ __launch_bounds__(256) void pack_weight_bf16_kernel(const float* __re
     wp[i] = (__bf16)v;
   }
 }
-
-template <int TILE>
-struct Mfma;
-template <>
-struct Mfma<32> {
-  typedef f32x16 acc_t;
-  static __device__ __forceinline__ acc_t run(bf16x8 a, bf16x8 b, acc_t c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-  }
-};
-template <>
-struct Mfma<16> {
-  typedef f32x4 acc_t;
-  static __device__ __forceinline__ acc_t run(bf16x8 a, bf16x8 b, acc_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-  }
-};
 
 // TILE: MFMA shape (32: 32x32x16, 16: 16x16x32).  A wave computes (WM * 32) rows x (WN * 32) columns; the 4 waves of a
 // workgroup are arranged WAVES_M x (4 / WAVES_M).  TRANSPOSED: polyphase epilogue scatter.  VEC: the x window is staged
@@ -262,12 +242,12 @@ __global__ __launch_bounds__(256) void conv1d_bf16_mfma_kernel(Bf16Args a) {
     }
   }
 
-  // epilogue (fp32): C layout col = lane % TILE, row = (i & 3) + 4 * (lane / TILE) + 4 * HL * (i >> 2)
+  // epilogue (fp32): C layout col = lane % TILE, row = mfma_acc_row (bf16_mfma.h)
 #pragma unroll
   for (int mi = 0; mi < TM; ++mi) {
 #pragma unroll
     for (int i = 0; i < NREG; ++i) {
-      const int m = m0 + wave_m * (WM * 32) + mi * TILE + (i & 3) + 4 * h + 4 * HL * (i >> 2);
+      const int m = mfma_acc_row<TILE>(m0 + wave_m * (WM * 32) + mi * TILE, i, h);
       if (m >= a.m) continue;
       int co = m, ph = 0;
       if (TRANSPOSED) {

@@ -26,16 +26,14 @@
 // pwg_wavenet_bf16_layer_forward_cfg selects.  Deterministic: one workgroup owns its output tile over the whole
 // reduction, no split-K, no atomics.
 #include "common.h"
+#include "bf16_mfma.h"
 
 #include <stdint.h>
 
 namespace pwg {
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));  // 16-B load at a 4-B aligned address
 
 constexpr int BR = 64;                  // residual channels
@@ -79,23 +77,6 @@ __device__ __forceinline__ float gate_fp32(float t, float s) {
   return th * sg;
 }
 
-template <int TILE>
-struct Mfma;
-template <>
-struct Mfma<32> {
-  typedef f32x16 acc_t;
-  static __device__ __forceinline__ acc_t run(bf16x8 a, bf16x8 b, acc_t c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-  }
-};
-template <>
-struct Mfma<16> {
-  typedef f32x4 acc_t;
-  static __device__ __forceinline__ acc_t run(bf16x8 a, bf16x8 b, acc_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-  }
-};
-
 // TILE: MFMA shape (32: 32x32x16, 16: 16x16x32).  A wave owns a 32 x 32 block of each half: TM x TN MFMA tiles.
 template <int TILE>
 __global__ __launch_bounds__(256, 2) void wavenet_bf16_layer_kernel(WbArgs a) {
@@ -125,7 +106,7 @@ __global__ __launch_bounds__(256, 2) void wavenet_bf16_layer_kernel(WbArgs a) {
   const float* cb = a.c + (long)b * BA * T;
 
   // accumulator element i of tile (mi, ni): row h * 32 + mi * TILE + rowin(i), column cn * 32 + ni * TILE + r
-  auto rowin = [&](int i) { return (i & 3) + 4 * lg + 4 * HL * (i >> 2); };
+  auto rowin = [&](int i) { return mfma_acc_row<TILE>(0, i, lg); };
 
   {
     const float* src = tid < BG ? a.b_dil : (tid < BG + BS ? a.b_skip : a.b_out);

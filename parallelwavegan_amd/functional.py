@@ -108,10 +108,11 @@ class PreparedWeights:
 
     __slots__ = ("key", "w", "_scale", "_fwd", "_fwd_desc", "_bwd", "_res", "_bf16", "_stale")
 
-    def __init__(self, key, w, scale, fwd=None, fwd_desc=None):
+    def __init__(self, key, w, scale, fwd=None, fwd_desc=None, bwd=None):
         """``fwd``: the packed forward image, or None with ``fwd_desc`` (any descriptor of the layer) to build it
-        on first use -- layers that only run inside a fused multi-layer kernel never need it."""
-        self.key, self.w, self._scale, self._fwd, self._fwd_desc, self._bwd, self._res = key, w, scale, fwd, fwd_desc, None, None
+        on first use -- layers that only run inside a fused multi-layer kernel never need it.  ``bwd``: the packed
+        data-gradient image where the caller (the weight bank) has built it already."""
+        self.key, self.w, self._scale, self._fwd, self._fwd_desc, self._bwd, self._res = key, w, scale, fwd, fwd_desc, bwd, None
         self._bf16 = None
         self._stale = False  # set by weight_bank.WeightBank when it overwrites the (shared, persistent) images
 
@@ -127,37 +128,30 @@ class PreparedWeights:
                                "through a graph built before the last parameter update is not supported with a "
                                "weight bank (call backward before the optimizer step, or disable the bank)")
 
+    def _image(self, slot, pack, *desc):
+        """The image kept in ``slot``; built on first use by ``pack(*desc, w, scale)``."""
+        self._check()
+        img = getattr(self, slot)
+        if img is None:
+            with torch.no_grad():
+                img = pack(*desc, self.w, self._scale)
+            setattr(self, slot, img)
+        return img
+
     @property
     def fwd(self):
-        self._check()
-        if self._fwd is None:
-            with torch.no_grad():
-                self._fwd = ops.pack_weight(self._fwd_desc, self.w, self._scale)
-        return self._fwd
+        return self._image("_fwd", ops.pack_weight, self._fwd_desc)
 
     def res(self):
-        """MFMA A-operand image for the one-launch residual unit (csrc/resunit.hip), built on first use."""
-        self._check()
-        if self._res is None:
-            with torch.no_grad():
-                self._res = ops.resunit_pack_weight(self.w, self._scale)
-        return self._res
+        """MFMA A-operand image for the one-launch residual unit (csrc/resunit.hip)."""
+        return self._image("_res", ops.resunit_pack_weight)
 
     def bf16(self):
-        """bf16 MFMA weight image of the opt-in bf16-operand inference mode (csrc/conv1d_bf16.hip), built on first use;
-        it lives and dies with this instance, i.e. with the parameter state the fp32 image is keyed on."""
-        self._check()
-        if self._bf16 is None:
-            with torch.no_grad():
-                self._bf16 = ops.pack_weight_bf16(self._fwd_desc, self.w, self._scale)
-        return self._bf16
+        """bf16 MFMA weight image of the opt-in bf16-operand inference mode (csrc/conv1d_bf16.hip)."""
+        return self._image("_bf16", ops.pack_weight_bf16, self._fwd_desc)
 
     def bwd(self, desc):
-        self._check()
-        if self._bwd is None:
-            with torch.no_grad():
-                self._bwd = ops.pack_weight_bwd(desc, self.w, self._scale)
-        return self._bwd
+        return self._image("_bwd", ops.pack_weight_bwd, desc)
 
 
 class FusedConvFn(torch.autograd.Function):
@@ -426,7 +420,7 @@ class WaveNetLayerFn(torch.autograd.Function):
         ctx.param_refs = params
         # the backward reads the weights through ``block`` (packed images, weight-norm tensors), not through
         # saved_tensors: remember their versions so that an update between forward and backward is an error here too
-        ctx.param_keys = tuple(cv._params_key()[1:] for cv in convs)
+        ctx.param_keys = tuple(cv._param_state() for cv in convs)
         ctx.save_for_backward(x, c, z, gt)
         ctx.set_materialize_grads(False)
         # third output: c itself, for the NEXT layer -- the gradient of the shared aux features then arrives here
@@ -442,7 +436,7 @@ class WaveNetLayerFn(torch.autograd.Function):
         x, c, z, gt = ctx.saved_tensors
         block, desc = ctx.block, ctx.desc
         conv_d, conv_a, conv_s, conv_o = block.fused_convs()
-        if tuple(cv._params_key()[1:] for cv in (conv_d, conv_a, conv_s, conv_o)) != ctx.param_keys:
+        if tuple(cv._param_state() for cv in (conv_d, conv_a, conv_s, conv_o)) != ctx.param_keys:
             raise RuntimeError("WaveNetLayerFn.backward: a parameter of the layer was modified after the forward pass "
                                "(in-place update or optimizer step between forward and backward)")
         h_d, h_a, h_s, h_o = ctx.holders
@@ -538,7 +532,7 @@ class ResStackFn(torch.autograd.Function):
         y, h = ops.resstack_forward(x, stack.unit_image(), d, slope, *bias, save_h=True)
         ctx.stack, ctx.geom = stack, (d, slope)
         ctx.holders = [cv.prepared() for cv in convs]  # (the parameter values this forward used)
-        ctx.param_keys = tuple(cv._params_key()[1:] for cv in convs)
+        ctx.param_keys = tuple(cv._param_state() for cv in convs)
         ctx.save_for_backward(x, h)
         ctx.set_materialize_grads(False)
         return y
@@ -551,7 +545,7 @@ class ResStackFn(torch.autograd.Function):
         n_par = [1 + int(cv.has_weight_norm) + int(cv.bias is not None) for cv in convs]
         if dy is None:
             return (None, None) + (None,) * sum(n_par)
-        if tuple(cv._params_key()[1:] for cv in convs) != ctx.param_keys:
+        if tuple(cv._param_state() for cv in convs) != ctx.param_keys:
             raise RuntimeError("ResStackFn.backward: a parameter of the unit was modified after the forward pass")
         d, slope = ctx.geom
         dy = _c(dy)

@@ -13,12 +13,11 @@ class GraphedInference:
     static buffers and replays.  One graph per distinct input shape (cached).
 
     The capture records the kernels that read the packed weight images of that moment.  Every call first compares the
-    model's *parameter state* -- storage address, torch version counter and the engine's own epoch of every parameter
-    and buffer (``ops.param_epoch``: the fused optimizers update through raw pointers), plus the global weight-cache
-    epoch and every convolution's inference precision -- with the state at capture time; after ``load_state_dict``, an
-    optimizer step, ``remove_weight_norm``, ``set_inference_precision`` ... the stale graphs are dropped and the call
-    captures again, so a replay can never synthesise with old weights
-    (VERDICT r04).  :meth:`reset` does the same by hand."""
+    model's *parameter state* -- the key of the weight-image caches (``ops.cache_epoch``, ``ops.tensor_state``;
+    DESIGN.md s3.7) over every parameter and buffer, plus the training flag and every convolution's inference precision
+    -- with the state at capture time; after ``load_state_dict``, an optimizer step, ``remove_weight_norm``,
+    ``set_inference_precision`` ... the stale graphs are dropped and the call captures again, so a replay can never
+    synthesise with old weights.  :meth:`reset` does the same by hand."""
 
     def __init__(self, model, warmup=2, frozen=False):
         self.model = model
@@ -44,17 +43,15 @@ class GraphedInference:
             return None
         if self.frozen and self._state is not None:
             return self._state  # the caller vouches for frozen weights: no per-call walk over the tensors
-        st = [ops.PARAM_EPOCH[0], model.training]
-        for t in model.parameters():
-            st.append((t.data_ptr(), ops.tensor_version(t), ops.param_epoch(t)))
-        for t in model.buffers():
-            st.append((t.data_ptr(), ops.tensor_version(t)))
+        st = [ops.cache_epoch(), model.training]
+        st += [ops.tensor_state(t) for t in model.parameters()]
+        st += [ops.tensor_state(t) for t in model.buffers()]
         # the inference precision of every convolution: switching it (utils.set_inference_precision) drops the graphs
         # (the list of convolution modules is taken once: walking the module tree costs as much as the tensors above)
         if self._convs is None:
-            from .layers.conv import _ConvNd
+            from .layers.conv import each_conv
 
-            self._convs = [m for m in model.modules() if isinstance(m, _ConvNd)]
+            self._convs = list(each_conv(model))
         st.append(tuple(m.precision for m in self._convs))
         return st
 

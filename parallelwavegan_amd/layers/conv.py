@@ -55,8 +55,7 @@ class _ConvNd(torch.nn.Module):
             self.bias = torch.nn.Parameter(torch.empty(out_channels))
         else:
             self.register_parameter("bias", None)
-        self._cache_key = None
-        self._cache_packed = None
+        self._cache_packed = None  # functional.PreparedWeights; current while its key equals _params_key()
         self.spectral_eps = 1e-12
         self.reset_parameters()
 
@@ -103,7 +102,7 @@ class _ConvNd(torch.nn.Module):
             g = w.detach().reshape(w.shape[0], -1).norm(dim=1).reshape((-1,) + (1,) * (w.dim() - 1))
         self.weight_g = torch.nn.Parameter(g.clone())
         self.weight_v = torch.nn.Parameter(w.detach().clone())
-        self._cache_key = None
+        self._cache_packed = None
         return self
 
     def remove_weight_norm(self):
@@ -111,7 +110,7 @@ class _ConvNd(torch.nn.Module):
             raise ValueError(f"weight norm is not applied to {self.__class__.__name__}")
         g, v = self._parameters.pop("weight_g"), self._parameters.pop("weight_v")
         self.weight = torch.nn.Parameter(self._bake_weight_norm(g.detach(), v.detach()))
-        self._cache_key = None
+        self._cache_packed = None
         return self
 
     @staticmethod
@@ -146,7 +145,7 @@ class _ConvNd(torch.nn.Module):
         self.weight_orig = torch.nn.Parameter(w.detach().clone())
         self.register_buffer("weight_u", u)
         self.register_buffer("weight_v", v)
-        self._cache_key = None
+        self._cache_packed = None
         return self
 
     def remove_spectral_norm(self):
@@ -158,7 +157,7 @@ class _ConvNd(torch.nn.Module):
             wm = w.detach().reshape(w.shape[0], -1)
             sigma = torch.dot(u, torch.mv(wm, v))
         self.weight = torch.nn.Parameter(w.detach() / sigma)
-        self._cache_key = None
+        self._cache_packed = None
         return self
 
     # -- effective weight
@@ -175,20 +174,23 @@ class _ConvNd(torch.nn.Module):
         with torch.no_grad():
             return self.weight_tensor().detach()
 
-    def _params_key(self):
+    def _param_state(self):
+        """``ops.tensor_state`` of the tensors the effective weight is derived from (the key without the global epoch)."""
         ps = [self.raw_weight] + ([self.weight_g] if self.has_weight_norm else [])
         if self.has_spectral_norm:
             ps += [self.weight_u, self.weight_v]
-        # the fused optimizers update parameters through raw pointers: they bump a per-parameter
-        # epoch (ops.param_epoch) instead of torch's version counter
-        return (ops.PARAM_EPOCH[0],) + tuple((p.data_ptr(), ops.tensor_version(p), ops.param_epoch(p), str(p.device)) for p in ps)
+        return tuple(ops.tensor_state(p) for p in ps)
+
+    def _params_key(self):
+        """The key every image derived from this layer's weight is cached under."""
+        return (ops.cache_epoch(),) + self._param_state()
 
     def prepared(self):
         """:class:`functional.PreparedWeights` for the current parameter values (weight or weight-norm
         layers): weight-norm scale, packed forward image and, lazily, the packed data-gradient image.
         Shared by every forward / backward until a parameter changes."""
         key = self._params_key()
-        if self._cache_key != key or self._cache_packed is None:
+        if self._cache_packed is None or self._cache_packed.key != key:
             desc = self.make_desc(1, self._probe_len())
             with torch.no_grad():
                 if self.has_weight_norm:
@@ -198,22 +200,30 @@ class _ConvNd(torch.nn.Module):
                 else:
                     w = self._w3(self.effective_weight())
                     self._cache_packed = Fn.PreparedWeights(key, w, None, None, desc)
-            self._cache_key = key
         return self._cache_packed
+
+    def adopt_prepared(self, pw):
+        """Take ``pw``, built elsewhere (weight_bank.WeightBank) under the current ``_params_key()``, as what
+        ``prepared()`` returns until a parameter changes."""
+        self._cache_packed = pw
+
+    def holds_current(self, pw):
+        """Is ``pw`` the instance this layer holds, and is it current?"""
+        return self._cache_packed is pw and pw.key == self._params_key()
+
+    def _packed(self, pack, cached):
+        if self.has_spectral_norm and self.training:
+            # every training-mode forward performs a power iteration: nothing to cache
+            return pack(self.make_desc(1, self._probe_len()), self._w3(self.effective_weight()))
+        return cached(self.prepared())
 
     def packed_weight(self):
         """Cached forward weight image (no-grad path)."""
-        if self.has_spectral_norm and self.training:
-            # every training-mode forward performs a power iteration: nothing to cache
-            return ops.pack_weight(self.make_desc(1, self._probe_len()), self._w3(self.effective_weight()))
-        return self.prepared().fwd
+        return self._packed(ops.pack_weight, lambda pw: pw.fwd)
 
     def packed_weight_bf16(self):
-        """Cached bf16 weight image (bf16-operand inference); keyed like the fp32 image, so ``load_state_dict``, optimizer
-        steps and ``remove_weight_norm`` invalidate both together."""
-        if self.has_spectral_norm and self.training:
-            return ops.pack_weight_bf16(self.make_desc(1, self._probe_len()), self._w3(self.effective_weight()))
-        return self.prepared().bf16()
+        """Cached bf16 weight image (bf16-operand inference), held by the same ``prepared()`` instance."""
+        return self._packed(ops.pack_weight_bf16, lambda pw: pw.bf16())
 
     def bf16_capable(self):
         """Does the bf16-operand kernel cover this layer's geometry (host logic, no device needed)?"""
@@ -281,10 +291,7 @@ class _ConvNd(torch.nn.Module):
                      out_mul=out_mul, out_div=out_div)
         width_mode = self.width_mode or folded > 0
         if self.precision == "bf16" and self._needs_grad(x, add1, add2):
-            raise RuntimeError(
-                f"{self.__class__.__name__} is in bf16 inference precision, which has no backward pass: run it under "
-                "torch.no_grad() (HiFiGANGenerator.inference(..., precision='bf16') does), or switch back with "
-                "utils.set_inference_precision(model, 'fp32') before training")
+            raise bf16_no_backward_error(self, "HiFiGANGenerator")
         if self._needs_grad(x, add1, add2):
             geom = self.geom()
             if width_mode:
@@ -337,6 +344,34 @@ class _ConvNd(torch.nn.Module):
         norm = "weight_norm" if self.has_weight_norm else ("spectral_norm" if self.has_spectral_norm else "none")
         return (f"{self.in_channels}, {self.out_channels}, kernel_size={self.kernel_size}, stride={self.stride}, "
                 f"padding={self.padding}, dilation={self.dilation}, groups={self.groups}, norm={norm}")
+
+
+def each_conv(module):
+    """Every convolution module (:class:`_ConvNd`) of a module tree."""
+    return (m for m in module.modules() if isinstance(m, _ConvNd))
+
+
+def group_image(owner, slot, convs, pack, *extra):
+    """The image that ``pack(w0, scale0, w1, scale1, ...)`` builds from the weights and weight-norm row scales of
+    ``convs`` (a fused multi-layer kernel's operand), cached on ``owner`` under ``slot`` until a parameter of any of
+    them changes; ``extra``: further key parts (what else the image depends on)."""
+    key = extra + tuple(cv._params_key() for cv in convs)
+    held = getattr(owner, slot, None)
+    if held is None or held[0] != key:
+        hs = [cv.prepared() for cv in convs]
+        with torch.no_grad():
+            held = (key, pack(*(t for h in hs for t in (h.w, h.scale))))
+        setattr(owner, slot, held)
+    return held[1]
+
+
+def bf16_no_backward_error(module, model):
+    """What a gradient-requiring call of a module in bf16 mode raises (``model``: the generator class whose
+    ``inference(..., precision='bf16')`` is the intended entry)."""
+    return RuntimeError(
+        f"{module.__class__.__name__} is in bf16 inference precision, which has no backward pass: run it under "
+        f"torch.no_grad() ({model}.inference(..., precision='bf16') does), or switch back with "
+        "utils.set_inference_precision(model, 'fp32') before training")
 
 
 class Conv1d(_ConvNd):

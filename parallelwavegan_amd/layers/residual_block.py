@@ -8,6 +8,7 @@ from .. import functional as Fn
 from .. import ops
 from .activation import FusedActivation
 from .conv import Conv1d as _Conv1d
+from .conv import bf16_no_backward_error, group_image
 
 
 from .causal_conv import CausalConv1d  # noqa: E402  (depends on .conv only)
@@ -86,28 +87,14 @@ class WaveNetResidualBlock(torch.nn.Module):
 
     def fused_image(self):
         """MFMA A-operand image of the layer's four weights for the current parameter values."""
-        convs = self.fused_convs()
-        key = tuple(cv._params_key() for cv in convs)
-        if getattr(self, "_fused_key", None) != key:
-            hs = [cv.prepared() for cv in convs]
-            with torch.no_grad():
-                self._fused_img = ops.wavenet_pack_weights(self.fused_desc(1, 64), hs[0].w, hs[0].scale, hs[1].w,
-                                                           hs[1].scale, hs[2].w, hs[2].scale, hs[3].w, hs[3].scale)
-            self._fused_key = key
-        return self._fused_img
+        return group_image(self, "_fused_img", self.fused_convs(),
+                           lambda *ws: ops.wavenet_pack_weights(self.fused_desc(1, 64), *ws))
 
     def fused_image_bwd(self, skip_scale=1.0):
         """Backward-pass image (gate / dilated / aux data gradients) for the current parameter values."""
-        convs = self.fused_convs()
-        key = (float(skip_scale),) + tuple(cv._params_key() for cv in convs)
-        if getattr(self, "_fused_bwd_key", None) != key:
-            hs = [cv.prepared() for cv in convs]
-            with torch.no_grad():
-                self._fused_bwd_img = ops.wavenet_pack_weights_bwd(self.fused_desc(1, 64, skip_scale), hs[0].w, hs[0].scale,
-                                                                   hs[1].w, hs[1].scale, hs[2].w, hs[2].scale, hs[3].w,
-                                                                   hs[3].scale)
-            self._fused_bwd_key = key
-        return self._fused_bwd_img
+        return group_image(self, "_fused_bwd_img", self.fused_convs(),
+                           lambda *ws: ops.wavenet_pack_weights_bwd(self.fused_desc(1, 64, skip_scale), *ws),
+                           float(skip_scale))
 
     def _fusable(self, x, c):
         if not self.fuse_layer or c is None or self.conv1x1_aux is None or x.dim() != 3 or not x.is_cuda:
@@ -142,30 +129,16 @@ class WaveNetResidualBlock(torch.nn.Module):
         return tuple(self.fused_convs()) if self._bf16_geometry_reason() is None else ()
 
     def fused_image_bf16(self):
-        """bf16 MFMA image of the layer's four weights; keyed like ``fused_image`` (``load_state_dict``, optimizer steps
-        and ``remove_weight_norm`` invalidate both together)."""
-        convs = self.fused_convs()
-        key = tuple(cv._params_key() for cv in convs)
-        if getattr(self, "_fused_bf16_key", None) != key:
-            hs = [cv.prepared() for cv in convs]
-            with torch.no_grad():
-                self._fused_bf16_img = ops.wavenet_bf16_pack_weights(self.fused_desc(1, 64), hs[0].w, hs[0].scale,
-                                                                     hs[1].w, hs[1].scale, hs[2].w, hs[2].scale,
-                                                                     hs[3].w, hs[3].scale)
-            self._fused_bf16_key = key
-        return self._fused_bf16_img
+        """bf16 MFMA image of the layer's four weights, cached like ``fused_image``."""
+        return group_image(self, "_fused_bf16_img", self.fused_convs(),
+                           lambda *ws: ops.wavenet_bf16_pack_weights(self.fused_desc(1, 64), *ws))
 
     def _forward_bf16(self, x, c, skips, skip_scale, chain_aux, inplace_skips):
         """Some convolution of the block is in bf16 mode: the fused bf16 launch when all four are and it covers the
         call, else the per-convolution path -- where every bf16 convolution must run in bf16 on its own kernel."""
         convs = [cv for cv in self.fused_convs() if cv is not None]
-        if torch.is_grad_enabled() and (x.requires_grad or (c is not None and c.requires_grad)
-                                        or (skips is not None and skips.requires_grad)
-                                        or any(p.requires_grad for cv in convs for p in cv.parameters())):
-            raise RuntimeError(
-                f"{self.__class__.__name__} is in bf16 inference precision, which has no backward pass: run it under "
-                "torch.no_grad() (ParallelWaveGANGenerator.inference(..., precision='bf16') does), or switch back with "
-                "utils.set_inference_precision(model, 'fp32') before training")
+        if any(cv._needs_grad(x, c, skips) for cv in convs):
+            raise bf16_no_backward_error(self, "ParallelWaveGANGenerator")
         all_bf16 = all(cv.precision == "bf16" for cv in convs)
         reason = None
         if not all_bf16:

@@ -7,7 +7,7 @@ from .. import functional as Fn
 from .. import ops
 from .activation import FusedActivation
 from .causal_conv import CausalConv1d
-from .conv import Conv1d
+from .conv import Conv1d, group_image
 from .padding import get_pad
 
 
@@ -73,23 +73,13 @@ class ResidualStack(torch.nn.Module):
                 ps.append(cv.bias)
         return ps
 
-    def _image(self, attr, pack):
-        convs = self.unit_convs()
-        key = tuple(cv._params_key() for cv in convs)
-        if getattr(self, attr + "_key", None) != key:
-            hs = [cv.prepared() for cv in convs]
-            with torch.no_grad():
-                setattr(self, attr, pack(hs[0].w, hs[0].scale, hs[1].w, hs[1].scale, hs[2].w, hs[2].scale))
-            setattr(self, attr + "_key", key)
-        return getattr(self, attr)
-
     def unit_image(self):
         """MFMA A-operand image of the three weights for the current parameter values (cached)."""
-        return self._image("_unit_img", ops.resstack_pack_weight)
+        return group_image(self, "_unit_img", self.unit_convs(), ops.resstack_pack_weight)
 
     def unit_image_bwd(self):
         """The same for the unit's data gradient (transposed weights)."""
-        return self._image("_unit_img_bwd", ops.resstack_pack_weight_bwd)
+        return group_image(self, "_unit_img_bwd", self.unit_convs(), ops.resstack_pack_weight_bwd)
 
     def _unit_ok(self, c, a0, conv0, a1, conv1):
         if not self.fuse_unit or self.use_causal_conv or not c.is_cuda or c.dim() != 3 or c.dtype != torch.float32:

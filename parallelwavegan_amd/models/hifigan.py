@@ -4,7 +4,6 @@ Drop-in for ``parallel_wavegan.models.hifigan`` (constructor kwargs, method
 names and state-dict keys follow /root/reference/parallel_wavegan/models/hifigan.py);
 the arithmetic is hand-written HIP behind ``parallelwavegan_amd.ops``.
 """
-import contextlib
 import copy
 import logging
 
@@ -14,16 +13,10 @@ import torch
 from .. import functional as Fn
 from ..layers.activation import FusedActivation, PreActivated, deferrable
 from ..layers.causal_conv import CausalConv1d, CausalConvTranspose1d
-from ..layers.conv import Conv1d, Conv2d, ConvTranspose1d
+from ..layers.conv import Conv1d, Conv2d, ConvTranspose1d, each_conv
 from ..layers.pooling import get_pooling
 from ..streams import fork_now, run_branches, run_branches_chained
 from ..layers.residual_block import HiFiGANResidualBlock as ResidualBlock
-
-
-def _each_conv(module):
-    for m in module.modules():
-        if isinstance(m, (Conv1d, ConvTranspose1d)):
-            yield m
 
 
 class HiFiGANGenerator(torch.nn.Module):
@@ -127,20 +120,20 @@ class HiFiGANGenerator(torch.nn.Module):
         ``weight_g``/``weight_v`` (SURVEY.md App. A "Init quirk"); reproduced here by
         only touching plain ``weight`` parameters.
         """
-        for m in _each_conv(self):
+        for m in each_conv(self):
             if not m.has_weight_norm:
                 with torch.no_grad():
                     m.weight.normal_(0.0, 0.01)
                 logging.debug(f"Reset parameters in {m}.")
 
     def remove_weight_norm(self):
-        for m in _each_conv(self):
+        for m in each_conv(self):
             if m.has_weight_norm:
                 m.remove_weight_norm()
                 logging.debug(f"Weight norm is removed from {m}.")
 
     def apply_weight_norm(self):
-        for m in _each_conv(self):
+        for m in each_conv(self):
             m.apply_weight_norm()
             logging.debug(f"Weight norm is applied to {m}.")
 
@@ -165,22 +158,13 @@ class HiFiGANGenerator(torch.nn.Module):
         ``precision``: None = whatever ``utils.set_inference_precision`` set on the model (default fp32); ``"bf16"`` /
         ``"fp32"`` = this call only (the modules' settings are restored afterwards).  A bf16 call runs under
         ``torch.no_grad()``: the mode has no backward pass."""
-        if precision is not None:
-            from ..utils.precision import set_inference_precision
+        from ..utils.precision import inference_precision, no_grad_if_bf16
 
-            saved = [(m, m.precision) for m in _each_conv(self)]
-            set_inference_precision(self, precision)
-            try:
-                return self.inference(c, normalize_before)
-            finally:
-                for m, p in saved:
-                    m.precision = p
         if not isinstance(c, torch.Tensor):
             c = torch.tensor(c, dtype=torch.float).to(next(self.parameters()).device)
         if normalize_before:
             c = (c - self.mean) / self.scale
-        bf16 = any(m.precision == "bf16" for m in _each_conv(self))
-        with torch.no_grad() if bf16 else contextlib.nullcontext():
+        with inference_precision(self, precision), no_grad_if_bf16(self):
             c = self.forward(c.transpose(1, 0).unsqueeze(0).contiguous())
         return c.squeeze(0).transpose(1, 0)
 

@@ -10,7 +10,6 @@ from .. import functional as Fn
 from ..layers import upsample
 from ..layers.activation import FusedActivation
 from ..layers.conv import Conv1d as _AnyConv1d
-from ..layers.conv import _ConvNd
 from ..layers.residual_block import Conv1d, Conv1d1x1
 from ..layers.residual_block import WaveNetResidualBlock as ResidualBlock
 from ..layers.upsample import Conv2d as UpsampleConv2d
@@ -126,20 +125,10 @@ class ParallelWaveGANGenerator(torch.nn.Module, _WeightNormMixin):
         ``precision``: None = whatever ``utils.set_inference_precision`` set on the model (default fp32); ``"bf16"`` /
         ``"fp32"`` = this call only (the modules' settings are restored afterwards).  A bf16 call runs under
         ``torch.no_grad()``: the mode has no backward pass."""
-        if precision is not None:
-            from ..utils.precision import set_inference_precision
+        from ..utils.precision import inference_precision, no_grad_if_bf16
 
-            saved = [(m, m.precision) for m in self.modules() if isinstance(m, _ConvNd)]
-            set_inference_precision(self, precision)
-            try:
-                return self.inference(c, x, normalize_before)
-            finally:
-                for m, p in saved:
-                    m.precision = p
-        if any(isinstance(m, _ConvNd) and m.precision == "bf16" for m in self.modules()):
-            with torch.no_grad():
-                return self._inference(c, x, normalize_before)
-        return self._inference(c, x, normalize_before)
+        with inference_precision(self, precision), no_grad_if_bf16(self):
+            return self._inference(c, x, normalize_before)
 
     def _inference(self, c, x, normalize_before):
         dev = next(self.parameters()).device

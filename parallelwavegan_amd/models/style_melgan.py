@@ -11,7 +11,7 @@ import torch
 
 from .. import functional as Fn
 from ..layers.activation import FusedActivation
-from ..layers.conv import Conv1d, ConvTranspose1d
+from ..layers.conv import Conv1d, ConvTranspose1d, each_conv
 from ..layers.pqmf import PQMF
 from ..layers.tade_res_block import TADEResBlock
 from .melgan import MelGANDiscriminator as BaseDiscriminator
@@ -19,20 +19,14 @@ from .melgan import MelGANDiscriminator as BaseDiscriminator
 __all__ = ["StyleMelGANGenerator", "StyleMelGANDiscriminator"]
 
 
-def _each_conv(module):
-    for m in module.modules():
-        if isinstance(m, (Conv1d, ConvTranspose1d)):
-            yield m
-
-
 class _NormMixin:
     def apply_weight_norm(self):
-        for m in _each_conv(self):
+        for m in each_conv(self):
             m.apply_weight_norm()
             logging.debug(f"Weight norm is applied to {m}.")
 
     def remove_weight_norm(self):
-        for m in _each_conv(self):
+        for m in each_conv(self):
             if m.has_weight_norm:
                 m.remove_weight_norm()
                 logging.debug(f"Weight norm is removed from {m}.")
@@ -40,7 +34,7 @@ class _NormMixin:
     def reset_parameters(self):
         """N(0, 0.02) on conv weights (style_melgan.py:169-179); as in the reference this only reaches
         plain ``weight`` parameters, i.e. it is a no-op once weight norm has been applied."""
-        for m in _each_conv(self):
+        for m in each_conv(self):
             if not m.has_weight_norm:
                 with torch.no_grad():
                     m.weight.normal_(0.0, 0.02)

@@ -14,17 +14,11 @@ import torch
 
 from .. import functional as Fn
 from ..layers.activation import FusedActivation
-from ..layers.conv import Conv1d, ConvTranspose1d
+from ..layers.conv import Conv1d, ConvTranspose1d, each_conv
 from ..layers.dropout import Dropout as _Dropout
 from ..layers.residual_block import HiFiGANResidualBlock as ResidualBlock
 
 __all__ = ["UHiFiGANGenerator"]
-
-
-def _each_conv(module):
-    for m in module.modules():
-        if isinstance(m, (Conv1d, ConvTranspose1d)):
-            yield m
 
 
 class UHiFiGANGenerator(torch.nn.Module):
@@ -111,19 +105,19 @@ class UHiFiGANGenerator(torch.nn.Module):
     def reset_parameters(self):
         """N(0, 0.01) on conv weights; with weight norm applied this touches no trainable parameter,
         exactly as the reference's version (it writes the derived ``.weight``)."""
-        for m in _each_conv(self):
+        for m in each_conv(self):
             if not m.has_weight_norm:
                 with torch.no_grad():
                     m.weight.normal_(0.0, 0.01)
 
     def remove_weight_norm(self):
-        for m in _each_conv(self):
+        for m in each_conv(self):
             if m.has_weight_norm:
                 m.remove_weight_norm()
                 logging.debug(f"Weight norm is removed from {m}.")
 
     def apply_weight_norm(self):
-        for m in _each_conv(self):
+        for m in each_conv(self):
             m.apply_weight_norm()
             logging.debug(f"Weight norm is applied to {m}.")
 

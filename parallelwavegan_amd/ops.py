@@ -14,8 +14,8 @@ ACT = {None: _lib.PWG_ACT_NONE, "none": _lib.PWG_ACT_NONE, "leaky_relu": _lib.PW
 PAD = {"zero": _lib.PWG_PAD_ZERO, "reflect": _lib.PWG_PAD_REFLECT, "replicate": _lib.PWG_PAD_REPLICATE}
 
 
-# Parameters updated through raw pointers (fused optimizer kernels) do not bump torch's version
-# counters; every such update bumps this epoch instead, and the packed-weight caches key on it.
+# The staleness rule of every derived weight image: an image is current
+# while cache_epoch() and the tensor_state() of every tensor it was derived from are what they were when it was built.
 PARAM_EPOCH = [0]
 
 
@@ -25,8 +25,20 @@ def bump_param_epoch():
     PARAM_EPOCH[0] += 1
 
 
+def cache_epoch():
+    """The global part of the key: what ``bump_param_epoch`` bumps."""
+    return PARAM_EPOCH[0]
+
+
 def param_epoch(p):
+    """The engine's own update count of ``p``: parameters updated through raw pointers (fused optimizer kernels) do not
+    bump torch's version counter; ``bump_params`` bumps this instead."""
     return getattr(p, "_pwg_epoch", 0)
+
+
+def tensor_state(t):
+    """The per-tensor part of the key: storage address, torch's version counter, the engine's epoch, device."""
+    return (t.data_ptr(), tensor_version(t), param_epoch(t), t.device)
 
 
 def tensor_version(t):

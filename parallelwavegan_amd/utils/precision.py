@@ -1,6 +1,10 @@
 """Opt-in reduced-precision inference: bf16 operands, fp32 accumulation, fp32 tensors (csrc/conv1d_bf16.hip,
 csrc/wavenet_bf16.hip)."""
-from ..layers.conv import _ConvNd
+import contextlib
+
+import torch
+
+from ..layers.conv import each_conv
 
 PRECISIONS = ("fp32", "bf16")
 
@@ -22,9 +26,7 @@ def set_inference_precision(model, precision):
             if callable(hook):
                 covered.update(id(cv) for cv in hook())
     n = 0
-    for m in model.modules():
-        if not isinstance(m, _ConvNd):
-            continue
+    for m in each_conv(model):
         if precision == "bf16" and id(m) not in covered and not m.bf16_capable():
             m.precision = "fp32"
             continue
@@ -35,4 +37,26 @@ def set_inference_precision(model, precision):
 
 def get_inference_precision(model):
     """``"bf16"`` if any convolution of ``model`` is in bf16 mode, else ``"fp32"``."""
-    return "bf16" if any(isinstance(m, _ConvNd) and m.precision == "bf16" for m in model.modules()) else "fp32"
+    return "bf16" if any(m.precision == "bf16" for m in each_conv(model)) else "fp32"
+
+
+@contextlib.contextmanager
+def inference_precision(model, precision):
+    """``with`` block that runs ``model`` in ``precision`` and restores every convolution's own mode afterwards
+    (``None``: leave the modes as they are) -- the ``precision=`` argument of the generators' ``inference()``."""
+    if precision is None:
+        yield
+        return
+    saved = [(m, m.precision) for m in each_conv(model)]
+    set_inference_precision(model, precision)
+    try:
+        yield
+    finally:
+        for m, p in saved:
+            m.precision = p
+
+
+def no_grad_if_bf16(model):
+    """``torch.no_grad()`` when any convolution of ``model`` is in bf16 mode (which has no backward pass), else a
+    context that changes nothing."""
+    return torch.no_grad() if get_inference_precision(model) == "bf16" else contextlib.nullcontext()

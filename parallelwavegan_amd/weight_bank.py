@@ -17,7 +17,7 @@ import torch
 
 from . import _lib, ops
 from . import functional as Fn
-from .layers.conv import _ConvNd
+from .layers.conv import each_conv
 
 
 class WeightBank:
@@ -33,8 +33,7 @@ class WeightBank:
 
     # -- which layers: every convolution of the tree whose effective weight is a pure function of its parameters
     def _collect(self):
-        return [m for m in self.module.modules()
-                if isinstance(m, _ConvNd) and not m.has_spectral_norm and m.raw_weight.is_cuda]
+        return [m for m in each_conv(self.module) if not m.has_spectral_norm and m.raw_weight.is_cuda]
 
     def _signature(self, layers):
         return tuple((id(m), m.raw_weight.data_ptr(), m.weight_g.data_ptr() if m.has_weight_norm else 0,
@@ -80,10 +79,8 @@ class WeightBank:
     def _current(self, with_bwd):
         if not self._layers or (with_bwd and not self._has_bwd):
             return False
-        for m, pw in zip(self._layers, self._handed):
-            if m._cache_packed is not pw or m._cache_key != m._params_key():
-                return False
-        return len(self._handed) == len(self._layers)
+        return (len(self._handed) == len(self._layers)
+                and all(m.holds_current(pw) for m, pw in zip(self._layers, self._handed)))
 
     def ensure(self, with_bwd=True):
         """Make every layer's prepared weights current (no launch when they already are)."""
@@ -103,9 +100,6 @@ class WeightBank:
         self._handed = []
         self._has_bwd = bool(with_bwd)
         for m, (w3, scale, fwd, bwd, desc) in zip(self._layers, self._bufs):
-            key = m._params_key()
-            pw = Fn.PreparedWeights(key, w3, scale, fwd, desc)
-            if with_bwd and bwd is not None:
-                pw._bwd = bwd
-            m._cache_packed, m._cache_key = pw, key
+            pw = Fn.PreparedWeights(m._params_key(), w3, scale, fwd, desc, bwd if with_bwd else None)
+            m.adopt_prepared(pw)
             self._handed.append(pw)

@@ -47,7 +47,7 @@ def test_bank_images_equal_the_per_layer_kernels(device, with_bwd):
         n_wn = 0
         for m in layers:
             pw = m._cache_packed
-            assert isinstance(pw, Fn.PreparedWeights) and m._cache_key == m._params_key()
+            assert isinstance(pw, Fn.PreparedWeights) and m.holds_current(pw)
             assert m.prepared() is pw  # the layer's own cache is warm: no further launches
             desc = m.make_desc(1, m._probe_len())
             w3 = m._w3(m.raw_weight.detach())
