@@ -233,6 +233,29 @@ int pwg_conv1d_bf16_forward(const pwg_conv1d_desc* d, const float* x, const void
 int pwg_conv1d_bf16_forward_cfg(const pwg_conv1d_desc* d, const float* x, const void* w_packed, const float* bias,
                                 const float* add1, const float* add2, float* y, int32_t mfma_shape, void* stream);
 
+/* ---- stateful streaming form of the causal convolutions (fp32; csrc/conv1d_stream.hip; ABI v14) ----
+ * The causal layers of the reference -- CausalConv1d.forward, layers/causal_conv.py:32-42 (`self.conv(self.pad(x))
+ * [:, :, :x.size(2)]`), and CausalConvTranspose1d.forward, :68-78 (`self.deconv(self.pad(x))[:, :, self.stride :
+ * -self.stride]`) -- evaluated on one CHUNK of a stream: x (batch, c_in, n) are the n new columns (d->t_in = n), the
+ * columns before them come from hist_in (batch, c_in, H), H = (kernel - 1) * dilation (1 for the transposed form).  The
+ * same launch writes y (batch, c_out, n), or n * stride for the transposed form (d->t_out), and hist_out (batch, c_in, H)
+ * = the last H columns of concat(hist_in, x), also when n < H.  History is the RAW input: pre_act is applied while the
+ * window is staged, to both sources alike.  hist_in == NULL: start of stream, the left context is what pad_mode gives
+ * (zero / reflect, which needs n > H / replicate; the transposed form: replicated first column, or zero).  hist_in and
+ * hist_out must be distinct buffers (ping-pong).  The fused epilogue is pwg_conv1d_forward's; w_packed is the SAME image
+ * (pwg_conv1d_pack_weight).  Covered: groups == 1, width == 1, and either a stride-1 Conv1d with pad_left == (kernel - 1)
+ * * dilation and t_out == t_in, or a ConvTranspose1d with kernel == 2 * stride, pad_left == stride, t_out == t_in *
+ * stride; pwg_conv1d_stream_supported is pure host logic (no device needed; pwg_last_error names the reason for 0).
+ * pwg_conv1d_stream_hist_floats = batch * c_in * H (0 = unsupported, or kernel 1).  Deterministic, and the sum order of
+ * an output element depends neither on n, nor on the batch, nor on the chunk's position: any partition of a stream
+ * gives the same bits -- provided every convolution of the push runs here, so a kernel-1 layer (H == 0; hist_in and
+ * hist_out may be NULL) belongs on this entry point too: pwg_conv1d_forward picks its reduction split from n and batch. */
+int pwg_conv1d_stream_supported(const pwg_conv1d_desc* d);
+size_t pwg_conv1d_stream_hist_floats(const pwg_conv1d_desc* d);
+int pwg_conv1d_stream_forward(const pwg_conv1d_desc* d, const float* x, const float* hist_in, float* hist_out,
+                              const float* w_packed, const float* bias, const float* add1, const float* add2, float* y,
+                              void* stream);
+
 /* Diagnostics (host only, no launch, no device needed): the plan pwg_conv1d_forward derives for a descriptor.
  * has_addends: 1 if add1 / add2 will be passed.  out[8]:
  *   out[0] kernel family: 0 = MFMA implicit-GEMM kernel, 1 = grouped 16x16x4 kernel, 2 = single-input-channel

@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("PWG_KERNEL_LIB") or os.path.join(_HERE, "libpwgkernel
 
 PWG_ACT_NONE, PWG_ACT_LEAKY_RELU, PWG_ACT_TANH, PWG_ACT_RELU = 0, 1, 2, 3
 PWG_PAD_ZERO, PWG_PAD_REFLECT, PWG_PAD_REPLICATE = 0, 1, 2
-ABI_VERSION = 13
+ABI_VERSION = 14
 SPECTRAL_NORM_SCRATCH_FLOATS = 257  # PWG_SPECTRAL_NORM_SCRATCH_FLOATS (include/pwg_kernels.h)
 
 
@@ -139,6 +139,9 @@ SIGNATURES = {
     "pwg_conv1d_bf16_forward": (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t,
                                                _vp]),
     "pwg_conv1d_bf16_forward_cfg": (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "pwg_conv1d_stream_supported": (ctypes.c_int, [ctypes.POINTER(ConvDesc)]),
+    "pwg_conv1d_stream_hist_floats": (ctypes.c_size_t, [ctypes.POINTER(ConvDesc)]),
+    "pwg_conv1d_stream_forward": (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pwg_conv1d_packed_weight_bwd_floats": (ctypes.c_size_t, [ctypes.POINTER(ConvDesc)]),
     "pwg_conv1d_pack_weight_bwd": (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, _vp]),
     "pwg_weight_bank_table_bytes": (ctypes.c_size_t, [_i32]),

@@ -1,0 +1,404 @@
+// conv1d_stream.hip -- stateful (streaming) form of the causal convolutions, fp32 on the exact-fp32 MFMA.
+//
+// A causal stride-1 convolution (left-only padding (k-1)*d, t_out = t_in) needs only its last H = (k-1)*d input columns
+// from the past; the causal k = 2s transposed convolution (polyphase, two taps) needs one.  One launch takes the new chunk
+// x (B, C_in, n) and the history hist_in (B, C_in, H), writes y (B, C_out, n) -- n*s for the transposed form -- and
+// hist_out = the last H columns of concat(hist_in, x), also when n < H (part of hist_in carries over).  hist_in and
+// hist_out are distinct buffers: other workgroups of the launch read hist_in while this one writes hist_out.
+//
+// Numerical definition.  History holds the RAW input; the fused pre-activation is applied while the window is staged,
+// to both sources alike (pad and an element-wise activation commute).  hist_in == NULL is the start of a stream: the
+// left context is synthesised from pad_mode exactly as the whole-utterance kernels pad implicitly (zero; reflect:
+// column -j is x[j]; replicate: x[0]; the transposed form replicates the first column or pads zero).
+//   Y[m][j] = sum_{group, tap, ci in group} W[tap][ci][m] * act(X[ci][j - H + tap * dil])       X[t < 0] = history
+//   Conv1d:          m = output channel, taps = k, dil = dilation
+//   ConvTranspose1d: m = phase * C_out + co, taps = 2 (x[j - 1] with w[phase + s], x[j] with w[phase]), output column
+//                    j * s + phase -- the row order and tap order of the fp32 packed image (csrc/conv1d.hip)
+// The A operand is read straight from that image ([tap][ci pad 16][m pad 128], no second image); the B operand is the
+// window of NT + H columns, staged per 64 input channels into LDS.  A kernel-1 convolution is the case H = 0 (no history
+// buffers): the 1 x 1 layers of a streamed network run here too, because the bit-for-bit rule below holds for a network
+// only if it holds for every one of its convolutions.
+//
+// Contraction: v_mfma_f32_16x16x4_f32 only, whatever the tile.  An output element is the sum of four partial sums,
+// ((p0 + p1) + p2) + p3, where p_w runs over the 16-channel groups g with g % 4 == w in the order (group ascending, tap
+// ascending, 4 channels per MFMA step; an fmaf chain).  That order depends neither on n, nor on the batch, nor on where
+// the chunk sits in the stream, nor on the tile a launch picks: two partitions of the same frames give bit-identical results.  One
+// workgroup owns an output tile over the whole reduction: no split across workgroups, no workspace, no atomics.
+//
+// Tiles: 16 rows x 16 / 32 / 64 columns for chunks of up to 16 / 32 / more columns, 32 x 64 when that still gives every
+// CU two workgroups.  Chunks are short and the layers wide (8 columns x 512 rows at the top of HiFi-GAN V1): a launch is a
+// pass over the layer's weights for a handful of columns, so what counts is how many waves pull weights at once.  The
+// 16-column MFMA wastes half a tile at 8 columns where the 32-column shape would waste three quarters; 16-row blocks
+// give 32 workgroups for 512 rows; and inside a workgroup the four waves split the REDUCTION (each takes every fourth
+// 16-channel group) instead of the rows, with the next four taps' weights in flight while the current ones are contracted.
+// DESIGN.md s11.
+#include "common.h"
+
+namespace pwg {
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int SC = 64;           // input channels staged per LDS block (four 16-channel groups of the image)
+constexpr int kMaxXs = 256;      // LDS row stride limit: SC * kMaxXs * 4 B = 64 KiB
+constexpr int kMaxNt = 64;       // widest column tile
+constexpr int kFillWorkgroups = 256;  // one per CU
+
+// LDS row stride for a window of w columns: >= w and == 16 (mod 64), so that the four channel rows one MFMA step reads
+// (16 lanes each, consecutive columns) fall on four different groups of 16 banks
+static inline int xs_stride(int w) { return round_up(w > 16 ? w - 16 : 0, 64) + 16; }
+
+struct StreamGeom {
+  int taps, dil, hist;  // reduction taps, their spacing, history columns H
+  int m, m_pad, cin_pad;
+  int phases;           // transposed: stride (output column j * phases + phase), else 1
+};
+
+struct StreamArgs {
+  const float* x;
+  const float* hist_in;
+  float* hist_out;
+  const float* w;
+  const float* bias;
+  const float* add1;
+  const float* add2;
+  float* y;
+  int c_in, c_out, n, t_out, hist;
+  int taps, dil, cin_pad, m, m_pad, phases, xs;
+  int step_r, step_w;  // 256 / W and 256 % W for the staged window of W = tile columns + hist columns
+  int pad_mode, pre_act, post_act;
+  float pre_slope, post_slope, out_mul, out_div;
+};
+
+static int stream_geometry(const pwg_conv1d_desc* d, StreamGeom* g) {
+  PWG_REQUIRE(d != nullptr, PWG_ERR_NULL, "conv1d_stream: NULL descriptor");
+  PWG_REQUIRE(d->batch > 0 && d->c_in > 0 && d->c_out > 0 && d->t_in > 0 && d->t_out > 0 && d->kernel > 0 &&
+                  d->stride > 0 && d->dilation > 0 && d->groups > 0 && d->width > 0 && d->pad_left >= 0,
+              PWG_ERR_BAD_SHAPE, "conv1d_stream: non-positive size in descriptor");
+  PWG_REQUIRE(d->groups == 1, PWG_ERR_UNSUPPORTED, "conv1d_stream: groups = %d (only groups == 1)", d->groups);
+  PWG_REQUIRE(d->width == 1, PWG_ERR_UNSUPPORTED, "conv1d_stream: width = %d (only width == 1)", d->width);
+  PWG_REQUIRE(d->pad_mode == PWG_PAD_ZERO || d->pad_mode == PWG_PAD_REFLECT || d->pad_mode == PWG_PAD_REPLICATE,
+              PWG_ERR_UNSUPPORTED, "conv1d_stream: pad_mode = %d", d->pad_mode);
+  PWG_REQUIRE(d->pre_act == PWG_ACT_NONE || d->pre_act == PWG_ACT_LEAKY_RELU || d->pre_act == PWG_ACT_RELU,
+              PWG_ERR_UNSUPPORTED, "conv1d_stream: pre_act = %d", d->pre_act);
+  PWG_REQUIRE(d->post_act >= PWG_ACT_NONE && d->post_act <= PWG_ACT_RELU, PWG_ERR_UNSUPPORTED,
+              "conv1d_stream: post_act = %d", d->post_act);
+  PWG_REQUIRE(d->batch <= 65535, PWG_ERR_UNSUPPORTED, "conv1d_stream: batch = %d (> 65535)", d->batch);
+  if (d->transposed) {
+    PWG_REQUIRE(d->kernel == 2 * d->stride && d->dilation == 1, PWG_ERR_UNSUPPORTED,
+                "conv1d_stream: transposed convolution with kernel = %d, stride = %d, dilation = %d (only kernel == 2 * "
+                "stride, dilation 1)", d->kernel, d->stride, d->dilation);
+    PWG_REQUIRE(d->pad_left == d->stride, PWG_ERR_UNSUPPORTED,
+                "conv1d_stream: transposed convolution with padding = %d (the causal form has padding == stride = %d)",
+                d->pad_left, d->stride);
+    PWG_REQUIRE((long)d->t_out == (long)d->t_in * d->stride, PWG_ERR_BAD_SHAPE,
+                "conv1d_stream: transposed t_out = %d must be t_in * stride = %d * %d", d->t_out, d->t_in, d->stride);
+    PWG_REQUIRE(d->pad_mode != PWG_PAD_REFLECT, PWG_ERR_UNSUPPORTED,
+                "conv1d_stream: the transposed form starts a stream from a replicated or zero column, not a reflected one");
+    g->taps = 2;
+    g->dil = 1;
+    g->hist = 1;
+    g->m = d->c_out * d->stride;
+    g->phases = d->stride;
+  } else {
+    PWG_REQUIRE(d->stride == 1, PWG_ERR_UNSUPPORTED, "conv1d_stream: stride = %d (only stride 1)", d->stride);
+    PWG_REQUIRE((long)d->pad_left == (long)(d->kernel - 1) * d->dilation && d->t_out == d->t_in, PWG_ERR_UNSUPPORTED,
+                "conv1d_stream: not a causal convolution (pad_left = %d, t_in = %d, t_out = %d; needs left-only padding "
+                "(k - 1) * d = %ld and t_out == t_in)", d->pad_left, d->t_in, d->t_out, (long)(d->kernel - 1) * d->dilation);
+    g->taps = d->kernel;
+    g->dil = d->dilation;
+    g->hist = d->pad_left;
+    g->m = d->c_out;
+    g->phases = 1;
+  }
+  PWG_REQUIRE(kMaxNt + g->hist <= kMaxXs - 48, PWG_ERR_UNSUPPORTED,
+              "conv1d_stream: history of %d columns (%d taps, dilation %d) does not fit the LDS window", g->hist, g->taps,
+              g->dil);
+  PWG_REQUIRE(ceil_div(g->m, 16) <= 65535, PWG_ERR_UNSUPPORTED, "conv1d_stream: too many row blocks");
+  g->m_pad = round_up(g->m, 128);   // the fp32 packed image's row extent (csrc/conv1d.hip make_geometry)
+  g->cin_pad = round_up(d->c_in, 16);
+  return PWG_OK;
+}
+
+// One workgroup (4 waves) owns MT = 16 * TM rows x NT = 16 * TN columns.  The reduction is dealt over the four waves:
+// wave w takes the w-th 16-channel group of every staged block of 64 channels, and the four partial tiles are summed
+// through LDS in wave order, ((p0 + p1) + p2) + p3 -- the same in every configuration.
+template <int TM, int TN, bool TRANSPOSED>
+__global__ __launch_bounds__(256) void conv1d_stream_kernel(StreamArgs a) {
+  constexpr int MT = 16 * TM, NT = 16 * TN;
+  extern __shared__ __attribute__((aligned(16))) float xs[];  // [SC][a.xs]; afterwards the partial tiles [4][MT][NT]
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l15 = lane & 15, lq = lane >> 4;
+  const int q0 = blockIdx.x * NT, m0 = blockIdx.y * MT, b = blockIdx.z;
+  const int H = a.hist, n = a.n, XS = a.xs;
+  const int W = NT + H;  // window column w holds stream column q0 - H + w (chunk-relative; < 0: history)
+  const float* __restrict__ xb = a.x + (size_t)b * a.c_in * n;
+  const float* __restrict__ hb = a.hist_in ? a.hist_in + (size_t)b * a.c_in * H : nullptr;
+
+  // ---- hist_out = last H columns of concat(hist_in, x), raw; the elements are dealt over the workgroups of the item
+  {
+    const int total = a.c_in * H;
+    const int wg = blockIdx.y * gridDim.x + blockIdx.x, nwg = gridDim.x * gridDim.y;
+    float* __restrict__ ho = a.hist_out + (size_t)b * a.c_in * H;
+    for (int i = wg * 256 + tid; i < total; i += nwg * 256) {
+      const int ci = i / H, h = i - ci * H;
+      const int t = n - H + h;
+      float v = 0.f;
+      if (t >= 0)
+        v = xb[(size_t)ci * n + t];
+      else if (hb)
+        v = hb[(size_t)ci * H + n + h];
+      else if (a.pad_mode == PWG_PAD_REPLICATE)
+        v = xb[(size_t)ci * n];
+      ho[i] = v;
+    }
+  }
+
+  f32x4 acc[TM][TN];
+#pragma unroll
+  for (int mi = 0; mi < TM; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < TN; ++ni) acc[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  // A operands straight from the packed image: per (16-channel group, tap) 4 MFMA steps x TM row tiles, one float per
+  // lane each (row m0 + mi * 16 + lane % 16, channel group base + 4 * step + lane / 16).  They are fetched in batches
+  // of up to TB taps, the next batch in flight while the current one is contracted (and across the staging of the next
+  // block): a launch is mostly a pass over the weights, few waves are resident, so loads in flight per wave are what
+  // bounds it.
+  constexpr int TB = 4;
+  typedef float abuf_t[TB][4][TM];
+  const float* __restrict__ wlane = a.w + (size_t)(wave * 16 + lq) * a.m_pad + m0 + l15;
+  auto load_batch = [&](abuf_t& av, int c0, int tap0) {
+#pragma unroll
+    for (int u = 0; u < TB; ++u) {
+      if (tap0 + u < a.taps) {
+        const float* __restrict__ wp = wlane + ((size_t)(tap0 + u) * a.cin_pad + c0) * a.m_pad;
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+          for (int mi = 0; mi < TM; ++mi) av[u][kk][mi] = wp[(size_t)kk * 4 * a.m_pad + mi * 16];
+      }
+    }
+  };
+  auto contract = [&](const abuf_t& av, int tap0, const float* xt) {
+#pragma unroll
+    for (int u = 0; u < TB; ++u) {
+      if (tap0 + u < a.taps) {
+        float bv[4][TN];
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+          for (int ni = 0; ni < TN; ++ni) bv[kk][ni] = xt[kk * 4 * XS + (tap0 + u) * a.dil + ni * 16];
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+          for (int mi = 0; mi < TM; ++mi)
+#pragma unroll
+            for (int ni = 0; ni < TN; ++ni)
+              acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u][kk][mi], bv[kk][ni], acc[mi][ni], 0, 0, 0);
+      }
+    }
+  };
+  abuf_t buf0, buf1;
+  int parity = 0;
+  if (wave * 16 < a.cin_pad) load_batch(buf0, 0, 0);
+
+  // window elements come from the history, the chunk or the start-of-stream padding; the pre-activation is applied on
+  // the way into LDS.  The load phase is branch-free: the source address is selected (a safe one where the element is
+  // zero padding or past the chunk) and always loaded, so that the loads of a staging batch are issued back to back
+  const bool replicate = a.pad_mode == PWG_PAD_REPLICATE, reflect = a.pad_mode == PWG_PAD_REFLECT;
+  const bool has_hist = hb != nullptr;
+  const float* hsafe = has_hist ? hb : xb;
+  const int r_first = tid / W, w_first = tid - r_first * W;
+
+  for (int c0 = 0; c0 < a.cin_pad; c0 += SC) {
+    if (c0) __syncthreads();
+    // ---- stage the block's channels (up to SC; none past the image) x W columns, 8 loads in flight per thread.
+    // Element tid + 256 * i is (row, column) = (r, w); stepping by 256 adds (a.step_r, a.step_w) with one carry, so
+    // the only division is the one per thread in front of the block loop
+    const int rows = a.cin_pad - c0 < SC ? a.cin_pad - c0 : SC;
+    for (int r = r_first, w = w_first; r < rows;) {
+      float v[8];
+      bool ok[8];
+      int off[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const bool live = r < rows;
+        off[u] = live ? r * XS + w : -1;
+        const int ci = c0 + r, t = q0 - H + w;
+        const bool in_chunk = t >= 0;
+        const int tt = in_chunk ? t : (reflect ? -t : 0);  // column of x: the chunk's own, the mirrored one, or the first
+        ok[u] = live && ci < a.c_in && (in_chunk ? t < n : (has_hist || replicate || (reflect && tt < n)));
+        const float* src = (!in_chunk && has_hist) ? hsafe + ((size_t)ci * H + H + t) : xb + ((size_t)ci * n + tt);
+        v[u] = *(ok[u] ? src : xb);
+        r += a.step_r;
+        w += a.step_w;
+        if (w >= W) {
+          w -= W;
+          ++r;
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        float f = ok[u] ? v[u] : 0.f;
+        const float neg = a.pre_act == PWG_ACT_LEAKY_RELU ? f * a.pre_slope : (a.pre_act == PWG_ACT_RELU ? 0.f : f);
+        f = f > 0.f ? f : neg;
+        if (off[u] >= 0) xs[off[u]] = f;
+      }
+    }
+    __syncthreads();
+    if (c0 + wave * 16 >= a.cin_pad) continue;  // this wave's group of the block lies past the image (wave-uniform)
+    const bool more_blocks = c0 + SC + wave * 16 < a.cin_pad;
+    const float* xt = xs + (wave * 16 + lq) * XS + l15;
+    for (int tap0 = 0; tap0 < a.taps; tap0 += TB) {
+      const bool in_block = tap0 + TB < a.taps;
+      const bool has_next = in_block || more_blocks;
+      const int nc0 = in_block ? c0 : c0 + SC, ntap0 = in_block ? tap0 + TB : 0;
+      if (parity == 0) {
+        if (has_next) load_batch(buf1, nc0, ntap0);
+        contract(buf0, tap0, xt);
+      } else {
+        if (has_next) load_batch(buf0, nc0, ntap0);
+        contract(buf1, tap0, xt);
+      }
+      parity ^= 1;
+    }
+  }
+
+  // ---- the four waves' partial tiles through LDS (D layout of the 16 x 16 x 4 form: column = lane % 16,
+  // row = 4 * (lane / 16) + register); every wave writes its tile, zeros where it had no channel group
+  __syncthreads();
+  float* red = xs;  // [4][MT][NT + 1]
+  constexpr int RS = NT + 1;
+#pragma unroll
+  for (int mi = 0; mi < TM; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < TN; ++ni)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) red[(wave * MT + mi * 16 + 4 * lq + i) * RS + ni * 16 + l15] = acc[mi][ni][i];
+  __syncthreads();
+
+  // ---- epilogue: one thread per output element, partial sums added in wave order
+  for (int e = tid; e < MT * NT; e += 256) {
+    const int row = e / NT, col = e - row * NT;
+    const int m = m0 + row, j = q0 + col;
+    if (m >= a.m || j >= n) continue;
+    float v = red[row * RS + col];
+    v += red[(MT + row) * RS + col];
+    v += red[(2 * MT + row) * RS + col];
+    v += red[(3 * MT + row) * RS + col];
+    int co = m, ph = 0;
+    if (TRANSPOSED) {
+      ph = m / a.c_out;
+      co = m - ph * a.c_out;
+    }
+    const size_t o = ((size_t)b * a.c_out + co) * a.t_out + (TRANSPOSED ? j * a.phases + ph : j);
+    if (a.bias) v += a.bias[co];
+    if (a.add1) v += a.add1[o];
+    if (a.add2) v += a.add2[o];
+    if (a.out_mul != 1.0f) v *= a.out_mul;
+    if (a.out_div != 1.0f) v = v / a.out_div;
+    v = apply_act(v, a.post_act, a.post_slope);
+    a.y[o] = v;
+  }
+}
+
+template <int TM, int TN>
+static void launch_tile(const StreamArgs& a, bool transposed, dim3 grid, size_t lds, hipStream_t stream) {
+  if (transposed)
+    hipLaunchKernelGGL((conv1d_stream_kernel<TM, TN, true>), grid, dim3(256), lds, stream, a);
+  else
+    hipLaunchKernelGGL((conv1d_stream_kernel<TM, TN, false>), grid, dim3(256), lds, stream, a);
+}
+
+}  // namespace
+}  // namespace pwg
+
+using namespace pwg;
+
+extern "C" int pwg_conv1d_stream_supported(const pwg_conv1d_desc* d) {
+  StreamGeom g;
+  return stream_geometry(d, &g) == PWG_OK ? 1 : 0;
+}
+
+extern "C" size_t pwg_conv1d_stream_hist_floats(const pwg_conv1d_desc* d) {
+  StreamGeom g;
+  if (stream_geometry(d, &g) != PWG_OK) return 0;
+  return (size_t)d->batch * d->c_in * g.hist;
+}
+
+extern "C" int pwg_conv1d_stream_forward(const pwg_conv1d_desc* d, const float* x, const float* hist_in, float* hist_out,
+                                         const float* w_packed, const float* bias, const float* add1, const float* add2,
+                                         float* y, void* stream_) {
+  StreamGeom g;
+  int rc = stream_geometry(d, &g);
+  if (rc != PWG_OK) return rc;
+  hipStream_t stream = (hipStream_t)stream_;
+  PWG_REQUIRE(x && w_packed && y, PWG_ERR_NULL, "conv1d_stream: NULL pointer");
+  PWG_REQUIRE(hist_out || g.hist == 0, PWG_ERR_NULL, "conv1d_stream: hist_out is NULL (the layer keeps %d columns)", g.hist);
+  PWG_REQUIRE(g.hist == 0 || hist_in != hist_out, PWG_ERR_BAD_SHAPE,
+              "conv1d_stream: hist_in and hist_out must be distinct buffers (other workgroups read the history)");
+  PWG_REQUIRE(hist_in || d->pad_mode != PWG_PAD_REFLECT || d->t_in > g.hist, PWG_ERR_BAD_SHAPE,
+              "conv1d_stream: a reflect-padded stream starts with at least %d columns (got %d)", g.hist + 1, d->t_in);
+  PWG_REQUIRE((reinterpret_cast<uintptr_t>(w_packed) & 3u) == 0, PWG_ERR_BAD_SHAPE, "conv1d_stream: unaligned weight image");
+  const int n = d->t_in;
+  const int tn = n <= 16 ? 1 : (n <= 32 ? 2 : 4);
+  const int nt = 16 * tn;
+  const int col_tiles = ceil_div(n, nt);
+  // 32-row blocks only when they still give every CU two workgroups (the order of an element's sum is the same)
+  const int tm = (tn == 4 && (long)ceil_div(g.m, 32) * col_tiles * d->batch >= 2 * kFillWorkgroups) ? 2 : 1;
+  const int xs = xs_stride(nt + g.hist);
+  const size_t red = (size_t)4 * (16 * tm) * (nt + 1) * sizeof(float);  // the partial tiles reuse the window's LDS
+  const size_t lds = (size_t)SC * xs * sizeof(float) > red ? (size_t)SC * xs * sizeof(float) : red;
+
+  StreamArgs a;
+  a.x = x;
+  a.hist_in = g.hist ? hist_in : nullptr;
+  a.hist_out = hist_out;
+  a.w = w_packed;
+  a.bias = bias;
+  a.add1 = add1;
+  a.add2 = add2;
+  a.y = y;
+  a.c_in = d->c_in;
+  a.c_out = d->c_out;
+  a.n = n;
+  a.t_out = d->t_out;
+  a.hist = g.hist;
+  a.taps = g.taps;
+  a.dil = g.dil;
+  a.cin_pad = g.cin_pad;
+  a.m = g.m;
+  a.m_pad = g.m_pad;
+  a.phases = g.phases;
+  a.xs = xs;
+  a.step_r = 256 / (nt + g.hist);
+  a.step_w = 256 % (nt + g.hist);
+  a.pad_mode = d->pad_mode;
+  a.pre_act = d->pre_act;
+  a.post_act = d->post_act;
+  a.pre_slope = d->pre_slope;
+  a.post_slope = d->post_slope;
+  a.out_mul = d->out_mul;
+  a.out_div = d->out_div;
+
+  const dim3 grid(col_tiles, ceil_div(g.m, 16 * tm), d->batch);
+  const double out_elems = (double)d->batch * d->c_out * d->t_out;
+  const double flops = 2.0 * (double)d->batch * g.m * n * g.taps * d->c_in;
+  const double bytes = 4.0 * ((double)d->batch * d->c_in * (n + 2.0 * g.hist) +
+                              out_elems * (1 + (add1 ? 1 : 0) + (add2 ? 1 : 0)) + (double)g.taps * g.cin_pad * g.m_pad);
+  maybe_poison_lds(stream);
+  ProfScope prof(stream, "conv1d_stream_kernel", flops, bytes);
+  if (tn == 1)
+    launch_tile<1, 1>(a, d->transposed != 0, grid, lds, stream);
+  else if (tn == 2)
+    launch_tile<1, 2>(a, d->transposed != 0, grid, lds, stream);
+  else if (tm == 1)
+    launch_tile<1, 4>(a, d->transposed != 0, grid, lds, stream);
+  else
+    launch_tile<2, 4>(a, d->transposed != 0, grid, lds, stream);
+  PWG_CHECK_LAUNCH("conv1d_stream");
+  return PWG_OK;
+}

@@ -10,6 +10,7 @@ got one replicated sample on the left.
 import torch
 
 from .. import functional as Fn
+from .. import ops
 from .conv import Conv1d, ConvTranspose1d
 from .padding import get_pad
 
@@ -29,6 +30,27 @@ class CausalConv1d(torch.nn.Module):
         """Accepts the fused-epilogue keywords of :class:`Conv1d` (pre_act, add1, post_act, ...)."""
         return self.conv(x, **fused)
 
+    def stream_desc(self, batch, n, **fused):
+        """Descriptor of one push of ``n`` columns through the streaming kernel (csrc/conv1d_stream.hip)."""
+        cv = self.conv
+        return ops.make_conv_desc(batch, cv.in_channels, cv.out_channels, n, n, cv.kernel_size, 1, cv.dilation, cv.padding,
+                                  cv.groups, transposed=False, pad_mode=cv.pad_mode, **fused)
+
+    def history_shape(self, batch):
+        """Shape of one history buffer: the last ``(k - 1) * d`` raw input columns (allocate two: ping-pong)."""
+        return (batch, self.conv.in_channels, self.conv.padding)
+
+    def history_columns_at_start(self):
+        """Input columns the first push needs: reflect padding mirrors the first ``(k - 1) * d + 1`` of them."""
+        return self.conv.padding + 1 if self.conv.pad_mode == "reflect" and self.conv.padding > 0 else 1
+
+    def stream_forward(self, x, hist_in, hist_out, **fused):
+        """The next ``x.shape[-1]`` columns of a stream whose previous columns are ``hist_in`` (None: start of stream,
+        the layer's own padding); also writes ``hist_out`` (a buffer distinct from ``hist_in``).  One launch; the
+        fused-epilogue keywords and the weight image are those of ``forward``."""
+        return _stream_forward(self.conv, self.stream_desc(x.shape[0], x.shape[-1], **_desc_kw(fused)), x, hist_in,
+                               hist_out, fused)
+
 
 class CausalConvTranspose1d(torch.nn.Module):
     """``deconv(replicate_pad_left(x, 1))[:, :, stride:-stride]`` (causal_conv.py:46-77)."""
@@ -46,3 +68,51 @@ class CausalConvTranspose1d(torch.nn.Module):
     def forward(self, x, **fused):
         # the left pad and an element-wise pre-activation commute, so the activation stays fused
         return self.deconv(Fn.pad1d(x, 1, 0, self.pad.mode), **fused)
+
+    def stream_desc(self, batch, n, **fused):
+        """Descriptor of one push of ``n`` columns (``n * stride`` out) through the streaming kernel."""
+        cv = self.deconv
+        return ops.make_conv_desc(batch, cv.in_channels, cv.out_channels, n, n * self.stride, cv.kernel_size, self.stride, 1,
+                                  cv.padding, cv.groups, transposed=True, pad_mode=self.pad.mode, **fused)
+
+    def history_shape(self, batch):
+        """Shape of one history buffer: the previous raw input column (allocate two: ping-pong)."""
+        return (batch, self.deconv.in_channels, 1)
+
+    def history_columns_at_start(self):
+        return 1
+
+    def stream_forward(self, x, hist_in, hist_out, **fused):
+        """As :meth:`CausalConv1d.stream_forward`; the start-of-stream context is the replicated first column."""
+        return _stream_forward(self.deconv, self.stream_desc(x.shape[0], x.shape[-1], **_desc_kw(fused)), x, hist_in,
+                               hist_out, fused)
+
+
+def stream_pointwise(cv, x, **fused):
+    """A 1 x 1 ``Conv1d`` on the next columns of a stream, through the streaming kernel with no history (``H = 0``):
+    its sum order does not depend on the column count or the batch, which the general kernel's choice of tile and
+    reduction split does."""
+    if cv.kernel_size != 1 or cv.padding != 0 or cv.padding_right != 0:
+        raise ValueError("stream_pointwise: not an unpadded 1 x 1 convolution")
+    n = x.shape[-1]
+    desc = ops.make_conv_desc(x.shape[0], cv.in_channels, cv.out_channels, n, n, 1, cv.stride, 1, 0, cv.groups,
+                              transposed=False, pad_mode="zero", **_desc_kw(fused))
+    return _stream_forward(cv, desc, x, None, None, fused)
+
+
+def _desc_kw(fused):
+    return {k: v for k, v in fused.items() if k not in ("add1", "add2")}
+
+
+def _stream_forward(cv, desc, x, hist_in, hist_out, fused):
+    if cv.precision != "fp32":
+        raise RuntimeError(f"{cv.__class__.__name__} is in {cv.precision} inference precision: the streaming kernel is fp32")
+    if not ops.conv1d_stream_supported(desc):
+        from .. import _lib
+
+        raise RuntimeError("the streaming kernel does not cover this layer: "
+                           + _lib.lib().pwg_last_error().decode(errors="replace"))
+    with torch.no_grad():
+        return ops.conv1d_stream_forward(desc, x.contiguous(), hist_in, hist_out, cv.packed_weight(),
+                                         None if cv.bias is None else cv.bias.detach(), fused.get("add1"),
+                                         fused.get("add2"))

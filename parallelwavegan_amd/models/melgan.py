@@ -111,6 +111,53 @@ class MelGANGenerator(torch.nn.Module, _MelGANNormMixin):
                 act = None
         return x
 
+    def _stream_walk(self):
+        """``(index, module, pending activation, rate)`` of the modules that compute, in ``forward`` order."""
+        act, rate = None, 1
+        for i, m in enumerate(self.melgan):
+            if isinstance(m, FusedActivation):
+                act = m
+            elif isinstance(m, (FusedPad, torch.nn.Identity)):
+                continue
+            elif isinstance(m, ResidualStack):
+                yield i, m, None, rate
+            else:
+                yield i, m, act, rate
+                act = None
+                if isinstance(m, CausalConvTranspose1d):
+                    rate *= m.stride
+
+    def stream_layers(self):
+        """``(layer, rate)`` of every causal convolution that keeps history, in the order :meth:`stream_forward` visits
+        them; ``rate``: the layer's input columns per mel frame."""
+        if not isinstance(self.melgan[0], CausalConv1d):
+            raise ValueError("MelGANGenerator: streaming needs use_causal_conv=True")
+        out = []
+        for _, m, _, rate in self._stream_walk():
+            out += [(cv, rate) for cv in (m.stream_layers() if isinstance(m, ResidualStack) else [m])]
+        return out
+
+    @torch.no_grad()
+    def stream_forward(self, c, hist_in, hist_out):
+        """The causal ``forward`` on the next chunk ``c`` (B, in_channels, n) of a stream -> (B, out_channels, n *
+        upsample_factor): the same modules in the same order with the same fused epilogues.  ``hist_in`` / ``hist_out``:
+        one history tensor per layer of :meth:`stream_layers` (``hist_in`` None: start of stream, which for the
+        reflect-padded layers needs ``utils.CausalStream.warmup_frames`` frames); see :class:`utils.CausalStream`."""
+        layers = self.stream_layers()
+        hist = iter(zip(hist_in if hist_in is not None else [None] * len(layers), hist_out))
+        walk = list(self._stream_walk())
+        last_conv = max(i for i, m, _, _ in walk if isinstance(m, CausalConv1d))
+        x = c
+        for i, m, act, _ in walk:
+            if isinstance(m, ResidualStack):
+                x = m.stream_forward(x, hist)
+                continue
+            kw = dict(pre_act=act.kind, pre_slope=act.slope) if act is not None else {}
+            if i == last_conv and self.use_final_nonlinear_activation:
+                kw["post_act"] = "tanh"
+            x = m.stream_forward(x, *next(hist), **kw)
+        return x
+
     def register_stats(self, stats):
         from ..utils import load_stats
 

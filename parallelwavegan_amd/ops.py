@@ -247,6 +247,38 @@ def conv1d_forward_bf16(desc, x, w_packed, bias=None, add1=None, add2=None, out=
     return out
 
 
+def conv1d_stream_supported(desc):
+    """Does the streaming kernel (csrc/conv1d_stream.hip) cover this descriptor -- a causal stride-1 convolution or the
+    causal k = 2s transposed convolution, ``desc.t_in`` = columns per push?  Host logic only (no device needed);
+    ``_lib.lib().pwg_last_error()`` names the reason for a False."""
+    return bool(_lib.lib().pwg_conv1d_stream_supported(ctypes.byref(desc)))
+
+
+def conv1d_stream_hist_floats(desc):
+    """Floats of one history buffer of the layer: ``batch * c_in * H`` (0: unsupported, or a layer without history)."""
+    return _lib.lib().pwg_conv1d_stream_hist_floats(ctypes.byref(desc))
+
+
+def conv1d_stream_forward(desc, x, hist_in, hist_out, w_packed, bias=None, add1=None, add2=None, out=None):
+    """One chunk of a causal convolution's stream: ``out`` from the ``desc.t_in`` new columns ``x`` and the history
+    ``hist_in`` (None: start of stream), and ``hist_out`` = the last H columns of ``concat(hist_in, x)``, in one
+    launch.  ``hist_in`` and ``hist_out`` must be distinct buffers."""
+    _require_device(x, hist_in, hist_out, w_packed, bias, add1, add2, out)
+    if out is None:
+        out = torch.empty((desc.batch, desc.c_out, desc.t_out), device=x.device, dtype=torch.float32)
+    assert x.numel() == desc.batch * desc.c_in * desc.t_in, (tuple(x.shape), desc.batch, desc.c_in, desc.t_in)
+    assert out.numel() == desc.batch * desc.c_out * desc.t_out
+    n_hist = conv1d_stream_hist_floats(desc)
+    for t in (hist_in, hist_out):
+        assert t is None or t.numel() == n_hist, (tuple(t.shape), n_hist)
+    for t in (add1, add2):
+        assert t is None or t.numel() == out.numel()
+    _lib.check(_lib.lib().pwg_conv1d_stream_forward(ctypes.byref(desc), _ptr(x), _ptr(hist_in), _ptr(hist_out),
+                                                    _ptr(w_packed), _ptr(bias), _ptr(add1), _ptr(add2), _ptr(out),
+                                                    _stream()), "conv1d_stream_forward")
+    return out
+
+
 def make_resunit_desc(batch, channels, t, kernel, dilation, has_conv2=True, slope1=0.1, slope2=0.1, out_div=1.0):
     return ResUnitDesc(int(batch), int(channels), int(t), int(kernel), int(dilation), int(bool(has_conv2)),
                        float(slope1), float(slope2), float(out_div))

@@ -15,6 +15,11 @@ run without a halo there (they are batched across utterances when their lengths 
 
 Everything on the device runs in libpwgkernels.so: feature normalisation + (T', C) -> (C, T')
 transpose, the generator, and the float -> PCM16 conversion.
+
+``CausalStream`` is the other regime: synthesis WHILE the mel frames arrive, for generators built with
+``use_causal_conv=True``.  Every causal layer keeps the last ``(k-1)*d`` columns of its raw input (one column for a
+transposed layer) on the device, so a push of ``n`` frames costs ``n`` frames of work with zero look-ahead
+(csrc/conv1d_stream.hip).
 """
 import ctypes
 
@@ -22,7 +27,7 @@ import torch
 
 from .. import _lib
 from ..graphs import GraphedInference
-from ..ops import _ptr, _require_device, _stream
+from ..ops import _ptr, _require_device, _stream, conv1d_stream_supported
 
 
 def normalize_transpose(c, mean=None, scale=None):
@@ -134,3 +139,182 @@ class ChunkedSynthesizer:
     def synthesize(self, feat, normalize_before=False):
         """(T', C) -> (T' * upsample_factor,)"""
         return self.synthesize_many([feat], normalize_before)[0]
+
+
+class CausalStream:
+    """Stateful streaming synthesis for ``HiFiGANGenerator`` and full-band ``MelGANGenerator`` built with
+    ``use_causal_conv=True``: ``push`` takes the next mel frames of ``batch`` lock-step streams and returns their
+    samples; any partition of the same frames gives bit-identical audio, equal to the whole-utterance ``forward`` up to
+    fp32 summation order.
+
+    State: per causal layer two history tensors (ping-pong: a push reads one half and writes the other, in the layer's
+    own launch).  ``use_graph``: steady-state pushes of one chunk size replay two captured graphs (A -> B, B -> A);
+    the first push of a stream (the layers' own start-of-stream padding) runs eagerly.  Graphs are dropped when the
+    model's parameter state (``GraphedInference._param_state``) changes, so a replay never uses old weights.
+    Graph mode wants a fixed chunk size: the first push of a new size captures inside ``push`` (four warm-up runs and
+    two captures), each captured size holds a private pool of all activations, and only the ``max_graph_shapes`` most
+    recently used sizes are kept.  A stream whose chunk size varies freely should pass ``use_graph=False``.
+
+    Reflect-padded models (causal MelGAN) need the first ``warmup_frames`` frames before anything can be emitted -- an
+    utterance shorter than that is one the whole-utterance forward cannot pad either: the stream holds what is pushed
+    until then, returning zero-length waveforms, and ``close()`` raises if frames are still held.
+    """
+
+    max_graph_shapes = 4  # chunk sizes whose graphs are kept (least recently used evicted)
+
+    def __init__(self, model, batch=1, use_graph=True, normalize_before=False):
+        from ..layers.conv import each_conv
+        from ..models import HiFiGANGenerator, MelGANGenerator
+
+        if not isinstance(model, (HiFiGANGenerator, MelGANGenerator)):
+            raise ValueError(f"CausalStream: {model.__class__.__name__} is not supported (only the causal HiFiGANGenerator "
+                             "and full-band MelGANGenerator map mel frames to samples layer by layer)")
+        self._layers = model.stream_layers()  # ValueError for a non-causal model
+        out_channels = model.output_conv[1].conv.out_channels if isinstance(model, HiFiGANGenerator) else \
+            self._layers[-1][0].conv.out_channels
+        if out_channels != 1 or getattr(model, "pqmf", None) is not None:
+            raise ValueError(f"CausalStream: the generator emits {out_channels} sub-bands; PQMF synthesis is a symmetric "
+                             "FIR (it looks ahead), so multi-band models cannot be streamed causally")
+        if any(cv.precision != "fp32" for cv in each_conv(model)):
+            raise ValueError("CausalStream: the model is in bf16 inference precision; the streaming kernel is fp32 "
+                             "(utils.set_inference_precision(model, 'fp32'))")
+        batch = int(batch)
+        if batch < 1:
+            raise ValueError("CausalStream: batch must be >= 1")
+        for layer, _ in self._layers:
+            if not conv1d_stream_supported(layer.stream_desc(batch, 8)):
+                raise ValueError(f"CausalStream: {layer} cannot be streamed: "
+                                 + _lib.lib().pwg_last_error().decode(errors="replace"))
+        _require_device(next(model.parameters()))  # no CPU fallback
+        if normalize_before and not (hasattr(model, "mean") and hasattr(model, "scale")):
+            raise ValueError("CausalStream: normalize_before=True needs model.register_stats(...)")
+        self.model = model.eval()
+        self.batch = batch
+        self.use_graph = bool(use_graph)
+        self.normalize_before = bool(normalize_before)
+        self.up = model.upsample_factor
+        self.warmup_frames = self.required_warmup_frames(model)
+        dev = next(model.parameters()).device
+        self._halves = [[torch.zeros(layer.history_shape(batch), device=dev) for layer, _ in self._layers]
+                        for _ in range(2)]
+        self._watch = GraphedInference(model)  # (only its parameter-state key is used)
+        self._state = None
+        self._graphs = {}
+        self.reset()
+
+    @staticmethod
+    def required_warmup_frames(model):
+        """Frames the first emission needs, from the layer geometry alone (no device, no kernel): the maximum over
+        the causal layers of ``ceil(columns the layer's start-of-stream padding reads / the layer's columns per
+        frame)`` -- 1 for zero-padded models."""
+        return max(-(-layer.history_columns_at_start() // rate) for layer, rate in model.stream_layers())
+
+    @property
+    def state_bytes(self):
+        """Bytes of history held on the device (both ping-pong halves)."""
+        return sum(t.numel() * t.element_size() for half in self._halves for t in half)
+
+    def reset(self):
+        """Back to start of stream: the next push starts from the layers' own padding.  Held frames are dropped."""
+        self._cur = 0          # which half holds the current history
+        self._started = False  # False: the next run passes hist_in = None
+        self._held = []
+        self.frames_in = 0
+        self.frames_out = 0
+
+    def _run(self, feats, hist_in, hist_out):
+        mean = self.model.mean if self.normalize_before else None
+        scale = self.model.scale if self.normalize_before else None
+        return self.model.stream_forward(normalize_transpose(feats, mean, scale), hist_in, hist_out)
+
+    def _capture(self, feats):
+        """Graphs for both directions of one chunk shape.  The warm-up runs write history: both halves are saved and
+        put back, so capturing never advances the stream."""
+        saved = [[t.clone() for t in half] for half in self._halves]
+        static_in = feats.clone()
+        out = {}
+        for cur in (0, 1):
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                for _ in range(2):  # fills the weight caches / sets kernel attributes outside the capture
+                    self._run(static_in, self._halves[cur], self._halves[1 - cur])
+            torch.cuda.current_stream().wait_stream(side)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                static_out = self._run(static_in, self._halves[cur], self._halves[1 - cur])
+            out[cur] = (g, static_out)
+        for half, keep in zip(self._halves, saved):
+            for t, k in zip(half, keep):
+                t.copy_(k)
+        return static_in, out
+
+    @torch.no_grad()
+    def push(self, feats):
+        """feats: (n, C) or (batch, n, C) float features -> (batch, m * upsample_factor) fp32 samples, ``m`` the frames
+        emitted by this push (``n``, except around the warm-up of a reflect-padded model).  The result is the caller's
+        own tensor (not a graph's static buffer)."""
+        dev = self._halves[0][0].device
+        feats = torch.as_tensor(feats, dtype=torch.float32).to(dev)
+        if feats.dim() == 2:
+            feats = feats.unsqueeze(0)
+        if feats.dim() != 3 or feats.shape[0] != self.batch:
+            raise ValueError(f"CausalStream.push: expected (n, C) or ({self.batch}, n, C) features, got {tuple(feats.shape)}")
+        self.frames_in += feats.shape[1]
+        if not self._started:
+            self._held.append(feats)
+            if sum(f.shape[1] for f in self._held) < self.warmup_frames:
+                return torch.empty((self.batch, 0), device=dev, dtype=torch.float32)
+            feats = torch.cat(self._held, 1) if len(self._held) > 1 else feats
+            self._held = []
+        feats = feats.contiguous()
+        n = feats.shape[1]
+        if n == 0:
+            return torch.empty((self.batch, 0), device=dev, dtype=torch.float32)
+        if not self._started:
+            # start of stream: the layers' own padding; once per utterance, eager
+            y = self._run(feats, None, self._halves[0])
+            self._cur, self._started = 0, True
+        else:
+            hist_in, hist_out = self._halves[self._cur], self._halves[1 - self._cur]
+            if self.use_graph:
+                state = self._watch._param_state()
+                if state != self._state:
+                    self._graphs, self._state = {}, state
+                key = (n, feats.shape[2])
+                entry = self._graphs.pop(key, None)
+                if entry is None:
+                    while len(self._graphs) >= self.max_graph_shapes:
+                        del self._graphs[next(iter(self._graphs))]  # least recently used chunk shape
+                    entry = self._capture(feats)
+                self._graphs[key] = entry  # most recently used last
+                static_in, graphs = entry
+                g, static_out = graphs[self._cur]
+                static_in.copy_(feats, non_blocking=True)
+                g.replay()
+                y = static_out.clone()
+            else:
+                y = self._run(feats, hist_in, hist_out)
+            self._cur = 1 - self._cur
+        self.frames_out += n
+        return y.reshape(self.batch, n * self.up)
+
+    def push_pcm16(self, feats):
+        """``push`` through the float -> PCM16 conversion: (batch, m * upsample_factor) int16."""
+        return to_pcm16(self.push(feats))
+
+    def close(self):
+        """End of the utterance: raises if frames are still held (the utterance was shorter than ``warmup_frames``,
+        which the whole-utterance forward cannot pad either)."""
+        held = sum(f.shape[1] for f in self._held)
+        if held:
+            raise RuntimeError(f"CausalStream: {held} frame(s) were pushed but the reflect-padded start of this model "
+                               f"needs {self.warmup_frames} before the first sample can be emitted")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            self.close()
+        return False

@@ -1,0 +1,137 @@
+"""Stateful streaming synthesis (utils.CausalStream) against the halo-recompute path, in ONE process: causal HiFi-GAN at
+the V1 geometry, chunks of 4 / 8 / 32 frames, 1 and 16 concurrent streams.
+
+A causal MelGAN at the recipe's geometry is measured at 8 frames as well.  For every combination a steady-state ``CausalStream.push`` of n frames (hipGraph replay, history kept per layer on the
+device) alternates with what exists without it: one ``GraphedInference`` forward over ``left + n`` frames, ``left`` from
+``receptive_field_frames`` -- what ``ChunkedSynthesizer`` runs for an interior chunk.  (The halo side is timed WITHOUT the
+feature transposition and without copying the result out, both of which ``push`` includes: the comparison leans towards
+the halo path.)  Device events around ``--reps`` calls after warm-up, three alternating repeats to show the spread;
+launches per call counted through pwg_prof_* on one eager run of each.  GPU box only.
+
+usage: python tools/bench_stream.py [--reps 200] [--repeats 3] [--out profiles/stream_infer.json]
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch  # noqa: E402
+
+from parallelwavegan_amd import ops  # noqa: E402
+from parallelwavegan_amd.graphs import GraphedInference  # noqa: E402
+from parallelwavegan_amd.models import HiFiGANGenerator, MelGANGenerator  # noqa: E402
+from parallelwavegan_amd.utils import CausalStream  # noqa: E402
+from parallelwavegan_amd.utils.streaming import receptive_field_frames  # noqa: E402
+from tests.golden import synth  # noqa: E402
+
+CHUNKS = (4, 8, 32)
+STREAMS = (1, 16)
+MELGAN_CHUNKS = (8,)  # a second family at one chunk size: its 1 x 1 layers run on the stream kernel too
+MELGAN_RECIPE_CAUSAL = dict(in_channels=80, out_channels=1, kernel_size=7, channels=512, upsample_scales=[8, 8, 2, 2],
+                            stack_kernel_size=3, stacks=3, use_causal_conv=True)
+
+
+def build_model(dev):
+    """Causal HiFi-GAN V1 on seeded weights: the recipe of tests/util.py::synth_for, weight norm removed."""
+    g = HiFiGANGenerator(**dict(synth.HIFIGAN_V1, use_causal_conv=True))
+    g.load_state_dict(synth.synth_state_dict(g.state_dict(), seed=11, g_scale=1.25))
+    g.remove_weight_norm()
+    return g.to(dev).eval()
+
+
+def build_melgan(dev):
+    """Causal MelGAN at the recipe's geometry on seeded weights, weight norm removed."""
+    g = MelGANGenerator(**MELGAN_RECIPE_CAUSAL)
+    g.load_state_dict(synth.synth_state_dict(g.state_dict(), seed=12, g_scale=synth.MELGAN_G_SCALE))
+    g.remove_weight_norm()
+    return g.to(dev).eval()
+
+
+def event_ms(fn, reps):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def launches(fn):
+    """Kernel launches of one eager call, per kernel family (pwg_prof_*)."""
+    with torch.no_grad():
+        fn()
+        with ops.profile() as prof:
+            fn()
+    fam = {k: v["launches"] for k, v in prof.results.items()}
+    return sum(fam.values()), fam
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=200)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "stream_infer.json"))
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    rec = {"tool": "tools/bench_stream.py", "device": torch.cuda.get_device_name(0), "reps": args.reps,
+           "repeats": args.repeats, "models": {}, "points": []}
+    gen = torch.Generator(device="cpu").manual_seed(100)
+    for name, model, chunks in (("hifigan_v1_causal", build_model(dev), CHUNKS),
+                                ("melgan_recipe_causal", build_melgan(dev), MELGAN_CHUNKS)):
+        measure(rec, name, model, chunks, gen, args, dev)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(rec, f, indent=1)
+        f.write("\n")
+    print(json.dumps({"out": args.out, "points": [[p["model"], p["streams"], p["chunk_frames"], p["stream_push_ms"],
+                                                   p["halo_forward_ms"]] for p in rec["points"]]}))
+
+
+def measure(rec, name, model, chunks, gen, args, dev):
+    left, right = receptive_field_frames(model)
+    assert right == 0, "a causal generator has no look-ahead"
+    up = model.upsample_factor
+    rec["models"][name] = {"workload": "seeded weights, weight norm removed", "halo_left_frames": left,
+                           "stream_state_bytes_per_stream": CausalStream(model, use_graph=False).state_bytes}
+    for b in STREAMS:
+        for n in chunks:
+            feats = torch.randn(b, n, 80, generator=gen).to(dev)
+            ctx = torch.randn(b, 80, left + n, generator=gen).to(dev)
+            s = CausalStream(model, batch=b, use_graph=True)
+            halo = GraphedInference(model)
+            for _ in range(6):  # start of stream, both graph directions, and the halo graph
+                s.push(feats)
+                halo(ctx)
+            t_s, t_h = [], []
+            for _ in range(args.repeats):
+                t_s.append(event_ms(lambda: s.push(feats), args.reps))
+                t_h.append(event_ms(lambda: halo(ctx), args.reps))
+            eager = CausalStream(model, batch=b, use_graph=False)
+            while eager.frames_out == 0:  # past the start of the stream (and a reflect-padded model's warm-up)
+                eager.push(feats)
+            n_s, fam_s = launches(lambda: eager.push(feats))
+            n_h, fam_h = launches(lambda: model(ctx))
+            med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+            spread = max(max(t_s) - min(t_s), max(t_h) - min(t_h))
+            p = {"model": name, "streams": b, "chunk_frames": n, "samples_per_push": b * n * up,
+                 "stream_push_ms": round(med(t_s), 4), "stream_runs_ms": [round(t, 4) for t in t_s],
+                 "halo_forward_ms": round(med(t_h), 4), "halo_runs_ms": [round(t, 4) for t in t_h],
+                 "halo_frames_computed": left + n, "arithmetic_ratio_halo_over_stream": round((left + n) / n, 2),
+                 "spread_ms": round(spread, 4), "speedup_stream_over_halo": round(med(t_h) / med(t_s), 3),
+                 "stream_not_slower_beyond_spread": med(t_s) <= med(t_h) + spread,
+                 "stream_faster_beyond_spread": med(t_s) + spread < med(t_h),
+                 "real_time_factor_22050Hz": round(n * up / 22050.0 / (med(t_s) / 1e3), 1),
+                 "launches_per_push_stream": n_s, "launches_per_forward_halo": n_h,
+                 "stream_kernels": fam_s, "halo_kernels": fam_h}
+            rec["points"].append(p)
+            print(json.dumps({k: p[k] for k in ("model", "streams", "chunk_frames", "stream_push_ms", "halo_forward_ms",
+                                                "spread_ms", "speedup_stream_over_halo", "launches_per_push_stream",
+                                                "launches_per_forward_halo")}), file=sys.stderr, flush=True)
+
+
+if __name__ == "__main__":
+    main()
