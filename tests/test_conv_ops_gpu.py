@@ -237,7 +237,23 @@ def test_split_reduction_forward_backward(B, Cin, Cout, T, K, stride, pad, group
     _close(dx, x.grad + acc, "split backward_data")
 
 
-@pytest.mark.parametrize("cin,cout,t,k,dil,pre,post,kernel", [
+def _off4(t):
+    """A device copy of ``t`` that starts 4 bytes past a 16-byte boundary (what a view into a larger buffer can be)."""
+    buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=t.device)
+    v = buf[1:].view(t.shape)
+    v.copy_(t)
+    assert v.data_ptr() % 16 == 4
+    return v
+
+
+def _with_misaligned(cases, extra):
+    """parametrize list: ``cases`` (aligned tensors, ids as without the extra argument) + ``extra`` cases whose last
+    element names the tensors that start 4 bytes off a 16-byte boundary."""
+    return ([pytest.param(*c, None, id="-".join(map(str, c))) for c in cases] +
+            [pytest.param(*c, id="-".join(map(str, c[:-1])) + "-misaligned_" + c[-1]) for c in extra])
+
+
+@pytest.mark.parametrize("cin,cout,t,k,dil,pre,post,kernel,misaligned", _with_misaligned([
     (32, 1, 5000, 7, 1, "leaky_relu", "tanh", "conv1d_small_cout_stream_kernel"),   # HiFi-GAN / MelGAN output layer
     (48, 4, 9000, 7, 2, "leaky_relu", None, "conv1d_small_cout_kernel"),     # multi-band output, dilated
     (64, 1, 4100, 1, 1, "relu", None, "conv1d_small_cout_stream_kernel"),           # Parallel WaveGAN's last 1x1
@@ -245,8 +261,13 @@ def test_split_reduction_forward_backward(B, Cin, Cout, T, K, stride, pad, group
     (32, 1, 4098, 7, 1, "leaky_relu", "tanh", "conv1d_small_cout_kernel"),  # rows not 16-B aligned: the LDS kernel
     (24, 4, 4096, 3, 1, "leaky_relu", None, "conv1d_small_cout_stream_kernel"),  # 4 output channels, exactly 4 tiles
     (8, 1, 6148, 5, 1, None, "tanh", "conv1d_small_cout_stream_kernel"),  # ragged last tile
-])
-def test_small_cout_streaming_kernel(cin, cout, t, k, dil, pre, post, kernel, device):
+], [
+    # stream-shaped layers (T % 4 == 0) whose x or y is a view 4 bytes off: the stream's 16-B loads / stores are out, the
+    # LDS kernel must take them
+    (32, 1, 4100, 7, 1, "leaky_relu", "tanh", "conv1d_small_cout_kernel", "x"),
+    (24, 4, 4096, 3, 1, "leaky_relu", None, "conv1d_small_cout_kernel", "y"),
+]))
+def test_small_cout_streaming_kernel(cin, cout, t, k, dil, pre, post, kernel, misaligned, device):
     """C -> <= 4 channels over a long sequence takes a streaming VALU kernel instead of a 1-row MFMA tile: the LDS-free
     stream (round 6: dilation 1, "same" padding, 16-B aligned rows) or conv1d_small_cout_kernel; values vs ATen CPU
     (the two kernels run the same fmaf chain in the same (ci, tap) order: tools/experiments/r6_i.sh compares them bit for bit)."""
@@ -262,13 +283,17 @@ def test_small_cout_streaming_kernel(cin, cout, t, k, dil, pre, post, kernel, de
     desc = ops.make_conv_desc(2, cin, cout, t, t, k, dilation=dil, pad_left=pad, pre_act=pre, pre_slope=0.1,
                               post_act=post)
     wd = w.to(device)
+    xd = _off4(x.to(device)) if misaligned == "x" else x.to(device)
+    out = _off4(torch.full(ref.shape, float("nan"), device=device)) if misaligned == "y" else None
     with ops.profile() as prof:
-        y = ops.conv1d_forward(desc, x.to(device), ops.pack_weight(desc, wd), b.to(device))
+        y = ops.conv1d_forward(desc, xd, ops.pack_weight(desc, wd), b.to(device), out=out)
     assert kernel in prof.results, sorted(prof.results)
+    if misaligned:
+        assert "conv1d_small_cout_stream_kernel" not in prof.results, sorted(prof.results)
     assert (y.cpu() - ref).abs().max().item() <= 2e-5 * max(1.0, float(ref.abs().max()))
 
 
-@pytest.mark.parametrize("B,cout,t,k,dil,pad,pre,post,wn", [
+@pytest.mark.parametrize("B,cout,t,k,dil,pad,pre,post,wn,misaligned", _with_misaligned([
     (2, 16, 3000, 15, 1, 7, None, "leaky_relu", True),     # MelGAN discriminator's first layer (zero padding)
     (3, 16, 2600, 15, 1, 0, None, "leaky_relu", False),    # ... as trained: reflect pad applied beforehand, pad 0
     (1, 128, 4100, 15, 1, 7, None, "leaky_relu", True),    # HiFi-GAN scale discriminator's first layer, ragged tiles
@@ -276,8 +301,12 @@ def test_small_cout_streaming_kernel(cin, cout, t, k, dil, pre, post, kernel, de
     (2, 8, 2048, 16, 1, 8, None, None, True),              # maximal tap count, exactly two tiles
     (3, 16, 4200, 15, 1, 0, None, "leaky_relu", False),    # long enough for the streaming DATA gradient too ("full" padding)
     (2, 64, 8192, 3, 1, 1, None, "leaky_relu", True),      # PWG discriminator's first layer: the LDS-free stream (k = 3, "same")
-])
-def test_single_input_channel_kernels(B, cout, t, k, dil, pad, pre, post, wn, device):
+], [
+    # t_out % 4 == 0 with y a view 4 bytes off: the forward's 16-B store flag must turn off; the data gradient (16 -> 1,
+    # k = 7 "same": stream-shaped) with dy, then dx, 4 bytes off must leave the LDS-free stream for the LDS kernel
+    (2, 16, 4096, 7, 1, 3, None, "leaky_relu", False, "y_dy_dx"),
+]))
+def test_single_input_channel_kernels(B, cout, t, k, dil, pad, pre, post, wn, misaligned, device):
     """Cin = 1 over a long sequence (every discriminator's first layer) takes the streaming VALU kernels
     conv1d_small_cin_kernel / conv1d_small_cin_wgrad_kernel instead of an MFMA tile with one live channel: forward,
     weight and bias gradient (plain and through the weight-norm finish) vs ATen CPU; the data gradient keeps its path."""
@@ -299,8 +328,9 @@ def test_single_input_channel_kernels(B, cout, t, k, dil, pad, pre, post, wn, de
                               post_act=post, post_slope=0.1)
     xd, dyd, bd = x.detach().to(device), dy.to(device), b.detach().to(device)
     wd = w.detach().to(device).contiguous()
+    out = _off4(torch.full(out_ref.shape, float("nan"), device=device)) if misaligned else None
     with poison_lds(), poison_empty(), ops.profile() as prof:
-        y = ops.conv1d_forward(desc, xd, ops.pack_weight(desc, wd), bd)
+        y = ops.conv1d_forward(desc, xd, ops.pack_weight(desc, wd), bd, out=out)
         if wn:
             dv, dg, db = ops.conv1d_backward_weight_wn(desc, xd, dyd, v.detach().to(device), gg.detach().reshape(-1).to(device))
             dv2, dg2, db2 = ops.conv1d_backward_weight_wn(desc, xd, dyd, v.detach().to(device), gg.detach().reshape(-1).to(device))
@@ -308,7 +338,15 @@ def test_single_input_channel_kernels(B, cout, t, k, dil, pad, pre, post, wn, de
             dv, db = ops.conv1d_backward_weight(desc, xd, dyd, tuple(v.shape))
             dv2, db2 = ops.conv1d_backward_weight(desc, xd, dyd, tuple(v.shape))
             dw_only, none = ops.conv1d_backward_weight(desc, xd, dyd, tuple(v.shape), need_db=False)
-        dx = ops.conv1d_backward_data(desc, dyd, ops.pack_weight_bwd(desc, wd), xd)
+        dx = ops.conv1d_backward_data(desc, _off4(dyd) if misaligned else dyd, ops.pack_weight_bwd(desc, wd), xd)
+    if misaligned:
+        assert t_out % 4 == 0 and y.data_ptr() % 16 == 4
+        assert "conv1d_small_cout_kernel" in prof.results and "conv1d_small_cout_stream_kernel" not in prof.results, list(prof.results)
+        with poison_empty(), ops.profile() as prof_dx:
+            dx_off = ops.conv1d_backward_data(desc, dyd, ops.pack_weight_bwd(desc, wd), xd,
+                                              out=_off4(torch.full(x.shape, float("nan"), device=device)))
+        assert "conv1d_small_cout_kernel" in prof_dx.results and "conv1d_small_cout_stream_kernel" not in prof_dx.results, list(prof_dx.results)
+        assert torch.equal(dx_off, dx)  # (the same LDS kernel on the same values)
     assert "conv1d_small_cin_kernel" in prof.results and "conv1d_small_cin_wgrad_kernel" in prof.results, list(prof.results)
     if t >= 4096 and pre is None and (cout <= 32 or k <= 7):  # round 6: the data gradient (one output channel) streams as well
         assert any(k.startswith("conv1d_small_cout") for k in prof.results), list(prof.results)
