@@ -515,6 +515,25 @@ int pwg_pqmf_down(const float* x, const float* h, float* y, int32_t batch, int64
 int pwg_pqmf_up(const float* y, const float* g, float* x, int32_t batch, int64_t n_in, int64_t t_out,
                 int32_t subbands, int32_t len, int32_t pad, void* stream);
 
+/* ---- stateful streaming form of PQMF.synthesis (csrc/pqmf.hip; ABI v15) ----
+ * `up` with g[k][m] = K * synthesis_filter[k][taps - m] (layers/pqmf.py:133-149), evaluated WHILE the sub-band columns
+ * arrive.  In groups ("positions") of K output samples, position q reads the columns q + d, d in [dlo, dhi] =
+ * [ceil((pad - len + 1) / K), floor((K - 1 + pad) / K)], so a stream emits position q once column q + dhi is there:
+ * a fixed delay of D = dhi columns (K * D samples; 8 columns = 32 samples for K = 4, taps = 62) and a history of
+ * H = dhi - dlo raw columns per band (15).  pwg_pqmf_up_stream_geometry returns H and D (pure host logic).
+ * One launch: the window is concat(hist_in (batch, K, H), y (batch, K, n)); hist_in == NULL is the start of a stream
+ * (zero context, which is what `up` pads).  It writes x (batch, K * n_emit) = the last n_emit positions complete in the
+ * window, i.e. the chunk positions [n - D - n_emit, n - D) -- n_emit == n in steady state, max(0, n - D) at the start
+ * of a stream, 0 (x may be NULL) while a stream has no more than D columns; 0 <= n_emit <= n -- and hist_out
+ * (batch, K, H) = the last H columns of the window, also when n < H.  hist_in and hist_out must be distinct buffers.
+ * D zero columns pushed at the end flush the tail.  Every output is one fma chain from 0 over (k ascending, column
+ * ascending), the chain of `up`: for finite input the emissions of any partition of a stream, batched or not,
+ * concatenate to the bits of pwg_pqmf_up on the whole signal.  No workspace, no atomics.  1 <= subbands <= 8. */
+int pwg_pqmf_up_stream_geometry(int32_t subbands, int32_t len, int32_t pad, int32_t* hist_columns,
+                                int32_t* delay_columns);
+int pwg_pqmf_up_stream(const float* y, const float* hist_in, float* hist_out, const float* g, float* x, int32_t batch,
+                       int64_t n, int64_t n_emit, int32_t subbands, int32_t len, int32_t pad, void* stream);
+
 /* ---- StyleMelGAN pieces (layers/tade_res_block.py, models/style_melgan.py) ---- */
 /* torch.nn.InstanceNorm1d(affine=False) over `rows` = B*C rows of t samples (tade_res_block.py:27,66):
  * y = (x - mean) / sqrt(var + eps) with the biased variance; mean / rstd (rows floats each) are kept

@@ -345,6 +345,102 @@ static int launch_up_reg(const float* y, const float* g, float* x, int batch, in
   return PWG_OK;
 }
 
+// ---- stateful (streaming) synthesis.  The whole-utterance sum of position q (outputs x[qK .. qK + K)) reads the columns
+// i = q + d, d in [dlo, dhi]: a stream can emit q once column q + dhi has arrived -- a fixed delay of D = dhi columns --
+// and needs the last H = dhi - dlo columns of the past.  One launch sees the window concat(hist_in (H), y (n)), emits the
+// last n_emit positions that are complete in it (emitted position j reads the window columns n - n_emit + j + a,
+// a in [0, H]: all of them inside the window) and writes hist_out = the last H window columns, also when n < H (part of
+// hist_in carries over).  hist_in == NULL: start of stream, the columns before the first one are zero, which is what
+// `up` pads.  Every output is the fma chain of `up` from 0 over (k ascending, d ascending) -- `up` only adds fmas with
+// a zero coefficient past dhi -- so the emissions of ANY partition of a stream are, for finite input, the bits of `up`
+// on the whole signal.  grid (ceil(n_emit / ST), B), at least one workgroup per item (the first one of an item moves
+// the history); block 256, one position per lane.  LDS: K planes of ST + H window columns, then the taps as in `up`.
+// A push is a few hundred columns per stream: 256 positions per workgroup instead of `up`'s 1024 spread a batch-1
+// push over several CUs; the price is the H-column halo per 256 instead of per 1024 positions.
+constexpr int PQMF_ST = 256;
+
+template <int K>
+__global__ __launch_bounds__(256) void pqmf_up_stream_kernel(const float* __restrict__ y, const float* __restrict__ hist_in,
+                                                             float* __restrict__ hist_out, const float* __restrict__ g,
+                                                             float* __restrict__ x, int n, int n_emit, int hist, int len,
+                                                             int pad, int dlo) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int span = hist + 1;
+  const int pl = PQMF_ST + hist;  // per-band window of this workgroup: window columns [w0, w0 + pl)
+  float* ct = lds + K * pl;       // [K][span][K]
+  const int j0 = blockIdx.x * PQMF_ST;
+  const long b = blockIdx.y;
+  const float* yb = y + b * K * (long)n;
+  const float* hb = hist_in ? hist_in + b * K * (long)hist : nullptr;
+  // window column w of band k: history for w < hist, the chunk up to hist + n, zero past it (only lanes that emit
+  // nothing read those) and before a stream's first column
+  auto window = [&](int k, int w) -> float {
+    if (w < hist) return hb ? hb[k * hist + w] : 0.f;
+    return w - hist < n ? yb[k * (long)n + (w - hist)] : 0.f;
+  };
+  if (blockIdx.x == 0) {
+    float* ho = hist_out + b * K * (long)hist;
+    for (int idx = threadIdx.x; idx < K * hist; idx += 256) {
+      const int k = idx / hist, h = idx - k * hist;
+      ho[idx] = window(k, n + h);
+    }
+  }
+  const int w0 = n - n_emit + j0;
+  for (int idx = threadIdx.x; idx < K * pl; idx += 256) {
+    const int k = idx / pl, a = idx - k * pl;
+    lds[idx] = window(k, w0 + a);
+  }
+  for (int idx = threadIdx.x; idx < K * span * K; idx += 256) {
+    const int r = idx % K, a = (idx / K) % span, k = idx / (K * span);
+    const int m = r + pad - (dlo + a) * K;
+    ct[idx] = (m >= 0 && m < len) ? g[k * len + m] : 0.f;
+  }
+  __syncthreads();
+  float acc[K];
+#pragma unroll
+  for (int r = 0; r < K; ++r) acc[r] = 0.f;
+  const int q = threadIdx.x;
+  for (int k = 0; k < K; ++k) {
+    for (int a = 0; a < span; ++a) {
+      float cv[K];
+#pragma unroll
+      for (int r = 0; r < K; ++r) cv[r] = ct[(k * span + a) * K + r];
+      pqmf_fma_row<K>(acc, cv, lds[k * pl + q + a]);
+    }
+  }
+  __syncthreads();  // the window is dead: K strided stores per lane -> coalesced ones, as in `up`
+#pragma unroll
+  for (int r = 0; r < K; ++r) lds[q * K + r] = acc[r];
+  __syncthreads();
+  float* xb = x + b * K * (long)n_emit;
+  const long tbase = (long)j0 * K, t_out = (long)n_emit * K;
+  for (int idx = threadIdx.x; idx < PQMF_ST * K; idx += 256) {
+    const long t = tbase + idx;
+    if (t < t_out) xb[t] = lds[idx];
+  }
+}
+
+// d = i - q of `up`: [dlo, dhi] = [ceil((pad - len + 1) / K), floor((K - 1 + pad) / K)]
+static inline void up_reach(int K, int len, int pad, int* dlo, int* dhi) {
+  const int lo_num = pad - len + 1;  // (floor division towards -inf for the negative lower bound)
+  *dlo = lo_num >= 0 ? (lo_num + K - 1) / K : -((-lo_num) / K);
+  *dhi = (K - 1 + pad) / K;
+}
+
+template <int K>
+static int launch_up_stream(const float* y, const float* hist_in, float* hist_out, const float* g, float* x, int batch, int n,
+                            int n_emit, int len, int pad, hipStream_t s) {
+  int dlo, dhi;
+  up_reach(K, len, pad, &dlo, &dhi);
+  const int hist = dhi - dlo;
+  const size_t lds = sizeof(float) * ((size_t)K * (PQMF_ST + hist) + (size_t)K * (hist + 1) * K);  // (window >= K * ST outputs)
+  const int tiles = n_emit > 0 ? ceil_div(n_emit, PQMF_ST) : 1;
+  hipLaunchKernelGGL(pqmf_up_stream_kernel<K>, dim3(tiles, batch), dim3(256), lds, s, y, hist_in, hist_out, g, x, n, n_emit,
+                     hist, len, pad, dlo);
+  PWG_CHECK_LAUNCH("pqmf_up_stream_kernel");
+  return PWG_OK;
+}
+
 template <int K>
 static int launch_down(const float* x, const float* h, float* y, int batch, int t_in, int n_out, int len, int pad,
                        hipStream_t s) {
@@ -429,4 +525,44 @@ extern "C" int pwg_pqmf_up(const float* y, const float* g, float* x, int32_t bat
   ProfScope prof((hipStream_t)stream, "pqmf_up_kernel", 2.0 * batch * (double)t_out * len,
                  4.0 * batch * ((double)t_out + (double)n_in * subbands));
   PQMF_DISPATCH(launch_up, y, g, x, batch, (int)n_in, (int)t_out, len, pad, (hipStream_t)stream);
+}
+
+static int pqmf_stream_check(int32_t subbands, int32_t len, int32_t pad) {
+  PWG_REQUIRE(subbands >= 1 && subbands <= 8, PWG_ERR_UNSUPPORTED,
+              "pqmf_up_stream: 1 <= subbands <= 8 (got %d): more sub-bands cannot be streamed", subbands);
+  PWG_REQUIRE(len >= 1 && len <= PQMF_MAXL && pad >= 0 && pad < len, PWG_ERR_BAD_SHAPE,
+              "pqmf_up_stream: filter length %d (<= %d) / pad %d", len, PQMF_MAXL, pad);
+  return PWG_OK;
+}
+
+extern "C" int pwg_pqmf_up_stream_geometry(int32_t subbands, int32_t len, int32_t pad, int32_t* hist_columns,
+                                           int32_t* delay_columns) {
+  const int rc = pqmf_stream_check(subbands, len, pad);
+  if (rc != PWG_OK) return rc;
+  int dlo, dhi;
+  up_reach(subbands, len, pad, &dlo, &dhi);
+  if (hist_columns) *hist_columns = dhi - dlo;
+  if (delay_columns) *delay_columns = dhi;
+  return PWG_OK;
+}
+
+extern "C" int pwg_pqmf_up_stream(const float* y, const float* hist_in, float* hist_out, const float* g, float* x,
+                                  int32_t batch, int64_t n, int64_t n_emit, int32_t subbands, int32_t len, int32_t pad,
+                                  void* stream) {
+  int32_t hist = 0;
+  const int rc = pwg_pqmf_up_stream_geometry(subbands, len, pad, &hist, nullptr);
+  if (rc != PWG_OK) return rc;
+  PWG_REQUIRE(batch > 0 && batch <= 65535 && n > 0 && n * subbands < (1LL << 31), PWG_ERR_BAD_SHAPE,
+              "pqmf_up_stream: bad geometry (B=%d n=%lld)", batch, (long long)n);
+  PWG_REQUIRE(n_emit >= 0 && n_emit <= n, PWG_ERR_BAD_SHAPE,
+              "pqmf_up_stream: n_emit = %lld outside [0, n = %lld] (a launch emits at most one position per new column)",
+              (long long)n_emit, (long long)n);
+  PWG_REQUIRE(y && g && (hist_out || hist == 0) && (x || n_emit == 0), PWG_ERR_NULL, "pqmf_up_stream: NULL pointer");
+  PWG_REQUIRE(hist == 0 || hist_in != hist_out, PWG_ERR_BAD_SHAPE,
+              "pqmf_up_stream: hist_in and hist_out must be distinct buffers (other workgroups read the history)");
+  hipStream_t s = (hipStream_t)stream;
+  maybe_poison_lds(s);
+  ProfScope prof(s, "pqmf_up_stream_kernel", 2.0 * batch * (double)n_emit * subbands * subbands * (hist + 1),
+                 4.0 * batch * subbands * ((double)n + 2.0 * hist + (double)n_emit));
+  PQMF_DISPATCH(launch_up_stream, y, hist_in, hist_out, g, x, batch, (int)n, (int)n_emit, len, pad, s);
 }

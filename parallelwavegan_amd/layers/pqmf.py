@@ -9,11 +9,21 @@ Here each direction is ONE launch of a dedicated HBM-bound polyphase kernel (csr
 which produce exactly the kept samples; each kernel is the other's adjoint, so the backward passes are the same two
 launches.  More than 8 sub-bands run the general convolution kernel in the same polyphase form.  Filter design follows
 the same published formulas (Kaiser-windowed sinc prototype, cosine modulation).
+
+``stream_synthesis`` is the synthesis of a stream of sub-band columns (K <= 8): the symmetric filter looks ahead
+``taps / 2`` samples, so a stream emits every sample ``stream_delay_columns * K`` samples late (32 for the recipe filter)
+and keeps ``stream_history_columns`` raw columns per band; its emissions are, bit for bit, ``synthesis`` of the whole
+signal (csrc/pqmf.hip).
 """
+import ctypes
+
+
 import numpy as np
 import torch
 
+from .. import _lib
 from .. import functional as Fn
+from ..ops import _ptr, _require_device, _stream
 
 
 def design_prototype_filter(taps=62, cutoff_ratio=0.142, beta=9.0):
@@ -71,3 +81,42 @@ class PQMF(torch.nn.Module):
         if self.subbands <= 8:
             return Fn.PQMFUpFn.apply(x, self._synthesis_weight[:, 0], x.shape[-1] * self.subbands, self.taps // 2)
         return Fn.FusedConvFn.apply(x, self._synthesis_weight, None, None, None, self._geom(True), self._fused, None)
+
+    def _stream_geometry(self):
+        if self.subbands > 8:
+            raise ValueError(f"PQMF: {self.subbands} sub-bands cannot be streamed (the stream kernel covers 1 .. 8)")
+        h, d = ctypes.c_int32(), ctypes.c_int32()
+        _lib.check(_lib.lib().pwg_pqmf_up_stream_geometry(self.subbands, self.taps + 1, self.taps // 2, ctypes.byref(h),
+                                                          ctypes.byref(d)), "pqmf_up_stream_geometry")
+        return h.value, d.value
+
+    @property
+    def stream_history_columns(self):
+        """H: raw sub-band columns per band a stream keeps, ``ceil(pad / K) + floor(pad / K)``, ``pad = taps / 2``."""
+        return self._stream_geometry()[0]
+
+    @property
+    def stream_delay_columns(self):
+        """D = ``ceil(pad / K)``: a stream emits the K samples of position q once column q + D has arrived."""
+        return self._stream_geometry()[1]
+
+    def history_shape(self, batch):
+        return (int(batch), self.subbands, self.stream_history_columns)
+
+    @torch.no_grad()
+    def stream_synthesis(self, y, hist_in, hist_out, n_emit):
+        """The next ``n`` columns ``y`` (B, subbands, n) of a stream -> (B, subbands * n_emit) samples: the last
+        ``n_emit`` positions that are complete in ``concat(hist_in, y)``, ``stream_delay_columns`` behind the newest
+        column (``n_emit == n`` in steady state, ``max(0, n - D)`` at the start of a stream).  ``hist_in`` None: start of
+        stream; ``hist_out`` receives the last ``stream_history_columns`` columns of the window; the two must be distinct
+        buffers.  Inference only."""
+        _require_device(y, hist_in, hist_out, self._synthesis_weight)
+        b, k, n = y.shape
+        assert k == self.subbands, (tuple(y.shape), self.subbands)
+        for t in (hist_in, hist_out):
+            assert t is None or tuple(t.shape) == self.history_shape(b), (tuple(t.shape), self.history_shape(b))
+        x = torch.empty((b, k * max(int(n_emit), 0)), device=y.device, dtype=torch.float32)
+        _lib.check(_lib.lib().pwg_pqmf_up_stream(_ptr(y), _ptr(hist_in), _ptr(hist_out), _ptr(self._synthesis_weight), _ptr(x),
+                                                 b, n, int(n_emit), k, self.taps + 1, self.taps // 2, _stream()),
+                   "pqmf_up_stream")
+        return x

@@ -19,7 +19,8 @@ transpose, the generator, and the float -> PCM16 conversion.
 ``CausalStream`` is the other regime: synthesis WHILE the mel frames arrive, for generators built with
 ``use_causal_conv=True``.  Every causal layer keeps the last ``(k-1)*d`` columns of its raw input (one column for a
 transposed layer) on the device, so a push of ``n`` frames costs ``n`` frames of work with zero look-ahead
-(csrc/conv1d_stream.hip).
+(csrc/conv1d_stream.hip).  A causal multi-band MelGAN streams through a stateful PQMF synthesis, whose
+symmetric filter adds a fixed latency of ``latency_samples`` (32 for the recipe filter; csrc/pqmf.hip).
 """
 import ctypes
 
@@ -46,6 +47,8 @@ def to_pcm16(wave):
     wave = wave.contiguous()
     _require_device(wave)
     pcm = torch.empty(wave.shape, device=wave.device, dtype=torch.int16)
+    if wave.numel() == 0:  # (a push that emits nothing yet: warm-up, or inside the PQMF delay)
+        return pcm
     _lib.check(_lib.lib().pwg_wave_to_pcm16(_ptr(wave), ctypes.c_void_p(pcm.data_ptr()), wave.numel(), _stream()),
                "wave_to_pcm16")
     return pcm
@@ -69,8 +72,9 @@ def receptive_field_frames(model, in_channels=None, probe_frames=96):
         c_future[..., half:] = torch.randn(1, ch, n - half, generator=gen).to(dev)
         c_past[..., :half] = torch.randn(1, ch, half, generator=gen).to(dev)
         y = model(c1)
-        d_future = (model(c_future) != y).flatten().nonzero()
-        d_past = (model(c_past) != y).flatten().nonzero()
+        # (several output channels, i.e. sub-bands: a change is located along time, whichever band shows it)
+        d_future = (model(c_future) != y).flatten().nonzero() % y.shape[-1]
+        d_past = (model(c_past) != y).flatten().nonzero() % y.shape[-1]
         # frames >= half changed: earliest affected sample tells how far the future reaches back
         first = int(d_future.min()) if d_future.numel() else half * up
         last = int(d_past.max()) if d_past.numel() else half * up - 1
@@ -85,7 +89,9 @@ def receptive_field_frames(model, in_channels=None, probe_frames=96):
 class ChunkedSynthesizer:
     """Exact chunked synthesis for generators that map (B, C, T') mel -> (B, 1, T' * upsample_factor)
     from the mel alone (HiFi-GAN, MelGAN).  ``chunk_frames`` frames of output per chunk;
-    ``max_batch`` chunks per forward."""
+    ``max_batch`` chunks per forward.  A multi-band model (``model.pqmf`` attached) has its K sub-band rows stitched
+    the same way, then one ``pqmf.synthesis`` per utterance: T' * upsample_factor * K samples.  Several output channels
+    without a PQMF are an error."""
 
     def __init__(self, model, chunk_frames=256, max_batch=16, halo=None, use_graph=True):
         self.model = model.eval()
@@ -93,6 +99,8 @@ class ChunkedSynthesizer:
         self.max_batch = int(max_batch)
         self.left, self.right = halo if halo is not None else receptive_field_frames(model)
         self.up = model.upsample_factor
+        self.pqmf = getattr(model, "pqmf", None)
+        self.rows = self.pqmf.subbands if self.pqmf is not None else 1  # output channels of the generator
         self._run = GraphedInference(self.model) if use_graph else self.model
 
     def _plan(self, n_frames):
@@ -107,7 +115,7 @@ class ChunkedSynthesizer:
 
     @torch.no_grad()
     def synthesize_many(self, feats, normalize_before=False):
-        """feats: list of (T'_i, C) tensors/arrays -> list of (T'_i * upsample_factor,) float waveforms."""
+        """feats: list of (T'_i, C) tensors/arrays -> list of (T'_i * upsample_factor [* subbands],) float waveforms."""
         dev = next(self.model.parameters()).device
         mean = getattr(self.model, "mean", None) if normalize_before else None
         scale = getattr(self.model, "scale", None) if normalize_before else None
@@ -115,7 +123,7 @@ class ChunkedSynthesizer:
         for f in feats:
             f = torch.as_tensor(f, dtype=torch.float32).to(dev)
             mels.append(normalize_transpose(f.unsqueeze(0), mean, scale)[0])  # (C, T')
-        outs = [torch.empty(m.shape[-1] * self.up, device=dev) for m in mels]
+        outs = [torch.empty(self.rows, m.shape[-1] * self.up, device=dev) for m in mels]
         # group chunks by (context length, whether the model's own padding is on the left / right):
         # only equal-shaped chunks share a batch, and edge chunks keep their true zero-padded side
         groups = {}
@@ -132,24 +140,39 @@ class ChunkedSynthesizer:
                     pad = self.max_batch - len(part)
                     batch = torch.cat([batch, batch[:1].expand(pad, -1, -1)], 0)
                 y = self._run(batch.contiguous())
+                if y.shape[1] != self.rows:
+                    raise ValueError(f"ChunkedSynthesizer: the generator emits {y.shape[1]} channels but "
+                                     + (f"model.pqmf has {self.rows} sub-bands" if self.pqmf is not None else
+                                        "no PQMF is attached (model.pqmf = PQMF(subbands=...), as utils.load_model does)"))
                 for j, (ui, s, e, cs, ce) in enumerate(part):
-                    outs[ui][s * self.up:e * self.up] = y[j, 0, (s - cs) * self.up:(e - cs) * self.up]
-        return outs
+                    outs[ui][:, s * self.up:e * self.up] = y[j, :, (s - cs) * self.up:(e - cs) * self.up]
+        if self.pqmf is not None:
+            return [self.pqmf.synthesis(o.unsqueeze(0))[0, 0] for o in outs]
+        return [o[0] for o in outs]
 
     def synthesize(self, feat, normalize_before=False):
-        """(T', C) -> (T' * upsample_factor,)"""
+        """(T', C) -> (T' * upsample_factor [* subbands],)"""
         return self.synthesize_many([feat], normalize_before)[0]
 
 
 class CausalStream:
-    """Stateful streaming synthesis for ``HiFiGANGenerator`` and full-band ``MelGANGenerator`` built with
+    """Stateful streaming synthesis for ``HiFiGANGenerator`` and ``MelGANGenerator`` built with
     ``use_causal_conv=True``: ``push`` takes the next mel frames of ``batch`` lock-step streams and returns their
     samples; any partition of the same frames gives bit-identical audio, equal to the whole-utterance ``forward`` up to
     fp32 summation order.
 
+    Multi-band MelGAN (``model.pqmf`` attached, up to 8 sub-bands): the sub-bands of a push go through
+    ``PQMF.stream_synthesis`` in the same push.  The synthesis filter is symmetric, so every sample leaves
+    ``latency_samples`` (K * ceil(taps / 2 / K); 32 for the recipe filter) late: the first emissions of an utterance are
+    short by that much in total, afterwards a push of ``n`` frames returns ``n * up`` samples (``up`` =
+    ``upsample_factor * K``), and ``flush()`` returns the tail, after which the emissions total ``frames * up`` samples and
+    equal ``pqmf.synthesis`` of the whole utterance's sub-bands bit for bit.  ``close()`` does not flush: an unflushed
+    tail is dropped.
+
     State: per causal layer two history tensors (ping-pong: a push reads one half and writes the other, in the layer's
     own launch).  ``use_graph``: steady-state pushes of one chunk size replay two captured graphs (A -> B, B -> A);
-    the first push of a stream (the layers' own start-of-stream padding) runs eagerly.  Graphs are dropped when the
+    the first push of a stream (the layers' own start-of-stream padding) runs eagerly, as do the pushes of a
+    multi-band stream that has not yet received more columns than the PQMF delay.  Graphs are dropped when the
     model's parameter state (``GraphedInference._param_state``) changes, so a replay never uses old weights.
     Graph mode wants a fixed chunk size: the first push of a new size captures inside ``push`` (four warm-up runs and
     two captures), each captured size holds a private pool of all activations, and only the ``max_graph_shapes`` most
@@ -164,17 +187,27 @@ class CausalStream:
 
     def __init__(self, model, batch=1, use_graph=True, normalize_before=False):
         from ..layers.conv import each_conv
+        from ..layers.pqmf import PQMF
         from ..models import HiFiGANGenerator, MelGANGenerator
 
         if not isinstance(model, (HiFiGANGenerator, MelGANGenerator)):
             raise ValueError(f"CausalStream: {model.__class__.__name__} is not supported (only the causal HiFiGANGenerator "
-                             "and full-band MelGANGenerator map mel frames to samples layer by layer)")
+                             "and MelGANGenerator map mel frames to samples layer by layer)")
         self._layers = model.stream_layers()  # ValueError for a non-causal model
         out_channels = model.output_conv[1].conv.out_channels if isinstance(model, HiFiGANGenerator) else \
             self._layers[-1][0].conv.out_channels
-        if out_channels != 1 or getattr(model, "pqmf", None) is not None:
-            raise ValueError(f"CausalStream: the generator emits {out_channels} sub-bands; PQMF synthesis is a symmetric "
-                             "FIR (it looks ahead), so multi-band models cannot be streamed causally")
+        pqmf = getattr(model, "pqmf", None)
+        if out_channels != 1 and (pqmf is None or not isinstance(model, MelGANGenerator)):
+            raise ValueError(f"CausalStream: the generator emits {out_channels} sub-bands; only a multi-band "
+                             "MelGANGenerator with its PQMF attached (model.pqmf = PQMF(subbands=...), as utils.load_model "
+                             "does) can be streamed, through the stateful PQMF synthesis")
+        if pqmf is not None:
+            if not isinstance(pqmf, PQMF) or pqmf.subbands != out_channels:
+                raise ValueError(f"CausalStream: model.pqmf must be a PQMF with as many sub-bands as the generator emits "
+                                 f"({out_channels}); got {getattr(pqmf, 'subbands', pqmf.__class__.__name__)}")
+            if pqmf.subbands > 8:
+                raise ValueError(f"CausalStream: a PQMF of {pqmf.subbands} sub-bands cannot be streamed (the stream kernel "
+                                 "covers up to 8)")
         if any(cv.precision != "fp32" for cv in each_conv(model)):
             raise ValueError("CausalStream: the model is in bf16 inference precision; the streaming kernel is fp32 "
                              "(utils.set_inference_precision(model, 'fp32'))")
@@ -192,11 +225,18 @@ class CausalStream:
         self.batch = batch
         self.use_graph = bool(use_graph)
         self.normalize_before = bool(normalize_before)
-        self.up = model.upsample_factor
+        self.pqmf = pqmf
+        self.subbands = out_channels
+        self.up = model.upsample_factor * out_channels  # samples per frame
+        self._delay = pqmf.stream_delay_columns if pqmf is not None else 0
+        self.latency_samples = self._delay * out_channels
         self.warmup_frames = self.required_warmup_frames(model)
         dev = next(model.parameters()).device
         self._halves = [[torch.zeros(layer.history_shape(batch), device=dev) for layer, _ in self._layers]
                         for _ in range(2)]
+        if pqmf is not None:  # the PQMF history rides behind the layers' in both ping-pong halves
+            for half in self._halves:
+                half.append(torch.zeros(pqmf.history_shape(batch), device=dev))
         self._watch = GraphedInference(model)  # (only its parameter-state key is used)
         self._state = None
         self._graphs = {}
@@ -215,17 +255,31 @@ class CausalStream:
         return sum(t.numel() * t.element_size() for half in self._halves for t in half)
 
     def reset(self):
-        """Back to start of stream: the next push starts from the layers' own padding.  Held frames are dropped."""
+        """Back to start of stream: the next push starts from the layers' own padding and, for a multi-band model, from
+        the PQMF's zero context.  Held frames and an unflushed tail are dropped."""
         self._cur = 0          # which half holds the current history
         self._started = False  # False: the next run passes hist_in = None
         self._held = []
+        self._columns = 0      # sub-band columns the PQMF stream has taken (multi-band)
+        self._flushed = False
         self.frames_in = 0
         self.frames_out = 0
+        self.samples_out = 0
 
-    def _run(self, feats, hist_in, hist_out):
+    def _emit(self, n_cols):
+        """Positions a PQMF launch over the next ``n_cols`` columns completes: ``n_cols`` once the stream is past the
+        delay, fewer (or none) before."""
+        return max(0, self._columns + n_cols - self._delay) - max(0, self._columns - self._delay)
+
+    def _run(self, feats, hist_in, hist_out, n_emit=None):
+        """``hist_in`` (None: start of stream) / ``hist_out``: one ping-pong half each.  -> (batch, samples)."""
         mean = self.model.mean if self.normalize_before else None
         scale = self.model.scale if self.normalize_before else None
-        return self.model.stream_forward(normalize_transpose(feats, mean, scale), hist_in, hist_out)
+        y = self.model.stream_forward(normalize_transpose(feats, mean, scale), hist_in, hist_out)
+        if self.pqmf is None:
+            return y.reshape(self.batch, -1)
+        return self.pqmf.stream_synthesis(y, None if hist_in is None else hist_in[-1], hist_out[-1],
+                                          y.shape[-1] if n_emit is None else n_emit)
 
     def _capture(self, feats):
         """Graphs for both directions of one chunk shape.  The warm-up runs write history: both halves are saved and
@@ -251,9 +305,12 @@ class CausalStream:
 
     @torch.no_grad()
     def push(self, feats):
-        """feats: (n, C) or (batch, n, C) float features -> (batch, m * upsample_factor) fp32 samples, ``m`` the frames
-        emitted by this push (``n``, except around the warm-up of a reflect-padded model).  The result is the caller's
-        own tensor (not a graph's static buffer)."""
+        """feats: (n, C) or (batch, n, C) float features -> (batch, samples) fp32: ``m * up`` samples, ``m`` the frames
+        emitted by this push (``n``, except around the warm-up of a reflect-padded model), less what the PQMF delay of a
+        multi-band model still holds back at the start of an utterance (``latency_samples`` in total).  The result is the
+        caller's own tensor (not a graph's static buffer)."""
+        if self._flushed:
+            raise RuntimeError("CausalStream.push: the utterance was flushed; reset() starts the next one")
         dev = self._halves[0][0].device
         feats = torch.as_tensor(feats, dtype=torch.float32).to(dev)
         if feats.dim() == 2:
@@ -271,13 +328,15 @@ class CausalStream:
         n = feats.shape[1]
         if n == 0:
             return torch.empty((self.batch, 0), device=dev, dtype=torch.float32)
+        n_cols = n * self.model.upsample_factor
+        n_emit = self._emit(n_cols)
         if not self._started:
             # start of stream: the layers' own padding; once per utterance, eager
-            y = self._run(feats, None, self._halves[0])
+            y = self._run(feats, None, self._halves[0], n_emit)
             self._cur, self._started = 0, True
         else:
             hist_in, hist_out = self._halves[self._cur], self._halves[1 - self._cur]
-            if self.use_graph:
+            if self.use_graph and n_emit == n_cols:  # (a multi-band stream still inside the PQMF delay: eager)
                 state = self._watch._param_state()
                 if state != self._state:
                     self._graphs, self._state = {}, state
@@ -294,18 +353,38 @@ class CausalStream:
                 g.replay()
                 y = static_out.clone()
             else:
-                y = self._run(feats, hist_in, hist_out)
+                y = self._run(feats, hist_in, hist_out, n_emit)
             self._cur = 1 - self._cur
         self.frames_out += n
-        return y.reshape(self.batch, n * self.up)
+        self._columns += n_cols
+        self.samples_out += y.shape[1]
+        return y
+
+    @torch.no_grad()
+    def flush(self):
+        """End of the utterance of a multi-band stream: ``stream_delay_columns`` zero columns through the PQMF launch
+        (the zeros the whole-utterance synthesis pads with) -> the last ``latency_samples`` samples, (batch, samples).
+        Zero-length for a full-band model, before anything was synthesised, and on a second call.  The next utterance
+        starts with ``reset()``."""
+        dev = self._halves[0][0].device
+        if self.pqmf is None or not self._started or self._flushed:
+            return torch.empty((self.batch, 0), device=dev, dtype=torch.float32)
+        zeros = torch.zeros((self.batch, self.subbands, self._delay), device=dev)
+        y = self.pqmf.stream_synthesis(zeros, self._halves[self._cur][-1], self._halves[1 - self._cur][-1],
+                                       self._emit(self._delay))
+        self._columns += self._delay
+        self._flushed = True  # (the halves are not swapped: nothing may follow but reset())
+        self.samples_out += y.shape[1]
+        return y
 
     def push_pcm16(self, feats):
-        """``push`` through the float -> PCM16 conversion: (batch, m * upsample_factor) int16."""
+        """``push`` through the float -> PCM16 conversion: (batch, samples) int16."""
         return to_pcm16(self.push(feats))
 
     def close(self):
         """End of the utterance: raises if frames are still held (the utterance was shorter than ``warmup_frames``,
-        which the whole-utterance forward cannot pad either)."""
+        which the whole-utterance forward cannot pad either).  It does not flush: the last ``latency_samples`` samples of
+        a multi-band utterance come from ``flush()``, and without it they are dropped."""
         held = sum(f.shape[1] for f in self._held)
         if held:
             raise RuntimeError(f"CausalStream: {held} frame(s) were pushed but the reflect-padded start of this model "

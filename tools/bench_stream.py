@@ -8,7 +8,13 @@ feature transposition and without copying the result out, both of which ``push``
 the halo path.)  Device events around ``--reps`` calls after warm-up, three alternating repeats to show the spread;
 launches per call counted through pwg_prof_* on one eager run of each.  GPU box only.
 
-usage: python tools/bench_stream.py [--reps 200] [--repeats 3] [--out profiles/stream_infer.json]
+``--multiband``: the same method for a causal multi-band MelGAN (the multi_band_melgan.v2 generator geometry of
+tests/fixtures/conf with use_causal_conv=True and its PQMF attached), 1 and 16 streams x 8 and 32 frames, into
+profiles/stream_mb_infer.json.  ``push`` includes the stateful PQMF synthesis; the halo side is ONE graph of the forward
+over ``left + n`` frames and ``pqmf.synthesis`` over that output.  The PQMF launch's own time per push comes from the
+library's profiler scope (pwg_prof_*) on eager pushes.
+
+usage: python tools/bench_stream.py [--multiband] [--reps 200] [--repeats 3] [--out profiles/stream_infer.json]
 """
 import argparse
 import json
@@ -21,6 +27,7 @@ import torch  # noqa: E402
 
 from parallelwavegan_amd import ops  # noqa: E402
 from parallelwavegan_amd.graphs import GraphedInference  # noqa: E402
+from parallelwavegan_amd.layers import PQMF  # noqa: E402
 from parallelwavegan_amd.models import HiFiGANGenerator, MelGANGenerator  # noqa: E402
 from parallelwavegan_amd.utils import CausalStream  # noqa: E402
 from parallelwavegan_amd.utils.streaming import receptive_field_frames  # noqa: E402
@@ -29,6 +36,7 @@ from tests.golden import synth  # noqa: E402
 CHUNKS = (4, 8, 32)
 STREAMS = (1, 16)
 MELGAN_CHUNKS = (8,)  # a second family at one chunk size: its 1 x 1 layers run on the stream kernel too
+MB_CHUNKS = (8, 32)
 MELGAN_RECIPE_CAUSAL = dict(in_channels=80, out_channels=1, kernel_size=7, channels=512, upsample_scales=[8, 8, 2, 2],
                             stack_kernel_size=3, stacks=3, use_causal_conv=True)
 
@@ -46,6 +54,20 @@ def build_melgan(dev):
     g = MelGANGenerator(**MELGAN_RECIPE_CAUSAL)
     g.load_state_dict(synth.synth_state_dict(g.state_dict(), seed=12, g_scale=synth.MELGAN_G_SCALE))
     g.remove_weight_norm()
+    return g.to(dev).eval()
+
+
+def build_multiband(dev):
+    """Causal multi-band MelGAN at the multi_band_melgan.v2 geometry on seeded weights, weight norm removed, PQMF
+    attached (the recipe's default filter)."""
+    import yaml
+
+    with open(os.path.join(ROOT, "tests", "fixtures", "conf", "multi_band_melgan.v2.yaml")) as f:
+        params = dict(yaml.safe_load(f)["generator_params"], use_causal_conv=True)
+    g = MelGANGenerator(**params)
+    g.load_state_dict(synth.synth_state_dict(g.state_dict(), seed=13, g_scale=synth.MELGAN_G_SCALE))
+    g.remove_weight_norm()
+    g.pqmf = PQMF(subbands=params["out_channels"])
     return g.to(dev).eval()
 
 
@@ -74,15 +96,20 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "stream_infer.json"))
+    ap.add_argument("--multiband", action="store_true")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    args.out = args.out or os.path.join(ROOT, "profiles", "stream_mb_infer.json" if args.multiband else "stream_infer.json")
     dev = torch.device("cuda:0")
     rec = {"tool": "tools/bench_stream.py", "device": torch.cuda.get_device_name(0), "reps": args.reps,
            "repeats": args.repeats, "models": {}, "points": []}
     gen = torch.Generator(device="cpu").manual_seed(100)
-    for name, model, chunks in (("hifigan_v1_causal", build_model(dev), CHUNKS),
-                                ("melgan_recipe_causal", build_melgan(dev), MELGAN_CHUNKS)):
-        measure(rec, name, model, chunks, gen, args, dev)
+    if args.multiband:
+        measure(rec, "multi_band_melgan_v2_causal", build_multiband(dev), MB_CHUNKS, gen, args, dev)
+    else:
+        for name, model, chunks in (("hifigan_v1_causal", build_model(dev), CHUNKS),
+                                    ("melgan_recipe_causal", build_melgan(dev), MELGAN_CHUNKS)):
+            measure(rec, name, model, chunks, gen, args, dev)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(rec, f, indent=1)
@@ -94,7 +121,11 @@ def main():
 def measure(rec, name, model, chunks, gen, args, dev):
     left, right = receptive_field_frames(model)
     assert right == 0, "a causal generator has no look-ahead"
-    up = model.upsample_factor
+    pqmf = getattr(model, "pqmf", None)
+    up = model.upsample_factor * (pqmf.subbands if pqmf is not None else 1)
+    # what exists without the stream: the forward over left + n frames and, for a multi-band model, the synthesis of
+    # that output, in one graph
+    whole = model if pqmf is None else (lambda c: pqmf.synthesis(model(c)))
     rec["models"][name] = {"workload": "seeded weights, weight norm removed", "halo_left_frames": left,
                            "stream_state_bytes_per_stream": CausalStream(model, use_graph=False).state_bytes}
     for b in STREAMS:
@@ -102,7 +133,7 @@ def measure(rec, name, model, chunks, gen, args, dev):
             feats = torch.randn(b, n, 80, generator=gen).to(dev)
             ctx = torch.randn(b, 80, left + n, generator=gen).to(dev)
             s = CausalStream(model, batch=b, use_graph=True)
-            halo = GraphedInference(model)
+            halo = GraphedInference(whole)
             for _ in range(6):  # start of stream, both graph directions, and the halo graph
                 s.push(feats)
                 halo(ctx)
@@ -114,7 +145,7 @@ def measure(rec, name, model, chunks, gen, args, dev):
             while eager.frames_out == 0:  # past the start of the stream (and a reflect-padded model's warm-up)
                 eager.push(feats)
             n_s, fam_s = launches(lambda: eager.push(feats))
-            n_h, fam_h = launches(lambda: model(ctx))
+            n_h, fam_h = launches(lambda: whole(ctx))
             med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
             spread = max(max(t_s) - min(t_s), max(t_h) - min(t_h))
             p = {"model": name, "streams": b, "chunk_frames": n, "samples_per_push": b * n * up,
@@ -127,6 +158,13 @@ def measure(rec, name, model, chunks, gen, args, dev):
                  "real_time_factor_22050Hz": round(n * up / 22050.0 / (med(t_s) / 1e3), 1),
                  "launches_per_push_stream": n_s, "launches_per_forward_halo": n_h,
                  "stream_kernels": fam_s, "halo_kernels": fam_h}
+            if pqmf is not None:
+                with ops.profile() as prof:  # the PQMF launch of a push, by the library's own event scope
+                    for _ in range(20):
+                        eager.push(feats)
+                r = prof.results["pqmf_up_stream_kernel"]
+                p["pqmf_stream_launch_ms"] = round(r["ms"] / r["launches"], 5)
+                p["real_time_factor_24000Hz"] = round(n * up / 24000.0 / (med(t_s) / 1e3), 1)
             rec["points"].append(p)
             print(json.dumps({k: p[k] for k in ("model", "streams", "chunk_frames", "stream_push_ms", "halo_forward_ms",
                                                 "spread_ms", "speedup_stream_over_halo", "launches_per_push_stream",
