@@ -256,6 +256,25 @@ int pwg_conv1d_stream_forward(const pwg_conv1d_desc* d, const float* x, const fl
                               const float* w_packed, const float* bias, const float* add1, const float* add2, float* y,
                               void* stream);
 
+/* ---- the stream launch with bf16 operands (opt-in; csrc/conv1d_stream_bf16.hip) ----
+ * pwg_conv1d_stream_forward under the numerical definition of the bf16-operand inference above: the window is
+ * concat(hist_in, x) with RAW fp32 history; pre_act is applied in fp32 while the window is staged, to history, chunk
+ * and start-of-stream padding alike; the activated value is rounded to bf16 (nearest-even); the weights are the bf16
+ * image of pwg_conv1d_bf16_pack_weight -- packed through a descriptor of the layer's geometry with PWG_PAD_ZERO, since
+ * the image does not depend on padding and the packer admits no other -- products accumulate in fp32 on
+ * v_mfma_f32_16x16x32_bf16; the epilogue and the stored result are fp32.  hist_out is bit-identical to what
+ * pwg_conv1d_stream_forward writes for the same inputs: the state tensors, their shapes and
+ * pwg_conv1d_stream_hist_floats are shared, a stream's state does not depend on its precision.
+ * pwg_conv1d_stream_bf16_supported answers exactly as pwg_conv1d_stream_supported for every descriptor (pure host
+ * logic; pwg_last_error names the reason for 0).  Deterministic, and the sum order of an output element depends on the
+ * layer alone (csrc/conv1d_stream_bf16.hip): any partition of a stream gives the same bits, kernel-1 layers (H == 0)
+ * included.
+ * These two symbols are purely additive -- no existing signature or behaviour changes -- so pwg_abi_version() stays 15. */
+int pwg_conv1d_stream_bf16_supported(const pwg_conv1d_desc* d);
+int pwg_conv1d_stream_bf16_forward(const pwg_conv1d_desc* d, const float* x, const float* hist_in, float* hist_out,
+                                   const void* w_packed_bf16, const float* bias, const float* add1,
+                                   const float* add2, float* y, void* stream);
+
 /* Diagnostics (host only, no launch, no device needed): the plan pwg_conv1d_forward derives for a descriptor.
  * has_addends: 1 if add1 / add2 will be passed.  out[8]:
  *   out[0] kernel family: 0 = MFMA implicit-GEMM kernel, 1 = grouped 16x16x4 kernel, 2 = single-input-channel

@@ -44,12 +44,14 @@ class CausalConv1d(torch.nn.Module):
         """Input columns the first push needs: reflect padding mirrors the first ``(k - 1) * d + 1`` of them."""
         return self.conv.padding + 1 if self.conv.pad_mode == "reflect" and self.conv.padding > 0 else 1
 
-    def stream_forward(self, x, hist_in, hist_out, **fused):
+    def stream_forward(self, x, hist_in, hist_out, precision="fp32", **fused):
         """The next ``x.shape[-1]`` columns of a stream whose previous columns are ``hist_in`` (None: start of stream,
         the layer's own padding); also writes ``hist_out`` (a buffer distinct from ``hist_in``).  One launch; the
-        fused-epilogue keywords and the weight image are those of ``forward``."""
+        fused-epilogue keywords and the weight image are those of ``forward``.  ``precision="bf16"``: the same launch
+        with bf16 operands (csrc/conv1d_stream_bf16.hip) on the layer's bf16 image; history stays raw fp32, so the
+        state of a stream does not depend on its precision."""
         return _stream_forward(self.conv, self.stream_desc(x.shape[0], x.shape[-1], **_desc_kw(fused)), x, hist_in,
-                               hist_out, fused)
+                               hist_out, fused, precision)
 
 
 class CausalConvTranspose1d(torch.nn.Module):
@@ -82,37 +84,50 @@ class CausalConvTranspose1d(torch.nn.Module):
     def history_columns_at_start(self):
         return 1
 
-    def stream_forward(self, x, hist_in, hist_out, **fused):
+    def stream_forward(self, x, hist_in, hist_out, precision="fp32", **fused):
         """As :meth:`CausalConv1d.stream_forward`; the start-of-stream context is the replicated first column."""
         return _stream_forward(self.deconv, self.stream_desc(x.shape[0], x.shape[-1], **_desc_kw(fused)), x, hist_in,
-                               hist_out, fused)
+                               hist_out, fused, precision)
 
 
-def stream_pointwise(cv, x, **fused):
+def stream_pointwise(cv, x, precision="fp32", **fused):
     """A 1 x 1 ``Conv1d`` on the next columns of a stream, through the streaming kernel with no history (``H = 0``):
     its sum order does not depend on the column count or the batch, which the general kernel's choice of tile and
-    reduction split does."""
+    reduction split does.  ``precision`` as in :meth:`CausalConv1d.stream_forward`."""
     if cv.kernel_size != 1 or cv.padding != 0 or cv.padding_right != 0:
         raise ValueError("stream_pointwise: not an unpadded 1 x 1 convolution")
     n = x.shape[-1]
     desc = ops.make_conv_desc(x.shape[0], cv.in_channels, cv.out_channels, n, n, 1, cv.stride, 1, 0, cv.groups,
                               transposed=False, pad_mode="zero", **_desc_kw(fused))
-    return _stream_forward(cv, desc, x, None, None, fused)
+    return _stream_forward(cv, desc, x, None, None, fused, precision)
 
 
 def _desc_kw(fused):
     return {k: v for k, v in fused.items() if k not in ("add1", "add2")}
 
 
-def _stream_forward(cv, desc, x, hist_in, hist_out, fused):
+def _stream_forward(cv, desc, x, hist_in, hist_out, fused, precision="fp32"):
+    if precision not in ("fp32", "bf16"):
+        raise ValueError(f"stream precision must be 'fp32' or 'bf16', got {precision!r}")
+    bias = None if cv.bias is None else cv.bias.detach()
+    if precision == "bf16":
+        # the precision of the call: the module's own `precision` attribute (whole-utterance mode) is not consulted
+        if not ops.conv1d_stream_bf16_supported(desc):
+            from .. import _lib
+
+            raise RuntimeError("the bf16 streaming kernel does not cover this layer: "
+                               + _lib.lib().pwg_last_error().decode(errors="replace"))
+        with torch.no_grad():
+            return ops.conv1d_stream_forward_bf16(desc, x.contiguous(), hist_in, hist_out, cv.packed_weight_bf16(), bias,
+                                                  fused.get("add1"), fused.get("add2"))
     if cv.precision != "fp32":
-        raise RuntimeError(f"{cv.__class__.__name__} is in {cv.precision} inference precision: the streaming kernel is fp32")
+        raise RuntimeError(f"{cv.__class__.__name__} is in {cv.precision} inference precision: the streaming kernel is fp32 "
+                           "(pass precision='bf16' to stream with bf16 operands)")
     if not ops.conv1d_stream_supported(desc):
         from .. import _lib
 
         raise RuntimeError("the streaming kernel does not cover this layer: "
                            + _lib.lib().pwg_last_error().decode(errors="replace"))
     with torch.no_grad():
-        return ops.conv1d_stream_forward(desc, x.contiguous(), hist_in, hist_out, cv.packed_weight(),
-                                         None if cv.bias is None else cv.bias.detach(), fused.get("add1"),
-                                         fused.get("add2"))
+        return ops.conv1d_stream_forward(desc, x.contiguous(), hist_in, hist_out, cv.packed_weight(), bias,
+                                         fused.get("add1"), fused.get("add2"))

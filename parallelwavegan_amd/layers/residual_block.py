@@ -325,10 +325,10 @@ class HiFiGANResidualBlock(torch.nn.Module):
                 out.append(self.convs2[idx][1])
         return out
 
-    def stream_forward(self, x, hist, accum=None, out_div=1.0):
+    def stream_forward(self, x, hist, accum=None, out_div=1.0, precision="fp32"):
         """The causal ``forward`` on the next chunk of a stream: the same modules in the same order with the same fused
         epilogues, every convolution through its ``stream_forward``.  ``hist``: iterator of ``(hist_in, hist_out)`` pairs,
-        one per layer of :meth:`stream_layers`."""
+        one per layer of :meth:`stream_layers`; ``precision``: passed to every convolution."""
         if not self.use_causal_conv:
             raise ValueError("HiFiGANResidualBlock.stream_forward needs use_causal_conv=True")
         n = len(self.convs1)
@@ -337,10 +337,10 @@ class HiFiGANResidualBlock(torch.nn.Module):
             act1, conv1 = self.convs1[idx][0], self.convs1[idx][1]
             if self.use_additional_convs:
                 act2, conv2 = self.convs2[idx][0], self.convs2[idx][1]
-                xt = conv1.stream_forward(x, *next(hist), pre_act=act1.kind, pre_slope=act1.slope)
-                x = conv2.stream_forward(xt, *next(hist), pre_act=act2.kind, pre_slope=act2.slope, add1=x,
-                                         add2=accum if last else None, out_div=out_div if last else 1.0)
+                xt = conv1.stream_forward(x, *next(hist), precision=precision, pre_act=act1.kind, pre_slope=act1.slope)
+                x = conv2.stream_forward(xt, *next(hist), precision=precision, pre_act=act2.kind, pre_slope=act2.slope,
+                                         add1=x, add2=accum if last else None, out_div=out_div if last else 1.0)
             else:
-                x = conv1.stream_forward(x, *next(hist), pre_act=act1.kind, pre_slope=act1.slope, add1=x,
-                                         add2=accum if last else None, out_div=out_div if last else 1.0)
+                x = conv1.stream_forward(x, *next(hist), precision=precision, pre_act=act1.kind, pre_slope=act1.slope,
+                                         add1=x, add2=accum if last else None, out_div=out_div if last else 1.0)
         return x

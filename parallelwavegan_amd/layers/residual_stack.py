@@ -127,15 +127,16 @@ class ResidualStack(torch.nn.Module):
         """The causal convolutions that keep history (the 1 x 1 layers have none)."""
         return [self.stack[1]]
 
-    def stream_forward(self, c, hist):
+    def stream_forward(self, c, hist, precision="fp32"):
         """The causal ``forward`` on the next chunk of a stream; ``hist``: iterator of ``(hist_in, hist_out)`` pairs, one
         per layer of :meth:`stream_layers`.  The skip and second 1 x 1 convolutions keep no history, but they too run
         on the streaming kernel (``H = 0``): the general kernel picks its tile and its split of the reduction from the
-        column count and the batch, so its sums would depend on how the stream is cut into pushes."""
+        column count and the batch, so its sums would depend on how the stream is cut into pushes.
+        ``precision``: passed to all three convolutions."""
         if not self.use_causal_conv:
             raise ValueError("ResidualStack.stream_forward needs use_causal_conv=True")
         a0, conv0, a1, conv1 = self.stack[0], self.stack[1], self.stack[2], self.stack[3]
         with torch.no_grad():
-            skip = stream_pointwise(self.skip_layer, c)
-            t = conv0.stream_forward(c, *next(hist), pre_act=a0.kind, pre_slope=a0.slope)
-            return stream_pointwise(conv1, t, pre_act=a1.kind, pre_slope=a1.slope, add1=skip)
+            skip = stream_pointwise(self.skip_layer, c, precision=precision)
+            t = conv0.stream_forward(c, *next(hist), precision=precision, pre_act=a0.kind, pre_slope=a0.slope)
+            return stream_pointwise(conv1, t, precision=precision, pre_act=a1.kind, pre_slope=a1.slope, add1=skip)

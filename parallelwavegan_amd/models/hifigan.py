@@ -128,25 +128,29 @@ class HiFiGANGenerator(torch.nn.Module):
         return out
 
     @torch.no_grad()
-    def stream_forward(self, c, hist_in, hist_out):
+    def stream_forward(self, c, hist_in, hist_out, precision="fp32"):
         """The causal ``forward`` on the next chunk ``c`` (B, in_channels, n) of a stream -> (B, out_channels, n *
         upsample_factor): the same modules in the same order with the same fused epilogues (MRF running sum through
         ``accum`` / ``out_div``, residual ``add1``, the default-slope LeakyReLU in front of the output convolution,
         tanh), one launch per convolution, no stream forking.  ``hist_in`` / ``hist_out``: one history tensor per layer
-        of :meth:`stream_layers` (``hist_in`` None: start of stream); see :class:`utils.CausalStream`."""
+        of :meth:`stream_layers` (``hist_in`` None: start of stream); see :class:`utils.CausalStream`.  ``precision``:
+        ``"bf16"`` runs every convolution on the bf16-operand stream kernel (the modules' own ``precision`` attributes
+        are not consulted)."""
         layers = self.stream_layers()
         hist = iter(zip(hist_in if hist_in is not None else [None] * len(layers), hist_out))
-        c = self.input_conv.stream_forward(c, *next(hist))
+        c = self.input_conv.stream_forward(c, *next(hist), precision=precision)
         nb = self.num_blocks
         for i in range(self.num_upsamples):
             act, up = self.upsamples[i][0], self.upsamples[i][1]
-            c = up.stream_forward(c, *next(hist), pre_act=act.kind, pre_slope=act.slope)
+            c = up.stream_forward(c, *next(hist), precision=precision, pre_act=act.kind, pre_slope=act.slope)
             cs = None
             for j in range(nb):
-                cs = self.blocks[i * nb + j].stream_forward(c, hist, accum=cs, out_div=float(nb) if j == nb - 1 else 1.0)
+                cs = self.blocks[i * nb + j].stream_forward(c, hist, accum=cs, out_div=float(nb) if j == nb - 1 else 1.0,
+                                                            precision=precision)
             c = cs
         act, conv = self.output_conv[0], self.output_conv[1]
-        return conv.stream_forward(c, *next(hist), pre_act=act.kind, pre_slope=act.slope, post_act="tanh")
+        return conv.stream_forward(c, *next(hist), precision=precision, pre_act=act.kind, pre_slope=act.slope,
+                                   post_act="tanh")
 
     def reset_parameters(self):
         """N(0, 0.01) on conv weights as in the official implementation.

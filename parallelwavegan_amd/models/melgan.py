@@ -138,11 +138,12 @@ class MelGANGenerator(torch.nn.Module, _MelGANNormMixin):
         return out
 
     @torch.no_grad()
-    def stream_forward(self, c, hist_in, hist_out):
+    def stream_forward(self, c, hist_in, hist_out, precision="fp32"):
         """The causal ``forward`` on the next chunk ``c`` (B, in_channels, n) of a stream -> (B, out_channels, n *
         upsample_factor): the same modules in the same order with the same fused epilogues.  ``hist_in`` / ``hist_out``:
         one history tensor per layer of :meth:`stream_layers` (``hist_in`` None: start of stream, which for the
-        reflect-padded layers needs ``utils.CausalStream.warmup_frames`` frames); see :class:`utils.CausalStream`."""
+        reflect-padded layers needs ``utils.CausalStream.warmup_frames`` frames); see :class:`utils.CausalStream`.
+        ``precision``: ``"bf16"`` runs every convolution, the 1 x 1 ones included, on the bf16-operand stream kernel."""
         layers = self.stream_layers()
         hist = iter(zip(hist_in if hist_in is not None else [None] * len(layers), hist_out))
         walk = list(self._stream_walk())
@@ -150,12 +151,12 @@ class MelGANGenerator(torch.nn.Module, _MelGANNormMixin):
         x = c
         for i, m, act, _ in walk:
             if isinstance(m, ResidualStack):
-                x = m.stream_forward(x, hist)
+                x = m.stream_forward(x, hist, precision=precision)
                 continue
             kw = dict(pre_act=act.kind, pre_slope=act.slope) if act is not None else {}
             if i == last_conv and self.use_final_nonlinear_activation:
                 kw["post_act"] = "tanh"
-            x = m.stream_forward(x, *next(hist), **kw)
+            x = m.stream_forward(x, *next(hist), precision=precision, **kw)
         return x
 
     def register_stats(self, stats):

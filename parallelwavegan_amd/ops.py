@@ -214,8 +214,13 @@ def conv1d_bf16_supported(desc):
 
 def pack_weight_bf16(desc, w, scale=None):
     """torch-layout fp32 weight (+ optional weight_norm row scale) -> bf16 MFMA weight image (an opaque byte tensor);
-    the effective weight ``w * scale`` is rounded to bf16 here, once."""
+    the effective weight ``w * scale`` is rounded to bf16 here, once.  The image does not depend on padding, which the
+    packer's geometry check admits only as zero: a reflect- / replicate-padded layer (the causal MelGAN layers, for
+    the bf16 stream kernel) is packed through a descriptor of the same geometry with zero padding."""
     _require_device(w, scale)
+    if desc.pad_mode != PAD["zero"]:
+        desc = ConvDesc.from_buffer_copy(desc)
+        desc.pad_mode = PAD["zero"]
     n = _lib.lib().pwg_conv1d_bf16_packed_weight_bytes(ctypes.byref(desc))
     if n == 0:
         _lib.check(-1, "conv1d_bf16_packed_weight_bytes")
@@ -276,6 +281,40 @@ def conv1d_stream_forward(desc, x, hist_in, hist_out, w_packed, bias=None, add1=
     _lib.check(_lib.lib().pwg_conv1d_stream_forward(ctypes.byref(desc), _ptr(x), _ptr(hist_in), _ptr(hist_out),
                                                     _ptr(w_packed), _ptr(bias), _ptr(add1), _ptr(add2), _ptr(out),
                                                     _stream()), "conv1d_stream_forward")
+    return out
+
+
+def conv1d_stream_bf16_supported(desc):
+    """Does the bf16-operand streaming kernel (csrc/conv1d_stream_bf16.hip) cover this descriptor?  It answers exactly
+    as :func:`conv1d_stream_supported`.  Host logic only; ``_lib.lib().pwg_last_error()`` names the reason for a False."""
+    return bool(_lib.lib().pwg_conv1d_stream_bf16_supported(ctypes.byref(desc)))
+
+
+def conv1d_stream_forward_bf16(desc, x, hist_in, hist_out, w_packed_bf16, bias=None, add1=None, add2=None, out=None):
+    """:func:`conv1d_stream_forward` with bf16 operands: the activated window and the weights (``w_packed_bf16``, the
+    image of :func:`pack_weight_bf16`) are bf16, accumulation / epilogue / tensors / history fp32; ``hist_out`` is
+    bit-identical to the fp32 launch's."""
+    _require_device(x, hist_in, hist_out, bias, add1, add2, out)
+    if not w_packed_bf16.is_cuda or w_packed_bf16.dtype != torch.uint8:
+        raise RuntimeError("conv1d_stream_forward_bf16: w_packed_bf16 must be the device image of pack_weight_bf16")
+    if out is None:
+        out = torch.empty((desc.batch, desc.c_out, desc.t_out), device=x.device, dtype=torch.float32)
+    assert x.numel() == desc.batch * desc.c_in * desc.t_in, (tuple(x.shape), desc.batch, desc.c_in, desc.t_in)
+    assert out.numel() == desc.batch * desc.c_out * desc.t_out
+    n_hist = conv1d_stream_hist_floats(desc)
+    for t in (hist_in, hist_out):
+        assert t is None or t.numel() == n_hist, (tuple(t.shape), n_hist)
+    for t in (add1, add2):
+        assert t is None or t.numel() == out.numel()
+    zdesc = desc
+    if desc.pad_mode != PAD["zero"]:
+        zdesc = ConvDesc.from_buffer_copy(desc)
+        zdesc.pad_mode = PAD["zero"]
+    assert w_packed_bf16.numel() == _lib.lib().pwg_conv1d_bf16_packed_weight_bytes(ctypes.byref(zdesc)), \
+        "conv1d_stream_forward_bf16: w_packed_bf16 is not this layer's bf16 image"
+    _lib.check(_lib.lib().pwg_conv1d_stream_bf16_forward(ctypes.byref(desc), _ptr(x), _ptr(hist_in), _ptr(hist_out),
+                                                         _ptr(w_packed_bf16), _ptr(bias), _ptr(add1), _ptr(add2),
+                                                         _ptr(out), _stream()), "conv1d_stream_bf16_forward")
     return out
 
 

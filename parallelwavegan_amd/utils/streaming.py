@@ -28,7 +28,7 @@ import torch
 
 from .. import _lib
 from ..graphs import GraphedInference
-from ..ops import _ptr, _require_device, _stream, conv1d_stream_supported
+from ..ops import _ptr, _require_device, _stream, conv1d_stream_bf16_supported, conv1d_stream_supported
 
 
 def normalize_transpose(c, mean=None, scale=None):
@@ -178,6 +178,13 @@ class CausalStream:
     two captures), each captured size holds a private pool of all activations, and only the ``max_graph_shapes`` most
     recently used sizes are kept.  A stream whose chunk size varies freely should pass ``use_graph=False``.
 
+    ``precision="bf16"``: every convolution of every push runs with bf16 operands (csrc/conv1d_stream_bf16.hip, DESIGN.md
+    s11.2: the activated window and the weights are rounded to bf16, sums, epilogues, tensors and history stay fp32; the
+    PQMF synthesis stays fp32).  The precision belongs to the stream, is fixed for its life (``.precision``) and neither
+    reads nor writes the modules' own ``precision`` attributes; partition invariance holds bit for bit as in fp32, and a
+    bf16 stream's state is interchangeable with an fp32 stream's.  ``None`` and ``"fp32"`` are the fp32 stream, which
+    refuses a model that ``set_inference_precision`` put in bf16 mode.
+
     Reflect-padded models (causal MelGAN) need the first ``warmup_frames`` frames before anything can be emitted -- an
     utterance shorter than that is one the whole-utterance forward cannot pad either: the stream holds what is pushed
     until then, returning zero-length waveforms, and ``close()`` raises if frames are still held.
@@ -185,11 +192,13 @@ class CausalStream:
 
     max_graph_shapes = 4  # chunk sizes whose graphs are kept (least recently used evicted)
 
-    def __init__(self, model, batch=1, use_graph=True, normalize_before=False):
+    def __init__(self, model, batch=1, use_graph=True, normalize_before=False, precision=None):
         from ..layers.conv import each_conv
         from ..layers.pqmf import PQMF
         from ..models import HiFiGANGenerator, MelGANGenerator
 
+        if precision not in (None, "fp32", "bf16"):
+            raise ValueError(f"CausalStream: precision must be None, 'fp32' or 'bf16', got {precision!r}")
         if not isinstance(model, (HiFiGANGenerator, MelGANGenerator)):
             raise ValueError(f"CausalStream: {model.__class__.__name__} is not supported (only the causal HiFiGANGenerator "
                              "and MelGANGenerator map mel frames to samples layer by layer)")
@@ -208,14 +217,16 @@ class CausalStream:
             if pqmf.subbands > 8:
                 raise ValueError(f"CausalStream: a PQMF of {pqmf.subbands} sub-bands cannot be streamed (the stream kernel "
                                  "covers up to 8)")
-        if any(cv.precision != "fp32" for cv in each_conv(model)):
-            raise ValueError("CausalStream: the model is in bf16 inference precision; the streaming kernel is fp32 "
-                             "(utils.set_inference_precision(model, 'fp32'))")
+        if precision != "bf16" and any(cv.precision != "fp32" for cv in each_conv(model)):
+            raise ValueError("CausalStream: the model is in bf16 inference precision; the fp32 streaming kernel does not "
+                             "read that mode (utils.set_inference_precision(model, 'fp32'), or stream with bf16 operands: "
+                             "CausalStream(model, precision='bf16'))")
         batch = int(batch)
         if batch < 1:
             raise ValueError("CausalStream: batch must be >= 1")
+        supported = conv1d_stream_bf16_supported if precision == "bf16" else conv1d_stream_supported
         for layer, _ in self._layers:
-            if not conv1d_stream_supported(layer.stream_desc(batch, 8)):
+            if not supported(layer.stream_desc(batch, 8)):
                 raise ValueError(f"CausalStream: {layer} cannot be streamed: "
                                  + _lib.lib().pwg_last_error().decode(errors="replace"))
         _require_device(next(model.parameters()))  # no CPU fallback
@@ -225,6 +236,7 @@ class CausalStream:
         self.batch = batch
         self.use_graph = bool(use_graph)
         self.normalize_before = bool(normalize_before)
+        self.precision = precision or "fp32"  # of the stream, fixed for its life
         self.pqmf = pqmf
         self.subbands = out_channels
         self.up = model.upsample_factor * out_channels  # samples per frame
@@ -275,7 +287,8 @@ class CausalStream:
         """``hist_in`` (None: start of stream) / ``hist_out``: one ping-pong half each.  -> (batch, samples)."""
         mean = self.model.mean if self.normalize_before else None
         scale = self.model.scale if self.normalize_before else None
-        y = self.model.stream_forward(normalize_transpose(feats, mean, scale), hist_in, hist_out)
+        y = self.model.stream_forward(normalize_transpose(feats, mean, scale), hist_in, hist_out,
+                                      precision=self.precision)
         if self.pqmf is None:
             return y.reshape(self.batch, -1)
         return self.pqmf.stream_synthesis(y, None if hist_in is None else hist_in[-1], hist_out[-1],

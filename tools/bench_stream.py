@@ -14,7 +14,14 @@ profiles/stream_mb_infer.json.  ``push`` includes the stateful PQMF synthesis; t
 over ``left + n`` frames and ``pqmf.synthesis`` over that output.  The PQMF launch's own time per push comes from the
 library's profiler scope (pwg_prof_*) on eager pushes.
 
-usage: python tools/bench_stream.py [--multiband] [--reps 200] [--repeats 3] [--out profiles/stream_infer.json]
+``--precision bf16``: the bf16-operand stream (``CausalStream(model, precision="bf16")``, csrc/conv1d_stream_bf16.hip)
+against the fp32 stream of the SAME model, same method: graph-replayed ``push`` of the two streams alternate, at the
+table points of DESIGN.md s11 (HiFi-GAN V1 causal 1 / 16 streams x 4 / 8 / 32 frames, MelGAN recipe 1 / 16 x 8; with
+``--multiband`` the multi-band geometry at 1 / 16 x 8 / 32 as well), into profiles/stream_bf16_infer.json.  The time
+inside the two convolution kernels per push comes from the library's profiler scope on eager pushes.
+
+usage: python tools/bench_stream.py [--multiband] [--precision bf16] [--reps 200] [--repeats 3]
+                                    [--out profiles/stream_infer.json]
 """
 import argparse
 import json
@@ -97,13 +104,29 @@ def main():
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--multiband", action="store_true")
+    ap.add_argument("--precision", choices=("fp32", "bf16"), default="fp32")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    args.out = args.out or os.path.join(ROOT, "profiles", "stream_mb_infer.json" if args.multiband else "stream_infer.json")
+    default_out = "stream_bf16_infer.json" if args.precision == "bf16" else (
+        "stream_mb_infer.json" if args.multiband else "stream_infer.json")
+    args.out = args.out or os.path.join(ROOT, "profiles", default_out)
     dev = torch.device("cuda:0")
     rec = {"tool": "tools/bench_stream.py", "device": torch.cuda.get_device_name(0), "reps": args.reps,
            "repeats": args.repeats, "models": {}, "points": []}
     gen = torch.Generator(device="cpu").manual_seed(100)
+    if args.precision == "bf16":
+        families = [("hifigan_v1_causal", build_model, CHUNKS), ("melgan_recipe_causal", build_melgan, MELGAN_CHUNKS)]
+        if args.multiband:
+            families.append(("multi_band_melgan_v2_causal", build_multiband, MB_CHUNKS))
+        for name, build, chunks in families:
+            measure_precision(rec, name, build(dev), chunks, gen, args, dev)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(rec, f, indent=1)
+            f.write("\n")
+        print(json.dumps({"out": args.out, "points": [[p["model"], p["streams"], p["chunk_frames"], p["fp32_push_ms"],
+                                                       p["bf16_push_ms"]] for p in rec["points"]]}))
+        return
     if args.multiband:
         measure(rec, "multi_band_melgan_v2_causal", build_multiband(dev), MB_CHUNKS, gen, args, dev)
     else:
@@ -169,6 +192,50 @@ def measure(rec, name, model, chunks, gen, args, dev):
             print(json.dumps({k: p[k] for k in ("model", "streams", "chunk_frames", "stream_push_ms", "halo_forward_ms",
                                                 "spread_ms", "speedup_stream_over_halo", "launches_per_push_stream",
                                                 "launches_per_forward_halo")}), file=sys.stderr, flush=True)
+
+
+def measure_precision(rec, name, model, chunks, gen, args, dev):
+    """fp32 ``push`` and bf16 ``push`` of the same model, alternating."""
+    pqmf = getattr(model, "pqmf", None)
+    up = model.upsample_factor * (pqmf.subbands if pqmf is not None else 1)
+    rec["models"][name] = {"workload": "seeded weights, weight norm removed",
+                           "stream_state_bytes_per_stream": CausalStream(model, use_graph=False).state_bytes}
+    for b in STREAMS:
+        for n in chunks:
+            feats = torch.randn(b, n, 80, generator=gen).to(dev)
+            s32 = CausalStream(model, batch=b, use_graph=True)
+            s16 = CausalStream(model, batch=b, use_graph=True, precision="bf16")
+            for _ in range(6):  # start of stream and both graph directions of both
+                s32.push(feats)
+                s16.push(feats)
+            t32, t16 = [], []
+            for _ in range(args.repeats):
+                t32.append(event_ms(lambda: s32.push(feats), args.reps))
+                t16.append(event_ms(lambda: s16.push(feats), args.reps))
+            kernel_ms, n_launch = {}, {}
+            for prec, kernel in (("fp32", "conv1d_stream_kernel"), ("bf16", "conv1d_stream_bf16_kernel")):
+                eager = CausalStream(model, batch=b, use_graph=False, precision=prec)
+                while eager.frames_out == 0:
+                    eager.push(feats)
+                eager.push(feats)
+                with ops.profile() as prof:
+                    for _ in range(10):
+                        eager.push(feats)
+                kernel_ms[prec] = round(prof.results[kernel]["ms"] / 10, 4)
+                n_launch[prec] = prof.results[kernel]["launches"] // 10
+            med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+            spread = max(max(t32) - min(t32), max(t16) - min(t16))
+            p = {"model": name, "streams": b, "chunk_frames": n, "samples_per_push": b * n * up,
+                 "fp32_push_ms": round(med(t32), 4), "fp32_runs_ms": [round(t, 4) for t in t32],
+                 "bf16_push_ms": round(med(t16), 4), "bf16_runs_ms": [round(t, 4) for t in t16],
+                 "spread_ms": round(spread, 4), "speedup_bf16_over_fp32": round(med(t32) / med(t16), 3),
+                 "bf16_not_slower_beyond_spread": med(t16) <= med(t32) + spread,
+                 "bf16_faster_beyond_spread": med(t16) + spread < med(t32),
+                 "conv_kernel_ms_per_eager_push": kernel_ms, "conv_launches_per_push": n_launch}
+            rec["points"].append(p)
+            print(json.dumps({k: p[k] for k in ("model", "streams", "chunk_frames", "fp32_push_ms", "bf16_push_ms", "spread_ms",
+                                                "speedup_bf16_over_fp32", "conv_kernel_ms_per_eager_push")}),
+                  file=sys.stderr, flush=True)
 
 
 if __name__ == "__main__":
