@@ -390,6 +390,26 @@ int pwg_wavenet_pack_weights(const pwg_wavenet_desc* d, const float* w_dil, cons
 int pwg_wavenet_layer_forward(const pwg_wavenet_desc* d, const float* x, const float* c, const float* skips,
                               const float* packed, const float* b_dil, const float* b_skip, const float* b_out,
                               float* x_out, float* skips_out, float* z_out, float* g_out, void* stream);
+/* ---- stateful streaming form of the CAUSAL layer (fp32; csrc/wavenet_stream.hip) ----
+ * The layer formula above on the next d->t = n columns of a stream, d->causal = 1 (layers/residual_block.py:74-76,
+ * 102-140: left-only padding (kernel-1)*dilation): the dilated taps read columns n - 2d, n - d, n of
+ * X = concat(hist_in (batch, 64, H), x (batch, 64, n)), H = (kernel-1)*dilation = 2d; the residual is x.
+ * hist_in == NULL is the start of a stream: zero left context.  The same launch writes hist_out = the last H raw
+ * columns of X, also when n < H.  hist_in and hist_out must be distinct buffers; skips may be NULL (first layer);
+ * skips_out may alias skips; x_out must not alias x.  c: (batch, 80, n).
+ * Geometry: 64 residual / 128 gate / 64 skip / 80 aux channels, kernel 3, causal, any dilation >= 1, any n >= 1,
+ * batch 1 .. 65535; pwg_wavenet_stream_supported is pure host logic (no device needed; pwg_last_error names the reason
+ * for 0).  pwg_wavenet_stream_hist_floats = batch * 64 * (kernel-1) * dilation (0 = unsupported).
+ * `packed`: the pwg_wavenet_pack_weights image, unchanged -- its row order (tap 0, 1, 2, aux) does not depend on
+ * causality; the packer refuses a causal descriptor, so pack through a non-causal one of the same channels.
+ * Deterministic, and the sum order of an output element depends on the layer alone (not on n, the batch or the chunk's
+ * position): any partition of a stream gives bit-identical results.
+ * These three symbols are purely additive -- no existing signature or behaviour changes.                         */
+int pwg_wavenet_stream_supported(const pwg_wavenet_desc* d);
+size_t pwg_wavenet_stream_hist_floats(const pwg_wavenet_desc* d);
+int pwg_wavenet_stream_forward(const pwg_wavenet_desc* d, const float* x, const float* c, const float* skips,
+                               const float* hist_in, float* hist_out, const float* packed, const float* b_dil,
+                               const float* b_skip, const float* b_out, float* x_out, float* skips_out, void* stream);
 /* ---- bf16-operand inference form of the same layer (opt-in; csrc/wavenet_bf16.hip) ----
  * The definition of the bf16-operand convolution (pwg_conv1d_bf16_*, above) applied to each of the layer's four
  * convolutions, in ONE launch:
@@ -517,6 +537,15 @@ int pwg_gate_backward(const float* z, const float* dout, float* dz, int32_t batc
 int pwg_stretch_conv_forward(const float* x, const float* w, float* y, int64_t rows, int32_t t_in,
                              int32_t scale, int32_t kernel, int32_t pad_left, int32_t channels,
                              int32_t freq_kernel, int32_t act, float slope, void* stream);
+/* The causal stage (kernel 2*scale+1, pad_left 2*scale, freq_kernel 1) on the next n input columns of a stream:
+ *   y[r][t] = act(sum_j w[j] * X[r][floor((t + j - 2*scale) / scale)]),  t in [0, n*scale),
+ *   X = concat(hist_in (rows, 2), x (rows, n)); hist_in == NULL: zeros (start of stream = the stage's zero padding).
+ * One launch writes y (rows, n*scale) and hist_out (rows, 2) = the last 2 columns of X (also for n = 1).  hist_in and
+ * hist_out must be distinct buffers.  Fixed j-ascending sum order: partitions of a stream agree bit for bit.
+ * freq_kernel != 1 is refused (pwg_last_error names the reason).  Purely additive.                              */
+int pwg_stretch_conv_stream(const float* x, const float* hist_in, float* hist_out, const float* w, float* y,
+                            int64_t rows, int32_t n, int32_t scale, int32_t freq_kernel, int32_t act, float slope,
+                            void* stream);
 size_t pwg_stretch_conv_backward_workspace_floats(int32_t kernel, int32_t freq_kernel);
 int pwg_stretch_conv_backward(const float* dy, const float* x, const float* w, float* dx, float* dw,
                               int64_t rows, int32_t t_in, int32_t scale, int32_t kernel, int32_t pad_left,

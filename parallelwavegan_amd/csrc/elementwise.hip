@@ -484,6 +484,37 @@ __global__ __launch_bounds__(256) void stretch_conv_fwd4_kernel(const float* __r
     *reinterpret_cast<float4*>(y + i * 4) = make_float4(o4[0], o4[1], o4[2], o4[3]);
   }
 }
+// Stateful (streaming) form of the causal stage (pad = 2 s, output trimmed to the stretched length, no channel-axis taps):
+// output column t of a chunk of n input columns reads X[floor((t + j - 2 s) / s)], j = 0 .. 2 s, of
+// X = concat(hist_in (rows, 2), x (rows, n)) -- exactly two raw input columns of the past (zeros at start of stream, the
+// whole-utterance kernel's zero padding).  Threads past the outputs write hist_out = the last 2 columns of X in the same
+// launch.  One fmaf chain per output, j ascending: the sum order does not depend on n or on the chunk's position.
+__global__ __launch_bounds__(256) void stretch_conv_stream_kernel(const float* __restrict__ x, const float* __restrict__ hist_in,
+                                                                  float* __restrict__ hist_out, const float* __restrict__ w,
+                                                                  float* __restrict__ y, long rows, int n, int s, int act,
+                                                                  float slope) {
+  const int t_out = n * s;
+  const long total = rows * t_out;
+  GRID_STRIDE(i, total + 2 * rows) {
+    if (i < total) {
+      const long r = i / t_out;
+      const int t = (int)(i - r * t_out);
+      const float* xr = x + r * n;
+      float acc = 0.f;
+      for (int j = 0; j <= 2 * s; ++j) {
+        const int q = (t + j) / s - 2;  // = floor((t + j - 2 s) / s), in [-2, n)
+        const float v = q >= 0 ? xr[q] : (hist_in ? hist_in[2 * r + 2 + q] : 0.f);
+        acc = __builtin_fmaf(w[j], v, acc);
+      }
+      y[i] = apply_act(acc, act, slope);
+    } else {
+      const long k = i - total;
+      const long r = k >> 1;
+      const int col = n + (int)(k & 1);  // column of X; the last two are n, n + 1
+      hist_out[k] = col >= 2 ? x[r * n + col - 2] : (hist_in ? hist_in[2 * r + col] : 0.f);
+    }
+  }
+}
 __global__ void stretch_conv_bwd_data_kernel(const float* dy, const float* w, float* dx, long rows, int t_in, int s,
                                              int k, int pad, int channels, int fk) {
   const int t_out = t_in * s;
@@ -1058,6 +1089,26 @@ extern "C" int pwg_stretch_conv_forward(const float* x, const float* w, float* y
   }
   LAUNCH1D(stretch_conv_fwd_kernel, n, stream, x, w, y, (long)rows, t_in, scale, kernel, pad_left, channels, freq_kernel,
            act, slope);
+  return PWG_OK;
+}
+
+extern "C" int pwg_stretch_conv_stream(const float* x, const float* hist_in, float* hist_out, const float* w, float* y,
+                                       int64_t rows, int32_t n, int32_t scale, int32_t freq_kernel, int32_t act,
+                                       float slope, void* stream) {
+  PWG_REQUIRE(x && hist_out && w && y, PWG_ERR_NULL, "stretch_conv_stream: NULL pointer");
+  PWG_REQUIRE(hist_in != hist_out, PWG_ERR_BAD_SHAPE,
+              "stretch_conv_stream: hist_in and hist_out must be distinct buffers (other threads read the history)");
+  PWG_REQUIRE(freq_kernel == 1, PWG_ERR_UNSUPPORTED,
+              "stretch_conv_stream: freq_kernel = %d (only 1: taps along the channel axis are not built for streams)",
+              freq_kernel);
+  PWG_REQUIRE(act == PWG_ACT_NONE || act == PWG_ACT_LEAKY_RELU || act == PWG_ACT_RELU || act == PWG_ACT_TANH,
+              PWG_ERR_UNSUPPORTED, "stretch_conv_stream: activation %d", act);
+  PWG_REQUIRE(rows > 0 && n > 0 && scale > 0 && (long)n * scale < (1L << 31), PWG_ERR_BAD_SHAPE,
+              "stretch_conv_stream: bad geometry (rows %lld, n %d, scale %d)", (long long)rows, n, scale);
+  const long total = rows * (long)n * scale;
+  ProfScope prof((hipStream_t)stream, "stretch_conv_stream_kernel", 2.0 * total * (2 * scale + 1),
+                 4.0 * (rows * (double)(n + 4) + total));
+  LAUNCH1D(stretch_conv_stream_kernel, total + 2 * rows, stream, x, hist_in, hist_out, w, y, (long)rows, n, scale, act, slope);
   return PWG_OK;
 }
 

@@ -22,21 +22,13 @@
 // the two 1x1 convolutions (one K = 64 contraction with 128 rows); the residual x comes from the resident centre
 // window.  Training additionally stores z and g (the backward pass reads them).
 #include "common.h"
+#include "wavenet_gate.h"  // geometry constants, f32x16, gate_fast (shared with wavenet_stream.hip)
 
 #include <stdint.h>
 #include <type_traits>
 #include <stdlib.h>
 
 namespace pwg {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-constexpr int WN_R = 64;     // residual channels
-constexpr int WN_G = 128;    // gate channels
-constexpr int WN_S = 64;     // skip channels
-constexpr int WN_K = 3;      // taps
-constexpr int WN_COLS = 64;  // columns per workgroup
 
 struct WnArgs {
   const float* x;       // (B, 64, T)
@@ -57,16 +49,6 @@ struct WnArgs {
   int dbg;  // timing experiments only (PWG_WN_DBG): 1 = phase-1 weights loaded once, 2 = no tanh / exp, 4 = no epilogue
             // loads / stores, 8 = no operand DMA
 };
-
-// tanh(t) * sigmoid(s) on the hardware exp2 / rcp (1 ulp each): sigmoid(v) = 1 / (1 + 2^(-v log2 e)),
-// tanh(t) = 2 sigmoid(2 t) - 1; saturates correctly (2^inf = inf -> rcp = 0).  Absolute error ~1e-7, against
-// 8 % of the kernel for libm's tanhf + expf (profiles/r03_wavenet_ablation.txt).
-__device__ __forceinline__ float gate_fast(float t, float s) {
-  const float L2E = 1.4426950408889634f;
-  const float sg = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-s * L2E));
-  const float th = 2.f * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-2.f * L2E * t)) - 1.f;
-  return th * sg;
-}
 
 template <int AUX>
 __global__ __launch_bounds__(256, 2) void wavenet_layer_kernel(WnArgs a) {

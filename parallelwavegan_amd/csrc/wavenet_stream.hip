@@ -1,0 +1,386 @@
+// wavenet_stream.hip -- stateful (streaming) form of the causal gated residual layer of the Parallel WaveGAN generator:
+// ONE launch per layer and chunk, fp32 on the exact-fp32 MFMA.
+//
+// A causal layer (layers/residual_block.py:74-76,102-140 of the reference: the dilated convolution is padded (k-1)*d on
+// both sides and the future part of its output dropped, i.e. left-only padding) reads x at n - 2d, n - d and n, so from
+// the past it needs only the last H = (k-1)*d = 2d columns of its raw input.  One launch takes the chunk x (B, 64, n),
+// the aux features c (B, 80, n), the running skip sum and the history hist_in (B, 64, H), computes
+//
+//     X      = concat(hist_in, x)                                   (hist_in == NULL: start of stream, zeros)
+//     z      = sum_tap W_dil[tap] X[n + (tap - 2) d] + b_dil + W_aux c      (128 rows; K = 3 * 64 + 80 = 272)
+//     g      = tanh(z[:64]) * sigmoid(z[64:])
+//     skips' = (W_skip g + b_skip + skips) * skip_mul
+//     x'     = (W_out g + b_out + x) * out_mul
+//
+// and writes hist_out = the last H columns of X (raw), also when n < H (part of hist_in carries over).  hist_in and
+// hist_out are distinct buffers: other workgroups of the launch read hist_in while this one writes hist_out.
+//
+// The kernel is wavenet_layer_kernel<80> of csrc/wavenet.hip (a 4-wave workgroup per 64 columns of one item, a 272 x 64
+// fp32 operand tile in LDS, v_mfma_f32_32x32x2_f32 with the A operands streamed from the SAME pre-swizzled image --
+// its row order tap0, tap1, tap2, aux does not depend on causality -- gate_fast, two workgroups per CU) with three
+// differences:
+//   * two-source tap windows.  Window `tap` starts at chunk-relative column f0 = n0 + (tap - 2) d.  Columns < 0 come
+//     from hist_in[H + f] (zeros at start of stream), columns >= 0 from x.  A window that lies wholly inside one
+//     source keeps the 16-B LDS-DMA pass (16 B per lane at 4-B aligned addresses, all lanes in range: the form the
+//     whole-utterance kernel uses); a window that straddles the boundary, leaves the data, or is all start-of-stream
+//     zeros is staged per sample through registers with range checks (plain loads, plain LDS stores).
+//   * the residual x is the LAST tap window (rows 128..191), so the epilogue's wave-private transposition scratch
+//     cannot sit in rows 128.. as in the whole-utterance kernel.  It sits in the aux rows 192..271, which every wave
+//     has finished reading when phase 1 ends (there is a workgroup barrier between phase 1 and the first scratch
+//     write); the 80 rows hold one 32 x 36 tile per wave, so the skip tile and the out tile are transposed one after the
+//     other through the same scratch.  Nobody writes rows 128..191.
+//   * the history write: the item's 64 * H elements of hist_out are dealt over the item's column workgroups, at the end
+//     of the same launch.
+//
+// Sum order.  An output element is sum over K in the fixed order of the image -- tap 0, tap 1, tap 2, aux; inside a tap
+// channel ascending, two channels per MFMA step -- accumulated in one MFMA accumulator register, then the K = 64
+// contraction over g in channel order, then + bias, + skips / + x, * scale.  One workgroup owns a column over the whole
+// reduction: no split across workgroups or waves, no workspace, no atomics.  That order depends on the layer alone --
+// not on n, the batch, the chunk's position in the stream, or the column's place in the tile (a column is one MFMA
+// lane position; its accumulator sees the same operand sequence wherever it sits, a padded or history operand is the
+// same value through either staging path) -- so any partition of a stream gives bit-identical results.  DESIGN.md s11.3.
+#include "common.h"
+#include "wavenet_gate.h"
+
+#include <stdint.h>
+
+namespace pwg {
+namespace {
+
+constexpr int WS_AUX = 80;
+constexpr int WS_ROWS = WN_K * WN_R + WS_AUX;  // 272 operand rows
+
+struct WnStreamArgs {
+  const float* x;        // (B, 64, n)
+  const float* c;        // (B, 80, n)
+  const float* skips;    // (B, 64, n) or NULL
+  const float* hist_in;  // (B, 64, H) or NULL (start of stream)
+  float* hist_out;       // (B, 64, H)
+  const float* w1;       // image [ROWS / 8][4 row tiles][64 lanes][4]
+  const float* w2;       // image [8][4 row tiles][64 lanes][4]
+  const float* b_dil;    // (128), may be NULL
+  const float* b_skip;   // (64), may be NULL
+  const float* b_out;    // (64), may be NULL
+  float* x_out;          // (B, 64, n)
+  float* skips_out;      // (B, 64, n) (may alias skips)
+  int n, dil;
+  float out_mul, skip_mul;
+  int vec_ok;  // x_out / skips / skips_out are 16-B aligned
+};
+
+__global__ __launch_bounds__(256, 2) void wavenet_stream_kernel(WnStreamArgs a) {
+  constexpr int NQ1 = WS_ROWS / 8;  // 16-B weight records per lane and row tile in phase 1 (4 k-steps each)
+  constexpr int NQ2 = WN_R / 8;     // phase 2: K = 64 rows of g
+  extern __shared__ __attribute__((aligned(16))) float tile[];  // [ROWS][64]; rows 0..63 are overwritten by g
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int h = wave >> 1, cn = wave & 1;
+  const int l31 = lane & 31, lhi = lane >> 5;
+  const int b = blockIdx.y;
+  const int n0 = blockIdx.x * WN_COLS;
+  const int n = a.n;
+  const int H = 2 * a.dil;
+  const float* __restrict__ xb = a.x + (long)b * WN_R * n;
+  const float* __restrict__ cb = a.c + (long)b * WS_AUX * n;
+  const float* __restrict__ hb = a.hist_in ? a.hist_in + (long)b * WN_R * H : nullptr;
+
+  // ---- stage the operand tile: window `tap` of X starts at chunk-relative column n0 + (tap - 2) d
+  {
+    __amdgpu_buffer_rsrc_t x_rs = uniform_buffer_rsrc(xb, (unsigned)(WN_R * n) * 4u);
+    __amdgpu_buffer_rsrc_t c_rs = uniform_buffer_rsrc(cb, (unsigned)(WS_AUX * n) * 4u);
+    __amdgpu_buffer_rsrc_t h_rs = uniform_buffer_rsrc(hb ? hb : xb, hb ? (unsigned)(WN_R * H) * 4u : 0u);
+    for (int q = wave; q < WS_ROWS / 4; q += 4) {  // 4 rows (1 KiB of LDS) per wave instruction
+      const int r0 = 4 * q;
+      const bool is_x = r0 < WN_K * WN_R;
+      const int tap = r0 / WN_R;
+      const int f0 = is_x ? n0 + (tap - 2) * a.dil : n0;  // first column of the window (< 0: history)
+      const int ch0 = is_x ? r0 - tap * WN_R : r0 - WN_K * WN_R;
+      const int in_chunk = __builtin_amdgcn_readfirstlane((f0 >= 0 && f0 + WN_COLS <= n) ? 1 : 0);
+      const int in_hist = __builtin_amdgcn_readfirstlane((is_x && hb != nullptr && f0 + WN_COLS <= 0) ? 1 : 0);
+      if (in_chunk) {
+        const unsigned off = (unsigned)((ch0 + (lane >> 4)) * n + f0 + 4 * (lane & 15)) * 4u;
+        if (is_x) __builtin_amdgcn_raw_ptr_buffer_load_lds(x_rs, (lds_ptr_t)(tile + r0 * WN_COLS), 16, off, 0, 0, 0);
+        else __builtin_amdgcn_raw_ptr_buffer_load_lds(c_rs, (lds_ptr_t)(tile + r0 * WN_COLS), 16, off, 0, 0, 0);
+      } else if (in_hist) {
+        // (f0 >= -H: H + f0 >= 0, and H + f0 + 64 <= H)
+        const unsigned off = (unsigned)((ch0 + (lane >> 4)) * H + H + f0 + 4 * (lane & 15)) * 4u;
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(h_rs, (lds_ptr_t)(tile + r0 * WN_COLS), 16, off, 0, 0, 0);
+      } else {
+        // the window straddles history and chunk, leaves the chunk on the right, or is start-of-stream padding:
+        // per sample, range-checked, zeros outside
+        const int f = f0 + lane;
+        float v[4];
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+          v[rr] = 0.f;
+          if (is_x) {
+            if (f < 0) {
+              if (hb) v[rr] = hb[(long)(ch0 + rr) * H + (H + f)];
+            } else if (f < n) {
+              v[rr] = xb[(long)(ch0 + rr) * n + f];
+            }
+          } else if (f < n) {
+            v[rr] = cb[(long)(ch0 + rr) * n + f];
+          }
+        }
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) tile[(r0 + rr) * WN_COLS + lane] = v[rr];
+      }
+    }
+  }
+
+  // biases of this lane's accumulator rows: row = 8 * (r >> 2) + 4 * lhi + (r & 3) of the wave's 32-row block
+  f32x16 bt, bs, bsk, bo;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int row = h * 32 + 8 * (r >> 2) + 4 * lhi + (r & 3);
+    bt[r] = a.b_dil ? a.b_dil[row] : 0.f;
+    bs[r] = a.b_dil ? a.b_dil[WN_R + row] : 0.f;
+    bsk[r] = a.b_skip ? a.b_skip[row] : 0.f;
+    bo[r] = a.b_out ? a.b_out[row] : 0.f;
+  }
+
+  f32x16 acc[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+
+  // ---- phase 1: z rows [32 h, +32) (tanh half) and [64 + 32 h, +32) (sigmoid half) over K = ROWS
+  {
+    const float4* wa = reinterpret_cast<const float4*>(a.w1) + (h * 64 + lane);        // row tile h
+    const float4* wb = reinterpret_cast<const float4*>(a.w1) + ((2 + h) * 64 + lane);  // row tile 2 + h
+    float4 A[3][2];
+    A[0][0] = wa[0];
+    A[0][1] = wb[0];
+    A[1][0] = wa[4 * 64];
+    A[1][1] = wb[4 * 64];
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's share of the DMA pass (and its first weight records)
+    __syncthreads();
+    const float* bl = tile + lhi * WN_COLS + cn * 32 + l31;  // + (8 q + 2 j) * 64
+    float B0[4], B1[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) B0[j] = bl[(2 * j) * WN_COLS];
+#pragma unroll
+    for (int q = 0; q < NQ1; ++q) {
+      const int qn = q + 2 < NQ1 ? q + 2 : NQ1 - 1;
+      A[(q + 2) % 3][0] = wa[(long)qn * 4 * 64];
+      A[(q + 2) % 3][1] = wb[(long)qn * 4 * 64];
+      float(&Bc)[4] = (q & 1) ? B1 : B0;
+      float(&Bn)[4] = (q & 1) ? B0 : B1;
+      const int q1 = q + 1 < NQ1 ? q + 1 : q;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) Bn[j] = bl[(8 * q1 + 2 * j) * WN_COLS];
+      __builtin_amdgcn_sched_barrier(0);
+      const float4 a0 = A[q % 3][0], a1 = A[q % 3][1];
+      const float av0[4] = {a0.x, a0.y, a0.z, a0.w}, av1[4] = {a1.x, a1.y, a1.z, a1.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av0[j], Bc[j], acc[0], 0, 0, 0);
+        acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av1[j], Bc[j], acc[1], 0, 0, 0);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+
+  // ---- gate in registers; g to LDS rows 0..63 (every wave is done with the first window and with the aux rows)
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int rl = 8 * (r >> 2) + 4 * lhi + (r & 3);
+    tile[(h * 32 + rl) * WN_COLS + cn * 32 + l31] = gate_fast(acc[0][r] + bt[r], acc[1][r] + bs[r]);
+    acc[0][r] = 0.f;
+    acc[1][r] = 0.f;
+  }
+  __syncthreads();
+
+  // ---- phase 2: skip rows [32 h, +32) and out rows [32 h, +32) over K = 64 rows of g
+  {
+    const float4* wa = reinterpret_cast<const float4*>(a.w2) + (h * 64 + lane);
+    const float4* wb = reinterpret_cast<const float4*>(a.w2) + ((2 + h) * 64 + lane);
+    const float* bl = tile + lhi * WN_COLS + cn * 32 + l31;
+    float4 A0[NQ2], A1[NQ2];
+#pragma unroll
+    for (int q = 0; q < NQ2; ++q) {
+      A0[q] = wa[q * 4 * 64];
+      A1[q] = wb[q * 4 * 64];
+    }
+#pragma unroll
+    for (int q = 0; q < NQ2; ++q) {
+      float Bv[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) Bv[j] = bl[(8 * q + 2 * j) * WN_COLS];
+      const float av0[4] = {A0[q].x, A0[q].y, A0[q].z, A0[q].w}, av1[4] = {A1[q].x, A1[q].y, A1[q].z, A1[q].w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av0[j], Bv[j], acc[0], 0, 0, 0);
+        acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av1[j], Bv[j], acc[1], 0, 0, 0);
+      }
+    }
+  }
+
+  // ---- epilogue: D layout col = lane & 31 (time), rows as above.  Each wave transposes its two 32 x 32 result tiles,
+  // one after the other, through a private 32 x 36 scratch in the aux rows (dead since phase 1) so that a lane owns 4
+  // consecutive samples of a row: 16-B loads of the skip sum, 16-B stores of both outputs.  The residual comes from the
+  // last tap window (rows 128..191 = x[n]), which no wave writes.  (Wave-private scratch: no workgroup barrier, the
+  // wave's own LDS accesses are ordered.)
+  float* scr = tile + (WN_K * WN_R) * WN_COLS + wave * (32 * 36);
+  const int trow = lane >> 3, tcol = (lane & 7) * 4;
+  const int nq = n0 + cn * 32 + tcol;
+  const bool vec = ((n & 3) == 0) && a.vec_ok;
+  const long ob = (long)b * WN_R * n + nq;
+#pragma unroll
+  for (int pass = 0; pass < 2; ++pass) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int rl = 8 * (r >> 2) + 4 * lhi + (r & 3);
+      if (pass == 0) {
+        scr[rl * 36 + l31] = acc[0][r] + bsk[r];
+      } else {
+        const float xc = tile[(2 * WN_R + h * 32 + rl) * WN_COLS + cn * 32 + l31];  // last window = x[n]
+        scr[rl * 36 + l31] = (acc[1][r] + bo[r] + xc) * a.out_mul;
+      }
+    }
+#pragma unroll
+    for (int ps = 0; ps < 4; ++ps) {
+      const int rl = ps * 8 + trow;
+      const long o = ob + (long)(h * 32 + rl) * n;
+      float4 v = *reinterpret_cast<const float4*>(scr + rl * 36 + tcol);
+      if (vec) {
+        if (nq < n) {  // (n % 4 == 0: a float4 is inside the chunk or outside it)
+          if (pass == 0) {
+            if (a.skips) {
+              const float4 k = *reinterpret_cast<const float4*>(a.skips + o);
+              v.x += k.x; v.y += k.y; v.z += k.z; v.w += k.w;
+            }
+            if (a.skip_mul != 1.0f) { v.x *= a.skip_mul; v.y *= a.skip_mul; v.z *= a.skip_mul; v.w *= a.skip_mul; }
+            *reinterpret_cast<float4*>(a.skips_out + o) = v;
+          } else {
+            *reinterpret_cast<float4*>(a.x_out + o) = v;
+          }
+        }
+      } else {
+        const float e4[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          if (nq + e < n) {
+            if (pass == 0) {
+              float s = e4[e] + (a.skips ? a.skips[o + e] : 0.f);
+              if (a.skip_mul != 1.0f) s *= a.skip_mul;
+              a.skips_out[o + e] = s;
+            } else {
+              a.x_out[o + e] = e4[e];
+            }
+          }
+        }
+      }
+    }
+  }
+
+  // ---- hist_out = last H columns of concat(hist_in, x), raw; the item's elements are dealt over its workgroups
+  {
+    const int total = WN_R * H;
+    float* __restrict__ ho = a.hist_out + (long)b * WN_R * H;
+#pragma unroll 4
+    for (int i = blockIdx.x * 256 + tid; i < total; i += gridDim.x * 256) {
+      const int ci = i / H, hh = i - ci * H;
+      const int t = n - H + hh;
+      float v = 0.f;
+      if (t >= 0)
+        v = xb[(long)ci * n + t];
+      else if (hb)
+        v = hb[(long)ci * H + n + hh];
+      ho[i] = v;
+    }
+  }
+}
+
+static int wavenet_stream_geometry(const pwg_wavenet_desc* d) {
+  PWG_REQUIRE(d != nullptr, PWG_ERR_NULL, "wavenet_stream: NULL descriptor");
+  PWG_REQUIRE(d->causal, PWG_ERR_UNSUPPORTED,
+              "wavenet_stream: not a causal layer (a stream keeps only past columns; non-causal layers look ahead)");
+  PWG_REQUIRE(d->kernel == WN_K, PWG_ERR_UNSUPPORTED, "wavenet_stream: kernel = %d (only kernel 3)", d->kernel);
+  PWG_REQUIRE(d->residual_channels == WN_R && d->gate_channels == WN_G && d->skip_channels == WN_S, PWG_ERR_UNSUPPORTED,
+              "wavenet_stream: residual / gate / skip channels = %d / %d / %d (only 64 / 128 / 64)", d->residual_channels,
+              d->gate_channels, d->skip_channels);
+  PWG_REQUIRE(d->aux_channels == WS_AUX, PWG_ERR_UNSUPPORTED, "wavenet_stream: aux channels = %d (only 80)",
+              d->aux_channels);
+  PWG_REQUIRE(d->batch >= 1 && d->batch <= 65535, PWG_ERR_UNSUPPORTED, "wavenet_stream: batch = %d (1 .. 65535)", d->batch);
+  PWG_REQUIRE(d->t >= 1, PWG_ERR_BAD_SHAPE, "wavenet_stream: t = %d columns per push (>= 1)", d->t);
+  PWG_REQUIRE(d->dilation >= 1, PWG_ERR_BAD_SHAPE, "wavenet_stream: dilation = %d (>= 1)", d->dilation);
+  // byte offsets inside one item of x / c / the history are 32-bit (buffer addressing), element indices int
+  PWG_REQUIRE((long)WN_G * d->t * 4 < (1L << 31), PWG_ERR_UNSUPPORTED, "wavenet_stream: t = %d columns per push is too long",
+              d->t);
+  PWG_REQUIRE((long)WN_R * 2 * d->dilation * 4 < (1L << 31), PWG_ERR_UNSUPPORTED,
+              "wavenet_stream: dilation = %d: the history of one item is too long", d->dilation);
+  return PWG_OK;
+}
+
+}  // namespace
+}  // namespace pwg
+
+using namespace pwg;
+
+extern "C" int pwg_wavenet_stream_supported(const pwg_wavenet_desc* d) {
+  return wavenet_stream_geometry(d) == PWG_OK ? 1 : 0;
+}
+
+extern "C" size_t pwg_wavenet_stream_hist_floats(const pwg_wavenet_desc* d) {
+  if (wavenet_stream_geometry(d) != PWG_OK) return 0;
+  return (size_t)d->batch * WN_R * (size_t)(d->kernel - 1) * d->dilation;
+}
+
+extern "C" int pwg_wavenet_stream_forward(const pwg_wavenet_desc* d, const float* x, const float* c, const float* skips,
+                                          const float* hist_in, float* hist_out, const float* packed, const float* b_dil,
+                                          const float* b_skip, const float* b_out, float* x_out, float* skips_out,
+                                          void* stream_) {
+  const int rc = wavenet_stream_geometry(d);
+  if (rc != PWG_OK) return rc;
+  PWG_REQUIRE(x && c && packed && x_out && skips_out && hist_out, PWG_ERR_NULL, "wavenet_stream_forward: NULL pointer");
+  PWG_REQUIRE(hist_in != hist_out, PWG_ERR_BAD_SHAPE,
+              "wavenet_stream_forward: hist_in and hist_out must be distinct buffers (other workgroups read the history)");
+  PWG_REQUIRE(x != x_out, PWG_ERR_BAD_SHAPE,
+              "wavenet_stream_forward: x_out must not alias x (tiles read their neighbours' samples)");
+  auto al = [](const void* p, unsigned m) { return (reinterpret_cast<uintptr_t>(p) & m) == 0; };
+  PWG_REQUIRE(al(x, 3) && al(c, 3) && al(hist_in, 3) && al(hist_out, 3) && al(packed, 15), PWG_ERR_BAD_SHAPE,
+              "wavenet_stream_forward: unaligned tensor (4 B; the weight image 16 B)");
+  hipStream_t stream = (hipStream_t)stream_;
+  WnStreamArgs a;
+  a.x = x;
+  a.c = c;
+  a.skips = skips;
+  a.hist_in = hist_in;
+  a.hist_out = hist_out;
+  a.w1 = packed;
+  a.w2 = packed + (size_t)WS_ROWS * WN_G;
+  a.b_dil = b_dil;
+  a.b_skip = b_skip;
+  a.b_out = b_out;
+  a.x_out = x_out;
+  a.skips_out = skips_out;
+  a.n = d->t;
+  a.dil = d->dilation;
+  a.out_mul = d->out_mul;
+  a.skip_mul = d->skip_mul;
+  a.vec_ok = al(x_out, 15) && al(skips, 15) && al(skips_out, 15);
+  const size_t lds = (size_t)WS_ROWS * WN_COLS * sizeof(float);
+  void (*kern)(WnStreamArgs) = wavenet_stream_kernel;
+  if (!lds_limit_is_set(reinterpret_cast<const void*>(kern), lds)) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    PWG_REQUIRE(e == hipSuccess, PWG_ERR_LAUNCH, "wavenet_stream_forward: cannot raise the LDS limit to %zu: %s", lds,
+                hipGetErrorString(e));
+  }
+  const double samples = (double)d->batch * d->t;
+  const double hist = (double)d->batch * WN_R * 2.0 * d->dilation;
+  const double flops = 2.0 * samples * (WN_G * (double)WS_ROWS + (double)(WN_S + WN_R) * WN_R);
+  const double bytes = 4.0 * (samples * (WN_R * 4 + WS_AUX + (skips ? WN_S : 0)) + 2.0 * hist) +
+                       4.0 * ((double)WS_ROWS * WN_G + (double)WN_R * (WN_S + WN_R));
+  maybe_poison_lds(stream);
+  {
+    ProfScope prof(stream, "wavenet_stream_kernel", flops, bytes);
+    hipLaunchKernelGGL(kern, dim3(ceil_div(d->t, WN_COLS), d->batch), dim3(256), lds, stream, a);
+  }
+  PWG_CHECK_LAUNCH("wavenet_stream_forward");
+  return PWG_OK;
+}

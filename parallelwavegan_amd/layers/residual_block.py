@@ -170,6 +170,63 @@ class WaveNetResidualBlock(torch.nn.Module):
                                    f"it ({why})")
         return None
 
+    # ---- stateful streaming of the causal block (csrc/wavenet_stream.hip): one launch per chunk
+    def history_shape(self, batch):
+        """Shape of one history buffer: the last ``(k - 1) * d`` raw input columns (allocate two: ping-pong)."""
+        return (batch, self.conv.in_channels, (self.conv.kernel_size - 1) * self.conv.dilation)
+
+    def history_columns_at_start(self):
+        return 1  # (zero-padded: the first push needs nothing but itself)
+
+    def stream_desc(self, batch, n, skip_scale=1.0):
+        """Descriptor of one push of ``n`` columns through the streaming layer kernel."""
+        return self.fused_desc(batch, n, skip_scale)
+
+    def stream_unsupported_reason(self, batch=1, n=1):
+        """None if the streaming layer kernel covers this block at (batch, n), else the reason it does not (host
+        logic only).  A non-causal block is not a geometry question: ``stream_forward`` raises ValueError for it."""
+        if self.conv1x1_aux is None:
+            return "the block has no aux (conditioning) convolution"
+        if any(cv.has_spectral_norm or cv.pad_mode != "zero" for cv in self.fused_convs()):
+            return "spectral norm or non-zero padding"
+        if self.conv1x1_out.out_channels != self.conv.in_channels:
+            return "out channels differ from the residual channels"
+        if not ops.wavenet_stream_supported(self.stream_desc(batch, n)):
+            return _lib.lib().pwg_last_error().decode(errors="replace")
+        return None
+
+    def stream_image(self):
+        """The layer's fp32 weight image for the streaming kernel: the image of ``fused_image`` -- its row order (tap 0,
+        1, 2, aux) does not depend on causality -- packed through a non-causal descriptor of the same channels, because
+        the packer's geometry check admits only the layers its own forward covers."""
+        def pack(*ws):
+            d = self.fused_desc(1, 64)
+            d.causal = 0
+            return ops.wavenet_pack_weights(d, *ws)
+
+        return group_image(self, "_stream_img", self.fused_convs(), pack)
+
+    def stream_forward(self, x, c, hist_in, hist_out, skips=None, skip_scale=1.0, inplace_skips=False):
+        """The causal block on the next ``x.shape[-1]`` columns of a stream whose previous columns are ``hist_in`` (None:
+        start of stream, zero left context) -> (x_out, skips + s); also writes ``hist_out`` (a buffer distinct from
+        ``hist_in``).  One launch; fp32 only.  ``inplace_skips``: the new running sum is written into ``skips``."""
+        if not self.use_causal_conv:
+            raise ValueError("WaveNetResidualBlock: streaming needs use_causal_conv=True")
+        if any(cv is not None and cv.precision != "fp32" for cv in self.fused_convs()):
+            raise RuntimeError("WaveNetResidualBlock is in bf16 inference precision: the streaming layer kernel is fp32 "
+                               "(utils.set_inference_precision(model, 'fp32'))")
+        reason = self.stream_unsupported_reason(x.shape[0], x.shape[-1]) if x.dim() == 3 else "x is not (B, C, n)"
+        if reason is None and self.dropout > 0.0 and self.training:
+            reason = "dropout in training mode"
+        if reason is not None:
+            raise RuntimeError("the streaming layer kernel does not cover this block: " + reason)
+        with torch.no_grad():
+            b_d, b_s, b_o = (None if cv.bias is None else cv.bias.detach()
+                             for cv in (self.conv, self.conv1x1_skip, self.conv1x1_out))
+            return ops.wavenet_stream_forward(self.stream_desc(x.shape[0], x.shape[-1], skip_scale), x.contiguous(),
+                                              c.contiguous(), skips, hist_in, hist_out, self.stream_image(), b_d, b_s, b_o,
+                                              skips_out=skips if (inplace_skips and skips is not None) else None)
+
     def forward(self, x, c, skips=None, skip_scale=1.0, chain_aux=False, inplace_skips=False):
         """Returns (x_out, skips + s) -- the running skip sum is an addend of the skip conv's epilogue
         (``skip_scale`` is the final ``sqrt(1/layers)`` of the generator, applied by the last block).

@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from .. import functional as Fn
+from .. import ops
 from .residual_block import Conv1d
 
 
@@ -127,6 +128,94 @@ class UpsampleNetwork(torch.nn.Module):
                                        2 * scale if self.use_causal_conv else scale, self.act, self.slope)
         return c
 
+    # ---- stateful streaming of the causal network (csrc/elementwise.hip, pwg_stretch_conv_stream)
+    def stream_unsupported_reason(self):
+        """None if every stage can be streamed, else the reason (host logic only)."""
+        if not self.use_causal_conv:
+            return "streaming needs use_causal_conv=True"
+        for i in self._stages:
+            if self.up_layers[i].mode != "nearest":
+                return f"interpolate mode {self.up_layers[i].mode!r} (only 'nearest')"
+            if self.up_layers[i + 1].kernel_size[0] != 1:
+                return (f"freq_axis_kernel_size = {self.up_layers[i + 1].kernel_size[0]} (only 1: taps along the channel "
+                        "axis are not built for streams)")
+        return None
+
+    def stream_layers(self, channels=80):
+        """``(stage, rate)`` per upsampling stage in visiting order; ``rate``: the stage's input columns per input
+        column of the network.  A stage keeps the last two raw input columns of every row (``channels`` rows per item:
+        the network itself is agnostic of the mel width)."""
+        reason = self.stream_unsupported_reason()
+        if reason is not None:
+            raise ValueError(f"{self.__class__.__name__}: {reason}")
+        out, rate = [], 1
+        for i in self._stages:
+            out.append((StretchStageStream(self, i, channels), rate))
+            rate *= self.up_layers[i].x_scale
+        return out
+
+    @torch.no_grad()
+    def stream_forward(self, c, hist_in, hist_out):
+        """The causal ``forward`` on the next chunk c (B, C, n) of a stream -> (B, C, n * prod(scales)); one launch per
+        stage.  ``hist_in`` / ``hist_out``: one (B, C, 2) tensor per stage (``hist_in`` None: start of stream)."""
+        stages = self.stream_layers()
+        for k, (stage, _) in enumerate(stages):
+            c = stage.stream_forward(c, None if hist_in is None else hist_in[k], hist_out[k])
+        return c
+
+
+class StretchStageStream:
+    """One stage of a causal :class:`UpsampleNetwork` as a stateful stream layer (a view, no parameters of its own)."""
+
+    def __init__(self, net, index, channels):
+        self.net, self.index, self.channels = net, index, int(channels)
+        self.scale = net.up_layers[index].x_scale
+
+    def history_shape(self, batch):
+        """Shape of one history buffer: the last two raw input columns (allocate two: ping-pong)."""
+        return (batch, self.channels, 2)
+
+    def history_columns_at_start(self):
+        return 1  # zero-padded
+
+    def stream_forward(self, c, hist_in, hist_out):
+        conv = self.net.up_layers[self.index + 1]
+        with torch.no_grad():
+            return ops.stretch_conv_stream(c, hist_in, hist_out, conv.weight_tensor().detach(), self.scale,
+                                           conv.kernel_size[0], self.net.act, self.net.slope)
+
+    def __repr__(self):
+        return f"StretchStageStream(scale={self.scale})"
+
+
+class ConvInStream:
+    """The causal ``conv_in`` of :class:`ConvInUpsampleNetwork` as a stateful stream layer: kernel
+    ``aux_context_window + 1`` over the current frame and the ``aux_context_window`` frames before it.  The start of a
+    stream replicates the first frame -- what ``inference()``'s replicate padding of the mel gives on the left (the
+    right padding only feeds outputs the causal trim drops)."""
+
+    def __init__(self, conv, context):
+        self.conv, self.context = conv, int(context)
+
+    def stream_desc(self, batch, n):
+        cv = self.conv
+        return ops.make_conv_desc(batch, cv.in_channels, cv.out_channels, n, n, cv.kernel_size, 1, 1, self.context, 1,
+                                  transposed=False, pad_mode="replicate")
+
+    def history_shape(self, batch):
+        return (batch, self.conv.in_channels, self.context)
+
+    def history_columns_at_start(self):
+        return 1
+
+    def stream_forward(self, c, hist_in, hist_out):
+        from .causal_conv import _stream_forward
+
+        return _stream_forward(self.conv, self.stream_desc(c.shape[0], c.shape[-1]), c, hist_in, hist_out, {})
+
+    def __repr__(self):
+        return f"ConvInStream({self.conv})"
+
 
 class ConvInUpsampleNetwork(torch.nn.Module):
     """Context conv (k = 2*aux_context_window+1, no padding) + UpsampleNetwork (layers/upsample.py:131-194)."""
@@ -149,3 +238,29 @@ class ConvInUpsampleNetwork(torch.nn.Module):
 
     def forward(self, c):
         return self.upsample(self.conv_in(c))
+
+    # ---- stateful streaming of the causal network
+    def stream_layers(self):
+        """``(layer, rate)`` of the stateful layers in visiting order: ``conv_in`` (history: the last
+        ``aux_context_window`` frames; absent without a context window), then the upsampling stages."""
+        stages = self.upsample.stream_layers(self.conv_in.out_channels)  # ValueError for a non-causal network
+        if self.aux_context_window > 0:
+            return [(ConvInStream(self.conv_in, self.aux_context_window), 1)] + stages
+        return stages
+
+    @torch.no_grad()
+    def stream_forward(self, c, hist_in, hist_out):
+        """The causal ``forward`` on the next frames c (B, C, n) of a stream (frame t of the stream is column
+        ``t + aux_context_window`` of the whole-utterance input) -> (B, C, n * prod(scales)).  ``hist_in`` / ``hist_out``:
+        one tensor per layer of :meth:`stream_layers` (``hist_in`` None: start of stream, ``conv_in`` replicates the first
+        frame)."""
+        k = 0
+        if self.aux_context_window > 0:
+            layer = ConvInStream(self.conv_in, self.aux_context_window)
+            c = layer.stream_forward(c, None if hist_in is None else hist_in[0], hist_out[0])
+            k = 1
+        else:
+            from .causal_conv import stream_pointwise
+
+            c = stream_pointwise(self.conv_in, c)
+        return self.upsample.stream_forward(c, None if hist_in is None else hist_in[k:], hist_out[k:])

@@ -101,6 +101,65 @@ class ParallelWaveGANGenerator(torch.nn.Module, _WeightNormMixin):
         x = self.last_conv_layers[1](skips, pre_act="relu")
         return self.last_conv_layers[3](x, pre_act="relu")
 
+    # ---- stateful streaming of the causal generator (utils.PWGStream)
+    def stream_unsupported_reason(self, batch=1):
+        """None if the causal generator can be streamed layer by layer, else the reason (host logic only)."""
+        if not all(f.use_causal_conv for f in self.conv_layers):
+            return "streaming needs use_causal_conv=True"
+        if self.upsample_net is None:
+            return "upsample_conditional_features=False: the stream maps mel frames to samples through the upsampler"
+        if not isinstance(self.upsample_net, (upsample.UpsampleNetwork, upsample.ConvInUpsampleNetwork)):
+            return (f"upsample_net={self.upsample_net.__class__.__name__!r} is not built for streams (only UpsampleNetwork "
+                    "and ConvInUpsampleNetwork)")
+        net = self.upsample_net.upsample if isinstance(self.upsample_net, upsample.ConvInUpsampleNetwork) \
+            else self.upsample_net
+        reason = net.stream_unsupported_reason()
+        if reason is not None:
+            return "the mel upsampler: " + reason
+        for f in self.conv_layers:
+            reason = f.stream_unsupported_reason(batch, 8)
+            if reason is not None:
+                return f"{f.__class__.__name__}: {reason}"
+        return None
+
+    def stream_layers(self):
+        """``(layer, rate)`` of every stateful layer in the order :meth:`stream_forward` visits them: the upsampler's
+        (``conv_in``, then one per stage), then the residual blocks; ``rate``: the layer's input columns per mel frame."""
+        reason = self.stream_unsupported_reason()
+        if reason is not None:
+            raise ValueError(f"{self.__class__.__name__}: {reason}")
+        if isinstance(self.upsample_net, upsample.ConvInUpsampleNetwork):
+            out = self.upsample_net.stream_layers()
+        else:
+            out = self.upsample_net.stream_layers(self.aux_channels)
+        return out + [(f, self.upsample_factor) for f in self.conv_layers]
+
+    @torch.no_grad()
+    def stream_forward(self, z, c, hist_in, hist_out):
+        """The causal ``forward`` on the next chunk of a stream: noise z (B, 1, n * upsample_factor) and mel frames
+        c (B, C, n) -- frame t of the stream is column ``t + aux_context_window`` of the whole-utterance input -- ->
+        (B, out_channels, n * upsample_factor).  The same modules in the same order: the upsampler's stream launches, the
+        1 x 1 convolutions through the streaming kernel (its sum order does not depend on n), one launch per residual
+        block; the running skip sum is updated in place and the last block applies sqrt(1 / layers).  ``hist_in`` /
+        ``hist_out``: one history tensor per layer of :meth:`stream_layers` (``hist_in`` None: start of stream); see
+        :class:`utils.PWGStream`."""
+        from ..layers.causal_conv import stream_pointwise
+
+        n_layers = len(self.stream_layers())
+        n_up = n_layers - len(self.conv_layers)
+        assert len(hist_out) == n_layers and (hist_in is None or len(hist_in) == n_layers)
+        c = self.upsample_net.stream_forward(c, None if hist_in is None else hist_in[:n_up], hist_out[:n_up])
+        assert c.size(-1) == z.size(-1)
+        x = stream_pointwise(self.first_conv, z)
+        skips = None
+        n = len(self.conv_layers)
+        for i, f in enumerate(self.conv_layers):
+            x, skips = f.stream_forward(x, c, None if hist_in is None else hist_in[n_up + i], hist_out[n_up + i],
+                                        skips=skips, skip_scale=math.sqrt(1.0 / n) if i == n - 1 else 1.0,
+                                        inplace_skips=True)
+        x = stream_pointwise(self.last_conv_layers[1], skips, pre_act="relu")
+        return stream_pointwise(self.last_conv_layers[3], x, pre_act="relu")
+
     @staticmethod
     def _get_receptive_field_size(layers, stacks, kernel_size, dilation=lambda x: 2 ** x):
         assert layers % stacks == 0

@@ -447,6 +447,56 @@ def wavenet_layer_forward(desc, x, c, skips, packed, b_dil, b_skip, b_out, save=
     return x_out, skips_out, z, g
 
 
+def wavenet_stream_supported(desc):
+    """Does the streaming form of the causal layer (csrc/wavenet_stream.hip) cover this geometry, ``desc.t`` = columns
+    per push?  Host logic only (no device needed); ``_lib.lib().pwg_last_error()`` names the reason for a False."""
+    return bool(_lib.lib().pwg_wavenet_stream_supported(ctypes.byref(desc)))
+
+
+def wavenet_stream_hist_floats(desc):
+    """Floats of one history buffer of the layer: ``batch * 64 * (kernel - 1) * dilation`` (0: unsupported)."""
+    return _lib.lib().pwg_wavenet_stream_hist_floats(ctypes.byref(desc))
+
+
+def wavenet_stream_forward(desc, x, c, skips, hist_in, hist_out, packed, b_dil, b_skip, b_out, skips_out=None):
+    """One chunk of a causal gated residual layer's stream in one launch -> (x_out, skips_out); also writes
+    ``hist_out`` = the last H columns of ``concat(hist_in, x)``.  ``hist_in`` None: start of stream (zero left context).
+    ``hist_in`` and ``hist_out`` must be distinct buffers; ``skips_out`` may be ``skips`` itself."""
+    _require_device(x, c, skips, hist_in, hist_out, packed, b_dil, b_skip, b_out, skips_out)
+    assert x.numel() == desc.batch * desc.residual_channels * desc.t, (tuple(x.shape), desc.batch, desc.t)
+    assert c.numel() == desc.batch * desc.aux_channels * desc.t, (tuple(c.shape), desc.batch, desc.t)
+    n_hist = wavenet_stream_hist_floats(desc)
+    for t in (hist_in, hist_out):
+        assert t is None or n_hist == 0 or t.numel() == n_hist, (tuple(t.shape), n_hist)
+    x_out = torch.empty_like(x)
+    if skips_out is None:
+        skips_out = torch.empty_like(x)
+    for t in (skips, skips_out):
+        assert t is None or t.numel() == x.numel()
+    _lib.check(_lib.lib().pwg_wavenet_stream_forward(ctypes.byref(desc), _ptr(x), _ptr(c), _ptr(skips), _ptr(hist_in),
+                                                     _ptr(hist_out), _ptr(packed), _ptr(b_dil), _ptr(b_skip), _ptr(b_out),
+                                                     _ptr(x_out), _ptr(skips_out), _stream()), "wavenet_stream_forward")
+    return x_out, skips_out
+
+
+def stretch_conv_stream(x, hist_in, hist_out, w, scale, freq_kernel=1, act=None, slope=0.0):
+    """One chunk of a causal upsampler stage's stream (nearest stretch x ``scale`` + the 1 x (2 scale + 1) conv with
+    left padding 2 scale) in one launch: x (B, C, n) -> (B, C, n * scale); ``hist_in`` / ``hist_out`` (B, C, 2): the
+    last two raw input columns (``hist_in`` None: zeros), distinct buffers."""
+    x = x.contiguous()
+    w = w.reshape(-1).contiguous()
+    _require_device(x, hist_in, hist_out, w)
+    b, ch, n = x.shape
+    assert w.numel() == (2 * scale + 1) * freq_kernel, (w.numel(), scale, freq_kernel)
+    for t in (hist_in, hist_out):
+        assert t is None or t.numel() == b * ch * 2, tuple(t.shape)
+    y = torch.empty((b, ch, n * scale), device=x.device, dtype=torch.float32)
+    _lib.check(_lib.lib().pwg_stretch_conv_stream(_ptr(x), _ptr(hist_in), _ptr(hist_out), _ptr(w), _ptr(y), b * ch, n,
+                                                  int(scale), int(freq_kernel), ACT[act], float(slope), _stream()),
+               "stretch_conv_stream")
+    return y
+
+
 def wavenet_bf16_supported(desc):
     """Does the bf16-operand one-launch layer (csrc/wavenet_bf16.hip) cover this geometry?  Host logic only (no device
     needed); ``_lib.lib().pwg_last_error()`` names the reason for a False."""

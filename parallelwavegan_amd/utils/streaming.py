@@ -155,7 +155,51 @@ class ChunkedSynthesizer:
         return self.synthesize_many([feat], normalize_before)[0]
 
 
-class CausalStream:
+def _capture_directions(halves, run):
+    """Graphs for both directions (A -> B, B -> A) of one chunk shape: ``run(hist_in, hist_out)`` on static inputs ->
+    {cur: (graph, static_out)}.  The warm-up runs write history: both halves are saved and put back, so capturing never
+    advances a stream."""
+    saved = [[t.clone() for t in half] for half in halves]
+    out = {}
+    for cur in (0, 1):
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(2):  # fills the weight caches / sets kernel attributes outside the capture
+                run(halves[cur], halves[1 - cur])
+        torch.cuda.current_stream().wait_stream(side)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            static_out = run(halves[cur], halves[1 - cur])
+        out[cur] = (g, static_out)
+    for half, keep in zip(halves, saved):
+        for t, k in zip(half, keep):
+            t.copy_(k)
+    return out
+
+
+class _StreamGraphs:
+    """The captured graphs of a stream (``_graphs``: chunk shape -> entry, most recently used last; ``_state``: the
+    model's parameter state they were captured under; ``_watch``: a ``GraphedInference`` asked for that state only)."""
+
+    max_graph_shapes = 4  # chunk sizes whose graphs are kept (least recently used evicted)
+
+    def _graph_entry(self, key, capture):
+        """The entry of chunk shape ``key``, captured by ``capture()`` on first use.  All graphs are dropped when the
+        model's parameter state changed, so a replay never uses old weights."""
+        state = self._watch._param_state()
+        if state != self._state:
+            self._graphs, self._state = {}, state
+        entry = self._graphs.pop(key, None)
+        if entry is None:
+            while len(self._graphs) >= self.max_graph_shapes:
+                del self._graphs[next(iter(self._graphs))]  # least recently used chunk shape
+            entry = capture()
+        self._graphs[key] = entry  # most recently used last
+        return entry
+
+
+class CausalStream(_StreamGraphs):
     """Stateful streaming synthesis for ``HiFiGANGenerator`` and ``MelGANGenerator`` built with
     ``use_causal_conv=True``: ``push`` takes the next mel frames of ``batch`` lock-step streams and returns their
     samples; any partition of the same frames gives bit-identical audio, equal to the whole-utterance ``forward`` up to
@@ -201,7 +245,8 @@ class CausalStream:
             raise ValueError(f"CausalStream: precision must be None, 'fp32' or 'bf16', got {precision!r}")
         if not isinstance(model, (HiFiGANGenerator, MelGANGenerator)):
             raise ValueError(f"CausalStream: {model.__class__.__name__} is not supported (only the causal HiFiGANGenerator "
-                             "and MelGANGenerator map mel frames to samples layer by layer)")
+                             "and MelGANGenerator map mel frames to samples layer by layer; a causal "
+                             "ParallelWaveGANGenerator, which also takes noise, streams through utils.PWGStream)")
         self._layers = model.stream_layers()  # ValueError for a non-causal model
         out_channels = model.output_conv[1].conv.out_channels if isinstance(model, HiFiGANGenerator) else \
             self._layers[-1][0].conv.out_channels
@@ -297,24 +342,8 @@ class CausalStream:
     def _capture(self, feats):
         """Graphs for both directions of one chunk shape.  The warm-up runs write history: both halves are saved and
         put back, so capturing never advances the stream."""
-        saved = [[t.clone() for t in half] for half in self._halves]
         static_in = feats.clone()
-        out = {}
-        for cur in (0, 1):
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(2):  # fills the weight caches / sets kernel attributes outside the capture
-                    self._run(static_in, self._halves[cur], self._halves[1 - cur])
-            torch.cuda.current_stream().wait_stream(side)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                static_out = self._run(static_in, self._halves[cur], self._halves[1 - cur])
-            out[cur] = (g, static_out)
-        for half, keep in zip(self._halves, saved):
-            for t, k in zip(half, keep):
-                t.copy_(k)
-        return static_in, out
+        return static_in, _capture_directions(self._halves, lambda hi, ho: self._run(static_in, hi, ho))
 
     @torch.no_grad()
     def push(self, feats):
@@ -350,17 +379,7 @@ class CausalStream:
         else:
             hist_in, hist_out = self._halves[self._cur], self._halves[1 - self._cur]
             if self.use_graph and n_emit == n_cols:  # (a multi-band stream still inside the PQMF delay: eager)
-                state = self._watch._param_state()
-                if state != self._state:
-                    self._graphs, self._state = {}, state
-                key = (n, feats.shape[2])
-                entry = self._graphs.pop(key, None)
-                if entry is None:
-                    while len(self._graphs) >= self.max_graph_shapes:
-                        del self._graphs[next(iter(self._graphs))]  # least recently used chunk shape
-                    entry = self._capture(feats)
-                self._graphs[key] = entry  # most recently used last
-                static_in, graphs = entry
+                static_in, graphs = self._graph_entry((n, feats.shape[2]), lambda: self._capture(feats))
                 g, static_out = graphs[self._cur]
                 static_in.copy_(feats, non_blocking=True)
                 g.replay()
@@ -402,6 +421,186 @@ class CausalStream:
         if held:
             raise RuntimeError(f"CausalStream: {held} frame(s) were pushed but the reflect-padded start of this model "
                                f"needs {self.warmup_frames} before the first sample can be emitted")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            self.close()
+        return False
+
+
+class PWGStream(_StreamGraphs):
+    """Stateful streaming synthesis for ``ParallelWaveGANGenerator`` built with ``use_causal_conv=True``: ``push`` takes
+    the next mel frames (and, optionally, the noise for their samples) of ``batch`` lock-step streams and returns their
+    samples, one launch per layer: the upsampler's ``conv_in`` and stages, the 1 x 1 convolutions and the 30 gated
+    residual blocks each run their stream kernel on the chunk (csrc/wavenet_stream.hip, csrc/elementwise.hip,
+    csrc/conv1d_stream.hip).  Any partition of the same frames and noise gives bit-identical audio,
+    equal to the whole-utterance ``forward`` up to fp32 summation order.  fp32 only.
+
+    State: ``conv_in`` keeps the last ``aux_context_window`` frames, an upsampling stage the last 2 columns of its
+    input, a residual block the last ``2 * dilation`` columns of its input (``state_bytes``: both ping-pong halves).
+    ``reset()``: the next push starts an utterance as ``model.inference`` does -- ``conv_in`` sees its first frame
+    replicated to the left, every other layer zeros.  ``reset(context)`` seeds ``conv_in`` with ``aux_context_window``
+    real frames instead (the frames before a cut): the stream then equals ``model.forward(z, concat(context, frames,
+    anything))``.
+
+    ``use_graph``, ``max_graph_shapes`` and the parameter-state watch are those of :class:`CausalStream`: steady-state
+    pushes of one chunk size replay two captured graphs; the first push of an utterance started without context runs
+    eagerly.  Noise is never drawn inside a graph: it is written into the graph's static buffer before the replay.
+    """
+
+    warmup_frames = 1  # zero / replicate start: the first frame can be synthesised at once
+
+    def __init__(self, model, batch=1, use_graph=True, normalize_before=False):
+        from ..layers.conv import each_conv
+        from ..layers.upsample import ConvInStream
+        from ..models import ParallelWaveGANGenerator
+
+        if not isinstance(model, ParallelWaveGANGenerator):
+            raise ValueError(f"PWGStream: {model.__class__.__name__} is not supported (only the causal "
+                             "ParallelWaveGANGenerator; HiFiGANGenerator and MelGANGenerator stream through CausalStream)")
+        batch = int(batch)
+        if batch < 1:
+            raise ValueError("PWGStream: batch must be >= 1")
+        reason = model.stream_unsupported_reason(batch)
+        if reason is not None:
+            raise ValueError(f"PWGStream: {reason}")
+        if model.in_channels != 1 or model.out_channels != 1:
+            raise ValueError(f"PWGStream: in_channels / out_channels = {model.in_channels} / {model.out_channels} (the "
+                             "stream takes one noise row and emits one waveform per stream)")
+        if any(cv.precision != "fp32" for cv in each_conv(model)):
+            raise ValueError("PWGStream: the model is in bf16 inference precision; the streaming layer kernel is fp32 "
+                             "(utils.set_inference_precision(model, 'fp32'))")
+        self._layers = model.stream_layers()
+        for layer, _ in self._layers:
+            if isinstance(layer, ConvInStream) and not conv1d_stream_supported(layer.stream_desc(batch, 8)):
+                raise ValueError(f"PWGStream: {layer} cannot be streamed: "
+                                 + _lib.lib().pwg_last_error().decode(errors="replace"))
+        _require_device(next(model.parameters()))  # no CPU fallback
+        if normalize_before and not (hasattr(model, "mean") and hasattr(model, "scale")):
+            raise ValueError("PWGStream: normalize_before=True needs model.register_stats(...)")
+        self.model = model.eval()
+        self.batch = batch
+        self.use_graph = bool(use_graph)
+        self.normalize_before = bool(normalize_before)
+        self.precision = "fp32"
+        self.up = model.upsample_factor  # samples per frame
+        self._context = model.aux_context_window if isinstance(self._layers[0][0], ConvInStream) else 0
+        dev = next(model.parameters()).device
+        self._halves = [[torch.zeros(layer.history_shape(batch), device=dev) for layer, _ in self._layers]
+                        for _ in range(2)]
+        self._watch = GraphedInference(model)  # (only its parameter-state key is used)
+        self._state = None
+        self._graphs = {}
+        self.reset()
+
+    @property
+    def state_bytes(self):
+        """Bytes of history held on the device (both ping-pong halves)."""
+        return sum(t.numel() * t.element_size() for half in self._halves for t in half)
+
+    def _features(self, feats):
+        """(B, n, C) features -> (B, C, n), normalised with the model's statistics if the stream says so."""
+        mean = self.model.mean if self.normalize_before else None
+        scale = self.model.scale if self.normalize_before else None
+        return normalize_transpose(feats, mean, scale)
+
+    @torch.no_grad()
+    def reset(self, context=None):
+        """Back to start of stream.  ``context`` None: the next push starts from ``conv_in``'s replicated first frame and
+        zero history everywhere else (``model.inference``).  ``context`` (batch, aux_context_window, C) or
+        (aux_context_window, C): those frames are ``conv_in``'s history, every other layer starts from zeros
+        (``model.forward`` on ``concat(context, frames, anything)``)."""
+        self._cur = 0          # which half holds the current history
+        self._started = False  # False: the next run passes hist_in = None
+        self.frames_in = 0
+        self.frames_out = 0
+        self.samples_out = 0
+        if context is None:
+            return
+        if self._context == 0:
+            raise ValueError("PWGStream.reset: the model has no aux_context_window, so there is no context to seed")
+        dev = self._halves[0][0].device
+        context = torch.as_tensor(context, dtype=torch.float32).to(dev)
+        if context.dim() == 2:
+            context = context.unsqueeze(0).expand(self.batch, -1, -1)
+        if context.dim() != 3 or context.shape[0] != self.batch or context.shape[1] != self._context:
+            raise ValueError(f"PWGStream.reset: expected ({self._context}, C) or ({self.batch}, {self._context}, C) context "
+                             f"frames, got {tuple(context.shape)}")
+        for t in self._halves[0]:
+            t.zero_()
+        self._halves[0][0].copy_(self._features(context.contiguous()))
+        self._started = True
+
+    def _run(self, feats, z, hist_in, hist_out):
+        """``hist_in`` (None: start of stream) / ``hist_out``: one ping-pong half each.  -> (batch, samples)."""
+        return self.model.stream_forward(z, self._features(feats), hist_in, hist_out).reshape(self.batch, -1)
+
+    def _capture(self, feats, z):
+        static_in, static_z = feats.clone(), z.clone()
+        return static_in, static_z, _capture_directions(self._halves, lambda hi, ho: self._run(static_in, static_z, hi, ho))
+
+    @torch.no_grad()
+    def push(self, feats, noise=None):
+        """feats: (n, C) or (batch, n, C) float features; noise: (batch, n * up) or (n * up,) (the same for every
+        stream), drawn with ``torch.randn`` on the device if omitted -> (batch, n * up) fp32.  The result is the caller's
+        own tensor (not a graph's static buffer)."""
+        dev = self._halves[0][0].device
+        feats = torch.as_tensor(feats, dtype=torch.float32).to(dev)
+        if feats.dim() == 2:
+            feats = feats.unsqueeze(0)
+        if feats.dim() != 3 or feats.shape[0] != self.batch:
+            raise ValueError(f"PWGStream.push: expected (n, C) or ({self.batch}, n, C) features, got {tuple(feats.shape)}")
+        feats = feats.contiguous()
+        n = feats.shape[1]
+        if noise is not None:
+            noise = torch.as_tensor(noise, dtype=torch.float32).to(dev)
+            if noise.dim() == 1:
+                noise = noise.unsqueeze(0).expand(self.batch, -1)
+            if tuple(noise.shape) != (self.batch, n * self.up):
+                raise ValueError(f"PWGStream.push: expected ({n * self.up},) or ({self.batch}, {n * self.up}) noise for "
+                                 f"{n} frame(s), got {tuple(noise.shape)}")
+            noise = noise.reshape(self.batch, 1, n * self.up).contiguous()
+        self.frames_in += n
+        if n == 0:
+            return torch.empty((self.batch, 0), device=dev, dtype=torch.float32)
+        if not self._started:
+            # start of stream: the layers' own padding; once per utterance, eager
+            z = noise if noise is not None else torch.randn(self.batch, 1, n * self.up, device=dev)
+            y = self._run(feats, z, None, self._halves[0])
+            self._cur, self._started = 0, True
+        else:
+            hist_in, hist_out = self._halves[self._cur], self._halves[1 - self._cur]
+            if self.use_graph:
+                def capture():
+                    return self._capture(feats, torch.zeros(self.batch, 1, n * self.up, device=dev))
+
+                static_in, static_z, graphs = self._graph_entry((n, feats.shape[2]), capture)
+                g, static_out = graphs[self._cur]
+                static_in.copy_(feats, non_blocking=True)
+                if noise is None:
+                    static_z.normal_()  # (outside the graph: a replay never draws)
+                else:
+                    static_z.copy_(noise, non_blocking=True)
+                g.replay()
+                y = static_out.clone()
+            else:
+                z = noise if noise is not None else torch.randn(self.batch, 1, n * self.up, device=dev)
+                y = self._run(feats, z, hist_in, hist_out)
+            self._cur = 1 - self._cur
+        self.frames_out += n
+        self.samples_out += y.shape[1]
+        return y
+
+    def push_pcm16(self, feats, noise=None):
+        """``push`` through the float -> PCM16 conversion: (batch, samples) int16."""
+        return to_pcm16(self.push(feats, noise))
+
+    def close(self):
+        """End of the utterance.  Nothing is held back (``warmup_frames`` = 1, no filterbank delay): a no-op kept for
+        symmetry with :class:`CausalStream`."""
 
     def __enter__(self):
         return self

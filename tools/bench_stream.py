@@ -20,7 +20,13 @@ table points of DESIGN.md s11 (HiFi-GAN V1 causal 1 / 16 streams x 4 / 8 / 32 fr
 ``--multiband`` the multi-band geometry at 1 / 16 x 8 / 32 as well), into profiles/stream_bf16_infer.json.  The time
 inside the two convolution kernels per push comes from the library's profiler scope on eager pushes.
 
-usage: python tools/bench_stream.py [--multiband] [--precision bf16] [--reps 200] [--repeats 3]
+``--model pwg``: the causal Parallel WaveGAN (PWG.v1 geometry, use_causal_conv=True) through ``utils.PWGStream`` -- one
+launch per gated layer on the chunk (csrc/wavenet_stream.hip) -- against halo recompute, same method: pushes of 4 / 8 /
+32 frames at 1 and 16 streams, into profiles/stream_pwg_infer.json.  The halo side is ONE graph of the package's own
+whole-utterance causal ``forward`` over ``left + n`` frames (plus the context window), ``left`` from
+``receptive_field_frames``, on static noise; ``push`` is given its noise too (it copies it into the graph's buffer).
+
+usage: python tools/bench_stream.py [--model pwg] [--multiband] [--precision bf16] [--reps 200] [--repeats 3]
                                     [--out profiles/stream_infer.json]
 """
 import argparse
@@ -35,8 +41,8 @@ import torch  # noqa: E402
 from parallelwavegan_amd import ops  # noqa: E402
 from parallelwavegan_amd.graphs import GraphedInference  # noqa: E402
 from parallelwavegan_amd.layers import PQMF  # noqa: E402
-from parallelwavegan_amd.models import HiFiGANGenerator, MelGANGenerator  # noqa: E402
-from parallelwavegan_amd.utils import CausalStream  # noqa: E402
+from parallelwavegan_amd.models import HiFiGANGenerator, MelGANGenerator, ParallelWaveGANGenerator  # noqa: E402
+from parallelwavegan_amd.utils import CausalStream, PWGStream  # noqa: E402
 from parallelwavegan_amd.utils.streaming import receptive_field_frames  # noqa: E402
 from tests.golden import synth  # noqa: E402
 
@@ -78,6 +84,31 @@ def build_multiband(dev):
     return g.to(dev).eval()
 
 
+def build_pwg(dev):
+    """Causal Parallel WaveGAN at the PWG.v1 geometry on seeded weights, weight norm removed."""
+    g = ParallelWaveGANGenerator(use_causal_conv=True)
+    g.load_state_dict(synth.synth_state_dict(g.state_dict(), seed=14, g_scale=synth.PWG_G_SCALE))
+    g.remove_weight_norm()
+    return g.to(dev).eval()
+
+
+class _MelOnly(torch.nn.Module):
+    """The causal PWG generator as a map from mel frames alone (zero noise, the context window replicated on both sides
+    as ``inference`` does): what ``receptive_field_frames`` probes."""
+
+    def __init__(self, model):
+        super().__init__()
+        self.model = model
+        self.upsample_factor = model.upsample_factor
+
+    def forward(self, c):
+        from parallelwavegan_amd import functional as Fn
+
+        w = self.model.aux_context_window
+        z = torch.zeros(c.shape[0], 1, c.shape[-1] * self.upsample_factor, device=c.device)
+        return self.model(z, Fn.pad1d(c, w, w, "replicate"))
+
+
 def event_ms(fn, reps):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     torch.cuda.synchronize()
@@ -103,11 +134,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--model", choices=("default", "pwg"), default="default")
     ap.add_argument("--multiband", action="store_true")
     ap.add_argument("--precision", choices=("fp32", "bf16"), default="fp32")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    default_out = "stream_bf16_infer.json" if args.precision == "bf16" else (
+    if args.model == "pwg" and (args.multiband or args.precision != "fp32"):
+        ap.error("--model pwg is the fp32 full-band Parallel WaveGAN stream (no --multiband, no --precision bf16)")
+    default_out = "stream_pwg_infer.json" if args.model == "pwg" else "stream_bf16_infer.json" if args.precision == "bf16" else (
         "stream_mb_infer.json" if args.multiband else "stream_infer.json")
     args.out = args.out or os.path.join(ROOT, "profiles", default_out)
     dev = torch.device("cuda:0")
@@ -127,7 +161,9 @@ def main():
         print(json.dumps({"out": args.out, "points": [[p["model"], p["streams"], p["chunk_frames"], p["fp32_push_ms"],
                                                        p["bf16_push_ms"]] for p in rec["points"]]}))
         return
-    if args.multiband:
+    if args.model == "pwg":
+        measure_pwg(rec, "parallel_wavegan_v1_causal", build_pwg(dev), CHUNKS, gen, args, dev)
+    elif args.multiband:
         measure(rec, "multi_band_melgan_v2_causal", build_multiband(dev), MB_CHUNKS, gen, args, dev)
     else:
         for name, model, chunks in (("hifigan_v1_causal", build_model(dev), CHUNKS),
@@ -192,6 +228,58 @@ def measure(rec, name, model, chunks, gen, args, dev):
             print(json.dumps({k: p[k] for k in ("model", "streams", "chunk_frames", "stream_push_ms", "halo_forward_ms",
                                                 "spread_ms", "speedup_stream_over_halo", "launches_per_push_stream",
                                                 "launches_per_forward_halo")}), file=sys.stderr, flush=True)
+
+
+def measure_pwg(rec, name, model, chunks, gen, args, dev):
+    """``PWGStream.push`` against the whole-utterance causal forward over ``left + n`` frames, alternating."""
+    with torch.no_grad():
+        left, right = receptive_field_frames(_MelOnly(model), in_channels=80)
+    assert right == 0, "a causal generator has no look-ahead"
+    up, w = model.upsample_factor, model.aux_context_window
+    rec["models"][name] = {"workload": "seeded weights, weight norm removed", "halo_left_frames": left,
+                           "stream_state_bytes_per_stream": PWGStream(model, use_graph=False).state_bytes}
+    for b in STREAMS:
+        for n in chunks:
+            feats = torch.randn(b, n, 80, generator=gen).to(dev)
+            noise = torch.randn(b, n * up, generator=gen).to(dev)
+            ctx = torch.randn(b, 80, left + n + 2 * w, generator=gen).to(dev)
+            z_halo = torch.randn(b, 1, (left + n) * up, generator=gen).to(dev)
+            whole = lambda c: model(z_halo, c)  # noqa: E731
+            s = PWGStream(model, batch=b, use_graph=True)
+            halo = GraphedInference(whole)
+            for _ in range(6):  # start of stream, both graph directions, and the halo graph
+                s.push(feats, noise)
+                halo(ctx)
+            t_s, t_h = [], []
+            for _ in range(args.repeats):
+                t_s.append(event_ms(lambda: s.push(feats, noise), args.reps))
+                t_h.append(event_ms(lambda: halo(ctx), args.reps))
+            eager = PWGStream(model, batch=b, use_graph=False)
+            eager.push(feats, noise)
+            n_s, fam_s = launches(lambda: eager.push(feats, noise))
+            n_h, fam_h = launches(lambda: whole(ctx))
+            with ops.profile() as prof:  # the layer launches of a push, by the library's own event scope
+                for _ in range(10):
+                    eager.push(feats, noise)
+            r = prof.results["wavenet_stream_kernel"]
+            med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+            spread = max(max(t_s) - min(t_s), max(t_h) - min(t_h))
+            p = {"model": name, "streams": b, "chunk_frames": n, "samples_per_push": b * n * up,
+                 "stream_push_ms": round(med(t_s), 4), "stream_runs_ms": [round(t, 4) for t in t_s],
+                 "halo_forward_ms": round(med(t_h), 4), "halo_runs_ms": [round(t, 4) for t in t_h],
+                 "halo_frames_computed": left + n, "arithmetic_ratio_halo_over_stream": round((left + n) / n, 2),
+                 "spread_ms": round(spread, 4), "speedup_stream_over_halo": round(med(t_h) / med(t_s), 3),
+                 "stream_not_slower_beyond_spread": med(t_s) <= med(t_h) + spread,
+                 "stream_faster_beyond_spread": med(t_s) + spread < med(t_h),
+                 "real_time_factor_22050Hz": round(n * up / 22050.0 / (med(t_s) / 1e3), 1),
+                 "launches_per_push_stream": n_s, "launches_per_forward_halo": n_h,
+                 "layer_launch_ms": round(r["ms"] / r["launches"], 5),
+                 "stream_kernels": fam_s, "halo_kernels": fam_h}
+            rec["points"].append(p)
+            print(json.dumps({k: p[k] for k in ("model", "streams", "chunk_frames", "stream_push_ms", "halo_forward_ms",
+                                                "spread_ms", "speedup_stream_over_halo", "launches_per_push_stream",
+                                                "launches_per_forward_halo", "layer_launch_ms")}), file=sys.stderr,
+                  flush=True)
 
 
 def measure_precision(rec, name, model, chunks, gen, args, dev):
