@@ -32,45 +32,11 @@
 // give 32 workgroups for 512 rows; and inside a workgroup the four waves split the REDUCTION (each takes every fourth
 // 16-channel group) instead of the rows, with the next four taps' weights in flight while the current ones are contracted.
 // DESIGN.md s11.
-#include "common.h"
+#include "stream_common.h"
 
 namespace pwg {
-namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int SC = 64;           // input channels staged per LDS block (four 16-channel groups of the image)
-constexpr int kMaxXs = 256;      // LDS row stride limit: SC * kMaxXs * 4 B = 64 KiB
-constexpr int kMaxNt = 64;       // widest column tile
-constexpr int kFillWorkgroups = 256;  // one per CU
-
-// LDS row stride for a window of w columns: >= w and == 16 (mod 64), so that the four channel rows one MFMA step reads
-// (16 lanes each, consecutive columns) fall on four different groups of 16 banks
-static inline int xs_stride(int w) { return round_up(w > 16 ? w - 16 : 0, 64) + 16; }
-
-struct StreamGeom {
-  int taps, dil, hist;  // reduction taps, their spacing, history columns H
-  int m, m_pad, cin_pad;
-  int phases;           // transposed: stride (output column j * phases + phase), else 1
-};
-
-struct StreamArgs {
-  const float* x;
-  const float* hist_in;
-  float* hist_out;
-  const float* w;
-  const float* bias;
-  const float* add1;
-  const float* add2;
-  float* y;
-  int c_in, c_out, n, t_out, hist;
-  int taps, dil, cin_pad, m, m_pad, phases, xs;
-  int step_r, step_w;  // 256 / W and 256 % W for the staged window of W = tile columns + hist columns
-  int pad_mode, pre_act, post_act;
-  float pre_slope, post_slope, out_mul, out_div;
-};
-
-static int stream_geometry(const pwg_conv1d_desc* d, StreamGeom* g) {
+int stream_geometry(const pwg_conv1d_desc* d, StreamGeom* g) {
   PWG_REQUIRE(d != nullptr, PWG_ERR_NULL, "conv1d_stream: NULL descriptor");
   PWG_REQUIRE(d->batch > 0 && d->c_in > 0 && d->c_out > 0 && d->t_in > 0 && d->t_out > 0 && d->kernel > 0 &&
                   d->stride > 0 && d->dilation > 0 && d->groups > 0 && d->width > 0 && d->pad_left >= 0,
@@ -111,7 +77,7 @@ static int stream_geometry(const pwg_conv1d_desc* d, StreamGeom* g) {
     g->m = d->c_out;
     g->phases = 1;
   }
-  PWG_REQUIRE(kMaxNt + g->hist <= kMaxXs - 48, PWG_ERR_UNSUPPORTED,
+  PWG_REQUIRE(g->hist <= kStreamMaxHist, PWG_ERR_UNSUPPORTED,
               "conv1d_stream: history of %d columns (%d taps, dilation %d) does not fit the LDS window", g->hist, g->taps,
               g->dil);
   PWG_REQUIRE(ceil_div(g->m, 16) <= 65535, PWG_ERR_UNSUPPORTED, "conv1d_stream: too many row blocks");
@@ -119,6 +85,21 @@ static int stream_geometry(const pwg_conv1d_desc* d, StreamGeom* g) {
   g->cin_pad = round_up(d->c_in, 16);
   return PWG_OK;
 }
+
+namespace {
+
+constexpr int SC = 64;  // input channels staged per LDS block (four 16-channel groups of the image)
+
+// LDS row stride for a window of w columns: >= w and == 16 (mod 64), so that the four channel rows one MFMA step reads
+// (16 lanes each, consecutive columns) fall on four different groups of 16 banks
+constexpr int xs_stride(int w) { return (((w > 16 ? w - 16 : 0) + 63) / 64) * 64 + 16; }
+static_assert(SC * xs_stride(kStreamMaxNt + kStreamMaxHist) * sizeof(float) <= kStreamLdsBytes,
+              "the widest fp32 window does not fit LDS");
+
+struct StreamArgs : StreamCommonArgs {
+  const float* w;
+  int cin_pad, m_pad, xs;
+};
 
 // One workgroup (4 waves) owns MT = 16 * TM rows x NT = 16 * TN columns.  The reduction is dealt over the four waves:
 // wave w takes the w-th 16-channel group of every staged block of 64 channels, and the four partial tiles are summed
@@ -132,29 +113,13 @@ __global__ __launch_bounds__(256) void conv1d_stream_kernel(StreamArgs a) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l15 = lane & 15, lq = lane >> 4;
   const int q0 = blockIdx.x * NT, m0 = blockIdx.y * MT, b = blockIdx.z;
-  const int H = a.hist, n = a.n, XS = a.xs;
+  const int H = a.hist, n = a.ep.n, XS = a.xs;
   const int W = NT + H;  // window column w holds stream column q0 - H + w (chunk-relative; < 0: history)
   const float* __restrict__ xb = a.x + (size_t)b * a.c_in * n;
   const float* __restrict__ hb = a.hist_in ? a.hist_in + (size_t)b * a.c_in * H : nullptr;
 
-  // ---- hist_out = last H columns of concat(hist_in, x), raw; the elements are dealt over the workgroups of the item
-  {
-    const int total = a.c_in * H;
-    const int wg = blockIdx.y * gridDim.x + blockIdx.x, nwg = gridDim.x * gridDim.y;
-    float* __restrict__ ho = a.hist_out + (size_t)b * a.c_in * H;
-    for (int i = wg * 256 + tid; i < total; i += nwg * 256) {
-      const int ci = i / H, h = i - ci * H;
-      const int t = n - H + h;
-      float v = 0.f;
-      if (t >= 0)
-        v = xb[(size_t)ci * n + t];
-      else if (hb)
-        v = hb[(size_t)ci * H + n + h];
-      else if (a.pad_mode == PWG_PAD_REPLICATE)
-        v = xb[(size_t)ci * n];
-      ho[i] = v;
-    }
-  }
+  stream_write_history<1>(xb, hb, a.hist_out + (size_t)b * a.c_in * H, a.c_in, n, H, a.pad_mode == PWG_PAD_REPLICATE,
+                       blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
 
   f32x4 acc[TM][TN];
 #pragma unroll
@@ -208,15 +173,13 @@ __global__ __launch_bounds__(256) void conv1d_stream_kernel(StreamArgs a) {
   // window elements come from the history, the chunk or the start-of-stream padding; the pre-activation is applied on
   // the way into LDS.  The load phase is branch-free: the source address is selected (a safe one where the element is
   // zero padding or past the chunk) and always loaded, so that the loads of a staging batch are issued back to back
-  const bool replicate = a.pad_mode == PWG_PAD_REPLICATE, reflect = a.pad_mode == PWG_PAD_REFLECT;
-  const bool has_hist = hb != nullptr;
-  const float* hsafe = has_hist ? hb : xb;
+  const StreamWindow win = {xb, hb, n, H, a.pad_mode};
   const int r_first = tid / W, w_first = tid - r_first * W;
 
   for (int c0 = 0; c0 < a.cin_pad; c0 += SC) {
     if (c0) __syncthreads();
     // ---- stage the block's channels (up to SC; none past the image) x W columns, 8 loads in flight per thread.
-    // Element tid + 256 * i is (row, column) = (r, w); stepping by 256 adds (a.step_r, a.step_w) with one carry, so
+    // Element tid + 256 * i is (row, column) = (r, w); stepping by 256 adds (a.step_q, a.step_w) with one carry, so
     // the only division is the one per thread in front of the block loop
     const int rows = a.cin_pad - c0 < SC ? a.cin_pad - c0 : SC;
     for (int r = r_first, w = w_first; r < rows;) {
@@ -227,13 +190,12 @@ __global__ __launch_bounds__(256) void conv1d_stream_kernel(StreamArgs a) {
       for (int u = 0; u < 8; ++u) {
         const bool live = r < rows;
         off[u] = live ? r * XS + w : -1;
-        const int ci = c0 + r, t = q0 - H + w;
-        const bool in_chunk = t >= 0;
-        const int tt = in_chunk ? t : (reflect ? -t : 0);  // column of x: the chunk's own, the mirrored one, or the first
-        ok[u] = live && ci < a.c_in && (in_chunk ? t < n : (has_hist || replicate || (reflect && tt < n)));
-        const float* src = (!in_chunk && has_hist) ? hsafe + ((size_t)ci * H + H + t) : xb + ((size_t)ci * n + tt);
+        const int ci = c0 + r;
+        const StreamWindow::Column col = win.at(q0 - H + w);
+        ok[u] = live && ci < a.c_in && col.live;
+        const float* src = col.hist ? hb + ((size_t)ci * H + col.col) : xb + ((size_t)ci * n + col.col);
         v[u] = *(ok[u] ? src : xb);
-        r += a.step_r;
+        r += a.step_q;
         w += a.step_w;
         if (w >= W) {
           w -= W;
@@ -267,51 +229,13 @@ __global__ __launch_bounds__(256) void conv1d_stream_kernel(StreamArgs a) {
     }
   }
 
-  // ---- the four waves' partial tiles through LDS (D layout of the 16 x 16 x 4 form: column = lane % 16,
-  // row = 4 * (lane / 16) + register); every wave writes its tile, zeros where it had no channel group
-  __syncthreads();
-  float* red = xs;  // [4][MT][NT + 1]
-  constexpr int RS = NT + 1;
-#pragma unroll
-  for (int mi = 0; mi < TM; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < TN; ++ni)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) red[(wave * MT + mi * 16 + 4 * lq + i) * RS + ni * 16 + l15] = acc[mi][ni][i];
-  __syncthreads();
-
-  // ---- epilogue: one thread per output element, partial sums added in wave order
-  for (int e = tid; e < MT * NT; e += 256) {
-    const int row = e / NT, col = e - row * NT;
-    const int m = m0 + row, j = q0 + col;
-    if (m >= a.m || j >= n) continue;
-    float v = red[row * RS + col];
-    v += red[(MT + row) * RS + col];
-    v += red[(2 * MT + row) * RS + col];
-    v += red[(3 * MT + row) * RS + col];
-    int co = m, ph = 0;
-    if (TRANSPOSED) {
-      ph = m / a.c_out;
-      co = m - ph * a.c_out;
-    }
-    const size_t o = ((size_t)b * a.c_out + co) * a.t_out + (TRANSPOSED ? j * a.phases + ph : j);
-    if (a.bias) v += a.bias[co];
-    if (a.add1) v += a.add1[o];
-    if (a.add2) v += a.add2[o];
-    if (a.out_mul != 1.0f) v *= a.out_mul;
-    if (a.out_div != 1.0f) v = v / a.out_div;
-    v = apply_act(v, a.post_act, a.post_slope);
-    a.y[o] = v;
-  }
+  stream_reduce_epilogue<MT, NT, TRANSPOSED, StreamRows::PhaseMajor>(xs, acc, a.ep, m0, q0, b);
 }
 
-template <int TM, int TN>
-static void launch_tile(const StreamArgs& a, bool transposed, dim3 grid, size_t lds, hipStream_t stream) {
-  if (transposed)
-    hipLaunchKernelGGL((conv1d_stream_kernel<TM, TN, true>), grid, dim3(256), lds, stream, a);
-  else
-    hipLaunchKernelGGL((conv1d_stream_kernel<TM, TN, false>), grid, dim3(256), lds, stream, a);
-}
+template <int TM, int TN, bool TRANSPOSED>
+struct Kernel {
+  static constexpr auto fn = conv1d_stream_kernel<TM, TN, TRANSPOSED>;
+};
 
 }  // namespace
 }  // namespace pwg
@@ -336,69 +260,27 @@ extern "C" int pwg_conv1d_stream_forward(const pwg_conv1d_desc* d, const float* 
   int rc = stream_geometry(d, &g);
   if (rc != PWG_OK) return rc;
   hipStream_t stream = (hipStream_t)stream_;
-  PWG_REQUIRE(x && w_packed && y, PWG_ERR_NULL, "conv1d_stream: NULL pointer");
-  PWG_REQUIRE(hist_out || g.hist == 0, PWG_ERR_NULL, "conv1d_stream: hist_out is NULL (the layer keeps %d columns)", g.hist);
-  PWG_REQUIRE(g.hist == 0 || hist_in != hist_out, PWG_ERR_BAD_SHAPE,
-              "conv1d_stream: hist_in and hist_out must be distinct buffers (other workgroups read the history)");
-  PWG_REQUIRE(hist_in || d->pad_mode != PWG_PAD_REFLECT || d->t_in > g.hist, PWG_ERR_BAD_SHAPE,
-              "conv1d_stream: a reflect-padded stream starts with at least %d columns (got %d)", g.hist + 1, d->t_in);
+  rc = stream_check_pointers("conv1d_stream", d, g, x, w_packed, y, hist_in, hist_out);
+  if (rc != PWG_OK) return rc;
   PWG_REQUIRE((reinterpret_cast<uintptr_t>(w_packed) & 3u) == 0, PWG_ERR_BAD_SHAPE, "conv1d_stream: unaligned weight image");
   const int n = d->t_in;
-  const int tn = n <= 16 ? 1 : (n <= 32 ? 2 : 4);
-  const int nt = 16 * tn;
-  const int col_tiles = ceil_div(n, nt);
-  // 32-row blocks only when they still give every CU two workgroups (the order of an element's sum is the same)
-  const int tm = (tn == 4 && (long)ceil_div(g.m, 32) * col_tiles * d->batch >= 2 * kFillWorkgroups) ? 2 : 1;
-  const int xs = xs_stride(nt + g.hist);
-  const size_t red = (size_t)4 * (16 * tm) * (nt + 1) * sizeof(float);  // the partial tiles reuse the window's LDS
-  const size_t lds = (size_t)SC * xs * sizeof(float) > red ? (size_t)SC * xs * sizeof(float) : red;
+  const StreamTile tile = stream_tile(n, g.m, d->batch);
 
   StreamArgs a;
-  a.x = x;
-  a.hist_in = g.hist ? hist_in : nullptr;
-  a.hist_out = hist_out;
+  stream_fill_args(&a, d, g, tile, x, hist_in, hist_out, bias, add1, add2, y);
   a.w = w_packed;
-  a.bias = bias;
-  a.add1 = add1;
-  a.add2 = add2;
-  a.y = y;
-  a.c_in = d->c_in;
-  a.c_out = d->c_out;
-  a.n = n;
-  a.t_out = d->t_out;
-  a.hist = g.hist;
-  a.taps = g.taps;
-  a.dil = g.dil;
   a.cin_pad = g.cin_pad;
-  a.m = g.m;
   a.m_pad = g.m_pad;
-  a.phases = g.phases;
-  a.xs = xs;
-  a.step_r = 256 / (nt + g.hist);
-  a.step_w = 256 % (nt + g.hist);
-  a.pad_mode = d->pad_mode;
-  a.pre_act = d->pre_act;
-  a.post_act = d->post_act;
-  a.pre_slope = d->pre_slope;
-  a.post_slope = d->post_slope;
-  a.out_mul = d->out_mul;
-  a.out_div = d->out_div;
+  a.xs = xs_stride(16 * tile.tn + g.hist);
 
-  const dim3 grid(col_tiles, ceil_div(g.m, 16 * tm), d->batch);
   const double out_elems = (double)d->batch * d->c_out * d->t_out;
   const double flops = 2.0 * (double)d->batch * g.m * n * g.taps * d->c_in;
   const double bytes = 4.0 * ((double)d->batch * d->c_in * (n + 2.0 * g.hist) +
                               out_elems * (1 + (add1 ? 1 : 0) + (add2 ? 1 : 0)) + (double)g.taps * g.cin_pad * g.m_pad);
   maybe_poison_lds(stream);
   ProfScope prof(stream, "conv1d_stream_kernel", flops, bytes);
-  if (tn == 1)
-    launch_tile<1, 1>(a, d->transposed != 0, grid, lds, stream);
-  else if (tn == 2)
-    launch_tile<1, 2>(a, d->transposed != 0, grid, lds, stream);
-  else if (tm == 1)
-    launch_tile<1, 4>(a, d->transposed != 0, grid, lds, stream);
-  else
-    launch_tile<2, 4>(a, d->transposed != 0, grid, lds, stream);
+  stream_launch<Kernel>(tile, d->transposed != 0, a, g.m, d->batch,
+                        stream_lds_bytes((size_t)SC * a.xs * sizeof(float), tile), stream);
   PWG_CHECK_LAUNCH("conv1d_stream");
   return PWG_OK;
 }

@@ -33,8 +33,7 @@
 // Tiles: as the fp32 stream kernel -- 16 rows x 16 / 32 / 64 columns for chunks of up to 16 / 32 / more columns, 32 x 64
 // when that still gives every CU two workgroups; the four waves deal the REDUCTION, and the A fragments of the next four
 // items (one 16-B load per lane and item) are in flight while the current four are contracted.  DESIGN.md s11.2.
-#include "common.h"
-#include "bf16_mfma.h"
+#include "stream_common.h"
 
 namespace pwg {
 namespace {
@@ -42,25 +41,13 @@ namespace {
 constexpr int KC = 32;            // input channels per chunk of the image = one MFMA reduction step
 constexpr int SC = 4 * KC;        // input channels staged per LDS block
 constexpr int ROW = SC + 8;       // bf16 elements per LDS row: 17 slots of 16 B
-constexpr int kMaxNt = 64;        // widest column tile
-constexpr int kMaxHist = 144;     // what pwg_conv1d_stream_supported admits: (64 + 144) * 272 B = 56.6 KB of LDS
-constexpr int kFillWorkgroups = 256;  // one per CU
+static_assert((kStreamMaxNt + kStreamMaxHist) * ROW * sizeof(__bf16) <= kStreamLdsBytes,
+              "the widest bf16 window does not fit LDS");
 
-struct StreamBf16Args {
-  const float* x;
-  const float* hist_in;
-  float* hist_out;
+struct StreamBf16Args : StreamCommonArgs {
   const bf16x8* w;
-  const float* bias;
-  const float* add1;
-  const float* add2;
-  float* y;
-  int c_in, c_out, n, t_out, hist;
-  int taps, dil, cin_chunks, m, m_pad, phases;
-  int q4, r4;          // 4 / taps and 4 % taps: a wave's next item is 4 items on
-  int step_o, step_w;  // 256 / W and 256 % W for the staged window of W = tile columns + hist columns
-  int pad_mode, pre_act, post_act;
-  float pre_slope, post_slope, out_mul, out_div;
+  int cin_chunks, m_pad;
+  int q4, r4;  // 4 / taps and 4 % taps: a wave's next item is 4 items on
 };
 
 // (chunk of the staged block, tap) of an item; wave-uniform
@@ -80,29 +67,13 @@ __global__ __launch_bounds__(256) void conv1d_stream_bf16_kernel(StreamBf16Args 
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l15 = lane & 15, lq = lane >> 4;
   const int q0 = blockIdx.x * NT, m0 = blockIdx.y * MT, b = blockIdx.z;
-  const int H = a.hist, n = a.n;
+  const int H = a.hist, n = a.ep.n;
   const int W = NT + H;  // window column w holds stream column q0 - H + w (chunk-relative; < 0: history)
   const float* __restrict__ xb = a.x + (size_t)b * a.c_in * n;
   const float* __restrict__ hb = a.hist_in ? a.hist_in + (size_t)b * a.c_in * H : nullptr;
 
-  // ---- hist_out = last H columns of concat(hist_in, x), raw fp32; the elements are dealt over the workgroups of the item
-  {
-    const int total = a.c_in * H;
-    const int wg = blockIdx.y * gridDim.x + blockIdx.x, nwg = gridDim.x * gridDim.y;
-    float* __restrict__ ho = a.hist_out + (size_t)b * a.c_in * H;
-    for (int i = wg * 256 + tid; i < total; i += nwg * 256) {
-      const int ci = i / H, h = i - ci * H;
-      const int t = n - H + h;
-      float v = 0.f;
-      if (t >= 0)
-        v = xb[(size_t)ci * n + t];
-      else if (hb)
-        v = hb[(size_t)ci * H + n + h];
-      else if (a.pad_mode == PWG_PAD_REPLICATE)
-        v = xb[(size_t)ci * n];
-      ho[i] = v;
-    }
-  }
+  stream_write_history<1>(xb, hb, a.hist_out + (size_t)b * a.c_in * H, a.c_in, n, H, a.pad_mode == PWG_PAD_REPLICATE,
+                       blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
 
   f32x4 acc[TM][TN];
 #pragma unroll
@@ -172,8 +143,7 @@ __global__ __launch_bounds__(256) void conv1d_stream_bf16_kernel(StreamBf16Args 
   // window elements come from the history, the chunk or the start-of-stream padding; the pre-activation and the
   // rounding are applied on the way into LDS.  The load phase is branch-free: the source address is selected (a safe
   // one where the element is zero padding, past the chunk or past c_in) and always loaded
-  const bool replicate = a.pad_mode == PWG_PAD_REPLICATE, reflect = a.pad_mode == PWG_PAD_REFLECT;
-  const bool has_hist = hb != nullptr;
+  const StreamWindow win = {xb, hb, n, H, a.pad_mode};
   const int o_first = tid / W, w_first = tid - o_first * W;
   const int nblocks = (a.cin_chunks + 3) >> 2;
 
@@ -181,7 +151,7 @@ __global__ __launch_bounds__(256) void conv1d_stream_bf16_kernel(StreamBf16Args 
     if (blk) __syncthreads();
     // ---- stage the block's chunks (all 32 channels of each: zeros past c_in) x W columns.  Item tid + 256 * i is
     // (channel octet, column) = (o, w): lanes walk the columns (coalesced fp32 rows), 8 channels are activated, rounded
-    // and written as one 16-B LDS store; 16 loads in flight per thread.  Stepping by 256 adds (a.step_o, a.step_w)
+    // and written as one 16-B LDS store; 16 loads in flight per thread.  Stepping by 256 adds (a.step_q, a.step_w)
     // with one carry, so the only division is the one per thread in front of the block loop
     const int c0 = blk * SC, nch = chunks_of(blk), octs = nch * 4;
     for (int o = o_first, w = w_first; o < octs;) {
@@ -193,20 +163,17 @@ __global__ __launch_bounds__(256) void conv1d_stream_bf16_kernel(StreamBf16Args 
       for (int u = 0; u < U; ++u) {
         const bool live = o < octs;
         off[u] = live ? w * ROW + o * 8 : -1;
-        const int t = q0 - H + w;
-        const bool in_chunk = t >= 0;
-        const int tt = in_chunk ? t : (reflect ? -t : 0);  // column of x: the chunk's own, the mirrored one, or the first
-        const bool okc = live && (in_chunk ? t < n : (has_hist || replicate || (reflect && tt < n)));
-        const bool from_hist = !in_chunk && has_hist;
-        const float* src = from_hist ? hb + (H + t) : xb + tt;
-        const size_t rs = from_hist ? H : n;
+        const StreamWindow::Column col = win.at(q0 - H + w);
+        const bool okc = live && col.live;
+        const float* src = (col.hist ? hb : xb) + col.col;
+        const size_t rs = col.hist ? H : n;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const int ci = c0 + o * 8 + j;
           ok[u][j] = okc && ci < a.c_in;
           v[u][j] = *(ok[u][j] ? src + (size_t)ci * rs : xb);
         }
-        o += a.step_o;
+        o += a.step_q;
         w += a.step_w;
         if (w >= W) {
           w -= W;
@@ -240,51 +207,13 @@ __global__ __launch_bounds__(256) void conv1d_stream_bf16_kernel(StreamBf16Args 
     }
   }
 
-  // ---- the four waves' partial tiles through LDS (D layout of the 16 x 16 forms: column = lane % 16,
-  // row = 4 * (lane / 16) + register); every wave writes its tile, zeros where it had no item
-  __syncthreads();
-  float* red = reinterpret_cast<float*>(smem);  // [4][MT][NT + 1]
-  constexpr int RS = NT + 1;
-#pragma unroll
-  for (int mi = 0; mi < TM; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < TN; ++ni)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) red[(wave * MT + mi * 16 + 4 * lq + i) * RS + ni * 16 + l15] = acc[mi][ni][i];
-  __syncthreads();
-
-  // ---- epilogue (fp32): one thread per output element, partial sums added in wave order
-  for (int e = tid; e < MT * NT; e += 256) {
-    const int row = e / NT, col = e - row * NT;
-    const int m = m0 + row, j = q0 + col;
-    if (m >= a.m || j >= n) continue;
-    float v = red[row * RS + col];
-    v += red[(MT + row) * RS + col];
-    v += red[(2 * MT + row) * RS + col];
-    v += red[(3 * MT + row) * RS + col];
-    int co = m, ph = 0;
-    if (TRANSPOSED) {
-      co = m / a.phases;
-      ph = m - co * a.phases;
-    }
-    const size_t o = ((size_t)b * a.c_out + co) * a.t_out + (TRANSPOSED ? j * a.phases + ph : j);
-    if (a.bias) v += a.bias[co];
-    if (a.add1) v += a.add1[o];
-    if (a.add2) v += a.add2[o];
-    if (a.out_mul != 1.0f) v *= a.out_mul;
-    if (a.out_div != 1.0f) v = v / a.out_div;
-    v = apply_act(v, a.post_act, a.post_slope);
-    a.y[o] = v;
-  }
+  stream_reduce_epilogue<MT, NT, TRANSPOSED, StreamRows::ChannelMajor>(reinterpret_cast<float*>(smem), acc, a.ep, m0, q0, b);
 }
 
-template <int TM, int TN>
-static void launch_tile(const StreamBf16Args& a, bool transposed, dim3 grid, size_t lds, hipStream_t stream) {
-  if (transposed)
-    hipLaunchKernelGGL((conv1d_stream_bf16_kernel<TM, TN, true>), grid, dim3(256), lds, stream, a);
-  else
-    hipLaunchKernelGGL((conv1d_stream_bf16_kernel<TM, TN, false>), grid, dim3(256), lds, stream, a);
-}
+template <int TM, int TN, bool TRANSPOSED>
+struct Kernel {
+  static constexpr auto fn = conv1d_stream_bf16_kernel<TM, TN, TRANSPOSED>;
+};
 
 }  // namespace
 }  // namespace pwg
@@ -297,12 +226,9 @@ extern "C" int pwg_conv1d_stream_bf16_supported(const pwg_conv1d_desc* d) { retu
 extern "C" int pwg_conv1d_stream_bf16_forward(const pwg_conv1d_desc* d, const float* x, const float* hist_in,
                                               float* hist_out, const void* w_packed_bf16, const float* bias,
                                               const float* add1, const float* add2, float* y, void* stream_) {
-  if (!pwg_conv1d_stream_supported(d)) return PWG_ERR_UNSUPPORTED;  // (pwg_last_error holds the reason)
+  StreamGeom g;
+  if (stream_geometry(d, &g) != PWG_OK) return PWG_ERR_UNSUPPORTED;  // (pwg_last_error holds the reason)
   hipStream_t stream = (hipStream_t)stream_;
-  const bool transposed = d->transposed != 0;
-  const int taps = transposed ? 2 : d->kernel, dil = transposed ? 1 : d->dilation;
-  const int hist = transposed ? 1 : d->pad_left;
-  const int m = transposed ? d->c_out * d->stride : d->c_out, phases = transposed ? d->stride : 1;
   const int cin_chunks = ceil_div(d->c_in, KC);
   // the row extent of the image comes from its owner (csrc/conv1d_bf16.hip); the image does not depend on padding,
   // which the packer's geometry check admits only as zero
@@ -310,77 +236,33 @@ extern "C" int pwg_conv1d_stream_bf16_forward(const pwg_conv1d_desc* d, const fl
   dz.pad_mode = PWG_PAD_ZERO;
   const size_t image_bytes = pwg_conv1d_bf16_packed_weight_bytes(&dz);
   PWG_REQUIRE(image_bytes != 0, PWG_ERR_UNSUPPORTED, "conv1d_stream_bf16: the layer has no bf16 weight image");
-  const size_t row_bytes = (size_t)taps * cin_chunks * KC * sizeof(__bf16);
+  const size_t row_bytes = (size_t)g.taps * cin_chunks * KC * sizeof(__bf16);
   const int m_pad = (int)(image_bytes / row_bytes);
-  PWG_REQUIRE((size_t)m_pad * row_bytes == image_bytes && m_pad % 32 == 0 && m_pad >= m, PWG_ERR_UNSUPPORTED,
-              "conv1d_stream_bf16: unexpected bf16 weight image of %zu B for %d rows", image_bytes, m);
-  PWG_REQUIRE(hist <= kMaxHist, PWG_ERR_UNSUPPORTED, "conv1d_stream_bf16: history of %d columns does not fit the LDS window",
-              hist);
-  PWG_REQUIRE(x && w_packed_bf16 && y, PWG_ERR_NULL, "conv1d_stream_bf16: NULL pointer");
-  PWG_REQUIRE(hist_out || hist == 0, PWG_ERR_NULL, "conv1d_stream_bf16: hist_out is NULL (the layer keeps %d columns)", hist);
-  PWG_REQUIRE(hist == 0 || hist_in != hist_out, PWG_ERR_BAD_SHAPE,
-              "conv1d_stream_bf16: hist_in and hist_out must be distinct buffers (other workgroups read the history)");
-  PWG_REQUIRE(hist_in || d->pad_mode != PWG_PAD_REFLECT || d->t_in > hist, PWG_ERR_BAD_SHAPE,
-              "conv1d_stream_bf16: a reflect-padded stream starts with at least %d columns (got %d)", hist + 1, d->t_in);
+  PWG_REQUIRE((size_t)m_pad * row_bytes == image_bytes && m_pad % 32 == 0 && m_pad >= g.m, PWG_ERR_UNSUPPORTED,
+              "conv1d_stream_bf16: unexpected bf16 weight image of %zu B for %d rows", image_bytes, g.m);
+  const int rc = stream_check_pointers("conv1d_stream_bf16", d, g, x, w_packed_bf16, y, hist_in, hist_out);
+  if (rc != PWG_OK) return rc;
   PWG_REQUIRE((reinterpret_cast<uintptr_t>(w_packed_bf16) & 15u) == 0, PWG_ERR_BAD_SHAPE,
               "conv1d_stream_bf16: the weight image must be 16-B aligned");
   const int n = d->t_in;
-  const int tn = n <= 16 ? 1 : (n <= 32 ? 2 : 4);
-  const int nt = 16 * tn;
-  const int col_tiles = ceil_div(n, nt);
-  // 32-row blocks only when they still give every CU two workgroups (the order of an element's sum is the same)
-  const int tm = (tn == 4 && (long)ceil_div(m, 32) * col_tiles * d->batch >= 2 * kFillWorkgroups) ? 2 : 1;
-  const size_t win = (size_t)(nt + hist) * ROW * sizeof(__bf16);
-  const size_t red = (size_t)4 * (16 * tm) * (nt + 1) * sizeof(float);  // the partial tiles reuse the window's LDS
-  const size_t lds = win > red ? win : red;
+  const StreamTile tile = stream_tile(n, g.m, d->batch);
 
   StreamBf16Args a;
-  a.x = x;
-  a.hist_in = hist ? hist_in : nullptr;
-  a.hist_out = hist_out;
+  stream_fill_args(&a, d, g, tile, x, hist_in, hist_out, bias, add1, add2, y);
   a.w = static_cast<const bf16x8*>(w_packed_bf16);
-  a.bias = bias;
-  a.add1 = add1;
-  a.add2 = add2;
-  a.y = y;
-  a.c_in = d->c_in;
-  a.c_out = d->c_out;
-  a.n = n;
-  a.t_out = d->t_out;
-  a.hist = hist;
-  a.taps = taps;
-  a.dil = dil;
   a.cin_chunks = cin_chunks;
-  a.m = m;
-  a.m_pad = m_pad;
-  a.phases = phases;
-  a.q4 = 4 / taps;
-  a.r4 = 4 % taps;
-  a.step_o = 256 / (nt + hist);
-  a.step_w = 256 % (nt + hist);
-  a.pad_mode = d->pad_mode;
-  a.pre_act = d->pre_act;
-  a.post_act = d->post_act;
-  a.pre_slope = d->pre_slope;
-  a.post_slope = d->post_slope;
-  a.out_mul = d->out_mul;
-  a.out_div = d->out_div;
+  a.m_pad = m_pad;  // of the bf16 image, not g.m_pad
+  a.q4 = 4 / g.taps;
+  a.r4 = 4 % g.taps;
 
-  const dim3 grid(col_tiles, ceil_div(m, 16 * tm), d->batch);
   const double out_elems = (double)d->batch * d->c_out * d->t_out;
-  const double flops = 2.0 * (double)d->batch * m * n * taps * d->c_in;
-  const double bytes = 4.0 * ((double)d->batch * d->c_in * (n + 2.0 * hist) +
+  const double flops = 2.0 * (double)d->batch * g.m * n * g.taps * d->c_in;
+  const double bytes = 4.0 * ((double)d->batch * d->c_in * (n + 2.0 * g.hist) +
                               out_elems * (1 + (add1 ? 1 : 0) + (add2 ? 1 : 0))) + (double)image_bytes;
   maybe_poison_lds(stream);
   ProfScope prof(stream, "conv1d_stream_bf16_kernel", flops, bytes);
-  if (tn == 1)
-    launch_tile<1, 1>(a, transposed, grid, lds, stream);
-  else if (tn == 2)
-    launch_tile<1, 2>(a, transposed, grid, lds, stream);
-  else if (tm == 1)
-    launch_tile<1, 4>(a, transposed, grid, lds, stream);
-  else
-    launch_tile<2, 4>(a, transposed, grid, lds, stream);
+  stream_launch<Kernel>(tile, d->transposed != 0, a, g.m, d->batch,
+                        stream_lds_bytes((size_t)(16 * tile.tn + g.hist) * ROW * sizeof(__bf16), tile), stream);
   PWG_CHECK_LAUNCH("conv1d_stream_bf16");
   return PWG_OK;
 }

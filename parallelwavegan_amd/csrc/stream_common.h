@@ -1,0 +1,228 @@
+// What the stream kernels share (conv1d_stream.hip, conv1d_stream_bf16.hip and, for the history writer,
+// wavenet_stream.hip): every rule of a stream that has to agree bit for bit between the kernels is stated here, once.
+//   history rule          stream_write_history   hist_out = the last H RAW columns of concat(hist_in, x)
+//   start-of-stream rule  StreamWindow::at       which source window column t comes from (history, chunk, padding)
+//   sum order, epilogue   stream_reduce_epilogue ((p0 + p1) + p2) + p3, then the fp32 epilogue
+//   tile rule             stream_tile            column tile from n; 32-row blocks only at 2 x 256 or more workgroups
+//   coverage              stream_geometry        defined in conv1d_stream.hip; both precisions admit the same layers
+// Internal to csrc/; the staging loops and contractions of the kernels differ on purpose and stay with them.
+#pragma once
+#include "common.h"
+
+#include "bf16_mfma.h"  // f32x4 (after common.h: it needs the HIP runtime header)
+
+#include <stdint.h>
+
+namespace pwg {
+
+constexpr int kStreamMaxNt = 64;            // widest column tile
+constexpr int kStreamMaxHist = 144;         // history columns stream_geometry() admits; each kernel asserts its window fits LDS
+constexpr int kStreamLdsBytes = 64 * 1024;  // what a workgroup gets without raising the kernel's limit
+constexpr int kStreamFillWorkgroups = 256;  // one per CU
+
+// ---- history rule.  hist_out = last H columns of concat(hist_in, x), raw, also when n < H (part of hist_in carries
+// over); hb == NULL is the start of a stream: the replicated first column, or zeros.  xb / hb / ho are one item's
+// (c, n) / (c, H) / (c, H); its c * H elements are dealt over the item's nwg workgroups, this one being number wg.
+// UNROLL: the wavenet kernel's long copy (64 * 2d elements) is unrolled by 4; the conv kernels pass 1, which compiles
+// to the instruction stream of the loop without a pragma.
+template <int UNROLL>
+__device__ __forceinline__ void stream_write_history(const float* __restrict__ xb, const float* __restrict__ hb,
+                                                     float* __restrict__ ho, int c, int n, int H, bool replicate, int wg,
+                                                     int nwg) {
+  const int total = c * H;
+#pragma unroll UNROLL
+  for (int i = wg * 256 + (int)threadIdx.x; i < total; i += nwg * 256) {
+    const int ci = i / H, h = i - ci * H;
+    const int t = n - H + h;
+    float v = 0.f;
+    if (t >= 0)
+      v = xb[(size_t)ci * n + t];
+    else if (hb)
+      v = hb[(size_t)ci * H + n + h];
+    else if (replicate)
+      v = xb[(size_t)ci * n];
+    ho[i] = v;
+  }
+}
+
+// ---- start-of-stream rule.  The window of one item: chunk-relative column t >= 0 is x[t]; t < 0 is hist_in[H + t],
+// or at the start of a stream (hb == NULL) what pad_mode synthesises: reflect x[-t], replicate x[0], zero nothing.
+struct StreamWindow {
+  const float* xb;  // (c_in, n)
+  const float* hb;  // (c_in, H) or NULL
+  int n, H, pad_mode;
+
+  // Column t: `live` if it holds data (else zero: zero padding, a mirror image past the chunk, or past the chunk's
+  // end); it is column `col` of the history if `hist`, else of the chunk.  A staging loop forms the address from the
+  // buffer that `hist` names (never from a NULL history), selects a safe one where the column is not live, and always
+  // loads.
+  struct Column {
+    bool live, hist;
+    int col;
+  };
+  __device__ __forceinline__ Column at(int t) const {
+    const bool replicate = pad_mode == PWG_PAD_REPLICATE, reflect = pad_mode == PWG_PAD_REFLECT;
+    const bool has_hist = hb != nullptr;
+    const bool in_chunk = t >= 0;
+    const int tt = in_chunk ? t : (reflect ? -t : 0);  // column of x: the chunk's own, the mirrored one, or the first
+    Column c;
+    c.live = in_chunk ? t < n : (has_hist || replicate || (reflect && tt < n));
+    c.hist = !in_chunk && has_hist;
+    c.col = c.hist ? H + t : tt;
+    return c;
+  }
+};
+
+// ---- the fp32 epilogue of an output tile; both argument structs embed it
+struct StreamEpilogue {
+  const float* bias;
+  const float* add1;
+  const float* add2;
+  float* y;
+  int c_out, n, t_out, m, phases;
+  int post_act;
+  float post_slope, out_mul, out_div;
+};
+
+// Row order of a transposed layer's image: row m = phase * C_out + co (fp32 image) or co * s + phase (bf16 image)
+enum class StreamRows { PhaseMajor, ChannelMajor };
+
+// Sum order and epilogue.  The four waves' partial tiles (D layout of the 16 x 16 MFMA forms: column = lane % 16,
+// row = 4 * (lane / 16) + register) go through LDS -- every wave writes its tile, zeros where it contracted nothing --
+// and one thread per output element adds them in wave order, ((p0 + p1) + p2) + p3, then bias, add1, add2, out_mul,
+// out_div and the post-activation.  `red` is the workgroup's LDS ([4][MT][NT + 1] floats, reusing the window's).
+template <int MT, int NT, bool TRANSPOSED, StreamRows ROWS>
+__device__ __forceinline__ void stream_reduce_epilogue(float* red, const f32x4 (&acc)[MT / 16][NT / 16],
+                                                       const StreamEpilogue& a, int m0, int q0, int b) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l15 = lane & 15, lq = lane >> 4;
+  constexpr int RS = NT + 1;
+  __syncthreads();
+#pragma unroll
+  for (int mi = 0; mi < MT / 16; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < NT / 16; ++ni)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) red[(wave * MT + mi * 16 + 4 * lq + i) * RS + ni * 16 + l15] = acc[mi][ni][i];
+  __syncthreads();
+
+  for (int e = tid; e < MT * NT; e += 256) {
+    const int row = e / NT, col = e - row * NT;
+    const int m = m0 + row, j = q0 + col;
+    if (m >= a.m || j >= a.n) continue;
+    float v = red[row * RS + col];
+    v += red[(MT + row) * RS + col];
+    v += red[(2 * MT + row) * RS + col];
+    v += red[(3 * MT + row) * RS + col];
+    int co = m, ph = 0;
+    if (TRANSPOSED) {
+      if (ROWS == StreamRows::PhaseMajor) {
+        ph = m / a.c_out;
+        co = m - ph * a.c_out;
+      } else {
+        co = m / a.phases;
+        ph = m - co * a.phases;
+      }
+    }
+    const size_t o = ((size_t)b * a.c_out + co) * a.t_out + (TRANSPOSED ? j * a.phases + ph : j);
+    if (a.bias) v += a.bias[co];
+    if (a.add1) v += a.add1[o];
+    if (a.add2) v += a.add2[o];
+    if (a.out_mul != 1.0f) v *= a.out_mul;
+    if (a.out_div != 1.0f) v = v / a.out_div;
+    v = apply_act(v, a.post_act, a.post_slope);
+    a.y[o] = v;
+  }
+}
+
+// ---- host side
+
+struct StreamGeom {
+  int taps, dil, hist;  // reduction taps, their spacing, history columns H
+  int m, m_pad, cin_pad;  // m_pad, cin_pad: of the fp32 packed image
+  int phases;           // transposed: stride (output column j * phases + phase), else 1
+};
+
+// What a stream launch covers, in either precision (conv1d_stream.hip); the reason for a refusal is pwg_last_error.
+// Shared between two translation units but not exported from the library.
+__attribute__((visibility("hidden"))) int stream_geometry(const pwg_conv1d_desc* d, StreamGeom* g);
+
+// The fields both kernels' argument structs share
+struct StreamCommonArgs {
+  const float* x;
+  const float* hist_in;
+  float* hist_out;
+  int c_in, hist, taps, dil;
+  int step_q, step_w;  // 256 / W and 256 % W for the staged window of W = tile columns + hist columns
+  int pad_mode, pre_act;
+  float pre_slope;
+  StreamEpilogue ep;
+};
+
+// ---- tile rule: 16 / 32 / 64 columns for chunks of up to 16 / 32 / more; 32-row blocks only when they still give
+// every CU two workgroups (the order of an element's sum is the same)
+struct StreamTile {
+  int tn, tm, col_tiles;
+};
+static inline StreamTile stream_tile(int n, int m, int batch) {
+  StreamTile t;
+  t.tn = n <= 16 ? 1 : (n <= 32 ? 2 : 4);
+  t.col_tiles = ceil_div(n, 16 * t.tn);
+  t.tm = (t.tn == 4 && (long)ceil_div(m, 32) * t.col_tiles * batch >= 2 * kStreamFillWorkgroups) ? 2 : 1;
+  return t;
+}
+
+// LDS of a launch: the window, or the partial tiles that reuse it
+static inline size_t stream_lds_bytes(size_t window_bytes, const StreamTile& t) {
+  const size_t red = (size_t)4 * (16 * t.tm) * (16 * t.tn + 1) * sizeof(float);
+  return window_bytes > red ? window_bytes : red;
+}
+
+static inline int stream_check_pointers(const char* name, const pwg_conv1d_desc* d, const StreamGeom& g, const void* x,
+                                        const void* w, const void* y, const float* hist_in, const float* hist_out) {
+  PWG_REQUIRE(x && w && y, PWG_ERR_NULL, "%s: NULL pointer", name);
+  PWG_REQUIRE(hist_out || g.hist == 0, PWG_ERR_NULL, "%s: hist_out is NULL (the layer keeps %d columns)", name, g.hist);
+  PWG_REQUIRE(g.hist == 0 || hist_in != hist_out, PWG_ERR_BAD_SHAPE,
+              "%s: hist_in and hist_out must be distinct buffers (other workgroups read the history)", name);
+  PWG_REQUIRE(hist_in || d->pad_mode != PWG_PAD_REFLECT || d->t_in > g.hist, PWG_ERR_BAD_SHAPE,
+              "%s: a reflect-padded stream starts with at least %d columns (got %d)", name, g.hist + 1, d->t_in);
+  return PWG_OK;
+}
+
+static inline void stream_fill_args(StreamCommonArgs* a, const pwg_conv1d_desc* d, const StreamGeom& g, const StreamTile& t,
+                                    const float* x, const float* hist_in, float* hist_out, const float* bias,
+                                    const float* add1, const float* add2, float* y) {
+  a->x = x;
+  a->hist_in = g.hist ? hist_in : nullptr;
+  a->hist_out = hist_out;
+  a->c_in = d->c_in;
+  a->hist = g.hist;
+  a->taps = g.taps;
+  a->dil = g.dil;
+  a->step_q = 256 / (16 * t.tn + g.hist);
+  a->step_w = 256 % (16 * t.tn + g.hist);
+  a->pad_mode = d->pad_mode;
+  a->pre_act = d->pre_act;
+  a->pre_slope = d->pre_slope;
+  a->ep = StreamEpilogue{bias, add1, add2, y, d->c_out, d->t_in, d->t_out, g.m, g.phases,
+                         d->post_act, d->post_slope, d->out_mul, d->out_div};
+}
+
+// The four tile configurations of a kernel template, handed over as K<TM, TN, TRANSPOSED>::fn
+template <template <int, int, bool> class K, class Args>
+static inline void stream_launch(const StreamTile& t, bool transposed, const Args& a, int m, int batch, size_t lds,
+                                 hipStream_t stream) {
+  void (*kern)(Args);
+  if (t.tn == 1)
+    kern = transposed ? K<1, 1, true>::fn : K<1, 1, false>::fn;
+  else if (t.tn == 2)
+    kern = transposed ? K<1, 2, true>::fn : K<1, 2, false>::fn;
+  else if (t.tm == 1)
+    kern = transposed ? K<1, 4, true>::fn : K<1, 4, false>::fn;
+  else
+    kern = transposed ? K<2, 4, true>::fn : K<2, 4, false>::fn;
+  hipLaunchKernelGGL(kern, dim3(t.col_tiles, ceil_div(m, 16 * t.tm), batch), dim3(256), lds, stream, a);
+}
+
+}  // namespace pwg

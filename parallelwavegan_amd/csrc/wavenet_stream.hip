@@ -39,7 +39,7 @@
 // not on n, the batch, the chunk's position in the stream, or the column's place in the tile (a column is one MFMA
 // lane position; its accumulator sees the same operand sequence wherever it sits, a padded or history operand is the
 // same value through either staging path) -- so any partition of a stream gives bit-identical results.  DESIGN.md s11.3.
-#include "common.h"
+#include "stream_common.h"
 #include "wavenet_gate.h"
 
 #include <stdint.h>
@@ -278,22 +278,8 @@ __global__ __launch_bounds__(256, 2) void wavenet_stream_kernel(WnStreamArgs a) 
     }
   }
 
-  // ---- hist_out = last H columns of concat(hist_in, x), raw; the item's elements are dealt over its workgroups
-  {
-    const int total = WN_R * H;
-    float* __restrict__ ho = a.hist_out + (long)b * WN_R * H;
-#pragma unroll 4
-    for (int i = blockIdx.x * 256 + tid; i < total; i += gridDim.x * 256) {
-      const int ci = i / H, hh = i - ci * H;
-      const int t = n - H + hh;
-      float v = 0.f;
-      if (t >= 0)
-        v = xb[(long)ci * n + t];
-      else if (hb)
-        v = hb[(long)ci * H + n + hh];
-      ho[i] = v;
-    }
-  }
+  // ---- hist_out = last H columns of concat(hist_in, x), raw (start of stream: zeros)
+  stream_write_history<4>(xb, hb, a.hist_out + (long)b * WN_R * H, WN_R, n, H, false, blockIdx.x, gridDim.x);
 }
 
 static int wavenet_stream_geometry(const pwg_wavenet_desc* d) {

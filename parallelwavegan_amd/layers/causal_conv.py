@@ -102,6 +102,16 @@ def stream_pointwise(cv, x, precision="fp32", **fused):
     return _stream_forward(cv, desc, x, None, None, fused, precision)
 
 
+def stream_history_pairs(layers, hist_in, hist_out):
+    """Iterator over ``(hist_in[i], hist_out[i])`` for the layers of a model's ``stream_layers()`` (``hist_in`` None, the
+    start of a stream: ``(None, hist_out[i])``).  A list of the wrong length is an error, not a shorter walk."""
+    n = len(layers)
+    if len(hist_out) != n or (hist_in is not None and len(hist_in) != n):
+        raise ValueError(f"stream_forward: hist_in / hist_out hold {None if hist_in is None else len(hist_in)} / "
+                         f"{len(hist_out)} history tensors, stream_layers() has {n}")
+    return iter(zip(hist_in if hist_in is not None else [None] * n, hist_out))
+
+
 def _desc_kw(fused):
     return {k: v for k, v in fused.items() if k not in ("add1", "add2")}
 
@@ -109,25 +119,21 @@ def _desc_kw(fused):
 def _stream_forward(cv, desc, x, hist_in, hist_out, fused, precision="fp32"):
     if precision not in ("fp32", "bf16"):
         raise ValueError(f"stream precision must be 'fp32' or 'bf16', got {precision!r}")
-    bias = None if cv.bias is None else cv.bias.detach()
-    if precision == "bf16":
-        # the precision of the call: the module's own `precision` attribute (whole-utterance mode) is not consulted
-        if not ops.conv1d_stream_bf16_supported(desc):
-            from .. import _lib
-
-            raise RuntimeError("the bf16 streaming kernel does not cover this layer: "
-                               + _lib.lib().pwg_last_error().decode(errors="replace"))
-        with torch.no_grad():
-            return ops.conv1d_stream_forward_bf16(desc, x.contiguous(), hist_in, hist_out, cv.packed_weight_bf16(), bias,
-                                                  fused.get("add1"), fused.get("add2"))
-    if cv.precision != "fp32":
+    # the precision of the call: a bf16 call does not consult the module's own `precision` attribute (whole-utterance
+    # mode); an fp32 call refuses a module in bf16 mode
+    if precision == "fp32" and cv.precision != "fp32":
         raise RuntimeError(f"{cv.__class__.__name__} is in {cv.precision} inference precision: the streaming kernel is fp32 "
                            "(pass precision='bf16' to stream with bf16 operands)")
-    if not ops.conv1d_stream_supported(desc):
+    if precision == "bf16":
+        kernel, supported, forward = "bf16 streaming kernel", ops.conv1d_stream_bf16_supported, ops.conv1d_stream_forward_bf16
+    else:
+        kernel, supported, forward = "streaming kernel", ops.conv1d_stream_supported, ops.conv1d_stream_forward
+    if not supported(desc):
         from .. import _lib
 
-        raise RuntimeError("the streaming kernel does not cover this layer: "
+        raise RuntimeError(f"the {kernel} does not cover this layer: "
                            + _lib.lib().pwg_last_error().decode(errors="replace"))
+    bias = None if cv.bias is None else cv.bias.detach()
     with torch.no_grad():
-        return ops.conv1d_stream_forward(desc, x.contiguous(), hist_in, hist_out, cv.packed_weight(), bias,
-                                         fused.get("add1"), fused.get("add2"))
+        image = cv.packed_weight_bf16() if precision == "bf16" else cv.packed_weight()
+        return forward(desc, x.contiguous(), hist_in, hist_out, image, bias, fused.get("add1"), fused.get("add2"))

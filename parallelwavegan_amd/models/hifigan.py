@@ -12,7 +12,7 @@ import torch
 
 from .. import functional as Fn
 from ..layers.activation import FusedActivation, PreActivated, deferrable
-from ..layers.causal_conv import CausalConv1d, CausalConvTranspose1d
+from ..layers.causal_conv import CausalConv1d, CausalConvTranspose1d, stream_history_pairs
 from ..layers.conv import Conv1d, Conv2d, ConvTranspose1d, each_conv
 from ..layers.pooling import get_pooling
 from ..streams import fork_now, run_branches, run_branches_chained
@@ -136,8 +136,7 @@ class HiFiGANGenerator(torch.nn.Module):
         of :meth:`stream_layers` (``hist_in`` None: start of stream); see :class:`utils.CausalStream`.  ``precision``:
         ``"bf16"`` runs every convolution on the bf16-operand stream kernel (the modules' own ``precision`` attributes
         are not consulted)."""
-        layers = self.stream_layers()
-        hist = iter(zip(hist_in if hist_in is not None else [None] * len(layers), hist_out))
+        hist = stream_history_pairs(self.stream_layers(), hist_in, hist_out)
         c = self.input_conv.stream_forward(c, *next(hist), precision=precision)
         nb = self.num_blocks
         for i in range(self.num_upsamples):

@@ -6,7 +6,7 @@ import numpy as np
 import torch
 
 from ..layers.activation import FusedActivation, PreActivated, deferrable
-from ..layers.causal_conv import CausalConv1d, CausalConvTranspose1d
+from ..layers.causal_conv import CausalConv1d, CausalConvTranspose1d, stream_history_pairs
 from ..layers.conv import Conv1d, ConvTranspose1d
 from ..layers.padding import FusedPad, get_pad
 from ..layers.pooling import get_pooling
@@ -144,8 +144,7 @@ class MelGANGenerator(torch.nn.Module, _MelGANNormMixin):
         one history tensor per layer of :meth:`stream_layers` (``hist_in`` None: start of stream, which for the
         reflect-padded layers needs ``utils.CausalStream.warmup_frames`` frames); see :class:`utils.CausalStream`.
         ``precision``: ``"bf16"`` runs every convolution, the 1 x 1 ones included, on the bf16-operand stream kernel."""
-        layers = self.stream_layers()
-        hist = iter(zip(hist_in if hist_in is not None else [None] * len(layers), hist_out))
+        hist = stream_history_pairs(self.stream_layers(), hist_in, hist_out)
         walk = list(self._stream_walk())
         last_conv = max(i for i, m, _, _ in walk if isinstance(m, CausalConv1d))
         x = c

@@ -143,20 +143,18 @@ class ParallelWaveGANGenerator(torch.nn.Module, _WeightNormMixin):
         block; the running skip sum is updated in place and the last block applies sqrt(1 / layers).  ``hist_in`` /
         ``hist_out``: one history tensor per layer of :meth:`stream_layers` (``hist_in`` None: start of stream); see
         :class:`utils.PWGStream`."""
-        from ..layers.causal_conv import stream_pointwise
+        from ..layers.causal_conv import stream_history_pairs, stream_pointwise
 
-        n_layers = len(self.stream_layers())
-        n_up = n_layers - len(self.conv_layers)
-        assert len(hist_out) == n_layers and (hist_in is None or len(hist_in) == n_layers)
-        c = self.upsample_net.stream_forward(c, None if hist_in is None else hist_in[:n_up], hist_out[:n_up])
+        hist = list(stream_history_pairs(self.stream_layers(), hist_in, hist_out))
+        n, n_up = len(self.conv_layers), len(hist) - len(self.conv_layers)
+        # (the upsampler takes its layers' pairs as two lists; a None entry is its start of stream too)
+        c = self.upsample_net.stream_forward(c, [h_in for h_in, _ in hist[:n_up]], [h_out for _, h_out in hist[:n_up]])
         assert c.size(-1) == z.size(-1)
         x = stream_pointwise(self.first_conv, z)
         skips = None
-        n = len(self.conv_layers)
-        for i, f in enumerate(self.conv_layers):
-            x, skips = f.stream_forward(x, c, None if hist_in is None else hist_in[n_up + i], hist_out[n_up + i],
-                                        skips=skips, skip_scale=math.sqrt(1.0 / n) if i == n - 1 else 1.0,
-                                        inplace_skips=True)
+        for i, (f, (h_in, h_out)) in enumerate(zip(self.conv_layers, hist[n_up:])):
+            x, skips = f.stream_forward(x, c, h_in, h_out, skips=skips,
+                                        skip_scale=math.sqrt(1.0 / n) if i == n - 1 else 1.0, inplace_skips=True)
         x = stream_pointwise(self.last_conv_layers[1], skips, pre_act="relu")
         return stream_pointwise(self.last_conv_layers[3], x, pre_act="relu")
 

@@ -264,11 +264,8 @@ def conv1d_stream_hist_floats(desc):
     return _lib.lib().pwg_conv1d_stream_hist_floats(ctypes.byref(desc))
 
 
-def conv1d_stream_forward(desc, x, hist_in, hist_out, w_packed, bias=None, add1=None, add2=None, out=None):
-    """One chunk of a causal convolution's stream: ``out`` from the ``desc.t_in`` new columns ``x`` and the history
-    ``hist_in`` (None: start of stream), and ``hist_out`` = the last H columns of ``concat(hist_in, x)``, in one
-    launch.  ``hist_in`` and ``hist_out`` must be distinct buffers."""
-    _require_device(x, hist_in, hist_out, w_packed, bias, add1, add2, out)
+def _conv1d_stream_out(desc, x, hist_in, hist_out, add1, add2, out):
+    """The checks the two conv stream wrappers share -> ``out`` (allocated if None)."""
     if out is None:
         out = torch.empty((desc.batch, desc.c_out, desc.t_out), device=x.device, dtype=torch.float32)
     assert x.numel() == desc.batch * desc.c_in * desc.t_in, (tuple(x.shape), desc.batch, desc.c_in, desc.t_in)
@@ -278,6 +275,15 @@ def conv1d_stream_forward(desc, x, hist_in, hist_out, w_packed, bias=None, add1=
         assert t is None or t.numel() == n_hist, (tuple(t.shape), n_hist)
     for t in (add1, add2):
         assert t is None or t.numel() == out.numel()
+    return out
+
+
+def conv1d_stream_forward(desc, x, hist_in, hist_out, w_packed, bias=None, add1=None, add2=None, out=None):
+    """One chunk of a causal convolution's stream: ``out`` from the ``desc.t_in`` new columns ``x`` and the history
+    ``hist_in`` (None: start of stream), and ``hist_out`` = the last H columns of ``concat(hist_in, x)``, in one
+    launch.  ``hist_in`` and ``hist_out`` must be distinct buffers."""
+    _require_device(x, hist_in, hist_out, w_packed, bias, add1, add2, out)
+    out = _conv1d_stream_out(desc, x, hist_in, hist_out, add1, add2, out)
     _lib.check(_lib.lib().pwg_conv1d_stream_forward(ctypes.byref(desc), _ptr(x), _ptr(hist_in), _ptr(hist_out),
                                                     _ptr(w_packed), _ptr(bias), _ptr(add1), _ptr(add2), _ptr(out),
                                                     _stream()), "conv1d_stream_forward")
@@ -297,15 +303,7 @@ def conv1d_stream_forward_bf16(desc, x, hist_in, hist_out, w_packed_bf16, bias=N
     _require_device(x, hist_in, hist_out, bias, add1, add2, out)
     if not w_packed_bf16.is_cuda or w_packed_bf16.dtype != torch.uint8:
         raise RuntimeError("conv1d_stream_forward_bf16: w_packed_bf16 must be the device image of pack_weight_bf16")
-    if out is None:
-        out = torch.empty((desc.batch, desc.c_out, desc.t_out), device=x.device, dtype=torch.float32)
-    assert x.numel() == desc.batch * desc.c_in * desc.t_in, (tuple(x.shape), desc.batch, desc.c_in, desc.t_in)
-    assert out.numel() == desc.batch * desc.c_out * desc.t_out
-    n_hist = conv1d_stream_hist_floats(desc)
-    for t in (hist_in, hist_out):
-        assert t is None or t.numel() == n_hist, (tuple(t.shape), n_hist)
-    for t in (add1, add2):
-        assert t is None or t.numel() == out.numel()
+    out = _conv1d_stream_out(desc, x, hist_in, hist_out, add1, add2, out)
     zdesc = desc
     if desc.pad_mode != PAD["zero"]:
         zdesc = ConvDesc.from_buffer_copy(desc)

@@ -178,11 +178,75 @@ def _capture_directions(halves, run):
     return out
 
 
-class _StreamGraphs:
-    """The captured graphs of a stream (``_graphs``: chunk shape -> entry, most recently used last; ``_state``: the
-    model's parameter state they were captured under; ``_watch``: a ``GraphedInference`` asked for that state only)."""
+class _Stream:
+    """What the stream classes share: the constructor's common checks, the ping-pong state (``_halves``: two lists of
+    history tensors, a push reads ``_halves[_cur]`` and writes the other), feature coercion, the counters, the step
+    (eager first push, then replay or run, then swap) and the captured graphs (``_graphs``: chunk shape -> entry, most
+    recently used last; ``_state``: the model's parameter state they were captured under; ``_watch``: a
+    ``GraphedInference`` asked for that state only).  A subclass validates its model, then calls ``__init__``; it
+    provides ``push``, ``reset`` and ``_capture``."""
 
     max_graph_shapes = 4  # chunk sizes whose graphs are kept (least recently used evicted)
+
+    def __init__(self, model, layers, batch, use_graph, normalize_before, extra_history=()):
+        """``layers``: ``model.stream_layers()``; ``batch``: from ``_checked_batch``; ``extra_history``: shapes of
+        further state tensors that ride behind the layers' in both halves."""
+        name = type(self).__name__
+        _require_device(next(model.parameters()))  # no CPU fallback
+        if normalize_before and not (hasattr(model, "mean") and hasattr(model, "scale")):
+            raise ValueError(f"{name}: normalize_before=True needs model.register_stats(...)")
+        self.model = model.eval()
+        self.batch = batch
+        self.use_graph = bool(use_graph)
+        self.normalize_before = bool(normalize_before)
+        self._layers = layers
+        self._device = next(model.parameters()).device
+        shapes = [layer.history_shape(batch) for layer, _ in layers] + list(extra_history)
+        self._halves = [[torch.zeros(shape, device=self._device) for shape in shapes] for _ in range(2)]
+        self._watch = GraphedInference(model)  # (only its parameter-state key is used)
+        self._state = None
+        self._graphs = {}
+        self.reset()
+
+    @classmethod
+    def _checked_batch(cls, batch):
+        batch = int(batch)
+        if batch < 1:
+            raise ValueError(f"{cls.__name__}: batch must be >= 1")
+        return batch
+
+    @property
+    def state_bytes(self):
+        """Bytes of history held on the device (both ping-pong halves)."""
+        return sum(t.numel() * t.element_size() for half in self._halves for t in half)
+
+    def _restart(self):
+        """Back to start of stream: half 0 is written next, from ``hist_in = None``; the counters start over."""
+        self._cur = 0          # which half holds the current history
+        self._started = False  # False: the next run passes hist_in = None
+        self.frames_in = 0
+        self.frames_out = 0
+        self.samples_out = 0
+
+    def _features(self, feats):
+        """(B, n, C) features -> (B, C, n), normalised with the model's statistics if the stream says so."""
+        mean = self.model.mean if self.normalize_before else None
+        scale = self.model.scale if self.normalize_before else None
+        return normalize_transpose(feats, mean, scale)
+
+    def _coerce(self, feats):
+        """What ``push`` takes -> contiguous (batch, n, C) fp32 on the stream's device."""
+        feats = torch.as_tensor(feats, dtype=torch.float32).to(self._device)
+        if feats.dim() == 2:
+            feats = feats.unsqueeze(0)
+        if feats.dim() != 3 or feats.shape[0] != self.batch:
+            raise ValueError(f"{type(self).__name__}.push: expected (n, C) or ({self.batch}, n, C) features, got "
+                             f"{tuple(feats.shape)}")
+        return feats.contiguous()
+
+    def _empty(self):
+        """The emission of a push that emits nothing."""
+        return torch.empty((self.batch, 0), device=self._device, dtype=torch.float32)
 
     def _graph_entry(self, key, capture):
         """The entry of chunk shape ``key``, captured by ``capture()`` on first use.  All graphs are dropped when the
@@ -198,8 +262,46 @@ class _StreamGraphs:
         self._graphs[key] = entry  # most recently used last
         return entry
 
+    def _step(self, n, key, eager, capture, fill_static):
+        """One push of ``n`` frames through the ping-pong halves -> (batch, samples), the caller's own tensor.
+        ``eager(hist_in, hist_out)`` runs the model.  Start of stream (the layers' own padding; once per utterance):
+        ``eager(None, half 0)``.  Afterwards current half -> other half, then the halves swap: eagerly, or with
+        ``capture`` (not None: graph mode) by replaying the graph of chunk shape ``key`` -- ``capture()`` ->
+        ``(*statics, graphs)`` on first use -- after ``fill_static(*statics)`` wrote this push's inputs."""
+        if not self._started:
+            y = eager(None, self._halves[0])
+            self._cur, self._started = 0, True
+        else:
+            if capture is not None:
+                *statics, graphs = self._graph_entry(key, capture)
+                g, static_out = graphs[self._cur]
+                fill_static(*statics)
+                g.replay()
+                y = static_out.clone()
+            else:
+                y = eager(self._halves[self._cur], self._halves[1 - self._cur])
+            self._cur = 1 - self._cur
+        self.frames_out += n
+        self.samples_out += y.shape[1]
+        return y
 
-class CausalStream(_StreamGraphs):
+    def push_pcm16(self, *args, **kwargs):
+        """``push`` through the float -> PCM16 conversion: (batch, samples) int16."""
+        return to_pcm16(self.push(*args, **kwargs))
+
+    def close(self):
+        """End of the utterance.  Nothing is held back here; a stream that can hold frames overrides it."""
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            self.close()
+        return False
+
+
+class CausalStream(_Stream):
     """Stateful streaming synthesis for ``HiFiGANGenerator`` and ``MelGANGenerator`` built with
     ``use_causal_conv=True``: ``push`` takes the next mel frames of ``batch`` lock-step streams and returns their
     samples; any partition of the same frames gives bit-identical audio, equal to the whole-utterance ``forward`` up to
@@ -234,8 +336,6 @@ class CausalStream(_StreamGraphs):
     until then, returning zero-length waveforms, and ``close()`` raises if frames are still held.
     """
 
-    max_graph_shapes = 4  # chunk sizes whose graphs are kept (least recently used evicted)
-
     def __init__(self, model, batch=1, use_graph=True, normalize_before=False, precision=None):
         from ..layers.conv import each_conv
         from ..layers.pqmf import PQMF
@@ -247,9 +347,9 @@ class CausalStream(_StreamGraphs):
             raise ValueError(f"CausalStream: {model.__class__.__name__} is not supported (only the causal HiFiGANGenerator "
                              "and MelGANGenerator map mel frames to samples layer by layer; a causal "
                              "ParallelWaveGANGenerator, which also takes noise, streams through utils.PWGStream)")
-        self._layers = model.stream_layers()  # ValueError for a non-causal model
+        layers = model.stream_layers()  # ValueError for a non-causal model
         out_channels = model.output_conv[1].conv.out_channels if isinstance(model, HiFiGANGenerator) else \
-            self._layers[-1][0].conv.out_channels
+            layers[-1][0].conv.out_channels
         pqmf = getattr(model, "pqmf", None)
         if out_channels != 1 and (pqmf is None or not isinstance(model, MelGANGenerator)):
             raise ValueError(f"CausalStream: the generator emits {out_channels} sub-bands; only a multi-band "
@@ -266,21 +366,12 @@ class CausalStream(_StreamGraphs):
             raise ValueError("CausalStream: the model is in bf16 inference precision; the fp32 streaming kernel does not "
                              "read that mode (utils.set_inference_precision(model, 'fp32'), or stream with bf16 operands: "
                              "CausalStream(model, precision='bf16'))")
-        batch = int(batch)
-        if batch < 1:
-            raise ValueError("CausalStream: batch must be >= 1")
+        batch = self._checked_batch(batch)
         supported = conv1d_stream_bf16_supported if precision == "bf16" else conv1d_stream_supported
-        for layer, _ in self._layers:
+        for layer, _ in layers:
             if not supported(layer.stream_desc(batch, 8)):
                 raise ValueError(f"CausalStream: {layer} cannot be streamed: "
                                  + _lib.lib().pwg_last_error().decode(errors="replace"))
-        _require_device(next(model.parameters()))  # no CPU fallback
-        if normalize_before and not (hasattr(model, "mean") and hasattr(model, "scale")):
-            raise ValueError("CausalStream: normalize_before=True needs model.register_stats(...)")
-        self.model = model.eval()
-        self.batch = batch
-        self.use_graph = bool(use_graph)
-        self.normalize_before = bool(normalize_before)
         self.precision = precision or "fp32"  # of the stream, fixed for its life
         self.pqmf = pqmf
         self.subbands = out_channels
@@ -288,16 +379,9 @@ class CausalStream(_StreamGraphs):
         self._delay = pqmf.stream_delay_columns if pqmf is not None else 0
         self.latency_samples = self._delay * out_channels
         self.warmup_frames = self.required_warmup_frames(model)
-        dev = next(model.parameters()).device
-        self._halves = [[torch.zeros(layer.history_shape(batch), device=dev) for layer, _ in self._layers]
-                        for _ in range(2)]
-        if pqmf is not None:  # the PQMF history rides behind the layers' in both ping-pong halves
-            for half in self._halves:
-                half.append(torch.zeros(pqmf.history_shape(batch), device=dev))
-        self._watch = GraphedInference(model)  # (only its parameter-state key is used)
-        self._state = None
-        self._graphs = {}
-        self.reset()
+        # the PQMF history rides behind the layers' in both ping-pong halves
+        super().__init__(model, layers, batch, use_graph, normalize_before,
+                         [pqmf.history_shape(batch)] if pqmf is not None else [])
 
     @staticmethod
     def required_warmup_frames(model):
@@ -306,22 +390,13 @@ class CausalStream(_StreamGraphs):
         frame)`` -- 1 for zero-padded models."""
         return max(-(-layer.history_columns_at_start() // rate) for layer, rate in model.stream_layers())
 
-    @property
-    def state_bytes(self):
-        """Bytes of history held on the device (both ping-pong halves)."""
-        return sum(t.numel() * t.element_size() for half in self._halves for t in half)
-
     def reset(self):
         """Back to start of stream: the next push starts from the layers' own padding and, for a multi-band model, from
         the PQMF's zero context.  Held frames and an unflushed tail are dropped."""
-        self._cur = 0          # which half holds the current history
-        self._started = False  # False: the next run passes hist_in = None
+        self._restart()
         self._held = []
         self._columns = 0      # sub-band columns the PQMF stream has taken (multi-band)
         self._flushed = False
-        self.frames_in = 0
-        self.frames_out = 0
-        self.samples_out = 0
 
     def _emit(self, n_cols):
         """Positions a PQMF launch over the next ``n_cols`` columns completes: ``n_cols`` once the stream is past the
@@ -330,9 +405,8 @@ class CausalStream(_StreamGraphs):
 
     def _run(self, feats, hist_in, hist_out, n_emit=None):
         """``hist_in`` (None: start of stream) / ``hist_out``: one ping-pong half each.  -> (batch, samples)."""
-        mean = self.model.mean if self.normalize_before else None
-        scale = self.model.scale if self.normalize_before else None
-        y = self.model.stream_forward(normalize_transpose(feats, mean, scale), hist_in, hist_out,
+        k = len(self._layers)  # (a multi-band stream's halves end with the PQMF's history)
+        y = self.model.stream_forward(self._features(feats), None if hist_in is None else hist_in[:k], hist_out[:k],
                                       precision=self.precision)
         if self.pqmf is None:
             return y.reshape(self.batch, -1)
@@ -353,43 +427,24 @@ class CausalStream(_StreamGraphs):
         caller's own tensor (not a graph's static buffer)."""
         if self._flushed:
             raise RuntimeError("CausalStream.push: the utterance was flushed; reset() starts the next one")
-        dev = self._halves[0][0].device
-        feats = torch.as_tensor(feats, dtype=torch.float32).to(dev)
-        if feats.dim() == 2:
-            feats = feats.unsqueeze(0)
-        if feats.dim() != 3 or feats.shape[0] != self.batch:
-            raise ValueError(f"CausalStream.push: expected (n, C) or ({self.batch}, n, C) features, got {tuple(feats.shape)}")
+        feats = self._coerce(feats)
         self.frames_in += feats.shape[1]
         if not self._started:
             self._held.append(feats)
             if sum(f.shape[1] for f in self._held) < self.warmup_frames:
-                return torch.empty((self.batch, 0), device=dev, dtype=torch.float32)
+                return self._empty()
             feats = torch.cat(self._held, 1) if len(self._held) > 1 else feats
             self._held = []
-        feats = feats.contiguous()
         n = feats.shape[1]
         if n == 0:
-            return torch.empty((self.batch, 0), device=dev, dtype=torch.float32)
+            return self._empty()
         n_cols = n * self.model.upsample_factor
         n_emit = self._emit(n_cols)
-        if not self._started:
-            # start of stream: the layers' own padding; once per utterance, eager
-            y = self._run(feats, None, self._halves[0], n_emit)
-            self._cur, self._started = 0, True
-        else:
-            hist_in, hist_out = self._halves[self._cur], self._halves[1 - self._cur]
-            if self.use_graph and n_emit == n_cols:  # (a multi-band stream still inside the PQMF delay: eager)
-                static_in, graphs = self._graph_entry((n, feats.shape[2]), lambda: self._capture(feats))
-                g, static_out = graphs[self._cur]
-                static_in.copy_(feats, non_blocking=True)
-                g.replay()
-                y = static_out.clone()
-            else:
-                y = self._run(feats, hist_in, hist_out, n_emit)
-            self._cur = 1 - self._cur
-        self.frames_out += n
+        graph = self.use_graph and n_emit == n_cols  # (a multi-band stream still inside the PQMF delay: eager)
+        y = self._step(n, (n, feats.shape[2]), lambda hi, ho: self._run(feats, hi, ho, n_emit),
+                       (lambda: self._capture(feats)) if graph else None,
+                       lambda static_in: static_in.copy_(feats, non_blocking=True))
         self._columns += n_cols
-        self.samples_out += y.shape[1]
         return y
 
     @torch.no_grad()
@@ -398,20 +453,15 @@ class CausalStream(_StreamGraphs):
         (the zeros the whole-utterance synthesis pads with) -> the last ``latency_samples`` samples, (batch, samples).
         Zero-length for a full-band model, before anything was synthesised, and on a second call.  The next utterance
         starts with ``reset()``."""
-        dev = self._halves[0][0].device
         if self.pqmf is None or not self._started or self._flushed:
-            return torch.empty((self.batch, 0), device=dev, dtype=torch.float32)
-        zeros = torch.zeros((self.batch, self.subbands, self._delay), device=dev)
+            return self._empty()
+        zeros = torch.zeros((self.batch, self.subbands, self._delay), device=self._device)
         y = self.pqmf.stream_synthesis(zeros, self._halves[self._cur][-1], self._halves[1 - self._cur][-1],
                                        self._emit(self._delay))
         self._columns += self._delay
         self._flushed = True  # (the halves are not swapped: nothing may follow but reset())
         self.samples_out += y.shape[1]
         return y
-
-    def push_pcm16(self, feats):
-        """``push`` through the float -> PCM16 conversion: (batch, samples) int16."""
-        return to_pcm16(self.push(feats))
 
     def close(self):
         """End of the utterance: raises if frames are still held (the utterance was shorter than ``warmup_frames``,
@@ -422,16 +472,8 @@ class CausalStream(_StreamGraphs):
             raise RuntimeError(f"CausalStream: {held} frame(s) were pushed but the reflect-padded start of this model "
                                f"needs {self.warmup_frames} before the first sample can be emitted")
 
-    def __enter__(self):
-        return self
 
-    def __exit__(self, exc_type, exc, tb):
-        if exc_type is None:
-            self.close()
-        return False
-
-
-class PWGStream(_StreamGraphs):
+class PWGStream(_Stream):
     """Stateful streaming synthesis for ``ParallelWaveGANGenerator`` built with ``use_causal_conv=True``: ``push`` takes
     the next mel frames (and, optionally, the noise for their samples) of ``batch`` lock-step streams and returns their
     samples, one launch per layer: the upsampler's ``conv_in`` and stages, the 1 x 1 convolutions and the 30 gated
@@ -461,9 +503,7 @@ class PWGStream(_StreamGraphs):
         if not isinstance(model, ParallelWaveGANGenerator):
             raise ValueError(f"PWGStream: {model.__class__.__name__} is not supported (only the causal "
                              "ParallelWaveGANGenerator; HiFiGANGenerator and MelGANGenerator stream through CausalStream)")
-        batch = int(batch)
-        if batch < 1:
-            raise ValueError("PWGStream: batch must be >= 1")
+        batch = self._checked_batch(batch)
         reason = model.stream_unsupported_reason(batch)
         if reason is not None:
             raise ValueError(f"PWGStream: {reason}")
@@ -473,39 +513,15 @@ class PWGStream(_StreamGraphs):
         if any(cv.precision != "fp32" for cv in each_conv(model)):
             raise ValueError("PWGStream: the model is in bf16 inference precision; the streaming layer kernel is fp32 "
                              "(utils.set_inference_precision(model, 'fp32'))")
-        self._layers = model.stream_layers()
-        for layer, _ in self._layers:
+        layers = model.stream_layers()
+        for layer, _ in layers:
             if isinstance(layer, ConvInStream) and not conv1d_stream_supported(layer.stream_desc(batch, 8)):
                 raise ValueError(f"PWGStream: {layer} cannot be streamed: "
                                  + _lib.lib().pwg_last_error().decode(errors="replace"))
-        _require_device(next(model.parameters()))  # no CPU fallback
-        if normalize_before and not (hasattr(model, "mean") and hasattr(model, "scale")):
-            raise ValueError("PWGStream: normalize_before=True needs model.register_stats(...)")
-        self.model = model.eval()
-        self.batch = batch
-        self.use_graph = bool(use_graph)
-        self.normalize_before = bool(normalize_before)
         self.precision = "fp32"
         self.up = model.upsample_factor  # samples per frame
-        self._context = model.aux_context_window if isinstance(self._layers[0][0], ConvInStream) else 0
-        dev = next(model.parameters()).device
-        self._halves = [[torch.zeros(layer.history_shape(batch), device=dev) for layer, _ in self._layers]
-                        for _ in range(2)]
-        self._watch = GraphedInference(model)  # (only its parameter-state key is used)
-        self._state = None
-        self._graphs = {}
-        self.reset()
-
-    @property
-    def state_bytes(self):
-        """Bytes of history held on the device (both ping-pong halves)."""
-        return sum(t.numel() * t.element_size() for half in self._halves for t in half)
-
-    def _features(self, feats):
-        """(B, n, C) features -> (B, C, n), normalised with the model's statistics if the stream says so."""
-        mean = self.model.mean if self.normalize_before else None
-        scale = self.model.scale if self.normalize_before else None
-        return normalize_transpose(feats, mean, scale)
+        self._context = model.aux_context_window if isinstance(layers[0][0], ConvInStream) else 0
+        super().__init__(model, layers, batch, use_graph, normalize_before)
 
     @torch.no_grad()
     def reset(self, context=None):
@@ -513,17 +529,12 @@ class PWGStream(_StreamGraphs):
         zero history everywhere else (``model.inference``).  ``context`` (batch, aux_context_window, C) or
         (aux_context_window, C): those frames are ``conv_in``'s history, every other layer starts from zeros
         (``model.forward`` on ``concat(context, frames, anything)``)."""
-        self._cur = 0          # which half holds the current history
-        self._started = False  # False: the next run passes hist_in = None
-        self.frames_in = 0
-        self.frames_out = 0
-        self.samples_out = 0
+        self._restart()
         if context is None:
             return
         if self._context == 0:
             raise ValueError("PWGStream.reset: the model has no aux_context_window, so there is no context to seed")
-        dev = self._halves[0][0].device
-        context = torch.as_tensor(context, dtype=torch.float32).to(dev)
+        context = torch.as_tensor(context, dtype=torch.float32).to(self._device)
         if context.dim() == 2:
             context = context.unsqueeze(0).expand(self.batch, -1, -1)
         if context.dim() != 3 or context.shape[0] != self.batch or context.shape[1] != self._context:
@@ -547,16 +558,10 @@ class PWGStream(_StreamGraphs):
         """feats: (n, C) or (batch, n, C) float features; noise: (batch, n * up) or (n * up,) (the same for every
         stream), drawn with ``torch.randn`` on the device if omitted -> (batch, n * up) fp32.  The result is the caller's
         own tensor (not a graph's static buffer)."""
-        dev = self._halves[0][0].device
-        feats = torch.as_tensor(feats, dtype=torch.float32).to(dev)
-        if feats.dim() == 2:
-            feats = feats.unsqueeze(0)
-        if feats.dim() != 3 or feats.shape[0] != self.batch:
-            raise ValueError(f"PWGStream.push: expected (n, C) or ({self.batch}, n, C) features, got {tuple(feats.shape)}")
-        feats = feats.contiguous()
+        feats = self._coerce(feats)
         n = feats.shape[1]
         if noise is not None:
-            noise = torch.as_tensor(noise, dtype=torch.float32).to(dev)
+            noise = torch.as_tensor(noise, dtype=torch.float32).to(self._device)
             if noise.dim() == 1:
                 noise = noise.unsqueeze(0).expand(self.batch, -1)
             if tuple(noise.shape) != (self.batch, n * self.up):
@@ -565,47 +570,20 @@ class PWGStream(_StreamGraphs):
             noise = noise.reshape(self.batch, 1, n * self.up).contiguous()
         self.frames_in += n
         if n == 0:
-            return torch.empty((self.batch, 0), device=dev, dtype=torch.float32)
-        if not self._started:
-            # start of stream: the layers' own padding; once per utterance, eager
-            z = noise if noise is not None else torch.randn(self.batch, 1, n * self.up, device=dev)
-            y = self._run(feats, z, None, self._halves[0])
-            self._cur, self._started = 0, True
-        else:
-            hist_in, hist_out = self._halves[self._cur], self._halves[1 - self._cur]
-            if self.use_graph:
-                def capture():
-                    return self._capture(feats, torch.zeros(self.batch, 1, n * self.up, device=dev))
+            return self._empty()
 
-                static_in, static_z, graphs = self._graph_entry((n, feats.shape[2]), capture)
-                g, static_out = graphs[self._cur]
-                static_in.copy_(feats, non_blocking=True)
-                if noise is None:
-                    static_z.normal_()  # (outside the graph: a replay never draws)
-                else:
-                    static_z.copy_(noise, non_blocking=True)
-                g.replay()
-                y = static_out.clone()
+        def eager(hist_in, hist_out):
+            z = noise if noise is not None else torch.randn(self.batch, 1, n * self.up, device=self._device)
+            return self._run(feats, z, hist_in, hist_out)
+
+        def capture():
+            return self._capture(feats, torch.zeros(self.batch, 1, n * self.up, device=self._device))
+
+        def fill_static(static_in, static_z):
+            static_in.copy_(feats, non_blocking=True)
+            if noise is None:
+                static_z.normal_()  # (outside the graph: a replay never draws)
             else:
-                z = noise if noise is not None else torch.randn(self.batch, 1, n * self.up, device=dev)
-                y = self._run(feats, z, hist_in, hist_out)
-            self._cur = 1 - self._cur
-        self.frames_out += n
-        self.samples_out += y.shape[1]
-        return y
+                static_z.copy_(noise, non_blocking=True)
 
-    def push_pcm16(self, feats, noise=None):
-        """``push`` through the float -> PCM16 conversion: (batch, samples) int16."""
-        return to_pcm16(self.push(feats, noise))
-
-    def close(self):
-        """End of the utterance.  Nothing is held back (``warmup_frames`` = 1, no filterbank delay): a no-op kept for
-        symmetry with :class:`CausalStream`."""
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, exc_type, exc, tb):
-        if exc_type is None:
-            self.close()
-        return False
+        return self._step(n, (n, feats.shape[2]), eager, capture if self.use_graph else None, fill_static)

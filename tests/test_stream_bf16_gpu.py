@@ -145,6 +145,31 @@ def test_streamed_bf16_conv_matches_float64_of_rounded_operands(c_in, c_out, k, 
         assert err <= RTOL
 
 
+def test_streamed_bf16_conv_32_row_tile(device, worst):
+    """The 32 x 64 tile, which no other case here reaches: c_out 512, 256 columns, batch 8 is 16 x 4 x 8 = 512
+    workgroups of 32 rows, the threshold of the dispatch rule.  Same reference and bar as the cases above; and stream 0
+    alone, in four chunks of 64 (16 workgroups: the 16-row tile), gives the same bits -- the tile does not change an
+    element's sum order."""
+    c_in, c_out, k, n, batch = 32, 512, 3, 256, 8
+    g = torch.Generator().manual_seed(c_in * 31 + c_out * 7 + k)
+    x = _bf16r(torch.randn(batch, c_in, n, generator=g))
+    w = _bf16r(torch.randn(c_out, c_in, k, generator=g) / (c_in * k) ** 0.5)
+    b = torch.randn(c_out, generator=g)
+    fused, _, post = _epilogue("pre", g, None)
+    xa = _bf16r(_act(x, fused["pre_act"], fused["pre_slope"]))
+    ref = post(torch_cpu.causal_conv1d(xa.double(), w.double(), b.double(), 1))
+    layer = layers.CausalConv1d(c_in, c_out, k)
+    _set(layer.conv, w, b)
+    layer = layer.to(device)
+    y = _stream_layer(layer, x.to(device), (n,), **fused)
+    err = _rel_err(y, ref)
+    print(f"conv {c_in}->{c_out} k{k} B{batch} one push of {n}: rel-to-max error {err:.3e}")
+    worst[(c_in, c_out, k, 1, (n,))] = err
+    assert err <= RTOL
+    alone = _stream_layer(layer, x[:1].to(device), (64,) * 4, **fused)
+    assert torch.equal(alone[0], y[0]), max_abs(alone[0], y[0])
+
+
 @pytest.mark.parametrize("c_in,c_out,batch,epi", POINTWISE_CASES)
 def test_streamed_bf16_pointwise_matches_float64_of_rounded_operands(c_in, c_out, batch, epi, device, worst):
     g = torch.Generator().manual_seed(c_in * 31 + c_out * 7 + 1)

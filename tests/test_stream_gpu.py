@@ -204,6 +204,10 @@ def test_v1_geometry_partition_invariance(device):
 # MelGAN at the recipe's widths: 256 and 128 channels behind the k = 16 / k = 4 upsampling layers, 8 and 16 columns per
 # frame.  At these widths the general convolution kernel has several tiles and reduction splits to choose from, by
 # column count and batch -- the 1 x 1 layers of a ResidualStack must not inherit that choice in a stream.
+# These are also the tests that reach the stream kernel's 32 x 64 tile in fp32: one push of 208 frames at batch 3 is
+# 1664 columns at 256 rows, 8 x 26 x 3 = 624 workgroups of 32 rows (the dispatch rule wants 512), and the batched test
+# compares it bit for bit with the batch-1 streams (208 workgroups: the 16-row tile).  So no separate fp32 case exists;
+# the bf16 kernel's is tests/test_stream_bf16_gpu.py::test_streamed_bf16_conv_32_row_tile.
 MELGAN_WIDE_CAUSAL = dict(in_channels=80, out_channels=1, kernel_size=7, channels=512, upsample_scales=[8, 2],
                           stack_kernel_size=3, stacks=2, use_causal_conv=True)
 
