@@ -233,6 +233,34 @@ int pwg_conv1d_bf16_forward(const pwg_conv1d_desc* d, const float* x, const void
 int pwg_conv1d_bf16_forward_cfg(const pwg_conv1d_desc* d, const float* x, const void* w_packed, const float* bias,
                                 const float* add1, const float* add2, float* y, int32_t mfma_shape, void* stream);
 
+/* ---- split-operand inference (fp32-accurate on the bf16 matrix pipe; csrc/conv1d_split.hip) ----
+ * The fused convolution of pwg_conv1d_forward for stride-1 Conv1d, groups == 1, width == 1, zero padding, forward only,
+ * computed on the gfx950 bf16 MFMA instructions from operands split three ways.  Numerical definition:
+ *   1. pre_act is applied to the fp32 input in fp32;
+ *   2. an fp32 value v (activated input; effective weight w * scale, split once by the packer) is split exactly as
+ *      hi = bf16_rne(v), r = v - float(hi), mid = bf16_rne(r), lo = bf16_rne(r - float(mid)), v == hi + mid + lo;
+ *   3. per operand pair the six products lo.hi, hi.lo, mid.mid, mid.hi, hi.mid, hi.hi (weight part . input part) are
+ *      accumulated in this order in fp32 by the MFMA; each dropped product is <= 2^-24 of the full product (about 2^-28 on average);
+ *   4. bias, add1, add2, out_mul, out_div, post_act and the stored result are fp32.
+ * Non-finite inputs give non-finite outputs (an inf may come out as NaN).  Deterministic (no split reduction, no
+ * atomics; the accumulation order of an element does not depend on tile or grid).  pwg_conv1d_split_supported is pure
+ * host logic (no device needed; pwg_last_error names the reason for 0).  The image is
+ * pwg_conv1d_split_packed_weight_bytes bytes (0 = unsupported), 16-B aligned: three images of the bf16 layout.
+ * pwg_conv1d_split_forward takes the arguments of pwg_conv1d_forward in the same order (the workspace is never used and
+ * may be NULL / 0).  pwg_conv1d_split_forward_cfg (tuning / tests): mfma_shape 32 = 32x32x16, 16 = 16x16x32 at the same
+ * output tile; tile_mode 0 = the small-grid rule decides, 1 = full-size tiles (where they fit LDS), 2 = half-size tiles
+ * (same bits).                                                                                                       */
+int pwg_conv1d_split_supported(const pwg_conv1d_desc* d);
+size_t pwg_conv1d_split_packed_weight_bytes(const pwg_conv1d_desc* d);
+int pwg_conv1d_split_pack_weight(const pwg_conv1d_desc* d, const float* w, const float* scale, void* w_packed,
+                                 void* stream);
+int pwg_conv1d_split_forward(const pwg_conv1d_desc* d, const float* x, const void* w_packed, const float* bias,
+                             const float* add1, const float* add2, float* y, float* workspace, size_t workspace_floats,
+                             void* stream);
+int pwg_conv1d_split_forward_cfg(const pwg_conv1d_desc* d, const float* x, const void* w_packed, const float* bias,
+                                 const float* add1, const float* add2, float* y, int32_t mfma_shape, int32_t tile_mode,
+                                 void* stream);
+
 /* ---- stateful streaming form of the causal convolutions (fp32; csrc/conv1d_stream.hip; ABI v14) ----
  * The causal layers of the reference -- CausalConv1d.forward, layers/causal_conv.py:32-42 (`self.conv(self.pad(x))
  * [:, :, :x.size(2)]`), and CausalConvTranspose1d.forward, :68-78 (`self.deconv(self.pad(x))[:, :, self.stride :

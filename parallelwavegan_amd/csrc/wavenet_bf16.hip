@@ -20,7 +20,7 @@
 // second LDS tile ([column][64 channels], bf16) and is the B operand of the two 1x1 convolutions (one K = 64
 // contraction with 128 rows: skip rows then out rows).  A operands (weights) are 16-B fragments of a packed image
 // [K / 8][128 rows][8] (phase 1, then phase 2), read straight from L2 through a 4-step register ring.  The kernel is
-// latency-bound (DESIGN.md s10): everything a workgroup needs from memory is requested up front -- the staging loads,
+// latency-bound (DESIGN.md s9.1): everything a workgroup needs from memory is requested up front -- the staging loads,
 // then the epilogue's fp32 residual and skip sum, then the first weight fragments -- and the biases sit in LDS.
 // LDS: 47 KB, three workgroups per CU.  Both bf16 MFMA shapes (32x32x16, 16x16x32) are built at the same tiles;
 // pwg_wavenet_bf16_layer_forward_cfg selects.  Deterministic: one workgroup owns its output tile over the whole
@@ -49,7 +49,7 @@ constexpr int RS = K1 + 8;              // bf16 per column of the operand tile (
 constexpr int RG = K2 + 8;              // bf16 per column of the gate tile (144 B = 9 x 16 B)
 constexpr size_t kLds = (size_t)BCOLS * (RS + RG) * sizeof(__bf16) + (BG + BS + BR) * sizeof(float);
 constexpr int RING = 4;                 // phase-1 weight fragments in flight (k-steps)
-constexpr int kDefaultMfmaShape = 32;  // by wall time at the PWG.v1 shapes (DESIGN.md s10)
+constexpr int kDefaultMfmaShape = 32;  // by wall time at the PWG.v1 shapes (DESIGN.md s9.1)
 
 struct WbArgs {
   const float* x;       // (B, 64, T)

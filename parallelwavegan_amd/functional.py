@@ -106,7 +106,7 @@ class PreparedWeights:
     keeps one instance per parameter epoch, so every forward / backward of that epoch -- e.g. D(y) and
     D(G(c)) of a discriminator phase -- shares a single scale + pack + pack launch sequence."""
 
-    __slots__ = ("key", "w", "_scale", "_fwd", "_fwd_desc", "_bwd", "_res", "_bf16", "_stale")
+    __slots__ = ("key", "w", "_scale", "_fwd", "_fwd_desc", "_bwd", "_res", "_bf16", "_split", "_stale")
 
     def __init__(self, key, w, scale, fwd=None, fwd_desc=None, bwd=None):
         """``fwd``: the packed forward image, or None with ``fwd_desc`` (any descriptor of the layer) to build it
@@ -114,6 +114,7 @@ class PreparedWeights:
         data-gradient image where the caller (the weight bank) has built it already."""
         self.key, self.w, self._scale, self._fwd, self._fwd_desc, self._bwd, self._res = key, w, scale, fwd, fwd_desc, bwd, None
         self._bf16 = None
+        self._split = None
         self._stale = False  # set by weight_bank.WeightBank when it overwrites the (shared, persistent) images
 
     @property
@@ -149,6 +150,10 @@ class PreparedWeights:
     def bf16(self):
         """bf16 MFMA weight image of the opt-in bf16-operand inference mode (csrc/conv1d_bf16.hip)."""
         return self._image("_bf16", ops.pack_weight_bf16, self._fwd_desc)
+
+    def split(self):
+        """The three bf16 images of the split-operand fp32 inference kernel (csrc/conv1d_split.hip)."""
+        return self._image("_split", ops.pack_weight_split, self._fwd_desc)
 
     def bwd(self, desc):
         return self._image("_bwd", ops.pack_weight_bwd, desc)

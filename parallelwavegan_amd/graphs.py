@@ -15,7 +15,7 @@ class GraphedInference:
     The capture records the kernels that read the packed weight images of that moment.  Every call first compares the
     model's *parameter state* -- the key of the weight-image caches (``ops.cache_epoch``, ``ops.tensor_state``;
     DESIGN.md s3.7) over every parameter and buffer, plus the training flag and every convolution's inference precision
-    -- with the state at capture time; after ``load_state_dict``, an optimizer step, ``remove_weight_norm``,
+    and split-operand switch -- with the state at capture time; after ``load_state_dict``, an optimizer step, ``remove_weight_norm``,
     ``set_inference_precision`` ... the stale graphs are dropped and the call captures again, so a replay can never
     synthesise with old weights.  :meth:`reset` does the same by hand."""
 
@@ -53,6 +53,8 @@ class GraphedInference:
 
             self._convs = list(each_conv(model))
         st.append(tuple(m.precision for m in self._convs))
+        # ... and the split-operand switch with its admission table (layers/conv.py): both decide which kernel a layer runs
+        st.append(tuple((m.split_exact, m.split_admit_all) for m in self._convs))
         return st
 
     def _capture(self, inputs):

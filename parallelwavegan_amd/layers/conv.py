@@ -35,6 +35,11 @@ class _ConvNd(torch.nn.Module):
     # (csrc/conv1d_bf16.hip), fp32 accumulation, epilogue and tensors; inference only.  Set through
     # utils.set_inference_precision; a layer the bf16 kernel does not cover stays on the fp32 kernels.
     precision = "fp32"
+    # Split-operand fp32 inference (csrc/conv1d_split.hip): a no-grad forward of an fp32 module whose
+    # class is in SPLIT_ADMITTED runs on the bf16 MFMA with 3-way split operands.  On by default; PWG_SPLIT_EXACT=0
+    # switches it off for A/B runs (read once).  split_admit_all (tests, measurements): every layer the kernel supports.
+    split_exact = {"0": False, "1": True}.get(os.environ.get("PWG_SPLIT_EXACT", ""), True)
+    split_admit_all = False
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1,
                  bias=True, output_padding=0, pad_mode="zero"):
@@ -225,6 +230,15 @@ class _ConvNd(torch.nn.Module):
         """Cached bf16 weight image (bf16-operand inference), held by the same ``prepared()`` instance."""
         return self._packed(ops.pack_weight_bf16, lambda pw: pw.bf16())
 
+    def packed_weight_split(self):
+        """Cached split-operand weight images (fp32 inference on the bf16 MFMA), held by the same ``prepared()``."""
+        return self._packed(ops.pack_weight_split, lambda pw: pw.split())
+
+    def _split_route(self, desc, needs_grad=False):
+        """Does this no-grad call (``desc``) of an fp32 module run on the split-operand kernel?"""
+        return split_admitted(desc.c_in, desc.c_out, desc.kernel, desc.batch * desc.t_out, needs_grad,
+                              self.split_exact, self.split_admit_all) and ops.conv1d_split_supported(desc)
+
     def bf16_capable(self):
         """Does the bf16-operand kernel cover this layer's geometry (host logic, no device needed)?"""
         return not self.width_mode and ops.conv1d_bf16_supported(self.make_desc(1, self._probe_len()))
@@ -337,6 +351,9 @@ class _ConvNd(torch.nn.Module):
             if self.precision == "bf16" and ops.conv1d_bf16_supported(desc):
                 return ops.conv1d_forward_bf16(desc, x.contiguous(), self.packed_weight_bf16(),
                                                None if self.bias is None else self.bias.detach(), add1, add2)
+            if self.precision == "fp32" and self._split_route(desc):
+                return ops.conv1d_forward_split(desc, x.contiguous(), self.packed_weight_split(),
+                                                None if self.bias is None else self.bias.detach(), add1, add2)
             return ops.conv1d_forward(desc, x.contiguous(), self.packed_weight(),
                                       None if self.bias is None else self.bias.detach(), add1, add2)
 
@@ -344,6 +361,32 @@ class _ConvNd(torch.nn.Module):
         norm = "weight_norm" if self.has_weight_norm else ("spectral_norm" if self.has_spectral_norm else "none")
         return (f"{self.in_channels}, {self.out_channels}, kernel_size={self.kernel_size}, stride={self.stride}, "
                 f"padding={self.padding}, dilation={self.dilation}, groups={self.groups}, norm={norm}")
+
+
+# Admission table of the split-operand kernel: (c_in, c_out, kernel) -> fewest output columns per launch (batch x t_out)
+# from which the class measured faster than the fp32 kernel by more than the spread of its repeated runs
+# (profiles/split_infer.txt).  Classes not listed, and shorter launches, stay on the fp32 kernel.
+# 6400 columns is the shortest launch measured on which each class wins (128 channels: one utterance of 100 frames,
+# 1.30 - 1.36 x; 256 channels: one utterance of 800 frames, 1.04 - 1.07 x; at 800 columns the 256-channel classes lose
+# 2 - 3 x).  16 x 800 frames: k = 7 1.46 x (128) / 1.56 x (256), k = 11 1.70 x / 1.73 x.
+SPLIT_ADMITTED = {
+    (128, 128, 7): 6400,
+    (128, 128, 11): 6400,
+    (256, 256, 7): 6400,
+    (256, 256, 11): 6400,
+}
+
+
+def split_admitted(c_in, c_out, kernel, cols, needs_grad, enabled=True, admit_all=False):
+    """The admission predicate of the split-operand kernel (pure host logic): never when a gradient is needed or the
+    switch is off; else every class (``admit_all``) or the classes of ``SPLIT_ADMITTED`` from their column count on.
+    What the kernel itself covers is ``ops.conv1d_split_supported``'s to say."""
+    if needs_grad or not enabled:
+        return False
+    if admit_all:
+        return True
+    min_cols = SPLIT_ADMITTED.get((c_in, c_out, kernel))
+    return min_cols is not None and cols >= min_cols
 
 
 def each_conv(module):

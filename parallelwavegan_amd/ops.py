@@ -252,6 +252,51 @@ def conv1d_forward_bf16(desc, x, w_packed, bias=None, add1=None, add2=None, out=
     return out
 
 
+def conv1d_split_supported(desc):
+    """Does the split-operand inference kernel (csrc/conv1d_split.hip) cover this descriptor?  Host logic only (no
+    device needed); ``_lib.lib().pwg_last_error()`` names the reason for a False."""
+    return bool(_lib.lib().pwg_conv1d_split_supported(ctypes.byref(desc)))
+
+
+def pack_weight_split(desc, w, scale=None):
+    """torch-layout fp32 weight (+ optional weight_norm row scale) -> the three bf16 MFMA weight images of the
+    split-operand kernel (an opaque byte tensor); the effective weight ``w * scale`` is split here, once."""
+    _require_device(w, scale)
+    n = _lib.lib().pwg_conv1d_split_packed_weight_bytes(ctypes.byref(desc))
+    if n == 0:
+        _lib.check(-1, "conv1d_split_packed_weight_bytes")
+    out = torch.empty(n, device=w.device, dtype=torch.uint8)
+    _lib.check(_lib.lib().pwg_conv1d_split_pack_weight(ctypes.byref(desc), _ptr(w), _ptr(scale), _ptr(out), _stream()),
+               "conv1d_split_pack_weight")
+    return out
+
+
+def conv1d_forward_split(desc, x, w_packed, bias=None, add1=None, add2=None, out=None, mfma_shape=None, tile_mode=0):
+    """Fused fp32 convolution computed on the bf16 MFMA from 3-way split operands (inference only).
+    ``mfma_shape`` (tuning): 32 or 16 selects the MFMA instruction; ``tile_mode`` (tests): 1 = full-size, 2 = half-size
+    tiles instead of the small-grid rule."""
+    _require_device(x, bias, add1, add2, out)
+    if not w_packed.is_cuda or w_packed.dtype != torch.uint8:
+        raise RuntimeError("conv1d_forward_split: w_packed must be the device image of pack_weight_split")
+    if out is None:
+        out = torch.empty((desc.batch, desc.c_out, desc.t_out), device=x.device, dtype=torch.float32)
+    assert x.numel() == desc.batch * desc.c_in * desc.t_in, (tuple(x.shape), desc.batch, desc.c_in, desc.t_in)
+    assert out.numel() == desc.batch * desc.c_out * desc.t_out
+    assert w_packed.numel() == _lib.lib().pwg_conv1d_split_packed_weight_bytes(ctypes.byref(desc)), \
+        "conv1d_forward_split: w_packed is not this layer's split image"
+    for t in (add1, add2):
+        assert t is None or t.numel() == out.numel()
+    if mfma_shape is None and not tile_mode:
+        rc = _lib.lib().pwg_conv1d_split_forward(ctypes.byref(desc), _ptr(x), _ptr(w_packed), _ptr(bias), _ptr(add1),
+                                                 _ptr(add2), _ptr(out), None, 0, _stream())
+    else:
+        rc = _lib.lib().pwg_conv1d_split_forward_cfg(ctypes.byref(desc), _ptr(x), _ptr(w_packed), _ptr(bias),
+                                                     _ptr(add1), _ptr(add2), _ptr(out), int(mfma_shape or 16),
+                                                     int(tile_mode), _stream())
+    _lib.check(rc, "conv1d_forward_split")
+    return out
+
+
 def conv1d_stream_supported(desc):
     """Does the streaming kernel (csrc/conv1d_stream.hip) cover this descriptor -- a causal stride-1 convolution or the
     causal k = 2s transposed convolution, ``desc.t_in`` = columns per push?  Host logic only (no device needed);
