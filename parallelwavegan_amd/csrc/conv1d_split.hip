@@ -59,8 +59,11 @@ struct SplitArgs {
   int m, m_pad, cin_chunks, taps, dil, x_off, nq;
   int plane;         // bf16 elements per LDS plane
   long part_stride;  // bf16x8 elements per weight part image
-  int pre_act, post_act;
-  float pre_slope, post_slope, out_mul, out_div;
+  float pre_mul;      // pre-activation, one branch-free form for none / leaky / relu (pre_activate)
+  unsigned pre_mask;
+  int post_act;
+  float post_slope, out_mul, out_div;
+  int wide_out;  // y / add1 / add2 are 16-B aligned and t_out % 4 == 0: 16-B accesses in the epilogue
 };
 
 static int split_geometry(const pwg_conv1d_desc* d, SplitGeom* g) {
@@ -103,6 +106,14 @@ __device__ __forceinline__ void split3(float v, __bf16& hi, __bf16& mid, __bf16&
   lo = (__bf16)(r - (float)mid);
 }
 
+// The pre-activation without control flow: v > 0 ? v : bits(v * mul) & mask, with (mul, mask) = (1, ~0) for none,
+// (slope, ~0) for leaky and (0, 0) for relu.  For finite v these are the bits of apply_act(): v * 1 is v, v * slope is
+// the same rounded product, and the relu's negative side is +0.0 (the mask clears the sign of v * 0).
+__device__ __forceinline__ float pre_activate(float v, float mul, unsigned mask) {
+  const float n = __uint_as_float(__float_as_uint(v * mul) & mask);
+  return v > 0.f ? v : n;
+}
+
 // one thread per element of ONE part image [tap][ci / 8][m_pad][8], writing that element of all three parts; padding
 // rows / channels are zero
 __global__ __launch_bounds__(256) void pack_weight_split_kernel(const float* __restrict__ w, const float* __restrict__ scale,
@@ -130,11 +141,170 @@ __global__ __launch_bounds__(256) void pack_weight_split_kernel(const float* __r
   }
 }
 
+// Vector staging of one 32-channel chunk of the x window (xc: channel 0 of the chunk, c_left channels are left).
+// item = (group of 4 columns, channel octet): 8 loads of 16 B (one per channel, lanes walk t), then per column 8 channels
+// are activated, split and written as three 16-B LDS stores (one per plane).  CHECKED (edge tiles): a load whose group
+// of columns lies outside the row or whose channel is past the end gives zeros.
+template <int NT, bool CHECKED>
+__device__ __forceinline__ void stage_window_vec(const SplitArgs& a, const float* __restrict__ xc, int c_left, int base,
+                                                 int ngroups, __bf16* xs, int tid) {
+  constexpr int ITEMS = NT >= 128 ? NT / 128 : 1;
+  f32x4 st[ITEMS][8];
+#pragma unroll
+  for (int it = 0; it < ITEMS; ++it) {
+    const int idx = tid + it * 256, oct = idx & 3, grp = idx >> 2;
+    const int t = base + grp * 4;
+    const float* __restrict__ src = xc + (size_t)(oct * 8) * a.t_in + t;
+    if (!CHECKED) {
+      if (grp < ngroups) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) st[it][j] = *reinterpret_cast<const f32x4*>(src + (size_t)j * a.t_in);
+      }
+    } else {
+      const bool tin = grp < ngroups && t >= 0 && t < a.t_in;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (tin && oct * 8 + j < c_left) v = *reinterpret_cast<const f32x4*>(src + (size_t)j * a.t_in);
+        st[it][j] = v;
+      }
+    }
+  }
+#pragma unroll
+  for (int it = 0; it < ITEMS; ++it) {
+    const int idx = tid + it * 256, oct = idx & 3, grp = idx >> 2;
+    if (grp < ngroups) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        bf16x8 vh, vm, vl;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          __bf16 hi, mid, lo;
+          split3(pre_activate(st[it][j][e], a.pre_mul, a.pre_mask), hi, mid, lo);
+          vh[j] = hi;
+          vm[j] = mid;
+          vl[j] = lo;
+        }
+        __bf16* dst = xs + (grp * 4 + e) * ROW + oct * 8;
+        *reinterpret_cast<bf16x8*>(dst) = vh;
+        *reinterpret_cast<bf16x8*>(dst + a.plane) = vm;
+        *reinterpret_cast<bf16x8*>(dst + 2 * a.plane) = vl;
+        // one column at a time: the scheduler otherwise interleaves all 32 splits and spills the accumulators
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+  }
+}
+
+// The epilogue of one wave (fp32, the operation order of the fp32 kernel: acc + bias + add1 + add2, * out_mul, / out_div,
+// post-activation).  The kernel issues its MFMAs with the x fragment as the first operand, so the accumulators hold the
+// TRANSPOSED tile: a lane owns ONE output row per mi (row0 + mi * TILE) and, per accumulator, NREG / 4 "values" of 4
+// consecutive samples (value g of tile ni starts at col0 + ni * TILE + 4 * (64 / TILE) * g; col0 includes 4 * lane_group).
+// Every switch of the descriptor is wave-uniform and is taken once per batch of values, around straight-line code; the
+// loads of a batch are issued together and waited for once, and no store is waited for.
+// WIDE: 16-B accesses (y / add1 / add2 16-B aligned, t_out % 4 == 0: a value is inside a row or outside it), a batch is
+// the TN * NREG / 4 values of one mi.  Otherwise 4-B accesses and batches of one value (an address per sample: larger
+// batches would cost the kernel a wave per SIMD).  FULL: the tile has no padded row and no column past the end; otherwise
+// a load of a missing sample reads the last row / the last samples of the row instead, and its store is masked.
+// add1 / add2 may be y itself (same element, same lane), not a shifted view of it.
+template <int TILE, int TM, int TN, bool WIDE, bool FULL>
+__device__ __forceinline__ void split_epilogue(const SplitArgs& a, const typename Mfma<TILE>::acc_t (&acc)[TM][TN],
+                                               int row0, int col0, size_t out_base) {
+  constexpr int HL = 64 / TILE, NG = TILE * TILE / 64 / 4, NV = TN * NG;
+  constexpr int NB = WIDE ? NV : 1, BATCHES = TM * NV / NB;
+  const bool has_bias = a.bias != nullptr, has1 = a.add1 != nullptr, has2 = a.add2 != nullptr;
+#pragma unroll
+  for (int bi = 0; bi < BATCHES; ++bi) {
+    const int mi = bi * NB / NV;
+    const int m = row0 + mi * TILE, mc = FULL ? m : min(m, a.m - 1);
+    const size_t row = out_base + (size_t)mc * a.t_out;
+    int q[NB];  // first sample of value k
+#pragma unroll
+    for (int k = 0; k < NB; ++k) {
+      const int n = (bi * NB + k) % NV;
+      q[k] = col0 + (n / NG) * TILE + (n % NG) * (4 * HL);
+    }
+    auto load = [&](const float* __restrict__ src, f32x4 (&t)[NB]) {
+#pragma unroll
+      for (int k = 0; k < NB; ++k) {
+        if (WIDE) {
+          t[k] = *reinterpret_cast<const f32x4*>(src + row + (FULL ? q[k] : min(q[k], a.nq - 4)));
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) t[k][e] = src[row + min(q[k] + e, a.nq - 1)];
+        }
+      }
+    };
+    f32x4 t1[NB], t2[NB], v[NB];
+    float bias = 0.f;
+    if (has_bias) bias = a.bias[mc];
+    if (has1) load(a.add1, t1);
+    if (has2) load(a.add2, t2);
+#pragma unroll
+    for (int k = 0; k < NB; ++k) {
+      const int n = (bi * NB + k) % NV;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[k][e] = acc[mi][n / NG][(n % NG) * 4 + e];
+    }
+    if (has_bias) {
+#pragma unroll
+      for (int k = 0; k < NB; ++k) v[k] += bias;
+    }
+    if (has1) {
+#pragma unroll
+      for (int k = 0; k < NB; ++k) v[k] += t1[k];
+    }
+    if (has2) {
+#pragma unroll
+      for (int k = 0; k < NB; ++k) v[k] += t2[k];
+    }
+    if (a.out_mul != 1.0f) {
+#pragma unroll
+      for (int k = 0; k < NB; ++k) v[k] *= a.out_mul;
+    }
+    if (a.out_div != 1.0f) {
+#pragma unroll
+      for (int k = 0; k < NB; ++k) v[k] = v[k] / a.out_div;
+    }
+    if (a.post_act == PWG_ACT_LEAKY_RELU) {
+#pragma unroll
+      for (int k = 0; k < NB; ++k)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[k][e] = v[k][e] > 0.f ? v[k][e] : v[k][e] * a.post_slope;
+    } else if (a.post_act == PWG_ACT_RELU) {
+#pragma unroll
+      for (int k = 0; k < NB; ++k)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[k][e] = v[k][e] > 0.f ? v[k][e] : 0.f;
+    } else if (a.post_act == PWG_ACT_TANH) {
+#pragma unroll
+      for (int k = 0; k < NB; ++k) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[k][e] = tanhf(v[k][e]);
+        __builtin_amdgcn_sched_barrier(0);  // one value's tanhf at a time: interleaved, their temporaries cost a wave
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < NB; ++k) {
+      if (WIDE) {
+        if (FULL || (m < a.m && q[k] < a.nq)) *reinterpret_cast<f32x4*>(a.y + row + q[k]) = v[k];
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (m < a.m && q[k] + e < a.nq) a.y[row + q[k] + e] = v[k][e];
+      }
+    }
+  }
+}
+
 // Template parameters as in conv1d_bf16.hip.  TILE: MFMA shape (32: 32x32x16, 16: 16x16x32).  A wave computes (WM * 32)
 // rows x (WN * 32) columns; the 4 waves of a workgroup are arranged WAVES_M x (4 / WAVES_M).  VEC: the x window is staged
 // with 16-B loads along t (rows 16-B aligned, t_in % 4 == 0, window <= 2 * NT columns) and transposed in registers.
+// The second launch bound (waves per SIMD) is the occupancy that the main loop's registers allow: without it the register
+// allocator copies every accumulator out of the AGPRs at the head of the epilogue and the kernel loses a wave.
 template <int TILE, int WM, int WN, int WAVES_M, bool VEC>
-__global__ __launch_bounds__(256) void conv1d_split_mfma_kernel(SplitArgs a) {
+__global__ __launch_bounds__(256, WM * WN == 4 ? (TILE == 16 ? 3 : 2) : (WM * WN == 2 ? 3 : 4)) void
+conv1d_split_mfma_kernel(SplitArgs a) {
   constexpr int HL = 64 / TILE;
   constexpr int KSTEPS = KC / (8 * HL);
   constexpr int TM = WM * 32 / TILE, TN = WN * 32 / TILE;
@@ -167,60 +337,38 @@ __global__ __launch_bounds__(256) void conv1d_split_mfma_kernel(SplitArgs a) {
   for (int chunk = 0; chunk < a.cin_chunks; ++chunk) {
     if (chunk) __syncthreads();
     if (VEC) {
-      // item = (group of 4 columns, channel octet): 8 loads of 16 B (one per channel, lanes walk t), then per column 8
-      // channels are activated, split and written as three 16-B LDS stores (one per plane)
-      constexpr int ITEMS = NT >= 128 ? NT / 128 : 1;
-      const int ngroups = (wcols + 3) >> 2;
-      f32x4 st[ITEMS][8];
-#pragma unroll
-      for (int it = 0; it < ITEMS; ++it) {
-        const int idx = tid + it * 256, oct = idx & 3, grp = idx >> 2;
-        const int t = base + grp * 4;
-        const bool tin = grp < ngroups && t >= 0 && t < a.t_in;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const int ci = chunk * KC + oct * 8 + j;
-          f32x4 v = {0.f, 0.f, 0.f, 0.f};
-          if (tin && ci < a.c_in) v = *reinterpret_cast<const f32x4*>(xb + (size_t)ci * a.t_in + t);
-          st[it][j] = v;
-        }
-      }
-#pragma unroll
-      for (int it = 0; it < ITEMS; ++it) {
-        const int idx = tid + it * 256, oct = idx & 3, grp = idx >> 2;
-        if (grp < ngroups) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            bf16x8 vh, vm, vl;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-              __bf16 hi, mid, lo;
-              split3(apply_act(st[it][j][e], a.pre_act, a.pre_slope), hi, mid, lo);
-              vh[j] = hi;
-              vm[j] = mid;
-              vl[j] = lo;
-            }
-            __bf16* dst = xs + (grp * 4 + e) * ROW + oct * 8;
-            *reinterpret_cast<bf16x8*>(dst) = vh;
-            *reinterpret_cast<bf16x8*>(dst + a.plane) = vm;
-            *reinterpret_cast<bf16x8*>(dst + 2 * a.plane) = vl;
-          }
-        }
-      }
+      // an interior tile (decided once per workgroup and chunk: every staged column inside the row, a whole chunk of
+      // channels) takes unconditional loads; an edge tile checks every load
+      const int ngroups = (wcols + 3) >> 2, c_left = a.c_in - chunk * KC;
+      const float* __restrict__ xc = xb + (size_t)chunk * KC * a.t_in;
+      if (base >= 0 && base + 4 * ngroups <= a.t_in && c_left >= KC)
+        stage_window_vec<NT, false>(a, xc, c_left, base, ngroups, xs, tid);
+      else
+        stage_window_vec<NT, true>(a, xc, c_left, base, ngroups, xs, tid);
     } else {
       // wave `wave` stages channel octet `wave` of the chunk: lanes walk the columns (coalesced fp32 rows)
       const int c_base = chunk * KC + wave * 8;
+      const bool interior = base >= 0 && base + wcols <= a.t_in && c_base + 8 <= a.c_in;  // per wave and chunk
       for (int col = lane; col < wcols; col += 64) {
         const int t = base + col;
-        const bool tin = t >= 0 && t < a.t_in;
+        const float* __restrict__ src = xb + (size_t)c_base * a.t_in + t;
+        float f[8];
+        if (interior) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) f[j] = src[(size_t)j * a.t_in];
+        } else {
+          const bool tin = t >= 0 && t < a.t_in;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            f[j] = 0.f;
+            if (tin && c_base + j < a.c_in) f[j] = src[(size_t)j * a.t_in];
+          }
+        }
         bf16x8 vh, vm, vl;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-          const int ci = c_base + j;
-          float f = 0.f;
-          if (tin && ci < a.c_in) f = xb[(size_t)ci * a.t_in + t];
           __bf16 hi, mid, lo;
-          split3(apply_act(f, a.pre_act, a.pre_slope), hi, mid, lo);
+          split3(pre_activate(f[j], a.pre_mul, a.pre_mask), hi, mid, lo);
           vh[j] = hi;
           vm[j] = mid;
           vl[j] = lo;
@@ -250,7 +398,8 @@ __global__ __launch_bounds__(256) void conv1d_split_mfma_kernel(SplitArgs a) {
 #pragma unroll
           for (int p = 0; p < PARTS; ++p) bfr[p][ni] = *reinterpret_cast<const bf16x8*>(src + p * a.plane);
         }
-        // (weight part, input part), small terms first
+        // (weight part, input part), small terms first.  The x fragment goes first: the same products summed in the
+        // same order, the tile transposed (a lane gets 4 consecutive samples of a row, split_epilogue)
         constexpr int PA[6] = {2, 0, 1, 1, 0, 0};
         constexpr int PB[6] = {0, 2, 1, 0, 1, 0};
 #pragma unroll
@@ -258,36 +407,20 @@ __global__ __launch_bounds__(256) void conv1d_split_mfma_kernel(SplitArgs a) {
 #pragma unroll
           for (int mi = 0; mi < TM; ++mi)
 #pragma unroll
-            for (int ni = 0; ni < TN; ++ni) acc[mi][ni] = Mfma<TILE>::run(af[PA[p]][mi], bfr[PB[p]][ni], acc[mi][ni]);
+            for (int ni = 0; ni < TN; ++ni) acc[mi][ni] = Mfma<TILE>::run(bfr[PB[p]][ni], af[PA[p]][mi], acc[mi][ni]);
       }
     }
   }
 
-  // epilogue (fp32): C layout col = lane % TILE, row = mfma_acc_row (bf16_mfma.h)
-#pragma unroll
-  for (int mi = 0; mi < TM; ++mi) {
-#pragma unroll
-    for (int i = 0; i < NREG; ++i) {
-      const int m = mfma_acc_row<TILE>(m0 + wave_m * (WM * 32) + mi * TILE, i, h);
-      if (m >= a.m) continue;
-      const float bias = a.bias ? a.bias[m] : 0.f;
-      const size_t rowbase = ((size_t)b * a.c_out + m) * a.t_out;
-#pragma unroll
-      for (int ni = 0; ni < TN; ++ni) {
-        const int q = q0 + wave_n * (WN * 32) + ni * TILE + r;
-        if (q >= a.nq) continue;
-        const size_t idx = rowbase + q;
-        float v = acc[mi][ni][i];
-        if (a.bias) v += bias;
-        if (a.add1) v += a.add1[idx];
-        if (a.add2) v += a.add2[idx];
-        if (a.out_mul != 1.0f) v *= a.out_mul;
-        if (a.out_div != 1.0f) v = v / a.out_div;
-        v = apply_act(v, a.post_act, a.post_slope);
-        a.y[idx] = v;
-      }
-    }
-  }
+  const size_t out_base = (size_t)b * a.c_out * a.t_out;
+  const int row0 = m0 + wave_m * (WM * 32) + r, col0 = q0 + wave_n * (WN * 32) + 4 * h;
+  const bool full = m0 + MT <= a.m && q0 + NT <= a.nq;  // no padded row and no column past the end in this tile
+  if (!a.wide_out)
+    split_epilogue<TILE, TM, TN, false, false>(a, acc, row0, col0, out_base);
+  else if (full)
+    split_epilogue<TILE, TM, TN, true, true>(a, acc, row0, col0, out_base);
+  else
+    split_epilogue<TILE, TM, TN, true, false>(a, acc, row0, col0, out_base);
 }
 
 template <int TILE, bool VEC>
@@ -348,12 +481,14 @@ static int split_forward(const pwg_conv1d_desc* d, const float* x, const void* w
   a.nq = g.nq;
   a.plane = plane_rows(nt, halo) * ROW;
   a.part_stride = (long)g.taps * g.cin_chunks * (KC / 8) * g.m_pad;
-  a.pre_act = d->pre_act;
+  a.pre_mul = d->pre_act == PWG_ACT_LEAKY_RELU ? d->pre_slope : (d->pre_act == PWG_ACT_RELU ? 0.0f : 1.0f);
+  a.pre_mask = d->pre_act == PWG_ACT_RELU ? 0u : ~0u;
   a.post_act = d->post_act;
-  a.pre_slope = d->pre_slope;
   a.post_slope = d->post_slope;
   a.out_mul = d->out_mul;
   a.out_div = d->out_div;
+  a.wide_out = d->t_out % 4 == 0 && ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(add1) |
+                                      reinterpret_cast<uintptr_t>(add2)) & 15u) == 0;
   const size_t lds = lds_bytes(nt, halo);
   // vector staging: 16-B loads along t need aligned rows, and the window must fit the per-thread register items
   const bool vec = d->t_in % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15u) == 0 &&

@@ -1,0 +1,178 @@
+"""SHA-256 of the output bytes of the split-operand kernel (csrc/conv1d_split.hip) on a fixed case list, as JSON on
+stdout: what a change of the kernel that must not change a bit is compared by (run this file on both checkouts and
+compare the two objects).  GPU box only.  Every input is seeded on the CPU.
+The cases: those of tests/test_conv_split_gpu.py (default launch and 32x32x16); those of
+tests/test_conv_split_pipeline_gpu.py, whose shape / variant tables live here so that this file also runs on a checkout
+that has no such test (default launch, tile_mode 1 / 2, 32x32x16, and the launches with one operand 4 bytes off a 16-byte
+boundary); and the four admitted classes (128 / 256 channels, k = 7 / 11) at one utterance of 100 frames with dilations
+1 and 5, at tile_mode 0 / 1 / 2 and both MFMA shapes."""
+import hashlib
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+# name -> B, cin, cout, T, k, dil, pad_left (t_out = T: zeros on the right make up the rest of the receptive field)
+PIPELINE_SHAPES = {
+    # a single chunk; second row block with padded rows; first, interior and partial column tiles; window shift 3
+    "one_chunk": dict(B=1, cin=24, cout=136, T=300, k=3, dil=1, pad_left=1),
+    # whole chunks, 16-byte staging, shift 1, interior tiles
+    "two_chunks": dict(B=2, cin=64, cout=128, T=516, k=7, dil=1, pad_left=3),
+    # odd chunk count, 8-channel chunk tail, the widest window, padded rows
+    "three_chunks_tail": dict(B=2, cin=72, cout=72, T=640, k=11, dil=5, pad_left=25),
+    # no next tap; shift 0
+    "one_tap": dict(B=1, cin=96, cout=128, T=260, k=1, dil=1, pad_left=0),
+    # halo on the left only; 64-row tile
+    "causal": dict(B=1, cin=64, cout=64, T=512, k=3, dil=2, pad_left=4),
+    # 32-row tile; T % 4 != 0: 4-byte staging and the epilogue's 4-byte path; shift 2
+    "narrow": dict(B=2, cin=40, cout=24, T=515, k=5, dil=1, pad_left=2),
+    # T under one tile, one-channel chunk tail, row tail, per-item base pointers
+    "tiny": dict(B=3, cin=33, cout=33, T=37, k=3, dil=1, pad_left=1),
+}
+
+# every epilogue / activation switch alone, and all together
+PIPELINE_VARIANTS = {
+    "plain": dict(),
+    "bias": dict(bias=True),
+    "add1": dict(add1=True),
+    "add2": dict(add2=True),
+    "mul": dict(out_mul=0.5),
+    "div3": dict(out_div=3.0),
+    "post_lrelu": dict(post_act="leaky_relu", post_slope=0.1),
+    "post_relu": dict(post_act="relu"),
+    "post_tanh": dict(post_act="tanh"),
+    "pre_lrelu": dict(pre_act="leaky_relu", pre_slope=0.1),
+    "pre_relu": dict(pre_act="relu"),
+    "all": dict(bias=True, add1=True, add2=True, out_mul=0.5, out_div=3.0, pre_act="leaky_relu", pre_slope=0.1,
+                post_act="tanh"),
+}
+ALL_VARIANT_SHAPES = ("one_chunk", "three_chunks_tail")
+ALIGN_SHAPES = ("two_chunks", "three_chunks_tail", "one_tap")
+# (shape, variant, input kind); kinds as in tests/test_conv_split_gpu.py
+PIPELINE_CASES = ([(s, v, "randn") for s in ALL_VARIANT_SHAPES for v in PIPELINE_VARIANTS]
+                  + [(s, v, "randn") for s in PIPELINE_SHAPES if s not in ALL_VARIANT_SHAPES for v in ("plain", "all")]
+                  + [("three_chunks_tail", "plain", "wide"), ("three_chunks_tail", "plain", "cancel")])
+
+
+def pipeline_variant(name):
+    v = dict(bias=False, add1=False, add2=False, out_mul=1.0, out_div=1.0, pre_act=None, pre_slope=0.0, post_act=None,
+             post_slope=0.0)
+    v.update(PIPELINE_VARIANTS[name])
+    return v
+
+
+def pipeline_inputs(shape, kind):
+    """CPU float32 operands of a pipeline case (the kinds of tests/test_conv_split_gpu.py::_inputs)."""
+    s = PIPELINE_SHAPES[shape]
+    g = torch.Generator().manual_seed(sum(map(ord, shape + kind)) * 977 + s["T"])
+    x = torch.randn(s["B"], s["cin"], s["T"], generator=g)
+    w = torch.randn(s["cout"], s["cin"], s["k"], generator=g) / (s["cin"] * s["k"]) ** 0.5
+    if kind == "wide":
+        e = torch.linspace(-20, 20, s["cin"])[torch.randperm(s["cin"], generator=g)]
+        x = x * torch.exp2(e.round()).view(1, -1, 1)
+    if kind == "cancel":
+        u = torch.rand(s["B"], s["cin"] // 2, s["T"], generator=g) * 2 - 1
+        x[:, 1::2] = x[:, 0::2] * (1 + u / 16)
+        w[:, 1::2] = -w[:, 0::2]
+    bias = torch.randn(s["cout"], generator=g)
+    add1 = torch.randn(s["B"], s["cout"], s["T"], generator=g)
+    add2 = torch.randn(s["B"], s["cout"], s["T"], generator=g)
+    return dict(x=x, w=w, bias=bias, add1=add1, add2=add2)
+
+
+def pipeline_desc(shape, variant):
+    from parallelwavegan_amd import ops
+
+    s, v = PIPELINE_SHAPES[shape], pipeline_variant(variant)
+    return ops.make_conv_desc(s["B"], s["cin"], s["cout"], s["T"], s["T"], s["k"], 1, s["dil"], s["pad_left"],
+                              pre_act=v["pre_act"], pre_slope=v["pre_slope"], post_act=v["post_act"],
+                              post_slope=v["post_slope"], out_mul=v["out_mul"], out_div=v["out_div"])
+
+
+def off_by_4_bytes(t):
+    """A copy of t that starts 4 bytes after a 16-byte boundary."""
+    buf = torch.empty(t.numel() + 4, dtype=t.dtype, device=t.device)
+    assert buf.data_ptr() % 16 == 0
+    view = buf[1:1 + t.numel()].view(t.shape)
+    view.copy_(t)
+    return view
+
+
+def sha(t):
+    torch.cuda.synchronize()
+    return hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
+
+
+def hash_existing(out, dev):
+    from parallelwavegan_amd import ops
+    from tests import test_conv_split_gpu as ex
+
+    for shape, variant, kind in ex.CASES:
+        s, v, t = ex.SHAPES[shape], ex._variant(variant), ex._inputs(shape, kind)
+        pad = (s["k"] - 1) // 2 * s["dil"]
+        desc = ops.make_conv_desc(s["B"], s["cin"], s["cout"], s["T"], s["T"], s["k"], 1, s["dil"], pad,
+                                  pre_act=v["pre_act"], pre_slope=v["pre_slope"], post_act=v["post_act"],
+                                  out_div=v["out_div"])
+        x, ws = t["x"].to(dev), ops.pack_weight_split(desc, t["w"].to(dev))
+        bias, add1, add2 = (t[n].to(dev) if v[n] else None for n in ("bias", "add1", "add2"))
+        for shp in (16, 32):
+            y = ops.conv1d_forward_split(desc, x, ws, bias, add1, add2, mfma_shape=shp)
+            out[f"split_gpu/{shape}-{variant}-{kind}/mfma{shp}"] = sha(y)
+
+
+def hash_pipeline(out, dev):
+    from parallelwavegan_amd import ops
+
+    for shape, variant, kind in PIPELINE_CASES:
+        v, t = pipeline_variant(variant), pipeline_inputs(shape, kind)
+        desc = pipeline_desc(shape, variant)
+        x, ws = t["x"].to(dev), ops.pack_weight_split(desc, t["w"].to(dev))
+        bias, add1, add2 = (t[n].to(dev) if v[n] else None for n in ("bias", "add1", "add2"))
+        name = f"pipeline/{shape}-{variant}-{kind}"
+        for mode in (0, 1, 2):
+            out[f"{name}/tile{mode}"] = sha(ops.conv1d_forward_split(desc, x, ws, bias, add1, add2, tile_mode=mode))
+        out[f"{name}/mfma32"] = sha(ops.conv1d_forward_split(desc, x, ws, bias, add1, add2, mfma_shape=32))
+    for shape in ALIGN_SHAPES:
+        t = pipeline_inputs(shape, "randn")
+        desc = pipeline_desc(shape, "all")
+        ws = ops.pack_weight_split(desc, t["w"].to(dev))
+        for which in ("x", "add1", "add2", "out"):
+            arg = {n: t[n].to(dev) for n in ("x", "bias", "add1", "add2")}
+            y = None
+            if which == "out":
+                y = off_by_4_bytes(torch.zeros(t["add1"].shape, device=dev))
+            else:
+                arg[which] = off_by_4_bytes(arg[which])
+            y = ops.conv1d_forward_split(desc, arg["x"], ws, arg["bias"], arg["add1"], arg["add2"], out=y)
+            out[f"pipeline/{shape}-all-randn/{which}_off4"] = sha(y)
+
+
+def hash_admitted(out, dev):
+    from parallelwavegan_amd import ops
+
+    for ch, T in ((256, 800), (128, 6400)):  # HiFi-GAN V1 stages 1 and 2 at one utterance of 100 frames
+        for k in (7, 11):
+            for d in (1, 5):
+                g = torch.Generator().manual_seed(ch * 1000 + k * 10 + d)
+                w = torch.randn(ch, ch, k, generator=g) * 0.05
+                x, bias = torch.randn(1, ch, T, generator=g), torch.randn(ch, generator=g)
+                add1 = torch.randn(1, ch, T, generator=g)
+                desc = ops.make_conv_desc(1, ch, ch, T, T, k, dilation=d, pad_left=(k - 1) // 2 * d,
+                                          pre_act="leaky_relu", pre_slope=0.1)
+                ws = ops.pack_weight_split(desc, w.to(dev))
+                x, bias, add1 = x.to(dev), bias.to(dev), add1.to(dev)
+                for mode in (0, 1, 2):
+                    for shp in (16, 32):
+                        y = ops.conv1d_forward_split(desc, x, ws, bias, add1, tile_mode=mode, mfma_shape=shp)
+                        out[f"admitted/c{ch}_k{k}_d{d}_T{T}/tile{mode}/mfma{shp}"] = sha(y)
+
+
+if __name__ == "__main__":
+    dev = torch.device("cuda:0")
+    hashes = {}
+    hash_existing(hashes, dev)
+    hash_pipeline(hashes, dev)
+    hash_admitted(hashes, dev)
+    print(json.dumps({"hashes": len(hashes), "sha256": hashes}, indent=1, sort_keys=True))
