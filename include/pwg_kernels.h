@@ -319,6 +319,26 @@ int pwg_conv1d_plan(const pwg_conv1d_desc* d, int32_t has_addends, int32_t* out)
 int pwg_debug_conv_tile_of_workgroup(int32_t grid_x, int32_t grid_y, int32_t grid_z, int32_t row_blocks,
                                      int32_t ksplit, int32_t item_major, int32_t workgroup, int32_t* out);
 
+/* The sibling for the weight gradient (host only, no launch, no device needed; purely additive): what
+ * pwg_conv1d_backward_weight (weight_norm = 0) or pwg_conv1d_backward_weight_wn (weight_norm = 1) launches for `d`,
+ * decided by the functions the launcher itself calls, so it reflects this process's PWG_WG_* overrides and concurrency
+ * hint.  has_bias: db will be requested.  out[20]:
+ *   out[0]  kernel family: 0 = conv1d_wgrad_kernel (fp32 MFMA), 1 = grouped 16x16x4 kernel (gconv.hip), 2 = single-input-
+ *           channel kernel, 3 = 1 x 1 kernel (wgrad_k1.hip); out[4..17] are 0 unless out[0] == 0
+ *   out[1]  slab finisher: 0 = none (one slice: the kernel stores the gradients), 1 = reduce_slabs_kernel (family 1: its own
+ *           reduction kernel), 2 = reduce_slabs_wide_kernel, 3 = slab reduction + pwg_weight_norm_backward, 4 / 5 = the fused
+ *           weight-norm finisher, narrow / wide
+ *   out[2], out[3]  workspace floats the entry point asks for, low 31 bits and the bits above: what the workspace query
+ *           returns (the queries always reserve the fused bias row; with weight_norm = 0 and has_bias = 0 the row is left out)
+ *   out[4]  1 = 32 x 32 tile, out[5] accumulators (taps) per wave TG, out[6] taps per workgroup, out[7] tap groups (grid z),
+ *   out[8]  1 = per-tap windows, out[9] chunk columns TT, out[10] rows_half (> 0: row-aligned chunks), out[11] 1 = 16-byte
+ *           row staging, out[12] MODE (0..4), out[13] 1 = an activating instantiation, out[14] compile-time stride of MODE 3
+ *           (0 = run time), out[15] tiles (grid y), out[16] reduction slices (grid x), out[17] dynamic LDS bytes
+ *   out[18] slabs the finisher sums (families 0, 2, 3), out[19] floats between the X tile's rows in LDS (family 0).
+ * Refuses what the launcher refuses: bad groups, a pad mode, tensors above 4 GiB, a LeakyReLU slope outside [0, 1],
+ * a transposed layer with dilation and stride, more than 160 KiB of LDS, a weight-norm row beyond the LDS row buffer. */
+int pwg_conv1d_backward_weight_plan(const pwg_conv1d_desc* d, int32_t weight_norm, int32_t has_bias, int32_t* out);
+
 /* ------------------------------------------------------------------------- */
 /* One HiFi-GAN MRF residual unit as ONE launch (inference; channels 32 / 64)  */
 /*                                                                            */

@@ -169,6 +169,7 @@ SIGNATURES = {
     "pwg_conv1d_num_tile_configs": (ctypes.c_int, []),
     "pwg_conv1d_forward_cfg": (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "pwg_conv1d_plan": (ctypes.c_int, [ctypes.POINTER(ConvDesc), _i32, ctypes.POINTER(_i32)]),
+    "pwg_conv1d_backward_weight_plan": (ctypes.c_int, [ctypes.POINTER(ConvDesc), _i32, _i32, ctypes.POINTER(_i32)]),
     "pwg_debug_conv_tile_of_workgroup": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, ctypes.POINTER(_i32)]),
     "pwg_resunit_supported": (ctypes.c_int, [ctypes.POINTER(ResUnitDesc)]),
     "pwg_resunit_profitable": (ctypes.c_int, [ctypes.POINTER(ResUnitDesc)]),

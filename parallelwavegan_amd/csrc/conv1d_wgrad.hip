@@ -1015,23 +1015,77 @@ static WgPlan wgrad_plan(int co_g, int ci_g, int groups, int k, int stride, int 
   return p;
 }
 
+// ---- host dispatch, decided once: the launchers below and pwg_conv1d_backward_weight_plan read the same functions ----
+// How the reduction slabs become the gradients (the values are the ABI of pwg_conv1d_backward_weight_plan, out[1]).
+enum WgFinisher {
+  WG_FIN_DIRECT = 0,         // one slice, no weight norm: the kernel stores the gradients itself (torch layout)
+  WG_FIN_SLABS = 1,          // reduce_slabs_kernel
+  WG_FIN_SLABS_WIDE = 2,     // reduce_slabs_wide_kernel
+  WG_FIN_WN_TWO_KERNEL = 3,  // reduce_slabs_wide_kernel into a spare slab + pwg_weight_norm_backward
+  WG_FIN_WN_FUSED = 4,       // reduce_slabs_wn_kernel<false>
+  WG_FIN_WN_FUSED_WIDE = 5,  // reduce_slabs_wn_kernel<true>
+};
+
+// fused weight-norm finisher: one workgroup per weight row, so it needs many rows or few slabs to fill the chip; layers
+// with few rows cut into many slabs (C <= 128 generator stages) keep the wide slab reduction (one workgroup
+// per 32 elements) followed by the row-wise weight-norm backward, into a spare slab of the workspace
+// (round 6, measured twice and NOT kept: the fused finisher also for short rows cut into many slabs -- MelGAN's 48 / 96 / 192-
+// channel stacks, one workgroup per row walking 128 - 512 slabs.  With dependent load + add rounds: 62 - 121 us per layer
+// instead of 13 - 16 us for the two launches; with eight loads in flight (as the kernel has them now): 8.6 - 25 us, better at
+// 128 / 192 rows, worse at 32 - 64, and the captured steps lose: C3 45.9 -> 46.4 ms, C5 41.9 -> 42.5 ms, C4 25.8 -> 25.9 ms,
+// profiles/r06_wgrad_k1.txt)
+static WgFinisher wgrad_finisher(int splits, bool wn, int n0, int inner) {
+  if (wn) {
+    if (!(splits < 16 || n0 >= 512)) return WG_FIN_WN_TWO_KERNEL;
+    const bool wide = splits >= 16 && (size_t)9 * inner * sizeof(float) <= 64 * 1024;  // (>= 512 rows of <= 1820 floats)
+    return wide ? WG_FIN_WN_FUSED_WIDE : WG_FIN_WN_FUSED;
+  }
+  if (splits <= 1) return WG_FIN_DIRECT;
+  return splits >= 16 ? WG_FIN_SLABS_WIDE : WG_FIN_SLABS;
+}
+
+// Which instantiation of conv1d_wgrad_kernel a plan runs: MODE, whether the operand activation is compiled in (MODE 1, or
+// ACT23 of modes 2 - 4) and the compile-time stride of MODE 3 (0 = run time).  `act`: the layer has a pre-activation.
+struct WgVariant {
+  int mode;
+  bool act;
+  int stride_ct;
+};
+
+static int wgrad_dbg() {
+  static const int dbg = getenv("PWG_WG_DBG") ? atoi(getenv("PWG_WG_DBG")) : 0;
+  return dbg;
+}
+
+static WgVariant wgrad_variant(const WgPlan& p, int width, int stride, bool act) {
+  static const bool fast23 = !(getenv("PWG_WG_FAST23") && atoi(getenv("PWG_WG_FAST23")) == 0);  // (0: the round-5 loops, A/B)
+  WgVariant v{0, act, 0};
+  if (p.rows_half > 0) {  // row-aligned (k,1) chunks
+    v.mode = 4;
+  } else if (width != 1) {  // per-tap windows need width == 1 and stride == 1 (wgrad_plan)
+    v.mode = 2;
+    v.act = act || !fast23;
+  } else if (stride != 1) {
+    v.mode = 3;
+    v.act = act || !fast23;
+    // the strides of the recipes' layers: scale discriminators 4 (2 in some recipes), upsamplers 8 / 5 / 3; activated
+    // (ConvTranspose1d of the generators: activated input): 8 / 4 / 2
+    if (fast23 && (stride == 2 || stride == 4 || stride == 8 || (stride == 3 && !act))) v.stride_ct = stride;
+  } else {
+    v.mode = act ? 1 : 0;
+  }
+  return v;
+}
+
 // Sum `splits` tap-major slabs (+ fused bias row) of a layer with `n0` rows, `ci_g` input channels per group and `k`
 // taps into the torch-layout gradients; with `wn`, through the weight-norm backward.  (Shared by the MFMA kernel's
 // launcher and the single-input-channel path.)
 static int finish_wgrad_slabs(float* workspace, int splits, long slab_elems, long slab_stride, int n0, int ci_g, int k,
                               float* dw_out, float* db_out, const WnFinish* wn, hipStream_t stream) {
-  // fused finisher: one workgroup per weight row, so it needs many rows or few slabs to fill the chip; layers
-  // with few rows cut into many slabs (C <= 128 generator stages) keep the wide slab reduction (one workgroup
-  // per 32 elements) followed by the row-wise weight-norm backward, into a spare slab of the workspace
   const long plane = (long)n0 * ci_g;  // elements per tap of a tap-major slab
   const int inner = ci_g * k;
-  // (round 6, measured twice and NOT kept: the fused finisher also for short rows cut into many slabs -- MelGAN's 48 / 96 / 192-
-  // channel stacks, one workgroup per row walking 128 - 512 slabs.  With dependent load + add rounds: 62 - 121 us per layer
-  // instead of 13 - 16 us for the two launches; with eight loads in flight (as the kernel has them now): 8.6 - 25 us, better at
-  // 128 / 192 rows, worse at 32 - 64, and the captured steps lose: C3 45.9 -> 46.4 ms, C5 41.9 -> 42.5 ms, C4 25.8 -> 25.9 ms,
-  // profiles/r06_wgrad_k1.txt)
-  const bool wn_fused = wn != nullptr && (splits < 16 || n0 >= 512);
-  if (wn != nullptr && !wn_fused) {
+  const WgFinisher fin = wgrad_finisher(splits, wn != nullptr, n0, inner);
+  if (fin == WG_FIN_WN_TWO_KERNEL) {
     float* dw_tmp = workspace + (size_t)splits * slab_stride;
     {
       ProfScope prof(stream, "reduce_slabs_kernel", 0, 4.0 * slab_stride * (splits + 1));
@@ -1041,11 +1095,10 @@ static int finish_wgrad_slabs(float* workspace, int splits, long slab_elems, lon
     }
     return pwg_weight_norm_backward(dw_tmp, wn->v, wn->g, wn->dv, wn->dg, n0, inner, stream);
   }
-  if (wn != nullptr) {
+  if (fin == WG_FIN_WN_FUSED || fin == WG_FIN_WN_FUSED_WIDE) {
     const int nbias = db_out ? n0 : 0;
     ProfScope prof(stream, "reduce_slabs_wn_kernel", 0, 4.0 * (slab_stride * (double)splits + 3.0 * slab_elems));
-    const bool wide = splits >= 16 && (size_t)9 * inner * sizeof(float) <= 64 * 1024;  // (>= 512 rows of <= 1820 floats)
-    if (wide)
+    if (fin == WG_FIN_WN_FUSED_WIDE)
       hipLaunchKernelGGL(reduce_slabs_wn_kernel<true>, dim3(n0 + ceil_div(nbias, 256)), dim3(256),
                          (size_t)9 * inner * sizeof(float), stream, (const float*)workspace, slab_stride, splits,
                          slab_elems, wn->v, wn->g, wn->dv, wn->dg, db_out, n0, inner, nbias, ci_g, k);
@@ -1056,9 +1109,9 @@ static int finish_wgrad_slabs(float* workspace, int splits, long slab_elems, lon
     PWG_CHECK_LAUNCH("reduce_slabs_wn");
     return PWG_OK;
   }
-  if (splits > 1) {
+  if (fin != WG_FIN_DIRECT) {
     ProfScope prof(stream, "reduce_slabs_kernel", 0, 4.0 * slab_stride * (splits + 1));
-    if (splits >= 16) {
+    if (fin == WG_FIN_SLABS_WIDE) {
       hipLaunchKernelGGL(reduce_slabs_wide_kernel, dim3((unsigned)((slab_stride + 31) / 32)), dim3(256), 0, stream,
                          workspace, dw_out, db_out, slab_elems, slab_stride, splits, plane, k);
     } else {
@@ -1092,7 +1145,7 @@ static int launch_wgrad_mode(WgArgs a, const WgPlan& p, float* dw_out, float* wo
   float* db_out = a.db;  // non-null: the bias gradient rides along (row sums of the G tiles)
   a.slab_stride = a.slab_elems + (db_out ? (long)a.co_g * a.groups : 0);
   a.tap_major = 0;
-  if (p.splits == 1 && wn == nullptr) {
+  if (wgrad_finisher(p.splits, wn != nullptr, a.co_g * a.groups, a.ci_g * a.k) == WG_FIN_DIRECT) {
     a.dw = dw_out;  // single slice: write the gradients directly (torch layout)
   } else {
     a.tap_major = 1;
@@ -1118,51 +1171,50 @@ static int launch_wgrad_mode(WgArgs a, const WgPlan& p, float* dw_out, float* wo
 }
 
 template <int TG, bool SMALL, int TT>
-static int launch_wgrad(WgArgs a, const WgPlan& p, float* dw_out, float* workspace, size_t ws_floats,
+static int launch_wgrad(WgArgs a, const WgPlan& p, const WgVariant& v, float* dw_out, float* workspace, size_t ws_floats,
                         hipStream_t stream, double flops, double bytes, const WnFinish* wn) {
-  const bool act = (a.slope_g != 1.f || a.slope_x != 1.f) && !(a.dbg & 8);
 #define WG_GO(WINV, MODEV) \
   return launch_wgrad_mode<TG, SMALL, TT, WINV, MODEV>(a, p, dw_out, workspace, ws_floats, stream, flops, bytes, wn)
 #define WG_GO23(MODEV, ACTV, SV) \
   return launch_wgrad_mode<TG, SMALL, TT, false, MODEV, ACTV, SV>(a, p, dw_out, workspace, ws_floats, stream, flops, bytes, wn)
-  static const bool fast23 = !(getenv("PWG_WG_FAST23") && atoi(getenv("PWG_WG_FAST23")) == 0);  // (0: the round-5 loops, A/B)
-  if (a.width != 1) {  // per-tap windows need width == 1 and stride == 1 (wgrad_plan)
-    if (act || !fast23) WG_GO23(2, true, 0);
-    WG_GO23(2, false, 0);
-  }
-  if (a.stride != 1) {
-    if (fast23 && !act) {  // the strides of the recipes' layers: scale discriminators 4 (2 in some recipes), upsamplers 8 / 5 / 3
-      switch (a.stride) {
-        case 2: WG_GO23(3, false, 2);
-        case 3: WG_GO23(3, false, 3);
-        case 4: WG_GO23(3, false, 4);
-        case 8: WG_GO23(3, false, 8);
-        default: WG_GO23(3, false, 0);
+  switch (v.mode) {  // (wgrad_variant chose; only the instantiations it can name exist)
+    case 2:
+      if (v.act) WG_GO23(2, true, 0);
+      WG_GO23(2, false, 0);
+    case 3:
+      if (!v.act) {
+        switch (v.stride_ct) {
+          case 2: WG_GO23(3, false, 2);
+          case 3: WG_GO23(3, false, 3);
+          case 4: WG_GO23(3, false, 4);
+          case 8: WG_GO23(3, false, 8);
+          default: WG_GO23(3, false, 0);
+        }
       }
-    }
-    if (fast23 && a.stride == 8) WG_GO23(3, true, 8);  // (ConvTranspose1d of the generators: activated input)
-    if (fast23 && a.stride == 4) WG_GO23(3, true, 4);
-    if (fast23 && a.stride == 2) WG_GO23(3, true, 2);
-    WG_GO23(3, true, 0);
+      switch (v.stride_ct) {
+        case 8: WG_GO23(3, true, 8);
+        case 4: WG_GO23(3, true, 4);
+        case 2: WG_GO23(3, true, 2);
+        default: WG_GO23(3, true, 0);
+      }
+    case 1:
+      if (p.win) WG_GO(true, 1);
+      WG_GO(false, 1);
+    default:
+      if (p.win) WG_GO(true, 0);
+      WG_GO(false, 0);
   }
-  if (p.win) {
-    if (act) WG_GO(true, 1);
-    WG_GO(true, 0);
-  }
-  if (act) WG_GO(false, 1);
-  WG_GO(false, 0);
 #undef WG_GO
 #undef WG_GO23
 }
 
 // MODE 4 only (row-aligned (k,1) chunks, TT = 64): kept apart so that the 64 x 64 tile gets no other TT = 64 instantiation
 template <int TG, bool SMALL>
-static int launch_wgrad_rows(WgArgs a, const WgPlan& p, float* dw_out, float* workspace, size_t ws_floats,
+static int launch_wgrad_rows(WgArgs a, const WgPlan& p, const WgVariant& v, float* dw_out, float* workspace, size_t ws_floats,
                              hipStream_t stream, double flops, double bytes, const WnFinish* wn) {
-  const bool act = (a.slope_g != 1.f || a.slope_x != 1.f) && !(a.dbg & 8);
   a.rows_half = p.rows_half;
   a.rows_x4 = p.rows_x4 ? 1 : 0;
-  if (act) return launch_wgrad_mode<TG, SMALL, 64, false, 4, true, 0>(a, p, dw_out, workspace, ws_floats, stream, flops, bytes, wn);
+  if (v.act) return launch_wgrad_mode<TG, SMALL, 64, false, 4, true, 0>(a, p, dw_out, workspace, ws_floats, stream, flops, bytes, wn);
   return launch_wgrad_mode<TG, SMALL, 64, false, 4, false, 0>(a, p, dw_out, workspace, ws_floats, stream, flops, bytes, wn);
 }
 
@@ -1179,6 +1231,26 @@ static bool small_cin_wgrad_applicable(const pwg_conv1d_desc* d) {
 }
 static long small_cin_wgrad_slabs(const pwg_conv1d_desc* d) { return (long)d->batch * ceil_div(d->t_out, SIW_TILE); }
 
+// The kernel family of a (flattened) descriptor, in the launcher's order of preference (the values are the ABI of
+// pwg_conv1d_backward_weight_plan, out[0]).
+enum WgPath { WG_PATH_MFMA = 0, WG_PATH_GCONV = 1, WG_PATH_SMALL_CIN = 2, WG_PATH_K1 = 3 };
+static WgPath wgrad_path(const pwg_conv1d_desc* d) {
+  if (gconv_wgrad_applicable(d)) return WG_PATH_GCONV;
+  if (small_cin_wgrad_applicable(d)) return WG_PATH_SMALL_CIN;
+  if (k1_wgrad_applicable(d)) return WG_PATH_K1;
+  return WG_PATH_MFMA;
+}
+
+// branch-free operand activation max(v, slope * v): 1 = none, 0 = ReLU
+static float wgrad_slope(const pwg_conv1d_desc* d) {
+  return d->pre_act == PWG_ACT_LEAKY_RELU ? d->pre_slope : (d->pre_act == PWG_ACT_RELU ? 0.f : 1.f);
+}
+static bool wgrad_act(float slope) { return slope != 1.f && !(wgrad_dbg() & 8); }
+
+// (the weight-norm finishing kernel holds one weight row in dynamic LDS next to 32 B of static LDS: stay below the 64 KiB
+// default limit with room to spare; functional.py routes longer rows to the two-kernel finish)
+static bool wn_row_fits(int ci_g, int k) { return (size_t)ci_g * k * sizeof(float) + 256 <= 64 * 1024; }
+
 static void wgrad_roles(const pwg_conv1d_desc* d, int* co_g, int* ci_g, int* n_cols) {
   if (!d->transposed) {
     *co_g = d->c_out / d->groups;
@@ -1191,18 +1263,58 @@ static void wgrad_roles(const pwg_conv1d_desc* d, int* co_g, int* ci_g, int* n_c
   }
 }
 
-extern "C" size_t pwg_conv1d_backward_weight_workspace_floats(const pwg_conv1d_desc* d_in) {
-  if (!d_in || d_in->groups <= 0 || d_in->c_in % d_in->groups || d_in->c_out % d_in->groups) return 0;
-  const pwg_conv1d_desc flat = flatten_width(*d_in);
-  const pwg_conv1d_desc* d = &flat;
+// What every entry point below refuses, in the launcher's words (`d` flattened).
+static int wgrad_check_desc(const pwg_conv1d_desc* d) {
+  PWG_REQUIRE(d->c_in % d->groups == 0 && d->c_out % d->groups == 0 && d->groups > 0, PWG_ERR_BAD_SHAPE,
+              "conv1d_backward_weight: bad groups");
+  PWG_REQUIRE(d->pad_mode == PWG_PAD_ZERO, PWG_ERR_UNSUPPORTED,
+              "conv1d_backward_weight: only zero padding (pad reflect/replicate inputs explicitly)");
+  const long y_elems = (long)d->batch * d->c_out * d->t_out * d->width;
+  const long x_elems = (long)d->batch * d->c_in * d->t_in * d->width;
+  PWG_REQUIRE(y_elems * 4 < 0xFFFFFFF0L && x_elems * 4 < 0xFFFFFFF0L, PWG_ERR_UNSUPPORTED,
+              "conv1d_backward_weight: tensors above 4 GiB need batch splitting");
+  return PWG_OK;
+}
+// (every path but gconv.hip's, which takes its own activation arguments)
+static int wgrad_check_slope(float slope) {
+  PWG_REQUIRE(slope >= 0.f && slope <= 1.f, PWG_ERR_UNSUPPORTED,
+              "conv1d_backward_weight: LeakyReLU slope %g outside [0, 1] (the operand activation is max(v, slope*v))",
+              (double)slope);
+  return PWG_OK;
+}
+static int wgrad_check_transposed(const pwg_conv1d_desc* d) {
+  PWG_REQUIRE(!d->transposed || d->dilation == 1 || d->stride == 1, PWG_ERR_UNSUPPORTED,
+              "conv_transpose1d wgrad: dilation with stride");
+  return PWG_OK;
+}
+
+// Workspace floats an entry point asks for (`d` flattened): the slabs of the path's reduction slices, each dW plus --
+// with `bias_row` -- the fused bias row; with `wn`, one spare slab for the summed gradient of the two-kernel finish.
+// The two public queries always reserve the bias row; pwg_conv1d_backward_weight_plan reports either.
+static size_t wgrad_workspace(const pwg_conv1d_desc* d, bool wn, bool bias_row) {
+  const size_t b = bias_row ? 1 : 0, spare = wn ? 1 : 0;
+  // (the single-input-channel and 1 x 1 kernels always write slabs -- both cut every layer they accept into at least two
+  // -- so only the MFMA kernel below has a slab-free single slice)
+  switch (wgrad_path(d)) {
+    case WG_PATH_GCONV: return gconv_wgrad_workspace_floats(d);
+    case WG_PATH_SMALL_CIN: return (size_t)(small_cin_wgrad_slabs(d) + spare) * ((size_t)d->c_out * (d->kernel + b));
+    case WG_PATH_K1: return (size_t)(k1_wgrad_slabs(d) + spare) * ((size_t)d->c_out * (d->c_in + b));
+    default: break;
+  }
   int co_g, ci_g, n_cols;
   wgrad_roles(d, &co_g, &ci_g, &n_cols);
   const WgPlan p = wgrad_plan(co_g, ci_g, d->groups, d->kernel, d->stride, d->dilation, d->width, n_cols, d->batch);
-  if (gconv_wgrad_applicable(d)) return gconv_wgrad_workspace_floats(d);
-  if (small_cin_wgrad_applicable(d)) return (size_t)small_cin_wgrad_slabs(d) * ((size_t)d->c_out * (d->kernel + 1));
-  if (k1_wgrad_applicable(d)) return (size_t)k1_wgrad_slabs(d) * ((size_t)d->c_out * (d->c_in + 1));
-  // one slab per reduction slice: dW plus the fused bias row
-  return p.splits > 1 ? (size_t)p.splits * ((size_t)co_g * d->groups * ci_g * d->kernel + (size_t)co_g * d->groups) : 0;
+  const size_t n0 = (size_t)co_g * d->groups;
+  const size_t slab = n0 * ci_g * d->kernel + b * n0;
+  if (wn) return (size_t)(p.splits + 1) * slab;
+  // one slab per reduction slice; a single slice stores the gradients itself
+  return wgrad_finisher(p.splits, false, (int)n0, ci_g * d->kernel) == WG_FIN_DIRECT ? 0 : (size_t)p.splits * slab;
+}
+
+extern "C" size_t pwg_conv1d_backward_weight_workspace_floats(const pwg_conv1d_desc* d_in) {
+  if (!d_in || d_in->groups <= 0 || d_in->c_in % d_in->groups || d_in->c_out % d_in->groups) return 0;
+  const pwg_conv1d_desc flat = flatten_width(*d_in);
+  return wgrad_workspace(&flat, false, true);
 }
 
 // wn != nullptr: finish the slabs with the fused weight-norm backward (pwg_conv1d_backward_weight_wn)
@@ -1211,15 +1323,10 @@ static int backward_weight_impl(const pwg_conv1d_desc* d_in, const float* x, con
   PWG_REQUIRE(d_in && x && dy, PWG_ERR_NULL, "conv1d_backward_weight: NULL pointer");
   const pwg_conv1d_desc flat = flatten_width(*d_in);
   const pwg_conv1d_desc* d = &flat;
-  PWG_REQUIRE(d->c_in % d->groups == 0 && d->c_out % d->groups == 0 && d->groups > 0, PWG_ERR_BAD_SHAPE,
-              "conv1d_backward_weight: bad groups");
-  PWG_REQUIRE(d->pad_mode == PWG_PAD_ZERO, PWG_ERR_UNSUPPORTED,
-              "conv1d_backward_weight: only zero padding (pad reflect/replicate inputs explicitly)");
+  if (int rc = wgrad_check_desc(d)) return rc;
   hipStream_t stream = (hipStream_t)stream_;
   const long y_elems = (long)d->batch * d->c_out * d->t_out * d->width;
   const long x_elems = (long)d->batch * d->c_in * d->t_in * d->width;
-  PWG_REQUIRE(y_elems * 4 < 0xFFFFFFF0L && x_elems * 4 < 0xFFFFFFF0L, PWG_ERR_UNSUPPORTED,
-              "conv1d_backward_weight: tensors above 4 GiB need batch splitting");
   // The bias gradient (row sums of dy) is fused into the weight-gradient kernel whenever dy plays the
   // G role there (plain convolutions); ConvTranspose1d and bias-only calls use the separate kernel.
   const bool fuse_bias = db && dw && !d->transposed;
@@ -1230,7 +1337,8 @@ static int backward_weight_impl(const pwg_conv1d_desc* d_in, const float* x, con
     PWG_CHECK_LAUNCH("bias_grad");
   }
   if (!dw) return PWG_OK;
-  if (gconv_wgrad_applicable(d)) {
+  const WgPath path = wgrad_path(d);
+  if (path == WG_PATH_GCONV) {
     // few channels per group: 16 x 16 x 4 MFMA kernel of gconv.hip (bias gradient fused when dy is the G operand)
     float* db_fused = fuse_bias ? db : nullptr;
     if (wn == nullptr) return gconv_backward_weight(d, x, dy, dw, db_fused, workspace, workspace_floats, stream);
@@ -1244,11 +1352,9 @@ static int backward_weight_impl(const pwg_conv1d_desc* d_in, const float* x, con
     return pwg_weight_norm_backward(dw_tmp, wn->v, wn->g, wn->dv, wn->dg, d->c_out, (int)(w_elems / d->c_out), stream);
   }
   WgArgs a;
-  const float slope = d->pre_act == PWG_ACT_LEAKY_RELU ? d->pre_slope : (d->pre_act == PWG_ACT_RELU ? 0.f : 1.f);
-  PWG_REQUIRE(slope >= 0.f && slope <= 1.f, PWG_ERR_UNSUPPORTED,
-              "conv1d_backward_weight: LeakyReLU slope %g outside [0, 1] (the operand activation is max(v, slope*v))",
-              (double)slope);
-  if (small_cin_wgrad_applicable(d)) {
+  const float slope = wgrad_slope(d);
+  if (int rc = wgrad_check_slope(slope)) return rc;
+  if (path == WG_PATH_SMALL_CIN) {
     const long nslabs = small_cin_wgrad_slabs(d);
     const long slab_elems = (long)d->c_out * d->kernel, slab_stride = slab_elems + (db ? d->c_out : 0);
     const size_t need = (size_t)(nslabs + (wn ? 1 : 0)) * slab_stride;
@@ -1266,7 +1372,7 @@ static int backward_weight_impl(const pwg_conv1d_desc* d_in, const float* x, con
     }
     return finish_wgrad_slabs(workspace, (int)nslabs, slab_elems, slab_stride, d->c_out, 1, d->kernel, dw, db, wn, stream);
   }
-  if (k1_wgrad_applicable(d)) {
+  if (path == WG_PATH_K1) {
     // 1 x 1 layers with few channels: HBM-bound kernel of wgrad_k1.hip, one slab per workgroup
     const int nslabs = k1_wgrad_slabs(d);
     const long slab_elems = (long)d->c_out * d->c_in, slab_stride = slab_elems + (db ? d->c_out : 0);
@@ -1290,7 +1396,7 @@ static int backward_weight_impl(const pwg_conv1d_desc* d_in, const float* x, con
     a.x_bytes = (unsigned)(x_elems * 4);
   } else {
     // ConvTranspose1d: dW[ci][co][k] = sum x[ci][q] * dy[co][q*s - p + k]: same kernel, roles swapped
-    PWG_REQUIRE(d->dilation == 1 || d->stride == 1, PWG_ERR_UNSUPPORTED, "conv_transpose1d wgrad: dilation with stride");
+    if (int rc = wgrad_check_transposed(d)) return rc;
     a.g = x;
     a.x = dy;
     a.co_g = d->c_in / d->groups;
@@ -1302,8 +1408,7 @@ static int backward_weight_impl(const pwg_conv1d_desc* d_in, const float* x, con
     a.g_bytes = (unsigned)(x_elems * 4);
     a.x_bytes = (unsigned)(y_elems * 4);
   }
-  static const int dbg = getenv("PWG_WG_DBG") ? atoi(getenv("PWG_WG_DBG")) : 0;
-  a.dbg = dbg;
+  a.dbg = wgrad_dbg();
   a.dw = nullptr;
   a.db = fuse_bias ? db : nullptr;
   a.groups = d->groups;
@@ -1317,16 +1422,17 @@ static int backward_weight_impl(const pwg_conv1d_desc* d_in, const float* x, con
   const double bytes = 4.0 * ((double)x_elems + (double)y_elems + (double)a.co_g * a.ci_g * d->groups * d->kernel);
   const WgPlan p = wgrad_plan(a.co_g, a.ci_g, d->groups, d->kernel, d->stride, d->dilation, d->width, a.n_cols,
                               d->batch);
+  const WgVariant v = wgrad_variant(p, d->width, d->stride, wgrad_act(slope));
 #define WG_CASE(TGV, SM)                                                                             \
   switch (p.tt) {                                                                                    \
-    case 128: return launch_wgrad<TGV, SM, 128>(a, p, dw, workspace, workspace_floats, stream, flops, bytes, wn); \
-    case 64: return launch_wgrad<TGV, SM, 64>(a, p, dw, workspace, workspace_floats, stream, flops, bytes, wn);   \
-    default: return launch_wgrad<TGV, SM, 32>(a, p, dw, workspace, workspace_floats, stream, flops, bytes, wn);   \
+    case 128: return launch_wgrad<TGV, SM, 128>(a, p, v, dw, workspace, workspace_floats, stream, flops, bytes, wn); \
+    case 64: return launch_wgrad<TGV, SM, 64>(a, p, v, dw, workspace, workspace_floats, stream, flops, bytes, wn);   \
+    default: return launch_wgrad<TGV, SM, 32>(a, p, v, dw, workspace, workspace_floats, stream, flops, bytes, wn);   \
   }
   a.rows_half = 0;
   a.rows_x4 = 0;
   if (p.rows_half > 0) {
-#define WG_ROWS(TGV, SM) return launch_wgrad_rows<TGV, SM>(a, p, dw, workspace, workspace_floats, stream, flops, bytes, wn)
+#define WG_ROWS(TGV, SM) return launch_wgrad_rows<TGV, SM>(a, p, v, dw, workspace, workspace_floats, stream, flops, bytes, wn)
     if (p.small) {
       switch (p.tg) {
         case 1: WG_ROWS(1, true);
@@ -1355,7 +1461,7 @@ static int backward_weight_impl(const pwg_conv1d_desc* d_in, const float* x, con
     }
   }
 #undef WG_CASE
-#define WG_CASE(TGV) return launch_wgrad<TGV, false, 32>(a, p, dw, workspace, workspace_floats, stream, flops, bytes, wn)
+#define WG_CASE(TGV) return launch_wgrad<TGV, false, 32>(a, p, v, dw, workspace, workspace_floats, stream, flops, bytes, wn)
   switch (p.tg) {  // 64x64 tiles always run 32-column chunks (LDS)
     case 1: WG_CASE(1);
     case 2: WG_CASE(2);
@@ -1379,15 +1485,7 @@ extern "C" int pwg_conv1d_backward_weight(const pwg_conv1d_desc* d, const float*
 extern "C" size_t pwg_conv1d_backward_weight_wn_workspace_floats(const pwg_conv1d_desc* d_in) {
   if (!d_in || d_in->groups <= 0 || d_in->c_in % d_in->groups || d_in->c_out % d_in->groups) return 0;
   const pwg_conv1d_desc flat = flatten_width(*d_in);
-  const pwg_conv1d_desc* d = &flat;
-  int co_g, ci_g, n_cols;
-  wgrad_roles(d, &co_g, &ci_g, &n_cols);
-  const WgPlan p = wgrad_plan(co_g, ci_g, d->groups, d->kernel, d->stride, d->dilation, d->width, n_cols, d->batch);
-  if (gconv_wgrad_applicable(d)) return gconv_wgrad_workspace_floats(d);
-  if (small_cin_wgrad_applicable(d)) return (size_t)(small_cin_wgrad_slabs(d) + 1) * ((size_t)d->c_out * (d->kernel + 1));
-  if (k1_wgrad_applicable(d)) return (size_t)(k1_wgrad_slabs(d) + 1) * ((size_t)d->c_out * (d->c_in + 1));
-  // (+1: room for the summed gradient when the two-kernel finish is used)
-  return (size_t)(p.splits + 1) * ((size_t)co_g * d->groups * ci_g * d->kernel + (size_t)co_g * d->groups);
+  return wgrad_workspace(&flat, true, true);
 }
 
 extern "C" int pwg_conv1d_backward_weight_wn(const pwg_conv1d_desc* d, const float* x, const float* dy, const float* v,
@@ -1397,13 +1495,72 @@ extern "C" int pwg_conv1d_backward_weight_wn(const pwg_conv1d_desc* d, const flo
   int co_g, ci_g, n_cols;
   const pwg_conv1d_desc flat = flatten_width(*d);
   wgrad_roles(&flat, &co_g, &ci_g, &n_cols);
-  // (the finishing kernel holds one weight row in dynamic LDS next to 32 B of static LDS: stay below the 64 KiB
-  // default limit with room to spare; functional.py routes longer rows to the two-kernel finish)
-  PWG_REQUIRE((size_t)ci_g * d->kernel * sizeof(float) + 256 <= 64 * 1024, PWG_ERR_UNSUPPORTED,
+  PWG_REQUIRE(wn_row_fits(ci_g, d->kernel), PWG_ERR_UNSUPPORTED,
               "conv1d_backward_weight_wn: a weight row of %d floats exceeds the LDS row buffer", ci_g * d->kernel);
   PWG_REQUIRE(workspace_floats >= pwg_conv1d_backward_weight_wn_workspace_floats(d), PWG_ERR_WORKSPACE,
               "conv1d_backward_weight_wn: workspace too small");
   const WnFinish wn{v, g, dv, dg};
   // (dw argument: any non-NULL pointer selects the weight-gradient path; the slabs live in the workspace)
   return backward_weight_impl(d, x, dy, dv, db, workspace, workspace_floats, stream, &wn);
+}
+
+// Host only (no HIP call): what pwg_conv1d_backward_weight[_wn] would launch for `d` -- see include/pwg_kernels.h.
+extern "C" int pwg_conv1d_backward_weight_plan(const pwg_conv1d_desc* d_in, int32_t weight_norm, int32_t has_bias,
+                                               int32_t* out) {
+  PWG_REQUIRE(d_in && out, PWG_ERR_NULL, "conv1d_backward_weight: NULL pointer");
+  const pwg_conv1d_desc flat = flatten_width(*d_in);
+  const pwg_conv1d_desc* d = &flat;
+  if (int rc = wgrad_check_desc(d)) return rc;
+  const bool wn = weight_norm != 0;
+  int co_g, ci_g, n_cols;
+  wgrad_roles(d, &co_g, &ci_g, &n_cols);
+  PWG_REQUIRE(!wn || wn_row_fits(ci_g, d->kernel), PWG_ERR_UNSUPPORTED,
+              "conv1d_backward_weight_wn: a weight row of %d floats exceeds the LDS row buffer", ci_g * d->kernel);
+  for (int i = 0; i < 20; ++i) out[i] = 0;
+  const WgPath path = wgrad_path(d);
+  int fin = WG_FIN_DIRECT, nslabs = 0;
+  if (path == WG_PATH_GCONV) {
+    // gconv.hip sums its slabs with a kernel of its own; weight norm: that, then pwg_weight_norm_backward
+    fin = wn ? WG_FIN_WN_TWO_KERNEL : WG_FIN_SLABS;
+  } else {
+    const float slope = wgrad_slope(d);
+    if (int rc = wgrad_check_slope(slope)) return rc;
+    if (path == WG_PATH_SMALL_CIN) {
+      nslabs = (int)small_cin_wgrad_slabs(d);
+      fin = wgrad_finisher(nslabs, wn, d->c_out, d->kernel);
+    } else if (path == WG_PATH_K1) {
+      nslabs = k1_wgrad_slabs(d);
+      fin = wgrad_finisher(nslabs, wn, d->c_out, d->c_in);
+    } else {
+      if (int rc = wgrad_check_transposed(d)) return rc;
+      const WgPlan p = wgrad_plan(co_g, ci_g, d->groups, d->kernel, d->stride, d->dilation, d->width, n_cols, d->batch);
+      PWG_REQUIRE(p.lds <= 160 * 1024, PWG_ERR_UNSUPPORTED, "conv1d_backward_weight: tile needs %zu B of LDS", p.lds);
+      const WgVariant v = wgrad_variant(p, d->width, d->stride, wgrad_act(slope));
+      nslabs = p.splits;
+      fin = wgrad_finisher(p.splits, wn, co_g * d->groups, ci_g * d->kernel);
+      out[4] = p.small ? 1 : 0;
+      out[5] = p.tg;
+      out[6] = p.taps_block;
+      out[7] = p.tap_groups;
+      out[8] = p.win ? 1 : 0;
+      out[9] = p.tt;
+      out[10] = p.rows_half;
+      out[11] = p.rows_x4 ? 1 : 0;
+      out[12] = v.mode;
+      out[13] = v.act ? 1 : 0;
+      out[14] = v.stride_ct;
+      out[15] = p.tiles;
+      out[16] = p.splits;
+      out[17] = (int32_t)p.lds;
+      out[19] = p.xs_stride;
+    }
+  }
+  // (the weight-norm entry point always asks for the bias row, as its query does)
+  const size_t ws = wgrad_workspace(d, wn, wn || has_bias != 0);
+  out[0] = path;
+  out[1] = fin;
+  out[2] = (int32_t)(ws & 0x7FFFFFFFu);
+  out[3] = (int32_t)(ws >> 31);
+  out[18] = nslabs;
+  return PWG_OK;
 }

@@ -593,6 +593,8 @@ size_t gconv_wgrad_workspace_floats(const pwg_conv1d_desc* d) {
   return (size_t)gconv_wgrad_slices(d) * d->groups * 16 * roww + (size_t)d->c_out * cig * d->kernel + d->c_out;
 }
 
+// Always slabs + gconv_wgrad_reduce_kernel, under weight norm followed by pwg_weight_norm_backward (backward_weight_impl):
+// pwg_conv1d_backward_weight_plan reports exactly that for this path -- keep the two together.
 // dw: torch layout (c_out, cig, k); db may be NULL.  dw == NULL is not supported here (bias-only calls use the general path).
 int gconv_backward_weight(const pwg_conv1d_desc* d, const float* x, const float* dy, float* dw, float* db, float* workspace,
                           size_t ws_floats, hipStream_t stream) {

@@ -765,6 +765,26 @@ def conv1d_plan(desc, has_addends=False):
                 item_major=bool(out[4]), grid=(out[5], out[6], out[7]))
 
 
+WGRAD_PATHS = ("mfma", "gconv", "small_cin", "k1")
+WGRAD_FINISHERS = ("direct", "slabs", "slabs_wide", "wn_two_kernel", "wn_fused", "wn_fused_wide")
+
+
+def conv1d_wgrad_plan(desc, weight_norm=False, has_bias=True):
+    """What ``conv1d_backward_weight`` (``weight_norm=True``: ``conv1d_backward_weight_wn``) launches for ``desc`` (host
+    only: no launch, no device needed): dict(path, finisher, workspace_floats, slabs) and, for the ``mfma`` path,
+    small, tg, taps_block, tap_groups, win, tt, rows_half, rows_x4, mode, act, stride_ct, tiles, splits, lds, xs_stride."""
+    out = (ctypes.c_int32 * 20)()
+    _lib.check(_lib.lib().pwg_conv1d_backward_weight_plan(ctypes.byref(desc), int(bool(weight_norm)), int(bool(has_bias)),
+                                                          out), "conv1d_backward_weight_plan")
+    plan = dict(path=WGRAD_PATHS[out[0]], finisher=WGRAD_FINISHERS[out[1]], workspace_floats=out[2] + (out[3] << 31),
+                slabs=out[18])
+    if plan["path"] == "mfma":
+        plan.update(small=bool(out[4]), tg=out[5], taps_block=out[6], tap_groups=out[7], win=bool(out[8]), tt=out[9],
+                    rows_half=out[10], rows_x4=bool(out[11]), mode=out[12], act=bool(out[13]), stride_ct=out[14],
+                    tiles=out[15], splits=out[16], lds=out[17], xs_stride=out[19])
+    return plan
+
+
 def conv_tile_of_workgroup(grid, row_blocks, ksplit, item_major, workgroup):
     """Host evaluation of the convolution kernel's dispatch-id -> logical-tile map (column tile, row block index,
     item * ksplit + slice)."""
