@@ -15,95 +15,31 @@
 // an inf comes out as NaN.  There is no branch for it.
 //
 // Scope: stride-1 Conv1d, groups 1, width 1, zero padding, forward only.
-// Layout and tiles are those of csrc/conv1d_bf16.hip: A operand = three weight images [part][tap][ci / 8][m_pad][8] read
-// from global memory (L2-resident), B operand = three bf16 planes of the x window in LDS, rows of 80 B, staged per
-// 32-channel chunk.  A wave holds all A and B fragments of a reduction step (3 x TM + 3 x TN) and issues 6 x TM x TN
-// MFMAs on them: six times the MFMA work of the bf16 kernel behind the same global loads and barriers.
-// Tiles (rows x columns, 4 waves): 128 x 128 above 64 rows, 64 x 128 for 33 .. 64 rows, 32 x 256 up to 32 rows; launches of
-// fewer than 256 such workgroups run on 64 x 64 / 32 x 128 tiles, and so does a window whose three planes do not fit 64 KB
-// of LDS at the full-size column tile (32 rows, k = 11 at dilation 5).
+// Contraction, coverage, weight image, tiles and launch plan are those of csrc/mfma_conv.h, with three parts: A operand =
+// three weight images read from global memory (L2-resident), B operand = three bf16 planes of the x window in LDS, staged
+// per 32-channel chunk.  A wave holds all A and B fragments of a reduction step (3 x TM + 3 x TN) and issues 6 x TM x TN
+// MFMAs on them: six times the MFMA work of the bf16 kernel behind the same global loads and barriers.  A window whose
+// three planes do not fit 64 KB of LDS at the full-size column tile runs on the half-size tiles (32 rows, k = 11 at
+// dilation 5).
 // Deterministic: one workgroup owns an output tile, no split reduction, no atomics; the accumulation order of an element
 // (chunk, tap, reduction step, product) does not depend on the tile or the grid.
-#include "common.h"
-#include "bf16_mfma.h"
+#include "mfma_conv.h"
 
 namespace pwg {
 namespace {
 
-constexpr int KC = 32;       // input channels per staged chunk
-constexpr int ROW = KC + 8;  // bf16 elements per LDS row (80 B)
 constexpr int PARTS = 3;
-constexpr size_t kMaxLds = 64 * 1024;
-constexpr int kSmallGridWorkgroups = 256;  // one per CU
 
-// LDS rows of one plane of a column tile (as in conv1d_bf16.hip): nt + halo columns, up to 3 in front for the 16-B
-// aligned start of the vector staging, rounded up to whole groups of 4 columns
-static inline int plane_rows(int nt, int halo) { return round_up(nt + halo + 3, 4); }
-static inline size_t lds_bytes(int nt, int halo) { return (size_t)PARTS * plane_rows(nt, halo) * ROW * sizeof(__bf16); }
-
-struct SplitGeom {
-  int taps, dil, x_off;
-  int m, m_pad, mt, nt;
-  int nq, cin_chunks;
-  bool half_only;  // three planes of the full-size column tile do not fit LDS: half-size tiles whatever the grid
-};
-
-struct SplitArgs {
-  const float* x;
-  const bf16x8* w;
-  const float* bias;
-  const float* add1;
-  const float* add2;
-  float* y;
-  int c_in, c_out, t_in, t_out;
-  int m, m_pad, cin_chunks, taps, dil, x_off, nq;
-  int plane;         // bf16 elements per LDS plane
-  long part_stride;  // bf16x8 elements per weight part image
+struct SplitArgs : MfmaConvArgs {
+  int plane;          // bf16 elements per LDS plane
+  long part_stride;   // bf16x8 elements per weight part image
   float pre_mul;      // pre-activation, one branch-free form for none / leaky / relu (pre_activate)
   unsigned pre_mask;
-  int post_act;
-  float post_slope, out_mul, out_div;
   int wide_out;  // y / add1 / add2 are 16-B aligned and t_out % 4 == 0: 16-B accesses in the epilogue
 };
 
-static int split_geometry(const pwg_conv1d_desc* d, SplitGeom* g) {
-  PWG_REQUIRE(d != nullptr, PWG_ERR_NULL, "conv1d_split: NULL descriptor");
-  PWG_REQUIRE(d->batch > 0 && d->c_in > 0 && d->c_out > 0 && d->t_in > 0 && d->t_out > 0 && d->kernel > 0 &&
-                  d->stride > 0 && d->dilation > 0 && d->groups > 0 && d->width > 0 && d->pad_left >= 0,
-              PWG_ERR_BAD_SHAPE, "conv1d_split: non-positive size in descriptor");
-  PWG_REQUIRE(d->groups == 1, PWG_ERR_UNSUPPORTED, "conv1d_split: groups = %d (only groups == 1)", d->groups);
-  PWG_REQUIRE(d->width == 1, PWG_ERR_UNSUPPORTED, "conv1d_split: width = %d (only width == 1)", d->width);
-  PWG_REQUIRE(d->pad_mode == PWG_PAD_ZERO, PWG_ERR_UNSUPPORTED, "conv1d_split: only zero padding (pad_mode = %d)",
-              d->pad_mode);
-  PWG_REQUIRE(!d->transposed, PWG_ERR_UNSUPPORTED, "conv1d_split: transposed convolutions are not covered");
-  PWG_REQUIRE(d->stride == 1, PWG_ERR_UNSUPPORTED, "conv1d_split: stride = %d (only stride 1)", d->stride);
-  PWG_REQUIRE(d->pre_act == PWG_ACT_NONE || d->pre_act == PWG_ACT_LEAKY_RELU || d->pre_act == PWG_ACT_RELU,
-              PWG_ERR_UNSUPPORTED, "conv1d_split: pre_act = %d", d->pre_act);
-  PWG_REQUIRE(d->batch <= 65535, PWG_ERR_UNSUPPORTED, "conv1d_split: batch = %d (> 65535)", d->batch);
-  g->taps = d->kernel;
-  g->dil = d->dilation;
-  g->x_off = -d->pad_left;
-  g->m = d->c_out;
-  g->nq = d->t_out;
-  g->mt = g->m <= 32 ? 32 : (g->m <= 64 ? 64 : 128);
-  g->nt = g->m <= 32 ? 256 : 128;
-  g->m_pad = round_up(g->m, g->mt);
-  g->cin_chunks = ceil_div(d->c_in, KC);
-  PWG_REQUIRE((long)(g->taps - 1) * g->dil < (1 << 20), PWG_ERR_UNSUPPORTED, "conv1d_split: receptive field too long");
-  g->half_only = lds_bytes(g->nt, (g->taps - 1) * g->dil) > kMaxLds;
-  const size_t lds = lds_bytes(g->half_only ? g->nt / 2 : g->nt, (g->taps - 1) * g->dil);
-  PWG_REQUIRE(lds <= kMaxLds, PWG_ERR_UNSUPPORTED, "conv1d_split: receptive field (%d taps, dilation %d) needs %zu B of LDS",
-              g->taps, g->dil, lds);
-  PWG_REQUIRE(ceil_div(g->m_pad, g->mt) <= 65535, PWG_ERR_UNSUPPORTED, "conv1d_split: too many row blocks");
-  return PWG_OK;
-}
-
-// the exact 3-way split of the header comment
-__device__ __forceinline__ void split3(float v, __bf16& hi, __bf16& mid, __bf16& lo) {
-  hi = (__bf16)v;
-  const float r = v - (float)hi;
-  mid = (__bf16)r;
-  lo = (__bf16)(r - (float)mid);
+static int split_geometry(const pwg_conv1d_desc* d, MfmaConvGeom* g) {
+  return mfma_conv_geometry("conv1d_split", PARTS, false, d, g);
 }
 
 // The pre-activation without control flow: v > 0 ? v : bits(v * mul) & mask, with (mul, mask) = (1, ~0) for none,
@@ -114,33 +50,6 @@ __device__ __forceinline__ float pre_activate(float v, float mul, unsigned mask)
   return v > 0.f ? v : n;
 }
 
-// one thread per element of ONE part image [tap][ci / 8][m_pad][8], writing that element of all three parts; padding
-// rows / channels are zero
-__global__ __launch_bounds__(256) void pack_weight_split_kernel(const float* __restrict__ w, const float* __restrict__ scale,
-                                                                __bf16* __restrict__ wp, int c_in, int kernel, int cin_pad,
-                                                                int m, int m_pad) {
-  const long total = (long)kernel * cin_pad * m_pad;
-  for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256L) {
-    const int j = (int)(i & 7);
-    long rest = i >> 3;
-    const int row = (int)(rest % m_pad);
-    rest /= m_pad;
-    const int oct = (int)(rest % (cin_pad / 8));
-    const int tap = (int)(rest / (cin_pad / 8));
-    const int ci = oct * 8 + j;
-    float v = 0.f;
-    if (ci < c_in && row < m) {
-      v = w[((long)row * c_in + ci) * kernel + tap];
-      if (scale) v *= scale[row];
-    }
-    __bf16 hi, mid, lo;
-    split3(v, hi, mid, lo);
-    wp[i] = hi;
-    wp[total + i] = mid;
-    wp[2 * total + i] = lo;
-  }
-}
-
 // Vector staging of one 32-channel chunk of the x window (xc: channel 0 of the chunk, c_left channels are left).
 // item = (group of 4 columns, channel octet): 8 loads of 16 B (one per channel, lanes walk t), then per column 8 channels
 // are activated, split and written as three 16-B LDS stores (one per plane).  CHECKED (edge tiles): a load whose group
@@ -148,7 +57,7 @@ __global__ __launch_bounds__(256) void pack_weight_split_kernel(const float* __r
 template <int NT, bool CHECKED>
 __device__ __forceinline__ void stage_window_vec(const SplitArgs& a, const float* __restrict__ xc, int c_left, int base,
                                                  int ngroups, __bf16* xs, int tid) {
-  constexpr int ITEMS = NT >= 128 ? NT / 128 : 1;
+  constexpr int ITEMS = window_items(NT);
   f32x4 st[ITEMS][8];
 #pragma unroll
   for (int it = 0; it < ITEMS; ++it) {
@@ -185,7 +94,7 @@ __device__ __forceinline__ void stage_window_vec(const SplitArgs& a, const float
           vm[j] = mid;
           vl[j] = lo;
         }
-        __bf16* dst = xs + (grp * 4 + e) * ROW + oct * 8;
+        __bf16* dst = xs + (grp * 4 + e) * kConvRow + oct * 8;
         *reinterpret_cast<bf16x8*>(dst) = vh;
         *reinterpret_cast<bf16x8*>(dst + a.plane) = vm;
         *reinterpret_cast<bf16x8*>(dst + 2 * a.plane) = vl;
@@ -297,9 +206,8 @@ __device__ __forceinline__ void split_epilogue(const SplitArgs& a, const typenam
   }
 }
 
-// Template parameters as in conv1d_bf16.hip.  TILE: MFMA shape (32: 32x32x16, 16: 16x16x32).  A wave computes (WM * 32)
-// rows x (WN * 32) columns; the 4 waves of a workgroup are arranged WAVES_M x (4 / WAVES_M).  VEC: the x window is staged
-// with 16-B loads along t (rows 16-B aligned, t_in % 4 == 0, window <= 2 * NT columns) and transposed in registers.
+// TILE, WM, WN, WAVES_M: the tile ladder of mfma_conv.h.  VEC: the x window is staged with 16-B loads along t (rows 16-B
+// aligned, t_in % 4 == 0, window <= 2 * NT columns) and transposed in registers.
 // The second launch bound (waves per SIMD) is the occupancy that the main loop's registers allow: without it the register
 // allocator copies every accumulator out of the AGPRs at the head of the epilogue and the kernel loses a wave.
 template <int TILE, int WM, int WN, int WAVES_M, bool VEC>
@@ -316,15 +224,8 @@ conv1d_split_mfma_kernel(SplitArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __bf16* xs = reinterpret_cast<__bf16*>(smem);  // [part][column][ROW]
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wave_m = wave % WAVES_M, wave_n = wave / WAVES_M;
-  const int r = lane & (TILE - 1), h = lane / TILE;
-  const int q0 = blockIdx.x * NT, m0 = blockIdx.y * MT, b = blockIdx.z;
-  const int start = q0 + a.x_off;               // input column of (local column 0, tap 0)
-  const int base = VEC ? (start & ~3) : start;  // first staged input column (VEC: 16-B aligned, also when negative)
-  const int sh = start - base;                  // 0 .. 3
-  const int wcols = NT + (a.taps - 1) * a.dil + sh;
-  const float* __restrict__ xb = a.x + (size_t)b * a.c_in * a.t_in;
+  const MfmaConvTile c = mfma_conv_tile<TILE, MT, NT, WAVES_M, VEC>(a);
+  const float* __restrict__ xb = c.xb;
 
   acc_t acc[TM][TN];
 #pragma unroll
@@ -339,18 +240,18 @@ conv1d_split_mfma_kernel(SplitArgs a) {
     if (VEC) {
       // an interior tile (decided once per workgroup and chunk: every staged column inside the row, a whole chunk of
       // channels) takes unconditional loads; an edge tile checks every load
-      const int ngroups = (wcols + 3) >> 2, c_left = a.c_in - chunk * KC;
+      const int ngroups = (c.wcols + 3) >> 2, c_left = a.c_in - chunk * KC;
       const float* __restrict__ xc = xb + (size_t)chunk * KC * a.t_in;
-      if (base >= 0 && base + 4 * ngroups <= a.t_in && c_left >= KC)
-        stage_window_vec<NT, false>(a, xc, c_left, base, ngroups, xs, tid);
+      if (c.base >= 0 && c.base + 4 * ngroups <= a.t_in && c_left >= KC)
+        stage_window_vec<NT, false>(a, xc, c_left, c.base, ngroups, xs, c.tid);
       else
-        stage_window_vec<NT, true>(a, xc, c_left, base, ngroups, xs, tid);
+        stage_window_vec<NT, true>(a, xc, c_left, c.base, ngroups, xs, c.tid);
     } else {
       // wave `wave` stages channel octet `wave` of the chunk: lanes walk the columns (coalesced fp32 rows)
-      const int c_base = chunk * KC + wave * 8;
-      const bool interior = base >= 0 && base + wcols <= a.t_in && c_base + 8 <= a.c_in;  // per wave and chunk
-      for (int col = lane; col < wcols; col += 64) {
-        const int t = base + col;
+      const int c_base = chunk * KC + c.wave * 8;
+      const bool interior = c.base >= 0 && c.base + c.wcols <= a.t_in && c_base + 8 <= a.c_in;  // per wave and chunk
+      for (int col = c.lane; col < c.wcols; col += 64) {
+        const int t = c.base + col;
         const float* __restrict__ src = xb + (size_t)c_base * a.t_in + t;
         float f[8];
         if (interior) {
@@ -373,7 +274,7 @@ conv1d_split_mfma_kernel(SplitArgs a) {
           vm[j] = mid;
           vl[j] = lo;
         }
-        __bf16* dst = xs + col * ROW + wave * 8;
+        __bf16* dst = xs + col * kConvRow + c.wave * 8;
         *reinterpret_cast<bf16x8*>(dst) = vh;
         *reinterpret_cast<bf16x8*>(dst + a.plane) = vm;
         *reinterpret_cast<bf16x8*>(dst + 2 * a.plane) = vl;
@@ -383,9 +284,9 @@ conv1d_split_mfma_kernel(SplitArgs a) {
     for (int tap = 0; tap < a.taps; ++tap) {
 #pragma unroll
       for (int ks = 0; ks < KSTEPS; ++ks) {
-        const int oct = ks * HL + h;
+        const int oct = ks * HL + c.h;
         const bf16x8* __restrict__ wp =
-            a.w + ((size_t)(tap * a.cin_chunks + chunk) * (KC / 8) + oct) * a.m_pad + m0 + wave_m * (WM * 32) + r;
+            image_rows(a.w, a.cin_chunks, a.m_pad, tap, chunk, oct) + c.m0 + c.wave_m * (WM * 32) + c.r;
         bf16x8 af[PARTS][TM], bfr[PARTS][TN];  // [0] hi, [1] mid, [2] lo
 #pragma unroll
         for (int p = 0; p < PARTS; ++p)
@@ -393,8 +294,8 @@ conv1d_split_mfma_kernel(SplitArgs a) {
           for (int mi = 0; mi < TM; ++mi) af[p][mi] = wp[p * a.part_stride + mi * TILE];
 #pragma unroll
         for (int ni = 0; ni < TN; ++ni) {
-          const int col = sh + wave_n * (WN * 32) + ni * TILE + r + tap * a.dil;
-          const __bf16* src = xs + col * ROW + oct * 8;
+          const int col = c.sh + c.wave_n * (WN * 32) + ni * TILE + c.r + tap * a.dil;
+          const __bf16* src = xs + col * kConvRow + oct * 8;
 #pragma unroll
           for (int p = 0; p < PARTS; ++p) bfr[p][ni] = *reinterpret_cast<const bf16x8*>(src + p * a.plane);
         }
@@ -412,9 +313,9 @@ conv1d_split_mfma_kernel(SplitArgs a) {
     }
   }
 
-  const size_t out_base = (size_t)b * a.c_out * a.t_out;
-  const int row0 = m0 + wave_m * (WM * 32) + r, col0 = q0 + wave_n * (WN * 32) + 4 * h;
-  const bool full = m0 + MT <= a.m && q0 + NT <= a.nq;  // no padded row and no column past the end in this tile
+  const size_t out_base = (size_t)c.b * a.c_out * a.t_out;
+  const int row0 = c.m0 + c.wave_m * (WM * 32) + c.r, col0 = c.q0 + c.wave_n * (WN * 32) + 4 * c.h;
+  const bool full = c.m0 + MT <= a.m && c.q0 + NT <= a.nq;  // no padded row and no column past the end in this tile
   if (!a.wide_out)
     split_epilogue<TILE, TM, TN, false, false>(a, acc, row0, col0, out_base);
   else if (full)
@@ -423,95 +324,36 @@ conv1d_split_mfma_kernel(SplitArgs a) {
     split_epilogue<TILE, TM, TN, true, false>(a, acc, row0, col0, out_base);
 }
 
-template <int TILE, bool VEC>
-static void launch_tile(const SplitGeom& g, const SplitArgs& a, int batch, bool small, size_t lds, hipStream_t stream) {
-  const int mt = small ? (g.mt > 32 ? 64 : 32) : g.mt, nt = small ? g.nt / 2 : g.nt;
-  const dim3 grid(ceil_div(g.nq, nt), g.m_pad / mt, batch);
-  if (small && mt == 32)  // 32 x 128
-    hipLaunchKernelGGL((conv1d_split_mfma_kernel<TILE, 1, 1, 1, VEC>), grid, dim3(256), lds, stream, a);
-  else if (small)  // 64 x 64
-    hipLaunchKernelGGL((conv1d_split_mfma_kernel<TILE, 1, 1, 2, VEC>), grid, dim3(256), lds, stream, a);
-  else if (g.mt == 32)  // 32 x 256
-    hipLaunchKernelGGL((conv1d_split_mfma_kernel<TILE, 1, 2, 1, VEC>), grid, dim3(256), lds, stream, a);
-  else if (g.mt == 64)  // 64 x 128
-    hipLaunchKernelGGL((conv1d_split_mfma_kernel<TILE, 1, 2, 2, VEC>), grid, dim3(256), lds, stream, a);
-  else  // 128 x 128
-    hipLaunchKernelGGL((conv1d_split_mfma_kernel<TILE, 2, 2, 2, VEC>), grid, dim3(256), lds, stream, a);
-}
+template <bool VEC>
+struct Family {
+  template <int TILE, int WM, int WN, int WAVES_M>
+  struct K {
+    static constexpr auto fn = conv1d_split_mfma_kernel<TILE, WM, WN, WAVES_M, VEC>;
+  };
+};
 
-// tile_mode: 0 = the small-grid rule decides, 1 = full-size tiles (where their three planes fit LDS), 2 = half-size tiles
 static int split_forward(const pwg_conv1d_desc* d, const float* x, const void* w_packed, const float* bias,
                          const float* add1, const float* add2, float* y, int mfma_shape, int tile_mode,
                          hipStream_t stream) {
-  SplitGeom g;
+  MfmaConvGeom g;
   int rc = split_geometry(d, &g);
+  if (rc == PWG_OK) rc = mfma_conv_check_forward("conv1d_split", d, x, w_packed, y, mfma_shape, tile_mode);
   if (rc != PWG_OK) return rc;
-  PWG_REQUIRE(x && w_packed && y, PWG_ERR_NULL, "conv1d_split: NULL pointer");
-  PWG_REQUIRE((reinterpret_cast<uintptr_t>(w_packed) & 15u) == 0, PWG_ERR_BAD_SHAPE,
-              "conv1d_split: the weight image must be 16-B aligned");
-  PWG_REQUIRE(mfma_shape == 16 || mfma_shape == 32, PWG_ERR_BAD_SHAPE, "conv1d_split: mfma_shape = %d (16 or 32)",
-              mfma_shape);
-  PWG_REQUIRE(tile_mode >= 0 && tile_mode <= 2, PWG_ERR_BAD_SHAPE, "conv1d_split: tile_mode = %d (0, 1 or 2)", tile_mode);
-  PWG_REQUIRE(d->post_act >= PWG_ACT_NONE && d->post_act <= PWG_ACT_RELU, PWG_ERR_BAD_SHAPE, "conv1d_split: post_act = %d",
-              d->post_act);
-  const int halo = (g.taps - 1) * g.dil;
-  // short inputs: a launch that would not give every CU a workgroup runs on half-size tiles (the weight image is the
-  // same); the accumulation order of an output element does not depend on the tile
-  const bool small = g.half_only || (tile_mode == 0 ? (long)ceil_div(g.nq, g.nt) * (g.m_pad / g.mt) * d->batch <
-                                                          kSmallGridWorkgroups
-                                                    : tile_mode == 2);
-  const int nt = small ? g.nt / 2 : g.nt;
+  const MfmaConvPlan p = mfma_conv_plan(d, g, PARTS, tile_mode, x, add1, add2);
   SplitArgs a;
-  a.x = x;
-  a.w = static_cast<const bf16x8*>(w_packed);
-  a.bias = bias;
-  a.add1 = add1;
-  a.add2 = add2;
-  a.y = y;
-  a.c_in = d->c_in;
-  a.c_out = d->c_out;
-  a.t_in = d->t_in;
-  a.t_out = d->t_out;
-  a.m = g.m;
-  a.m_pad = g.m_pad;
-  a.cin_chunks = g.cin_chunks;
-  a.taps = g.taps;
-  a.dil = g.dil;
-  a.x_off = g.x_off;
-  a.nq = g.nq;
-  a.plane = plane_rows(nt, halo) * ROW;
-  a.part_stride = (long)g.taps * g.cin_chunks * (KC / 8) * g.m_pad;
+  mfma_conv_fill_args(&a, d, g, x, w_packed, bias, add1, add2, y);
+  a.plane = p.plane;
+  a.part_stride = image_elems(g) / 8;
   a.pre_mul = d->pre_act == PWG_ACT_LEAKY_RELU ? d->pre_slope : (d->pre_act == PWG_ACT_RELU ? 0.0f : 1.0f);
   a.pre_mask = d->pre_act == PWG_ACT_RELU ? 0u : ~0u;
-  a.post_act = d->post_act;
-  a.post_slope = d->post_slope;
-  a.out_mul = d->out_mul;
-  a.out_div = d->out_div;
   a.wide_out = d->t_out % 4 == 0 && ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(add1) |
                                       reinterpret_cast<uintptr_t>(add2)) & 15u) == 0;
-  const size_t lds = lds_bytes(nt, halo);
-  // vector staging: 16-B loads along t need aligned rows, and the window must fit the per-thread register items
-  const bool vec = d->t_in % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15u) == 0 &&
-                   nt + halo + 3 <= (nt >= 128 ? 2 * nt : 256);
-  const double out_elems = (double)d->batch * d->c_out * d->t_out;
-  const double in_elems = (double)d->batch * d->c_in * d->t_in;
-  // the ALGORITHMIC flops of the convolution, not the six products that are executed
-  const double flops = 2.0 * (double)d->batch * g.m * g.nq * g.taps * d->c_in;
-  const double bytes = 4.0 * (in_elems + out_elems * (1 + (add1 ? 1 : 0) + (add2 ? 1 : 0))) +
-                       2.0 * PARTS * (double)g.taps * g.cin_chunks * KC * g.m_pad;
   maybe_poison_lds(stream);
-  ProfScope prof(stream, "conv1d_split_mfma_kernel", flops, bytes);
-  if (mfma_shape == 32) {
-    if (vec)
-      launch_tile<32, true>(g, a, d->batch, small, lds, stream);
-    else
-      launch_tile<32, false>(g, a, d->batch, small, lds, stream);
-  } else {
-    if (vec)
-      launch_tile<16, true>(g, a, d->batch, small, lds, stream);
-    else
-      launch_tile<16, false>(g, a, d->batch, small, lds, stream);
-  }
+  ProfScope prof(stream, "conv1d_split_mfma_kernel", p.flops, p.bytes);
+  if (p.vec)
+    mfma_conv_launch<Family<true>::K>(p, mfma_shape, a, stream);
+  else
+    mfma_conv_launch<Family<false>::K>(p, mfma_shape, a, stream);
   PWG_CHECK_LAUNCH("conv1d_split");
   return PWG_OK;
 }
@@ -525,27 +367,23 @@ constexpr int kDefaultMfmaShape = 16;
 using namespace pwg;
 
 extern "C" int pwg_conv1d_split_supported(const pwg_conv1d_desc* d) {
-  SplitGeom g;
+  MfmaConvGeom g;
   return split_geometry(d, &g) == PWG_OK ? 1 : 0;
 }
 
 extern "C" size_t pwg_conv1d_split_packed_weight_bytes(const pwg_conv1d_desc* d) {
-  SplitGeom g;
+  MfmaConvGeom g;
   if (split_geometry(d, &g) != PWG_OK) return 0;
-  return (size_t)PARTS * g.taps * g.cin_chunks * KC * g.m_pad * sizeof(__bf16);
+  return (size_t)PARTS * image_elems(g) * sizeof(__bf16);
 }
 
 extern "C" int pwg_conv1d_split_pack_weight(const pwg_conv1d_desc* d, const float* w, const float* scale, void* w_packed,
                                             void* stream) {
-  SplitGeom g;
+  MfmaConvGeom g;
   int rc = split_geometry(d, &g);
   if (rc != PWG_OK) return rc;
   PWG_REQUIRE(w && w_packed, PWG_ERR_NULL, "conv1d_split_pack_weight: NULL pointer");
-  const long total = (long)g.taps * g.cin_chunks * KC * g.m_pad;
-  int blocks = (int)((total + 255) / 256);
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(pack_weight_split_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w, scale,
-                     static_cast<__bf16*>(w_packed), d->c_in, d->kernel, g.cin_chunks * KC, g.m, g.m_pad);
+  mfma_conv_pack<PARTS>(d, g, w, scale, w_packed, (hipStream_t)stream);
   PWG_CHECK_LAUNCH("conv1d_split_pack_weight");
   return PWG_OK;
 }

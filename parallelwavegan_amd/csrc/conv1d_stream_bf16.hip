@@ -12,9 +12,9 @@
 //   Y[m][j] = sum_{tap, ci} W[m][tap][ci] * bf16(act(X[ci][j - H + tap * dil]))        X[t < 0] = history
 //   Conv1d:          m = output channel, taps = k, dil = dilation
 //   ConvTranspose1d: m = co * s + phase, taps = 2 (x[j - 1] with w[phase + s], x[j] with w[phase]), output column
-//                    j * s + phase -- the row order of the bf16 image (csrc/conv1d_bf16.hip), NOT the phase-major order
+//                    j * s + phase -- the row order of the bf16 image (csrc/mfma_conv.h), NOT the phase-major order
 //                    of the fp32 one
-// The A operand is read straight from that image ([tap][ci / 8][m_pad][8], rows padded to 32 / 64 / 128, channels to 32:
+// The A operand is read straight from that image (layout and row padding: csrc/mfma_conv.h; rows come in whole tiles of 32:
 // a 16-row block never leaves it; no second image).  The B operand is the window of NT + H columns, staged per block of
 // 128 input channels into LDS as bf16 in [column][channel] order: a lane's 8 reduction elements are one ds_read_b128,
 // and a row is 17 slots of 16 B (odd), so that the 16 columns an MFMA reads start on 16 different slots of the bank row.
@@ -33,13 +33,13 @@
 // Tiles: as the fp32 stream kernel -- 16 rows x 16 / 32 / 64 columns for chunks of up to 16 / 32 / more columns, 32 x 64
 // when that still gives every CU two workgroups; the four waves deal the REDUCTION, and the A fragments of the next four
 // items (one 16-B load per lane and item) are in flight while the current four are contracted.  DESIGN.md s11.2.
+#include "mfma_conv.h"
 #include "stream_common.h"
 
 namespace pwg {
 namespace {
 
-constexpr int KC = 32;            // input channels per chunk of the image = one MFMA reduction step
-constexpr int SC = 4 * KC;        // input channels staged per LDS block
+constexpr int SC = 4 * KC;        // input channels staged per LDS block (KC, a chunk of the image: one MFMA reduction step)
 constexpr int ROW = SC + 8;       // bf16 elements per LDS row: 17 slots of 16 B
 static_assert((kStreamMaxNt + kStreamMaxHist) * ROW * sizeof(__bf16) <= kStreamLdsBytes,
               "the widest bf16 window does not fit LDS");
@@ -229,17 +229,13 @@ extern "C" int pwg_conv1d_stream_bf16_forward(const pwg_conv1d_desc* d, const fl
   StreamGeom g;
   if (stream_geometry(d, &g) != PWG_OK) return PWG_ERR_UNSUPPORTED;  // (pwg_last_error holds the reason)
   hipStream_t stream = (hipStream_t)stream_;
-  const int cin_chunks = ceil_div(d->c_in, KC);
-  // the row extent of the image comes from its owner (csrc/conv1d_bf16.hip); the image does not depend on padding,
-  // which the packer's geometry check admits only as zero
+  // the image and its geometry come from their owner (csrc/mfma_conv.h); the image does not depend on padding, which
+  // that geometry admits only as zero
   pwg_conv1d_desc dz = *d;
   dz.pad_mode = PWG_PAD_ZERO;
-  const size_t image_bytes = pwg_conv1d_bf16_packed_weight_bytes(&dz);
-  PWG_REQUIRE(image_bytes != 0, PWG_ERR_UNSUPPORTED, "conv1d_stream_bf16: the layer has no bf16 weight image");
-  const size_t row_bytes = (size_t)g.taps * cin_chunks * KC * sizeof(__bf16);
-  const int m_pad = (int)(image_bytes / row_bytes);
-  PWG_REQUIRE((size_t)m_pad * row_bytes == image_bytes && m_pad % 32 == 0 && m_pad >= g.m, PWG_ERR_UNSUPPORTED,
-              "conv1d_stream_bf16: unexpected bf16 weight image of %zu B for %d rows", image_bytes, g.m);
+  MfmaConvGeom image;
+  PWG_REQUIRE(mfma_conv_geometry("conv1d_bf16", 1, true, &dz, &image) == PWG_OK, PWG_ERR_UNSUPPORTED,
+              "conv1d_stream_bf16: the layer has no bf16 weight image");
   const int rc = stream_check_pointers("conv1d_stream_bf16", d, g, x, w_packed_bf16, y, hist_in, hist_out);
   if (rc != PWG_OK) return rc;
   PWG_REQUIRE((reinterpret_cast<uintptr_t>(w_packed_bf16) & 15u) == 0, PWG_ERR_BAD_SHAPE,
@@ -250,15 +246,15 @@ extern "C" int pwg_conv1d_stream_bf16_forward(const pwg_conv1d_desc* d, const fl
   StreamBf16Args a;
   stream_fill_args(&a, d, g, tile, x, hist_in, hist_out, bias, add1, add2, y);
   a.w = static_cast<const bf16x8*>(w_packed_bf16);
-  a.cin_chunks = cin_chunks;
-  a.m_pad = m_pad;  // of the bf16 image, not g.m_pad
+  a.cin_chunks = image.cin_chunks;
+  a.m_pad = image.m_pad;  // of the bf16 image, not g.m_pad
   a.q4 = 4 / g.taps;
   a.r4 = 4 % g.taps;
 
   const double out_elems = (double)d->batch * d->c_out * d->t_out;
   const double flops = 2.0 * (double)d->batch * g.m * n * g.taps * d->c_in;
   const double bytes = 4.0 * ((double)d->batch * d->c_in * (n + 2.0 * g.hist) +
-                              out_elems * (1 + (add1 ? 1 : 0) + (add2 ? 1 : 0))) + (double)image_bytes;
+                              out_elems * (1 + (add1 ? 1 : 0) + (add2 ? 1 : 0))) + 2.0 * (double)image_elems(image);
   maybe_poison_lds(stream);
   ProfScope prof(stream, "conv1d_stream_bf16_kernel", flops, bytes);
   stream_launch<Kernel>(tile, d->transposed != 0, a, g.m, d->batch,

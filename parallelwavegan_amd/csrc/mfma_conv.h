@@ -1,0 +1,284 @@
+// What the whole-utterance MFMA convolutions share (conv1d_bf16.hip, conv1d_split.hip and, for the weight image,
+// conv1d_stream_bf16.hip): everything that has to agree between the kernels is stated here, once.
+//   chunk, LDS row        KC, kConvRow, plane_rows   32 channels per staged chunk; rows of 80 B; rows of a column tile
+//   coverage, tile rule   mfma_conv_geometry         128 / 64 / 32 rows x 128 / 128 / 256 columns from the GEMM rows
+//   weight image          image_elems, image_decode, image_rows, mfma_conv_pack   [tap][ci / 8][m_pad][8] per part
+//   launch plan           mfma_conv_plan             half-size tiles for short inputs, grid, LDS, vector staging
+//   tile ladder           mfma_conv_launch           the five tiles x two MFMA shapes of a kernel family
+//   arguments             MfmaConvArgs, mfma_conv_fill_args, mfma_conv_check_forward
+//   tile coordinates      MfmaConvTile               thread, wave and window coordinates of a workgroup
+// Internal to csrc/; the staging conversions, the contractions and the epilogues of the kernels differ on purpose and
+// stay with them.  The stream kernel reads the bf16 image with its own tiles and LDS row (conv1d_stream_bf16.hip).
+#pragma once
+#include "common.h"
+
+#include "bf16_mfma.h"  // after common.h: it needs the HIP runtime header
+
+#include <stdint.h>
+
+namespace pwg {
+
+constexpr int KC = 32;                     // input channels per chunk of the image and per staged chunk
+constexpr int kConvRow = KC + 8;           // bf16 elements per LDS row: 80 B, 5 slots of 16 B (odd)
+constexpr size_t kConvMaxLds = 64 * 1024;  // what a workgroup gets without raising the kernel's limit
+constexpr int kConvFillWorkgroups = 256;   // one per CU
+
+// LDS rows of one plane of a column tile: the window of nt + halo columns, plus up to 3 columns in front when the
+// staging starts at a 16-B aligned input column (vector path), rounded up to whole groups of 4 columns
+static inline int plane_rows(int nt, int halo) { return round_up(nt + halo + 3, 4); }
+static inline size_t conv_lds_bytes(int parts, int nt, int halo) {
+  return (size_t)parts * plane_rows(nt, halo) * kConvRow * sizeof(__bf16);
+}
+
+// ---- coverage and tile rule.  Contraction: Y[m][q] = sum_{tap, ci} W[m][tap][ci] * X[ci][q + x_off + tap * dil]
+//   Conv1d (stride 1):           m = output channel, q = output column, taps = kernel, x_off = -pad_left
+//   ConvTranspose1d with k = 2s: polyphase -- m = co * s + phase, q = (o + padding) / s, two taps (x[q - 1] with
+//                                w[.., phase + s], x[q] with w[.., phase]); output column o = q * s + phase - padding
+// Tiles (rows x columns, 4 waves): 128 x 128 above 64 rows, 64 x 128 for 33 .. 64 rows, 32 x 256 up to 32 rows.  Rows are
+// zero-padded in the weight image, columns are masked.
+struct MfmaConvGeom {
+  int taps, dil, x_off;  // reduction taps, their spacing, input column of (q = 0, tap 0)
+  int m, m_pad, mt;      // GEMM rows, padded to the row tile mt
+  int phases, out_off;   // transposed: stride and padding (o = q * phases + phase - out_off), else 1 and 0
+  int nq;                // GEMM columns
+  int cin_chunks;        // ceil(c_in / KC)
+  int nt;                // column tile of the configuration
+  bool half_only;        // the planes of the full-size column tile do not fit LDS: half-size tiles whatever the grid
+};
+
+// parts: operand parts = LDS planes and weight images (1: bf16 operands, 3: split operands).  The refusals are worded
+// and ordered as each kernel has always reported them.
+static inline int mfma_conv_geometry(const char* name, int parts, bool allow_transposed, const pwg_conv1d_desc* d,
+                                     MfmaConvGeom* g) {
+  PWG_REQUIRE(d != nullptr, PWG_ERR_NULL, "%s: NULL descriptor", name);
+  PWG_REQUIRE(d->batch > 0 && d->c_in > 0 && d->c_out > 0 && d->t_in > 0 && d->t_out > 0 && d->kernel > 0 &&
+                  d->stride > 0 && d->dilation > 0 && d->groups > 0 && d->width > 0 && d->pad_left >= 0,
+              PWG_ERR_BAD_SHAPE, "%s: non-positive size in descriptor", name);
+  PWG_REQUIRE(d->groups == 1, PWG_ERR_UNSUPPORTED, "%s: groups = %d (only groups == 1)", name, d->groups);
+  PWG_REQUIRE(d->width == 1, PWG_ERR_UNSUPPORTED, "%s: width = %d (only width == 1)", name, d->width);
+  PWG_REQUIRE(d->pad_mode == PWG_PAD_ZERO, PWG_ERR_UNSUPPORTED, "%s: only zero padding (pad_mode = %d)", name, d->pad_mode);
+  if (!allow_transposed) {
+    PWG_REQUIRE(!d->transposed, PWG_ERR_UNSUPPORTED, "%s: transposed convolutions are not covered", name);
+    PWG_REQUIRE(d->stride == 1, PWG_ERR_UNSUPPORTED, "%s: stride = %d (only stride 1)", name, d->stride);
+  }
+  PWG_REQUIRE(d->pre_act == PWG_ACT_NONE || d->pre_act == PWG_ACT_LEAKY_RELU || d->pre_act == PWG_ACT_RELU,
+              PWG_ERR_UNSUPPORTED, "%s: pre_act = %d", name, d->pre_act);
+  PWG_REQUIRE(d->batch <= 65535, PWG_ERR_UNSUPPORTED, "%s: batch = %d (> 65535)", name, d->batch);
+  if (d->transposed) {
+    PWG_REQUIRE(d->kernel == 2 * d->stride && d->dilation == 1, PWG_ERR_UNSUPPORTED,
+                "%s: transposed convolution with kernel = %d, stride = %d (only kernel == 2 * stride)", name, d->kernel,
+                d->stride);
+    *g = MfmaConvGeom{2, 1, -1, d->c_out * d->stride, 0, 0, d->stride, d->pad_left,
+                      ceil_div(d->t_out + d->pad_left, d->stride)};
+  } else {
+    PWG_REQUIRE(d->stride == 1, PWG_ERR_UNSUPPORTED, "%s: stride = %d (only stride 1)", name, d->stride);
+    *g = MfmaConvGeom{d->kernel, d->dilation, -d->pad_left, d->c_out, 0, 0, 1, 0, d->t_out};
+  }
+  g->mt = g->m <= 32 ? 32 : (g->m <= 64 ? 64 : 128);
+  g->nt = g->m <= 32 ? 256 : 128;
+  g->m_pad = round_up(g->m, g->mt);
+  g->cin_chunks = ceil_div(d->c_in, KC);
+  // Only the split kernel bounds the window before it sizes it, and only it falls back to half-size tiles for LDS alone
+  // (the bf16 kernel refuses such a window; admitting it there would be a new rule)
+  PWG_REQUIRE(parts == 1 || (long)(g->taps - 1) * g->dil < (1 << 20), PWG_ERR_UNSUPPORTED, "%s: receptive field too long",
+              name);
+  const int halo = (g->taps - 1) * g->dil;
+  g->half_only = parts > 1 && conv_lds_bytes(parts, g->nt, halo) > kConvMaxLds;
+  const size_t lds = conv_lds_bytes(parts, g->half_only ? g->nt / 2 : g->nt, halo);
+  PWG_REQUIRE(lds <= kConvMaxLds, PWG_ERR_UNSUPPORTED, "%s: receptive field (%d taps, dilation %d) needs %zu B of LDS", name,
+              g->taps, g->dil, lds);
+  PWG_REQUIRE(ceil_div(g->m_pad, g->mt) <= 65535, PWG_ERR_UNSUPPORTED, "%s: too many row blocks", name);
+  return PWG_OK;
+}
+
+// ---- weight image.  One part is [tap][ci / 8][m_pad][8] bf16: rows padded to the row tile (g.m_pad), channels to whole
+// chunks, padding zero; a lane's A fragment is 16 B and a half wave reads 512 B contiguous.  The split kernel's image is
+// three parts (hi, mid, lo) of image_elems() each, one after the other.
+static inline long image_elems(const MfmaConvGeom& g) { return (long)g.taps * g.cin_chunks * KC * g.m_pad; }
+
+struct ImageIndex {
+  int tap, ci, row;
+};
+__device__ __forceinline__ ImageIndex image_decode(long i, int cin_pad, int m_pad) {
+  const int j = (int)(i & 7);
+  long rest = i >> 3;
+  const int row = (int)(rest % m_pad);
+  rest /= m_pad;
+  const int oct = (int)(rest % (cin_pad / 8));
+  return ImageIndex{(int)(rest / (cin_pad / 8)), oct * 8 + j, row};
+}
+
+// the A fragments (8 channels from channel 8 * oct of chunk `chunk`, one fragment per row) at tap `tap`
+__device__ __forceinline__ const bf16x8* image_rows(const bf16x8* w, int cin_chunks, int m_pad, int tap, int chunk, int oct) {
+  return w + ((size_t)(tap * cin_chunks + chunk) * (KC / 8) + oct) * m_pad;
+}
+
+// The exact 3-way split of an fp32 value (numerical definition: conv1d_split.hip, which is built without FMA
+// contraction for it)
+__device__ __forceinline__ void split3(float v, __bf16& hi, __bf16& mid, __bf16& lo) {
+  hi = (__bf16)v;
+  const float r = v - (float)hi;
+  mid = (__bf16)r;
+  lo = (__bf16)(r - (float)mid);
+}
+
+// One thread per element of ONE part image.  PARTS == 1 stores the rounded effective weight w * scale, PARTS == 3 its
+// split3 parts at i, total + i and 2 * total + i.  Instantiated in each translation unit, under that unit's flags.
+template <int PARTS>
+static __global__ __launch_bounds__(256) void mfma_conv_pack_kernel(const float* __restrict__ w,
+                                                                    const float* __restrict__ scale,
+                                                                    __bf16* __restrict__ wp, int c_in, int c_out, int kernel,
+                                                                    int taps, int cin_pad, int m, int m_pad, int phases,
+                                                                    int transposed) {
+  const long total = (long)taps * cin_pad * m_pad;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256L) {
+    const ImageIndex e = image_decode(i, cin_pad, m_pad);
+    float v = 0.f;
+    if (e.ci < c_in && e.row < m) {
+      if (transposed) {
+        const int co = e.row / phases, ph = e.row - co * phases;
+        const int kk = e.tap == 0 ? ph + phases : ph;
+        v = w[((long)e.ci * c_out + co) * kernel + kk];
+        if (scale) v *= scale[e.ci];
+      } else {
+        v = w[((long)e.row * c_in + e.ci) * kernel + e.tap];
+        if (scale) v *= scale[e.row];
+      }
+    }
+    if (PARTS == 1) {
+      wp[i] = (__bf16)v;
+    } else {
+      __bf16 hi, mid, lo;
+      split3(v, hi, mid, lo);
+      wp[i] = hi;
+      wp[total + i] = mid;
+      wp[2 * total + i] = lo;
+    }
+  }
+}
+
+template <int PARTS>
+static inline void mfma_conv_pack(const pwg_conv1d_desc* d, const MfmaConvGeom& g, const float* w, const float* scale,
+                                  void* w_packed, hipStream_t stream) {
+  int blocks = (int)((image_elems(g) + 255) / 256);
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(mfma_conv_pack_kernel<PARTS>, dim3(blocks), dim3(256), 0, stream, w, scale,
+                     static_cast<__bf16*>(w_packed), d->c_in, d->c_out, d->kernel, g.taps, g.cin_chunks * KC, g.m, g.m_pad,
+                     g.phases, d->transposed);
+}
+
+// ---- launch plan.  The vector staging deals its items = (group of 4 columns, channel octet) of a chunk over the 256
+// threads: window_items(nt) per thread, nt / 4 groups * 4 octets / 256, so a window of up to that many * 256 columns
+constexpr int window_items(int nt) { return nt >= 128 ? nt / 128 : 1; }
+
+struct MfmaConvPlan {
+  bool small, vec;  // half-size tiles; 16-B staging loads
+  int mt, nt;       // the launch's tile
+  int plane;        // bf16 elements of one LDS plane
+  dim3 grid;
+  size_t lds;
+  double flops, bytes;  // the ALGORITHMIC flops of the convolution, whatever the number of part products
+};
+
+// tile_mode: 0 = the small-grid rule decides, 1 = full-size tiles (where their planes fit LDS), 2 = half-size tiles
+static inline MfmaConvPlan mfma_conv_plan(const pwg_conv1d_desc* d, const MfmaConvGeom& g, int parts, int tile_mode,
+                                          const float* x, const float* add1, const float* add2) {
+  MfmaConvPlan p;
+  const int halo = (g.taps - 1) * g.dil;
+  // short inputs: a launch that would not give every CU a workgroup runs on half-size tiles (64 x 64 / 32 x 128; the
+  // weight image is the same).  The accumulation order of an output element does not depend on the tile.
+  const bool few = (long)ceil_div(g.nq, g.nt) * (g.m_pad / g.mt) * d->batch < kConvFillWorkgroups;
+  p.small = g.half_only || (tile_mode == 0 ? few : tile_mode == 2);
+  p.mt = p.small ? (g.mt > 32 ? 64 : 32) : g.mt;
+  p.nt = p.small ? g.nt / 2 : g.nt;
+  p.plane = plane_rows(p.nt, halo) * kConvRow;
+  p.grid = dim3(ceil_div(g.nq, p.nt), g.m_pad / p.mt, d->batch);
+  p.lds = conv_lds_bytes(parts, p.nt, halo);
+  // vector staging: 16-B loads along t need aligned rows, and the window must fit the per-thread register items
+  p.vec = d->t_in % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15u) == 0 &&
+          p.nt + halo + 3 <= window_items(p.nt) * 256;
+  const double out_elems = (double)d->batch * d->c_out * d->t_out;
+  const double in_elems = (double)d->batch * d->c_in * d->t_in;
+  p.flops = 2.0 * (double)d->batch * g.m * g.nq * g.taps * d->c_in;
+  p.bytes = 4.0 * (in_elems + out_elems * (1 + (add1 ? 1 : 0) + (add2 ? 1 : 0))) + 2.0 * parts * (double)image_elems(g);
+  return p;
+}
+
+// The tile ladder of a kernel family, handed over as K<TILE, WM, WN, WAVES_M>::fn.  TILE: MFMA shape (32: 32x32x16,
+// 16: 16x16x32; both are built at the same tiles).  A wave computes (WM * 32) rows x (WN * 32) columns; the 4 waves of a
+// workgroup are arranged WAVES_M x (4 / WAVES_M).
+template <template <int, int, int, int> class K, int TILE, class Args>
+static inline auto mfma_conv_tile_kernel(const MfmaConvPlan& p) -> void (*)(Args) {
+  if (p.small && p.mt == 32) return K<TILE, 1, 1, 1>::fn;  // 32 x 128
+  if (p.small) return K<TILE, 1, 1, 2>::fn;                // 64 x 64
+  if (p.mt == 32) return K<TILE, 1, 2, 1>::fn;             // 32 x 256
+  if (p.mt == 64) return K<TILE, 1, 2, 2>::fn;             // 64 x 128
+  return K<TILE, 2, 2, 2>::fn;                             // 128 x 128
+}
+template <template <int, int, int, int> class K, class Args>
+static inline void mfma_conv_launch(const MfmaConvPlan& p, int mfma_shape, const Args& a, hipStream_t stream) {
+  void (*kern)(Args) = mfma_shape == 32 ? mfma_conv_tile_kernel<K, 32, Args>(p) : mfma_conv_tile_kernel<K, 16, Args>(p);
+  hipLaunchKernelGGL(kern, p.grid, dim3(256), p.lds, stream, a);
+}
+
+// ---- the arguments both kernels' structs share
+struct MfmaConvArgs {
+  const float* x;
+  const bf16x8* w;
+  const float* bias;
+  const float* add1;
+  const float* add2;
+  float* y;
+  int c_in, c_out, t_in, t_out;
+  int m, m_pad, cin_chunks, taps, dil, x_off, nq;
+  int post_act;
+  float post_slope, out_mul, out_div;
+};
+
+static inline void mfma_conv_fill_args(MfmaConvArgs* a, const pwg_conv1d_desc* d, const MfmaConvGeom& g, const float* x,
+                                       const void* w_packed, const float* bias, const float* add1, const float* add2,
+                                       float* y) {
+  *a = MfmaConvArgs{x, static_cast<const bf16x8*>(w_packed), bias, add1, add2, y, d->c_in, d->c_out, d->t_in, d->t_out,
+                    g.m, g.m_pad, g.cin_chunks, g.taps, g.dil, g.x_off, g.nq, d->post_act, d->post_slope, d->out_mul,
+                    d->out_div};
+}
+
+// what a forward call checks after the geometry (the bf16 kernel has no tile_mode and passes 0)
+static inline int mfma_conv_check_forward(const char* name, const pwg_conv1d_desc* d, const void* x, const void* w_packed,
+                                          const void* y, int mfma_shape, int tile_mode) {
+  PWG_REQUIRE(x && w_packed && y, PWG_ERR_NULL, "%s: NULL pointer", name);
+  PWG_REQUIRE((reinterpret_cast<uintptr_t>(w_packed) & 15u) == 0, PWG_ERR_BAD_SHAPE,
+              "%s: the weight image must be 16-B aligned", name);
+  PWG_REQUIRE(mfma_shape == 16 || mfma_shape == 32, PWG_ERR_BAD_SHAPE, "%s: mfma_shape = %d (16 or 32)", name, mfma_shape);
+  PWG_REQUIRE(tile_mode >= 0 && tile_mode <= 2, PWG_ERR_BAD_SHAPE, "%s: tile_mode = %d (0, 1 or 2)", name, tile_mode);
+  PWG_REQUIRE(d->post_act >= PWG_ACT_NONE && d->post_act <= PWG_ACT_RELU, PWG_ERR_BAD_SHAPE, "%s: post_act = %d", name,
+              d->post_act);
+  return PWG_OK;
+}
+
+// ---- device side.  Coordinates of a thread in its workgroup's MT x NT tile, and of the tile's x window
+struct MfmaConvTile {
+  int tid, lane, wave, wave_m, wave_n;
+  int r, h;         // lane % TILE, lane / TILE: row / column inside an MFMA tile, lane group along the reduction
+  int q0, m0, b;    // first column, first row, batch item
+  int base;         // first staged input column (VEC: 16-B aligned, also when negative)
+  int sh;           // local column 0 at tap 0 is staged column sh (0 .. 3)
+  int wcols;        // staged columns
+  const float* xb;  // the item's input
+};
+template <int TILE, int MT, int NT, int WAVES_M, bool VEC>
+__device__ __forceinline__ MfmaConvTile mfma_conv_tile(const MfmaConvArgs& a) {
+  MfmaConvTile c;
+  c.tid = threadIdx.x, c.lane = c.tid & 63, c.wave = c.tid >> 6;
+  c.wave_m = c.wave % WAVES_M, c.wave_n = c.wave / WAVES_M;
+  c.r = c.lane & (TILE - 1), c.h = c.lane / TILE;
+  c.q0 = blockIdx.x * NT, c.m0 = blockIdx.y * MT, c.b = blockIdx.z;
+  const int start = c.q0 + a.x_off;  // input column of (local column 0, tap 0)
+  c.base = VEC ? (start & ~3) : start;
+  c.sh = start - c.base;
+  c.wcols = NT + (a.taps - 1) * a.dil + c.sh;
+  c.xb = a.x + (size_t)c.b * a.c_in * a.t_in;
+  return c;
+}
+
+}  // namespace pwg

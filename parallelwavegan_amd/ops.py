@@ -212,44 +212,67 @@ def conv1d_bf16_supported(desc):
     return bool(_lib.lib().pwg_conv1d_bf16_supported(ctypes.byref(desc)))
 
 
+def _zero_padded(desc):
+    """``desc`` with zero padding: a weight image does not depend on padding, which the MFMA kernels' geometry check
+    admits only as zero."""
+    if desc.pad_mode == PAD["zero"]:
+        return desc
+    desc = ConvDesc.from_buffer_copy(desc)
+    desc.pad_mode = PAD["zero"]
+    return desc
+
+
+def _pack_weight_mfma(kind, desc, w, scale):
+    """The packer of the ``kind`` ("bf16" / "split") MFMA kernel: one image layout, csrc/mfma_conv.h."""
+    _require_device(w, scale)
+    n = getattr(_lib.lib(), f"pwg_conv1d_{kind}_packed_weight_bytes")(ctypes.byref(desc))
+    if n == 0:
+        _lib.check(-1, f"conv1d_{kind}_packed_weight_bytes")
+    out = torch.empty(n, device=w.device, dtype=torch.uint8)
+    pack = getattr(_lib.lib(), f"pwg_conv1d_{kind}_pack_weight")
+    _lib.check(pack(ctypes.byref(desc), _ptr(w), _ptr(scale), _ptr(out), _stream()), f"conv1d_{kind}_pack_weight")
+    return out
+
+
+def _conv1d_forward_mfma(kind, desc, image_desc, x, w_packed, bias, add1, add2, out, cfg):
+    """The forward of the ``kind`` ("bf16" / "split") MFMA kernel.  ``image_desc``: the descriptor the image was packed
+    through; ``cfg``: the tuning integers of ``pwg_conv1d_<kind>_forward_cfg``, None for the default launch."""
+    name = f"conv1d_forward_{kind}"
+    _require_device(x, bias, add1, add2, out)
+    if not w_packed.is_cuda or w_packed.dtype != torch.uint8:
+        raise RuntimeError(f"{name}: w_packed must be the device image of pack_weight_{kind}")
+    if out is None:
+        out = torch.empty((desc.batch, desc.c_out, desc.t_out), device=x.device, dtype=torch.float32)
+    assert x.numel() == desc.batch * desc.c_in * desc.t_in, (tuple(x.shape), desc.batch, desc.c_in, desc.t_in)
+    assert out.numel() == desc.batch * desc.c_out * desc.t_out
+    image_bytes = getattr(_lib.lib(), f"pwg_conv1d_{kind}_packed_weight_bytes")(ctypes.byref(image_desc))
+    if image_bytes == 0:  # the kernel refuses the descriptor: report its reason, not a mismatch
+        _lib.check(-1, f"conv1d_{kind}_packed_weight_bytes")
+    assert w_packed.numel() == image_bytes, f"{name}: w_packed is not this layer's {kind} image"
+    for t in (add1, add2):
+        assert t is None or t.numel() == out.numel()
+    args = (ctypes.byref(desc), _ptr(x), _ptr(w_packed), _ptr(bias), _ptr(add1), _ptr(add2), _ptr(out))
+    if cfg is None:
+        rc = getattr(_lib.lib(), f"pwg_conv1d_{kind}_forward")(*args, None, 0, _stream())
+    else:
+        rc = getattr(_lib.lib(), f"pwg_conv1d_{kind}_forward_cfg")(*args, *cfg, _stream())
+    _lib.check(rc, name)
+    return out
+
+
 def pack_weight_bf16(desc, w, scale=None):
     """torch-layout fp32 weight (+ optional weight_norm row scale) -> bf16 MFMA weight image (an opaque byte tensor);
     the effective weight ``w * scale`` is rounded to bf16 here, once.  The image does not depend on padding, which the
     packer's geometry check admits only as zero: a reflect- / replicate-padded layer (the causal MelGAN layers, for
     the bf16 stream kernel) is packed through a descriptor of the same geometry with zero padding."""
-    _require_device(w, scale)
-    if desc.pad_mode != PAD["zero"]:
-        desc = ConvDesc.from_buffer_copy(desc)
-        desc.pad_mode = PAD["zero"]
-    n = _lib.lib().pwg_conv1d_bf16_packed_weight_bytes(ctypes.byref(desc))
-    if n == 0:
-        _lib.check(-1, "conv1d_bf16_packed_weight_bytes")
-    out = torch.empty(n, device=w.device, dtype=torch.uint8)
-    _lib.check(_lib.lib().pwg_conv1d_bf16_pack_weight(ctypes.byref(desc), _ptr(w), _ptr(scale), _ptr(out), _stream()),
-               "conv1d_bf16_pack_weight")
-    return out
+    return _pack_weight_mfma("bf16", _zero_padded(desc), w, scale)
 
 
 def conv1d_forward_bf16(desc, x, w_packed, bias=None, add1=None, add2=None, out=None, mfma_shape=None):
     """Fused convolution with bf16 operands and fp32 accumulation / epilogue (inference only).  ``mfma_shape``
     (tuning): 32 or 16 selects the MFMA instruction explicitly."""
-    _require_device(x, bias, add1, add2, out)
-    if not w_packed.is_cuda or w_packed.dtype != torch.uint8:
-        raise RuntimeError("conv1d_forward_bf16: w_packed must be the device image of pack_weight_bf16")
-    if out is None:
-        out = torch.empty((desc.batch, desc.c_out, desc.t_out), device=x.device, dtype=torch.float32)
-    assert x.numel() == desc.batch * desc.c_in * desc.t_in, (tuple(x.shape), desc.batch, desc.c_in, desc.t_in)
-    assert out.numel() == desc.batch * desc.c_out * desc.t_out
-    for t in (add1, add2):
-        assert t is None or t.numel() == out.numel()
-    if mfma_shape is None:
-        rc = _lib.lib().pwg_conv1d_bf16_forward(ctypes.byref(desc), _ptr(x), _ptr(w_packed), _ptr(bias), _ptr(add1),
-                                                _ptr(add2), _ptr(out), None, 0, _stream())
-    else:
-        rc = _lib.lib().pwg_conv1d_bf16_forward_cfg(ctypes.byref(desc), _ptr(x), _ptr(w_packed), _ptr(bias), _ptr(add1),
-                                                    _ptr(add2), _ptr(out), int(mfma_shape), _stream())
-    _lib.check(rc, "conv1d_forward_bf16")
-    return out
+    return _conv1d_forward_mfma("bf16", desc, _zero_padded(desc), x, w_packed, bias, add1, add2, out,
+                                None if mfma_shape is None else (int(mfma_shape),))
 
 
 def conv1d_split_supported(desc):
@@ -261,40 +284,15 @@ def conv1d_split_supported(desc):
 def pack_weight_split(desc, w, scale=None):
     """torch-layout fp32 weight (+ optional weight_norm row scale) -> the three bf16 MFMA weight images of the
     split-operand kernel (an opaque byte tensor); the effective weight ``w * scale`` is split here, once."""
-    _require_device(w, scale)
-    n = _lib.lib().pwg_conv1d_split_packed_weight_bytes(ctypes.byref(desc))
-    if n == 0:
-        _lib.check(-1, "conv1d_split_packed_weight_bytes")
-    out = torch.empty(n, device=w.device, dtype=torch.uint8)
-    _lib.check(_lib.lib().pwg_conv1d_split_pack_weight(ctypes.byref(desc), _ptr(w), _ptr(scale), _ptr(out), _stream()),
-               "conv1d_split_pack_weight")
-    return out
+    return _pack_weight_mfma("split", desc, w, scale)
 
 
 def conv1d_forward_split(desc, x, w_packed, bias=None, add1=None, add2=None, out=None, mfma_shape=None, tile_mode=0):
     """Fused fp32 convolution computed on the bf16 MFMA from 3-way split operands (inference only).
     ``mfma_shape`` (tuning): 32 or 16 selects the MFMA instruction; ``tile_mode`` (tests): 1 = full-size, 2 = half-size
     tiles instead of the small-grid rule."""
-    _require_device(x, bias, add1, add2, out)
-    if not w_packed.is_cuda or w_packed.dtype != torch.uint8:
-        raise RuntimeError("conv1d_forward_split: w_packed must be the device image of pack_weight_split")
-    if out is None:
-        out = torch.empty((desc.batch, desc.c_out, desc.t_out), device=x.device, dtype=torch.float32)
-    assert x.numel() == desc.batch * desc.c_in * desc.t_in, (tuple(x.shape), desc.batch, desc.c_in, desc.t_in)
-    assert out.numel() == desc.batch * desc.c_out * desc.t_out
-    assert w_packed.numel() == _lib.lib().pwg_conv1d_split_packed_weight_bytes(ctypes.byref(desc)), \
-        "conv1d_forward_split: w_packed is not this layer's split image"
-    for t in (add1, add2):
-        assert t is None or t.numel() == out.numel()
-    if mfma_shape is None and not tile_mode:
-        rc = _lib.lib().pwg_conv1d_split_forward(ctypes.byref(desc), _ptr(x), _ptr(w_packed), _ptr(bias), _ptr(add1),
-                                                 _ptr(add2), _ptr(out), None, 0, _stream())
-    else:
-        rc = _lib.lib().pwg_conv1d_split_forward_cfg(ctypes.byref(desc), _ptr(x), _ptr(w_packed), _ptr(bias),
-                                                     _ptr(add1), _ptr(add2), _ptr(out), int(mfma_shape or 16),
-                                                     int(tile_mode), _stream())
-    _lib.check(rc, "conv1d_forward_split")
-    return out
+    cfg = None if mfma_shape is None and not tile_mode else (int(mfma_shape or 16), int(tile_mode))
+    return _conv1d_forward_mfma("split", desc, desc, x, w_packed, bias, add1, add2, out, cfg)
 
 
 def conv1d_stream_supported(desc):
@@ -349,11 +347,7 @@ def conv1d_stream_forward_bf16(desc, x, hist_in, hist_out, w_packed_bf16, bias=N
     if not w_packed_bf16.is_cuda or w_packed_bf16.dtype != torch.uint8:
         raise RuntimeError("conv1d_stream_forward_bf16: w_packed_bf16 must be the device image of pack_weight_bf16")
     out = _conv1d_stream_out(desc, x, hist_in, hist_out, add1, add2, out)
-    zdesc = desc
-    if desc.pad_mode != PAD["zero"]:
-        zdesc = ConvDesc.from_buffer_copy(desc)
-        zdesc.pad_mode = PAD["zero"]
-    assert w_packed_bf16.numel() == _lib.lib().pwg_conv1d_bf16_packed_weight_bytes(ctypes.byref(zdesc)), \
+    assert w_packed_bf16.numel() == _lib.lib().pwg_conv1d_bf16_packed_weight_bytes(ctypes.byref(_zero_padded(desc))), \
         "conv1d_stream_forward_bf16: w_packed_bf16 is not this layer's bf16 image"
     _lib.check(_lib.lib().pwg_conv1d_stream_bf16_forward(ctypes.byref(desc), _ptr(x), _ptr(hist_in), _ptr(hist_out),
                                                          _ptr(w_packed_bf16), _ptr(bias), _ptr(add1), _ptr(add2),

@@ -224,3 +224,17 @@ def test_cancellation_needs_three_parts(shape, device):
     print(f"2-part emulation {err2:.3e}, split kernel {r['err']:.3e}, fp32 kernel {r['err_fp32']:.3e}")
     assert err2 > RTOL, "the case does not separate two parts from three"
     assert r["err"] <= RTOL
+
+
+@pytest.mark.parametrize("scaled", [False, True], ids=["plain", "weight_norm"])
+@pytest.mark.parametrize("cin,cout,k", [(24, 136, 3), (33, 24, 5)], ids=["c24_m136_k3", "c33_m24_k5"])
+def test_first_part_is_the_bf16_image(cin, cout, k, scaled, device):
+    """One layout, one owner: the hi part of the split image, bf16_rne(w * scale), is the bf16 kernel's image byte for
+    byte (padded rows at the 128- and the 32-row tile, a partial and a one-channel-tail channel chunk)."""
+    g = torch.Generator().manual_seed(cin * 1000 + cout * 10 + k)
+    w = torch.randn(cout, cin, k, generator=g).to(device)
+    scale = (torch.rand(cout, generator=g) + 0.5).to(device) if scaled else None
+    desc = ops.make_conv_desc(1, cin, cout, 64, 64, k, pad_left=(k - 1) // 2)
+    image, parts = ops.pack_weight_bf16(desc, w, scale), ops.pack_weight_split(desc, w, scale)
+    assert parts.numel() == 3 * image.numel()
+    assert torch.equal(parts[:image.numel()], image)

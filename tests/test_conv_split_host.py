@@ -79,6 +79,13 @@ def test_supported_declines_what_is_out_of_scope():
     assert _lib.lib().pwg_conv1d_split_packed_weight_bytes(_desc(groups=2)) == 0
     d = _desc(c_in=40, c_out=72)  # 2 chunks of 32 channels, 128 padded rows, 3 parts of bf16
     assert _lib.lib().pwg_conv1d_split_packed_weight_bytes(d) == 3 * 7 * 64 * 128 * 2
+    # one image layout for both MFMA kernels: the split image is three bf16 images
+    for c_out in (24, 64, 136, 512):
+        for c_in in (24, 33, 80):
+            d = _desc(c_in=c_in, c_out=c_out)
+            assert ops.conv1d_bf16_supported(d) and ops.conv1d_split_supported(d)
+            assert (_lib.lib().pwg_conv1d_split_packed_weight_bytes(d)
+                    == 3 * _lib.lib().pwg_conv1d_bf16_packed_weight_bytes(d)), (c_in, c_out)
 
 
 def test_admission_predicate(monkeypatch):

@@ -1,11 +1,14 @@
-"""SHA-256 of the output bytes of the split-operand kernel (csrc/conv1d_split.hip) on a fixed case list, as JSON on
-stdout: what a change of the kernel that must not change a bit is compared by (run this file on both checkouts and
-compare the two objects).  GPU box only.  Every input is seeded on the CPU.
-The cases: those of tests/test_conv_split_gpu.py (default launch and 32x32x16); those of
-tests/test_conv_split_pipeline_gpu.py, whose shape / variant tables live here so that this file also runs on a checkout
-that has no such test (default launch, tile_mode 1 / 2, 32x32x16, and the launches with one operand 4 bytes off a 16-byte
-boundary); and the four admitted classes (128 / 256 channels, k = 7 / 11) at one utterance of 100 frames with dilations
-1 and 5, at tile_mode 0 / 1 / 2 and both MFMA shapes."""
+"""SHA-256 of the output bytes of the MFMA convolutions (csrc/conv1d_split.hip, csrc/conv1d_bf16.hip and, for the bf16
+weight image it reads, csrc/conv1d_stream_bf16.hip) on a fixed case list, as JSON on stdout: what a change of the
+kernels that must not change a bit is compared by (run this file on both checkouts and compare the two objects).  GPU
+box only.  Every input is seeded on the CPU.
+The split cases (the packed images are hashed next to the outputs): those of tests/test_conv_split_gpu.py (default
+launch and 32x32x16); those of tests/test_conv_split_pipeline_gpu.py, whose shape / variant tables live here so that this
+file also runs on a checkout that has no such test (default launch, tile_mode 1 / 2, 32x32x16, and the launches with one
+operand 4 bytes off a 16-byte boundary); and the four admitted classes (128 / 256 channels, k = 7 / 11) at one utterance
+of 100 frames with dilations 1 and 5, at tile_mode 0 / 1 / 2 and both MFMA shapes.
+The bf16 cases: every case of tests/test_conv_bf16_gpu.py::ALL, the packed image and the output at both MFMA shapes;
+and pushes through the bf16 stream kernel on layers whose rows are padded in the image (y and hist_out)."""
 import hashlib
 import json
 import os
@@ -116,6 +119,7 @@ def hash_existing(out, dev):
                                   pre_act=v["pre_act"], pre_slope=v["pre_slope"], post_act=v["post_act"],
                                   out_div=v["out_div"])
         x, ws = t["x"].to(dev), ops.pack_weight_split(desc, t["w"].to(dev))
+        out[f"split_gpu/{shape}-{variant}-{kind}/image"] = sha(ws)
         bias, add1, add2 = (t[n].to(dev) if v[n] else None for n in ("bias", "add1", "add2"))
         for shp in (16, 32):
             y = ops.conv1d_forward_split(desc, x, ws, bias, add1, add2, mfma_shape=shp)
@@ -131,6 +135,7 @@ def hash_pipeline(out, dev):
         x, ws = t["x"].to(dev), ops.pack_weight_split(desc, t["w"].to(dev))
         bias, add1, add2 = (t[n].to(dev) if v[n] else None for n in ("bias", "add1", "add2"))
         name = f"pipeline/{shape}-{variant}-{kind}"
+        out[f"{name}/image"] = sha(ws)
         for mode in (0, 1, 2):
             out[f"{name}/tile{mode}"] = sha(ops.conv1d_forward_split(desc, x, ws, bias, add1, add2, tile_mode=mode))
         out[f"{name}/mfma32"] = sha(ops.conv1d_forward_split(desc, x, ws, bias, add1, add2, mfma_shape=32))
@@ -162,11 +167,77 @@ def hash_admitted(out, dev):
                 desc = ops.make_conv_desc(1, ch, ch, T, T, k, dilation=d, pad_left=(k - 1) // 2 * d,
                                           pre_act="leaky_relu", pre_slope=0.1)
                 ws = ops.pack_weight_split(desc, w.to(dev))
+                out[f"admitted/c{ch}_k{k}_d{d}_T{T}/image"] = sha(ws)
                 x, bias, add1 = x.to(dev), bias.to(dev), add1.to(dev)
                 for mode in (0, 1, 2):
                     for shp in (16, 32):
                         y = ops.conv1d_forward_split(desc, x, ws, bias, add1, tile_mode=mode, mfma_shape=shp)
                         out[f"admitted/c{ch}_k{k}_d{d}_T{T}/tile{mode}/mfma{shp}"] = sha(y)
+
+
+def hash_bf16(out, dev):
+    from parallelwavegan_amd import ops
+    from tests import test_conv_bf16_gpu as ex
+
+    for c in ex.ALL:
+        g = torch.Generator().manual_seed(c["B"] * 7919 + c["Cin"] * 31 + c["K"] * 7 + c["T"])
+        B, cin, cout, T, K, s, d = c["B"], c["Cin"], c["Cout"], c["T"], c["K"], c["stride"], c["dil"]
+        x = torch.randn(B, cin, T, generator=g)
+        if c["transposed"]:
+            w = torch.randn(cin, cout, K, generator=g) / (cin * 2) ** 0.5
+            pad = s // 2 + s % 2
+            t_out = ops.conv_transpose_out_length(T, K, s, pad, s % 2)
+        else:
+            w = torch.randn(cout, cin, K, generator=g) / (cin * K) ** 0.5
+            pad, t_out = (K - 1) // 2 * d, T
+        bias, add1, add2 = torch.randn(cout, generator=g), torch.randn(B, cout, t_out, generator=g), \
+            torch.randn(B, cout, t_out, generator=g)
+        bias, add1, add2 = (t.to(dev) if c[n] else None for n, t in (("bias", bias), ("add1", add1), ("add2", add2)))
+        desc = ops.make_conv_desc(B, cin, cout, T, t_out, K, stride=s, dilation=d, pad_left=pad,
+                                  transposed=c["transposed"], pre_act=c["pre"], pre_slope=c["slope"] if c["pre"] else 0.0,
+                                  post_act=c["post"], post_slope=c["post_slope"], out_mul=c["mul"], out_div=c["div"])
+        wp = ops.pack_weight_bf16(desc, w.to(dev))
+        out[f"bf16/{ex._id(c)}/image"] = sha(wp)
+        for shp in (16, 32):
+            y = ops.conv1d_forward_bf16(desc, x.to(dev), wp, bias, add1, add2, mfma_shape=shp)
+            out[f"bf16/{ex._id(c)}/mfma{shp}"] = sha(y)
+
+
+# name -> c_in, c_out, k, dilation, transposed stride (0: Conv1d), start-of-stream padding, columns per push: the rows
+# of every image are padded (c_out 33 / 40; 33 * 4 phases), c_in 20 is a partial chunk, 160 a block and a chunk
+STREAM_CASES = {
+    "c20_o40_k7_zero": (20, 40, 7, 1, 0, "zero", (5, 17, 33)),
+    "c160_o33_k5_d3_zero": (160, 33, 5, 3, 0, "zero", (17, 5, 33)),
+    "c160_o40_k7_replicate": (160, 40, 7, 1, 0, "replicate", (33, 5, 17)),
+    "t_c20_o33_k8_s4_replicate": (20, 33, 8, 1, 4, "replicate", (5, 17, 33)),
+}
+
+
+def hash_stream_bf16(out, dev):
+    from parallelwavegan_amd import ops
+
+    for name, (cin, cout, k, d, s, mode, pushes) in STREAM_CASES.items():
+        g = torch.Generator().manual_seed(sum(map(ord, name)) * 131 + cin)
+        B, H = 2, 1 if s else (k - 1) * d
+        w = torch.randn((cin, cout, k) if s else (cout, cin, k), generator=g) / (cin * k) ** 0.5
+        bias = torch.randn(cout, generator=g).to(dev)
+        wp, hist = None, None
+        for i, n in enumerate(pushes):
+            x = torch.randn(B, cin, n, generator=g).to(dev)
+            if s:
+                desc = ops.make_conv_desc(B, cin, cout, n, n * s, k, s, 1, s, transposed=True, pad_mode=mode,
+                                          pre_act="leaky_relu", pre_slope=0.1)
+            else:
+                desc = ops.make_conv_desc(B, cin, cout, n, n, k, 1, d, H, pad_mode=mode, pre_act="leaky_relu",
+                                          pre_slope=0.1)
+            if wp is None:
+                wp = ops.pack_weight_bf16(desc, w.to(dev))
+                out[f"stream_bf16/{name}/image"] = sha(wp)
+            hist_out = torch.full((B, cin, H), float("nan"), device=dev)
+            y = ops.conv1d_stream_forward_bf16(desc, x, hist, hist_out, wp, bias)
+            out[f"stream_bf16/{name}/push{i}_n{n}/y"] = sha(y)
+            out[f"stream_bf16/{name}/push{i}_n{n}/hist_out"] = sha(hist_out)
+            hist = hist_out
 
 
 if __name__ == "__main__":
@@ -175,4 +246,6 @@ if __name__ == "__main__":
     hash_existing(hashes, dev)
     hash_pipeline(hashes, dev)
     hash_admitted(hashes, dev)
+    hash_bf16(hashes, dev)
+    hash_stream_bf16(hashes, dev)
     print(json.dumps({"hashes": len(hashes), "sha256": hashes}, indent=1, sort_keys=True))
