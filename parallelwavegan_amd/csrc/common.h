@@ -82,6 +82,7 @@ int gconv_backward_data(const pwg_conv1d_desc* d, const float* dy, const float* 
                         float* dx, hipStream_t stream);
 bool gconv_wgrad_applicable(const pwg_conv1d_desc* d);
 size_t gconv_wgrad_workspace_floats(const pwg_conv1d_desc* d);
+size_t gconv_wgrad_sum_offset(const pwg_conv1d_desc* d);  // floats of the slabs: the summed gradient sits behind them
 int gconv_backward_weight(const pwg_conv1d_desc* d, const float* x, const float* dy, float* dw, float* db, float* workspace,
                           size_t ws_floats, hipStream_t stream);
 

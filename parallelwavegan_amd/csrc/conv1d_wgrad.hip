@@ -1015,7 +1015,8 @@ static WgPlan wgrad_plan(int co_g, int ci_g, int groups, int k, int stride, int 
   return p;
 }
 
-// ---- host dispatch, decided once: the launchers below and pwg_conv1d_backward_weight_plan read the same functions ----
+// ---- host dispatch: wgrad_describe decides a call once; the workspace queries, the launcher and
+// pwg_conv1d_backward_weight_plan read its answer ----
 // How the reduction slabs become the gradients (the values are the ABI of pwg_conv1d_backward_weight_plan, out[1]).
 enum WgFinisher {
   WG_FIN_DIRECT = 0,         // one slice, no weight norm: the kernel stores the gradients itself (torch layout)
@@ -1077,15 +1078,43 @@ static WgVariant wgrad_variant(const WgPlan& p, int width, int stride, bool act)
   return v;
 }
 
-// Sum `splits` tap-major slabs (+ fused bias row) of a layer with `n0` rows, `ci_g` input channels per group and `k`
-// taps into the torch-layout gradients; with `wn`, through the weight-norm backward.  (Shared by the MFMA kernel's
-// launcher and the single-input-channel path.)
-static int finish_wgrad_slabs(float* workspace, int splits, long slab_elems, long slab_stride, int n0, int ci_g, int k,
-                              float* dw_out, float* db_out, const WnFinish* wn, hipStream_t stream) {
+using WgKernel = void (*)(WgArgs);
+
+// The kernel family of a (flattened) descriptor, in the launcher's order of preference (the values are the ABI of
+// pwg_conv1d_backward_weight_plan, out[0]).
+enum WgPath { WG_PATH_MFMA = 0, WG_PATH_GCONV = 1, WG_PATH_SMALL_CIN = 2, WG_PATH_K1 = 3 };
+
+// Everything decided before a launch, by wgrad_describe and nowhere else (`d` flattened).
+struct WgCall {
+  WgPath path;
+  // roles.  G: the operand whose channels are dW's dim 0 (dy), X: the one the taps shift over (x); ConvTranspose1d:
+  // dW[ci][co][k] = sum x[ci][q] * dy[co][q*s - p + k], the same kernels with the two `swapped`
+  bool swapped;
+  int co_g, ci_g;           // G / X channels per group
+  int n_cols, x_len;        // samples per channel row of G (the reduction columns per item) / of X
+  unsigned g_bytes, x_bytes;
+  float slope_g, slope_x;   // branch-free operand activation max(v, slope * v): 1 = none, 0 = ReLU
+  // slabs: `nslabs` reduction slices of n0 rows x ci_g x k (+ the bias row, n0 floats, when it rides along), `slab_stride`
+  // floats apart.  (gconv.hip lays out and sums its own: nslabs = 0.)
+  int n0, k, nslabs;
+  long slab_elems, slab_stride;
+  WgFinisher fin;
+  size_t ws_floats;         // what the entry point asks for
+  // WG_PATH_MFMA only
+  WgPlan plan;
+  WgVariant variant;
+  WgKernel kern;
+};
+
+// Sum the tap-major slabs (+ fused bias row) of `c` into the torch-layout gradients; with `wn`, through the weight-norm
+// backward.  (Shared by the MFMA kernel, the single-input-channel and the 1 x 1 paths.)
+static int finish_wgrad_slabs(const WgCall& c, float* workspace, float* dw_out, float* db_out, const WnFinish* wn,
+                              hipStream_t stream) {
+  const int splits = c.nslabs, n0 = c.n0, ci_g = c.ci_g, k = c.k;
+  const long slab_elems = c.slab_elems, slab_stride = c.slab_stride;
   const long plane = (long)n0 * ci_g;  // elements per tap of a tap-major slab
   const int inner = ci_g * k;
-  const WgFinisher fin = wgrad_finisher(splits, wn != nullptr, n0, inner);
-  if (fin == WG_FIN_WN_TWO_KERNEL) {
+  if (c.fin == WG_FIN_WN_TWO_KERNEL) {
     float* dw_tmp = workspace + (size_t)splits * slab_stride;
     {
       ProfScope prof(stream, "reduce_slabs_kernel", 0, 4.0 * slab_stride * (splits + 1));
@@ -1095,10 +1124,10 @@ static int finish_wgrad_slabs(float* workspace, int splits, long slab_elems, lon
     }
     return pwg_weight_norm_backward(dw_tmp, wn->v, wn->g, wn->dv, wn->dg, n0, inner, stream);
   }
-  if (fin == WG_FIN_WN_FUSED || fin == WG_FIN_WN_FUSED_WIDE) {
+  if (c.fin == WG_FIN_WN_FUSED || c.fin == WG_FIN_WN_FUSED_WIDE) {
     const int nbias = db_out ? n0 : 0;
     ProfScope prof(stream, "reduce_slabs_wn_kernel", 0, 4.0 * (slab_stride * (double)splits + 3.0 * slab_elems));
-    if (fin == WG_FIN_WN_FUSED_WIDE)
+    if (c.fin == WG_FIN_WN_FUSED_WIDE)
       hipLaunchKernelGGL(reduce_slabs_wn_kernel<true>, dim3(n0 + ceil_div(nbias, 256)), dim3(256),
                          (size_t)9 * inner * sizeof(float), stream, (const float*)workspace, slab_stride, splits,
                          slab_elems, wn->v, wn->g, wn->dv, wn->dg, db_out, n0, inner, nbias, ci_g, k);
@@ -1109,9 +1138,9 @@ static int finish_wgrad_slabs(float* workspace, int splits, long slab_elems, lon
     PWG_CHECK_LAUNCH("reduce_slabs_wn");
     return PWG_OK;
   }
-  if (fin != WG_FIN_DIRECT) {
+  if (c.fin != WG_FIN_DIRECT) {
     ProfScope prof(stream, "reduce_slabs_kernel", 0, 4.0 * slab_stride * (splits + 1));
-    if (fin == WG_FIN_SLABS_WIDE) {
+    if (c.fin == WG_FIN_SLABS_WIDE) {
       hipLaunchKernelGGL(reduce_slabs_wide_kernel, dim3((unsigned)((slab_stride + 31) / 32)), dim3(256), 0, stream,
                          workspace, dw_out, db_out, slab_elems, slab_stride, splits, plane, k);
     } else {
@@ -1125,102 +1154,97 @@ static int finish_wgrad_slabs(float* workspace, int splits, long slab_elems, lon
   return PWG_OK;
 }
 
-template <int TG, bool SMALL, int TT, bool WIN, int MODE, bool ACT23 = true, int STRIDE3 = 0>
-static int launch_wgrad_mode(WgArgs a, const WgPlan& p, float* dw_out, float* workspace, size_t ws_floats,
-                        hipStream_t stream, double flops, double bytes, const WnFinish* wn) {
-  a.xs_stride = p.xs_stride;
-  a.chunks_per_item = p.chunks_per_item;
-  a.chunks_total = p.chunks_total;
-  const size_t lds = p.lds;
-  PWG_REQUIRE(lds <= 160 * 1024, PWG_ERR_UNSUPPORTED, "conv1d_backward_weight: tile needs %zu B of LDS", lds);
-  void (*kern)(WgArgs) = conv1d_wgrad_kernel<TG, WIN, SMALL, TT, MODE, ACT23, STRIDE3>;
-  if (lds > 64 * 1024 && !lds_limit_is_set(reinterpret_cast<const void*>(kern), lds)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    PWG_REQUIRE(e == hipSuccess, PWG_ERR_LAUNCH, "conv1d_backward_weight: cannot raise LDS limit: %s",
-                hipGetErrorString(e));
-  }
-  a.chunks_per_block = ceil_div(a.chunks_total, p.splits);
-  a.slab_elems = (long)a.co_g * a.groups * a.ci_g * a.k;
-  float* db_out = a.db;  // non-null: the bias gradient rides along (row sums of the G tiles)
-  a.slab_stride = a.slab_elems + (db_out ? (long)a.co_g * a.groups : 0);
-  a.tap_major = 0;
-  if (wgrad_finisher(p.splits, wn != nullptr, a.co_g * a.groups, a.ci_g * a.k) == WG_FIN_DIRECT) {
-    a.dw = dw_out;  // single slice: write the gradients directly (torch layout)
-  } else {
-    a.tap_major = 1;
-    PWG_REQUIRE(workspace && ws_floats >= (size_t)p.splits * a.slab_stride, PWG_ERR_WORKSPACE,
-                "conv1d_backward_weight: workspace of %zu floats needed, %zu given",
-                (size_t)p.splits * a.slab_stride, ws_floats);
-    a.dw = workspace;
-    if (db_out) a.db = workspace + a.slab_elems;
-  }
-  dim3 grid(p.splits, p.tiles, p.tap_groups);
-  maybe_poison_lds(stream);
-  {
-    ProfScope prof(stream,
-                   prof_shape_name("conv1d_wgrad_kernel", "B%d Co%d Ci%d k%d s%d d%d g%d W%d cols%d splits%d tiles%d tg%d small%d win%d tt%d rows%d",
-                                   a.batch, a.co_g * a.groups, a.ci_g * a.groups, a.k, a.stride, a.dil, a.groups, a.width,
-                                   a.n_cols, p.splits, p.tiles, p.tg, (int)p.small, (int)p.win, p.tt, 2 * p.rows_half),
-                   flops, bytes);
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, a);
-  }
-  PWG_CHECK_LAUNCH("conv1d_backward_weight");
-  return finish_wgrad_slabs(workspace, p.splits, a.slab_elems, a.slab_stride, a.co_g * a.groups, a.ci_g, a.k, dw_out,
-                            db_out, wn, stream);
+// ---- (plan, variant) -> kernel: wgrad_kernel and its helpers name every instantiation of conv1d_wgrad_kernel there is;
+// a combination without one is nullptr (wgrad_describe refuses it), never a neighbour ----
+// (hipcc lays the kernels out in the order the host code first names them, and their bytes depend on the layout through
+// PC-relative calls: reordering the map changes every kernel's hash, not its code -- profiles/refactor_wgrad_dispatch.txt)
+// MODE 4 (row-aligned (k,1) chunks, TT = 64): kept apart so that the 64 x 64 tile gets no other TT = 64 instantiation
+static WgKernel wgrad_kernel_rows(const WgPlan& p, const WgVariant& v) {
+  static const WgKernel small[4][2] = {  // [tg - 1][activating, plain]
+      {conv1d_wgrad_kernel<1, false, true, 64, 4, true>, conv1d_wgrad_kernel<1, false, true, 64, 4, false>},
+      {conv1d_wgrad_kernel<2, false, true, 64, 4, true>, conv1d_wgrad_kernel<2, false, true, 64, 4, false>},
+      {conv1d_wgrad_kernel<3, false, true, 64, 4, true>, conv1d_wgrad_kernel<3, false, true, 64, 4, false>},
+      {conv1d_wgrad_kernel<4, false, true, 64, 4, true>, conv1d_wgrad_kernel<4, false, true, 64, 4, false>}};
+  static const WgKernel big[7][2] = {
+      {conv1d_wgrad_kernel<1, false, false, 64, 4, true>, conv1d_wgrad_kernel<1, false, false, 64, 4, false>},
+      {conv1d_wgrad_kernel<2, false, false, 64, 4, true>, conv1d_wgrad_kernel<2, false, false, 64, 4, false>},
+      {conv1d_wgrad_kernel<3, false, false, 64, 4, true>, conv1d_wgrad_kernel<3, false, false, 64, 4, false>},
+      {conv1d_wgrad_kernel<4, false, false, 64, 4, true>, conv1d_wgrad_kernel<4, false, false, 64, 4, false>},
+      {conv1d_wgrad_kernel<5, false, false, 64, 4, true>, conv1d_wgrad_kernel<5, false, false, 64, 4, false>},
+      {conv1d_wgrad_kernel<6, false, false, 64, 4, true>, conv1d_wgrad_kernel<6, false, false, 64, 4, false>},
+      {conv1d_wgrad_kernel<7, false, false, 64, 4, true>, conv1d_wgrad_kernel<7, false, false, 64, 4, false>}};
+  if (p.tt != 64 || p.win || v.stride_ct != 0 || p.tg < 1 || p.tg > (p.small ? 4 : 7)) return nullptr;
+  return (p.small ? small : big)[p.tg - 1][v.act ? 0 : 1];
 }
 
+// modes 0 - 3 of one tile shape, tap count and chunk length: 15 instantiations
 template <int TG, bool SMALL, int TT>
-static int launch_wgrad(WgArgs a, const WgPlan& p, const WgVariant& v, float* dw_out, float* workspace, size_t ws_floats,
-                        hipStream_t stream, double flops, double bytes, const WnFinish* wn) {
-#define WG_GO(WINV, MODEV) \
-  return launch_wgrad_mode<TG, SMALL, TT, WINV, MODEV>(a, p, dw_out, workspace, ws_floats, stream, flops, bytes, wn)
-#define WG_GO23(MODEV, ACTV, SV) \
-  return launch_wgrad_mode<TG, SMALL, TT, false, MODEV, ACTV, SV>(a, p, dw_out, workspace, ws_floats, stream, flops, bytes, wn)
-  switch (v.mode) {  // (wgrad_variant chose; only the instantiations it can name exist)
-    case 2:
-      if (v.act) WG_GO23(2, true, 0);
-      WG_GO23(2, false, 0);
-    case 3:
+static WgKernel wgrad_kernel_chunked(bool win, const WgVariant& v) {
+  if (win && v.mode != 0 && v.mode != 1) return nullptr;  // (per-tap windows need width == 1 and stride == 1)
+  switch (v.mode) {
+    case 2:  // (k,1), per-lane row wrap
+      if (v.stride_ct != 0) return nullptr;
+      return v.act ? conv1d_wgrad_kernel<TG, false, SMALL, TT, 2, true> : conv1d_wgrad_kernel<TG, false, SMALL, TT, 2, false>;
+    case 3:  // strided, width 1: the recipes' strides at compile time (no activated stride 3), any stride at run time
       if (!v.act) {
         switch (v.stride_ct) {
-          case 2: WG_GO23(3, false, 2);
-          case 3: WG_GO23(3, false, 3);
-          case 4: WG_GO23(3, false, 4);
-          case 8: WG_GO23(3, false, 8);
-          default: WG_GO23(3, false, 0);
+          case 2: return conv1d_wgrad_kernel<TG, false, SMALL, TT, 3, false, 2>;
+          case 3: return conv1d_wgrad_kernel<TG, false, SMALL, TT, 3, false, 3>;
+          case 4: return conv1d_wgrad_kernel<TG, false, SMALL, TT, 3, false, 4>;
+          case 8: return conv1d_wgrad_kernel<TG, false, SMALL, TT, 3, false, 8>;
+          case 0: return conv1d_wgrad_kernel<TG, false, SMALL, TT, 3, false, 0>;
+          default: return nullptr;
         }
       }
       switch (v.stride_ct) {
-        case 8: WG_GO23(3, true, 8);
-        case 4: WG_GO23(3, true, 4);
-        case 2: WG_GO23(3, true, 2);
-        default: WG_GO23(3, true, 0);
+        case 8: return conv1d_wgrad_kernel<TG, false, SMALL, TT, 3, true, 8>;
+        case 4: return conv1d_wgrad_kernel<TG, false, SMALL, TT, 3, true, 4>;
+        case 2: return conv1d_wgrad_kernel<TG, false, SMALL, TT, 3, true, 2>;
+        case 0: return conv1d_wgrad_kernel<TG, false, SMALL, TT, 3, true, 0>;
+        default: return nullptr;
       }
-    case 1:
-      if (p.win) WG_GO(true, 1);
-      WG_GO(false, 1);
-    default:
-      if (p.win) WG_GO(true, 0);
-      WG_GO(false, 0);
+    case 1:  // width 1, stride 1, activating
+      if (!v.act || v.stride_ct != 0) return nullptr;
+      return win ? conv1d_wgrad_kernel<TG, true, SMALL, TT, 1> : conv1d_wgrad_kernel<TG, false, SMALL, TT, 1>;
+    case 0:  // width 1, stride 1, plain
+      if (v.act || v.stride_ct != 0) return nullptr;
+      return win ? conv1d_wgrad_kernel<TG, true, SMALL, TT, 0> : conv1d_wgrad_kernel<TG, false, SMALL, TT, 0>;
+    default: return nullptr;
   }
-#undef WG_GO
-#undef WG_GO23
 }
 
-// MODE 4 only (row-aligned (k,1) chunks, TT = 64): kept apart so that the 64 x 64 tile gets no other TT = 64 instantiation
+// one tile shape and tap count: the 32 x 32 tile walks 128-, 64- or 32-column chunks, the 64 x 64 tile 32-column chunks (LDS)
 template <int TG, bool SMALL>
-static int launch_wgrad_rows(WgArgs a, const WgPlan& p, const WgVariant& v, float* dw_out, float* workspace, size_t ws_floats,
-                             hipStream_t stream, double flops, double bytes, const WnFinish* wn) {
-  a.rows_half = p.rows_half;
-  a.rows_x4 = p.rows_x4 ? 1 : 0;
-  if (v.act) return launch_wgrad_mode<TG, SMALL, 64, false, 4, true, 0>(a, p, dw_out, workspace, ws_floats, stream, flops, bytes, wn);
-  return launch_wgrad_mode<TG, SMALL, 64, false, 4, false, 0>(a, p, dw_out, workspace, ws_floats, stream, flops, bytes, wn);
+static WgKernel wgrad_kernel_tile(const WgPlan& p, const WgVariant& v) {
+  if constexpr (SMALL) {
+    if (p.tt == 128) return wgrad_kernel_chunked<TG, SMALL, 128>(p.win, v);
+    if (p.tt == 64) return wgrad_kernel_chunked<TG, SMALL, 64>(p.win, v);
+  }
+  return p.tt == 32 ? wgrad_kernel_chunked<TG, SMALL, 32>(p.win, v) : nullptr;
 }
 
-}  // namespace pwg
-
-using namespace pwg;
+static WgKernel wgrad_kernel(const WgPlan& p, const WgVariant& v) {
+  if (v.mode == 4) return wgrad_kernel_rows(p, v);
+  if (p.small) {
+    switch (p.tg) {
+      case 1: return wgrad_kernel_tile<1, true>(p, v);
+      case 2: return wgrad_kernel_tile<2, true>(p, v);
+      case 3: return wgrad_kernel_tile<3, true>(p, v);
+      case 4: return wgrad_kernel_tile<4, true>(p, v);
+      default: return nullptr;
+    }
+  }
+  switch (p.tg) {
+    case 1: return wgrad_kernel_tile<1, false>(p, v);
+    case 2: return wgrad_kernel_tile<2, false>(p, v);
+    case 3: return wgrad_kernel_tile<3, false>(p, v);
+    case 4: return wgrad_kernel_tile<4, false>(p, v);
+    case 5: return wgrad_kernel_tile<5, false>(p, v);
+    case 6: return wgrad_kernel_tile<6, false>(p, v);
+    case 7: return wgrad_kernel_tile<7, false>(p, v);
+    default: return nullptr;
+  }
+}
 
 // single-input-channel path (conv1d_small_cin_wgrad_kernel): `d` flattened; PWG_SMALL_CIN=0 disables it
 static bool small_cin_wgrad_applicable(const pwg_conv1d_desc* d) {
@@ -1229,11 +1253,7 @@ static bool small_cin_wgrad_applicable(const pwg_conv1d_desc* d) {
          d->pad_mode == PWG_PAD_ZERO && d->kernel <= SIW_MAXK && d->c_out >= 8 && d->c_out <= 1024 && d->t_out >= 2048 &&
          (size_t)(SIW_TILE + (d->kernel - 1) * d->dilation + 4) * sizeof(float) <= 64 * 1024;
 }
-static long small_cin_wgrad_slabs(const pwg_conv1d_desc* d) { return (long)d->batch * ceil_div(d->t_out, SIW_TILE); }
 
-// The kernel family of a (flattened) descriptor, in the launcher's order of preference (the values are the ABI of
-// pwg_conv1d_backward_weight_plan, out[0]).
-enum WgPath { WG_PATH_MFMA = 0, WG_PATH_GCONV = 1, WG_PATH_SMALL_CIN = 2, WG_PATH_K1 = 3 };
 static WgPath wgrad_path(const pwg_conv1d_desc* d) {
   if (gconv_wgrad_applicable(d)) return WG_PATH_GCONV;
   if (small_cin_wgrad_applicable(d)) return WG_PATH_SMALL_CIN;
@@ -1241,31 +1261,9 @@ static WgPath wgrad_path(const pwg_conv1d_desc* d) {
   return WG_PATH_MFMA;
 }
 
-// branch-free operand activation max(v, slope * v): 1 = none, 0 = ReLU
-static float wgrad_slope(const pwg_conv1d_desc* d) {
-  return d->pre_act == PWG_ACT_LEAKY_RELU ? d->pre_slope : (d->pre_act == PWG_ACT_RELU ? 0.f : 1.f);
-}
-static bool wgrad_act(float slope) { return slope != 1.f && !(wgrad_dbg() & 8); }
-
-// (the weight-norm finishing kernel holds one weight row in dynamic LDS next to 32 B of static LDS: stay below the 64 KiB
-// default limit with room to spare; functional.py routes longer rows to the two-kernel finish)
-static bool wn_row_fits(int ci_g, int k) { return (size_t)ci_g * k * sizeof(float) + 256 <= 64 * 1024; }
-
-static void wgrad_roles(const pwg_conv1d_desc* d, int* co_g, int* ci_g, int* n_cols) {
-  if (!d->transposed) {
-    *co_g = d->c_out / d->groups;
-    *ci_g = d->c_in / d->groups;
-    *n_cols = d->t_out * d->width;
-  } else {
-    *co_g = d->c_in / d->groups;
-    *ci_g = d->c_out / d->groups;
-    *n_cols = d->t_in * d->width;
-  }
-}
-
-// What every entry point below refuses, in the launcher's words (`d` flattened).
+// What every entry point refuses whatever it is asked for, bias-only calls included, in the launcher's words.
 static int wgrad_check_desc(const pwg_conv1d_desc* d) {
-  PWG_REQUIRE(d->c_in % d->groups == 0 && d->c_out % d->groups == 0 && d->groups > 0, PWG_ERR_BAD_SHAPE,
+  PWG_REQUIRE(d->groups > 0 && d->c_in % d->groups == 0 && d->c_out % d->groups == 0, PWG_ERR_BAD_SHAPE,
               "conv1d_backward_weight: bad groups");
   PWG_REQUIRE(d->pad_mode == PWG_PAD_ZERO, PWG_ERR_UNSUPPORTED,
               "conv1d_backward_weight: only zero padding (pad reflect/replicate inputs explicitly)");
@@ -1275,46 +1273,144 @@ static int wgrad_check_desc(const pwg_conv1d_desc* d) {
               "conv1d_backward_weight: tensors above 4 GiB need batch splitting");
   return PWG_OK;
 }
-// (every path but gconv.hip's, which takes its own activation arguments)
-static int wgrad_check_slope(float slope) {
+
+// The one decision.  `wn`: the slabs are finished through the weight-norm backward; `bias_row`: the bias gradient rides
+// along as a row of every slab.  Evaluated per call, never cached: wgrad_plan reads the concurrency hint.
+static int wgrad_describe(const pwg_conv1d_desc* d, bool wn, bool bias_row, WgCall* c) {
+  if (int rc = wgrad_check_desc(d)) return rc;
+  const long y_elems = (long)d->batch * d->c_out * d->t_out * d->width;
+  const long x_elems = (long)d->batch * d->c_in * d->t_in * d->width;
+  const float slope = d->pre_act == PWG_ACT_LEAKY_RELU ? d->pre_slope : (d->pre_act == PWG_ACT_RELU ? 0.f : 1.f);
+  const bool sw = c->swapped = d->transposed != 0;
+  c->co_g = (sw ? d->c_in : d->c_out) / d->groups;
+  c->ci_g = (sw ? d->c_out : d->c_in) / d->groups;
+  c->n_cols = (sw ? d->t_in : d->t_out) * d->width;
+  c->x_len = (sw ? d->t_out : d->t_in) * d->width;
+  c->g_bytes = (unsigned)((sw ? x_elems : y_elems) * 4);
+  c->x_bytes = (unsigned)((sw ? y_elems : x_elems) * 4);
+  c->slope_g = sw ? slope : 1.f;  // (the pre-activation is the forward input's, whichever role x plays)
+  c->slope_x = sw ? 1.f : slope;
+  c->n0 = c->co_g * d->groups;
+  c->k = d->kernel;
+  const int inner = c->ci_g * c->k;  // floats of a weight row
+  // (the weight-norm finishing kernel holds one weight row in dynamic LDS next to 32 B of static LDS: stay below the 64 KiB
+  // default limit with room to spare; functional.py routes longer rows to the two-kernel finish)
+  PWG_REQUIRE(!wn || (size_t)inner * sizeof(float) + 256 <= 64 * 1024, PWG_ERR_UNSUPPORTED,
+              "conv1d_backward_weight_wn: a weight row of %d floats exceeds the LDS row buffer", inner);
+  // (gconv.hip takes its own activation arguments, and only slopes in [0, 1])
   PWG_REQUIRE(slope >= 0.f && slope <= 1.f, PWG_ERR_UNSUPPORTED,
               "conv1d_backward_weight: LeakyReLU slope %g outside [0, 1] (the operand activation is max(v, slope*v))",
               (double)slope);
-  return PWG_OK;
-}
-static int wgrad_check_transposed(const pwg_conv1d_desc* d) {
-  PWG_REQUIRE(!d->transposed || d->dilation == 1 || d->stride == 1, PWG_ERR_UNSUPPORTED,
-              "conv_transpose1d wgrad: dilation with stride");
-  return PWG_OK;
-}
-
-// Workspace floats an entry point asks for (`d` flattened): the slabs of the path's reduction slices, each dW plus --
-// with `bias_row` -- the fused bias row; with `wn`, one spare slab for the summed gradient of the two-kernel finish.
-// The two public queries always reserve the bias row; pwg_conv1d_backward_weight_plan reports either.
-static size_t wgrad_workspace(const pwg_conv1d_desc* d, bool wn, bool bias_row) {
-  const size_t b = bias_row ? 1 : 0, spare = wn ? 1 : 0;
-  // (the single-input-channel and 1 x 1 kernels always write slabs -- both cut every layer they accept into at least two
-  // -- so only the MFMA kernel below has a slab-free single slice)
-  switch (wgrad_path(d)) {
-    case WG_PATH_GCONV: return gconv_wgrad_workspace_floats(d);
-    case WG_PATH_SMALL_CIN: return (size_t)(small_cin_wgrad_slabs(d) + spare) * ((size_t)d->c_out * (d->kernel + b));
-    case WG_PATH_K1: return (size_t)(k1_wgrad_slabs(d) + spare) * ((size_t)d->c_out * (d->c_in + b));
-    default: break;
+  c->slab_elems = (long)c->n0 * inner;
+  c->slab_stride = c->slab_elems + (bias_row ? c->n0 : 0);
+  c->path = wgrad_path(d);
+  switch (c->path) {
+    case WG_PATH_GCONV:
+      // gconv.hip sums its slabs with a kernel of its own; weight norm: that, then pwg_weight_norm_backward
+      c->nslabs = 0;
+      c->fin = wn ? WG_FIN_WN_TWO_KERNEL : WG_FIN_SLABS;
+      c->ws_floats = gconv_wgrad_workspace_floats(d);
+      return PWG_OK;
+    case WG_PATH_SMALL_CIN: {  // one slab per (item, SIW_TILE columns): at least two, t_out >= 2048
+      const long nslabs = (long)d->batch * ceil_div(d->t_out, SIW_TILE);
+      PWG_REQUIRE(nslabs < (1L << 30), PWG_ERR_UNSUPPORTED, "conv1d_backward_weight: too many slabs");
+      c->nslabs = (int)nslabs;
+      break;
+    }
+    case WG_PATH_K1:  // one slab per workgroup, at least two
+      c->nslabs = k1_wgrad_slabs(d);
+      break;
+    case WG_PATH_MFMA: {
+      PWG_REQUIRE(!d->transposed || d->dilation == 1 || d->stride == 1, PWG_ERR_UNSUPPORTED,
+                  "conv_transpose1d wgrad: dilation with stride");
+      const WgPlan& p = c->plan = wgrad_plan(c->co_g, c->ci_g, d->groups, d->kernel, d->stride, d->dilation, d->width,
+                                             c->n_cols, d->batch);
+      PWG_REQUIRE(p.lds <= 160 * 1024, PWG_ERR_UNSUPPORTED, "conv1d_backward_weight: tile needs %zu B of LDS", p.lds);
+      const WgVariant& v = c->variant = wgrad_variant(p, d->width, d->stride, slope != 1.f && !(wgrad_dbg() & 8));
+      c->kern = wgrad_kernel(p, v);
+      PWG_REQUIRE(c->kern, PWG_ERR_UNSUPPORTED,
+                  "conv1d_backward_weight: no kernel for the %s tile with tg %d, tt %d, win %d, mode %d, act %d, stride_ct %d",
+                  p.small ? "32 x 32" : "64 x 64", p.tg, p.tt, (int)p.win, v.mode, (int)v.act, v.stride_ct);
+      c->nslabs = p.splits;
+      break;
+    }
   }
-  int co_g, ci_g, n_cols;
-  wgrad_roles(d, &co_g, &ci_g, &n_cols);
-  const WgPlan p = wgrad_plan(co_g, ci_g, d->groups, d->kernel, d->stride, d->dilation, d->width, n_cols, d->batch);
-  const size_t n0 = (size_t)co_g * d->groups;
-  const size_t slab = n0 * ci_g * d->kernel + b * n0;
-  if (wn) return (size_t)(p.splits + 1) * slab;
-  // one slab per reduction slice; a single slice stores the gradients itself
-  return wgrad_finisher(p.splits, false, (int)n0, ci_g * d->kernel) == WG_FIN_DIRECT ? 0 : (size_t)p.splits * slab;
+  c->fin = wgrad_finisher(c->nslabs, wn, c->n0, inner);
+  // One slab per slice (only the MFMA kernel ever runs a single slice, which stores the gradients itself); with weight
+  // norm, one spare slab for the summed gradient of the two-kernel finish, and always room for the bias row: the
+  // weight-norm entry point asks for its query's size whatever db is.
+  const size_t ws_stride = (size_t)c->slab_elems + ((bias_row || wn) ? c->n0 : 0);
+  c->ws_floats = c->fin == WG_FIN_DIRECT ? 0 : (size_t)(c->nslabs + (wn ? 1 : 0)) * ws_stride;
+  return PWG_OK;
 }
 
-extern "C" size_t pwg_conv1d_backward_weight_workspace_floats(const pwg_conv1d_desc* d_in) {
-  if (!d_in || d_in->groups <= 0 || d_in->c_in % d_in->groups || d_in->c_out % d_in->groups) return 0;
+// WG_PATH_MFMA: conv1d_wgrad_kernel as `c` describes it.  db_fused non-null: the bias gradient rides along (row sums of
+// the G tiles).  A single slice writes dw_out / db_fused itself (torch layout), otherwise the slabs go to the workspace.
+static int launch_wgrad(const WgCall& c, const pwg_conv1d_desc* d, const float* x, const float* dy, float* dw_out,
+                        float* db_fused, float* workspace, hipStream_t stream) {
+  const WgPlan& p = c.plan;
+  if (p.lds > 64 * 1024 && !lds_limit_is_set(reinterpret_cast<const void*>(c.kern), p.lds)) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(c.kern),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+    PWG_REQUIRE(e == hipSuccess, PWG_ERR_LAUNCH, "conv1d_backward_weight: cannot raise LDS limit: %s",
+                hipGetErrorString(e));
+  }
+  const bool direct = c.fin == WG_FIN_DIRECT;
+  WgArgs a = {};
+  a.g = c.swapped ? x : dy;
+  a.x = c.swapped ? dy : x;
+  a.dw = direct ? dw_out : workspace;
+  a.db = !db_fused ? nullptr : direct ? db_fused : workspace + c.slab_elems;
+  a.tap_major = direct ? 0 : 1;
+  a.co_g = c.co_g;
+  a.ci_g = c.ci_g;
+  a.groups = d->groups;
+  a.k = d->kernel;
+  a.stride = d->stride;
+  a.dil = d->dilation;
+  a.pad = d->pad_left;
+  a.width = d->width;
+  a.n_cols = c.n_cols;
+  a.x_len = c.x_len;
+  a.batch = d->batch;
+  a.chunks_per_item = p.chunks_per_item;
+  a.chunks_total = p.chunks_total;
+  a.chunks_per_block = ceil_div(p.chunks_total, p.splits);
+  a.xs_stride = p.xs_stride;
+  a.slab_elems = c.slab_elems;
+  a.slab_stride = c.slab_stride;
+  a.slope_g = c.slope_g;
+  a.slope_x = c.slope_x;
+  a.g_bytes = c.g_bytes;
+  a.x_bytes = c.x_bytes;
+  a.rows_x4 = p.rows_x4 ? 1 : 0;
+  a.rows_half = p.rows_half;
+  a.dbg = wgrad_dbg();
+  maybe_poison_lds(stream);
+  ProfScope prof(stream,
+                 prof_shape_name("conv1d_wgrad_kernel", "B%d Co%d Ci%d k%d s%d d%d g%d W%d cols%d splits%d tiles%d tg%d small%d win%d tt%d rows%d",
+                                 a.batch, a.co_g * a.groups, a.ci_g * a.groups, a.k, a.stride, a.dil, a.groups, a.width,
+                                 a.n_cols, p.splits, p.tiles, p.tg, (int)p.small, (int)p.win, p.tt, 2 * p.rows_half),
+                 2.0 * a.batch * (double)a.n_cols * c.slab_elems, (double)c.g_bytes + (double)c.x_bytes + 4.0 * c.slab_elems);
+  hipLaunchKernelGGL(c.kern, dim3(p.splits, p.tiles, p.tap_groups), dim3(256), p.lds, stream, a);
+  PWG_CHECK_LAUNCH("conv1d_backward_weight");
+  return PWG_OK;
+}
+
+}  // namespace pwg
+
+using namespace pwg;
+
+static size_t wgrad_workspace_query(const pwg_conv1d_desc* d_in, bool wn) {
+  if (!d_in) return 0;
   const pwg_conv1d_desc flat = flatten_width(*d_in);
-  return wgrad_workspace(&flat, false, true);
+  WgCall c;
+  // (the queries always reserve the bias row; a descriptor the launcher refuses needs nothing)
+  return wgrad_describe(&flat, wn, true, &c) == PWG_OK ? c.ws_floats : 0;
+}
+
+extern "C" size_t pwg_conv1d_backward_weight_workspace_floats(const pwg_conv1d_desc* d) {
+  return wgrad_workspace_query(d, false);
 }
 
 // wn != nullptr: finish the slabs with the fused weight-norm backward (pwg_conv1d_backward_weight_wn)
@@ -1323,155 +1419,59 @@ static int backward_weight_impl(const pwg_conv1d_desc* d_in, const float* x, con
   PWG_REQUIRE(d_in && x && dy, PWG_ERR_NULL, "conv1d_backward_weight: NULL pointer");
   const pwg_conv1d_desc flat = flatten_width(*d_in);
   const pwg_conv1d_desc* d = &flat;
-  if (int rc = wgrad_check_desc(d)) return rc;
   hipStream_t stream = (hipStream_t)stream_;
-  const long y_elems = (long)d->batch * d->c_out * d->t_out * d->width;
-  const long x_elems = (long)d->batch * d->c_in * d->t_in * d->width;
   // The bias gradient (row sums of dy) is fused into the weight-gradient kernel whenever dy plays the
   // G role there (plain convolutions); ConvTranspose1d and bias-only calls use the separate kernel.
-  const bool fuse_bias = db && dw && !d->transposed;
-  if (db && !fuse_bias) {
-    const int n = d->t_out * d->width;
+  float* db_fused = (dw && !d->transposed) ? db : nullptr;
+  WgCall c = {};
+  if (!dw) {  // bias only: nothing of the weight gradient's is decided, or refused
+    if (int rc = wgrad_check_desc(d)) return rc;
+  } else {
+    if (int rc = wgrad_describe(d, wn != nullptr, db_fused != nullptr, &c)) return rc;
+    if (wn) {
+      PWG_REQUIRE(workspace_floats >= c.ws_floats, PWG_ERR_WORKSPACE, "conv1d_backward_weight_wn: workspace too small");
+    } else if (c.path != WG_PATH_GCONV) {  // (gconv.hip checks its slabs itself: they are all it needs here)
+      PWG_REQUIRE(c.ws_floats == 0 || (workspace && workspace_floats >= c.ws_floats), PWG_ERR_WORKSPACE,
+                  "conv1d_backward_weight: workspace of %zu floats needed, %zu given", c.ws_floats, workspace_floats);
+    }
+  }
+  if (db && !db_fused) {
+    const long y_elems = (long)d->batch * d->c_out * d->t_out * d->width;
     ProfScope prof(stream, "bias_grad_kernel", 0, 4.0 * y_elems);
-    hipLaunchKernelGGL(bias_grad_kernel, dim3(d->c_out), dim3(1024), 0, stream, dy, db, d->c_out, n, d->batch);
+    hipLaunchKernelGGL(bias_grad_kernel, dim3(d->c_out), dim3(1024), 0, stream, dy, db, d->c_out, d->t_out * d->width,
+                       d->batch);
     PWG_CHECK_LAUNCH("bias_grad");
   }
   if (!dw) return PWG_OK;
-  const WgPath path = wgrad_path(d);
-  if (path == WG_PATH_GCONV) {
-    // few channels per group: 16 x 16 x 4 MFMA kernel of gconv.hip (bias gradient fused when dy is the G operand)
-    float* db_fused = fuse_bias ? db : nullptr;
-    if (wn == nullptr) return gconv_backward_weight(d, x, dy, dw, db_fused, workspace, workspace_floats, stream);
-    const size_t need = gconv_wgrad_workspace_floats(d);
-    PWG_REQUIRE(workspace && workspace_floats >= need, PWG_ERR_WORKSPACE,
-                "conv1d_backward_weight_wn: workspace of %zu floats needed, %zu given", need, workspace_floats);
-    const size_t w_elems = (size_t)d->c_out * (d->c_in / d->groups) * d->kernel;
-    float* dw_tmp = workspace + (need - w_elems - d->c_out);  // behind the slabs
-    const int rc = gconv_backward_weight(d, x, dy, dw_tmp, db_fused, workspace, need - w_elems - d->c_out, stream);
-    if (rc != PWG_OK) return rc;
-    return pwg_weight_norm_backward(dw_tmp, wn->v, wn->g, wn->dv, wn->dg, d->c_out, (int)(w_elems / d->c_out), stream);
-  }
-  WgArgs a;
-  const float slope = wgrad_slope(d);
-  if (int rc = wgrad_check_slope(slope)) return rc;
-  if (path == WG_PATH_SMALL_CIN) {
-    const long nslabs = small_cin_wgrad_slabs(d);
-    const long slab_elems = (long)d->c_out * d->kernel, slab_stride = slab_elems + (db ? d->c_out : 0);
-    const size_t need = (size_t)(nslabs + (wn ? 1 : 0)) * slab_stride;
-    PWG_REQUIRE(workspace && workspace_floats >= need, PWG_ERR_WORKSPACE,
-                "conv1d_backward_weight: workspace of %zu floats needed, %zu given", need, workspace_floats);
-    PWG_REQUIRE(nslabs < (1L << 30), PWG_ERR_UNSUPPORTED, "conv1d_backward_weight: too many slabs");
-    {
-      ProfScope prof(stream, "conv1d_small_cin_wgrad_kernel", 2.0 * y_elems * d->kernel, 4.0 * ((double)x_elems + (double)y_elems));
-      hipLaunchKernelGGL(conv1d_small_cin_wgrad_kernel,
-                         dim3(ceil_div(d->t_out, SIW_TILE), d->batch, ceil_div(d->c_out, SIW_CO_PER_WG)), dim3(256),
+  switch (c.path) {
+    case WG_PATH_GCONV: {
+      // few channels per group: 16 x 16 x 4 MFMA kernel of gconv.hip (bias gradient fused when dy is the G operand)
+      if (!wn) return gconv_backward_weight(d, x, dy, dw, db_fused, workspace, workspace_floats, stream);
+      const size_t sum_at = gconv_wgrad_sum_offset(d);
+      float* dw_sum = workspace + sum_at;
+      if (int rc = gconv_backward_weight(d, x, dy, dw_sum, db_fused, workspace, sum_at, stream)) return rc;
+      return pwg_weight_norm_backward(dw_sum, wn->v, wn->g, wn->dv, wn->dg, c.n0, c.ci_g * c.k, stream);
+    }
+    case WG_PATH_SMALL_CIN: {
+      const int tiles = ceil_div(d->t_out, SIW_TILE);
+      ProfScope prof(stream, "conv1d_small_cin_wgrad_kernel", 2.0 * (c.g_bytes / 4.0) * d->kernel, (double)c.x_bytes + (double)c.g_bytes);
+      hipLaunchKernelGGL(conv1d_small_cin_wgrad_kernel, dim3(tiles, d->batch, ceil_div(d->c_out, SIW_CO_PER_WG)), dim3(256),
                          (size_t)(SIW_TILE + (d->kernel - 1) * d->dilation + 4) * sizeof(float), stream, x, dy, workspace,
-                         slab_stride, d->c_out, d->t_in, d->t_out, d->kernel, d->dilation, d->pad_left,
-                         ceil_div(d->t_out, SIW_TILE), slope, db ? 1 : 0);
+                         c.slab_stride, d->c_out, d->t_in, d->t_out, d->kernel, d->dilation, d->pad_left, tiles, c.slope_x,
+                         db_fused ? 1 : 0);
       PWG_CHECK_LAUNCH("conv1d_small_cin_wgrad");
+      break;
     }
-    return finish_wgrad_slabs(workspace, (int)nslabs, slab_elems, slab_stride, d->c_out, 1, d->kernel, dw, db, wn, stream);
+    case WG_PATH_K1:
+      // 1 x 1 layers with few channels: HBM-bound kernel of wgrad_k1.hip, one slab per workgroup
+      if (int rc = k1_wgrad_launch(d, x, dy, workspace, c.slab_stride, c.nslabs, c.slope_x, db_fused != nullptr, stream))
+        return rc;
+      break;
+    case WG_PATH_MFMA:
+      if (int rc = launch_wgrad(c, d, x, dy, dw, db_fused, workspace, stream)) return rc;
+      break;
   }
-  if (path == WG_PATH_K1) {
-    // 1 x 1 layers with few channels: HBM-bound kernel of wgrad_k1.hip, one slab per workgroup
-    const int nslabs = k1_wgrad_slabs(d);
-    const long slab_elems = (long)d->c_out * d->c_in, slab_stride = slab_elems + (db ? d->c_out : 0);
-    const size_t need = (size_t)(nslabs + (wn ? 1 : 0)) * slab_stride;
-    PWG_REQUIRE(workspace && workspace_floats >= need, PWG_ERR_WORKSPACE,
-                "conv1d_backward_weight: workspace of %zu floats needed, %zu given", need, workspace_floats);
-    const int rc = k1_wgrad_launch(d, x, dy, workspace, slab_stride, nslabs, slope, db != nullptr, stream);
-    if (rc != PWG_OK) return rc;
-    return finish_wgrad_slabs(workspace, nslabs, slab_elems, slab_stride, d->c_out, d->c_in, 1, dw, db, wn, stream);
-  }
-  if (!d->transposed) {
-    a.g = dy;
-    a.x = x;
-    a.co_g = d->c_out / d->groups;
-    a.ci_g = d->c_in / d->groups;
-    a.n_cols = d->t_out * d->width;
-    a.x_len = d->t_in * d->width;
-    a.slope_g = 1.f;
-    a.slope_x = slope;
-    a.g_bytes = (unsigned)(y_elems * 4);
-    a.x_bytes = (unsigned)(x_elems * 4);
-  } else {
-    // ConvTranspose1d: dW[ci][co][k] = sum x[ci][q] * dy[co][q*s - p + k]: same kernel, roles swapped
-    if (int rc = wgrad_check_transposed(d)) return rc;
-    a.g = x;
-    a.x = dy;
-    a.co_g = d->c_in / d->groups;
-    a.ci_g = d->c_out / d->groups;
-    a.n_cols = d->t_in * d->width;
-    a.x_len = d->t_out * d->width;
-    a.slope_g = slope;
-    a.slope_x = 1.f;
-    a.g_bytes = (unsigned)(x_elems * 4);
-    a.x_bytes = (unsigned)(y_elems * 4);
-  }
-  a.dbg = wgrad_dbg();
-  a.dw = nullptr;
-  a.db = fuse_bias ? db : nullptr;
-  a.groups = d->groups;
-  a.k = d->kernel;
-  a.stride = d->stride;
-  a.dil = d->dilation;
-  a.pad = d->pad_left;
-  a.width = d->width;
-  a.batch = d->batch;
-  const double flops = 2.0 * d->batch * (double)a.n_cols * a.co_g * a.ci_g * d->groups * d->kernel;
-  const double bytes = 4.0 * ((double)x_elems + (double)y_elems + (double)a.co_g * a.ci_g * d->groups * d->kernel);
-  const WgPlan p = wgrad_plan(a.co_g, a.ci_g, d->groups, d->kernel, d->stride, d->dilation, d->width, a.n_cols,
-                              d->batch);
-  const WgVariant v = wgrad_variant(p, d->width, d->stride, wgrad_act(slope));
-#define WG_CASE(TGV, SM)                                                                             \
-  switch (p.tt) {                                                                                    \
-    case 128: return launch_wgrad<TGV, SM, 128>(a, p, v, dw, workspace, workspace_floats, stream, flops, bytes, wn); \
-    case 64: return launch_wgrad<TGV, SM, 64>(a, p, v, dw, workspace, workspace_floats, stream, flops, bytes, wn);   \
-    default: return launch_wgrad<TGV, SM, 32>(a, p, v, dw, workspace, workspace_floats, stream, flops, bytes, wn);   \
-  }
-  a.rows_half = 0;
-  a.rows_x4 = 0;
-  if (p.rows_half > 0) {
-#define WG_ROWS(TGV, SM) return launch_wgrad_rows<TGV, SM>(a, p, v, dw, workspace, workspace_floats, stream, flops, bytes, wn)
-    if (p.small) {
-      switch (p.tg) {
-        case 1: WG_ROWS(1, true);
-        case 2: WG_ROWS(2, true);
-        case 3: WG_ROWS(3, true);
-        default: WG_ROWS(4, true);
-      }
-    }
-    switch (p.tg) {
-      case 1: WG_ROWS(1, false);
-      case 2: WG_ROWS(2, false);
-      case 3: WG_ROWS(3, false);
-      case 4: WG_ROWS(4, false);
-      case 5: WG_ROWS(5, false);
-      case 6: WG_ROWS(6, false);
-      default: WG_ROWS(7, false);
-    }
-#undef WG_ROWS
-  }
-  if (p.small) {
-    switch (p.tg) {
-      case 1: WG_CASE(1, true);
-      case 2: WG_CASE(2, true);
-      case 3: WG_CASE(3, true);
-      default: WG_CASE(4, true);
-    }
-  }
-#undef WG_CASE
-#define WG_CASE(TGV) return launch_wgrad<TGV, false, 32>(a, p, v, dw, workspace, workspace_floats, stream, flops, bytes, wn)
-  switch (p.tg) {  // 64x64 tiles always run 32-column chunks (LDS)
-    case 1: WG_CASE(1);
-    case 2: WG_CASE(2);
-    case 3: WG_CASE(3);
-    case 4: WG_CASE(4);
-    case 5: WG_CASE(5);
-    case 6: WG_CASE(6);
-    default: WG_CASE(7);
-  }
-#undef WG_CASE
+  return finish_wgrad_slabs(c, workspace, dw, db_fused, wn, stream);
 }
 
 extern "C" int pwg_conv1d_backward_weight(const pwg_conv1d_desc* d, const float* x, const float* dy, float* dw,
@@ -1482,23 +1482,14 @@ extern "C" int pwg_conv1d_backward_weight(const pwg_conv1d_desc* d, const float*
 // Weight-normalised layers: dv, dg (and db) straight from the reduction slabs -- see reduce_slabs_wn_kernel.
 // v (weight_v, torch layout) and g (weight_g, one value per dim-0 slice) are the forward's parameters.  The
 // workspace is always needed here (>= 1 slab): query it with the function below.
-extern "C" size_t pwg_conv1d_backward_weight_wn_workspace_floats(const pwg_conv1d_desc* d_in) {
-  if (!d_in || d_in->groups <= 0 || d_in->c_in % d_in->groups || d_in->c_out % d_in->groups) return 0;
-  const pwg_conv1d_desc flat = flatten_width(*d_in);
-  return wgrad_workspace(&flat, true, true);
+extern "C" size_t pwg_conv1d_backward_weight_wn_workspace_floats(const pwg_conv1d_desc* d) {
+  return wgrad_workspace_query(d, true);
 }
 
 extern "C" int pwg_conv1d_backward_weight_wn(const pwg_conv1d_desc* d, const float* x, const float* dy, const float* v,
                                              const float* g, float* dv, float* dg, float* db, float* workspace,
                                              size_t workspace_floats, void* stream) {
   PWG_REQUIRE(d && v && g && dv && dg && workspace, PWG_ERR_NULL, "conv1d_backward_weight_wn: NULL pointer");
-  int co_g, ci_g, n_cols;
-  const pwg_conv1d_desc flat = flatten_width(*d);
-  wgrad_roles(&flat, &co_g, &ci_g, &n_cols);
-  PWG_REQUIRE(wn_row_fits(ci_g, d->kernel), PWG_ERR_UNSUPPORTED,
-              "conv1d_backward_weight_wn: a weight row of %d floats exceeds the LDS row buffer", ci_g * d->kernel);
-  PWG_REQUIRE(workspace_floats >= pwg_conv1d_backward_weight_wn_workspace_floats(d), PWG_ERR_WORKSPACE,
-              "conv1d_backward_weight_wn: workspace too small");
   const WnFinish wn{v, g, dv, dg};
   // (dw argument: any non-NULL pointer selects the weight-gradient path; the slabs live in the workspace)
   return backward_weight_impl(d, x, dy, dv, db, workspace, workspace_floats, stream, &wn);
@@ -1509,58 +1500,30 @@ extern "C" int pwg_conv1d_backward_weight_plan(const pwg_conv1d_desc* d_in, int3
                                                int32_t* out) {
   PWG_REQUIRE(d_in && out, PWG_ERR_NULL, "conv1d_backward_weight: NULL pointer");
   const pwg_conv1d_desc flat = flatten_width(*d_in);
-  const pwg_conv1d_desc* d = &flat;
-  if (int rc = wgrad_check_desc(d)) return rc;
-  const bool wn = weight_norm != 0;
-  int co_g, ci_g, n_cols;
-  wgrad_roles(d, &co_g, &ci_g, &n_cols);
-  PWG_REQUIRE(!wn || wn_row_fits(ci_g, d->kernel), PWG_ERR_UNSUPPORTED,
-              "conv1d_backward_weight_wn: a weight row of %d floats exceeds the LDS row buffer", ci_g * d->kernel);
+  WgCall c;
+  if (int rc = wgrad_describe(&flat, weight_norm != 0, has_bias != 0, &c)) return rc;
   for (int i = 0; i < 20; ++i) out[i] = 0;
-  const WgPath path = wgrad_path(d);
-  int fin = WG_FIN_DIRECT, nslabs = 0;
-  if (path == WG_PATH_GCONV) {
-    // gconv.hip sums its slabs with a kernel of its own; weight norm: that, then pwg_weight_norm_backward
-    fin = wn ? WG_FIN_WN_TWO_KERNEL : WG_FIN_SLABS;
-  } else {
-    const float slope = wgrad_slope(d);
-    if (int rc = wgrad_check_slope(slope)) return rc;
-    if (path == WG_PATH_SMALL_CIN) {
-      nslabs = (int)small_cin_wgrad_slabs(d);
-      fin = wgrad_finisher(nslabs, wn, d->c_out, d->kernel);
-    } else if (path == WG_PATH_K1) {
-      nslabs = k1_wgrad_slabs(d);
-      fin = wgrad_finisher(nslabs, wn, d->c_out, d->c_in);
-    } else {
-      if (int rc = wgrad_check_transposed(d)) return rc;
-      const WgPlan p = wgrad_plan(co_g, ci_g, d->groups, d->kernel, d->stride, d->dilation, d->width, n_cols, d->batch);
-      PWG_REQUIRE(p.lds <= 160 * 1024, PWG_ERR_UNSUPPORTED, "conv1d_backward_weight: tile needs %zu B of LDS", p.lds);
-      const WgVariant v = wgrad_variant(p, d->width, d->stride, wgrad_act(slope));
-      nslabs = p.splits;
-      fin = wgrad_finisher(p.splits, wn, co_g * d->groups, ci_g * d->kernel);
-      out[4] = p.small ? 1 : 0;
-      out[5] = p.tg;
-      out[6] = p.taps_block;
-      out[7] = p.tap_groups;
-      out[8] = p.win ? 1 : 0;
-      out[9] = p.tt;
-      out[10] = p.rows_half;
-      out[11] = p.rows_x4 ? 1 : 0;
-      out[12] = v.mode;
-      out[13] = v.act ? 1 : 0;
-      out[14] = v.stride_ct;
-      out[15] = p.tiles;
-      out[16] = p.splits;
-      out[17] = (int32_t)p.lds;
-      out[19] = p.xs_stride;
-    }
-  }
-  // (the weight-norm entry point always asks for the bias row, as its query does)
-  const size_t ws = wgrad_workspace(d, wn, wn || has_bias != 0);
-  out[0] = path;
-  out[1] = fin;
-  out[2] = (int32_t)(ws & 0x7FFFFFFFu);
-  out[3] = (int32_t)(ws >> 31);
-  out[18] = nslabs;
+  out[0] = c.path;
+  out[1] = c.fin;
+  out[2] = (int32_t)(c.ws_floats & 0x7FFFFFFFu);
+  out[3] = (int32_t)(c.ws_floats >> 31);
+  out[18] = c.nslabs;
+  if (c.path != WG_PATH_MFMA) return PWG_OK;
+  const WgPlan& p = c.plan;
+  out[4] = p.small ? 1 : 0;
+  out[5] = p.tg;
+  out[6] = p.taps_block;
+  out[7] = p.tap_groups;
+  out[8] = p.win ? 1 : 0;
+  out[9] = p.tt;
+  out[10] = p.rows_half;
+  out[11] = p.rows_x4 ? 1 : 0;
+  out[12] = c.variant.mode;
+  out[13] = c.variant.act ? 1 : 0;
+  out[14] = c.variant.stride_ct;
+  out[15] = p.tiles;
+  out[16] = p.splits;
+  out[17] = (int32_t)p.lds;
+  out[19] = p.xs_stride;
   return PWG_OK;
 }

@@ -586,15 +586,18 @@ static int gconv_wgrad_slices(const pwg_conv1d_desc* d) {
   return slices;
 }
 
+// Workspace layout: the slabs, then room for the summed gradient (weight-norm finish: dW and the bias row).
+// gconv_wgrad_sum_offset: the floats of the slabs, i.e. where the summed gradient starts.
+size_t gconv_wgrad_sum_offset(const pwg_conv1d_desc* d) {
+  const int roww = ceil_div(d->c_in / d->groups * d->kernel, 16) * 16 + 1;
+  return (size_t)gconv_wgrad_slices(d) * d->groups * 16 * roww;
+}
 size_t gconv_wgrad_workspace_floats(const pwg_conv1d_desc* d) {
-  const int cig = d->c_in / d->groups;
-  const int roww = ceil_div(cig * d->kernel, 16) * 16 + 1;
-  // slabs + room for the summed gradient (weight-norm finish)
-  return (size_t)gconv_wgrad_slices(d) * d->groups * 16 * roww + (size_t)d->c_out * cig * d->kernel + d->c_out;
+  return gconv_wgrad_sum_offset(d) + (size_t)d->c_out * (d->c_in / d->groups) * d->kernel + d->c_out;
 }
 
 // Always slabs + gconv_wgrad_reduce_kernel, under weight norm followed by pwg_weight_norm_backward (backward_weight_impl):
-// pwg_conv1d_backward_weight_plan reports exactly that for this path -- keep the two together.
+// wgrad_describe of conv1d_wgrad.hip says exactly that for this path -- keep the two together.
 // dw: torch layout (c_out, cig, k); db may be NULL.  dw == NULL is not supported here (bias-only calls use the general path).
 int gconv_backward_weight(const pwg_conv1d_desc* d, const float* x, const float* dy, float* dw, float* db, float* workspace,
                           size_t ws_floats, hipStream_t stream) {
@@ -616,7 +619,7 @@ int gconv_backward_weight(const pwg_conv1d_desc* d, const float* x, const float*
   a.slices = gconv_wgrad_slices(d);
   a.steps_total = d->batch * ceil_div(d->t_out, 64);
   a.total_waves = a.slices * d->groups;
-  const size_t need = (size_t)a.slices * d->groups * 16 * roww;
+  const size_t need = gconv_wgrad_sum_offset(d);  // (the slabs alone)
   PWG_REQUIRE(workspace && ws_floats >= need, PWG_ERR_WORKSPACE, "conv1d_backward_weight: workspace of %zu floats needed, %zu given",
               need, ws_floats);
   a.slabs = workspace;
