@@ -373,6 +373,30 @@ int pwg_resunit_pack_weight(int32_t channels, int32_t kernel, const float* w, co
 int pwg_resunit_forward(const pwg_resunit_desc* d, const float* x, const float* w1_packed, const float* b1,
                         const float* w2_packed, const float* b2, const float* add2, float* y, void* stream);
 
+/* ---- split-operand residual unit (fp32-accurate on the bf16 matrix pipe; csrc/resunit_split.hip) ----
+ * The unit of pwg_resunit_forward (same descriptor, same formula, both forms) under the numerical definition of the
+ * split-operand inference above, applied twice:
+ *   1. lrelu(x) is formed in fp32 and split three ways; the effective weights are split once by the packer;
+ *   2. the six products lo.hi, hi.lo, mid.mid, mid.hi, hi.mid, hi.hi go into one fp32 accumulator set;
+ *   3. h = lrelu(acc + b1) is formed in fp32 (v > 0 ? v : v * slope2), is zero outside [0, t) and is split three ways;
+ *   4. the residual is the raw fp32 x; the epilogue is acc + bias + x + add2, then the true division by out_div.
+ * The accumulation order of an output element is that of pwg_conv1d_split_forward (32-channel chunk, tap, reduction
+ * step, product), so a unit is bit-identical to two chained pwg_conv1d_split_forward_cfg launches at the same
+ * mfma_shape (conv1: pre_act = post_act = leaky, bias b1; conv2: bias b2, add1 = x, add2, out_div), and deterministic.
+ * w1_split / w2_split are the images of pwg_conv1d_split_pack_weight for a channels -> channels convolution of this
+ * kernel size (the image depends on neither dilation, padding nor length), 16-B aligned; w2_split is NULL exactly when
+ * has_conv2 == 0.  Covered: channels 32 / 64, odd kernel, t % 4 == 0, 0 < slope < 1, a window whose three bf16 planes
+ * fit 80 KB of LDS; x / y / add2 16-B aligned, y != x.  pwg_resunit_split_supported is pure host logic (no device
+ * needed; pwg_last_error names the reason for 0); anything else is refused with a message and launches nothing.
+ * pwg_resunit_split_forward_cfg (tuning / tests): mfma_shape 32 = 32x32x16, 16 = 16x16x32 (the default).
+ * These symbols are purely additive, so pwg_abi_version() stays 15. */
+int pwg_resunit_split_supported(const pwg_resunit_desc* d);
+int pwg_resunit_split_forward(const pwg_resunit_desc* d, const float* x, const void* w1_split, const float* b1,
+                              const void* w2_split, const float* b2, const float* add2, float* y, void* stream);
+int pwg_resunit_split_forward_cfg(const pwg_resunit_desc* d, const float* x, const void* w1_split, const float* b1,
+                                  const void* w2_split, const float* b2, const float* add2, float* y, int32_t mfma_shape,
+                                  void* stream);
+
 /* ------------------------------------------------------------------------- */
 /* One MelGAN residual stack as ONE launch (channels 48 / 96 / 192, kernel 3; csrc/resstack.hip)             */
 /*                                                                            */

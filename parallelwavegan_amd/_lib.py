@@ -176,6 +176,10 @@ SIGNATURES = {
     "pwg_resunit_packed_weight_floats": (ctypes.c_size_t, [_i32, _i32]),
     "pwg_resunit_pack_weight": (ctypes.c_int, [_i32, _i32, _vp, _vp, _vp, _vp]),
     "pwg_resunit_forward": (ctypes.c_int, [ctypes.POINTER(ResUnitDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pwg_resunit_split_supported": (ctypes.c_int, [ctypes.POINTER(ResUnitDesc)]),
+    "pwg_resunit_split_forward": (ctypes.c_int, [ctypes.POINTER(ResUnitDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pwg_resunit_split_forward_cfg": (ctypes.c_int, [ctypes.POINTER(ResUnitDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32,
+                                                     _vp]),
     "pwg_resstack_supported": (ctypes.c_int, [_i32, _i32, _i32]),
     "pwg_resstack_packed_weight_floats": (ctypes.c_size_t, [_i32]),
     "pwg_resstack_pack_weight": (ctypes.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -1,0 +1,424 @@
+// resunit_split.hip -- one HiFi-GAN MRF residual unit as ONE launch on the gfx950 bf16 MFMA instructions, operands split
+// three ways (inference, C = 32 / 64):
+//
+//     y = ( x + conv_{k,1}( lrelu( conv_{k,d}( lrelu(x) ) + b1 ) ) + b2  [+ add2] ) [/ out_div]
+//
+// and the single-convolution form y = ( x + conv_{k,d}(lrelu(x)) + b1 [+ add2] ) [/ out_div].  The structure is that of
+// resunit.hip (all channels of a column tile and the intermediate h resident in LDS, 2 HBM passes), the arithmetic that
+// of conv1d_split.hip, applied twice.
+//
+// Numerical definition (include/pwg_kernels.h, "split-operand residual unit"): lrelu(x) is formed in fp32 and split with
+// split3 while the window is staged; the effective weights are split once by pwg_conv1d_split_pack_weight (the same
+// image); per operand pair the products lo.hi, hi.lo, mid.mid, mid.hi, hi.mid, hi.hi (weight part . input part) go, in
+// this order, into one fp32 accumulator set; h = lrelu(acc + b1) is formed in fp32, is zero outside [0, T) and is split
+// with split3; the residual is the raw fp32 x and the epilogue is acc + bias + x + add2, then / out_div.
+// The accumulation order of an output element is the split kernel's: 32-channel chunk, tap, reduction step, product.  A
+// unit is therefore bit-identical to two chained pwg_conv1d_split_forward_cfg launches at the same MFMA shape (conv1 with
+// pre_act = post_act = leaky and bias b1; conv2 with bias b2, add1 = x, add2, out_div): that chain is the test oracle.
+// Built without FMA contraction for the reason given in build.py for conv1d_split.hip.
+//
+// Tile: 4 waves, each 32 channels x 64 columns; C = 32: 256 h-columns per workgroup, C = 64: 128 (2 x 2 waves).  A tile
+// of H h-columns yields (H - (k - 1)) & ~3 outputs (the halo is recomputed), H in the single form.
+// LDS: three bf16 planes [column][C + 8] of the activated x window (rows of 80 B / 144 B: an odd number of 16-B slots);
+// after phase 1 and a barrier the h planes take their place.  At k = 11, d = 5: 75 KB (C = 32) / 80 KB (C = 64), two
+// workgroups per CU.
+//   phase 1 (pair)   weight fragment first: a lane owns 4 consecutive channels of a column, each part of h is one 8-B
+//                    LDS write per 4 accumulator registers
+//   phase 2 / single x (h) fragment first: the transposed tile, a lane owns 4 consecutive samples of a channel and the
+//                    epilogue reads x / add2 and writes y with 16-B accesses straight from the accumulators
+// The operand order changes neither the products nor their summation order.  The residual x is re-read from global
+// memory in the epilogue (the workgroup fetched those lines while staging; an fp32 copy in LDS would cost the second
+// workgroup per CU).
+// Deterministic: one workgroup owns an output tile, no atomics.
+#include "mfma_conv.h"
+
+#include <stdlib.h>
+
+namespace pwg {
+namespace {
+
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+
+constexpr size_t kRuSplitMaxLds = 80 * 1024;  // two workgroups per 160 KB CU
+
+struct RuSplitArgs {
+  const float* x;
+  const bf16x8* w1;  // three-part image of pwg_conv1d_split_pack_weight
+  const float* b1;
+  const bf16x8* w2;  // nullptr: single convolution
+  const float* b2;
+  const float* add2;
+  float* y;
+  int T, k, d1;
+  int bn_out;  // outputs per tile (multiple of 4)
+  int hla;     // staged column of output slot 0 at the centre tap (left halo rounded up to a multiple of 4)
+  int sh;      // hla - (true left halo)
+  int p2;      // (k - 1) / 2 in pair mode, 0 otherwise
+  int rows;    // staged columns = LDS rows of a plane (multiple of 4)
+  int plane;   // bf16 elements per LDS plane
+  long part_stride;  // bf16x8 elements per weight part image
+  float slope1, slope2, out_div;
+};
+
+template <int C>
+struct RuSplitCfg {
+  static constexpr int MB = C / KC;       // 32-row blocks = waves along the channels
+  static constexpr int WAVES_N = 4 / MB;  // waves along the columns
+  static constexpr int H = WAVES_N * 64;  // h-columns / output slots per workgroup
+  static constexpr int ROW = C + 8;       // bf16 elements per LDS row
+  static constexpr int OCTS = C / 8;
+};
+
+// Stage the whole C-channel window: item = (group of 4 columns, channel octet), at most two per thread: 8 loads of 16 B
+// (one per channel, along t), then per column 8 channels are activated, split and written as three 16-B LDS stores.
+// T % 4 == 0 and the first staged column is a multiple of 4: a group lies inside the row or outside it.  CHECKED (first
+// / last tiles of a row): a group outside [0, T) gives zeros = the zero padding of conv1.
+template <int C, bool CHECKED>
+__device__ __forceinline__ void ru_stage_window(const RuSplitArgs& a, const float* __restrict__ xb, int base, __bf16* xs,
+                                                int tid) {
+  constexpr int OCTS = RuSplitCfg<C>::OCTS, ROW = RuSplitCfg<C>::ROW;
+  const int nitems = (a.rows >> 2) * OCTS;
+  f32x4 st[2][8];
+#pragma unroll
+  for (int it = 0; it < 2; ++it) {
+    const int idx = tid + it * 256, oct = idx % OCTS, grp = idx / OCTS;
+    const int t = base + grp * 4;
+    const float* __restrict__ src = xb + (size_t)(oct * 8) * a.T + t;
+    const bool in = idx < nitems && (!CHECKED || (t >= 0 && t < a.T));
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (in) v = *reinterpret_cast<const f32x4*>(src + (size_t)j * a.T);
+      st[it][j] = v;
+    }
+  }
+#pragma unroll
+  for (int it = 0; it < 2; ++it) {
+    const int idx = tid + it * 256, oct = idx % OCTS, grp = idx / OCTS;
+    if (idx < nitems) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        bf16x8 vh, vm, vl;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const float v = st[it][j][e];
+          __bf16 hi, mid, lo;
+          split3(v > 0.f ? v : v * a.slope1, hi, mid, lo);
+          vh[j] = hi;
+          vm[j] = mid;
+          vl[j] = lo;
+        }
+        __bf16* dst = xs + (grp * 4 + e) * ROW + oct * 8;
+        *reinterpret_cast<bf16x8*>(dst) = vh;
+        *reinterpret_cast<bf16x8*>(dst + a.plane) = vm;
+        *reinterpret_cast<bf16x8*>(dst + 2 * a.plane) = vl;
+        __builtin_amdgcn_sched_barrier(0);  // one column at a time (conv1d_split.hip, stage_window_vec)
+      }
+    }
+  }
+}
+
+// acc += W (*) B over (chunk, tap, reduction step, product): the order of conv1d_split_mfma_kernel.  wl: the part-0 image
+// at this lane's weight row; bl: plane 0 at this lane's column of tile 0, tap 0; tap_step: columns per tap.
+// XFIRST: the B fragment is the first MFMA operand (transposed tile).
+template <int C, int TILE, bool XFIRST>
+__device__ __forceinline__ void ru_contract(const bf16x8* __restrict__ wl, long part_stride, const __bf16* bl, int plane,
+                                            int tap_step, int taps, int h,
+                                            typename Mfma<TILE>::acc_t (&acc)[32 / TILE][64 / TILE]) {
+  constexpr int HL = 64 / TILE, KSTEPS = KC / (8 * HL), TM = 32 / TILE, TN = 64 / TILE;
+  constexpr int ROW = RuSplitCfg<C>::ROW, CHUNKS = C / KC;
+#pragma unroll 1
+  for (int chunk = 0; chunk < CHUNKS; ++chunk) {
+#pragma unroll 1
+    for (int tap = 0; tap < taps; ++tap) {
+#pragma unroll
+      for (int ks = 0; ks < KSTEPS; ++ks) {
+        const int oct = ks * HL + h;
+        const bf16x8* __restrict__ wp = image_rows(wl, CHUNKS, C, tap, chunk, oct);
+        bf16x8 af[3][TM], bfr[3][TN];  // [0] hi, [1] mid, [2] lo
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+#pragma unroll
+          for (int mi = 0; mi < TM; ++mi) af[p][mi] = wp[p * part_stride + mi * TILE];
+#pragma unroll
+        for (int ni = 0; ni < TN; ++ni) {
+          const __bf16* src = bl + (ni * TILE + tap * tap_step) * ROW + chunk * KC + oct * 8;
+#pragma unroll
+          for (int p = 0; p < 3; ++p) bfr[p][ni] = *reinterpret_cast<const bf16x8*>(src + p * plane);
+        }
+        // (weight part, input part), small terms first
+        constexpr int PA[6] = {2, 0, 1, 1, 0, 0};
+        constexpr int PB[6] = {0, 2, 1, 0, 1, 0};
+#pragma unroll
+        for (int p = 0; p < 6; ++p)
+#pragma unroll
+          for (int mi = 0; mi < TM; ++mi)
+#pragma unroll
+            for (int ni = 0; ni < TN; ++ni)
+              acc[mi][ni] = XFIRST ? Mfma<TILE>::run(bfr[PB[p]][ni], af[PA[p]][mi], acc[mi][ni])
+                                   : Mfma<TILE>::run(af[PA[p]][mi], bfr[PB[p]][ni], acc[mi][ni]);
+      }
+    }
+  }
+}
+
+template <int C, int TILE>
+__global__ __launch_bounds__(256, 2) void resunit_split_kernel(RuSplitArgs a) {
+  using Cfg = RuSplitCfg<C>;
+  constexpr int WAVES_N = Cfg::WAVES_N, ROW = Cfg::ROW, H = Cfg::H;
+  constexpr int HL = 64 / TILE, TM = 32 / TILE, TN = 64 / TILE, NREG = TILE * TILE / 64, NG = NREG / 4;
+  typedef typename Mfma<TILE>::acc_t acc_t;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __bf16* xs = reinterpret_cast<__bf16*>(smem);  // [part][column][ROW]: activated x, then h
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wave_m = wave / WAVES_N, wave_n = wave % WAVES_N;
+  const int r = lane & (TILE - 1), h = lane / TILE;
+  const int b = blockIdx.y;
+  const int t0 = blockIdx.x * a.bn_out;  // first output sample of this tile
+  const int base = t0 - a.hla;           // sample of staged column 0 (a multiple of 4, also when negative)
+  const int T = a.T;
+  const bool pair = a.w2 != nullptr;
+  const float* __restrict__ xb = a.x + (size_t)b * C * T;
+
+  if (base >= 0 && base + a.rows <= T)
+    ru_stage_window<C, false>(a, xb, base, xs, tid);
+  else
+    ru_stage_window<C, true>(a, xb, base, xs, tid);
+
+  acc_t acc[TM][TN];
+#pragma unroll
+  for (int mi = 0; mi < TM; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < TN; ++ni)
+#pragma unroll
+      for (int i = 0; i < NREG; ++i) acc[mi][ni][i] = 0.f;
+  __syncthreads();
+
+  const int wrow = wave_m * 32 + r;  // this lane's weight row of tile mi = 0
+  if (pair) {
+    // ---- phase 1: conv_{k,d} over lrelu(x); h column m reads staged column m + sh + tap * d
+    ru_contract<C, TILE, false>(a.w1 + wrow, a.part_stride, xs + (wave_n * 64 + r + a.sh) * ROW, a.plane, a.d1, a.k, h,
+                                acc);
+    __syncthreads();  // every wave has read its x columns: the h planes take their place
+    // h = lrelu(acc + b1), zero outside [0, T) (conv2's zero padding), split: a lane owns channels c .. c + 3 of a column
+    const bool has_b1 = a.b1 != nullptr;
+#pragma unroll
+    for (int mi = 0; mi < TM; ++mi)
+#pragma unroll
+      for (int g = 0; g < NG; ++g) {
+        const int c = wave_m * 32 + mi * TILE + 4 * h + 4 * HL * g;
+        f32x4 bias = {0.f, 0.f, 0.f, 0.f};
+        if (has_b1) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) bias[e] = a.b1[c + e];
+        }
+#pragma unroll
+        for (int ni = 0; ni < TN; ++ni) {
+          const int m = wave_n * 64 + ni * TILE + r;
+          const int th = t0 - a.p2 + m;
+          const bool inside = th >= 0 && th < T;
+          bf16x4 vh, vm, vl;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            float v = acc[mi][ni][4 * g + e];
+            if (has_b1) v += bias[e];
+            v = v > 0.f ? v : v * a.slope2;
+            v = inside ? v : 0.f;
+            __bf16 hi, mid, lo;
+            split3(v, hi, mid, lo);
+            vh[e] = hi;
+            vm[e] = mid;
+            vl[e] = lo;
+            acc[mi][ni][4 * g + e] = 0.f;
+          }
+          __bf16* dst = xs + m * ROW + c;
+          *reinterpret_cast<bf16x4*>(dst) = vh;
+          *reinterpret_cast<bf16x4*>(dst + a.plane) = vm;
+          *reinterpret_cast<bf16x4*>(dst + 2 * a.plane) = vl;
+        }
+      }
+    // h columns H .. H + k - 2 feed only the discarded output slots past bn_out: zeros, not what x left there
+    for (int i = tid; i < (a.k - 1) * Cfg::OCTS; i += 256) {
+      bf16x8 z;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) z[j] = (__bf16)0.f;
+      __bf16* dst = xs + (H + i / Cfg::OCTS) * ROW + (i % Cfg::OCTS) * 8;
+      *reinterpret_cast<bf16x8*>(dst) = z;
+      *reinterpret_cast<bf16x8*>(dst + a.plane) = z;
+      *reinterpret_cast<bf16x8*>(dst + 2 * a.plane) = z;
+    }
+    __syncthreads();
+    // ---- phase 2: conv_{k,1} over h; output slot n reads h column n + tap
+    ru_contract<C, TILE, true>(a.w2 + wrow, a.part_stride, xs + (wave_n * 64 + r) * ROW, a.plane, 1, a.k, h, acc);
+  } else {
+    ru_contract<C, TILE, true>(a.w1 + wrow, a.part_stride, xs + (wave_n * 64 + r + a.sh) * ROW, a.plane, a.d1, a.k, h,
+                               acc);
+  }
+
+  // ---- epilogue (fp32, the order of split_epilogue: acc + bias + x + add2, then / out_div).  Transposed tile: a lane
+  // owns channel c per mi and, per accumulator, NG values of 4 consecutive samples; value g of tile ni is output slot
+  // wave_n * 64 + ni * TILE + 4 * h + 4 * HL * g.  bn_out, t0 and T are multiples of 4: a value is stored whole or not
+  // at all; the loads of a value that is not stored read the tile's first samples instead.
+  constexpr int NV = TN * NG;
+  const float* __restrict__ bias_p = pair ? a.b2 : a.b1;
+  const bool has_bias = bias_p != nullptr, has2 = a.add2 != nullptr;
+#pragma unroll
+  for (int mi = 0; mi < TM; ++mi) {
+    const int c = wave_m * 32 + mi * TILE + r;
+    const size_t row = ((size_t)b * C + c) * T;
+    int t[NV];
+    bool ok[NV];
+#pragma unroll
+    for (int n = 0; n < NV; ++n) {
+      const int slot = wave_n * 64 + (n / NG) * TILE + 4 * h + 4 * HL * (n % NG);
+      ok[n] = slot < a.bn_out && t0 + slot < T;
+      t[n] = ok[n] ? t0 + slot : t0;
+    }
+    f32x4 t1[NV], t2[NV], v[NV];
+    float bias = 0.f;
+    if (has_bias) bias = bias_p[c];
+#pragma unroll
+    for (int n = 0; n < NV; ++n) t1[n] = *reinterpret_cast<const f32x4*>(a.x + row + t[n]);
+    if (has2) {
+#pragma unroll
+      for (int n = 0; n < NV; ++n) t2[n] = *reinterpret_cast<const f32x4*>(a.add2 + row + t[n]);
+    }
+#pragma unroll
+    for (int n = 0; n < NV; ++n)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[n][e] = acc[mi][n / NG][(n % NG) * 4 + e];
+    if (has_bias) {
+#pragma unroll
+      for (int n = 0; n < NV; ++n) v[n] += bias;
+    }
+#pragma unroll
+    for (int n = 0; n < NV; ++n) v[n] += t1[n];
+    if (has2) {
+#pragma unroll
+      for (int n = 0; n < NV; ++n) v[n] += t2[n];
+    }
+    if (a.out_div != 1.0f) {
+#pragma unroll
+      for (int n = 0; n < NV; ++n) v[n] = v[n] / a.out_div;
+    }
+#pragma unroll
+    for (int n = 0; n < NV; ++n)
+      if (ok[n]) *reinterpret_cast<f32x4*>(a.y + row + t[n]) = v[n];
+  }
+}
+
+struct RuSplitGeom {
+  int hla, sh, p2, bn_out, rows, tiles;
+  size_t lds;
+};
+
+// Coverage: that of resunit_geometry (resunit.hip) plus what the planes need.  Pure host logic.
+static int ru_split_geometry(const pwg_resunit_desc* d, RuSplitGeom* g) {
+  PWG_REQUIRE(d != nullptr, PWG_ERR_NULL, "resunit_split: NULL descriptor");
+  const int C = d->channels;
+  PWG_REQUIRE(C == 32 || C == 64, PWG_ERR_UNSUPPORTED, "resunit_split: channels = %d (only 32 and 64)", C);
+  PWG_REQUIRE(d->kernel >= 1 && (d->kernel & 1) == 1, PWG_ERR_UNSUPPORTED, "resunit_split: kernel = %d (only odd sizes)",
+              d->kernel);
+  PWG_REQUIRE(d->dilation >= 1, PWG_ERR_UNSUPPORTED, "resunit_split: dilation = %d", d->dilation);
+  PWG_REQUIRE(d->batch >= 1 && d->batch <= 65535, PWG_ERR_UNSUPPORTED, "resunit_split: batch = %d (1 .. 65535)", d->batch);
+  PWG_REQUIRE(d->t >= 4 && (d->t & 3) == 0, PWG_ERR_UNSUPPORTED, "resunit_split: t = %d (a positive multiple of 4)", d->t);
+  PWG_REQUIRE(d->slope1 > 0.f && d->slope1 < 1.f, PWG_ERR_UNSUPPORTED, "resunit_split: slope1 = %g (0 < slope < 1)",
+              (double)d->slope1);
+  PWG_REQUIRE(!d->has_conv2 || (d->slope2 > 0.f && d->slope2 < 1.f), PWG_ERR_UNSUPPORTED,
+              "resunit_split: slope2 = %g (0 < slope < 1)", (double)d->slope2);
+  const int k = d->kernel, H = C == 32 ? RuSplitCfg<32>::H : RuSplitCfg<64>::H;
+  PWG_REQUIRE((long)(k - 1) * d->dilation < (1 << 20), PWG_ERR_UNSUPPORTED, "resunit_split: receptive field too long");
+  g->p2 = d->has_conv2 ? (k - 1) / 2 : 0;
+  const int hl = (k - 1) / 2 * d->dilation + g->p2;
+  g->hla = round_up(hl, 4);
+  g->sh = g->hla - hl;
+  g->bn_out = d->has_conv2 ? ((H - (k - 1)) & ~3) : H;
+  PWG_REQUIRE(g->bn_out >= 64, PWG_ERR_UNSUPPORTED, "resunit_split: kernel = %d leaves %d outputs per tile", k, g->bn_out);
+  g->rows = round_up(H + (k - 1) * d->dilation + g->sh, 4);
+  g->lds = (size_t)3 * g->rows * (C + 8) * sizeof(__bf16);
+  // (two staging items per thread cover every window that fits)
+  PWG_REQUIRE(g->lds <= kRuSplitMaxLds && (g->rows / 4) * (C / 8) <= 512, PWG_ERR_UNSUPPORTED,
+              "resunit_split: the window (kernel %d, dilation %d) needs %zu B of LDS", k, d->dilation, g->lds);
+  g->tiles = ceil_div(d->t, g->bn_out);
+  return PWG_OK;
+}
+
+static int ru_split_forward(const pwg_resunit_desc* d, const float* x, const void* w1, const float* b1, const void* w2,
+                            const float* b2, const float* add2, float* y, int mfma_shape, hipStream_t stream) {
+  RuSplitGeom g;
+  const int rc = ru_split_geometry(d, &g);
+  if (rc != PWG_OK) return rc;
+  PWG_REQUIRE(x && w1 && y, PWG_ERR_NULL, "resunit_split_forward: NULL pointer");
+  PWG_REQUIRE(x != y, PWG_ERR_BAD_SHAPE, "resunit_split_forward: y must not alias x (tiles read their neighbours' halo)");
+  PWG_REQUIRE((d->has_conv2 != 0) == (w2 != nullptr), PWG_ERR_BAD_SHAPE,
+              "resunit_split_forward: has_conv2 = %d but w2_packed is %s", d->has_conv2, w2 ? "given" : "NULL");
+  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
+  PWG_REQUIRE(al16(x) && al16(y) && al16(add2), PWG_ERR_BAD_SHAPE,
+              "resunit_split_forward: x / y / add2 must be 16-B aligned");
+  PWG_REQUIRE(al16(w1) && al16(w2), PWG_ERR_BAD_SHAPE, "resunit_split_forward: the weight images must be 16-B aligned");
+  PWG_REQUIRE(mfma_shape == 16 || mfma_shape == 32, PWG_ERR_BAD_SHAPE, "resunit_split_forward: mfma_shape = %d (16 or 32)",
+              mfma_shape);
+  const int C = d->channels;
+  RuSplitArgs a;
+  a.x = x;
+  a.w1 = static_cast<const bf16x8*>(w1);
+  a.b1 = b1;
+  a.w2 = static_cast<const bf16x8*>(w2);
+  a.b2 = b2;
+  a.add2 = add2;
+  a.y = y;
+  a.T = d->t, a.k = d->kernel, a.d1 = d->dilation;
+  a.bn_out = g.bn_out, a.hla = g.hla, a.sh = g.sh, a.p2 = g.p2, a.rows = g.rows;
+  a.plane = g.rows * (C + 8);
+  a.part_stride = (long)d->kernel * C * C / 8;  // image_elems of a C -> C convolution (m_pad = C, whole chunks)
+  a.slope1 = d->slope1, a.slope2 = d->slope2, a.out_div = d->out_div;
+  void (*kern)(RuSplitArgs) = C == 32 ? (mfma_shape == 32 ? resunit_split_kernel<32, 32> : resunit_split_kernel<32, 16>)
+                                      : (mfma_shape == 32 ? resunit_split_kernel<64, 32> : resunit_split_kernel<64, 16>);
+  if (g.lds > kConvMaxLds && !lds_limit_is_set(reinterpret_cast<const void*>(kern), g.lds)) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)g.lds);
+    PWG_REQUIRE(e == hipSuccess, PWG_ERR_LAUNCH, "resunit_split_forward: cannot raise LDS limit to %zu: %s", g.lds,
+                hipGetErrorString(e));
+  }
+  // the ALGORITHMIC flops and bytes of the unit (those of resunit_forward), whatever the number of part products
+  const double elems = (double)d->batch * C * d->t;
+  const double flops = 2.0 * elems * C * d->kernel * (d->has_conv2 ? 2 : 1);
+  const double bytes = 4.0 * (elems * (2 + (add2 != nullptr)) + (d->has_conv2 ? 2 : 1) * (double)C * C * d->kernel);
+  maybe_poison_lds(stream);
+  {
+    ProfScope prof(stream,
+                   prof_shape_name("resunit_split_kernel", "resunit_split_kernel B%d C%d T%d k%d d%d pair%d", d->batch, C,
+                                   d->t, d->kernel, d->dilation, d->has_conv2),
+                   flops, bytes);
+    hipLaunchKernelGGL(kern, dim3(g.tiles, d->batch), dim3(256), g.lds, stream, a);
+  }
+  PWG_CHECK_LAUNCH("resunit_split_forward");
+  return PWG_OK;
+}
+
+// MFMA shape of pwg_resunit_split_forward
+constexpr int kDefaultMfmaShape = 16;
+
+}  // namespace
+}  // namespace pwg
+
+using namespace pwg;
+
+extern "C" int pwg_resunit_split_supported(const pwg_resunit_desc* d) {
+  RuSplitGeom g;
+  return ru_split_geometry(d, &g) == PWG_OK ? 1 : 0;
+}
+
+extern "C" int pwg_resunit_split_forward(const pwg_resunit_desc* d, const float* x, const void* w1_split, const float* b1,
+                                         const void* w2_split, const float* b2, const float* add2, float* y,
+                                         void* stream) {
+  return ru_split_forward(d, x, w1_split, b1, w2_split, b2, add2, y, kDefaultMfmaShape, (hipStream_t)stream);
+}
+
+extern "C" int pwg_resunit_split_forward_cfg(const pwg_resunit_desc* d, const float* x, const void* w1_split,
+                                             const float* b1, const void* w2_split, const float* b2, const float* add2,
+                                             float* y, int32_t mfma_shape, void* stream) {
+  return ru_split_forward(d, x, w1_split, b1, w2_split, b2, add2, y, mfma_shape, (hipStream_t)stream);
+}

@@ -389,6 +389,39 @@ def split_admitted(c_in, c_out, kernel, cols, needs_grad, enabled=True, admit_al
     return min_cols is not None and cols >= min_cols
 
 
+# Admission table of the split-operand residual units (profiles/resunit_split.txt):
+# (channels, kernel, has_conv2) -> (form, fewest columns per launch = batch x T).  form "unit": one launch of
+# csrc/resunit_split.hip; form "pair": the two general split-operand launches of csrc/conv1d_split.hip that the unit
+# kernel is defined by -- the same bits, and at 64 channels with k = 7 / 11 the faster of the two (1.00 / 1.40 ms
+# against 1.15 / 1.71 ms per unit at 16 x 800 frames).  A class is listed when every run of its form was faster than
+# every run of the incumbent (the fp32 unit; two fp32 convolutions at C = 64, k = 11) and the median gain at 16 x 800
+# frames was >= 1.25 x; the column count is the shortest measured launch on which it still won disjointly, and never
+# under RESUNIT_SPLIT_MIN_COLS.  C = 32, k = 3 gains 1.10 x and stays on the fp32 unit; the single-convolution form was
+# not measured and is not listed.  Classes not listed, and shorter launches, stay where they were.
+RESUNIT_SPLIT_MIN_COLS = 20480
+RESUNIT_SPLIT_ADMITTED = {
+    (64, 3, True): ("unit", 20480),
+    (64, 7, True): ("pair", 20480),
+    (64, 11, True): ("pair", 20480),
+    (32, 7, True): ("unit", 25600),
+    (32, 11, True): ("unit", 25600),
+}
+
+
+def resunit_split_admitted(channels, kernel, has_conv2, cols, needs_grad, enabled=True, admit_all=False):
+    """The admission predicate of the split-operand residual units (pure host logic), the sibling of
+    :func:`split_admitted`: None (never when a gradient is needed or the switch is off), else the form to run --
+    ``"unit"`` for every unit under ``admit_all``, or what ``RESUNIT_SPLIT_ADMITTED`` lists for the class from its column
+    count on.  What the kernels themselves cover is ``ops.resunit_split_supported`` / ``ops.conv1d_split_supported``'s
+    to say."""
+    if needs_grad or not enabled:
+        return None
+    if admit_all:
+        return "unit"
+    form, min_cols = RESUNIT_SPLIT_ADMITTED.get((channels, kernel, bool(has_conv2)), (None, 0))
+    return form if form is not None and cols >= max(min_cols, RESUNIT_SPLIT_MIN_COLS) else None
+
+
 def each_conv(module):
     """Every convolution module (:class:`_ConvNd`) of a module tree."""
     return (m for m in module.modules() if isinstance(m, _ConvNd))

@@ -8,7 +8,7 @@ from .. import functional as Fn
 from .. import ops
 from .activation import FusedActivation
 from .conv import Conv1d as _Conv1d
-from .conv import bf16_no_backward_error, group_image
+from .conv import bf16_no_backward_error, group_image, resunit_split_admitted
 
 
 from .causal_conv import CausalConv1d  # noqa: E402  (depends on .conv only)
@@ -298,7 +298,9 @@ class HiFiGANResidualBlock(torch.nn.Module):
                 self.convs2.append(torch.nn.Sequential(
                     FusedActivation(nonlinear_activation, **nonlinear_activation_params), conv(1)))
 
-    fuse_units = True  # inference: one launch per unit where csrc/resunit.hip covers the geometry (C = 32 / 64)
+    # inference: one launch per unit where csrc/resunit.hip (fp32 MFMA) or csrc/resunit_split.hip (bf16 MFMA, split
+    # operands; admitted classes only) covers the geometry (C = 32 / 64)
+    fuse_units = True
 
     def _unit_one_launch(self, idx, x, accum, out_div):
         """``(x + convs2[idx](convs1[idx](x)) [+ accum]) [/ out_div]`` as ONE kernel launch, or None when the
@@ -320,12 +322,36 @@ class HiFiGANResidualBlock(torch.nn.Module):
             return None  # bf16-operand inference: the unit's convolutions run one by one on csrc/conv1d_bf16.hip
         desc = ops.make_resunit_desc(x.shape[0], x.shape[1], x.shape[2], self.kernel_size, conv1.dilation,
                                      conv2 is not None, act1.slope, slope2, out_div)
-        if not ops.resunit_profitable(desc):
+        # the split-operand forms: the same unit on the bf16 MFMA where the class is admitted, as one
+        # launch of csrc/resunit_split.hip or as the pair of general split launches it is defined by (same bits).  A
+        # gradient is never needed here: checked above
+        convs = (conv1,) if conv2 is None else (conv1, conv2)
+        form = resunit_split_admitted(x.shape[1], self.kernel_size, conv2 is not None, x.shape[0] * x.shape[2], False,
+                                      all(cv.split_exact for cv in convs), all(cv.split_admit_all for cv in convs))
+        if form == "unit" and not ops.resunit_split_supported(desc):
+            form = None
+        if form == "pair":
+            b, t = x.shape[0], x.shape[2]
+            d1 = conv1.make_desc(b, t, pre_act="leaky_relu", pre_slope=act1.slope, post_act="leaky_relu",
+                                 post_slope=slope2)
+            d2 = conv2.make_desc(b, t, out_div=out_div)
+            if not (ops.conv1d_split_supported(d1) and ops.conv1d_split_supported(d2)):
+                form = None
+        if form is None and not ops.resunit_profitable(desc):
             return None
         if callable(accum):
             accum = accum()  # (resolved as late as possible: it may wait for another stream)
         with torch.no_grad():
             x = x.contiguous()
+            accum = None if accum is None else accum.contiguous()
+            b1 = None if conv1.bias is None else conv1.bias.detach()
+            b2 = None if (conv2 is None or conv2.bias is None) else conv2.bias.detach()
+            if form == "unit":
+                return ops.resunit_forward_split(desc, x, conv1.packed_weight_split(), b1,
+                                                 None if conv2 is None else conv2.packed_weight_split(), b2, accum)
+            if form == "pair":
+                h = ops.conv1d_forward_split(d1, x, conv1.packed_weight_split(), b1)
+                return ops.conv1d_forward_split(d2, h, conv2.packed_weight_split(), b2, x, accum)
             return ops.resunit_forward(
                 desc, x, conv1.prepared().res(), None if conv1.bias is None else conv1.bias.detach(),
                 None if conv2 is None else conv2.prepared().res(),

@@ -392,6 +392,36 @@ def resunit_forward(desc, x, w1_packed, b1, w2_packed=None, b2=None, add2=None, 
     return out
 
 
+def resunit_split_supported(desc):
+    """Does the split-operand residual unit (csrc/resunit_split.hip) cover this geometry?  Host logic only (no device
+    needed); ``_lib.lib().pwg_last_error()`` names the reason for a False."""
+    return bool(_lib.lib().pwg_resunit_split_supported(ctypes.byref(desc)))
+
+
+def resunit_forward_split(desc, x, w1_split, b1, w2_split=None, b2=None, add2=None, out=None, mfma_shape=None):
+    """:func:`resunit_forward` computed on the bf16 MFMA from 3-way split operands (inference only).
+    ``w1_split`` / ``w2_split``: the images of :func:`pack_weight_split` for the unit's convolutions; ``mfma_shape``
+    (tuning / tests): 32 or 16 selects the MFMA instruction."""
+    _require_device(x, b1, b2, add2, out)
+    for w in (w1_split, w2_split):
+        if w is not None and (not w.is_cuda or w.dtype != torch.uint8):
+            raise RuntimeError("resunit_forward_split: the weights must be device images of pack_weight_split")
+    assert x.numel() == desc.batch * desc.channels * desc.t
+    image_bytes = 6 * desc.kernel * desc.channels * desc.channels  # three bf16 parts of a (C, C, k) weight
+    for w in (w1_split, w2_split):
+        assert w is None or w.numel() == image_bytes, "resunit_forward_split: not this unit's split image"
+    assert add2 is None or add2.numel() == x.numel()
+    if out is None:
+        out = torch.empty_like(x)
+    args = (ctypes.byref(desc), _ptr(x), _ptr(w1_split), _ptr(b1), _ptr(w2_split), _ptr(b2), _ptr(add2), _ptr(out))
+    if mfma_shape is None:
+        rc = _lib.lib().pwg_resunit_split_forward(*args, _stream())
+    else:
+        rc = _lib.lib().pwg_resunit_split_forward_cfg(*args, int(mfma_shape), _stream())
+    _lib.check(rc, "resunit_split_forward")
+    return out
+
+
 def resstack_supported(channels, t, dilation):
     """Does the one-launch MelGAN residual stack (csrc/resstack.hip) cover this geometry?"""
     return bool(_lib.lib().pwg_resstack_supported(int(channels), int(t), int(dilation)))
