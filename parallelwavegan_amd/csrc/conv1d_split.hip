@@ -6,7 +6,8 @@
 // for finite v whose low parts are not subnormal.  The fused pre-activation is applied to the fp32 input in fp32, then the
 // activated input is split while it is staged; the effective fp32 weight (w * scale) is split once when the weight image
 // is packed.  Per operand pair the products lo.hi, hi.lo, mid.mid, mid.hi, hi.mid, hi.hi (weight part . input part) are
-// issued in this order -- small terms first -- into ONE fp32 accumulator set; each of the three dropped products
+// issued in this order -- small terms first; split_step of mfma_conv.h owns the order, for this kernel and for
+// resunit_split.hip -- into ONE fp32 accumulator set; each of the three dropped products
 // (mid.lo, lo.mid, lo.lo) is <= 2^-24 of the full product in the worst case (|mid| <= 2^-8 |v|, |lo| <= 2^-16 |v|) and
 // about 2^-28 of it on average.  A bf16 x bf16 product is exact in fp32, so what is left is
 // the fp32 accumulation of the MFMA.  bias / add1 / add2 / out_mul / out_div / post-activation / the stored result are
@@ -85,19 +86,10 @@ __device__ __forceinline__ void stage_window_vec(const SplitArgs& a, const float
     if (grp < ngroups) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        bf16x8 vh, vm, vl;
+        float v[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          __bf16 hi, mid, lo;
-          split3(pre_activate(st[it][j][e], a.pre_mul, a.pre_mask), hi, mid, lo);
-          vh[j] = hi;
-          vm[j] = mid;
-          vl[j] = lo;
-        }
-        __bf16* dst = xs + (grp * 4 + e) * kConvRow + oct * 8;
-        *reinterpret_cast<bf16x8*>(dst) = vh;
-        *reinterpret_cast<bf16x8*>(dst + a.plane) = vm;
-        *reinterpret_cast<bf16x8*>(dst + 2 * a.plane) = vl;
+        for (int j = 0; j < 8; ++j) v[j] = pre_activate(st[it][j][e], a.pre_mul, a.pre_mask);
+        split3_store<8>(v, xs + (grp * 4 + e) * kConvRow + oct * 8, a.plane);
         // one column at a time: the scheduler otherwise interleaves all 32 splits and spills the accumulators
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -265,19 +257,9 @@ conv1d_split_mfma_kernel(SplitArgs a) {
             if (tin && c_base + j < a.c_in) f[j] = src[(size_t)j * a.t_in];
           }
         }
-        bf16x8 vh, vm, vl;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          __bf16 hi, mid, lo;
-          split3(pre_activate(f[j], a.pre_mul, a.pre_mask), hi, mid, lo);
-          vh[j] = hi;
-          vm[j] = mid;
-          vl[j] = lo;
-        }
-        __bf16* dst = xs + col * kConvRow + c.wave * 8;
-        *reinterpret_cast<bf16x8*>(dst) = vh;
-        *reinterpret_cast<bf16x8*>(dst + a.plane) = vm;
-        *reinterpret_cast<bf16x8*>(dst + 2 * a.plane) = vl;
+        for (int j = 0; j < 8; ++j) f[j] = pre_activate(f[j], a.pre_mul, a.pre_mask);
+        split3_store<8>(f, xs + col * kConvRow + c.wave * 8, a.plane);
       }
     }
     __syncthreads();
@@ -287,28 +269,9 @@ conv1d_split_mfma_kernel(SplitArgs a) {
         const int oct = ks * HL + c.h;
         const bf16x8* __restrict__ wp =
             image_rows(a.w, a.cin_chunks, a.m_pad, tap, chunk, oct) + c.m0 + c.wave_m * (WM * 32) + c.r;
-        bf16x8 af[PARTS][TM], bfr[PARTS][TN];  // [0] hi, [1] mid, [2] lo
-#pragma unroll
-        for (int p = 0; p < PARTS; ++p)
-#pragma unroll
-          for (int mi = 0; mi < TM; ++mi) af[p][mi] = wp[p * a.part_stride + mi * TILE];
-#pragma unroll
-        for (int ni = 0; ni < TN; ++ni) {
-          const int col = c.sh + c.wave_n * (WN * 32) + ni * TILE + c.r + tap * a.dil;
-          const __bf16* src = xs + col * kConvRow + oct * 8;
-#pragma unroll
-          for (int p = 0; p < PARTS; ++p) bfr[p][ni] = *reinterpret_cast<const bf16x8*>(src + p * a.plane);
-        }
-        // (weight part, input part), small terms first.  The x fragment goes first: the same products summed in the
-        // same order, the tile transposed (a lane gets 4 consecutive samples of a row, split_epilogue)
-        constexpr int PA[6] = {2, 0, 1, 1, 0, 0};
-        constexpr int PB[6] = {0, 2, 1, 0, 1, 0};
-#pragma unroll
-        for (int p = 0; p < 6; ++p)
-#pragma unroll
-          for (int mi = 0; mi < TM; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < TN; ++ni) acc[mi][ni] = Mfma<TILE>::run(bfr[PB[p]][ni], af[PA[p]][mi], acc[mi][ni]);
+        // the x fragment goes first: the transposed tile, a lane gets 4 consecutive samples of a row (split_epilogue)
+        split_step<TILE, TM, TN, kConvRow, true>(wp, a.part_stride, xs, c.sh + c.wave_n * (WN * 32) + c.r + tap * a.dil,
+                                                 oct * 8, a.plane, acc);
       }
     }
   }

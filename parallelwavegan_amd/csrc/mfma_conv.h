@@ -1,14 +1,23 @@
-// What the whole-utterance MFMA convolutions share (conv1d_bf16.hip, conv1d_split.hip and, for the weight image,
-// conv1d_stream_bf16.hip): everything that has to agree between the kernels is stated here, once.
+// What the whole-utterance MFMA convolutions share (conv1d_bf16.hip, conv1d_split.hip; for the weight image also
+// conv1d_stream_bf16.hip; for the split image and the split arithmetic also resunit_split.hip): everything that has to
+// agree between the kernels is stated here, once.
 //   chunk, LDS row        KC, kConvRow, plane_rows   32 channels per staged chunk; rows of 80 B; rows of a column tile
 //   coverage, tile rule   mfma_conv_geometry         128 / 64 / 32 rows x 128 / 128 / 256 columns from the GEMM rows
-//   weight image          image_elems, image_decode, image_rows, mfma_conv_pack   [tap][ci / 8][m_pad][8] per part
+//   weight image          image_chunks, image_m_pad, image_elems, image_decode, image_rows, mfma_conv_pack
+//                                                    [tap][ci / 8][m_pad][8] per part
+//   split arithmetic      split3, split3_store, split_step   the 3-way split of a value; N values split and stored, a
+//                                                    vector per plane; one reduction step of the six part products.
+//                                                    split_step OWNS the product order of conv1d_split.hip and
+//                                                    resunit_split.hip, which must agree to the bit
 //   launch plan           mfma_conv_plan             half-size tiles for short inputs, grid, LDS, vector staging
 //   tile ladder           mfma_conv_launch           the five tiles x two MFMA shapes of a kernel family
 //   arguments             MfmaConvArgs, mfma_conv_fill_args, mfma_conv_check_forward
 //   tile coordinates      MfmaConvTile               thread, wave and window coordinates of a workgroup
-// Internal to csrc/; the staging conversions, the contractions and the epilogues of the kernels differ on purpose and
-// stay with them.  The stream kernel reads the bf16 image with its own tiles and LDS row (conv1d_stream_bf16.hip).
+// Internal to csrc/.  What stays with the kernels, on purpose: the bf16 kernel's contraction (one product, its own
+// operand pipeline); every kernel's chunk / tap / k-step loops, barriers and staging loads (shared forms of the loads
+// changed the VGPR counts, profiles/refactor_mfma_conv_resources.txt); the epilogues (the unit masks slot < bn_out and
+// clamps to t0, the conv clamps to nq - 4 and has a FULL form: different loads).  conv1d_bf16.hip instantiates none of the
+// split arithmetic.  The stream kernel reads the bf16 image with its own tiles and LDS row (conv1d_stream_bf16.hip).
 #pragma once
 #include "common.h"
 
@@ -29,6 +38,12 @@ static inline int plane_rows(int nt, int halo) { return round_up(nt + halo + 3, 
 static inline size_t conv_lds_bytes(int parts, int nt, int halo) {
   return (size_t)parts * plane_rows(nt, halo) * kConvRow * sizeof(__bf16);
 }
+
+// The row tile of a configuration and what the weight image pads to: rows to the row tile, channels to whole chunks.
+// constexpr: resunit_split.hip reads the image of a C -> C convolution with C a template parameter.
+constexpr int conv_row_tile(int m) { return m <= 32 ? 32 : (m <= 64 ? 64 : 128); }
+constexpr int image_m_pad(int m) { return (m + conv_row_tile(m) - 1) / conv_row_tile(m) * conv_row_tile(m); }
+constexpr int image_chunks(int c_in) { return (c_in + KC - 1) / KC; }
 
 // ---- coverage and tile rule.  Contraction: Y[m][q] = sum_{tap, ci} W[m][tap][ci] * X[ci][q + x_off + tap * dil]
 //   Conv1d (stride 1):           m = output channel, q = output column, taps = kernel, x_off = -pad_left
@@ -74,10 +89,10 @@ static inline int mfma_conv_geometry(const char* name, int parts, bool allow_tra
     PWG_REQUIRE(d->stride == 1, PWG_ERR_UNSUPPORTED, "%s: stride = %d (only stride 1)", name, d->stride);
     *g = MfmaConvGeom{d->kernel, d->dilation, -d->pad_left, d->c_out, 0, 0, 1, 0, d->t_out};
   }
-  g->mt = g->m <= 32 ? 32 : (g->m <= 64 ? 64 : 128);
+  g->mt = conv_row_tile(g->m);
   g->nt = g->m <= 32 ? 256 : 128;
-  g->m_pad = round_up(g->m, g->mt);
-  g->cin_chunks = ceil_div(d->c_in, KC);
+  g->m_pad = image_m_pad(g->m);
+  g->cin_chunks = image_chunks(d->c_in);
   // Only the split kernel bounds the window before it sizes it, and only it falls back to half-size tiles for LDS alone
   // (the bf16 kernel refuses such a window; admitting it there would be a new rule)
   PWG_REQUIRE(parts == 1 || (long)(g->taps - 1) * g->dil < (1 << 20), PWG_ERR_UNSUPPORTED, "%s: receptive field too long",
@@ -94,7 +109,8 @@ static inline int mfma_conv_geometry(const char* name, int parts, bool allow_tra
 // ---- weight image.  One part is [tap][ci / 8][m_pad][8] bf16: rows padded to the row tile (g.m_pad), channels to whole
 // chunks, padding zero; a lane's A fragment is 16 B and a half wave reads 512 B contiguous.  The split kernel's image is
 // three parts (hi, mid, lo) of image_elems() each, one after the other.
-static inline long image_elems(const MfmaConvGeom& g) { return (long)g.taps * g.cin_chunks * KC * g.m_pad; }
+constexpr long image_elems(int taps, int cin_chunks, int m_pad) { return (long)taps * cin_chunks * KC * m_pad; }
+static inline long image_elems(const MfmaConvGeom& g) { return image_elems(g.taps, g.cin_chunks, g.m_pad); }
 
 struct ImageIndex {
   int tap, ci, row;
@@ -113,13 +129,69 @@ __device__ __forceinline__ const bf16x8* image_rows(const bf16x8* w, int cin_chu
   return w + ((size_t)(tap * cin_chunks + chunk) * (KC / 8) + oct) * m_pad;
 }
 
-// The exact 3-way split of an fp32 value (numerical definition: conv1d_split.hip, which is built without FMA
-// contraction for it)
+// ---- split-operand arithmetic (numerical definition: conv1d_split.hip; a translation unit that uses it is built
+// without FMA contraction).  The exact 3-way split of an fp32 value:
 __device__ __forceinline__ void split3(float v, __bf16& hi, __bf16& mid, __bf16& lo) {
   hi = (__bf16)v;
   const float r = v - (float)hi;
   mid = (__bf16)r;
   lo = (__bf16)(r - (float)mid);
+}
+
+// Split N (8 or 4) fp32 values and write one N-wide vector per plane: hi at dst, mid at dst + plane, lo at
+// dst + 2 * plane.  The values are final: the caller has applied its activation.
+template <int N>
+__device__ __forceinline__ void split3_store(const float (&v)[N], __bf16* dst, int plane) {
+  typedef __bf16 vec_t __attribute__((ext_vector_type(N)));
+  vec_t vh, vm, vl;
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    __bf16 hi, mid, lo;
+    split3(v[j], hi, mid, lo);
+    vh[j] = hi;
+    vm[j] = mid;
+    vl[j] = lo;
+  }
+  *reinterpret_cast<vec_t*>(dst) = vh;
+  *reinterpret_cast<vec_t*>(dst + plane) = vm;
+  *reinterpret_cast<vec_t*>(dst + 2 * plane) = vl;
+}
+
+// One reduction step (the lane's 8 channels of one tap) of a split-operand contraction, for a wave's TM x TN MFMA tiles:
+// loads the 3 x TM weight fragments and the 3 x TN plane fragments and issues the 6 x TM x TN MFMAs.  This is the ONE
+// statement of the product order -- (weight part, input part) = lo.hi, hi.lo, mid.mid, mid.hi, hi.mid, hi.hi, small terms
+// first -- that conv1d_split_mfma_kernel and resunit_split_kernel share, so that a unit equals two chained convolutions
+// bit for bit by construction.
+//   wp, part_stride  the lane's row of tile mi = 0 in the part-0 (hi) image at this tap / chunk / octet (image_rows),
+//                    bf16x8 elements per part image
+//   xs, col, off     plane 0 (hi), the lane's column of tile ni = 0 at this tap (a caller may have folded part of it
+//                    into xs), element offset of its 8 channels in an LDS row of ROW elements; plane: elements per plane
+// XFIRST: the plane fragment is the first MFMA operand: the same products summed in the same order, the tile transposed
+// (a lane gets 4 consecutive samples of a row instead of 4 consecutive rows of a column).
+template <int TILE, int TM, int TN, int ROW, bool XFIRST>
+__device__ __forceinline__ void split_step(const bf16x8* __restrict__ wp, long part_stride, const __bf16* xs, int col,
+                                           int off, int plane, typename Mfma<TILE>::acc_t (&acc)[TM][TN]) {
+  bf16x8 af[3][TM], bfr[3][TN];  // [0] hi, [1] mid, [2] lo
+#pragma unroll
+  for (int p = 0; p < 3; ++p)
+#pragma unroll
+    for (int mi = 0; mi < TM; ++mi) af[p][mi] = wp[p * part_stride + mi * TILE];
+#pragma unroll
+  for (int ni = 0; ni < TN; ++ni) {
+    const __bf16* src = xs + (col + ni * TILE) * ROW + off;
+#pragma unroll
+    for (int p = 0; p < 3; ++p) bfr[p][ni] = *reinterpret_cast<const bf16x8*>(src + p * plane);
+  }
+  constexpr int PA[6] = {2, 0, 1, 1, 0, 0};
+  constexpr int PB[6] = {0, 2, 1, 0, 1, 0};
+#pragma unroll
+  for (int p = 0; p < 6; ++p)
+#pragma unroll
+    for (int mi = 0; mi < TM; ++mi)
+#pragma unroll
+      for (int ni = 0; ni < TN; ++ni)
+        acc[mi][ni] = XFIRST ? Mfma<TILE>::run(bfr[PB[p]][ni], af[PA[p]][mi], acc[mi][ni])
+                             : Mfma<TILE>::run(af[PA[p]][mi], bfr[PB[p]][ni], acc[mi][ni]);
 }
 
 // One thread per element of ONE part image.  PARTS == 1 stores the rounded effective weight w * scale, PARTS == 3 its

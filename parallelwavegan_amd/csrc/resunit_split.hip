@@ -10,8 +10,9 @@
 // Numerical definition (include/pwg_kernels.h, "split-operand residual unit"): lrelu(x) is formed in fp32 and split with
 // split3 while the window is staged; the effective weights are split once by pwg_conv1d_split_pack_weight (the same
 // image); per operand pair the products lo.hi, hi.lo, mid.mid, mid.hi, hi.mid, hi.hi (weight part . input part) go, in
-// this order, into one fp32 accumulator set; h = lrelu(acc + b1) is formed in fp32, is zero outside [0, T) and is split
-// with split3; the residual is the raw fp32 x and the epilogue is acc + bias + x + add2, then / out_div.
+// this order, into one fp32 accumulator set (split_step of mfma_conv.h owns the order, for this kernel and for
+// conv1d_split.hip); h = lrelu(acc + b1) is formed in fp32, is zero outside [0, T) and is split with split3; the
+// residual is the raw fp32 x and the epilogue is acc + bias + x + add2, then / out_div.
 // The accumulation order of an output element is the split kernel's: 32-channel chunk, tap, reduction step, product.  A
 // unit is therefore bit-identical to two chained pwg_conv1d_split_forward_cfg launches at the same MFMA shape (conv1 with
 // pre_act = post_act = leaky and bias b1; conv2 with bias b2, add1 = x, add2, out_div): that chain is the test oracle.
@@ -36,8 +37,6 @@
 
 namespace pwg {
 namespace {
-
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 constexpr size_t kRuSplitMaxLds = 80 * 1024;  // two workgroups per 160 KB CU
 
@@ -67,6 +66,7 @@ struct RuSplitCfg {
   static constexpr int H = WAVES_N * 64;  // h-columns / output slots per workgroup
   static constexpr int ROW = C + 8;       // bf16 elements per LDS row
   static constexpr int OCTS = C / 8;
+  static constexpr int CHUNKS = image_chunks(C), M_PAD = image_m_pad(C);  // the image of a C -> C convolution
 };
 
 // Stage the whole C-channel window: item = (group of 4 columns, channel octet), at most two per thread: 8 loads of 16 B
@@ -98,65 +98,37 @@ __device__ __forceinline__ void ru_stage_window(const RuSplitArgs& a, const floa
     if (idx < nitems) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        bf16x8 vh, vm, vl;
+        float v[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-          const float v = st[it][j][e];
-          __bf16 hi, mid, lo;
-          split3(v > 0.f ? v : v * a.slope1, hi, mid, lo);
-          vh[j] = hi;
-          vm[j] = mid;
-          vl[j] = lo;
+          const float s = st[it][j][e];
+          v[j] = s > 0.f ? s : s * a.slope1;
         }
-        __bf16* dst = xs + (grp * 4 + e) * ROW + oct * 8;
-        *reinterpret_cast<bf16x8*>(dst) = vh;
-        *reinterpret_cast<bf16x8*>(dst + a.plane) = vm;
-        *reinterpret_cast<bf16x8*>(dst + 2 * a.plane) = vl;
+        split3_store<8>(v, xs + (grp * 4 + e) * ROW + oct * 8, a.plane);
         __builtin_amdgcn_sched_barrier(0);  // one column at a time (conv1d_split.hip, stage_window_vec)
       }
     }
   }
 }
 
-// acc += W (*) B over (chunk, tap, reduction step, product): the order of conv1d_split_mfma_kernel.  wl: the part-0 image
-// at this lane's weight row; bl: plane 0 at this lane's column of tile 0, tap 0; tap_step: columns per tap.
-// XFIRST: the B fragment is the first MFMA operand (transposed tile).
+// acc += W (*) B over (chunk, tap, reduction step): the loop order of conv1d_split_mfma_kernel around the split_step the
+// two kernels share (mfma_conv.h).  wl: the part-0 image at this lane's weight row; bl: plane 0 at this lane's column of
+// tile 0, tap 0; tap_step: columns per tap.  XFIRST: the B fragment is the first MFMA operand (transposed tile).
 template <int C, int TILE, bool XFIRST>
 __device__ __forceinline__ void ru_contract(const bf16x8* __restrict__ wl, long part_stride, const __bf16* bl, int plane,
                                             int tap_step, int taps, int h,
                                             typename Mfma<TILE>::acc_t (&acc)[32 / TILE][64 / TILE]) {
+  using Cfg = RuSplitCfg<C>;
   constexpr int HL = 64 / TILE, KSTEPS = KC / (8 * HL), TM = 32 / TILE, TN = 64 / TILE;
-  constexpr int ROW = RuSplitCfg<C>::ROW, CHUNKS = C / KC;
 #pragma unroll 1
-  for (int chunk = 0; chunk < CHUNKS; ++chunk) {
+  for (int chunk = 0; chunk < Cfg::CHUNKS; ++chunk) {
 #pragma unroll 1
     for (int tap = 0; tap < taps; ++tap) {
 #pragma unroll
       for (int ks = 0; ks < KSTEPS; ++ks) {
         const int oct = ks * HL + h;
-        const bf16x8* __restrict__ wp = image_rows(wl, CHUNKS, C, tap, chunk, oct);
-        bf16x8 af[3][TM], bfr[3][TN];  // [0] hi, [1] mid, [2] lo
-#pragma unroll
-        for (int p = 0; p < 3; ++p)
-#pragma unroll
-          for (int mi = 0; mi < TM; ++mi) af[p][mi] = wp[p * part_stride + mi * TILE];
-#pragma unroll
-        for (int ni = 0; ni < TN; ++ni) {
-          const __bf16* src = bl + (ni * TILE + tap * tap_step) * ROW + chunk * KC + oct * 8;
-#pragma unroll
-          for (int p = 0; p < 3; ++p) bfr[p][ni] = *reinterpret_cast<const bf16x8*>(src + p * plane);
-        }
-        // (weight part, input part), small terms first
-        constexpr int PA[6] = {2, 0, 1, 1, 0, 0};
-        constexpr int PB[6] = {0, 2, 1, 0, 1, 0};
-#pragma unroll
-        for (int p = 0; p < 6; ++p)
-#pragma unroll
-          for (int mi = 0; mi < TM; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < TN; ++ni)
-              acc[mi][ni] = XFIRST ? Mfma<TILE>::run(bfr[PB[p]][ni], af[PA[p]][mi], acc[mi][ni])
-                                   : Mfma<TILE>::run(af[PA[p]][mi], bfr[PB[p]][ni], acc[mi][ni]);
+        const bf16x8* __restrict__ wp = image_rows(wl, Cfg::CHUNKS, Cfg::M_PAD, tap, chunk, oct);
+        split_step<TILE, TM, TN, Cfg::ROW, XFIRST>(wp, part_stride, bl, tap * tap_step, chunk * KC + oct * 8, plane, acc);
       }
     }
   }
@@ -219,24 +191,16 @@ __global__ __launch_bounds__(256, 2) void resunit_split_kernel(RuSplitArgs a) {
           const int m = wave_n * 64 + ni * TILE + r;
           const int th = t0 - a.p2 + m;
           const bool inside = th >= 0 && th < T;
-          bf16x4 vh, vm, vl;
+          float v[4];
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            float v = acc[mi][ni][4 * g + e];
-            if (has_b1) v += bias[e];
-            v = v > 0.f ? v : v * a.slope2;
-            v = inside ? v : 0.f;
-            __bf16 hi, mid, lo;
-            split3(v, hi, mid, lo);
-            vh[e] = hi;
-            vm[e] = mid;
-            vl[e] = lo;
+            v[e] = acc[mi][ni][4 * g + e];
+            if (has_b1) v[e] += bias[e];
+            v[e] = v[e] > 0.f ? v[e] : v[e] * a.slope2;
+            v[e] = inside ? v[e] : 0.f;
             acc[mi][ni][4 * g + e] = 0.f;
           }
-          __bf16* dst = xs + m * ROW + c;
-          *reinterpret_cast<bf16x4*>(dst) = vh;
-          *reinterpret_cast<bf16x4*>(dst + a.plane) = vm;
-          *reinterpret_cast<bf16x4*>(dst + 2 * a.plane) = vl;
+          split3_store<4>(v, xs + m * ROW + c, a.plane);
         }
       }
     // h columns H .. H + k - 2 feed only the discarded output slots past bn_out: zeros, not what x left there
@@ -372,7 +336,7 @@ static int ru_split_forward(const pwg_resunit_desc* d, const float* x, const voi
   a.T = d->t, a.k = d->kernel, a.d1 = d->dilation;
   a.bn_out = g.bn_out, a.hla = g.hla, a.sh = g.sh, a.p2 = g.p2, a.rows = g.rows;
   a.plane = g.rows * (C + 8);
-  a.part_stride = (long)d->kernel * C * C / 8;  // image_elems of a C -> C convolution (m_pad = C, whole chunks)
+  a.part_stride = image_elems(d->kernel, image_chunks(C), image_m_pad(C)) / 8;  // of the image RuSplitCfg<C> describes
   a.slope1 = d->slope1, a.slope2 = d->slope2, a.out_div = d->out_div;
   void (*kern)(RuSplitArgs) = C == 32 ? (mfma_shape == 32 ? resunit_split_kernel<32, 32> : resunit_split_kernel<32, 16>)
                                       : (mfma_shape == 32 ? resunit_split_kernel<64, 32> : resunit_split_kernel<64, 16>);

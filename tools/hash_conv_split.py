@@ -1,15 +1,18 @@
 """SHA-256 of the output bytes of the MFMA convolutions (csrc/conv1d_split.hip, csrc/conv1d_bf16.hip and, for the bf16
-weight image it reads, csrc/conv1d_stream_bf16.hip) on a fixed case list, as JSON on stdout: what a change of the
-kernels that must not change a bit is compared by (run this file on both checkouts and compare the two objects).  GPU
-box only.  Every input is seeded on the CPU.
+weight image it reads, csrc/conv1d_stream_bf16.hip) and of the split-operand residual unit (csrc/resunit_split.hip) on a
+fixed case list, as JSON on stdout: what a change of the kernels that must not change a bit is compared by (run this file
+on both checkouts and compare the two objects).  GPU box only.  Every input is seeded on the CPU.
 The split cases (the packed images are hashed next to the outputs): those of tests/test_conv_split_gpu.py (default
 launch and 32x32x16); those of tests/test_conv_split_pipeline_gpu.py, whose shape / variant tables live here so that this
 file also runs on a checkout that has no such test (default launch, tile_mode 1 / 2, 32x32x16, and the launches with one
 operand 4 bytes off a 16-byte boundary); and the four admitted classes (128 / 256 channels, k = 7 / 11) at one utterance
 of 100 frames with dilations 1 and 5, at tile_mode 0 / 1 / 2 and both MFMA shapes.
 The bf16 cases: every case of tests/test_conv_bf16_gpu.py::ALL, the packed image and the output at both MFMA shapes;
-and pushes through the bf16 stream kernel on layers whose rows are padded in the image (y and hist_out)."""
+and pushes through the bf16 stream kernel on layers whose rows are padded in the image (y and hist_out).
+The unit cases: the CASES of tests/test_resunit_split_gpu.py with that file's inputs, the table kept here as for the
+pipeline cases; ``ops.resunit_forward_split`` at both MFMA shapes."""
 import hashlib
+import itertools
 import json
 import os
 import sys
@@ -240,6 +243,59 @@ def hash_stream_bf16(out, dev):
             hist = hist_out
 
 
+# (C, k, d, pair, batch, T, variant, kind): the CASES of tests/test_resunit_split_gpu.py
+UNIT_KD = [(3, 1), (3, 5), (7, 3), (11, 1), (11, 5)]
+UNIT_BT = [(2, 100), (3, 1000), (2, 4148)]
+UNIT_VARIANTS = {
+    "plain": dict(bias=False, add2=False, out_div=1.0),
+    "all": dict(bias=True, add2=True, out_div=3.0),
+    "bias": dict(bias=True, add2=False, out_div=1.0),
+    "add2": dict(bias=False, add2=True, out_div=1.0),
+    "div3": dict(bias=False, add2=False, out_div=3.0),
+}
+UNIT_CASES = ([(c, k, d, pair, b, t, v, "randn") for c, (k, d), pair, (b, t), v
+               in itertools.product((32, 64), UNIT_KD, (True, False), UNIT_BT, ("plain", "all"))]
+              + [(32, 7, 3, True, 3, 1000, v, "randn") for v in ("bias", "add2", "div3")]
+              + [(64, 3, 5, False, 3, 1000, v, "randn") for v in ("bias", "add2", "div3")]
+              + [(64, 7, 3, True, 3, 1000, "all", "wide"), (32, 11, 5, True, 3, 1000, "plain", "wide"),
+                 (64, 11, 5, True, 3, 1000, "plain", "cancel"), (32, 7, 3, True, 3, 1000, "all", "cancel")])
+
+
+def unit_inputs(c, k, b, t, kind):
+    """CPU float32 operands of a unit case (tests/test_resunit_split_gpu.py::_inputs)."""
+    g = torch.Generator().manual_seed(c * 100003 + k * 1009 + b * 101 + t + len(kind))
+    x = torch.randn(b, c, t, generator=g)
+    w1 = torch.randn(c, c, k, generator=g) / (c * k) ** 0.5
+    w2 = torch.randn(c, c, k, generator=g) / (c * k) ** 0.5
+    if kind == "wide":
+        e = torch.linspace(-20, 20, c)[torch.randperm(c, generator=g)]
+        x = x * torch.exp2(e.round()).view(1, -1, 1)
+    if kind == "cancel":
+        u = torch.rand(b, c // 2, t, generator=g) * 2 - 1
+        x[:, 1::2] = x[:, 0::2] * (1 + u / 16)
+        w1[:, 1::2] = -w1[:, 0::2]
+    return dict(x=x, w1=w1, w2=w2, b1=torch.randn(c, generator=g), b2=torch.randn(c, generator=g),
+                add2=torch.randn(b, c, t, generator=g))
+
+
+def hash_unit(out, dev):
+    from parallelwavegan_amd import ops
+
+    for c, k, d, pair, b, t, variant, kind in UNIT_CASES:
+        i, v = unit_inputs(c, k, b, t, kind), UNIT_VARIANTS[variant]
+        desc = ops.make_resunit_desc(b, c, t, k, d, pair, 0.1, 0.1, v["out_div"])
+        wdesc = ops.make_conv_desc(1, c, c, 64, 64, k, pad_left=(k - 1) // 2)
+        i1 = ops.pack_weight_split(wdesc, i["w1"].to(dev))
+        i2 = ops.pack_weight_split(wdesc, i["w2"].to(dev)) if pair else None
+        b1 = i["b1"].to(dev) if v["bias"] else None
+        b2 = i["b2"].to(dev) if v["bias"] and pair else None
+        add2 = i["add2"].to(dev) if v["add2"] else None
+        name = "unit/c%d_k%d_d%d_%s_b%d_t%d-%s-%s" % (c, k, d, "pair" if pair else "single", b, t, variant, kind)
+        for shp in (16, 32):
+            y = ops.resunit_forward_split(desc, i["x"].to(dev), i1, b1, i2, b2, add2, mfma_shape=shp)
+            out[f"{name}/mfma{shp}"] = sha(y)
+
+
 if __name__ == "__main__":
     dev = torch.device("cuda:0")
     hashes = {}
@@ -248,4 +304,5 @@ if __name__ == "__main__":
     hash_admitted(hashes, dev)
     hash_bf16(hashes, dev)
     hash_stream_bf16(hashes, dev)
+    hash_unit(hashes, dev)
     print(json.dumps({"hashes": len(hashes), "sha256": hashes}, indent=1, sort_keys=True))
