@@ -75,7 +75,7 @@ float concurrency_hint();
 
 // gconv.hip: grouped k = 41 strided convolutions with 4 / 8 input channels per group on the 16 x 16 x 4 MFMA
 // (`d` is always the FORWARD descriptor of the layer)
-bool gconv_forward_applicable(const pwg_conv1d_desc* d, const float* add1, const float* add2);
+bool gconv_forward_applicable(const pwg_conv1d_desc* d, bool has_addends);
 int gconv_forward(const pwg_conv1d_desc* d, const float* x, const float* wp, const float* bias, float* y, hipStream_t stream);
 bool gconv_dgrad_applicable(const pwg_conv1d_desc* d);
 int gconv_backward_data(const pwg_conv1d_desc* d, const float* dy, const float* wp_bwd, const float* x_fwd, const float* accum,

@@ -1232,32 +1232,75 @@ static int make_geometry(const pwg_conv1d_desc* d, Geometry* g) {
   return PWG_OK;
 }
 
-// configurations that also have FAST instantiations (the ones the heuristic picks for the G stacks)
-template <int WM, int WN, int WAVES_M, int WAVES_N, int CK>
-struct HasFast {
-  static constexpr bool value = (WM == 2 && WN == 2 && WAVES_M == 2 && WAVES_N == 2 && CK == 4) ||   // 128x128x4
-                                (WM == 2 && WN == 1 && WAVES_M == 2 && WAVES_N == 2 && CK == 8) ||   // 128x64x8
-                                (WM == 1 && WN == 1 && WAVES_M == 1 && WAVES_N == 4 && CK == 8) ||   // 32x128x8
-                                (WM == 2 && WN == 2 && WAVES_M == 1 && WAVES_N == 4 && CK == 4) ||   // 64x256x4
-                                (WM == 1 && WN == 2 && WAVES_M == 2 && WAVES_N == 2 && CK == 8) ||   // 64x128x8
-                                (WM == 1 && WN == 1 && WAVES_M == 2 && WAVES_N == 2 && CK == 8) ||   // 64x64x8
-                                (WM == 1 && WN == 1 && WAVES_M == 2 && WAVES_N == 2 && CK == 16) ||  // 64x64x16
-                                (WM == 1 && WN == 1 && WAVES_M == 1 && WAVES_N == 4 && CK == 16) ||  // 32x128x16
-                                (WM == 1 && WN == 1 && WAVES_M == 2 && WAVES_N == 2 && CK == 4) ||   // 64x64x4 (k = 41 groups)
-                                (WM == 2 && WN == 2 && WAVES_M == 2 && WAVES_N == 4 && (CK == 4 || CK == 8));  // 128x256, 8 waves
+// Tile configurations (id -> instantiation); tools/bench_conv.py sweeps them.  (The 2x4-accumulator
+// tiles of round 1 needed scratch and never won a sweep: removed.)  Last column: the tile also has FAST instantiations
+// (the ones the heuristic picks for the G stacks; 17 = 64x64x4 for the k = 41 groups, 18 / 19 = 128x256, 8 waves).
+struct TileCfg {
+  int bm, bn, ck;
+  int wm, wn;  // 32x32 accumulator tiles per wave
+  int waves;   // waves per workgroup (4, or 8 for the 128x256 tiles: one workgroup per CU)
+  bool has_fast;
 };
+#define PWG_CONV_CFGS(X)         \
+  X(0, 2, 2, 2, 2, 8, false)     \
+  X(1, 2, 2, 2, 2, 16, false)    \
+  X(2, 2, 2, 2, 2, 4, true)      \
+  X(3, 2, 2, 1, 4, 8, false)     \
+  X(4, 2, 2, 1, 4, 16, false)    \
+  X(5, 1, 2, 1, 4, 8, false)     \
+  X(6, 1, 2, 1, 4, 16, false)    \
+  X(7, 1, 4, 1, 4, 8, false)     \
+  X(8, 1, 4, 1, 4, 16, false)    \
+  X(9, 2, 1, 2, 2, 8, true)      \
+  X(10, 1, 1, 1, 4, 8, true)     \
+  X(11, 2, 2, 1, 4, 4, true)     \
+  X(12, 1, 2, 2, 2, 8, true)     \
+  X(13, 1, 1, 2, 2, 8, true)     \
+  X(14, 1, 1, 4, 1, 8, false)    \
+  X(15, 1, 1, 2, 2, 16, true)    \
+  X(16, 1, 1, 1, 4, 16, true)    \
+  X(17, 1, 1, 2, 2, 4, true)     \
+  X(18, 2, 2, 2, 4, 4, true)     \
+  X(19, 2, 2, 2, 4, 8, true)
+static const int kNumCfgs = 20;
 
-template <int WM, int WN, int WAVES_M, int WAVES_N, int CK>
-static void (*pick_dma_kernel(bool fast, int act))(ConvArgs) {
-  if constexpr (HasFast<WM, WN, WAVES_M, WAVES_N, CK>::value) {
-    if (fast) {
-      if (act == 0) return conv1d_mfma_dma_kernel<WM, WN, WAVES_M, WAVES_N, CK, true, 0>;
-      if (act == 1) return conv1d_mfma_dma_kernel<WM, WN, WAVES_M, WAVES_N, CK, true, 1>;
-      return conv1d_mfma_dma_kernel<WM, WN, WAVES_M, WAVES_N, CK, true, 2>;
-    }
+// ---- (tile, staging path, FAST, pre-activation variant) -> kernel: the only templated host code.  Names every
+// instantiation there is; a combination without one is nullptr (conv_describe refuses it), never a neighbour.
+// (hipcc lays the kernels out in the order the host code first names them, and their bytes depend on the layout: per
+// tile the FAST variants, the generic DMA kernel, the register-staged kernel -- profiles/refactor_conv_dispatch.txt) ----
+using ConvKernel = void (*)(ConvArgs);
+struct Tile {
+  TileCfg cfg;
+  ConvKernel fast[3];  // LDS-DMA, FAST row stride; pre-activation none / LeakyReLU with 0 < slope < 1 / any
+  ConvKernel dma;      // LDS-DMA, any geometry and pre-activation
+  ConvKernel reg;      // register-staged
+};
+template <int WM, int WN, int WAVES_M, int WAVES_N, int CK, bool FAST>
+static Tile make_tile() {
+  Tile t = {{32 * WM * WAVES_M, 32 * WN * WAVES_N, CK, WM, WN, WAVES_M * WAVES_N, FAST}, {}, nullptr, nullptr};
+  if constexpr (FAST) {
+    t.fast[0] = conv1d_mfma_dma_kernel<WM, WN, WAVES_M, WAVES_N, CK, true, 0>;
+    t.fast[1] = conv1d_mfma_dma_kernel<WM, WN, WAVES_M, WAVES_N, CK, true, 1>;
+    t.fast[2] = conv1d_mfma_dma_kernel<WM, WN, WAVES_M, WAVES_N, CK, true, 2>;
   }
-  return conv1d_mfma_dma_kernel<WM, WN, WAVES_M, WAVES_N, CK, false, 2>;
+  t.dma = conv1d_mfma_dma_kernel<WM, WN, WAVES_M, WAVES_N, CK, false, 2>;
+  t.reg = conv1d_mfma_kernel<WM, WN, WAVES_M, WAVES_N, CK>;
+  return t;
 }
+static const Tile& tile(int id) {  // (0 <= id < kNumCfgs)
+#define X(ID, WM, WN, WVM, WVN, CK, FAST) make_tile<WM, WN, WVM, WVN, CK, FAST>(),
+  static const Tile tab[kNumCfgs] = {PWG_CONV_CFGS(X)};
+#undef X
+  return tab[id];
+}
+static TileCfg cfg_info(int id) { return tile(id).cfg; }
+static ConvKernel conv_kernel(int id, bool dma, bool fast, int act) {
+  if (id < 0 || id >= kNumCfgs || act < 0 || act > 2 || (fast && !dma)) return nullptr;
+  return !dma ? tile(id).reg : fast ? tile(id).fast[act] : tile(id).dma;
+}
+
+// The FAST geometry: stride 1, width 1 and a halo of at most 64 samples, so that an x row of any tile is BN + 64 floats.
+static bool fast_geometry(const Geometry& g, int W) { return g.stride == 1 && W == 1 && (g.k_phase - 1) * g.dil <= 64; }
 
 // LDS behind the two chunk buffers for the epilogue's transposition scratch: none for split-K launches (their
 // epilogue stores raw partial sums, no transposition) and none when the scratch fits the dead chunk buffer (mirrors
@@ -1266,6 +1309,32 @@ static size_t scratch_bytes_needed(size_t buf_bytes, size_t scr_bytes, int cin_g
   if (ksplit > 1) return 0;
   return (buf_bytes >= scr_bytes && ceil_div(cin_g, ck) >= 2) ? 0 : scr_bytes;
 }
+
+// LDS layout of a tile: x-row stride (floats), one chunk buffer, the transposition scratch, the launch's dynamic LDS.
+// The launcher takes it exactly.  The planner takes it as a bound, before it has settled tile and split, which differs
+// in two ways: the FAST stride wherever the geometry allows (also for a tile without FAST kernels), and the scratch of
+// an unsplit launch.
+struct TileLayout {
+  int xs_stride;
+  size_t buf, scr, lds;
+  bool fast;
+};
+static TileLayout tile_layout(const TileCfg& c, const Geometry& g, int W, bool dma, int ksplit, bool bound = false) {
+  TileLayout l;
+  const int rows = (W == 1) ? c.bn : ((c.bn - 1) / W + 2);
+  const int xs_len = ((rows - 1) * g.stride + (g.k_phase - 1) * g.dil + 1) * W;
+  l.fast = dma && (bound || c.has_fast) && fast_geometry(g, W);
+  // DMA variant: whole 64-lane pieces per row; register variant: 16-B aligned weight tile
+  l.xs_stride = l.fast ? c.bn + 64 : dma ? round_up(xs_len, 64) : round_up(xs_len, 4);
+  l.buf = ((size_t)c.ck * l.xs_stride + (size_t)g.k_phase * c.ck * c.bm) * sizeof(float);
+  // DMA kernel: two chunk buffers + one 32 x 36 float transposition scratch per wave (16-B epilogue), which lives
+  // in the dead chunk buffer when that is large enough (and the reduction has >= 2 chunks per slice)
+  l.scr = (size_t)c.waves * 32 * 36 * sizeof(float);
+  l.lds = dma ? 2 * l.buf + scratch_bytes_needed(l.buf, l.scr, g.cin_g, c.ck, bound ? 1 : ksplit) : l.buf;
+  return l;
+}
+static size_t lds_bound(int id, const Geometry& g, int W, bool dma) { return tile_layout(cfg_info(id), g, W, dma, 1, true).lds; }
+constexpr size_t kMaxLds = 160 * 1024;
 
 // Logical tile order of a launch (ConvArgs::item_major, tile_of_workgroup).  What an XCD pulls into its L2 is the set
 // of DISTINCT weight tiles (row block x group x reduction slice: k * Cin_slice * BM floats) and x windows (item x
@@ -1305,161 +1374,6 @@ static int choose_tile_order(const Geometry& g, int width, int t_in, int bm, int
   const double x1 = dmin(run, ig) * dmin(gs, cdiv(run, ig * mtiles));
   const double bytes0 = w0 * wt + x0 * xt, bytes1 = w1 * wt + x1 * xt;
   return bytes1 < 0.8 * bytes0 ? 1 : 0;
-}
-
-template <int WM, int WN, int WAVES_M, int WAVES_N, int CK, bool DMA>
-static int launch_conv(const ConvArgs& a0, const Geometry& g, int batch, int groups, hipStream_t stream) {
-  constexpr int BM = 32 * WM * WAVES_M;
-  constexpr int BN = 32 * WN * WAVES_N;
-  ConvArgs a = a0;
-  const int W = a.width;
-  const int rows = (W == 1) ? BN : ((BN - 1) / W + 2);
-  const int xs_len = ((rows - 1) * g.stride + (g.k_phase - 1) * g.dil + 1) * W;
-  // DMA variant: whole 64-lane pieces per row; register variant: 16-B aligned weight tile
-  a.xs_stride = DMA ? round_up(xs_len, 64) : round_up(xs_len, 4);
-  const bool fast = DMA && HasFast<WM, WN, WAVES_M, WAVES_N, CK>::value && g.stride == 1 && W == 1 &&
-                    (g.k_phase - 1) * g.dil <= 64;
-  if (fast) a.xs_stride = BN + 64;
-  const int act = a.pre_act == PWG_ACT_NONE ? 0
-                  : (a.pre_act == PWG_ACT_LEAKY_RELU && a.pre_slope > 0.f && a.pre_slope < 1.f) ? 1 : 2;
-  const size_t buf = ((size_t)CK * a.xs_stride + (size_t)g.k_phase * CK * BM) * sizeof(float);
-  // DMA kernel: two chunk buffers + one 32 x 36 float transposition scratch per wave (16-B epilogue), which lives
-  // in the dead chunk buffer when that is large enough (and the reduction has >= 2 chunks per slice)
-  const size_t scr = (size_t)WAVES_M * WAVES_N * 32 * 36 * sizeof(float);
-  const size_t lds = DMA ? 2 * buf + scratch_bytes_needed(buf, scr, g.cin_g, CK, a.ksplit) : buf;
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
-  a.epi_vec = DMA && a.width == 1 && (a.y_cstride % 4) == 0 && al16(a.y) && al16(a.add1) && al16(a.add2) &&
-              al16(a.mask_src) && (((size_t)a.y_bstride) % 4) == 0;
-  static const bool no_vec = getenv("PWG_NO_VEC_EPILOGUE") != nullptr;
-  if (no_vec) a.epi_vec = 0;
-  PWG_REQUIRE(lds <= 160 * 1024, PWG_ERR_UNSUPPORTED,
-              "conv1d: tile needs %zu B of LDS (k=%d stride=%d dil=%d)", lds, g.k_phase, g.stride, g.dil);
-  void (*kern)(ConvArgs);
-  if (DMA)
-    kern = pick_dma_kernel<WM, WN, WAVES_M, WAVES_N, CK>(fast, act);
-  else
-    kern = conv1d_mfma_kernel<WM, WN, WAVES_M, WAVES_N, CK>;
-  if (lds > 64 * 1024 && !lds_limit_is_set(reinterpret_cast<const void*>(kern), lds)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    PWG_REQUIRE(e == hipSuccess, PWG_ERR_LAUNCH, "conv1d: cannot raise LDS limit to %zu: %s", lds,
-                hipGetErrorString(e));
-  }
-  if (!DMA) a.ksplit = 1;  // (the register-staged kernel has no split-K)
-  dim3 grid(ceil_div(g.n_cols, BN), ceil_div(g.m_g, BM) * groups, batch * a.ksplit);
-  dim3 block(64 * WAVES_M * WAVES_N);
-  a.item_major = DMA ? choose_tile_order(g, W, a.t_in, BM, BN, (int)grid.x, ceil_div(g.m_g, BM), groups, batch, a.ksplit) : 0;
-  // algorithmic work of this launch: 2*taps*Cin_g MACs per real output element, and one read of
-  // x / one write of y / one read of each fused addend / one read of the packed weights
-  const double out_elems = (double)batch * groups * g.cout_g * a.t_out * a.width;
-  const double taps_eff = (double)g.k_phase * g.phases / g.out_stride;  // transposed: k/stride taps hit each output
-  const double flops = 2.0 * out_elems * g.cin_g * taps_eff;
-  const double bytes = 4.0 * ((double)batch * groups * g.cin_g * a.t_in * a.width +
-                              out_elems * (1 + (a.add1 != nullptr) + (a.add2 != nullptr)) +
-                              (double)groups * g.k_phase * g.cin_g * g.m_g);
-  maybe_poison_lds(stream);
-  {
-    ProfScope prof(stream,
-                   prof_shape_name(DMA ? "conv1d_mfma_dma_kernel" : "conv1d_mfma_kernel",
-                                   "B%d Cin%d M%d(x%dph) Tin%d cols%d k%d s%d d%d g%d W%d tile%dx%dx%d split%d%s%s", batch,
-                                   g.cin_g * groups, g.cout_g * groups, g.phases, a.t_in, g.n_cols, g.k_phase, g.stride,
-                                   g.dil, groups, a.width, BM, BN, CK, a.ksplit, a.item_major ? " im" : "",
-                                   a.mask_src ? " dgrad" : ""),
-                   flops, bytes);
-    hipLaunchKernelGGL(kern, grid, block, lds, stream, a);
-  }
-  PWG_CHECK_LAUNCH("conv1d_forward");
-  if (a.ksplit > 1) {
-    FinishArgs f;
-    f.partial = a.partial;
-    f.bias = a.bias;
-    f.add1 = a.add1;
-    f.add2 = a.add2;
-    f.mask_src = a.mask_src;
-    f.y = a.y;
-    f.elems = f.slab_elems = a.slab_elems;
-    f.nslabs = a.ksplit;
-    f.y_cstride = a.y_cstride;
-    f.c_out = g.cout_g * groups;
-    f.post_act = a.post_act;
-    f.post_slope = a.post_slope;
-    f.out_mul = a.out_mul;
-    f.out_div = a.out_div;
-    f.mask_slope = a.mask_slope;
-    long blocks = (f.elems + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    const int extra = (a.add1 != nullptr) + (a.add2 != nullptr) + (a.mask_src != nullptr);
-    ProfScope prof(stream, "splitk_finish_kernel", 0, 4.0 * f.elems * (a.ksplit + 1 + extra));
-    hipLaunchKernelGGL(splitk_finish_kernel, dim3((int)blocks), dim3(256), 0, stream, f);
-    PWG_CHECK_LAUNCH("splitk_finish");
-  }
-  return PWG_OK;
-}
-
-// Tile configurations (id -> instantiation); tools/bench_conv.py sweeps them.  (The 2x4-accumulator
-// tiles of round 1 needed scratch and never won a sweep: removed.)
-struct TileCfg {
-  int bm, bn, ck;
-  int wm, wn;  // 32x32 accumulator tiles per wave
-  int waves;   // waves per workgroup (4, or 8 for the 128x256 tiles: one workgroup per CU)
-};
-#define PWG_CONV_CFGS(X)  \
-  X(0, 2, 2, 2, 2, 8)     \
-  X(1, 2, 2, 2, 2, 16)    \
-  X(2, 2, 2, 2, 2, 4)     \
-  X(3, 2, 2, 1, 4, 8)     \
-  X(4, 2, 2, 1, 4, 16)    \
-  X(5, 1, 2, 1, 4, 8)     \
-  X(6, 1, 2, 1, 4, 16)    \
-  X(7, 1, 4, 1, 4, 8)     \
-  X(8, 1, 4, 1, 4, 16)    \
-  X(9, 2, 1, 2, 2, 8)     \
-  X(10, 1, 1, 1, 4, 8)    \
-  X(11, 2, 2, 1, 4, 4)    \
-  X(12, 1, 2, 2, 2, 8)    \
-  X(13, 1, 1, 2, 2, 8)    \
-  X(14, 1, 1, 4, 1, 8)    \
-  X(15, 1, 1, 2, 2, 16)   \
-  X(16, 1, 1, 1, 4, 16)   \
-  X(17, 1, 1, 2, 2, 4)    \
-  X(18, 2, 2, 2, 4, 4)    \
-  X(19, 2, 2, 2, 4, 8)
-static const int kNumCfgs = 20;
-
-static TileCfg cfg_info(int id) {
-  switch (id) {
-#define X(ID, WM, WN, WVM, WVN, CK) \
-  case ID:                          \
-    return TileCfg{32 * WM * WVM, 32 * WN * WVN, CK, WM, WN, WVM * WVN};
-    PWG_CONV_CFGS(X)
-#undef X
-  }
-  return TileCfg{0, 0, 0, 0, 0, 0};
-}
-
-static size_t cfg_lds(int id, const Geometry& g, int W, bool dma) {
-  TileCfg c = cfg_info(id);
-  const int rows = (W == 1) ? c.bn : ((c.bn - 1) / W + 2);
-  const int xs_len = ((rows - 1) * g.stride + (g.k_phase - 1) * g.dil + 1) * W;
-  int xs = dma ? round_up(xs_len, 64) : round_up(xs_len, 4);
-  if (dma && g.stride == 1 && W == 1 && (g.k_phase - 1) * g.dil <= 64) xs = c.bn + 64;  // FAST row stride (upper bound)
-  const size_t buf = ((size_t)c.ck * xs + (size_t)g.k_phase * c.ck * c.bm) * sizeof(float);
-  const size_t scr = (size_t)c.waves * 32 * 36 * sizeof(float);
-  return dma ? 2 * buf + scratch_bytes_needed(buf, scr, g.cin_g, c.ck, 1) : buf;
-}
-
-static int launch_cfg(int id, bool dma, const ConvArgs& a, const Geometry& g, int batch, int groups,
-                      hipStream_t stream) {
-  switch (id) {
-#define X(ID, WM, WN, WVM, WVN, CK)                                                        \
-  case ID:                                                                                 \
-    return dma ? launch_conv<WM, WN, WVM, WVN, CK, true>(a, g, batch, groups, stream)      \
-               : launch_conv<WM, WN, WVM, WVN, CK, false>(a, g, batch, groups, stream);
-    PWG_CONV_CFGS(X)
-#undef X
-  }
-  set_error("conv1d: unknown tile config %d", id);
-  return PWG_ERR_UNSUPPORTED;
 }
 
 // Heuristic from the tools/bench_conv.py sweep on MI355X (HiFi-GAN V1 problem set): the kernel is
@@ -1585,8 +1499,8 @@ static int choose_cfg(const Geometry& g, int W, int batch, int groups, bool dma,
       const TileCfg c = cfg_info(cand[i].id);
       // first try to keep >= 2 workgroups per CU (the 8-wave tiles are one workgroup per CU by design)
       const size_t cap = (pass == 0 && c.waves < 8) ? 80 * 1024 : 160 * 1024;
-      if (cfg_lds(cand[i].id, g, W, dma) > cap) continue;
-      if (c.waves == 8 && (!dma || g.stride != 1 || W != 1 || (k - 1) * g.dil > 64)) continue;  // FAST geometry only
+      if (lds_bound(cand[i].id, g, W, dma) > cap) continue;
+      if (c.waves == 8 && !(dma && fast_geometry(g, W))) continue;  // FAST geometry only
       // 16-channel chunks: long reductions -- or few taps (k <= 3: a 4 / 8-channel chunk carries 2 - 12 MFMAs per
       // wave against a 2.7 us DMA round trip; measured at 96 channels, see rows32 above)
       if (c.ck == 16 && (!dma || (g.cin_g < 256 && !(rows32_on && k <= 3 && g.cin_g >= 32)))) continue;
@@ -1616,58 +1530,6 @@ static int choose_cfg(const Geometry& g, int W, int batch, int groups, bool dma,
   return best;
 }
 
-static int fill_args(const pwg_conv1d_desc* d, const Geometry& g, const float* x, const float* w_packed,
-                     const float* bias, const float* add1, const float* add2, float* y, ConvArgs* out) {
-  PWG_REQUIRE(x && w_packed && y, PWG_ERR_NULL, "conv1d_forward: NULL pointer");
-  PWG_REQUIRE(d->pre_act == PWG_ACT_NONE || d->pre_act == PWG_ACT_LEAKY_RELU || d->pre_act == PWG_ACT_RELU,
-              PWG_ERR_UNSUPPORTED, "conv1d: pre_act %d unsupported", d->pre_act);
-  ConvArgs a;
-  a.x = x;
-  a.wp = w_packed;
-  a.bias = bias;
-  a.add1 = add1;
-  a.add2 = add2;
-  a.y = y;
-  a.cin_g = g.cin_g;
-  a.cin_pad = g.cin_pad;
-  a.cout_g = g.cout_g;
-  a.m_g = g.m_g;
-  a.m_pad = g.m_pad;
-  a.t_in = d->t_in;
-  a.t_out = d->t_out;
-  a.width = d->width;
-  a.k = g.k_phase;
-  a.stride = g.stride;
-  a.dil = g.dil;
-  a.pad = g.pad;
-  a.n_cols = g.n_cols;
-  a.out_stride = g.out_stride;
-  a.out_off = g.out_off;
-  a.x_cstride = d->t_in * d->width;
-  a.y_cstride = d->t_out * d->width;
-  a.x_bstride = (long)d->c_in * a.x_cstride;
-  a.y_bstride = (long)d->c_out * a.y_cstride;
-  a.xs_stride = 0;
-  a.pad_mode = d->pad_mode;
-  a.pre_act = d->pre_act;
-  a.post_act = d->post_act;
-  a.pre_slope = d->pre_slope;
-  a.post_slope = d->post_slope;
-  a.out_mul = d->out_mul;
-  a.out_div = d->out_div;
-  a.mask_src = nullptr;
-  a.mask_slope = 0.f;
-  static const int dbg = getenv("PWG_DBG") ? atoi(getenv("PWG_DBG")) : 0;
-  a.dbg = dbg;
-  a.ksplit = 1;
-  a.epi_vec = 0;
-  a.item_major = 0;
-  a.partial = nullptr;
-  a.slab_elems = (long)d->batch * d->c_out * d->t_out * d->width;
-  *out = a;
-  return PWG_OK;
-}
-
 }  // namespace pwg
 
 using namespace pwg;
@@ -1678,6 +1540,23 @@ extern "C" size_t pwg_conv1d_packed_weight_floats(const pwg_conv1d_desc* d) {
   return (size_t)d->groups * g.k_phase * g.cin_pad * g.m_pad;
 }
 
+static void fill_pack_args(const pwg_conv1d_desc* d, const Geometry& g, const float* w, const float* scale, float* wp,
+                           PackArgs* a) {
+  a->w = w;
+  a->scale = scale;
+  a->wp = wp;
+  a->groups = d->groups;
+  a->k_phase = g.k_phase;
+  a->cin_g = g.cin_g;
+  a->cin_pad = g.cin_pad;
+  a->cout_g = g.cout_g;
+  a->m_g = g.m_g;
+  a->m_pad = g.m_pad;
+  a->kernel = d->kernel;
+  a->stride = d->stride;
+  a->transposed = d->transposed;
+}
+
 extern "C" int pwg_conv1d_pack_weight(const pwg_conv1d_desc* d, const float* w, const float* scale,
                                       float* w_packed, void* stream) {
   Geometry g;
@@ -1685,25 +1564,29 @@ extern "C" int pwg_conv1d_pack_weight(const pwg_conv1d_desc* d, const float* w, 
   if (rc != PWG_OK) return rc;
   PWG_REQUIRE(w && w_packed, PWG_ERR_NULL, "pack_weight: NULL pointer");
   PackArgs a;
-  a.w = w;
-  a.scale = scale;
-  a.wp = w_packed;
-  a.groups = d->groups;
-  a.k_phase = g.k_phase;
-  a.cin_g = g.cin_g;
-  a.cin_pad = g.cin_pad;
-  a.cout_g = g.cout_g;
-  a.m_g = g.m_g;
-  a.m_pad = g.m_pad;
-  a.kernel = d->kernel;
-  a.stride = d->stride;
-  a.transposed = d->transposed;
+  fill_pack_args(d, g, w, scale, w_packed, &a);
   const long total = (long)a.groups * a.k_phase * a.cin_pad * a.m_pad;
   int blocks = (int)((total + 255) / 256);
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(pack_weight_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
   PWG_CHECK_LAUNCH("pack_weight");
   return PWG_OK;
+}
+
+// The data gradient of a convolution is the transposed convolution with the same torch-layout
+// weight (and vice versa), so both directions reuse the forward kernels through the dual descriptor.
+static void dual_desc(const pwg_conv1d_desc* d, pwg_conv1d_desc* o) {
+  *o = *d;
+  o->c_in = d->c_out;
+  o->c_out = d->c_in;
+  o->t_in = d->t_out;
+  o->t_out = d->t_in;
+  o->transposed = d->transposed ? 0 : 1;
+  o->pad_mode = PWG_PAD_ZERO;
+  o->pre_act = PWG_ACT_NONE;
+  o->post_act = PWG_ACT_NONE;
+  o->pre_slope = o->post_slope = 0.f;
+  o->out_mul = o->out_div = 1.f;
 }
 
 // which launches of pwg_conv1d_forward leave the MFMA kernel (flattened descriptors): the streaming VALU kernels for a
@@ -1722,109 +1605,319 @@ static bool small_cout_applicable(const pwg_conv1d_desc* d, bool has_addends) {
          d->t_out >= 4096 && (d->kernel - 1) * d->dilation <= 1024 &&
          (d->pre_act == PWG_ACT_NONE || d->pre_act == PWG_ACT_LEAKY_RELU || d->pre_act == PWG_ACT_RELU);
 }
+// round 6: the few-output-channel layers the LDS-free stream covers (conv1d_small_cout_stream_kernel): "same"-padded,
+// dilation 1, k = 1 / 3 / 5 / 7, 1 or 4 output channels, rows of x and y 16-B aligned (`aligned`: their base pointers are)
+static bool small_cout_stream_form(const pwg_conv1d_desc* d, bool aligned) {
+  return d->dilation == 1 && (d->kernel & 1) && d->kernel <= 7 && d->pad_left == (d->kernel - 1) / 2 &&
+         d->t_out == d->t_in && (d->t_in & 3) == 0 && aligned && (d->c_out == 1 || d->c_out == 4);
+}
 
-// tile configuration, staging path and split-K factor of a (flattened) forward-form descriptor
-struct ConvPlan {
-  int id, ksplit;
-  bool dma;
+// The kernel family of a call, in the dispatcher's order of preference (the values are the ABI of pwg_conv1d_plan, out[0]).
+enum ConvRoute { CONV_MFMA = 0, CONV_GCONV = 1, CONV_SMALL_CIN = 2, CONV_SMALL_COUT = 3 };
+
+// What an entry point tells conv_describe about a call besides its descriptor.
+struct ConvAsk {  // (the defaults: a query -- aligned pointers, all the workspace the plan wants)
+  bool dual = false;       // the data gradient of the layer the descriptor describes (else: its forward)
+  bool addends = false;    // add1 / add2 (data gradient: accum) present
+  bool fwd_input = false;  // data gradient: the forward input is at hand for the pre-activation mask
+  bool x16 = true, y16 = true, epi16 = true;  // 16-B alignment of x, of y, and of y with every addend and the mask
+  size_t ws_floats = SIZE_MAX;                // workspace on offer
+  bool forced = false;     // pwg_conv1d_forward_cfg: `tile` and `dma` come from the caller, no split, MFMA kernels only
+  int tile = 0;
+  bool dma = false;
+  bool query = true;       // nothing will be launched (plan, workspace): a launch's LDS need is reported, not refused
 };
-static ConvPlan plan_conv(const pwg_conv1d_desc* d, const Geometry& g) {
-  ConvPlan p;
-  p.dma = d->pad_mode == PWG_PAD_ZERO;  // reflect/replicate need index remapping: register path
-  p.ksplit = 1;
-  p.id = choose_cfg(g, d->width, d->batch, d->groups, p.dma, &p.ksplit);
-  // tuning override (tools/bench_dshapes.py): PWG_FORCE_CFG=<id>[,<ksplit>], read per call
-  if (const char* f = getenv("PWG_FORCE_CFG")) {
-    int id = -1, ks = 1;
-    if (sscanf(f, "%d,%d", &id, &ks) >= 1 && id >= 0 && id < kNumCfgs && p.dma && cfg_lds(id, g, d->width, true) <= 160 * 1024) {
-      p.id = id;
-      p.ksplit = ks < 1 ? 1 : (ks > 16 ? 16 : ks);
-      if (ceil_div(g.cin_g, cfg_info(id).ck) < p.ksplit) p.ksplit = 1;
-    }
-  }
-  if (p.dma && cfg_lds(p.id, g, d->width, true) > 160 * 1024) {  // very long filters (PQMF k=63): single buffer
-    p.dma = false;
-    p.ksplit = 1;
-    p.id = choose_cfg(g, d->width, d->batch, d->groups, false);
-  }
-  return p;
+
+// Everything decided before a launch, by conv_describe and nowhere else.
+struct ConvCall {
+  ConvRoute route;
+  pwg_conv1d_desc d;  // flattened, in forward form (data gradient: the dual descriptor; CONV_SMALL_COUT: its plain form;
+  Geometry g;         // CONV_GCONV: the layer's own descriptor, as given, and no geometry)
+  size_t lds;         // dynamic LDS of the launch (not CONV_GCONV)
+  // CONV_SMALL_COUT
+  bool stream;  // the LDS-free stream kernel
+  int opt;      // else: outputs per thread, the largest that still gives >= 1024 workgroups
+  // CONV_SMALL_CIN
+  int cg, ngroups;  // output channels per workgroup, channel groups
+  bool vec;
+  // CONV_MFMA
+  int id;           // tile configuration
+  bool dma, fast;   // staging path, FAST row stride
+  int act;          // pre-activation variant of the FAST kernels: 0 none, 1 LeakyReLU with 0 < slope < 1, 2 any
+  ConvKernel kern;
+  int ksplit;       // reduction slices, after the workspace check
+  size_t ws_floats; // workspace the launch uses
+  int item_major, xs_stride, epi_vec;  // ConvArgs fields of the same name
+  dim3 grid;
+  int block;
+};
+
+static void describe_small_cout(const ConvAsk& ask, ConvCall* c) {
+  static const bool stream_on = !(getenv("PWG_SMALL_COUT_STREAM") && atoi(getenv("PWG_SMALL_COUT_STREAM")) == 0);
+  const pwg_conv1d_desc& d = c->d;
+  c->route = CONV_SMALL_COUT;
+  c->stream = stream_on && small_cout_stream_form(&d, ask.x16 && ask.y16);
+  c->opt = 4;
+  while (c->opt > 1 && (long)ceil_div(d.t_out, 256 * c->opt) * d.batch < 1024) c->opt >>= 1;
+  const size_t weights = (size_t)d.c_out * d.c_in * d.kernel;
+  c->lds = (c->stream ? weights : weights + 256 * c->opt + (d.kernel - 1) * d.dilation) * sizeof(float);
 }
 
-static int run_conv(const pwg_conv1d_desc* d, const Geometry& g, ConvArgs& a, float* workspace, size_t ws_floats,
-                    hipStream_t stream) {
-  ConvPlan p = plan_conv(d, g);
-  if (p.ksplit > 1) {
-    const size_t need = (size_t)p.ksplit * a.slab_elems;
-    if (workspace && ws_floats >= need) {
-      a.ksplit = p.ksplit;
-      a.partial = workspace;
-    } else {
-      // no (or too small a) workspace: run unsplit with the best unsplit tile
-      p.id = choose_cfg(g, d->width, d->batch, d->groups, p.dma);
-    }
+// Route, tile, split and launch geometry of one call; every refusal of the dispatcher is raised here, before anything
+// is launched.  (Pointers are validated by the entry points: check_conv_args.)
+static int conv_describe(const pwg_conv1d_desc& d_in, const ConvAsk& ask, ConvCall* c) {
+  if (ask.dual) {
+    PWG_REQUIRE(d_in.pad_mode == PWG_PAD_ZERO, PWG_ERR_UNSUPPORTED,
+                "conv1d_backward_data: only zero padding (pad reflect/replicate inputs explicitly)");
+    PWG_REQUIRE(d_in.pre_act == PWG_ACT_NONE || ask.fwd_input, PWG_ERR_NULL,
+                "conv1d_backward_data: the forward input is needed for the pre-activation derivative");
+    c->d = d_in;
+    c->route = CONV_GCONV;
+    if (gconv_dgrad_applicable(&d_in)) return PWG_OK;
+    dual_desc(&d_in, &c->d);
+    c->d = flatten_width(c->d);
+  } else {
+    c->d = flatten_width(d_in);
   }
-  static const bool trace = getenv("PWG_TRACE_CFG") != nullptr;
-  if (trace)
-    fprintf(stderr, "[pwg] conv B=%d Cin=%d Cout=%d Tin=%d Tout=%d k=%d s=%d d=%d g=%d tr=%d -> cfg %d split %d dma %d\n",
-            d->batch, d->c_in, d->c_out, d->t_in, d->t_out, d->kernel, d->stride, d->dilation, d->groups,
-            d->transposed, p.id, a.ksplit, (int)p.dma);
-  return launch_cfg(p.id, p.dma, a, g, d->batch, d->groups, stream);
-}
-
-extern "C" size_t pwg_conv1d_forward_workspace_floats(const pwg_conv1d_desc* d_in) {
-  if (!d_in) return 0;
-  const pwg_conv1d_desc flat = flatten_width(*d_in);
-  Geometry g;
-  if (make_geometry(&flat, &g) != PWG_OK) return 0;
-  const ConvPlan p = plan_conv(&flat, g);
-  return p.ksplit > 1 ? (size_t)p.ksplit * flat.batch * flat.c_out * flat.t_out * flat.width : 0;
-}
-
-// Few output channels over a long sequence: the streaming VALU kernels (conv1d_small_cout_stream_kernel / conv1d_small_cout_kernel).
-// `d`: a plain (non-transposed) flattened descriptor for which small_cout_applicable holds; `g` its geometry.
-static int run_small_cout(const pwg_conv1d_desc* d, const Geometry& g, const float* x, const float* w_packed, const float* bias,
-                          float* y, void* stream) {
-  // few output channels over a long sequence: streaming VALU kernel (see conv1d_small_cout_kernel)
-  {
-    // round 6: the LDS-free stream for "same"-padded dilation-1 layers with 16-B aligned rows (PWG_SMALL_COUT_STREAM=0: off)
-    static const bool stream_on = !(getenv("PWG_SMALL_COUT_STREAM") && atoi(getenv("PWG_SMALL_COUT_STREAM")) == 0);
-    const int kk = d->kernel;
-    void (*sk)(const float*, const float*, const float*, float*, int, int, int, int, int, int, float, int, float, float) = nullptr;
-    if (stream_on && d->dilation == 1 && (kk & 1) && d->pad_left == (kk - 1) / 2 && d->t_out == d->t_in &&
-        (d->t_in & 3) == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0 && (d->c_out == 1 || d->c_out == 4)) {
-#define PWG_SCS(KV) (d->c_out == 1 ? conv1d_small_cout_stream_kernel<KV, (KV - 1) / 2, 1> : conv1d_small_cout_stream_kernel<KV, (KV - 1) / 2, 4>)
-      if (kk == 1) sk = PWG_SCS(1);
-      else if (kk == 3) sk = PWG_SCS(3);
-      else if (kk == 5) sk = PWG_SCS(5);
-      else if (kk == 7) sk = PWG_SCS(7);
-#undef PWG_SCS
+  pwg_conv1d_desc& d = c->d;
+  Geometry& g = c->g;
+  int rc = make_geometry(&d, &g);
+  if (rc != PWG_OK) return rc;
+  if (!ask.dual && !ask.forced) {
+    c->route = CONV_GCONV;
+    if (gconv_forward_applicable(&d, ask.addends)) return PWG_OK;
+    if (small_cin_applicable(&d, ask.addends)) {
+      c->route = CONV_SMALL_CIN;
+      // channel groups: at least ~1024 workgroups per launch (4 per CU), never fewer than 8 channels per group
+      const int pairs = ceil_div(d.t_out, SI_TILE) * d.batch;
+      int ngroups = ceil_div(1024, pairs);
+      if (ngroups > d.c_out / 8) ngroups = d.c_out / 8;
+      if (ngroups < 1) ngroups = 1;
+      c->cg = ceil_div(d.c_out, ngroups);
+      c->ngroups = ceil_div(d.c_out, c->cg);
+      c->vec = d.t_out % 4 == 0 && ask.y16;
+      c->lds = ((size_t)c->cg * (d.kernel + 1) + SI_TILE + (d.kernel - 1) * d.dilation) * sizeof(float);
+      PWG_REQUIRE(ask.query || c->lds <= 64 * 1024, PWG_ERR_UNSUPPORTED, "conv1d (single input channel): %zu B of LDS", c->lds);
+      return PWG_OK;
     }
-    if (sk) {
-      const double out_elems = (double)d->batch * d->c_out * d->t_out;
-      ProfScope prof((hipStream_t)stream, "conv1d_small_cout_stream_kernel", 2.0 * out_elems * d->c_in * d->kernel,
-                     4.0 * ((double)d->batch * d->c_in * d->t_in + out_elems));
-      hipLaunchKernelGGL(sk, dim3(ceil_div(d->t_out, 1024), d->batch), dim3(256),
-                         (size_t)d->c_out * d->c_in * d->kernel * sizeof(float), (hipStream_t)stream, x, w_packed, bias, y,
-                         d->c_in, g.cin_pad, g.m_pad, d->t_in, d->t_out, d->pre_act, d->pre_slope, d->post_act,
-                         d->post_slope, d->out_mul);
-      PWG_CHECK_LAUNCH("conv1d_small_cout_stream");
+    if (small_cout_applicable(&d, ask.addends)) {
+      describe_small_cout(ask, c);
       return PWG_OK;
     }
   }
-  int opt = 4;
-  while (opt > 1 && (long)ceil_div(d->t_out, 256 * opt) * d->batch < 1024) opt >>= 1;
-  const int tile = 256 * opt;
-  const size_t lds = ((size_t)d->c_out * d->c_in * d->kernel + tile + (d->kernel - 1) * d->dilation) * sizeof(float);
+  // Round 6: the data gradient of a stride-1 layer with one (<= 4) input channel over a long sequence -- every discriminator's
+  // first layer, when the discriminator's input needs a gradient (generator phase) -- is a plain few-OUTPUT-channel convolution
+  // over the flipped taps (make_geometry: that is how the backward image is packed): on the MFMA tile one of 32 rows carries data
+  // (2.5 TFLOP/s, 0.2 ms for MelGAN's 16 -> 1 k = 15 layer at B64 x 16384, 0.15 ms for HiFi-GAN's 128 -> 1); the streaming
+  // kernels read dy once.  PWG_SMALL_COUT_DGRAD=0: the MFMA path.
+  static const bool dgrad_stream = !(getenv("PWG_SMALL_COUT_DGRAD") && atoi(getenv("PWG_SMALL_COUT_DGRAD")) == 0);
+  if (ask.dual && dgrad_stream && d.stride == 1 && g.phases == 1 && g.out_off == 0 && !ask.addends && d_in.pre_act == PWG_ACT_NONE) {
+    pwg_conv1d_desc pd = d;
+    pd.transposed = 0;
+    pd.pad_left = g.pad;
+    // (the LDS kernel walks the input channels one by one, two barriers each: 0.29 ms for HiFi-GAN's 128 -> 1 k = 15 against 0.13 ms
+    // on the MFMA tile -- only few channels take it; the LDS-free stream (k <= 7, "same" padding) has no such walk)
+    if (small_cout_applicable(&pd, false) && (pd.c_in <= 32 || small_cout_stream_form(&pd, ask.x16 && ask.y16))) {
+      Geometry pg;
+      rc = make_geometry(&pd, &pg);
+      if (rc != PWG_OK) return rc;
+      PWG_REQUIRE(pg.cin_pad == g.cin_pad && pg.m_pad == g.m_pad && pg.k_phase == g.k_phase, PWG_ERR_UNSUPPORTED,
+                  "conv1d_backward_data: plain form of the dual descriptor has another image layout");
+      d = pd;
+      g = pg;
+      describe_small_cout(ask, c);
+      return PWG_OK;
+    }
+  }
+  // ---- the MFMA kernels: tile, staging path and split-K factor ----
+  c->route = CONV_MFMA;
+  const size_t slab = (size_t)d.batch * d.c_out * d.t_out * d.width;
+  int ksplit = 1;
+  if (ask.forced) {
+    PWG_REQUIRE(ask.tile >= 0 && ask.tile < kNumCfgs, PWG_ERR_UNSUPPORTED, "conv1d: tile config %d out of range", ask.tile);
+    PWG_REQUIRE(!(ask.dma && d.pad_mode != PWG_PAD_ZERO), PWG_ERR_UNSUPPORTED,
+                "conv1d: the DMA path implements zero padding only");
+    c->id = ask.tile;
+    c->dma = ask.dma;
+  } else {
+    c->dma = d.pad_mode == PWG_PAD_ZERO;  // reflect/replicate need index remapping: register path
+    c->id = choose_cfg(g, d.width, d.batch, d.groups, c->dma, &ksplit);
+    // tuning override (tools/bench_dshapes.py): PWG_FORCE_CFG=<id>[,<ksplit>], read per call
+    if (const char* f = getenv("PWG_FORCE_CFG")) {
+      int id = -1, ks = 1;
+      if (sscanf(f, "%d,%d", &id, &ks) >= 1 && id >= 0 && id < kNumCfgs && c->dma && lds_bound(id, g, d.width, true) <= kMaxLds) {
+        c->id = id;
+        ksplit = ks < 1 ? 1 : (ks > 16 ? 16 : ks);
+        if (ceil_div(g.cin_g, cfg_info(id).ck) < ksplit) ksplit = 1;
+      }
+    }
+    if (c->dma && lds_bound(c->id, g, d.width, true) > kMaxLds) {  // very long filters (PQMF k=63): single buffer
+      c->dma = false;
+      ksplit = 1;
+      c->id = choose_cfg(g, d.width, d.batch, d.groups, false);
+    }
+    if (ksplit > 1 && ask.ws_floats < ksplit * slab) {  // no (or too small a) workspace: run unsplit with the best unsplit tile
+      ksplit = 1;
+      c->id = choose_cfg(g, d.width, d.batch, d.groups, c->dma);
+    }
+  }
+  c->ksplit = c->dma ? ksplit : 1;  // (the register-staged kernel has no split-K)
+  c->ws_floats = c->ksplit > 1 ? c->ksplit * slab : 0;
+  // ---- ... and what the launch of that tile takes ----
+  const TileCfg t = cfg_info(c->id);
+  const TileLayout l = tile_layout(t, g, d.width, c->dma, c->ksplit);
+  c->fast = l.fast;
+  c->xs_stride = l.xs_stride;
+  c->lds = l.lds;
+  PWG_REQUIRE(ask.query || c->lds <= kMaxLds, PWG_ERR_UNSUPPORTED, "conv1d: tile needs %zu B of LDS (k=%d stride=%d dil=%d)",
+              c->lds, g.k_phase, g.stride, g.dil);
+  c->act = d.pre_act == PWG_ACT_NONE ? 0 : (d.pre_act == PWG_ACT_LEAKY_RELU && d.pre_slope > 0.f && d.pre_slope < 1.f) ? 1 : 2;
+  c->kern = conv_kernel(c->id, c->dma, c->fast, c->act);
+  PWG_REQUIRE(c->kern != nullptr, PWG_ERR_UNSUPPORTED, "conv1d: no kernel for tile config %d (dma %d, fast %d, pre-activation variant %d)",
+              c->id, (int)c->dma, (int)c->fast, c->act);
+  static const bool no_vec = getenv("PWG_NO_VEC_EPILOGUE") != nullptr;
+  c->epi_vec = c->dma && d.width == 1 && d.t_out % 4 == 0 && ask.epi16 && !no_vec;  // (y_cstride % 4 == 0: every row of y is 16-B aligned)
+  const int mtiles = ceil_div(g.m_g, t.bm);
+  c->grid = dim3(ceil_div(g.n_cols, t.bn), mtiles * d.groups, d.batch * c->ksplit);
+  c->block = 64 * t.waves;
+  c->item_major = c->dma ? choose_tile_order(g, d.width, d.t_in, t.bm, t.bn, (int)c->grid.x, mtiles, d.groups, d.batch, c->ksplit) : 0;
+  static const bool trace = getenv("PWG_TRACE_CFG") != nullptr;
+  if (trace && !ask.forced && !ask.query)
+    fprintf(stderr, "[pwg] conv B=%d Cin=%d Cout=%d Tin=%d Tout=%d k=%d s=%d d=%d g=%d tr=%d -> cfg %d split %d dma %d\n",
+            d.batch, d.c_in, d.c_out, d.t_in, d.t_out, d.kernel, d.stride, d.dilation, d.groups, d.transposed, c->id,
+            c->ksplit, (int)c->dma);
+  return PWG_OK;
+}
+
+static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+// A launching entry point's ConvAsk: input, output, up to three more operands of y's shape (addends, mask; NULL: absent)
+static ConvAsk ask_launch(const float* x, const float* y, const float* add1, const float* add2, const float* mask,
+                          const float* workspace, size_t workspace_floats) {
+  ConvAsk ask;
+  ask.addends = add1 || add2;
+  ask.x16 = al16(x);
+  ask.y16 = al16(y);
+  ask.epi16 = al16(y) && al16(add1) && al16(add2) && al16(mask);
+  ask.ws_floats = workspace ? workspace_floats : 0;
+  ask.query = false;
+  return ask;
+}
+
+// Pointer and pre-activation validation of the launching entry points (gconv.hip validates its own calls).
+static int check_conv_args(const pwg_conv1d_desc& d, const float* x, const float* w_packed, const float* y) {
+  PWG_REQUIRE(x && w_packed && y, PWG_ERR_NULL, "conv1d_forward: NULL pointer");
+  PWG_REQUIRE(d.pre_act == PWG_ACT_NONE || d.pre_act == PWG_ACT_LEAKY_RELU || d.pre_act == PWG_ACT_RELU,
+              PWG_ERR_UNSUPPORTED, "conv1d: pre_act %d unsupported", d.pre_act);
+  return PWG_OK;
+}
+
+static ConvArgs fill_args(const ConvCall& c, const float* x, const float* w_packed, const float* bias, const float* add1,
+                          const float* add2, float* y, float* workspace) {
+  const pwg_conv1d_desc& d = c.d;
+  const Geometry& g = c.g;
+  static const int dbg = getenv("PWG_DBG") ? atoi(getenv("PWG_DBG")) : 0;
+  const int x_cstride = d.t_in * d.width, y_cstride = d.t_out * d.width;
+  return ConvArgs{.x = x, .wp = w_packed, .bias = bias, .add1 = add1, .add2 = add2, .y = y,
+                  .cin_g = g.cin_g, .cin_pad = g.cin_pad, .cout_g = g.cout_g, .m_g = g.m_g, .m_pad = g.m_pad,
+                  .t_in = d.t_in, .t_out = d.t_out, .width = d.width,
+                  .k = g.k_phase, .stride = g.stride, .dil = g.dil, .pad = g.pad, .n_cols = g.n_cols,
+                  .out_stride = g.out_stride, .out_off = g.out_off,
+                  .x_cstride = x_cstride, .y_cstride = y_cstride,
+                  .x_bstride = (long)d.c_in * x_cstride, .y_bstride = (long)d.c_out * y_cstride,
+                  .xs_stride = c.xs_stride, .pad_mode = d.pad_mode, .pre_act = d.pre_act, .post_act = d.post_act,
+                  .pre_slope = d.pre_slope, .post_slope = d.post_slope, .out_mul = d.out_mul, .out_div = d.out_div,
+                  .mask_src = nullptr, .mask_slope = 0.f, .dbg = dbg,
+                  .ksplit = c.ksplit, .partial = c.ksplit > 1 ? workspace : nullptr,
+                  .slab_elems = (long)d.batch * d.c_out * y_cstride, .epi_vec = c.epi_vec, .item_major = c.item_major};
+}
+
+// Sum the reduction slices' slabs and apply the fused epilogue (splitk_finish_kernel).
+static int finish_splitk(const ConvCall& c, const ConvArgs& a, hipStream_t stream) {
+  const FinishArgs f = {.partial = a.partial, .bias = a.bias, .add1 = a.add1, .add2 = a.add2, .mask_src = a.mask_src,
+                        .y = a.y, .elems = a.slab_elems, .slab_elems = a.slab_elems, .nslabs = c.ksplit,
+                        .y_cstride = a.y_cstride, .c_out = c.d.c_out, .post_act = a.post_act, .post_slope = a.post_slope,
+                        .out_mul = a.out_mul, .out_div = a.out_div, .mask_slope = a.mask_slope};
+  long blocks = (f.elems + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  const int extra = (a.add1 != nullptr) + (a.add2 != nullptr) + (a.mask_src != nullptr);
+  ProfScope prof(stream, "splitk_finish_kernel", 0, 4.0 * f.elems * (c.ksplit + 1 + extra));
+  hipLaunchKernelGGL(splitk_finish_kernel, dim3((int)blocks), dim3(256), 0, stream, f);
+  PWG_CHECK_LAUNCH("splitk_finish");
+  return PWG_OK;
+}
+
+// The MFMA launch `c` describes, with the operands of `a` (fill_args of the same call).
+static int launch_conv(const ConvCall& c, const ConvArgs& a, hipStream_t stream) {
+  const pwg_conv1d_desc& d = c.d;
+  const Geometry& g = c.g;
+  if (c.lds > 64 * 1024 && !lds_limit_is_set(reinterpret_cast<const void*>(c.kern), c.lds)) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(c.kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.lds);
+    PWG_REQUIRE(e == hipSuccess, PWG_ERR_LAUNCH, "conv1d: cannot raise LDS limit to %zu: %s", c.lds, hipGetErrorString(e));
+  }
+  // algorithmic work of this launch: 2*taps*Cin_g MACs per real output element, and one read of
+  // x / one write of y / one read of each fused addend / one read of the packed weights
+  const double out_elems = (double)d.batch * d.groups * g.cout_g * d.t_out * d.width;
+  const double taps_eff = (double)g.k_phase * g.phases / g.out_stride;  // transposed: k/stride taps hit each output
+  const double flops = 2.0 * out_elems * g.cin_g * taps_eff;
+  const double bytes = 4.0 * ((double)d.batch * d.groups * g.cin_g * d.t_in * d.width +
+                              out_elems * (1 + (a.add1 != nullptr) + (a.add2 != nullptr)) +
+                              (double)d.groups * g.k_phase * g.cin_g * g.m_g);
+  maybe_poison_lds(stream);
+  {
+    const TileCfg t = cfg_info(c.id);
+    ProfScope prof(stream,
+                   prof_shape_name(c.dma ? "conv1d_mfma_dma_kernel" : "conv1d_mfma_kernel",
+                                   "B%d Cin%d M%d(x%dph) Tin%d cols%d k%d s%d d%d g%d W%d tile%dx%dx%d split%d%s%s", d.batch,
+                                   g.cin_g * d.groups, g.cout_g * d.groups, g.phases, d.t_in, g.n_cols, g.k_phase, g.stride,
+                                   g.dil, d.groups, d.width, t.bm, t.bn, t.ck, c.ksplit, c.item_major ? " im" : "",
+                                   a.mask_src ? " dgrad" : ""),
+                   flops, bytes);
+    hipLaunchKernelGGL(c.kern, c.grid, dim3(c.block), c.lds, stream, a);
+  }
+  PWG_CHECK_LAUNCH("conv1d_forward");
+  return c.ksplit > 1 ? finish_splitk(c, a, stream) : PWG_OK;
+}
+
+// Few output channels over a long sequence: the streaming VALU kernels (conv1d_small_cout_stream_kernel / conv1d_small_cout_kernel).
+static int launch_small_cout(const ConvCall& c, const float* x, const float* w_packed, const float* bias, float* y, hipStream_t stream) {
+  const pwg_conv1d_desc* d = &c.d;
+  const Geometry& g = c.g;
   const double out_elems = (double)d->batch * d->c_out * d->t_out;
-  ProfScope prof((hipStream_t)stream, "conv1d_small_cout_kernel", 2.0 * out_elems * d->c_in * d->kernel,
-                 4.0 * ((double)d->batch * d->c_in * d->t_in + out_elems));
+  const double flops = 2.0 * out_elems * d->c_in * d->kernel, bytes = 4.0 * ((double)d->batch * d->c_in * d->t_in + out_elems);
+  if (c.stream) {
+    using StreamKernel = void (*)(const float*, const float*, const float*, float*, int, int, int, int, int, int, float, int, float, float);
+#define PWG_SCS(KV) {conv1d_small_cout_stream_kernel<KV, (KV - 1) / 2, 1>, conv1d_small_cout_stream_kernel<KV, (KV - 1) / 2, 4>}
+    static const StreamKernel tab[4][2] = {PWG_SCS(1), PWG_SCS(3), PWG_SCS(5), PWG_SCS(7)};  // [k / 2][c_out == 4]
+#undef PWG_SCS
+    const StreamKernel sk = tab[d->kernel / 2][d->c_out == 4];
+    ProfScope prof(stream, "conv1d_small_cout_stream_kernel", flops, bytes);
+    hipLaunchKernelGGL(sk, dim3(ceil_div(d->t_out, 1024), d->batch), dim3(256), c.lds, stream, x, w_packed, bias, y,
+                       d->c_in, g.cin_pad, g.m_pad, d->t_in, d->t_out, d->pre_act, d->pre_slope, d->post_act,
+                       d->post_slope, d->out_mul);
+    PWG_CHECK_LAUNCH("conv1d_small_cout_stream");
+    return PWG_OK;
+  }
+  const int opt = c.opt;
+  ProfScope prof(stream, "conv1d_small_cout_kernel", flops, bytes);
   void (*sck)(const float*, const float*, const float*, float*, int, int, int, int, int, int, int, int, int, int, float, int,
               float, float) = opt == 4 ? conv1d_small_cout_kernel<4> : (opt == 2 ? conv1d_small_cout_kernel<2> : conv1d_small_cout_kernel<1>);
-  hipLaunchKernelGGL(sck, dim3(ceil_div(d->t_out, tile), d->batch), dim3(256), lds,
-                     (hipStream_t)stream, x, w_packed, bias, y, d->c_in, g.cin_pad, g.m_pad, d->c_out, d->t_in, d->t_out,
-                     d->kernel, d->dilation, d->pad_left, d->pre_act, d->pre_slope, d->post_act, d->post_slope,
-                     d->out_mul);
+  hipLaunchKernelGGL(sck, dim3(ceil_div(d->t_out, 256 * opt), d->batch), dim3(256), c.lds, stream, x, w_packed, bias, y,
+                     d->c_in, g.cin_pad, g.m_pad, d->c_out, d->t_in, d->t_out, d->kernel, d->dilation, d->pad_left,
+                     d->pre_act, d->pre_slope, d->post_act, d->post_slope, d->out_mul);
   PWG_CHECK_LAUNCH("conv1d_small_cout");
+  return PWG_OK;
+}
+
+// A single input channel: the streaming VALU kernel (conv1d_small_cin_kernel).
+static int launch_small_cin(const ConvCall& c, const float* x, const float* w_packed, const float* bias, float* y, hipStream_t stream) {
+  const pwg_conv1d_desc* d = &c.d;
+  const double out_elems = (double)d->batch * d->c_out * d->t_out;
+  ProfScope prof(stream, "conv1d_small_cin_kernel", 2.0 * out_elems * d->kernel, 4.0 * ((double)d->batch * d->t_in + out_elems));
+  hipLaunchKernelGGL(c.vec ? conv1d_small_cin_kernel<true> : conv1d_small_cin_kernel<false>,
+                     dim3(ceil_div(d->t_out, SI_TILE), d->batch, c.ngroups), dim3(256), c.lds, stream, x, w_packed, bias, y,
+                     c.g.cin_pad, c.g.m_pad, d->c_out, c.cg, d->t_in, d->t_out, d->kernel, d->dilation, d->pad_left,
+                     d->pre_act, d->pre_slope, d->post_act, d->post_slope, d->out_mul);
+  PWG_CHECK_LAUNCH("conv1d_small_cin");
   return PWG_OK;
 }
 
@@ -1832,63 +1925,24 @@ extern "C" int pwg_conv1d_forward(const pwg_conv1d_desc* d_in, const float* x, c
                                   const float* bias, const float* add1, const float* add2, float* y,
                                   float* workspace, size_t workspace_floats, void* stream) {
   PWG_REQUIRE(d_in != nullptr, PWG_ERR_NULL, "conv1d: NULL descriptor");
-  const pwg_conv1d_desc flat = flatten_width(*d_in);
-  const pwg_conv1d_desc* d = &flat;
-  Geometry g;
-  int rc = make_geometry(d, &g);
+  ConvCall c;
+  int rc = conv_describe(*d_in, ask_launch(x, y, add1, add2, nullptr, workspace, workspace_floats), &c);
   if (rc != PWG_OK) return rc;
-  if (gconv_forward_applicable(d, add1, add2)) return gconv_forward(d, x, w_packed, bias, y, (hipStream_t)stream);
-  if (small_cin_applicable(d, add1 || add2)) {
-    ConvArgs chk;
-    rc = fill_args(d, g, x, w_packed, bias, add1, add2, y, &chk);
-    if (rc != PWG_OK) return rc;
-    // channel groups: at least ~1024 workgroups per launch (4 per CU), never fewer than 8 channels per group
-    const int pairs = ceil_div(d->t_out, SI_TILE) * d->batch;
-    int ngroups = ceil_div(1024, pairs);
-    if (ngroups > d->c_out / 8) ngroups = d->c_out / 8;
-    if (ngroups < 1) ngroups = 1;
-    const int cg = ceil_div(d->c_out, ngroups);
-    ngroups = ceil_div(d->c_out, cg);
-    const size_t lds = ((size_t)cg * (d->kernel + 1) + SI_TILE + (d->kernel - 1) * d->dilation) * sizeof(float);
-    PWG_REQUIRE(lds <= 64 * 1024, PWG_ERR_UNSUPPORTED, "conv1d (single input channel): %zu B of LDS", lds);
-    const double out_elems = (double)d->batch * d->c_out * d->t_out;
-    const bool vec = d->t_out % 4 == 0 && (reinterpret_cast<uintptr_t>(y) & 15u) == 0;
-    ProfScope prof((hipStream_t)stream, "conv1d_small_cin_kernel", 2.0 * out_elems * d->kernel,
-                   4.0 * ((double)d->batch * d->t_in + out_elems));
-    hipLaunchKernelGGL(vec ? conv1d_small_cin_kernel<true> : conv1d_small_cin_kernel<false>,
-                       dim3(ceil_div(d->t_out, SI_TILE), d->batch, ngroups), dim3(256), lds, (hipStream_t)stream, x, w_packed,
-                       bias, y, g.cin_pad, g.m_pad, d->c_out, cg, d->t_in, d->t_out, d->kernel, d->dilation, d->pad_left,
-                       d->pre_act, d->pre_slope, d->post_act, d->post_slope, d->out_mul);
-    PWG_CHECK_LAUNCH("conv1d_small_cin");
-    return PWG_OK;
-  }
-  if (small_cout_applicable(d, add1 || add2)) {
-    // (the same argument checks as the MFMA path: fill_args validates pointers and the pre-activation)
-    ConvArgs chk;
-    rc = fill_args(d, g, x, w_packed, bias, add1, add2, y, &chk);
-    if (rc != PWG_OK) return rc;
-    return run_small_cout(d, g, x, w_packed, bias, y, stream);
-  }
-  ConvArgs a;
-  rc = fill_args(d, g, x, w_packed, bias, add1, add2, y, &a);
+  if (c.route == CONV_GCONV) return gconv_forward(&c.d, x, w_packed, bias, y, (hipStream_t)stream);
+  rc = check_conv_args(c.d, x, w_packed, y);
   if (rc != PWG_OK) return rc;
-  return run_conv(d, g, a, workspace, workspace_floats, (hipStream_t)stream);
+  if (c.route == CONV_SMALL_CIN) return launch_small_cin(c, x, w_packed, bias, y, (hipStream_t)stream);
+  if (c.route == CONV_SMALL_COUT) return launch_small_cout(c, x, w_packed, bias, y, (hipStream_t)stream);
+  return launch_conv(c, fill_args(c, x, w_packed, bias, add1, add2, y, workspace), (hipStream_t)stream);
 }
 
-// The data gradient of a convolution is the transposed convolution with the same torch-layout
-// weight (and vice versa), so both directions reuse the forward kernels through the dual descriptor.
-static void dual_desc(const pwg_conv1d_desc* d, pwg_conv1d_desc* o) {
-  *o = *d;
-  o->c_in = d->c_out;
-  o->c_out = d->c_in;
-  o->t_in = d->t_out;
-  o->t_out = d->t_in;
-  o->transposed = d->transposed ? 0 : 1;
-  o->pad_mode = PWG_PAD_ZERO;
-  o->pre_act = PWG_ACT_NONE;
-  o->post_act = PWG_ACT_NONE;
-  o->pre_slope = o->post_slope = 0.f;
-  o->out_mul = o->out_div = 1.f;
+// The workspace queries cannot see a call's addends.  They ask as a call with addends does: no route but the MFMA
+// kernels takes one, so the answer is the MFMA plan's need -- an upper bound, the other routes need none.
+extern "C" size_t pwg_conv1d_forward_workspace_floats(const pwg_conv1d_desc* d_in) {
+  ConvAsk ask;
+  ask.addends = true;
+  ConvCall c;
+  return d_in && conv_describe(*d_in, ask, &c) == PWG_OK ? c.ws_floats : 0;
 }
 
 extern "C" size_t pwg_conv1d_packed_weight_bwd_floats(const pwg_conv1d_desc* d) {
@@ -1917,85 +1971,45 @@ extern "C" int pwg_conv1d_backward_data(const pwg_conv1d_desc* d, const float* d
                                         const float* x, const float* accum, float* dx, float* workspace,
                                         size_t workspace_floats, void* stream) {
   PWG_REQUIRE(d, PWG_ERR_NULL, "conv1d_backward_data: NULL descriptor");
-  PWG_REQUIRE(d->pad_mode == PWG_PAD_ZERO, PWG_ERR_UNSUPPORTED,
-              "conv1d_backward_data: only zero padding (pad reflect/replicate inputs explicitly)");
-  PWG_REQUIRE(d->pre_act == PWG_ACT_NONE || x != nullptr, PWG_ERR_NULL,
-              "conv1d_backward_data: the forward input is needed for the pre-activation derivative");
-  if (gconv_dgrad_applicable(d)) return gconv_backward_data(d, dy, w_packed_bwd, x, accum, dx, (hipStream_t)stream);
-  pwg_conv1d_desc dd;
-  dual_desc(d, &dd);
-  dd = flatten_width(dd);
-  Geometry g;
-  int rc = make_geometry(&dd, &g);
+  const float* mask = d->pre_act != PWG_ACT_NONE ? x : nullptr;
+  ConvAsk ask = ask_launch(dy, dx, accum, nullptr, mask, workspace, workspace_floats);
+  ask.dual = true;
+  ask.fwd_input = x != nullptr;
+  ConvCall c;
+  int rc = conv_describe(*d, ask, &c);
   if (rc != PWG_OK) return rc;
-  // Round 6: the data gradient of a stride-1 layer with one (<= 4) input channel over a long sequence -- every discriminator's
-  // first layer, when the discriminator's input needs a gradient (generator phase) -- is a plain few-OUTPUT-channel convolution
-  // over the flipped taps (make_geometry: that is how the backward image is packed): on the MFMA tile one of 32 rows carries data
-  // (2.5 TFLOP/s, 0.2 ms for MelGAN's 16 -> 1 k = 15 layer at B64 x 16384, 0.15 ms for HiFi-GAN's 128 -> 1); the streaming
-  // kernels read dy once.  PWG_SMALL_COUT_DGRAD=0: the MFMA path.
-  static const bool dgrad_stream = !(getenv("PWG_SMALL_COUT_DGRAD") && atoi(getenv("PWG_SMALL_COUT_DGRAD")) == 0);
-  if (dgrad_stream && dd.stride == 1 && g.phases == 1 && g.out_off == 0 && accum == nullptr && d->pre_act == PWG_ACT_NONE) {
-    pwg_conv1d_desc pd = dd;
-    pd.transposed = 0;
-    pd.pad_left = g.pad;
-    // (the LDS kernel walks the input channels one by one, two barriers each: 0.29 ms for HiFi-GAN's 128 -> 1 k = 15 against 0.13 ms
-    // on the MFMA tile -- only few channels take it; the LDS-free stream (k <= 7, "same" padding) has no such walk)
-    const bool stream_form = pd.dilation == 1 && (pd.kernel & 1) && pd.kernel <= 7 && pd.pad_left == (pd.kernel - 1) / 2 &&
-                             pd.t_out == pd.t_in && (pd.t_in & 3) == 0 && ((((uintptr_t)dy) | ((uintptr_t)dx)) & 15) == 0 &&
-                             (pd.c_out == 1 || pd.c_out == 4);
-    if (small_cout_applicable(&pd, false) && (pd.c_in <= 32 || stream_form)) {
-      PWG_REQUIRE(dy && w_packed_bwd && dx, PWG_ERR_NULL, "conv1d_backward_data: NULL pointer");
-      Geometry pg;
-      rc = make_geometry(&pd, &pg);
-      if (rc != PWG_OK) return rc;
-      PWG_REQUIRE(pg.cin_pad == g.cin_pad && pg.m_pad == g.m_pad && pg.k_phase == g.k_phase, PWG_ERR_UNSUPPORTED,
-                  "conv1d_backward_data: plain form of the dual descriptor has another image layout");
-      return run_small_cout(&pd, pg, dy, w_packed_bwd, nullptr, dx, stream);
-    }
+  if (c.route == CONV_GCONV) return gconv_backward_data(d, dy, w_packed_bwd, x, accum, dx, (hipStream_t)stream);
+  if (c.route == CONV_SMALL_COUT) {
+    PWG_REQUIRE(dy && w_packed_bwd && dx, PWG_ERR_NULL, "conv1d_backward_data: NULL pointer");
+    return launch_small_cout(c, dy, w_packed_bwd, nullptr, dx, (hipStream_t)stream);
   }
-  ConvArgs a;
-  rc = fill_args(&dd, g, dy, w_packed_bwd, nullptr, accum, nullptr, dx, &a);
+  rc = check_conv_args(c.d, dy, w_packed_bwd, dx);
   if (rc != PWG_OK) return rc;
-  if (d->pre_act != PWG_ACT_NONE) {
-    a.mask_src = x;
-    a.mask_slope = d->pre_act == PWG_ACT_LEAKY_RELU ? d->pre_slope : 0.f;
-  }
-  return run_conv(&dd, g, a, workspace, workspace_floats, (hipStream_t)stream);
+  ConvArgs a = fill_args(c, dy, w_packed_bwd, nullptr, accum, nullptr, dx, workspace);
+  a.mask_src = mask;
+  a.mask_slope = d->pre_act == PWG_ACT_LEAKY_RELU ? d->pre_slope : 0.f;
+  return launch_conv(c, a, (hipStream_t)stream);
 }
 
 extern "C" int pwg_conv1d_num_tile_configs(void) { return kNumCfgs; }
 
 extern "C" int pwg_conv1d_plan(const pwg_conv1d_desc* d_in, int32_t has_addends, int32_t* out) {
   PWG_REQUIRE(d_in != nullptr && out != nullptr, PWG_ERR_NULL, "conv1d_plan: NULL pointer");
-  const pwg_conv1d_desc flat = flatten_width(*d_in);
-  const pwg_conv1d_desc* d = &flat;
-  Geometry g;
-  int rc = make_geometry(d, &g);
+  ConvAsk ask;
+  ask.addends = has_addends != 0;
+  ConvCall c;
+  int rc = conv_describe(*d_in, ask, &c);
   if (rc != PWG_OK) return rc;
   for (int i = 0; i < 8; ++i) out[i] = 0;
-  const float* addend = has_addends ? reinterpret_cast<const float*>(out) : nullptr;  // (only tested against NULL)
-  if (gconv_forward_applicable(d, addend, nullptr)) {
-    out[0] = 1;
-    return PWG_OK;
-  }
-  if (small_cin_applicable(d, has_addends != 0)) {
-    out[0] = 2;
-    return PWG_OK;
-  }
-  if (small_cout_applicable(d, has_addends != 0)) {
-    out[0] = 3;
-    return PWG_OK;
-  }
-  const ConvPlan p = plan_conv(d, g);
-  const TileCfg c = cfg_info(p.id);
-  const int gx = ceil_div(g.n_cols, c.bn), mtiles = ceil_div(g.m_g, c.bm);
-  out[1] = p.id;
-  out[2] = p.dma ? p.ksplit : 1;
-  out[3] = p.dma ? 1 : 0;
-  out[4] = p.dma ? choose_tile_order(g, d->width, d->t_in, c.bm, c.bn, gx, mtiles, d->groups, d->batch, out[2]) : 0;
-  out[5] = gx;
-  out[6] = mtiles * d->groups;
-  out[7] = d->batch * out[2];
+  out[0] = c.route;
+  if (c.route != CONV_MFMA) return PWG_OK;
+  out[1] = c.id;
+  out[2] = c.ksplit;
+  out[3] = c.dma ? 1 : 0;
+  out[4] = c.item_major;
+  out[5] = (int32_t)c.grid.x;
+  out[6] = (int32_t)c.grid.y;
+  out[7] = (int32_t)c.grid.z;
   return PWG_OK;
 }
 
@@ -2025,19 +2039,15 @@ extern "C" int pwg_conv1d_forward_cfg(const pwg_conv1d_desc* d_in, const float* 
                                       const float* bias, const float* add1, const float* add2, float* y,
                                       int32_t tile_config, int32_t use_dma, void* stream) {
   PWG_REQUIRE(d_in != nullptr, PWG_ERR_NULL, "conv1d: NULL descriptor");
-  const pwg_conv1d_desc flat = flatten_width(*d_in);
-  const pwg_conv1d_desc* d = &flat;
-  Geometry g;
-  int rc = make_geometry(d, &g);
+  ConvAsk ask = ask_launch(x, y, add1, add2, nullptr, nullptr, 0);
+  ask.forced = true;
+  ask.tile = tile_config;
+  ask.dma = use_dma != 0;
+  ConvCall c;
+  int rc = conv_describe(*d_in, ask, &c);
+  if (rc == PWG_OK) rc = check_conv_args(c.d, x, w_packed, y);
   if (rc != PWG_OK) return rc;
-  ConvArgs a;
-  rc = fill_args(d, g, x, w_packed, bias, add1, add2, y, &a);
-  if (rc != PWG_OK) return rc;
-  PWG_REQUIRE(tile_config >= 0 && tile_config < kNumCfgs, PWG_ERR_UNSUPPORTED, "conv1d: tile config %d out of range",
-              tile_config);
-  PWG_REQUIRE(!(use_dma && d->pad_mode != PWG_PAD_ZERO), PWG_ERR_UNSUPPORTED,
-              "conv1d: the DMA path implements zero padding only");
-  return launch_cfg(tile_config, use_dma != 0, a, g, d->batch, d->groups, (hipStream_t)stream);
+  return launch_conv(c, fill_args(c, x, w_packed, bias, add1, add2, y, nullptr), (hipStream_t)stream);
 }
 
 extern "C" int pwg_weight_norm_scale(const float* v, const float* g, float* scale, int32_t n0,
@@ -2070,23 +2080,6 @@ extern "C" int pwg_scale_rows(const float* v, const float* scale, float* w, int3
 // info[0] = n_rows_tab, info[1] = total scale rows, info[2] = n forward images, info[3] = pack workgroups of the
 // forward images, info[4] = n images, info[5] = pack workgroups of all images, info[6] = byte offset of the images.
 // ---------------------------------------------------------------------------
-static void fill_pack_args(const pwg_conv1d_desc* d, const Geometry& g, const float* w, const float* scale, float* wp,
-                           PackArgs* a) {
-  a->w = w;
-  a->scale = scale;
-  a->wp = wp;
-  a->groups = d->groups;
-  a->k_phase = g.k_phase;
-  a->cin_g = g.cin_g;
-  a->cin_pad = g.cin_pad;
-  a->cout_g = g.cout_g;
-  a->m_g = g.m_g;
-  a->m_pad = g.m_pad;
-  a->kernel = d->kernel;
-  a->stride = d->stride;
-  a->transposed = d->transposed;
-}
-
 extern "C" size_t pwg_weight_bank_table_bytes(int32_t n_items) {
   if (n_items <= 0) return 0;
   return (size_t)n_items * (sizeof(BankRows) + 2 * sizeof(BankImage));

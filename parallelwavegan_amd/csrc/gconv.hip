@@ -417,8 +417,8 @@ static bool gconv_geometry_ok(const pwg_conv1d_desc* d) {
   return !off;
 }
 
-bool gconv_forward_applicable(const pwg_conv1d_desc* d, const float* add1, const float* add2) {
-  if (!gconv_geometry_ok(d) || add1 || add2 || d->out_div != 1.0f) return false;
+bool gconv_forward_applicable(const pwg_conv1d_desc* d, bool has_addends) {
+  if (!gconv_geometry_ok(d) || has_addends || d->out_div != 1.0f) return false;
   if (d->pre_act == PWG_ACT_TANH) return false;
   if (d->pre_act == PWG_ACT_LEAKY_RELU && !(d->pre_slope >= 0.f && d->pre_slope <= 1.f)) return false;
   return true;

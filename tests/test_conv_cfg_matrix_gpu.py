@@ -355,3 +355,33 @@ def test_data_gradient(shape, mode, device):
     assert torch.equal(dx, dx_o), f"misaligned out changes {int((dx != dx_o).sum())} values"
     if with_accum:
         assert torch.equal(dx, dx_a), f"misaligned accum changes {int((dx != dx_a).sum())} values"
+
+
+def test_split_plan_without_enough_workspace(device):
+    """S4 through the C entry point itself (``ops.conv1d_forward`` always brings the workspace the query asks for): with
+    no workspace, and with one a float short of the query, the dispatcher drops the plan's two reduction slices and
+    launches the best unsplit tile instead -- same bound, same guard bands, and the same bits either way."""
+    v = _variant("mrf")
+    desc = _desc("S4", v)
+    lib = _lib.lib()
+    need = lib.pwg_conv1d_forward_workspace_floats(ctypes.byref(desc))
+    assert ops.conv1d_plan(desc, has_addends=True)["ksplit"] == 2 and need > 1
+    x, w, bias, add1, add2 = _dev("S4", device, "x", "w", "bias", "add1", "add2")
+    ref = _forward_ref("S4", "mrf").to(device)
+    scale = float(ref.abs().max()) + 1e-12
+    short = torch.empty(need - 1, device=device, dtype=torch.float32)
+    outs = []
+    with poison_lds(), poison_empty(), ops.profile() as prof:
+        wp = ops.pack_weight(desc, w)
+        for what, ws, ws_n in (("NULL workspace", None, need), ("workspace one float short", short, need - 1)):
+            gd = Guarded(tuple(ref.shape), device)
+            rc = lib.pwg_conv1d_forward(ctypes.byref(desc), ops._ptr(x), ops._ptr(wp), ops._ptr(bias), ops._ptr(add1),
+                                        ops._ptr(add2), ops._ptr(gd.out), ops._ptr(ws), ws_n, ops._stream())
+            assert rc == 0, f"{what}: status {rc}: {lib.pwg_last_error().decode(errors='replace')}"
+            y = gd.check(what)
+            err = _rel_err(y, ref, scale)
+            print(f"{what}: rel-to-max error {err:.3e}")
+            assert err <= RTOL, f"{what}: rel-to-max error {err:.3e}"
+            outs.append(y)
+    assert "splitk_finish_kernel" not in prof.results, sorted(prof.results)
+    assert torch.equal(outs[0], outs[1])
