@@ -303,6 +303,34 @@ int pwg_conv1d_stream_bf16_forward(const pwg_conv1d_desc* d, const float* x, con
                                    const void* w_packed_bf16, const float* bias, const float* add1,
                                    const float* add2, float* y, void* stream);
 
+/* ---- the stream launch with delayed addends and a valid window (fp32; csrc/conv1d_stream.hip) ----
+ * For streaming a NON-causal network with a fixed look-ahead: every layer runs in its causal form on a shifted time
+ * axis, so an addend of the epilogue (the residual input of a unit, the running sum of the MRF blocks) is older than
+ * the launch's output by a fixed number of columns and is read through a delay line, and the columns that lie outside
+ * the utterance on the shifted axis must be exact zeros, as the whole-utterance zero padding is.
+ * d, x, hist_in, hist_out, w_packed, bias, y: as for pwg_conv1d_stream_forward, with d->pad_mode == PWG_PAD_ZERO.
+ * For output column j (chunk-relative, 0 <= j < d->t_out):
+ *   valid_lo <= j < valid_hi: the value pwg_conv1d_stream_forward computes, with add_i[j] replaced by
+ *     concat(add_i_hist_in, add_i)[j] -- add_i_hist_in (batch, c_out, delay_i) holds the delay_i addend columns before
+ *     this chunk, NULL = zeros (start of stream);
+ *   every other column: 0.0f is STORED (not skipped), whatever bias, addends and post_act are.
+ * add_i_hist_out (batch, c_out, delay_i) = the last delay_i columns of concat(add_i_hist_in, add_i), written by the
+ * same launch, also when d->t_out < delay_i; it must be a buffer distinct from add_i_hist_in.  delay_i == 0: a plain
+ * addend (or none: add_i NULL), both history pointers ignored.  delay_i > 0 needs add_i and add_i_hist_out.
+ * Contraction, sum order ((p0 + p1) + p2) + p3 and tile rule are pwg_conv1d_stream_forward's: with delay_i == 0 and
+ * the window [0, t_out) y and hist_out equal that entry's bit for bit; with delays they equal that entry given the
+ * addends delayed on the host.  The addends are read from their two sources in the epilogue (no LDS).
+ * pwg_conv1d_stream_delayed_supported: pure host logic (no device needed); 0 -- pwg_last_error names the reason -- for
+ * whatever pwg_conv1d_stream_supported refuses, for a pad_mode other than PWG_PAD_ZERO, and for a delay that is
+ * negative or above 144 columns (the cap of a history).
+ * These two symbols are purely additive -- no existing signature or behaviour changes -- so pwg_abi_version() stays 15. */
+int pwg_conv1d_stream_delayed_supported(const pwg_conv1d_desc* d, int32_t delay1, int32_t delay2);
+int pwg_conv1d_stream_delayed_forward(const pwg_conv1d_desc* d, const float* x, const float* hist_in, float* hist_out,
+                                      const float* w_packed, const float* bias, const float* add1,
+                                      const float* add1_hist_in, float* add1_hist_out, int32_t delay1, const float* add2,
+                                      const float* add2_hist_in, float* add2_hist_out, int32_t delay2, int32_t valid_lo,
+                                      int32_t valid_hi, float* y, void* stream);
+
 /* Diagnostics (host only, no launch, no device needed): the plan pwg_conv1d_forward derives for a descriptor.
  * has_addends: 1 if add1 / add2 will be passed.  out[8]:
  *   out[0] kernel family: 0 = MFMA implicit-GEMM kernel, 1 = grouped 16x16x4 kernel, 2 = single-input-channel

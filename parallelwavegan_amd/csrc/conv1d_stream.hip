@@ -32,6 +32,13 @@
 // give 32 workgroups for 512 rows; and inside a workgroup the four waves split the REDUCTION (each takes every fourth
 // 16-channel group) instead of the rows, with the next four taps' weights in flight while the current ones are contracted.
 // DESIGN.md s11.
+//
+// Delayed form (pwg_conv1d_stream_delayed_forward): the same launch for a layer of a NON-causal
+// network streamed with a fixed look-ahead.  The layer runs in its causal form on a shifted time axis, so its addends
+// (the residual input, the MRF running sum) arrive earlier than its output and are read through delay lines kept like
+// the history, and output columns outside the utterance's valid window are stored as zeros (StreamDelay,
+// stream_common.h).  Operand pipeline, contraction and sum order are those of the plain form: only the history writer
+// and the epilogue differ, and the plain instantiations are the code they were.
 #include "stream_common.h"
 
 namespace pwg {
@@ -101,11 +108,15 @@ struct StreamArgs : StreamCommonArgs {
   int cin_pad, m_pad, xs;
 };
 
+struct StreamDelayedArgs : StreamArgs {
+  StreamDelay dl;
+};
+
 // One workgroup (4 waves) owns MT = 16 * TM rows x NT = 16 * TN columns.  The reduction is dealt over the four waves:
 // wave w takes the w-th 16-channel group of every staged block of 64 channels, and the four partial tiles are summed
 // through LDS in wave order, ((p0 + p1) + p2) + p3 -- the same in every configuration.
-template <int TM, int TN, bool TRANSPOSED>
-__global__ __launch_bounds__(256) void conv1d_stream_kernel(StreamArgs a) {
+template <int TM, int TN, bool TRANSPOSED, bool DELAYED = false>
+__global__ __launch_bounds__(256) void conv1d_stream_kernel(std::conditional_t<DELAYED, StreamDelayedArgs, StreamArgs> a) {
   constexpr int MT = 16 * TM, NT = 16 * TN;
   extern __shared__ __attribute__((aligned(16))) float xs[];  // [SC][a.xs]; afterwards the partial tiles [4][MT][NT]
 
@@ -120,6 +131,19 @@ __global__ __launch_bounds__(256) void conv1d_stream_kernel(StreamArgs a) {
 
   stream_write_history<1>(xb, hb, a.hist_out + (size_t)b * a.c_in * H, a.c_in, n, H, a.pad_mode == PWG_PAD_REPLICATE,
                        blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
+  if constexpr (DELAYED) {
+    // the addends' delay lines: the history rule on (c_out, t_out) rows, zero start
+    const float* adds[2] = {a.ep.add1, a.ep.add2};
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int D = a.dl.delay[i];
+      if (D == 0) continue;
+      const size_t rows = (size_t)b * a.ep.c_out;
+      stream_write_history<1>(adds[i] + rows * a.ep.t_out, a.dl.hist_in[i] ? a.dl.hist_in[i] + rows * D : nullptr,
+                              a.dl.hist_out[i] + rows * D, a.ep.c_out, a.ep.t_out, D, false,
+                              blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
+    }
+  }
 
   f32x4 acc[TM][TN];
 #pragma unroll
@@ -229,13 +253,36 @@ __global__ __launch_bounds__(256) void conv1d_stream_kernel(StreamArgs a) {
     }
   }
 
-  stream_reduce_epilogue<MT, NT, TRANSPOSED, StreamRows::PhaseMajor>(xs, acc, a.ep, m0, q0, b);
+  if constexpr (DELAYED)
+    stream_reduce_epilogue<MT, NT, TRANSPOSED, StreamRows::PhaseMajor>(xs, acc, a.ep, m0, q0, b, a.dl);
+  else
+    stream_reduce_epilogue<MT, NT, TRANSPOSED, StreamRows::PhaseMajor>(xs, acc, a.ep, m0, q0, b);
 }
 
 template <int TM, int TN, bool TRANSPOSED>
 struct Kernel {
   static constexpr auto fn = conv1d_stream_kernel<TM, TN, TRANSPOSED>;
 };
+
+template <int TM, int TN, bool TRANSPOSED>
+struct DelayedKernel {
+  static constexpr auto fn = conv1d_stream_kernel<TM, TN, TRANSPOSED, true>;
+};
+
+// What the delayed form adds to stream_geometry(): zero padding only (the shifted time axis starts from the
+// whole-utterance zero padding) and delay lines no longer than a history
+int delayed_geometry(const pwg_conv1d_desc* d, int32_t delay1, int32_t delay2, StreamGeom* g) {
+  const int rc = stream_geometry(d, g);
+  if (rc != PWG_OK) return rc;
+  PWG_REQUIRE(d->pad_mode == PWG_PAD_ZERO, PWG_ERR_UNSUPPORTED,
+              "conv1d_stream_delayed: pad_mode = %d (the delayed form starts a stream from zeros only)", d->pad_mode);
+  PWG_REQUIRE(delay1 >= 0 && delay2 >= 0, PWG_ERR_BAD_SHAPE, "conv1d_stream_delayed: negative delay (%d, %d)", delay1,
+              delay2);
+  PWG_REQUIRE(delay1 <= kStreamMaxHist && delay2 <= kStreamMaxHist, PWG_ERR_UNSUPPORTED,
+              "conv1d_stream_delayed: addend delay of %d columns (at most %d)", delay1 > delay2 ? delay1 : delay2,
+              kStreamMaxHist);
+  return PWG_OK;
+}
 
 }  // namespace
 }  // namespace pwg
@@ -282,5 +329,65 @@ extern "C" int pwg_conv1d_stream_forward(const pwg_conv1d_desc* d, const float* 
   stream_launch<Kernel>(tile, d->transposed != 0, a, g.m, d->batch,
                         stream_lds_bytes((size_t)SC * a.xs * sizeof(float), tile), stream);
   PWG_CHECK_LAUNCH("conv1d_stream");
+  return PWG_OK;
+}
+
+extern "C" int pwg_conv1d_stream_delayed_supported(const pwg_conv1d_desc* d, int32_t delay1, int32_t delay2) {
+  StreamGeom g;
+  return delayed_geometry(d, delay1, delay2, &g) == PWG_OK ? 1 : 0;
+}
+
+extern "C" int pwg_conv1d_stream_delayed_forward(const pwg_conv1d_desc* d, const float* x, const float* hist_in,
+                                                 float* hist_out, const float* w_packed, const float* bias,
+                                                 const float* add1, const float* add1_hist_in, float* add1_hist_out,
+                                                 int32_t delay1, const float* add2, const float* add2_hist_in,
+                                                 float* add2_hist_out, int32_t delay2, int32_t valid_lo, int32_t valid_hi,
+                                                 float* y, void* stream_) {
+  StreamGeom g;
+  int rc = delayed_geometry(d, delay1, delay2, &g);
+  if (rc != PWG_OK) return rc;
+  hipStream_t stream = (hipStream_t)stream_;
+  rc = stream_check_pointers("conv1d_stream_delayed", d, g, x, w_packed, y, hist_in, hist_out);
+  if (rc != PWG_OK) return rc;
+  PWG_REQUIRE((reinterpret_cast<uintptr_t>(w_packed) & 3u) == 0, PWG_ERR_BAD_SHAPE,
+              "conv1d_stream_delayed: unaligned weight image");
+  const float* adds[2] = {add1, add2};
+  const float* hin[2] = {add1_hist_in, add2_hist_in};
+  float* hout[2] = {add1_hist_out, add2_hist_out};
+  const int delays[2] = {delay1, delay2};
+  for (int i = 0; i < 2; ++i) {
+    if (delays[i] == 0) continue;
+    PWG_REQUIRE(adds[i] && hout[i], PWG_ERR_NULL,
+                "conv1d_stream_delayed: delay%d = %d needs add%d and add%d_hist_out", i + 1, delays[i], i + 1, i + 1);
+    PWG_REQUIRE(hin[i] != hout[i], PWG_ERR_BAD_SHAPE,
+                "conv1d_stream_delayed: add%d_hist_in and add%d_hist_out must be distinct buffers", i + 1, i + 1);
+  }
+  const int n = d->t_in;
+  const StreamTile tile = stream_tile(n, g.m, d->batch);
+
+  StreamDelayedArgs a;
+  stream_fill_args(&a, d, g, tile, x, hist_in, hist_out, bias, add1, add2, y);
+  a.w = w_packed;
+  a.cin_pad = g.cin_pad;
+  a.m_pad = g.m_pad;
+  a.xs = xs_stride(16 * tile.tn + g.hist);
+  for (int i = 0; i < 2; ++i) {
+    a.dl.hist_in[i] = delays[i] ? hin[i] : nullptr;
+    a.dl.hist_out[i] = delays[i] ? hout[i] : nullptr;
+    a.dl.delay[i] = delays[i];
+  }
+  a.dl.valid_lo = valid_lo;
+  a.dl.valid_hi = valid_hi;
+
+  const double out_elems = (double)d->batch * d->c_out * d->t_out;
+  const double flops = 2.0 * (double)d->batch * g.m * n * g.taps * d->c_in;
+  const double bytes = 4.0 * ((double)d->batch * d->c_in * (n + 2.0 * g.hist) +
+                              out_elems * (1 + (add1 ? 1 : 0) + (add2 ? 1 : 0)) +
+                              2.0 * d->batch * d->c_out * (delay1 + delay2) + (double)g.taps * g.cin_pad * g.m_pad);
+  maybe_poison_lds(stream);
+  ProfScope prof(stream, "conv1d_stream_delayed_kernel", flops, bytes);
+  stream_launch<DelayedKernel>(tile, d->transposed != 0, a, g.m, d->batch,
+                               stream_lds_bytes((size_t)SC * a.xs * sizeof(float), tile), stream);
+  PWG_CHECK_LAUNCH("conv1d_stream_delayed");
   return PWG_OK;
 }

@@ -3,6 +3,7 @@
 //   history rule          stream_write_history   hist_out = the last H RAW columns of concat(hist_in, x)
 //   start-of-stream rule  StreamWindow::at       which source window column t comes from (history, chunk, padding)
 //   sum order, epilogue   stream_reduce_epilogue ((p0 + p1) + p2) + p3, then the fp32 epilogue
+//   delayed form          StreamDelay            addends read through a delay line, zeros stored outside a valid window
 //   tile rule             stream_tile            column tile from n; 32-row blocks only at 2 x 256 or more workgroups
 //   coverage              stream_geometry        defined in conv1d_stream.hip; both precisions admit the same layers
 // Internal to csrc/; the staging loops and contractions of the kernels differ on purpose and stay with them.
@@ -12,6 +13,8 @@
 #include "bf16_mfma.h"  // f32x4 (after common.h: it needs the HIP runtime header)
 
 #include <stdint.h>
+
+#include <type_traits>
 
 namespace pwg {
 
@@ -84,6 +87,26 @@ struct StreamEpilogue {
   float post_slope, out_mul, out_div;
 };
 
+// ---- the delayed form of the epilogue (the look-ahead stream of a non-causal network).  Addend i is
+// read through a delay line of delay[i] columns: output column j takes concat(hist_in[i], add_i)[j], i.e. hist_in[i][j]
+// for j < delay[i] (zero when hist_in[i] is NULL: start of stream) and add_i[j - delay[i]] afterwards; hist_out[i] = the
+// last delay[i] columns of that concatenation, written by the history rule above.  Output columns outside
+// [valid_lo, valid_hi) are STORED as 0.0f: the next layer then sees the whole-utterance zero padding there.  The value
+// of a valid column is formed by the same operations in the same order as without a delay.
+struct StreamDelay {
+  const float* hist_in[2];  // (B, c_out, delay[i]) or NULL
+  float* hist_out[2];       // (B, c_out, delay[i]); NULL where delay[i] == 0
+  int delay[2];
+  int valid_lo, valid_hi;   // output columns (chunk-relative, of t_out)
+};
+struct StreamNoDelay {};
+
+__device__ __forceinline__ float stream_delayed_addend(const float* __restrict__ add, const float* __restrict__ hist,
+                                                       int delay, size_t row, int t_out, int j) {
+  if (j >= delay) return add[row * t_out + (j - delay)];
+  return hist ? hist[row * delay + j] : 0.f;
+}
+
 // Row order of a transposed layer's image: row m = phase * C_out + co (fp32 image) or co * s + phase (bf16 image)
 enum class StreamRows { PhaseMajor, ChannelMajor };
 
@@ -91,9 +114,11 @@ enum class StreamRows { PhaseMajor, ChannelMajor };
 // row = 4 * (lane / 16) + register) go through LDS -- every wave writes its tile, zeros where it contracted nothing --
 // and one thread per output element adds them in wave order, ((p0 + p1) + p2) + p3, then bias, add1, add2, out_mul,
 // out_div and the post-activation.  `red` is the workgroup's LDS ([4][MT][NT + 1] floats, reusing the window's).
-template <int MT, int NT, bool TRANSPOSED, StreamRows ROWS>
+template <int MT, int NT, bool TRANSPOSED, StreamRows ROWS, class DELAY = StreamNoDelay>
 __device__ __forceinline__ void stream_reduce_epilogue(float* red, const f32x4 (&acc)[MT / 16][NT / 16],
-                                                       const StreamEpilogue& a, int m0, int q0, int b) {
+                                                       const StreamEpilogue& a, int m0, int q0, int b,
+                                                       const DELAY& dl = DELAY()) {
+  constexpr bool DELAYED = !std::is_same<DELAY, StreamNoDelay>::value;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l15 = lane & 15, lq = lane >> 4;
@@ -126,9 +151,21 @@ __device__ __forceinline__ void stream_reduce_epilogue(float* red, const f32x4 (
       }
     }
     const size_t o = ((size_t)b * a.c_out + co) * a.t_out + (TRANSPOSED ? j * a.phases + ph : j);
-    if (a.bias) v += a.bias[co];
-    if (a.add1) v += a.add1[o];
-    if (a.add2) v += a.add2[o];
+    if constexpr (DELAYED) {
+      const int jo = TRANSPOSED ? j * a.phases + ph : j;  // output column
+      if (jo < dl.valid_lo || jo >= dl.valid_hi) {
+        a.y[o] = 0.f;
+        continue;
+      }
+      const size_t orow = (size_t)b * a.c_out + co;
+      if (a.bias) v += a.bias[co];
+      if (a.add1) v += stream_delayed_addend(a.add1, dl.hist_in[0], dl.delay[0], orow, a.t_out, jo);
+      if (a.add2) v += stream_delayed_addend(a.add2, dl.hist_in[1], dl.delay[1], orow, a.t_out, jo);
+    } else {
+      if (a.bias) v += a.bias[co];
+      if (a.add1) v += a.add1[o];
+      if (a.add2) v += a.add2[o];
+    }
     if (a.out_mul != 1.0f) v *= a.out_mul;
     if (a.out_div != 1.0f) v = v / a.out_div;
     v = apply_act(v, a.post_act, a.post_slope);

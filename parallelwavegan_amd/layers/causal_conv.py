@@ -7,6 +7,8 @@ padded and trimmed: a causal convolution is the MFMA convolution kernel with lef
 ``padding = stride`` (which is exactly the reference's ``[stride:-stride]`` trim) on an input that
 got one replicated sample on the left.
 """
+import collections
+
 import torch
 
 from .. import functional as Fn
@@ -137,3 +139,104 @@ def _stream_forward(cv, desc, x, hist_in, hist_out, fused, precision="fp32"):
     with torch.no_grad():
         image = cv.packed_weight_bf16() if precision == "bf16" else cv.packed_weight()
         return forward(desc, x.contiguous(), hist_in, hist_out, image, bias, fused.get("add1"), fused.get("add2"))
+
+
+# ---- the NON-causal layers in causal form: streaming with a fixed look-ahead (utils.LookaheadStream).
+# A symmetric ``Conv1d(k, d, padding (k-1)d/2)`` is its causal form (history ``(k-1)d``) on a time axis shifted by its
+# padding; a ``ConvTranspose1d(2s, s, padding s//2 + s%2)`` is the causal polyphase form (one column of history, zero
+# start) shifted by its padding.  Every tensor of the streamed network therefore has a delay: stream column ``t`` holds
+# the whole-utterance column ``t - delay``, and exact zeros where that column does not exist.
+
+def lookahead_delay(cv, delay_in):
+    """Delay (columns) of the output of the non-causal ``cv`` run in causal form on an input delayed by ``delay_in``.
+    ValueError for a layer that has no such form."""
+    if cv.groups != 1 or cv.pad_mode != "zero":
+        raise ValueError(f"{cv}: only zero-padded, ungrouped layers stream with a look-ahead")
+    if cv.transposed:
+        s = cv.stride
+        if cv.kernel_size != 2 * s or cv.padding != s // 2 + s % 2 or cv.output_padding != s % 2 or cv.dilation != 1:
+            raise ValueError(f"{cv}: only ConvTranspose1d(kernel 2s, stride s, padding s//2 + s%2, output_padding s%2) "
+                             "streams with a look-ahead")
+        return delay_in * s + cv.padding
+    reach = (cv.kernel_size - 1) * cv.dilation
+    if cv.stride != 1 or reach % 2 or cv.padding != reach // 2 or cv.padding_right != reach // 2:
+        raise ValueError(f"{cv}: only a stride-1 Conv1d with symmetric padding (k - 1) * d / 2 streams with a look-ahead")
+    return delay_in + cv.padding
+
+
+def lookahead_history_columns(cv):
+    """Columns of raw input the causal form of the non-causal ``cv`` keeps: ``(k - 1) * d``, 1 for a transposed layer."""
+    return 1 if cv.transposed else (cv.kernel_size - 1) * cv.dilation
+
+
+def lookahead_desc(cv, batch, n, **fused):
+    """Descriptor of one push of ``n`` columns through the causal form of the non-causal ``cv``."""
+    if cv.transposed:
+        return ops.make_conv_desc(batch, cv.in_channels, cv.out_channels, n, n * cv.stride, cv.kernel_size, cv.stride, 1,
+                                  cv.stride, cv.groups, transposed=True, pad_mode="zero", **fused)
+    return ops.make_conv_desc(batch, cv.in_channels, cv.out_channels, n, n, cv.kernel_size, 1, cv.dilation,
+                              lookahead_history_columns(cv), cv.groups, transposed=False, pad_mode="zero", **fused)
+
+
+# One launch of the look-ahead walk: ``rate`` output columns per mel frame, ``delay`` of the output, ``delay1`` /
+# ``delay2`` = output delay minus the delay of addend 1 / 2 (0: no addend, or one that is not delayed)
+LookaheadLaunch = collections.namedtuple("LookaheadLaunch", "conv rate delay delay1 delay2")
+
+
+def lookahead_state_shapes(plan, batch):
+    """Shapes of the state tensors of one ping-pong half, in the order :class:`LookaheadWalk` takes them: per launch
+    its history (if any), then the delay line of addend 1, then of addend 2 (where delayed)."""
+    shapes = []
+    for launch in plan:
+        cv = launch.conv
+        if lookahead_history_columns(cv):
+            shapes.append((batch, cv.in_channels, lookahead_history_columns(cv)))
+        shapes += [(batch, cv.out_channels, d) for d in (launch.delay1, launch.delay2) if d]
+    return shapes
+
+
+class LookaheadWalk:
+    """One push through the launches of a delay plan: hands every launch its state tensors and its valid window.
+    ``state_in`` (None: start of stream, every state reads as zeros) / ``state_out``: one ping-pong half each, of
+    :func:`lookahead_state_shapes`.  ``frames_before``: frames the stream took before this push (None: steady state,
+    every window is full); ``total_frames``: the utterance's length once it is known (the flush), else None."""
+
+    def __init__(self, plan, state_in, state_out, frames_before=None, total_frames=None):
+        self._plan = iter(plan)
+        self._in = None if state_in is None else iter(state_in)
+        self._out = iter(state_out)
+        self.frames_before, self.total_frames = frames_before, total_frames
+
+    def _take(self, wanted):
+        if not wanted:
+            return (None, None)
+        return (None if self._in is None else next(self._in), next(self._out))
+
+    def run(self, cv, x, add1=None, add2=None, **fused):
+        """The next launch of the plan, which must be ``cv``'s, on the chunk ``x``; fused-epilogue keywords as in
+        ``forward``."""
+        launch = next(self._plan)
+        if launch.conv is not cv:
+            raise RuntimeError(f"look-ahead walk out of step: the plan expects {launch.conv}, the model ran {cv}")
+        if cv.precision != "fp32":
+            raise RuntimeError(f"{cv.__class__.__name__} is in {cv.precision} inference precision: the look-ahead stream is "
+                               "fp32 (utils.set_inference_precision(model, 'fp32'))")
+        hist = self._take(lookahead_history_columns(cv))
+        line1, line2 = self._take(launch.delay1), self._take(launch.delay2)
+        desc = lookahead_desc(cv, x.shape[0], x.shape[-1], **fused)
+        t_out = desc.t_out
+        lo, hi = 0, t_out
+        if self.frames_before is not None:
+            before = self.frames_before * launch.rate  # output columns the stream produced before this push
+            lo = min(max(launch.delay - before, 0), t_out)
+            if self.total_frames is not None:
+                hi = min(max(launch.delay + self.total_frames * launch.rate - before, 0), t_out)
+        if not ops.conv1d_stream_delayed_supported(desc, launch.delay1, launch.delay2):
+            from .. import _lib
+
+            raise RuntimeError("the delayed streaming kernel does not cover this layer: "
+                               + _lib.lib().pwg_last_error().decode(errors="replace"))
+        bias = None if cv.bias is None else cv.bias.detach()
+        with torch.no_grad():
+            return ops.conv1d_stream_delayed_forward(desc, x.contiguous(), hist[0], hist[1], cv.packed_weight(), bias,
+                                                     add1, line1, launch.delay1, add2, line2, launch.delay2, (lo, hi))

@@ -11,7 +11,7 @@ from .conv import Conv1d as _Conv1d
 from .conv import bf16_no_backward_error, group_image, resunit_split_admitted
 
 
-from .causal_conv import CausalConv1d  # noqa: E402  (depends on .conv only)
+from .causal_conv import CausalConv1d, LookaheadLaunch, lookahead_delay  # noqa: E402  (depends on .conv only)
 from .dropout import Dropout as _Dropout  # noqa: E402
 
 
@@ -426,4 +426,50 @@ class HiFiGANResidualBlock(torch.nn.Module):
             else:
                 x = conv1.stream_forward(x, *next(hist), precision=precision, pre_act=act1.kind, pre_slope=act1.slope,
                                          add1=x, add2=accum if last else None, out_div=out_div if last else 1.0)
+        return x
+
+    def lookahead_plan(self, delay_in, rate, delay_accum=None):
+        """Delay plan of the NON-causal block streamed with a look-ahead (layers/causal_conv.py; host only) ->
+        ``(launches, delay_out)``: one :class:`LookaheadLaunch` per convolution in the order :meth:`lookahead_forward`
+        runs them.  ``delay_in``: delay of the block's input; ``rate``: its columns per mel frame; ``delay_accum``: delay
+        of the MRF running sum added by the block's last launch (None: no sum yet).  The residual input of a unit is
+        older than the unit's output by the paddings of its convolutions; the running sum by the difference of the block
+        delays, which must not be negative."""
+        if self.use_causal_conv:
+            raise ValueError("HiFiGANResidualBlock: a causal block streams without look-ahead (stream_forward)")
+        launches, dx, n = [], delay_in, len(self.convs1)
+        for idx in range(n):
+            d_out = d1 = lookahead_delay(self.convs1[idx][1], dx)
+            if self.use_additional_convs:
+                d_out = lookahead_delay(self.convs2[idx][1], d1)
+                launches.append(LookaheadLaunch(self.convs1[idx][1], rate, d1, 0, 0))
+            delay2 = 0
+            if idx == n - 1 and delay_accum is not None:
+                delay2 = d_out - delay_accum
+                if delay2 < 0:
+                    raise ValueError(
+                        f"the MRF blocks of a stage must have non-decreasing delays to stream with a look-ahead: a block "
+                        f"of kernel {self.kernel_size}, dilations {self.dilations} (delay {d_out - delay_in} columns) "
+                        f"follows one with delay {delay_accum - delay_in} (order resblock_kernel_sizes ascending)")
+            last_conv = self.convs2[idx][1] if self.use_additional_convs else self.convs1[idx][1]
+            launches.append(LookaheadLaunch(last_conv, rate, d_out, d_out - dx, delay2))
+            dx = d_out
+        return launches, dx
+
+    def lookahead_forward(self, x, walk, accum=None, out_div=1.0):
+        """The NON-causal block on the next chunk of a look-ahead stream: the modules, order and fused epilogues of
+        :meth:`stream_forward`, every convolution in its causal form through ``walk`` (a
+        :class:`layers.causal_conv.LookaheadWalk` over the launches of :meth:`lookahead_plan`), which delays the addends."""
+        n = len(self.convs1)
+        for idx in range(n):
+            last = idx == n - 1
+            act1, conv1 = self.convs1[idx][0], self.convs1[idx][1]
+            if self.use_additional_convs:
+                act2, conv2 = self.convs2[idx][0], self.convs2[idx][1]
+                xt = walk.run(conv1, x, pre_act=act1.kind, pre_slope=act1.slope)
+                x = walk.run(conv2, xt, add1=x, add2=accum if last else None, pre_act=act2.kind, pre_slope=act2.slope,
+                             out_div=out_div if last else 1.0)
+            else:
+                x = walk.run(conv1, x, add1=x, add2=accum if last else None, pre_act=act1.kind, pre_slope=act1.slope,
+                             out_div=out_div if last else 1.0)
         return x

@@ -12,7 +12,8 @@ import torch
 
 from .. import functional as Fn
 from ..layers.activation import FusedActivation, PreActivated, deferrable
-from ..layers.causal_conv import CausalConv1d, CausalConvTranspose1d, stream_history_pairs
+from ..layers.causal_conv import (CausalConv1d, CausalConvTranspose1d, LookaheadLaunch, lookahead_delay,
+                                  stream_history_pairs)
 from ..layers.conv import Conv1d, Conv2d, ConvTranspose1d, each_conv
 from ..layers.pooling import get_pooling
 from ..streams import fork_now, run_branches, run_branches_chained
@@ -150,6 +151,48 @@ class HiFiGANGenerator(torch.nn.Module):
         act, conv = self.output_conv[0], self.output_conv[1]
         return conv.stream_forward(c, *next(hist), precision=precision, pre_act=act.kind, pre_slope=act.slope,
                                    post_act="tanh")
+
+    def lookahead_plan(self):
+        """Delay plan of the NON-causal generator streamed with a fixed look-ahead (:class:`utils.LookaheadStream`,
+        DESIGN.md s11.4): one ``LookaheadLaunch(conv, rate, delay, delay1, delay2)`` per convolution in the order
+        :meth:`lookahead_forward` runs them -- output columns per mel frame, delay of the output in columns, and how much
+        older its two addends are.  The last launch's delay is the stream's latency in samples.  Pure host logic over
+        the module geometry.  ValueError for a causal generator and for MRF blocks whose delays decrease."""
+        if self.use_causal_conv:
+            raise ValueError("HiFiGANGenerator: a causal generator streams without look-ahead (utils.CausalStream)")
+        delay, rate = lookahead_delay(self.input_conv, 0), 1
+        plan = [LookaheadLaunch(self.input_conv, rate, delay, 0, 0)]
+        nb = self.num_blocks
+        for i in range(self.num_upsamples):
+            up = self.upsamples[i][1]
+            delay, rate = lookahead_delay(up, delay), rate * up.stride
+            plan.append(LookaheadLaunch(up, rate, delay, 0, 0))
+            accum = None
+            for j in range(nb):
+                launches, accum = self.blocks[i * nb + j].lookahead_plan(delay, rate, accum)
+                plan += launches
+            delay = accum  # the stage's delay is its last block's
+        conv = self.output_conv[1]
+        plan.append(LookaheadLaunch(conv, rate, lookahead_delay(conv, delay), 0, 0))
+        return plan
+
+    @torch.no_grad()
+    def lookahead_forward(self, c, walk):
+        """The NON-causal ``forward`` on the next chunk ``c`` (B, in_channels, n) of a look-ahead stream -> (B,
+        out_channels, n * upsample_factor), late by the plan's last delay: the modules, order and fused epilogues of
+        :meth:`stream_forward`, every convolution in its causal form through ``walk`` (a
+        :class:`layers.causal_conv.LookaheadWalk` over :meth:`lookahead_plan`)."""
+        c = walk.run(self.input_conv, c)
+        nb = self.num_blocks
+        for i in range(self.num_upsamples):
+            act, up = self.upsamples[i][0], self.upsamples[i][1]
+            c = walk.run(up, c, pre_act=act.kind, pre_slope=act.slope)
+            cs = None
+            for j in range(nb):
+                cs = self.blocks[i * nb + j].lookahead_forward(c, walk, accum=cs, out_div=float(nb) if j == nb - 1 else 1.0)
+            c = cs
+        act, conv = self.output_conv[0], self.output_conv[1]
+        return walk.run(conv, c, pre_act=act.kind, pre_slope=act.slope, post_act="tanh")
 
     def reset_parameters(self):
         """N(0, 0.01) on conv weights as in the official implementation.

@@ -333,6 +333,34 @@ def conv1d_stream_forward(desc, x, hist_in, hist_out, w_packed, bias=None, add1=
     return out
 
 
+def conv1d_stream_delayed_supported(desc, delay1=0, delay2=0):
+    """Does the delayed form of the streaming kernel cover this descriptor with addend delays of ``delay1`` / ``delay2``
+    columns?  What :func:`conv1d_stream_supported` admits, with zero padding and delays up to the cap of a history.  Host
+    logic only; ``_lib.lib().pwg_last_error()`` names the reason for a False."""
+    return bool(_lib.lib().pwg_conv1d_stream_delayed_supported(ctypes.byref(desc), int(delay1), int(delay2)))
+
+
+def conv1d_stream_delayed_forward(desc, x, hist_in, hist_out, w_packed, bias=None, add1=None, add1_hist=(None, None),
+                                  delay1=0, add2=None, add2_hist=(None, None), delay2=0, valid=None, out=None):
+    """:func:`conv1d_stream_forward` for a layer of a non-causal network streamed with a fixed look-ahead: addend ``i``
+    is read through a delay line of ``delay_i`` columns -- ``add_i_hist = (hist_in, hist_out)``, each (batch, c_out,
+    delay_i), ``hist_in`` None for zeros; ``hist_out`` receives the last ``delay_i`` columns of ``concat(hist_in,
+    add_i)`` -- and output columns outside ``valid = (lo, hi)`` (chunk-relative; None: all of them are valid) are stored
+    as exact zeros.  One launch."""
+    flat = (add1_hist[0], add1_hist[1], add2_hist[0], add2_hist[1])
+    _require_device(x, hist_in, hist_out, w_packed, bias, add1, add2, out, *flat)
+    out = _conv1d_stream_out(desc, x, hist_in, hist_out, add1, add2, out)
+    for delay, (h_in, h_out) in ((delay1, add1_hist), (delay2, add2_hist)):
+        for t in (h_in, h_out):
+            assert t is None or t.numel() == desc.batch * desc.c_out * delay, (tuple(t.shape), delay)
+    lo, hi = (0, desc.t_out) if valid is None else valid
+    _lib.check(_lib.lib().pwg_conv1d_stream_delayed_forward(
+        ctypes.byref(desc), _ptr(x), _ptr(hist_in), _ptr(hist_out), _ptr(w_packed), _ptr(bias),
+        _ptr(add1), _ptr(flat[0]), _ptr(flat[1]), int(delay1), _ptr(add2), _ptr(flat[2]), _ptr(flat[3]), int(delay2),
+        int(lo), int(hi), _ptr(out), _stream()), "conv1d_stream_delayed_forward")
+    return out
+
+
 def conv1d_stream_bf16_supported(desc):
     """Does the bf16-operand streaming kernel (csrc/conv1d_stream_bf16.hip) cover this descriptor?  It answers exactly
     as :func:`conv1d_stream_supported`.  Host logic only; ``_lib.lib().pwg_last_error()`` names the reason for a False."""

@@ -21,6 +21,10 @@ transpose, the generator, and the float -> PCM16 conversion.
 transposed layer) on the device, so a push of ``n`` frames costs ``n`` frames of work with zero look-ahead
 (csrc/conv1d_stream.hip).  A causal multi-band MelGAN streams through a stateful PQMF synthesis, whose
 symmetric filter adds a fixed latency of ``latency_samples`` (32 for the recipe filter; csrc/pqmf.hip).
+
+``LookaheadStream`` streams the standard NON-causal HiFi-GAN: every layer runs in its causal form on a shifted time
+axis, so a push of ``n`` frames still costs ``n`` frames of work and every sample leaves a fixed ``latency_samples``
+late (3258 samples, 12.73 frames, for HiFi-GAN V1).
 """
 import ctypes
 
@@ -28,7 +32,8 @@ import torch
 
 from .. import _lib
 from ..graphs import GraphedInference
-from ..ops import _ptr, _require_device, _stream, conv1d_stream_bf16_supported, conv1d_stream_supported
+from ..ops import (_ptr, _require_device, _stream, conv1d_stream_bf16_supported, conv1d_stream_delayed_supported,
+                   conv1d_stream_supported)
 
 
 def normalize_transpose(c, mean=None, scale=None):
@@ -587,3 +592,118 @@ class PWGStream(_Stream):
                 static_z.copy_(noise, non_blocking=True)
 
         return self._step(n, (n, feats.shape[2]), eager, capture if self.use_graph else None, fill_static)
+
+
+class LookaheadStream(_Stream):
+    """Stateful streaming synthesis for the standard NON-causal ``HiFiGANGenerator`` (symmetric ``Conv1d``,
+    ``ConvTranspose1d(padding = s//2 + s%2)``: every recipe and released checkpoint) with a fixed look-ahead: ``push``
+    takes the next mel frames of ``batch`` lock-step streams at ``n`` frames of work, and every sample leaves
+    ``latency_samples`` late (``latency_frames``: the ceiling in frames; 3258 samples = 12.73 frames for HiFi-GAN V1).
+    After any push the samples emitted total ``max(0, frames_in * up - latency_samples)``, so the first pushes of an
+    utterance return short or empty tensors; ``flush()`` returns the tail, after which the emissions total ``frames *
+    up`` samples.  Any partition of the same frames gives bit-identical audio, equal to the whole-utterance ``forward``
+    up to fp32 summation order.  fp32 only.
+
+    How: every layer runs in its causal form on a shifted time axis (csrc/conv1d_stream.hip, the
+    delayed form).  A tensor of the network is a stream with a delay: a symmetric convolution adds its padding, a
+    transposed one multiplies by its stride and adds its padding; the residual input of a unit and the MRF running sum
+    are older than the launch that adds them and go through delay lines; every launch stores exact zeros outside the
+    utterance, which is what the next layer's zero padding is.  ``model.lookahead_plan()`` lists the delays.
+
+    State: per convolution the last ``(k - 1) * d`` columns of its raw input (one for a transposed layer) and the delay
+    lines of its addends, ping-pong (``state_bytes``: both halves).  ``use_graph``: a push whose windows are all full
+    (``latency_frames`` frames went before it) replays the two captured graphs of its chunk size, as in
+    :class:`CausalStream`; the pushes at the start of an utterance and ``flush()`` run eagerly.  ``close()`` does not
+    flush: an unflushed tail is dropped.
+    """
+
+    warmup_frames = 1
+
+    def __init__(self, model, batch=1, use_graph=True, normalize_before=False):
+        from ..layers.causal_conv import lookahead_desc, lookahead_state_shapes
+        from ..layers.conv import each_conv
+        from ..models import HiFiGANGenerator
+
+        if not isinstance(model, HiFiGANGenerator):
+            raise ValueError(f"LookaheadStream: {model.__class__.__name__} is not supported (only the non-causal "
+                             "HiFiGANGenerator; a reflect-padded MelGAN mirrors columns that have not arrived)")
+        if model.use_causal_conv:
+            raise ValueError("LookaheadStream: the model is causal (use_causal_conv=True) and streams without look-ahead "
+                             "through utils.CausalStream")
+        out_channels = model.output_conv[1].out_channels
+        if out_channels != 1:
+            raise ValueError(f"LookaheadStream: the generator emits {out_channels} channels; the stream returns one "
+                             "waveform per stream (out_channels == 1)")
+        if any(cv.precision != "fp32" for cv in each_conv(model)):
+            raise ValueError("LookaheadStream: the model is in bf16 inference precision; the look-ahead stream is fp32 "
+                             "(utils.set_inference_precision(model, 'fp32'))")
+        batch = self._checked_batch(batch)
+        plan = model.lookahead_plan()  # ValueError: decreasing block delays, a layer without a causal form
+        for launch in plan:
+            if not conv1d_stream_delayed_supported(lookahead_desc(launch.conv, batch, 8), launch.delay1, launch.delay2):
+                raise ValueError(f"LookaheadStream: {launch.conv} cannot be streamed: "
+                                 + _lib.lib().pwg_last_error().decode(errors="replace"))
+        self.precision = "fp32"
+        self.up = model.upsample_factor  # samples per frame
+        self._plan = plan
+        self._in_channels = model.input_conv.in_channels
+        self.latency_samples = plan[-1].delay
+        self.latency_frames = -(-self.latency_samples // self.up)
+        super().__init__(model, [], batch, use_graph, normalize_before, lookahead_state_shapes(plan, batch))
+
+    @staticmethod
+    def latency_samples_of(model):
+        """Samples every output leaves late, from the module geometry alone (no device, no kernel)."""
+        return model.lookahead_plan()[-1].delay
+
+    def reset(self):
+        """Back to start of stream; an unflushed tail is dropped."""
+        self._restart()
+        self._flushed = False
+
+    def _run(self, c, state_in, state_out, frames_before=None, total_frames=None):
+        """``c``: (batch, C, n) features, normalised; ``state_in`` (None: start of stream) / ``state_out``: one
+        ping-pong half each; ``frames_before`` None: steady state.  -> (batch, n * up), not yet trimmed."""
+        from ..layers.causal_conv import LookaheadWalk
+
+        walk = LookaheadWalk(self._plan, state_in, state_out, frames_before, total_frames)
+        return self.model.lookahead_forward(c, walk).reshape(self.batch, -1)
+
+    def _capture(self, feats):
+        static_in = feats.clone()
+        return static_in, _capture_directions(self._halves, lambda si, so: self._run(self._features(static_in), si, so))
+
+    @torch.no_grad()
+    def push(self, feats):
+        """feats: (n, C) or (batch, n, C) float features -> (batch, samples) fp32, the samples that became complete:
+        ``n * up`` once ``latency_samples`` are behind, fewer (or none) before.  The result is the caller's own tensor."""
+        if self._flushed:
+            raise RuntimeError("LookaheadStream.push: the utterance was flushed; reset() starts the next one")
+        feats = self._coerce(feats)
+        n = feats.shape[1]
+        if n == 0:
+            return self._empty()
+        before = self.frames_in
+        self.frames_in += n
+        skip = max(0, self.latency_samples - before * self.up)  # columns of this chunk in front of the first sample
+        steady = before >= self.latency_frames                  # every launch's window is full
+        return self._step(n, (n, feats.shape[2]),
+                          lambda si, so: self._run(self._features(feats), si, so, before)[:, skip:].contiguous(),
+                          (lambda: self._capture(feats)) if self.use_graph and steady else None,
+                          lambda static_in: static_in.copy_(feats, non_blocking=True))
+
+    @torch.no_grad()
+    def flush(self):
+        """End of the utterance: ``latency_frames`` zero frames with the end-of-utterance windows (every launch stores
+        zeros past the utterance's last column, as the whole-utterance padding is) -> the last ``min(latency_samples,
+        frames * up)`` samples, (batch, samples).  Zero-length before anything was pushed and on a second call.  The next
+        utterance starts with ``reset()``."""
+        if not self._started or self._flushed:
+            return self._empty()
+        total = self.frames_in
+        zeros = torch.zeros((self.batch, self._in_channels, self.latency_frames), device=self._device)
+        y = self._run(zeros, self._halves[self._cur], self._halves[1 - self._cur], total, total)
+        y = y[:, max(0, self.latency_samples - total * self.up):self.latency_samples].contiguous()
+        self._flushed = True  # (the halves are not swapped: nothing may follow but reset())
+        self.samples_out += y.shape[1]
+        return y

@@ -26,8 +26,14 @@ launch per gated layer on the chunk (csrc/wavenet_stream.hip) -- against halo re
 whole-utterance causal ``forward`` over ``left + n`` frames (plus the context window), ``left`` from
 ``receptive_field_frames``, on static noise; ``push`` is given its noise too (it copies it into the graph's buffer).
 
-usage: python tools/bench_stream.py [--model pwg] [--multiband] [--precision bf16] [--reps 200] [--repeats 3]
-                                    [--out profiles/stream_infer.json]
+``--lookahead``: the standard NON-causal HiFi-GAN V1 through ``utils.LookaheadStream`` (every layer in causal form on a
+shifted time axis, csrc/conv1d_stream.hip's delayed form) against halo recompute, same method: steady-
+state pushes of 4 / 8 / 32 frames at 1 and 16 streams, into profiles/stream_lookahead_infer.json.  The halo side is ONE
+graph of the whole-utterance forward over ``left + n + right`` frames, both from ``receptive_field_frames``: a non-causal
+chunk needs its future context too, and cannot be emitted before those ``right`` frames arrived either.
+
+usage: python tools/bench_stream.py [--model pwg] [--multiband] [--precision bf16] [--lookahead] [--reps 200]
+                                    [--repeats 3] [--out profiles/stream_infer.json]
 """
 import argparse
 import json
@@ -42,7 +48,7 @@ from parallelwavegan_amd import ops  # noqa: E402
 from parallelwavegan_amd.graphs import GraphedInference  # noqa: E402
 from parallelwavegan_amd.layers import PQMF  # noqa: E402
 from parallelwavegan_amd.models import HiFiGANGenerator, MelGANGenerator, ParallelWaveGANGenerator  # noqa: E402
-from parallelwavegan_amd.utils import CausalStream, PWGStream  # noqa: E402
+from parallelwavegan_amd.utils import CausalStream, LookaheadStream, PWGStream  # noqa: E402
 from parallelwavegan_amd.utils.streaming import receptive_field_frames  # noqa: E402
 from tests.golden import synth  # noqa: E402
 
@@ -57,6 +63,14 @@ MELGAN_RECIPE_CAUSAL = dict(in_channels=80, out_channels=1, kernel_size=7, chann
 def build_model(dev):
     """Causal HiFi-GAN V1 on seeded weights: the recipe of tests/util.py::synth_for, weight norm removed."""
     g = HiFiGANGenerator(**dict(synth.HIFIGAN_V1, use_causal_conv=True))
+    g.load_state_dict(synth.synth_state_dict(g.state_dict(), seed=11, g_scale=1.25))
+    g.remove_weight_norm()
+    return g.to(dev).eval()
+
+
+def build_noncausal(dev):
+    """The standard (non-causal) HiFi-GAN V1 on the same seeded weights, weight norm removed."""
+    g = HiFiGANGenerator(**synth.HIFIGAN_V1)
     g.load_state_dict(synth.synth_state_dict(g.state_dict(), seed=11, g_scale=1.25))
     g.remove_weight_norm()
     return g.to(dev).eval()
@@ -137,11 +151,14 @@ def main():
     ap.add_argument("--model", choices=("default", "pwg"), default="default")
     ap.add_argument("--multiband", action="store_true")
     ap.add_argument("--precision", choices=("fp32", "bf16"), default="fp32")
+    ap.add_argument("--lookahead", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.lookahead and (args.model != "default" or args.multiband or args.precision != "fp32"):
+        ap.error("--lookahead is the fp32 non-causal HiFi-GAN stream (no --model, no --multiband, no --precision bf16)")
     if args.model == "pwg" and (args.multiband or args.precision != "fp32"):
         ap.error("--model pwg is the fp32 full-band Parallel WaveGAN stream (no --multiband, no --precision bf16)")
-    default_out = "stream_pwg_infer.json" if args.model == "pwg" else "stream_bf16_infer.json" if args.precision == "bf16" else (
+    default_out = "stream_lookahead_infer.json" if args.lookahead else "stream_pwg_infer.json" if args.model == "pwg" else "stream_bf16_infer.json" if args.precision == "bf16" else (
         "stream_mb_infer.json" if args.multiband else "stream_infer.json")
     args.out = args.out or os.path.join(ROOT, "profiles", default_out)
     dev = torch.device("cuda:0")
@@ -161,7 +178,9 @@ def main():
         print(json.dumps({"out": args.out, "points": [[p["model"], p["streams"], p["chunk_frames"], p["fp32_push_ms"],
                                                        p["bf16_push_ms"]] for p in rec["points"]]}))
         return
-    if args.model == "pwg":
+    if args.lookahead:
+        measure_lookahead(rec, "hifigan_v1", build_noncausal(dev), CHUNKS, gen, args, dev)
+    elif args.model == "pwg":
         measure_pwg(rec, "parallel_wavegan_v1_causal", build_pwg(dev), CHUNKS, gen, args, dev)
     elif args.multiband:
         measure(rec, "multi_band_melgan_v2_causal", build_multiband(dev), MB_CHUNKS, gen, args, dev)
@@ -280,6 +299,52 @@ def measure_pwg(rec, name, model, chunks, gen, args, dev):
                                                 "spread_ms", "speedup_stream_over_halo", "launches_per_push_stream",
                                                 "launches_per_forward_halo", "layer_launch_ms")}), file=sys.stderr,
                   flush=True)
+
+
+def measure_lookahead(rec, name, model, chunks, gen, args, dev):
+    """Steady-state ``LookaheadStream.push`` against the whole-utterance forward over ``left + n + right`` frames,
+    alternating."""
+    left, right = receptive_field_frames(model)
+    up = model.upsample_factor
+    probe = LookaheadStream(model, use_graph=False)
+    rec["models"][name] = {"workload": "seeded weights, weight norm removed", "halo_left_frames": left,
+                           "halo_right_frames": right, "latency_samples": probe.latency_samples,
+                           "latency_frames": probe.latency_frames, "stream_state_bytes_per_stream": probe.state_bytes}
+    for b in STREAMS:
+        for n in chunks:
+            feats = torch.randn(b, n, 80, generator=gen).to(dev)
+            ctx = torch.randn(b, 80, left + n + right, generator=gen).to(dev)
+            s = LookaheadStream(model, batch=b, use_graph=True)
+            halo = GraphedInference(model)
+            while s.frames_in < s.latency_frames + 4 * n:  # the eager start, then both graph directions; the halo graph
+                s.push(feats)
+                halo(ctx)
+            t_s, t_h = [], []
+            for _ in range(args.repeats):
+                t_s.append(event_ms(lambda: s.push(feats), args.reps))
+                t_h.append(event_ms(lambda: halo(ctx), args.reps))
+            eager = LookaheadStream(model, batch=b, use_graph=False)
+            while eager.frames_in < eager.latency_frames:  # past the partial windows
+                eager.push(feats)
+            n_s, fam_s = launches(lambda: eager.push(feats))
+            n_h, fam_h = launches(lambda: model(ctx))
+            med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+            spread = max(max(t_s) - min(t_s), max(t_h) - min(t_h))
+            p = {"model": name, "streams": b, "chunk_frames": n, "samples_per_push": b * n * up,
+                 "stream_push_ms": round(med(t_s), 4), "stream_runs_ms": [round(t, 4) for t in t_s],
+                 "halo_forward_ms": round(med(t_h), 4), "halo_runs_ms": [round(t, 4) for t in t_h],
+                 "halo_frames_computed": left + n + right,
+                 "arithmetic_ratio_halo_over_stream": round((left + n + right) / n, 2),
+                 "spread_ms": round(spread, 4), "speedup_stream_over_halo": round(med(t_h) / med(t_s), 3),
+                 "stream_not_slower_beyond_spread": med(t_s) <= med(t_h) + spread,
+                 "stream_faster_beyond_spread": med(t_s) + spread < med(t_h),
+                 "real_time_factor_22050Hz": round(n * up / 22050.0 / (med(t_s) / 1e3), 1),
+                 "launches_per_push_stream": n_s, "launches_per_forward_halo": n_h,
+                 "stream_kernels": fam_s, "halo_kernels": fam_h}
+            rec["points"].append(p)
+            print(json.dumps({k: p[k] for k in ("model", "streams", "chunk_frames", "stream_push_ms", "halo_forward_ms",
+                                                "spread_ms", "speedup_stream_over_halo", "launches_per_push_stream",
+                                                "launches_per_forward_halo")}), file=sys.stderr, flush=True)
 
 
 def measure_precision(rec, name, model, chunks, gen, args, dev):
