@@ -6,7 +6,7 @@
 // for finite v whose low parts are not subnormal.  The fused pre-activation is applied to the fp32 input in fp32, then the
 // activated input is split while it is staged; the effective fp32 weight (w * scale) is split once when the weight image
 // is packed.  Per operand pair the products lo.hi, hi.lo, mid.mid, mid.hi, hi.mid, hi.hi (weight part . input part) are
-// issued in this order -- small terms first; split_step of mfma_conv.h owns the order, for this kernel and for
+// issued in this order -- small terms first; split_product of mfma_conv.h owns it, for this kernel and for
 // resunit_split.hip -- into ONE fp32 accumulator set; each of the three dropped products
 // (mid.lo, lo.mid, lo.lo) is <= 2^-24 of the full product in the worst case (|mid| <= 2^-8 |v|, |lo| <= 2^-16 |v|) and
 // about 2^-28 of it on average.  A bf16 x bf16 product is exact in fp32, so what is left is

@@ -5,10 +5,16 @@
 //   coverage, tile rule   mfma_conv_geometry         128 / 64 / 32 rows x 128 / 128 / 256 columns from the GEMM rows
 //   weight image          image_chunks, image_m_pad, image_elems, image_decode, image_rows, mfma_conv_pack
 //                                                    [tap][ci / 8][m_pad][8] per part
-//   split arithmetic      split3, split3_store, split_step   the 3-way split of a value; N values split and stored, a
-//                                                    vector per plane; one reduction step of the six part products.
-//                                                    split_step OWNS the product order of conv1d_split.hip and
+//   split arithmetic      split3, split3_store, split_product   the 3-way split of a value; N values split and stored, a
+//                                                    vector per plane; one of the six part products of a row tile.
+//                                                    split_product OWNS the product order of conv1d_split.hip and
 //                                                    resunit_split.hip, which must agree to the bit
+//   reduction step        split_step                 resident form (conv1d_split.hip): all fragments of a step loaded,
+//                                                    then its MFMAs
+//                         split_step_streamed, SplitStepId, split_step_successor, split_step_rows, split_step_request
+//                                                    streamed form (resunit_split.hip): the weight fragments a row
+//                                                    tile ahead of their MFMAs; the numbering of the steps and the one
+//                                                    rule for the step that follows
 //   launch plan           mfma_conv_plan             half-size tiles for short inputs, grid, LDS, vector staging
 //   tile ladder           mfma_conv_launch           the five tiles x two MFMA shapes of a kernel family
 //   arguments             MfmaConvArgs, mfma_conv_fill_args, mfma_conv_check_forward
@@ -157,41 +163,155 @@ __device__ __forceinline__ void split3_store(const float (&v)[N], __bf16* dst, i
   *reinterpret_cast<vec_t*>(dst + 2 * plane) = vl;
 }
 
-// One reduction step (the lane's 8 channels of one tap) of a split-operand contraction, for a wave's TM x TN MFMA tiles:
-// loads the 3 x TM weight fragments and the 3 x TN plane fragments and issues the 6 x TM x TN MFMAs.  This is the ONE
-// statement of the product order -- (weight part, input part) = lo.hi, hi.lo, mid.mid, mid.hi, hi.mid, hi.hi, small terms
-// first -- that conv1d_split_mfma_kernel and resunit_split_kernel share, so that a unit equals two chained convolutions
-// bit for bit by construction.
-//   wp, part_stride  the lane's row of tile mi = 0 in the part-0 (hi) image at this tap / chunk / octet (image_rows),
-//                    bf16x8 elements per part image
-//   xs, col, off     plane 0 (hi), the lane's column of tile ni = 0 at this tap (a caller may have folded part of it
-//                    into xs), element offset of its 8 channels in an LDS row of ROW elements; plane: elements per plane
+// Product p (0 .. 5) of one row tile of a reduction step: the ONE statement of the product order -- (weight part, input
+// part) = lo.hi, hi.lo, mid.mid, mid.hi, hi.mid, hi.hi, small terms first -- that conv1d_split_mfma_kernel and
+// resunit_split_kernel share, so that a unit equals two chained convolutions bit for bit by construction.  Per
+// accumulator the products arrive in the order (chunk, tap, step, product) in both forms of the step below.
+//   wf, bfr   the weight fragments of the row tile and the plane fragments of the step, [0] hi, [1] mid, [2] lo
 // XFIRST: the plane fragment is the first MFMA operand: the same products summed in the same order, the tile transposed
 // (a lane gets 4 consecutive samples of a row instead of 4 consecutive rows of a column).
-template <int TILE, int TM, int TN, int ROW, bool XFIRST>
-__device__ __forceinline__ void split_step(const bf16x8* __restrict__ wp, long part_stride, const __bf16* xs, int col,
-                                           int off, int plane, typename Mfma<TILE>::acc_t (&acc)[TM][TN]) {
-  bf16x8 af[3][TM], bfr[3][TN];  // [0] hi, [1] mid, [2] lo
+constexpr int kSplitWeightPart[6] = {2, 0, 1, 1, 0, 0};
+constexpr int kSplitInputPart[6] = {0, 2, 1, 0, 1, 0};
+template <int TILE, int TN, bool XFIRST>
+__device__ __forceinline__ void split_product(int p, const bf16x8 (&wf)[3], const bf16x8 (&bfr)[3][TN],
+                                              typename Mfma<TILE>::acc_t (&acc)[TN]) {
 #pragma unroll
-  for (int p = 0; p < 3; ++p)
-#pragma unroll
-    for (int mi = 0; mi < TM; ++mi) af[p][mi] = wp[p * part_stride + mi * TILE];
+  for (int ni = 0; ni < TN; ++ni)
+    acc[ni] = XFIRST ? Mfma<TILE>::run(bfr[kSplitInputPart[p]][ni], wf[kSplitWeightPart[p]], acc[ni])
+                     : Mfma<TILE>::run(wf[kSplitWeightPart[p]], bfr[kSplitInputPart[p]][ni], acc[ni]);
+}
+
+// the 3 x TN plane fragments of a step.  xs, col, off: plane 0 (hi), the lane's column of tile ni = 0 at this tap (a
+// caller may have folded part of it into xs), element offset of its 8 channels in an LDS row of ROW elements; plane:
+// elements per plane
+template <int TILE, int TN, int ROW>
+__device__ __forceinline__ void split_plane_fragments(bf16x8 (&bfr)[3][TN], const __bf16* xs, int col, int off, int plane) {
 #pragma unroll
   for (int ni = 0; ni < TN; ++ni) {
     const __bf16* src = xs + (col + ni * TILE) * ROW + off;
 #pragma unroll
     for (int p = 0; p < 3; ++p) bfr[p][ni] = *reinterpret_cast<const bf16x8*>(src + p * plane);
   }
-  constexpr int PA[6] = {2, 0, 1, 1, 0, 0};
-  constexpr int PB[6] = {0, 2, 1, 0, 1, 0};
+}
+
+// One reduction step (the lane's 8 channels of one tap), RESIDENT form (conv1d_split_mfma_kernel): loads the 3 x TM
+// weight fragments and the 3 x TN plane fragments and issues the 6 x TM x TN MFMAs, product by product.
+//   wp, part_stride  the lane's row of tile mi = 0 in the part-0 (hi) image at this tap / chunk / octet (image_rows),
+//                    bf16x8 elements per part image
+template <int TILE, int TM, int TN, int ROW, bool XFIRST>
+__device__ __forceinline__ void split_step(const bf16x8* __restrict__ wp, long part_stride, const __bf16* xs, int col,
+                                           int off, int plane, typename Mfma<TILE>::acc_t (&acc)[TM][TN]) {
+  bf16x8 af[TM][3], bfr[3][TN];
+#pragma unroll
+  for (int p = 0; p < 3; ++p)
+#pragma unroll
+    for (int mi = 0; mi < TM; ++mi) af[mi][p] = wp[p * part_stride + mi * TILE];
+  split_plane_fragments<TILE, TN, ROW>(bfr, xs, col, off, plane);
 #pragma unroll
   for (int p = 0; p < 6; ++p)
 #pragma unroll
-    for (int mi = 0; mi < TM; ++mi)
+    for (int mi = 0; mi < TM; ++mi) split_product<TILE, TN, XFIRST>(p, af[mi], bfr, acc[mi]);
+}
+
+// ---- STREAMED form of the step (resunit_split_kernel): the plane fragments stay resident for a step and the weight
+// fragments run one ROW TILE ahead of their MFMAs, across tap, k-step and chunk boundaries.
+// The steps of a contraction are numbered (chunk, tap, k-step), k-step fastest: a step is the lane's 8 channels (octet
+// ks * (64 / TILE) + lane group) of one tap of one 32-channel chunk.  split_step_successor is the ONE rule for "which
+// step follows this one".  After the last step of the last chunk the successor is that step itself: a valid fragment of
+// the same image, so the last request needs no branch and reads no address past the image.
+struct SplitStepId {
+  int chunk, tap, ks;
+};
+__host__ __device__ __forceinline__ constexpr SplitStepId split_step_successor(SplitStepId s, int chunks, int taps,
+                                                                               int ksteps) {
+  if (s.ks + 1 < ksteps) return SplitStepId{s.chunk, s.tap, s.ks + 1};
+  if (s.tap + 1 < taps) return SplitStepId{s.chunk, s.tap + 1, 0};
+  if (s.chunk + 1 < chunks) return SplitStepId{s.chunk + 1, 0, 0};
+  return s;
+}
+constexpr bool split_step_is(SplitStepId s, int chunk, int tap, int ks) {
+  return s.chunk == chunk && s.tap == tap && s.ks == ks;
+}
+// k-step, then tap; the last step of an inner chunk -> step 0 of the next chunk; the last of the last -> clamped
+static_assert(split_step_is(split_step_successor({0, 0, 0}, 2, 3, 2), 0, 0, 1), "k-step advances first");
+static_assert(split_step_is(split_step_successor({0, 0, 1}, 2, 3, 2), 0, 1, 0), "then the tap");
+static_assert(split_step_is(split_step_successor({0, 2, 1}, 2, 3, 2), 1, 0, 0), "last step of an inner chunk");
+static_assert(split_step_is(split_step_successor({1, 2, 1}, 2, 3, 2), 1, 2, 1), "last step of the last chunk: clamped");
+static_assert(split_step_is(split_step_successor({0, 0, 0}, 2, 3, 1), 0, 1, 0), "KSTEPS = 1: every step is a tap");
+static_assert(split_step_is(split_step_successor({0, 2, 0}, 2, 3, 1), 1, 0, 0), "KSTEPS = 1: chunk crossing");
+static_assert(split_step_is(split_step_successor({1, 2, 0}, 2, 3, 1), 1, 2, 0), "KSTEPS = 1: clamped");
+static_assert(split_step_is(split_step_successor({0, 0, 0}, 1, 1, 1), 0, 0, 0), "one step in total: clamped at once");
+static_assert(split_step_is(split_step_successor({0, 0, 0}, 3, 1, 1), 1, 0, 0), "k = 1: a chunk crossing every step");
+
+// Where the weight fragments of step s start, for a lane of group h: the bf16x8 index of row 0 in a part image (the lane
+// adds its row), and the element offset of the step's 8 channels inside a staged chunk.  A fragment is addressed as
+// (part image, 32-bit index): a part image is below 4 GiB (split_image_addressable, checked by the host), and one index
+// register serves all three parts.
+constexpr bool split_image_addressable(long elems_per_part) { return elems_per_part * (long)sizeof(__bf16) < (1L << 32); }
+template <int TILE>
+__device__ __forceinline__ unsigned split_step_rows(int cin_chunks, int m_pad, SplitStepId s, int h) {
+  return (unsigned)(((s.tap * cin_chunks + s.chunk) * (KC / 8) + s.ks * (64 / TILE) + h) * m_pad);
+}
+template <int TILE>
+__device__ __forceinline__ int split_step_off(SplitStepId s, int h) {
+  return (s.ks * (64 / TILE) + h) * 8;
+}
+
+// Request weight fragment `part` (0 hi, 1 mid, 2 lo) at index `row` of its part image (w: part 0), or all three.  A
+// contraction calls split_step_request once, for row tile 0 of its first step, as early as it can (before the window is
+// staged); split_step_streamed requests every later fragment.
+__device__ __forceinline__ bf16x8 split_part_request(const bf16x8* __restrict__ w, long part_stride, unsigned row, int part) {
+  return *reinterpret_cast<const bf16x8*>(reinterpret_cast<const char*>(w + part * part_stride) +
+                                          (size_t)(row * (unsigned)sizeof(bf16x8)));
+}
+__device__ __forceinline__ void split_step_request(bf16x8 (&wf)[3], const bf16x8* __restrict__ w, long part_stride,
+                                                   unsigned row) {
 #pragma unroll
-      for (int ni = 0; ni < TN; ++ni)
-        acc[mi][ni] = XFIRST ? Mfma<TILE>::run(bfr[PB[p]][ni], af[PA[p]][mi], acc[mi][ni])
-                             : Mfma<TILE>::run(af[PA[p]][mi], bfr[PB[p]][ni], acc[mi][ni]);
+  for (int p = 0; p < 3; ++p) wf[p] = split_part_request(w, part_stride, row, p);
+}
+
+// One reduction step, streamed: loads the 3 x TN plane fragments; before the 6 x TN MFMAs of row tile mi are issued, row
+// tile mi + 1 is requested, and after the last row tile, row tile 0 of the NEXT step.  So a weight fragment is requested
+// 5 x TN (lo) or 6 x TN MFMAs ahead of its first use, and the step holds 3 x TN + 5 fragments.
+//   wf               in: the fragments of row tile 0 of this step (split_step_request, or the step before);
+//                    out: those of row tile 0 of the next step
+//   w, part_stride   the part-0 (hi) image; bf16x8 elements per part image
+//   row, row_next    the lane's row of tile mi = 0 at this step and at its successor (its row in the image +
+//                    split_step_rows of the step / of split_step_successor)
+//   xs, col, off, plane   as split_plane_fragments
+template <int TILE, int TM, int TN, int ROW, bool XFIRST>
+__device__ __forceinline__ void split_step_streamed(bf16x8 (&wf)[3], const bf16x8* __restrict__ w, long part_stride,
+                                                    unsigned row, unsigned row_next, const __bf16* xs, int col, int off,
+                                                    int plane, typename Mfma<TILE>::acc_t (&acc)[TM][TN]) {
+  bf16x8 bfr[3][TN];
+  split_plane_fragments<TILE, TN, ROW>(bfr, xs, col, off, plane);
+  // only the first product reads the weight's lo part: its successor is requested behind that product, into the
+  // registers it frees (20 instead of 24 fragment registers for the two row tiles in flight)
+  static_assert(kSplitWeightPart[0] == 2 && kSplitWeightPart[1] != 2 && kSplitWeightPart[2] != 2 &&
+                    kSplitWeightPart[3] != 2 && kSplitWeightPart[4] != 2 && kSplitWeightPart[5] != 2,
+                "lo is read by the first product only");
+#pragma unroll
+  for (int mi = 0; mi < TM; ++mi) {
+    const unsigned rn = mi + 1 < TM ? row + (mi + 1) * TILE : row_next;
+    bf16x8 nx[3];
+    nx[0] = split_part_request(w, part_stride, rn, 0);
+    nx[1] = split_part_request(w, part_stride, rn, 1);
+    // the requests go out in front of this row tile's MFMAs: the scheduler otherwise sinks them to their first use
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int p = 0; p < 6; ++p) {
+      split_product<TILE, TN, XFIRST>(p, wf, bfr, acc[mi]);
+      if (p == 0) {
+        __builtin_amdgcn_sched_barrier(0);
+        nx[2] = split_part_request(w, part_stride, rn, 2);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+#pragma unroll
+    for (int p = 0; p < 3; ++p) wf[p] = nx[p];
+    // a row tile at a time: the scheduler otherwise gathers the requests of all row tiles in front of the first MFMA
+    __builtin_amdgcn_sched_barrier(0);
+  }
 }
 
 // One thread per element of ONE part image.  PARTS == 1 stores the rounded effective weight w * scale, PARTS == 3 its

@@ -10,7 +10,7 @@
 // Numerical definition (include/pwg_kernels.h, "split-operand residual unit"): lrelu(x) is formed in fp32 and split with
 // split3 while the window is staged; the effective weights are split once by pwg_conv1d_split_pack_weight (the same
 // image); per operand pair the products lo.hi, hi.lo, mid.mid, mid.hi, hi.mid, hi.hi (weight part . input part) go, in
-// this order, into one fp32 accumulator set (split_step of mfma_conv.h owns the order, for this kernel and for
+// this order, into one fp32 accumulator set (split_product of mfma_conv.h owns the order, for this kernel and for
 // conv1d_split.hip); h = lrelu(acc + b1) is formed in fp32, is zero outside [0, T) and is split with split3; the
 // residual is the raw fp32 x and the epilogue is acc + bias + x + add2, then / out_div.
 // The accumulation order of an output element is the split kernel's: 32-channel chunk, tap, reduction step, product.  A
@@ -111,26 +111,32 @@ __device__ __forceinline__ void ru_stage_window(const RuSplitArgs& a, const floa
   }
 }
 
-// acc += W (*) B over (chunk, tap, reduction step): the loop order of conv1d_split_mfma_kernel around the split_step the
-// two kernels share (mfma_conv.h).  wl: the part-0 image at this lane's weight row; bl: plane 0 at this lane's column of
+// acc += W (*) B over (chunk, tap, reduction step): the step sequence of conv1d_split_mfma_kernel around the streamed form
+// of the step (split_step_streamed, mfma_conv.h: the product order the two kernels share); the weight fragments run a
+// row tile ahead across taps and chunks.  w: the part-0 image; wrow: this lane's weight row; wf: row tile 0 of the first
+// step, requested by the caller (ru_request) ahead of whatever it has to wait for; bl: plane 0 at this lane's column of
 // tile 0, tap 0; tap_step: columns per tap.  XFIRST: the B fragment is the first MFMA operand (transposed tile).
+template <int C, int TILE>
+__device__ __forceinline__ void ru_request(bf16x8 (&wf)[3], const bf16x8* __restrict__ w, long part_stride, unsigned wrow,
+                                           int h) {
+  using Cfg = RuSplitCfg<C>;
+  split_step_request(wf, w, part_stride, wrow + split_step_rows<TILE>(Cfg::CHUNKS, Cfg::M_PAD, SplitStepId{0, 0, 0}, h));
+}
 template <int C, int TILE, bool XFIRST>
-__device__ __forceinline__ void ru_contract(const bf16x8* __restrict__ wl, long part_stride, const __bf16* bl, int plane,
-                                            int tap_step, int taps, int h,
+__device__ __forceinline__ void ru_contract(bf16x8 (&wf)[3], const bf16x8* __restrict__ w, long part_stride, unsigned wrow,
+                                            const __bf16* bl, int plane, int tap_step, int taps, int h,
                                             typename Mfma<TILE>::acc_t (&acc)[32 / TILE][64 / TILE]) {
   using Cfg = RuSplitCfg<C>;
   constexpr int HL = 64 / TILE, KSTEPS = KC / (8 * HL), TM = 32 / TILE, TN = 64 / TILE;
+  SplitStepId step{0, 0, 0};
 #pragma unroll 1
-  for (int chunk = 0; chunk < Cfg::CHUNKS; ++chunk) {
-#pragma unroll 1
-    for (int tap = 0; tap < taps; ++tap) {
-#pragma unroll
-      for (int ks = 0; ks < KSTEPS; ++ks) {
-        const int oct = ks * HL + h;
-        const bf16x8* __restrict__ wp = image_rows(wl, Cfg::CHUNKS, Cfg::M_PAD, tap, chunk, oct);
-        split_step<TILE, TM, TN, Cfg::ROW, XFIRST>(wp, part_stride, bl, tap * tap_step, chunk * KC + oct * 8, plane, acc);
-      }
-    }
+  for (int s = 0; s < Cfg::CHUNKS * taps * KSTEPS; ++s) {
+    const SplitStepId next = split_step_successor(step, Cfg::CHUNKS, taps, KSTEPS);
+    split_step_streamed<TILE, TM, TN, Cfg::ROW, XFIRST>(
+        wf, w, part_stride, wrow + split_step_rows<TILE>(Cfg::CHUNKS, Cfg::M_PAD, step, h),
+        wrow + split_step_rows<TILE>(Cfg::CHUNKS, Cfg::M_PAD, next, h), bl, step.tap * tap_step,
+        step.chunk * KC + split_step_off<TILE>(step, h), plane, acc);
+    step = next;
   }
 }
 
@@ -154,6 +160,11 @@ __global__ __launch_bounds__(256, 2) void resunit_split_kernel(RuSplitArgs a) {
   const bool pair = a.w2 != nullptr;
   const float* __restrict__ xb = a.x + (size_t)b * C * T;
 
+  // the weight fragments run a row tile ahead of their MFMAs: the first ones of w1 are requested in front of the staging
+  const unsigned wrow = wave_m * 32 + r;  // this lane's weight row of tile mi = 0
+  bf16x8 wf[3];
+  ru_request<C, TILE>(wf, a.w1, a.part_stride, wrow, h);
+
   if (base >= 0 && base + a.rows <= T)
     ru_stage_window<C, false>(a, xb, base, xs, tid);
   else
@@ -168,11 +179,11 @@ __global__ __launch_bounds__(256, 2) void resunit_split_kernel(RuSplitArgs a) {
       for (int i = 0; i < NREG; ++i) acc[mi][ni][i] = 0.f;
   __syncthreads();
 
-  const int wrow = wave_m * 32 + r;  // this lane's weight row of tile mi = 0
   if (pair) {
     // ---- phase 1: conv_{k,d} over lrelu(x); h column m reads staged column m + sh + tap * d
-    ru_contract<C, TILE, false>(a.w1 + wrow, a.part_stride, xs + (wave_n * 64 + r + a.sh) * ROW, a.plane, a.d1, a.k, h,
-                                acc);
+    ru_contract<C, TILE, false>(wf, a.w1, a.part_stride, wrow, xs + (wave_n * 64 + r + a.sh) * ROW, a.plane, a.d1, a.k,
+                                h, acc);
+    ru_request<C, TILE>(wf, a.w2, a.part_stride, wrow, h);  // lands behind the forming of h and both barriers
     __syncthreads();  // every wave has read its x columns: the h planes take their place
     // h = lrelu(acc + b1), zero outside [0, T) (conv2's zero padding), split: a lane owns channels c .. c + 3 of a column
     const bool has_b1 = a.b1 != nullptr;
@@ -215,10 +226,11 @@ __global__ __launch_bounds__(256, 2) void resunit_split_kernel(RuSplitArgs a) {
     }
     __syncthreads();
     // ---- phase 2: conv_{k,1} over h; output slot n reads h column n + tap
-    ru_contract<C, TILE, true>(a.w2 + wrow, a.part_stride, xs + (wave_n * 64 + r) * ROW, a.plane, 1, a.k, h, acc);
-  } else {
-    ru_contract<C, TILE, true>(a.w1 + wrow, a.part_stride, xs + (wave_n * 64 + r + a.sh) * ROW, a.plane, a.d1, a.k, h,
+    ru_contract<C, TILE, true>(wf, a.w2, a.part_stride, wrow, xs + (wave_n * 64 + r) * ROW, a.plane, 1, a.k, h,
                                acc);
+  } else {
+    ru_contract<C, TILE, true>(wf, a.w1, a.part_stride, wrow, xs + (wave_n * 64 + r + a.sh) * ROW, a.plane, a.d1, a.k,
+                               h, acc);
   }
 
   // ---- epilogue (fp32, the order of split_epilogue: acc + bias + x + add2, then / out_div).  Transposed tile: a lane
@@ -337,6 +349,8 @@ static int ru_split_forward(const pwg_resunit_desc* d, const float* x, const voi
   a.bn_out = g.bn_out, a.hla = g.hla, a.sh = g.sh, a.p2 = g.p2, a.rows = g.rows;
   a.plane = g.rows * (C + 8);
   a.part_stride = image_elems(d->kernel, image_chunks(C), image_m_pad(C)) / 8;  // of the image RuSplitCfg<C> describes
+  // (a window that fits LDS has a few hundred taps: the 32-bit fragment index of split_step_request always holds)
+  PWG_REQUIRE(split_image_addressable(a.part_stride * 8), PWG_ERR_UNSUPPORTED, "resunit_split_forward: weight image too large");
   a.slope1 = d->slope1, a.slope2 = d->slope2, a.out_div = d->out_div;
   void (*kern)(RuSplitArgs) = C == 32 ? (mfma_shape == 32 ? resunit_split_kernel<32, 32> : resunit_split_kernel<32, 16>)
                                       : (mfma_shape == 32 ? resunit_split_kernel<64, 32> : resunit_split_kernel<64, 16>);
