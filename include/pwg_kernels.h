@@ -331,6 +331,29 @@ int pwg_conv1d_stream_delayed_forward(const pwg_conv1d_desc* d, const float* x, 
                                       const float* add2_hist_in, float* add2_hist_out, int32_t delay2, int32_t valid_lo,
                                       int32_t valid_hi, float* y, void* stream);
 
+/* ---- the delayed stream launch with bf16 operands (opt-in; csrc/conv1d_stream_bf16.hip) ----
+ * pwg_conv1d_stream_delayed_forward under the numerical definition of pwg_conv1d_stream_bf16_forward: the activated
+ * window is rounded to bf16, w_packed_bf16 is the bf16 image of pwg_conv1d_bf16_pack_weight (16-B aligned), products
+ * accumulate in fp32 on v_mfma_f32_16x16x32_bf16; bias, the delayed addends, out_mul / out_div, post_act, the stored
+ * result, the history and the delay lines are fp32.  Every other parameter, the delay lines, the valid window and the
+ * pointer rules (delay_i > 0 needs add_i and add_i_hist_out; every hist_in distinct from its hist_out) are those of
+ * pwg_conv1d_stream_delayed_forward; a column outside [valid_lo, valid_hi) is stored as 0.0f, and bf16(act(0)) = 0, so
+ * the next layer sees the whole-utterance zero padding.  hist_out and both add_i_hist_out are bit-identical to what
+ * pwg_conv1d_stream_delayed_forward writes for the same inputs: a stream's state does not depend on its precision.
+ * With delay_i == 0 and the window [0, t_out) y equals pwg_conv1d_stream_bf16_forward's bit for bit; with delays it
+ * equals that entry given the addends delayed on the host.  Sum order and tile rule are that entry's: any partition of
+ * a stream gives the same bits.
+ * pwg_conv1d_stream_bf16_delayed_supported answers exactly as pwg_conv1d_stream_delayed_supported for every descriptor
+ * and pair of delays, with the same pwg_last_error reason (pure host logic, no device needed).
+ * These two symbols are purely additive -- no existing signature or behaviour changes -- so pwg_abi_version() stays 15. */
+int pwg_conv1d_stream_bf16_delayed_supported(const pwg_conv1d_desc* d, int32_t delay1, int32_t delay2);
+int pwg_conv1d_stream_bf16_delayed_forward(const pwg_conv1d_desc* d, const float* x, const float* hist_in,
+                                           float* hist_out, const void* w_packed_bf16, const float* bias,
+                                           const float* add1, const float* add1_hist_in, float* add1_hist_out,
+                                           int32_t delay1, const float* add2, const float* add2_hist_in,
+                                           float* add2_hist_out, int32_t delay2, int32_t valid_lo, int32_t valid_hi,
+                                           float* y, void* stream);
+
 /* Diagnostics (host only, no launch, no device needed): the plan pwg_conv1d_forward derives for a descriptor.
  * has_addends: 1 if add1 / add2 will be passed.  out[8]:
  *   out[0] kernel family: 0 = MFMA implicit-GEMM kernel, 1 = grouped 16x16x4 kernel, 2 = single-input-channel

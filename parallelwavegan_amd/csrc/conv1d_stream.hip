@@ -93,6 +93,21 @@ int stream_geometry(const pwg_conv1d_desc* d, StreamGeom* g) {
   return PWG_OK;
 }
 
+// What the delayed form adds to stream_geometry(): zero padding only (the shifted time axis starts from the
+// whole-utterance zero padding) and delay lines no longer than a history
+int delayed_geometry(const pwg_conv1d_desc* d, int32_t delay1, int32_t delay2, StreamGeom* g) {
+  const int rc = stream_geometry(d, g);
+  if (rc != PWG_OK) return rc;
+  PWG_REQUIRE(d->pad_mode == PWG_PAD_ZERO, PWG_ERR_UNSUPPORTED,
+              "conv1d_stream_delayed: pad_mode = %d (the delayed form starts a stream from zeros only)", d->pad_mode);
+  PWG_REQUIRE(delay1 >= 0 && delay2 >= 0, PWG_ERR_BAD_SHAPE, "conv1d_stream_delayed: negative delay (%d, %d)", delay1,
+              delay2);
+  PWG_REQUIRE(delay1 <= kStreamMaxHist && delay2 <= kStreamMaxHist, PWG_ERR_UNSUPPORTED,
+              "conv1d_stream_delayed: addend delay of %d columns (at most %d)", delay1 > delay2 ? delay1 : delay2,
+              kStreamMaxHist);
+  return PWG_OK;
+}
+
 namespace {
 
 constexpr int SC = 64;  // input channels staged per LDS block (four 16-channel groups of the image)
@@ -269,21 +284,6 @@ struct DelayedKernel {
   static constexpr auto fn = conv1d_stream_kernel<TM, TN, TRANSPOSED, true>;
 };
 
-// What the delayed form adds to stream_geometry(): zero padding only (the shifted time axis starts from the
-// whole-utterance zero padding) and delay lines no longer than a history
-int delayed_geometry(const pwg_conv1d_desc* d, int32_t delay1, int32_t delay2, StreamGeom* g) {
-  const int rc = stream_geometry(d, g);
-  if (rc != PWG_OK) return rc;
-  PWG_REQUIRE(d->pad_mode == PWG_PAD_ZERO, PWG_ERR_UNSUPPORTED,
-              "conv1d_stream_delayed: pad_mode = %d (the delayed form starts a stream from zeros only)", d->pad_mode);
-  PWG_REQUIRE(delay1 >= 0 && delay2 >= 0, PWG_ERR_BAD_SHAPE, "conv1d_stream_delayed: negative delay (%d, %d)", delay1,
-              delay2);
-  PWG_REQUIRE(delay1 <= kStreamMaxHist && delay2 <= kStreamMaxHist, PWG_ERR_UNSUPPORTED,
-              "conv1d_stream_delayed: addend delay of %d columns (at most %d)", delay1 > delay2 ? delay1 : delay2,
-              kStreamMaxHist);
-  return PWG_OK;
-}
-
 }  // namespace
 }  // namespace pwg
 
@@ -351,33 +351,18 @@ extern "C" int pwg_conv1d_stream_delayed_forward(const pwg_conv1d_desc* d, const
   if (rc != PWG_OK) return rc;
   PWG_REQUIRE((reinterpret_cast<uintptr_t>(w_packed) & 3u) == 0, PWG_ERR_BAD_SHAPE,
               "conv1d_stream_delayed: unaligned weight image");
-  const float* adds[2] = {add1, add2};
-  const float* hin[2] = {add1_hist_in, add2_hist_in};
-  float* hout[2] = {add1_hist_out, add2_hist_out};
-  const int delays[2] = {delay1, delay2};
-  for (int i = 0; i < 2; ++i) {
-    if (delays[i] == 0) continue;
-    PWG_REQUIRE(adds[i] && hout[i], PWG_ERR_NULL,
-                "conv1d_stream_delayed: delay%d = %d needs add%d and add%d_hist_out", i + 1, delays[i], i + 1, i + 1);
-    PWG_REQUIRE(hin[i] != hout[i], PWG_ERR_BAD_SHAPE,
-                "conv1d_stream_delayed: add%d_hist_in and add%d_hist_out must be distinct buffers", i + 1, i + 1);
-  }
+  StreamDelayedArgs a;
+  rc = stream_delay_lines("conv1d_stream_delayed", add1, add1_hist_in, add1_hist_out, delay1, add2, add2_hist_in,
+                          add2_hist_out, delay2, valid_lo, valid_hi, &a.dl);
+  if (rc != PWG_OK) return rc;
   const int n = d->t_in;
   const StreamTile tile = stream_tile(n, g.m, d->batch);
 
-  StreamDelayedArgs a;
   stream_fill_args(&a, d, g, tile, x, hist_in, hist_out, bias, add1, add2, y);
   a.w = w_packed;
   a.cin_pad = g.cin_pad;
   a.m_pad = g.m_pad;
   a.xs = xs_stride(16 * tile.tn + g.hist);
-  for (int i = 0; i < 2; ++i) {
-    a.dl.hist_in[i] = delays[i] ? hin[i] : nullptr;
-    a.dl.hist_out[i] = delays[i] ? hout[i] : nullptr;
-    a.dl.delay[i] = delays[i];
-  }
-  a.dl.valid_lo = valid_lo;
-  a.dl.valid_hi = valid_hi;
 
   const double out_elems = (double)d->batch * d->c_out * d->t_out;
   const double flops = 2.0 * (double)d->batch * g.m * n * g.taps * d->c_in;

@@ -33,6 +33,14 @@
 // Tiles: as the fp32 stream kernel -- 16 rows x 16 / 32 / 64 columns for chunks of up to 16 / 32 / more columns, 32 x 64
 // when that still gives every CU two workgroups; the four waves deal the REDUCTION, and the A fragments of the next four
 // items (one 16-B load per lane and item) are in flight while the current four are contracted.  DESIGN.md s11.2.
+//
+// Delayed form (pwg_conv1d_stream_bf16_delayed_forward): the delayed form of conv1d_stream.hip under
+// the numerical definition above, for a layer of a NON-causal network streamed with a fixed look-ahead.  The addends
+// are read through delay lines kept like the history (raw fp32, bit-identical to what the fp32 delayed launch writes)
+// and output columns outside the valid window are stored as 0.0f (StreamDelay, stream_common.h): bf16(act(0)) = 0, so
+// the next layer sees the whole-utterance zero padding.  Staging, item dealing, A-fragment prefetch, contraction and
+// sum order are those of the plain form: only the history writer and the epilogue differ, and the plain instantiations
+// are the code they were.
 #include "mfma_conv.h"
 #include "stream_common.h"
 
@@ -50,6 +58,10 @@ struct StreamBf16Args : StreamCommonArgs {
   int q4, r4;  // 4 / taps and 4 % taps: a wave's next item is 4 items on
 };
 
+struct StreamBf16DelayedArgs : StreamBf16Args {
+  StreamDelay dl;
+};
+
 // (chunk of the staged block, tap) of an item; wave-uniform
 struct Item {
   int cl, tap;
@@ -57,8 +69,9 @@ struct Item {
 
 // One workgroup (4 waves) owns MT = 16 * TM rows x NT = 16 * TN columns; wave w contracts the items with item % 4 == w
 // and the four partial tiles are summed through LDS in wave order, ((p0 + p1) + p2) + p3 -- the same in every configuration.
-template <int TM, int TN, bool TRANSPOSED>
-__global__ __launch_bounds__(256) void conv1d_stream_bf16_kernel(StreamBf16Args a) {
+template <int TM, int TN, bool TRANSPOSED, bool DELAYED = false>
+__global__ __launch_bounds__(256) void conv1d_stream_bf16_kernel(
+    std::conditional_t<DELAYED, StreamBf16DelayedArgs, StreamBf16Args> a) {
   constexpr int MT = 16 * TM, NT = 16 * TN;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __bf16* xs = reinterpret_cast<__bf16*>(smem);  // [W][ROW]; afterwards the partial tiles [4][MT][NT + 1] fp32
@@ -74,6 +87,19 @@ __global__ __launch_bounds__(256) void conv1d_stream_bf16_kernel(StreamBf16Args 
 
   stream_write_history<1>(xb, hb, a.hist_out + (size_t)b * a.c_in * H, a.c_in, n, H, a.pad_mode == PWG_PAD_REPLICATE,
                        blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
+  if constexpr (DELAYED) {
+    // the addends' delay lines: the history rule on (c_out, t_out) rows, zero start
+    const float* adds[2] = {a.ep.add1, a.ep.add2};
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int D = a.dl.delay[i];
+      if (D == 0) continue;
+      const size_t rows = (size_t)b * a.ep.c_out;
+      stream_write_history<1>(adds[i] + rows * a.ep.t_out, a.dl.hist_in[i] ? a.dl.hist_in[i] + rows * D : nullptr,
+                              a.dl.hist_out[i] + rows * D, a.ep.c_out, a.ep.t_out, D, false,
+                              blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
+    }
+  }
 
   f32x4 acc[TM][TN];
 #pragma unroll
@@ -207,13 +233,40 @@ __global__ __launch_bounds__(256) void conv1d_stream_bf16_kernel(StreamBf16Args 
     }
   }
 
-  stream_reduce_epilogue<MT, NT, TRANSPOSED, StreamRows::ChannelMajor>(reinterpret_cast<float*>(smem), acc, a.ep, m0, q0, b);
+  if constexpr (DELAYED)
+    stream_reduce_epilogue<MT, NT, TRANSPOSED, StreamRows::ChannelMajor>(reinterpret_cast<float*>(smem), acc, a.ep, m0, q0, b,
+                                                                         a.dl);
+  else
+    stream_reduce_epilogue<MT, NT, TRANSPOSED, StreamRows::ChannelMajor>(reinterpret_cast<float*>(smem), acc, a.ep, m0, q0, b);
 }
 
 template <int TM, int TN, bool TRANSPOSED>
 struct Kernel {
   static constexpr auto fn = conv1d_stream_bf16_kernel<TM, TN, TRANSPOSED>;
 };
+
+template <int TM, int TN, bool TRANSPOSED>
+struct DelayedKernel {
+  static constexpr auto fn = conv1d_stream_bf16_kernel<TM, TN, TRANSPOSED, true>;
+};
+
+// The image of the layer (csrc/mfma_conv.h) and the fields of the argument struct that come from it.  The image does
+// not depend on padding, which its owner's geometry admits only as zero.
+int bf16_image(const char* name, const pwg_conv1d_desc* d, MfmaConvGeom* image) {
+  pwg_conv1d_desc dz = *d;
+  dz.pad_mode = PWG_PAD_ZERO;
+  PWG_REQUIRE(mfma_conv_geometry("conv1d_bf16", 1, true, &dz, image) == PWG_OK, PWG_ERR_UNSUPPORTED,
+              "%s: the layer has no bf16 weight image", name);
+  return PWG_OK;
+}
+
+void fill_image_args(StreamBf16Args* a, const void* w_packed_bf16, const MfmaConvGeom& image, const StreamGeom& g) {
+  a->w = static_cast<const bf16x8*>(w_packed_bf16);
+  a->cin_chunks = image.cin_chunks;
+  a->m_pad = image.m_pad;  // of the bf16 image, not g.m_pad
+  a->q4 = 4 / g.taps;
+  a->r4 = 4 % g.taps;
+}
 
 }  // namespace
 }  // namespace pwg
@@ -229,14 +282,10 @@ extern "C" int pwg_conv1d_stream_bf16_forward(const pwg_conv1d_desc* d, const fl
   StreamGeom g;
   if (stream_geometry(d, &g) != PWG_OK) return PWG_ERR_UNSUPPORTED;  // (pwg_last_error holds the reason)
   hipStream_t stream = (hipStream_t)stream_;
-  // the image and its geometry come from their owner (csrc/mfma_conv.h); the image does not depend on padding, which
-  // that geometry admits only as zero
-  pwg_conv1d_desc dz = *d;
-  dz.pad_mode = PWG_PAD_ZERO;
   MfmaConvGeom image;
-  PWG_REQUIRE(mfma_conv_geometry("conv1d_bf16", 1, true, &dz, &image) == PWG_OK, PWG_ERR_UNSUPPORTED,
-              "conv1d_stream_bf16: the layer has no bf16 weight image");
-  const int rc = stream_check_pointers("conv1d_stream_bf16", d, g, x, w_packed_bf16, y, hist_in, hist_out);
+  int rc = bf16_image("conv1d_stream_bf16", d, &image);
+  if (rc != PWG_OK) return rc;
+  rc = stream_check_pointers("conv1d_stream_bf16", d, g, x, w_packed_bf16, y, hist_in, hist_out);
   if (rc != PWG_OK) return rc;
   PWG_REQUIRE((reinterpret_cast<uintptr_t>(w_packed_bf16) & 15u) == 0, PWG_ERR_BAD_SHAPE,
               "conv1d_stream_bf16: the weight image must be 16-B aligned");
@@ -245,11 +294,7 @@ extern "C" int pwg_conv1d_stream_bf16_forward(const pwg_conv1d_desc* d, const fl
 
   StreamBf16Args a;
   stream_fill_args(&a, d, g, tile, x, hist_in, hist_out, bias, add1, add2, y);
-  a.w = static_cast<const bf16x8*>(w_packed_bf16);
-  a.cin_chunks = image.cin_chunks;
-  a.m_pad = image.m_pad;  // of the bf16 image, not g.m_pad
-  a.q4 = 4 / g.taps;
-  a.r4 = 4 % g.taps;
+  fill_image_args(&a, w_packed_bf16, image, g);
 
   const double out_elems = (double)d->batch * d->c_out * d->t_out;
   const double flops = 2.0 * (double)d->batch * g.m * n * g.taps * d->c_in;
@@ -260,5 +305,50 @@ extern "C" int pwg_conv1d_stream_bf16_forward(const pwg_conv1d_desc* d, const fl
   stream_launch<Kernel>(tile, d->transposed != 0, a, g.m, d->batch,
                         stream_lds_bytes((size_t)(16 * tile.tn + g.hist) * ROW * sizeof(__bf16), tile), stream);
   PWG_CHECK_LAUNCH("conv1d_stream_bf16");
+  return PWG_OK;
+}
+
+// Coverage is that of the fp32 delayed form by construction: both go through delayed_geometry().
+extern "C" int pwg_conv1d_stream_bf16_delayed_supported(const pwg_conv1d_desc* d, int32_t delay1, int32_t delay2) {
+  return pwg_conv1d_stream_delayed_supported(d, delay1, delay2);
+}
+
+extern "C" int pwg_conv1d_stream_bf16_delayed_forward(const pwg_conv1d_desc* d, const float* x, const float* hist_in,
+                                                      float* hist_out, const void* w_packed_bf16, const float* bias,
+                                                      const float* add1, const float* add1_hist_in, float* add1_hist_out,
+                                                      int32_t delay1, const float* add2, const float* add2_hist_in,
+                                                      float* add2_hist_out, int32_t delay2, int32_t valid_lo,
+                                                      int32_t valid_hi, float* y, void* stream_) {
+  StreamGeom g;
+  int rc = delayed_geometry(d, delay1, delay2, &g);
+  if (rc != PWG_OK) return rc;
+  hipStream_t stream = (hipStream_t)stream_;
+  MfmaConvGeom image;
+  rc = bf16_image("conv1d_stream_bf16_delayed", d, &image);
+  if (rc != PWG_OK) return rc;
+  rc = stream_check_pointers("conv1d_stream_bf16_delayed", d, g, x, w_packed_bf16, y, hist_in, hist_out);
+  if (rc != PWG_OK) return rc;
+  PWG_REQUIRE((reinterpret_cast<uintptr_t>(w_packed_bf16) & 15u) == 0, PWG_ERR_BAD_SHAPE,
+              "conv1d_stream_bf16_delayed: the weight image must be 16-B aligned");
+  StreamBf16DelayedArgs a;
+  rc = stream_delay_lines("conv1d_stream_bf16_delayed", add1, add1_hist_in, add1_hist_out, delay1, add2, add2_hist_in,
+                          add2_hist_out, delay2, valid_lo, valid_hi, &a.dl);
+  if (rc != PWG_OK) return rc;
+  const int n = d->t_in;
+  const StreamTile tile = stream_tile(n, g.m, d->batch);
+
+  stream_fill_args(&a, d, g, tile, x, hist_in, hist_out, bias, add1, add2, y);
+  fill_image_args(&a, w_packed_bf16, image, g);
+
+  const double out_elems = (double)d->batch * d->c_out * d->t_out;
+  const double flops = 2.0 * (double)d->batch * g.m * n * g.taps * d->c_in;
+  const double bytes = 4.0 * ((double)d->batch * d->c_in * (n + 2.0 * g.hist) +
+                              out_elems * (1 + (add1 ? 1 : 0) + (add2 ? 1 : 0)) +
+                              2.0 * d->batch * d->c_out * (delay1 + delay2)) + 2.0 * (double)image_elems(image);
+  maybe_poison_lds(stream);
+  ProfScope prof(stream, "conv1d_stream_bf16_delayed_kernel", flops, bytes);
+  stream_launch<DelayedKernel>(tile, d->transposed != 0, a, g.m, d->batch,
+                               stream_lds_bytes((size_t)(16 * tile.tn + g.hist) * ROW * sizeof(__bf16), tile), stream);
+  PWG_CHECK_LAUNCH("conv1d_stream_bf16_delayed");
   return PWG_OK;
 }

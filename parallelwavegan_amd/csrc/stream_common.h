@@ -6,6 +6,7 @@
 //   delayed form          StreamDelay            addends read through a delay line, zeros stored outside a valid window
 //   tile rule             stream_tile            column tile from n; 32-row blocks only at 2 x 256 or more workgroups
 //   coverage              stream_geometry        defined in conv1d_stream.hip; both precisions admit the same layers
+//                         delayed_geometry       ... and the same delays (what the delayed form adds; defined there too)
 // Internal to csrc/; the staging loops and contractions of the kernels differ on purpose and stay with them.
 #pragma once
 #include "common.h"
@@ -185,6 +186,11 @@ struct StreamGeom {
 // Shared between two translation units but not exported from the library.
 __attribute__((visibility("hidden"))) int stream_geometry(const pwg_conv1d_desc* d, StreamGeom* g);
 
+// What the delayed form adds to it, in either precision (conv1d_stream.hip): zero padding only, delays >= 0 and no
+// longer than a history.
+__attribute__((visibility("hidden"))) int delayed_geometry(const pwg_conv1d_desc* d, int32_t delay1, int32_t delay2,
+                                                           StreamGeom* g);
+
 // The fields both kernels' argument structs share
 struct StreamCommonArgs {
   const float* x;
@@ -224,6 +230,31 @@ static inline int stream_check_pointers(const char* name, const pwg_conv1d_desc*
               "%s: hist_in and hist_out must be distinct buffers (other workgroups read the history)", name);
   PWG_REQUIRE(hist_in || d->pad_mode != PWG_PAD_REFLECT || d->t_in > g.hist, PWG_ERR_BAD_SHAPE,
               "%s: a reflect-padded stream starts with at least %d columns (got %d)", name, g.hist + 1, d->t_in);
+  return PWG_OK;
+}
+
+// The delay lines of a delayed launch: a delayed addend needs its tensor and a hist_out distinct from its hist_in;
+// the pointers of an addend that is not delayed are ignored
+static inline int stream_delay_lines(const char* name, const float* add1, const float* add1_hist_in, float* add1_hist_out,
+                                     int delay1, const float* add2, const float* add2_hist_in, float* add2_hist_out,
+                                     int delay2, int valid_lo, int valid_hi, StreamDelay* dl) {
+  const float* adds[2] = {add1, add2};
+  const float* hin[2] = {add1_hist_in, add2_hist_in};
+  float* hout[2] = {add1_hist_out, add2_hist_out};
+  const int delays[2] = {delay1, delay2};
+  for (int i = 0; i < 2; ++i) {
+    if (delays[i]) {
+      PWG_REQUIRE(adds[i] && hout[i], PWG_ERR_NULL, "%s: delay%d = %d needs add%d and add%d_hist_out", name, i + 1,
+                  delays[i], i + 1, i + 1);
+      PWG_REQUIRE(hin[i] != hout[i], PWG_ERR_BAD_SHAPE, "%s: add%d_hist_in and add%d_hist_out must be distinct buffers",
+                  name, i + 1, i + 1);
+    }
+    dl->hist_in[i] = delays[i] ? hin[i] : nullptr;
+    dl->hist_out[i] = delays[i] ? hout[i] : nullptr;
+    dl->delay[i] = delays[i];
+  }
+  dl->valid_lo = valid_lo;
+  dl->valid_hi = valid_hi;
   return PWG_OK;
 }
 

@@ -199,9 +199,14 @@ class LookaheadWalk:
     """One push through the launches of a delay plan: hands every launch its state tensors and its valid window.
     ``state_in`` (None: start of stream, every state reads as zeros) / ``state_out``: one ping-pong half each, of
     :func:`lookahead_state_shapes`.  ``frames_before``: frames the stream took before this push (None: steady state,
-    every window is full); ``total_frames``: the utterance's length once it is known (the flush), else None."""
+    every window is full); ``total_frames``: the utterance's length once it is known (the flush), else None.
+    ``precision="bf16"``: every launch runs with bf16 operands on the layer's bf16 image (csrc/conv1d_stream_bf16.hip,
+    the delayed form); the state tensors are the same raw fp32 in either precision."""
 
-    def __init__(self, plan, state_in, state_out, frames_before=None, total_frames=None):
+    def __init__(self, plan, state_in, state_out, frames_before=None, total_frames=None, precision="fp32"):
+        if precision not in ("fp32", "bf16"):
+            raise ValueError(f"LookaheadWalk: precision must be 'fp32' or 'bf16', got {precision!r}")
+        self.precision = precision
         self._plan = iter(plan)
         self._in = None if state_in is None else iter(state_in)
         self._out = iter(state_out)
@@ -218,9 +223,13 @@ class LookaheadWalk:
         launch = next(self._plan)
         if launch.conv is not cv:
             raise RuntimeError(f"look-ahead walk out of step: the plan expects {launch.conv}, the model ran {cv}")
-        if cv.precision != "fp32":
+        # the precision of the walk, by the rule of _stream_forward: a bf16 walk does not consult the module's own
+        # `precision` attribute (whole-utterance mode); an fp32 walk refuses a module in bf16 mode
+        bf16 = self.precision == "bf16"
+        if not bf16 and cv.precision != "fp32":
             raise RuntimeError(f"{cv.__class__.__name__} is in {cv.precision} inference precision: the look-ahead stream is "
-                               "fp32 (utils.set_inference_precision(model, 'fp32'))")
+                               "fp32 (utils.set_inference_precision(model, 'fp32'), or pass precision='bf16' to stream "
+                               "with bf16 operands)")
         hist = self._take(lookahead_history_columns(cv))
         line1, line2 = self._take(launch.delay1), self._take(launch.delay2)
         desc = lookahead_desc(cv, x.shape[0], x.shape[-1], **fused)
@@ -231,12 +240,19 @@ class LookaheadWalk:
             lo = min(max(launch.delay - before, 0), t_out)
             if self.total_frames is not None:
                 hi = min(max(launch.delay + self.total_frames * launch.rate - before, 0), t_out)
-        if not ops.conv1d_stream_delayed_supported(desc, launch.delay1, launch.delay2):
+        if bf16:
+            kernel, supported, forward = "delayed bf16 streaming kernel", ops.conv1d_stream_bf16_delayed_supported, \
+                ops.conv1d_stream_delayed_forward_bf16
+        else:
+            kernel, supported, forward = "delayed streaming kernel", ops.conv1d_stream_delayed_supported, \
+                ops.conv1d_stream_delayed_forward
+        if not supported(desc, launch.delay1, launch.delay2):
             from .. import _lib
 
-            raise RuntimeError("the delayed streaming kernel does not cover this layer: "
+            raise RuntimeError(f"the {kernel} does not cover this layer: "
                                + _lib.lib().pwg_last_error().decode(errors="replace"))
         bias = None if cv.bias is None else cv.bias.detach()
         with torch.no_grad():
-            return ops.conv1d_stream_delayed_forward(desc, x.contiguous(), hist[0], hist[1], cv.packed_weight(), bias,
-                                                     add1, line1, launch.delay1, add2, line2, launch.delay2, (lo, hi))
+            image = cv.packed_weight_bf16() if bf16 else cv.packed_weight()
+            return forward(desc, x.contiguous(), hist[0], hist[1], image, bias, add1, line1, launch.delay1, add2, line2,
+                           launch.delay2, (lo, hi))

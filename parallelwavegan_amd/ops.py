@@ -347,17 +347,26 @@ def conv1d_stream_delayed_forward(desc, x, hist_in, hist_out, w_packed, bias=Non
     delay_i), ``hist_in`` None for zeros; ``hist_out`` receives the last ``delay_i`` columns of ``concat(hist_in,
     add_i)`` -- and output columns outside ``valid = (lo, hi)`` (chunk-relative; None: all of them are valid) are stored
     as exact zeros.  One launch."""
+    _require_device(w_packed)
+    return _conv1d_stream_delayed(_lib.lib().pwg_conv1d_stream_delayed_forward, "conv1d_stream_delayed_forward", desc, x, hist_in, hist_out, w_packed, bias, add1,
+                                  add1_hist, delay1, add2, add2_hist, delay2, valid, out)
+
+
+def _conv1d_stream_delayed(entry, name, desc, x, hist_in, hist_out, image, bias, add1, add1_hist, delay1, add2, add2_hist,
+                           delay2, valid, out):
+    """What the two delayed conv stream wrappers share: the checks of every tensor but the weight image, and the call of
+    the library's ``entry``."""
     flat = (add1_hist[0], add1_hist[1], add2_hist[0], add2_hist[1])
-    _require_device(x, hist_in, hist_out, w_packed, bias, add1, add2, out, *flat)
+    _require_device(x, hist_in, hist_out, bias, add1, add2, out, *flat)
     out = _conv1d_stream_out(desc, x, hist_in, hist_out, add1, add2, out)
     for delay, (h_in, h_out) in ((delay1, add1_hist), (delay2, add2_hist)):
         for t in (h_in, h_out):
             assert t is None or t.numel() == desc.batch * desc.c_out * delay, (tuple(t.shape), delay)
     lo, hi = (0, desc.t_out) if valid is None else valid
-    _lib.check(_lib.lib().pwg_conv1d_stream_delayed_forward(
-        ctypes.byref(desc), _ptr(x), _ptr(hist_in), _ptr(hist_out), _ptr(w_packed), _ptr(bias),
+    _lib.check(entry(
+        ctypes.byref(desc), _ptr(x), _ptr(hist_in), _ptr(hist_out), _ptr(image), _ptr(bias),
         _ptr(add1), _ptr(flat[0]), _ptr(flat[1]), int(delay1), _ptr(add2), _ptr(flat[2]), _ptr(flat[3]), int(delay2),
-        int(lo), int(hi), _ptr(out), _stream()), "conv1d_stream_delayed_forward")
+        int(lo), int(hi), _ptr(out), _stream()), name)
     return out
 
 
@@ -367,20 +376,45 @@ def conv1d_stream_bf16_supported(desc):
     return bool(_lib.lib().pwg_conv1d_stream_bf16_supported(ctypes.byref(desc)))
 
 
+def _check_stream_image_bf16(name, desc, w_packed_bf16):
+    """The image checks the two bf16 conv stream wrappers share."""
+    if not w_packed_bf16.is_cuda or w_packed_bf16.dtype != torch.uint8:
+        raise RuntimeError(f"{name}: w_packed_bf16 must be the device image of pack_weight_bf16")
+    assert w_packed_bf16.numel() == _lib.lib().pwg_conv1d_bf16_packed_weight_bytes(ctypes.byref(_zero_padded(desc))), \
+        f"{name}: w_packed_bf16 is not this layer's bf16 image"
+
+
 def conv1d_stream_forward_bf16(desc, x, hist_in, hist_out, w_packed_bf16, bias=None, add1=None, add2=None, out=None):
     """:func:`conv1d_stream_forward` with bf16 operands: the activated window and the weights (``w_packed_bf16``, the
     image of :func:`pack_weight_bf16`) are bf16, accumulation / epilogue / tensors / history fp32; ``hist_out`` is
     bit-identical to the fp32 launch's."""
     _require_device(x, hist_in, hist_out, bias, add1, add2, out)
-    if not w_packed_bf16.is_cuda or w_packed_bf16.dtype != torch.uint8:
-        raise RuntimeError("conv1d_stream_forward_bf16: w_packed_bf16 must be the device image of pack_weight_bf16")
+    _check_stream_image_bf16("conv1d_stream_forward_bf16", desc, w_packed_bf16)
     out = _conv1d_stream_out(desc, x, hist_in, hist_out, add1, add2, out)
-    assert w_packed_bf16.numel() == _lib.lib().pwg_conv1d_bf16_packed_weight_bytes(ctypes.byref(_zero_padded(desc))), \
-        "conv1d_stream_forward_bf16: w_packed_bf16 is not this layer's bf16 image"
     _lib.check(_lib.lib().pwg_conv1d_stream_bf16_forward(ctypes.byref(desc), _ptr(x), _ptr(hist_in), _ptr(hist_out),
                                                          _ptr(w_packed_bf16), _ptr(bias), _ptr(add1), _ptr(add2),
                                                          _ptr(out), _stream()), "conv1d_stream_bf16_forward")
     return out
+
+
+def conv1d_stream_bf16_delayed_supported(desc, delay1=0, delay2=0):
+    """Does the delayed form of the bf16-operand streaming kernel cover this descriptor and these addend delays?  It
+    answers exactly as :func:`conv1d_stream_delayed_supported`, with the same ``pwg_last_error`` reason.  Host logic
+    only."""
+    return bool(_lib.lib().pwg_conv1d_stream_bf16_delayed_supported(ctypes.byref(desc), int(delay1), int(delay2)))
+
+
+def conv1d_stream_delayed_forward_bf16(desc, x, hist_in, hist_out, w_packed_bf16, bias=None, add1=None,
+                                       add1_hist=(None, None), delay1=0, add2=None, add2_hist=(None, None), delay2=0,
+                                       valid=None, out=None):
+    """:func:`conv1d_stream_delayed_forward` with bf16 operands (``w_packed_bf16``: the image of
+    :func:`pack_weight_bf16`), as :func:`conv1d_stream_forward_bf16` is to :func:`conv1d_stream_forward`: accumulation,
+    epilogue, addends, tensors, history and delay lines are fp32, and the state written is bit-identical to the fp32
+    delayed launch's.  One launch."""
+    _check_stream_image_bf16("conv1d_stream_delayed_forward_bf16", desc, w_packed_bf16)
+    return _conv1d_stream_delayed(_lib.lib().pwg_conv1d_stream_bf16_delayed_forward, "conv1d_stream_bf16_delayed_forward",
+                                  desc, x, hist_in, hist_out, w_packed_bf16, bias, add1, add1_hist, delay1, add2,
+                                  add2_hist, delay2, valid, out)
 
 
 def make_resunit_desc(batch, channels, t, kernel, dilation, has_conv2=True, slope1=0.1, slope2=0.1, out_div=1.0):

@@ -32,8 +32,8 @@ import torch
 
 from .. import _lib
 from ..graphs import GraphedInference
-from ..ops import (_ptr, _require_device, _stream, conv1d_stream_bf16_supported, conv1d_stream_delayed_supported,
-                   conv1d_stream_supported)
+from ..ops import (_ptr, _require_device, _stream, conv1d_stream_bf16_delayed_supported, conv1d_stream_bf16_supported,
+                   conv1d_stream_delayed_supported, conv1d_stream_supported)
 
 
 def normalize_transpose(c, mean=None, scale=None):
@@ -602,7 +602,7 @@ class LookaheadStream(_Stream):
     After any push the samples emitted total ``max(0, frames_in * up - latency_samples)``, so the first pushes of an
     utterance return short or empty tensors; ``flush()`` returns the tail, after which the emissions total ``frames *
     up`` samples.  Any partition of the same frames gives bit-identical audio, equal to the whole-utterance ``forward``
-    up to fp32 summation order.  fp32 only.
+    up to fp32 summation order.
 
     How: every layer runs in its causal form on a shifted time axis (csrc/conv1d_stream.hip, the
     delayed form).  A tensor of the network is a stream with a delay: a symmetric convolution adds its padding, a
@@ -615,15 +615,25 @@ class LookaheadStream(_Stream):
     (``latency_frames`` frames went before it) replays the two captured graphs of its chunk size, as in
     :class:`CausalStream`; the pushes at the start of an utterance and ``flush()`` run eagerly.  ``close()`` does not
     flush: an unflushed tail is dropped.
+
+    ``precision="bf16"``: every convolution of every push, the eager pushes at the start of an utterance and ``flush()``
+    included, runs with bf16 operands (csrc/conv1d_stream_bf16.hip, the delayed form; DESIGN.md s11.5: the activated
+    window and the weights are rounded to bf16; sums, epilogues, addends, tensors, history and delay lines stay fp32).
+    As in :class:`CausalStream` the precision belongs to the stream, is fixed for its life (``.precision``) and neither
+    reads nor writes the modules' own ``precision`` attributes; plan, latency, state and partition invariance are those
+    of the fp32 stream.  ``None`` and ``"fp32"`` are the fp32 stream, which refuses a model that
+    ``set_inference_precision`` put in bf16 mode.
     """
 
     warmup_frames = 1
 
-    def __init__(self, model, batch=1, use_graph=True, normalize_before=False):
+    def __init__(self, model, batch=1, use_graph=True, normalize_before=False, precision=None):
         from ..layers.causal_conv import lookahead_desc, lookahead_state_shapes
         from ..layers.conv import each_conv
         from ..models import HiFiGANGenerator
 
+        if precision not in (None, "fp32", "bf16"):
+            raise ValueError(f"LookaheadStream: precision must be None, 'fp32' or 'bf16', got {precision!r}")
         if not isinstance(model, HiFiGANGenerator):
             raise ValueError(f"LookaheadStream: {model.__class__.__name__} is not supported (only the non-causal "
                              "HiFiGANGenerator; a reflect-padded MelGAN mirrors columns that have not arrived)")
@@ -634,16 +644,18 @@ class LookaheadStream(_Stream):
         if out_channels != 1:
             raise ValueError(f"LookaheadStream: the generator emits {out_channels} channels; the stream returns one "
                              "waveform per stream (out_channels == 1)")
-        if any(cv.precision != "fp32" for cv in each_conv(model)):
-            raise ValueError("LookaheadStream: the model is in bf16 inference precision; the look-ahead stream is fp32 "
-                             "(utils.set_inference_precision(model, 'fp32'))")
+        if precision != "bf16" and any(cv.precision != "fp32" for cv in each_conv(model)):
+            raise ValueError("LookaheadStream: the model is in bf16 inference precision; the fp32 look-ahead stream does "
+                             "not read that mode (utils.set_inference_precision(model, 'fp32'), or stream with bf16 "
+                             "operands: LookaheadStream(model, precision='bf16'))")
         batch = self._checked_batch(batch)
         plan = model.lookahead_plan()  # ValueError: decreasing block delays, a layer without a causal form
+        supported = conv1d_stream_bf16_delayed_supported if precision == "bf16" else conv1d_stream_delayed_supported
         for launch in plan:
-            if not conv1d_stream_delayed_supported(lookahead_desc(launch.conv, batch, 8), launch.delay1, launch.delay2):
+            if not supported(lookahead_desc(launch.conv, batch, 8), launch.delay1, launch.delay2):
                 raise ValueError(f"LookaheadStream: {launch.conv} cannot be streamed: "
                                  + _lib.lib().pwg_last_error().decode(errors="replace"))
-        self.precision = "fp32"
+        self.precision = precision or "fp32"  # of the stream, fixed for its life
         self.up = model.upsample_factor  # samples per frame
         self._plan = plan
         self._in_channels = model.input_conv.in_channels
@@ -666,7 +678,7 @@ class LookaheadStream(_Stream):
         ping-pong half each; ``frames_before`` None: steady state.  -> (batch, n * up), not yet trimmed."""
         from ..layers.causal_conv import LookaheadWalk
 
-        walk = LookaheadWalk(self._plan, state_in, state_out, frames_before, total_frames)
+        walk = LookaheadWalk(self._plan, state_in, state_out, frames_before, total_frames, self.precision)
         return self.model.lookahead_forward(c, walk).reshape(self.batch, -1)
 
     def _capture(self, feats):

@@ -32,6 +32,13 @@ state pushes of 4 / 8 / 32 frames at 1 and 16 streams, into profiles/stream_look
 graph of the whole-utterance forward over ``left + n + right`` frames, both from ``receptive_field_frames``: a non-causal
 chunk needs its future context too, and cannot be emitted before those ``right`` frames arrived either.
 
+``--lookahead --precision bf16``: the bf16-operand look-ahead stream (``LookaheadStream(model, precision="bf16")``, the
+delayed form of csrc/conv1d_stream_bf16.hip) at the same grid, four measurements alternating in one
+process: the fp32 push, the bf16 push, one graph of the halo forward over ``left + n + right`` frames in fp32, and the
+same halo forward of a second instance of the model put in bf16 inference precision -- the fair comparator of the bf16
+push, since the whole-utterance forward runs those shapes on the bf16 matrix pipe.  Into
+profiles/stream_lookahead_bf16_infer.json.
+
 usage: python tools/bench_stream.py [--model pwg] [--multiband] [--precision bf16] [--lookahead] [--reps 200]
                                     [--repeats 3] [--out profiles/stream_infer.json]
 """
@@ -48,7 +55,7 @@ from parallelwavegan_amd import ops  # noqa: E402
 from parallelwavegan_amd.graphs import GraphedInference  # noqa: E402
 from parallelwavegan_amd.layers import PQMF  # noqa: E402
 from parallelwavegan_amd.models import HiFiGANGenerator, MelGANGenerator, ParallelWaveGANGenerator  # noqa: E402
-from parallelwavegan_amd.utils import CausalStream, LookaheadStream, PWGStream  # noqa: E402
+from parallelwavegan_amd.utils import CausalStream, LookaheadStream, PWGStream, set_inference_precision  # noqa: E402
 from parallelwavegan_amd.utils.streaming import receptive_field_frames  # noqa: E402
 from tests.golden import synth  # noqa: E402
 
@@ -154,17 +161,29 @@ def main():
     ap.add_argument("--lookahead", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    if args.lookahead and (args.model != "default" or args.multiband or args.precision != "fp32"):
-        ap.error("--lookahead is the fp32 non-causal HiFi-GAN stream (no --model, no --multiband, no --precision bf16)")
+    if args.lookahead and (args.model != "default" or args.multiband):
+        ap.error("--lookahead is the non-causal HiFi-GAN stream (no --model, no --multiband)")
     if args.model == "pwg" and (args.multiband or args.precision != "fp32"):
         ap.error("--model pwg is the fp32 full-band Parallel WaveGAN stream (no --multiband, no --precision bf16)")
-    default_out = "stream_lookahead_infer.json" if args.lookahead else "stream_pwg_infer.json" if args.model == "pwg" else "stream_bf16_infer.json" if args.precision == "bf16" else (
+    default_out = "stream_lookahead_bf16_infer.json" if args.lookahead and args.precision == "bf16" else "stream_lookahead_infer.json" if args.lookahead else "stream_pwg_infer.json" if args.model == "pwg" else "stream_bf16_infer.json" if args.precision == "bf16" else (
         "stream_mb_infer.json" if args.multiband else "stream_infer.json")
     args.out = args.out or os.path.join(ROOT, "profiles", default_out)
     dev = torch.device("cuda:0")
     rec = {"tool": "tools/bench_stream.py", "device": torch.cuda.get_device_name(0), "reps": args.reps,
            "repeats": args.repeats, "models": {}, "points": []}
     gen = torch.Generator(device="cpu").manual_seed(100)
+    if args.lookahead and args.precision == "bf16":
+        model16 = build_noncausal(dev)  # the halo forward's own instance: the streamed one stays in fp32 mode
+        set_inference_precision(model16, "bf16")
+        measure_lookahead_precision(rec, "hifigan_v1", build_noncausal(dev), model16, CHUNKS, gen, args, dev)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(rec, f, indent=1)
+            f.write("\n")
+        print(json.dumps({"out": args.out, "points": [[p["model"], p["streams"], p["chunk_frames"], p["fp32_push_ms"],
+                                                       p["bf16_push_ms"], p["halo_fp32_ms"], p["halo_bf16_ms"]]
+                                                      for p in rec["points"]]}))
+        return
     if args.precision == "bf16":
         families = [("hifigan_v1_causal", build_model, CHUNKS), ("melgan_recipe_causal", build_melgan, MELGAN_CHUNKS)]
         if args.multiband:
@@ -345,6 +364,67 @@ def measure_lookahead(rec, name, model, chunks, gen, args, dev):
             print(json.dumps({k: p[k] for k in ("model", "streams", "chunk_frames", "stream_push_ms", "halo_forward_ms",
                                                 "spread_ms", "speedup_stream_over_halo", "launches_per_push_stream",
                                                 "launches_per_forward_halo")}), file=sys.stderr, flush=True)
+
+
+def measure_lookahead_precision(rec, name, model, model16, chunks, gen, args, dev):
+    """Steady-state fp32 and bf16 ``LookaheadStream.push`` of ``model`` and the halo forward over ``left + n + right``
+    frames of ``model`` (fp32) and of ``model16`` (the same weights in bf16 inference precision), alternating."""
+    left, right = receptive_field_frames(model)
+    up = model.upsample_factor
+    probe = LookaheadStream(model, use_graph=False, precision="bf16")
+    rec["models"][name] = {"workload": "seeded weights, weight norm removed", "halo_left_frames": left,
+                           "halo_right_frames": right, "latency_samples": probe.latency_samples,
+                           "latency_frames": probe.latency_frames, "stream_state_bytes_per_stream": probe.state_bytes}
+    kernels = {"fp32": "conv1d_stream_delayed_kernel", "bf16": "conv1d_stream_bf16_delayed_kernel"}
+    for b in STREAMS:
+        for n in chunks:
+            feats = torch.randn(b, n, 80, generator=gen).to(dev)
+            ctx = torch.randn(b, 80, left + n + right, generator=gen).to(dev)
+            streams = {prec: LookaheadStream(model, batch=b, use_graph=True, precision=prec) for prec in kernels}
+            halos = {"fp32": GraphedInference(model), "bf16": GraphedInference(model16)}
+            while streams["fp32"].frames_in < probe.latency_frames + 4 * n:  # the eager start, both graph directions
+                for prec in kernels:
+                    streams[prec].push(feats)
+                    halos[prec](ctx)
+            calls = {"fp32_push": lambda: streams["fp32"].push(feats), "bf16_push": lambda: streams["bf16"].push(feats),
+                     "halo_fp32": lambda: halos["fp32"](ctx), "halo_bf16": lambda: halos["bf16"](ctx)}
+            runs = {k: [] for k in calls}
+            for _ in range(args.repeats):
+                for k, fn in calls.items():
+                    runs[k].append(event_ms(fn, args.reps))
+            kernel_ms, n_launch = {}, {}
+            for prec, kernel in kernels.items():
+                eager = LookaheadStream(model, batch=b, use_graph=False, precision=prec)
+                while eager.frames_in < eager.latency_frames:  # past the partial windows
+                    eager.push(feats)
+                eager.push(feats)
+                with ops.profile() as prof:
+                    for _ in range(10):
+                        eager.push(feats)
+                kernel_ms[prec] = round(prof.results[kernel]["ms"] / 10, 4)
+                n_launch[prec] = prof.results[kernel]["launches"] // 10
+            _, fam_h16 = launches(lambda: model16(ctx))
+            med = {k: sorted(v)[len(v) // 2] for k, v in runs.items()}
+            spread = max(max(v) - min(v) for v in runs.values())
+            p = {"model": name, "streams": b, "chunk_frames": n, "samples_per_push": b * n * up,
+                 "halo_frames_computed": left + n + right, "spread_ms": round(spread, 4)}
+            for k in calls:
+                p[k + "_ms"] = round(med[k], 4)
+                p[k + "_runs_ms"] = [round(t, 4) for t in runs[k]]
+            p.update({"speedup_bf16_push_over_fp32_push": round(med["fp32_push"] / med["bf16_push"], 3),
+                      "speedup_bf16_push_over_halo_fp32": round(med["halo_fp32"] / med["bf16_push"], 3),
+                      "speedup_bf16_push_over_halo_bf16": round(med["halo_bf16"] / med["bf16_push"], 3),
+                      "speedup_fp32_push_over_halo_fp32": round(med["halo_fp32"] / med["fp32_push"], 3),
+                      "bf16_push_faster_than_halo_bf16_beyond_spread": med["bf16_push"] + spread < med["halo_bf16"],
+                      "bf16_push_slower_than_halo_bf16_beyond_spread": med["bf16_push"] > med["halo_bf16"] + spread,
+                      "real_time_factor_22050Hz": round(n * up / 22050.0 / (med["bf16_push"] / 1e3), 1),
+                      "conv_kernel_ms_per_eager_push": kernel_ms, "conv_launches_per_push": n_launch,
+                      "halo_bf16_kernels": fam_h16})
+            rec["points"].append(p)
+            print(json.dumps({k: p[k] for k in ("model", "streams", "chunk_frames", "fp32_push_ms", "bf16_push_ms",
+                                                "halo_fp32_ms", "halo_bf16_ms", "spread_ms",
+                                                "speedup_bf16_push_over_fp32_push", "speedup_bf16_push_over_halo_bf16",
+                                                "conv_kernel_ms_per_eager_push")}), file=sys.stderr, flush=True)
 
 
 def measure_precision(rec, name, model, chunks, gen, args, dev):
