@@ -533,6 +533,37 @@ size_t pwg_wavenet_stream_hist_floats(const pwg_wavenet_desc* d);
 int pwg_wavenet_stream_forward(const pwg_wavenet_desc* d, const float* x, const float* c, const float* skips,
                                const float* hist_in, float* hist_out, const float* packed, const float* b_dil,
                                const float* b_skip, const float* b_out, float* x_out, float* skips_out, void* stream);
+/* ---- the delayed form: the NON-causal layer in a stream with a fixed look-ahead (fp32; csrc/wavenet_stream.hip) ----
+ * d->causal = 0 (the layer's own descriptor).  The non-causal layer reads x at t - d, t, t + d; on a time axis shifted
+ * by d these are the causal taps n - 2d, n - d, n of X = concat(hist_in, x), so the launch is the causal one -- same
+ * kernel body, same image, same contraction -- whose output is d columns later than its input, with four differences:
+ *   residual      the MIDDLE tap X[n - d] (the causal layer adds X[n]);
+ *   conditioning  output column j reads C[j - c_delay], C = concat(c_line (batch, 80, c_cols), c (batch, 80, n)) indexed
+ *                 from the chunk's first column (j - c_delay < 0: c_line[c_cols + j - c_delay]); c_line == NULL reads
+ *                 as zeros (start of stream); 0 <= c_delay <= c_cols.  The line is the caller's (pwg_delay_line_forward
+ *                 keeps it): one line serves every layer of a generator, each at its own c_delay;
+ *   skip sum      output column j adds concat(skip_line_in (batch, 64, d), skips (batch, 64, n))[j] -- the running sum is
+ *                 d columns older than this layer's output; skip_line_in == NULL: zeros.  The same launch writes
+ *                 skip_line_out (batch, 64, d) = the last d columns of that concatenation, also when n < d.
+ *                 skips == NULL (first layer): no addend, both line pointers ignored;
+ *   valid window  x_out and skips_out columns outside [valid_lo, valid_hi) (chunk-relative) are STORED as 0.0f: the
+ *                 zero padding the next layer sees.
+ * hist_in / hist_out and skip_line_in / skip_line_out must be distinct buffers; x_out must not alias x and skips_out
+ * must not alias skips (tiles read their neighbours' columns).
+ * Geometry: that of pwg_wavenet_stream_supported with causal == 0; a causal descriptor and a negative c_delay are
+ * refused, as is whatever takes a byte offset inside one item past 32 bits (pwg_last_error names the reason).
+ * pwg_wavenet_stream_delayed_supported is pure host logic; pwg_wavenet_stream_delayed_hist_floats = batch * 64 *
+ * (kernel-1) * dilation (0 = unsupported).  The sum order of an output element is the causal form's and depends on the
+ * layer alone (not on n, the batch, c_delay, its alignment, or which staging path a window took): any partition of a
+ * stream gives bit-identical results.
+ * These three symbols are purely additive -- no existing signature or behaviour changes -- so pwg_abi_version() stays 15. */
+int pwg_wavenet_stream_delayed_supported(const pwg_wavenet_desc* d, int32_t c_delay);
+size_t pwg_wavenet_stream_delayed_hist_floats(const pwg_wavenet_desc* d);
+int pwg_wavenet_stream_delayed_forward(const pwg_wavenet_desc* d, const float* x, const float* c, const float* c_line,
+                                       int32_t c_cols, int32_t c_delay, const float* skips, const float* skip_line_in,
+                                       float* skip_line_out, const float* hist_in, float* hist_out, const float* packed,
+                                       const float* b_dil, const float* b_skip, const float* b_out, int32_t valid_lo,
+                                       int32_t valid_hi, float* x_out, float* skips_out, void* stream);
 /* ---- bf16-operand inference form of the same layer (opt-in; csrc/wavenet_bf16.hip) ----
  * The definition of the bf16-operand convolution (pwg_conv1d_bf16_*, above) applied to each of the layer's four
  * convolutions, in ONE launch:
@@ -669,6 +700,21 @@ int pwg_stretch_conv_forward(const float* x, const float* w, float* y, int64_t r
 int pwg_stretch_conv_stream(const float* x, const float* hist_in, float* hist_out, const float* w, float* y,
                             int64_t rows, int32_t n, int32_t scale, int32_t freq_kernel, int32_t act, float slope,
                             void* stream);
+/* The NON-causal stage (pad_left = scale) in a stream with a fixed look-ahead: it is the causal stage above on a time
+ * axis shifted by `scale` columns, same weights.  pwg_stretch_conv_stream plus a valid window: output columns outside
+ * [valid_lo, valid_hi) (chunk-relative, of n*scale) are STORED as 0.0f -- the stage has no bias and act(0) = 0, yet the
+ * `scale` columns around the utterance are not zero by themselves.  With the window [0, n*scale) y and hist_out are
+ * pwg_stretch_conv_stream's bit for bit.
+ * pwg_delay_line_forward: X = concat(line_in (rows, columns), x (rows, n)), line_in == NULL: zeros; line_out (rows,
+ * columns) = the last `columns` columns of X, also when n < columns; delayed_out (rows, n), if not NULL, = the first n
+ * columns of X (x, `columns` columns late).  line_in and line_out must be distinct buffers; delayed_out must not alias
+ * x.  It only copies: exact.  (The noise line and the conditioning line of the Parallel WaveGAN look-ahead stream.)
+ * These two symbols are purely additive -- no existing signature or behaviour changes -- so pwg_abi_version() stays 15. */
+int pwg_stretch_conv_stream_delayed(const float* x, const float* hist_in, float* hist_out, const float* w, float* y,
+                                    int64_t rows, int32_t n, int32_t scale, int32_t freq_kernel, int32_t act, float slope,
+                                    int32_t valid_lo, int32_t valid_hi, void* stream);
+int pwg_delay_line_forward(const float* x, const float* line_in, float* line_out, float* delayed_out, int64_t rows,
+                           int32_t n, int32_t columns, void* stream);
 size_t pwg_stretch_conv_backward_workspace_floats(int32_t kernel, int32_t freq_kernel);
 int pwg_stretch_conv_backward(const float* dy, const float* x, const float* w, float* dx, float* dw,
                               int64_t rows, int32_t t_in, int32_t scale, int32_t kernel, int32_t pad_left,

@@ -1,7 +1,7 @@
 // elementwise.hip -- HBM-bound helper kernels around the convolutions: activation backward,
 // weight/spectral-norm reparametrisation (forward pieces are in conv1d.hip), pooling, explicit
 // padding, STFT framing / magnitude / log.  All are single-pass, coalesced along time.
-#include "common.h"
+#include "stream_common.h"  // (common.h; the history rule for the delay line)
 
 namespace pwg {
 
@@ -489,16 +489,23 @@ __global__ __launch_bounds__(256) void stretch_conv_fwd4_kernel(const float* __r
 // X = concat(hist_in (rows, 2), x (rows, n)) -- exactly two raw input columns of the past (zeros at start of stream, the
 // whole-utterance kernel's zero padding).  Threads past the outputs write hist_out = the last 2 columns of X in the same
 // launch.  One fmaf chain per output, j ascending: the sum order does not depend on n or on the chunk's position.
+// WINDOW (the look-ahead stream of the non-causal stage, which is this stage on a time axis shifted by s; DESIGN.md
+// s11.6): output columns outside [valid_lo, valid_hi) are stored as 0.0f, the others are formed as without a window.
+template <bool WINDOW>
 __global__ __launch_bounds__(256) void stretch_conv_stream_kernel(const float* __restrict__ x, const float* __restrict__ hist_in,
                                                                   float* __restrict__ hist_out, const float* __restrict__ w,
                                                                   float* __restrict__ y, long rows, int n, int s, int act,
-                                                                  float slope) {
+                                                                  float slope, int valid_lo, int valid_hi) {
   const int t_out = n * s;
   const long total = rows * t_out;
   GRID_STRIDE(i, total + 2 * rows) {
     if (i < total) {
       const long r = i / t_out;
       const int t = (int)(i - r * t_out);
+      if (WINDOW && (t < valid_lo || t >= valid_hi)) {
+        y[i] = 0.f;
+        continue;
+      }
       const float* xr = x + r * n;
       float acc = 0.f;
       for (int j = 0; j <= 2 * s; ++j) {
@@ -512,6 +519,21 @@ __global__ __launch_bounds__(256) void stretch_conv_stream_kernel(const float* _
       const long r = k >> 1;
       const int col = n + (int)(k & 1);  // column of X; the last two are n, n + 1
       hist_out[k] = col >= 2 ? x[r * n + col - 2] : (hist_in ? hist_in[2 * r + col] : 0.f);
+    }
+  }
+}
+// Delay line of a stream: X = concat(line_in (rows, L), x (rows, n)), line_in == NULL: zeros.  line_out = the last L
+// columns of X (the history rule of stream_common.h, the rows dealt over the grid); delayed_out (rows, n), if wanted,
+// = the first n columns of X, i.e. x delayed by L columns.  Copies only.
+__global__ __launch_bounds__(256) void delay_line_kernel(const float* __restrict__ x, const float* __restrict__ line_in,
+                                                         float* __restrict__ line_out, float* __restrict__ delayed_out,
+                                                         int rows, int n, int L) {
+  stream_write_history<1>(x, line_in, line_out, rows, n, L, false, blockIdx.x, gridDim.x);
+  if (delayed_out) {
+    GRID_STRIDE(i, (long)rows * n) {
+      const long r = i / n;
+      const int j = (int)(i - r * n);
+      delayed_out[i] = j >= L ? x[r * n + (j - L)] : (line_in ? line_in[r * L + j] : 0.f);
     }
   }
 }
@@ -1092,23 +1114,59 @@ extern "C" int pwg_stretch_conv_forward(const float* x, const float* w, float* y
   return PWG_OK;
 }
 
-extern "C" int pwg_stretch_conv_stream(const float* x, const float* hist_in, float* hist_out, const float* w, float* y,
-                                       int64_t rows, int32_t n, int32_t scale, int32_t freq_kernel, int32_t act,
-                                       float slope, void* stream) {
-  PWG_REQUIRE(x && hist_out && w && y, PWG_ERR_NULL, "stretch_conv_stream: NULL pointer");
+// pwg_stretch_conv_stream, and with window != NULL ({valid_lo, valid_hi}) its delayed form
+static int stretch_conv_stream_launch(const char* name, const float* x, const float* hist_in, float* hist_out, const float* w,
+                                      float* y, int64_t rows, int32_t n, int32_t scale, int32_t freq_kernel, int32_t act,
+                                      float slope, const int32_t* window, void* stream) {
+  PWG_REQUIRE(x && hist_out && w && y, PWG_ERR_NULL, "%s: NULL pointer", name);
   PWG_REQUIRE(hist_in != hist_out, PWG_ERR_BAD_SHAPE,
-              "stretch_conv_stream: hist_in and hist_out must be distinct buffers (other threads read the history)");
+              "%s: hist_in and hist_out must be distinct buffers (other threads read the history)", name);
   PWG_REQUIRE(freq_kernel == 1, PWG_ERR_UNSUPPORTED,
-              "stretch_conv_stream: freq_kernel = %d (only 1: taps along the channel axis are not built for streams)",
-              freq_kernel);
+              "%s: freq_kernel = %d (only 1: taps along the channel axis are not built for streams)", name, freq_kernel);
   PWG_REQUIRE(act == PWG_ACT_NONE || act == PWG_ACT_LEAKY_RELU || act == PWG_ACT_RELU || act == PWG_ACT_TANH,
-              PWG_ERR_UNSUPPORTED, "stretch_conv_stream: activation %d", act);
+              PWG_ERR_UNSUPPORTED, "%s: activation %d", name, act);
   PWG_REQUIRE(rows > 0 && n > 0 && scale > 0 && (long)n * scale < (1L << 31), PWG_ERR_BAD_SHAPE,
-              "stretch_conv_stream: bad geometry (rows %lld, n %d, scale %d)", (long long)rows, n, scale);
+              "%s: bad geometry (rows %lld, n %d, scale %d)", name, (long long)rows, n, scale);
   const long total = rows * (long)n * scale;
   ProfScope prof((hipStream_t)stream, "stretch_conv_stream_kernel", 2.0 * total * (2 * scale + 1),
                  4.0 * (rows * (double)(n + 4) + total));
-  LAUNCH1D(stretch_conv_stream_kernel, total + 2 * rows, stream, x, hist_in, hist_out, w, y, (long)rows, n, scale, act, slope);
+  if (window)
+    LAUNCH1D(stretch_conv_stream_kernel<true>, total + 2 * rows, stream, x, hist_in, hist_out, w, y, (long)rows, n, scale, act,
+             slope, window[0], window[1]);
+  else
+    LAUNCH1D(stretch_conv_stream_kernel<false>, total + 2 * rows, stream, x, hist_in, hist_out, w, y, (long)rows, n, scale, act,
+             slope, 0, 0);
+  return PWG_OK;
+}
+
+extern "C" int pwg_stretch_conv_stream(const float* x, const float* hist_in, float* hist_out, const float* w, float* y,
+                                       int64_t rows, int32_t n, int32_t scale, int32_t freq_kernel, int32_t act,
+                                       float slope, void* stream) {
+  return stretch_conv_stream_launch("stretch_conv_stream", x, hist_in, hist_out, w, y, rows, n, scale, freq_kernel, act, slope,
+                                    nullptr, stream);
+}
+
+extern "C" int pwg_stretch_conv_stream_delayed(const float* x, const float* hist_in, float* hist_out, const float* w,
+                                               float* y, int64_t rows, int32_t n, int32_t scale, int32_t freq_kernel,
+                                               int32_t act, float slope, int32_t valid_lo, int32_t valid_hi, void* stream) {
+  const int32_t window[2] = {valid_lo, valid_hi};
+  return stretch_conv_stream_launch("stretch_conv_stream_delayed", x, hist_in, hist_out, w, y, rows, n, scale, freq_kernel, act,
+                                    slope, window, stream);
+}
+
+extern "C" int pwg_delay_line_forward(const float* x, const float* line_in, float* line_out, float* delayed_out,
+                                      int64_t rows, int32_t n, int32_t columns, void* stream) {
+  PWG_REQUIRE(x && line_out, PWG_ERR_NULL, "delay_line_forward: NULL pointer");
+  PWG_REQUIRE(line_in != line_out, PWG_ERR_BAD_SHAPE,
+              "delay_line_forward: line_in and line_out must be distinct buffers (other threads read the line)");
+  PWG_REQUIRE(delayed_out != x, PWG_ERR_BAD_SHAPE, "delay_line_forward: delayed_out must not alias x");
+  PWG_REQUIRE(rows > 0 && n > 0 && columns > 0 && rows * (long)columns < (1L << 31) && rows * (long)n < (1L << 31),
+              PWG_ERR_BAD_SHAPE, "delay_line_forward: bad geometry (rows %lld, n %d, %d columns; int element indices)",
+              (long long)rows, n, columns);
+  const long work = rows * (long)(columns > n ? columns : n);
+  ProfScope prof((hipStream_t)stream, "delay_line_kernel", 0.0,
+                 4.0 * rows * (2.0 * columns + (delayed_out ? 2.0 * n : (double)n)));
+  LAUNCH1D(delay_line_kernel, work, stream, x, line_in, line_out, delayed_out, (int)rows, n, columns);
   return PWG_OK;
 }
 

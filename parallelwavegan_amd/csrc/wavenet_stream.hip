@@ -39,10 +39,28 @@
 // not on n, the batch, the chunk's position in the stream, or the column's place in the tile (a column is one MFMA
 // lane position; its accumulator sees the same operand sequence wherever it sits, a padded or history operand is the
 // same value through either staging path) -- so any partition of a stream gives bit-identical results.  DESIGN.md s11.3.
+//
+// The delayed form (pwg_wavenet_stream_delayed_*) is the NON-causal layer of a stream with a fixed
+// look-ahead: the same kernel body (wavenet_stream_kernel<WnDelayedArgs>) on a time axis shifted by d.  The taps
+// x~[n - 2d], x~[n - d], x~[n] are the causal ones, the output is d columns later than the input, and
+//   * the residual is the MIDDLE tap window (rows 64..127 = x~[n - d]), which nobody writes either;
+//   * the aux window starts at n0 - c_delay and is staged from two sources by the rule of the tap windows: columns < 0
+//     from the conditioning line c_line[c_cols + f] (zeros when NULL), columns >= 0 from the chunk c; the 16-B LDS-DMA
+//     pass when the window lies in one source, per sample otherwise;
+//   * the skip addend of output column j is concat(skip_line_in, skips)[j] (a delay of d columns, read in the epilogue
+//     as the delayed conv kernel reads its addends), and skip_line_out = the last d columns of that concatenation,
+//     dealt over the workgroups as the history is;
+//   * outside [valid_lo, valid_hi) 0.0f is STORED to x_out and skips_out: the next layer's zero padding.
+// Sum order of the delayed form: that of the causal form, word for word -- the image's K order in one accumulator, the
+// K = 64 contraction, + bias, + the skip addend / + the residual, * scale.  It depends on the layer alone: not on n, the
+// batch, the chunk's position, c_delay or its alignment, or which staging path a window took (an operand is the same
+// fp32 value through the DMA pass and through registers; the addend is the same value from the line and from the chunk).
 #include "stream_common.h"
 #include "wavenet_gate.h"
 
 #include <stdint.h>
+
+#include <type_traits>
 
 namespace pwg {
 namespace {
@@ -68,7 +86,18 @@ struct WnStreamArgs {
   int vec_ok;  // x_out / skips / skips_out are 16-B aligned
 };
 
-__global__ __launch_bounds__(256, 2) void wavenet_stream_kernel(WnStreamArgs a) {
+// What the delayed form adds (file header).  skips_out must not alias skips: tiles read their neighbours' skip columns.
+struct WnDelayedArgs : WnStreamArgs {
+  const float* c_line;        // (B, 80, c_cols) or NULL (zeros): the conditioning columns before this chunk
+  const float* skip_line_in;  // (B, 64, d) or NULL (zeros)
+  float* skip_line_out;       // (B, 64, d); unused without skips
+  int c_cols, c_delay;        // 0 <= c_delay <= c_cols
+  int valid_lo, valid_hi;     // output columns (chunk-relative)
+};
+
+template <class ARGS>
+__global__ __launch_bounds__(256, 2) void wavenet_stream_kernel(ARGS a) {
+  constexpr bool DELAYED = std::is_same<ARGS, WnDelayedArgs>::value;
   constexpr int NQ1 = WS_ROWS / 8;  // 16-B weight records per lane and row tile in phase 1 (4 k-steps each)
   constexpr int NQ2 = WN_R / 8;     // phase 2: K = 64 rows of g
   extern __shared__ __attribute__((aligned(16))) float tile[];  // [ROWS][64]; rows 0..63 are overwritten by g
@@ -84,44 +113,54 @@ __global__ __launch_bounds__(256, 2) void wavenet_stream_kernel(WnStreamArgs a) 
   const float* __restrict__ xb = a.x + (long)b * WN_R * n;
   const float* __restrict__ cb = a.c + (long)b * WS_AUX * n;
   const float* __restrict__ hb = a.hist_in ? a.hist_in + (long)b * WN_R * H : nullptr;
+  // the aux window's past (delayed form): the conditioning line, c_cols columns; the window starts c_delay columns early
+  const float* __restrict__ lb = nullptr;
+  int L = 0, c_delay = 0;
+  if constexpr (DELAYED) {
+    L = a.c_cols;
+    c_delay = a.c_delay;
+    lb = a.c_line ? a.c_line + (long)b * WS_AUX * L : nullptr;
+  }
 
-  // ---- stage the operand tile: window `tap` of X starts at chunk-relative column n0 + (tap - 2) d
+  // ---- stage the operand tile: window `tap` of X starts at chunk-relative column n0 + (tap - 2) d, the aux window at
+  // n0 - c_delay
   {
     __amdgpu_buffer_rsrc_t x_rs = uniform_buffer_rsrc(xb, (unsigned)(WN_R * n) * 4u);
     __amdgpu_buffer_rsrc_t c_rs = uniform_buffer_rsrc(cb, (unsigned)(WS_AUX * n) * 4u);
     __amdgpu_buffer_rsrc_t h_rs = uniform_buffer_rsrc(hb ? hb : xb, hb ? (unsigned)(WN_R * H) * 4u : 0u);
+    __amdgpu_buffer_rsrc_t l_rs = uniform_buffer_rsrc(lb ? lb : xb, lb ? (unsigned)(WS_AUX * L) * 4u : 0u);
     for (int q = wave; q < WS_ROWS / 4; q += 4) {  // 4 rows (1 KiB of LDS) per wave instruction
       const int r0 = 4 * q;
       const bool is_x = r0 < WN_K * WN_R;
       const int tap = r0 / WN_R;
-      const int f0 = is_x ? n0 + (tap - 2) * a.dil : n0;  // first column of the window (< 0: history)
+      const int f0 = is_x ? n0 + (tap - 2) * a.dil : n0 - c_delay;  // first column of the window (< 0: the past)
       const int ch0 = is_x ? r0 - tap * WN_R : r0 - WN_K * WN_R;
+      const float* __restrict__ pb = is_x ? hb : lb;  // the window's past source and its columns
+      const int P = is_x ? H : L;
       const int in_chunk = __builtin_amdgcn_readfirstlane((f0 >= 0 && f0 + WN_COLS <= n) ? 1 : 0);
-      const int in_hist = __builtin_amdgcn_readfirstlane((is_x && hb != nullptr && f0 + WN_COLS <= 0) ? 1 : 0);
+      const int in_past = __builtin_amdgcn_readfirstlane((pb != nullptr && f0 + WN_COLS <= 0) ? 1 : 0);
       if (in_chunk) {
         const unsigned off = (unsigned)((ch0 + (lane >> 4)) * n + f0 + 4 * (lane & 15)) * 4u;
         if (is_x) __builtin_amdgcn_raw_ptr_buffer_load_lds(x_rs, (lds_ptr_t)(tile + r0 * WN_COLS), 16, off, 0, 0, 0);
         else __builtin_amdgcn_raw_ptr_buffer_load_lds(c_rs, (lds_ptr_t)(tile + r0 * WN_COLS), 16, off, 0, 0, 0);
-      } else if (in_hist) {
-        // (f0 >= -H: H + f0 >= 0, and H + f0 + 64 <= H)
-        const unsigned off = (unsigned)((ch0 + (lane >> 4)) * H + H + f0 + 4 * (lane & 15)) * 4u;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(h_rs, (lds_ptr_t)(tile + r0 * WN_COLS), 16, off, 0, 0, 0);
+      } else if (in_past) {
+        // (f0 >= -P: P + f0 >= 0, and P + f0 + 64 <= P)
+        const unsigned off = (unsigned)((ch0 + (lane >> 4)) * P + P + f0 + 4 * (lane & 15)) * 4u;
+        if (is_x) __builtin_amdgcn_raw_ptr_buffer_load_lds(h_rs, (lds_ptr_t)(tile + r0 * WN_COLS), 16, off, 0, 0, 0);
+        else __builtin_amdgcn_raw_ptr_buffer_load_lds(l_rs, (lds_ptr_t)(tile + r0 * WN_COLS), 16, off, 0, 0, 0);
       } else {
-        // the window straddles history and chunk, leaves the chunk on the right, or is start-of-stream padding:
+        // the window straddles past and chunk, leaves the chunk on the right, or is start-of-stream padding:
         // per sample, range-checked, zeros outside
         const int f = f0 + lane;
+        const float* __restrict__ sb = is_x ? xb : cb;
         float v[4];
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) {
           v[rr] = 0.f;
-          if (is_x) {
-            if (f < 0) {
-              if (hb) v[rr] = hb[(long)(ch0 + rr) * H + (H + f)];
-            } else if (f < n) {
-              v[rr] = xb[(long)(ch0 + rr) * n + f];
-            }
+          if (f < 0) {
+            if (pb) v[rr] = pb[(long)(ch0 + rr) * P + (P + f)];
           } else if (f < n) {
-            v[rr] = cb[(long)(ch0 + rr) * n + f];
+            v[rr] = sb[(long)(ch0 + rr) * n + f];
           }
         }
 #pragma unroll
@@ -223,8 +262,9 @@ __global__ __launch_bounds__(256, 2) void wavenet_stream_kernel(WnStreamArgs a) 
   // ---- epilogue: D layout col = lane & 31 (time), rows as above.  Each wave transposes its two 32 x 32 result tiles,
   // one after the other, through a private 32 x 36 scratch in the aux rows (dead since phase 1) so that a lane owns 4
   // consecutive samples of a row: 16-B loads of the skip sum, 16-B stores of both outputs.  The residual comes from the
-  // last tap window (rows 128..191 = x[n]), which no wave writes.  (Wave-private scratch: no workgroup barrier, the
-  // wave's own LDS accesses are ordered.)
+  // last tap window (rows 128..191 = x[n]; the delayed form: from the middle one, rows 64..127 = x~[n - d]), which no
+  // wave writes.  (Wave-private scratch: no workgroup barrier, the wave's own LDS accesses are ordered.)
+  constexpr int RES_TAP = DELAYED ? 1 : 2;
   float* scr = tile + (WN_K * WN_R) * WN_COLS + wave * (32 * 36);
   const int trow = lane >> 3, tcol = (lane & 7) * 4;
   const int nq = n0 + cn * 32 + tcol;
@@ -238,7 +278,7 @@ __global__ __launch_bounds__(256, 2) void wavenet_stream_kernel(WnStreamArgs a) 
       if (pass == 0) {
         scr[rl * 36 + l31] = acc[0][r] + bsk[r];
       } else {
-        const float xc = tile[(2 * WN_R + h * 32 + rl) * WN_COLS + cn * 32 + l31];  // last window = x[n]
+        const float xc = tile[(RES_TAP * WN_R + h * 32 + rl) * WN_COLS + cn * 32 + l31];
         scr[rl * 36 + l31] = (acc[1][r] + bo[r] + xc) * a.out_mul;
       }
     }
@@ -247,7 +287,25 @@ __global__ __launch_bounds__(256, 2) void wavenet_stream_kernel(WnStreamArgs a) 
       const int rl = ps * 8 + trow;
       const long o = ob + (long)(h * 32 + rl) * n;
       float4 v = *reinterpret_cast<const float4*>(scr + rl * 36 + tcol);
-      if (vec) {
+      if constexpr (DELAYED) {
+        // per element: the skip addend through its delay line, then zeros outside the valid window; the same values
+        // whether the store below is a float4 or four floats
+        float e4[4] = {v.x, v.y, v.z, v.w};
+        float* __restrict__ out = pass == 0 ? a.skips_out : a.x_out;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int j = nq + e;
+          if (j >= n) continue;
+          if (pass == 0) {
+            if (a.skips)
+              e4[e] += stream_delayed_addend(a.skips, a.skip_line_in, a.dil, (size_t)b * WN_S + h * 32 + rl, n, j);
+            if (a.skip_mul != 1.0f) e4[e] *= a.skip_mul;
+          }
+          if (j < a.valid_lo || j >= a.valid_hi) e4[e] = 0.f;
+          if (!vec) out[o + e] = e4[e];
+        }
+        if (vec && nq < n) *reinterpret_cast<float4*>(out + o) = make_float4(e4[0], e4[1], e4[2], e4[3]);
+      } else if (vec) {
         if (nq < n) {  // (n % 4 == 0: a float4 is inside the chunk or outside it)
           if (pass == 0) {
             if (a.skips) {
@@ -280,12 +338,23 @@ __global__ __launch_bounds__(256, 2) void wavenet_stream_kernel(WnStreamArgs a) 
 
   // ---- hist_out = last H columns of concat(hist_in, x), raw (start of stream: zeros)
   stream_write_history<4>(xb, hb, a.hist_out + (long)b * WN_R * H, WN_R, n, H, false, blockIdx.x, gridDim.x);
+  // ---- delayed form: skip_line_out = last d columns of concat(skip_line_in, skips), raw
+  if constexpr (DELAYED) {
+    if (a.skips)
+      stream_write_history<4>(a.skips + (long)b * WN_S * n, a.skip_line_in ? a.skip_line_in + (long)b * WN_S * a.dil : nullptr,
+                              a.skip_line_out + (long)b * WN_S * a.dil, WN_S, n, a.dil, false, blockIdx.x, gridDim.x);
+  }
 }
 
-static int wavenet_stream_geometry(const pwg_wavenet_desc* d) {
+// delayed: the look-ahead form, whose descriptor is the non-causal layer's own
+static int wavenet_stream_geometry(const pwg_wavenet_desc* d, bool delayed = false) {
   PWG_REQUIRE(d != nullptr, PWG_ERR_NULL, "wavenet_stream: NULL descriptor");
-  PWG_REQUIRE(d->causal, PWG_ERR_UNSUPPORTED,
-              "wavenet_stream: not a causal layer (a stream keeps only past columns; non-causal layers look ahead)");
+  if (delayed)
+    PWG_REQUIRE(!d->causal, PWG_ERR_UNSUPPORTED,
+                "wavenet_stream_delayed: a causal layer streams without look-ahead (pwg_wavenet_stream_forward)");
+  else
+    PWG_REQUIRE(d->causal, PWG_ERR_UNSUPPORTED,
+                "wavenet_stream: not a causal layer (a stream keeps only past columns; non-causal layers look ahead)");
   PWG_REQUIRE(d->kernel == WN_K, PWG_ERR_UNSUPPORTED, "wavenet_stream: kernel = %d (only kernel 3)", d->kernel);
   PWG_REQUIRE(d->residual_channels == WN_R && d->gate_channels == WN_G && d->skip_channels == WN_S, PWG_ERR_UNSUPPORTED,
               "wavenet_stream: residual / gate / skip channels = %d / %d / %d (only 64 / 128 / 64)", d->residual_channels,
@@ -300,6 +369,72 @@ static int wavenet_stream_geometry(const pwg_wavenet_desc* d) {
               d->t);
   PWG_REQUIRE((long)WN_R * 2 * d->dilation * 4 < (1L << 31), PWG_ERR_UNSUPPORTED,
               "wavenet_stream: dilation = %d: the history of one item is too long", d->dilation);
+  return PWG_OK;
+}
+
+// What the delayed form adds to it: the aux window starts c_delay columns early, inside a line of at least as many
+static int wavenet_delayed_geometry(const pwg_wavenet_desc* d, int32_t c_delay) {
+  const int rc = wavenet_stream_geometry(d, true);
+  if (rc != PWG_OK) return rc;
+  PWG_REQUIRE(c_delay >= 0, PWG_ERR_BAD_SHAPE, "wavenet_stream_delayed: c_delay = %d is negative", c_delay);
+  PWG_REQUIRE((long)WS_AUX * c_delay * 4 < (1L << 31), PWG_ERR_UNSUPPORTED,
+              "wavenet_stream_delayed: c_delay = %d: the conditioning line of one item is too long", c_delay);
+  return PWG_OK;
+}
+
+static bool aligned(const void* p, unsigned m) { return (reinterpret_cast<uintptr_t>(p) & m) == 0; }
+
+// The pointer rules and argument fields the two forms share
+static int wavenet_stream_fill(const char* name, WnStreamArgs* a, const pwg_wavenet_desc* d, const float* x, const float* c,
+                               const float* skips, const float* hist_in, float* hist_out, const float* packed,
+                               const float* b_dil, const float* b_skip, const float* b_out, float* x_out, float* skips_out) {
+  PWG_REQUIRE(x && c && packed && x_out && skips_out && hist_out, PWG_ERR_NULL, "%s: NULL pointer", name);
+  PWG_REQUIRE(hist_in != hist_out, PWG_ERR_BAD_SHAPE,
+              "%s: hist_in and hist_out must be distinct buffers (other workgroups read the history)", name);
+  PWG_REQUIRE(x != x_out, PWG_ERR_BAD_SHAPE, "%s: x_out must not alias x (tiles read their neighbours' samples)", name);
+  PWG_REQUIRE(aligned(x, 3) && aligned(c, 3) && aligned(hist_in, 3) && aligned(hist_out, 3) && aligned(packed, 15),
+              PWG_ERR_BAD_SHAPE, "%s: unaligned tensor (4 B; the weight image 16 B)", name);
+  a->x = x;
+  a->c = c;
+  a->skips = skips;
+  a->hist_in = hist_in;
+  a->hist_out = hist_out;
+  a->w1 = packed;
+  a->w2 = packed + (size_t)WS_ROWS * WN_G;
+  a->b_dil = b_dil;
+  a->b_skip = b_skip;
+  a->b_out = b_out;
+  a->x_out = x_out;
+  a->skips_out = skips_out;
+  a->n = d->t;
+  a->dil = d->dilation;
+  a->out_mul = d->out_mul;
+  a->skip_mul = d->skip_mul;
+  a->vec_ok = aligned(x_out, 15) && aligned(skips, 15) && aligned(skips_out, 15);
+  return PWG_OK;
+}
+
+// state_floats: what the launch reads and writes besides the chunk (history; the delayed form's lines)
+template <class ARGS>
+static int wavenet_stream_launch(const char* name, const char* kernel_name, const pwg_wavenet_desc* d, const ARGS& a,
+                                 double state_floats, hipStream_t stream) {
+  const size_t lds = (size_t)WS_ROWS * WN_COLS * sizeof(float);
+  void (*kern)(ARGS) = wavenet_stream_kernel<ARGS>;
+  if (!lds_limit_is_set(reinterpret_cast<const void*>(kern), lds)) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    PWG_REQUIRE(e == hipSuccess, PWG_ERR_LAUNCH, "%s: cannot raise the LDS limit to %zu: %s", name, lds,
+                hipGetErrorString(e));
+  }
+  const double samples = (double)d->batch * d->t;
+  const double flops = 2.0 * samples * (WN_G * (double)WS_ROWS + (double)(WN_S + WN_R) * WN_R);
+  const double bytes = 4.0 * (samples * (WN_R * 4 + WS_AUX + (a.skips ? WN_S : 0)) + state_floats) +
+                       4.0 * ((double)WS_ROWS * WN_G + (double)WN_R * (WN_S + WN_R));
+  maybe_poison_lds(stream);
+  {
+    ProfScope prof(stream, kernel_name, flops, bytes);
+    hipLaunchKernelGGL(kern, dim3(ceil_div(d->t, WN_COLS), d->batch), dim3(256), lds, stream, a);
+  }
+  PWG_CHECK_LAUNCH(name);
   return PWG_OK;
 }
 
@@ -321,52 +456,56 @@ extern "C" int pwg_wavenet_stream_forward(const pwg_wavenet_desc* d, const float
                                           const float* hist_in, float* hist_out, const float* packed, const float* b_dil,
                                           const float* b_skip, const float* b_out, float* x_out, float* skips_out,
                                           void* stream_) {
-  const int rc = wavenet_stream_geometry(d);
+  int rc = wavenet_stream_geometry(d);
   if (rc != PWG_OK) return rc;
-  PWG_REQUIRE(x && c && packed && x_out && skips_out && hist_out, PWG_ERR_NULL, "wavenet_stream_forward: NULL pointer");
-  PWG_REQUIRE(hist_in != hist_out, PWG_ERR_BAD_SHAPE,
-              "wavenet_stream_forward: hist_in and hist_out must be distinct buffers (other workgroups read the history)");
-  PWG_REQUIRE(x != x_out, PWG_ERR_BAD_SHAPE,
-              "wavenet_stream_forward: x_out must not alias x (tiles read their neighbours' samples)");
-  auto al = [](const void* p, unsigned m) { return (reinterpret_cast<uintptr_t>(p) & m) == 0; };
-  PWG_REQUIRE(al(x, 3) && al(c, 3) && al(hist_in, 3) && al(hist_out, 3) && al(packed, 15), PWG_ERR_BAD_SHAPE,
-              "wavenet_stream_forward: unaligned tensor (4 B; the weight image 16 B)");
-  hipStream_t stream = (hipStream_t)stream_;
   WnStreamArgs a;
-  a.x = x;
-  a.c = c;
-  a.skips = skips;
-  a.hist_in = hist_in;
-  a.hist_out = hist_out;
-  a.w1 = packed;
-  a.w2 = packed + (size_t)WS_ROWS * WN_G;
-  a.b_dil = b_dil;
-  a.b_skip = b_skip;
-  a.b_out = b_out;
-  a.x_out = x_out;
-  a.skips_out = skips_out;
-  a.n = d->t;
-  a.dil = d->dilation;
-  a.out_mul = d->out_mul;
-  a.skip_mul = d->skip_mul;
-  a.vec_ok = al(x_out, 15) && al(skips, 15) && al(skips_out, 15);
-  const size_t lds = (size_t)WS_ROWS * WN_COLS * sizeof(float);
-  void (*kern)(WnStreamArgs) = wavenet_stream_kernel;
-  if (!lds_limit_is_set(reinterpret_cast<const void*>(kern), lds)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    PWG_REQUIRE(e == hipSuccess, PWG_ERR_LAUNCH, "wavenet_stream_forward: cannot raise the LDS limit to %zu: %s", lds,
-                hipGetErrorString(e));
-  }
-  const double samples = (double)d->batch * d->t;
-  const double hist = (double)d->batch * WN_R * 2.0 * d->dilation;
-  const double flops = 2.0 * samples * (WN_G * (double)WS_ROWS + (double)(WN_S + WN_R) * WN_R);
-  const double bytes = 4.0 * (samples * (WN_R * 4 + WS_AUX + (skips ? WN_S : 0)) + 2.0 * hist) +
-                       4.0 * ((double)WS_ROWS * WN_G + (double)WN_R * (WN_S + WN_R));
-  maybe_poison_lds(stream);
-  {
-    ProfScope prof(stream, "wavenet_stream_kernel", flops, bytes);
-    hipLaunchKernelGGL(kern, dim3(ceil_div(d->t, WN_COLS), d->batch), dim3(256), lds, stream, a);
-  }
-  PWG_CHECK_LAUNCH("wavenet_stream_forward");
-  return PWG_OK;
+  rc = wavenet_stream_fill("wavenet_stream_forward", &a, d, x, c, skips, hist_in, hist_out, packed, b_dil, b_skip, b_out,
+                           x_out, skips_out);
+  if (rc != PWG_OK) return rc;
+  return wavenet_stream_launch("wavenet_stream_forward", "wavenet_stream_kernel", d, a,
+                               2.0 * d->batch * WN_R * 2.0 * d->dilation, (hipStream_t)stream_);
+}
+
+extern "C" int pwg_wavenet_stream_delayed_supported(const pwg_wavenet_desc* d, int32_t c_delay) {
+  return wavenet_delayed_geometry(d, c_delay) == PWG_OK ? 1 : 0;
+}
+
+extern "C" size_t pwg_wavenet_stream_delayed_hist_floats(const pwg_wavenet_desc* d) {
+  if (wavenet_stream_geometry(d, true) != PWG_OK) return 0;
+  return (size_t)d->batch * WN_R * (size_t)(d->kernel - 1) * d->dilation;
+}
+
+extern "C" int pwg_wavenet_stream_delayed_forward(const pwg_wavenet_desc* d, const float* x, const float* c,
+                                                  const float* c_line, int32_t c_cols, int32_t c_delay, const float* skips,
+                                                  const float* skip_line_in, float* skip_line_out, const float* hist_in,
+                                                  float* hist_out, const float* packed, const float* b_dil,
+                                                  const float* b_skip, const float* b_out, int32_t valid_lo,
+                                                  int32_t valid_hi, float* x_out, float* skips_out, void* stream_) {
+  const char* name = "wavenet_stream_delayed_forward";
+  int rc = wavenet_delayed_geometry(d, c_delay);
+  if (rc != PWG_OK) return rc;
+  PWG_REQUIRE(c_line == nullptr || (c_cols >= c_delay && (long)WS_AUX * c_cols * 4 < (1L << 31)), PWG_ERR_BAD_SHAPE,
+              "%s: a conditioning line of %d columns cannot serve c_delay = %d (c_delay .. 2^31 bytes per item)", name,
+              c_cols, c_delay);
+  PWG_REQUIRE(skips == nullptr || skip_line_out != nullptr, PWG_ERR_NULL,
+              "%s: skips needs skip_line_out (the layer keeps %d columns of the skip sum)", name, d->dilation);
+  PWG_REQUIRE(skips == nullptr || skip_line_in != skip_line_out, PWG_ERR_BAD_SHAPE,
+              "%s: skip_line_in and skip_line_out must be distinct buffers (other workgroups read the line)", name);
+  PWG_REQUIRE(skips == nullptr || skips != skips_out, PWG_ERR_BAD_SHAPE,
+              "%s: skips_out must not alias skips (tiles read their neighbours' skip columns)", name);
+  PWG_REQUIRE(aligned(c_line, 3) && aligned(skips, 3) && aligned(skip_line_in, 3) && aligned(skip_line_out, 3),
+              PWG_ERR_BAD_SHAPE, "%s: unaligned tensor (4 B)", name);
+  WnDelayedArgs a;
+  rc = wavenet_stream_fill(name, &a, d, x, c, skips, hist_in, hist_out, packed, b_dil, b_skip, b_out, x_out, skips_out);
+  if (rc != PWG_OK) return rc;
+  a.c_line = c_line;
+  a.c_cols = c_line ? c_cols : 0;
+  a.c_delay = c_delay;
+  a.skip_line_in = skips ? skip_line_in : nullptr;
+  a.skip_line_out = skips ? skip_line_out : nullptr;
+  a.valid_lo = valid_lo;
+  a.valid_hi = valid_hi;
+  return wavenet_stream_launch(name, "wavenet_stream_delayed_kernel", d, a,
+                               (double)d->batch * (2.0 * WN_R * 2.0 * d->dilation + (skips ? 2.0 * WN_S * d->dilation : 0.0)),
+                               (hipStream_t)stream_);
 }

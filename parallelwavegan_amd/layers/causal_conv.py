@@ -195,6 +195,20 @@ def lookahead_state_shapes(plan, batch):
     return shapes
 
 
+def lookahead_window(delay, rate, t_out, frames_before=None, total_frames=None):
+    """Valid window ``(lo, hi)`` of a launch's ``t_out`` output columns (chunk-relative): the columns that hold the
+    utterance on the launch's shifted axis.  ``delay`` / ``rate``: the launch's output delay and columns per mel frame;
+    ``frames_before``: frames the stream took before this push (None: steady state, the window is full);
+    ``total_frames``: the utterance's length once it is known (the flush), else None."""
+    lo, hi = 0, t_out
+    if frames_before is not None:
+        before = frames_before * rate  # output columns the stream produced before this push
+        lo = min(max(delay - before, 0), t_out)
+        if total_frames is not None:
+            hi = min(max(delay + total_frames * rate - before, 0), t_out)
+    return lo, hi
+
+
 class LookaheadWalk:
     """One push through the launches of a delay plan: hands every launch its state tensors and its valid window.
     ``state_in`` (None: start of stream, every state reads as zeros) / ``state_out``: one ping-pong half each, of
@@ -234,12 +248,7 @@ class LookaheadWalk:
         line1, line2 = self._take(launch.delay1), self._take(launch.delay2)
         desc = lookahead_desc(cv, x.shape[0], x.shape[-1], **fused)
         t_out = desc.t_out
-        lo, hi = 0, t_out
-        if self.frames_before is not None:
-            before = self.frames_before * launch.rate  # output columns the stream produced before this push
-            lo = min(max(launch.delay - before, 0), t_out)
-            if self.total_frames is not None:
-                hi = min(max(launch.delay + self.total_frames * launch.rate - before, 0), t_out)
+        lo, hi = lookahead_window(launch.delay, launch.rate, t_out, self.frames_before, self.total_frames)
         if bf16:
             kernel, supported, forward = "delayed bf16 streaming kernel", ops.conv1d_stream_bf16_delayed_supported, \
                 ops.conv1d_stream_delayed_forward_bf16
@@ -256,3 +265,73 @@ class LookaheadWalk:
             image = cv.packed_weight_bf16() if bf16 else cv.packed_weight()
             return forward(desc, x.contiguous(), hist[0], hist[1], image, bias, add1, line1, launch.delay1, add2, line2,
                            launch.delay2, (lo, hi))
+
+
+# ---- the same for the NON-causal Parallel WaveGAN generator (utils.PWGLookaheadStream).  Its launches
+# are not all convolutions (upsampler stages, gated layers, delay lines), so a launch names its kind and module and lists
+# its state itself: ``state`` = the ``(channels, columns)`` of every state tensor it keeps, in the order it takes them;
+# ``c_delay``: how late a gated layer reads the conditioning (0 for every other launch).
+PWGLookaheadLaunch = collections.namedtuple("PWGLookaheadLaunch", "kind module rate delay c_delay state")
+
+
+def pwg_lookahead_state_shapes(plan, batch):
+    """Shapes of the state tensors of one ping-pong half, in the order :class:`PWGLookaheadWalk` takes them."""
+    return [(batch, ch, cols) for launch in plan for ch, cols in launch.state]
+
+
+def lookahead_launch(cv, desc, x, hist=(None, None), valid=None):
+    """One fp32 delayed launch of ``cv`` under ``desc`` without addends: the history pair and the valid window are the
+    caller's (``conv_in`` and the 1 x 1 convolutions of the Parallel WaveGAN look-ahead stream).  A module in bf16 mode
+    and a layer the kernel does not cover are errors, by the rule of :meth:`LookaheadWalk.run`."""
+    if cv.precision != "fp32":
+        raise RuntimeError(f"{cv.__class__.__name__} is in {cv.precision} inference precision: the look-ahead stream is "
+                           "fp32 (utils.set_inference_precision(model, 'fp32'))")
+    if not ops.conv1d_stream_delayed_supported(desc):
+        from .. import _lib
+
+        raise RuntimeError("the delayed streaming kernel does not cover this layer: "
+                           + _lib.lib().pwg_last_error().decode(errors="replace"))
+    with torch.no_grad():
+        return ops.conv1d_stream_delayed_forward(desc, x.contiguous(), hist[0], hist[1], cv.packed_weight(),
+                                                 None if cv.bias is None else cv.bias.detach(), valid=valid)
+
+
+def lookahead_pointwise(cv, x, valid, **fused):
+    """A 1 x 1 ``Conv1d`` on the next columns of a look-ahead stream: :func:`stream_pointwise` with a valid window, which
+    keeps the bias out of the padding."""
+    if cv.kernel_size != 1 or cv.padding != 0 or cv.padding_right != 0:
+        raise ValueError("lookahead_pointwise: not an unpadded 1 x 1 convolution")
+    n = x.shape[-1]
+    desc = ops.make_conv_desc(x.shape[0], cv.in_channels, cv.out_channels, n, n, 1, cv.stride, 1, 0, cv.groups,
+                              transposed=False, pad_mode="zero", **fused)
+    return lookahead_launch(cv, desc, x, valid=valid)
+
+
+class PWGLookaheadWalk:
+    """One push through the launches of ``ParallelWaveGANGenerator.lookahead_plan()``: hands every launch its state
+    pairs and its valid window (the arithmetic of :func:`lookahead_window`, as :class:`LookaheadWalk`).  ``state_in``
+    (None: start of stream, every state reads as zeros) / ``state_out``: one ping-pong half each, of
+    :func:`pwg_lookahead_state_shapes`; ``frames_before`` / ``total_frames`` as in :class:`LookaheadWalk`."""
+
+    def __init__(self, plan, state_in, state_out, frames_before=None, total_frames=None):
+        self._plan = iter(plan)
+        self._in = None if state_in is None else iter(state_in)
+        self._out = iter(state_out)
+        self.frames_before, self.total_frames = frames_before, total_frames
+
+    @property
+    def at_start(self):
+        """No state yet: the first push of an utterance."""
+        return self._in is None
+
+    def take(self, kind, module, frames):
+        """The next launch of the plan, which must be ``(kind, module)``, on a chunk of ``frames`` mel frames ->
+        ``(launch, [(state_in, state_out), ...], (lo, hi))``: its state pairs (``state_in`` None at the start of a stream)
+        and the valid window of its ``frames * launch.rate`` output columns."""
+        launch = next(self._plan)
+        if launch.kind != kind or launch.module is not module:
+            raise RuntimeError(f"look-ahead walk out of step: the plan expects {launch.kind} {launch.module}, the model "
+                               f"ran {kind} {module}")
+        pairs = [(None if self._in is None else next(self._in), next(self._out)) for _ in launch.state]
+        window = lookahead_window(launch.delay, launch.rate, frames * launch.rate, self.frames_before, self.total_frames)
+        return launch, pairs, window

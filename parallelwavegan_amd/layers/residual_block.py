@@ -227,6 +227,47 @@ class WaveNetResidualBlock(torch.nn.Module):
                                               c.contiguous(), skips, hist_in, hist_out, self.stream_image(), b_d, b_s, b_o,
                                               skips_out=skips if (inplace_skips and skips is not None) else None)
 
+    # ---- the NON-causal block streamed with a fixed look-ahead (csrc/wavenet_stream.hip, the delayed form; DESIGN.md
+    # s11.6): the causal launch on a time axis shifted by the dilation
+    def lookahead_unsupported_reason(self, batch=1, n=1, c_delay=0):
+        """None if the delayed form of the streaming layer kernel covers this non-causal block at (batch, n) with the
+        conditioning read ``c_delay`` columns late, else the reason it does not (host logic only).  A causal block is
+        not a geometry question: ``lookahead_forward`` raises ValueError for it."""
+        if self.conv1x1_aux is None:
+            return "the block has no aux (conditioning) convolution"
+        if any(cv.has_spectral_norm or cv.pad_mode != "zero" for cv in self.fused_convs()):
+            return "spectral norm or non-zero padding"
+        if self.conv1x1_out.out_channels != self.conv.in_channels:
+            return "out channels differ from the residual channels"
+        if not ops.wavenet_stream_delayed_supported(self.fused_desc(batch, n), c_delay):
+            return _lib.lib().pwg_last_error().decode(errors="replace")
+        return None
+
+    def lookahead_forward(self, x, c, c_line, c_delay, hist, skips=None, skip_line=(None, None), valid=None,
+                          skip_scale=1.0):
+        """The non-causal block on the next ``x.shape[-1]`` columns of a look-ahead stream -> (x_out, skips + s), both
+        ``dilation`` columns later than ``x``.  ``hist = (hist_in, hist_out)``: the last ``2 * dilation`` columns of the
+        block's input (``hist_in`` None: start of stream); the conditioning is read ``c_delay`` columns late from
+        ``concat(c_line, c)``; the running skip sum goes through ``skip_line = (line_in, line_out)`` of ``dilation``
+        columns; columns outside ``valid = (lo, hi)`` are stored as zeros.  One launch; fp32 only."""
+        if self.use_causal_conv:
+            raise ValueError("WaveNetResidualBlock: a causal block streams without look-ahead (stream_forward, "
+                             "utils.PWGStream)")
+        if any(cv is not None and cv.precision != "fp32" for cv in self.fused_convs()):
+            raise RuntimeError("WaveNetResidualBlock is in bf16 inference precision: the streaming layer kernel is fp32 "
+                               "(utils.set_inference_precision(model, 'fp32'))")
+        reason = self.lookahead_unsupported_reason(x.shape[0], x.shape[-1], c_delay) if x.dim() == 3 else "x is not (B, C, n)"
+        if reason is None and self.dropout > 0.0 and self.training:
+            reason = "dropout in training mode"
+        if reason is not None:
+            raise RuntimeError("the delayed streaming layer kernel does not cover this block: " + reason)
+        with torch.no_grad():
+            b_d, b_s, b_o = (None if cv.bias is None else cv.bias.detach()
+                             for cv in (self.conv, self.conv1x1_skip, self.conv1x1_out))
+            return ops.wavenet_stream_delayed_forward(self.fused_desc(x.shape[0], x.shape[-1], skip_scale), x.contiguous(),
+                                                      c.contiguous(), c_line, c_delay, skips, skip_line, hist[0], hist[1],
+                                                      self.stream_image(), b_d, b_s, b_o, valid)
+
     def forward(self, x, c, skips=None, skip_scale=1.0, chain_aux=False, inplace_skips=False):
         """Returns (x_out, skips + s) -- the running skip sum is an addend of the skip conv's epilogue
         (``skip_scale`` is the final ``sqrt(1/layers)`` of the generator, applied by the last block).

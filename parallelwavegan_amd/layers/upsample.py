@@ -133,6 +133,10 @@ class UpsampleNetwork(torch.nn.Module):
         """None if every stage can be streamed, else the reason (host logic only)."""
         if not self.use_causal_conv:
             return "streaming needs use_causal_conv=True"
+        return self._stage_geometry_reason()
+
+    def _stage_geometry_reason(self):
+        """What the stream kernel of a stage does not cover, causal or not."""
         for i in self._stages:
             if self.up_layers[i].mode != "nearest":
                 return f"interpolate mode {self.up_layers[i].mode!r} (only 'nearest')"
@@ -161,6 +165,41 @@ class UpsampleNetwork(torch.nn.Module):
         stages = self.stream_layers()
         for k, (stage, _) in enumerate(stages):
             c = stage.stream_forward(c, None if hist_in is None else hist_in[k], hist_out[k])
+        return c
+
+
+    # ---- the NON-causal network streamed with a fixed look-ahead (pwg_stretch_conv_stream_delayed):
+    # the stage y[u] = sum_j w[j] xs[u + j - s] is the causal stage (left padding 2 s) on a time axis shifted by s
+    def lookahead_unsupported_reason(self):
+        """None if every stage streams with a look-ahead, else the reason (host logic only)."""
+        if self.use_causal_conv:
+            return "the network is causal (use_causal_conv=True) and streams without look-ahead"
+        return self._stage_geometry_reason()
+
+    def lookahead_plan(self, channels, delay_in=0, rate=1):
+        """One ``PWGLookaheadLaunch("stage", conv, rate, delay, 0, [(channels, 2)])`` per stage -> ``(launches, delay,
+        rate)`` of the network's output: a stage of scale ``s`` takes an input delayed by ``D`` to ``D * s + s``."""
+        from .causal_conv import PWGLookaheadLaunch
+
+        reason = self.lookahead_unsupported_reason()
+        if reason is not None:
+            raise ValueError(f"{self.__class__.__name__}: {reason}")
+        launches, delay = [], delay_in
+        for i in self._stages:
+            s = self.up_layers[i].x_scale
+            delay, rate = delay * s + s, rate * s
+            launches.append(PWGLookaheadLaunch("stage", self.up_layers[i + 1], rate, delay, 0, [(int(channels), 2)]))
+        return launches, delay, rate
+
+    @torch.no_grad()
+    def lookahead_forward(self, c, walk, frames):
+        """The non-causal ``forward`` on the next chunk of a look-ahead stream (``frames`` mel frames): one delayed
+        launch per stage, state and valid window from ``walk`` (a :class:`layers.causal_conv.PWGLookaheadWalk`)."""
+        for i in self._stages:
+            conv, scale = self.up_layers[i + 1], self.up_layers[i].x_scale
+            _, ((hist_in, hist_out),), valid = walk.take("stage", conv, frames)
+            c = ops.stretch_conv_stream_delayed(c, hist_in, hist_out, conv.weight_tensor().detach(), scale,
+                                                conv.kernel_size[0], self.act, self.slope, valid)
         return c
 
 
@@ -264,3 +303,38 @@ class ConvInUpsampleNetwork(torch.nn.Module):
 
             c = stream_pointwise(self.conv_in, c)
         return self.upsample.stream_forward(c, None if hist_in is None else hist_in[k:], hist_out[k:])
+
+    # ---- the NON-causal network streamed with a fixed look-ahead
+    def _lookahead_desc(self, batch, n):
+        """``conv_in`` (kernel 2 w + 1, no padding, on the replicate-padded mel) in causal form: left padding 2 w."""
+        cv = self.conv_in
+        return ops.make_conv_desc(batch, cv.in_channels, cv.out_channels, n, n, cv.kernel_size, 1, 1, cv.kernel_size - 1, 1,
+                                  transposed=False, pad_mode="zero")
+
+    def lookahead_plan(self):
+        """``conv_in`` (history ``2 w`` frames, output ``w`` frames late), then the stages -> ``(launches, delay, rate)``."""
+        from .causal_conv import PWGLookaheadLaunch
+
+        if self.use_causal_conv:
+            raise ValueError(f"{self.__class__.__name__}: the network is causal (use_causal_conv=True) and streams "
+                             "without look-ahead")
+        cv, w = self.conv_in, self.aux_context_window
+        first = PWGLookaheadLaunch("conv_in", cv, 1, w, 0, [(cv.in_channels, 2 * w)] if w > 0 else [])
+        launches, delay, rate = self.upsample.lookahead_plan(cv.out_channels, w, 1)
+        return [first] + launches, delay, rate
+
+    @torch.no_grad()
+    def lookahead_forward(self, c, walk):
+        """The non-causal ``forward`` on the next frames c (B, C, n) of a look-ahead stream -> (B, C, n * prod(scales)),
+        late by the plan's delay.  The start of a stream replicates the first frame into ``conv_in``'s history (what
+        ``inference()``'s replicate padding gives on the left); the end is the caller's: it feeds copies of the last
+        frame."""
+        from .causal_conv import lookahead_launch
+
+        cv, w, n = self.conv_in, self.aux_context_window, c.shape[-1]
+        _, pairs, valid = walk.take("conv_in", cv, n)
+        hist_in, hist_out = pairs[0] if pairs else (None, None)
+        if pairs and hist_in is None:
+            hist_in = c[:, :, :1].expand(-1, -1, 2 * w).contiguous()
+        c = lookahead_launch(cv, self._lookahead_desc(c.shape[0], n), c, (hist_in, hist_out), valid)
+        return self.upsample.lookahead_forward(c, walk, n)

@@ -7,6 +7,7 @@ import numpy as np
 import torch
 
 from .. import functional as Fn
+from .. import ops
 from ..layers import upsample
 from ..layers.activation import FusedActivation
 from ..layers.conv import Conv1d as _AnyConv1d
@@ -157,6 +158,98 @@ class ParallelWaveGANGenerator(torch.nn.Module, _WeightNormMixin):
                                         skip_scale=math.sqrt(1.0 / n) if i == n - 1 else 1.0, inplace_skips=True)
         x = stream_pointwise(self.last_conv_layers[1], skips, pre_act="relu")
         return stream_pointwise(self.last_conv_layers[3], x, pre_act="relu")
+
+    # ---- streaming the NON-causal generator with a fixed look-ahead (utils.PWGLookaheadStream)
+    def lookahead_unsupported_reason(self, batch=1):
+        """None if the non-causal generator streams with a look-ahead, else the reason (host logic only)."""
+        if any(f.use_causal_conv for f in self.conv_layers):
+            return ("the model is causal (use_causal_conv=True) and streams without look-ahead through utils.PWGStream")
+        if self.upsample_net is None:
+            return "upsample_conditional_features=False: the stream maps mel frames to samples through the upsampler"
+        if not isinstance(self.upsample_net, (upsample.UpsampleNetwork, upsample.ConvInUpsampleNetwork)):
+            return (f"upsample_net={self.upsample_net.__class__.__name__!r} is not built for streams (only UpsampleNetwork "
+                    "and ConvInUpsampleNetwork)")
+        net = self.upsample_net.upsample if isinstance(self.upsample_net, upsample.ConvInUpsampleNetwork) \
+            else self.upsample_net
+        reason = net.lookahead_unsupported_reason()
+        if reason is not None:
+            return "the mel upsampler: " + reason
+        c_delay = 0
+        for f in self.conv_layers:
+            c_delay += f.conv.dilation
+            reason = f.lookahead_unsupported_reason(batch, 8, c_delay)
+            if reason is not None:
+                return f"{f.__class__.__name__}: {reason}"
+        return None
+
+    def lookahead_plan(self):
+        """Every launch of one push of the look-ahead stream, in the order :meth:`lookahead_forward` runs them, as
+        ``PWGLookaheadLaunch(kind, module, rate, delay, c_delay, state)``: output columns per mel frame, delay of the
+        output in columns, how late a gated layer reads the conditioning, and the ``(channels, columns)`` of the state
+        tensors it keeps.  ``conv_in`` (delay ``w`` frames), the upsampling stages (``D * s + s``), the noise line and
+        ``first_conv`` (the conditioning's delay ``D_c``), the conditioning line (``sum d`` columns), the gated layers
+        (``+ d`` each: history ``2 d``, from the second on a skip line of ``d``) and the two last 1 x 1 convolutions.
+        The last launch's delay is the stream's latency in samples.  Pure host logic; ValueError with the reason for a
+        generator that does not stream this way."""
+        from ..layers.causal_conv import PWGLookaheadLaunch as Launch
+
+        reason = self.lookahead_unsupported_reason()
+        if reason is not None:
+            raise ValueError(f"{self.__class__.__name__}: {reason}")
+        if isinstance(self.upsample_net, upsample.ConvInUpsampleNetwork):
+            plan, delay, rate = self.upsample_net.lookahead_plan()
+        else:
+            plan, delay, rate = self.upsample_net.lookahead_plan(self.aux_channels)
+        plan = list(plan)
+        plan.append(Launch("noise", None, rate, delay, 0, [(self.in_channels, delay)] if delay else []))
+        plan.append(Launch("first_conv", self.first_conv, rate, delay, 0, []))
+        reach = sum(f.conv.dilation for f in self.conv_layers)
+        plan.append(Launch("cond_line", None, rate, delay, 0, [(self.aux_channels, reach)]))
+        c_delay = 0
+        for i, f in enumerate(self.conv_layers):
+            d = f.conv.dilation
+            c_delay, delay = c_delay + d, delay + d
+            state = [(f.conv.in_channels, (f.conv.kernel_size - 1) * d)]
+            if i > 0:
+                state.append((f.conv1x1_skip.out_channels, d))
+            plan.append(Launch("layer", f, rate, delay, c_delay, state))
+        for cv in (self.last_conv_layers[1], self.last_conv_layers[3]):
+            plan.append(Launch("last_conv", cv, rate, delay, 0, []))
+        return plan
+
+    @torch.no_grad()
+    def lookahead_forward(self, z, c, walk):
+        """The NON-causal ``forward`` on the next chunk of a look-ahead stream: noise z (B, 1, n * upsample_factor) for the
+        samples of the mel frames c (B, C, n), undelayed -> (B, out_channels, n * upsample_factor), late by the plan's
+        last delay.  ``walk``: a :class:`layers.causal_conv.PWGLookaheadWalk` over :meth:`lookahead_plan`.  Every layer
+        runs in its causal form on a shifted time axis: the noise waits for the conditioning in a delay line, every gated
+        layer reads the conditioning from the shared line at its own delay and the running skip sum through its skip
+        line, and every launch stores zeros outside the utterance.  The last block applies sqrt(1 / layers)."""
+        from ..layers.causal_conv import lookahead_pointwise
+
+        frames = c.shape[-1]
+        if isinstance(self.upsample_net, upsample.ConvInUpsampleNetwork):
+            c = self.upsample_net.lookahead_forward(c, walk)
+        else:
+            c = self.upsample_net.lookahead_forward(c, walk, frames)
+        assert c.size(-1) == z.size(-1)
+        _, pairs, _ = walk.take("noise", None, frames)
+        if pairs:
+            z = ops.delay_line_forward(z, pairs[0][0], pairs[0][1], delayed=True)
+        _, _, valid = walk.take("first_conv", self.first_conv, frames)
+        x = lookahead_pointwise(self.first_conv, z, valid)
+        _, ((c_line, c_line_out),), _ = walk.take("cond_line", None, frames)
+        ops.delay_line_forward(c, c_line, c_line_out)
+        skips, n = None, len(self.conv_layers)
+        for i, f in enumerate(self.conv_layers):
+            launch, pairs, valid = walk.take("layer", f, frames)
+            x, skips = f.lookahead_forward(x, c, c_line, launch.c_delay, pairs[0], skips,
+                                           pairs[1] if i > 0 else (None, None), valid,
+                                           skip_scale=math.sqrt(1.0 / n) if i == n - 1 else 1.0)
+        _, _, valid = walk.take("last_conv", self.last_conv_layers[1], frames)
+        x = lookahead_pointwise(self.last_conv_layers[1], skips, valid, pre_act="relu")
+        _, _, valid = walk.take("last_conv", self.last_conv_layers[3], frames)
+        return lookahead_pointwise(self.last_conv_layers[3], x, valid, pre_act="relu")
 
     @staticmethod
     def _get_receptive_field_size(layers, stacks, kernel_size, dilation=lambda x: 2 ** x):

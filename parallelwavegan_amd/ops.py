@@ -626,6 +626,85 @@ def stretch_conv_stream(x, hist_in, hist_out, w, scale, freq_kernel=1, act=None,
     return y
 
 
+def wavenet_stream_delayed_supported(desc, c_delay=0):
+    """Does the delayed form of the streaming layer (csrc/wavenet_stream.hip; the NON-causal layer in a stream with a
+    fixed look-ahead) cover this geometry with the conditioning read ``c_delay`` columns late?  ``desc`` is the layer's
+    own (``causal == 0``).  Host logic only; ``_lib.lib().pwg_last_error()`` names the reason for a False."""
+    return bool(_lib.lib().pwg_wavenet_stream_delayed_supported(ctypes.byref(desc), int(c_delay)))
+
+
+def wavenet_stream_delayed_hist_floats(desc):
+    """Floats of one history buffer of the layer in delayed form: ``batch * 64 * 2 * dilation`` (0: unsupported)."""
+    return _lib.lib().pwg_wavenet_stream_delayed_hist_floats(ctypes.byref(desc))
+
+
+def wavenet_stream_delayed_forward(desc, x, c, c_line, c_delay, skips, skip_line, hist_in, hist_out, packed, b_dil, b_skip,
+                                   b_out, valid=None):
+    """One chunk of a NON-causal gated residual layer streamed with a fixed look-ahead, in one launch -> (x_out,
+    skips_out), both ``dilation`` columns later than ``x``.  The conditioning of output column ``j`` is column
+    ``j - c_delay`` of ``concat(c_line, c)`` counted from the chunk (``c_line`` (B, 80, L), None: zeros); the skip addend
+    is ``concat(skip_line[0], skips)[j]`` and ``skip_line[1]`` receives the last ``dilation`` columns of that
+    concatenation (``skip_line = (line_in, line_out)``, each (B, 64, dilation); ignored without ``skips``); ``hist_out`` =
+    the last ``2 * dilation`` columns of ``concat(hist_in, x)``.  Columns outside ``valid = (lo, hi)`` (None: all are
+    valid) are stored as exact zeros in both outputs."""
+    line_in, line_out = skip_line if skips is not None else (None, None)
+    _require_device(x, c, c_line, skips, line_in, line_out, hist_in, hist_out, packed, b_dil, b_skip, b_out)
+    assert x.numel() == desc.batch * desc.residual_channels * desc.t, (tuple(x.shape), desc.batch, desc.t)
+    assert c.numel() == desc.batch * desc.aux_channels * desc.t, (tuple(c.shape), desc.batch, desc.t)
+    n_hist = wavenet_stream_delayed_hist_floats(desc)
+    for t in (hist_in, hist_out):
+        assert t is None or n_hist == 0 or t.numel() == n_hist, (tuple(t.shape), n_hist)
+    for t in (line_in, line_out):
+        assert t is None or t.numel() == desc.batch * desc.skip_channels * desc.dilation, tuple(t.shape)
+    assert skips is None or skips.numel() == x.numel()
+    c_cols = 0
+    if c_line is not None:
+        assert c_line.is_contiguous() and c_line.numel() % (desc.batch * desc.aux_channels) == 0, tuple(c_line.shape)
+        c_cols = c_line.numel() // (desc.batch * desc.aux_channels)
+    x_out, skips_out = torch.empty_like(x), torch.empty_like(x)
+    lo, hi = (0, desc.t) if valid is None else valid
+    _lib.check(_lib.lib().pwg_wavenet_stream_delayed_forward(
+        ctypes.byref(desc), _ptr(x), _ptr(c), _ptr(c_line), c_cols, int(c_delay), _ptr(skips), _ptr(line_in), _ptr(line_out),
+        _ptr(hist_in), _ptr(hist_out), _ptr(packed), _ptr(b_dil), _ptr(b_skip), _ptr(b_out), int(lo), int(hi), _ptr(x_out),
+        _ptr(skips_out), _stream()), "wavenet_stream_delayed_forward")
+    return x_out, skips_out
+
+
+def stretch_conv_stream_delayed(x, hist_in, hist_out, w, scale, freq_kernel=1, act=None, slope=0.0, valid=None):
+    """:func:`stretch_conv_stream` for the NON-causal stage streamed with a fixed look-ahead (the causal stage on a time
+    axis shifted by ``scale``): output columns outside ``valid = (lo, hi)`` (None: all are valid) are stored as exact
+    zeros.  One launch."""
+    x = x.contiguous()
+    w = w.reshape(-1).contiguous()
+    _require_device(x, hist_in, hist_out, w)
+    b, ch, n = x.shape
+    assert w.numel() == (2 * scale + 1) * freq_kernel, (w.numel(), scale, freq_kernel)
+    for t in (hist_in, hist_out):
+        assert t is None or t.numel() == b * ch * 2, tuple(t.shape)
+    y = torch.empty((b, ch, n * scale), device=x.device, dtype=torch.float32)
+    lo, hi = (0, n * scale) if valid is None else valid
+    _lib.check(_lib.lib().pwg_stretch_conv_stream_delayed(_ptr(x), _ptr(hist_in), _ptr(hist_out), _ptr(w), _ptr(y), b * ch, n,
+                                                          int(scale), int(freq_kernel), ACT[act], float(slope), int(lo),
+                                                          int(hi), _stream()), "stretch_conv_stream_delayed")
+    return y
+
+
+def delay_line_forward(x, line_in, line_out, delayed=False):
+    """A delay line of a stream: ``line_out`` = the last L columns of ``concat(line_in, x)`` (x (B, C, n), lines
+    (B, C, L), ``line_in`` None: zeros), also when ``n < L``.  ``delayed``: -> the first ``n`` columns of that
+    concatenation (``x``, L columns late), else None.  One launch; copies only."""
+    x = x.contiguous()
+    _require_device(x, line_in, line_out)
+    b, ch, n = x.shape
+    L = line_out.shape[-1]
+    for t in (line_in, line_out):
+        assert t is None or (t.is_contiguous() and tuple(t.shape) == (b, ch, L)), (tuple(t.shape), (b, ch, L))
+    out = torch.empty_like(x) if delayed else None
+    _lib.check(_lib.lib().pwg_delay_line_forward(_ptr(x), _ptr(line_in), _ptr(line_out), _ptr(out), b * ch, n, L, _stream()),
+               "delay_line_forward")
+    return out
+
+
 def wavenet_bf16_supported(desc):
     """Does the bf16-operand one-launch layer (csrc/wavenet_bf16.hip) cover this geometry?  Host logic only (no device
     needed); ``_lib.lib().pwg_last_error()`` names the reason for a False."""

@@ -24,7 +24,8 @@ symmetric filter adds a fixed latency of ``latency_samples`` (32 for the recipe 
 
 ``LookaheadStream`` streams the standard NON-causal HiFi-GAN: every layer runs in its causal form on a shifted time
 axis, so a push of ``n`` frames still costs ``n`` frames of work and every sample leaves a fixed ``latency_samples``
-late (3258 samples, 12.73 frames, for HiFi-GAN V1).
+late (3258 samples, 12.73 frames, for HiFi-GAN V1).  ``PWGLookaheadStream`` does the same for the
+standard NON-causal Parallel WaveGAN (3921 samples, 15.3 frames, for ``parallel_wavegan.v1``).
 """
 import ctypes
 
@@ -715,6 +716,143 @@ class LookaheadStream(_Stream):
         total = self.frames_in
         zeros = torch.zeros((self.batch, self._in_channels, self.latency_frames), device=self._device)
         y = self._run(zeros, self._halves[self._cur], self._halves[1 - self._cur], total, total)
+        y = y[:, max(0, self.latency_samples - total * self.up):self.latency_samples].contiguous()
+        self._flushed = True  # (the halves are not swapped: nothing may follow but reset())
+        self.samples_out += y.shape[1]
+        return y
+
+
+class PWGLookaheadStream(_Stream):
+    """Stateful streaming synthesis for the standard NON-causal ``ParallelWaveGANGenerator`` (every recipe and released
+    checkpoint) with a fixed look-ahead: ``push`` takes the next mel frames of ``batch`` lock-step streams, and
+    optionally the noise for their samples, at ``n`` frames of work, and every sample leaves ``latency_samples`` late
+    (``latency_frames``: the ceiling in frames; 3921 samples = 15.3 frames for ``parallel_wavegan.v1``).  After any push
+    the samples emitted total ``max(0, frames_in * up - latency_samples)``; ``flush()`` returns the tail, after which the
+    emissions total ``frames * up`` samples.  Any partition of the same frames and noise gives bit-identical audio, equal
+    to ``model.inference`` up to fp32 summation order.  fp32 only.
+
+    How: every layer runs in its causal form on a shifted time axis.  ``conv_in`` is ``w`` frames late
+    and starts from its first frame replicated; an upsampling stage of scale ``s`` takes a delay ``D`` to ``D * s + s``;
+    the noise waits in a delay line for the conditioning; a gated layer of dilation ``d`` adds ``d`` columns, takes its
+    residual from the middle tap, reads the conditioning from one shared line at its own delay and the running skip sum
+    through a line of ``d`` columns (csrc/wavenet_stream.hip, the delayed form; one launch per layer); every launch
+    stores exact zeros outside the utterance.  ``model.lookahead_plan()`` lists the launches, delays and state.
+
+    State (``state_bytes``: both ping-pong halves): the layers' histories (``2 d`` columns each), their skip lines, the
+    conditioning line (``sum d`` columns of 80 rows), the noise line and the upsampler's few columns -- about 3.3 MB
+    per half and stream for V1.  ``use_graph``: a push with ``latency_frames`` frames before it replays the two
+    captured graphs of its chunk size, as in :class:`LookaheadStream`; the pushes at the start of an utterance and
+    ``flush()`` run eagerly.  Noise is never drawn inside a graph.  ``close()`` does not flush: an unflushed tail is
+    dropped.
+    """
+
+    warmup_frames = 1
+
+    def __init__(self, model, batch=1, use_graph=True, normalize_before=False):
+        from ..layers.causal_conv import pwg_lookahead_state_shapes
+        from ..layers.conv import each_conv
+        from ..models import HiFiGANGenerator, ParallelWaveGANGenerator
+
+        if not isinstance(model, ParallelWaveGANGenerator):
+            hint = "; the non-causal HiFiGANGenerator streams through utils.LookaheadStream" \
+                if isinstance(model, HiFiGANGenerator) else ""
+            raise ValueError(f"PWGLookaheadStream: {model.__class__.__name__} is not supported (only the non-causal "
+                             f"ParallelWaveGANGenerator{hint})")
+        batch = self._checked_batch(batch)
+        reason = model.lookahead_unsupported_reason(batch)
+        if reason is not None:
+            raise ValueError(f"PWGLookaheadStream: {reason}")
+        if model.in_channels != 1 or model.out_channels != 1:
+            raise ValueError(f"PWGLookaheadStream: in_channels / out_channels = {model.in_channels} / {model.out_channels} "
+                             "(the stream takes one noise row and emits one waveform per stream)")
+        if any(cv.precision != "fp32" for cv in each_conv(model)):
+            raise ValueError("PWGLookaheadStream: the model is in bf16 inference precision; the look-ahead stream of "
+                             "Parallel WaveGAN is fp32 (utils.set_inference_precision(model, 'fp32'))")
+        plan = model.lookahead_plan()
+        self.precision = "fp32"
+        self.up = model.upsample_factor  # samples per frame
+        self._plan = plan
+        self.latency_samples = plan[-1].delay
+        self.latency_frames = -(-self.latency_samples // self.up)
+        super().__init__(model, [], batch, use_graph, normalize_before, pwg_lookahead_state_shapes(plan, batch))
+
+    @staticmethod
+    def latency_samples_of(model):
+        """Samples every output leaves late, from the module geometry alone (no device, no kernel)."""
+        return model.lookahead_plan()[-1].delay
+
+    def reset(self):
+        """Back to start of stream; an unflushed tail is dropped."""
+        self._restart()
+        self._flushed = False
+        self._last = None  # the last frame pushed, (batch, 1, C): the flush replicates it
+
+    def _run(self, feats, z, state_in, state_out, frames_before=None, total_frames=None):
+        """``feats``: (batch, n, C) features; ``z``: (batch, 1, n * up) noise; ``state_in`` (None: start of stream) /
+        ``state_out``: one ping-pong half each; ``frames_before`` None: steady state.  -> (batch, n * up), not trimmed."""
+        from ..layers.causal_conv import PWGLookaheadWalk
+
+        walk = PWGLookaheadWalk(self._plan, state_in, state_out, frames_before, total_frames)
+        return self.model.lookahead_forward(z, self._features(feats), walk).reshape(self.batch, -1)
+
+    def _capture(self, feats, z):
+        static_in, static_z = feats.clone(), z.clone()
+        return static_in, static_z, _capture_directions(self._halves, lambda si, so: self._run(static_in, static_z, si, so))
+
+    @torch.no_grad()
+    def push(self, feats, noise=None):
+        """feats: (n, C) or (batch, n, C) float features; noise: (batch, n * up) or (n * up,) (the same for every
+        stream) for the samples of THESE frames, undelayed, drawn with ``torch.randn`` on the device if omitted ->
+        (batch, samples) fp32, the samples that became complete: ``n * up`` once ``latency_samples`` are behind, fewer
+        (or none) before.  The result is the caller's own tensor."""
+        if self._flushed:
+            raise RuntimeError("PWGLookaheadStream.push: the utterance was flushed; reset() starts the next one")
+        feats = self._coerce(feats)
+        n = feats.shape[1]
+        if noise is not None:
+            noise = torch.as_tensor(noise, dtype=torch.float32).to(self._device)
+            if noise.dim() == 1:
+                noise = noise.unsqueeze(0).expand(self.batch, -1)
+            if tuple(noise.shape) != (self.batch, n * self.up):
+                raise ValueError(f"PWGLookaheadStream.push: expected ({n * self.up},) or ({self.batch}, {n * self.up}) "
+                                 f"noise for {n} frame(s), got {tuple(noise.shape)}")
+            noise = noise.reshape(self.batch, 1, n * self.up).contiguous()
+        if n == 0:
+            return self._empty()
+        before = self.frames_in
+        self.frames_in += n
+        self._last = feats[:, -1:, :].clone()
+        skip = max(0, self.latency_samples - before * self.up)  # columns of this chunk in front of the first sample
+        steady = before >= self.latency_frames                  # every launch's window is full
+
+        def eager(state_in, state_out):
+            z = noise if noise is not None else torch.randn(self.batch, 1, n * self.up, device=self._device)
+            return self._run(feats, z, state_in, state_out, before)[:, skip:].contiguous()
+
+        def capture():
+            return self._capture(feats, torch.zeros(self.batch, 1, n * self.up, device=self._device))
+
+        def fill_static(static_in, static_z):
+            static_in.copy_(feats, non_blocking=True)
+            if noise is None:
+                static_z.normal_()  # (outside the graph: a replay never draws)
+            else:
+                static_z.copy_(noise, non_blocking=True)
+
+        return self._step(n, (n, feats.shape[2]), eager, capture if self.use_graph and steady else None, fill_static)
+
+    @torch.no_grad()
+    def flush(self):
+        """End of the utterance: ``latency_frames`` copies of the last frame (what ``inference()``'s replicate padding
+        gives ``conv_in`` on the right) with zero noise and the end-of-utterance windows (every launch stores zeros past
+        the utterance's last column) -> the last ``min(latency_samples, frames * up)`` samples, (batch, samples).
+        Zero-length before anything was pushed and on a second call.  The next utterance starts with ``reset()``."""
+        if not self._started or self._flushed:
+            return self._empty()
+        total = self.frames_in
+        feats = self._last.expand(-1, self.latency_frames, -1).contiguous()
+        zeros = torch.zeros((self.batch, 1, self.latency_frames * self.up), device=self._device)
+        y = self._run(feats, zeros, self._halves[self._cur], self._halves[1 - self._cur], total, total)
         y = y[:, max(0, self.latency_samples - total * self.up):self.latency_samples].contiguous()
         self._flushed = True  # (the halves are not swapped: nothing may follow but reset())
         self.samples_out += y.shape[1]

@@ -39,7 +39,13 @@ same halo forward of a second instance of the model put in bf16 inference precis
 push, since the whole-utterance forward runs those shapes on the bf16 matrix pipe.  Into
 profiles/stream_lookahead_bf16_infer.json.
 
-usage: python tools/bench_stream.py [--model pwg] [--multiband] [--precision bf16] [--lookahead] [--reps 200]
+``--model pwg --lookahead``: the standard NON-causal Parallel WaveGAN (PWG.v1) through ``utils.PWGLookaheadStream`` (one
+delayed launch per gated layer, csrc/wavenet_stream.hip) against halo recompute, same method: steady-
+state pushes of 4 / 8 / 32 frames at 1 and 16 streams, into profiles/stream_pwg_lookahead_infer.json.  The halo side is
+ONE graph of the whole-utterance forward over ``L + n + L`` frames (plus the context window), ``L`` = the stream's
+latency in frames, rounded up -- the receptive field is symmetric -- on static noise.
+
+usage: python tools/bench_stream.py [--model pwg [--lookahead]] [--multiband] [--precision bf16] [--lookahead] [--reps 200]
                                     [--repeats 3] [--out profiles/stream_infer.json]
 """
 import argparse
@@ -55,7 +61,8 @@ from parallelwavegan_amd import ops  # noqa: E402
 from parallelwavegan_amd.graphs import GraphedInference  # noqa: E402
 from parallelwavegan_amd.layers import PQMF  # noqa: E402
 from parallelwavegan_amd.models import HiFiGANGenerator, MelGANGenerator, ParallelWaveGANGenerator  # noqa: E402
-from parallelwavegan_amd.utils import CausalStream, LookaheadStream, PWGStream, set_inference_precision  # noqa: E402
+from parallelwavegan_amd.utils import (CausalStream, LookaheadStream, PWGLookaheadStream, PWGStream,  # noqa: E402
+                                       set_inference_precision)
 from parallelwavegan_amd.utils.streaming import receptive_field_frames  # noqa: E402
 from tests.golden import synth  # noqa: E402
 
@@ -105,9 +112,10 @@ def build_multiband(dev):
     return g.to(dev).eval()
 
 
-def build_pwg(dev):
-    """Causal Parallel WaveGAN at the PWG.v1 geometry on seeded weights, weight norm removed."""
-    g = ParallelWaveGANGenerator(use_causal_conv=True)
+def build_pwg(dev, causal=True):
+    """Parallel WaveGAN at the PWG.v1 geometry (causal, or the standard non-causal one) on seeded weights, weight norm
+    removed."""
+    g = ParallelWaveGANGenerator(use_causal_conv=causal)
     g.load_state_dict(synth.synth_state_dict(g.state_dict(), seed=14, g_scale=synth.PWG_G_SCALE))
     g.remove_weight_norm()
     return g.to(dev).eval()
@@ -161,11 +169,11 @@ def main():
     ap.add_argument("--lookahead", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    if args.lookahead and (args.model != "default" or args.multiband):
-        ap.error("--lookahead is the non-causal HiFi-GAN stream (no --model, no --multiband)")
+    if args.lookahead and args.multiband:
+        ap.error("--lookahead is the non-causal HiFi-GAN or (--model pwg) Parallel WaveGAN stream (no --multiband)")
     if args.model == "pwg" and (args.multiband or args.precision != "fp32"):
         ap.error("--model pwg is the fp32 full-band Parallel WaveGAN stream (no --multiband, no --precision bf16)")
-    default_out = "stream_lookahead_bf16_infer.json" if args.lookahead and args.precision == "bf16" else "stream_lookahead_infer.json" if args.lookahead else "stream_pwg_infer.json" if args.model == "pwg" else "stream_bf16_infer.json" if args.precision == "bf16" else (
+    default_out = "stream_pwg_lookahead_infer.json" if args.lookahead and args.model == "pwg" else "stream_lookahead_bf16_infer.json" if args.lookahead and args.precision == "bf16" else "stream_lookahead_infer.json" if args.lookahead else "stream_pwg_infer.json" if args.model == "pwg" else "stream_bf16_infer.json" if args.precision == "bf16" else (
         "stream_mb_infer.json" if args.multiband else "stream_infer.json")
     args.out = args.out or os.path.join(ROOT, "profiles", default_out)
     dev = torch.device("cuda:0")
@@ -197,7 +205,9 @@ def main():
         print(json.dumps({"out": args.out, "points": [[p["model"], p["streams"], p["chunk_frames"], p["fp32_push_ms"],
                                                        p["bf16_push_ms"]] for p in rec["points"]]}))
         return
-    if args.lookahead:
+    if args.lookahead and args.model == "pwg":
+        measure_pwg_lookahead(rec, "parallel_wavegan_v1", build_pwg(dev, causal=False), CHUNKS, gen, args, dev)
+    elif args.lookahead:
         measure_lookahead(rec, "hifigan_v1", build_noncausal(dev), CHUNKS, gen, args, dev)
     elif args.model == "pwg":
         measure_pwg(rec, "parallel_wavegan_v1_causal", build_pwg(dev), CHUNKS, gen, args, dev)
@@ -364,6 +374,61 @@ def measure_lookahead(rec, name, model, chunks, gen, args, dev):
             print(json.dumps({k: p[k] for k in ("model", "streams", "chunk_frames", "stream_push_ms", "halo_forward_ms",
                                                 "spread_ms", "speedup_stream_over_halo", "launches_per_push_stream",
                                                 "launches_per_forward_halo")}), file=sys.stderr, flush=True)
+
+
+def measure_pwg_lookahead(rec, name, model, chunks, gen, args, dev):
+    """Steady-state ``PWGLookaheadStream.push`` against the whole-utterance forward over ``L + n + L`` frames, ``L`` the
+    stream's latency in frames, alternating."""
+    up, w = model.upsample_factor, model.aux_context_window
+    probe = PWGLookaheadStream(model, use_graph=False)
+    halo_frames = probe.latency_frames
+    rec["models"][name] = {"workload": "seeded weights, weight norm removed", "halo_left_frames": halo_frames,
+                           "halo_right_frames": halo_frames, "latency_samples": probe.latency_samples,
+                           "latency_frames": probe.latency_frames, "stream_state_bytes_per_stream": probe.state_bytes}
+    for b in STREAMS:
+        for n in chunks:
+            total = 2 * halo_frames + n
+            feats = torch.randn(b, n, 80, generator=gen).to(dev)
+            noise = torch.randn(b, n * up, generator=gen).to(dev)
+            ctx = torch.randn(b, 80, total + 2 * w, generator=gen).to(dev)
+            z_halo = torch.randn(b, 1, total * up, generator=gen).to(dev)
+            whole = lambda c: model(z_halo, c)  # noqa: E731
+            s = PWGLookaheadStream(model, batch=b, use_graph=True)
+            halo = GraphedInference(whole)
+            while s.frames_in < s.latency_frames + 4 * n:  # the eager start, then both graph directions; the halo graph
+                s.push(feats, noise)
+                halo(ctx)
+            t_s, t_h = [], []
+            for _ in range(args.repeats):
+                t_s.append(event_ms(lambda: s.push(feats, noise), args.reps))
+                t_h.append(event_ms(lambda: halo(ctx), args.reps))
+            eager = PWGLookaheadStream(model, batch=b, use_graph=False)
+            while eager.frames_in < eager.latency_frames:  # past the partial windows
+                eager.push(feats, noise)
+            n_s, fam_s = launches(lambda: eager.push(feats, noise))
+            n_h, fam_h = launches(lambda: whole(ctx))
+            with ops.profile() as prof:  # the layer launches of a push, by the library's own event scope
+                for _ in range(10):
+                    eager.push(feats, noise)
+            r = prof.results["wavenet_stream_delayed_kernel"]
+            med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+            spread = max(max(t_s) - min(t_s), max(t_h) - min(t_h))
+            p = {"model": name, "streams": b, "chunk_frames": n, "samples_per_push": b * n * up,
+                 "stream_push_ms": round(med(t_s), 4), "stream_runs_ms": [round(t, 4) for t in t_s],
+                 "halo_forward_ms": round(med(t_h), 4), "halo_runs_ms": [round(t, 4) for t in t_h],
+                 "halo_frames_computed": total, "arithmetic_ratio_halo_over_stream": round(total / n, 2),
+                 "spread_ms": round(spread, 4), "speedup_stream_over_halo": round(med(t_h) / med(t_s), 3),
+                 "stream_not_slower_beyond_spread": med(t_s) <= med(t_h) + spread,
+                 "stream_faster_beyond_spread": med(t_s) + spread < med(t_h),
+                 "real_time_factor_22050Hz": round(n * up / 22050.0 / (med(t_s) / 1e3), 1),
+                 "launches_per_push_stream": n_s, "launches_per_forward_halo": n_h,
+                 "layer_launch_ms": round(r["ms"] / r["launches"], 5),
+                 "stream_kernels": fam_s, "halo_kernels": fam_h}
+            rec["points"].append(p)
+            print(json.dumps({k: p[k] for k in ("model", "streams", "chunk_frames", "stream_push_ms", "halo_forward_ms",
+                                                "spread_ms", "speedup_stream_over_halo", "launches_per_push_stream",
+                                                "launches_per_forward_halo", "layer_launch_ms")}), file=sys.stderr,
+                  flush=True)
 
 
 def measure_lookahead_precision(rec, name, model, model16, chunks, gen, args, dev):
