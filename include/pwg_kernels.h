@@ -591,6 +591,36 @@ int pwg_wavenet_bf16_layer_forward_cfg(const pwg_wavenet_desc* d, const float* x
                                        const void* packed, const float* b_dil, const float* b_skip, const float* b_out,
                                        float* x_out, float* skips_out, float* z_out, float* g_out, int32_t mfma_shape,
                                        void* stream);
+/* ---- the two streaming forms of the layer with bf16 operands (opt-in; csrc/wavenet_stream_bf16.hip) ----
+ * pwg_wavenet_stream_forward and pwg_wavenet_stream_delayed_forward computed the way pwg_wavenet_bf16_layer_forward
+ * computes: the windows of x and c (history, conditioning line and chunk alike) are rounded to bf16 while they are
+ * staged, `packed` is the pwg_wavenet_bf16_pack_weights image (its K order tap 0, 1, 2, aux does not depend on
+ * causality; the packer refuses a causal descriptor, so pack through a non-causal one of the same channels), products
+ * are accumulated in fp32 on the 32x32x16 bf16 MFMA, the gate is fp32 and rounded to bf16; biases, the residual (the
+ * fp32 value re-read from memory: x[n], or concat(hist_in, x)[n - d] in the delayed form), the skip addend, scales,
+ * tensors, history and lines are fp32.  hist_out and skip_line_out are the raw fp32 columns the fp32 launches write,
+ * bit for bit, so the state of a stream does not depend on its precision.
+ * Arguments: those of the fp32 entries in the same order, then z_out (batch, 128, n) / g_out (batch, 64, n) (both or
+ * neither, NULL in normal use: the fp32 z and the bf16-rounded g, stored as fp32, for stage tests).  Geometry, pointer,
+ * aliasing and 32-bit-offset rules are those of the fp32 forms, refused with the same words in pwg_last_error; the
+ * *_supported entries are pure host logic; history sizes are pwg_wavenet_stream_hist_floats and
+ * pwg_wavenet_stream_delayed_hist_floats.  The sum order of an output element is that of pwg_wavenet_bf16_layer_forward
+ * and depends on the layer alone (not on n, the batch, the chunk's position, c_delay, its alignment, or which staging
+ * path a window took): any partition of a stream gives bit-identical results, and the delayed launch over a whole
+ * utterance gives the bits of pwg_wavenet_bf16_layer_forward.  Inference only.
+ * These four symbols are purely additive -- no existing signature or behaviour changes -- so pwg_abi_version() stays 15. */
+int pwg_wavenet_stream_bf16_supported(const pwg_wavenet_desc* d);
+int pwg_wavenet_stream_bf16_forward(const pwg_wavenet_desc* d, const float* x, const float* c, const float* skips,
+                                    const float* hist_in, float* hist_out, const void* packed, const float* b_dil,
+                                    const float* b_skip, const float* b_out, float* x_out, float* skips_out, float* z_out,
+                                    float* g_out, void* stream);
+int pwg_wavenet_stream_bf16_delayed_supported(const pwg_wavenet_desc* d, int32_t c_delay);
+int pwg_wavenet_stream_bf16_delayed_forward(const pwg_wavenet_desc* d, const float* x, const float* c, const float* c_line,
+                                            int32_t c_cols, int32_t c_delay, const float* skips, const float* skip_line_in,
+                                            float* skip_line_out, const float* hist_in, float* hist_out, const void* packed,
+                                            const float* b_dil, const float* b_skip, const float* b_out, int32_t valid_lo,
+                                            int32_t valid_hi, float* x_out, float* skips_out, float* z_out, float* g_out,
+                                            void* stream);
 /* Data path of the layer's backward pass in two launches (the weight gradients use pwg_conv1d_backward_weight*):
  *   gate_backward: dz (batch, 128, t) = d loss / d z from dx_out, ds_out (gradients w.r.t. x_out / skips_out; dx_out
  *     may be NULL) and the saved z -- the two 1x1 data gradients (K = 128), the out_mul / skip_mul scales and the

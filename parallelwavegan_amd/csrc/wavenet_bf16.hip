@@ -26,29 +26,13 @@
 // pwg_wavenet_bf16_layer_forward_cfg selects.  Deterministic: one workgroup owns its output tile over the whole
 // reduction, no split-K, no atomics.
 #include "common.h"
-#include "bf16_mfma.h"
+#include "wavenet_bf16.h"
 
 #include <stdint.h>
 
 namespace pwg {
 namespace {
 
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));  // 16-B load at a 4-B aligned address
-
-constexpr int BR = 64;                  // residual channels
-constexpr int BG = 128;                 // gate channels
-constexpr int BS = 64;                  // skip channels
-constexpr int BA = 80;                  // aux channels
-constexpr int BK = 3;                   // taps
-constexpr int BCOLS = 64;               // columns per workgroup
-constexpr int K1 = 288;                 // phase-1 reduction: 3 * 64 + 80 = 272, padded to 32-channel chunks
-constexpr int OCT1 = K1 / 8;            // 36 channel octets per column
-constexpr int K2 = BR;                  // phase-2 reduction: the 64 gate outputs
-constexpr int RS = K1 + 8;              // bf16 per column of the operand tile (592 B = 37 x 16 B)
-constexpr int RG = K2 + 8;              // bf16 per column of the gate tile (144 B = 9 x 16 B)
-constexpr size_t kLds = (size_t)BCOLS * (RS + RG) * sizeof(__bf16) + (BG + BS + BR) * sizeof(float);
-constexpr int RING = 4;                 // phase-1 weight fragments in flight (k-steps)
 constexpr int kDefaultMfmaShape = 32;  // by wall time at the PWG.v1 shapes
 
 struct WbArgs {
@@ -67,15 +51,6 @@ struct WbArgs {
   int T, dil;
   float out_mul, skip_mul;
 };
-
-// tanh(t) * sigmoid(s) on the hardware exp2 / rcp: the form of wavenet.hip (gate_fast), so that the fp32 gate of the
-// two kernels is the same function
-__device__ __forceinline__ float gate_fp32(float t, float s) {
-  const float L2E = 1.4426950408889634f;
-  const float sg = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-s * L2E));
-  const float th = 2.f * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-2.f * L2E * t)) - 1.f;
-  return th * sg;
-}
 
 // TILE: MFMA shape (32: 32x32x16, 16: 16x16x32).  A wave owns a 32 x 32 block of each half: TM x TN MFMA tiles.
 template <int TILE>

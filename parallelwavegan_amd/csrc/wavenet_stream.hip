@@ -57,6 +57,7 @@
 // fp32 value through the DMA pass and through registers; the addend is the same value from the line and from the chunk).
 #include "stream_common.h"
 #include "wavenet_gate.h"
+#include "wavenet_stream.h"
 
 #include <stdint.h>
 
@@ -346,8 +347,12 @@ __global__ __launch_bounds__(256, 2) void wavenet_stream_kernel(ARGS a) {
   }
 }
 
-// delayed: the look-ahead form, whose descriptor is the non-causal layer's own
-static int wavenet_stream_geometry(const pwg_wavenet_desc* d, bool delayed = false) {
+}  // namespace
+
+static bool aligned(const void* p, unsigned m) { return (reinterpret_cast<uintptr_t>(p) & m) == 0; }
+
+// ---- the host rules of both precisions (wavenet_stream.h)
+int wavenet_stream_geometry(const pwg_wavenet_desc* d, bool delayed) {
   PWG_REQUIRE(d != nullptr, PWG_ERR_NULL, "wavenet_stream: NULL descriptor");
   if (delayed)
     PWG_REQUIRE(!d->causal, PWG_ERR_UNSUPPORTED,
@@ -372,8 +377,7 @@ static int wavenet_stream_geometry(const pwg_wavenet_desc* d, bool delayed = fal
   return PWG_OK;
 }
 
-// What the delayed form adds to it: the aux window starts c_delay columns early, inside a line of at least as many
-static int wavenet_delayed_geometry(const pwg_wavenet_desc* d, int32_t c_delay) {
+int wavenet_delayed_geometry(const pwg_wavenet_desc* d, int32_t c_delay) {
   const int rc = wavenet_stream_geometry(d, true);
   if (rc != PWG_OK) return rc;
   PWG_REQUIRE(c_delay >= 0, PWG_ERR_BAD_SHAPE, "wavenet_stream_delayed: c_delay = %d is negative", c_delay);
@@ -382,18 +386,42 @@ static int wavenet_delayed_geometry(const pwg_wavenet_desc* d, int32_t c_delay) 
   return PWG_OK;
 }
 
-static bool aligned(const void* p, unsigned m) { return (reinterpret_cast<uintptr_t>(p) & m) == 0; }
-
-// The pointer rules and argument fields the two forms share
-static int wavenet_stream_fill(const char* name, WnStreamArgs* a, const pwg_wavenet_desc* d, const float* x, const float* c,
-                               const float* skips, const float* hist_in, float* hist_out, const float* packed,
-                               const float* b_dil, const float* b_skip, const float* b_out, float* x_out, float* skips_out) {
+int wavenet_stream_pointers(const char* name, const float* x, const float* c, const float* hist_in, const float* hist_out,
+                            const void* packed, const float* x_out, const float* skips_out) {
   PWG_REQUIRE(x && c && packed && x_out && skips_out && hist_out, PWG_ERR_NULL, "%s: NULL pointer", name);
   PWG_REQUIRE(hist_in != hist_out, PWG_ERR_BAD_SHAPE,
               "%s: hist_in and hist_out must be distinct buffers (other workgroups read the history)", name);
   PWG_REQUIRE(x != x_out, PWG_ERR_BAD_SHAPE, "%s: x_out must not alias x (tiles read their neighbours' samples)", name);
   PWG_REQUIRE(aligned(x, 3) && aligned(c, 3) && aligned(hist_in, 3) && aligned(hist_out, 3) && aligned(packed, 15),
               PWG_ERR_BAD_SHAPE, "%s: unaligned tensor (4 B; the weight image 16 B)", name);
+  return PWG_OK;
+}
+
+int wavenet_delayed_pointers(const char* name, const pwg_wavenet_desc* d, const float* c_line, int32_t c_cols,
+                             int32_t c_delay, const float* skips, const float* skip_line_in, const float* skip_line_out,
+                             const float* skips_out) {
+  PWG_REQUIRE(c_line == nullptr || (c_cols >= c_delay && (long)WS_AUX * c_cols * 4 < (1L << 31)), PWG_ERR_BAD_SHAPE,
+              "%s: a conditioning line of %d columns cannot serve c_delay = %d (c_delay .. 2^31 bytes per item)", name,
+              c_cols, c_delay);
+  PWG_REQUIRE(skips == nullptr || skip_line_out != nullptr, PWG_ERR_NULL,
+              "%s: skips needs skip_line_out (the layer keeps %d columns of the skip sum)", name, d->dilation);
+  PWG_REQUIRE(skips == nullptr || skip_line_in != skip_line_out, PWG_ERR_BAD_SHAPE,
+              "%s: skip_line_in and skip_line_out must be distinct buffers (other workgroups read the line)", name);
+  PWG_REQUIRE(skips == nullptr || skips != skips_out, PWG_ERR_BAD_SHAPE,
+              "%s: skips_out must not alias skips (tiles read their neighbours' skip columns)", name);
+  PWG_REQUIRE(aligned(c_line, 3) && aligned(skips, 3) && aligned(skip_line_in, 3) && aligned(skip_line_out, 3),
+              PWG_ERR_BAD_SHAPE, "%s: unaligned tensor (4 B)", name);
+  return PWG_OK;
+}
+
+namespace {
+
+// The argument fields the two forms share, behind the pointer rules
+static int wavenet_stream_fill(const char* name, WnStreamArgs* a, const pwg_wavenet_desc* d, const float* x, const float* c,
+                               const float* skips, const float* hist_in, float* hist_out, const float* packed,
+                               const float* b_dil, const float* b_skip, const float* b_out, float* x_out, float* skips_out) {
+  const int rc = wavenet_stream_pointers(name, x, c, hist_in, hist_out, packed, x_out, skips_out);
+  if (rc != PWG_OK) return rc;
   a->x = x;
   a->c = c;
   a->skips = skips;
@@ -484,17 +512,8 @@ extern "C" int pwg_wavenet_stream_delayed_forward(const pwg_wavenet_desc* d, con
   const char* name = "wavenet_stream_delayed_forward";
   int rc = wavenet_delayed_geometry(d, c_delay);
   if (rc != PWG_OK) return rc;
-  PWG_REQUIRE(c_line == nullptr || (c_cols >= c_delay && (long)WS_AUX * c_cols * 4 < (1L << 31)), PWG_ERR_BAD_SHAPE,
-              "%s: a conditioning line of %d columns cannot serve c_delay = %d (c_delay .. 2^31 bytes per item)", name,
-              c_cols, c_delay);
-  PWG_REQUIRE(skips == nullptr || skip_line_out != nullptr, PWG_ERR_NULL,
-              "%s: skips needs skip_line_out (the layer keeps %d columns of the skip sum)", name, d->dilation);
-  PWG_REQUIRE(skips == nullptr || skip_line_in != skip_line_out, PWG_ERR_BAD_SHAPE,
-              "%s: skip_line_in and skip_line_out must be distinct buffers (other workgroups read the line)", name);
-  PWG_REQUIRE(skips == nullptr || skips != skips_out, PWG_ERR_BAD_SHAPE,
-              "%s: skips_out must not alias skips (tiles read their neighbours' skip columns)", name);
-  PWG_REQUIRE(aligned(c_line, 3) && aligned(skips, 3) && aligned(skip_line_in, 3) && aligned(skip_line_out, 3),
-              PWG_ERR_BAD_SHAPE, "%s: unaligned tensor (4 B)", name);
+  rc = wavenet_delayed_pointers(name, d, c_line, c_cols, c_delay, skips, skip_line_in, skip_line_out, skips_out);
+  if (rc != PWG_OK) return rc;
   WnDelayedArgs a;
   rc = wavenet_stream_fill(name, &a, d, x, c, skips, hist_in, hist_out, packed, b_dil, b_skip, b_out, x_out, skips_out);
   if (rc != PWG_OK) return rc;

@@ -98,10 +98,8 @@ def stream_pointwise(cv, x, precision="fp32", **fused):
     reduction split does.  ``precision`` as in :meth:`CausalConv1d.stream_forward`."""
     if cv.kernel_size != 1 or cv.padding != 0 or cv.padding_right != 0:
         raise ValueError("stream_pointwise: not an unpadded 1 x 1 convolution")
-    n = x.shape[-1]
-    desc = ops.make_conv_desc(x.shape[0], cv.in_channels, cv.out_channels, n, n, 1, cv.stride, 1, 0, cv.groups,
-                              transposed=False, pad_mode="zero", **_desc_kw(fused))
-    return _stream_forward(cv, desc, x, None, None, fused, precision)
+    return _stream_forward(cv, pointwise_desc(cv, x.shape[0], x.shape[-1], **_desc_kw(fused)), x, None, None, fused,
+                           precision)
 
 
 def stream_history_pairs(layers, hist_in, hist_out):
@@ -279,41 +277,60 @@ def pwg_lookahead_state_shapes(plan, batch):
     return [(batch, ch, cols) for launch in plan for ch, cols in launch.state]
 
 
-def lookahead_launch(cv, desc, x, hist=(None, None), valid=None):
-    """One fp32 delayed launch of ``cv`` under ``desc`` without addends: the history pair and the valid window are the
-    caller's (``conv_in`` and the 1 x 1 convolutions of the Parallel WaveGAN look-ahead stream).  A module in bf16 mode
-    and a layer the kernel does not cover are errors, by the rule of :meth:`LookaheadWalk.run`."""
-    if cv.precision != "fp32":
+def lookahead_launch(cv, desc, x, hist=(None, None), valid=None, precision="fp32"):
+    """One delayed launch of ``cv`` under ``desc`` without addends: the history pair and the valid window are the
+    caller's (``conv_in`` and the 1 x 1 convolutions of the Parallel WaveGAN look-ahead stream).  ``precision``, a module
+    in bf16 mode and a layer the kernel does not cover: by the rule of :meth:`LookaheadWalk.run`."""
+    if precision not in ("fp32", "bf16"):
+        raise ValueError(f"stream precision must be 'fp32' or 'bf16', got {precision!r}")
+    bf16 = precision == "bf16"
+    if not bf16 and cv.precision != "fp32":
         raise RuntimeError(f"{cv.__class__.__name__} is in {cv.precision} inference precision: the look-ahead stream is "
-                           "fp32 (utils.set_inference_precision(model, 'fp32'))")
-    if not ops.conv1d_stream_delayed_supported(desc):
+                           "fp32 (utils.set_inference_precision(model, 'fp32'), or pass precision='bf16' to stream with "
+                           "bf16 operands)")
+    if bf16:
+        kernel, supported, forward = "delayed bf16 streaming kernel", ops.conv1d_stream_bf16_delayed_supported, \
+            ops.conv1d_stream_delayed_forward_bf16
+    else:
+        kernel, supported, forward = "delayed streaming kernel", ops.conv1d_stream_delayed_supported, \
+            ops.conv1d_stream_delayed_forward
+    if not supported(desc):
         from .. import _lib
 
-        raise RuntimeError("the delayed streaming kernel does not cover this layer: "
+        raise RuntimeError(f"the {kernel} does not cover this layer: "
                            + _lib.lib().pwg_last_error().decode(errors="replace"))
     with torch.no_grad():
-        return ops.conv1d_stream_delayed_forward(desc, x.contiguous(), hist[0], hist[1], cv.packed_weight(),
-                                                 None if cv.bias is None else cv.bias.detach(), valid=valid)
+        image = cv.packed_weight_bf16() if bf16 else cv.packed_weight()
+        return forward(desc, x.contiguous(), hist[0], hist[1], image, None if cv.bias is None else cv.bias.detach(),
+                       valid=valid)
 
 
-def lookahead_pointwise(cv, x, valid, **fused):
+def pointwise_desc(cv, batch, n, **fused):
+    """Descriptor of an unpadded 1 x 1 ``Conv1d`` on ``n`` columns of a stream (no history)."""
+    return ops.make_conv_desc(batch, cv.in_channels, cv.out_channels, n, n, 1, cv.stride, 1, 0, cv.groups,
+                              transposed=False, pad_mode="zero", **fused)
+
+
+def lookahead_pointwise(cv, x, valid, precision="fp32", **fused):
     """A 1 x 1 ``Conv1d`` on the next columns of a look-ahead stream: :func:`stream_pointwise` with a valid window, which
     keeps the bias out of the padding."""
     if cv.kernel_size != 1 or cv.padding != 0 or cv.padding_right != 0:
         raise ValueError("lookahead_pointwise: not an unpadded 1 x 1 convolution")
-    n = x.shape[-1]
-    desc = ops.make_conv_desc(x.shape[0], cv.in_channels, cv.out_channels, n, n, 1, cv.stride, 1, 0, cv.groups,
-                              transposed=False, pad_mode="zero", **fused)
-    return lookahead_launch(cv, desc, x, valid=valid)
+    return lookahead_launch(cv, pointwise_desc(cv, x.shape[0], x.shape[-1], **fused), x, valid=valid, precision=precision)
 
 
 class PWGLookaheadWalk:
     """One push through the launches of ``ParallelWaveGANGenerator.lookahead_plan()``: hands every launch its state
     pairs and its valid window (the arithmetic of :func:`lookahead_window`, as :class:`LookaheadWalk`).  ``state_in``
     (None: start of stream, every state reads as zeros) / ``state_out``: one ping-pong half each, of
-    :func:`pwg_lookahead_state_shapes`; ``frames_before`` / ``total_frames`` as in :class:`LookaheadWalk`."""
+    :func:`pwg_lookahead_state_shapes`; ``frames_before`` / ``total_frames`` as in :class:`LookaheadWalk`.
+    ``precision="bf16"``: the model runs every convolution and gated layer of the push with bf16 operands (DESIGN.md
+    s11.7); the state tensors are the same raw fp32 in either precision."""
 
-    def __init__(self, plan, state_in, state_out, frames_before=None, total_frames=None):
+    def __init__(self, plan, state_in, state_out, frames_before=None, total_frames=None, precision="fp32"):
+        if precision not in ("fp32", "bf16"):
+            raise ValueError(f"PWGLookaheadWalk: precision must be 'fp32' or 'bf16', got {precision!r}")
+        self.precision = precision
         self._plan = iter(plan)
         self._in = None if state_in is None else iter(state_in)
         self._out = iter(state_out)

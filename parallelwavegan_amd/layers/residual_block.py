@@ -182,16 +182,18 @@ class WaveNetResidualBlock(torch.nn.Module):
         """Descriptor of one push of ``n`` columns through the streaming layer kernel."""
         return self.fused_desc(batch, n, skip_scale)
 
-    def stream_unsupported_reason(self, batch=1, n=1):
-        """None if the streaming layer kernel covers this block at (batch, n), else the reason it does not (host
-        logic only).  A non-causal block is not a geometry question: ``stream_forward`` raises ValueError for it."""
+    def stream_unsupported_reason(self, batch=1, n=1, precision="fp32"):
+        """None if the streaming layer kernel of ``precision`` covers this block at (batch, n), else the reason it does
+        not (host logic only).  A non-causal block is not a geometry question: ``stream_forward`` raises ValueError for
+        it."""
         if self.conv1x1_aux is None:
             return "the block has no aux (conditioning) convolution"
         if any(cv.has_spectral_norm or cv.pad_mode != "zero" for cv in self.fused_convs()):
             return "spectral norm or non-zero padding"
         if self.conv1x1_out.out_channels != self.conv.in_channels:
             return "out channels differ from the residual channels"
-        if not ops.wavenet_stream_supported(self.stream_desc(batch, n)):
+        supported = ops.wavenet_stream_bf16_supported if precision == "bf16" else ops.wavenet_stream_supported
+        if not supported(self.stream_desc(batch, n)):
             return _lib.lib().pwg_last_error().decode(errors="replace")
         return None
 
@@ -206,16 +208,39 @@ class WaveNetResidualBlock(torch.nn.Module):
 
         return group_image(self, "_stream_img", self.fused_convs(), pack)
 
-    def stream_forward(self, x, c, hist_in, hist_out, skips=None, skip_scale=1.0, inplace_skips=False):
+    def stream_image_bf16(self):
+        """The layer's bf16 weight image for the bf16 streaming kernel (csrc/wavenet_stream_bf16.hip): the image of
+        ``fused_image_bf16`` -- its K order (tap 0, 1, 2, aux) does not depend on causality -- packed through a
+        non-causal descriptor of the same channels, as ``stream_image`` is; cached under a key of its own."""
+        def pack(*ws):
+            d = self.fused_desc(1, 64)
+            d.causal = 0
+            return ops.wavenet_bf16_pack_weights(d, *ws)
+
+        return group_image(self, "_stream_bf16_img", self.fused_convs(), pack)
+
+    def _stream_precision(self, precision):
+        """The precision of a stream call, by the rule of ``layers.causal_conv._stream_forward``: a bf16 call neither
+        reads nor writes the modules' own ``precision`` attributes (whole-utterance mode); an fp32 call refuses a block
+        in bf16 mode."""
+        if precision not in ("fp32", "bf16"):
+            raise ValueError(f"stream precision must be 'fp32' or 'bf16', got {precision!r}")
+        if precision == "fp32" and any(cv is not None and cv.precision != "fp32" for cv in self.fused_convs()):
+            raise RuntimeError("WaveNetResidualBlock is in bf16 inference precision: the fp32 streaming layer kernel does "
+                               "not read that mode (utils.set_inference_precision(model, 'fp32'), or pass "
+                               "precision='bf16' to stream with bf16 operands)")
+        return precision == "bf16"
+
+    def stream_forward(self, x, c, hist_in, hist_out, skips=None, skip_scale=1.0, inplace_skips=False, precision="fp32"):
         """The causal block on the next ``x.shape[-1]`` columns of a stream whose previous columns are ``hist_in`` (None:
         start of stream, zero left context) -> (x_out, skips + s); also writes ``hist_out`` (a buffer distinct from
-        ``hist_in``).  One launch; fp32 only.  ``inplace_skips``: the new running sum is written into ``skips``."""
+        ``hist_in``).  One launch.  ``inplace_skips``: the new running sum is written into ``skips``.
+        ``precision="bf16"``: the same launch with bf16 operands (csrc/wavenet_stream_bf16.hip) on the block's bf16
+        image; the history stays raw fp32, so the state of a stream does not depend on its precision."""
         if not self.use_causal_conv:
             raise ValueError("WaveNetResidualBlock: streaming needs use_causal_conv=True")
-        if any(cv is not None and cv.precision != "fp32" for cv in self.fused_convs()):
-            raise RuntimeError("WaveNetResidualBlock is in bf16 inference precision: the streaming layer kernel is fp32 "
-                               "(utils.set_inference_precision(model, 'fp32'))")
-        reason = self.stream_unsupported_reason(x.shape[0], x.shape[-1]) if x.dim() == 3 else "x is not (B, C, n)"
+        bf16 = self._stream_precision(precision)
+        reason = self.stream_unsupported_reason(x.shape[0], x.shape[-1], precision) if x.dim() == 3 else "x is not (B, C, n)"
         if reason is None and self.dropout > 0.0 and self.training:
             reason = "dropout in training mode"
         if reason is not None:
@@ -223,40 +248,43 @@ class WaveNetResidualBlock(torch.nn.Module):
         with torch.no_grad():
             b_d, b_s, b_o = (None if cv.bias is None else cv.bias.detach()
                              for cv in (self.conv, self.conv1x1_skip, self.conv1x1_out))
-            return ops.wavenet_stream_forward(self.stream_desc(x.shape[0], x.shape[-1], skip_scale), x.contiguous(),
-                                              c.contiguous(), skips, hist_in, hist_out, self.stream_image(), b_d, b_s, b_o,
-                                              skips_out=skips if (inplace_skips and skips is not None) else None)
+            forward = ops.wavenet_stream_forward_bf16 if bf16 else ops.wavenet_stream_forward
+            return forward(self.stream_desc(x.shape[0], x.shape[-1], skip_scale), x.contiguous(), c.contiguous(), skips,
+                           hist_in, hist_out, self.stream_image_bf16() if bf16 else self.stream_image(), b_d, b_s, b_o,
+                           skips_out=skips if (inplace_skips and skips is not None) else None)
 
     # ---- the NON-causal block streamed with a fixed look-ahead (csrc/wavenet_stream.hip, the delayed form; DESIGN.md
     # s11.6): the causal launch on a time axis shifted by the dilation
-    def lookahead_unsupported_reason(self, batch=1, n=1, c_delay=0):
-        """None if the delayed form of the streaming layer kernel covers this non-causal block at (batch, n) with the
-        conditioning read ``c_delay`` columns late, else the reason it does not (host logic only).  A causal block is
-        not a geometry question: ``lookahead_forward`` raises ValueError for it."""
+    def lookahead_unsupported_reason(self, batch=1, n=1, c_delay=0, precision="fp32"):
+        """None if the delayed form of the streaming layer kernel of ``precision`` covers this non-causal block at
+        (batch, n) with the conditioning read ``c_delay`` columns late, else the reason it does not (host logic only).
+        A causal block is not a geometry question: ``lookahead_forward`` raises ValueError for it."""
         if self.conv1x1_aux is None:
             return "the block has no aux (conditioning) convolution"
         if any(cv.has_spectral_norm or cv.pad_mode != "zero" for cv in self.fused_convs()):
             return "spectral norm or non-zero padding"
         if self.conv1x1_out.out_channels != self.conv.in_channels:
             return "out channels differ from the residual channels"
-        if not ops.wavenet_stream_delayed_supported(self.fused_desc(batch, n), c_delay):
+        supported = ops.wavenet_stream_delayed_bf16_supported if precision == "bf16" else \
+            ops.wavenet_stream_delayed_supported
+        if not supported(self.fused_desc(batch, n), c_delay):
             return _lib.lib().pwg_last_error().decode(errors="replace")
         return None
 
     def lookahead_forward(self, x, c, c_line, c_delay, hist, skips=None, skip_line=(None, None), valid=None,
-                          skip_scale=1.0):
+                          skip_scale=1.0, precision="fp32"):
         """The non-causal block on the next ``x.shape[-1]`` columns of a look-ahead stream -> (x_out, skips + s), both
         ``dilation`` columns later than ``x``.  ``hist = (hist_in, hist_out)``: the last ``2 * dilation`` columns of the
         block's input (``hist_in`` None: start of stream); the conditioning is read ``c_delay`` columns late from
         ``concat(c_line, c)``; the running skip sum goes through ``skip_line = (line_in, line_out)`` of ``dilation``
-        columns; columns outside ``valid = (lo, hi)`` are stored as zeros.  One launch; fp32 only."""
+        columns; columns outside ``valid = (lo, hi)`` are stored as zeros.  One launch.  ``precision="bf16"``: the same
+        launch with bf16 operands (csrc/wavenet_stream_bf16.hip); history and lines stay raw fp32."""
         if self.use_causal_conv:
             raise ValueError("WaveNetResidualBlock: a causal block streams without look-ahead (stream_forward, "
                              "utils.PWGStream)")
-        if any(cv is not None and cv.precision != "fp32" for cv in self.fused_convs()):
-            raise RuntimeError("WaveNetResidualBlock is in bf16 inference precision: the streaming layer kernel is fp32 "
-                               "(utils.set_inference_precision(model, 'fp32'))")
-        reason = self.lookahead_unsupported_reason(x.shape[0], x.shape[-1], c_delay) if x.dim() == 3 else "x is not (B, C, n)"
+        bf16 = self._stream_precision(precision)
+        reason = self.lookahead_unsupported_reason(x.shape[0], x.shape[-1], c_delay, precision) if x.dim() == 3 \
+            else "x is not (B, C, n)"
         if reason is None and self.dropout > 0.0 and self.training:
             reason = "dropout in training mode"
         if reason is not None:
@@ -264,9 +292,10 @@ class WaveNetResidualBlock(torch.nn.Module):
         with torch.no_grad():
             b_d, b_s, b_o = (None if cv.bias is None else cv.bias.detach()
                              for cv in (self.conv, self.conv1x1_skip, self.conv1x1_out))
-            return ops.wavenet_stream_delayed_forward(self.fused_desc(x.shape[0], x.shape[-1], skip_scale), x.contiguous(),
-                                                      c.contiguous(), c_line, c_delay, skips, skip_line, hist[0], hist[1],
-                                                      self.stream_image(), b_d, b_s, b_o, valid)
+            forward = ops.wavenet_stream_delayed_forward_bf16 if bf16 else ops.wavenet_stream_delayed_forward
+            return forward(self.fused_desc(x.shape[0], x.shape[-1], skip_scale), x.contiguous(), c.contiguous(), c_line,
+                           c_delay, skips, skip_line, hist[0], hist[1],
+                           self.stream_image_bf16() if bf16 else self.stream_image(), b_d, b_s, b_o, valid)
 
     def forward(self, x, c, skips=None, skip_scale=1.0, chain_aux=False, inplace_skips=False):
         """Returns (x_out, skips + s) -- the running skip sum is an addend of the skip conv's epilogue

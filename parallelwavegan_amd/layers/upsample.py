@@ -247,10 +247,10 @@ class ConvInStream:
     def history_columns_at_start(self):
         return 1
 
-    def stream_forward(self, c, hist_in, hist_out):
+    def stream_forward(self, c, hist_in, hist_out, precision="fp32"):
         from .causal_conv import _stream_forward
 
-        return _stream_forward(self.conv, self.stream_desc(c.shape[0], c.shape[-1]), c, hist_in, hist_out, {})
+        return _stream_forward(self.conv, self.stream_desc(c.shape[0], c.shape[-1]), c, hist_in, hist_out, {}, precision)
 
     def __repr__(self):
         return f"ConvInStream({self.conv})"
@@ -288,20 +288,20 @@ class ConvInUpsampleNetwork(torch.nn.Module):
         return stages
 
     @torch.no_grad()
-    def stream_forward(self, c, hist_in, hist_out):
+    def stream_forward(self, c, hist_in, hist_out, precision="fp32"):
         """The causal ``forward`` on the next frames c (B, C, n) of a stream (frame t of the stream is column
         ``t + aux_context_window`` of the whole-utterance input) -> (B, C, n * prod(scales)).  ``hist_in`` / ``hist_out``:
         one tensor per layer of :meth:`stream_layers` (``hist_in`` None: start of stream, ``conv_in`` replicates the first
-        frame)."""
+        frame).  ``precision``: of ``conv_in``'s launch; the stretch stages are fp32 in either."""
         k = 0
         if self.aux_context_window > 0:
             layer = ConvInStream(self.conv_in, self.aux_context_window)
-            c = layer.stream_forward(c, None if hist_in is None else hist_in[0], hist_out[0])
+            c = layer.stream_forward(c, None if hist_in is None else hist_in[0], hist_out[0], precision)
             k = 1
         else:
             from .causal_conv import stream_pointwise
 
-            c = stream_pointwise(self.conv_in, c)
+            c = stream_pointwise(self.conv_in, c, precision)
         return self.upsample.stream_forward(c, None if hist_in is None else hist_in[k:], hist_out[k:])
 
     # ---- the NON-causal network streamed with a fixed look-ahead (DESIGN.md s11.6)
@@ -328,7 +328,7 @@ class ConvInUpsampleNetwork(torch.nn.Module):
         """The non-causal ``forward`` on the next frames c (B, C, n) of a look-ahead stream -> (B, C, n * prod(scales)),
         late by the plan's delay.  The start of a stream replicates the first frame into ``conv_in``'s history (what
         ``inference()``'s replicate padding gives on the left); the end is the caller's: it feeds copies of the last
-        frame."""
+        frame.  ``conv_in`` runs in the walk's precision; the stretch stages are fp32 in either."""
         from .causal_conv import lookahead_launch
 
         cv, w, n = self.conv_in, self.aux_context_window, c.shape[-1]
@@ -336,5 +336,5 @@ class ConvInUpsampleNetwork(torch.nn.Module):
         hist_in, hist_out = pairs[0] if pairs else (None, None)
         if pairs and hist_in is None:
             hist_in = c[:, :, :1].expand(-1, -1, 2 * w).contiguous()
-        c = lookahead_launch(cv, self._lookahead_desc(c.shape[0], n), c, (hist_in, hist_out), valid)
+        c = lookahead_launch(cv, self._lookahead_desc(c.shape[0], n), c, (hist_in, hist_out), valid, walk.precision)
         return self.upsample.lookahead_forward(c, walk, n)

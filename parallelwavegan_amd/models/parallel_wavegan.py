@@ -103,8 +103,9 @@ class ParallelWaveGANGenerator(torch.nn.Module, _WeightNormMixin):
         return self.last_conv_layers[3](x, pre_act="relu")
 
     # ---- stateful streaming of the causal generator (utils.PWGStream)
-    def stream_unsupported_reason(self, batch=1):
-        """None if the causal generator can be streamed layer by layer, else the reason (host logic only)."""
+    def stream_unsupported_reason(self, batch=1, precision="fp32"):
+        """None if the causal generator can be streamed layer by layer in ``precision``, else the reason (host logic
+        only)."""
         if not all(f.use_causal_conv for f in self.conv_layers):
             return "streaming needs use_causal_conv=True"
         if self.upsample_net is None:
@@ -118,10 +119,18 @@ class ParallelWaveGANGenerator(torch.nn.Module, _WeightNormMixin):
         if reason is not None:
             return "the mel upsampler: " + reason
         for f in self.conv_layers:
-            reason = f.stream_unsupported_reason(batch, 8)
+            reason = f.stream_unsupported_reason(batch, 8, precision)
             if reason is not None:
                 return f"{f.__class__.__name__}: {reason}"
         return None
+
+    def pointwise_convs(self):
+        """The 1 x 1 convolutions the causal stream runs through the conv stream kernel without history, in the order it
+        visits them (``conv_in`` is one of them when there is no context window)."""
+        convs = [self.first_conv, self.last_conv_layers[1], self.last_conv_layers[3]]
+        if isinstance(self.upsample_net, upsample.ConvInUpsampleNetwork) and self.upsample_net.aux_context_window == 0:
+            convs.insert(0, self.upsample_net.conv_in)
+        return convs
 
     def stream_layers(self):
         """``(layer, rate)`` of every stateful layer in the order :meth:`stream_forward` visits them: the upsampler's
@@ -136,32 +145,39 @@ class ParallelWaveGANGenerator(torch.nn.Module, _WeightNormMixin):
         return out + [(f, self.upsample_factor) for f in self.conv_layers]
 
     @torch.no_grad()
-    def stream_forward(self, z, c, hist_in, hist_out):
+    def stream_forward(self, z, c, hist_in, hist_out, precision="fp32"):
         """The causal ``forward`` on the next chunk of a stream: noise z (B, 1, n * upsample_factor) and mel frames
         c (B, C, n) -- frame t of the stream is column ``t + aux_context_window`` of the whole-utterance input -- ->
         (B, out_channels, n * upsample_factor).  The same modules in the same order: the upsampler's stream launches, the
         1 x 1 convolutions through the streaming kernel (its sum order does not depend on n), one launch per residual
         block; the running skip sum is updated in place and the last block applies sqrt(1 / layers).  ``hist_in`` /
         ``hist_out``: one history tensor per layer of :meth:`stream_layers` (``hist_in`` None: start of stream); see
-        :class:`utils.PWGStream`."""
+        :class:`utils.PWGStream`.  ``precision="bf16"``: ``conv_in``, the 1 x 1 convolutions and the residual blocks run
+        with bf16 operands; the stretch stages and every history stay fp32."""
         from ..layers.causal_conv import stream_history_pairs, stream_pointwise
 
         hist = list(stream_history_pairs(self.stream_layers(), hist_in, hist_out))
         n, n_up = len(self.conv_layers), len(hist) - len(self.conv_layers)
         # (the upsampler takes its layers' pairs as two lists; a None entry is its start of stream too)
-        c = self.upsample_net.stream_forward(c, [h_in for h_in, _ in hist[:n_up]], [h_out for _, h_out in hist[:n_up]])
+        up_in, up_out = [h_in for h_in, _ in hist[:n_up]], [h_out for _, h_out in hist[:n_up]]
+        if isinstance(self.upsample_net, upsample.ConvInUpsampleNetwork):
+            c = self.upsample_net.stream_forward(c, up_in, up_out, precision)
+        else:
+            c = self.upsample_net.stream_forward(c, up_in, up_out)  # (stretch stages only: fp32 in either precision)
         assert c.size(-1) == z.size(-1)
-        x = stream_pointwise(self.first_conv, z)
+        x = stream_pointwise(self.first_conv, z, precision)
         skips = None
         for i, (f, (h_in, h_out)) in enumerate(zip(self.conv_layers, hist[n_up:])):
             x, skips = f.stream_forward(x, c, h_in, h_out, skips=skips,
-                                        skip_scale=math.sqrt(1.0 / n) if i == n - 1 else 1.0, inplace_skips=True)
-        x = stream_pointwise(self.last_conv_layers[1], skips, pre_act="relu")
-        return stream_pointwise(self.last_conv_layers[3], x, pre_act="relu")
+                                        skip_scale=math.sqrt(1.0 / n) if i == n - 1 else 1.0, inplace_skips=True,
+                                        precision=precision)
+        x = stream_pointwise(self.last_conv_layers[1], skips, precision, pre_act="relu")
+        return stream_pointwise(self.last_conv_layers[3], x, precision, pre_act="relu")
 
     # ---- streaming the NON-causal generator with a fixed look-ahead (utils.PWGLookaheadStream; DESIGN.md s11.6)
-    def lookahead_unsupported_reason(self, batch=1):
-        """None if the non-causal generator streams with a look-ahead, else the reason (host logic only)."""
+    def lookahead_unsupported_reason(self, batch=1, precision="fp32"):
+        """None if the non-causal generator streams with a look-ahead in ``precision``, else the reason (host logic
+        only)."""
         if any(f.use_causal_conv for f in self.conv_layers):
             return ("the model is causal (use_causal_conv=True) and streams without look-ahead through utils.PWGStream")
         if self.upsample_net is None:
@@ -177,7 +193,7 @@ class ParallelWaveGANGenerator(torch.nn.Module, _WeightNormMixin):
         c_delay = 0
         for f in self.conv_layers:
             c_delay += f.conv.dilation
-            reason = f.lookahead_unsupported_reason(batch, 8, c_delay)
+            reason = f.lookahead_unsupported_reason(batch, 8, c_delay, precision)
             if reason is not None:
                 return f"{f.__class__.__name__}: {reason}"
         return None
@@ -224,10 +240,12 @@ class ParallelWaveGANGenerator(torch.nn.Module, _WeightNormMixin):
         last delay.  ``walk``: a :class:`layers.causal_conv.PWGLookaheadWalk` over :meth:`lookahead_plan`.  Every layer
         runs in its causal form on a shifted time axis: the noise waits for the conditioning in a delay line, every gated
         layer reads the conditioning from the shared line at its own delay and the running skip sum through its skip
-        line, and every launch stores zeros outside the utterance.  The last block applies sqrt(1 / layers)."""
+        line, and every launch stores zeros outside the utterance.  The last block applies sqrt(1 / layers).  The walk's
+        ``precision`` is the push's: ``"bf16"`` runs ``conv_in``, the 1 x 1 convolutions and the gated layers with bf16
+        operands; the stretch stages, the delay lines and every state tensor stay fp32."""
         from ..layers.causal_conv import lookahead_pointwise
 
-        frames = c.shape[-1]
+        frames, precision = c.shape[-1], walk.precision
         if isinstance(self.upsample_net, upsample.ConvInUpsampleNetwork):
             c = self.upsample_net.lookahead_forward(c, walk)
         else:
@@ -237,7 +255,7 @@ class ParallelWaveGANGenerator(torch.nn.Module, _WeightNormMixin):
         if pairs:
             z = ops.delay_line_forward(z, pairs[0][0], pairs[0][1], delayed=True)
         _, _, valid = walk.take("first_conv", self.first_conv, frames)
-        x = lookahead_pointwise(self.first_conv, z, valid)
+        x = lookahead_pointwise(self.first_conv, z, valid, precision)
         _, ((c_line, c_line_out),), _ = walk.take("cond_line", None, frames)
         ops.delay_line_forward(c, c_line, c_line_out)
         skips, n = None, len(self.conv_layers)
@@ -245,11 +263,11 @@ class ParallelWaveGANGenerator(torch.nn.Module, _WeightNormMixin):
             launch, pairs, valid = walk.take("layer", f, frames)
             x, skips = f.lookahead_forward(x, c, c_line, launch.c_delay, pairs[0], skips,
                                            pairs[1] if i > 0 else (None, None), valid,
-                                           skip_scale=math.sqrt(1.0 / n) if i == n - 1 else 1.0)
+                                           skip_scale=math.sqrt(1.0 / n) if i == n - 1 else 1.0, precision=precision)
         _, _, valid = walk.take("last_conv", self.last_conv_layers[1], frames)
-        x = lookahead_pointwise(self.last_conv_layers[1], skips, valid, pre_act="relu")
+        x = lookahead_pointwise(self.last_conv_layers[1], skips, valid, precision, pre_act="relu")
         _, _, valid = walk.take("last_conv", self.last_conv_layers[3], frames)
-        return lookahead_pointwise(self.last_conv_layers[3], x, valid, pre_act="relu")
+        return lookahead_pointwise(self.last_conv_layers[3], x, valid, precision, pre_act="relu")
 
     @staticmethod
     def _get_receptive_field_size(layers, stacks, kernel_size, dilation=lambda x: 2 ** x):

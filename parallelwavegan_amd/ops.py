@@ -756,6 +756,81 @@ def wavenet_bf16_layer_forward(desc, x, c, skips, packed, b_dil, b_skip, b_out, 
     return x_out, skips_out, z, g
 
 
+def wavenet_stream_bf16_supported(desc):
+    """Does the bf16-operand streaming form of the causal layer (csrc/wavenet_stream_bf16.hip) cover this geometry?  The
+    answer and the reason in ``_lib.lib().pwg_last_error()`` are those of :func:`wavenet_stream_supported`.  Host logic
+    only."""
+    return bool(_lib.lib().pwg_wavenet_stream_bf16_supported(ctypes.byref(desc)))
+
+
+def wavenet_stream_delayed_bf16_supported(desc, c_delay=0):
+    """Does the bf16-operand delayed form (csrc/wavenet_stream_bf16.hip) cover this geometry with the conditioning read
+    ``c_delay`` columns late?  The answer and the reason are those of :func:`wavenet_stream_delayed_supported`.  Host
+    logic only."""
+    return bool(_lib.lib().pwg_wavenet_stream_bf16_delayed_supported(ctypes.byref(desc), int(c_delay)))
+
+
+def _bf16_stream_image(name, packed):
+    if not packed.is_cuda or packed.dtype != torch.uint8:
+        raise RuntimeError(f"{name}: packed must be the device image of wavenet_bf16_pack_weights")
+
+
+def wavenet_stream_forward_bf16(desc, x, c, skips, hist_in, hist_out, packed, b_dil, b_skip, b_out, skips_out=None,
+                                save=False):
+    """:func:`wavenet_stream_forward` with bf16 operands on the image of :func:`wavenet_bf16_pack_weights` -> (x_out,
+    skips_out), with ``save`` (stage tests) -> (x_out, skips_out, z, g): the fp32 ``z`` and the bf16-rounded gate output
+    (stored as fp32).  ``hist_out`` receives the same raw fp32 columns as in fp32."""
+    _require_device(x, c, skips, hist_in, hist_out, b_dil, b_skip, b_out, skips_out)
+    _bf16_stream_image("wavenet_stream_forward_bf16", packed)
+    assert x.numel() == desc.batch * desc.residual_channels * desc.t, (tuple(x.shape), desc.batch, desc.t)
+    assert c.numel() == desc.batch * desc.aux_channels * desc.t, (tuple(c.shape), desc.batch, desc.t)
+    n_hist = wavenet_stream_hist_floats(desc)
+    for t in (hist_in, hist_out):
+        assert t is None or n_hist == 0 or t.numel() == n_hist, (tuple(t.shape), n_hist)
+    x_out = torch.empty_like(x)
+    if skips_out is None:
+        skips_out = torch.empty_like(x)
+    for t in (skips, skips_out):
+        assert t is None or t.numel() == x.numel()
+    z = torch.empty((x.shape[0], desc.gate_channels, x.shape[2]), device=x.device, dtype=torch.float32) if save else None
+    g = torch.empty_like(x) if save else None
+    _lib.check(_lib.lib().pwg_wavenet_stream_bf16_forward(
+        ctypes.byref(desc), _ptr(x), _ptr(c), _ptr(skips), _ptr(hist_in), _ptr(hist_out), _ptr(packed), _ptr(b_dil),
+        _ptr(b_skip), _ptr(b_out), _ptr(x_out), _ptr(skips_out), _ptr(z), _ptr(g), _stream()), "wavenet_stream_forward_bf16")
+    return (x_out, skips_out, z, g) if save else (x_out, skips_out)
+
+
+def wavenet_stream_delayed_forward_bf16(desc, x, c, c_line, c_delay, skips, skip_line, hist_in, hist_out, packed, b_dil,
+                                        b_skip, b_out, valid=None, save=False):
+    """:func:`wavenet_stream_delayed_forward` with bf16 operands on the image of :func:`wavenet_bf16_pack_weights` ->
+    (x_out, skips_out), with ``save`` (stage tests) -> (x_out, skips_out, z, g); ``z`` and ``g`` are not masked by the
+    valid window.  The history and the skip line receive the same raw fp32 columns as in fp32."""
+    line_in, line_out = skip_line if skips is not None else (None, None)
+    _require_device(x, c, c_line, skips, line_in, line_out, hist_in, hist_out, b_dil, b_skip, b_out)
+    _bf16_stream_image("wavenet_stream_delayed_forward_bf16", packed)
+    assert x.numel() == desc.batch * desc.residual_channels * desc.t, (tuple(x.shape), desc.batch, desc.t)
+    assert c.numel() == desc.batch * desc.aux_channels * desc.t, (tuple(c.shape), desc.batch, desc.t)
+    n_hist = wavenet_stream_delayed_hist_floats(desc)
+    for t in (hist_in, hist_out):
+        assert t is None or n_hist == 0 or t.numel() == n_hist, (tuple(t.shape), n_hist)
+    for t in (line_in, line_out):
+        assert t is None or t.numel() == desc.batch * desc.skip_channels * desc.dilation, tuple(t.shape)
+    assert skips is None or skips.numel() == x.numel()
+    c_cols = 0
+    if c_line is not None:
+        assert c_line.is_contiguous() and c_line.numel() % (desc.batch * desc.aux_channels) == 0, tuple(c_line.shape)
+        c_cols = c_line.numel() // (desc.batch * desc.aux_channels)
+    x_out, skips_out = torch.empty_like(x), torch.empty_like(x)
+    z = torch.empty((x.shape[0], desc.gate_channels, x.shape[2]), device=x.device, dtype=torch.float32) if save else None
+    g = torch.empty_like(x) if save else None
+    lo, hi = (0, desc.t) if valid is None else valid
+    _lib.check(_lib.lib().pwg_wavenet_stream_bf16_delayed_forward(
+        ctypes.byref(desc), _ptr(x), _ptr(c), _ptr(c_line), c_cols, int(c_delay), _ptr(skips), _ptr(line_in), _ptr(line_out),
+        _ptr(hist_in), _ptr(hist_out), _ptr(packed), _ptr(b_dil), _ptr(b_skip), _ptr(b_out), int(lo), int(hi), _ptr(x_out),
+        _ptr(skips_out), _ptr(z), _ptr(g), _stream()), "wavenet_stream_delayed_forward_bf16")
+    return (x_out, skips_out, z, g) if save else (x_out, skips_out)
+
+
 def wavenet_pack_weights_bwd(desc, w_dil, s_dil, w_aux, s_aux, w_skip, s_skip, w_out, s_out):
     """Backward-pass image of a layer (gate / dilated / aux data gradients; folds desc.out_mul and desc.skip_mul)."""
     _require_device(w_dil, s_dil, w_aux, s_aux, w_skip, s_skip, w_out, s_out)

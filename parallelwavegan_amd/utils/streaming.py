@@ -485,7 +485,7 @@ class PWGStream(_Stream):
     samples, one launch per layer: the upsampler's ``conv_in`` and stages, the 1 x 1 convolutions and the 30 gated
     residual blocks each run their stream kernel on the chunk (csrc/wavenet_stream.hip, csrc/elementwise.hip,
     csrc/conv1d_stream.hip).  Any partition of the same frames and noise gives bit-identical audio,
-    equal to the whole-utterance ``forward`` up to fp32 summation order.  fp32 only.
+    equal to the whole-utterance ``forward`` up to fp32 summation order.
 
     State: ``conv_in`` keeps the last ``aux_context_window`` frames, an upsampling stage the last 2 columns of its
     input, a residual block the last ``2 * dilation`` columns of its input (``state_bytes``: both ping-pong halves).
@@ -497,34 +497,53 @@ class PWGStream(_Stream):
     ``use_graph``, ``max_graph_shapes`` and the parameter-state watch are those of :class:`CausalStream`: steady-state
     pushes of one chunk size replay two captured graphs; the first push of an utterance started without context runs
     eagerly.  Noise is never drawn inside a graph: it is written into the graph's static buffer before the replay.
+
+    ``precision="bf16"``: ``conv_in``, the 1 x 1 convolutions and the 30 residual blocks of every push run with bf16
+    operands (csrc/conv1d_stream_bf16.hip, csrc/wavenet_stream_bf16.hip; DESIGN.md s11.7: windows, weights and the gate
+    output are rounded to bf16; sums, the gate, biases, residual, skip sum, tensors and history stay fp32; the stretch
+    stages of the upsampler stay fp32).  As in :class:`CausalStream` the precision belongs to the stream, is fixed for its
+    life (``.precision``) and neither reads nor writes the modules' own ``precision`` attributes; state, ``reset(context)``
+    and partition invariance are those of the fp32 stream, and a bf16 stream's state is interchangeable with an fp32
+    stream's.  ``None`` and ``"fp32"`` are the fp32 stream, which refuses a model that ``set_inference_precision`` put in
+    bf16 mode.
     """
 
     warmup_frames = 1  # zero / replicate start: the first frame can be synthesised at once
 
-    def __init__(self, model, batch=1, use_graph=True, normalize_before=False):
+    def __init__(self, model, batch=1, use_graph=True, normalize_before=False, precision=None):
+        from ..layers.causal_conv import pointwise_desc
         from ..layers.conv import each_conv
         from ..layers.upsample import ConvInStream
         from ..models import ParallelWaveGANGenerator
 
+        if precision not in (None, "fp32", "bf16"):
+            raise ValueError(f"PWGStream: precision must be None, 'fp32' or 'bf16', got {precision!r}")
         if not isinstance(model, ParallelWaveGANGenerator):
             raise ValueError(f"PWGStream: {model.__class__.__name__} is not supported (only the causal "
                              "ParallelWaveGANGenerator; HiFiGANGenerator and MelGANGenerator stream through CausalStream)")
         batch = self._checked_batch(batch)
-        reason = model.stream_unsupported_reason(batch)
+        reason = model.stream_unsupported_reason(batch, precision or "fp32")
         if reason is not None:
             raise ValueError(f"PWGStream: {reason}")
         if model.in_channels != 1 or model.out_channels != 1:
             raise ValueError(f"PWGStream: in_channels / out_channels = {model.in_channels} / {model.out_channels} (the "
                              "stream takes one noise row and emits one waveform per stream)")
-        if any(cv.precision != "fp32" for cv in each_conv(model)):
-            raise ValueError("PWGStream: the model is in bf16 inference precision; the streaming layer kernel is fp32 "
-                             "(utils.set_inference_precision(model, 'fp32'))")
+        if precision != "bf16" and any(cv.precision != "fp32" for cv in each_conv(model)):
+            raise ValueError("PWGStream: the model is in bf16 inference precision; the fp32 streaming layer kernel does "
+                             "not read that mode (utils.set_inference_precision(model, 'fp32'), or stream with bf16 "
+                             "operands: PWGStream(model, precision='bf16'))")
         layers = model.stream_layers()
+        supported = conv1d_stream_bf16_supported if precision == "bf16" else conv1d_stream_supported
         for layer, _ in layers:
-            if isinstance(layer, ConvInStream) and not conv1d_stream_supported(layer.stream_desc(batch, 8)):
+            if isinstance(layer, ConvInStream) and not supported(layer.stream_desc(batch, 8)):
                 raise ValueError(f"PWGStream: {layer} cannot be streamed: "
                                  + _lib.lib().pwg_last_error().decode(errors="replace"))
-        self.precision = "fp32"
+        if precision == "bf16":  # a bf16 stream never runs a convolution the bf16 kernel refuses in fp32 instead
+            for cv in model.pointwise_convs():
+                if not supported(pointwise_desc(cv, batch, 8)):
+                    raise ValueError(f"PWGStream: {cv} cannot be streamed with bf16 operands: "
+                                     + _lib.lib().pwg_last_error().decode(errors="replace"))
+        self.precision = precision or "fp32"  # of the stream, fixed for its life
         self.up = model.upsample_factor  # samples per frame
         self._context = model.aux_context_window if isinstance(layers[0][0], ConvInStream) else 0
         super().__init__(model, layers, batch, use_graph, normalize_before)
@@ -553,7 +572,8 @@ class PWGStream(_Stream):
 
     def _run(self, feats, z, hist_in, hist_out):
         """``hist_in`` (None: start of stream) / ``hist_out``: one ping-pong half each.  -> (batch, samples)."""
-        return self.model.stream_forward(z, self._features(feats), hist_in, hist_out).reshape(self.batch, -1)
+        return self.model.stream_forward(z, self._features(feats), hist_in, hist_out,
+                                         precision=self.precision).reshape(self.batch, -1)
 
     def _capture(self, feats, z):
         static_in, static_z = feats.clone(), z.clone()
@@ -729,7 +749,7 @@ class PWGLookaheadStream(_Stream):
     (``latency_frames``: the ceiling in frames; 3921 samples = 15.3 frames for ``parallel_wavegan.v1``).  After any push
     the samples emitted total ``max(0, frames_in * up - latency_samples)``; ``flush()`` returns the tail, after which the
     emissions total ``frames * up`` samples.  Any partition of the same frames and noise gives bit-identical audio, equal
-    to ``model.inference`` up to fp32 summation order.  fp32 only.
+    to ``model.inference`` up to fp32 summation order.
 
     How: every layer runs in its causal form on a shifted time axis.  ``conv_in`` is ``w`` frames late
     and starts from its first frame replicated; an upsampling stage of scale ``s`` takes a delay ``D`` to ``D * s + s``;
@@ -744,32 +764,55 @@ class PWGLookaheadStream(_Stream):
     captured graphs of its chunk size, as in :class:`LookaheadStream`; the pushes at the start of an utterance and
     ``flush()`` run eagerly.  Noise is never drawn inside a graph.  ``close()`` does not flush: an unflushed tail is
     dropped.
+
+    ``precision="bf16"``: ``conv_in``, the 1 x 1 convolutions and the gated layers of every push, the eager pushes at the
+    start of an utterance and ``flush()`` included, run with bf16 operands (csrc/conv1d_stream_bf16.hip and
+    csrc/wavenet_stream_bf16.hip, the delayed forms; DESIGN.md s11.7: windows, weights and the gate output are rounded to
+    bf16; sums, the gate, biases, residual, skip sum, tensors, history and lines stay fp32; the stretch stages and the
+    delay lines stay fp32).  As in :class:`LookaheadStream` the precision belongs to the stream, is fixed for its life
+    (``.precision``) and neither reads nor writes the modules' own ``precision`` attributes; plan, latency, state and
+    partition invariance are those of the fp32 stream.  ``None`` and ``"fp32"`` are the fp32 stream, which refuses a
+    model that ``set_inference_precision`` put in bf16 mode.
     """
 
     warmup_frames = 1
 
-    def __init__(self, model, batch=1, use_graph=True, normalize_before=False):
-        from ..layers.causal_conv import pwg_lookahead_state_shapes
+    def __init__(self, model, batch=1, use_graph=True, normalize_before=False, precision=None):
+        from ..layers.causal_conv import pointwise_desc, pwg_lookahead_state_shapes
         from ..layers.conv import each_conv
         from ..models import HiFiGANGenerator, ParallelWaveGANGenerator
 
+        if precision not in (None, "fp32", "bf16"):
+            raise ValueError(f"PWGLookaheadStream: precision must be None, 'fp32' or 'bf16', got {precision!r}")
         if not isinstance(model, ParallelWaveGANGenerator):
             hint = "; the non-causal HiFiGANGenerator streams through utils.LookaheadStream" \
                 if isinstance(model, HiFiGANGenerator) else ""
             raise ValueError(f"PWGLookaheadStream: {model.__class__.__name__} is not supported (only the non-causal "
                              f"ParallelWaveGANGenerator{hint})")
         batch = self._checked_batch(batch)
-        reason = model.lookahead_unsupported_reason(batch)
+        reason = model.lookahead_unsupported_reason(batch, precision or "fp32")
         if reason is not None:
             raise ValueError(f"PWGLookaheadStream: {reason}")
         if model.in_channels != 1 or model.out_channels != 1:
             raise ValueError(f"PWGLookaheadStream: in_channels / out_channels = {model.in_channels} / {model.out_channels} "
                              "(the stream takes one noise row and emits one waveform per stream)")
-        if any(cv.precision != "fp32" for cv in each_conv(model)):
-            raise ValueError("PWGLookaheadStream: the model is in bf16 inference precision; the look-ahead stream of "
-                             "Parallel WaveGAN is fp32 (utils.set_inference_precision(model, 'fp32'))")
+        if precision != "bf16" and any(cv.precision != "fp32" for cv in each_conv(model)):
+            raise ValueError("PWGLookaheadStream: the model is in bf16 inference precision; the fp32 look-ahead stream "
+                             "does not read that mode (utils.set_inference_precision(model, 'fp32'), or stream with bf16 "
+                             "operands: PWGLookaheadStream(model, precision='bf16'))")
         plan = model.lookahead_plan()
-        self.precision = "fp32"
+        if precision == "bf16":  # a bf16 stream never runs a convolution the bf16 kernel refuses in fp32 instead
+            for launch in plan:
+                if launch.kind == "conv_in":
+                    desc = model.upsample_net._lookahead_desc(batch, 8)
+                elif launch.kind in ("first_conv", "last_conv"):
+                    desc = pointwise_desc(launch.module, batch, 8)
+                else:
+                    continue
+                if not conv1d_stream_bf16_delayed_supported(desc):
+                    raise ValueError(f"PWGLookaheadStream: {launch.module} cannot be streamed with bf16 operands: "
+                                     + _lib.lib().pwg_last_error().decode(errors="replace"))
+        self.precision = precision or "fp32"  # of the stream, fixed for its life
         self.up = model.upsample_factor  # samples per frame
         self._plan = plan
         self.latency_samples = plan[-1].delay
@@ -792,7 +835,7 @@ class PWGLookaheadStream(_Stream):
         ``state_out``: one ping-pong half each; ``frames_before`` None: steady state.  -> (batch, n * up), not trimmed."""
         from ..layers.causal_conv import PWGLookaheadWalk
 
-        walk = PWGLookaheadWalk(self._plan, state_in, state_out, frames_before, total_frames)
+        walk = PWGLookaheadWalk(self._plan, state_in, state_out, frames_before, total_frames, self.precision)
         return self.model.lookahead_forward(z, self._features(feats), walk).reshape(self.batch, -1)
 
     def _capture(self, feats, z):

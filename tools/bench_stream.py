@@ -45,6 +45,12 @@ state pushes of 4 / 8 / 32 frames at 1 and 16 streams, into profiles/stream_pwg_
 ONE graph of the whole-utterance forward over ``L + n + L`` frames (plus the context window), ``L`` = the stream's
 latency in frames, rounded up -- the receptive field is symmetric -- on static noise.
 
+``--model pwg [--lookahead] --precision bf16``: the bf16-operand Parallel WaveGAN streams (``PWGStream`` /
+``PWGLookaheadStream`` with ``precision="bf16"``, csrc/wavenet_stream_bf16.hip) at the same grids, four
+measurements alternating in one process as for ``--lookahead --precision bf16``: the fp32 push, the bf16 push, and the halo
+forward of the two fp32 tools above in fp32 and -- on a second instance of the model put in bf16 inference precision -- in
+bf16.  Into profiles/stream_pwg_bf16_infer.json and profiles/stream_pwg_lookahead_bf16_infer.json.
+
 usage: python tools/bench_stream.py [--model pwg [--lookahead]] [--multiband] [--precision bf16] [--lookahead] [--reps 200]
                                     [--repeats 3] [--out profiles/stream_infer.json]
 """
@@ -171,15 +177,29 @@ def main():
     args = ap.parse_args()
     if args.lookahead and args.multiband:
         ap.error("--lookahead is the non-causal HiFi-GAN or (--model pwg) Parallel WaveGAN stream (no --multiband)")
-    if args.model == "pwg" and (args.multiband or args.precision != "fp32"):
-        ap.error("--model pwg is the fp32 full-band Parallel WaveGAN stream (no --multiband, no --precision bf16)")
-    default_out = "stream_pwg_lookahead_infer.json" if args.lookahead and args.model == "pwg" else "stream_lookahead_bf16_infer.json" if args.lookahead and args.precision == "bf16" else "stream_lookahead_infer.json" if args.lookahead else "stream_pwg_infer.json" if args.model == "pwg" else "stream_bf16_infer.json" if args.precision == "bf16" else (
+    if args.model == "pwg" and args.multiband:
+        ap.error("--model pwg is the full-band Parallel WaveGAN stream (no --multiband)")
+    default_out = ("stream_pwg_lookahead_bf16_infer.json" if args.lookahead else "stream_pwg_bf16_infer.json") if args.model == "pwg" and args.precision == "bf16" else "stream_pwg_lookahead_infer.json" if args.lookahead and args.model == "pwg" else "stream_lookahead_bf16_infer.json" if args.lookahead and args.precision == "bf16" else "stream_lookahead_infer.json" if args.lookahead else "stream_pwg_infer.json" if args.model == "pwg" else "stream_bf16_infer.json" if args.precision == "bf16" else (
         "stream_mb_infer.json" if args.multiband else "stream_infer.json")
     args.out = args.out or os.path.join(ROOT, "profiles", default_out)
     dev = torch.device("cuda:0")
     rec = {"tool": "tools/bench_stream.py", "device": torch.cuda.get_device_name(0), "reps": args.reps,
            "repeats": args.repeats, "models": {}, "points": []}
     gen = torch.Generator(device="cpu").manual_seed(100)
+    if args.model == "pwg" and args.precision == "bf16":
+        causal = not args.lookahead
+        model16 = build_pwg(dev, causal=causal)  # the halo forward's own instance: the streamed one stays in fp32 mode
+        set_inference_precision(model16, "bf16")
+        measure_pwg_precision(rec, "parallel_wavegan_v1_causal" if causal else "parallel_wavegan_v1",
+                              build_pwg(dev, causal=causal), model16, args.lookahead, CHUNKS, gen, args, dev)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(rec, f, indent=1)
+            f.write("\n")
+        print(json.dumps({"out": args.out, "points": [[p["model"], p["streams"], p["chunk_frames"], p["fp32_push_ms"],
+                                                       p["bf16_push_ms"], p["halo_fp32_ms"], p["halo_bf16_ms"]]
+                                                      for p in rec["points"]]}))
+        return
     if args.lookahead and args.precision == "bf16":
         model16 = build_noncausal(dev)  # the halo forward's own instance: the streamed one stays in fp32 mode
         set_inference_precision(model16, "bf16")
@@ -490,6 +510,83 @@ def measure_lookahead_precision(rec, name, model, model16, chunks, gen, args, de
                                                 "halo_fp32_ms", "halo_bf16_ms", "spread_ms",
                                                 "speedup_bf16_push_over_fp32_push", "speedup_bf16_push_over_halo_bf16",
                                                 "conv_kernel_ms_per_eager_push")}), file=sys.stderr, flush=True)
+
+
+def measure_pwg_precision(rec, name, model, model16, lookahead, chunks, gen, args, dev):
+    """Steady-state fp32 and bf16 pushes of ``model`` through ``PWGStream`` (``lookahead``: ``PWGLookaheadStream``) and
+    the halo forward of :func:`measure_pwg` (:func:`measure_pwg_lookahead`) of ``model`` (fp32) and of ``model16`` (the
+    same weights in bf16 inference precision), alternating."""
+    up, w = model.upsample_factor, model.aux_context_window
+    cls = PWGLookaheadStream if lookahead else PWGStream
+    probe = cls(model, use_graph=False, precision="bf16")
+    if lookahead:
+        left = right = probe.latency_frames
+        warm = lambda s, n: s.frames_in < probe.latency_frames + 4 * n  # noqa: E731  (the eager start, both directions)
+        kernels = {"fp32": "wavenet_stream_delayed_kernel", "bf16": "wavenet_stream_bf16_delayed_kernel"}
+    else:
+        with torch.no_grad():
+            left, right = receptive_field_frames(_MelOnly(model), in_channels=80)
+        assert right == 0, "a causal generator has no look-ahead"
+        warm = lambda s, n: s.frames_in < 6 * n  # noqa: E731
+        kernels = {"fp32": "wavenet_stream_kernel", "bf16": "wavenet_stream_bf16_kernel"}
+    rec["models"][name] = {"workload": "seeded weights, weight norm removed", "halo_left_frames": left,
+                           "halo_right_frames": right, "stream_state_bytes_per_stream": probe.state_bytes}
+    if lookahead:
+        rec["models"][name].update(latency_samples=probe.latency_samples, latency_frames=probe.latency_frames)
+    for b in STREAMS:
+        for n in chunks:
+            total = left + n + right
+            feats = torch.randn(b, n, 80, generator=gen).to(dev)
+            noise = torch.randn(b, n * up, generator=gen).to(dev)
+            ctx = torch.randn(b, 80, total + 2 * w, generator=gen).to(dev)
+            z_halo = torch.randn(b, 1, total * up, generator=gen).to(dev)
+            streams = {prec: cls(model, batch=b, use_graph=True, precision=prec) for prec in kernels}
+            halos = {"fp32": GraphedInference(lambda c: model(z_halo, c)),
+                     "bf16": GraphedInference(lambda c: model16(z_halo, c))}
+            while warm(streams["fp32"], n):
+                for prec in kernels:
+                    streams[prec].push(feats, noise)
+                    halos[prec](ctx)
+            calls = {"fp32_push": lambda: streams["fp32"].push(feats, noise),
+                     "bf16_push": lambda: streams["bf16"].push(feats, noise),
+                     "halo_fp32": lambda: halos["fp32"](ctx), "halo_bf16": lambda: halos["bf16"](ctx)}
+            runs = {k: [] for k in calls}
+            for _ in range(args.repeats):
+                for k, fn in calls.items():
+                    runs[k].append(event_ms(fn, args.reps))
+            layer_ms, fam = {}, {}
+            for prec, kernel in kernels.items():
+                eager = cls(model, batch=b, use_graph=False, precision=prec)
+                while eager.frames_in < (probe.latency_frames if lookahead else 1):  # past the partial windows
+                    eager.push(feats, noise)
+                _, fam[prec] = launches(lambda: eager.push(feats, noise))
+                with ops.profile() as prof:  # the layer launches of a push, by the library's own event scope
+                    for _ in range(10):
+                        eager.push(feats, noise)
+                layer_ms[prec] = round(prof.results[kernel]["ms"] / prof.results[kernel]["launches"], 5)
+            _, fam_h16 = launches(lambda: model16(z_halo, ctx))
+            med = {k: sorted(v)[len(v) // 2] for k, v in runs.items()}
+            spread = max(max(v) - min(v) for v in runs.values())
+            p = {"model": name, "streams": b, "chunk_frames": n, "samples_per_push": b * n * up,
+                 "halo_frames_computed": total, "spread_ms": round(spread, 4)}
+            for k in calls:
+                p[k + "_ms"] = round(med[k], 4)
+                p[k + "_runs_ms"] = [round(t, 4) for t in runs[k]]
+            p.update({"speedup_bf16_push_over_fp32_push": round(med["fp32_push"] / med["bf16_push"], 3),
+                      "speedup_bf16_push_over_halo_fp32": round(med["halo_fp32"] / med["bf16_push"], 3),
+                      "speedup_bf16_push_over_halo_bf16": round(med["halo_bf16"] / med["bf16_push"], 3),
+                      "speedup_fp32_push_over_halo_fp32": round(med["halo_fp32"] / med["fp32_push"], 3),
+                      "bf16_push_faster_than_fp32_push_beyond_spread": med["bf16_push"] + spread < med["fp32_push"],
+                      "bf16_push_slower_than_fp32_push_beyond_spread": med["bf16_push"] > med["fp32_push"] + spread,
+                      "bf16_push_faster_than_halo_bf16_beyond_spread": med["bf16_push"] + spread < med["halo_bf16"],
+                      "bf16_push_slower_than_halo_bf16_beyond_spread": med["bf16_push"] > med["halo_bf16"] + spread,
+                      "real_time_factor_22050Hz": round(n * up / 22050.0 / (med["bf16_push"] / 1e3), 1),
+                      "layer_launch_ms": layer_ms, "stream_kernels": fam, "halo_bf16_kernels": fam_h16})
+            rec["points"].append(p)
+            print(json.dumps({k: p[k] for k in ("model", "streams", "chunk_frames", "fp32_push_ms", "bf16_push_ms",
+                                                "halo_fp32_ms", "halo_bf16_ms", "spread_ms",
+                                                "speedup_bf16_push_over_fp32_push", "speedup_bf16_push_over_halo_bf16",
+                                                "layer_launch_ms")}), file=sys.stderr, flush=True)
 
 
 def measure_precision(rec, name, model, chunks, gen, args, dev):
