@@ -354,6 +354,38 @@ int pwg_conv1d_stream_bf16_delayed_forward(const pwg_conv1d_desc* d, const float
                                            float* add2_hist_out, int32_t delay2, int32_t valid_lo, int32_t valid_hi,
                                            float* y, void* stream);
 
+/* ---- the delayed stream launch of a REFLECT-padded layer: the mirrored form (fp32; csrc/conv1d_stream.hip) ----
+ * For streaming the non-causal (multi-band) MelGAN with a fixed look-ahead.  Replaces, chunk by chunk, the
+ * ReflectionPad1d + Conv1d pairs of the reference generator (models/melgan.py:70-73 the first k = 7 convolution,
+ * :135-140 the last one; layers/residual_stack.py:49-52 the dilated k = 3 convolution of a stack) as the delayed entry
+ * replaces the zero-padded layers.  The layer runs in its causal form on an axis shifted by its padding p = (k-1)*d/2:
+ * output column q is produced once input column q + p has arrived, and by then the columns reflection reads have
+ * arrived too (left edge: -1 .. q-p mirror to 1 .. p-q <= q+p; right edge: T-1+i mirrors to T-1-i inside the same
+ * 2p+1 window).  History and chunk stay RAW -- they hold stored zeros (or a flush's dummy columns) outside the
+ * utterance, never mirror images -- and the window mirrors on read.
+ * d: the causal descriptor of the layer (stride 1, pad_left == (k-1)*d, t_out == t_in, groups == 1) with
+ *   pad_mode == PWG_PAD_REFLECT and an even (k-1)*d <= 144; t_in = columns of this chunk.
+ * x, hist_in (NULL: start of stream, zeros), hist_out, w_packed, bias, y: as for pwg_conv1d_stream_delayed_forward;
+ *   hist_out = the last (k-1)*d raw columns of concat(hist_in, x).  There are no addends.
+ * [in_lo, in_hi): the valid window of the INPUT in chunk-relative input columns, unclamped: in_lo < 0 means the
+ *   utterance's first column lies in the history, in_hi = INT32_MAX that its length is not known yet.  Both are saturated
+ *   on the host.  A window column t in [-(k-1)*d, t_in) reads column 2*in_lo - t if t < in_lo, 2*(in_hi-1) - t if
+ *   t >= in_hi, else t; the mapped column is then taken from the history if negative, from the chunk otherwise, and
+ *   reads as zero if it lies outside [-(k-1)*d, t_in) (no address is formed from it).
+ * [valid_lo, valid_hi): the valid window of the output as for the delayed entry: other columns are STORED as 0.0f.  For a
+ *   layer of a network, valid_lo = in_lo + p and valid_hi = in_hi + p; a valid column never depends on a column that
+ *   read as zero, provided the utterance is longer than p (reflection's own precondition).
+ * Contraction, sum order, tile rule, pre- and post-activation (tanh included) are pwg_conv1d_stream_forward's: any
+ * partition of a stream gives the same bits.
+ * pwg_conv1d_stream_mirrored_supported: pure host logic (no device needed); 0 -- pwg_last_error names the reason -- for a
+ * transposed layer, a pad_mode other than PWG_PAD_REFLECT, an odd (k-1)*d, and whatever pwg_conv1d_stream_supported
+ * refuses (stride, groups, a history above 144 columns).
+ * These two symbols are purely additive -- no existing signature or behaviour changes -- so pwg_abi_version() stays 15. */
+int pwg_conv1d_stream_mirrored_supported(const pwg_conv1d_desc* d);
+int pwg_conv1d_stream_mirrored_forward(const pwg_conv1d_desc* d, const float* x, const float* hist_in, float* hist_out,
+                                       const float* w_packed, const float* bias, float* y, int32_t in_lo, int32_t in_hi,
+                                       int32_t valid_lo, int32_t valid_hi, void* stream);
+
 /* Diagnostics (host only, no launch, no device needed): the plan pwg_conv1d_forward derives for a descriptor.
  * has_addends: 1 if add1 / add2 will be passed.  out[8]:
  *   out[0] kernel family: 0 = MFMA implicit-GEMM kernel, 1 = grouped 16x16x4 kernel, 2 = single-input-channel

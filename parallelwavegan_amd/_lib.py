@@ -158,6 +158,9 @@ SIGNATURES = {
     "pwg_conv1d_stream_bf16_delayed_supported": (ctypes.c_int, [ctypes.POINTER(ConvDesc), _i32, _i32]),
     "pwg_conv1d_stream_bf16_delayed_forward": (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                                               _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "pwg_conv1d_stream_mirrored_supported": (ctypes.c_int, [ctypes.POINTER(ConvDesc)]),
+    "pwg_conv1d_stream_mirrored_forward": (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _i32,
+                                                          _i32, _i32, _i32, _vp]),
     "pwg_conv1d_packed_weight_bwd_floats": (ctypes.c_size_t, [ctypes.POINTER(ConvDesc)]),
     "pwg_conv1d_pack_weight_bwd": (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, _vp]),
     "pwg_weight_bank_table_bytes": (ctypes.c_size_t, [_i32]),

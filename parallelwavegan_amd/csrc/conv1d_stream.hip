@@ -108,6 +108,23 @@ int delayed_geometry(const pwg_conv1d_desc* d, int32_t delay1, int32_t delay2, S
   return PWG_OK;
 }
 
+// What the mirrored form admits: the reflect-padded stride-1 layer of stream_geometry() with a symmetric reach.  The
+// refusals that name the form come first, so that a transposed or zero-padded layer is told why THIS entry turns it down
+int mirrored_geometry(const pwg_conv1d_desc* d, StreamGeom* g) {
+  PWG_REQUIRE(d != nullptr, PWG_ERR_NULL, "conv1d_stream_mirrored: NULL descriptor");
+  PWG_REQUIRE(!d->transposed, PWG_ERR_UNSUPPORTED,
+              "conv1d_stream_mirrored: a transposed convolution is not reflect-padded (it streams through the delayed form)");
+  PWG_REQUIRE(d->pad_mode == PWG_PAD_REFLECT, PWG_ERR_UNSUPPORTED,
+              "conv1d_stream_mirrored: pad_mode = %d (the mirrored form is the reflect-padded layer's; a zero-padded one "
+              "streams through the delayed form)", d->pad_mode);
+  const int rc = stream_geometry(d, g);
+  if (rc != PWG_OK) return rc;
+  PWG_REQUIRE(g->hist % 2 == 0, PWG_ERR_UNSUPPORTED,
+              "conv1d_stream_mirrored: history of %d columns is odd (symmetric padding needs an even (k - 1) * d)", g->hist);
+  PWG_REQUIRE(d->t_in <= (1 << 28), PWG_ERR_UNSUPPORTED, "conv1d_stream_mirrored: chunk of %d columns", d->t_in);
+  return PWG_OK;
+}
+
 namespace {
 
 constexpr int SC = 64;  // input channels staged per LDS block (four 16-channel groups of the image)
@@ -130,8 +147,19 @@ struct StreamDelayedArgs : StreamArgs {
 // One workgroup (4 waves) owns MT = 16 * TM rows x NT = 16 * TN columns.  The reduction is dealt over the four waves:
 // wave w takes the w-th 16-channel group of every staged block of 64 channels, and the four partial tiles are summed
 // through LDS in wave order, ((p0 + p1) + p2) + p3 -- the same in every configuration.
-template <int TM, int TN, bool TRANSPOSED, bool DELAYED = false>
-__global__ __launch_bounds__(256) void conv1d_stream_kernel(std::conditional_t<DELAYED, StreamDelayedArgs, StreamArgs> a) {
+// MIRRORED (with DELAYED): the window is read through the mirror rule (StreamMirrorWindow); everything else is the
+// delayed form.
+struct StreamMirroredArgs : StreamDelayedArgs {
+  int in_lo, in_hi;  // the input's valid window, saturated (mirror_bound)
+};
+
+template <bool DELAYED, bool MIRRORED>
+using stream_args_t =
+    std::conditional_t<MIRRORED, StreamMirroredArgs, std::conditional_t<DELAYED, StreamDelayedArgs, StreamArgs>>;
+
+template <int TM, int TN, bool TRANSPOSED, bool DELAYED = false, bool MIRRORED = false>
+__global__ __launch_bounds__(256) void conv1d_stream_kernel(stream_args_t<DELAYED, MIRRORED> a) {
+  static_assert(!MIRRORED || (DELAYED && !TRANSPOSED), "the mirrored form is a delayed stride-1 convolution");
   constexpr int MT = 16 * TM, NT = 16 * TN;
   extern __shared__ __attribute__((aligned(16))) float xs[];  // [SC][a.xs]; afterwards the partial tiles [4][MT][NT]
 
@@ -212,7 +240,13 @@ __global__ __launch_bounds__(256) void conv1d_stream_kernel(std::conditional_t<D
   // window elements come from the history, the chunk or the start-of-stream padding; the pre-activation is applied on
   // the way into LDS.  The load phase is branch-free: the source address is selected (a safe one where the element is
   // zero padding or past the chunk) and always loaded, so that the loads of a staging batch are issued back to back
-  const StreamWindow win = {xb, hb, n, H, a.pad_mode};
+  const StreamWindow raw_win = {xb, hb, n, H, a.pad_mode};
+  const auto win = [&] {
+    if constexpr (MIRRORED)
+      return StreamMirrorWindow{raw_win, a.in_lo, a.in_hi};  // (the launch passes pad_mode zero: history reads raw)
+    else
+      return raw_win;
+  }();
   const int r_first = tid / W, w_first = tid - r_first * W;
 
   for (int c0 = 0; c0 < a.cin_pad; c0 += SC) {
@@ -282,6 +316,12 @@ struct Kernel {
 template <int TM, int TN, bool TRANSPOSED>
 struct DelayedKernel {
   static constexpr auto fn = conv1d_stream_kernel<TM, TN, TRANSPOSED, true>;
+};
+
+// (mirrored_geometry() admits no transposed layer: that slot of stream_launch names the same kernel, never launched)
+template <int TM, int TN, bool TRANSPOSED>
+struct MirroredKernel {
+  static constexpr auto fn = conv1d_stream_kernel<TM, TN, false, true, true>;
 };
 
 }  // namespace
@@ -374,5 +414,52 @@ extern "C" int pwg_conv1d_stream_delayed_forward(const pwg_conv1d_desc* d, const
   stream_launch<DelayedKernel>(tile, d->transposed != 0, a, g.m, d->batch,
                                stream_lds_bytes((size_t)SC * a.xs * sizeof(float), tile), stream);
   PWG_CHECK_LAUNCH("conv1d_stream_delayed");
+  return PWG_OK;
+}
+
+extern "C" int pwg_conv1d_stream_mirrored_supported(const pwg_conv1d_desc* d) {
+  StreamGeom g;
+  return mirrored_geometry(d, &g) == PWG_OK ? 1 : 0;
+}
+
+extern "C" int pwg_conv1d_stream_mirrored_forward(const pwg_conv1d_desc* d, const float* x, const float* hist_in,
+                                                  float* hist_out, const float* w_packed, const float* bias, float* y,
+                                                  int32_t in_lo, int32_t in_hi, int32_t valid_lo, int32_t valid_hi,
+                                                  void* stream_) {
+  StreamGeom g;
+  int rc = mirrored_geometry(d, &g);
+  if (rc != PWG_OK) return rc;
+  hipStream_t stream = (hipStream_t)stream_;
+  // history and chunk are read raw (zeros before the stream, stored zeros around the utterance): the launch itself is
+  // a zero-padded one, the reflection lives in the window's mirror rule alone
+  pwg_conv1d_desc raw = *d;
+  raw.pad_mode = PWG_PAD_ZERO;
+  rc = stream_check_pointers("conv1d_stream_mirrored", &raw, g, x, w_packed, y, hist_in, hist_out);
+  if (rc != PWG_OK) return rc;
+  PWG_REQUIRE((reinterpret_cast<uintptr_t>(w_packed) & 3u) == 0, PWG_ERR_BAD_SHAPE,
+              "conv1d_stream_mirrored: unaligned weight image");
+  StreamMirroredArgs a;
+  rc = stream_delay_lines("conv1d_stream_mirrored", nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, valid_lo,
+                          valid_hi, &a.dl);
+  if (rc != PWG_OK) return rc;
+  const int n = d->t_in;
+  const StreamTile tile = stream_tile(n, g.m, d->batch);
+
+  stream_fill_args(&a, &raw, g, tile, x, hist_in, hist_out, bias, nullptr, nullptr, y);
+  a.w = w_packed;
+  a.cin_pad = g.cin_pad;
+  a.m_pad = g.m_pad;
+  a.xs = xs_stride(16 * tile.tn + g.hist);
+  a.in_lo = mirror_bound(in_lo, g.hist, n);
+  a.in_hi = mirror_bound(in_hi, g.hist, n);
+
+  const double flops = 2.0 * (double)d->batch * g.m * n * g.taps * d->c_in;
+  const double bytes = 4.0 * ((double)d->batch * d->c_in * (n + 2.0 * g.hist) + (double)d->batch * d->c_out * d->t_out +
+                              (double)g.taps * g.cin_pad * g.m_pad);
+  maybe_poison_lds(stream);
+  ProfScope prof(stream, "conv1d_stream_mirrored_kernel", flops, bytes);
+  stream_launch<MirroredKernel>(tile, false, a, g.m, d->batch, stream_lds_bytes((size_t)SC * a.xs * sizeof(float), tile),
+                                stream);
+  PWG_CHECK_LAUNCH("conv1d_stream_mirrored");
   return PWG_OK;
 }

@@ -4,6 +4,7 @@
 //   start-of-stream rule  StreamWindow::at       which source window column t comes from (history, chunk, padding)
 //   sum order, epilogue   stream_reduce_epilogue ((p0 + p1) + p2) + p3, then the fp32 epilogue
 //   delayed form          StreamDelay            addends read through a delay line, zeros stored outside a valid window
+//   mirror rule           StreamMirrorWindow::at the reflect-padded layer of a look-ahead stream: mirror, then resolve
 //   tile rule             stream_tile            column tile from n; 32-row blocks only at 2 x 256 or more workgroups
 //   coverage              stream_geometry        defined in conv1d_stream.hip; both precisions admit the same layers
 //                         delayed_geometry       ... and the same delays (what the delayed form adds; defined there too)
@@ -73,6 +74,28 @@ struct StreamWindow {
     c.live = in_chunk ? t < n : (has_hist || replicate || (reflect && tt < n));
     c.hist = !in_chunk && has_hist;
     c.col = c.hist ? H + t : tt;
+    return c;
+  }
+};
+
+// ---- mirror rule (the mirrored form: a REFLECT-padded layer of a non-causal network in a look-ahead stream, DESIGN.md
+// s11.8).  The layer's input is valid on [in_lo, in_hi) (chunk-relative, in_lo < 0: the left edge lies in the history);
+// outside it the raw history and chunk hold stored zeros (or the flush's dummy columns), not mirror images, and keep
+// holding them.  So a window column t is first mapped to the column reflection reads -- t < in_lo: 2 * in_lo - t;
+// t >= in_hi: 2 * (in_hi - 1) - t; at most one applies to a column a valid output reads (pad < T) -- and the mapped
+// column is then resolved by the start-of-stream rule above with zero padding.  A mapped column outside [-H, n) is not
+// live (it reads as zero through the staging loop's safe address): only outputs outside the valid window can depend on
+// one, and those are stored as zeros.  The host saturates in_lo / in_hi to [-H, n + kStreamMaxNt] (mirror_bound), which
+// changes no mapped column inside [-H, n) and keeps the arithmetic far from overflow.
+struct StreamMirrorWindow {
+  StreamWindow raw;  // pad_mode == PWG_PAD_ZERO
+  int in_lo, in_hi;
+
+  __device__ __forceinline__ StreamWindow::Column at(int t) const {
+    const int m = t < in_lo ? 2 * in_lo - t : (t >= in_hi ? 2 * (in_hi - 1) - t : t);
+    StreamWindow::Column c = raw.at(m);
+    c.live = c.live && m >= -raw.H;
+    c.col = c.live ? c.col : 0;  // (the staging loop selects its safe address anyway; this one stays in range too)
     return c;
   }
 };
@@ -190,6 +213,17 @@ __attribute__((visibility("hidden"))) int stream_geometry(const pwg_conv1d_desc*
 // longer than a history.
 __attribute__((visibility("hidden"))) int delayed_geometry(const pwg_conv1d_desc* d, int32_t delay1, int32_t delay2,
                                                            StreamGeom* g);
+
+// What the mirrored form admits (conv1d_stream.hip): a stride-1, non-transposed, ungrouped PWG_PAD_REFLECT layer whose
+// history (k - 1) * d is even (symmetric padding) and fits the window.
+__attribute__((visibility("hidden"))) int mirrored_geometry(const pwg_conv1d_desc* d, StreamGeom* g);
+
+// An edge of the mirrored form's input window, saturated for the kernel (StreamMirrorWindow): every window column t lies
+// in [-H, n + kStreamMaxNt), so an edge at or below -H, or at or above n + kStreamMaxNt, acts as that bound does
+static inline int mirror_bound(long edge, int H, int n) {
+  const long lo = -(long)H, hi = (long)n + kStreamMaxNt;
+  return (int)(edge < lo ? lo : (edge > hi ? hi : edge));
+}
 
 // The fields both kernels' argument structs share
 struct StreamCommonArgs {

@@ -162,6 +162,63 @@ def lookahead_delay(cv, delay_in):
     return delay_in + cv.padding
 
 
+def mirrored_delay(cv, delay_in):
+    """:func:`lookahead_delay` for a REFLECT-padded ``Conv1d`` (the non-causal MelGAN's; the mirrored form of the
+    streaming kernel): its causal form on an axis shifted by its padding, the window mirroring on read.
+    ValueError for a layer that has no such form."""
+    reach = (cv.kernel_size - 1) * cv.dilation
+    if cv.groups != 1 or cv.pad_mode != "reflect" or cv.transposed:
+        raise ValueError(f"{cv}: only a reflect-padded, ungrouped Conv1d streams through the mirrored form")
+    if reach % 2:
+        raise ValueError(f"{cv}: an even kernel has no symmetric padding, so it does not stream with a look-ahead")
+    if cv.stride != 1 or cv.padding != reach // 2 or cv.padding_right != reach // 2:
+        raise ValueError(f"{cv}: only a stride-1 Conv1d with symmetric padding (k - 1) * d / 2 streams with a look-ahead")
+    return delay_in + cv.padding
+
+
+def mirrored_desc(cv, batch, n, **fused):
+    """Descriptor of one push of ``n`` columns through the mirrored form of the reflect-padded ``cv``: its causal
+    descriptor, ``pad_mode="reflect"``."""
+    return ops.make_conv_desc(batch, cv.in_channels, cv.out_channels, n, n, cv.kernel_size, 1, cv.dilation,
+                              lookahead_history_columns(cv), cv.groups, transposed=False, pad_mode="reflect", **fused)
+
+
+def launch_is_mirrored(launch):
+    """Does this launch of a delay plan go through the mirrored entry point (a reflect-padded convolution)?"""
+    return launch.conv.pad_mode == "reflect"
+
+
+def launch_desc(launch, batch, n, **fused):
+    """The descriptor of a plan's launch for a push of ``n`` input columns, mirrored or delayed."""
+    return (mirrored_desc if launch_is_mirrored(launch) else lookahead_desc)(launch.conv, batch, n, **fused)
+
+
+def lookahead_settle_frames(plan):
+    """Frames that must have gone before a push for none of its launches to have an edge of the utterance in its window
+    or history -- the condition under which a captured graph, whose window arguments are fixed, may be replayed:
+    ``frames_before * rate >= delay + pad`` for every launch, ``pad`` being the mirror reach of a reflect-padded launch
+    (its window goes ``2 * pad`` input columns back, and its input is ``pad`` columns younger than its output) and 0 for
+    a zero-padded one (whose only edge is its valid window's)."""
+    return max(-(-(launch.delay + (launch.conv.padding if launch_is_mirrored(launch) else 0)) // launch.rate)
+               for launch in plan)
+
+
+def mirrored_min_frames(plan):
+    """The shortest utterance reflection can pad: every reflect-padded launch needs more input columns than its padding,
+    ``frames * rate > pad`` (4 frames for a first layer of kernel 7).  1 for a plan without such a launch."""
+    return max([launch.conv.padding // launch.rate + 1 for launch in plan if launch_is_mirrored(launch)] + [1])
+
+
+def mirrored_in_window(launch, frames_before=None, total_frames=None):
+    """Valid window ``(lo, hi)`` of a mirrored launch's INPUT, chunk-relative and unclamped: the producing launch's
+    valid window, i.e. the launch's own shifted back by its padding.  ``lo < 0``: the utterance began in the history;
+    ``hi`` None: its length is not known yet.  ``frames_before`` None: steady state, no edge in reach."""
+    if frames_before is None:
+        return -(2 ** 30), None
+    start = launch.delay - launch.conv.padding - frames_before * launch.rate
+    return start, (None if total_frames is None else start + total_frames * launch.rate)
+
+
 def lookahead_history_columns(cv):
     """Columns of raw input the causal form of the non-causal ``cv`` keeps: ``(k - 1) * d``, 1 for a transposed layer."""
     return 1 if cv.transposed else (cv.kernel_size - 1) * cv.dilation
@@ -244,9 +301,11 @@ class LookaheadWalk:
                                "with bf16 operands)")
         hist = self._take(lookahead_history_columns(cv))
         line1, line2 = self._take(launch.delay1), self._take(launch.delay2)
-        desc = lookahead_desc(cv, x.shape[0], x.shape[-1], **fused)
+        desc = launch_desc(launch, x.shape[0], x.shape[-1], **fused)
         t_out = desc.t_out
         lo, hi = lookahead_window(launch.delay, launch.rate, t_out, self.frames_before, self.total_frames)
+        if launch_is_mirrored(launch):
+            return self._run_mirrored(launch, desc, x, hist, (lo, hi), add1, add2)
         if bf16:
             kernel, supported, forward = "delayed bf16 streaming kernel", ops.conv1d_stream_bf16_delayed_supported, \
                 ops.conv1d_stream_delayed_forward_bf16
@@ -263,6 +322,25 @@ class LookaheadWalk:
             image = cv.packed_weight_bf16() if bf16 else cv.packed_weight()
             return forward(desc, x.contiguous(), hist[0], hist[1], image, bias, add1, line1, launch.delay1, add2, line2,
                            launch.delay2, (lo, hi))
+
+    def _run_mirrored(self, launch, desc, x, hist, valid, add1, add2):
+        """A reflect-padded launch (the non-causal MelGAN's): the mirrored entry point, whose input window is the
+        producing launch's unclamped valid window.  fp32 only, no addends."""
+        cv = launch.conv
+        if self.precision != "fp32":
+            raise RuntimeError("the mirrored form of the streaming kernel has no bf16 form yet: a reflect-padded layer "
+                               "streams with a look-ahead in fp32 only")
+        if add1 is not None or add2 is not None or launch.delay1 or launch.delay2:
+            raise RuntimeError("the mirrored form of the streaming kernel takes no addends")
+        if not ops.conv1d_stream_mirrored_supported(desc):
+            from .. import _lib
+
+            raise RuntimeError("the mirrored streaming kernel does not cover this layer: "
+                               + _lib.lib().pwg_last_error().decode(errors="replace"))
+        with torch.no_grad():
+            return ops.conv1d_stream_mirrored_forward(
+                desc, x.contiguous(), hist[0], hist[1], cv.packed_weight(), None if cv.bias is None else cv.bias.detach(),
+                mirrored_in_window(launch, self.frames_before, self.total_frames), valid)
 
 
 # ---- the same for the NON-causal Parallel WaveGAN generator (utils.PWGLookaheadStream, DESIGN.md s11.6).  Its launches

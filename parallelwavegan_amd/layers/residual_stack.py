@@ -6,7 +6,7 @@ import torch
 from .. import functional as Fn
 from .. import ops
 from .activation import FusedActivation
-from .causal_conv import CausalConv1d, stream_pointwise
+from .causal_conv import CausalConv1d, LookaheadLaunch, lookahead_delay, mirrored_delay, stream_pointwise
 from .conv import Conv1d, group_image
 from .padding import get_pad
 
@@ -140,3 +140,27 @@ class ResidualStack(torch.nn.Module):
             skip = stream_pointwise(self.skip_layer, c, precision=precision)
             t = conv0.stream_forward(c, *next(hist), precision=precision, pre_act=a0.kind, pre_slope=a0.slope)
             return stream_pointwise(conv1, t, precision=precision, pre_act=a1.kind, pre_slope=a1.slope, add1=skip)
+
+    # ---- the NON-causal stack streamed with a fixed look-ahead (utils.MelGANLookaheadStream)
+    def lookahead_plan(self, delay_in, rate):
+        """Delay plan of the non-causal stack on an input delayed by ``delay_in`` columns -> ``(launches, delay_out)``:
+        the skip 1 x 1 at the input's delay, the reflect-padded dilated convolution (the mirrored form), which adds its
+        padding, and the second 1 x 1 with the skip as addend 1 through a delay line of that padding.  ValueError for a
+        causal stack and for a layer without such a form."""
+        if self.use_causal_conv:
+            raise ValueError("ResidualStack: a causal stack streams without look-ahead (utils.CausalStream)")
+        conv0, conv1, skip = self.unit_convs()
+        d_skip = lookahead_delay(skip, delay_in)
+        d0 = mirrored_delay(conv0, delay_in)
+        d1 = lookahead_delay(conv1, d0)
+        return [LookaheadLaunch(skip, rate, d_skip, 0, 0), LookaheadLaunch(conv0, rate, d0, 0, 0),
+                LookaheadLaunch(conv1, rate, d1, d1 - d_skip, 0)], d1
+
+    def lookahead_forward(self, c, walk):
+        """The non-causal ``forward`` on the next chunk of a look-ahead stream: the three launches of
+        :meth:`lookahead_plan` through ``walk`` (a :class:`layers.causal_conv.LookaheadWalk`), which delays the skip."""
+        a0, a1 = self.stack[0], self.stack[3]
+        conv0, conv1, skip_layer = self.unit_convs()
+        skip = walk.run(skip_layer, c)
+        t = walk.run(conv0, c, pre_act=a0.kind, pre_slope=a0.slope)
+        return walk.run(conv1, t, add1=skip, pre_act=a1.kind, pre_slope=a1.slope)

@@ -6,7 +6,8 @@ import numpy as np
 import torch
 
 from ..layers.activation import FusedActivation, PreActivated, deferrable
-from ..layers.causal_conv import CausalConv1d, CausalConvTranspose1d, stream_history_pairs
+from ..layers.causal_conv import (CausalConv1d, CausalConvTranspose1d, LookaheadLaunch, lookahead_delay, mirrored_delay,
+                                  stream_history_pairs)
 from ..layers.conv import Conv1d, ConvTranspose1d
 from ..layers.padding import FusedPad, get_pad
 from ..layers.pooling import get_pooling
@@ -156,6 +157,66 @@ class MelGANGenerator(torch.nn.Module, _MelGANNormMixin):
             if i == last_conv and self.use_final_nonlinear_activation:
                 kw["post_act"] = "tanh"
             x = m.stream_forward(x, *next(hist), precision=precision, **kw)
+        return x
+
+    def _lookahead_walk(self):
+        """``(module, pending activation, is last convolution)`` of the modules that compute, in ``forward`` order."""
+        mods = list(self.melgan)
+        last_conv = max(i for i, m in enumerate(mods) if isinstance(m, Conv1d))
+        act = None
+        for i, m in enumerate(mods):
+            if isinstance(m, FusedActivation):
+                act = m
+            elif isinstance(m, ResidualStack):
+                yield m, None, False
+            elif isinstance(m, (Conv1d, ConvTranspose1d)):
+                yield m, act, i == last_conv
+                act = None
+
+    def lookahead_plan(self):
+        """Delay plan of the NON-causal generator streamed with a fixed look-ahead
+        (:class:`utils.MelGANLookaheadStream`): one ``LookaheadLaunch(conv, rate, delay, delay1, delay2)``
+        per convolution in the order :meth:`lookahead_forward` runs them.  The reflect-padded convolutions (the first and
+        last one, each stack's dilated one) run the mirrored form of the streaming kernel, the transposed and 1 x 1 ones
+        the delayed form; a residual stack is three launches (``ResidualStack.lookahead_plan``).  The last launch's delay
+        is the generator's latency in output columns (samples, or sub-band columns of a multi-band model).  Pure host
+        logic over the module geometry.  ValueError for a causal generator, for a ``pad`` other than ``ReflectionPad1d``
+        and for a layer without a causal form (an even kernel)."""
+        if isinstance(self.melgan[0], CausalConv1d):
+            raise ValueError("MelGANGenerator: a causal generator (use_causal_conv=True) streams without look-ahead "
+                             "(utils.CausalStream)")
+        for m in self.melgan:
+            if isinstance(m, FusedPad) and m.mode != "reflect":
+                raise ValueError(f"MelGANGenerator: pad = {m.__class__.__name__} ({m.mode}); only a ReflectionPad1d model "
+                                 "streams with a look-ahead (the mirrored form of the streaming kernel)")
+        plan, delay, rate = [], 0, 1
+        for m, _, _ in self._lookahead_walk():
+            if isinstance(m, ResidualStack):
+                launches, delay = m.lookahead_plan(delay, rate)
+                plan += launches
+                continue
+            if m.transposed:
+                delay, rate = lookahead_delay(m, delay), rate * m.stride
+            else:
+                delay = mirrored_delay(m, delay)
+            plan.append(LookaheadLaunch(m, rate, delay, 0, 0))
+        return plan
+
+    @torch.no_grad()
+    def lookahead_forward(self, c, walk):
+        """The NON-causal ``forward`` on the next chunk ``c`` (B, in_channels, n) of a look-ahead stream -> (B,
+        out_channels, n * upsample_factor), late by the plan's last delay: the modules, order and fused epilogues of
+        ``forward``, every convolution in its causal form through ``walk`` (a :class:`layers.causal_conv.LookaheadWalk`
+        over :meth:`lookahead_plan`)."""
+        x = c
+        for m, act, last in self._lookahead_walk():
+            if isinstance(m, ResidualStack):
+                x = m.lookahead_forward(x, walk)
+                continue
+            kw = dict(pre_act=act.kind, pre_slope=act.slope) if act is not None else {}
+            if last and self.use_final_nonlinear_activation:
+                kw["post_act"] = "tanh"
+            x = walk.run(m, x, **kw)
         return x
 
     def register_stats(self, stats):

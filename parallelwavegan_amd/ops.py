@@ -370,6 +370,33 @@ def _conv1d_stream_delayed(entry, name, desc, x, hist_in, hist_out, image, bias,
     return out
 
 
+def conv1d_stream_mirrored_supported(desc):
+    """Does the mirrored form of the streaming kernel -- the reflect-padded layer of a non-causal network in a
+    look-ahead stream -- cover this descriptor (the layer's causal descriptor with ``pad_mode="reflect"``)?  Host logic
+    only; ``_lib.lib().pwg_last_error()`` names the reason for a False."""
+    return bool(_lib.lib().pwg_conv1d_stream_mirrored_supported(ctypes.byref(desc)))
+
+
+_I32_MAX = 2 ** 31 - 1
+
+
+def conv1d_stream_mirrored_forward(desc, x, hist_in, hist_out, w_packed, bias=None, in_window=(0, None), valid=None,
+                                   out=None):
+    """:func:`conv1d_stream_delayed_forward` for a reflect-padded layer, without addends: the input is valid on
+    ``in_window = (lo, hi)`` (chunk-relative input columns, unclamped: ``lo < 0`` lies in the history, ``hi`` None is not
+    known yet) and a window column outside it reads its mirror image; history and chunk stay raw.  Output columns outside
+    ``valid`` are stored as exact zeros.  One launch."""
+    _require_device(x, hist_in, hist_out, w_packed, bias, out)
+    out = _conv1d_stream_out(desc, x, hist_in, hist_out, None, None, out)
+    lo, hi = (0, desc.t_out) if valid is None else valid
+    in_lo, in_hi = in_window
+    clamp = lambda v: max(-_I32_MAX, min(_I32_MAX, int(v)))  # noqa: E731  (the library saturates further)
+    _lib.check(_lib.lib().pwg_conv1d_stream_mirrored_forward(
+        ctypes.byref(desc), _ptr(x), _ptr(hist_in), _ptr(hist_out), _ptr(w_packed), _ptr(bias), _ptr(out), clamp(in_lo),
+        _I32_MAX if in_hi is None else clamp(in_hi), int(lo), int(hi), _stream()), "conv1d_stream_mirrored_forward")
+    return out
+
+
 def conv1d_stream_bf16_supported(desc):
     """Does the bf16-operand streaming kernel (csrc/conv1d_stream_bf16.hip) cover this descriptor?  It answers exactly
     as :func:`conv1d_stream_supported`.  Host logic only; ``_lib.lib().pwg_last_error()`` names the reason for a False."""

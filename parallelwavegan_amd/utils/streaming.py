@@ -25,7 +25,9 @@ symmetric filter adds a fixed latency of ``latency_samples`` (32 for the recipe 
 ``LookaheadStream`` streams the standard NON-causal HiFi-GAN: every layer runs in its causal form on a shifted time
 axis, so a push of ``n`` frames still costs ``n`` frames of work and every sample leaves a fixed ``latency_samples``
 late (3258 samples, 12.73 frames, for HiFi-GAN V1).  ``PWGLookaheadStream`` does the same for the
-standard NON-causal Parallel WaveGAN (3921 samples, 15.3 frames, for ``parallel_wavegan.v1``).
+standard NON-causal Parallel WaveGAN (3921 samples, 15.3 frames, for ``parallel_wavegan.v1``), and
+``MelGANLookaheadStream`` for the standard NON-causal, reflect-padded MelGAN and multi-band MelGAN, whose reflect-padded
+layers mirror their window on read (1425 samples for ``melgan.v1``, 2720 for ``multi_band_melgan.v2``).
 """
 import ctypes
 
@@ -34,7 +36,7 @@ import torch
 from .. import _lib
 from ..graphs import GraphedInference
 from ..ops import (_ptr, _require_device, _stream, conv1d_stream_bf16_delayed_supported, conv1d_stream_bf16_supported,
-                   conv1d_stream_delayed_supported, conv1d_stream_supported)
+                   conv1d_stream_delayed_supported, conv1d_stream_mirrored_supported, conv1d_stream_supported)
 
 
 def normalize_transpose(c, mean=None, scale=None):
@@ -657,7 +659,8 @@ class LookaheadStream(_Stream):
             raise ValueError(f"LookaheadStream: precision must be None, 'fp32' or 'bf16', got {precision!r}")
         if not isinstance(model, HiFiGANGenerator):
             raise ValueError(f"LookaheadStream: {model.__class__.__name__} is not supported (only the non-causal "
-                             "HiFiGANGenerator; a reflect-padded MelGAN mirrors columns that have not arrived)")
+                             "HiFiGANGenerator; a non-causal MelGANGenerator streams through "
+                             "utils.MelGANLookaheadStream, a ParallelWaveGANGenerator through utils.PWGLookaheadStream)")
         if model.use_causal_conv:
             raise ValueError("LookaheadStream: the model is causal (use_causal_conv=True) and streams without look-ahead "
                              "through utils.CausalStream")
@@ -737,6 +740,206 @@ class LookaheadStream(_Stream):
         zeros = torch.zeros((self.batch, self._in_channels, self.latency_frames), device=self._device)
         y = self._run(zeros, self._halves[self._cur], self._halves[1 - self._cur], total, total)
         y = y[:, max(0, self.latency_samples - total * self.up):self.latency_samples].contiguous()
+        self._flushed = True  # (the halves are not swapped: nothing may follow but reset())
+        self.samples_out += y.shape[1]
+        return y
+
+
+class MelGANLookaheadStream(_Stream):
+    """Stateful streaming synthesis for the standard NON-causal ``MelGANGenerator`` (reflect padding: every recipe and
+    released checkpoint, ``multi_band_melgan.v2`` included) with a fixed look-ahead.  The interface and the emission
+    rule are :class:`LookaheadStream`'s: after any push the samples emitted total ``max(0, frames_in * up -
+    latency_samples)``, ``flush()`` returns the tail, after which the emissions total ``frames * up`` samples; any
+    partition of the same frames gives bit-identical audio, equal to the whole-utterance ``forward`` / ``inference`` up
+    to fp32 summation order.  ``latency_samples`` is 1425 (5.6 frames) for ``melgan.v1``, 2720 (10.6 frames) for the
+    LJSpeech ``multi_band_melgan.v2`` (scales ``[8, 4, 2]``) and 4208 (14.0 frames) for its 24 kHz variants (``[5, 5, 3]``).
+
+    How: as in :class:`LookaheadStream` every layer runs in its causal form on a shifted time axis.
+    A reflect-padded layer of padding ``p`` produces output column ``q`` once input column ``q + p`` has arrived, and by
+    then the columns reflection reads at either edge have arrived too; its launch (csrc/conv1d_stream.hip, the mirrored
+    form) reads its window through a mirror at the edges of the input's valid window, while the history keeps the raw
+    stored zeros.  The transposed and 1 x 1 convolutions run the delayed form unchanged; a residual stack is three
+    launches, the skip branch going through a delay line.  ``model.lookahead_plan()`` lists the delays.
+
+    Multi-band (``model.pqmf`` attached, ``out_channels == pqmf.subbands``): the sub-band columns of a push go through
+    ``PQMF.stream_synthesis`` in the same push, as in :class:`CausalStream` -- the stored zeros around the utterance are
+    the zero padding the whole-utterance synthesis applies -- and ``latency_samples`` = generator delay * K + the PQMF's
+    ``K * stream_delay_columns``.  ``flush()`` drains that tail too.
+
+    ``use_graph``: a captured graph has fixed window arguments, so a push replays one only if no launch has an edge of
+    the utterance in its window or history and nothing is trimmed from its emission: ``settle_frames`` frames went
+    before it (``frames_before * rate >= delay + pad`` for every launch, and ``latency_frames``).  Earlier pushes and
+    ``flush()`` run eagerly.  ``flush()`` pushes ``latency_frames`` dummy frames with the end-of-utterance windows; their
+    content is never read, because the first layer mirrors at the utterance's end.  An utterance too short for
+    reflection (fewer than ``min_frames`` frames: 4 for a first layer of kernel 7), which the whole-utterance forward
+    cannot pad either, makes ``flush()`` raise.  ``close()`` does not flush: an unflushed tail is dropped.
+
+    ``precision`` may be ``None`` or ``"fp32"``: the mirrored form has no bf16 form yet.
+    """
+
+    warmup_frames = 1
+
+    def __init__(self, model, batch=1, use_graph=True, normalize_before=False, precision=None):
+        from ..layers.causal_conv import (launch_desc, launch_is_mirrored, lookahead_settle_frames, lookahead_state_shapes,
+                                          mirrored_min_frames)
+
+        if precision == "bf16":
+            raise ValueError("MelGANLookaheadStream: precision='bf16' is not available: the mirrored form of the streaming "
+                             "kernel, which the reflect-padded layers run, does not exist with bf16 operands yet")
+        if precision not in (None, "fp32"):
+            raise ValueError(f"MelGANLookaheadStream: precision must be None or 'fp32', got {precision!r}")
+        plan, pqmf, out_channels = self._checked_model(model)
+        batch = self._checked_batch(batch)
+        for launch in plan:
+            desc = launch_desc(launch, batch, 8)
+            ok = conv1d_stream_mirrored_supported(desc) if launch_is_mirrored(launch) else \
+                conv1d_stream_delayed_supported(desc, launch.delay1, launch.delay2)
+            if not ok:
+                raise ValueError(f"MelGANLookaheadStream: {launch.conv} cannot be streamed: "
+                                 + _lib.lib().pwg_last_error().decode(errors="replace"))
+        self.precision = "fp32"
+        self.pqmf = pqmf
+        self.subbands = out_channels
+        self.up = model.upsample_factor * out_channels  # samples per frame
+        self._plan = plan
+        self._in_channels = plan[0].conv.in_channels
+        self._pq_delay = pqmf.stream_delay_columns if pqmf is not None else 0
+        self._front = plan[-1].delay * out_channels  # samples the generator's own delay puts in front of the audio
+        self.latency_samples = self._front + self._pq_delay * out_channels
+        self.latency_frames = -(-self.latency_samples // self.up)
+        self.settle_frames = max(lookahead_settle_frames(plan), self.latency_frames)
+        self.min_frames = mirrored_min_frames(plan)
+        super().__init__(model, [], batch, use_graph, normalize_before,
+                         lookahead_state_shapes(plan, batch) + ([pqmf.history_shape(batch)] if pqmf is not None else []))
+
+    @staticmethod
+    def _checked_model(model):
+        """The refusals that need no device, in order: the class, a causal model, the padding and the layer geometry (the
+        plan), the sub-bands, a bf16 model -> ``(plan, pqmf or None, out_channels)``."""
+        from ..layers.conv import each_conv
+        from ..layers.pqmf import PQMF
+        from ..models import MelGANGenerator
+
+        name = "MelGANLookaheadStream"
+        if not isinstance(model, MelGANGenerator):
+            raise ValueError(f"{name}: {model.__class__.__name__} is not supported (only the non-causal MelGANGenerator; "
+                             "HiFiGANGenerator streams through utils.LookaheadStream, ParallelWaveGANGenerator through "
+                             "utils.PWGLookaheadStream)")
+        try:
+            plan = model.lookahead_plan()  # ValueError: causal, a pad other than reflection, an even kernel
+        except ValueError as e:
+            raise ValueError(f"{name}: {e}") from None
+        out_channels = plan[-1].conv.out_channels
+        pqmf = getattr(model, "pqmf", None)
+        if out_channels != 1 and pqmf is None:
+            raise ValueError(f"{name}: the generator emits {out_channels} sub-bands; only a multi-band MelGANGenerator with "
+                             "its PQMF attached (model.pqmf = PQMF(subbands=...), as utils.load_model does) can be "
+                             "streamed, through the stateful PQMF synthesis")
+        if pqmf is not None:
+            if not isinstance(pqmf, PQMF) or pqmf.subbands != out_channels:
+                raise ValueError(f"{name}: model.pqmf must be a PQMF with as many sub-bands as the generator emits "
+                                 f"({out_channels}); got {getattr(pqmf, 'subbands', pqmf.__class__.__name__)}")
+            if pqmf.subbands > 8:
+                raise ValueError(f"{name}: a PQMF of {pqmf.subbands} sub-bands cannot be streamed (the stream kernel "
+                                 "covers up to 8)")
+        if any(cv.precision != "fp32" for cv in each_conv(model)):
+            raise ValueError(f"{name}: the model is in bf16 inference precision; the look-ahead stream of a reflect-padded "
+                             "model is fp32 (utils.set_inference_precision(model, 'fp32'))")
+        return plan, pqmf, out_channels
+
+    @classmethod
+    def latency_samples_of(cls, model):
+        """Samples every output leaves late, from the module geometry alone (no device, no kernel): the generator's
+        delay times the sub-band count, plus the PQMF's ``K * stream_delay_columns`` for a multi-band model."""
+        plan, pqmf, k = cls._checked_model(model)
+        return (plan[-1].delay + (pqmf.stream_delay_columns if pqmf is not None else 0)) * k
+
+    @classmethod
+    def settle_frames_of(cls, model):
+        """Frames after which a push has no edge of the utterance in any window or history and emits ``n * up``
+        samples, from the module geometry alone: the plan's ``lookahead_settle_frames`` and ``latency_frames``."""
+        from ..layers.causal_conv import lookahead_settle_frames
+
+        plan, _, k = cls._checked_model(model)
+        up = model.upsample_factor * k
+        return max(lookahead_settle_frames(plan), -(-cls.latency_samples_of(model) // up))
+
+    @classmethod
+    def min_frames_of(cls, model):
+        """The shortest utterance reflection can pad (``layers.causal_conv.mirrored_min_frames`` of the plan)."""
+        from ..layers.causal_conv import mirrored_min_frames
+
+        return mirrored_min_frames(cls._checked_model(model)[0])
+
+    def reset(self):
+        """Back to start of stream; an unflushed tail is dropped."""
+        self._restart()
+        self._flushed = False
+
+    def _run(self, c, state_in, state_out, frames_before=None, total_frames=None):
+        """``c``: (batch, C, n) features, normalised; ``state_in`` (None: start of stream) / ``state_out``: one
+        ping-pong half each (a multi-band stream's end with the PQMF's history); ``frames_before`` None: steady state.
+        -> (batch, samples): the positions of the whole late stream (zeros, then the utterance) this push completes."""
+        from ..layers.causal_conv import LookaheadWalk
+
+        k = len(state_out) - (self.pqmf is not None)
+        walk = LookaheadWalk(self._plan, None if state_in is None else state_in[:k], state_out[:k], frames_before,
+                             total_frames)
+        y = self.model.lookahead_forward(c, walk)
+        if self.pqmf is None:
+            return y.reshape(self.batch, -1)
+        n_cols = y.shape[-1]
+        n_emit = n_cols if frames_before is None else self._positions(frames_before, c.shape[-1])[1] // self.subbands
+        return self.pqmf.stream_synthesis(y, None if state_in is None else state_in[-1], state_out[-1], n_emit)
+
+    def _positions(self, frames_before, n):
+        """``(first, count)``: the samples of the whole late stream that a push of ``n`` frames after ``frames_before``
+        completes -- all of its ``n * up`` for a full-band model, those ``stream_delay_columns`` behind the newest
+        column for a multi-band one."""
+        hold = self._pq_delay * self.subbands
+        first = max(0, frames_before * self.up - hold)
+        return first, max(0, (frames_before + n) * self.up - hold) - first
+
+    def _capture(self, feats):
+        static_in = feats.clone()
+        return static_in, _capture_directions(self._halves, lambda si, so: self._run(self._features(static_in), si, so))
+
+    @torch.no_grad()
+    def push(self, feats):
+        """feats: (n, C) or (batch, n, C) float features -> (batch, samples) fp32, the samples that became complete:
+        ``n * up`` once ``latency_samples`` are behind, fewer (or none) before.  The result is the caller's own tensor."""
+        if self._flushed:
+            raise RuntimeError("MelGANLookaheadStream.push: the utterance was flushed; reset() starts the next one")
+        feats = self._coerce(feats)
+        n = feats.shape[1]
+        if n == 0:
+            return self._empty()
+        before = self.frames_in
+        self.frames_in += n
+        skip = max(0, self._front - self._positions(before, n)[0])  # samples of this push in front of the first one
+        steady = before >= self.settle_frames                       # no edge in reach, nothing to trim
+        return self._step(n, (n, feats.shape[2]),
+                          lambda si, so: self._run(self._features(feats), si, so, before)[:, skip:].contiguous(),
+                          (lambda: self._capture(feats)) if self.use_graph and steady else None,
+                          lambda static_in: static_in.copy_(feats, non_blocking=True))
+
+    @torch.no_grad()
+    def flush(self):
+        """End of the utterance: ``latency_frames`` dummy frames with the end-of-utterance windows (the first layer
+        mirrors at the utterance's last frame, so their content is never read; every launch stores zeros past the
+        utterance's last column; a multi-band model's PQMF tail drains with them) -> the last ``min(latency_samples,
+        frames * up)`` samples, (batch, samples).  Zero-length before anything was pushed and on a second call.
+        RuntimeError for an utterance shorter than ``min_frames``.  The next utterance starts with ``reset()``."""
+        if not self._started or self._flushed:
+            return self._empty()
+        total = self.frames_in
+        if total < self.min_frames:
+            raise RuntimeError(f"MelGANLookaheadStream.flush: the utterance has {total} frame(s); reflection padding needs "
+                               f"at least {self.min_frames} (the whole-utterance forward cannot pad a shorter one either)")
+        dummy = torch.zeros((self.batch, self._in_channels, self.latency_frames), device=self._device)
+        y = self._run(dummy, self._halves[self._cur], self._halves[1 - self._cur], total, total)
+        first = self._positions(total, self.latency_frames)[0]
+        y = y[:, max(0, self._front - first):self._front + total * self.up - first].contiguous()
         self._flushed = True  # (the halves are not swapped: nothing may follow but reset())
         self.samples_out += y.shape[1]
         return y

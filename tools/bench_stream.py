@@ -51,7 +51,15 @@ measurements alternating in one process as for ``--lookahead --precision bf16``:
 forward of the two fp32 tools above in fp32 and -- on a second instance of the model put in bf16 inference precision -- in
 bf16.  Into profiles/stream_pwg_bf16_infer.json and profiles/stream_pwg_lookahead_bf16_infer.json.
 
-usage: python tools/bench_stream.py [--model pwg [--lookahead]] [--multiband] [--precision bf16] [--lookahead] [--reps 200]
+``--model melgan --lookahead [--multiband]``: the standard NON-causal MelGAN (melgan.v1 geometry) or, with ``--multiband``,
+the non-causal multi-band MelGAN (multi_band_melgan.v2 generator, PQMF attached) through ``utils.MelGANLookaheadStream``
+(the reflect-padded layers on the mirrored form of csrc/conv1d_stream.hip) against halo recompute, the
+method of ``--lookahead``: steady-state pushes of 4 / 8 / 32 frames at 1 and 16 streams, the halo side ONE graph of the
+whole-utterance forward (and, multi-band, ``pqmf.synthesis`` of its output) over ``left + n + right`` frames of the
+generator's reach (the PQMF filter's own 31 samples are not added: the comparison leans towards the halo path).  Into
+profiles/stream_melgan_lookahead_infer.json; ``--multiband`` adds the multi-band model to the same file.
+
+usage: python tools/bench_stream.py [--model pwg|melgan [--lookahead]] [--multiband] [--precision bf16] [--lookahead] [--reps 200]
                                     [--repeats 3] [--out profiles/stream_infer.json]
 """
 import argparse
@@ -67,8 +75,8 @@ from parallelwavegan_amd import ops  # noqa: E402
 from parallelwavegan_amd.graphs import GraphedInference  # noqa: E402
 from parallelwavegan_amd.layers import PQMF  # noqa: E402
 from parallelwavegan_amd.models import HiFiGANGenerator, MelGANGenerator, ParallelWaveGANGenerator  # noqa: E402
-from parallelwavegan_amd.utils import (CausalStream, LookaheadStream, PWGLookaheadStream, PWGStream,  # noqa: E402
-                                       set_inference_precision)
+from parallelwavegan_amd.utils import (CausalStream, LookaheadStream, MelGANLookaheadStream,  # noqa: E402
+                                       PWGLookaheadStream, PWGStream, set_inference_precision)
 from parallelwavegan_amd.utils.streaming import receptive_field_frames  # noqa: E402
 from tests.golden import synth  # noqa: E402
 
@@ -104,13 +112,21 @@ def build_melgan(dev):
     return g.to(dev).eval()
 
 
-def build_multiband(dev):
-    """Causal multi-band MelGAN at the multi_band_melgan.v2 geometry on seeded weights, weight norm removed, PQMF
-    attached (the recipe's default filter)."""
+def build_melgan_noncausal(dev):
+    """The standard (non-causal) MelGAN at the recipe's geometry on the same seeded weights, weight norm removed."""
+    g = MelGANGenerator(**dict(MELGAN_RECIPE_CAUSAL, use_causal_conv=False))
+    g.load_state_dict(synth.synth_state_dict(g.state_dict(), seed=12, g_scale=synth.MELGAN_G_SCALE))
+    g.remove_weight_norm()
+    return g.to(dev).eval()
+
+
+def build_multiband(dev, causal=True):
+    """Multi-band MelGAN at the multi_band_melgan.v2 geometry (causal, or the standard non-causal one) on seeded
+    weights, weight norm removed, PQMF attached (the recipe's default filter)."""
     import yaml
 
     with open(os.path.join(ROOT, "tests", "fixtures", "conf", "multi_band_melgan.v2.yaml")) as f:
-        params = dict(yaml.safe_load(f)["generator_params"], use_causal_conv=True)
+        params = dict(yaml.safe_load(f)["generator_params"], use_causal_conv=causal)
     g = MelGANGenerator(**params)
     g.load_state_dict(synth.synth_state_dict(g.state_dict(), seed=13, g_scale=synth.MELGAN_G_SCALE))
     g.remove_weight_norm()
@@ -169,13 +185,17 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=3)
-    ap.add_argument("--model", choices=("default", "pwg"), default="default")
+    ap.add_argument("--model", choices=("default", "pwg", "melgan"), default="default")
     ap.add_argument("--multiband", action="store_true")
     ap.add_argument("--precision", choices=("fp32", "bf16"), default="fp32")
     ap.add_argument("--lookahead", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    if args.lookahead and args.multiband:
+    if args.model == "melgan":
+        if not args.lookahead or args.precision != "fp32":
+            ap.error("--model melgan is the fp32 look-ahead stream of the non-causal MelGAN: pass --lookahead (no --precision)")
+        args.out = args.out or os.path.join(ROOT, "profiles", "stream_melgan_lookahead_infer.json")
+    elif args.lookahead and args.multiband:
         ap.error("--lookahead is the non-causal HiFi-GAN or (--model pwg) Parallel WaveGAN stream (no --multiband)")
     if args.model == "pwg" and args.multiband:
         ap.error("--model pwg is the full-band Parallel WaveGAN stream (no --multiband)")
@@ -225,7 +245,12 @@ def main():
         print(json.dumps({"out": args.out, "points": [[p["model"], p["streams"], p["chunk_frames"], p["fp32_push_ms"],
                                                        p["bf16_push_ms"]] for p in rec["points"]]}))
         return
-    if args.lookahead and args.model == "pwg":
+    if args.model == "melgan":
+        measure_lookahead(rec, "melgan_v1", build_melgan_noncausal(dev), CHUNKS, gen, args, dev, MelGANLookaheadStream)
+        if args.multiband:
+            measure_lookahead(rec, "multi_band_melgan_v2", build_multiband(dev, causal=False), CHUNKS, gen, args, dev,
+                              MelGANLookaheadStream)
+    elif args.lookahead and args.model == "pwg":
         measure_pwg_lookahead(rec, "parallel_wavegan_v1", build_pwg(dev, causal=False), CHUNKS, gen, args, dev)
     elif args.lookahead:
         measure_lookahead(rec, "hifigan_v1", build_noncausal(dev), CHUNKS, gen, args, dev)
@@ -350,12 +375,16 @@ def measure_pwg(rec, name, model, chunks, gen, args, dev):
                   flush=True)
 
 
-def measure_lookahead(rec, name, model, chunks, gen, args, dev):
-    """Steady-state ``LookaheadStream.push`` against the whole-utterance forward over ``left + n + right`` frames,
+def measure_lookahead(rec, name, model, chunks, gen, args, dev, stream_cls=LookaheadStream):
+    """Steady-state ``stream_cls.push`` (``LookaheadStream``, ``MelGANLookaheadStream``) against the whole-utterance
+    forward over ``left + n + right`` frames -- and, for a multi-band model, the PQMF synthesis of its output --
     alternating."""
     left, right = receptive_field_frames(model)
-    up = model.upsample_factor
-    probe = LookaheadStream(model, use_graph=False)
+    pqmf = getattr(model, "pqmf", None)
+    up = model.upsample_factor * (pqmf.subbands if pqmf is not None else 1)
+    whole = model if pqmf is None else (lambda c: pqmf.synthesis(model(c)))
+    probe = stream_cls(model, use_graph=False)
+    settle = getattr(probe, "settle_frames", probe.latency_frames)  # frames before a push replays a graph
     rec["models"][name] = {"workload": "seeded weights, weight norm removed", "halo_left_frames": left,
                            "halo_right_frames": right, "latency_samples": probe.latency_samples,
                            "latency_frames": probe.latency_frames, "stream_state_bytes_per_stream": probe.state_bytes}
@@ -363,20 +392,20 @@ def measure_lookahead(rec, name, model, chunks, gen, args, dev):
         for n in chunks:
             feats = torch.randn(b, n, 80, generator=gen).to(dev)
             ctx = torch.randn(b, 80, left + n + right, generator=gen).to(dev)
-            s = LookaheadStream(model, batch=b, use_graph=True)
-            halo = GraphedInference(model)
-            while s.frames_in < s.latency_frames + 4 * n:  # the eager start, then both graph directions; the halo graph
+            s = stream_cls(model, batch=b, use_graph=True)
+            halo = GraphedInference(whole)
+            while s.frames_in < settle + 4 * n:  # the eager start, then both graph directions; the halo graph
                 s.push(feats)
                 halo(ctx)
             t_s, t_h = [], []
             for _ in range(args.repeats):
                 t_s.append(event_ms(lambda: s.push(feats), args.reps))
                 t_h.append(event_ms(lambda: halo(ctx), args.reps))
-            eager = LookaheadStream(model, batch=b, use_graph=False)
-            while eager.frames_in < eager.latency_frames:  # past the partial windows
+            eager = stream_cls(model, batch=b, use_graph=False)
+            while eager.frames_in < settle:  # past the partial windows
                 eager.push(feats)
             n_s, fam_s = launches(lambda: eager.push(feats))
-            n_h, fam_h = launches(lambda: model(ctx))
+            n_h, fam_h = launches(lambda: whole(ctx))
             med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
             spread = max(max(t_s) - min(t_s), max(t_h) - min(t_h))
             p = {"model": name, "streams": b, "chunk_frames": n, "samples_per_push": b * n * up,
