@@ -340,36 +340,29 @@ extern "C" size_t pwg_conv1d_stream_hist_floats(const pwg_conv1d_desc* d) {
   return (size_t)d->batch * d->c_in * g.hist;
 }
 
+// The fields of the argument struct that come from the fp32 packed image -> the LDS bytes of the staged window
+static size_t fill_image_args(StreamArgs* a, const float* w_packed, const StreamGeom& g, const StreamTile& tile) {
+  a->w = w_packed;
+  a->cin_pad = g.cin_pad;
+  a->m_pad = g.m_pad;
+  a->xs = xs_stride(16 * tile.tn + g.hist);
+  return (size_t)SC * a->xs * sizeof(float);
+}
+
+static double image_bytes(const StreamGeom& g) { return 4.0 * (double)g.taps * g.cin_pad * g.m_pad; }
+
 extern "C" int pwg_conv1d_stream_forward(const pwg_conv1d_desc* d, const float* x, const float* hist_in, float* hist_out,
                                          const float* w_packed, const float* bias, const float* add1, const float* add2,
                                          float* y, void* stream_) {
   StreamGeom g;
-  int rc = stream_geometry(d, &g);
-  if (rc != PWG_OK) return rc;
-  hipStream_t stream = (hipStream_t)stream_;
-  rc = stream_check_pointers("conv1d_stream", d, g, x, w_packed, y, hist_in, hist_out);
+  const int rc = stream_geometry(d, &g);
   if (rc != PWG_OK) return rc;
   PWG_REQUIRE((reinterpret_cast<uintptr_t>(w_packed) & 3u) == 0, PWG_ERR_BAD_SHAPE, "conv1d_stream: unaligned weight image");
-  const int n = d->t_in;
-  const StreamTile tile = stream_tile(n, g.m, d->batch);
-
+  const StreamTile tile = stream_tile(d->t_in, g.m, d->batch);
   StreamArgs a;
-  stream_fill_args(&a, d, g, tile, x, hist_in, hist_out, bias, add1, add2, y);
-  a.w = w_packed;
-  a.cin_pad = g.cin_pad;
-  a.m_pad = g.m_pad;
-  a.xs = xs_stride(16 * tile.tn + g.hist);
-
-  const double out_elems = (double)d->batch * d->c_out * d->t_out;
-  const double flops = 2.0 * (double)d->batch * g.m * n * g.taps * d->c_in;
-  const double bytes = 4.0 * ((double)d->batch * d->c_in * (n + 2.0 * g.hist) +
-                              out_elems * (1 + (add1 ? 1 : 0) + (add2 ? 1 : 0)) + (double)g.taps * g.cin_pad * g.m_pad);
-  maybe_poison_lds(stream);
-  ProfScope prof(stream, "conv1d_stream_kernel", flops, bytes);
-  stream_launch<Kernel>(tile, d->transposed != 0, a, g.m, d->batch,
-                        stream_lds_bytes((size_t)SC * a.xs * sizeof(float), tile), stream);
-  PWG_CHECK_LAUNCH("conv1d_stream");
-  return PWG_OK;
+  const size_t window = fill_image_args(&a, w_packed, g, tile);
+  return stream_run<Kernel>("conv1d_stream", "conv1d_stream_kernel", d, g, tile, &a, x, hist_in, hist_out, w_packed, bias,
+                            add1, add2, y, window, 0.0, image_bytes(g), (hipStream_t)stream_);
 }
 
 extern "C" int pwg_conv1d_stream_delayed_supported(const pwg_conv1d_desc* d, int32_t delay1, int32_t delay2) {
@@ -386,35 +379,17 @@ extern "C" int pwg_conv1d_stream_delayed_forward(const pwg_conv1d_desc* d, const
   StreamGeom g;
   int rc = delayed_geometry(d, delay1, delay2, &g);
   if (rc != PWG_OK) return rc;
-  hipStream_t stream = (hipStream_t)stream_;
-  rc = stream_check_pointers("conv1d_stream_delayed", d, g, x, w_packed, y, hist_in, hist_out);
-  if (rc != PWG_OK) return rc;
   PWG_REQUIRE((reinterpret_cast<uintptr_t>(w_packed) & 3u) == 0, PWG_ERR_BAD_SHAPE,
               "conv1d_stream_delayed: unaligned weight image");
   StreamDelayedArgs a;
   rc = stream_delay_lines("conv1d_stream_delayed", add1, add1_hist_in, add1_hist_out, delay1, add2, add2_hist_in,
                           add2_hist_out, delay2, valid_lo, valid_hi, &a.dl);
   if (rc != PWG_OK) return rc;
-  const int n = d->t_in;
-  const StreamTile tile = stream_tile(n, g.m, d->batch);
-
-  stream_fill_args(&a, d, g, tile, x, hist_in, hist_out, bias, add1, add2, y);
-  a.w = w_packed;
-  a.cin_pad = g.cin_pad;
-  a.m_pad = g.m_pad;
-  a.xs = xs_stride(16 * tile.tn + g.hist);
-
-  const double out_elems = (double)d->batch * d->c_out * d->t_out;
-  const double flops = 2.0 * (double)d->batch * g.m * n * g.taps * d->c_in;
-  const double bytes = 4.0 * ((double)d->batch * d->c_in * (n + 2.0 * g.hist) +
-                              out_elems * (1 + (add1 ? 1 : 0) + (add2 ? 1 : 0)) +
-                              2.0 * d->batch * d->c_out * (delay1 + delay2) + (double)g.taps * g.cin_pad * g.m_pad);
-  maybe_poison_lds(stream);
-  ProfScope prof(stream, "conv1d_stream_delayed_kernel", flops, bytes);
-  stream_launch<DelayedKernel>(tile, d->transposed != 0, a, g.m, d->batch,
-                               stream_lds_bytes((size_t)SC * a.xs * sizeof(float), tile), stream);
-  PWG_CHECK_LAUNCH("conv1d_stream_delayed");
-  return PWG_OK;
+  const StreamTile tile = stream_tile(d->t_in, g.m, d->batch);
+  const size_t window = fill_image_args(&a, w_packed, g, tile);
+  return stream_run<DelayedKernel>("conv1d_stream_delayed", "conv1d_stream_delayed_kernel", d, g, tile, &a, x, hist_in,
+                                   hist_out, w_packed, bias, add1, add2, y, window,
+                                   (double)d->batch * d->c_out * (delay1 + delay2), image_bytes(g), (hipStream_t)stream_);
 }
 
 extern "C" int pwg_conv1d_stream_mirrored_supported(const pwg_conv1d_desc* d) {
@@ -429,37 +404,21 @@ extern "C" int pwg_conv1d_stream_mirrored_forward(const pwg_conv1d_desc* d, cons
   StreamGeom g;
   int rc = mirrored_geometry(d, &g);
   if (rc != PWG_OK) return rc;
-  hipStream_t stream = (hipStream_t)stream_;
-  // history and chunk are read raw (zeros before the stream, stored zeros around the utterance): the launch itself is
-  // a zero-padded one, the reflection lives in the window's mirror rule alone
-  pwg_conv1d_desc raw = *d;
-  raw.pad_mode = PWG_PAD_ZERO;
-  rc = stream_check_pointers("conv1d_stream_mirrored", &raw, g, x, w_packed, y, hist_in, hist_out);
-  if (rc != PWG_OK) return rc;
   PWG_REQUIRE((reinterpret_cast<uintptr_t>(w_packed) & 3u) == 0, PWG_ERR_BAD_SHAPE,
               "conv1d_stream_mirrored: unaligned weight image");
   StreamMirroredArgs a;
   rc = stream_delay_lines("conv1d_stream_mirrored", nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, valid_lo,
                           valid_hi, &a.dl);
   if (rc != PWG_OK) return rc;
-  const int n = d->t_in;
-  const StreamTile tile = stream_tile(n, g.m, d->batch);
-
-  stream_fill_args(&a, &raw, g, tile, x, hist_in, hist_out, bias, nullptr, nullptr, y);
-  a.w = w_packed;
-  a.cin_pad = g.cin_pad;
-  a.m_pad = g.m_pad;
-  a.xs = xs_stride(16 * tile.tn + g.hist);
-  a.in_lo = mirror_bound(in_lo, g.hist, n);
-  a.in_hi = mirror_bound(in_hi, g.hist, n);
-
-  const double flops = 2.0 * (double)d->batch * g.m * n * g.taps * d->c_in;
-  const double bytes = 4.0 * ((double)d->batch * d->c_in * (n + 2.0 * g.hist) + (double)d->batch * d->c_out * d->t_out +
-                              (double)g.taps * g.cin_pad * g.m_pad);
-  maybe_poison_lds(stream);
-  ProfScope prof(stream, "conv1d_stream_mirrored_kernel", flops, bytes);
-  stream_launch<MirroredKernel>(tile, false, a, g.m, d->batch, stream_lds_bytes((size_t)SC * a.xs * sizeof(float), tile),
-                                stream);
-  PWG_CHECK_LAUNCH("conv1d_stream_mirrored");
-  return PWG_OK;
+  const StreamTile tile = stream_tile(d->t_in, g.m, d->batch);
+  const size_t window = fill_image_args(&a, w_packed, g, tile);
+  a.in_lo = mirror_bound(in_lo, g.hist, d->t_in);
+  a.in_hi = mirror_bound(in_hi, g.hist, d->t_in);
+  // history and chunk are read raw (zeros before the stream, stored zeros around the utterance): the launch itself is
+  // a zero-padded one, the reflection lives in the window's mirror rule alone
+  pwg_conv1d_desc raw = *d;
+  raw.pad_mode = PWG_PAD_ZERO;
+  return stream_run<MirroredKernel>("conv1d_stream_mirrored", "conv1d_stream_mirrored_kernel", &raw, g, tile, &a, x, hist_in,
+                                    hist_out, w_packed, bias, nullptr, nullptr, y, window, 0.0, image_bytes(g),
+                                    (hipStream_t)stream_);
 }

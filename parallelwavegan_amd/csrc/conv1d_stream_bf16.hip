@@ -276,36 +276,27 @@ using namespace pwg;
 // Coverage is that of the fp32 stream kernel by construction: a layer that streams in fp32 streams in bf16.
 extern "C" int pwg_conv1d_stream_bf16_supported(const pwg_conv1d_desc* d) { return pwg_conv1d_stream_supported(d); }
 
+// LDS bytes of the staged window
+static size_t window_bytes(const StreamGeom& g, const StreamTile& tile) {
+  return (size_t)(16 * tile.tn + g.hist) * ROW * sizeof(__bf16);
+}
+
 extern "C" int pwg_conv1d_stream_bf16_forward(const pwg_conv1d_desc* d, const float* x, const float* hist_in,
                                               float* hist_out, const void* w_packed_bf16, const float* bias,
                                               const float* add1, const float* add2, float* y, void* stream_) {
   StreamGeom g;
   if (stream_geometry(d, &g) != PWG_OK) return PWG_ERR_UNSUPPORTED;  // (pwg_last_error holds the reason)
-  hipStream_t stream = (hipStream_t)stream_;
   MfmaConvGeom image;
-  int rc = bf16_image("conv1d_stream_bf16", d, &image);
-  if (rc != PWG_OK) return rc;
-  rc = stream_check_pointers("conv1d_stream_bf16", d, g, x, w_packed_bf16, y, hist_in, hist_out);
+  const int rc = bf16_image("conv1d_stream_bf16", d, &image);
   if (rc != PWG_OK) return rc;
   PWG_REQUIRE((reinterpret_cast<uintptr_t>(w_packed_bf16) & 15u) == 0, PWG_ERR_BAD_SHAPE,
               "conv1d_stream_bf16: the weight image must be 16-B aligned");
-  const int n = d->t_in;
-  const StreamTile tile = stream_tile(n, g.m, d->batch);
-
+  const StreamTile tile = stream_tile(d->t_in, g.m, d->batch);
   StreamBf16Args a;
-  stream_fill_args(&a, d, g, tile, x, hist_in, hist_out, bias, add1, add2, y);
   fill_image_args(&a, w_packed_bf16, image, g);
-
-  const double out_elems = (double)d->batch * d->c_out * d->t_out;
-  const double flops = 2.0 * (double)d->batch * g.m * n * g.taps * d->c_in;
-  const double bytes = 4.0 * ((double)d->batch * d->c_in * (n + 2.0 * g.hist) +
-                              out_elems * (1 + (add1 ? 1 : 0) + (add2 ? 1 : 0))) + 2.0 * (double)image_elems(image);
-  maybe_poison_lds(stream);
-  ProfScope prof(stream, "conv1d_stream_bf16_kernel", flops, bytes);
-  stream_launch<Kernel>(tile, d->transposed != 0, a, g.m, d->batch,
-                        stream_lds_bytes((size_t)(16 * tile.tn + g.hist) * ROW * sizeof(__bf16), tile), stream);
-  PWG_CHECK_LAUNCH("conv1d_stream_bf16");
-  return PWG_OK;
+  return stream_run<Kernel>("conv1d_stream_bf16", "conv1d_stream_bf16_kernel", d, g, tile, &a, x, hist_in, hist_out,
+                            w_packed_bf16, bias, add1, add2, y, window_bytes(g, tile), 0.0,
+                            2.0 * (double)image_elems(image), (hipStream_t)stream_);
 }
 
 // Coverage is that of the fp32 delayed form by construction: both go through delayed_geometry().
@@ -322,11 +313,8 @@ extern "C" int pwg_conv1d_stream_bf16_delayed_forward(const pwg_conv1d_desc* d, 
   StreamGeom g;
   int rc = delayed_geometry(d, delay1, delay2, &g);
   if (rc != PWG_OK) return rc;
-  hipStream_t stream = (hipStream_t)stream_;
   MfmaConvGeom image;
   rc = bf16_image("conv1d_stream_bf16_delayed", d, &image);
-  if (rc != PWG_OK) return rc;
-  rc = stream_check_pointers("conv1d_stream_bf16_delayed", d, g, x, w_packed_bf16, y, hist_in, hist_out);
   if (rc != PWG_OK) return rc;
   PWG_REQUIRE((reinterpret_cast<uintptr_t>(w_packed_bf16) & 15u) == 0, PWG_ERR_BAD_SHAPE,
               "conv1d_stream_bf16_delayed: the weight image must be 16-B aligned");
@@ -334,21 +322,10 @@ extern "C" int pwg_conv1d_stream_bf16_delayed_forward(const pwg_conv1d_desc* d, 
   rc = stream_delay_lines("conv1d_stream_bf16_delayed", add1, add1_hist_in, add1_hist_out, delay1, add2, add2_hist_in,
                           add2_hist_out, delay2, valid_lo, valid_hi, &a.dl);
   if (rc != PWG_OK) return rc;
-  const int n = d->t_in;
-  const StreamTile tile = stream_tile(n, g.m, d->batch);
-
-  stream_fill_args(&a, d, g, tile, x, hist_in, hist_out, bias, add1, add2, y);
+  const StreamTile tile = stream_tile(d->t_in, g.m, d->batch);
   fill_image_args(&a, w_packed_bf16, image, g);
-
-  const double out_elems = (double)d->batch * d->c_out * d->t_out;
-  const double flops = 2.0 * (double)d->batch * g.m * n * g.taps * d->c_in;
-  const double bytes = 4.0 * ((double)d->batch * d->c_in * (n + 2.0 * g.hist) +
-                              out_elems * (1 + (add1 ? 1 : 0) + (add2 ? 1 : 0)) +
-                              2.0 * d->batch * d->c_out * (delay1 + delay2)) + 2.0 * (double)image_elems(image);
-  maybe_poison_lds(stream);
-  ProfScope prof(stream, "conv1d_stream_bf16_delayed_kernel", flops, bytes);
-  stream_launch<DelayedKernel>(tile, d->transposed != 0, a, g.m, d->batch,
-                               stream_lds_bytes((size_t)(16 * tile.tn + g.hist) * ROW * sizeof(__bf16), tile), stream);
-  PWG_CHECK_LAUNCH("conv1d_stream_bf16_delayed");
-  return PWG_OK;
+  return stream_run<DelayedKernel>("conv1d_stream_bf16_delayed", "conv1d_stream_bf16_delayed_kernel", d, g, tile, &a, x,
+                                   hist_in, hist_out, w_packed_bf16, bias, add1, add2, y, window_bytes(g, tile),
+                                   (double)d->batch * d->c_out * (delay1 + delay2), 2.0 * (double)image_elems(image),
+                                   (hipStream_t)stream_);
 }

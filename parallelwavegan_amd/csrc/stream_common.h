@@ -8,6 +8,7 @@
 //   tile rule             stream_tile            column tile from n; 32-row blocks only at 2 x 256 or more workgroups
 //   coverage              stream_geometry        defined in conv1d_stream.hip; both precisions admit the same layers
 //                         delayed_geometry       ... and the same delays (what the delayed form adds; defined there too)
+//   host path             stream_run             pointer checks, common arguments, accounting (stream_work), launch
 // Internal to csrc/; the staging loops and contractions of the kernels differ on purpose and stay with them.
 #pragma once
 #include "common.h"
@@ -325,6 +326,39 @@ static inline void stream_launch(const StreamTile& t, bool transposed, const Arg
   else
     kern = transposed ? K<2, 4, true>::fn : K<2, 4, false>::fn;
   hipLaunchKernelGGL(kern, dim3(t.col_tiles, ceil_div(m, 16 * t.tm), batch), dim3(256), lds, stream, a);
+}
+
+// What a launch is accounted with (ProfScope): the contraction, and the bytes of the chunk and both histories, of the
+// output and its addends, of `line_floats` delay-line elements read and as many written, and of the weight image
+struct StreamWork {
+  double flops, bytes;
+};
+static inline StreamWork stream_work(const pwg_conv1d_desc* d, const StreamGeom& g, int addends, double line_floats,
+                                     double image_bytes) {
+  const double n = d->t_in, out_elems = (double)d->batch * d->c_out * d->t_out;
+  return StreamWork{2.0 * (double)d->batch * g.m * n * g.taps * d->c_in,
+                    4.0 * ((double)d->batch * d->c_in * (n + 2.0 * g.hist) + out_elems * (1 + addends) + 2.0 * line_floats) +
+                        image_bytes};
+}
+
+// The host path the conv stream entry points share, from the pointer checks to the launch.  The entry point has done
+// what is its own: the geometry `g` of `d`, the tile, its image and alignment line, the delay lines and every field of
+// `a` beyond StreamCommonArgs.  `name` heads an error text, `scope` names the ProfScope, K is the kernel family
+// (stream_launch), `window_bytes` the LDS of the staged window under `tile`.
+template <template <int, int, bool> class K, class Args>
+static inline int stream_run(const char* name, const char* scope, const pwg_conv1d_desc* d, const StreamGeom& g,
+                             const StreamTile& tile, Args* a, const float* x, const float* hist_in, float* hist_out,
+                             const void* w, const float* bias, const float* add1, const float* add2, float* y,
+                             size_t window_bytes, double line_floats, double image_bytes, hipStream_t stream) {
+  const int rc = stream_check_pointers(name, d, g, x, w, y, hist_in, hist_out);
+  if (rc != PWG_OK) return rc;
+  stream_fill_args(a, d, g, tile, x, hist_in, hist_out, bias, add1, add2, y);
+  const StreamWork work = stream_work(d, g, (add1 ? 1 : 0) + (add2 ? 1 : 0), line_floats, image_bytes);
+  maybe_poison_lds(stream);
+  ProfScope prof(stream, scope, work.flops, work.bytes);
+  stream_launch<K>(tile, d->transposed != 0, *a, g.m, d->batch, stream_lds_bytes(window_bytes, tile), stream);
+  PWG_CHECK_LAUNCH(name);
+  return PWG_OK;
 }
 
 }  // namespace pwg

@@ -116,19 +116,42 @@ def _desc_kw(fused):
     return {k: v for k, v in fused.items() if k not in ("add1", "add2")}
 
 
-def _stream_forward(cv, desc, x, hist_in, hist_out, fused, precision="fp32"):
+# ---- the rule of a stream launch, stated once.  A form's row per precision: the kernel's name in a
+# refusal, the coverage query, the launch.  A (form, precision) without a row does not exist yet.
+_STREAM_KERNELS = {
+    ("plain", "fp32"): ("streaming kernel", ops.conv1d_stream_supported, ops.conv1d_stream_forward),
+    ("plain", "bf16"): ("bf16 streaming kernel", ops.conv1d_stream_bf16_supported, ops.conv1d_stream_forward_bf16),
+    ("delayed", "fp32"): ("delayed streaming kernel", ops.conv1d_stream_delayed_supported,
+                          ops.conv1d_stream_delayed_forward),
+    ("delayed", "bf16"): ("delayed bf16 streaming kernel", ops.conv1d_stream_bf16_delayed_supported,
+                          ops.conv1d_stream_delayed_forward_bf16),
+    ("mirrored", "fp32"): ("mirrored streaming kernel", ops.conv1d_stream_mirrored_supported,
+                           ops.conv1d_stream_mirrored_forward),
+}
+# what an fp32 launch tells a module in bf16 mode, per form
+_LOOKAHEAD_IS_FP32 = ("the look-ahead stream is fp32 (utils.set_inference_precision(model, 'fp32'), or pass "
+                      "precision='bf16' to stream with bf16 operands)")
+_FORM_IS_FP32 = {"plain": "the streaming kernel is fp32 (pass precision='bf16' to stream with bf16 operands)",
+                 "delayed": _LOOKAHEAD_IS_FP32, "mirrored": _LOOKAHEAD_IS_FP32}
+_FORM_IS_FP32_ONLY = {"mirrored": "a reflect-padded layer streams with a look-ahead in fp32 only"}
+
+
+def _launch(form, precision, cv, desc, x, hist, *args, delays=(), **kwargs):
+    """One launch of ``cv`` under ``desc`` through the ``form`` ("plain", "delayed", "mirrored") of the streaming kernel
+    on the chunk ``x`` and the history pair ``hist``; ``args`` / ``kwargs``: what the form's launch takes behind the
+    bias (addends, delay lines, windows), ``delays``: what its coverage query takes behind the descriptor.  The
+    precision is the call's: a bf16 call does not consult the module's own ``precision`` attribute (whole-utterance mode)
+    and runs on the layer's bf16 image; an fp32 call refuses a module in bf16 mode.  A layer the kernel does not cover is
+    a RuntimeError that names the reason."""
     if precision not in ("fp32", "bf16"):
         raise ValueError(f"stream precision must be 'fp32' or 'bf16', got {precision!r}")
-    # the precision of the call: a bf16 call does not consult the module's own `precision` attribute (whole-utterance
-    # mode); an fp32 call refuses a module in bf16 mode
     if precision == "fp32" and cv.precision != "fp32":
-        raise RuntimeError(f"{cv.__class__.__name__} is in {cv.precision} inference precision: the streaming kernel is fp32 "
-                           "(pass precision='bf16' to stream with bf16 operands)")
-    if precision == "bf16":
-        kernel, supported, forward = "bf16 streaming kernel", ops.conv1d_stream_bf16_supported, ops.conv1d_stream_forward_bf16
-    else:
-        kernel, supported, forward = "streaming kernel", ops.conv1d_stream_supported, ops.conv1d_stream_forward
-    if not supported(desc):
+        raise RuntimeError(f"{cv.__class__.__name__} is in {cv.precision} inference precision: {_FORM_IS_FP32[form]}")
+    if (form, precision) not in _STREAM_KERNELS:
+        raise RuntimeError(f"the {form} form of the streaming kernel has no {precision} form yet: "
+                           + _FORM_IS_FP32_ONLY[form])
+    kernel, supported, forward = _STREAM_KERNELS[form, precision]
+    if not supported(desc, *delays):
         from .. import _lib
 
         raise RuntimeError(f"the {kernel} does not cover this layer: "
@@ -136,7 +159,11 @@ def _stream_forward(cv, desc, x, hist_in, hist_out, fused, precision="fp32"):
     bias = None if cv.bias is None else cv.bias.detach()
     with torch.no_grad():
         image = cv.packed_weight_bf16() if precision == "bf16" else cv.packed_weight()
-        return forward(desc, x.contiguous(), hist_in, hist_out, image, bias, fused.get("add1"), fused.get("add2"))
+        return forward(desc, x.contiguous(), hist[0], hist[1], image, bias, *args, **kwargs)
+
+
+def _stream_forward(cv, desc, x, hist_in, hist_out, fused, precision="fp32"):
+    return _launch("plain", precision, cv, desc, x, (hist_in, hist_out), fused.get("add1"), fused.get("add2"))
 
 
 # ---- the NON-causal layers in causal form: streaming with a fixed look-ahead (utils.LookaheadStream).
@@ -264,83 +291,58 @@ def lookahead_window(delay, rate, t_out, frames_before=None, total_frames=None):
     return lo, hi
 
 
-class LookaheadWalk:
-    """One push through the launches of a delay plan: hands every launch its state tensors and its valid window.
-    ``state_in`` (None: start of stream, every state reads as zeros) / ``state_out``: one ping-pong half each, of
-    :func:`lookahead_state_shapes`.  ``frames_before``: frames the stream took before this push (None: steady state,
-    every window is full); ``total_frames``: the utterance's length once it is known (the flush), else None.
-    ``precision="bf16"``: every launch runs with bf16 operands on the layer's bf16 image (csrc/conv1d_stream_bf16.hip,
-    the delayed form); the state tensors are the same raw fp32 in either precision."""
+class _Walk:
+    """What the two walks of a delay plan share: one push through the plan's launches, each taking its state pairs in
+    plan order and its valid window.  ``state_in`` (None: start of stream, every state reads as zeros) / ``state_out``:
+    one ping-pong half each; ``frames_before``: frames the stream took before this push (None: steady state, every
+    window is full); ``total_frames``: the utterance's length once it is known (the flush), else None; ``precision``:
+    of every launch of the push -- the state tensors are the same raw fp32 in either."""
 
     def __init__(self, plan, state_in, state_out, frames_before=None, total_frames=None, precision="fp32"):
         if precision not in ("fp32", "bf16"):
-            raise ValueError(f"LookaheadWalk: precision must be 'fp32' or 'bf16', got {precision!r}")
+            raise ValueError(f"{type(self).__name__}: precision must be 'fp32' or 'bf16', got {precision!r}")
         self.precision = precision
         self._plan = iter(plan)
         self._in = None if state_in is None else iter(state_in)
         self._out = iter(state_out)
         self.frames_before, self.total_frames = frames_before, total_frames
 
-    def _take(self, wanted):
-        if not wanted:
-            return (None, None)
+    @property
+    def at_start(self):
+        """No state yet: the first push of an utterance."""
+        return self._in is None
+
+    def _pair(self):
+        """The next ``(state_in, state_out)`` pair; ``state_in`` None at the start of a stream."""
         return (None if self._in is None else next(self._in), next(self._out))
+
+    def _window(self, launch, t_out):
+        return lookahead_window(launch.delay, launch.rate, t_out, self.frames_before, self.total_frames)
+
+
+class LookaheadWalk(_Walk):
+    """The walk of a convolution plan (HiFi-GAN, MelGAN): hands every launch its state tensors, of
+    :func:`lookahead_state_shapes`, and its valid window, and runs it.  ``precision="bf16"``: every launch runs with
+    bf16 operands on the layer's bf16 image (csrc/conv1d_stream_bf16.hip, the delayed form)."""
 
     def run(self, cv, x, add1=None, add2=None, **fused):
         """The next launch of the plan, which must be ``cv``'s, on the chunk ``x``; fused-epilogue keywords as in
-        ``forward``."""
+        ``forward``.  A reflect-padded launch (the non-causal MelGAN's) goes through the mirrored form, whose input
+        window is the producing launch's unclamped valid window: fp32 only, no addends."""
         launch = next(self._plan)
         if launch.conv is not cv:
             raise RuntimeError(f"look-ahead walk out of step: the plan expects {launch.conv}, the model ran {cv}")
-        # the precision of the walk, by the rule of _stream_forward: a bf16 walk does not consult the module's own
-        # `precision` attribute (whole-utterance mode); an fp32 walk refuses a module in bf16 mode
-        bf16 = self.precision == "bf16"
-        if not bf16 and cv.precision != "fp32":
-            raise RuntimeError(f"{cv.__class__.__name__} is in {cv.precision} inference precision: the look-ahead stream is "
-                               "fp32 (utils.set_inference_precision(model, 'fp32'), or pass precision='bf16' to stream "
-                               "with bf16 operands)")
-        hist = self._take(lookahead_history_columns(cv))
-        line1, line2 = self._take(launch.delay1), self._take(launch.delay2)
+        hist = self._pair() if lookahead_history_columns(cv) else (None, None)
+        line1, line2 = (self._pair() if d else (None, None) for d in (launch.delay1, launch.delay2))
         desc = launch_desc(launch, x.shape[0], x.shape[-1], **fused)
-        t_out = desc.t_out
-        lo, hi = lookahead_window(launch.delay, launch.rate, t_out, self.frames_before, self.total_frames)
-        if launch_is_mirrored(launch):
-            return self._run_mirrored(launch, desc, x, hist, (lo, hi), add1, add2)
-        if bf16:
-            kernel, supported, forward = "delayed bf16 streaming kernel", ops.conv1d_stream_bf16_delayed_supported, \
-                ops.conv1d_stream_delayed_forward_bf16
-        else:
-            kernel, supported, forward = "delayed streaming kernel", ops.conv1d_stream_delayed_supported, \
-                ops.conv1d_stream_delayed_forward
-        if not supported(desc, launch.delay1, launch.delay2):
-            from .. import _lib
-
-            raise RuntimeError(f"the {kernel} does not cover this layer: "
-                               + _lib.lib().pwg_last_error().decode(errors="replace"))
-        bias = None if cv.bias is None else cv.bias.detach()
-        with torch.no_grad():
-            image = cv.packed_weight_bf16() if bf16 else cv.packed_weight()
-            return forward(desc, x.contiguous(), hist[0], hist[1], image, bias, add1, line1, launch.delay1, add2, line2,
-                           launch.delay2, (lo, hi))
-
-    def _run_mirrored(self, launch, desc, x, hist, valid, add1, add2):
-        """A reflect-padded launch (the non-causal MelGAN's): the mirrored entry point, whose input window is the
-        producing launch's unclamped valid window.  fp32 only, no addends."""
-        cv = launch.conv
-        if self.precision != "fp32":
-            raise RuntimeError("the mirrored form of the streaming kernel has no bf16 form yet: a reflect-padded layer "
-                               "streams with a look-ahead in fp32 only")
+        valid = self._window(launch, desc.t_out)
+        if not launch_is_mirrored(launch):
+            return _launch("delayed", self.precision, cv, desc, x, hist, add1, line1, launch.delay1, add2, line2,
+                           launch.delay2, valid, delays=(launch.delay1, launch.delay2))
         if add1 is not None or add2 is not None or launch.delay1 or launch.delay2:
             raise RuntimeError("the mirrored form of the streaming kernel takes no addends")
-        if not ops.conv1d_stream_mirrored_supported(desc):
-            from .. import _lib
-
-            raise RuntimeError("the mirrored streaming kernel does not cover this layer: "
-                               + _lib.lib().pwg_last_error().decode(errors="replace"))
-        with torch.no_grad():
-            return ops.conv1d_stream_mirrored_forward(
-                desc, x.contiguous(), hist[0], hist[1], cv.packed_weight(), None if cv.bias is None else cv.bias.detach(),
-                mirrored_in_window(launch, self.frames_before, self.total_frames), valid)
+        return _launch("mirrored", self.precision, cv, desc, x, hist,
+                       mirrored_in_window(launch, self.frames_before, self.total_frames), valid)
 
 
 # ---- the same for the NON-causal Parallel WaveGAN generator (utils.PWGLookaheadStream, DESIGN.md s11.6).  Its launches
@@ -358,29 +360,8 @@ def pwg_lookahead_state_shapes(plan, batch):
 def lookahead_launch(cv, desc, x, hist=(None, None), valid=None, precision="fp32"):
     """One delayed launch of ``cv`` under ``desc`` without addends: the history pair and the valid window are the
     caller's (``conv_in`` and the 1 x 1 convolutions of the Parallel WaveGAN look-ahead stream).  ``precision``, a module
-    in bf16 mode and a layer the kernel does not cover: by the rule of :meth:`LookaheadWalk.run`."""
-    if precision not in ("fp32", "bf16"):
-        raise ValueError(f"stream precision must be 'fp32' or 'bf16', got {precision!r}")
-    bf16 = precision == "bf16"
-    if not bf16 and cv.precision != "fp32":
-        raise RuntimeError(f"{cv.__class__.__name__} is in {cv.precision} inference precision: the look-ahead stream is "
-                           "fp32 (utils.set_inference_precision(model, 'fp32'), or pass precision='bf16' to stream with "
-                           "bf16 operands)")
-    if bf16:
-        kernel, supported, forward = "delayed bf16 streaming kernel", ops.conv1d_stream_bf16_delayed_supported, \
-            ops.conv1d_stream_delayed_forward_bf16
-    else:
-        kernel, supported, forward = "delayed streaming kernel", ops.conv1d_stream_delayed_supported, \
-            ops.conv1d_stream_delayed_forward
-    if not supported(desc):
-        from .. import _lib
-
-        raise RuntimeError(f"the {kernel} does not cover this layer: "
-                           + _lib.lib().pwg_last_error().decode(errors="replace"))
-    with torch.no_grad():
-        image = cv.packed_weight_bf16() if bf16 else cv.packed_weight()
-        return forward(desc, x.contiguous(), hist[0], hist[1], image, None if cv.bias is None else cv.bias.detach(),
-                       valid=valid)
+    in bf16 mode and a layer the kernel does not cover: by the rule of :func:`_launch`."""
+    return _launch("delayed", precision, cv, desc, x, hist, valid=valid)
 
 
 def pointwise_desc(cv, batch, n, **fused):
@@ -397,27 +378,10 @@ def lookahead_pointwise(cv, x, valid, precision="fp32", **fused):
     return lookahead_launch(cv, pointwise_desc(cv, x.shape[0], x.shape[-1], **fused), x, valid=valid, precision=precision)
 
 
-class PWGLookaheadWalk:
-    """One push through the launches of ``ParallelWaveGANGenerator.lookahead_plan()``: hands every launch its state
-    pairs and its valid window (the arithmetic of :func:`lookahead_window`, as :class:`LookaheadWalk`).  ``state_in``
-    (None: start of stream, every state reads as zeros) / ``state_out``: one ping-pong half each, of
-    :func:`pwg_lookahead_state_shapes`; ``frames_before`` / ``total_frames`` as in :class:`LookaheadWalk`.
-    ``precision="bf16"``: the model runs every convolution and gated layer of the push with bf16 operands (DESIGN.md
-    s11.7); the state tensors are the same raw fp32 in either precision."""
-
-    def __init__(self, plan, state_in, state_out, frames_before=None, total_frames=None, precision="fp32"):
-        if precision not in ("fp32", "bf16"):
-            raise ValueError(f"PWGLookaheadWalk: precision must be 'fp32' or 'bf16', got {precision!r}")
-        self.precision = precision
-        self._plan = iter(plan)
-        self._in = None if state_in is None else iter(state_in)
-        self._out = iter(state_out)
-        self.frames_before, self.total_frames = frames_before, total_frames
-
-    @property
-    def at_start(self):
-        """No state yet: the first push of an utterance."""
-        return self._in is None
+class PWGLookaheadWalk(_Walk):
+    """The walk of ``ParallelWaveGANGenerator.lookahead_plan()``: hands every launch its state pairs, of
+    :func:`pwg_lookahead_state_shapes`, and its valid window; the model runs it.  ``precision="bf16"``: the model runs
+    every convolution and gated layer of the push with bf16 operands."""
 
     def take(self, kind, module, frames):
         """The next launch of the plan, which must be ``(kind, module)``, on a chunk of ``frames`` mel frames ->
@@ -427,6 +391,4 @@ class PWGLookaheadWalk:
         if launch.kind != kind or launch.module is not module:
             raise RuntimeError(f"look-ahead walk out of step: the plan expects {launch.kind} {launch.module}, the model "
                                f"ran {kind} {module}")
-        pairs = [(None if self._in is None else next(self._in), next(self._out)) for _ in launch.state]
-        window = lookahead_window(launch.delay, launch.rate, frames * launch.rate, self.frames_before, self.total_frames)
-        return launch, pairs, window
+        return launch, [self._pair() for _ in launch.state], self._window(launch, frames * launch.rate)

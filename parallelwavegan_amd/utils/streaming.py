@@ -187,12 +187,13 @@ def _capture_directions(halves, run):
 
 
 class _Stream:
-    """What the stream classes share: the constructor's common checks, the ping-pong state (``_halves``: two lists of
-    history tensors, a push reads ``_halves[_cur]`` and writes the other), feature coercion, the counters, the step
-    (eager first push, then replay or run, then swap) and the captured graphs (``_graphs``: chunk shape -> entry, most
-    recently used last; ``_state``: the model's parameter state they were captured under; ``_watch``: a
-    ``GraphedInference`` asked for that state only).  A subclass validates its model, then calls ``__init__``; it
-    provides ``push``, ``reset`` and ``_capture``."""
+    """What the stream classes share: the constructor's checks (small class methods; the class name in a message is
+    the caller's), the ping-pong state (``_halves``: two lists of history tensors, a push reads ``_halves[_cur]`` and
+    writes the other), feature and noise coercion, the counters, the step (eager first push, then replay or run, then
+    swap) and the captured graphs (``_graphs``: chunk shape -> entry, most recently used last; ``_state``: the model's
+    parameter state they were captured under; ``_watch``: a ``GraphedInference`` asked for that state only).  A subclass
+    validates its model, then calls ``__init__``; it provides ``push``, ``reset`` and ``_run(feats, [z,] hist_in,
+    hist_out)``, the model on one push's inputs in steady state."""
 
     max_graph_shapes = 4  # chunk sizes whose graphs are kept (least recently used evicted)
 
@@ -223,6 +224,59 @@ class _Stream:
             raise ValueError(f"{cls.__name__}: batch must be >= 1")
         return batch
 
+    @classmethod
+    def _checked_precision(cls, precision, no_bf16=None):
+        """The constructor's ``precision`` -> ``"fp32"`` (also for None) or ``"bf16"``; ``no_bf16``: why the class has no
+        bf16 stream."""
+        if no_bf16 is None:
+            if precision not in (None, "fp32", "bf16"):
+                raise ValueError(f"{cls.__name__}: precision must be None, 'fp32' or 'bf16', got {precision!r}")
+        elif precision == "bf16":
+            raise ValueError(f"{cls.__name__}: precision='bf16' is not available: {no_bf16}")
+        elif precision not in (None, "fp32"):
+            raise ValueError(f"{cls.__name__}: precision must be None or 'fp32', got {precision!r}")
+        return precision or "fp32"
+
+    @classmethod
+    def _refuse_bf16_model(cls, model, precision, stream, has_bf16=True):
+        """An fp32 stream does not read the mode ``set_inference_precision(model, 'bf16')`` put the modules in."""
+        from ..layers.conv import each_conv
+
+        if precision == "bf16" or all(cv.precision == "fp32" for cv in each_conv(model)):
+            return
+        name, undo = cls.__name__, "utils.set_inference_precision(model, 'fp32')"
+        if has_bf16:
+            raise ValueError(f"{name}: the model is in bf16 inference precision; the fp32 {stream} does not read that mode "
+                             f"({undo}, or stream with bf16 operands: {name}(model, precision='bf16'))")
+        raise ValueError(f"{name}: the model is in bf16 inference precision; the {stream} is fp32 ({undo})")
+
+    @classmethod
+    def _checked_pqmf(cls, model, out_channels):
+        """``model.pqmf`` (None: full-band) of a generator that emits ``out_channels`` rows, or the refusal."""
+        from ..layers.pqmf import PQMF
+        from ..models import MelGANGenerator
+
+        name, pqmf = cls.__name__, getattr(model, "pqmf", None)
+        if out_channels != 1 and (pqmf is None or not isinstance(model, MelGANGenerator)):
+            raise ValueError(f"{name}: the generator emits {out_channels} sub-bands; only a multi-band MelGANGenerator with "
+                             "its PQMF attached (model.pqmf = PQMF(subbands=...), as utils.load_model does) can be "
+                             "streamed, through the stateful PQMF synthesis")
+        if pqmf is not None:
+            if not isinstance(pqmf, PQMF) or pqmf.subbands != out_channels:
+                raise ValueError(f"{name}: model.pqmf must be a PQMF with as many sub-bands as the generator emits "
+                                 f"({out_channels}); got {getattr(pqmf, 'subbands', pqmf.__class__.__name__)}")
+            if pqmf.subbands > 8:
+                raise ValueError(f"{name}: a PQMF of {pqmf.subbands} sub-bands cannot be streamed (the stream kernel "
+                                 "covers up to 8)")
+        return pqmf
+
+    @classmethod
+    def _require_supported(cls, ok, what, how=""):
+        """``ok``: the answer of a kernel's ``*_supported``, whose reason for a refusal is ``pwg_last_error``."""
+        if not ok:
+            raise ValueError(f"{cls.__name__}: {what} cannot be streamed{how}: "
+                             + _lib.lib().pwg_last_error().decode(errors="replace"))
+
     @property
     def state_bytes(self):
         """Bytes of history held on the device (both ping-pong halves)."""
@@ -252,6 +306,19 @@ class _Stream:
                              f"{tuple(feats.shape)}")
         return feats.contiguous()
 
+    def _coerce_noise(self, noise, n):
+        """The noise ``push`` takes for ``n`` frames -> contiguous (batch, 1, n * up) fp32 on the stream's device; None
+        (drawn on the device in ``_push_step``) stays None."""
+        if noise is None:
+            return None
+        noise = torch.as_tensor(noise, dtype=torch.float32).to(self._device)
+        if noise.dim() == 1:
+            noise = noise.unsqueeze(0).expand(self.batch, -1)
+        if tuple(noise.shape) != (self.batch, n * self.up):
+            raise ValueError(f"{type(self).__name__}.push: expected ({n * self.up},) or ({self.batch}, {n * self.up}) noise "
+                             f"for {n} frame(s), got {tuple(noise.shape)}")
+        return noise.reshape(self.batch, 1, n * self.up).contiguous()
+
     def _empty(self):
         """The emission of a push that emits nothing."""
         return torch.empty((self.batch, 0), device=self._device, dtype=torch.float32)
@@ -269,6 +336,13 @@ class _Stream:
             entry = capture()
         self._graphs[key] = entry  # most recently used last
         return entry
+
+    def _capture(self, *inputs):
+        """Graphs for both directions of one chunk shape, ``_run`` on static copies of ``inputs`` -> ``(*statics,
+        graphs)``.  The warm-up runs write history: both halves are saved and put back, so capturing never advances the
+        stream."""
+        statics = [t.clone() for t in inputs]
+        return (*statics, _capture_directions(self._halves, lambda hi, ho: self._run(*statics, hi, ho)))
 
     def _step(self, n, key, eager, capture, fill_static):
         """One push of ``n`` frames through the ping-pong halves -> (batch, samples), the caller's own tensor.
@@ -292,6 +366,31 @@ class _Stream:
         self.frames_out += n
         self.samples_out += y.shape[1]
         return y
+
+    def _push_step(self, feats, noise, run, graph):
+        """``_step`` on the inputs of one push: ``feats`` from ``_coerce``; ``noise``: ``()`` for a stream that takes
+        none, else ``(z,)`` from ``_coerce_noise``, None being drawn with ``torch.randn`` on the device -- never inside a
+        graph: it is written into the graph's static buffer before the replay.  ``run(feats, *noise, hist_in,
+        hist_out)``: the eager run of this push; ``graph``: may it replay the graphs of its chunk shape instead."""
+        n = feats.shape[1]
+        shape = (self.batch, 1, n * self.up)
+
+        def eager(hist_in, hist_out):
+            return run(feats, *(torch.randn(shape, device=self._device) if z is None else z for z in noise), hist_in,
+                       hist_out)
+
+        def capture():
+            return self._capture(feats, *(torch.zeros(shape, device=self._device) for _ in noise))
+
+        def fill_static(static_in, *static_noise):
+            static_in.copy_(feats, non_blocking=True)
+            for static_z, z in zip(static_noise, noise):
+                if z is None:
+                    static_z.normal_()  # (outside the graph: a replay never draws)
+                else:
+                    static_z.copy_(z, non_blocking=True)
+
+        return self._step(n, (n, feats.shape[2]), eager, capture if graph else None, fill_static)
 
     def push_pcm16(self, *args, **kwargs):
         """``push`` through the float -> PCM16 conversion: (batch, samples) int16."""
@@ -345,12 +444,9 @@ class CausalStream(_Stream):
     """
 
     def __init__(self, model, batch=1, use_graph=True, normalize_before=False, precision=None):
-        from ..layers.conv import each_conv
-        from ..layers.pqmf import PQMF
         from ..models import HiFiGANGenerator, MelGANGenerator
 
-        if precision not in (None, "fp32", "bf16"):
-            raise ValueError(f"CausalStream: precision must be None, 'fp32' or 'bf16', got {precision!r}")
+        precision = self._checked_precision(precision)
         if not isinstance(model, (HiFiGANGenerator, MelGANGenerator)):
             raise ValueError(f"CausalStream: {model.__class__.__name__} is not supported (only the causal HiFiGANGenerator "
                              "and MelGANGenerator map mel frames to samples layer by layer; a causal "
@@ -358,29 +454,13 @@ class CausalStream(_Stream):
         layers = model.stream_layers()  # ValueError for a non-causal model
         out_channels = model.output_conv[1].conv.out_channels if isinstance(model, HiFiGANGenerator) else \
             layers[-1][0].conv.out_channels
-        pqmf = getattr(model, "pqmf", None)
-        if out_channels != 1 and (pqmf is None or not isinstance(model, MelGANGenerator)):
-            raise ValueError(f"CausalStream: the generator emits {out_channels} sub-bands; only a multi-band "
-                             "MelGANGenerator with its PQMF attached (model.pqmf = PQMF(subbands=...), as utils.load_model "
-                             "does) can be streamed, through the stateful PQMF synthesis")
-        if pqmf is not None:
-            if not isinstance(pqmf, PQMF) or pqmf.subbands != out_channels:
-                raise ValueError(f"CausalStream: model.pqmf must be a PQMF with as many sub-bands as the generator emits "
-                                 f"({out_channels}); got {getattr(pqmf, 'subbands', pqmf.__class__.__name__)}")
-            if pqmf.subbands > 8:
-                raise ValueError(f"CausalStream: a PQMF of {pqmf.subbands} sub-bands cannot be streamed (the stream kernel "
-                                 "covers up to 8)")
-        if precision != "bf16" and any(cv.precision != "fp32" for cv in each_conv(model)):
-            raise ValueError("CausalStream: the model is in bf16 inference precision; the fp32 streaming kernel does not "
-                             "read that mode (utils.set_inference_precision(model, 'fp32'), or stream with bf16 operands: "
-                             "CausalStream(model, precision='bf16'))")
+        pqmf = self._checked_pqmf(model, out_channels)
+        self._refuse_bf16_model(model, precision, "streaming kernel")
         batch = self._checked_batch(batch)
         supported = conv1d_stream_bf16_supported if precision == "bf16" else conv1d_stream_supported
         for layer, _ in layers:
-            if not supported(layer.stream_desc(batch, 8)):
-                raise ValueError(f"CausalStream: {layer} cannot be streamed: "
-                                 + _lib.lib().pwg_last_error().decode(errors="replace"))
-        self.precision = precision or "fp32"  # of the stream, fixed for its life
+            self._require_supported(supported(layer.stream_desc(batch, 8)), layer)
+        self.precision = precision  # of the stream, fixed for its life
         self.pqmf = pqmf
         self.subbands = out_channels
         self.up = model.upsample_factor * out_channels  # samples per frame
@@ -421,12 +501,6 @@ class CausalStream(_Stream):
         return self.pqmf.stream_synthesis(y, None if hist_in is None else hist_in[-1], hist_out[-1],
                                           y.shape[-1] if n_emit is None else n_emit)
 
-    def _capture(self, feats):
-        """Graphs for both directions of one chunk shape.  The warm-up runs write history: both halves are saved and
-        put back, so capturing never advances the stream."""
-        static_in = feats.clone()
-        return static_in, _capture_directions(self._halves, lambda hi, ho: self._run(static_in, hi, ho))
-
     @torch.no_grad()
     def push(self, feats):
         """feats: (n, C) or (batch, n, C) float features -> (batch, samples) fp32: ``m * up`` samples, ``m`` the frames
@@ -449,9 +523,7 @@ class CausalStream(_Stream):
         n_cols = n * self.model.upsample_factor
         n_emit = self._emit(n_cols)
         graph = self.use_graph and n_emit == n_cols  # (a multi-band stream still inside the PQMF delay: eager)
-        y = self._step(n, (n, feats.shape[2]), lambda hi, ho: self._run(feats, hi, ho, n_emit),
-                       (lambda: self._capture(feats)) if graph else None,
-                       lambda static_in: static_in.copy_(feats, non_blocking=True))
+        y = self._push_step(feats, (), lambda f, hi, ho: self._run(f, hi, ho, n_emit), graph)
         self._columns += n_cols
         return y
 
@@ -514,38 +586,30 @@ class PWGStream(_Stream):
 
     def __init__(self, model, batch=1, use_graph=True, normalize_before=False, precision=None):
         from ..layers.causal_conv import pointwise_desc
-        from ..layers.conv import each_conv
         from ..layers.upsample import ConvInStream
         from ..models import ParallelWaveGANGenerator
 
-        if precision not in (None, "fp32", "bf16"):
-            raise ValueError(f"PWGStream: precision must be None, 'fp32' or 'bf16', got {precision!r}")
+        precision = self._checked_precision(precision)
         if not isinstance(model, ParallelWaveGANGenerator):
             raise ValueError(f"PWGStream: {model.__class__.__name__} is not supported (only the causal "
                              "ParallelWaveGANGenerator; HiFiGANGenerator and MelGANGenerator stream through CausalStream)")
         batch = self._checked_batch(batch)
-        reason = model.stream_unsupported_reason(batch, precision or "fp32")
+        reason = model.stream_unsupported_reason(batch, precision)
         if reason is not None:
             raise ValueError(f"PWGStream: {reason}")
         if model.in_channels != 1 or model.out_channels != 1:
             raise ValueError(f"PWGStream: in_channels / out_channels = {model.in_channels} / {model.out_channels} (the "
                              "stream takes one noise row and emits one waveform per stream)")
-        if precision != "bf16" and any(cv.precision != "fp32" for cv in each_conv(model)):
-            raise ValueError("PWGStream: the model is in bf16 inference precision; the fp32 streaming layer kernel does "
-                             "not read that mode (utils.set_inference_precision(model, 'fp32'), or stream with bf16 "
-                             "operands: PWGStream(model, precision='bf16'))")
+        self._refuse_bf16_model(model, precision, "streaming layer kernel")
         layers = model.stream_layers()
         supported = conv1d_stream_bf16_supported if precision == "bf16" else conv1d_stream_supported
         for layer, _ in layers:
-            if isinstance(layer, ConvInStream) and not supported(layer.stream_desc(batch, 8)):
-                raise ValueError(f"PWGStream: {layer} cannot be streamed: "
-                                 + _lib.lib().pwg_last_error().decode(errors="replace"))
+            if isinstance(layer, ConvInStream):
+                self._require_supported(supported(layer.stream_desc(batch, 8)), layer)
         if precision == "bf16":  # a bf16 stream never runs a convolution the bf16 kernel refuses in fp32 instead
             for cv in model.pointwise_convs():
-                if not supported(pointwise_desc(cv, batch, 8)):
-                    raise ValueError(f"PWGStream: {cv} cannot be streamed with bf16 operands: "
-                                     + _lib.lib().pwg_last_error().decode(errors="replace"))
-        self.precision = precision or "fp32"  # of the stream, fixed for its life
+                self._require_supported(supported(pointwise_desc(cv, batch, 8)), cv, " with bf16 operands")
+        self.precision = precision  # of the stream, fixed for its life
         self.up = model.upsample_factor  # samples per frame
         self._context = model.aux_context_window if isinstance(layers[0][0], ConvInStream) else 0
         super().__init__(model, layers, batch, use_graph, normalize_before)
@@ -577,10 +641,6 @@ class PWGStream(_Stream):
         return self.model.stream_forward(z, self._features(feats), hist_in, hist_out,
                                          precision=self.precision).reshape(self.batch, -1)
 
-    def _capture(self, feats, z):
-        static_in, static_z = feats.clone(), z.clone()
-        return static_in, static_z, _capture_directions(self._halves, lambda hi, ho: self._run(static_in, static_z, hi, ho))
-
     @torch.no_grad()
     def push(self, feats, noise=None):
         """feats: (n, C) or (batch, n, C) float features; noise: (batch, n * up) or (n * up,) (the same for every
@@ -588,75 +648,193 @@ class PWGStream(_Stream):
         own tensor (not a graph's static buffer)."""
         feats = self._coerce(feats)
         n = feats.shape[1]
-        if noise is not None:
-            noise = torch.as_tensor(noise, dtype=torch.float32).to(self._device)
-            if noise.dim() == 1:
-                noise = noise.unsqueeze(0).expand(self.batch, -1)
-            if tuple(noise.shape) != (self.batch, n * self.up):
-                raise ValueError(f"PWGStream.push: expected ({n * self.up},) or ({self.batch}, {n * self.up}) noise for "
-                                 f"{n} frame(s), got {tuple(noise.shape)}")
-            noise = noise.reshape(self.batch, 1, n * self.up).contiguous()
+        noise = self._coerce_noise(noise, n)
         self.frames_in += n
         if n == 0:
             return self._empty()
-
-        def eager(hist_in, hist_out):
-            z = noise if noise is not None else torch.randn(self.batch, 1, n * self.up, device=self._device)
-            return self._run(feats, z, hist_in, hist_out)
-
-        def capture():
-            return self._capture(feats, torch.zeros(self.batch, 1, n * self.up, device=self._device))
-
-        def fill_static(static_in, static_z):
-            static_in.copy_(feats, non_blocking=True)
-            if noise is None:
-                static_z.normal_()  # (outside the graph: a replay never draws)
-            else:
-                static_z.copy_(noise, non_blocking=True)
-
-        return self._step(n, (n, feats.shape[2]), eager, capture if self.use_graph else None, fill_static)
+        return self._push_step(feats, (noise,), self._run, self.use_graph)
 
 
-class LookaheadStream(_Stream):
-    """Stateful streaming synthesis for the standard NON-causal ``HiFiGANGenerator`` (symmetric ``Conv1d``,
-    ``ConvTranspose1d(padding = s//2 + s%2)``: every recipe and released checkpoint) with a fixed look-ahead: ``push``
-    takes the next mel frames of ``batch`` lock-step streams at ``n`` frames of work, and every sample leaves
-    ``latency_samples`` late (``latency_frames``: the ceiling in frames; 3258 samples = 12.73 frames for HiFi-GAN V1).
-    After any push the samples emitted total ``max(0, frames_in * up - latency_samples)``, so the first pushes of an
-    utterance return short or empty tensors; ``flush()`` returns the tail, after which the emissions total ``frames *
-    up`` samples.  Any partition of the same frames gives bit-identical audio, equal to the whole-utterance ``forward``
-    up to fp32 summation order.
+class _LookaheadStream(_Stream):
+    """The look-ahead streams' core: what streaming a NON-causal generator with a fixed look-ahead is, whatever the
+    model.  Every layer runs in its causal form on a shifted time axis (``model.lookahead_plan()`` lists the launches and
+    their delays), so a push of ``n`` frames costs ``n`` frames of work and every sample leaves ``latency_samples`` late
+    (``latency_frames``: the ceiling in frames).
 
-    How: every layer runs in its causal form on a shifted time axis (csrc/conv1d_stream.hip, the
-    delayed form).  A tensor of the network is a stream with a delay: a symmetric convolution adds its padding, a
-    transposed one multiplies by its stride and adds its padding; the residual input of a unit and the MRF running sum
-    are older than the launch that adds them and go through delay lines; every launch stores exact zeros outside the
-    utterance, which is what the next layer's zero padding is.  ``model.lookahead_plan()`` lists the delays.
+    Emission rule: after any push the samples emitted total ``max(0, frames_in * up - latency_samples)``, so the first
+    pushes of an utterance return short or empty tensors; ``flush()`` returns the tail, after which the emissions total
+    ``frames * up`` samples; ``reset()`` starts the next utterance.  ``close()`` does not flush: an unflushed tail is
+    dropped.  Any partition of the same inputs gives bit-identical audio, equal to the whole-utterance forward up to fp32
+    summation order.  Of ``latency_samples`` the generator's own delay (``_front``) stands in front of the audio in the
+    late stream; a multi-band model's PQMF synthesis holds the rest (``_hold``) back behind the newest column.
 
-    State: per convolution the last ``(k - 1) * d`` columns of its raw input (one for a transposed layer) and the delay
-    lines of its addends, ping-pong (``state_bytes``: both halves).  ``use_graph``: a push whose windows are all full
-    (``latency_frames`` frames went before it) replays the two captured graphs of its chunk size, as in
-    :class:`CausalStream`; the pushes at the start of an utterance and ``flush()`` run eagerly.  ``close()`` does not
-    flush: an unflushed tail is dropped.
+    State (``state_bytes``: both ping-pong halves): what the plan's launches keep -- histories and delay lines.
+    ``use_graph``: a captured graph has fixed window arguments, so a push replays the two graphs of its chunk size, as in
+    :class:`CausalStream`, only if no launch has an edge of the utterance in its window or history and nothing is trimmed
+    from its emission: ``settle_frames`` frames went before it (``latency_frames``, or more for a reflect-padded plan).
+    Earlier pushes and ``flush()`` run eagerly.  ``flush()`` refuses an utterance shorter than ``min_frames`` (1, or what
+    reflection needs), which the whole-utterance forward cannot pad either.
 
-    ``precision="bf16"``: every convolution of every push, the eager pushes at the start of an utterance and ``flush()``
-    included, runs with bf16 operands (csrc/conv1d_stream_bf16.hip, the delayed form; DESIGN.md s11.5: the activated
-    window and the weights are rounded to bf16; sums, epilogues, addends, tensors, history and delay lines stay fp32).
-    As in :class:`CausalStream` the precision belongs to the stream, is fixed for its life (``.precision``) and neither
-    reads nor writes the modules' own ``precision`` attributes; plan, latency, state and partition invariance are those
-    of the fp32 stream.  ``None`` and ``"fp32"`` are the fp32 stream, which refuses a model that
-    ``set_inference_precision`` put in bf16 mode.
-    """
+    ``precision``: of the stream, fixed for its life (``.precision``); as in :class:`CausalStream` it neither reads nor
+    writes the modules' own ``precision`` attributes, every launch of every push, the eager pushes and ``flush()``
+    included, runs in it, and plan, latency, state and partition invariance do not depend on it.  ``None`` and ``"fp32"``
+    are the fp32 stream, which refuses a model that ``set_inference_precision`` put in bf16 mode.
+
+    A subclass supplies its constructor (the model's checks in its own order, the plan, the state shapes), ``_run`` and
+    ``_run_tail``, what ``flush`` feeds; the ones here run a convolution plan (HiFi-GAN, MelGAN)."""
 
     warmup_frames = 1
+    _takes_noise = False  # does ``push`` take noise beside the features
+    _keeps_last = False   # does ``flush`` replicate the last frame pushed (``_last``)
+
+    def __init__(self, model, plan, batch, use_graph, normalize_before, precision, state_shapes, pqmf=None, settle_frames=0,
+                 min_frames=1):
+        """``plan``: ``model.lookahead_plan()``; ``pqmf``: of a multi-band model, its history rides behind
+        ``state_shapes`` in both halves; ``settle_frames``: what the plan's edges need, if more than ``latency_frames``."""
+        k = pqmf.subbands if pqmf is not None else 1
+        self.precision = precision
+        self.up = model.upsample_factor * k  # samples per frame
+        self._plan = plan
+        self._pqmf = pqmf
+        self._hold = pqmf.stream_delay_columns * k if pqmf is not None else 0
+        self._front = plan[-1].delay * k
+        self.latency_samples = self._front + self._hold
+        self.latency_frames = -(-self.latency_samples // self.up)
+        self.settle_frames = max(settle_frames, self.latency_frames)
+        self.min_frames = min_frames
+        super().__init__(model, [], batch, use_graph, normalize_before,
+                         state_shapes + ([pqmf.history_shape(batch)] if pqmf is not None else []))
+
+    @classmethod
+    def _require_plan(cls, plan, batch, precision):
+        """Every launch of a convolution plan must be one its kernel covers."""
+        from ..layers.causal_conv import launch_desc, launch_is_mirrored
+
+        delayed = conv1d_stream_bf16_delayed_supported if precision == "bf16" else conv1d_stream_delayed_supported
+        for launch in plan:
+            desc = launch_desc(launch, batch, 8)
+            cls._require_supported(conv1d_stream_mirrored_supported(desc) if launch_is_mirrored(launch) else
+                                   delayed(desc, launch.delay1, launch.delay2), launch.conv)
+
+    @classmethod
+    def _plan_of(cls, model):
+        """``(plan, pqmf or None)`` of a model, from the module geometry alone."""
+        return model.lookahead_plan(), None
+
+    @classmethod
+    def latency_samples_of(cls, model):
+        """Samples every output leaves late, from the module geometry alone (no device, no kernel): the generator's
+        delay times the sub-band count, plus the PQMF's ``K * stream_delay_columns`` for a multi-band model."""
+        plan, pqmf = cls._plan_of(model)
+        return plan[-1].delay if pqmf is None else (plan[-1].delay + pqmf.stream_delay_columns) * pqmf.subbands
+
+    def reset(self):
+        """Back to start of stream; an unflushed tail is dropped."""
+        self._restart()
+        self._flushed = False
+        self._last = None  # the last frame pushed, (batch, 1, C), where the flush replicates it (``_keeps_last``)
+
+    def _positions(self, frames_before, n):
+        """``(first, count)``: the samples of the whole late stream (``_front`` zeros, then the utterance) that a push of
+        ``n`` frames after ``frames_before`` completes -- all of its ``n * up`` for a full-band model, those ``_hold``
+        behind the newest column for a multi-band one."""
+        first = max(0, frames_before * self.up - self._hold)
+        return first, max(0, (frames_before + n) * self.up - self._hold) - first
+
+    def _walk_run(self, c, state_in, state_out, frames_before, total_frames):
+        """``c``: (batch, C, n) features, normalised, through the convolution plan and the PQMF."""
+        from ..layers.causal_conv import LookaheadWalk
+
+        k = len(state_out) - (self._pqmf is not None)  # (a multi-band stream's halves end with the PQMF's history)
+        walk = LookaheadWalk(self._plan, None if state_in is None else state_in[:k], state_out[:k], frames_before,
+                             total_frames, self.precision)
+        y = self.model.lookahead_forward(c, walk)
+        if self._pqmf is None:
+            return y.reshape(self.batch, -1)
+        n_emit = y.shape[-1] if frames_before is None else \
+            self._positions(frames_before, c.shape[-1])[1] // self._pqmf.subbands
+        return self._pqmf.stream_synthesis(y, None if state_in is None else state_in[-1], state_out[-1], n_emit)
+
+    def _run(self, feats, state_in, state_out, frames_before=None):
+        """The inputs of one push; ``state_in`` (None: start of stream) / ``state_out``: one ping-pong half each;
+        ``frames_before`` None: steady state.  -> (batch, samples): the positions of the whole late stream this push
+        completes, not yet trimmed."""
+        return self._walk_run(self._features(feats), state_in, state_out, frames_before, None)
+
+    def _run_tail(self, state_in, state_out, total):
+        """``_run`` on what ``flush`` feeds after an utterance of ``total`` frames, with the end-of-utterance windows:
+        ``latency_frames`` zero frames (normalised: the whole-utterance padding; a reflect-padded first layer mirrors at
+        the utterance's last frame, so it never reads them)."""
+        zeros = torch.zeros((self.batch, self._plan[0].conv.in_channels, self.latency_frames), device=self._device)
+        return self._walk_run(zeros, state_in, state_out, total, total)
+
+    @torch.no_grad()
+    def push(self, feats, noise=None):
+        """feats: (n, C) or (batch, n, C) float features; noise, for a stream that takes it (Parallel WaveGAN):
+        (batch, n * up) or (n * up,) (the same for every stream) for the samples of THESE frames, undelayed, drawn with
+        ``torch.randn`` on the device if omitted -> (batch, samples) fp32, the samples that became complete: ``n * up``
+        once ``latency_samples`` are behind, fewer (or none) before.  The result is the caller's own tensor."""
+        if noise is not None and not self._takes_noise:
+            raise TypeError(f"{type(self).__name__}.push takes no noise")
+        if self._flushed:
+            raise RuntimeError(f"{type(self).__name__}.push: the utterance was flushed; reset() starts the next one")
+        feats = self._coerce(feats)
+        n = feats.shape[1]
+        z = (self._coerce_noise(noise, n),) if self._takes_noise else ()
+        if n == 0:
+            return self._empty()
+        before = self.frames_in
+        self.frames_in += n
+        if self._keeps_last:
+            self._last = feats[:, -1:, :].clone()
+        steady = before >= self.settle_frames  # no edge in reach, nothing to trim
+        skip = 0 if steady else max(0, self._front - self._positions(before, n)[0])  # samples in front of the first one
+        return self._push_step(feats, z, lambda *a: self._run(*a, before)[:, skip:].contiguous(),
+                               self.use_graph and steady)
+
+    @torch.no_grad()
+    def flush(self):
+        """End of the utterance: ``latency_frames`` more frames (``_run_tail``) with the end-of-utterance windows --
+        every launch stores zeros past the utterance's last column, as the whole-utterance padding is, and a multi-band
+        model's PQMF tail drains with them -> the last ``min(latency_samples, frames * up)`` samples, (batch, samples).
+        Zero-length before anything was pushed and on a second call.  RuntimeError for an utterance shorter than
+        ``min_frames``.  The next utterance starts with ``reset()``."""
+        if not self._started or self._flushed:
+            return self._empty()
+        total = self.frames_in
+        if total < self.min_frames:
+            raise RuntimeError(f"{type(self).__name__}.flush: the utterance has {total} frame(s); reflection padding needs "
+                               f"at least {self.min_frames} (the whole-utterance forward cannot pad a shorter one either)")
+        y = self._run_tail(self._halves[self._cur], self._halves[1 - self._cur], total)
+        first = self._positions(total, self.latency_frames)[0]
+        y = y[:, max(0, self._front - first):self._front + total * self.up - first].contiguous()
+        self._flushed = True  # (the halves are not swapped: nothing may follow but reset())
+        self.samples_out += y.shape[1]
+        return y
+
+
+class LookaheadStream(_LookaheadStream):
+    """Stateful streaming synthesis for the standard NON-causal ``HiFiGANGenerator`` (symmetric ``Conv1d``,
+    ``ConvTranspose1d(padding = s//2 + s%2)``: every recipe and released checkpoint) with a fixed look-ahead.  Interface,
+    emission rule, graph rule, ``flush`` / ``close`` and the precision's scope: :class:`_LookaheadStream`.
+    ``latency_samples`` is 3258 (12.73 frames) for HiFi-GAN V1; ``settle_frames == latency_frames``, ``min_frames == 1``.
+
+    How: csrc/conv1d_stream.hip, the delayed form.  A tensor of the network is a stream with a delay:
+    a symmetric convolution adds its padding, a transposed one multiplies by its stride and adds its padding; the
+    residual input of a unit and the MRF running sum are older than the launch that adds them and go through delay
+    lines; every launch stores exact zeros outside the utterance, which is what the next layer's zero padding is.
+
+    State: per convolution the last ``(k - 1) * d`` columns of its raw input (one for a transposed layer) and the delay
+    lines of its addends.  ``precision="bf16"``: every convolution runs with bf16 operands (csrc/conv1d_stream_bf16.hip,
+    the delayed form; DESIGN.md s11.5: the activated window and the weights are rounded to bf16; sums, epilogues,
+    addends, tensors, history and delay lines stay fp32).
+    """
 
     def __init__(self, model, batch=1, use_graph=True, normalize_before=False, precision=None):
-        from ..layers.causal_conv import lookahead_desc, lookahead_state_shapes
-        from ..layers.conv import each_conv
+        from ..layers.causal_conv import lookahead_state_shapes
         from ..models import HiFiGANGenerator
 
-        if precision not in (None, "fp32", "bf16"):
-            raise ValueError(f"LookaheadStream: precision must be None, 'fp32' or 'bf16', got {precision!r}")
+        precision = self._checked_precision(precision)
         if not isinstance(model, HiFiGANGenerator):
             raise ValueError(f"LookaheadStream: {model.__class__.__name__} is not supported (only the non-causal "
                              "HiFiGANGenerator; a non-causal MelGANGenerator streams through "
@@ -668,159 +846,56 @@ class LookaheadStream(_Stream):
         if out_channels != 1:
             raise ValueError(f"LookaheadStream: the generator emits {out_channels} channels; the stream returns one "
                              "waveform per stream (out_channels == 1)")
-        if precision != "bf16" and any(cv.precision != "fp32" for cv in each_conv(model)):
-            raise ValueError("LookaheadStream: the model is in bf16 inference precision; the fp32 look-ahead stream does "
-                             "not read that mode (utils.set_inference_precision(model, 'fp32'), or stream with bf16 "
-                             "operands: LookaheadStream(model, precision='bf16'))")
+        self._refuse_bf16_model(model, precision, "look-ahead stream")
         batch = self._checked_batch(batch)
         plan = model.lookahead_plan()  # ValueError: decreasing block delays, a layer without a causal form
-        supported = conv1d_stream_bf16_delayed_supported if precision == "bf16" else conv1d_stream_delayed_supported
-        for launch in plan:
-            if not supported(lookahead_desc(launch.conv, batch, 8), launch.delay1, launch.delay2):
-                raise ValueError(f"LookaheadStream: {launch.conv} cannot be streamed: "
-                                 + _lib.lib().pwg_last_error().decode(errors="replace"))
-        self.precision = precision or "fp32"  # of the stream, fixed for its life
-        self.up = model.upsample_factor  # samples per frame
-        self._plan = plan
-        self._in_channels = model.input_conv.in_channels
-        self.latency_samples = plan[-1].delay
-        self.latency_frames = -(-self.latency_samples // self.up)
-        super().__init__(model, [], batch, use_graph, normalize_before, lookahead_state_shapes(plan, batch))
-
-    @staticmethod
-    def latency_samples_of(model):
-        """Samples every output leaves late, from the module geometry alone (no device, no kernel)."""
-        return model.lookahead_plan()[-1].delay
-
-    def reset(self):
-        """Back to start of stream; an unflushed tail is dropped."""
-        self._restart()
-        self._flushed = False
-
-    def _run(self, c, state_in, state_out, frames_before=None, total_frames=None):
-        """``c``: (batch, C, n) features, normalised; ``state_in`` (None: start of stream) / ``state_out``: one
-        ping-pong half each; ``frames_before`` None: steady state.  -> (batch, n * up), not yet trimmed."""
-        from ..layers.causal_conv import LookaheadWalk
-
-        walk = LookaheadWalk(self._plan, state_in, state_out, frames_before, total_frames, self.precision)
-        return self.model.lookahead_forward(c, walk).reshape(self.batch, -1)
-
-    def _capture(self, feats):
-        static_in = feats.clone()
-        return static_in, _capture_directions(self._halves, lambda si, so: self._run(self._features(static_in), si, so))
-
-    @torch.no_grad()
-    def push(self, feats):
-        """feats: (n, C) or (batch, n, C) float features -> (batch, samples) fp32, the samples that became complete:
-        ``n * up`` once ``latency_samples`` are behind, fewer (or none) before.  The result is the caller's own tensor."""
-        if self._flushed:
-            raise RuntimeError("LookaheadStream.push: the utterance was flushed; reset() starts the next one")
-        feats = self._coerce(feats)
-        n = feats.shape[1]
-        if n == 0:
-            return self._empty()
-        before = self.frames_in
-        self.frames_in += n
-        skip = max(0, self.latency_samples - before * self.up)  # columns of this chunk in front of the first sample
-        steady = before >= self.latency_frames                  # every launch's window is full
-        return self._step(n, (n, feats.shape[2]),
-                          lambda si, so: self._run(self._features(feats), si, so, before)[:, skip:].contiguous(),
-                          (lambda: self._capture(feats)) if self.use_graph and steady else None,
-                          lambda static_in: static_in.copy_(feats, non_blocking=True))
-
-    @torch.no_grad()
-    def flush(self):
-        """End of the utterance: ``latency_frames`` zero frames with the end-of-utterance windows (every launch stores
-        zeros past the utterance's last column, as the whole-utterance padding is) -> the last ``min(latency_samples,
-        frames * up)`` samples, (batch, samples).  Zero-length before anything was pushed and on a second call.  The next
-        utterance starts with ``reset()``."""
-        if not self._started or self._flushed:
-            return self._empty()
-        total = self.frames_in
-        zeros = torch.zeros((self.batch, self._in_channels, self.latency_frames), device=self._device)
-        y = self._run(zeros, self._halves[self._cur], self._halves[1 - self._cur], total, total)
-        y = y[:, max(0, self.latency_samples - total * self.up):self.latency_samples].contiguous()
-        self._flushed = True  # (the halves are not swapped: nothing may follow but reset())
-        self.samples_out += y.shape[1]
-        return y
+        self._require_plan(plan, batch, precision)
+        super().__init__(model, plan, batch, use_graph, normalize_before, precision, lookahead_state_shapes(plan, batch))
 
 
-class MelGANLookaheadStream(_Stream):
+class MelGANLookaheadStream(_LookaheadStream):
     """Stateful streaming synthesis for the standard NON-causal ``MelGANGenerator`` (reflect padding: every recipe and
-    released checkpoint, ``multi_band_melgan.v2`` included) with a fixed look-ahead.  The interface and the emission
-    rule are :class:`LookaheadStream`'s: after any push the samples emitted total ``max(0, frames_in * up -
-    latency_samples)``, ``flush()`` returns the tail, after which the emissions total ``frames * up`` samples; any
-    partition of the same frames gives bit-identical audio, equal to the whole-utterance ``forward`` / ``inference`` up
-    to fp32 summation order.  ``latency_samples`` is 1425 (5.6 frames) for ``melgan.v1``, 2720 (10.6 frames) for the
-    LJSpeech ``multi_band_melgan.v2`` (scales ``[8, 4, 2]``) and 4208 (14.0 frames) for its 24 kHz variants (``[5, 5, 3]``).
+    released checkpoint, ``multi_band_melgan.v2`` included) with a fixed look-ahead.  Interface, emission rule, graph
+    rule and ``flush`` / ``close``: :class:`_LookaheadStream`; the whole-utterance forward is ``forward`` /
+    ``inference``.  ``latency_samples`` is 1425 (5.6 frames) for ``melgan.v1``, 2720 (10.6 frames) for the LJSpeech
+    ``multi_band_melgan.v2`` (scales ``[8, 4, 2]``) and 4208 (14.0 frames) for its 24 kHz variants (``[5, 5, 3]``).
 
-    How: as in :class:`LookaheadStream` every layer runs in its causal form on a shifted time axis.
-    A reflect-padded layer of padding ``p`` produces output column ``q`` once input column ``q + p`` has arrived, and by
-    then the columns reflection reads at either edge have arrived too; its launch (csrc/conv1d_stream.hip, the mirrored
-    form) reads its window through a mirror at the edges of the input's valid window, while the history keeps the raw
-    stored zeros.  The transposed and 1 x 1 convolutions run the delayed form unchanged; a residual stack is three
-    launches, the skip branch going through a delay line.  ``model.lookahead_plan()`` lists the delays.
+    How: a reflect-padded layer of padding ``p`` produces output column ``q`` once input column
+    ``q + p`` has arrived, and by then the columns reflection reads at either edge have arrived too; its launch
+    (csrc/conv1d_stream.hip, the mirrored form) reads its window through a mirror at the edges of the input's valid
+    window, while the history keeps the raw stored zeros.  The transposed and 1 x 1 convolutions run the delayed form
+    unchanged; a residual stack is three launches, the skip branch going through a delay line.
 
     Multi-band (``model.pqmf`` attached, ``out_channels == pqmf.subbands``): the sub-band columns of a push go through
     ``PQMF.stream_synthesis`` in the same push, as in :class:`CausalStream` -- the stored zeros around the utterance are
     the zero padding the whole-utterance synthesis applies -- and ``latency_samples`` = generator delay * K + the PQMF's
     ``K * stream_delay_columns``.  ``flush()`` drains that tail too.
 
-    ``use_graph``: a captured graph has fixed window arguments, so a push replays one only if no launch has an edge of
-    the utterance in its window or history and nothing is trimmed from its emission: ``settle_frames`` frames went
-    before it (``frames_before * rate >= delay + pad`` for every launch, and ``latency_frames``).  Earlier pushes and
-    ``flush()`` run eagerly.  ``flush()`` pushes ``latency_frames`` dummy frames with the end-of-utterance windows; their
-    content is never read, because the first layer mirrors at the utterance's end.  An utterance too short for
-    reflection (fewer than ``min_frames`` frames: 4 for a first layer of kernel 7), which the whole-utterance forward
-    cannot pad either, makes ``flush()`` raise.  ``close()`` does not flush: an unflushed tail is dropped.
-
-    ``precision`` may be ``None`` or ``"fp32"``: the mirrored form has no bf16 form yet.
+    ``settle_frames``: ``frames_before * rate >= delay + pad`` for every launch, and ``latency_frames``.  The frames
+    ``flush()`` feeds are dummies: the first layer mirrors at the utterance's end.  ``min_frames``: 4 for a first layer
+    of kernel 7.  ``precision`` may be ``None`` or ``"fp32"``: the mirrored form has no bf16 form yet.
     """
 
-    warmup_frames = 1
-
     def __init__(self, model, batch=1, use_graph=True, normalize_before=False, precision=None):
-        from ..layers.causal_conv import (launch_desc, launch_is_mirrored, lookahead_settle_frames, lookahead_state_shapes,
-                                          mirrored_min_frames)
+        from ..layers.causal_conv import lookahead_settle_frames, lookahead_state_shapes, mirrored_min_frames
 
-        if precision == "bf16":
-            raise ValueError("MelGANLookaheadStream: precision='bf16' is not available: the mirrored form of the streaming "
-                             "kernel, which the reflect-padded layers run, does not exist with bf16 operands yet")
-        if precision not in (None, "fp32"):
-            raise ValueError(f"MelGANLookaheadStream: precision must be None or 'fp32', got {precision!r}")
+        precision = self._checked_precision(precision, "the mirrored form of the streaming kernel, which the reflect-padded "
+                                            "layers run, does not exist with bf16 operands yet")
         plan, pqmf, out_channels = self._checked_model(model)
         batch = self._checked_batch(batch)
-        for launch in plan:
-            desc = launch_desc(launch, batch, 8)
-            ok = conv1d_stream_mirrored_supported(desc) if launch_is_mirrored(launch) else \
-                conv1d_stream_delayed_supported(desc, launch.delay1, launch.delay2)
-            if not ok:
-                raise ValueError(f"MelGANLookaheadStream: {launch.conv} cannot be streamed: "
-                                 + _lib.lib().pwg_last_error().decode(errors="replace"))
-        self.precision = "fp32"
+        self._require_plan(plan, batch, precision)
         self.pqmf = pqmf
         self.subbands = out_channels
-        self.up = model.upsample_factor * out_channels  # samples per frame
-        self._plan = plan
-        self._in_channels = plan[0].conv.in_channels
-        self._pq_delay = pqmf.stream_delay_columns if pqmf is not None else 0
-        self._front = plan[-1].delay * out_channels  # samples the generator's own delay puts in front of the audio
-        self.latency_samples = self._front + self._pq_delay * out_channels
-        self.latency_frames = -(-self.latency_samples // self.up)
-        self.settle_frames = max(lookahead_settle_frames(plan), self.latency_frames)
-        self.min_frames = mirrored_min_frames(plan)
-        super().__init__(model, [], batch, use_graph, normalize_before,
-                         lookahead_state_shapes(plan, batch) + ([pqmf.history_shape(batch)] if pqmf is not None else []))
+        super().__init__(model, plan, batch, use_graph, normalize_before, precision, lookahead_state_shapes(plan, batch),
+                         pqmf, lookahead_settle_frames(plan), mirrored_min_frames(plan))
 
-    @staticmethod
-    def _checked_model(model):
+    @classmethod
+    def _checked_model(cls, model):
         """The refusals that need no device, in order: the class, a causal model, the padding and the layer geometry (the
         plan), the sub-bands, a bf16 model -> ``(plan, pqmf or None, out_channels)``."""
-        from ..layers.conv import each_conv
-        from ..layers.pqmf import PQMF
         from ..models import MelGANGenerator
 
-        name = "MelGANLookaheadStream"
+        name = cls.__name__
         if not isinstance(model, MelGANGenerator):
             raise ValueError(f"{name}: {model.__class__.__name__} is not supported (only the non-causal MelGANGenerator; "
                              "HiFiGANGenerator streams through utils.LookaheadStream, ParallelWaveGANGenerator through "
@@ -830,29 +905,13 @@ class MelGANLookaheadStream(_Stream):
         except ValueError as e:
             raise ValueError(f"{name}: {e}") from None
         out_channels = plan[-1].conv.out_channels
-        pqmf = getattr(model, "pqmf", None)
-        if out_channels != 1 and pqmf is None:
-            raise ValueError(f"{name}: the generator emits {out_channels} sub-bands; only a multi-band MelGANGenerator with "
-                             "its PQMF attached (model.pqmf = PQMF(subbands=...), as utils.load_model does) can be "
-                             "streamed, through the stateful PQMF synthesis")
-        if pqmf is not None:
-            if not isinstance(pqmf, PQMF) or pqmf.subbands != out_channels:
-                raise ValueError(f"{name}: model.pqmf must be a PQMF with as many sub-bands as the generator emits "
-                                 f"({out_channels}); got {getattr(pqmf, 'subbands', pqmf.__class__.__name__)}")
-            if pqmf.subbands > 8:
-                raise ValueError(f"{name}: a PQMF of {pqmf.subbands} sub-bands cannot be streamed (the stream kernel "
-                                 "covers up to 8)")
-        if any(cv.precision != "fp32" for cv in each_conv(model)):
-            raise ValueError(f"{name}: the model is in bf16 inference precision; the look-ahead stream of a reflect-padded "
-                             "model is fp32 (utils.set_inference_precision(model, 'fp32'))")
+        pqmf = cls._checked_pqmf(model, out_channels)
+        cls._refuse_bf16_model(model, "fp32", "look-ahead stream of a reflect-padded model", has_bf16=False)
         return plan, pqmf, out_channels
 
     @classmethod
-    def latency_samples_of(cls, model):
-        """Samples every output leaves late, from the module geometry alone (no device, no kernel): the generator's
-        delay times the sub-band count, plus the PQMF's ``K * stream_delay_columns`` for a multi-band model."""
-        plan, pqmf, k = cls._checked_model(model)
-        return (plan[-1].delay + (pqmf.stream_delay_columns if pqmf is not None else 0)) * k
+    def _plan_of(cls, model):
+        return cls._checked_model(model)[:2]
 
     @classmethod
     def settle_frames_of(cls, model):
@@ -871,138 +930,52 @@ class MelGANLookaheadStream(_Stream):
 
         return mirrored_min_frames(cls._checked_model(model)[0])
 
-    def reset(self):
-        """Back to start of stream; an unflushed tail is dropped."""
-        self._restart()
-        self._flushed = False
 
-    def _run(self, c, state_in, state_out, frames_before=None, total_frames=None):
-        """``c``: (batch, C, n) features, normalised; ``state_in`` (None: start of stream) / ``state_out``: one
-        ping-pong half each (a multi-band stream's end with the PQMF's history); ``frames_before`` None: steady state.
-        -> (batch, samples): the positions of the whole late stream (zeros, then the utterance) this push completes."""
-        from ..layers.causal_conv import LookaheadWalk
-
-        k = len(state_out) - (self.pqmf is not None)
-        walk = LookaheadWalk(self._plan, None if state_in is None else state_in[:k], state_out[:k], frames_before,
-                             total_frames)
-        y = self.model.lookahead_forward(c, walk)
-        if self.pqmf is None:
-            return y.reshape(self.batch, -1)
-        n_cols = y.shape[-1]
-        n_emit = n_cols if frames_before is None else self._positions(frames_before, c.shape[-1])[1] // self.subbands
-        return self.pqmf.stream_synthesis(y, None if state_in is None else state_in[-1], state_out[-1], n_emit)
-
-    def _positions(self, frames_before, n):
-        """``(first, count)``: the samples of the whole late stream that a push of ``n`` frames after ``frames_before``
-        completes -- all of its ``n * up`` for a full-band model, those ``stream_delay_columns`` behind the newest
-        column for a multi-band one."""
-        hold = self._pq_delay * self.subbands
-        first = max(0, frames_before * self.up - hold)
-        return first, max(0, (frames_before + n) * self.up - hold) - first
-
-    def _capture(self, feats):
-        static_in = feats.clone()
-        return static_in, _capture_directions(self._halves, lambda si, so: self._run(self._features(static_in), si, so))
-
-    @torch.no_grad()
-    def push(self, feats):
-        """feats: (n, C) or (batch, n, C) float features -> (batch, samples) fp32, the samples that became complete:
-        ``n * up`` once ``latency_samples`` are behind, fewer (or none) before.  The result is the caller's own tensor."""
-        if self._flushed:
-            raise RuntimeError("MelGANLookaheadStream.push: the utterance was flushed; reset() starts the next one")
-        feats = self._coerce(feats)
-        n = feats.shape[1]
-        if n == 0:
-            return self._empty()
-        before = self.frames_in
-        self.frames_in += n
-        skip = max(0, self._front - self._positions(before, n)[0])  # samples of this push in front of the first one
-        steady = before >= self.settle_frames                       # no edge in reach, nothing to trim
-        return self._step(n, (n, feats.shape[2]),
-                          lambda si, so: self._run(self._features(feats), si, so, before)[:, skip:].contiguous(),
-                          (lambda: self._capture(feats)) if self.use_graph and steady else None,
-                          lambda static_in: static_in.copy_(feats, non_blocking=True))
-
-    @torch.no_grad()
-    def flush(self):
-        """End of the utterance: ``latency_frames`` dummy frames with the end-of-utterance windows (the first layer
-        mirrors at the utterance's last frame, so their content is never read; every launch stores zeros past the
-        utterance's last column; a multi-band model's PQMF tail drains with them) -> the last ``min(latency_samples,
-        frames * up)`` samples, (batch, samples).  Zero-length before anything was pushed and on a second call.
-        RuntimeError for an utterance shorter than ``min_frames``.  The next utterance starts with ``reset()``."""
-        if not self._started or self._flushed:
-            return self._empty()
-        total = self.frames_in
-        if total < self.min_frames:
-            raise RuntimeError(f"MelGANLookaheadStream.flush: the utterance has {total} frame(s); reflection padding needs "
-                               f"at least {self.min_frames} (the whole-utterance forward cannot pad a shorter one either)")
-        dummy = torch.zeros((self.batch, self._in_channels, self.latency_frames), device=self._device)
-        y = self._run(dummy, self._halves[self._cur], self._halves[1 - self._cur], total, total)
-        first = self._positions(total, self.latency_frames)[0]
-        y = y[:, max(0, self._front - first):self._front + total * self.up - first].contiguous()
-        self._flushed = True  # (the halves are not swapped: nothing may follow but reset())
-        self.samples_out += y.shape[1]
-        return y
-
-
-class PWGLookaheadStream(_Stream):
+class PWGLookaheadStream(_LookaheadStream):
     """Stateful streaming synthesis for the standard NON-causal ``ParallelWaveGANGenerator`` (every recipe and released
-    checkpoint) with a fixed look-ahead: ``push`` takes the next mel frames of ``batch`` lock-step streams, and
-    optionally the noise for their samples, at ``n`` frames of work, and every sample leaves ``latency_samples`` late
-    (``latency_frames``: the ceiling in frames; 3921 samples = 15.3 frames for ``parallel_wavegan.v1``).  After any push
-    the samples emitted total ``max(0, frames_in * up - latency_samples)``; ``flush()`` returns the tail, after which the
-    emissions total ``frames * up`` samples.  Any partition of the same frames and noise gives bit-identical audio, equal
-    to ``model.inference`` up to fp32 summation order.
+    checkpoint) with a fixed look-ahead; ``push`` also takes, optionally, the noise for the samples of its frames, and
+    the whole-utterance forward is ``model.inference``.  Interface, emission rule, graph rule, ``flush`` / ``close`` and
+    the precision's scope: :class:`_LookaheadStream`.  ``latency_samples`` is 3921 (15.3 frames) for
+    ``parallel_wavegan.v1``; ``settle_frames == latency_frames``, ``min_frames == 1``.
 
-    How: every layer runs in its causal form on a shifted time axis.  ``conv_in`` is ``w`` frames late
-    and starts from its first frame replicated; an upsampling stage of scale ``s`` takes a delay ``D`` to ``D * s + s``;
-    the noise waits in a delay line for the conditioning; a gated layer of dilation ``d`` adds ``d`` columns, takes its
-    residual from the middle tap, reads the conditioning from one shared line at its own delay and the running skip sum
-    through a line of ``d`` columns (csrc/wavenet_stream.hip, the delayed form; one launch per layer); every launch
-    stores exact zeros outside the utterance.  ``model.lookahead_plan()`` lists the launches, delays and state.
+    How: ``conv_in`` is ``w`` frames late and starts from its first frame replicated; an upsampling
+    stage of scale ``s`` takes a delay ``D`` to ``D * s + s``; the noise waits in a delay line for the conditioning; a
+    gated layer of dilation ``d`` adds ``d`` columns, takes its residual from the middle tap, reads the conditioning from
+    one shared line at its own delay and the running skip sum through a line of ``d`` columns
+    (csrc/wavenet_stream.hip, the delayed form; one launch per layer); every launch stores exact zeros outside the
+    utterance.  ``model.lookahead_plan()`` lists the launches, delays and state.
 
-    State (``state_bytes``: both ping-pong halves): the layers' histories (``2 d`` columns each), their skip lines, the
-    conditioning line (``sum d`` columns of 80 rows), the noise line and the upsampler's few columns -- about 3.3 MB
-    per half and stream for V1.  ``use_graph``: a push with ``latency_frames`` frames before it replays the two
-    captured graphs of its chunk size, as in :class:`LookaheadStream`; the pushes at the start of an utterance and
-    ``flush()`` run eagerly.  Noise is never drawn inside a graph.  ``close()`` does not flush: an unflushed tail is
-    dropped.
+    State: the layers' histories (``2 d`` columns each), their skip lines, the conditioning line (``sum d`` columns of 80
+    rows), the noise line and the upsampler's few columns -- about 3.3 MB per half and stream for V1.  Noise is never
+    drawn inside a graph.  ``flush()`` feeds ``latency_frames`` copies of the last frame (what ``inference()``'s
+    replicate padding gives ``conv_in`` on the right) with zero noise.
 
-    ``precision="bf16"``: ``conv_in``, the 1 x 1 convolutions and the gated layers of every push, the eager pushes at the
-    start of an utterance and ``flush()`` included, run with bf16 operands (csrc/conv1d_stream_bf16.hip and
-    csrc/wavenet_stream_bf16.hip, the delayed forms; DESIGN.md s11.7: windows, weights and the gate output are rounded to
-    bf16; sums, the gate, biases, residual, skip sum, tensors, history and lines stay fp32; the stretch stages and the
-    delay lines stay fp32).  As in :class:`LookaheadStream` the precision belongs to the stream, is fixed for its life
-    (``.precision``) and neither reads nor writes the modules' own ``precision`` attributes; plan, latency, state and
-    partition invariance are those of the fp32 stream.  ``None`` and ``"fp32"`` are the fp32 stream, which refuses a
-    model that ``set_inference_precision`` put in bf16 mode.
+    ``precision="bf16"``: ``conv_in``, the 1 x 1 convolutions and the gated layers run with bf16 operands
+    (csrc/conv1d_stream_bf16.hip and csrc/wavenet_stream_bf16.hip, the delayed forms; DESIGN.md s11.7: windows, weights
+    and the gate output are rounded to bf16; sums, the gate, biases, residual, skip sum, tensors, history and lines stay
+    fp32; the stretch stages and the delay lines stay fp32).
     """
 
-    warmup_frames = 1
+    _takes_noise = _keeps_last = True
 
     def __init__(self, model, batch=1, use_graph=True, normalize_before=False, precision=None):
         from ..layers.causal_conv import pointwise_desc, pwg_lookahead_state_shapes
-        from ..layers.conv import each_conv
         from ..models import HiFiGANGenerator, ParallelWaveGANGenerator
 
-        if precision not in (None, "fp32", "bf16"):
-            raise ValueError(f"PWGLookaheadStream: precision must be None, 'fp32' or 'bf16', got {precision!r}")
+        precision = self._checked_precision(precision)
         if not isinstance(model, ParallelWaveGANGenerator):
             hint = "; the non-causal HiFiGANGenerator streams through utils.LookaheadStream" \
                 if isinstance(model, HiFiGANGenerator) else ""
             raise ValueError(f"PWGLookaheadStream: {model.__class__.__name__} is not supported (only the non-causal "
                              f"ParallelWaveGANGenerator{hint})")
         batch = self._checked_batch(batch)
-        reason = model.lookahead_unsupported_reason(batch, precision or "fp32")
+        reason = model.lookahead_unsupported_reason(batch, precision)
         if reason is not None:
             raise ValueError(f"PWGLookaheadStream: {reason}")
         if model.in_channels != 1 or model.out_channels != 1:
             raise ValueError(f"PWGLookaheadStream: in_channels / out_channels = {model.in_channels} / {model.out_channels} "
                              "(the stream takes one noise row and emits one waveform per stream)")
-        if precision != "bf16" and any(cv.precision != "fp32" for cv in each_conv(model)):
-            raise ValueError("PWGLookaheadStream: the model is in bf16 inference precision; the fp32 look-ahead stream "
-                             "does not read that mode (utils.set_inference_precision(model, 'fp32'), or stream with bf16 "
-                             "operands: PWGLookaheadStream(model, precision='bf16'))")
+        self._refuse_bf16_model(model, precision, "look-ahead stream")
         plan = model.lookahead_plan()
         if precision == "bf16":  # a bf16 stream never runs a convolution the bf16 kernel refuses in fp32 instead
             for launch in plan:
@@ -1012,94 +985,18 @@ class PWGLookaheadStream(_Stream):
                     desc = pointwise_desc(launch.module, batch, 8)
                 else:
                     continue
-                if not conv1d_stream_bf16_delayed_supported(desc):
-                    raise ValueError(f"PWGLookaheadStream: {launch.module} cannot be streamed with bf16 operands: "
-                                     + _lib.lib().pwg_last_error().decode(errors="replace"))
-        self.precision = precision or "fp32"  # of the stream, fixed for its life
-        self.up = model.upsample_factor  # samples per frame
-        self._plan = plan
-        self.latency_samples = plan[-1].delay
-        self.latency_frames = -(-self.latency_samples // self.up)
-        super().__init__(model, [], batch, use_graph, normalize_before, pwg_lookahead_state_shapes(plan, batch))
-
-    @staticmethod
-    def latency_samples_of(model):
-        """Samples every output leaves late, from the module geometry alone (no device, no kernel)."""
-        return model.lookahead_plan()[-1].delay
-
-    def reset(self):
-        """Back to start of stream; an unflushed tail is dropped."""
-        self._restart()
-        self._flushed = False
-        self._last = None  # the last frame pushed, (batch, 1, C): the flush replicates it
+                self._require_supported(conv1d_stream_bf16_delayed_supported(desc), launch.module, " with bf16 operands")
+        super().__init__(model, plan, batch, use_graph, normalize_before, precision,
+                         pwg_lookahead_state_shapes(plan, batch))
 
     def _run(self, feats, z, state_in, state_out, frames_before=None, total_frames=None):
-        """``feats``: (batch, n, C) features; ``z``: (batch, 1, n * up) noise; ``state_in`` (None: start of stream) /
-        ``state_out``: one ping-pong half each; ``frames_before`` None: steady state.  -> (batch, n * up), not trimmed."""
+        """``feats``: (batch, n, C) features; ``z``: (batch, 1, n * up) noise; the rest as in the core."""
         from ..layers.causal_conv import PWGLookaheadWalk
 
         walk = PWGLookaheadWalk(self._plan, state_in, state_out, frames_before, total_frames, self.precision)
         return self.model.lookahead_forward(z, self._features(feats), walk).reshape(self.batch, -1)
 
-    def _capture(self, feats, z):
-        static_in, static_z = feats.clone(), z.clone()
-        return static_in, static_z, _capture_directions(self._halves, lambda si, so: self._run(static_in, static_z, si, so))
-
-    @torch.no_grad()
-    def push(self, feats, noise=None):
-        """feats: (n, C) or (batch, n, C) float features; noise: (batch, n * up) or (n * up,) (the same for every
-        stream) for the samples of THESE frames, undelayed, drawn with ``torch.randn`` on the device if omitted ->
-        (batch, samples) fp32, the samples that became complete: ``n * up`` once ``latency_samples`` are behind, fewer
-        (or none) before.  The result is the caller's own tensor."""
-        if self._flushed:
-            raise RuntimeError("PWGLookaheadStream.push: the utterance was flushed; reset() starts the next one")
-        feats = self._coerce(feats)
-        n = feats.shape[1]
-        if noise is not None:
-            noise = torch.as_tensor(noise, dtype=torch.float32).to(self._device)
-            if noise.dim() == 1:
-                noise = noise.unsqueeze(0).expand(self.batch, -1)
-            if tuple(noise.shape) != (self.batch, n * self.up):
-                raise ValueError(f"PWGLookaheadStream.push: expected ({n * self.up},) or ({self.batch}, {n * self.up}) "
-                                 f"noise for {n} frame(s), got {tuple(noise.shape)}")
-            noise = noise.reshape(self.batch, 1, n * self.up).contiguous()
-        if n == 0:
-            return self._empty()
-        before = self.frames_in
-        self.frames_in += n
-        self._last = feats[:, -1:, :].clone()
-        skip = max(0, self.latency_samples - before * self.up)  # columns of this chunk in front of the first sample
-        steady = before >= self.latency_frames                  # every launch's window is full
-
-        def eager(state_in, state_out):
-            z = noise if noise is not None else torch.randn(self.batch, 1, n * self.up, device=self._device)
-            return self._run(feats, z, state_in, state_out, before)[:, skip:].contiguous()
-
-        def capture():
-            return self._capture(feats, torch.zeros(self.batch, 1, n * self.up, device=self._device))
-
-        def fill_static(static_in, static_z):
-            static_in.copy_(feats, non_blocking=True)
-            if noise is None:
-                static_z.normal_()  # (outside the graph: a replay never draws)
-            else:
-                static_z.copy_(noise, non_blocking=True)
-
-        return self._step(n, (n, feats.shape[2]), eager, capture if self.use_graph and steady else None, fill_static)
-
-    @torch.no_grad()
-    def flush(self):
-        """End of the utterance: ``latency_frames`` copies of the last frame (what ``inference()``'s replicate padding
-        gives ``conv_in`` on the right) with zero noise and the end-of-utterance windows (every launch stores zeros past
-        the utterance's last column) -> the last ``min(latency_samples, frames * up)`` samples, (batch, samples).
-        Zero-length before anything was pushed and on a second call.  The next utterance starts with ``reset()``."""
-        if not self._started or self._flushed:
-            return self._empty()
-        total = self.frames_in
+    def _run_tail(self, state_in, state_out, total):
         feats = self._last.expand(-1, self.latency_frames, -1).contiguous()
         zeros = torch.zeros((self.batch, 1, self.latency_frames * self.up), device=self._device)
-        y = self._run(feats, zeros, self._halves[self._cur], self._halves[1 - self._cur], total, total)
-        y = y[:, max(0, self.latency_samples - total * self.up):self.latency_samples].contiguous()
-        self._flushed = True  # (the halves are not swapped: nothing may follow but reset())
-        self.samples_out += y.shape[1]
-        return y
+        return self._run(feats, zeros, state_in, state_out, total, total)

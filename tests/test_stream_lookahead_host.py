@@ -10,7 +10,7 @@ import torch.nn.functional as F
 
 from oracle import torch_cpu
 from parallelwavegan_amd import _lib, layers, models, ops
-from parallelwavegan_amd.layers.causal_conv import lookahead_desc, lookahead_state_shapes
+from parallelwavegan_amd.layers.causal_conv import lookahead_desc, lookahead_settle_frames, lookahead_state_shapes
 from parallelwavegan_amd.utils import LookaheadStream, set_inference_precision
 from tests.golden import synth
 from tests.util import max_abs, synth_for
@@ -25,6 +25,15 @@ def _why():
                                          (synth.HIFIGAN_TINY, 182)])
 def test_latency_from_the_geometry(cfg, latency):
     assert LookaheadStream.latency_samples_of(models.HiFiGANGenerator(**cfg)) == latency
+
+
+@pytest.mark.parametrize("cfg", [synth.HIFIGAN_V1, synth.HIFIGAN_V1_LIBRITTS, synth.HIFIGAN_TINY,
+                                 dict(synth.HIFIGAN_TINY, use_additional_convs=False)])
+def test_no_launch_settles_later_than_the_output(cfg):
+    """``LookaheadStream`` replays a graph once ``latency_frames`` frames went before a push: its ``settle_frames`` is the
+    look-ahead core's degenerate value, which is right because the last launch has the largest delay in frames."""
+    g = models.HiFiGANGenerator(**cfg)
+    assert lookahead_settle_frames(g.lookahead_plan()) == -(-LookaheadStream.latency_samples_of(g) // g.upsample_factor)
 
 
 def test_delay_plan_of_the_tiny_config():
