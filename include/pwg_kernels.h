@@ -261,6 +261,33 @@ int pwg_conv1d_split_forward_cfg(const pwg_conv1d_desc* d, const float* x, const
                                  const float* add1, const float* add2, float* y, int32_t mfma_shape, int32_t tile_mode,
                                  void* stream);
 
+/* ---- split-operand inference of the upsampling layers (csrc/conv1d_split.hip, convtr1d_split_mfma_kernel) ----
+ * The fused transposed convolution of pwg_conv1d_forward at the ConvTranspose1d call site of the HiFi-GAN generator
+ * (models/hifigan.py:184-185: `c = self.upsamples[i](c)`, LeakyReLU + ConvTranspose1d with kernel == 2 * stride,
+ * under torch.no_grad(), bin/decode.py:158-169), computed under the numerical definition of the split-operand inference above, points 1 - 4 word for
+ * word.  Covered: transposed descriptors with kernel == 2 * stride (any stride, odd ones included), groups == 1,
+ * width == 1, zero padding, forward only; a stride-1 descriptor is refused (it belongs to pwg_conv1d_split_*), and
+ * pwg_conv1d_split_supported keeps refusing transposed ones.  The contraction is the polyphase one of the bf16 kernel
+ * (rows co * stride + phase, two taps); the image is three parts of the bf16 kernel's transposed image
+ * (pwg_convtr1d_split_packed_weight_bytes == 3 x pwg_conv1d_bf16_packed_weight_bytes), `scale` per INPUT channel as
+ * torch lays out a ConvTranspose1d weight.  Output samples are written 16 B at a time when stride % 4 == 0,
+ * padding % 4 == 0, t_out % 4 == 0 and y / add1 / add2 are 16-B aligned, else 4 B at a time; samples outside
+ * [0, t_out) are never written.  Deterministic; the accumulation order of an element is that of
+ * pwg_conv1d_split_forward on the stride-1 twin of the layer (kernel 2, pad_left 1, rows co * stride + phase), so the
+ * two agree bit for bit.  pwg_convtr1d_split_supported is pure host logic (pwg_last_error names the reason for 0).
+ * pwg_convtr1d_split_forward takes the arguments of pwg_conv1d_forward (the workspace is never used);
+ * pwg_convtr1d_split_forward_cfg (tuning / tests): mfma_shape and tile_mode as for pwg_conv1d_split_forward_cfg.     */
+int pwg_convtr1d_split_supported(const pwg_conv1d_desc* d);
+size_t pwg_convtr1d_split_packed_weight_bytes(const pwg_conv1d_desc* d);
+int pwg_convtr1d_split_pack_weight(const pwg_conv1d_desc* d, const float* w, const float* scale, void* w_packed,
+                                   void* stream);
+int pwg_convtr1d_split_forward(const pwg_conv1d_desc* d, const float* x, const void* w_packed, const float* bias,
+                               const float* add1, const float* add2, float* y, float* workspace,
+                               size_t workspace_floats, void* stream);
+int pwg_convtr1d_split_forward_cfg(const pwg_conv1d_desc* d, const float* x, const void* w_packed, const float* bias,
+                                   const float* add1, const float* add2, float* y, int32_t mfma_shape,
+                                   int32_t tile_mode, void* stream);
+
 /* ---- stateful streaming form of the causal convolutions (fp32; csrc/conv1d_stream.hip; ABI v14) ----
  * The causal layers of the reference -- CausalConv1d.forward, layers/causal_conv.py:32-42 (`self.conv(self.pad(x))
  * [:, :, :x.size(2)]`), and CausalConvTranspose1d.forward, :68-78 (`self.deconv(self.pad(x))[:, :, self.stride :

@@ -146,6 +146,13 @@ SIGNATURES = {
                                                 ctypes.c_size_t, _vp]),
     "pwg_conv1d_split_forward_cfg": (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32,
                                                     _vp]),
+    "pwg_convtr1d_split_supported": (ctypes.c_int, [ctypes.POINTER(ConvDesc)]),
+    "pwg_convtr1d_split_packed_weight_bytes": (ctypes.c_size_t, [ctypes.POINTER(ConvDesc)]),
+    "pwg_convtr1d_split_pack_weight": (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, _vp]),
+    "pwg_convtr1d_split_forward": (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                  ctypes.c_size_t, _vp]),
+    "pwg_convtr1d_split_forward_cfg": (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32,
+                                                      _vp]),
     "pwg_conv1d_stream_supported": (ctypes.c_int, [ctypes.POINTER(ConvDesc)]),
     "pwg_conv1d_stream_hist_floats": (ctypes.c_size_t, [ctypes.POINTER(ConvDesc)]),
     "pwg_conv1d_stream_forward": (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

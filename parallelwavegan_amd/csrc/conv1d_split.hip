@@ -15,7 +15,8 @@
 // Non-finite inputs give non-finite outputs, but not necessarily the same ones: hi(inf) = inf and r = inf - inf = NaN, so
 // an inf comes out as NaN.  There is no branch for it.
 //
-// Scope: stride-1 Conv1d, groups 1, width 1, zero padding, forward only.
+// Scope: stride-1 Conv1d, groups 1, width 1, zero padding, forward only (conv1d_split_mfma_kernel); and, under the same
+// definition, ConvTranspose1d with kernel == 2 * stride (convtr1d_split_mfma_kernel, further down).
 // Contraction, coverage, weight image, tiles and launch plan are those of csrc/mfma_conv.h, with three parts: A operand =
 // three weight images read from global memory (L2-resident), B operand = three bf16 planes of the x window in LDS, staged
 // per 32-channel chunk.  A wave holds all A and B fragments of a reduction step (3 x TM + 3 x TN) and issues 6 x TM x TN
@@ -295,6 +296,20 @@ struct Family {
   };
 };
 
+// what the stride-1 and the transposed launch fill alike.  wide_out here is the stride-1 rule (a value = 4 consecutive
+// samples of an output row); the transposed launch adds its own conditions
+static void split_fill_args(SplitArgs* a, const pwg_conv1d_desc* d, const MfmaConvGeom& g, const MfmaConvPlan& p,
+                            const float* x, const void* w_packed, const float* bias, const float* add1, const float* add2,
+                            float* y) {
+  mfma_conv_fill_args(a, d, g, x, w_packed, bias, add1, add2, y);
+  a->plane = p.plane;
+  a->part_stride = image_elems(g) / 8;
+  a->pre_mul = d->pre_act == PWG_ACT_LEAKY_RELU ? d->pre_slope : (d->pre_act == PWG_ACT_RELU ? 0.0f : 1.0f);
+  a->pre_mask = d->pre_act == PWG_ACT_RELU ? 0u : ~0u;
+  a->wide_out = d->t_out % 4 == 0 && ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(add1) |
+                                       reinterpret_cast<uintptr_t>(add2)) & 15u) == 0;
+}
+
 static int split_forward(const pwg_conv1d_desc* d, const float* x, const void* w_packed, const float* bias,
                          const float* add1, const float* add2, float* y, int mfma_shape, int tile_mode,
                          hipStream_t stream) {
@@ -304,13 +319,7 @@ static int split_forward(const pwg_conv1d_desc* d, const float* x, const void* w
   if (rc != PWG_OK) return rc;
   const MfmaConvPlan p = mfma_conv_plan(d, g, PARTS, tile_mode, x, add1, add2);
   SplitArgs a;
-  mfma_conv_fill_args(&a, d, g, x, w_packed, bias, add1, add2, y);
-  a.plane = p.plane;
-  a.part_stride = image_elems(g) / 8;
-  a.pre_mul = d->pre_act == PWG_ACT_LEAKY_RELU ? d->pre_slope : (d->pre_act == PWG_ACT_RELU ? 0.0f : 1.0f);
-  a.pre_mask = d->pre_act == PWG_ACT_RELU ? 0u : ~0u;
-  a.wide_out = d->t_out % 4 == 0 && ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(add1) |
-                                      reinterpret_cast<uintptr_t>(add2)) & 15u) == 0;
+  split_fill_args(&a, d, g, p, x, w_packed, bias, add1, add2, y);
   maybe_poison_lds(stream);
   ProfScope prof(stream, "conv1d_split_mfma_kernel", p.flops, p.bytes);
   if (p.vec)
@@ -321,7 +330,283 @@ static int split_forward(const pwg_conv1d_desc* d, const float* x, const void* w
   return PWG_OK;
 }
 
-// MFMA shape of pwg_conv1d_split_forward (both are built at the same tiles)
+// ---- ConvTranspose1d with kernel == 2 * stride: the polyphase contraction of mfma_conv.h -- rows
+// m = co * s + phase, two taps (x[q - 1], x[q]), sample o = q * s + phase - padding -- under the numerical definition
+// above, word for word: the same staging, the same split_step, the same six products in the same order.  What is its own
+// is the operand order and the epilogue: the WEIGHT fragment is the first MFMA operand, so a lane owns 4 consecutive rows
+// of one column q (mfma_acc_row), which are 4 consecutive samples of one output channel when s % 4 == 0.
+struct ConvtrArgs : SplitArgs {
+  int phases, out_off;  // stride and padding; wide_out additionally needs phases % 4 == 0 and out_off % 4 == 0
+};
+
+static int convtr_geometry(const pwg_conv1d_desc* d, MfmaConvGeom* g) {
+  PWG_REQUIRE(d != nullptr, PWG_ERR_NULL, "convtr1d_split: NULL descriptor");
+  PWG_REQUIRE(d->transposed, PWG_ERR_UNSUPPORTED,
+              "convtr1d_split: not a transposed convolution (a stride-1 Conv1d runs on conv1d_split)");
+  return mfma_conv_geometry("convtr1d_split", PARTS, true, d, g);
+}
+
+// One 32-channel chunk of the x window into the three LDS planes, as conv1d_split_mfma_kernel stages it
+template <int NT, bool VEC>
+__device__ __forceinline__ void stage_chunk(const SplitArgs& a, const MfmaConvTile& c, int chunk, __bf16* xs) {
+  if (VEC) {
+    const int ngroups = (c.wcols + 3) >> 2, c_left = a.c_in - chunk * KC;
+    const float* __restrict__ xc = c.xb + (size_t)chunk * KC * a.t_in;
+    if (c.base >= 0 && c.base + 4 * ngroups <= a.t_in && c_left >= KC)
+      stage_window_vec<NT, false>(a, xc, c_left, c.base, ngroups, xs, c.tid);
+    else
+      stage_window_vec<NT, true>(a, xc, c_left, c.base, ngroups, xs, c.tid);
+  } else {
+    const int c_base = chunk * KC + c.wave * 8;
+    const bool interior = c.base >= 0 && c.base + c.wcols <= a.t_in && c_base + 8 <= a.c_in;  // per wave and chunk
+    for (int col = c.lane; col < c.wcols; col += 64) {
+      const int t = c.base + col;
+      const float* __restrict__ src = c.xb + (size_t)c_base * a.t_in + t;
+      float f[8];
+      if (interior) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) f[j] = src[(size_t)j * a.t_in];
+      } else {
+        const bool tin = t >= 0 && t < a.t_in;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          f[j] = 0.f;
+          if (tin && c_base + j < a.c_in) f[j] = src[(size_t)j * a.t_in];
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) f[j] = pre_activate(f[j], a.pre_mul, a.pre_mask);
+      split3_store<8>(f, xs + col * kConvRow + c.wave * 8, a.plane);
+    }
+  }
+}
+
+// The fp32 tail of a batch of N values of 4 samples, in the fp32 kernel's order (acc + bias + add1 + add2, * out_mul,
+// / out_div, post-activation); bias: per sample (the 4 samples of a value may lie in different channels).  Every switch
+// is wave-uniform and taken once per batch.  The four scalars come by value: read through a reference to the argument
+// struct, 16 of the 20 instantiations kept a piece of it in 24 B of scratch (profiles/convtr_split_resources.txt).
+template <int N>
+__device__ __forceinline__ void convtr_finish(float out_mul, float out_div, int post_act, float post_slope, f32x4 (&v)[N],
+                                              const f32x4& bias, bool has_bias, bool has1, bool has2,
+                                              const f32x4 (&t1)[N], const f32x4 (&t2)[N]) {
+  if (has_bias) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] += bias;
+  }
+  if (has1) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] += t1[k];
+  }
+  if (has2) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] += t2[k];
+  }
+  if (out_mul != 1.0f) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] *= out_mul;
+  }
+  if (out_div != 1.0f) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] = v[k] / out_div;
+  }
+  if (post_act == PWG_ACT_LEAKY_RELU) {
+#pragma unroll
+    for (int k = 0; k < N; ++k)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[k][e] = v[k][e] > 0.f ? v[k][e] : v[k][e] * post_slope;
+  } else if (post_act == PWG_ACT_RELU) {
+#pragma unroll
+    for (int k = 0; k < N; ++k)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[k][e] = v[k][e] > 0.f ? v[k][e] : 0.f;
+  } else if (post_act == PWG_ACT_TANH) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[k][e] = tanhf(v[k][e]);
+      __builtin_amdgcn_sched_barrier(0);  // one value's tanhf at a time, as in split_epilogue
+    }
+  }
+}
+
+// The epilogue of one wave.  Accumulator registers 4 g .. 4 g + 3 of tile (mi, ni) are rows m4 .. m4 + 3
+// (m4 = row0 + mi * TILE + 4 * (64 / TILE) * g, row0 includes 4 * lane_group) of column col0 + ni * TILE: one "value".
+// The structure is split_epilogue's: wave-uniform switches once per batch around straight-line code, the add1 / add2
+// loads of a batch issued together and waited for once, no store waited for.
+// WIDE (s % 4 == 0, padding % 4 == 0, t_out % 4 == 0, y / add1 / add2 16-B aligned): the 4 rows are phases ph .. ph + 3
+// of ONE channel, the value is the 4 samples from o = q * s + ph - padding, 16-B aligned and wholly inside [0, t_out) or
+// wholly outside it; a batch is the TN values of one (mi, g); a 16-lane group covers 16 columns of a row.  FULL: the
+// tile has no padded row and no sample outside [0, t_out); otherwise a load of a missing value reads a clamped address
+// and its store is masked.
+// Otherwise 4-B accesses, a (channel, phase) per sample and batches of one value: s == 2 (two channels x two phases, the
+// pair of a channel starting at the odd sample 2 q - 1), odd strides (rows straddle channels), ragged or unaligned rows.
+// Samples with o < 0 or o >= t_out (first and last q) and padded rows are never written.
+template <int TILE, int TM, int TN, bool WIDE, bool FULL>
+__device__ __forceinline__ void convtr_epilogue(const ConvtrArgs& a, const typename Mfma<TILE>::acc_t (&acc)[TM][TN],
+                                                int row0, int col0, size_t out_base) {
+  constexpr int HL = 64 / TILE, NG = TILE * TILE / 64 / 4;
+  const bool has_bias = a.bias != nullptr, has1 = a.add1 != nullptr, has2 = a.add2 != nullptr;
+  const int s = a.phases, post_act = a.post_act;
+  const float out_mul = a.out_mul, out_div = a.out_div, post_slope = a.post_slope;
+#pragma unroll
+  for (int mi = 0; mi < TM; ++mi) {
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+      const int m4 = row0 + mi * TILE + 4 * HL * g;
+      if (WIDE) {
+        const int mc = FULL ? m4 : min(m4, a.m - 4);  // a.m = c_out * s is a multiple of 4
+        const int co = mc / s, ph = mc - co * s;
+        const size_t row = out_base + (size_t)co * a.t_out;
+        int o[TN];
+#pragma unroll
+        for (int ni = 0; ni < TN; ++ni) o[ni] = (col0 + ni * TILE) * s + ph - a.out_off;
+        auto load = [&](const float* __restrict__ src, f32x4 (&t)[TN]) {
+#pragma unroll
+          for (int ni = 0; ni < TN; ++ni)
+            t[ni] = *reinterpret_cast<const f32x4*>(src + row + (FULL ? o[ni] : min(max(o[ni], 0), a.t_out - 4)));
+        };
+        f32x4 t1[TN], t2[TN], v[TN];
+        float b = 0.f;
+        if (has_bias) b = a.bias[co];
+        if (has1) load(a.add1, t1);
+        if (has2) load(a.add2, t2);
+#pragma unroll
+        for (int ni = 0; ni < TN; ++ni)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[ni][e] = acc[mi][ni][g * 4 + e];
+        const f32x4 bias = {b, b, b, b};
+        convtr_finish<TN>(out_mul, out_div, post_act, post_slope, v, bias, has_bias, has1, has2, t1, t2);
+#pragma unroll
+        for (int ni = 0; ni < TN; ++ni)
+          if (FULL || (m4 < a.m && o[ni] >= 0 && o[ni] < a.t_out)) *reinterpret_cast<f32x4*>(a.y + row + o[ni]) = v[ni];
+      } else {
+        // (channel, phase) of the 4 rows: one division per (mi, g), then counted up
+        int co = m4 / s, ph = m4 - co * s;
+        size_t row[4];
+        int phr[4];
+        f32x4 bias = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int cc = min(co, a.c_out - 1);
+          row[e] = out_base + (size_t)cc * a.t_out;
+          phr[e] = ph - a.out_off;
+          if (has_bias) bias[e] = a.bias[cc];
+          if (++ph == s) ph = 0, ++co;
+        }
+#pragma unroll
+        for (int ni = 0; ni < TN; ++ni) {
+          const int qs = (col0 + ni * TILE) * s;
+          f32x4 t1[1], t2[1], v[1];
+          if (has1) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) t1[0][e] = a.add1[row[e] + min(max(qs + phr[e], 0), a.t_out - 1)];
+          }
+          if (has2) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) t2[0][e] = a.add2[row[e] + min(max(qs + phr[e], 0), a.t_out - 1)];
+          }
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[0][e] = acc[mi][ni][g * 4 + e];
+          convtr_finish<1>(out_mul, out_div, post_act, post_slope, v, bias, has_bias, has1, has2, t1, t2);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int o = qs + phr[e];
+            if (m4 + e < a.m && o >= 0 && o < a.t_out) a.y[row[e] + o] = v[0][e];
+          }
+        }
+      }
+    }
+  }
+}
+
+// The tile ladder, VEC and the second launch bound are those of conv1d_split_mfma_kernel.
+template <int TILE, int WM, int WN, int WAVES_M, bool VEC>
+__global__ __launch_bounds__(256, WM * WN == 4 ? (TILE == 16 ? 3 : 2) : (WM * WN == 2 ? 3 : 4)) void
+convtr1d_split_mfma_kernel(ConvtrArgs a) {
+  constexpr int HL = 64 / TILE;
+  constexpr int KSTEPS = KC / (8 * HL);
+  constexpr int TM = WM * 32 / TILE, TN = WN * 32 / TILE;
+  constexpr int NREG = TILE * TILE / 64;
+  constexpr int WAVES_N = 4 / WAVES_M;
+  constexpr int MT = WAVES_M * WM * 32, NT = WAVES_N * WN * 32;
+  typedef typename Mfma<TILE>::acc_t acc_t;
+
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __bf16* xs = reinterpret_cast<__bf16*>(smem);  // [part][column][ROW]
+
+  const MfmaConvTile c = mfma_conv_tile<TILE, MT, NT, WAVES_M, VEC>(a);
+
+  acc_t acc[TM][TN];
+#pragma unroll
+  for (int mi = 0; mi < TM; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < TN; ++ni)
+#pragma unroll
+      for (int i = 0; i < NREG; ++i) acc[mi][ni][i] = 0.f;
+
+  for (int chunk = 0; chunk < a.cin_chunks; ++chunk) {
+    if (chunk) __syncthreads();
+    stage_chunk<NT, VEC>(a, c, chunk, xs);
+    __syncthreads();
+    for (int tap = 0; tap < a.taps; ++tap) {
+#pragma unroll
+      for (int ks = 0; ks < KSTEPS; ++ks) {
+        const int oct = ks * HL + c.h;
+        const bf16x8* __restrict__ wp =
+            image_rows(a.w, a.cin_chunks, a.m_pad, tap, chunk, oct) + c.m0 + c.wave_m * (WM * 32) + c.r;
+        // the weight fragment goes first: a lane gets 4 consecutive rows (phases) of a column (convtr_epilogue)
+        split_step<TILE, TM, TN, kConvRow, false>(wp, a.part_stride, xs, c.sh + c.wave_n * (WN * 32) + c.r + tap * a.dil,
+                                                  oct * 8, a.plane, acc);
+      }
+    }
+  }
+
+  const size_t out_base = (size_t)c.b * a.c_out * a.t_out;
+  const int row0 = c.m0 + c.wave_m * (WM * 32) + 4 * c.h, col0 = c.q0 + c.wave_n * (WN * 32) + c.r;
+  // no padded row, and every sample of the tile's columns inside the output row
+  const bool full = c.m0 + MT <= a.m && c.q0 * a.phases >= a.out_off && (c.q0 + NT) * a.phases - a.out_off <= a.t_out;
+  if (!a.wide_out)
+    convtr_epilogue<TILE, TM, TN, false, false>(a, acc, row0, col0, out_base);
+  else if (full)
+    convtr_epilogue<TILE, TM, TN, true, true>(a, acc, row0, col0, out_base);
+  else
+    convtr_epilogue<TILE, TM, TN, true, false>(a, acc, row0, col0, out_base);
+}
+
+template <bool VEC>
+struct ConvtrFamily {
+  template <int TILE, int WM, int WN, int WAVES_M>
+  struct K {
+    static constexpr auto fn = convtr1d_split_mfma_kernel<TILE, WM, WN, WAVES_M, VEC>;
+  };
+};
+
+static int convtr_forward(const pwg_conv1d_desc* d, const float* x, const void* w_packed, const float* bias,
+                          const float* add1, const float* add2, float* y, int mfma_shape, int tile_mode,
+                          hipStream_t stream) {
+  MfmaConvGeom g;
+  int rc = convtr_geometry(d, &g);
+  if (rc == PWG_OK) rc = mfma_conv_check_forward("convtr1d_split", d, x, w_packed, y, mfma_shape, tile_mode);
+  if (rc != PWG_OK) return rc;
+  // 32-bit sample index q * s + phase - padding of a column past the end of the last tile
+  PWG_REQUIRE((long)(g.nq + 256) * g.phases < (1L << 31), PWG_ERR_UNSUPPORTED, "convtr1d_split: output row too long");
+  const MfmaConvPlan p = mfma_conv_plan(d, g, PARTS, tile_mode, x, add1, add2);
+  ConvtrArgs a;
+  split_fill_args(&a, d, g, p, x, w_packed, bias, add1, add2, y);
+  a.phases = g.phases;
+  a.out_off = g.out_off;
+  a.wide_out = a.wide_out && g.phases % 4 == 0 && g.out_off % 4 == 0;
+  maybe_poison_lds(stream);
+  ProfScope prof(stream, "convtr1d_split_mfma_kernel", p.flops, p.bytes);
+  if (p.vec)
+    mfma_conv_launch<ConvtrFamily<true>::K>(p, mfma_shape, a, stream);
+  else
+    mfma_conv_launch<ConvtrFamily<false>::K>(p, mfma_shape, a, stream);
+  PWG_CHECK_LAUNCH("convtr1d_split");
+  return PWG_OK;
+}
+
+// MFMA shape of pwg_conv1d_split_forward and pwg_convtr1d_split_forward (both are built at the same tiles)
 constexpr int kDefaultMfmaShape = 16;
 
 }  // namespace
@@ -363,4 +648,40 @@ extern "C" int pwg_conv1d_split_forward_cfg(const pwg_conv1d_desc* d, const floa
                                             const float* bias, const float* add1, const float* add2, float* y,
                                             int32_t mfma_shape, int32_t tile_mode, void* stream) {
   return split_forward(d, x, w_packed, bias, add1, add2, y, mfma_shape, tile_mode, (hipStream_t)stream);
+}
+
+extern "C" int pwg_convtr1d_split_supported(const pwg_conv1d_desc* d) {
+  MfmaConvGeom g;
+  return convtr_geometry(d, &g) == PWG_OK ? 1 : 0;
+}
+
+extern "C" size_t pwg_convtr1d_split_packed_weight_bytes(const pwg_conv1d_desc* d) {
+  MfmaConvGeom g;
+  if (convtr_geometry(d, &g) != PWG_OK) return 0;
+  return (size_t)PARTS * image_elems(g) * sizeof(__bf16);
+}
+
+extern "C" int pwg_convtr1d_split_pack_weight(const pwg_conv1d_desc* d, const float* w, const float* scale, void* w_packed,
+                                              void* stream) {
+  MfmaConvGeom g;
+  int rc = convtr_geometry(d, &g);
+  if (rc != PWG_OK) return rc;
+  PWG_REQUIRE(w && w_packed, PWG_ERR_NULL, "convtr1d_split_pack_weight: NULL pointer");
+  mfma_conv_pack<PARTS>(d, g, w, scale, w_packed, (hipStream_t)stream);
+  PWG_CHECK_LAUNCH("convtr1d_split_pack_weight");
+  return PWG_OK;
+}
+
+extern "C" int pwg_convtr1d_split_forward(const pwg_conv1d_desc* d, const float* x, const void* w_packed, const float* bias,
+                                          const float* add1, const float* add2, float* y, float* workspace,
+                                          size_t workspace_floats, void* stream) {
+  (void)workspace;  // no split reduction: one workgroup owns an output tile
+  (void)workspace_floats;
+  return convtr_forward(d, x, w_packed, bias, add1, add2, y, kDefaultMfmaShape, 0, (hipStream_t)stream);
+}
+
+extern "C" int pwg_convtr1d_split_forward_cfg(const pwg_conv1d_desc* d, const float* x, const void* w_packed,
+                                              const float* bias, const float* add1, const float* add2, float* y,
+                                              int32_t mfma_shape, int32_t tile_mode, void* stream) {
+  return convtr_forward(d, x, w_packed, bias, add1, add2, y, mfma_shape, tile_mode, (hipStream_t)stream);
 }

@@ -106,7 +106,7 @@ class PreparedWeights:
     keeps one instance per parameter epoch, so every forward / backward of that epoch -- e.g. D(y) and
     D(G(c)) of a discriminator phase -- shares a single scale + pack + pack launch sequence."""
 
-    __slots__ = ("key", "w", "_scale", "_fwd", "_fwd_desc", "_bwd", "_res", "_bf16", "_split", "_stale")
+    __slots__ = ("key", "w", "_scale", "_fwd", "_fwd_desc", "_bwd", "_res", "_bf16", "_split", "_split_tr", "_stale")
 
     def __init__(self, key, w, scale, fwd=None, fwd_desc=None, bwd=None):
         """``fwd``: the packed forward image, or None with ``fwd_desc`` (any descriptor of the layer) to build it
@@ -115,6 +115,7 @@ class PreparedWeights:
         self.key, self.w, self._scale, self._fwd, self._fwd_desc, self._bwd, self._res = key, w, scale, fwd, fwd_desc, bwd, None
         self._bf16 = None
         self._split = None
+        self._split_tr = None
         self._stale = False  # set by weight_bank.WeightBank when it overwrites the (shared, persistent) images
 
     @property
@@ -154,6 +155,10 @@ class PreparedWeights:
     def split(self):
         """The three bf16 images of the split-operand fp32 inference kernel (csrc/conv1d_split.hip)."""
         return self._image("_split", ops.pack_weight_split, self._fwd_desc)
+
+    def split_transposed(self):
+        """The three bf16 images of the split-operand transposed kernel (``convtr1d_split_mfma_kernel``)."""
+        return self._image("_split_tr", ops.pack_weight_split_transposed, self._fwd_desc)
 
     def bwd(self, desc):
         return self._image("_bwd", ops.pack_weight_bwd, desc)

@@ -239,6 +239,17 @@ class _ConvNd(torch.nn.Module):
         return split_admitted(desc.c_in, desc.c_out, desc.kernel, desc.batch * desc.t_out, needs_grad,
                               self.split_exact, self.split_admit_all) and ops.conv1d_split_supported(desc)
 
+    def packed_weight_split_transposed(self):
+        """Cached split-operand images of a k = 2s transposed layer, held by the same ``prepared()``."""
+        return self._packed(ops.pack_weight_split_transposed, lambda pw: pw.split_transposed())
+
+    def _upsample_split_route(self, desc, needs_grad=False):
+        """Does this no-grad call (``desc``) of an fp32 transposed module run on the split-operand transposed kernel?"""
+        return (self.transposed
+                and upsample_split_admitted(desc.c_in, desc.c_out, desc.kernel, desc.stride, desc.batch * desc.t_out,
+                                            needs_grad, self.split_exact, self.split_admit_all)
+                and ops.convtr1d_split_supported(desc))
+
     def bf16_capable(self):
         """Does the bf16-operand kernel cover this layer's geometry (host logic, no device needed)?"""
         return not self.width_mode and ops.conv1d_bf16_supported(self.make_desc(1, self._probe_len()))
@@ -354,6 +365,9 @@ class _ConvNd(torch.nn.Module):
             if self.precision == "fp32" and self._split_route(desc):
                 return ops.conv1d_forward_split(desc, x.contiguous(), self.packed_weight_split(),
                                                 None if self.bias is None else self.bias.detach(), add1, add2)
+            if self.precision == "fp32" and self._upsample_split_route(desc):
+                return ops.conv1d_forward_split_transposed(desc, x.contiguous(), self.packed_weight_split_transposed(),
+                                                           None if self.bias is None else self.bias.detach(), add1, add2)
             return ops.conv1d_forward(desc, x.contiguous(), self.packed_weight(),
                                       None if self.bias is None else self.bias.detach(), add1, add2)
 
@@ -387,6 +401,39 @@ def split_admitted(c_in, c_out, kernel, cols, needs_grad, enabled=True, admit_al
         return True
     min_cols = SPLIT_ADMITTED.get((c_in, c_out, kernel))
     return min_cols is not None and cols >= min_cols
+
+
+# Admission table of the split-operand transposed kernel (convtr1d_split_mfma_kernel; DESIGN.md s9.3,
+# profiles/convtr_split.txt): (c_in, c_out, stride) of a ConvTranspose1d with kernel == 2 * stride -> fewest output
+# columns per launch (batch x t_out).  The rule is that of the two tables around it: a class is listed when every run of
+# the new kernel was faster than every run of the fp32 kernel and the median gain at 16 x 800 frames was >= 1.25 x; its
+# column count is the shortest measured launch (16 x 800, 1 x 800, 1 x 100 frames) on which it still won disjointly,
+# and never under UPSAMPLE_SPLIT_MIN_COLS, the shortest launch measured at all.  Classes not listed, and shorter
+# launches, stay on the fp32 kernel.
+# 16 x 800 frames: 1.77 x (512 -> 256), 2.28 x (256 -> 128), 1.93 x (128 -> 64), 1.94 x (64 -> 32), all disjoint.  One
+# utterance of 800 frames: 512 -> 256 ties (0.99 x at 6400 columns) and loses at 100 frames (0.62 x), so it is admitted
+# from the 16-utterance launch only; the other three still win disjointly at one utterance of 100 frames (1.17 x,
+# 2.21 x, 1.73 x), the shortest launch measured.
+UPSAMPLE_SPLIT_MIN_COLS = 800
+UPSAMPLE_SPLIT_ADMITTED = {
+    (512, 256, 8): 102400,
+    (256, 128, 8): 6400,
+    (128, 64, 2): 12800,
+    (64, 32, 2): 25600,
+}
+
+
+def upsample_split_admitted(c_in, c_out, kernel, stride, cols, needs_grad, enabled=True, admit_all=False):
+    """The admission predicate of the split-operand transposed kernel (pure host logic), the sibling of
+    :func:`split_admitted`: never when a gradient is needed or the switch is off; else every k = 2s class
+    (``admit_all``) or the classes of ``UPSAMPLE_SPLIT_ADMITTED`` from their column count on.  What the kernel itself
+    covers is ``ops.convtr1d_split_supported``'s to say."""
+    if needs_grad or not enabled or kernel != 2 * stride:
+        return False
+    if admit_all:
+        return True
+    min_cols = UPSAMPLE_SPLIT_ADMITTED.get((c_in, c_out, stride))
+    return min_cols is not None and cols >= max(min_cols, UPSAMPLE_SPLIT_MIN_COLS)
 
 
 # Admission table of the split-operand residual units (DESIGN.md s9.2; profiles/resunit_split.txt):

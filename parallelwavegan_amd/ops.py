@@ -222,22 +222,23 @@ def _zero_padded(desc):
     return desc
 
 
-def _pack_weight_mfma(kind, desc, w, scale):
-    """The packer of the ``kind`` ("bf16" / "split") MFMA kernel: one image layout, csrc/mfma_conv.h."""
+def _pack_weight_mfma(kind, desc, w, scale, op="conv1d"):
+    """The packer of the ``kind`` ("bf16" / "split") MFMA kernel: one image layout, csrc/mfma_conv.h.  ``op``: the
+    entry-point family, "conv1d" or "convtr1d" (the split-operand transposed convolution)."""
     _require_device(w, scale)
-    n = getattr(_lib.lib(), f"pwg_conv1d_{kind}_packed_weight_bytes")(ctypes.byref(desc))
+    n = getattr(_lib.lib(), f"pwg_{op}_{kind}_packed_weight_bytes")(ctypes.byref(desc))
     if n == 0:
-        _lib.check(-1, f"conv1d_{kind}_packed_weight_bytes")
+        _lib.check(-1, f"{op}_{kind}_packed_weight_bytes")
     out = torch.empty(n, device=w.device, dtype=torch.uint8)
-    pack = getattr(_lib.lib(), f"pwg_conv1d_{kind}_pack_weight")
-    _lib.check(pack(ctypes.byref(desc), _ptr(w), _ptr(scale), _ptr(out), _stream()), f"conv1d_{kind}_pack_weight")
+    pack = getattr(_lib.lib(), f"pwg_{op}_{kind}_pack_weight")
+    _lib.check(pack(ctypes.byref(desc), _ptr(w), _ptr(scale), _ptr(out), _stream()), f"{op}_{kind}_pack_weight")
     return out
 
 
-def _conv1d_forward_mfma(kind, desc, image_desc, x, w_packed, bias, add1, add2, out, cfg):
+def _conv1d_forward_mfma(kind, desc, image_desc, x, w_packed, bias, add1, add2, out, cfg, op="conv1d"):
     """The forward of the ``kind`` ("bf16" / "split") MFMA kernel.  ``image_desc``: the descriptor the image was packed
-    through; ``cfg``: the tuning integers of ``pwg_conv1d_<kind>_forward_cfg``, None for the default launch."""
-    name = f"conv1d_forward_{kind}"
+    through; ``cfg``: the tuning integers of ``pwg_<op>_<kind>_forward_cfg``, None for the default launch."""
+    name = f"{op}_forward_{kind}"
     _require_device(x, bias, add1, add2, out)
     if not w_packed.is_cuda or w_packed.dtype != torch.uint8:
         raise RuntimeError(f"{name}: w_packed must be the device image of pack_weight_{kind}")
@@ -245,17 +246,17 @@ def _conv1d_forward_mfma(kind, desc, image_desc, x, w_packed, bias, add1, add2, 
         out = torch.empty((desc.batch, desc.c_out, desc.t_out), device=x.device, dtype=torch.float32)
     assert x.numel() == desc.batch * desc.c_in * desc.t_in, (tuple(x.shape), desc.batch, desc.c_in, desc.t_in)
     assert out.numel() == desc.batch * desc.c_out * desc.t_out
-    image_bytes = getattr(_lib.lib(), f"pwg_conv1d_{kind}_packed_weight_bytes")(ctypes.byref(image_desc))
+    image_bytes = getattr(_lib.lib(), f"pwg_{op}_{kind}_packed_weight_bytes")(ctypes.byref(image_desc))
     if image_bytes == 0:  # the kernel refuses the descriptor: report its reason, not a mismatch
-        _lib.check(-1, f"conv1d_{kind}_packed_weight_bytes")
+        _lib.check(-1, f"{op}_{kind}_packed_weight_bytes")
     assert w_packed.numel() == image_bytes, f"{name}: w_packed is not this layer's {kind} image"
     for t in (add1, add2):
         assert t is None or t.numel() == out.numel()
     args = (ctypes.byref(desc), _ptr(x), _ptr(w_packed), _ptr(bias), _ptr(add1), _ptr(add2), _ptr(out))
     if cfg is None:
-        rc = getattr(_lib.lib(), f"pwg_conv1d_{kind}_forward")(*args, None, 0, _stream())
+        rc = getattr(_lib.lib(), f"pwg_{op}_{kind}_forward")(*args, None, 0, _stream())
     else:
-        rc = getattr(_lib.lib(), f"pwg_conv1d_{kind}_forward_cfg")(*args, *cfg, _stream())
+        rc = getattr(_lib.lib(), f"pwg_{op}_{kind}_forward_cfg")(*args, *cfg, _stream())
     _lib.check(rc, name)
     return out
 
@@ -293,6 +294,27 @@ def conv1d_forward_split(desc, x, w_packed, bias=None, add1=None, add2=None, out
     tiles instead of the small-grid rule."""
     cfg = None if mfma_shape is None and not tile_mode else (int(mfma_shape or 16), int(tile_mode))
     return _conv1d_forward_mfma("split", desc, desc, x, w_packed, bias, add1, add2, out, cfg)
+
+
+def convtr1d_split_supported(desc):
+    """Does the split-operand transposed convolution (csrc/conv1d_split.hip, ``convtr1d_split_mfma_kernel``) cover this
+    descriptor -- a ConvTranspose1d with kernel == 2 * stride?  Host logic only (no device needed);
+    ``_lib.lib().pwg_last_error()`` names the reason for a False."""
+    return bool(_lib.lib().pwg_convtr1d_split_supported(ctypes.byref(desc)))
+
+
+def pack_weight_split_transposed(desc, w, scale=None):
+    """torch-layout ConvTranspose1d weight (C_in, C_out, k) (+ optional weight_norm scale, per input channel) -> the
+    three bf16 images of the split-operand transposed kernel: three parts of the bf16 kernel's transposed image."""
+    return _pack_weight_mfma("split", desc, w, scale, op="convtr1d")
+
+
+def conv1d_forward_split_transposed(desc, x, w_packed, bias=None, add1=None, add2=None, out=None, mfma_shape=None,
+                                    tile_mode=0):
+    """:func:`conv1d_forward_split` for a ConvTranspose1d with kernel == 2 * stride (inference only; DESIGN.md s9.3);
+    ``mfma_shape`` / ``tile_mode`` as there."""
+    cfg = None if mfma_shape is None and not tile_mode else (int(mfma_shape or 16), int(tile_mode))
+    return _conv1d_forward_mfma("split", desc, desc, x, w_packed, bias, add1, add2, out, cfg, op="convtr1d")
 
 
 def conv1d_stream_supported(desc):
