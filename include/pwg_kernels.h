@@ -381,6 +381,36 @@ int pwg_conv1d_stream_bf16_delayed_forward(const pwg_conv1d_desc* d, const float
                                            float* add2_hist_out, int32_t delay2, int32_t valid_lo, int32_t valid_hi,
                                            float* y, void* stream);
 
+/* ---- the delayed stream launch with a position per item: the slotted form (csrc/conv1d_stream.hip, _bf16.hip) ----
+ * For a pool of streams whose utterances start and end independently (utils.StreamPool): the delayed
+ * launch, its scalar window replaced by the launch's `rate` (output columns per frame), the output's `delay` (columns)
+ * and `slots`, a DEVICE table of 4 int32 per item b (read by the kernel; 4-B aligned):
+ *   slots[4b + 0]  frames that went before this push (>= 0; the caller may saturate it once before * rate >= delay).
+ *                  0: the item is FRESH -- hist_in and both add_i_hist_in read as zeros for it, whatever they hold
+ *   slots[4b + 1]  frames of the utterance from this push's first frame on (negative past its end), if bit 1 below
+ *   slots[4b + 2]  bit 0: the item is PAUSED; bit 1: slots[4b + 1] is known
+ *   slots[4b + 3]  not read by the kernel: the caller's own
+ * A running item's valid window is [max(delay - before * rate, 0), delay + left * rate) clamped to [0, t_out] (the whole
+ * of [.., t_out) while `left` is unknown), formed in 64 bits; its y, hist_out and add_i_hist_out are bit for bit what
+ * the delayed entry writes for a batch-1 launch of this item with that window (hist_in NULL if fresh).
+ * A paused item takes no frames: its hist_out / add_i_hist_out are its hist_in / add_i_hist_in copied through (zeros if
+ * it is fresh), its y columns are stored as 0.0f, and its x and addend columns are not read.
+ * Every other parameter and pointer rule is the delayed entry's, except that hist_in (where the layer has history) and
+ * add_i_hist_in (where delay_i > 0) must be given: the start of a stream is an item's, not the launch's.  Coverage is
+ * that of pwg_conv1d_stream_delayed_supported / pwg_conv1d_stream_bf16_delayed_supported.
+ * These two symbols are purely additive -- no existing signature or behaviour changes -- so pwg_abi_version() stays 15. */
+int pwg_conv1d_stream_slots_forward(const pwg_conv1d_desc* d, const float* x, const float* hist_in, float* hist_out,
+                                    const float* w_packed, const float* bias, const float* add1,
+                                    const float* add1_hist_in, float* add1_hist_out, int32_t delay1, const float* add2,
+                                    const float* add2_hist_in, float* add2_hist_out, int32_t delay2, const int32_t* slots,
+                                    int32_t rate, int32_t delay, float* y, void* stream);
+int pwg_conv1d_stream_slots_forward_bf16(const pwg_conv1d_desc* d, const float* x, const float* hist_in, float* hist_out,
+                                         const void* w_packed_bf16, const float* bias, const float* add1,
+                                         const float* add1_hist_in, float* add1_hist_out, int32_t delay1,
+                                         const float* add2, const float* add2_hist_in, float* add2_hist_out,
+                                         int32_t delay2, const int32_t* slots, int32_t rate, int32_t delay, float* y,
+                                         void* stream);
+
 /* ---- the delayed stream launch of a REFLECT-padded layer: the mirrored form (fp32; csrc/conv1d_stream.hip) ----
  * For streaming the non-causal (multi-band) MelGAN with a fixed look-ahead.  Replaces, chunk by chunk, the
  * ReflectionPad1d + Conv1d pairs of the reference generator (models/melgan.py:70-73 the first k = 7 convolution,

@@ -165,6 +165,10 @@ SIGNATURES = {
     "pwg_conv1d_stream_bf16_delayed_supported": (ctypes.c_int, [ctypes.POINTER(ConvDesc), _i32, _i32]),
     "pwg_conv1d_stream_bf16_delayed_forward": (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                                               _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "pwg_conv1d_stream_slots_forward": (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                       _i32, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp]),
+    "pwg_conv1d_stream_slots_forward_bf16": (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                            _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp]),
     "pwg_conv1d_stream_mirrored_supported": (ctypes.c_int, [ctypes.POINTER(ConvDesc)]),
     "pwg_conv1d_stream_mirrored_forward": (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _i32,
                                                           _i32, _i32, _i32, _vp]),

@@ -39,6 +39,13 @@
 // the history, and output columns outside the utterance's valid window are stored as zeros (StreamDelay,
 // stream_common.h).  Operand pipeline, contraction and sum order are those of the plain form: only the history writer
 // and the epilogue differ, and the plain instantiations are the code they were.
+//
+// Slotted form (pwg_conv1d_stream_slots_forward): the delayed form with one position per item.  Item
+// b reads its row of a device table (StreamSlots, stream_common.h): how many frames went before and how many remain give
+// its valid window by the window rule; a fresh item (nothing went before) reads history and delay lines as zeros whatever
+// the buffers hold; a paused item copies its state through, stores zeros for y and returns in front of every barrier.
+// A running item's columns are the delayed form's with the same window, bit for bit: one launch serves items at
+// different points of different utterances, and one captured graph covers start, steady state and tail.
 #include "stream_common.h"
 
 namespace pwg {
@@ -153,13 +160,22 @@ struct StreamMirroredArgs : StreamDelayedArgs {
   int in_lo, in_hi;  // the input's valid window, saturated (mirror_bound)
 };
 
-template <bool DELAYED, bool MIRRORED>
-using stream_args_t =
-    std::conditional_t<MIRRORED, StreamMirroredArgs, std::conditional_t<DELAYED, StreamDelayedArgs, StreamArgs>>;
+// SLOTTED (with DELAYED): the item's position comes from the launch's table (StreamSlots); a running item is from there
+// on the delayed form with its own window, a fresh one reads no state, a paused one copies its state through, stores
+// zeros and returns.
+struct StreamSlotsArgs : StreamArgs {
+  StreamSlots sl;
+};
 
-template <int TM, int TN, bool TRANSPOSED, bool DELAYED = false, bool MIRRORED = false>
-__global__ __launch_bounds__(256) void conv1d_stream_kernel(stream_args_t<DELAYED, MIRRORED> a) {
+template <bool DELAYED, bool MIRRORED, bool SLOTTED>
+using stream_args_t = std::conditional_t<
+    SLOTTED, StreamSlotsArgs,
+    std::conditional_t<MIRRORED, StreamMirroredArgs, std::conditional_t<DELAYED, StreamDelayedArgs, StreamArgs>>>;
+
+template <int TM, int TN, bool TRANSPOSED, bool DELAYED = false, bool MIRRORED = false, bool SLOTTED = false>
+__global__ __launch_bounds__(256) void conv1d_stream_kernel(stream_args_t<DELAYED, MIRRORED, SLOTTED> a) {
   static_assert(!MIRRORED || (DELAYED && !TRANSPOSED), "the mirrored form is a delayed stride-1 convolution");
+  static_assert(!SLOTTED || (DELAYED && !MIRRORED), "the slotted form is a delayed launch with a position per item");
   constexpr int MT = 16 * TM, NT = 16 * TN;
   extern __shared__ __attribute__((aligned(16))) float xs[];  // [SC][a.xs]; afterwards the partial tiles [4][MT][NT]
 
@@ -169,24 +185,33 @@ __global__ __launch_bounds__(256) void conv1d_stream_kernel(stream_args_t<DELAYE
   const int q0 = blockIdx.x * NT, m0 = blockIdx.y * MT, b = blockIdx.z;
   const int H = a.hist, n = a.ep.n, XS = a.xs;
   const int W = NT + H;  // window column w holds stream column q0 - H + w (chunk-relative; < 0: history)
+  const int wg = blockIdx.y * gridDim.x + blockIdx.x, nwg = gridDim.x * gridDim.y;
   const float* __restrict__ xb = a.x + (size_t)b * a.c_in * n;
-  const float* __restrict__ hb = a.hist_in ? a.hist_in + (size_t)b * a.c_in * H : nullptr;
 
-  stream_write_history<1>(xb, hb, a.hist_out + (size_t)b * a.c_in * H, a.c_in, n, H, a.pad_mode == PWG_PAD_REPLICATE,
-                       blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
-  if constexpr (DELAYED) {
-    // the addends' delay lines: the history rule on (c_out, t_out) rows, zero start
-    const float* adds[2] = {a.ep.add1, a.ep.add2};
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int D = a.dl.delay[i];
-      if (D == 0) continue;
-      const size_t rows = (size_t)b * a.ep.c_out;
-      stream_write_history<1>(adds[i] + rows * a.ep.t_out, a.dl.hist_in[i] ? a.dl.hist_in[i] + rows * D : nullptr,
-                              a.dl.hist_out[i] + rows * D, a.ep.c_out, a.ep.t_out, D, false,
-                              blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
+  // SLOTTED: what this item's table row resolves to -- fresh, paused and its own window (a.sl.delayed(item) stands
+  // where a.dl does)
+  [[maybe_unused]] std::conditional_t<SLOTTED, StreamSlots::Item, StreamNoDelay> item;
+  bool fresh = false;
+  if constexpr (SLOTTED) {
+    item = a.sl.at(b, a.ep.t_out);
+    fresh = item.fresh;
+  }
+  const float* __restrict__ hb = a.hist_in && !fresh ? a.hist_in + (size_t)b * a.c_in * H : nullptr;
+
+  if constexpr (SLOTTED) {
+    if (item.paused) {  // (workgroup-uniform) the history rule with n = 0, zeros for y; in front of every barrier
+      stream_write_history<1>(xb, hb, a.hist_out + (size_t)b * a.c_in * H, a.c_in, 0, H, false, wg, nwg);
+      stream_write_lines(a.sl.delayed(item), a.ep, b, 0, wg, nwg);
+      stream_store_zeros<MT, NT, TRANSPOSED, StreamRows::PhaseMajor>(a.ep, m0, q0, b);
+      return;
     }
   }
+  stream_write_history<1>(xb, hb, a.hist_out + (size_t)b * a.c_in * H, a.c_in, n, H, a.pad_mode == PWG_PAD_REPLICATE, wg,
+                          nwg);
+  if constexpr (SLOTTED)
+    stream_write_lines(a.sl.delayed(item), a.ep, b, a.ep.t_out, wg, nwg);
+  else if constexpr (DELAYED)
+    stream_write_lines(a.dl, a.ep, b, a.ep.t_out, wg, nwg);
 
   f32x4 acc[TM][TN];
 #pragma unroll
@@ -302,7 +327,9 @@ __global__ __launch_bounds__(256) void conv1d_stream_kernel(stream_args_t<DELAYE
     }
   }
 
-  if constexpr (DELAYED)
+  if constexpr (SLOTTED)
+    stream_reduce_epilogue<MT, NT, TRANSPOSED, StreamRows::PhaseMajor>(xs, acc, a.ep, m0, q0, b, a.sl.delayed(item));
+  else if constexpr (DELAYED)
     stream_reduce_epilogue<MT, NT, TRANSPOSED, StreamRows::PhaseMajor>(xs, acc, a.ep, m0, q0, b, a.dl);
   else
     stream_reduce_epilogue<MT, NT, TRANSPOSED, StreamRows::PhaseMajor>(xs, acc, a.ep, m0, q0, b);
@@ -316,6 +343,11 @@ struct Kernel {
 template <int TM, int TN, bool TRANSPOSED>
 struct DelayedKernel {
   static constexpr auto fn = conv1d_stream_kernel<TM, TN, TRANSPOSED, true>;
+};
+
+template <int TM, int TN, bool TRANSPOSED>
+struct SlotsKernel {
+  static constexpr auto fn = conv1d_stream_kernel<TM, TN, TRANSPOSED, true, false, true>;
 };
 
 // (mirrored_geometry() admits no transposed layer: that slot of stream_launch names the same kernel, never launched)
@@ -390,6 +422,30 @@ extern "C" int pwg_conv1d_stream_delayed_forward(const pwg_conv1d_desc* d, const
   return stream_run<DelayedKernel>("conv1d_stream_delayed", "conv1d_stream_delayed_kernel", d, g, tile, &a, x, hist_in,
                                    hist_out, w_packed, bias, add1, add2, y, window,
                                    (double)d->batch * d->c_out * (delay1 + delay2), image_bytes(g), (hipStream_t)stream_);
+}
+
+extern "C" int pwg_conv1d_stream_slots_forward(const pwg_conv1d_desc* d, const float* x, const float* hist_in,
+                                               float* hist_out, const float* w_packed, const float* bias,
+                                               const float* add1, const float* add1_hist_in, float* add1_hist_out,
+                                               int32_t delay1, const float* add2, const float* add2_hist_in,
+                                               float* add2_hist_out, int32_t delay2, const int32_t* slots, int32_t rate,
+                                               int32_t delay, float* y, void* stream_) {
+  StreamGeom g;
+  int rc = delayed_geometry(d, delay1, delay2, &g);
+  if (rc != PWG_OK) return rc;
+  PWG_REQUIRE((reinterpret_cast<uintptr_t>(w_packed) & 3u) == 0, PWG_ERR_BAD_SHAPE,
+              "conv1d_stream_slots: unaligned weight image");
+  PWG_REQUIRE(hist_in || g.hist == 0, PWG_ERR_NULL,
+              "conv1d_stream_slots: hist_in is NULL (the start of a stream is an item's, in the table)");
+  StreamSlotsArgs a;
+  rc = stream_slot_lines("conv1d_stream_slots", add1, add1_hist_in, add1_hist_out, delay1, add2, add2_hist_in,
+                         add2_hist_out, delay2, slots, rate, delay, &a.sl);
+  if (rc != PWG_OK) return rc;
+  const StreamTile tile = stream_tile(d->t_in, g.m, d->batch);
+  const size_t window = fill_image_args(&a, w_packed, g, tile);
+  return stream_run<SlotsKernel>("conv1d_stream_slots", "conv1d_stream_slots_kernel", d, g, tile, &a, x, hist_in, hist_out,
+                                 w_packed, bias, add1, add2, y, window,
+                                 (double)d->batch * d->c_out * (delay1 + delay2), image_bytes(g), (hipStream_t)stream_);
 }
 
 extern "C" int pwg_conv1d_stream_mirrored_supported(const pwg_conv1d_desc* d) {

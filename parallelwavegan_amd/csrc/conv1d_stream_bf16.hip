@@ -41,6 +41,10 @@
 // the next layer sees the whole-utterance zero padding.  Staging, item dealing, A-fragment prefetch, contraction and
 // sum order are those of the plain form: only the history writer and the epilogue differ, and the plain instantiations
 // are the code they were.
+//
+// Slotted form (pwg_conv1d_stream_slots_forward_bf16): the slotted form of conv1d_stream.hip under
+// the numerical definition above -- a position per item from a device table, fresh and paused items, and a running
+// item's columns bit for bit the delayed form's with the same window.
 #include "mfma_conv.h"
 #include "stream_common.h"
 
@@ -62,6 +66,10 @@ struct StreamBf16DelayedArgs : StreamBf16Args {
   StreamDelay dl;
 };
 
+struct StreamBf16SlotsArgs : StreamBf16Args {
+  StreamSlots sl;
+};
+
 // (chunk of the staged block, tap) of an item; wave-uniform
 struct Item {
   int cl, tap;
@@ -69,9 +77,11 @@ struct Item {
 
 // One workgroup (4 waves) owns MT = 16 * TM rows x NT = 16 * TN columns; wave w contracts the items with item % 4 == w
 // and the four partial tiles are summed through LDS in wave order, ((p0 + p1) + p2) + p3 -- the same in every configuration.
-template <int TM, int TN, bool TRANSPOSED, bool DELAYED = false>
+// SLOTTED (with DELAYED): as in conv1d_stream.hip -- the item's position comes from the launch's table (StreamSlots).
+template <int TM, int TN, bool TRANSPOSED, bool DELAYED = false, bool SLOTTED = false>
 __global__ __launch_bounds__(256) void conv1d_stream_bf16_kernel(
-    std::conditional_t<DELAYED, StreamBf16DelayedArgs, StreamBf16Args> a) {
+    std::conditional_t<SLOTTED, StreamBf16SlotsArgs, std::conditional_t<DELAYED, StreamBf16DelayedArgs, StreamBf16Args>> a) {
+  static_assert(!SLOTTED || DELAYED, "the slotted form is a delayed launch with a position per item");
   constexpr int MT = 16 * TM, NT = 16 * TN;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __bf16* xs = reinterpret_cast<__bf16*>(smem);  // [W][ROW]; afterwards the partial tiles [4][MT][NT + 1] fp32
@@ -82,24 +92,33 @@ __global__ __launch_bounds__(256) void conv1d_stream_bf16_kernel(
   const int q0 = blockIdx.x * NT, m0 = blockIdx.y * MT, b = blockIdx.z;
   const int H = a.hist, n = a.ep.n;
   const int W = NT + H;  // window column w holds stream column q0 - H + w (chunk-relative; < 0: history)
+  const int wg = blockIdx.y * gridDim.x + blockIdx.x, nwg = gridDim.x * gridDim.y;
   const float* __restrict__ xb = a.x + (size_t)b * a.c_in * n;
-  const float* __restrict__ hb = a.hist_in ? a.hist_in + (size_t)b * a.c_in * H : nullptr;
 
-  stream_write_history<1>(xb, hb, a.hist_out + (size_t)b * a.c_in * H, a.c_in, n, H, a.pad_mode == PWG_PAD_REPLICATE,
-                       blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
-  if constexpr (DELAYED) {
-    // the addends' delay lines: the history rule on (c_out, t_out) rows, zero start
-    const float* adds[2] = {a.ep.add1, a.ep.add2};
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int D = a.dl.delay[i];
-      if (D == 0) continue;
-      const size_t rows = (size_t)b * a.ep.c_out;
-      stream_write_history<1>(adds[i] + rows * a.ep.t_out, a.dl.hist_in[i] ? a.dl.hist_in[i] + rows * D : nullptr,
-                              a.dl.hist_out[i] + rows * D, a.ep.c_out, a.ep.t_out, D, false,
-                              blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
+  // SLOTTED: what this item's table row resolves to -- fresh, paused and its own window (a.sl.delayed(item) stands
+  // where a.dl does)
+  [[maybe_unused]] std::conditional_t<SLOTTED, StreamSlots::Item, StreamNoDelay> item;
+  bool fresh = false;
+  if constexpr (SLOTTED) {
+    item = a.sl.at(b, a.ep.t_out);
+    fresh = item.fresh;
+  }
+  const float* __restrict__ hb = a.hist_in && !fresh ? a.hist_in + (size_t)b * a.c_in * H : nullptr;
+
+  if constexpr (SLOTTED) {
+    if (item.paused) {  // (workgroup-uniform) the history rule with n = 0, zeros for y; in front of every barrier
+      stream_write_history<1>(xb, hb, a.hist_out + (size_t)b * a.c_in * H, a.c_in, 0, H, false, wg, nwg);
+      stream_write_lines(a.sl.delayed(item), a.ep, b, 0, wg, nwg);
+      stream_store_zeros<MT, NT, TRANSPOSED, StreamRows::ChannelMajor>(a.ep, m0, q0, b);
+      return;
     }
   }
+  stream_write_history<1>(xb, hb, a.hist_out + (size_t)b * a.c_in * H, a.c_in, n, H, a.pad_mode == PWG_PAD_REPLICATE, wg,
+                          nwg);
+  if constexpr (SLOTTED)
+    stream_write_lines(a.sl.delayed(item), a.ep, b, a.ep.t_out, wg, nwg);
+  else if constexpr (DELAYED)
+    stream_write_lines(a.dl, a.ep, b, a.ep.t_out, wg, nwg);
 
   f32x4 acc[TM][TN];
 #pragma unroll
@@ -233,7 +252,10 @@ __global__ __launch_bounds__(256) void conv1d_stream_bf16_kernel(
     }
   }
 
-  if constexpr (DELAYED)
+  if constexpr (SLOTTED)
+    stream_reduce_epilogue<MT, NT, TRANSPOSED, StreamRows::ChannelMajor>(reinterpret_cast<float*>(smem), acc, a.ep, m0, q0, b,
+                                                                         a.sl.delayed(item));
+  else if constexpr (DELAYED)
     stream_reduce_epilogue<MT, NT, TRANSPOSED, StreamRows::ChannelMajor>(reinterpret_cast<float*>(smem), acc, a.ep, m0, q0, b,
                                                                          a.dl);
   else
@@ -248,6 +270,11 @@ struct Kernel {
 template <int TM, int TN, bool TRANSPOSED>
 struct DelayedKernel {
   static constexpr auto fn = conv1d_stream_bf16_kernel<TM, TN, TRANSPOSED, true>;
+};
+
+template <int TM, int TN, bool TRANSPOSED>
+struct SlotsKernel {
+  static constexpr auto fn = conv1d_stream_bf16_kernel<TM, TN, TRANSPOSED, true, true>;
 };
 
 // The image of the layer (csrc/mfma_conv.h) and the fields of the argument struct that come from it.  The image does
@@ -328,4 +355,33 @@ extern "C" int pwg_conv1d_stream_bf16_delayed_forward(const pwg_conv1d_desc* d, 
                                    hist_in, hist_out, w_packed_bf16, bias, add1, add2, y, window_bytes(g, tile),
                                    (double)d->batch * d->c_out * (delay1 + delay2), 2.0 * (double)image_elems(image),
                                    (hipStream_t)stream_);
+}
+
+// The slotted form (conv1d_stream.hip) under the numerical definition above; coverage is that of the delayed forms.
+extern "C" int pwg_conv1d_stream_slots_forward_bf16(const pwg_conv1d_desc* d, const float* x, const float* hist_in,
+                                                    float* hist_out, const void* w_packed_bf16, const float* bias,
+                                                    const float* add1, const float* add1_hist_in, float* add1_hist_out,
+                                                    int32_t delay1, const float* add2, const float* add2_hist_in,
+                                                    float* add2_hist_out, int32_t delay2, const int32_t* slots,
+                                                    int32_t rate, int32_t delay, float* y, void* stream_) {
+  StreamGeom g;
+  int rc = delayed_geometry(d, delay1, delay2, &g);
+  if (rc != PWG_OK) return rc;
+  MfmaConvGeom image;
+  rc = bf16_image("conv1d_stream_slots_bf16", d, &image);
+  if (rc != PWG_OK) return rc;
+  PWG_REQUIRE((reinterpret_cast<uintptr_t>(w_packed_bf16) & 15u) == 0, PWG_ERR_BAD_SHAPE,
+              "conv1d_stream_slots_bf16: the weight image must be 16-B aligned");
+  PWG_REQUIRE(hist_in || g.hist == 0, PWG_ERR_NULL,
+              "conv1d_stream_slots_bf16: hist_in is NULL (the start of a stream is an item's, in the table)");
+  StreamBf16SlotsArgs a;
+  rc = stream_slot_lines("conv1d_stream_slots_bf16", add1, add1_hist_in, add1_hist_out, delay1, add2, add2_hist_in,
+                         add2_hist_out, delay2, slots, rate, delay, &a.sl);
+  if (rc != PWG_OK) return rc;
+  const StreamTile tile = stream_tile(d->t_in, g.m, d->batch);
+  fill_image_args(&a, w_packed_bf16, image, g);
+  return stream_run<SlotsKernel>("conv1d_stream_slots_bf16", "conv1d_stream_bf16_slots_kernel", d, g, tile, &a, x, hist_in,
+                                 hist_out, w_packed_bf16, bias, add1, add2, y, window_bytes(g, tile),
+                                 (double)d->batch * d->c_out * (delay1 + delay2), 2.0 * (double)image_elems(image),
+                                 (hipStream_t)stream_);
 }

@@ -4,6 +4,8 @@
 //   start-of-stream rule  StreamWindow::at       which source window column t comes from (history, chunk, padding)
 //   sum order, epilogue   stream_reduce_epilogue ((p0 + p1) + p2) + p3, then the fp32 epilogue
 //   delayed form          StreamDelay            addends read through a delay line, zeros stored outside a valid window
+//   window rule           stream_slot_window     the valid columns of a launch from a push-relative position
+//   slotted form          StreamSlots            the delayed form with one position per item, read from a device table
 //   mirror rule           StreamMirrorWindow::at the reflect-padded layer of a look-ahead stream: mirror, then resolve
 //   tile rule             stream_tile            column tile from n; 32-row blocks only at 2 x 256 or more workgroups
 //   coverage              stream_geometry        defined in conv1d_stream.hip; both precisions admit the same layers
@@ -118,13 +120,76 @@ struct StreamEpilogue {
 // last delay[i] columns of that concatenation, written by the history rule above.  Output columns outside
 // [valid_lo, valid_hi) are STORED as 0.0f: the next layer then sees the whole-utterance zero padding there.  The value
 // of a valid column is formed by the same operations in the same order as without a delay.
-struct StreamDelay {
+struct StreamLines {
   const float* hist_in[2];  // (B, c_out, delay[i]) or NULL
   float* hist_out[2];       // (B, c_out, delay[i]); NULL where delay[i] == 0
   int delay[2];
+};
+struct StreamDelay : StreamLines {
   int valid_lo, valid_hi;   // output columns (chunk-relative, of t_out)
 };
 struct StreamNoDelay {};
+
+// ---- window rule (layers.causal_conv.lookahead_window, stated for a position that is relative to the push): a launch
+// whose output is `delay` columns late at `rate` columns per frame, on a push of t_out columns that `before` frames
+// went before; `left` = frames of the utterance from this push's first frame on (negative once the stream is past its
+// end), if `left_known`.  The valid columns are [max(delay - before * rate, 0), delay + left * rate), clamped to
+// [0, t_out].  64-bit throughout: no position overflows, however long the stream.
+struct StreamValid {
+  int lo, hi;
+};
+__host__ __device__ static inline StreamValid stream_slot_window(int delay, int rate, int t_out, int before, int left,
+                                                                 bool left_known) {
+  const long long lo = (long long)delay - (long long)before * rate;
+  const long long hi = left_known ? (long long)delay + (long long)left * rate : (long long)t_out;
+  StreamValid v;
+  v.lo = (int)(lo < 0 ? 0 : (lo > t_out ? t_out : lo));
+  v.hi = (int)(hi < 0 ? 0 : (hi > t_out ? t_out : hi));
+  return v;
+}
+
+// ---- the slotted form of the delayed epilogue (utils.StreamPool): every item of the batch sits at
+// its own point of its own utterance.  The launch carries the delay lines, its `rate` and output `delay`, and a device
+// table with one row of kStreamSlotInts int32 per item b = blockIdx.z:
+//   row[0]  frames that went before this push (the host saturates it once it is past every delay of the plan);
+//           0: the item is FRESH -- history and both delay lines read as zeros whatever the buffers hold
+//   row[1]  frames of the utterance from this push's first frame on, if row[2] says it is known
+//   row[2]  kStreamSlotPaused: the item takes no frames in this launch; kStreamSlotLeftKnown: row[1] holds
+//   row[3]  not read by the kernel: the host's own (utils.StreamPool keeps the push's count of real frames there)
+// at(b) resolves the row, delayed(item) gives the item's StreamDelay: a running item IS a delayed launch with its window.
+constexpr int kStreamSlotInts = 4;
+constexpr int kStreamSlotPaused = 1, kStreamSlotLeftKnown = 2;
+struct StreamSlots : StreamLines {
+  const int32_t* slots;  // (B, kStreamSlotInts)
+  int rate, out_delay;
+
+  // What a kernel keeps of its item's row across its main loop: four scalars
+  struct Item {
+    int valid_lo, valid_hi;
+    bool fresh, paused;
+  };
+  __device__ __forceinline__ Item at(int b, int t_out) const {
+    const int32_t* __restrict__ row = slots + (size_t)b * kStreamSlotInts;
+    const int before = __builtin_amdgcn_readfirstlane(row[0]), left = __builtin_amdgcn_readfirstlane(row[1]);
+    const int flags = __builtin_amdgcn_readfirstlane(row[2]);
+    const StreamValid v = stream_slot_window(out_delay, rate, t_out, before, left, (flags & kStreamSlotLeftKnown) != 0);
+    return Item{v.lo, v.hi, before == 0, (flags & kStreamSlotPaused) != 0};
+  }
+  // The item's delayed form, built where it is used (the launch's fields come from the kernel arguments again): the
+  // launch's lines -- their inputs NULL for a fresh item -- and the item's window
+  __device__ __forceinline__ StreamDelay delayed(const Item& it) const {
+    StreamDelay dl;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      dl.hist_in[i] = it.fresh ? nullptr : hist_in[i];
+      dl.hist_out[i] = hist_out[i];
+      dl.delay[i] = delay[i];
+    }
+    dl.valid_lo = it.valid_lo;
+    dl.valid_hi = it.valid_hi;
+    return dl;
+  }
+};
 
 __device__ __forceinline__ float stream_delayed_addend(const float* __restrict__ add, const float* __restrict__ hist,
                                                        int delay, size_t row, int t_out, int j) {
@@ -161,6 +226,7 @@ __device__ __forceinline__ void stream_reduce_epilogue(float* red, const f32x4 (
     const int row = e / NT, col = e - row * NT;
     const int m = m0 + row, j = q0 + col;
     if (m >= a.m || j >= a.n) continue;
+    // (stream_store_zeros below walks the same elements to the same addresses)
     float v = red[row * RS + col];
     v += red[(MT + row) * RS + col];
     v += red[(2 * MT + row) * RS + col];
@@ -195,6 +261,43 @@ __device__ __forceinline__ void stream_reduce_epilogue(float* red, const f32x4 (
     if (a.out_div != 1.0f) v = v / a.out_div;
     v = apply_act(v, a.post_act, a.post_slope);
     a.y[o] = v;
+  }
+}
+
+// The addends' delay lines of one item: the history rule on (c_out, t_out) rows, zero start.  `t_out`: the output columns
+// this launch gives the item -- 0 for a paused one, whose lines are then copied through (zeros if it is fresh).
+__device__ __forceinline__ void stream_write_lines(const StreamLines& dl, const StreamEpilogue& a, int b, int t_out,
+                                                   int wg, int nwg) {
+  const float* adds[2] = {a.add1, a.add2};
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int D = dl.delay[i];
+    if (D == 0) continue;
+    const size_t rows = (size_t)b * a.c_out;
+    stream_write_history<1>(adds[i] + rows * a.t_out, dl.hist_in[i] ? dl.hist_in[i] + rows * D : nullptr,
+                            dl.hist_out[i] + rows * D, a.c_out, t_out, D, false, wg, nwg);
+  }
+}
+
+// What a paused item of a slotted launch stores for its output tile: exact zeros, at the elements and addresses of
+// stream_reduce_epilogue.  No LDS, no barrier.
+template <int MT, int NT, bool TRANSPOSED, StreamRows ROWS>
+__device__ __forceinline__ void stream_store_zeros(const StreamEpilogue& a, int m0, int q0, int b) {
+  for (int e = threadIdx.x; e < MT * NT; e += 256) {
+    const int row = e / NT, col = e - row * NT;
+    const int m = m0 + row, j = q0 + col;
+    if (m >= a.m || j >= a.n) continue;
+    int co = m, ph = 0;
+    if (TRANSPOSED) {
+      if (ROWS == StreamRows::PhaseMajor) {
+        ph = m / a.c_out;
+        co = m - ph * a.c_out;
+      } else {
+        co = m / a.phases;
+        ph = m - co * a.phases;
+      }
+    }
+    a.y[((size_t)b * a.c_out + co) * a.t_out + (TRANSPOSED ? j * a.phases + ph : j)] = 0.f;
   }
 }
 
@@ -270,9 +373,9 @@ static inline int stream_check_pointers(const char* name, const pwg_conv1d_desc*
 
 // The delay lines of a delayed launch: a delayed addend needs its tensor and a hist_out distinct from its hist_in;
 // the pointers of an addend that is not delayed are ignored
-static inline int stream_delay_lines(const char* name, const float* add1, const float* add1_hist_in, float* add1_hist_out,
-                                     int delay1, const float* add2, const float* add2_hist_in, float* add2_hist_out,
-                                     int delay2, int valid_lo, int valid_hi, StreamDelay* dl) {
+static inline int stream_lines(const char* name, const float* add1, const float* add1_hist_in, float* add1_hist_out,
+                               int delay1, const float* add2, const float* add2_hist_in, float* add2_hist_out,
+                               int delay2, StreamLines* dl) {
   const float* adds[2] = {add1, add2};
   const float* hin[2] = {add1_hist_in, add2_hist_in};
   float* hout[2] = {add1_hist_out, add2_hist_out};
@@ -288,9 +391,33 @@ static inline int stream_delay_lines(const char* name, const float* add1, const 
     dl->hist_out[i] = delays[i] ? hout[i] : nullptr;
     dl->delay[i] = delays[i];
   }
+  return PWG_OK;
+}
+
+// ... of a delayed launch, with its valid window
+static inline int stream_delay_lines(const char* name, const float* add1, const float* add1_hist_in, float* add1_hist_out,
+                                     int delay1, const float* add2, const float* add2_hist_in, float* add2_hist_out,
+                                     int delay2, int valid_lo, int valid_hi, StreamDelay* dl) {
   dl->valid_lo = valid_lo;
   dl->valid_hi = valid_hi;
-  return PWG_OK;
+  return stream_lines(name, add1, add1_hist_in, add1_hist_out, delay1, add2, add2_hist_in, add2_hist_out, delay2, dl);
+}
+
+// ... of a slotted launch, with its table: every state buffer is there from the first launch on (a fresh item does not
+// read its inputs, a launch-wide NULL would), so a delayed addend needs its hist_in too
+static inline int stream_slot_lines(const char* name, const float* add1, const float* add1_hist_in, float* add1_hist_out,
+                                    int delay1, const float* add2, const float* add2_hist_in, float* add2_hist_out,
+                                    int delay2, const int32_t* slots, int rate, int delay, StreamSlots* sl) {
+  PWG_REQUIRE(slots != nullptr, PWG_ERR_NULL, "%s: slots is NULL", name);
+  PWG_REQUIRE((reinterpret_cast<uintptr_t>(slots) & 3u) == 0, PWG_ERR_BAD_SHAPE, "%s: unaligned slot table", name);
+  PWG_REQUIRE(rate >= 1 && delay >= 0, PWG_ERR_BAD_SHAPE, "%s: rate = %d, delay = %d (needs rate >= 1, delay >= 0)", name,
+              rate, delay);
+  PWG_REQUIRE((!delay1 || add1_hist_in) && (!delay2 || add2_hist_in), PWG_ERR_NULL,
+              "%s: a delayed addend needs its add_hist_in (a fresh item does not read it)", name);
+  sl->slots = slots;
+  sl->rate = rate;
+  sl->out_delay = delay;
+  return stream_lines(name, add1, add1_hist_in, add1_hist_out, delay1, add2, add2_hist_in, add2_hist_out, delay2, sl);
 }
 
 static inline void stream_fill_args(StreamCommonArgs* a, const pwg_conv1d_desc* d, const StreamGeom& g, const StreamTile& t,

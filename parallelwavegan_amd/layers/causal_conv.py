@@ -127,12 +127,16 @@ _STREAM_KERNELS = {
                           ops.conv1d_stream_delayed_forward_bf16),
     ("mirrored", "fp32"): ("mirrored streaming kernel", ops.conv1d_stream_mirrored_supported,
                            ops.conv1d_stream_mirrored_forward),
+    # (the slotted form has no query of its own: its coverage is the delayed form's)
+    ("slots", "fp32"): ("slotted streaming kernel", ops.conv1d_stream_delayed_supported, ops.conv1d_stream_slots_forward),
+    ("slots", "bf16"): ("slotted bf16 streaming kernel", ops.conv1d_stream_bf16_delayed_supported,
+                        ops.conv1d_stream_slots_forward_bf16),
 }
 # what an fp32 launch tells a module in bf16 mode, per form
 _LOOKAHEAD_IS_FP32 = ("the look-ahead stream is fp32 (utils.set_inference_precision(model, 'fp32'), or pass "
                       "precision='bf16' to stream with bf16 operands)")
 _FORM_IS_FP32 = {"plain": "the streaming kernel is fp32 (pass precision='bf16' to stream with bf16 operands)",
-                 "delayed": _LOOKAHEAD_IS_FP32, "mirrored": _LOOKAHEAD_IS_FP32}
+                 "delayed": _LOOKAHEAD_IS_FP32, "mirrored": _LOOKAHEAD_IS_FP32, "slots": _LOOKAHEAD_IS_FP32}
 _FORM_IS_FP32_ONLY = {"mirrored": "a reflect-padded layer streams with a look-ahead in fp32 only"}
 
 
@@ -319,6 +323,16 @@ class _Walk:
     def _window(self, launch, t_out):
         return lookahead_window(launch.delay, launch.rate, t_out, self.frames_before, self.total_frames)
 
+    def _take_conv(self, cv):
+        """The next launch of a convolution plan, which must be ``cv``'s -> ``(launch, history pair, delay line pair of
+        addend 1, of addend 2)``, ``(None, None)`` where the launch keeps none."""
+        launch = next(self._plan)
+        if launch.conv is not cv:
+            raise RuntimeError(f"look-ahead walk out of step: the plan expects {launch.conv}, the model ran {cv}")
+        hist = self._pair() if lookahead_history_columns(cv) else (None, None)
+        line1, line2 = (self._pair() if d else (None, None) for d in (launch.delay1, launch.delay2))
+        return launch, hist, line1, line2
+
 
 class LookaheadWalk(_Walk):
     """The walk of a convolution plan (HiFi-GAN, MelGAN): hands every launch its state tensors, of
@@ -329,11 +343,7 @@ class LookaheadWalk(_Walk):
         """The next launch of the plan, which must be ``cv``'s, on the chunk ``x``; fused-epilogue keywords as in
         ``forward``.  A reflect-padded launch (the non-causal MelGAN's) goes through the mirrored form, whose input
         window is the producing launch's unclamped valid window: fp32 only, no addends."""
-        launch = next(self._plan)
-        if launch.conv is not cv:
-            raise RuntimeError(f"look-ahead walk out of step: the plan expects {launch.conv}, the model ran {cv}")
-        hist = self._pair() if lookahead_history_columns(cv) else (None, None)
-        line1, line2 = (self._pair() if d else (None, None) for d in (launch.delay1, launch.delay2))
+        launch, hist, line1, line2 = self._take_conv(cv)
         desc = launch_desc(launch, x.shape[0], x.shape[-1], **fused)
         valid = self._window(launch, desc.t_out)
         if not launch_is_mirrored(launch):
@@ -343,6 +353,29 @@ class LookaheadWalk(_Walk):
             raise RuntimeError("the mirrored form of the streaming kernel takes no addends")
         return _launch("mirrored", self.precision, cv, desc, x, hist,
                        mirrored_in_window(launch, self.frames_before, self.total_frames), valid)
+
+
+class SlotWalk(_Walk):
+    """:class:`LookaheadWalk` for a batch whose items sit at different points of different utterances
+    (utils.StreamPool): ``run`` has the same contract, but every launch goes through the slotted form
+    and derives each item's valid window itself, from ``slots`` -- the device table of ``ops.conv1d_stream_slots_forward``,
+    one row per item -- and its own rate and delay.  There is no start-of-stream walk: ``state_in`` is always a half, and
+    an item that starts an utterance is fresh in the table.  Zero-padded plans only (the mirrored form needs the
+    utterance's end before its last columns)."""
+
+    def __init__(self, plan, state_in, state_out, slots, precision="fp32"):
+        if state_in is None:
+            raise ValueError("SlotWalk: state_in is a ping-pong half; the start of a stream is an item's, in the table")
+        super().__init__(plan, state_in, state_out, precision=precision)
+        self.slots = slots
+
+    def run(self, cv, x, add1=None, add2=None, **fused):
+        launch, hist, line1, line2 = self._take_conv(cv)
+        if launch_is_mirrored(launch):
+            raise RuntimeError("the mirrored form of the streaming kernel has no slotted form")
+        desc = lookahead_desc(cv, x.shape[0], x.shape[-1], **fused)
+        return _launch("slots", self.precision, cv, desc, x, hist, add1, line1, launch.delay1, add2, line2, launch.delay2,
+                       self.slots, launch.rate, launch.delay, delays=(launch.delay1, launch.delay2))
 
 
 # ---- the same for the NON-causal Parallel WaveGAN generator (utils.PWGLookaheadStream, DESIGN.md s11.6).  Its launches

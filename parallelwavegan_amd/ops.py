@@ -375,21 +375,61 @@ def conv1d_stream_delayed_forward(desc, x, hist_in, hist_out, w_packed, bias=Non
 
 
 def _conv1d_stream_delayed(entry, name, desc, x, hist_in, hist_out, image, bias, add1, add1_hist, delay1, add2, add2_hist,
-                           delay2, valid, out):
-    """What the two delayed conv stream wrappers share: the checks of every tensor but the weight image, and the call of
-    the library's ``entry``."""
+                           delay2, valid, out, slots=None):
+    """What the delayed and slotted conv stream wrappers share: the checks of every tensor but the weight image, and the
+    call of the library's ``entry``.  ``slots``: None for a delayed entry, which takes the window ``valid``; else
+    ``(table, rate, delay)`` of a slotted one, which takes those in the window's place."""
     flat = (add1_hist[0], add1_hist[1], add2_hist[0], add2_hist[1])
     _require_device(x, hist_in, hist_out, bias, add1, add2, out, *flat)
     out = _conv1d_stream_out(desc, x, hist_in, hist_out, add1, add2, out)
     for delay, (h_in, h_out) in ((delay1, add1_hist), (delay2, add2_hist)):
         for t in (h_in, h_out):
             assert t is None or t.numel() == desc.batch * desc.c_out * delay, (tuple(t.shape), delay)
-    lo, hi = (0, desc.t_out) if valid is None else valid
+    if slots is None:
+        lo, hi = (0, desc.t_out) if valid is None else valid
+        position = (int(lo), int(hi))
+    else:
+        table, rate, delay = slots
+        if table is None or not table.is_cuda or table.dtype != torch.int32 or not table.is_contiguous():
+            raise RuntimeError(f"{name}: slots must be a contiguous int32 device tensor (the kernel reads it; there is no "
+                               "CPU fallback path)")
+        assert tuple(table.shape) == (desc.batch, SLOT_INTS), (tuple(table.shape), desc.batch)
+        position = (_ptr(table), int(rate), int(delay))
     _lib.check(entry(
         ctypes.byref(desc), _ptr(x), _ptr(hist_in), _ptr(hist_out), _ptr(image), _ptr(bias),
         _ptr(add1), _ptr(flat[0]), _ptr(flat[1]), int(delay1), _ptr(add2), _ptr(flat[2]), _ptr(flat[3]), int(delay2),
-        int(lo), int(hi), _ptr(out), _stream()), name)
+        *position, _ptr(out), _stream()), name)
     return out
+
+
+# A row of a slotted launch's table (include/pwg_kernels.h): [frames before, frames left, flags, 0]
+SLOT_INTS = 4
+SLOT_PAUSED, SLOT_LEFT_KNOWN = 1, 2
+
+
+def conv1d_stream_slots_forward(desc, x, hist_in, hist_out, w_packed, bias=None, add1=None, add1_hist=(None, None),
+                                delay1=0, add2=None, add2_hist=(None, None), delay2=0, slots=None, rate=1, delay=0,
+                                out=None):
+    """:func:`conv1d_stream_delayed_forward` with a position per item: ``slots`` is a device ``(batch, SLOT_INTS)`` int32
+    table -- per item the frames that went before (0: fresh, its state inputs read as zeros), the frames left, and
+    ``SLOT_PAUSED`` / ``SLOT_LEFT_KNOWN`` -- from which, with the launch's ``rate`` (output columns per frame) and output
+    ``delay``, the kernel derives each item's valid window.  A paused item's state is copied through and its output
+    columns are zeros.  Every state input must be given.  One launch."""
+    _require_device(w_packed)
+    return _conv1d_stream_delayed(_lib.lib().pwg_conv1d_stream_slots_forward, "conv1d_stream_slots_forward", desc, x,
+                                  hist_in, hist_out, w_packed, bias, add1, add1_hist, delay1, add2, add2_hist, delay2, None,
+                                  out, (slots, rate, delay))
+
+
+def conv1d_stream_slots_forward_bf16(desc, x, hist_in, hist_out, w_packed_bf16, bias=None, add1=None,
+                                     add1_hist=(None, None), delay1=0, add2=None, add2_hist=(None, None), delay2=0,
+                                     slots=None, rate=1, delay=0, out=None):
+    """:func:`conv1d_stream_slots_forward` with bf16 operands, as :func:`conv1d_stream_delayed_forward_bf16` is to
+    :func:`conv1d_stream_delayed_forward`."""
+    _check_stream_image_bf16("conv1d_stream_slots_forward_bf16", desc, w_packed_bf16)
+    return _conv1d_stream_delayed(_lib.lib().pwg_conv1d_stream_slots_forward_bf16, "conv1d_stream_slots_forward_bf16", desc,
+                                  x, hist_in, hist_out, w_packed_bf16, bias, add1, add1_hist, delay1, add2, add2_hist,
+                                  delay2, None, out, (slots, rate, delay))
 
 
 def conv1d_stream_mirrored_supported(desc):

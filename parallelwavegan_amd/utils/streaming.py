@@ -29,6 +29,7 @@ standard NON-causal Parallel WaveGAN (3921 samples, 15.3 frames, for ``parallel_
 ``MelGANLookaheadStream`` for the standard NON-causal, reflect-padded MelGAN and multi-band MelGAN, whose reflect-padded
 layers mirror their window on read (1425 samples for ``melgan.v1``, 2720 for ``multi_band_melgan.v2``).
 """
+import collections
 import ctypes
 
 import torch
@@ -1000,3 +1001,264 @@ class PWGLookaheadStream(_LookaheadStream):
         feats = self._last.expand(-1, self.latency_frames, -1).contiguous()
         zeros = torch.zeros((self.batch, 1, self.latency_frames * self.up), device=self._device)
         return self._run(feats, zeros, state_in, state_out, total, total)
+
+
+# ---- a pool of look-ahead streams whose utterances start and end independently -------------------
+
+def slot_window(delay, rate, t_out, before, left=None):
+    """The window rule of the slotted stream kernel (``stream_slot_window``, csrc/stream_common.h), restated: the valid
+    columns ``(lo, hi)`` of a launch ``delay`` columns late at ``rate`` columns per frame, on a push of ``t_out`` columns
+    that ``before`` frames went before; ``left``: frames of the utterance from this push's first frame on (negative past
+    its end), None while unknown.  ``layers.causal_conv.lookahead_window`` with ``left = total_frames - frames_before``."""
+    lo = min(max(delay - before * rate, 0), t_out)
+    hi = t_out if left is None else min(max(delay + left * rate, 0), t_out)
+    return lo, hi
+
+
+# What one slot does in one step of the pool.  ``action``: "empty" (no utterance: fresh and paused), "pause" (fewer
+# than a chunk queued, not ended), "run" (a chunk of queued frames), "tail" (ended: what is left, zero-padded) or "drain"
+# (ended: zero frames only); ``take``: queued frames it consumes; ``row``: its row of the kernels' table; ``emit``: the
+# range of the step's ``chunk * up`` output samples that became complete; ``closes``: the utterance is done.
+SlotStep = collections.namedtuple("SlotStep", "slot action take row emit closes")
+
+
+class SlotSchedule:
+    """The bookkeeping of :class:`StreamPool`, with no device in it: which slot holds an utterance, how many frames each
+    has queued and taken, and what every slot does in a step -- its action, its row of the slotted kernels' table
+    (``ops.conv1d_stream_slots_forward``) and the samples it emits.
+
+    Emission follows ``_LookaheadStream``: after a step in which a slot has taken ``frames_in`` frames (padding and
+    drain frames included) its emissions total ``clamp(frames_in * up - latency_samples, 0, frames * up)``, ``frames``
+    being the utterance's length once it has ended.  The table's position saturates at ``settle_frames`` (past every
+    delay of the plan) and the frames left at ``[-settle_frames, chunk]``, which changes no window and keeps the kernel's
+    arithmetic small however long an utterance is."""
+
+    def __init__(self, slots, chunk_frames, up, latency_samples, settle_frames):
+        self.slots, self.chunk, self.up = int(slots), int(chunk_frames), int(up)
+        self.latency, self.settle = int(latency_samples), max(int(settle_frames), 1)
+        self._state = [None] * self.slots  # per slot None (free) or [queued, fed, ended, before]
+
+    @property
+    def open_slots(self):
+        return [s for s, st in enumerate(self._state) if st is not None]
+
+    def _of(self, slot, what):
+        if not 0 <= slot < self.slots or self._state[slot] is None:
+            raise RuntimeError(f"StreamPool.{what}: slot {slot} is not open")
+        return self._state[slot]
+
+    def open(self):
+        for s, st in enumerate(self._state):
+            if st is None:
+                self._state[s] = [0, 0, False, 0]
+                return s
+        raise RuntimeError(f"StreamPool.open: all {self.slots} slots are taken")
+
+    def feed(self, slot, n):
+        st = self._of(slot, "feed")
+        if st[2]:
+            raise RuntimeError(f"StreamPool.feed: slot {slot} was ended")
+        st[0] += n
+        st[1] += n
+
+    def end(self, slot):
+        st = self._of(slot, "end")
+        st[2] = True
+        if st[1] == 0:  # an empty utterance emits nothing
+            self._state[slot] = None
+
+    def reset(self):
+        self._state = [None] * self.slots
+
+    def advance(self):
+        """The next step: one :class:`SlotStep` per slot, or ``[]`` (and no change) if no slot runs."""
+        from ..ops import SLOT_LEFT_KNOWN, SLOT_PAUSED
+
+        steps, runs = [], False
+        for s, st in enumerate(self._state):
+            if st is None:
+                steps.append(SlotStep(s, "empty", 0, (0, 0, SLOT_PAUSED, 0), (0, 0), False))
+                continue
+            queued, fed, ended, before = st
+            position = min(before, self.settle)
+            if queued < self.chunk and not ended:
+                steps.append(SlotStep(s, "pause", 0, (position, 0, SLOT_PAUSED, 0), (0, 0), False))
+                continue
+            runs = True
+            take = min(queued, self.chunk)
+            cap = fed * self.up if ended else None
+            lo, hi = (max(0, frames * self.up - self.latency) for frames in (before, before + self.chunk))
+            if ended:
+                lo, hi = min(lo, cap), min(hi, cap)
+            left = max(-self.settle, min(fed - before, self.chunk)) if ended else 0
+            action = "run" if take == self.chunk else ("tail" if take else "drain")
+            offset = self.latency - before * self.up  # the step's sample 0 is the late stream's before * up
+            steps.append(SlotStep(s, action, take, (position, left, SLOT_LEFT_KNOWN if ended else 0, take),
+                                  (lo + offset, hi + offset), ended and hi == cap))
+        if not runs:
+            return []
+        for step in steps:
+            if step.closes:
+                self._state[step.slot] = None
+            elif step.action in ("run", "tail", "drain"):
+                st = self._state[step.slot]
+                st[0] -= step.take
+                st[3] += self.chunk
+        return steps
+
+
+class StreamPool(_Stream):
+    """``slots`` look-ahead streams of the standard NON-causal ``HiFiGANGenerator`` in one batch, whose utterances start
+    and end whenever they like: what :class:`LookaheadStream` does for ``batch`` lock-step streams, for a server.
+
+    ``open()`` -> a free slot id (RuntimeError when every slot is taken); ``feed(slot, frames)`` queues ``(n, C)``
+    features, any ``n >= 0``, on the host; ``end(slot)``: no more frames.  ``step()`` is ONE set of launches over all
+    slots -> ``{slot: (samples,) fp32}`` for every slot that ran, the samples that became complete (views of one tensor
+    that is the caller's own).  In a step a slot with ``chunk_frames`` queued runs on them; one with fewer, not ended, is
+    paused (its state stays, it emits nothing); an ended one runs on what is left, padded with zero frames (inserted
+    after normalisation, as ``flush()`` does; the kernels know the remaining length), then on zero chunks until it has
+    emitted ``frames * up`` samples, and closes: its id leaves ``open_slots`` and is free again.  An utterance ended
+    without frames closes at once.  If no slot runs, ``step()`` returns ``{}`` and launches nothing.  A slot's
+    concatenated emissions are bit for bit what ``LookaheadStream(model, batch=1)`` emits for the same frames, pushes
+    and flush together; ``latency_samples`` is that class's.
+
+    How: every launch is the slotted form of the streaming kernel (csrc/conv1d_stream.hip), which
+    reads each item's position from a small device table -- frames before, frames left, paused -- and derives the
+    item's window itself; a slot taken for a new utterance is fresh and reads none of the old state.  A step uploads the
+    table and the features (two copies from pinned memory), so ``use_graph`` captures ONE pair of graphs (A -> B, B -> A)
+    and replays it from the first step on: start, steady state and tail are the same launches.  ``precision``,
+    ``normalize_before`` and the refusals are :class:`LookaheadStream`'s; ``reset()`` closes every slot."""
+
+    def __init__(self, model, slots=16, chunk_frames=8, use_graph=True, normalize_before=False, precision=None):
+        from ..layers.causal_conv import launch_desc, lookahead_settle_frames, lookahead_state_shapes
+        from ..models import HiFiGANGenerator
+
+        precision = self._checked_precision(precision)
+        if not isinstance(model, HiFiGANGenerator):
+            raise ValueError(f"StreamPool: {model.__class__.__name__} is not supported (only the non-causal "
+                             "HiFiGANGenerator; a non-causal MelGANGenerator streams in lock step through "
+                             "utils.MelGANLookaheadStream, a ParallelWaveGANGenerator through utils.PWGLookaheadStream)")
+        if model.use_causal_conv:
+            raise ValueError("StreamPool: the model is causal (use_causal_conv=True) and streams in lock step, without "
+                             "look-ahead, through utils.CausalStream")
+        out_channels = model.output_conv[1].out_channels
+        if out_channels != 1:
+            raise ValueError(f"StreamPool: the generator emits {out_channels} channels; a slot returns one waveform "
+                             "(out_channels == 1)")
+        self._refuse_bf16_model(model, precision, "look-ahead stream")
+        slots, chunk_frames = int(slots), int(chunk_frames)
+        if slots < 1:
+            raise ValueError("StreamPool: slots must be >= 1")
+        if chunk_frames < 1:
+            raise ValueError("StreamPool: chunk_frames must be >= 1")
+        plan = model.lookahead_plan()  # ValueError: decreasing block delays, a layer without a causal form
+        delayed = conv1d_stream_bf16_delayed_supported if precision == "bf16" else conv1d_stream_delayed_supported
+        for launch in plan:  # (the slotted form covers what the delayed form covers)
+            self._require_supported(delayed(launch_desc(launch, slots, chunk_frames), launch.delay1, launch.delay2),
+                                    launch.conv)
+        self.precision = precision
+        self.slots, self.chunk_frames = slots, chunk_frames
+        self.up = model.upsample_factor
+        self.latency_samples = plan[-1].delay
+        self._plan = plan
+        self._schedule = SlotSchedule(slots, chunk_frames, self.up, self.latency_samples, lookahead_settle_frames(plan))
+        super().__init__(model, [], slots, use_graph, normalize_before, lookahead_state_shapes(plan, slots))
+        channels = plan[0].conv.in_channels
+        from ..ops import SLOT_INTS
+
+        # what a step uploads: the table and the features, staged in two pinned buffers used in turn (a buffer is written
+        # again only after its copy of two steps ago has finished)
+        self._table = torch.zeros((slots, SLOT_INTS), device=self._device, dtype=torch.int32)
+        self._feats = torch.zeros((slots, chunk_frames, channels), device=self._device)
+        self._staging = [(torch.zeros((slots, SLOT_INTS), dtype=torch.int32).pin_memory(),
+                          torch.zeros((slots, chunk_frames, channels)).pin_memory(), torch.cuda.Event()) for _ in range(2)]
+        self._columns = torch.arange(chunk_frames, device=self._device).reshape(1, 1, -1)
+
+    @property
+    def open_slots(self):
+        """The ids that hold an utterance, ascending."""
+        return self._schedule.open_slots
+
+    @property
+    def graphs_captured(self):
+        """How many graphs the pool holds: 0, or 2 (both directions of its one chunk size)."""
+        return sum(len(graphs) for graphs in self._graphs.values())
+
+    def reset(self):
+        """Closes every slot, dropping what is queued; the state needs no clearing (a new utterance is fresh)."""
+        self._restart()
+        self._queues = [[] for _ in range(self.batch)]
+        self._step = 0
+        self._schedule.reset()
+
+    def open(self):
+        return self._schedule.open()
+
+    def feed(self, slot, frames):
+        frames = torch.as_tensor(frames, dtype=torch.float32).cpu()
+        if frames.dim() != 2 or frames.shape[1] != self._feats.shape[2]:
+            raise ValueError(f"StreamPool.feed: expected (n, {self._feats.shape[2]}) features, got {tuple(frames.shape)}")
+        self._schedule.feed(slot, frames.shape[0])
+        self.frames_in += frames.shape[0]
+        if frames.shape[0]:
+            self._queues[slot].append(frames)
+
+    def end(self, slot):
+        self._schedule.end(slot)
+
+    def _take(self, slot, n, out):
+        """Moves the next ``n`` queued frames of ``slot`` into ``out[:n]`` and zeros the rest of ``out``."""
+        queue, at = self._queues[slot], 0
+        while at < n:
+            head = queue[0]
+            k = min(n - at, head.shape[0])
+            out[at:at + k] = head[:k]
+            at += k
+            if k == head.shape[0]:
+                queue.pop(0)
+            else:
+                queue[0] = head[k:]
+        out[n:] = 0.0
+
+    def _run(self, feats, state_in, state_out):
+        """The generator on one step's inputs, every launch slotted -> (slots, chunk_frames * up)."""
+        from ..layers.causal_conv import SlotWalk
+
+        c = self._features(feats)
+        if self.normalize_before:  # the padding frames are zeros AFTER normalisation (row[3]: the real frames)
+            c.masked_fill_(self._columns >= self._table[:, 3].reshape(-1, 1, 1), 0.0)
+        walk = SlotWalk(self._plan, state_in, state_out, self._table, self.precision)
+        return self.model.lookahead_forward(c, walk).reshape(self.batch, -1)
+
+    @torch.no_grad()
+    def step(self):
+        steps = self._schedule.advance()
+        if not steps:
+            return {}
+        table, feats, copied = self._staging[self._step % 2]
+        self._step += 1
+        copied.synchronize()
+        table.copy_(torch.tensor([st.row for st in steps], dtype=torch.int32))
+        for st in steps:
+            if st.action in ("run", "tail", "drain"):
+                self._take(st.slot, st.take, feats[st.slot])
+        self._table.copy_(table, non_blocking=True)
+        self._feats.copy_(feats, non_blocking=True)
+        copied.record()
+        state_in, state_out = self._halves[self._cur], self._halves[1 - self._cur]
+        if self.use_graph:
+            graphs = self._graph_entry("pool", lambda: _capture_directions(
+                self._halves, lambda hist_in, hist_out: self._run(self._feats, hist_in, hist_out)))
+            graph, static_out = graphs[self._cur]
+            graph.replay()
+            y = static_out.clone()
+        else:
+            y = self._run(self._feats, state_in, state_out)
+        self._cur = 1 - self._cur
+        out = {}
+        for st in steps:
+            if st.action in ("run", "tail", "drain"):
+                out[st.slot] = y[st.slot, st.emit[0]:st.emit[1]]
+                self.frames_out += self.chunk_frames
+                self.samples_out += st.emit[1] - st.emit[0]
+        return out

@@ -59,7 +59,14 @@ whole-utterance forward (and, multi-band, ``pqmf.synthesis`` of its output) over
 generator's reach (the PQMF filter's own 31 samples are not added: the comparison leans towards the halo path).  Into
 profiles/stream_melgan_lookahead_infer.json; ``--multiband`` adds the multi-band model to the same file.
 
-usage: python tools/bench_stream.py [--model pwg|melgan [--lookahead]] [--multiband] [--precision bf16] [--lookahead] [--reps 200]
+``--pool [--precision bf16]``: ``utils.StreamPool`` on the non-causal HiFi-GAN V1 (the slotted form of the stream kernels;
+DESIGN.md s11.10).  (a) a step of 16 running slots -- every slot fed its 4 / 8 / 32 frames from the host, then ``step()``
+-- against ``LookaheadStream(batch=16).push`` of the same frames, already on the device, alternating; with the two uploads,
+the replay and the output copy of a step timed alone.  (b) 16 staggered utterances through the pool against the same 16
+through 16 batch-1 ``LookaheadStream``s stepped in turn, in frames per second of wall-clock time.  Into
+profiles/stream_pool_infer.json / profiles/stream_pool_bf16_infer.json.
+
+usage: python tools/bench_stream.py [--model pwg|melgan [--lookahead]] [--multiband] [--precision bf16] [--lookahead] [--pool] [--reps 200]
                                     [--repeats 3] [--out profiles/stream_infer.json]
 """
 import argparse
@@ -76,7 +83,7 @@ from parallelwavegan_amd.graphs import GraphedInference  # noqa: E402
 from parallelwavegan_amd.layers import PQMF  # noqa: E402
 from parallelwavegan_amd.models import HiFiGANGenerator, MelGANGenerator, ParallelWaveGANGenerator  # noqa: E402
 from parallelwavegan_amd.utils import (CausalStream, LookaheadStream, MelGANLookaheadStream,  # noqa: E402
-                                       PWGLookaheadStream, PWGStream, set_inference_precision)
+                                       PWGLookaheadStream, PWGStream, StreamPool, set_inference_precision)
 from parallelwavegan_amd.utils.streaming import receptive_field_frames  # noqa: E402
 from tests.golden import synth  # noqa: E402
 
@@ -189,8 +196,27 @@ def main():
     ap.add_argument("--multiband", action="store_true")
     ap.add_argument("--precision", choices=("fp32", "bf16"), default="fp32")
     ap.add_argument("--lookahead", action="store_true")
+    ap.add_argument("--pool", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.pool:
+        if args.model != "default" or args.multiband or args.lookahead:
+            ap.error("--pool is the stream pool of the non-causal HiFi-GAN (only --precision goes with it)")
+        args.out = args.out or os.path.join(ROOT, "profiles", "stream_pool_bf16_infer.json" if args.precision == "bf16"
+                                            else "stream_pool_infer.json")
+        rec = {"tool": "tools/bench_stream.py --pool", "device": torch.cuda.get_device_name(0), "reps": args.reps,
+               "repeats": args.repeats, "models": {}, "points": []}
+        measure_pool(rec, "hifigan_v1", build_noncausal(torch.device("cuda:0")), CHUNKS,
+                     torch.Generator(device="cpu").manual_seed(100), args, torch.device("cuda:0"))
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(rec, f, indent=1)
+            f.write("\n")
+        print(json.dumps({"out": args.out, "points": [[p["chunk_frames"], p["pool_step_ms"], p["lockstep_push_ms"]]
+                                                      if p["part"] == "a" else
+                                                      [p["pool_frames_per_s"], p["singles_frames_per_s"]]
+                                                      for p in rec["points"]]}))
+        return
     if args.model == "melgan":
         if not args.lookahead or args.precision != "fp32":
             ap.error("--model melgan is the fp32 look-ahead stream of the non-causal MelGAN: pass --lookahead (no --precision)")
@@ -616,6 +642,125 @@ def measure_pwg_precision(rec, name, model, model16, lookahead, chunks, gen, arg
                                                 "halo_fp32_ms", "halo_bf16_ms", "spread_ms",
                                                 "speedup_bf16_push_over_fp32_push", "speedup_bf16_push_over_halo_bf16",
                                                 "layer_launch_ms")}), file=sys.stderr, flush=True)
+
+
+def measure_pool(rec, name, model, chunks, gen, args, dev):
+    """``StreamPool`` in ``args.precision``.  (a) the cost of the table: a step with all 16 slots
+    running in steady state (every slot fed its ``n`` frames from the host, then ``step()``) against
+    ``LookaheadStream(batch=16).push`` of ``n`` device-resident frames, alternating; and where a step's time goes (the two
+    uploads, the replay, the output copy, each timed alone).  (b) what a server gains: 16 staggered utterances through
+    the pool against the same 16 through 16 batch-1 ``LookaheadStream``s stepped in turn, both fed from the host, in
+    frames per second of wall-clock time."""
+    import time
+
+    up, slots = model.upsample_factor, 16
+    med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+    probe = StreamPool(model, slots=slots, chunk_frames=8, use_graph=False, precision=args.precision)
+    rec["models"][name] = {"workload": "seeded weights, weight norm removed", "precision": args.precision, "slots": slots,
+                           "latency_samples": probe.latency_samples, "pool_state_bytes": probe.state_bytes}
+    for n in chunks:
+        host = torch.randn(slots, n, 80, generator=gen)
+        feats = host.to(dev)
+        pool = StreamPool(model, slots=slots, chunk_frames=n, use_graph=True, precision=args.precision)
+        lock = LookaheadStream(model, batch=slots, use_graph=True, precision=args.precision)
+        ids = [pool.open() for _ in range(slots)]
+
+        def pool_step():
+            for s in ids:
+                pool.feed(s, host[s])
+            pool.step()
+
+        while lock.frames_in < lock.settle_frames + 4 * n:  # past every edge; both graph directions of both
+            lock.push(feats)
+            pool_step()
+        t_p, t_l = [], []
+        for _ in range(args.repeats):
+            t_p.append(event_ms(pool_step, args.reps))
+            t_l.append(event_ms(lambda: lock.push(feats), args.reps))
+        graph, static_out = pool._graphs["pool"][0]
+        table, staged, _ = pool._staging[0]
+        parts = {"upload_ms": event_ms(lambda: (pool._table.copy_(table, non_blocking=True),
+                                                pool._feats.copy_(staged, non_blocking=True)), args.reps),
+                 "replay_ms": event_ms(graph.replay, args.reps),
+                 "output_copy_ms": event_ms(static_out.clone, args.reps),
+                 "lockstep_input_copy_ms": event_ms(lambda: feats.clone(), args.reps)}
+        spread = max(max(t_p) - min(t_p), max(t_l) - min(t_l))
+        p = {"part": "a", "model": name, "precision": args.precision, "slots": slots, "chunk_frames": n,
+             "samples_per_step": slots * n * up, "pool_step_ms": round(med(t_p), 4),
+             "pool_runs_ms": [round(t, 4) for t in t_p], "lockstep_push_ms": round(med(t_l), 4),
+             "lockstep_runs_ms": [round(t, 4) for t in t_l], "spread_ms": round(spread, 4),
+             "pool_over_lockstep": round(med(t_p) / med(t_l), 3),
+             "pool_not_slower_beyond_spread": med(t_p) <= med(t_l) + spread,
+             "pool_step_parts_ms": {k: round(v, 4) for k, v in parts.items()}}
+        rec["points"].append(p)
+        print(json.dumps({k: p[k] for k in ("part", "chunk_frames", "pool_step_ms", "lockstep_push_ms", "spread_ms",
+                                            "pool_not_slower_beyond_spread", "pool_step_parts_ms")}), file=sys.stderr,
+              flush=True)
+
+    # (b) 16 utterances of 200 .. 395 frames, one arriving every second step, 8 frames per utterance and step
+    n = 8
+    utts = [torch.randn(200 + 13 * i, 80, generator=gen) for i in range(slots)]
+    frames = sum(u.shape[0] for u in utts)
+    pool = StreamPool(model, slots=slots, chunk_frames=n, use_graph=True, precision=args.precision)
+    singles = [LookaheadStream(model, batch=1, use_graph=True, precision=args.precision) for _ in range(slots)]
+
+    def serve(open_, feed, end, step):
+        """Wall-clock seconds to serve every utterance; ``step()`` -> are utterances still in flight."""
+        torch.cuda.synchronize()
+        t0, at, tick = time.perf_counter(), {}, 0
+        while True:
+            if tick % 2 == 0 and tick // 2 < slots:
+                at[tick // 2] = [open_(tick // 2), 0]
+            for i, st in list(at.items()):
+                feed(st[0], utts[i][st[1]:st[1] + n])
+                st[1] += n
+                if st[1] >= utts[i].shape[0]:
+                    end(st[0])
+                    del at[i]
+            busy = step()
+            tick += 1
+            if not at and not busy and tick // 2 >= slots:
+                break
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    samples = {"pool": 0, "singles": 0}
+
+    def pool_open(i):
+        return pool.open()
+
+    def pool_busy():
+        samples["pool"] += sum(y.shape[0] for y in pool.step().values())
+        return bool(pool.open_slots)
+
+    def single_open(i):
+        singles[i].reset()
+        return i
+
+    def single_feed(i, f):
+        samples["singles"] += singles[i].push(f).shape[1]
+
+    def single_end(i):
+        samples["singles"] += singles[i].flush().shape[1]
+
+    legs = {"pool": lambda: serve(pool_open, pool.feed, pool.end, pool_busy),
+            "singles": lambda: serve(single_open, single_feed, single_end, lambda: False)}
+    for fn in legs.values():  # graphs, weight images
+        fn()
+    samples.update(pool=0, singles=0)
+    runs = {k: [] for k in legs}
+    for _ in range(args.repeats):
+        for k, fn in legs.items():
+            runs[k].append(fn())
+    assert samples["pool"] == samples["singles"] == args.repeats * frames * up, samples
+    fps = {k: frames / med(v) for k, v in runs.items()}
+    p = {"part": "b", "model": name, "precision": args.precision, "utterances": slots, "frames": frames, "chunk_frames": n,
+         "pool_frames_per_s": round(fps["pool"], 1), "singles_frames_per_s": round(fps["singles"], 1),
+         "pool_runs_s": [round(t, 4) for t in runs["pool"]], "singles_runs_s": [round(t, 4) for t in runs["singles"]],
+         "pool_over_singles": round(fps["pool"] / fps["singles"], 2),
+         "pool_real_time_streams_22050Hz": round(fps["pool"] * up / 22050.0, 1)}
+    rec["points"].append(p)
+    print(json.dumps(p), file=sys.stderr, flush=True)
 
 
 def measure_precision(rec, name, model, chunks, gen, args, dev):
