@@ -260,6 +260,16 @@ int pwg_conv1d_split_forward(const pwg_conv1d_desc* d, const float* x, const voi
 int pwg_conv1d_split_forward_cfg(const pwg_conv1d_desc* d, const float* x, const void* w_packed, const float* bias,
                                  const float* add1, const float* add2, float* y, int32_t mfma_shape, int32_t tile_mode,
                                  void* stream);
+/* The form of the kernel's reduction step (additive; pwg_abi_version() stays 15).  Resident: a step loads all its
+ * weight fragments, then issues its MFMAs.  Streamed: the fragments are requested a row tile ahead of their MFMAs, across
+ * taps and chunks.  Same products in the same order: same bits.  The launch plan chooses per class (input channels,
+ * taps); pwg_conv1d_split_step_form answers that choice for a descriptor -- 1 resident, 2 streamed, 0 unsupported
+ * (pwg_last_error names the reason) -- as pure host logic.  pwg_conv1d_split_forward_step (tests / A-B tools) is
+ * pwg_conv1d_split_forward_cfg plus step_form: 0 = the plan decides, 1 = resident, 2 = streamed.                       */
+int pwg_conv1d_split_step_form(const pwg_conv1d_desc* d);
+int pwg_conv1d_split_forward_step(const pwg_conv1d_desc* d, const float* x, const void* w_packed, const float* bias,
+                                  const float* add1, const float* add2, float* y, int32_t mfma_shape, int32_t tile_mode,
+                                  int32_t step_form, void* stream);
 
 /* ---- split-operand inference of the upsampling layers (csrc/conv1d_split.hip, convtr1d_split_mfma_kernel) ----
  * The fused transposed convolution of pwg_conv1d_forward at the ConvTranspose1d call site of the HiFi-GAN generator

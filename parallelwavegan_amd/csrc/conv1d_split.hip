@@ -199,6 +199,42 @@ __device__ __forceinline__ void split_epilogue(const SplitArgs& a, const typenam
   }
 }
 
+// One 32-channel chunk of the x window into the three LDS planes, as conv1d_split_mfma_kernel stages it (the streamed and
+// the transposed kernel)
+template <int NT, bool VEC>
+__device__ __forceinline__ void stage_chunk(const SplitArgs& a, const MfmaConvTile& c, int chunk, __bf16* xs) {
+  if (VEC) {
+    const int ngroups = (c.wcols + 3) >> 2, c_left = a.c_in - chunk * KC;
+    const float* __restrict__ xc = c.xb + (size_t)chunk * KC * a.t_in;
+    if (c.base >= 0 && c.base + 4 * ngroups <= a.t_in && c_left >= KC)
+      stage_window_vec<NT, false>(a, xc, c_left, c.base, ngroups, xs, c.tid);
+    else
+      stage_window_vec<NT, true>(a, xc, c_left, c.base, ngroups, xs, c.tid);
+  } else {
+    const int c_base = chunk * KC + c.wave * 8;
+    const bool interior = c.base >= 0 && c.base + c.wcols <= a.t_in && c_base + 8 <= a.c_in;  // per wave and chunk
+    for (int col = c.lane; col < c.wcols; col += 64) {
+      const int t = c.base + col;
+      const float* __restrict__ src = c.xb + (size_t)c_base * a.t_in + t;
+      float f[8];
+      if (interior) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) f[j] = src[(size_t)j * a.t_in];
+      } else {
+        const bool tin = t >= 0 && t < a.t_in;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          f[j] = 0.f;
+          if (tin && c_base + j < a.c_in) f[j] = src[(size_t)j * a.t_in];
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) f[j] = pre_activate(f[j], a.pre_mul, a.pre_mask);
+      split3_store<8>(f, xs + col * kConvRow + c.wave * 8, a.plane);
+    }
+  }
+}
+
 // TILE, WM, WN, WAVES_M: the tile ladder of mfma_conv.h.  VEC: the x window is staged with 16-B loads along t (rows 16-B
 // aligned, t_in % 4 == 0, window <= 2 * NT columns) and transposed in registers.
 // The second launch bound (waves per SIMD) is the occupancy that the main loop's registers allow: without it the register
@@ -288,11 +324,75 @@ conv1d_split_mfma_kernel(SplitArgs a) {
     split_epilogue<TILE, TM, TN, true, false>(a, acc, row0, col0, out_base);
 }
 
-template <bool VEC>
+// conv1d_split_mfma_kernel with the STREAMED form of the reduction step (split_step_streamed, as resunit_split_kernel runs
+// it) in place of the resident one: tap and k-step are one flat sequence of steps (split_step_successor), the weight
+// fragments run a row tile ahead of their MFMAs across taps and chunks -- those of a chunk's first step are in flight
+// while the chunk is staged -- and the very first request goes out in front of the first chunk's staging.  Staging,
+// tiles, launch bounds and epilogue are the resident kernel's, and an accumulator receives its products in the same
+// order (chunk, tap, step, product): the same bits.  split_step_form (below) chooses the kernel per launch.
+template <int TILE, int WM, int WN, int WAVES_M, bool VEC>
+__global__ __launch_bounds__(256, WM * WN == 4 ? (TILE == 16 ? 3 : 2) : (WM * WN == 2 ? 3 : 4)) void
+conv1d_split_streamed_mfma_kernel(SplitArgs a) {
+  constexpr int HL = 64 / TILE;
+  constexpr int KSTEPS = KC / (8 * HL);
+  constexpr int TM = WM * 32 / TILE, TN = WN * 32 / TILE;
+  constexpr int NREG = TILE * TILE / 64;
+  constexpr int WAVES_N = 4 / WAVES_M;
+  constexpr int MT = WAVES_M * WM * 32, NT = WAVES_N * WN * 32;
+  typedef typename Mfma<TILE>::acc_t acc_t;
+
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __bf16* xs = reinterpret_cast<__bf16*>(smem);  // [part][column][ROW]
+
+  const MfmaConvTile c = mfma_conv_tile<TILE, MT, NT, WAVES_M, VEC>(a);
+
+  // this lane's weight row of tile mi = 0; the fragments of row tile 0 of the step to come; that step
+  const unsigned wrow = c.m0 + c.wave_m * (WM * 32) + c.r;
+  bf16x8 wf[3];
+  SplitStepId step{0, 0, 0};
+  split_step_request(wf, a.w, a.part_stride, wrow + split_step_rows<TILE>(a.cin_chunks, a.m_pad, step, c.h));
+
+  acc_t acc[TM][TN];
+#pragma unroll
+  for (int mi = 0; mi < TM; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < TN; ++ni)
+#pragma unroll
+      for (int i = 0; i < NREG; ++i) acc[mi][ni][i] = 0.f;
+
+  for (int chunk = 0; chunk < a.cin_chunks; ++chunk) {
+    if (chunk) __syncthreads();
+    stage_chunk<NT, VEC>(a, c, chunk, xs);
+    __syncthreads();
+#pragma unroll 1
+    for (int s = 0; s < a.taps * KSTEPS; ++s) {  // the steps of this chunk: the planes hold one chunk
+      const SplitStepId next = split_step_successor(step, a.cin_chunks, a.taps, KSTEPS);
+      // the x fragment goes first: the transposed tile of split_epilogue
+      split_step_streamed<TILE, TM, TN, kConvRow, true>(
+          wf, a.w, a.part_stride, wrow + split_step_rows<TILE>(a.cin_chunks, a.m_pad, step, c.h),
+          wrow + split_step_rows<TILE>(a.cin_chunks, a.m_pad, next, c.h), xs,
+          c.sh + c.wave_n * (WN * 32) + c.r + step.tap * a.dil, split_step_off<TILE>(step, c.h), a.plane, acc);
+      step = next;
+    }
+  }
+
+  const size_t out_base = (size_t)c.b * a.c_out * a.t_out;
+  const int row0 = c.m0 + c.wave_m * (WM * 32) + c.r, col0 = c.q0 + c.wave_n * (WN * 32) + 4 * c.h;
+  const bool full = c.m0 + MT <= a.m && c.q0 + NT <= a.nq;  // no padded row and no column past the end in this tile
+  if (!a.wide_out)
+    split_epilogue<TILE, TM, TN, false, false>(a, acc, row0, col0, out_base);
+  else if (full)
+    split_epilogue<TILE, TM, TN, true, true>(a, acc, row0, col0, out_base);
+  else
+    split_epilogue<TILE, TM, TN, true, false>(a, acc, row0, col0, out_base);
+}
+
+template <bool VEC, bool STREAMED>
 struct Family {
   template <int TILE, int WM, int WN, int WAVES_M>
   struct K {
-    static constexpr auto fn = conv1d_split_mfma_kernel<TILE, WM, WN, WAVES_M, VEC>;
+    static constexpr auto fn = STREAMED ? conv1d_split_streamed_mfma_kernel<TILE, WM, WN, WAVES_M, VEC>
+                                        : conv1d_split_mfma_kernel<TILE, WM, WN, WAVES_M, VEC>;
   };
 };
 
@@ -310,22 +410,50 @@ static void split_fill_args(SplitArgs* a, const pwg_conv1d_desc* d, const MfmaCo
                                        reinterpret_cast<uintptr_t>(add2)) & 15u) == 0;
 }
 
+// The form of the reduction step of a launch (kStepResident / kStepStreamed), chosen where its plan is made, from the
+// launch's class: input channels (chunks) and taps.  Admitted to the streamed form is what the isolated A/B of the two
+// forms (tools/bench_conv_split_forms.py; DESIGN.md s9.1, profiles/split_early_loads.txt) measured: every run at
+// 16 x 800 frames disjointly faster than every resident run, and no shorter launch (1 x 800, 1 x 100; full-size and
+// half-size tiles) disjointly slower.  That held for every class measured -- 64, 128 and 256 input channels at 7 and 11
+// taps -- so the rule is their hull; classes nobody measured (fewer taps, a single chunk, the transposed kernel's two
+// taps) stay resident, and so does a part image that the 32-bit fragment index of the streamed form cannot address.
+// Pure host logic.
+constexpr int kStepPlanDecides = 0, kStepResident = 1, kStepStreamed = 2;
+constexpr int kStreamedMinTaps = 7, kStreamedMinChunks = 2;
+static int split_step_form(const MfmaConvGeom& g) {
+  if (!split_image_addressable(image_elems(g))) return kStepResident;
+  return g.taps >= kStreamedMinTaps && g.cin_chunks >= kStreamedMinChunks ? kStepStreamed : kStepResident;
+}
+
 static int split_forward(const pwg_conv1d_desc* d, const float* x, const void* w_packed, const float* bias,
-                         const float* add1, const float* add2, float* y, int mfma_shape, int tile_mode,
+                         const float* add1, const float* add2, float* y, int mfma_shape, int tile_mode, int step_form,
                          hipStream_t stream) {
   MfmaConvGeom g;
   int rc = split_geometry(d, &g);
-  if (rc == PWG_OK) rc = mfma_conv_check_forward("conv1d_split", d, x, w_packed, y, mfma_shape, tile_mode);
+  if (rc != PWG_OK) return rc;
+  PWG_REQUIRE(step_form >= kStepPlanDecides && step_form <= kStepStreamed, PWG_ERR_BAD_SHAPE,
+              "conv1d_split: step_form = %d (0 = the plan decides, 1 = resident, 2 = streamed)", step_form);
+  rc = mfma_conv_check_forward("conv1d_split", d, x, w_packed, y, mfma_shape, tile_mode);
   if (rc != PWG_OK) return rc;
   const MfmaConvPlan p = mfma_conv_plan(d, g, PARTS, tile_mode, x, add1, add2);
+  PWG_REQUIRE(step_form != kStepStreamed || split_image_addressable(image_elems(g)), PWG_ERR_UNSUPPORTED,
+              "conv1d_split: weight image too large for the streamed step");
+  const bool streamed = (step_form == kStepPlanDecides ? split_step_form(g) : step_form) == kStepStreamed;
   SplitArgs a;
   split_fill_args(&a, d, g, p, x, w_packed, bias, add1, add2, y);
   maybe_poison_lds(stream);
   ProfScope prof(stream, "conv1d_split_mfma_kernel", p.flops, p.bytes);
-  if (p.vec)
-    mfma_conv_launch<Family<true>::K>(p, mfma_shape, a, stream);
-  else
-    mfma_conv_launch<Family<false>::K>(p, mfma_shape, a, stream);
+  if (p.vec) {
+    if (streamed)
+      mfma_conv_launch<Family<true, true>::K>(p, mfma_shape, a, stream);
+    else
+      mfma_conv_launch<Family<true, false>::K>(p, mfma_shape, a, stream);
+  } else {
+    if (streamed)
+      mfma_conv_launch<Family<false, true>::K>(p, mfma_shape, a, stream);
+    else
+      mfma_conv_launch<Family<false, false>::K>(p, mfma_shape, a, stream);
+  }
   PWG_CHECK_LAUNCH("conv1d_split");
   return PWG_OK;
 }
@@ -344,41 +472,6 @@ static int convtr_geometry(const pwg_conv1d_desc* d, MfmaConvGeom* g) {
   PWG_REQUIRE(d->transposed, PWG_ERR_UNSUPPORTED,
               "convtr1d_split: not a transposed convolution (a stride-1 Conv1d runs on conv1d_split)");
   return mfma_conv_geometry("convtr1d_split", PARTS, true, d, g);
-}
-
-// One 32-channel chunk of the x window into the three LDS planes, as conv1d_split_mfma_kernel stages it
-template <int NT, bool VEC>
-__device__ __forceinline__ void stage_chunk(const SplitArgs& a, const MfmaConvTile& c, int chunk, __bf16* xs) {
-  if (VEC) {
-    const int ngroups = (c.wcols + 3) >> 2, c_left = a.c_in - chunk * KC;
-    const float* __restrict__ xc = c.xb + (size_t)chunk * KC * a.t_in;
-    if (c.base >= 0 && c.base + 4 * ngroups <= a.t_in && c_left >= KC)
-      stage_window_vec<NT, false>(a, xc, c_left, c.base, ngroups, xs, c.tid);
-    else
-      stage_window_vec<NT, true>(a, xc, c_left, c.base, ngroups, xs, c.tid);
-  } else {
-    const int c_base = chunk * KC + c.wave * 8;
-    const bool interior = c.base >= 0 && c.base + c.wcols <= a.t_in && c_base + 8 <= a.c_in;  // per wave and chunk
-    for (int col = c.lane; col < c.wcols; col += 64) {
-      const int t = c.base + col;
-      const float* __restrict__ src = c.xb + (size_t)c_base * a.t_in + t;
-      float f[8];
-      if (interior) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) f[j] = src[(size_t)j * a.t_in];
-      } else {
-        const bool tin = t >= 0 && t < a.t_in;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          f[j] = 0.f;
-          if (tin && c_base + j < a.c_in) f[j] = src[(size_t)j * a.t_in];
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < 8; ++j) f[j] = pre_activate(f[j], a.pre_mul, a.pre_mask);
-      split3_store<8>(f, xs + col * kConvRow + c.wave * 8, a.plane);
-    }
-  }
 }
 
 // The fp32 tail of a batch of N values of 4 samples, in the fp32 kernel's order (acc + bias + add1 + add2, * out_mul,
@@ -641,13 +734,25 @@ extern "C" int pwg_conv1d_split_forward(const pwg_conv1d_desc* d, const float* x
                                         size_t workspace_floats, void* stream) {
   (void)workspace;  // no split reduction: one workgroup owns an output tile
   (void)workspace_floats;
-  return split_forward(d, x, w_packed, bias, add1, add2, y, kDefaultMfmaShape, 0, (hipStream_t)stream);
+  return split_forward(d, x, w_packed, bias, add1, add2, y, kDefaultMfmaShape, 0, kStepPlanDecides, (hipStream_t)stream);
 }
 
 extern "C" int pwg_conv1d_split_forward_cfg(const pwg_conv1d_desc* d, const float* x, const void* w_packed,
                                             const float* bias, const float* add1, const float* add2, float* y,
                                             int32_t mfma_shape, int32_t tile_mode, void* stream) {
-  return split_forward(d, x, w_packed, bias, add1, add2, y, mfma_shape, tile_mode, (hipStream_t)stream);
+  return split_forward(d, x, w_packed, bias, add1, add2, y, mfma_shape, tile_mode, kStepPlanDecides, (hipStream_t)stream);
+}
+
+extern "C" int pwg_conv1d_split_forward_step(const pwg_conv1d_desc* d, const float* x, const void* w_packed,
+                                             const float* bias, const float* add1, const float* add2, float* y,
+                                             int32_t mfma_shape, int32_t tile_mode, int32_t step_form, void* stream) {
+  return split_forward(d, x, w_packed, bias, add1, add2, y, mfma_shape, tile_mode, step_form, (hipStream_t)stream);
+}
+
+extern "C" int pwg_conv1d_split_step_form(const pwg_conv1d_desc* d) {
+  MfmaConvGeom g;
+  if (split_geometry(d, &g) != PWG_OK) return 0;
+  return split_step_form(g);
 }
 
 extern "C" int pwg_convtr1d_split_supported(const pwg_conv1d_desc* d) {

@@ -27,9 +27,9 @@
 //                    LDS write per 4 accumulator registers
 //   phase 2 / single x (h) fragment first: the transposed tile, a lane owns 4 consecutive samples of a channel and the
 //                    epilogue reads x / add2 and writes y with 16-B accesses straight from the accumulators
-// The operand order changes neither the products nor their summation order.  The residual x is re-read from global
-// memory in the epilogue (the workgroup fetched those lines while staging; an fp32 copy in LDS would cost the second
-// workgroup per CU).
+// The operand order changes neither the products nor their summation order.  The residual x is read from global memory
+// a second time (an fp32 copy in LDS would cost the second workgroup per CU), but behind the staging loads that fetch
+// the same lines and into registers the two-wave occupancy leaves idle; add2 likewise ahead of the last contraction.
 // Deterministic: one workgroup owns an output tile, no atomics.
 #include "mfma_conv.h"
 
@@ -72,10 +72,11 @@ struct RuSplitCfg {
 // Stage the whole C-channel window: item = (group of 4 columns, channel octet), at most two per thread: 8 loads of 16 B
 // (one per channel, along t), then per column 8 channels are activated, split and written as three 16-B LDS stores.
 // T % 4 == 0 and the first staged column is a multiple of 4: a group lies inside the row or outside it.  CHECKED (first
-// / last tiles of a row): a group outside [0, T) gives zeros = the zero padding of conv1.
-template <int C, bool CHECKED>
+// / last tiles of a row): a group outside [0, T) gives zeros = the zero padding of conv1.  behind() runs between the
+// window's loads and its LDS stores: what it requests is in flight while the window is activated and split.
+template <int C, bool CHECKED, typename Behind>
 __device__ __forceinline__ void ru_stage_window(const RuSplitArgs& a, const float* __restrict__ xb, int base, __bf16* xs,
-                                                int tid) {
+                                                int tid, Behind&& behind) {
   constexpr int OCTS = RuSplitCfg<C>::OCTS, ROW = RuSplitCfg<C>::ROW;
   const int nitems = (a.rows >> 2) * OCTS;
   f32x4 st[2][8];
@@ -92,6 +93,7 @@ __device__ __forceinline__ void ru_stage_window(const RuSplitArgs& a, const floa
       st[it][j] = v;
     }
   }
+  behind();
 #pragma unroll
   for (int it = 0; it < 2; ++it) {
     const int idx = tid + it * 256, oct = idx % OCTS, grp = idx / OCTS;
@@ -140,6 +142,13 @@ __device__ __forceinline__ void ru_contract(bf16x8 (&wf)[3], const bf16x8* __res
   }
 }
 
+// Output slot of value n (0 .. TN * NG - 1) of a lane of group h in the transposed tile of phase 2 / the single form
+template <int TILE>
+__device__ __forceinline__ int ru_out_slot(int wave_n, int h, int n) {
+  constexpr int HL = 64 / TILE, NG = TILE * TILE / 256;
+  return wave_n * 64 + (n / NG) * TILE + 4 * h + 4 * HL * (n % NG);
+}
+
 template <int C, int TILE>
 __global__ __launch_bounds__(256, 2) void resunit_split_kernel(RuSplitArgs a) {
   using Cfg = RuSplitCfg<C>;
@@ -165,10 +174,62 @@ __global__ __launch_bounds__(256, 2) void resunit_split_kernel(RuSplitArgs a) {
   bf16x8 wf[3];
   ru_request<C, TILE>(wf, a.w1, a.part_stride, wrow, h);
 
+  // The epilogue's terms that no accumulator feeds -- the raw-x residual and add2 of the lane's own output values (the
+  // transposed tile described at the epilogue) -- are requested ahead of the contractions and held in registers: LDS,
+  // not registers, sets the two waves per SIMD.  The residual goes out behind the window's loads, which fetch the same
+  // lines; add2 behind it in the single form, behind phase 1 in the pair form.  A value that is not stored reads the
+  // tile's first samples (ok / t of the epilogue): no address outside the row.
+  constexpr int NV = TN * NG;
+  const bool has2 = a.add2 != nullptr;
+  f32x4 res[TM][NV], ad2[TM][NV];
+  auto request_values = [&](const float* __restrict__ src, f32x4 (&dst)[TM][NV]) {
+    __builtin_amdgcn_sched_barrier(0);  // behind what was requested before, and not sunk to the epilogue
+#pragma unroll
+    for (int mi = 0; mi < TM; ++mi) {
+      const float* __restrict__ rowp = src + ((size_t)b * C + wave_m * 32 + mi * TILE + r) * T;
+#pragma unroll
+      for (int n = 0; n < NV; ++n) {
+        const int slot = ru_out_slot<TILE>(wave_n, h, n);
+        const bool ok = slot < a.bn_out && t0 + slot < T;
+        dst[mi][n] = *reinterpret_cast<const f32x4*>(rowp + (ok ? t0 + slot : t0));
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  };
+#pragma unroll
+  for (int mi = 0; mi < TM; ++mi)
+#pragma unroll
+    for (int n = 0; n < NV; ++n) ad2[mi][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // the biases too: b1 of the lane's 4 consecutive channels per (mi, g) where h is formed, the epilogue's per row tile
+  const float* __restrict__ bias_p = pair ? a.b2 : a.b1;
+  const bool has_b1 = a.b1 != nullptr, has_bias = bias_p != nullptr;
+  f32x4 bias_h[TM][NG];
+  float bias_y[TM];
+#pragma unroll
+  for (int mi = 0; mi < TM; ++mi) {
+    bias_y[mi] = 0.f;
+#pragma unroll
+    for (int g = 0; g < NG; ++g) bias_h[mi][g] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  auto behind_window = [&] {
+    request_values(a.x, res);
+    if (!pair && has2) request_values(a.add2, ad2);
+#pragma unroll
+    for (int mi = 0; mi < TM; ++mi) {
+      if (has_bias) bias_y[mi] = bias_p[wave_m * 32 + mi * TILE + r];
+      if (pair && has_b1) {
+#pragma unroll
+        for (int g = 0; g < NG; ++g)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) bias_h[mi][g][e] = a.b1[wave_m * 32 + mi * TILE + 4 * h + 4 * HL * g + e];
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  };
   if (base >= 0 && base + a.rows <= T)
-    ru_stage_window<C, false>(a, xb, base, xs, tid);
+    ru_stage_window<C, false>(a, xb, base, xs, tid, behind_window);
   else
-    ru_stage_window<C, true>(a, xb, base, xs, tid);
+    ru_stage_window<C, true>(a, xb, base, xs, tid, behind_window);
 
   acc_t acc[TM][TN];
 #pragma unroll
@@ -184,19 +245,15 @@ __global__ __launch_bounds__(256, 2) void resunit_split_kernel(RuSplitArgs a) {
     ru_contract<C, TILE, false>(wf, a.w1, a.part_stride, wrow, xs + (wave_n * 64 + r + a.sh) * ROW, a.plane, a.d1, a.k,
                                 h, acc);
     ru_request<C, TILE>(wf, a.w2, a.part_stride, wrow, h);  // lands behind the forming of h and both barriers
+    if (has2) request_values(a.add2, ad2);                  // (so does add2)
     __syncthreads();  // every wave has read its x columns: the h planes take their place
     // h = lrelu(acc + b1), zero outside [0, T) (conv2's zero padding), split: a lane owns channels c .. c + 3 of a column
-    const bool has_b1 = a.b1 != nullptr;
 #pragma unroll
     for (int mi = 0; mi < TM; ++mi)
 #pragma unroll
       for (int g = 0; g < NG; ++g) {
         const int c = wave_m * 32 + mi * TILE + 4 * h + 4 * HL * g;
-        f32x4 bias = {0.f, 0.f, 0.f, 0.f};
-        if (has_b1) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) bias[e] = a.b1[c + e];
-        }
+        const f32x4 bias = bias_h[mi][g];
 #pragma unroll
         for (int ni = 0; ni < TN; ++ni) {
           const int m = wave_n * 64 + ni * TILE + r;
@@ -236,10 +293,8 @@ __global__ __launch_bounds__(256, 2) void resunit_split_kernel(RuSplitArgs a) {
   // ---- epilogue (fp32, the order of split_epilogue: acc + bias + x + add2, then / out_div).  Transposed tile: a lane
   // owns channel c per mi and, per accumulator, NG values of 4 consecutive samples; value g of tile ni is output slot
   // wave_n * 64 + ni * TILE + 4 * h + 4 * HL * g.  bn_out, t0 and T are multiples of 4: a value is stored whole or not
-  // at all; the loads of a value that is not stored read the tile's first samples instead.
-  constexpr int NV = TN * NG;
-  const float* __restrict__ bias_p = pair ? a.b2 : a.b1;
-  const bool has_bias = bias_p != nullptr, has2 = a.add2 != nullptr;
+  // at all; the loads of a value that is not stored read the tile's first samples instead.  x and add2 are the
+  // registers requested ahead of the contractions (res, ad2): the epilogue waits for no memory.
 #pragma unroll
   for (int mi = 0; mi < TM; ++mi) {
     const int c = wave_m * 32 + mi * TILE + r;
@@ -248,19 +303,14 @@ __global__ __launch_bounds__(256, 2) void resunit_split_kernel(RuSplitArgs a) {
     bool ok[NV];
 #pragma unroll
     for (int n = 0; n < NV; ++n) {
-      const int slot = wave_n * 64 + (n / NG) * TILE + 4 * h + 4 * HL * (n % NG);
+      const int slot = ru_out_slot<TILE>(wave_n, h, n);
       ok[n] = slot < a.bn_out && t0 + slot < T;
       t[n] = ok[n] ? t0 + slot : t0;
     }
-    f32x4 t1[NV], t2[NV], v[NV];
-    float bias = 0.f;
-    if (has_bias) bias = bias_p[c];
-#pragma unroll
-    for (int n = 0; n < NV; ++n) t1[n] = *reinterpret_cast<const f32x4*>(a.x + row + t[n]);
-    if (has2) {
-#pragma unroll
-      for (int n = 0; n < NV; ++n) t2[n] = *reinterpret_cast<const f32x4*>(a.add2 + row + t[n]);
-    }
+    const f32x4(&t1)[NV] = res[mi];
+    const f32x4(&t2)[NV] = ad2[mi];
+    f32x4 v[NV];
+    const float bias = bias_y[mi];
 #pragma unroll
     for (int n = 0; n < NV; ++n)
 #pragma unroll

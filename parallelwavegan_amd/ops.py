@@ -235,9 +235,9 @@ def _pack_weight_mfma(kind, desc, w, scale, op="conv1d"):
     return out
 
 
-def _conv1d_forward_mfma(kind, desc, image_desc, x, w_packed, bias, add1, add2, out, cfg, op="conv1d"):
+def _conv1d_forward_mfma(kind, desc, image_desc, x, w_packed, bias, add1, add2, out, cfg, op="conv1d", entry="cfg"):
     """The forward of the ``kind`` ("bf16" / "split") MFMA kernel.  ``image_desc``: the descriptor the image was packed
-    through; ``cfg``: the tuning integers of ``pwg_<op>_<kind>_forward_cfg``, None for the default launch."""
+    through; ``cfg``: the tuning integers of ``pwg_<op>_<kind>_forward_<entry>``, None for the default launch."""
     name = f"{op}_forward_{kind}"
     _require_device(x, bias, add1, add2, out)
     if not w_packed.is_cuda or w_packed.dtype != torch.uint8:
@@ -256,7 +256,7 @@ def _conv1d_forward_mfma(kind, desc, image_desc, x, w_packed, bias, add1, add2, 
     if cfg is None:
         rc = getattr(_lib.lib(), f"pwg_{op}_{kind}_forward")(*args, None, 0, _stream())
     else:
-        rc = getattr(_lib.lib(), f"pwg_{op}_{kind}_forward_cfg")(*args, *cfg, _stream())
+        rc = getattr(_lib.lib(), f"pwg_{op}_{kind}_forward_{entry}")(*args, *cfg, _stream())
     _lib.check(rc, name)
     return out
 
@@ -288,10 +288,28 @@ def pack_weight_split(desc, w, scale=None):
     return _pack_weight_mfma("split", desc, w, scale)
 
 
-def conv1d_forward_split(desc, x, w_packed, bias=None, add1=None, add2=None, out=None, mfma_shape=None, tile_mode=0):
+STEP_FORMS = {1: "resident", 2: "streamed"}
+
+
+def conv1d_split_step_form(desc):
+    """The form of the reduction step the split-operand kernel's launch plan chooses for this descriptor: "resident" or
+    "streamed" (csrc/conv1d_split.hip, ``split_step_form``).  Host logic only (no device needed); an unsupported
+    descriptor raises with the library's reason."""
+    form = _lib.lib().pwg_conv1d_split_step_form(ctypes.byref(desc))
+    if form == 0:
+        _lib.check(-1, "conv1d_split_step_form")
+    return STEP_FORMS[form]
+
+
+def conv1d_forward_split(desc, x, w_packed, bias=None, add1=None, add2=None, out=None, mfma_shape=None, tile_mode=0,
+                         step_form=0):
     """Fused fp32 convolution computed on the bf16 MFMA from 3-way split operands (inference only).
     ``mfma_shape`` (tuning): 32 or 16 selects the MFMA instruction; ``tile_mode`` (tests): 1 = full-size, 2 = half-size
-    tiles instead of the small-grid rule."""
+    tiles instead of the small-grid rule; ``step_form`` (tests / A-B): 1 = the resident, 2 = the streamed reduction step
+    instead of the plan's choice (same bits)."""
+    if step_form:
+        cfg = (int(mfma_shape or 16), int(tile_mode), int(step_form))
+        return _conv1d_forward_mfma("split", desc, desc, x, w_packed, bias, add1, add2, out, cfg, entry="step")
     cfg = None if mfma_shape is None and not tile_mode else (int(mfma_shape or 16), int(tile_mode))
     return _conv1d_forward_mfma("split", desc, desc, x, w_packed, bias, add1, add2, out, cfg)
 
