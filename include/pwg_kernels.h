@@ -546,6 +546,20 @@ int pwg_resunit_split_forward(const pwg_resunit_desc* d, const float* x, const v
 int pwg_resunit_split_forward_cfg(const pwg_resunit_desc* d, const float* x, const void* w1_split, const float* b1,
                                   const void* w2_split, const float* b2, const float* add2, float* y, int32_t mfma_shape,
                                   void* stream);
+/* The ragged form: one launch over a batch whose items have their own lengths (the batched form of the decode loop of
+ * bin/decode.py:214-243).  frames: device int32 (batch,), 0 <= frames[b]; item b ends at column
+ * tv = min(frames[b] * rate, t), t stays the row stride.  x and add2 must be exactly zero at the columns >= tv of their
+ * item (pwg_zero_tail establishes that); h is zero outside [0, tv); the columns < tv of y are bit for bit those of
+ * pwg_resunit_split_forward_cfg on the item alone with t = tv at the same mfma_shape, the columns >= tv are stored as
+ * 0.0f.  A workgroup whose tile lies at or beyond tv only stores zeros.  Nothing on the host depends on the table's
+ * values: a captured launch serves every set of lengths.  pwg_resunit_split_ragged_supported is
+ * pwg_resunit_split_supported plus rate % 4 == 0 (a value of four samples is stored whole or as zeros), pure host
+ * logic with its reason in pwg_last_error.  A NULL or unaligned table, or such a rate, is refused with a message and
+ * launches nothing.  Additive: pwg_abi_version() stays 15. */
+int pwg_resunit_split_ragged_supported(const pwg_resunit_desc* d, int32_t rate);
+int pwg_resunit_split_forward_ragged(const pwg_resunit_desc* d, const float* x, const void* w1_split, const float* b1,
+                                     const void* w2_split, const float* b2, const float* add2, float* y,
+                                     int32_t mfma_shape, const int32_t* frames, int32_t rate, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* One MelGAN residual stack as ONE launch (channels 48 / 96 / 192, kernel 3; csrc/resstack.hip)             */
@@ -939,6 +953,16 @@ int pwg_wave_to_pcm16(const float* x, int16_t* pcm, int64_t n, void* stream);
  * mean/scale may both be NULL (transpose only).                                       */
 int pwg_normalize_transpose(const float* x, const float* mean, const float* scale, float* y,
                             int32_t batch, int32_t frames, int32_t channels, void* stream);
+/* Ragged batches (utterances of different lengths in one forward; the batched form of the loop of
+ * bin/decode.py:214-243): y (batch, channels, t), frames device int32 (batch,), rate = columns of y per frame.  Stores
+ * 0.0f at the columns >= min(frames[b] * rate, t) of every row of item b; write-only (y may hold anything there, NaN
+ * included), the columns below are not touched.  16-B stores where a row's tail allows (rows of odd t are not 16-B
+ * aligned), scalar stores at the ragged head and end; a workgroup whose columns lie inside the item returns at once,
+ * so the cost follows the padding.  Run behind any convolution launch it re-establishes the invariant of a ragged
+ * forward: item b of a tensor at rate r is exactly zero at every column >= frames[b] * r.  Refused with a message,
+ * launching nothing: NULL or misaligned (4 B) y / frames, rate <= 0, batch outside 1 .. 65535. */
+int pwg_zero_tail(float* y, const int32_t* frames, int32_t batch, int32_t channels, int64_t t, int32_t rate,
+                  void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* Pooling / explicit padding                                                  */

@@ -203,6 +203,9 @@ SIGNATURES = {
     "pwg_resunit_split_forward": (ctypes.c_int, [ctypes.POINTER(ResUnitDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pwg_resunit_split_forward_cfg": (ctypes.c_int, [ctypes.POINTER(ResUnitDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32,
                                                      _vp]),
+    "pwg_resunit_split_ragged_supported": (ctypes.c_int, [ctypes.POINTER(ResUnitDesc), _i32]),
+    "pwg_resunit_split_forward_ragged": (ctypes.c_int, [ctypes.POINTER(ResUnitDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                        _i32, _vp, _i32, _vp]),
     "pwg_resstack_supported": (ctypes.c_int, [_i32, _i32, _i32]),
     "pwg_resstack_packed_weight_floats": (ctypes.c_size_t, [_i32]),
     "pwg_resstack_pack_weight": (ctypes.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -253,6 +256,7 @@ SIGNATURES = {
     "pwg_gather_crop": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32,
                                        _vp]),
     "pwg_normalize_transpose": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "pwg_zero_tail": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i64, _i32, _vp]),
     "pwg_weight_norm_backward": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "pwg_spectral_norm_forward": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp]),
     "pwg_spectral_norm_forward_saved": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp]),

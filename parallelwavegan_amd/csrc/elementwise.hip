@@ -857,6 +857,31 @@ __global__ void gather_crop_kernel(const float* audio, const long* audio_off, co
   }
 }
 
+// y[b][c][col] = 0 for col >= min(frames[b] * rate, t): the tail of every row of a ragged batch (the
+// batched form of the decode loop of bin/decode.py:214-243).  Write-only.  A workgroup owns kZeroTailCols columns of
+// kZeroTailRows rows of an item and returns at once when they all lie inside the item.  The columns are counted from
+// the 16-B boundary at or below the row's first element (rows of odd t start anywhere), so a thread's four columns are
+// one aligned 16-B store when they all lie in the tail, scalar stores at its ragged head and at the row's end.
+constexpr int kZeroTailCols = 1024, kZeroTailRows = 8;
+__global__ __launch_bounds__(256) void zero_tail_kernel(float* y, const int* frames, int channels, long t, int rate) {
+  const int b = blockIdx.z;
+  long tv = (long)frames[b] * rate;
+  tv = tv < 0 ? 0 : tv < t ? tv : t;
+  const long s0 = (long)blockIdx.x * kZeroTailCols;  // shifted columns [s0, s0 + kZeroTailCols): columns < s0 + kZeroTailCols
+  if (tv >= t || tv >= s0 + kZeroTailCols) return;
+  const int row_end = min((int)(blockIdx.y + 1) * kZeroTailRows, channels);
+  for (int row = blockIdx.y * kZeroTailRows; row < row_end; ++row) {
+    float* p = y + ((long)b * channels + row) * t;
+    const long lo = s0 + 4 * (long)threadIdx.x - (long)((reinterpret_cast<uintptr_t>(p) >> 2) & 3);
+    if (lo >= tv && lo + 4 <= t) {
+      *reinterpret_cast<float4*>(p + lo) = make_float4(0.f, 0.f, 0.f, 0.f);
+    } else {
+      const long hi = lo + 4 < t ? lo + 4 : t;
+      for (long col = lo > tv ? lo : tv; col < hi; ++col) p[col] = 0.f;
+    }
+  }
+}
+
 }  // namespace pwg
 
 using namespace pwg;
@@ -1226,6 +1251,24 @@ extern "C" int pwg_normalize_transpose(const float* x, const float* mean, const 
   const long n = (long)batch * frames * channels;
   ProfScope prof((hipStream_t)stream, "normalize_transpose_kernel", 0, 8.0 * n);
   LAUNCH1D(normalize_transpose_kernel, n, stream, x, mean, scale, y, batch, frames, channels);
+  return PWG_OK;
+}
+
+extern "C" int pwg_zero_tail(float* y, const int32_t* frames, int32_t batch, int32_t channels, int64_t t, int32_t rate,
+                             void* stream) {
+  PWG_REQUIRE(y && frames, PWG_ERR_NULL, "zero_tail: NULL pointer");
+  PWG_REQUIRE(((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(frames)) & 3u) == 0, PWG_ERR_BAD_SHAPE,
+              "zero_tail: y and the frames table must be 4-B aligned");
+  PWG_REQUIRE(rate > 0, PWG_ERR_BAD_SHAPE, "zero_tail: rate = %d (columns per frame, >= 1)", rate);
+  const int64_t col_tiles = t > 0 ? (t + 3 + kZeroTailCols - 1) / kZeroTailCols : 0;
+  PWG_REQUIRE(batch >= 1 && batch <= 65535 && channels >= 1 && channels <= 65535 * kZeroTailRows && t >= 1 &&
+                  col_tiles <= 0x7fffffff,
+              PWG_ERR_BAD_SHAPE, "zero_tail: bad shape (batch %d, channels %d, t %lld)", batch, channels, (long long)t);
+  // (the bytes are an upper bound: only the tails are written)
+  ProfScope prof((hipStream_t)stream, "zero_tail_kernel", 0, 4.0 * batch * channels * (double)t);
+  hipLaunchKernelGGL(zero_tail_kernel, dim3((unsigned)col_tiles, (channels + kZeroTailRows - 1) / kZeroTailRows, batch),
+                     dim3(256), 0, (hipStream_t)stream, y, frames, channels, (long)t, rate);
+  PWG_CHECK_LAUNCH("zero_tail");
   return PWG_OK;
 }
 

@@ -35,6 +35,8 @@
 
 #include <stdlib.h>
 
+#include <type_traits>
+
 namespace pwg {
 namespace {
 
@@ -58,6 +60,14 @@ struct RuSplitArgs {
   long part_stride;  // bf16x8 elements per weight part image
   float slope1, slope2, out_div;
 };
+
+// The ragged form: item b ends at column Tv = min(frames[b] * rate, T); T stays the row stride.
+struct RuSplitRaggedArgs : RuSplitArgs {
+  const int* frames;  // (batch,) device table, frames per item
+  int rate;           // columns per frame (a multiple of 4: Tv is one)
+};
+template <bool RAGGED>
+using RuSplitArgsOf = typename std::conditional<RAGGED, RuSplitRaggedArgs, RuSplitArgs>::type;
 
 template <int C>
 struct RuSplitCfg {
@@ -149,8 +159,12 @@ __device__ __forceinline__ int ru_out_slot(int wave_n, int h, int n) {
   return wave_n * 64 + (n / NG) * TILE + 4 * h + 4 * HL * (n % NG);
 }
 
-template <int C, int TILE>
-__global__ __launch_bounds__(256, 2) void resunit_split_kernel(RuSplitArgs a) {
+// RAGGED: x and add2 are zero at the columns >= Tv of their item (the invariant of a ragged forward), so the staging is
+// the plain form's; h is zero outside [0, Tv), the values at columns in [Tv, T) are stored as zeros, and a workgroup
+// whose tile lies at or beyond Tv stores its zeros and returns before it requests or stages anything.  The columns
+// below Tv are formed by the plain form's operations on the plain form's operands: bit for bit the item run alone.
+template <int C, int TILE, bool RAGGED>
+__global__ __launch_bounds__(256, 2) void resunit_split_kernel(RuSplitArgsOf<RAGGED> a) {
   using Cfg = RuSplitCfg<C>;
   constexpr int WAVES_N = Cfg::WAVES_N, ROW = Cfg::ROW, H = Cfg::H;
   constexpr int HL = 64 / TILE, TM = 32 / TILE, TN = 64 / TILE, NREG = TILE * TILE / 64, NG = NREG / 4;
@@ -168,6 +182,17 @@ __global__ __launch_bounds__(256, 2) void resunit_split_kernel(RuSplitArgs a) {
   const int T = a.T;
   const bool pair = a.w2 != nullptr;
   const float* __restrict__ xb = a.x + (size_t)b * C * T;
+  int Tv = T;  // end of the item: what h and the stored values are masked at
+  if constexpr (RAGGED) {
+    const long end = (long)a.frames[b] * a.rate;  // (read once per workgroup; wave-uniform)
+    Tv = end < 0 ? 0 : end < T ? (int)end : T;
+    if (t0 >= Tv) {
+      const int quads = (T - t0 < a.bn_out ? T - t0 : a.bn_out) >> 2;  // t0 < T: the grid covers [0, T)
+      for (int i = tid; i < C * quads; i += 256)
+        *reinterpret_cast<f32x4*>(a.y + ((size_t)b * C + i / quads) * T + t0 + 4 * (i % quads)) = f32x4{0.f, 0.f, 0.f, 0.f};
+      return;
+    }
+  }
 
   // the weight fragments run a row tile ahead of their MFMAs: the first ones of w1 are requested in front of the staging
   const unsigned wrow = wave_m * 32 + r;  // this lane's weight row of tile mi = 0
@@ -247,7 +272,8 @@ __global__ __launch_bounds__(256, 2) void resunit_split_kernel(RuSplitArgs a) {
     ru_request<C, TILE>(wf, a.w2, a.part_stride, wrow, h);  // lands behind the forming of h and both barriers
     if (has2) request_values(a.add2, ad2);                  // (so does add2)
     __syncthreads();  // every wave has read its x columns: the h planes take their place
-    // h = lrelu(acc + b1), zero outside [0, T) (conv2's zero padding), split: a lane owns channels c .. c + 3 of a column
+    // h = lrelu(acc + b1), zero outside [0, Tv) (conv2's zero padding; Tv = T in the plain form), split: a lane owns
+    // channels c .. c + 3 of a column
 #pragma unroll
     for (int mi = 0; mi < TM; ++mi)
 #pragma unroll
@@ -258,7 +284,7 @@ __global__ __launch_bounds__(256, 2) void resunit_split_kernel(RuSplitArgs a) {
         for (int ni = 0; ni < TN; ++ni) {
           const int m = wave_n * 64 + ni * TILE + r;
           const int th = t0 - a.p2 + m;
-          const bool inside = th >= 0 && th < T;
+          const bool inside = th >= 0 && th < Tv;
           float v[4];
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
@@ -329,6 +355,11 @@ __global__ __launch_bounds__(256, 2) void resunit_split_kernel(RuSplitArgs a) {
 #pragma unroll
       for (int n = 0; n < NV; ++n) v[n] = v[n] / a.out_div;
     }
+    if constexpr (RAGGED) {  // Tv is a multiple of 4 (or T): a value lies inside the item or outside it
+#pragma unroll
+      for (int n = 0; n < NV; ++n)
+        if (t[n] >= Tv) v[n] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
 #pragma unroll
     for (int n = 0; n < NV; ++n)
       if (ok[n]) *reinterpret_cast<f32x4*>(a.y + row + t[n]) = v[n];
@@ -371,8 +402,10 @@ static int ru_split_geometry(const pwg_resunit_desc* d, RuSplitGeom* g) {
   return PWG_OK;
 }
 
+template <bool RAGGED>
 static int ru_split_forward(const pwg_resunit_desc* d, const float* x, const void* w1, const float* b1, const void* w2,
-                            const float* b2, const float* add2, float* y, int mfma_shape, hipStream_t stream) {
+                            const float* b2, const float* add2, float* y, int mfma_shape, hipStream_t stream,
+                            const int32_t* frames = nullptr, int rate = 0) {
   RuSplitGeom g;
   const int rc = ru_split_geometry(d, &g);
   if (rc != PWG_OK) return rc;
@@ -387,7 +420,7 @@ static int ru_split_forward(const pwg_resunit_desc* d, const float* x, const voi
   PWG_REQUIRE(mfma_shape == 16 || mfma_shape == 32, PWG_ERR_BAD_SHAPE, "resunit_split_forward: mfma_shape = %d (16 or 32)",
               mfma_shape);
   const int C = d->channels;
-  RuSplitArgs a;
+  RuSplitArgsOf<RAGGED> a;
   a.x = x;
   a.w1 = static_cast<const bf16x8*>(w1);
   a.b1 = b1;
@@ -402,8 +435,10 @@ static int ru_split_forward(const pwg_resunit_desc* d, const float* x, const voi
   // (a window that fits LDS has a few hundred taps: the 32-bit fragment index of split_step_request always holds)
   PWG_REQUIRE(split_image_addressable(a.part_stride * 8), PWG_ERR_UNSUPPORTED, "resunit_split_forward: weight image too large");
   a.slope1 = d->slope1, a.slope2 = d->slope2, a.out_div = d->out_div;
-  void (*kern)(RuSplitArgs) = C == 32 ? (mfma_shape == 32 ? resunit_split_kernel<32, 32> : resunit_split_kernel<32, 16>)
-                                      : (mfma_shape == 32 ? resunit_split_kernel<64, 32> : resunit_split_kernel<64, 16>);
+  if constexpr (RAGGED) a.frames = frames, a.rate = rate;
+  void (*kern)(RuSplitArgsOf<RAGGED>) =
+      C == 32 ? (mfma_shape == 32 ? resunit_split_kernel<32, 32, RAGGED> : resunit_split_kernel<32, 16, RAGGED>)
+              : (mfma_shape == 32 ? resunit_split_kernel<64, 32, RAGGED> : resunit_split_kernel<64, 16, RAGGED>);
   if (g.lds > kConvMaxLds && !lds_limit_is_set(reinterpret_cast<const void*>(kern), g.lds)) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int)g.lds);
@@ -417,8 +452,11 @@ static int ru_split_forward(const pwg_resunit_desc* d, const float* x, const voi
   maybe_poison_lds(stream);
   {
     ProfScope prof(stream,
-                   prof_shape_name("resunit_split_kernel", "resunit_split_kernel B%d C%d T%d k%d d%d pair%d", d->batch, C,
-                                   d->t, d->kernel, d->dilation, d->has_conv2),
+                   RAGGED ? prof_shape_name("resunit_split_ragged_kernel",
+                                            "resunit_split_ragged_kernel B%d C%d T%d k%d d%d pair%d", d->batch, C, d->t,
+                                            d->kernel, d->dilation, d->has_conv2)
+                          : prof_shape_name("resunit_split_kernel", "resunit_split_kernel B%d C%d T%d k%d d%d pair%d",
+                                            d->batch, C, d->t, d->kernel, d->dilation, d->has_conv2),
                    flops, bytes);
     hipLaunchKernelGGL(kern, dim3(g.tiles, d->batch), dim3(256), g.lds, stream, a);
   }
@@ -428,6 +466,14 @@ static int ru_split_forward(const pwg_resunit_desc* d, const float* x, const voi
 
 // MFMA shape of pwg_resunit_split_forward
 constexpr int kDefaultMfmaShape = 16;
+
+// What the ragged form asks beyond the plain one: a value of four samples is stored whole or as zeros
+static int ru_split_ragged_rate(int rate) {
+  PWG_REQUIRE(rate > 0 && (rate & 3) == 0, PWG_ERR_UNSUPPORTED,
+              "resunit_split_ragged: rate = %d (a positive multiple of 4: an item ends between two values of four samples)",
+              rate);
+  return PWG_OK;
+}
 
 }  // namespace
 }  // namespace pwg
@@ -442,11 +488,28 @@ extern "C" int pwg_resunit_split_supported(const pwg_resunit_desc* d) {
 extern "C" int pwg_resunit_split_forward(const pwg_resunit_desc* d, const float* x, const void* w1_split, const float* b1,
                                          const void* w2_split, const float* b2, const float* add2, float* y,
                                          void* stream) {
-  return ru_split_forward(d, x, w1_split, b1, w2_split, b2, add2, y, kDefaultMfmaShape, (hipStream_t)stream);
+  return ru_split_forward<false>(d, x, w1_split, b1, w2_split, b2, add2, y, kDefaultMfmaShape, (hipStream_t)stream);
 }
 
 extern "C" int pwg_resunit_split_forward_cfg(const pwg_resunit_desc* d, const float* x, const void* w1_split,
                                              const float* b1, const void* w2_split, const float* b2, const float* add2,
                                              float* y, int32_t mfma_shape, void* stream) {
-  return ru_split_forward(d, x, w1_split, b1, w2_split, b2, add2, y, mfma_shape, (hipStream_t)stream);
+  return ru_split_forward<false>(d, x, w1_split, b1, w2_split, b2, add2, y, mfma_shape, (hipStream_t)stream);
+}
+
+extern "C" int pwg_resunit_split_ragged_supported(const pwg_resunit_desc* d, int32_t rate) {
+  RuSplitGeom g;
+  return ru_split_geometry(d, &g) == PWG_OK && ru_split_ragged_rate(rate) == PWG_OK ? 1 : 0;
+}
+
+extern "C" int pwg_resunit_split_forward_ragged(const pwg_resunit_desc* d, const float* x, const void* w1_split,
+                                                const float* b1, const void* w2_split, const float* b2,
+                                                const float* add2, float* y, int32_t mfma_shape, const int32_t* frames,
+                                                int32_t rate, void* stream) {
+  PWG_REQUIRE(frames != nullptr, PWG_ERR_NULL, "resunit_split_forward_ragged: NULL frames table");
+  PWG_REQUIRE((reinterpret_cast<uintptr_t>(frames) & 3u) == 0, PWG_ERR_BAD_SHAPE,
+              "resunit_split_forward_ragged: the frames table must be 4-B aligned");
+  const int rc = ru_split_ragged_rate(rate);
+  if (rc != PWG_OK) return rc;
+  return ru_split_forward<true>(d, x, w1_split, b1, w2_split, b2, add2, y, mfma_shape, (hipStream_t)stream, frames, rate);
 }

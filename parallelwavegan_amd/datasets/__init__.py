@@ -1,1 +1,1 @@
-from .audio_mel_dataset import AudioMelDataset, find_files  # noqa: F401
+from .audio_mel_dataset import AudioMelDataset, MelDataset, find_files  # noqa: F401

@@ -78,3 +78,43 @@ class AudioMelDataset(object):
         if self._cache is not None:
             self._cache[idx] = item
         return item
+
+
+class MelDataset(object):
+    """Mel features alone, for decoding (the contract of the reference's ``MelDataset``, audio_mel_dataset.py:500):
+    ``dataset[i]`` is ``mel[T', C] float32`` (``(utt_id, mel)`` with ``return_utt_id``).  ``format="npy"`` reads
+    ``<utt>-feats.npy``, ``format="hdf5"`` the dataset ``feats`` of ``<utt>.h5`` through ``utils.read_hdf5`` (needs
+    h5py); ``mel_query`` / ``mel_load_fn`` override either.  Utterances of at most ``mel_length_threshold`` frames are
+    dropped."""
+
+    def __init__(self, root_dir, mel_query=None, mel_load_fn=None, mel_length_threshold=None, return_utt_id=False,
+                 allow_cache=False, format="npy"):
+        if mel_query is None or mel_load_fn is None:
+            _, default_query, _, default_load = _loaders(format)
+            mel_query, mel_load_fn = mel_query or default_query, mel_load_fn or default_load
+        self.mel_load_fn = mel_load_fn
+        mel_files = find_files(root_dir, mel_query)
+        assert mel_files, f"no file matching {mel_query} under {root_dir}"
+        if mel_length_threshold is not None:
+            kept = [f for f in mel_files if self.mel_load_fn(f).shape[0] > mel_length_threshold]
+            if len(kept) != len(mel_files):
+                logging.warning(f"mel_length_threshold dropped {len(mel_files) - len(kept)} of {len(mel_files)} utterances.")
+            assert kept, f"every utterance of {root_dir} is shorter than the threshold"
+            mel_files = kept
+        self.mel_files = mel_files
+        strip = "-feats" if ".npy" in mel_query else ""
+        self.utt_ids = [os.path.splitext(os.path.basename(f))[0].replace(strip, "") for f in mel_files]
+        self.return_utt_id = return_utt_id
+        self._cache = [None] * len(mel_files) if allow_cache else None
+
+    def __len__(self):
+        return len(self.mel_files)
+
+    def __getitem__(self, idx):
+        if self._cache is not None and self._cache[idx] is not None:
+            return self._cache[idx]
+        mel = np.asarray(self.mel_load_fn(self.mel_files[idx]), dtype=np.float32)
+        item = (self.utt_ids[idx], mel) if self.return_utt_id else mel
+        if self._cache is not None:
+            self._cache[idx] = item
+        return item

@@ -372,10 +372,12 @@ class HiFiGANResidualBlock(torch.nn.Module):
     # operands; admitted classes only) covers the geometry (C = 32 / 64)
     fuse_units = True
 
-    def _unit_one_launch(self, idx, x, accum, out_div):
-        """``(x + convs2[idx](convs1[idx](x)) [+ accum]) [/ out_div]`` as ONE kernel launch, or None when the
-        unit has to run as separate convolutions (training: the intermediate is needed by the backward pass;
-        causal / wide layers: no resident-tile kernel)."""
+    def _unit_route(self, idx, x, accum, out_div):
+        """How ``forward`` runs unit ``idx`` on ``x``: None (separate convolutions: training, where the intermediate is
+        needed by the backward pass; causal / wide layers, which have no resident-tile kernel) or ``(form, desc, d1, d2)``
+        -- ``form``: ``"unit"`` (csrc/resunit_split.hip), ``"pair"`` (two split launches, descriptors ``d1`` / ``d2``) or
+        None (the fp32 unit, csrc/resunit.hip); ``desc``: the unit's descriptor.  One decision for ``forward`` and
+        ``forward_ragged``."""
         act1, conv1 = self.convs1[idx][0], self.convs1[idx][1]
         if (not self.fuse_units or self.use_causal_conv or act1.kind != "leaky_relu" or x.dim() != 3
                 or not x.is_cuda or conv1._needs_grad(x, None if callable(accum) else accum)):
@@ -400,6 +402,7 @@ class HiFiGANResidualBlock(torch.nn.Module):
                                       all(cv.split_exact for cv in convs), all(cv.split_admit_all for cv in convs))
         if form == "unit" and not ops.resunit_split_supported(desc):
             form = None
+        d1 = d2 = None
         if form == "pair":
             b, t = x.shape[0], x.shape[2]
             d1 = conv1.make_desc(b, t, pre_act="leaky_relu", pre_slope=act1.slope, post_act="leaky_relu",
@@ -409,6 +412,17 @@ class HiFiGANResidualBlock(torch.nn.Module):
                 form = None
         if form is None and not ops.resunit_profitable(desc):
             return None
+        return form, desc, d1, d2
+
+    def _unit_one_launch(self, idx, x, accum, out_div):
+        """``(x + convs2[idx](convs1[idx](x)) [+ accum]) [/ out_div]`` as ONE kernel launch (two for the ``"pair"``
+        form), or None when :meth:`_unit_route` sends the unit to its separate convolutions."""
+        route = self._unit_route(idx, x, accum, out_div)
+        if route is None:
+            return None
+        form, desc, d1, d2 = route
+        conv1 = self.convs1[idx][1]
+        conv2 = self.convs2[idx][1] if self.use_additional_convs else None
         if callable(accum):
             accum = accum()  # (resolved as late as possible: it may wait for another stream)
         with torch.no_grad():
@@ -467,6 +481,59 @@ class HiFiGANResidualBlock(torch.nn.Module):
             else:
                 x = conv1(x, pre_act=act1.kind, pre_slope=act1.slope, add1=x,
                           add2=acc() if last else None, out_div=out_div if last else 1.0)
+        return x
+
+    @torch.no_grad()
+    def forward_ragged(self, x, frames, rate, accum=None, out_div=1.0):
+        """``forward`` over a ragged batch (inference): ``frames`` is the device int32 table of frames per
+        item, ``rate`` the columns of ``x`` per frame; ``x`` and ``accum`` are zero past their items' ends and so is the
+        result.  The same modules, order and fused epilogues as ``forward``, serial.  A unit ``forward`` sends to
+        csrc/resunit_split.hip runs that kernel's ragged form where it is covered (``rate % 4 == 0``) and else the chain of
+        split launches it is defined by; the ``"pair"`` form runs its two split launches; the fp32 unit and every unit
+        ``forward`` does not fuse run as their separate convolutions, each with the route it takes on its own.  Every
+        launch but the ragged unit's is followed by ``ops.zero_tail``."""
+        if self.use_causal_conv:
+            raise ValueError("HiFiGANResidualBlock: a causal block has no ragged forward (it streams: stream_forward)")
+        n = len(self.convs1)
+        for idx in range(n):
+            last = idx == n - 1
+            act1, conv1 = self.convs1[idx][0], self.convs1[idx][1]
+            conv2 = self.convs2[idx][1] if self.use_additional_convs else None
+            add2, div = (accum, out_div) if last else (None, 1.0)
+            route = self._unit_route(idx, x, add2, div)
+            form, desc, d1, d2 = route if route is not None else (None,) * 4
+            b1 = None if conv1.bias is None else conv1.bias.detach()
+            b2 = None if (conv2 is None or conv2.bias is None) else conv2.bias.detach()
+            if form == "unit" and not ops.resunit_split_ragged_supported(desc, rate):
+                # the chain of general split launches the unit is defined by (DESIGN.md s9.2: the same bits)
+                slope2 = self.convs2[idx][0].slope if conv2 is not None else act1.slope
+                if conv2 is not None:
+                    d1 = conv1.make_desc(x.shape[0], x.shape[2], pre_act="leaky_relu", pre_slope=act1.slope,
+                                         post_act="leaky_relu", post_slope=slope2)
+                    d2 = conv2.make_desc(x.shape[0], x.shape[2], out_div=div)
+                else:
+                    d1 = conv1.make_desc(x.shape[0], x.shape[2], pre_act="leaky_relu", pre_slope=act1.slope, out_div=div)
+                form = "pair" if all(ops.conv1d_split_supported(dd) for dd in (d1, d2) if dd is not None) else None
+            if form == "unit":
+                x = ops.resunit_forward_split_ragged(desc, x.contiguous(), frames, rate, conv1.packed_weight_split(),
+                                                     b1, None if conv2 is None else conv2.packed_weight_split(), b2,
+                                                     None if add2 is None else add2.contiguous())
+            elif form == "pair":  # the split launches ``forward`` runs, the intermediate zeroed between them
+                x, add2 = x.contiguous(), None if add2 is None else add2.contiguous()
+                if conv2 is None:
+                    y = ops.conv1d_forward_split(d1, x, conv1.packed_weight_split(), b1, x, add2)
+                else:
+                    h = ops.zero_tail(ops.conv1d_forward_split(d1, x, conv1.packed_weight_split(), b1), frames, rate)
+                    y = ops.conv1d_forward_split(d2, h, conv2.packed_weight_split(), b2, x, add2)
+                x = ops.zero_tail(y, frames, rate)
+            elif conv2 is not None:
+                act2 = self.convs2[idx][0]
+                xt = conv1(x, pre_act=act1.kind, pre_slope=act1.slope, post_act=act2.kind, post_slope=act2.slope)
+                ops.zero_tail(xt, frames, rate)
+                x = ops.zero_tail(conv2(xt, add1=x, add2=add2, out_div=div), frames, rate)
+            else:
+                x = ops.zero_tail(conv1(x, pre_act=act1.kind, pre_slope=act1.slope, add1=x, add2=add2, out_div=div),
+                                  frames, rate)
         return x
 
     def stream_layers(self):

@@ -113,6 +113,46 @@ class HiFiGANGenerator(torch.nn.Module):
         act, conv = self.output_conv[0], self.output_conv[1]
         return conv(c, pre_act=act.kind, pre_slope=act.slope, post_act="tanh")
 
+    @torch.no_grad()
+    def forward_ragged(self, c, frames):
+        """``forward`` over utterances of different lengths in one batch (the batched form of the loop of
+        bin/decode.py:214-243 of the reference): ``c`` (B, in_channels, T_max), ``frames`` a device
+        int32 tensor (B,) with ``0 <= frames[b] <= T_max`` (0: an unused item) -> (B, out_channels, T_max *
+        upsample_factor) in which item ``b`` holds, up to ``frames[b] * upsample_factor``, the samples it gives alone,
+        and exact zeros past that.  ``c`` may hold anything past an item's end, NaN included: a copy is zeroed first.
+
+        The same modules, order and fused epilogues as ``forward`` (MRF running sum through ``accum`` / ``out_div``,
+        tanh), serial, no stream forking.  Between two layers item ``b`` of a tensor at ``rate`` columns per frame is
+        exactly zero at every column ``>= frames[b] * rate``, so a zero-padded convolution reads past an item's end what
+        it reads past the end of the item run alone: every convolution takes the route it takes in ``forward`` and is
+        followed by ``ops.zero_tail``; the fused split-operand units mask inside the kernel.  Nothing on the host reads
+        the table, so one captured graph per (B, T_max) serves every set of lengths."""
+        from .. import ops
+
+        if self.use_causal_conv:
+            raise ValueError("HiFiGANGenerator: a causal generator has no ragged forward (it streams in lock step: "
+                             "utils.CausalStream)")
+        ops._require_device(c)
+        if c.dim() != 3:
+            raise ValueError(f"HiFiGANGenerator.forward_ragged: expected (B, in_channels, T_max) features, got "
+                             f"{tuple(c.shape)}")
+        ops._require_frames(frames, c.shape[0], "HiFiGANGenerator.forward_ragged")
+        rate = 1
+        c = self.input_conv(ops.zero_tail(c.clone(), frames, rate))
+        ops.zero_tail(c, frames, rate)
+        nb = self.num_blocks
+        for i in range(self.num_upsamples):
+            act, up = self.upsamples[i][0], self.upsamples[i][1]
+            rate *= up.stride
+            c = ops.zero_tail(up(c, pre_act=act.kind, pre_slope=act.slope), frames, rate)
+            cs = None
+            for j in range(nb):
+                cs = self.blocks[i * nb + j].forward_ragged(c, frames, rate, accum=cs,
+                                                            out_div=float(nb) if j == nb - 1 else 1.0)
+            c = cs
+        act, conv = self.output_conv[0], self.output_conv[1]
+        return ops.zero_tail(conv(c, pre_act=act.kind, pre_slope=act.slope, post_act="tanh"), frames, rate)
+
     def stream_layers(self):
         """``(layer, rate)`` of every causal convolution in the order :meth:`stream_forward` visits them; ``rate``: the
         layer's input columns per mel frame."""

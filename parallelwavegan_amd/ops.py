@@ -591,6 +591,59 @@ def resunit_forward_split(desc, x, w1_split, b1, w2_split=None, b2=None, add2=No
     return out
 
 
+def _require_frames(frames, batch, what):
+    """The device table of a ragged batch: int32 ``(batch,)``, contiguous."""
+    if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
+        raise RuntimeError(f"{what}: the frames table must be a device tensor; there is no CPU fallback path")
+    if frames.dtype != torch.int32 or tuple(frames.shape) != (int(batch),) or not frames.is_contiguous():
+        raise RuntimeError(f"{what}: the frames table must be a contiguous int32 tensor of shape ({int(batch)},), got "
+                           f"{frames.dtype} {tuple(frames.shape)}")
+
+
+def zero_tail(y, frames, rate):
+    """Stores exact zeros at the columns ``>= frames[b] * rate`` of every row of item ``b`` of ``y`` (B, C, T), in place
+    (csrc/elementwise.hip; write-only: the tail may hold anything before).  ``frames``: device int32 ``(B,)``; ``rate``:
+    columns of ``y`` per frame.  Behind any convolution launch it re-establishes the invariant of a ragged forward
+    (DESIGN.md s9.4).  Returns ``y``."""
+    _require_device(y)
+    if y.dim() != 3:
+        raise RuntimeError(f"zero_tail: expected a (B, C, T) tensor, got {tuple(y.shape)}")
+    _require_frames(frames, y.shape[0], "zero_tail")
+    _lib.check(_lib.lib().pwg_zero_tail(_ptr(y), _ptr(frames), y.shape[0], y.shape[1], y.shape[2], int(rate), _stream()),
+               "zero_tail")
+    return y
+
+
+def resunit_split_ragged_supported(desc, rate):
+    """Does the ragged form of the split-operand residual unit cover this geometry at ``rate`` columns per frame?
+    :func:`resunit_split_supported` plus ``rate % 4 == 0``.  Host logic only; ``_lib.lib().pwg_last_error()`` names the
+    reason for a False."""
+    return bool(_lib.lib().pwg_resunit_split_ragged_supported(ctypes.byref(desc), int(rate)))
+
+
+def resunit_forward_split_ragged(desc, x, frames, rate, w1_split, b1, w2_split=None, b2=None, add2=None, out=None,
+                                 mfma_shape=16):
+    """:func:`resunit_forward_split` over a ragged batch: item ``b`` ends at column ``min(frames[b] * rate, T)``.  ``x``
+    and ``add2`` must be zero past their items' ends (:func:`zero_tail`); the output is, per item, bit for bit the plain
+    unit on the item alone up to its end and exact zeros past it.  ``mfma_shape``: as there (16: the default shape)."""
+    _require_device(x, b1, b2, add2, out)
+    for w in (w1_split, w2_split):
+        if w is not None and (not w.is_cuda or w.dtype != torch.uint8):
+            raise RuntimeError("resunit_forward_split_ragged: the weights must be device images of pack_weight_split")
+    _require_frames(frames, desc.batch, "resunit_forward_split_ragged")
+    assert x.numel() == desc.batch * desc.channels * desc.t
+    image_bytes = 6 * desc.kernel * desc.channels * desc.channels  # three bf16 parts of a (C, C, k) weight
+    for w in (w1_split, w2_split):
+        assert w is None or w.numel() == image_bytes, "resunit_forward_split_ragged: not this unit's split image"
+    assert add2 is None or add2.numel() == x.numel()
+    if out is None:
+        out = torch.empty_like(x)
+    _lib.check(_lib.lib().pwg_resunit_split_forward_ragged(
+        ctypes.byref(desc), _ptr(x), _ptr(w1_split), _ptr(b1), _ptr(w2_split), _ptr(b2), _ptr(add2), _ptr(out),
+        int(mfma_shape), _ptr(frames), int(rate), _stream()), "resunit_split_forward_ragged")
+    return out
+
+
 def resstack_supported(channels, t, dilation):
     """Does the one-launch MelGAN residual stack (csrc/resstack.hip) cover this geometry?"""
     return bool(_lib.lib().pwg_resstack_supported(int(channels), int(t), int(dilation)))

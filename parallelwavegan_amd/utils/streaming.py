@@ -13,6 +13,9 @@ convolution kernel picks for the two shapes, <= 1e-5).
 The first / last chunk of an utterance see the model's own zero padding on their outer side, so they
 run without a halo there (they are batched across utterances when their lengths agree).
 
+``RaggedSynthesizer`` batches WHOLE utterances of different lengths of the non-causal HiFi-GAN instead: one forward
+over a padded block with a device table of frames per item, every item exactly what it gives alone.
+
 Everything on the device runs in libpwgkernels.so: feature normalisation + (T', C) -> (C, T')
 transpose, the generator, and the float -> PCM16 conversion.
 
@@ -1262,3 +1265,170 @@ class StreamPool(_Stream):
                 self.frames_out += self.chunk_frames
                 self.samples_out += st.emit[1] - st.emit[0]
         return out
+
+
+RaggedGroup = collections.namedtuple("RaggedGroup", "indices frames t_pad")
+RaggedGroup.__doc__ = """One batched forward of :class:`RaggedSynthesizer`: ``indices`` -- which inputs ride in it, by item;
+``frames`` -- frames per item, ``max_batch`` long (0: an unused item); ``t_pad`` -- the batch's length in frames."""
+RaggedPlan = collections.namedtuple("RaggedPlan", "groups padded_fraction")
+
+
+class RaggedSynthesizer:
+    """Whole utterances of DIFFERENT lengths, ``max_batch`` per forward, each exactly what it gives alone: the batched
+    form of the reference's decode loop (/root/reference/parallel_wavegan/bin/decode.py:214-243) for the non-causal
+    ``HiFiGANGenerator``.
+
+    The utterances are sorted by length and grouped; a group is uploaded once as a ``(max_batch, T_pad, C)`` block,
+    ``T_pad`` its longest length rounded up to ``bucket_frames``, with a device table of frames per item, and runs
+    ``model.forward_ragged``: every layer leaves exact zeros past each item's end, so a short item
+    reads the zero padding it would read alone -- zero mel frames alone would not do that (a hidden layer is not zero
+    where the mel is zero).  Nothing on the host depends on the table, so ``use_graph`` replays ONE graph per
+    ``(max_batch, T_pad)``; a last, partial group is filled with items of 0 frames to reuse it.  ``max_graph_shapes``
+    graphs are kept, least recently used dropped, and all are dropped when the model's parameter state changes.
+    ``precision``: None = the modes ``utils.set_inference_precision`` left on the model, else ``"fp32"`` / ``"bf16"`` for
+    this synthesizer's forwards.
+
+    Only the non-causal ``HiFiGANGenerator`` with one output channel: a reflect-padded MelGAN needs a mirror at each
+    item's own end and Parallel WaveGAN replicates its edge and draws noise; ``ChunkedSynthesizer`` batches the
+    equal-shaped chunks of those."""
+
+    max_graph_shapes = 4  # (max_batch, T_pad) shapes whose graphs are kept (least recently used evicted)
+
+    def __init__(self, model, max_batch=16, bucket_frames=64, use_graph=True, precision=None):
+        from ..models import HiFiGANGenerator
+
+        name = type(model).__name__
+        other = "utils.ChunkedSynthesizer batches the equal-shaped chunks of any mel-only generator"
+        if not isinstance(model, HiFiGANGenerator):
+            raise ValueError(f"RaggedSynthesizer: {name} is not supported (only the non-causal HiFiGANGenerator; {other})")
+        if model.use_causal_conv:
+            raise ValueError(f"RaggedSynthesizer: this {name} is causal (use_causal_conv=True) and has no ragged forward "
+                             f"({other}; utils.CausalStream streams it)")
+        if model.output_conv[1].out_channels != 1:
+            raise ValueError(f"RaggedSynthesizer: this {name} emits {model.output_conv[1].out_channels} channels; an item "
+                             f"returns one waveform ({other})")
+        if precision not in (None, "fp32", "bf16"):
+            raise ValueError(f"RaggedSynthesizer: precision must be None, 'fp32' or 'bf16', got {precision!r}")
+        self.max_batch, self.bucket_frames = int(max_batch), int(bucket_frames)
+        if self.max_batch < 1 or self.bucket_frames < 1:
+            raise ValueError("RaggedSynthesizer: max_batch and bucket_frames must be >= 1")
+        _require_device(next(model.parameters()))  # no CPU fallback
+        self.model = model.eval()
+        self.use_graph = bool(use_graph)
+        self.precision = precision
+        self.up = model.upsample_factor
+        self.channels = model.input_conv.in_channels
+        self.max_frames = (2 ** 31 - 1) // (self.up * model.input_conv.out_channels)  # 32-bit element counts per item
+        self._device = next(model.parameters()).device
+        self._watch = GraphedInference(model)  # (only its parameter-state key is used)
+        self._state = None
+        self._graphs = collections.OrderedDict()
+        self.captures = 0  # graphs captured since construction
+
+    @property
+    def graphs_captured(self):
+        """How many graphs are held now."""
+        return len(self._graphs)
+
+    @staticmethod
+    def plan_groups(lengths, max_batch=16, bucket_frames=64, max_frames=None):
+        """Pure host logic: ``lengths`` (frames per utterance) -> ``RaggedPlan(groups, padded_fraction)``.  The
+        utterances are sorted by length (ties in input order) and cut into groups of ``max_batch``; a group's ``t_pad`` is
+        its longest length rounded up to ``bucket_frames``; a last, partial group is filled with items of 0 frames.
+        ``padded_fraction``: the share of all ``max_batch * t_pad`` frame slots that hold no frame.  ValueError for an
+        empty item and for one longer than ``max_frames``."""
+        lengths = [int(n) for n in lengths]
+        for i, n in enumerate(lengths):
+            if n < 1:
+                raise ValueError(f"RaggedSynthesizer: item {i} is empty ({n} frames)")
+            if max_frames is not None and n > max_frames:
+                raise ValueError(f"RaggedSynthesizer: item {i} has {n} frames, more than one forward holds ({max_frames}; "
+                                 "utils.ChunkedSynthesizer cuts long utterances)")
+        order = sorted(range(len(lengths)), key=lambda i: lengths[i])
+        groups, slots = [], 0
+        for at in range(0, len(order), max_batch):
+            idx = order[at:at + max_batch]
+            t_pad = -(-lengths[idx[-1]] // bucket_frames) * bucket_frames
+            groups.append(RaggedGroup(tuple(idx), tuple(lengths[i] for i in idx) + (0,) * (max_batch - len(idx)), t_pad))
+            slots += max_batch * t_pad
+        return RaggedPlan(groups, 1.0 - sum(lengths) / slots if slots else 0.0)
+
+    def plan(self, lengths):
+        """:meth:`plan_groups` with this synthesizer's ``max_batch``, ``bucket_frames`` and ``max_frames``."""
+        return self.plan_groups(lengths, self.max_batch, self.bucket_frames, self.max_frames)
+
+    def _forward(self, c, frames):
+        from .precision import inference_precision
+
+        with inference_precision(self.model, self.precision):
+            return self.model.forward_ragged(c, frames)
+
+    def _capture(self, c, frames):
+        static_c, static_frames = c.clone(), frames.clone()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(2):  # fills the weight caches / sets kernel attributes outside the capture
+                self._forward(static_c, static_frames)
+        torch.cuda.current_stream().wait_stream(side)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            static_out = self._forward(static_c, static_frames)
+        self.captures += 1
+        return graph, static_c, static_frames, static_out
+
+    def _run(self, c, frames):
+        """The ragged forward of one group -> (max_batch, 1, T_pad * up); in graph mode the graph's own output buffer."""
+        if not self.use_graph:
+            return self._forward(c, frames)
+        from .precision import inference_precision
+
+        with inference_precision(self.model, self.precision):
+            state = self._watch._param_state()
+        if state != self._state:
+            self._graphs.clear()  # the parameters changed: a replay would use the old weight images
+            self._state = state
+        key = tuple(c.shape)
+        entry = self._graphs.pop(key, None)
+        if entry is None:
+            while len(self._graphs) >= self.max_graph_shapes:
+                self._graphs.popitem(last=False)  # least recently used shape
+            entry = self._capture(c, frames)
+        self._graphs[key] = entry  # most recently used last
+        graph, static_c, static_frames, static_out = entry
+        static_c.copy_(c, non_blocking=True)
+        static_frames.copy_(frames, non_blocking=True)
+        graph.replay()
+        return static_out
+
+    @torch.no_grad()
+    def _synthesize(self, feats, normalize_before, convert):
+        if normalize_before and not (hasattr(self.model, "mean") and hasattr(self.model, "scale")):
+            raise ValueError("RaggedSynthesizer: normalize_before=True needs model.register_stats(...)")
+        mean = self.model.mean if normalize_before else None
+        scale = self.model.scale if normalize_before else None
+        feats = [torch.as_tensor(f, dtype=torch.float32).cpu() for f in feats]
+        for i, f in enumerate(feats):
+            if f.dim() != 2 or f.shape[1] != self.channels:
+                raise ValueError(f"RaggedSynthesizer: item {i}: expected (T, {self.channels}) features, got "
+                                 f"{tuple(f.shape)}")
+        outs = [None] * len(feats)
+        for group in self.plan([f.shape[0] for f in feats]).groups:
+            block = torch.zeros((self.max_batch, group.t_pad, self.channels)).pin_memory()  # one padded upload per group
+            for j, i in enumerate(group.indices):
+                block[j, :feats[i].shape[0]] = feats[i]
+            frames = torch.tensor(group.frames, dtype=torch.int32).pin_memory()
+            c = normalize_transpose(block.to(self._device, non_blocking=True), mean, scale)
+            y = convert(self._run(c, frames.to(self._device, non_blocking=True)))
+            for j, i in enumerate(group.indices):
+                outs[i] = y[j, 0, :feats[i].shape[0] * self.up].clone()  # (the graph's buffer is written again)
+        return outs
+
+    def synthesize_many(self, feats, normalize_before=False):
+        """feats: list of ``(T_i, C)`` tensors / arrays -> list of ``(T_i * upsample_factor,)`` fp32 device tensors, in
+        input order.  ValueError for an empty or over-long item."""
+        return self._synthesize(feats, normalize_before, lambda y: y)
+
+    def synthesize_many_pcm16(self, feats, normalize_before=False):
+        """:meth:`synthesize_many` through the float -> PCM16 conversion on the device: int16 tensors."""
+        return self._synthesize(feats, normalize_before, to_pcm16)

@@ -1,0 +1,177 @@
+"""16 utterances of different lengths through HiFi-GAN V1: ``utils.RaggedSynthesizer`` against the other ways to run
+them, alternating in one process.  GPU box only.
+usage: bench_ragged.py [--precision fp32|bf16] [--json FILE]
+Contenders, each timed as one call over the whole list with a host clock that stops after a device synchronisation
+(uploads and the slicing of the results included), ROUNDS rounds x REPS calls, alternating:
+  ragged16 / ragged8  RaggedSynthesizer.synthesize_many, max_batch 16 (one group) / 8 (two groups), graphs captured
+  chunked             ChunkedSynthesizer.synthesize_many (chunk_frames 256, max_batch 16), graphs captured
+  chunked_cold        the same from a new ChunkedSynthesizer, i.e. with its captures: a fresh set of lengths keeps it cold
+  inference           16 model.inference calls
+and, on the padded (16, T_pad) block of ragged16, graph replays alone (device events):
+  forward_graph       the plain forward (wrong past each item's end: zero mel frames are not zero padding)
+  ragged_graph        forward_ragged
+Their gap is what exactness costs on the device; the library's profiler (eager runs, per kernel family) splits it into
+the zero_tail launches, the fp32 units that run as separate convolutions, the ragged split units against the plain ones
+and the rest: the launches both forwards share, which read zeros past an item's end in the ragged one."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+from parallelwavegan_amd import ops
+from parallelwavegan_amd.graphs import GraphedInference
+from parallelwavegan_amd.models import HiFiGANGenerator
+from parallelwavegan_amd.utils import ChunkedSynthesizer, RaggedSynthesizer, set_inference_precision
+from parallelwavegan_amd.utils.streaming import receptive_field_frames
+
+LENGTHS = [200, 237, 281, 318, 352, 395, 431, 476, 512, 548, 590, 633, 671, 714, 762, 800]  # mel frames
+ROUNDS, REPS, COLD_RUNS = 5, 3, 3
+
+
+def wall_ms(fn, reps):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / reps * 1e3
+
+
+def event_ms(fn, reps):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def families(prof):
+    return {k: dict(launches=int(v["launches"]), ms=float(v["ms"])) for k, v in sorted(prof.results.items())}
+
+
+def split_gap(fam_plain, fam_ragged):
+    """The profiler's kernel time of forward_ragged minus forward's, in its parts (ms)."""
+    def ms(fam, name):
+        return fam.get(name, dict(ms=0.0))["ms"]
+
+    total = lambda fam: sum(v["ms"] for v in fam.values())  # noqa: E731
+    parts = dict(
+        zero_tail=ms(fam_ragged, "zero_tail_kernel"),
+        # the fp32 units (csrc/resunit.hip) run as two convolutions on the fp32 MFMA kernel
+        fp32_units_as_convolutions=ms(fam_ragged, "conv1d_mfma_dma_kernel") - ms(fam_plain, "conv1d_mfma_dma_kernel")
+        - ms(fam_plain, "resunit_kernel"),
+        # the ragged split units against the plain ones: the masks, less the tiles past an item's end that only store zeros
+        ragged_units=ms(fam_ragged, "resunit_split_ragged_kernel") - ms(fam_plain, "resunit_split_kernel"))
+    parts["same_launches_on_zero_tails"] = total(fam_ragged) - total(fam_plain) - sum(parts.values())
+    return parts
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--precision", default="fp32", choices=("fp32", "bf16"))
+    ap.add_argument("--json", default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_ragged.py measures on an MI355X: no device visible")
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    model = HiFiGANGenerator()
+    model.remove_weight_norm()
+    model = model.to(dev).eval()
+    if args.precision == "bf16":
+        set_inference_precision(model, "bf16")
+    gen = torch.Generator().manual_seed(1)
+    feats = [torch.randn(n, 80, generator=gen) for n in LENGTHS]
+    up = model.upsample_factor
+
+    ragged = {16: RaggedSynthesizer(model, max_batch=16, bucket_frames=64),
+              8: RaggedSynthesizer(model, max_batch=8, bucket_frames=64)}
+    halo = receptive_field_frames(model)
+    chunked = ChunkedSynthesizer(model, chunk_frames=256, max_batch=16, halo=halo)
+
+    def inference():
+        with torch.no_grad():
+            return [model.inference(f.to(dev)).reshape(-1) for f in feats]
+
+    def chunked_cold():
+        return ChunkedSynthesizer(model, chunk_frames=256, max_batch=16, halo=halo).synthesize_many(feats)
+
+    runs = {"ragged16": lambda: ragged[16].synthesize_many(feats), "ragged8": lambda: ragged[8].synthesize_many(feats),
+            "chunked": lambda: chunked.synthesize_many(feats), "inference": inference}
+    # what the contenders compute: every utterance against model.inference
+    ref = inference()
+    diffs = {n: max(float((y - r).abs().max()) for y, r in zip(fn(), ref)) for n, fn in runs.items()}
+    for fn in runs.values():  # warm: graphs captured, weight images cached
+        fn()
+    ms = {n: [] for n in runs}
+    for _ in range(ROUNDS):
+        for n, fn in runs.items():
+            ms[n].append(wall_ms(fn, REPS))
+    ms["chunked_cold"] = [wall_ms(chunked_cold, 1) for _ in range(COLD_RUNS)]
+
+    # the device cost of exactness on the padded block of ragged16
+    plan = ragged[16].plan(LENGTHS)
+    t_pad = plan.groups[0].t_pad
+    c = torch.randn(16, 80, t_pad, device=dev)
+    frames = torch.tensor(plan.groups[0].frames, dtype=torch.int32, device=dev)
+    plain_graph = GraphedInference(model)
+    plain_graph(c)
+    ragged[16]._run(c, frames)
+    dev_ms = {"forward_graph": [], "ragged_graph": []}
+    for _ in range(ROUNDS):
+        dev_ms["forward_graph"].append(event_ms(lambda: plain_graph(c), REPS))
+        dev_ms["ragged_graph"].append(event_ms(lambda: ragged[16]._run(c, frames), REPS))
+    with torch.no_grad():
+        model(c), model.forward_ragged(c, frames)
+        with ops.profile() as prof_plain:
+            model(c)
+        with ops.profile() as prof_ragged:
+            model.forward_ragged(c, frames)
+    fam_plain, fam_ragged = families(prof_plain), families(prof_ragged)
+    zero_tail = fam_ragged.get("zero_tail_kernel", dict(launches=0, ms=0.0))
+    kernels_plain = sum(v["ms"] for v in fam_plain.values())
+    kernels_ragged = sum(v["ms"] for v in fam_ragged.values())
+
+    def summary(v):
+        return dict(median=statistics.median(v), min=min(v), max=max(v), runs=v)
+
+    audio_s = sum(LENGTHS) * up / 22050.0
+    out = dict(model="HiFi-GAN V1", precision=args.precision, lengths=LENGTHS, frames_total=sum(LENGTHS),
+               weights="N(0, 0.01) initialisation (HiFiGANGenerator()), weight norm removed; the differences against "
+                       "model.inference are on waveforms of small amplitude and say only that the paths agree",
+               audio_seconds_at_22050=audio_s, rounds=ROUNDS, reps=REPS,
+               padded_fraction={k: ragged[k].plan(LENGTHS).padded_fraction for k in ragged},
+               t_pad={k: [g.t_pad for g in ragged[k].plan(LENGTHS).groups] for k in ragged},
+               wall_ms_per_list={n: summary(v) for n, v in ms.items()},
+               max_abs_vs_inference=diffs,
+               padded_block=dict(shape=[16, 80, t_pad], device_ms={n: summary(v) for n, v in dev_ms.items()},
+                                 launches=dict(forward=sum(v["launches"] for v in fam_plain.values()),
+                                               forward_ragged=sum(v["launches"] for v in fam_ragged.values())),
+                                 profiler_ms=dict(forward=kernels_plain, forward_ragged=kernels_ragged,
+                                                  zero_tail_launches=zero_tail["launches"],
+                                                  gap=split_gap(fam_plain, fam_ragged)),
+                                 families=dict(forward=fam_plain, forward_ragged=fam_ragged)))
+    for n, v in ms.items():
+        print(f"{n:13s} {statistics.median(v):8.2f} ms per list  [{min(v):8.2f} .. {max(v):8.2f}]  "
+              f"max |y - inference| {diffs.get(n, float('nan')):.2e}")
+    for n, v in dev_ms.items():
+        print(f"{n:13s} {statistics.median(v):8.2f} ms per replay [{min(v):8.2f} .. {max(v):8.2f}]  (16 x {t_pad} frames)")
+    print(f"profiler (eager): forward {kernels_plain:.2f} ms in {out['padded_block']['launches']['forward']} launches; "
+          f"forward_ragged {kernels_ragged:.2f} ms in {out['padded_block']['launches']['forward_ragged']} launches, "
+          f"{zero_tail['launches']} of them zero_tail; the gap in parts: "
+          + ", ".join(f"{k} {v:+.2f}" for k, v in out["padded_block"]["profiler_ms"]["gap"].items()))
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(out, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
