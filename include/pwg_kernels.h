@@ -580,6 +580,20 @@ int pwg_resstack_pack_weight(int32_t channels, const float* w1, const float* sca
 int pwg_resstack_forward(int32_t batch, int32_t channels, int32_t t, int32_t dilation, float slope, const float* x,
                          const float* w_packed, const float* b1, const float* b2, const float* bs, float* y, float* h,
                          void* stream);
+/* The ragged form (inference; ResidualStack.forward of layers/residual_stack.py:75-85 inside the batched form of the
+ * decode loop of bin/decode.py:214-243): frames device int32 (batch,), item b is the sequence [0, tb),
+ * tb = min(frames[b] * rate, t), inside a row of stride t.  The reflection (ReflectionPad1d of
+ * layers/residual_stack.py:49) mirrors at tb, nothing at or past tb is read (x may hold anything there, NaN included),
+ * the columns >= tb of y are stored as 0.0f, and a workgroup whose tile lies at or past tb only stores zeros.  For
+ * tb % 4 == 0, tb >= 64, tb > dilation the columns < tb of y are bit for bit pwg_resstack_forward on the item alone with
+ * t = tb; with every item at t the output is the plain call's.  h is not written.  Nothing on the host reads the table:
+ * a captured launch serves every set of lengths.  pwg_resstack_ragged_supported is pwg_resstack_supported plus
+ * rate >= 4, rate % 4 == 0 (pure host logic).  A NULL or misaligned table, such a rate and everything the plain call
+ * refuses are refused with a message before any launch.  Additive: pwg_abi_version() stays 15. */
+int pwg_resstack_ragged_supported(int32_t channels, int32_t t, int32_t dilation, int32_t rate);
+int pwg_resstack_forward_ragged(int32_t batch, int32_t channels, int32_t t, int32_t dilation, float slope, const float* x,
+                                const float* w_packed, const float* b1, const float* b2, const float* bs, float* y,
+                                const int32_t* frames, int32_t rate, void* stream);
 /* Data gradient of the same unit in ONE launch (the backward of the three convolutions' data paths and of both
  * LeakyReLUs, layers/residual_stack.py:45-85 under autograd), in the padded domain of the dilated convolution:
  *   dh[t]  = lrelu'(h[t]) * (W2^T dy)[t]                                              (batch, channels, t)
@@ -963,6 +977,15 @@ int pwg_normalize_transpose(const float* x, const float* mean, const float* scal
  * launching nothing: NULL or misaligned (4 B) y / frames, rate <= 0, batch outside 1 .. 65535. */
 int pwg_zero_tail(float* y, const int32_t* frames, int32_t batch, int32_t channels, int64_t t, int32_t rate,
                   void* stream);
+/* pwg_zero_tail with the mirror the next reflect-padded consumer reads (the per-item ReflectionPad1d of
+ * models/melgan.py:71,136 and layers/residual_stack.py:49 inside the batched form of the loop of
+ * bin/decode.py:214-243): with e = min(frames[b] * rate, t), column e + j (0 <= j < pad, e + j < t) receives
+ * y[b][c][e - 2 - j] and every column >= e + pad receives 0.0f; in place (sources lie below e, destinations at or
+ * above it).  pad = 0 stores what pwg_zero_tail stores; e = 0 zeroes the item; a source index below 0 (e <= pad:
+ * reflection is undefined) is clamped to 0 -- unspecified values, no access outside the tensor.  Refused as
+ * pwg_zero_tail refuses, plus pad < 0.  Additive: pwg_abi_version() stays 15. */
+int pwg_mirror_tail(float* y, const int32_t* frames, int32_t batch, int32_t channels, int64_t t, int32_t rate,
+                    int32_t pad, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* Pooling / explicit padding                                                  */

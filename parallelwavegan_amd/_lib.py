@@ -210,6 +210,9 @@ SIGNATURES = {
     "pwg_resstack_packed_weight_floats": (ctypes.c_size_t, [_i32]),
     "pwg_resstack_pack_weight": (ctypes.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pwg_resstack_forward": (ctypes.c_int, [_i32, _i32, _i32, _i32, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pwg_resstack_ragged_supported": (ctypes.c_int, [_i32, _i32, _i32, _i32]),
+    "pwg_resstack_forward_ragged": (ctypes.c_int, [_i32, _i32, _i32, _i32, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                   _i32, _vp]),
     "pwg_resstack_pack_weight_bwd": (ctypes.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pwg_resstack_backward_data": (ctypes.c_int, [_i32, _i32, _i32, _i32, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pwg_wavenet_layer_supported": (ctypes.c_int, [ctypes.POINTER(WaveNetDesc)]),
@@ -257,6 +260,7 @@ SIGNATURES = {
                                        _vp]),
     "pwg_normalize_transpose": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "pwg_zero_tail": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i64, _i32, _vp]),
+    "pwg_mirror_tail": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i64, _i32, _i32, _vp]),
     "pwg_weight_norm_backward": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "pwg_spectral_norm_forward": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp]),
     "pwg_spectral_norm_forward_saved": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp]),

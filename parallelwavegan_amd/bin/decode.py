@@ -2,7 +2,8 @@
 of the reference's ``bin/decode.py`` (its mel -> waveform case, decode.py:158-248) on the HIP kernels.
 
 A non-causal HiFi-GAN checkpoint is decoded ``--batch-size`` utterances per forward through
-``utils.RaggedSynthesizer`` -- every utterance exactly what ``model.inference`` gives for it alone (DESIGN.md s9.4);
+``utils.RaggedSynthesizer`` -- every utterance exactly what ``model.inference`` gives for it alone --
+and a non-causal, reflect-padded (multi-band) MelGAN checkpoint through ``utils.MelGANRaggedSynthesizer`` (s9.5);
 every other supported generator runs the reference's loop over ``model.inference`` (decode.py:214-243).  The float ->
 int16 step is ``utils.to_pcm16`` on the device and the files are written with the standard library's ``wave`` module.
 The RTF is timed after a device synchronisation; the reference stops its clock without one.
@@ -50,9 +51,21 @@ def _parser():
     p.add_argument("--normalize-before", default=False, action="store_true",
                    help="normalise the features with the registered statistics before the model")
     p.add_argument("--batch-size", default=16, type=int,
-                   help="utterances per forward of a non-causal HiFi-GAN (utils.RaggedSynthesizer; default 16)")
+                   help="utterances per forward of a non-causal HiFi-GAN or MelGAN (utils.RaggedSynthesizer / "
+                        "utils.MelGANRaggedSynthesizer; default 16)")
     p.add_argument("--verbose", type=int, default=1, help="logging level; higher is more logging")
     return p
+
+
+def _melgan_is_ragged(model):
+    """Does ``utils.MelGANRaggedSynthesizer`` take this ``MelGANGenerator``: non-causal, every padding a
+    ``ReflectionPad1d``, and one waveform per item (one output channel, or sub-bands with the PQMF ``load_model``
+    attached)?"""
+    try:
+        walk = model._ragged_walk()
+    except ValueError:
+        return False
+    return walk[-1][0].out_channels == 1 or getattr(model, "pqmf", None) is not None
 
 
 def main(argv=None):
@@ -60,8 +73,8 @@ def main(argv=None):
     import yaml
 
     from ..datasets import MelDataset
-    from ..models import HiFiGANGenerator
-    from ..utils import RaggedSynthesizer, load_model
+    from ..models import HiFiGANGenerator, MelGANGenerator
+    from ..utils import MelGANRaggedSynthesizer, RaggedSynthesizer, load_model
     from ..utils.streaming import to_pcm16
 
     args = _parser().parse_args(argv)
@@ -106,10 +119,12 @@ def main(argv=None):
 
     ragged = isinstance(model, HiFiGANGenerator) and not model.use_causal_conv \
         and model.output_conv[1].out_channels == 1
+    ragged_melgan = isinstance(model, MelGANGenerator) and _melgan_is_ragged(model)
     total_rtf, n_done = 0.0, 0
-    if ragged:
-        synth = RaggedSynthesizer(model, max_batch=args.batch_size)
-        logging.info(f"{gtype}: {args.batch_size} utterances of their own lengths per forward (RaggedSynthesizer).")
+    if ragged or ragged_melgan:
+        synth = (RaggedSynthesizer if ragged else MelGANRaggedSynthesizer)(model, max_batch=args.batch_size)
+        logging.info(f"{gtype}: {args.batch_size} utterances of their own lengths per forward "
+                     f"({type(synth).__name__}).")
         # one call per batch_size utterances in dump order: the host holds that many utterances at a time
         for at in range(0, len(dataset), args.batch_size):
             items = [dataset[i] for i in range(at, min(at + args.batch_size, len(dataset)))]

@@ -882,6 +882,36 @@ __global__ __launch_bounds__(256) void zero_tail_kernel(float* y, const int* fra
   }
 }
 
+// zero_tail with the mirror a reflect-padded consumer reads: for e = min(frames[b] * rate, t) the
+// columns e + j, 0 <= j < pad, receive y[b][c][e - 2 - j] -- ReflectionPad1d's image of the item's own last columns
+// (x[e-1+i] = x[e-1-i], i = j + 1) -- and every column >= e + pad receives 0.0f.  The sources lie below e and the
+// destinations at or above it, so the launch is safe in place.  A source index below 0 (an item not longer than pad,
+// for which reflection is undefined) is clamped to 0: the values are unspecified, no access leaves the tensor.  The
+// workgroups and the column shift are zero_tail_kernel's; pad = 0 stores exactly what that kernel stores.
+__global__ __launch_bounds__(256) void mirror_tail_kernel(float* y, const int* frames, int channels, long t, int rate,
+                                                          int pad) {
+  const int b = blockIdx.z;
+  long tv = (long)frames[b] * rate;
+  tv = tv < 0 ? 0 : tv < t ? tv : t;
+  const long s0 = (long)blockIdx.x * kZeroTailCols;
+  if (tv >= t || tv >= s0 + kZeroTailCols) return;
+  const long zero_from = tv > 0 ? tv + pad : 0;  // (an empty item has nothing to mirror: all zeros)
+  const int row_end = min((int)(blockIdx.y + 1) * kZeroTailRows, channels);
+  for (int row = blockIdx.y * kZeroTailRows; row < row_end; ++row) {
+    float* p = y + ((long)b * channels + row) * t;
+    const long lo = s0 + 4 * (long)threadIdx.x - (long)((reinterpret_cast<uintptr_t>(p) >> 2) & 3);
+    if (lo >= zero_from && lo + 4 <= t) {
+      *reinterpret_cast<float4*>(p + lo) = make_float4(0.f, 0.f, 0.f, 0.f);
+    } else {
+      const long hi = lo + 4 < t ? lo + 4 : t;
+      for (long col = lo > tv ? lo : tv; col < hi; ++col) {
+        const long src = 2 * tv - 2 - col;  // = tv - 2 - j, j = col - tv
+        p[col] = col < zero_from ? p[src > 0 ? src : 0] : 0.f;
+      }
+    }
+  }
+}
+
 }  // namespace pwg
 
 using namespace pwg;
@@ -1269,6 +1299,25 @@ extern "C" int pwg_zero_tail(float* y, const int32_t* frames, int32_t batch, int
   hipLaunchKernelGGL(zero_tail_kernel, dim3((unsigned)col_tiles, (channels + kZeroTailRows - 1) / kZeroTailRows, batch),
                      dim3(256), 0, (hipStream_t)stream, y, frames, channels, (long)t, rate);
   PWG_CHECK_LAUNCH("zero_tail");
+  return PWG_OK;
+}
+
+extern "C" int pwg_mirror_tail(float* y, const int32_t* frames, int32_t batch, int32_t channels, int64_t t, int32_t rate,
+                               int32_t pad, void* stream) {
+  PWG_REQUIRE(y && frames, PWG_ERR_NULL, "mirror_tail: NULL pointer");
+  PWG_REQUIRE(((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(frames)) & 3u) == 0, PWG_ERR_BAD_SHAPE,
+              "mirror_tail: y and the frames table must be 4-B aligned");
+  PWG_REQUIRE(rate > 0, PWG_ERR_BAD_SHAPE, "mirror_tail: rate = %d (columns per frame, >= 1)", rate);
+  PWG_REQUIRE(pad >= 0, PWG_ERR_BAD_SHAPE, "mirror_tail: pad = %d (mirror columns, >= 0)", pad);
+  const int64_t col_tiles = t > 0 ? (t + 3 + kZeroTailCols - 1) / kZeroTailCols : 0;
+  PWG_REQUIRE(batch >= 1 && batch <= 65535 && channels >= 1 && channels <= 65535 * kZeroTailRows && t >= 1 &&
+                  col_tiles <= 0x7fffffff,
+              PWG_ERR_BAD_SHAPE, "mirror_tail: bad shape (batch %d, channels %d, t %lld)", batch, channels, (long long)t);
+  // (the bytes are an upper bound: only the tails are written)
+  ProfScope prof((hipStream_t)stream, "mirror_tail_kernel", 0, 4.0 * batch * channels * (double)t);
+  hipLaunchKernelGGL(mirror_tail_kernel, dim3((unsigned)col_tiles, (channels + kZeroTailRows - 1) / kZeroTailRows, batch),
+                     dim3(256), 0, (hipStream_t)stream, y, frames, channels, (long)t, rate, pad);
+  PWG_CHECK_LAUNCH("mirror_tail");
   return PWG_OK;
 }
 

@@ -22,10 +22,14 @@
 //     C =  48: 2 x 6, N = 192,  84 KB (rows 48..63 of the second row block are zero weights).
 // (Measured against 6-wave workgroups with N = 64 / 96, two per CU: C96 178 -> 133 us, C48 122 -> 110 us per unit at B64.)
 // HBM traffic of a unit: x read once, y written once (+ h written once in training) instead of seven passes.
+// The forward kernel has a ragged instantiation (inference): every item of the batch is a sequence of
+// its own length inside a row of stride T, read from a device table.
 #include "common.h"
 
 #include <stdint.h>
 #include <stdlib.h>
+
+#include <type_traits>
 
 namespace pwg {
 
@@ -46,6 +50,14 @@ struct ResStackArgs {
   int xw4;  // 16-B pieces staged per x row
   float slope;
 };
+
+// The ragged form: item b ends at column Tb = min(frames[b] * rate, T); T stays the row stride.
+struct ResStackRaggedArgs : ResStackArgs {
+  const int* frames;  // (batch,) device table, frames per item
+  int rate;           // columns per frame (a multiple of 4: Tb is one)
+};
+template <bool RAGGED>
+using ResStackArgsOf = typename std::conditional<RAGGED, ResStackRaggedArgs, ResStackArgs>::type;
 
 template <int C>
 struct RsCfg {
@@ -117,8 +129,13 @@ __device__ __forceinline__ void rs_contract(const float* __restrict__ al, const 
   }
 }
 
-template <int C>
-__global__ __launch_bounds__(64 * RsCfg<C>::NW, 1) void resstack_kernel(ResStackArgs a) {
+// RAGGED: the sequence of item b is [0, Tb) inside a row of stride T.  The staging mirrors at Tb and reads nothing at or
+// past it, so x may hold anything there; the columns in [Tb, T) of y are stored as zeros, and a workgroup whose tile lies
+// at or past Tb stores its zeros and returns before it stages anything or meets a barrier (b and t0 are uniform per
+// workgroup).  The columns below Tb are formed by the plain form's operations on the x tile the plain form stages for
+// the item alone with T = Tb: the same bits.  h is not written (inference only).
+template <int C, bool RAGGED>
+__global__ __launch_bounds__(64 * RsCfg<C>::NW, 1) void resstack_kernel(ResStackArgsOf<RAGGED> a) {
   using Cfg = RsCfg<C>;
   constexpr int NG = Cfg::NG, N = Cfg::N, NW = Cfg::NW, XS = Cfg::XS, CP = Cfg::CP;
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -134,12 +151,25 @@ __global__ __launch_bounds__(64 * RsCfg<C>::NW, 1) void resstack_kernel(ResStack
   const int t0 = blockIdx.x * N;
   const int f0 = t0 - a.hl;  // sample of x-tile column 0
   const int T = a.T;
+  int Tb = T;  // end of the sequence: where the staging mirrors and what the stored values are masked at
+  if constexpr (RAGGED) {
+    const long end = (long)a.frames[b] * a.rate;  // (read once per workgroup)
+    Tb = __builtin_amdgcn_readfirstlane(end < 0 ? 0 : end < T ? (int)end : T);
+    if (t0 >= Tb) {
+      const int quads = (T - t0 < N ? T - t0 : N) >> 2;  // t0 < T: the grid covers [0, T); T and N are multiples of 4
+      for (int i = tid; i < C * quads; i += 64 * NW) {
+        float* p = a.y + ((long)b * C + i / quads) * T + t0 + 4 * (i % quads);  // (4-B aligned: scalar stores)
+        p[0] = 0.f, p[1] = 0.f, p[2] = 0.f, p[3] = 0.f;
+      }
+      return;
+    }
+  }
 
   // ---- stage the x tile
   const float* xb = a.x + (long)b * C * T;
   __amdgpu_buffer_rsrc_t x_rs = uniform_buffer_rsrc(xb, (unsigned)(C * T) * 4u);
   const int XW = a.xw4 * 4;
-  if (__builtin_amdgcn_readfirstlane((f0 >= 0 && f0 + XW <= T) ? 1 : 0)) {
+  if (__builtin_amdgcn_readfirstlane((f0 >= 0 && f0 + XW <= Tb) ? 1 : 0)) {
     for (int r = wave; r < C; r += NW)
       if (lane < a.xw4) {
         const unsigned off = (unsigned)(r * T + f0 + 4 * lane) * 4u;
@@ -147,14 +177,15 @@ __global__ __launch_bounds__(64 * RsCfg<C>::NW, 1) void resstack_kernel(ResStack
       }
   } else {
     // first / last tiles of a sequence: 4-B pieces, reflected source index (ReflectionPad1d: x[-j] = x[j],
-    // x[T-1+j] = x[T-1-j]); columns that are neither inside the sequence nor a reflection of it read zero
+    // x[Tb-1+j] = x[Tb-1-j]; Tb = T in the plain form); columns that are neither inside the sequence nor a reflection of
+    // it read zero
     for (int r = wave; r < C; r += NW)
       for (int i0 = 0; i0 < XW; i0 += 64) {
         const int j = i0 + lane;
         int f = f0 + j;
         if (f < 0) f = -f;
-        if (f >= T) f = 2 * (T - 1) - f;
-        const unsigned off = (j < XW && f >= 0 && f < T) ? (unsigned)(r * T + f) * 4u : 0xFFFFFFFCu;
+        if (f >= Tb) f = 2 * (Tb - 1) - f;
+        const unsigned off = (j < XW && f >= 0 && f < Tb) ? (unsigned)(r * T + f) * 4u : 0xFFFFFFFCu;
         if (j < XW) __builtin_amdgcn_raw_ptr_buffer_load_lds(x_rs, (lds_ptr_t)(xs + r * XS + i0), 4, off, 0, 0, 0);
       }
   }
@@ -191,7 +222,8 @@ __global__ __launch_bounds__(64 * RsCfg<C>::NW, 1) void resstack_kernel(ResStack
     if (c < C) {
       const float v = acc[r] + bias[r];
       hs[c * N + m] = v;
-      if (a.h != nullptr && t_ok) a.h[((long)b * C + c) * T + t0 + m] = v;
+      if constexpr (!RAGGED)
+        if (a.h != nullptr && t_ok) a.h[((long)b * C + c) * T + t0 + m] = v;
     }
     acc[r] = 0.f;
   }
@@ -209,7 +241,7 @@ __global__ __launch_bounds__(64 * RsCfg<C>::NW, 1) void resstack_kernel(ResStack
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int c = wm * 32 + 8 * (r >> 2) + 4 * lhi + (r & 3);
-      if (c < C) a.y[((long)b * C + c) * T + t0 + m] = acc[r] + bias[r];
+      if (c < C) a.y[((long)b * C + c) * T + t0 + m] = t0 + m < Tb ? acc[r] + bias[r] : 0.f;  // (plain: Tb = T, t_ok)
     }
   }
 }
@@ -498,9 +530,19 @@ int pwg_resstack_pack_weight(int32_t channels, const float* w1, const float* sca
   return PWG_OK;
 }
 
-int pwg_resstack_forward(int32_t batch, int32_t channels, int32_t t, int32_t dilation, float slope, const float* x,
-                         const float* w_packed, const float* b1, const float* b2, const float* bs, float* y, float* h,
-                         void* stream_) {
+}  // extern "C"
+
+// What the ragged form asks beyond the plain one: an item ends on a multiple of 4 columns, as T does
+static int resstack_ragged_rate(int rate) {
+  PWG_REQUIRE(rate >= 4 && (rate & 3) == 0, PWG_ERR_UNSUPPORTED,
+              "resstack_ragged: rate = %d (a positive multiple of 4: an item ends where a row of T %% 4 == 0 may end)", rate);
+  return PWG_OK;
+}
+
+template <bool RAGGED>
+static int resstack_forward(int32_t batch, int32_t channels, int32_t t, int32_t dilation, float slope, const float* x,
+                            const float* w_packed, const float* b1, const float* b2, const float* bs, float* y, float* h,
+                            void* stream_, const int32_t* frames = nullptr, int rate = 0) {
   PWG_REQUIRE(x && w_packed && y, PWG_ERR_NULL, "resstack_forward: null pointer");
   PWG_REQUIRE(x != y && x != h, PWG_ERR_BAD_SHAPE, "resstack_forward: y / h must not alias x (tiles read their neighbours' halo)");
   int hl, xw4;
@@ -513,10 +555,13 @@ int pwg_resstack_forward(int32_t batch, int32_t channels, int32_t t, int32_t dil
   // dilations, and conv1d.hip's interior tiles use the same instruction at arbitrary 4-B offsets.  Round 4 demanded a
   // 16-B aligned base here without need; tests/test_resstack_gpu.py runs both kernels on a base that is only 4-B aligned.)
   hipStream_t stream = (hipStream_t)stream_;
-  ResStackArgs a;
+  ResStackArgsOf<RAGGED> a;
   a.x = x; a.w = w_packed; a.b1 = b1; a.b2 = b2; a.bs = bs; a.y = y; a.h = h;
   a.T = t; a.d = dilation; a.hl = hl; a.xw4 = xw4; a.slope = slope;
-  void (*kern)(ResStackArgs) = channels == 48 ? resstack_kernel<48> : channels == 96 ? resstack_kernel<96> : resstack_kernel<192>;
+  if constexpr (RAGGED) a.frames = frames, a.rate = rate;
+  void (*kern)(ResStackArgsOf<RAGGED>) = channels == 48   ? resstack_kernel<48, RAGGED>
+                                         : channels == 96 ? resstack_kernel<96, RAGGED>
+                                                          : resstack_kernel<192, RAGGED>;
   const int n = channels == 48 ? RsCfg<48>::N : channels == 96 ? RsCfg<96>::N : RsCfg<192>::N;
   const int xs = n + 56;
   const int nw = channels == 48 ? RsCfg<48>::NW : channels == 96 ? RsCfg<96>::NW : RsCfg<192>::NW;
@@ -529,13 +574,42 @@ int pwg_resstack_forward(int32_t batch, int32_t channels, int32_t t, int32_t dil
   const double elems = (double)batch * C * t;
   maybe_poison_lds(stream);
   {
-    ProfScope prof(stream, prof_shape_name("resstack_kernel", "resstack_kernel B%d C%d T%d d%d save%d", batch, channels, t,
-                                           dilation, h != nullptr),
+    // (the ragged form's figures are upper bounds: a tile past its item's end only stores zeros)
+    ProfScope prof(stream,
+                   RAGGED ? prof_shape_name("resstack_ragged_kernel", "resstack_ragged_kernel B%d C%d T%d d%d", batch,
+                                            channels, t, dilation)
+                          : prof_shape_name("resstack_kernel", "resstack_kernel B%d C%d T%d d%d save%d", batch, channels, t,
+                                            dilation, h != nullptr),
                    2.0 * elems * C * 5, 4.0 * (elems * (2 + (h != nullptr)) + 5 * C * C));
     hipLaunchKernelGGL(kern, dim3(ceil_div(t, n), batch), dim3(64 * nw), lds, stream, a);
   }
   PWG_CHECK_LAUNCH("resstack_forward");
   return PWG_OK;
+}
+
+extern "C" {
+
+int pwg_resstack_forward(int32_t batch, int32_t channels, int32_t t, int32_t dilation, float slope, const float* x,
+                         const float* w_packed, const float* b1, const float* b2, const float* bs, float* y, float* h,
+                         void* stream) {
+  return resstack_forward<false>(batch, channels, t, dilation, slope, x, w_packed, b1, b2, bs, y, h, stream);
+}
+
+int pwg_resstack_ragged_supported(int32_t channels, int32_t t, int32_t dilation, int32_t rate) {
+  int hl, xw4;
+  return resstack_geometry(channels, t, dilation, &hl, &xw4) && resstack_ragged_rate(rate) == PWG_OK ? 1 : 0;
+}
+
+int pwg_resstack_forward_ragged(int32_t batch, int32_t channels, int32_t t, int32_t dilation, float slope, const float* x,
+                                const float* w_packed, const float* b1, const float* b2, const float* bs, float* y,
+                                const int32_t* frames, int32_t rate, void* stream) {
+  PWG_REQUIRE(frames != nullptr, PWG_ERR_NULL, "resstack_forward_ragged: NULL frames table");
+  PWG_REQUIRE((reinterpret_cast<uintptr_t>(frames) & 3u) == 0, PWG_ERR_BAD_SHAPE,
+              "resstack_forward_ragged: the frames table must be 4-B aligned");
+  const int rc = resstack_ragged_rate(rate);
+  if (rc != PWG_OK) return rc;
+  return resstack_forward<true>(batch, channels, t, dilation, slope, x, w_packed, b1, b2, bs, y, nullptr, stream, frames,
+                                rate);
 }
 
 int pwg_resstack_pack_weight_bwd(int32_t channels, const float* w1, const float* scale1, const float* w2, const float* scale2,

@@ -123,6 +123,58 @@ class ResidualStack(torch.nn.Module):
         t = conv0(c, pre_act=a0.kind, pre_slope=a0.slope)
         return conv1(t, pre_act=a1.kind, pre_slope=a1.slope, add1=skip)
 
+    # ---- utterances of different lengths in one batch (MelGANGenerator.forward_ragged)
+    def ragged_fuses(self, rate):
+        """Does :meth:`forward_ragged` run this stack as the ragged form of the one-launch unit at ``rate`` columns per
+        frame, for every batch of at least 64 columns?  Pure host logic over the module geometry (what ``_unit_ok`` asks
+        of the modules, and ``ops.resstack_ragged_supported`` at a covered length)."""
+        if self.use_causal_conv or not self.fuse_unit:
+            return False
+        a0, a1 = self.stack[0], self.stack[3]
+        conv0, conv1, skip = self.unit_convs()
+        if any(cv.has_spectral_norm or cv.groups != 1 or cv.stride != 1 for cv in (conv0, conv1, skip)):
+            return False
+        if (conv0.kernel_size != 3 or conv0.pad_mode != "reflect" or conv0.padding != conv0.dilation
+                or conv0.padding_right != conv0.dilation or conv1.kernel_size != 1 or skip.kernel_size != 1):
+            return False
+        if a0.kind != "leaky_relu" or a1.kind != "leaky_relu" or a0.slope != a1.slope or not 0.0 < a0.slope < 1.0:
+            return False
+        ch = conv0.in_channels
+        if any(cv.in_channels != ch or cv.out_channels != ch for cv in (conv0, conv1, skip)):
+            return False
+        return ops.resstack_ragged_supported(ch, 64, conv0.dilation, rate)
+
+    @torch.no_grad()
+    def forward_ragged(self, x, frames, rate):
+        """``forward`` over a ragged batch (inference): ``frames`` is the device int32 table of frames per
+        item, ``rate`` the columns of ``x`` per frame; item ``b`` is the sequence ``[0, frames[b] * rate)`` of its rows and
+        the reflection mirrors at its end.  Returns ``(y, tail)``: ``tail`` is 0 when ``y`` holds exact zeros past every
+        item's end and None when it holds unspecified values there.
+
+        Where :meth:`ragged_fuses` the stack is ONE launch of the ragged unit (csrc/resstack.hip): it reads nothing
+        past an item's end, so ``x`` may hold anything there, and it stores zeros there (``tail`` 0).  Otherwise the three
+        launches of ``forward``: ``ops.mirror_tail`` first writes the dilated convolution's ``dilation`` mirror columns
+        behind every item IN PLACE into ``x`` (the caller's intermediate; the columns must fit inside the buffer, the
+        slack rule of ``MelGANGenerator.forward_ragged``); ``tail`` None."""
+        if self.use_causal_conv:
+            raise ValueError("ResidualStack: a causal stack has no ragged forward (it streams: stream_forward)")
+        a0, conv0, a1, conv1 = self.stack[0], self.stack[2], self.stack[3], self.stack[4]
+        if conv0.pad_mode != "reflect":
+            raise ValueError(f"ResidualStack: pad = {self.stack[1].__class__.__name__}; only a ReflectionPad1d stack has "
+                             "a ragged forward (ops.mirror_tail writes the mirror of every item's own end)")
+        ops._require_device(x)
+        x = x.contiguous()
+        if self.ragged_fuses(rate):
+            if not ops.resstack_ragged_supported(x.shape[1], x.shape[2], conv0.dilation, rate):
+                raise ValueError(f"ResidualStack.forward_ragged: {x.shape[2]} columns per item; the one-launch unit covers "
+                                 "64 columns and more (below 4 GB per item): pad the batch")
+            bias = [None if cv.bias is None else cv.bias.detach() for cv in (conv0, conv1, self.skip_layer)]
+            return ops.resstack_forward_ragged(x, frames, rate, self.unit_image(), conv0.dilation, a0.slope, *bias), 0
+        ops.mirror_tail(x, frames, rate, conv0.padding)
+        skip = self.skip_layer(x)
+        t = conv0(x, pre_act=a0.kind, pre_slope=a0.slope)
+        return conv1(t, pre_act=a1.kind, pre_slope=a1.slope, add1=skip), None
+
     def stream_layers(self):
         """The causal convolutions that keep history (the 1 x 1 layers have none)."""
         return [self.stack[1]]

@@ -219,6 +219,91 @@ class MelGANGenerator(torch.nn.Module, _MelGANNormMixin):
             x = walk.run(m, x, **kw)
         return x
 
+    # ---- utterances of different lengths in one batch (utils.MelGANRaggedSynthesizer)
+    def _ragged_walk(self):
+        """``(module, pending activation, is last convolution, rate of its input)`` of the modules that compute, in
+        ``forward`` order; ValueError for a causal generator and for a ``pad`` other than ``ReflectionPad1d``."""
+        if isinstance(self.melgan[0], CausalConv1d):
+            raise ValueError("MelGANGenerator: a causal generator has no ragged forward (it streams in lock step: "
+                             "utils.CausalStream)")
+        for m in self.melgan:
+            if isinstance(m, FusedPad) and m.mode != "reflect":
+                raise ValueError(f"MelGANGenerator: pad = {m.__class__.__name__} ({m.mode}); only a ReflectionPad1d model "
+                                 "has a ragged forward (ops.mirror_tail writes the mirror of every item's own end)")
+        rate, out = 1, []
+        for m, act, last in self._lookahead_walk():
+            out.append((m, act, last, rate))
+            if isinstance(m, ConvTranspose1d):
+                rate *= m.stride
+        return out
+
+    @property
+    def ragged_min_frames(self):
+        """The shortest item of :meth:`forward_ragged`: every reflect-padded layer needs more columns than its padding
+        (``layers.causal_conv.mirrored_min_frames`` of :meth:`lookahead_plan`; 4 for a first layer of kernel 7).  Pure
+        host logic."""
+        from ..layers.causal_conv import mirrored_min_frames
+
+        return mirrored_min_frames(self.lookahead_plan())
+
+    @property
+    def ragged_slack_frames(self):
+        """Frames that :meth:`forward_ragged` needs free behind an item shorter than the batch: the largest
+        ``ceil(pad / rate)`` over the launches that read the mirror columns ``ops.mirror_tail`` wrote -- the first and the
+        last convolution, and the dilated convolution of every stack that runs as three launches
+        (``ResidualStack.ragged_fuses`` False).  3 for every released geometry (the first layer's ``(7 - 1) / 2`` at rate
+        1).  Pure host logic."""
+        slack = 0
+        for m, _, _, rate in self._ragged_walk():
+            if isinstance(m, ResidualStack):
+                pad = 0 if m.ragged_fuses(rate) else m.unit_convs()[0].padding
+            else:
+                pad = 0 if m.transposed else m.padding
+            slack = max(slack, -(-pad // rate))
+        return slack
+
+    @torch.no_grad()
+    def forward_ragged(self, c, frames):
+        """``forward`` over utterances of different lengths in one batch (the batched form of the loop of
+        bin/decode.py:214-243 of the reference): ``c`` (B, in_channels, T_max), ``frames`` a device
+        int32 tensor (B,) -> (B, out_channels, T_max * upsample_factor) in which item ``b`` holds, up to ``frames[b] *
+        upsample_factor``, the samples (sub-band columns) it gives alone, and exact zeros past that -- what the
+        zero-padded ``PQMF.synthesis`` needs.  ``c`` is not written and may hold anything past an item's end, NaN
+        included: a copy gets the mirror.
+
+        Every ``ReflectionPad1d`` must reflect at each item's own end.  Between two launches an item holds, past its
+        end, the ``pad`` mirror columns its next consumer reads and exact zeros after those: a reflect-padded convolution
+        on the general kernel reads an input on which ``ops.mirror_tail(pad = its padding)`` has run, a transposed
+        convolution one with a zero tail (``pad = 0``), a 1 x 1 convolution needs nothing, and the ragged residual
+        stack (csrc/resstack.hip) mirrors at the item's end itself, reads nothing past it and leaves zeros behind it.
+        For the ``multi_band_melgan.v2`` geometry that is one launch per stack and four ``mirror_tail`` launches.
+
+        The general kernel reflects at ``T_max``, so the mirror columns must fit inside the buffer.  Each item has
+        ``frames[b] == 0`` (unused: all zeros), ``frames[b] == T_max``, or ``ragged_min_frames <= frames[b] <= T_max -
+        ragged_slack_frames``.  The table lives on the device, so this is NOT checked here (no sync; one captured graph
+        per (B, T_max) serves every set of lengths): ``utils.MelGANRaggedSynthesizer`` guarantees it."""
+        from .. import ops
+
+        walk = self._ragged_walk()  # ValueError: causal, a pad other than reflection
+        ops._require_device(c)
+        if c.dim() != 3:
+            raise ValueError(f"MelGANGenerator.forward_ragged: expected (B, in_channels, T_max) features, got "
+                             f"{tuple(c.shape)}")
+        ops._require_frames(frames, c.shape[0], "MelGANGenerator.forward_ragged")
+        x, tail = c.clone(), None  # tail: the mirror columns x holds past every item's end (0: zeros; None: anything)
+        for m, act, last, rate in walk:
+            if isinstance(m, ResidualStack):
+                x, tail = m.forward_ragged(x, frames, rate)
+                continue
+            pad = 0 if m.transposed else m.padding
+            if (m.transposed or m.kernel_size > 1) and tail != pad:
+                ops.mirror_tail(x, frames, rate, pad)
+            kw = dict(pre_act=act.kind, pre_slope=act.slope) if act is not None else {}
+            if last and self.use_final_nonlinear_activation:
+                kw["post_act"] = "tanh"
+            x, tail = m(x, **kw), None
+        return ops.mirror_tail(x, frames, self.upsample_factor, 0)
+
     def register_stats(self, stats):
         from ..utils import load_stats
 

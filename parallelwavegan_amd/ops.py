@@ -614,6 +614,21 @@ def zero_tail(y, frames, rate):
     return y
 
 
+def mirror_tail(y, frames, rate, pad):
+    """:func:`zero_tail` with the mirror a reflect-padded consumer reads (csrc/elementwise.hip), in place:
+    with ``e = frames[b] * rate`` the columns ``e + j``, ``0 <= j < pad``, of item ``b`` receive ``y[b, :, e - 2 - j]``
+    (``ReflectionPad1d``'s image of the item's own last columns) and every column ``>= e + pad`` an exact zero.
+    ``pad = 0`` is :func:`zero_tail`; an item of 0 frames becomes all zeros; an item not longer than ``pad`` gets
+    unspecified mirror values (reflection is undefined for it).  Returns ``y``."""
+    _require_device(y)
+    if y.dim() != 3:
+        raise RuntimeError(f"mirror_tail: expected a (B, C, T) tensor, got {tuple(y.shape)}")
+    _require_frames(frames, y.shape[0], "mirror_tail")
+    _lib.check(_lib.lib().pwg_mirror_tail(_ptr(y), _ptr(frames), y.shape[0], y.shape[1], y.shape[2], int(rate), int(pad),
+                                          _stream()), "mirror_tail")
+    return y
+
+
 def resunit_split_ragged_supported(desc, rate):
     """Does the ragged form of the split-operand residual unit cover this geometry at ``rate`` columns per frame?
     :func:`resunit_split_supported` plus ``rate % 4 == 0``.  Host logic only; ``_lib.lib().pwg_last_error()`` names the
@@ -671,6 +686,30 @@ def resstack_forward(x, w_packed, dilation, slope, b1=None, b2=None, bs=None, sa
     _lib.check(_lib.lib().pwg_resstack_forward(b, c, t, int(dilation), float(slope), _ptr(x), _ptr(w_packed), _ptr(b1), _ptr(b2),
                                                _ptr(bs), _ptr(y), _ptr(h), _stream()), "resstack_forward")
     return y, h
+
+
+def resstack_ragged_supported(channels, t, dilation, rate):
+    """Does the ragged form of the one-launch residual stack cover this geometry at ``rate`` columns per frame?
+    :func:`resstack_supported` plus ``rate >= 4`` and ``rate % 4 == 0``.  Host logic only."""
+    return bool(_lib.lib().pwg_resstack_ragged_supported(int(channels), int(t), int(dilation), int(rate)))
+
+
+def resstack_forward_ragged(x, frames, rate, w_packed, dilation, slope, b1=None, b2=None, bs=None, out=None):
+    """:func:`resstack_forward` over a ragged batch (inference: no ``h``): item ``b`` is the sequence ``[0, frames[b] *
+    rate)`` of its rows, the reflection mirrors at its end, ``x`` may hold anything past it, and ``y`` holds exact zeros
+    there.  Per item bit for bit the plain unit on the item alone."""
+    _require_device(x, w_packed, b1, b2, bs, out)
+    if x.dim() != 3 or not x.is_contiguous():
+        raise RuntimeError(f"resstack_forward_ragged: expected a contiguous (B, C, T) tensor, got {tuple(x.shape)}")
+    b, c, t = x.shape
+    _require_frames(frames, b, "resstack_forward_ragged")
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.shape == x.shape and out.is_contiguous()
+    _lib.check(_lib.lib().pwg_resstack_forward_ragged(b, c, t, int(dilation), float(slope), _ptr(x), _ptr(w_packed),
+                                                      _ptr(b1), _ptr(b2), _ptr(bs), _ptr(out), _ptr(frames), int(rate),
+                                                      _stream()), "resstack_forward_ragged")
+    return out
 
 
 def resstack_pack_weight_bwd(w1, s1, w2, s2, ws, ss):

@@ -1,4 +1,4 @@
 from .utils import *  # noqa: F401,F403
 from .precision import get_inference_precision, set_inference_precision  # noqa: E402,F401
 from .streaming import (CausalStream, ChunkedSynthesizer, LookaheadStream, MelGANLookaheadStream,  # noqa: E402,F401
-                        PWGLookaheadStream, PWGStream, RaggedSynthesizer, StreamPool)
+                        MelGANRaggedSynthesizer, PWGLookaheadStream, PWGStream, RaggedSynthesizer, StreamPool)

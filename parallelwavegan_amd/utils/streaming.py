@@ -1273,52 +1273,27 @@ RaggedGroup.__doc__ = """One batched forward of :class:`RaggedSynthesizer`: ``in
 RaggedPlan = collections.namedtuple("RaggedPlan", "groups padded_fraction")
 
 
-class RaggedSynthesizer:
-    """Whole utterances of DIFFERENT lengths, ``max_batch`` per forward, each exactly what it gives alone: the batched
-    form of the reference's decode loop (/root/reference/parallel_wavegan/bin/decode.py:214-243) for the non-causal
-    ``HiFiGANGenerator``.
-
-    The utterances are sorted by length and grouped; a group is uploaded once as a ``(max_batch, T_pad, C)`` block,
-    ``T_pad`` its longest length rounded up to ``bucket_frames``, with a device table of frames per item, and runs
-    ``model.forward_ragged`` (DESIGN.md s9.4): every layer leaves exact zeros past each item's end, so a short item
-    reads the zero padding it would read alone -- zero mel frames alone would not do that (a hidden layer is not zero
-    where the mel is zero).  Nothing on the host depends on the table, so ``use_graph`` replays ONE graph per
-    ``(max_batch, T_pad)``; a last, partial group is filled with items of 0 frames to reuse it.  ``max_graph_shapes``
-    graphs are kept, least recently used dropped, and all are dropped when the model's parameter state changes.
-    ``precision``: None = the modes ``utils.set_inference_precision`` left on the model, else ``"fp32"`` / ``"bf16"`` for
-    this synthesizer's forwards.
-
-    Only the non-causal ``HiFiGANGenerator`` with one output channel: a reflect-padded MelGAN needs a mirror at each
-    item's own end and Parallel WaveGAN replicates its edge and draws noise; ``ChunkedSynthesizer`` batches the
-    equal-shaped chunks of those."""
+class _RaggedSynthesizer:
+    """What :class:`RaggedSynthesizer` and :class:`MelGANRaggedSynthesizer` share: the plan, one padded upload per group,
+    one graph per ``(max_batch, T_pad)`` and the recapture when the parameters change.  A subclass checks its model, calls
+    :meth:`_setup` and gives :meth:`_forward`."""
 
     max_graph_shapes = 4  # (max_batch, T_pad) shapes whose graphs are kept (least recently used evicted)
+    precision = None
 
-    def __init__(self, model, max_batch=16, bucket_frames=64, use_graph=True, precision=None):
-        from ..models import HiFiGANGenerator
-
-        name = type(model).__name__
-        other = "utils.ChunkedSynthesizer batches the equal-shaped chunks of any mel-only generator"
-        if not isinstance(model, HiFiGANGenerator):
-            raise ValueError(f"RaggedSynthesizer: {name} is not supported (only the non-causal HiFiGANGenerator; {other})")
-        if model.use_causal_conv:
-            raise ValueError(f"RaggedSynthesizer: this {name} is causal (use_causal_conv=True) and has no ragged forward "
-                             f"({other}; utils.CausalStream streams it)")
-        if model.output_conv[1].out_channels != 1:
-            raise ValueError(f"RaggedSynthesizer: this {name} emits {model.output_conv[1].out_channels} channels; an item "
-                             f"returns one waveform ({other})")
-        if precision not in (None, "fp32", "bf16"):
-            raise ValueError(f"RaggedSynthesizer: precision must be None, 'fp32' or 'bf16', got {precision!r}")
+    def _setup(self, model, max_batch, bucket_frames, use_graph, channels, samples_per_frame, widest_row, min_frames=1,
+               slack_frames=0):
+        name = type(self).__name__
         self.max_batch, self.bucket_frames = int(max_batch), int(bucket_frames)
         if self.max_batch < 1 or self.bucket_frames < 1:
-            raise ValueError("RaggedSynthesizer: max_batch and bucket_frames must be >= 1")
+            raise ValueError(f"{name}: max_batch and bucket_frames must be >= 1")
         _require_device(next(model.parameters()))  # no CPU fallback
         self.model = model.eval()
         self.use_graph = bool(use_graph)
-        self.precision = precision
-        self.up = model.upsample_factor
-        self.channels = model.input_conv.in_channels
-        self.max_frames = (2 ** 31 - 1) // (self.up * model.input_conv.out_channels)  # 32-bit element counts per item
+        self.up = int(samples_per_frame)
+        self.channels = int(channels)
+        self.min_frames, self.slack_frames = int(min_frames), int(slack_frames)
+        self.max_frames = (2 ** 31 - 1) // int(widest_row) - self.slack_frames  # 32-bit element counts per item
         self._device = next(model.parameters()).device
         self._watch = GraphedInference(model)  # (only its parameter-state key is used)
         self._state = None
@@ -1331,37 +1306,41 @@ class RaggedSynthesizer:
         return len(self._graphs)
 
     @staticmethod
-    def plan_groups(lengths, max_batch=16, bucket_frames=64, max_frames=None):
+    def plan_groups(lengths, max_batch=16, bucket_frames=64, max_frames=None, min_frames=1, slack_frames=0,
+                    who="RaggedSynthesizer"):
         """Pure host logic: ``lengths`` (frames per utterance) -> ``RaggedPlan(groups, padded_fraction)``.  The
         utterances are sorted by length (ties in input order) and cut into groups of ``max_batch``; a group's ``t_pad`` is
-        its longest length rounded up to ``bucket_frames``; a last, partial group is filled with items of 0 frames.
+        its longest length + ``slack_frames`` (the room a reflect-padded model's mirror columns need behind an item,
+        DESIGN.md s9.5) rounded up to ``bucket_frames``; a last, partial group is filled with items of 0 frames.
         ``padded_fraction``: the share of all ``max_batch * t_pad`` frame slots that hold no frame.  ValueError for an
-        empty item and for one longer than ``max_frames``."""
+        empty item, for one shorter than ``min_frames`` and for one longer than ``max_frames``."""
         lengths = [int(n) for n in lengths]
         for i, n in enumerate(lengths):
             if n < 1:
-                raise ValueError(f"RaggedSynthesizer: item {i} is empty ({n} frames)")
+                raise ValueError(f"{who}: item {i} is empty ({n} frames)")
+            if n < min_frames:
+                raise ValueError(f"{who}: item {i} has {n} frames, fewer than reflection can pad ({min_frames})")
             if max_frames is not None and n > max_frames:
-                raise ValueError(f"RaggedSynthesizer: item {i} has {n} frames, more than one forward holds ({max_frames}; "
+                raise ValueError(f"{who}: item {i} has {n} frames, more than one forward holds ({max_frames}; "
                                  "utils.ChunkedSynthesizer cuts long utterances)")
         order = sorted(range(len(lengths)), key=lambda i: lengths[i])
         groups, slots = [], 0
         for at in range(0, len(order), max_batch):
             idx = order[at:at + max_batch]
-            t_pad = -(-lengths[idx[-1]] // bucket_frames) * bucket_frames
+            t_pad = -(-(lengths[idx[-1]] + slack_frames) // bucket_frames) * bucket_frames
             groups.append(RaggedGroup(tuple(idx), tuple(lengths[i] for i in idx) + (0,) * (max_batch - len(idx)), t_pad))
             slots += max_batch * t_pad
         return RaggedPlan(groups, 1.0 - sum(lengths) / slots if slots else 0.0)
 
     def plan(self, lengths):
-        """:meth:`plan_groups` with this synthesizer's ``max_batch``, ``bucket_frames`` and ``max_frames``."""
-        return self.plan_groups(lengths, self.max_batch, self.bucket_frames, self.max_frames)
+        """:meth:`plan_groups` with this synthesizer's ``max_batch``, ``bucket_frames``, ``max_frames``, ``min_frames``
+        and ``slack_frames``."""
+        return self.plan_groups(lengths, self.max_batch, self.bucket_frames, self.max_frames, self.min_frames,
+                                self.slack_frames, type(self).__name__)
 
     def _forward(self, c, frames):
-        from .precision import inference_precision
-
-        with inference_precision(self.model, self.precision):
-            return self.model.forward_ragged(c, frames)
+        """The ragged forward of one group -> (max_batch, 1, T_pad * up), whatever it holds past an item's end."""
+        raise NotImplementedError
 
     def _capture(self, c, frames):
         static_c, static_frames = c.clone(), frames.clone()
@@ -1404,13 +1383,13 @@ class RaggedSynthesizer:
     @torch.no_grad()
     def _synthesize(self, feats, normalize_before, convert):
         if normalize_before and not (hasattr(self.model, "mean") and hasattr(self.model, "scale")):
-            raise ValueError("RaggedSynthesizer: normalize_before=True needs model.register_stats(...)")
+            raise ValueError(f"{type(self).__name__}: normalize_before=True needs model.register_stats(...)")
         mean = self.model.mean if normalize_before else None
         scale = self.model.scale if normalize_before else None
         feats = [torch.as_tensor(f, dtype=torch.float32).cpu() for f in feats]
         for i, f in enumerate(feats):
             if f.dim() != 2 or f.shape[1] != self.channels:
-                raise ValueError(f"RaggedSynthesizer: item {i}: expected (T, {self.channels}) features, got "
+                raise ValueError(f"{type(self).__name__}: item {i}: expected (T, {self.channels}) features, got "
                                  f"{tuple(f.shape)}")
         outs = [None] * len(feats)
         for group in self.plan([f.shape[0] for f in feats]).groups:
@@ -1425,10 +1404,109 @@ class RaggedSynthesizer:
         return outs
 
     def synthesize_many(self, feats, normalize_before=False):
-        """feats: list of ``(T_i, C)`` tensors / arrays -> list of ``(T_i * upsample_factor,)`` fp32 device tensors, in
-        input order.  ValueError for an empty or over-long item."""
+        """feats: list of ``(T_i, C)`` tensors / arrays -> list of ``(T_i * up,)`` fp32 device tensors, in input order
+        (``up``: samples per frame).  ValueError for an empty, too short or over-long item."""
         return self._synthesize(feats, normalize_before, lambda y: y)
 
     def synthesize_many_pcm16(self, feats, normalize_before=False):
         """:meth:`synthesize_many` through the float -> PCM16 conversion on the device: int16 tensors."""
         return self._synthesize(feats, normalize_before, to_pcm16)
+
+
+class RaggedSynthesizer(_RaggedSynthesizer):
+    """Whole utterances of DIFFERENT lengths, ``max_batch`` per forward, each exactly what it gives alone: the batched
+    form of the reference's decode loop (/root/reference/parallel_wavegan/bin/decode.py:214-243) for the non-causal
+    ``HiFiGANGenerator``.
+
+    The utterances are sorted by length and grouped; a group is uploaded once as a ``(max_batch, T_pad, C)`` block,
+    ``T_pad`` its longest length rounded up to ``bucket_frames``, with a device table of frames per item, and runs
+    ``model.forward_ragged`` (DESIGN.md s9.4): every layer leaves exact zeros past each item's end, so a short item
+    reads the zero padding it would read alone -- zero mel frames alone would not do that (a hidden layer is not zero
+    where the mel is zero).  Nothing on the host depends on the table, so ``use_graph`` replays ONE graph per
+    ``(max_batch, T_pad)``; a last, partial group is filled with items of 0 frames to reuse it.  ``max_graph_shapes``
+    graphs are kept, least recently used dropped, and all are dropped when the model's parameter state changes.
+    ``precision``: None = the modes ``utils.set_inference_precision`` left on the model, else ``"fp32"`` / ``"bf16"`` for
+    this synthesizer's forwards.
+
+    Only the non-causal ``HiFiGANGenerator`` with one output channel: a reflect-padded MelGAN needs a mirror at each
+    item's own end (:class:`MelGANRaggedSynthesizer`) and Parallel WaveGAN replicates its edge and draws noise;
+    ``ChunkedSynthesizer`` batches the equal-shaped chunks of those."""
+
+    def __init__(self, model, max_batch=16, bucket_frames=64, use_graph=True, precision=None):
+        from ..models import HiFiGANGenerator
+
+        name = type(model).__name__
+        other = "utils.ChunkedSynthesizer batches the equal-shaped chunks of any mel-only generator"
+        if not isinstance(model, HiFiGANGenerator):
+            raise ValueError(f"RaggedSynthesizer: {name} is not supported (only the non-causal HiFiGANGenerator; {other})")
+        if model.use_causal_conv:
+            raise ValueError(f"RaggedSynthesizer: this {name} is causal (use_causal_conv=True) and has no ragged forward "
+                             f"({other}; utils.CausalStream streams it)")
+        if model.output_conv[1].out_channels != 1:
+            raise ValueError(f"RaggedSynthesizer: this {name} emits {model.output_conv[1].out_channels} channels; an item "
+                             f"returns one waveform ({other})")
+        if precision not in (None, "fp32", "bf16"):
+            raise ValueError(f"RaggedSynthesizer: precision must be None, 'fp32' or 'bf16', got {precision!r}")
+        self.precision = precision
+        self._setup(model, max_batch, bucket_frames, use_graph, model.input_conv.in_channels, model.upsample_factor,
+                    model.upsample_factor * model.input_conv.out_channels)
+
+    def _forward(self, c, frames):
+        from .precision import inference_precision
+
+        with inference_precision(self.model, self.precision):
+            return self.model.forward_ragged(c, frames)
+
+
+class MelGANRaggedSynthesizer(_RaggedSynthesizer):
+    """:class:`RaggedSynthesizer` for the non-causal, reflect-padded ``MelGANGenerator``, ``multi_band_melgan.v2``
+    included: the same interface, plan, graphs and recapture, on ``model.forward_ragged``, which mirrors
+    every ``ReflectionPad1d`` at each item's own end.  fp32 only (MelGAN has no bf16 mode).
+
+    ``T_pad`` is the smallest multiple of ``bucket_frames`` that is at least the group's longest length +
+    ``model.ragged_slack_frames`` (the mirror columns behind an item must fit inside the buffer), and an item shorter
+    than ``model.ragged_min_frames`` (4 for kernel 7) is a ValueError naming it -- the reference raises for it too (a
+    reflection longer than its input).  With that every item of a group meets what ``forward_ragged`` asks of the
+    table: 0, or ``min_frames <= n <= T_pad - slack``.
+
+    Multi-band (``model.pqmf`` attached, as ``utils.load_model`` attaches it): ``pqmf.synthesis`` runs once per group
+    on the sub-bands, which are exact zeros past each item's end -- the zero padding the synthesis filter applies to the
+    item alone -- and an item returns ``T_i * upsample_factor * subbands`` samples; a plain model returns ``T_i *
+    upsample_factor``."""
+
+    def __init__(self, model, max_batch=16, bucket_frames=64, use_graph=True):
+        from ..layers.pqmf import PQMF
+        from ..models import HiFiGANGenerator, MelGANGenerator
+
+        name = type(model).__name__
+        if isinstance(model, HiFiGANGenerator):
+            raise ValueError(f"MelGANRaggedSynthesizer: {name} is not supported (only the non-causal MelGANGenerator; "
+                             "utils.RaggedSynthesizer batches HiFi-GAN utterances of different lengths)")
+        if not isinstance(model, MelGANGenerator):
+            raise ValueError(f"MelGANRaggedSynthesizer: {name} is not supported (only the non-causal MelGANGenerator; "
+                             "utils.ChunkedSynthesizer batches the equal-shaped chunks of any mel-only generator)")
+        try:
+            walk = model._ragged_walk()  # ValueError: causal, a pad other than reflection
+            min_frames, slack = model.ragged_min_frames, model.ragged_slack_frames
+        except ValueError as e:
+            raise ValueError(f"MelGANRaggedSynthesizer: {e} (utils.ChunkedSynthesizer batches the equal-shaped chunks of "
+                             "any mel-only generator)") from None
+        out_channels = walk[-1][0].out_channels
+        self.pqmf = getattr(model, "pqmf", None)
+        if self.pqmf is None and out_channels != 1:
+            raise ValueError(f"MelGANRaggedSynthesizer: this {name} emits {out_channels} channels without a PQMF "
+                             "(model.pqmf = PQMF(subbands=...), as utils.load_model attaches it); an item returns one "
+                             "waveform")
+        if self.pqmf is not None and (not isinstance(self.pqmf, PQMF) or self.pqmf.subbands != out_channels):
+            raise ValueError(f"MelGANRaggedSynthesizer: model.pqmf must be a PQMF with as many sub-bands as the generator "
+                             f"emits ({out_channels}); got {getattr(self.pqmf, 'subbands', type(self.pqmf).__name__)}")
+        self.subbands = out_channels
+        widest = max(m.out_channels * rate * (m.stride if m.transposed else 1) for m, _, _, rate in walk
+                     if hasattr(m, "out_channels"))
+        self._setup(model, max_batch, bucket_frames, use_graph, walk[0][0].in_channels,
+                    model.upsample_factor * out_channels, max(widest, model.upsample_factor * out_channels), min_frames,
+                    slack)
+
+    def _forward(self, c, frames):
+        y = self.model.forward_ragged(c, frames)
+        return y if self.pqmf is None else self.pqmf.synthesis(y)

@@ -1,6 +1,9 @@
 """16 utterances of different lengths through HiFi-GAN V1: ``utils.RaggedSynthesizer`` against the other ways to run
 them, alternating in one process.  GPU box only.
-usage: bench_ragged.py [--precision fp32|bf16] [--json FILE]
+usage: bench_ragged.py [--precision fp32|bf16] [--model hifigan|melgan] [--multiband] [--json FILE]
+``--model melgan``: the same lengths and contenders through ``utils.MelGANRaggedSynthesizer`` on
+``melgan.v1`` (the class defaults) or, with ``--multiband``, on the ``multi_band_melgan.v2`` generator with its PQMF
+attached; seeded weights, fp32 only.
 Contenders, each timed as one call over the whole list with a host clock that stops after a device synchronisation
 (uploads and the slicing of the results included), ROUNDS rounds x REPS calls, alternating:
   ragged16 / ragged8  RaggedSynthesizer.synthesize_many, max_batch 16 (one group) / 8 (two groups), graphs captured
@@ -9,10 +12,11 @@ Contenders, each timed as one call over the whole list with a host clock that st
   inference           16 model.inference calls
 and, on the padded (16, T_pad) block of ragged16, graph replays alone (device events):
   forward_graph       the plain forward (wrong past each item's end: zero mel frames are not zero padding)
-  ragged_graph        forward_ragged
+  ragged_graph        forward_ragged (--multiband: + the PQMF synthesis of the group)
 Their gap is what exactness costs on the device; the library's profiler (eager runs, per kernel family) splits it into
 the zero_tail launches, the fp32 units that run as separate convolutions, the ragged split units against the plain ones
-and the rest: the launches both forwards share, which read zeros past an item's end in the ragged one."""
+and the rest: the launches both forwards share, which read zeros past an item's end in the ragged one.  (MelGAN: the
+mirror_tail launches, the ragged stacks against the plain ones, the rest.)"""
 import argparse
 import json
 import os
@@ -25,9 +29,12 @@ import torch
 
 from parallelwavegan_amd import ops
 from parallelwavegan_amd.graphs import GraphedInference
-from parallelwavegan_amd.models import HiFiGANGenerator
-from parallelwavegan_amd.utils import ChunkedSynthesizer, RaggedSynthesizer, set_inference_precision
+from parallelwavegan_amd.layers import PQMF
+from parallelwavegan_amd.models import HiFiGANGenerator, MelGANGenerator
+from parallelwavegan_amd.utils import (ChunkedSynthesizer, MelGANRaggedSynthesizer, RaggedSynthesizer,
+                                       set_inference_precision)
 from parallelwavegan_amd.utils.streaming import receptive_field_frames
+from tests.golden import synth
 
 LENGTHS = [200, 237, 281, 318, 352, 395, 431, 476, 512, 548, 590, 633, 671, 714, 762, 800]  # mel frames
 ROUNDS, REPS, COLD_RUNS = 5, 3, 3
@@ -57,12 +64,18 @@ def families(prof):
     return {k: dict(launches=int(v["launches"]), ms=float(v["ms"])) for k, v in sorted(prof.results.items())}
 
 
-def split_gap(fam_plain, fam_ragged):
+def split_gap(fam_plain, fam_ragged, melgan=False):
     """The profiler's kernel time of forward_ragged minus forward's, in its parts (ms)."""
     def ms(fam, name):
         return fam.get(name, dict(ms=0.0))["ms"]
 
     total = lambda fam: sum(v["ms"] for v in fam.values())  # noqa: E731
+    if melgan:
+        parts = dict(mirror_tail=ms(fam_ragged, "mirror_tail_kernel"),
+                     # the ragged stacks against the plain ones: less the tiles past an item's end that only store zeros
+                     ragged_stacks=ms(fam_ragged, "resstack_ragged_kernel") - ms(fam_plain, "resstack_kernel"))
+        parts["same_launches_on_tails"] = total(fam_ragged) - total(fam_plain) - sum(parts.values())
+        return parts
     parts = dict(
         zero_tail=ms(fam_ragged, "zero_tail_kernel"),
         # the fp32 units (csrc/resunit.hip) run as two convolutions on the fp32 MFMA kernel
@@ -77,23 +90,44 @@ def split_gap(fam_plain, fam_ragged):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--precision", default="fp32", choices=("fp32", "bf16"))
+    ap.add_argument("--model", default="hifigan", choices=("hifigan", "melgan"))
+    ap.add_argument("--multiband", action="store_true", help="--model melgan: the multi_band_melgan.v2 generator + PQMF")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_ragged.py measures on an MI355X: no device visible")
+    melgan = args.model == "melgan"
+    if melgan and args.precision != "fp32":
+        raise SystemExit("bench_ragged.py: MelGAN has no bf16 mode")
+    if args.multiband and not melgan:
+        raise SystemExit("bench_ragged.py: --multiband goes with --model melgan")
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
-    model = HiFiGANGenerator()
-    model.remove_weight_norm()
+    if melgan:
+        # seeded weights of audible amplitude (tests/golden/synth.py), as tools/bench_stream.py builds them
+        params = dict(out_channels=4, channels=384, upsample_scales=[8, 4, 2], stacks=4) if args.multiband else {}
+        model = MelGANGenerator(**params)
+        model.load_state_dict(synth.synth_state_dict(model.state_dict(), seed=13, g_scale=synth.MELGAN_G_SCALE))
+        model.remove_weight_norm()
+        if args.multiband:
+            model.pqmf = PQMF(subbands=4)
+        name = "multi_band_melgan.v2 generator + PQMF" if args.multiband else "melgan.v1"
+        weights = "seeded synthetic weights (tests/golden/synth.py, seed 13), weight norm removed"
+    else:
+        model = HiFiGANGenerator()
+        model.remove_weight_norm()
+        name = "HiFi-GAN V1"
+        weights = ("N(0, 0.01) initialisation (HiFiGANGenerator()), weight norm removed; the differences against "
+                   "model.inference are on waveforms of small amplitude and say only that the paths agree")
     model = model.to(dev).eval()
     if args.precision == "bf16":
         set_inference_precision(model, "bf16")
     gen = torch.Generator().manual_seed(1)
     feats = [torch.randn(n, 80, generator=gen) for n in LENGTHS]
-    up = model.upsample_factor
+    up = model.upsample_factor * (4 if args.multiband else 1)
 
-    ragged = {16: RaggedSynthesizer(model, max_batch=16, bucket_frames=64),
-              8: RaggedSynthesizer(model, max_batch=8, bucket_frames=64)}
+    cls = MelGANRaggedSynthesizer if melgan else RaggedSynthesizer
+    ragged = {16: cls(model, max_batch=16, bucket_frames=64), 8: cls(model, max_batch=8, bucket_frames=64)}
     halo = receptive_field_frames(model)
     chunked = ChunkedSynthesizer(model, chunk_frames=256, max_batch=16, halo=halo)
 
@@ -122,7 +156,7 @@ def main():
     t_pad = plan.groups[0].t_pad
     c = torch.randn(16, 80, t_pad, device=dev)
     frames = torch.tensor(plan.groups[0].frames, dtype=torch.int32, device=dev)
-    plain_graph = GraphedInference(model)
+    plain_graph = GraphedInference(model)  # (``forward``: the sub-bands of a multi-band model, no PQMF)
     plain_graph(c)
     ragged[16]._run(c, frames)
     dev_ms = {"forward_graph": [], "ragged_graph": []}
@@ -136,7 +170,8 @@ def main():
         with ops.profile() as prof_ragged:
             model.forward_ragged(c, frames)
     fam_plain, fam_ragged = families(prof_plain), families(prof_ragged)
-    zero_tail = fam_ragged.get("zero_tail_kernel", dict(launches=0, ms=0.0))
+    tail_kernel = "mirror_tail_kernel" if melgan else "zero_tail_kernel"
+    zero_tail = fam_ragged.get(tail_kernel, dict(launches=0, ms=0.0))
     kernels_plain = sum(v["ms"] for v in fam_plain.values())
     kernels_ragged = sum(v["ms"] for v in fam_ragged.values())
 
@@ -144,9 +179,7 @@ def main():
         return dict(median=statistics.median(v), min=min(v), max=max(v), runs=v)
 
     audio_s = sum(LENGTHS) * up / 22050.0
-    out = dict(model="HiFi-GAN V1", precision=args.precision, lengths=LENGTHS, frames_total=sum(LENGTHS),
-               weights="N(0, 0.01) initialisation (HiFiGANGenerator()), weight norm removed; the differences against "
-                       "model.inference are on waveforms of small amplitude and say only that the paths agree",
+    out = dict(model=name, precision=args.precision, lengths=LENGTHS, frames_total=sum(LENGTHS), weights=weights,
                audio_seconds_at_22050=audio_s, rounds=ROUNDS, reps=REPS,
                padded_fraction={k: ragged[k].plan(LENGTHS).padded_fraction for k in ragged},
                t_pad={k: [g.t_pad for g in ragged[k].plan(LENGTHS).groups] for k in ragged},
@@ -156,8 +189,8 @@ def main():
                                  launches=dict(forward=sum(v["launches"] for v in fam_plain.values()),
                                                forward_ragged=sum(v["launches"] for v in fam_ragged.values())),
                                  profiler_ms=dict(forward=kernels_plain, forward_ragged=kernels_ragged,
-                                                  zero_tail_launches=zero_tail["launches"],
-                                                  gap=split_gap(fam_plain, fam_ragged)),
+                                                  **{tail_kernel[:-len("_kernel")] + "_launches": zero_tail["launches"]},
+                                                  gap=split_gap(fam_plain, fam_ragged, melgan)),
                                  families=dict(forward=fam_plain, forward_ragged=fam_ragged)))
     for n, v in ms.items():
         print(f"{n:13s} {statistics.median(v):8.2f} ms per list  [{min(v):8.2f} .. {max(v):8.2f}]  "
@@ -166,7 +199,7 @@ def main():
         print(f"{n:13s} {statistics.median(v):8.2f} ms per replay [{min(v):8.2f} .. {max(v):8.2f}]  (16 x {t_pad} frames)")
     print(f"profiler (eager): forward {kernels_plain:.2f} ms in {out['padded_block']['launches']['forward']} launches; "
           f"forward_ragged {kernels_ragged:.2f} ms in {out['padded_block']['launches']['forward_ragged']} launches, "
-          f"{zero_tail['launches']} of them zero_tail; the gap in parts: "
+          f"{zero_tail['launches']} of them {tail_kernel[:-len('_kernel')]}; the gap in parts: "
           + ", ".join(f"{k} {v:+.2f}" for k, v in out["padded_block"]["profiler_ms"]["gap"].items()))
     if args.json:
         with open(args.json, "w") as f:
