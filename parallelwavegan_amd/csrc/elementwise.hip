@@ -226,7 +226,7 @@ __global__ void stft_mag_bwd_kernel(const float* spec, const float* mag, const f
     const float re = spec[b * 2 * plane + r], im = spec[b * 2 * plane + plane + r];
     const float p = re * re + im * im;
     float gr = 0.f, gi = 0.f;
-    if (p > eps) {  // clamp passes no gradient below the floor
+    if (p >= eps) {  // clamp passes no gradient below the floor; AT the floor it does (torch.clamp: x >= min)
       const float s = dmag[i] / mag[i];
       gr = s * re;
       gi = s * im;
@@ -245,7 +245,7 @@ __global__ void log_clamp_fwd_kernel(const float* x, float* y, long n, float eps
 }
 
 __global__ void log_clamp_bwd_kernel(const float* x, const float* dy, float* dx, long n, float eps, float log_div) {
-  GRID_STRIDE(i, n) { dx[i] = x[i] > eps ? dy[i] / (x[i] * log_div) : 0.f; }
+  GRID_STRIDE(i, n) { dx[i] = x[i] >= eps ? dy[i] / (x[i] * log_div) : 0.f; }  // (x == eps: torch.clamp passes it)
 }
 
 // ---- spectral norm (torch.nn.utils.spectral_norm, dim 0, 1 power iteration) --------------
