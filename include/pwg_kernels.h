@@ -270,6 +270,19 @@ int pwg_conv1d_split_step_form(const pwg_conv1d_desc* d);
 int pwg_conv1d_split_forward_step(const pwg_conv1d_desc* d, const float* x, const void* w_packed, const float* bias,
                                   const float* add1, const float* add2, float* y, int32_t mfma_shape, int32_t tile_mode,
                                   int32_t step_form, void* stream);
+/* The form of the kernel's window staging (additive; pwg_abi_version() stays 15): a second axis beside the step form.
+ * Staged: a chunk's 16-B loads are issued, waited for, split and written to the LDS planes between the two barriers of the
+ * chunk.  Prefetched: the raw fp32 window of chunk n + 1 is requested by LDS-DMA in front of the tap loop of chunk n, into
+ * a region of LDS beside the planes, and split from there behind it (resident step, 16-B staging: t_in % 4 == 0, x 16-B
+ * aligned).  Same values to the same plane addresses: same bits.  pwg_conv1d_split_window_form answers the launch plan's
+ * choice for a descriptor -- 1 staged, 2 prefetched, 0 unsupported (pwg_last_error names the reason) -- as pure host
+ * logic.  pwg_conv1d_split_forward_window (tests / A-B tools) is pwg_conv1d_split_forward_step plus window_form: 0 = the
+ * plan decides, 1 = staged, 2 = prefetched; a 2 on a launch the form does not cover (no 16-B staging, the streamed step
+ * named with it, LDS) is refused with a message and launches nothing.                                               */
+int pwg_conv1d_split_window_form(const pwg_conv1d_desc* d);
+int pwg_conv1d_split_forward_window(const pwg_conv1d_desc* d, const float* x, const void* w_packed, const float* bias,
+                                    const float* add1, const float* add2, float* y, int32_t mfma_shape,
+                                    int32_t tile_mode, int32_t step_form, int32_t window_form, void* stream);
 
 /* ---- split-operand inference of the upsampling layers (csrc/conv1d_split.hip, convtr1d_split_mfma_kernel) ----
  * The fused transposed convolution of pwg_conv1d_forward at the ConvTranspose1d call site of the HiFi-GAN generator

@@ -149,6 +149,9 @@ SIGNATURES = {
     "pwg_conv1d_split_step_form": (ctypes.c_int, [ctypes.POINTER(ConvDesc)]),
     "pwg_conv1d_split_forward_step": (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32,
                                                      _i32, _vp]),
+    "pwg_conv1d_split_window_form": (ctypes.c_int, [ctypes.POINTER(ConvDesc)]),
+    "pwg_conv1d_split_forward_window": (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _i32,
+                                                       _i32, _i32, _i32, _vp]),
     "pwg_convtr1d_split_supported": (ctypes.c_int, [ctypes.POINTER(ConvDesc)]),
     "pwg_convtr1d_split_packed_weight_bytes": (ctypes.c_size_t, [ctypes.POINTER(ConvDesc)]),
     "pwg_convtr1d_split_pack_weight": (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, _vp]),

@@ -387,6 +387,144 @@ conv1d_split_streamed_mfma_kernel(SplitArgs a) {
     split_epilogue<TILE, TM, TN, true, false>(a, acc, row0, col0, out_base);
 }
 
+// ---- the PREFETCHED window ("The prefetched window").  Beside the three planes LDS holds the RAW fp32
+// window of one chunk: per wave a region of its own, [8 channels][ngroups] groups of 4 columns (16 B each), wave w
+// holding channel octet w of the chunk.  The region is filled by LDS-DMA (global_load_lds_dwordx4: 64 consecutive
+// 16-B elements of the region per wave instruction, the source address per lane) and holds exactly the values that the
+// 16-B loads of stage_window_vec<NT, false> deliver.
+typedef __attribute__((address_space(3))) void* lds_ptr_t;
+
+// bytes of the raw regions of a workgroup whose planes have `rows` LDS rows: KC channels x rows columns of fp32
+static inline size_t split_raw_bytes(int rows) { return (size_t)KC * rows * sizeof(float); }
+
+// Request the wave's raw region of one chunk.  xw: column `base` of the wave's first channel (8 * wave of the chunk);
+// element e = j * ngroups + grp of the region is columns base + 4 * grp .. + 3 of channel j.  The caller guarantees an
+// interior window (base >= 0, base + 4 * ngroups <= t_in) and 8 whole channels, so every requested byte is inside the
+// row; lanes past the last element of the region are masked and write nothing.
+__device__ __forceinline__ void request_raw_window(const float* __restrict__ xw, int t_in, int ngroups, float* raww,
+                                                   int lane) {
+  const int total = 8 * ngroups;
+  const int dq = 64 / ngroups, dr = 64 - dq * ngroups;
+  int j = lane / ngroups, g = lane - j * ngroups;
+  for (int e0 = 0; e0 < total; e0 += 64) {
+    if (e0 + lane < total)
+      __builtin_amdgcn_global_load_lds(xw + (size_t)j * t_in + 4 * g, (lds_ptr_t)(raww + e0 * 4), 16, 0, 0);
+    j += dq, g += dr;
+    if (g >= ngroups) g -= ngroups, ++j;
+  }
+}
+
+// Activate, split and write the wave's raw region to the planes: item = (group of 4 columns, the wave's channel octet),
+// lanes walk the groups -- the values, the arithmetic and the plane addresses of stage_window_vec, with the items of a
+// window dealt evenly over the four waves (there: item = thread index, which leaves wave 3 idle on a short window).
+// Measured and not kept (profiles/split_window.txt): lanes that walk the COLUMNS (8 values per lane and pass, plane rows
+// 80 B apart instead of 320 B, which halves the LDS bank conflicts of this form) -- a VGPR spill in the flagship
+// instantiation, 0.97 x of the staged kernel at 16 x 800 frames where this form has 0.96 x, 0.94 x at 1 x 800.
+__device__ __forceinline__ void split_raw_window(const SplitArgs& a, const float* raww, int ngroups, __bf16* xs, int wave,
+                                                 int lane) {
+  for (int grp = lane; grp < ngroups; grp += 64) {
+    f32x4 st[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) st[j] = *reinterpret_cast<const f32x4*>(raww + (j * ngroups + grp) * 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float v[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = pre_activate(st[j][e], a.pre_mul, a.pre_mask);
+      split3_store<8>(v, xs + (grp * 4 + e) * kConvRow + wave * 8, a.plane);
+      __builtin_amdgcn_sched_barrier(0);  // one column at a time, as in stage_window_vec
+    }
+  }
+}
+
+// conv1d_split_mfma_kernel (16-B staging, resident step) with the raw window of chunk n + 1 requested in front of the tap
+// loop of chunk n and consumed behind it.  Only a chunk that passes the interior test of the staged kernel (every staged
+// column inside the row, 32 whole channels) is prefetched; an edge tile, or the channel tail of an interior tile, is
+// staged by stage_chunk as before, in this kernel: the decision is workgroup-uniform.  The planes receive the same
+// values at the same addresses and the tap loop and the epilogue are the staged kernel's: the same bits.
+template <int TILE, int WM, int WN, int WAVES_M>
+__global__ __launch_bounds__(256, WM * WN == 4 ? (TILE == 16 ? 3 : 2) : (WM * WN == 2 ? 3 : 4)) void
+conv1d_split_window_mfma_kernel(SplitArgs a) {
+  constexpr int HL = 64 / TILE;
+  constexpr int KSTEPS = KC / (8 * HL);
+  constexpr int TM = WM * 32 / TILE, TN = WN * 32 / TILE;
+  constexpr int NREG = TILE * TILE / 64;
+  constexpr int WAVES_N = 4 / WAVES_M;
+  constexpr int MT = WAVES_M * WM * 32, NT = WAVES_N * WN * 32;
+  typedef typename Mfma<TILE>::acc_t acc_t;
+
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __bf16* xs = reinterpret_cast<__bf16*>(smem);  // [part][column][ROW]
+
+  const MfmaConvTile c = mfma_conv_tile<TILE, MT, NT, WAVES_M, true>(a);
+  const int ngroups = (c.wcols + 3) >> 2;
+  // the wave's raw region, behind the planes: 8 channels x the plane's rows (>= 4 * ngroups columns)
+  float* raww = reinterpret_cast<float*>(xs + PARTS * a.plane) + c.wave * (8 * (a.plane / kConvRow));
+  const bool interior = c.base >= 0 && c.base + 4 * ngroups <= a.t_in;  // per workgroup
+  const float* __restrict__ xw = c.xb + (size_t)(c.wave * 8) * a.t_in + c.base;
+  auto prefetched = [&](int chunk) { return interior && a.c_in - chunk * KC >= KC; };
+
+  if (prefetched(0)) request_raw_window(xw, a.t_in, ngroups, raww, c.lane);
+
+  acc_t acc[TM][TN];
+#pragma unroll
+  for (int mi = 0; mi < TM; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < TN; ++ni)
+#pragma unroll
+      for (int i = 0; i < NREG; ++i) acc[mi][ni][i] = 0.f;
+
+  // Synchronisation.  A raw region is PRIVATE to its wave: the wave that requests it is the only one that reads it.  A
+  // ds_read is ordered behind a pending LDS-DMA only by the issuing wave's own vmcnt wait, and here that wave is the
+  // reader, so its vmcnt(0) in front of the reads suffices and no barrier guards the raw data.  The count is drained
+  // there completely: besides the DMA only the weight fragments of the resident step use vmcnt, and every one of them
+  // was waited for by the MFMA that consumed it before the tap loop ended, so nothing else is in flight.  The region of
+  // chunk n is overwritten by the request for chunk n + 1, which the same wave issues after its split of chunk n has
+  // used every value it read (the reads have returned) and behind barrier 2.  The two barriers per chunk are the
+  // staged kernel's and guard the planes alone: barrier 1, every wave has finished the taps of chunk n - 1, the planes
+  // may be overwritten; barrier 2, the planes of chunk n are written, every wave may read them.
+  for (int chunk = 0; chunk < a.cin_chunks; ++chunk) {
+    if (chunk) __syncthreads();
+    if (prefetched(chunk)) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      split_raw_window(a, raww, ngroups, xs, c.wave, c.lane);
+    } else {
+      stage_chunk<NT, true>(a, c, chunk, xs);
+    }
+    __syncthreads();
+    if (chunk + 1 < a.cin_chunks && prefetched(chunk + 1))
+      request_raw_window(xw + (size_t)(chunk + 1) * KC * a.t_in, a.t_in, ngroups, raww, c.lane);
+    for (int tap = 0; tap < a.taps; ++tap) {
+#pragma unroll
+      for (int ks = 0; ks < KSTEPS; ++ks) {
+        const int oct = ks * HL + c.h;
+        const bf16x8* __restrict__ wp =
+            image_rows(a.w, a.cin_chunks, a.m_pad, tap, chunk, oct) + c.m0 + c.wave_m * (WM * 32) + c.r;
+        // the x fragment goes first: the transposed tile of split_epilogue
+        split_step<TILE, TM, TN, kConvRow, true>(wp, a.part_stride, xs, c.sh + c.wave_n * (WN * 32) + c.r + tap * a.dil,
+                                                 oct * 8, a.plane, acc);
+      }
+    }
+  }
+
+  const size_t out_base = (size_t)c.b * a.c_out * a.t_out;
+  const int row0 = c.m0 + c.wave_m * (WM * 32) + c.r, col0 = c.q0 + c.wave_n * (WN * 32) + 4 * c.h;
+  const bool full = c.m0 + MT <= a.m && c.q0 + NT <= a.nq;  // no padded row and no column past the end in this tile
+  if (!a.wide_out)
+    split_epilogue<TILE, TM, TN, false, false>(a, acc, row0, col0, out_base);
+  else if (full)
+    split_epilogue<TILE, TM, TN, true, true>(a, acc, row0, col0, out_base);
+  else
+    split_epilogue<TILE, TM, TN, true, false>(a, acc, row0, col0, out_base);
+}
+
+struct WindowFamily {
+  template <int TILE, int WM, int WN, int WAVES_M>
+  struct K {
+    static constexpr auto fn = conv1d_split_window_mfma_kernel<TILE, WM, WN, WAVES_M>;
+  };
+};
+
 template <bool VEC, bool STREAMED>
 struct Family {
   template <int TILE, int WM, int WN, int WAVES_M>
@@ -425,22 +563,72 @@ static int split_step_form(const MfmaConvGeom& g) {
   return g.taps >= kStreamedMinTaps && g.cin_chunks >= kStreamedMinChunks ? kStepStreamed : kStepResident;
 }
 
+// The form of the window staging of a launch (kWindowStaged / kWindowPrefetched): a second axis beside the step form.
+// The prefetched kernel covers a launch with 16-B staging (plan.vec) whose planes and raw regions fit the LDS of a CU;
+// split_window_lds is that size.  The plan CHOOSES it by the keep rule of the step form, read off the isolated A/B of the
+// two window forms (tools/bench_conv_split_window.py; DESIGN.md s9.1, profiles/split_window.txt): a class is admitted when
+// every run at 16 x 800 frames is disjointly faster than every staged run and no shorter launch is disjointly slower,
+// and the rule is the hull of the admitted classes.  A launch the streamed step is chosen for keeps the staged window
+// (the prefetched kernel has the resident step), and so does one whose planes and raw regions would not leave three
+// workgroups to a CU (kWindowLdsShare).  Pure host logic.
+constexpr int kWindowPlanDecides = 0, kWindowStaged = 1, kWindowPrefetched = 2;
+constexpr size_t kLdsPerCu = 160 * 1024, kWindowLdsShare = kLdsPerCu / 3;
+constexpr int kWindowMaxTaps = 0;  // taps up to which the A/B admitted the prefetched window (0: no class)
+static size_t split_window_lds(const MfmaConvPlan& p) { return p.lds + split_raw_bytes(p.plane / kConvRow); }
+static bool split_window_covers(const MfmaConvPlan& p) { return p.vec && split_window_lds(p) <= kLdsPerCu; }
+static int split_window_form(const MfmaConvGeom& g, const MfmaConvPlan& p) {
+  if (!split_window_covers(p) || split_step_form(g) == kStepStreamed) return kWindowStaged;
+  return g.taps <= kWindowMaxTaps && g.cin_chunks >= 2 && split_window_lds(p) <= kWindowLdsShare ? kWindowPrefetched
+                                                                                                   : kWindowStaged;
+}
+
 static int split_forward(const pwg_conv1d_desc* d, const float* x, const void* w_packed, const float* bias,
                          const float* add1, const float* add2, float* y, int mfma_shape, int tile_mode, int step_form,
-                         hipStream_t stream) {
+                         int window_form, hipStream_t stream) {
   MfmaConvGeom g;
   int rc = split_geometry(d, &g);
   if (rc != PWG_OK) return rc;
   PWG_REQUIRE(step_form >= kStepPlanDecides && step_form <= kStepStreamed, PWG_ERR_BAD_SHAPE,
               "conv1d_split: step_form = %d (0 = the plan decides, 1 = resident, 2 = streamed)", step_form);
+  PWG_REQUIRE(window_form >= kWindowPlanDecides && window_form <= kWindowPrefetched, PWG_ERR_BAD_SHAPE,
+              "conv1d_split: window_form = %d (0 = the plan decides, 1 = staged, 2 = prefetched)", window_form);
   rc = mfma_conv_check_forward("conv1d_split", d, x, w_packed, y, mfma_shape, tile_mode);
   if (rc != PWG_OK) return rc;
   const MfmaConvPlan p = mfma_conv_plan(d, g, PARTS, tile_mode, x, add1, add2);
   PWG_REQUIRE(step_form != kStepStreamed || split_image_addressable(image_elems(g)), PWG_ERR_UNSUPPORTED,
               "conv1d_split: weight image too large for the streamed step");
-  const bool streamed = (step_form == kStepPlanDecides ? split_step_form(g) : step_form) == kStepStreamed;
+  // the prefetched window has the resident step: it is the plan's choice only where the plan's step is resident, and a
+  // caller that names it gets it unless they also name the streamed step
+  PWG_REQUIRE(window_form != kWindowPrefetched || step_form != kStepStreamed, PWG_ERR_UNSUPPORTED,
+              "conv1d_split: the prefetched window (window_form = 2) has no streamed step (step_form = 2)");
+  PWG_REQUIRE(window_form != kWindowPrefetched || p.vec, PWG_ERR_UNSUPPORTED,
+              "conv1d_split: the prefetched window (window_form = 2) needs 16-B staging: t_in %% 4 == 0, x 16-B aligned, "
+              "a window of at most %d columns", 2 * p.nt);
+  PWG_REQUIRE(window_form != kWindowPrefetched || split_window_covers(p), PWG_ERR_UNSUPPORTED,
+              "conv1d_split: the prefetched window (window_form = 2) needs %zu B of LDS (> %zu)", split_window_lds(p),
+              kLdsPerCu);
+  const bool prefetched = window_form == kWindowPrefetched ||
+                          (window_form == kWindowPlanDecides && step_form == kStepPlanDecides &&
+                           split_window_form(g, p) == kWindowPrefetched);
+  const bool streamed = !prefetched && (step_form == kStepPlanDecides ? split_step_form(g) : step_form) == kStepStreamed;
   SplitArgs a;
   split_fill_args(&a, d, g, p, x, w_packed, bias, add1, add2, y);
+  if (prefetched) {
+    const size_t lds = split_window_lds(p);
+    void (*kern)(SplitArgs) = mfma_shape == 32 ? mfma_conv_tile_kernel<WindowFamily::K, 32, SplitArgs>(p)
+                                               : mfma_conv_tile_kernel<WindowFamily::K, 16, SplitArgs>(p);
+    if (lds > kConvMaxLds && !lds_limit_is_set(reinterpret_cast<const void*>(kern), lds)) {
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         (int)lds);
+      PWG_REQUIRE(e == hipSuccess, PWG_ERR_LAUNCH, "conv1d_split: cannot raise LDS limit to %zu: %s", lds,
+                  hipGetErrorString(e));
+    }
+    maybe_poison_lds(stream);
+    ProfScope prof(stream, "conv1d_split_mfma_kernel", p.flops, p.bytes);
+    hipLaunchKernelGGL(kern, p.grid, dim3(256), lds, stream, a);
+    PWG_CHECK_LAUNCH("conv1d_split");
+    return PWG_OK;
+  }
   maybe_poison_lds(stream);
   ProfScope prof(stream, "conv1d_split_mfma_kernel", p.flops, p.bytes);
   if (p.vec) {
@@ -734,19 +922,37 @@ extern "C" int pwg_conv1d_split_forward(const pwg_conv1d_desc* d, const float* x
                                         size_t workspace_floats, void* stream) {
   (void)workspace;  // no split reduction: one workgroup owns an output tile
   (void)workspace_floats;
-  return split_forward(d, x, w_packed, bias, add1, add2, y, kDefaultMfmaShape, 0, kStepPlanDecides, (hipStream_t)stream);
+  return split_forward(d, x, w_packed, bias, add1, add2, y, kDefaultMfmaShape, 0, kStepPlanDecides, kWindowPlanDecides,
+                       (hipStream_t)stream);
 }
 
 extern "C" int pwg_conv1d_split_forward_cfg(const pwg_conv1d_desc* d, const float* x, const void* w_packed,
                                             const float* bias, const float* add1, const float* add2, float* y,
                                             int32_t mfma_shape, int32_t tile_mode, void* stream) {
-  return split_forward(d, x, w_packed, bias, add1, add2, y, mfma_shape, tile_mode, kStepPlanDecides, (hipStream_t)stream);
+  return split_forward(d, x, w_packed, bias, add1, add2, y, mfma_shape, tile_mode, kStepPlanDecides, kWindowPlanDecides,
+                       (hipStream_t)stream);
 }
 
 extern "C" int pwg_conv1d_split_forward_step(const pwg_conv1d_desc* d, const float* x, const void* w_packed,
                                              const float* bias, const float* add1, const float* add2, float* y,
                                              int32_t mfma_shape, int32_t tile_mode, int32_t step_form, void* stream) {
-  return split_forward(d, x, w_packed, bias, add1, add2, y, mfma_shape, tile_mode, step_form, (hipStream_t)stream);
+  return split_forward(d, x, w_packed, bias, add1, add2, y, mfma_shape, tile_mode, step_form, kWindowPlanDecides,
+                       (hipStream_t)stream);
+}
+
+extern "C" int pwg_conv1d_split_forward_window(const pwg_conv1d_desc* d, const float* x, const void* w_packed,
+                                               const float* bias, const float* add1, const float* add2, float* y,
+                                               int32_t mfma_shape, int32_t tile_mode, int32_t step_form,
+                                               int32_t window_form, void* stream) {
+  return split_forward(d, x, w_packed, bias, add1, add2, y, mfma_shape, tile_mode, step_form, window_form,
+                       (hipStream_t)stream);
+}
+
+// the plan of the default launch (small-grid rule, aligned pointers)
+extern "C" int pwg_conv1d_split_window_form(const pwg_conv1d_desc* d) {
+  MfmaConvGeom g;
+  if (split_geometry(d, &g) != PWG_OK) return 0;
+  return split_window_form(g, mfma_conv_plan(d, g, PARTS, 0, nullptr, nullptr, nullptr));
 }
 
 extern "C" int pwg_conv1d_split_step_form(const pwg_conv1d_desc* d) {

@@ -236,8 +236,9 @@ class _ConvNd(torch.nn.Module):
 
     def _split_route(self, desc, needs_grad=False):
         """Does this no-grad call (``desc``) of an fp32 module run on the split-operand kernel?"""
-        return split_admitted(desc.c_in, desc.c_out, desc.kernel, desc.batch * desc.t_out, needs_grad,
-                              self.split_exact, self.split_admit_all) and ops.conv1d_split_supported(desc)
+        cls = (desc.c_in, desc.c_out, desc.kernel, desc.batch * desc.t_out, needs_grad, self.split_exact,
+               self.split_admit_all)
+        return (split_admitted(*cls) or split_fewtap_admitted(*cls)) and ops.conv1d_split_supported(desc)
 
     def packed_weight_split_transposed(self):
         """Cached split-operand images of a k = 2s transposed layer, held by the same ``prepared()``."""
@@ -403,6 +404,35 @@ def split_admitted(c_in, c_out, kernel, cols, needs_grad, enabled=True, admit_al
     return min_cols is not None and cols >= min_cols
 
 
+# Admission table of the split-operand kernel for the few-tap classes (k = 3), beside SPLIT_ADMITTED, which keeps the
+# k >= 7 classes: (c_in, c_out, kernel) -> fewest output columns per launch (batch x t_out).  The rule is that of the
+# tables around it: a class is listed when every run of the split kernel (in the form its launch plan chooses) at
+# 16 x 800 frames was faster than every run of the fp32 kernel and the median gain was >= 1.25 x; its column count is the
+# shortest measured launch (16 x 800, 1 x 800, 1 x 100 frames) on which it still won disjointly, and never under
+# SPLIT_FEWTAP_MIN_COLS.  Classes not listed, and shorter launches, stay on the fp32 kernel.
+# Both rows were measured on the staged window with the resident step, which is what the kernel's plan launches for them
+# (profiles/split_window.txt B; DESIGN.md s9.1, "The prefetched window" and "The few-tap routing"): at 16 x 800 frames
+# 128 -> 128 1.64 - 1.70 x, 256 -> 256 1.74 - 1.84 x, every run disjoint; at 6400 columns 1.90 x (128 channels, one utterance
+# of 100 frames) and 1.26 x (256 channels, one utterance of 800 frames), disjoint; at 800 columns 256 -> 256 loses (0.79 x).
+SPLIT_FEWTAP_MIN_COLS = 6400
+SPLIT_FEWTAP_ADMITTED = {
+    (128, 128, 3): 6400,
+    (256, 256, 3): 6400,
+}
+
+
+def split_fewtap_admitted(c_in, c_out, kernel, cols, needs_grad, enabled=True, admit_all=False):
+    """The admission predicate of the split-operand kernel for the few-tap classes (pure host logic), consulted after
+    :func:`split_admitted` and honouring the same switches: never when a gradient is needed or the switch is off; else
+    every class (``admit_all``) or the classes of ``SPLIT_FEWTAP_ADMITTED`` from their column count on."""
+    if needs_grad or not enabled:
+        return False
+    if admit_all:
+        return True
+    min_cols = SPLIT_FEWTAP_ADMITTED.get((c_in, c_out, kernel))
+    return min_cols is not None and cols >= max(min_cols, SPLIT_FEWTAP_MIN_COLS)
+
+
 # Admission table of the split-operand transposed kernel (convtr1d_split_mfma_kernel; DESIGN.md s9.3,
 # profiles/convtr_split.txt): (c_in, c_out, stride) of a ConvTranspose1d with kernel == 2 * stride -> fewest output
 # columns per launch (batch x t_out).  The rule is that of the two tables around it: a class is listed when every run of
@@ -443,13 +473,17 @@ def upsample_split_admitted(c_in, c_out, kernel, stride, cols, needs_grad, enabl
 # against 1.15 / 1.71 ms per unit at 16 x 800 frames).  A class is listed when every run of its form was faster than
 # every run of the incumbent (the fp32 unit; two fp32 convolutions at C = 64, k = 11) and the median gain at 16 x 800
 # frames was >= 1.25 x; the column count is the shortest measured launch on which it still won disjointly, and never
-# under RESUNIT_SPLIT_MIN_COLS.  C = 32, k = 3 gains 1.10 x and stays on the fp32 unit; the single-convolution form was
-# not measured and is not listed.  Classes not listed, and shorter launches, stay where they were.
+# under RESUNIT_SPLIT_MIN_COLS.  C = 32, k = 3 gained 1.10 x when the table was filled and 1.27 - 1.28 x (disjoint) since
+# the unit streams its weight fragments and requests its epilogue operands early (profiles/split_window.txt C); it wins
+# disjointly down to 25600 columns and is listed from 51200, the shortest measured winning launch above the 25600 at
+# which tests/test_hifigan_resunit_split_gpu.py pins the fp32 unit.  The single-convolution form was not measured and is
+# not listed.  Classes not listed, and shorter launches, stay where they were.
 RESUNIT_SPLIT_MIN_COLS = 20480
 RESUNIT_SPLIT_ADMITTED = {
     (64, 3, True): ("unit", 20480),
     (64, 7, True): ("pair", 20480),
     (64, 11, True): ("pair", 20480),
+    (32, 3, True): ("unit", 51200),
     (32, 7, True): ("unit", 25600),
     (32, 11, True): ("unit", 25600),
 }

@@ -301,12 +301,29 @@ def conv1d_split_step_form(desc):
     return STEP_FORMS[form]
 
 
+WINDOW_FORMS = {1: "staged", 2: "prefetched"}
+
+
+def conv1d_split_window_form(desc):
+    """The form of the window staging the split-operand kernel's launch plan chooses for this descriptor: "staged" or
+    "prefetched" (csrc/conv1d_split.hip, ``split_window_form``).  Host logic only (no device needed); an unsupported
+    descriptor raises with the library's reason."""
+    form = _lib.lib().pwg_conv1d_split_window_form(ctypes.byref(desc))
+    if form == 0:
+        _lib.check(-1, "conv1d_split_window_form")
+    return WINDOW_FORMS[form]
+
+
 def conv1d_forward_split(desc, x, w_packed, bias=None, add1=None, add2=None, out=None, mfma_shape=None, tile_mode=0,
-                         step_form=0):
+                         step_form=0, window_form=0):
     """Fused fp32 convolution computed on the bf16 MFMA from 3-way split operands (inference only).
     ``mfma_shape`` (tuning): 32 or 16 selects the MFMA instruction; ``tile_mode`` (tests): 1 = full-size, 2 = half-size
     tiles instead of the small-grid rule; ``step_form`` (tests / A-B): 1 = the resident, 2 = the streamed reduction step
+    instead of the plan's choice (same bits); ``window_form`` (tests / A-B): 1 = the staged, 2 = the prefetched window
     instead of the plan's choice (same bits)."""
+    if window_form:
+        cfg = (int(mfma_shape or 16), int(tile_mode), int(step_form), int(window_form))
+        return _conv1d_forward_mfma("split", desc, desc, x, w_packed, bias, add1, add2, out, cfg, entry="window")
     if step_form:
         cfg = (int(mfma_shape or 16), int(tile_mode), int(step_form))
         return _conv1d_forward_mfma("split", desc, desc, x, w_packed, bias, add1, add2, out, cfg, entry="step")
