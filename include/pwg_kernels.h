@@ -573,6 +573,23 @@ int pwg_resunit_split_ragged_supported(const pwg_resunit_desc* d, int32_t rate);
 int pwg_resunit_split_forward_ragged(const pwg_resunit_desc* d, const float* x, const void* w1_split, const float* b1,
                                      const void* w2_split, const float* b2, const float* add2, float* y,
                                      int32_t mfma_shape, const int32_t* frames, int32_t rate, void* stream);
+/* The chained block: n_units <= 3 pair-form units (has_conv2 = 1) of one kernel size, unit u with dilation dilations[u]
+ * and slopes slopes1[u] / slopes2[u], as ONE launch.  Bit for bit n_units chained pwg_resunit_split_forward_cfg launches
+ * at the same mfma_shape: units 0 .. n_units - 2 with add2 = NULL and out_div = 1, the last with add2 and d->out_div;
+ * d->dilation, d->slope1 and d->slope2 are not read.  Every phase of every unit computes the same frame of H columns
+ * (256 at 32 channels, 128 at 64); with edge = sum over the units of (k - 1) / 2 * (dilation + 1), rounded up to a
+ * multiple of 4, a frame starts at column t0 - edge and stores its central bn_out = H - 2 * edge columns.
+ * pwg_resblock_split_supported is pure host logic (reason in pwg_last_error); it refuses bn_out < H / 2, a
+ * single-convolution unit, n_units outside 1 .. 3 and whatever pwg_resunit_split_supported refuses for a unit; the
+ * forward refuses y == x.  pwg_resblock_split_frame reports out[0..5] = H, bn_out, edge, margin rows of a plane, LDS
+ * bytes, frames per row.  w1_split / b1 / w2_split / b2: host arrays of n_units device pointers (a bias may be NULL).
+ * Additive: pwg_abi_version() stays 15. */
+int pwg_resblock_split_supported(const pwg_resunit_desc* d, int32_t n_units, const int32_t* dilations);
+int pwg_resblock_split_frame(const pwg_resunit_desc* d, int32_t n_units, const int32_t* dilations, int32_t* out);
+int pwg_resblock_split_forward_cfg(const pwg_resunit_desc* d, int32_t n_units, const int32_t* dilations,
+                                   const float* slopes1, const float* slopes2, const float* x,
+                                   const void* const* w1_split, const float* const* b1, const void* const* w2_split,
+                                   const float* const* b2, const float* add2, float* y, int32_t mfma_shape, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* One MelGAN residual stack as ONE launch (channels 48 / 96 / 192, kernel 3; csrc/resstack.hip)             */

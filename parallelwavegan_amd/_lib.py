@@ -209,6 +209,13 @@ SIGNATURES = {
     "pwg_resunit_split_ragged_supported": (ctypes.c_int, [ctypes.POINTER(ResUnitDesc), _i32]),
     "pwg_resunit_split_forward_ragged": (ctypes.c_int, [ctypes.POINTER(ResUnitDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                                         _i32, _vp, _i32, _vp]),
+    "pwg_resblock_split_supported": (ctypes.c_int, [ctypes.POINTER(ResUnitDesc), _i32, ctypes.POINTER(_i32)]),
+    "pwg_resblock_split_frame": (ctypes.c_int, [ctypes.POINTER(ResUnitDesc), _i32, ctypes.POINTER(_i32),
+                                                ctypes.POINTER(_i32)]),
+    "pwg_resblock_split_forward_cfg": (ctypes.c_int, [ctypes.POINTER(ResUnitDesc), _i32, ctypes.POINTER(_i32),
+                                                      ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), _vp,
+                                                      ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                                                      ctypes.POINTER(_vp), _vp, _vp, _i32, _vp]),
     "pwg_resstack_supported": (ctypes.c_int, [_i32, _i32, _i32]),
     "pwg_resstack_packed_weight_floats": (ctypes.c_size_t, [_i32]),
     "pwg_resstack_pack_weight": (ctypes.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

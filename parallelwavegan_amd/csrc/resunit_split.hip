@@ -31,6 +31,7 @@
 // a second time (an fp32 copy in LDS would cost the second workgroup per CU), but behind the staging loads that fetch
 // the same lines and into registers the two-wave occupancy leaves idle; add2 likewise ahead of the last contraction.
 // Deterministic: one workgroup owns an output tile, no atomics.
+// resblock_split_kernel, further down, chains up to three pair-form units in one launch from the same pieces.
 #include "mfma_conv.h"
 
 #include <stdlib.h>
@@ -475,10 +476,362 @@ static int ru_split_ragged_rate(int rate) {
   return PWG_OK;
 }
 
+// ---- A chain of N <= 3 pair-form units as ONE launch (resblock_split_kernel; DESIGN.md s9.2, "the chained block") ----
+// Numerical definition: N chained pwg_resunit_split_forward_cfg launches at the same MFMA shape -- units 0 .. N - 2 with
+// add2 = NULL and out_div = 1, the last with the block's; between units y_u = acc + b2 + x_u is formed in fp32 in that
+// order, is zero outside [0, T), and is activated with the next unit's slope1 and split with split3, which is what the
+// next launch would do to the stored tensor.  That chain is the test oracle, bit for bit.
+// Fixed frame: every phase of every unit computes the same H absolute columns f0 .. f0 + H - 1; frame column m is plane
+// row margin + m and a tap reads row margin + m + (tap - (k - 1) / 2) * d.  The margin rows ((k - 1) / 2 * max d on each
+// side) are zeroed once and never written, so a column near the frame's edge is computed from a truncated window: it is
+// wrong, finite or not, and it is never an input of a column that is stored -- validity shrinks by (k - 1) / 2 * (d_u + 1)
+// columns per unit and side, the frame's `edge` is the sum over the units (rounded up to a multiple of 4: f0 = t0 - edge
+// stays 16-B aligned and the staging needs no halo loads), and only the central bn_out = H - 2 * edge columns are stored.
+// Registers: output slot -> absolute column is the same map in every unit (ru_out_slot), so the residual of unit u + 1 is
+// the y_u this lane just formed: it stays in `res`.  x is read once for the planes and once for `res`, add2 once (behind
+// the last unit's phase 1), y is written once.
+// LDS: lrelu(y_u) goes from the transposed tile of phase 2 (a lane owns 4 consecutive samples of a channel) to the
+// [column][channel] planes as 2-byte writes, 3 parts x 4 samples per value.
+constexpr int kRbMaxUnits = 3;
+
+struct RbSplitArgs {
+  RuSplitArgs u;  // x, add2, y, T, k, plane, part_stride, bn_out, out_div; rows = H, slope1 = unit 0's: what the staging reads
+  const bf16x8* w1[kRbMaxUnits];
+  const bf16x8* w2[kRbMaxUnits];
+  const float* b1[kRbMaxUnits];
+  const float* b2[kRbMaxUnits];
+  int d[kRbMaxUnits];
+  float slope1[kRbMaxUnits], slope2[kRbMaxUnits];
+  int n_units;
+  int margin;  // zero rows on each side of a plane
+  int edge;    // frame columns in front of output slot 0 (a multiple of 4)
+};
+
+template <int C, int TILE>
+__global__ __launch_bounds__(256, 2) void resblock_split_kernel(RbSplitArgs a) {
+  using Cfg = RuSplitCfg<C>;
+  constexpr int WAVES_N = Cfg::WAVES_N, ROW = Cfg::ROW, H = Cfg::H;
+  constexpr int HL = 64 / TILE, TM = 32 / TILE, TN = 64 / TILE, NREG = TILE * TILE / 64, NG = NREG / 4;
+  typedef typename Mfma<TILE>::acc_t acc_t;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __bf16* xs = reinterpret_cast<__bf16*>(smem);  // [part][margin + frame column + margin][ROW]
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wave_m = wave / WAVES_N, wave_n = wave % WAVES_N;
+  const int r = lane & (TILE - 1), h = lane / TILE;
+  const int b = blockIdx.y;
+  const int t0 = blockIdx.x * a.u.bn_out;  // first output sample of this tile
+  const int f0 = t0 - a.edge;              // sample of frame column 0 (a multiple of 4, also when negative)
+  const int T = a.u.T, k = a.u.k, p = (k - 1) / 2, plane = a.u.plane, margin = a.margin;
+  const long part_stride = a.u.part_stride;
+  const float* __restrict__ xb = a.u.x + (size_t)b * C * T;
+  __bf16* fr = xs + margin * ROW;  // plane 0 at frame column 0
+
+  const unsigned wrow = wave_m * 32 + r;
+  bf16x8 wf[3];
+  ru_request<C, TILE>(wf, a.w1[0], part_stride, wrow, h);
+
+  // the margins: zero, once
+  for (int i = tid; i < 2 * margin * Cfg::OCTS; i += 256) {
+    bf16x8 z;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) z[j] = (__bf16)0.f;
+    const int row = i / Cfg::OCTS;
+    __bf16* dst = xs + (row < margin ? row : H + row) * ROW + (i % Cfg::OCTS) * 8;
+    *reinterpret_cast<bf16x8*>(dst) = z;
+    *reinterpret_cast<bf16x8*>(dst + plane) = z;
+    *reinterpret_cast<bf16x8*>(dst + 2 * plane) = z;
+  }
+
+  // The residual of unit 0 is the raw x at the lane's own frame columns (every column of the frame inside [0, T): the
+  // columns in front of the stored ones are inputs of the next unit); add2 is needed at the stored columns only.  A value
+  // that is not needed reads the tile's first samples: no address outside the row.
+  constexpr int NV = TN * NG;
+  const bool has2 = a.u.add2 != nullptr;
+  f32x4 res[TM][NV], ad2[TM][NV];
+  auto request_values = [&](const float* __restrict__ src, f32x4 (&dst)[TM][NV], bool stored_only) {
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int mi = 0; mi < TM; ++mi) {
+      const float* __restrict__ rowp = src + ((size_t)b * C + wave_m * 32 + mi * TILE + r) * T;
+#pragma unroll
+      for (int n = 0; n < NV; ++n) {
+        const int slot = ru_out_slot<TILE>(wave_n, h, n), t = f0 + slot;
+        const bool ok = t >= 0 && t < T && (!stored_only || (slot >= a.edge && slot < a.edge + a.u.bn_out));
+        dst[mi][n] = *reinterpret_cast<const f32x4*>(rowp + (ok ? t : t0));
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  };
+#pragma unroll
+  for (int mi = 0; mi < TM; ++mi)
+#pragma unroll
+    for (int n = 0; n < NV; ++n) ad2[mi][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+  auto behind_window = [&] { request_values(a.u.x, res, false); };
+  if (f0 >= 0 && f0 + H <= T)
+    ru_stage_window<C, false>(a.u, xb, f0, fr, tid, behind_window);
+  else
+    ru_stage_window<C, true>(a.u, xb, f0, fr, tid, behind_window);
+
+  acc_t acc[TM][TN];
+#pragma unroll
+  for (int mi = 0; mi < TM; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < TN; ++ni)
+#pragma unroll
+      for (int i = 0; i < NREG; ++i) acc[mi][ni][i] = 0.f;
+
+#pragma unroll 1
+  for (int u = 0; u < a.n_units; ++u) {
+    const bool last = u + 1 == a.n_units;
+    const int d1 = a.d[u];
+    const float* __restrict__ b1p = a.b1[u];
+    const float* __restrict__ b2p = a.b2[u];
+    const bool has_b1 = b1p != nullptr, has_b2 = b2p != nullptr;
+    // the unit's biases: b1 of the lane's 4 consecutive channels per (mi, g) where h is formed, b2 per row tile
+    f32x4 bias_h[TM][NG];
+    float bias_y[TM];
+#pragma unroll
+    for (int mi = 0; mi < TM; ++mi) {
+      bias_y[mi] = has_b2 ? b2p[wave_m * 32 + mi * TILE + r] : 0.f;
+#pragma unroll
+      for (int g = 0; g < NG; ++g)
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          bias_h[mi][g][e] = has_b1 ? b1p[wave_m * 32 + mi * TILE + 4 * h + 4 * HL * g + e] : 0.f;
+    }
+    __syncthreads();  // the planes hold lrelu(x_u), split (and, for u = 0, the zeroed margins)
+
+    // ---- phase 1: conv_{k,d} over lrelu(x_u); frame column m reads row margin + m + (tap - p) * d
+    ru_contract<C, TILE, false>(wf, a.w1[u], part_stride, wrow, fr + (wave_n * 64 + r - p * d1) * ROW, plane, d1, k, h,
+                                acc);
+    ru_request<C, TILE>(wf, a.w2[u], part_stride, wrow, h);  // lands behind the forming of h and both barriers
+    if (last && has2) request_values(a.u.add2, ad2, true);   // (so does add2)
+    __syncthreads();  // every wave has read its x columns: the h planes take their place
+    // h = lrelu(acc + b1), zero outside [0, T), split: a lane owns channels c .. c + 3 of a column
+#pragma unroll
+    for (int mi = 0; mi < TM; ++mi)
+#pragma unroll
+      for (int g = 0; g < NG; ++g) {
+        const int c = wave_m * 32 + mi * TILE + 4 * h + 4 * HL * g;
+        const f32x4 bias = bias_h[mi][g];
+#pragma unroll
+        for (int ni = 0; ni < TN; ++ni) {
+          const int m = wave_n * 64 + ni * TILE + r;
+          const int th = f0 + m;
+          const bool inside = th >= 0 && th < T;
+          float v[4];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            v[e] = acc[mi][ni][4 * g + e];
+            if (has_b1) v[e] += bias[e];
+            v[e] = v[e] > 0.f ? v[e] : v[e] * a.slope2[u];
+            v[e] = inside ? v[e] : 0.f;
+            acc[mi][ni][4 * g + e] = 0.f;
+          }
+          split3_store<4>(v, fr + m * ROW + c, plane);
+        }
+      }
+    __syncthreads();
+    // ---- phase 2: conv_{k,1} over h; frame column m reads row margin + m + tap - p
+    ru_contract<C, TILE, true>(wf, a.w2[u], part_stride, wrow, fr + (wave_n * 64 + r - p) * ROW, plane, 1, k, h, acc);
+    if (last) break;
+
+    // ---- between units: y_u = acc + b2 + x_u (the epilogue's order), zero outside [0, T); it is the next unit's
+    // residual, and lrelu(y_u) with the next unit's slope1, split, is the next unit's window
+    ru_request<C, TILE>(wf, a.w1[u + 1], part_stride, wrow, h);
+    const float slope = a.slope1[u + 1];
+    __syncthreads();  // every wave has read its h columns
+#pragma unroll
+    for (int mi = 0; mi < TM; ++mi) {
+      const int c = wave_m * 32 + mi * TILE + r;
+      const float bias = bias_y[mi];
+#pragma unroll
+      for (int n = 0; n < NV; ++n) {
+        const int slot = ru_out_slot<TILE>(wave_n, h, n), t = f0 + slot;
+        const bool inside = t >= 0 && t < T;
+        f32x4 v;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          v[e] = acc[mi][n / NG][(n % NG) * 4 + e];
+          acc[mi][n / NG][(n % NG) * 4 + e] = 0.f;
+        }
+        if (has_b2) v += bias;
+        v += res[mi][n];
+        if (!inside) v = f32x4{0.f, 0.f, 0.f, 0.f};
+        res[mi][n] = v;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float s = v[e] > 0.f ? v[e] : v[e] * slope;
+          __bf16 hi, mid, lo;
+          split3(s, hi, mid, lo);
+          __bf16* dst = fr + (slot + e) * ROW + c;
+          dst[0] = hi;
+          dst[plane] = mid;
+          dst[2 * plane] = lo;
+        }
+      }
+    }
+  }
+
+  // ---- epilogue of the last unit: that of resunit_split_kernel (acc + bias + x + add2, then / out_div) on the stored
+  // slots edge .. edge + bn_out - 1
+  const float* __restrict__ b2l = a.b2[a.n_units - 1];
+#pragma unroll
+  for (int mi = 0; mi < TM; ++mi) {
+    const int c = wave_m * 32 + mi * TILE + r;
+    const size_t row = ((size_t)b * C + c) * T;
+    f32x4 v[NV];
+#pragma unroll
+    for (int n = 0; n < NV; ++n)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[n][e] = acc[mi][n / NG][(n % NG) * 4 + e];
+    if (b2l != nullptr) {
+      const float bias = b2l[c];
+#pragma unroll
+      for (int n = 0; n < NV; ++n) v[n] += bias;
+    }
+#pragma unroll
+    for (int n = 0; n < NV; ++n) v[n] += res[mi][n];
+    if (has2) {
+#pragma unroll
+      for (int n = 0; n < NV; ++n) v[n] += ad2[mi][n];
+    }
+    if (a.u.out_div != 1.0f) {
+#pragma unroll
+      for (int n = 0; n < NV; ++n) v[n] = v[n] / a.u.out_div;
+    }
+#pragma unroll
+    for (int n = 0; n < NV; ++n) {
+      const int slot = ru_out_slot<TILE>(wave_n, h, n), t = f0 + slot;
+      if (slot >= a.edge && slot < a.edge + a.u.bn_out && t < T) *reinterpret_cast<f32x4*>(a.u.y + row + t) = v[n];
+    }
+  }
+}
+
+struct RbSplitGeom {
+  int H, edge, margin, bn_out, rows, tiles;
+  size_t lds;
+};
+
+// Coverage of the chained block: every unit's own (ru_split_geometry), the pair form, and a frame that keeps at least
+// half of its columns.  Pure host logic.
+static int rb_split_geometry(const pwg_resunit_desc* d, int n_units, const int32_t* dilations, RbSplitGeom* g) {
+  PWG_REQUIRE(d != nullptr && dilations != nullptr, PWG_ERR_NULL, "resblock_split: NULL descriptor or dilations");
+  PWG_REQUIRE(n_units >= 1 && n_units <= kRbMaxUnits, PWG_ERR_UNSUPPORTED, "resblock_split: n_units = %d (1 .. %d)",
+              n_units, kRbMaxUnits);
+  PWG_REQUIRE(d->has_conv2, PWG_ERR_UNSUPPORTED, "resblock_split: single-convolution units are not chained");
+  int dmax = 1, sum = 0;
+  for (int u = 0; u < n_units; ++u) {
+    pwg_resunit_desc du = *d;
+    du.dilation = dilations[u];
+    RuSplitGeom gu;
+    const int rc = ru_split_geometry(&du, &gu);
+    if (rc != PWG_OK) return rc;
+    dmax = dilations[u] > dmax ? dilations[u] : dmax;
+    sum += (d->kernel - 1) / 2 * (dilations[u] + 1);
+  }
+  const int C = d->channels;
+  g->H = C == 32 ? RuSplitCfg<32>::H : RuSplitCfg<64>::H;
+  g->edge = round_up(sum, 4);
+  g->margin = (d->kernel - 1) / 2 * dmax;
+  g->bn_out = g->H - 2 * g->edge;
+  PWG_REQUIRE(g->bn_out >= g->H / 2, PWG_ERR_UNSUPPORTED,
+              "resblock_split: kernel = %d over %d units leaves %d outputs per frame of %d columns", d->kernel, n_units,
+              g->bn_out, g->H);
+  g->rows = g->H + 2 * g->margin;
+  g->lds = (size_t)3 * g->rows * (C + 8) * sizeof(__bf16);
+  PWG_REQUIRE(g->lds <= kRuSplitMaxLds, PWG_ERR_UNSUPPORTED, "resblock_split: the planes (kernel %d) need %zu B of LDS",
+              d->kernel, g->lds);
+  g->tiles = ceil_div(d->t, g->bn_out);
+  return PWG_OK;
+}
+
 }  // namespace
 }  // namespace pwg
 
 using namespace pwg;
+
+extern "C" int pwg_resblock_split_supported(const pwg_resunit_desc* d, int32_t n_units, const int32_t* dilations) {
+  RbSplitGeom g;
+  return rb_split_geometry(d, n_units, dilations, &g) == PWG_OK ? 1 : 0;
+}
+
+extern "C" int pwg_resblock_split_frame(const pwg_resunit_desc* d, int32_t n_units, const int32_t* dilations,
+                                        int32_t* out) {
+  RbSplitGeom g;
+  const int rc = rb_split_geometry(d, n_units, dilations, &g);
+  if (rc != PWG_OK) return rc;
+  PWG_REQUIRE(out != nullptr, PWG_ERR_NULL, "resblock_split_frame: NULL out");
+  out[0] = g.H, out[1] = g.bn_out, out[2] = g.edge, out[3] = g.margin, out[4] = (int32_t)g.lds, out[5] = g.tiles;
+  return PWG_OK;
+}
+
+extern "C" int pwg_resblock_split_forward_cfg(const pwg_resunit_desc* d, int32_t n_units, const int32_t* dilations,
+                                              const float* slopes1, const float* slopes2, const float* x,
+                                              const void* const* w1_split, const float* const* b1,
+                                              const void* const* w2_split, const float* const* b2, const float* add2,
+                                              float* y, int32_t mfma_shape, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  RbSplitGeom g;
+  const int rc = rb_split_geometry(d, n_units, dilations, &g);
+  if (rc != PWG_OK) return rc;
+  PWG_REQUIRE(x && y && w1_split && w2_split && b1 && b2 && slopes1 && slopes2, PWG_ERR_NULL,
+              "resblock_split_forward: NULL pointer");
+  PWG_REQUIRE(x != y, PWG_ERR_BAD_SHAPE, "resblock_split_forward: y must not alias x (frames read their neighbours' columns)");
+  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
+  PWG_REQUIRE(al16(x) && al16(y) && al16(add2), PWG_ERR_BAD_SHAPE,
+              "resblock_split_forward: x / y / add2 must be 16-B aligned");
+  PWG_REQUIRE(mfma_shape == 16 || mfma_shape == 32, PWG_ERR_BAD_SHAPE, "resblock_split_forward: mfma_shape = %d (16 or 32)",
+              mfma_shape);
+  const int C = d->channels;
+  RbSplitArgs a = {};
+  for (int u = 0; u < n_units; ++u) {
+    PWG_REQUIRE(w1_split[u] && w2_split[u], PWG_ERR_NULL, "resblock_split_forward: NULL weight image of unit %d", u);
+    PWG_REQUIRE(al16(w1_split[u]) && al16(w2_split[u]), PWG_ERR_BAD_SHAPE,
+                "resblock_split_forward: the weight images must be 16-B aligned");
+    PWG_REQUIRE(slopes1[u] > 0.f && slopes1[u] < 1.f && slopes2[u] > 0.f && slopes2[u] < 1.f, PWG_ERR_UNSUPPORTED,
+                "resblock_split_forward: slopes of unit %d = %g, %g (0 < slope < 1)", u, (double)slopes1[u],
+                (double)slopes2[u]);
+    a.w1[u] = static_cast<const bf16x8*>(w1_split[u]);
+    a.w2[u] = static_cast<const bf16x8*>(w2_split[u]);
+    a.b1[u] = b1[u], a.b2[u] = b2[u];
+    a.d[u] = dilations[u];
+    a.slope1[u] = slopes1[u], a.slope2[u] = slopes2[u];
+  }
+  a.n_units = n_units, a.margin = g.margin, a.edge = g.edge;
+  a.u.x = x, a.u.add2 = add2, a.u.y = y;
+  a.u.T = d->t, a.u.k = d->kernel, a.u.d1 = dilations[0];
+  a.u.bn_out = g.bn_out, a.u.rows = g.H;
+  a.u.plane = g.rows * (C + 8);
+  a.u.part_stride = image_elems(d->kernel, image_chunks(C), image_m_pad(C)) / 8;
+  PWG_REQUIRE(split_image_addressable(a.u.part_stride * 8), PWG_ERR_UNSUPPORTED,
+              "resblock_split_forward: weight image too large");
+  a.u.slope1 = slopes1[0], a.u.slope2 = slopes2[0], a.u.out_div = d->out_div;
+  void (*kern)(RbSplitArgs) = C == 32 ? (mfma_shape == 32 ? resblock_split_kernel<32, 32> : resblock_split_kernel<32, 16>)
+                                      : (mfma_shape == 32 ? resblock_split_kernel<64, 32> : resblock_split_kernel<64, 16>);
+  if (g.lds > kConvMaxLds && !lds_limit_is_set(reinterpret_cast<const void*>(kern), g.lds)) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)g.lds);
+    PWG_REQUIRE(e == hipSuccess, PWG_ERR_LAUNCH, "resblock_split_forward: cannot raise LDS limit to %zu: %s", g.lds,
+                hipGetErrorString(e));
+  }
+  // the ALGORITHMIC flops and bytes of the N units the launch stands for
+  const double elems = (double)d->batch * C * d->t;
+  const double flops = 2.0 * elems * C * d->kernel * 2 * n_units;
+  const double bytes = 4.0 * (elems * (2 * n_units + (add2 != nullptr)) + 2.0 * n_units * C * C * d->kernel);
+  maybe_poison_lds(stream);
+  {
+    ProfScope prof(stream,
+                   prof_shape_name("resblock_split_kernel", "resblock_split_kernel B%d C%d T%d k%d n%d", d->batch, C, d->t,
+                                   d->kernel, n_units),
+                   flops, bytes);
+    hipLaunchKernelGGL(kern, dim3(g.tiles, d->batch), dim3(256), g.lds, stream, a);
+  }
+  PWG_CHECK_LAUNCH("resblock_split_forward");
+  return PWG_OK;
+}
 
 extern "C" int pwg_resunit_split_supported(const pwg_resunit_desc* d) {
   RuSplitGeom g;

@@ -28,12 +28,14 @@ class GraphedInference:
         self._graphs = {}
         self._state = None
         self._convs = None
+        self._blocks = None
 
     def reset(self):
         """Drop the captured graphs (parameters changed)."""
         self._graphs = {}
         self._state = None
         self._convs = None
+        self._blocks = None
 
     def _param_state(self):
         from . import ops
@@ -52,9 +54,15 @@ class GraphedInference:
             from .layers.conv import each_conv
 
             self._convs = list(each_conv(model))
+            self._blocks = [m for m in model.modules() if hasattr(m, "fuse_block")]
         st.append(tuple(m.precision for m in self._convs))
         # ... and the split-operand switch with its admission table (layers/conv.py): both decide which kernel a layer runs
         st.append(tuple((m.split_exact, m.split_admit_all) for m in self._convs))
+        # ... and whether a residual block may run as one launch, with the table that admits it
+        # (layers/residual_block.py, fuse_block; layers/conv.py, RESBLOCK_SPLIT_ADMITTED)
+        from .layers import conv
+
+        st.append((tuple(m.fuse_block for m in self._blocks), tuple(sorted(conv.RESBLOCK_SPLIT_ADMITTED.items()))))
         return st
 
     def _capture(self, inputs):

@@ -503,6 +503,37 @@ def resunit_split_admitted(channels, kernel, has_conv2, cols, needs_grad, enable
     return form if form is not None and cols >= max(min_cols, RESUNIT_SPLIT_MIN_COLS) else None
 
 
+# Admission table of the chained block of split-operand units (resblock_split_kernel of csrc/resunit_split.hip; DESIGN.md
+# s9.2, "The chained block"; profiles/resblock_split.txt): (channels, kernel) -> (most units per launch, fewest columns
+# per launch = batch x T).  A block of pair-form units all of which route to the one-launch split unit runs as ONE launch,
+# the same bits.  The rule is that of the tables above: a class is listed when, at 16 x 800 frames, every run of the block
+# was faster than every run of the unit launches it replaces, in each of three processes; its column count is the
+# shortest measured launch (16 x 800, 1 x 800, 1 x 100 frames) from which it wins disjointly on.
+# Both k = 3 classes pass in every process, with three units and with two (the block in front of a pending join): at
+# 16 x 800 frames 1.22 - 1.23 x (C = 32, 1115 -> 910 us) and 1.06 - 1.07 x (C = 64, 1608 -> 1503 us), at 1 x 800 frames
+# 1.30 - 1.35 x and 1.23 - 1.25 x.  Their floors are those 1 x 800 launches: the 1 x 100 launches lie under the floors of
+# the units' own rows above, where the block has no split units to replace.  C = 32, k = 7 is disjointly slower with three
+# units (0.90 x: 35 % more matrix work for the frame's discarded edge columns) and overlaps with two; C = 32, k = 11 loses
+# (0.66 x); the 64-channel k = 7 / 11 units run as pairs, and their chain is refused by the kernel.  Not listed.
+RESBLOCK_SPLIT_ADMITTED = {
+    (32, 3): (3, 204800),
+    (64, 3): (3, 102400),
+}
+
+
+def resblock_split_admitted(channels, kernel, n_units, cols, needs_grad, enabled=True):
+    """The admission predicate of the chained block (pure host logic), beside :func:`resunit_split_admitted`: never
+    when a gradient is needed or the split switch is off; else the classes of ``RESBLOCK_SPLIT_ADMITTED``, from two
+    units up to their unit count and from their column count on.  ``split_admit_all`` does not reach it: that switch
+    sends every unit to its one-launch kernel, which is what the tests that set it count.  Whether every unit of the
+    block routes to the one-launch split unit is the caller's to check, what the kernel covers
+    ``ops.resblock_split_supported``'s to say."""
+    if needs_grad or not enabled or n_units < 2:
+        return False
+    max_units, min_cols = RESBLOCK_SPLIT_ADMITTED.get((channels, kernel), (0, 0))
+    return n_units <= max_units and cols >= min_cols
+
+
 def each_conv(module):
     """Every convolution module (:class:`_ConvNd`) of a module tree."""
     return (m for m in module.modules() if isinstance(m, _ConvNd))

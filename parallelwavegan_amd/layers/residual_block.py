@@ -8,7 +8,7 @@ from .. import functional as Fn
 from .. import ops
 from .activation import FusedActivation
 from .conv import Conv1d as _Conv1d
-from .conv import bf16_no_backward_error, group_image, resunit_split_admitted
+from .conv import bf16_no_backward_error, group_image, resblock_split_admitted, resunit_split_admitted
 
 
 from .causal_conv import CausalConv1d, LookaheadLaunch, lookahead_delay  # noqa: E402  (depends on .conv only)
@@ -442,6 +442,42 @@ class HiFiGANResidualBlock(torch.nn.Module):
                 None if (conv2 is None or conv2.bias is None) else conv2.bias.detach(),
                 None if accum is None else accum.contiguous())
 
+    # inference: a block whose units all run as one-launch split units runs as ONE launch where its class is admitted
+    # (resblock_split_kernel of csrc/resunit_split.hip; layers/conv.py, RESBLOCK_SPLIT_ADMITTED): the same bits
+    fuse_block = True
+
+    def _block_one_launch(self, x, m, accum, out_div):
+        """The first ``m`` units on ``x`` as ONE launch of the chained block: ``(m, result)``, or ``(0, x)`` where
+        the block stays on its unit loop -- the switch is off, the class is not admitted, or some unit of the ``m``
+        would not run as a one-launch split unit.  ``m == len(self.convs1)``: the whole block, with ``accum`` and
+        ``out_div`` in the last unit's epilogue; fewer: units ``0 .. m - 1`` as the loop runs them, no addend."""
+        n = len(self.convs1)
+        if (not self.fuse_block or not self.fuse_units or self.use_causal_conv or not self.use_additional_convs
+                or m < 2 or x.dim() != 3):
+            return 0, x  # (a causal block has no resident-tile kernel, and its convolutions no split switch)
+        whole = m == n
+        convs = [cv[1] for cv in self.convs1[:m]] + [cv[1] for cv in self.convs2[:m]]
+        # (before any unit is asked: the predicate is a table look-up, a unit's route builds descriptors)
+        if not resblock_split_admitted(x.shape[1], self.kernel_size, m, x.shape[0] * x.shape[2], False,
+                                       all(cv.split_exact for cv in convs)):
+            return 0, x
+        routes = [self._unit_route(idx, x, accum if whole and idx == n - 1 else None,
+                                   out_div if whole and idx == n - 1 else 1.0) for idx in range(m)]
+        if any(r is None or r[0] != "unit" for r in routes):
+            return 0, x
+        desc = routes[-1][1]  # batch, channels, t, kernel and the last unit's out_div: what the block reads of it
+        dilations = [r[1].dilation for r in routes]
+        if not ops.resblock_split_supported(desc, dilations):
+            return 0, x
+        with torch.no_grad():
+            bias = lambda cv: None if cv.bias is None else cv.bias.detach()
+            c1, c2 = convs[:m], convs[m:]
+            return m, ops.resblock_forward_split(
+                desc, x.contiguous(), dilations, [r[1].slope1 for r in routes], [r[1].slope2 for r in routes],
+                [cv.packed_weight_split() for cv in c1], [bias(cv) for cv in c1],
+                [cv.packed_weight_split() for cv in c2], [bias(cv) for cv in c2],
+                None if not whole or accum is None else accum.contiguous())
+
     def forward(self, x, accum=None, out_div=1.0, accum_join=None):
         """``accum_join``: optional callable evaluated right before the block's last kernel, returning ``accum``
         (streams.run_branches_chained: the previous MRF branch is only waited for there).
@@ -449,6 +485,14 @@ class HiFiGANResidualBlock(torch.nn.Module):
         MRF sum ``cs += block(c); c = cs / num_blocks`` (models/hifigan.py:186-190 in the
         reference) into this block's last kernel."""
         n = len(self.convs1)
+        if accum_join is not None and not getattr(accum_join, "pending", True):
+            accum, accum_join = accum_join(), None  # a join that waits for nothing: resolved here, the block may fuse
+        # the chained block (DESIGN.md s9.2): all units in one launch, or, in front of a pending join, all but the last
+        # one -- the previous MRF branch is still waited for only in front of the block's last kernel
+        first, fused = self._block_one_launch(x, n if accum_join is None else n - 1, accum, out_div)
+        if first == n:
+            return fused
+        x = fused
 
         def acc():
             """the addend of the last kernel, resolved right before that kernel is launched"""
@@ -457,7 +501,7 @@ class HiFiGANResidualBlock(torch.nn.Module):
                 accum, accum_join = accum_join(), None
             return accum
 
-        for idx in range(n):
+        for idx in range(first, n):
             last = idx == n - 1
             act1, conv1 = self.convs1[idx][0], self.convs1[idx][1]
             # (a pending join is passed on as a callable and resolved right before the launch)

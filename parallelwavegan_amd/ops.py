@@ -608,6 +608,53 @@ def resunit_forward_split(desc, x, w1_split, b1, w2_split=None, b2=None, add2=No
     return out
 
 
+def resblock_split_supported(desc, dilations):
+    """Does the chained block of split-operand units (``resblock_split_kernel``, csrc/resunit_split.hip) cover
+    ``len(dilations)`` pair-form units of this geometry?  Host logic only; ``_lib.lib().pwg_last_error()`` names the
+    reason for a False.  ``desc.dilation`` and the descriptor's slopes are not read."""
+    dil = (ctypes.c_int32 * len(dilations))(*[int(v) for v in dilations])
+    return bool(_lib.lib().pwg_resblock_split_supported(ctypes.byref(desc), len(dilations), dil))
+
+
+def resblock_split_frame(desc, dilations):
+    """The frame of the chained block: dict of ``H`` (columns every phase computes), ``bn_out`` (columns a frame
+    stores), ``edge`` (frame columns in front of the first stored one: a frame starts at ``t0 - edge``), ``margin``,
+    ``lds`` and ``tiles``.  Host logic only."""
+    dil = (ctypes.c_int32 * len(dilations))(*[int(v) for v in dilations])
+    out = (ctypes.c_int32 * 6)()
+    _lib.check(_lib.lib().pwg_resblock_split_frame(ctypes.byref(desc), len(dilations), dil, out), "resblock_split_frame")
+    return dict(zip(("H", "bn_out", "edge", "margin", "lds", "tiles"), (int(v) for v in out)))
+
+
+def resblock_forward_split(desc, x, dilations, slopes1, slopes2, w1_split, b1, w2_split, b2, add2=None, out=None,
+                           mfma_shape=None):
+    """``len(dilations)`` chained :func:`resunit_forward_split` units (pair form) as ONE launch, bit for bit the chain
+    at the same MFMA shape: the last unit takes ``add2`` and ``desc.out_div`` (inference only).
+    ``w1_split`` / ``b1`` / ``w2_split`` / ``b2``: one entry per unit (a bias may be None)."""
+    n = len(dilations)
+    assert len(slopes1) == len(slopes2) == len(w1_split) == len(b1) == len(w2_split) == len(b2) == n
+    _require_device(x, add2, out, *b1, *b2)
+    image_bytes = 6 * desc.kernel * desc.channels * desc.channels  # three bf16 parts of a (C, C, k) weight
+    for w in (*w1_split, *w2_split):
+        if w is None or not w.is_cuda or w.dtype != torch.uint8:
+            raise RuntimeError("resblock_forward_split: the weights must be device images of pack_weight_split")
+        assert w.numel() == image_bytes, "resblock_forward_split: not this unit's split image"
+    assert x.numel() == desc.batch * desc.channels * desc.t
+    assert add2 is None or add2.numel() == x.numel()
+    if out is None:
+        out = torch.empty_like(x)
+
+    def ptrs(ts):
+        return (ctypes.c_void_p * n)(*[None if t is None else t.data_ptr() for t in ts])
+
+    _lib.check(_lib.lib().pwg_resblock_split_forward_cfg(
+        ctypes.byref(desc), n, (ctypes.c_int32 * n)(*[int(v) for v in dilations]),
+        (ctypes.c_float * n)(*[float(v) for v in slopes1]), (ctypes.c_float * n)(*[float(v) for v in slopes2]), _ptr(x),
+        ptrs(w1_split), ptrs(b1), ptrs(w2_split), ptrs(b2), _ptr(add2), _ptr(out),
+        16 if mfma_shape is None else int(mfma_shape), _stream()), "resblock_split_forward")
+    return out
+
+
 def _require_frames(frames, batch, what):
     """The device table of a ragged batch: int32 ``(batch,)``, contiguous."""
     if not isinstance(frames, torch.Tensor) or not frames.is_cuda:

@@ -104,7 +104,9 @@ def run_branches_chained(branches, device, inputs=None):
         # capture of that pattern crashes inside hipGraphInstantiate -- run the chain in order on the caller's stream
         res = None
         for fn in branches:
-            res = fn(lambda r=res: r)
+            join = lambda r=res: r
+            join.pending = False  # one stream: nothing is waited for
+            res = fn(join)
         return res
     fork = torch.cuda.Event()
     fork.record(cur)
@@ -119,6 +121,9 @@ def run_branches_chained(branches, device, inputs=None):
                 _record(prev[1], s)  # produced on the previous branch's stream, consumed on this one
                 return prev[1]
 
+            # (a branch may ask whether its join waits for anything: the first branch's does not, and a block that runs
+            # as one launch resolves such a join at its head -- HiFiGANResidualBlock.forward)
+            join.pending = prev is not None
             out = fn(join)
             done = torch.cuda.Event()
             done.record(s)
