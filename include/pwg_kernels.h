@@ -748,6 +748,34 @@ int pwg_wavenet_bf16_layer_forward_cfg(const pwg_wavenet_desc* d, const float* x
                                        const void* packed, const float* b_dil, const float* b_skip, const float* b_out,
                                        float* x_out, float* skips_out, float* z_out, float* g_out, int32_t mfma_shape,
                                        void* stream);
+/* ---- the ragged forms of the layer, fp32 and bf16 (inference; csrc/wavenet.hip, csrc/wavenet_bf16.hip) ----
+ * One launch over a batch whose items have their own lengths (WaveNetResidualBlock.forward of
+ * layers/residual_block.py:102-140 inside the batched form of the decode loop of bin/decode.py:214-243).  frames: device
+ * int32 (batch,), 0 <= frames[b]; item b is the sequence [0, e), e = min(frames[b] * rate, t), inside a row of stride t.
+ * Every read of x, c and skips at a column >= e is replaced by zero -- the three tap windows, the residual, the skip sum,
+ * and the bf16 kernel's separate fp32 residual and skip loads -- so those columns may hold anything, NaN included; the
+ * columns >= e of x_out and skips_out are NOT written (no zero-tail pass is needed between layers: the next layer does
+ * not read them either).  A workgroup whose 64 columns lie at or past e returns before any load, so the cost follows
+ * the lengths; an item of 0 frames does nothing.  The fast staging path is taken where a window lies inside [0, e).
+ * The columns < e of both outputs are bit for bit those of pwg_wavenet_layer_forward (pwg_wavenet_bf16_layer_forward_cfg
+ * at the same mfma_shape) on the item alone: contiguous x[b, :, :e], c[b, :, :e], skips[b, :, :e] with d->t = e; with
+ * every item at t the outputs are the plain call's.  No z_out / g_out.  skips may be NULL; skips_out may alias skips;
+ * x_out must not alias x.  Nothing on the host depends on the table's values: a captured launch serves every set of
+ * lengths.  pwg_wavenet_layer_ragged_supported is pwg_wavenet_layer_supported plus rate >= 4, rate % 4 == 0 (an item
+ * ends where a row of t % 4 == 0 may end: a value of four samples is stored whole or not at all), with the kernel's
+ * limit on t (128 * t * 4 < 2^32: byte offsets into an item are 32-bit); pure host logic, no device needed, the reason
+ * for 0 in pwg_last_error.  It answers for both precisions.  A NULL or misaligned (4 B) table, rate <= 0 or another rate
+ * it refuses, a causal descriptor and everything the plain calls refuse are refused with a message, launching nothing.
+ * mfma_shape of the bf16 form: 32, 16, or 0 = the default of pwg_wavenet_bf16_layer_forward.
+ * These three symbols are purely additive, so pwg_abi_version() stays 15. */
+int pwg_wavenet_layer_ragged_supported(const pwg_wavenet_desc* d, int32_t rate);
+int pwg_wavenet_layer_forward_ragged(const pwg_wavenet_desc* d, const float* x, const float* c, const float* skips,
+                                     const float* packed, const float* b_dil, const float* b_skip, const float* b_out,
+                                     float* x_out, float* skips_out, const int32_t* frames, int32_t rate, void* stream);
+int pwg_wavenet_bf16_layer_forward_ragged(const pwg_wavenet_desc* d, const float* x, const float* c, const float* skips,
+                                          const void* packed, const float* b_dil, const float* b_skip,
+                                          const float* b_out, float* x_out, float* skips_out, int32_t mfma_shape,
+                                          const int32_t* frames, int32_t rate, void* stream);
 /* ---- the two streaming forms of the layer with bf16 operands (opt-in; csrc/wavenet_stream_bf16.hip) ----
  * pwg_wavenet_stream_forward and pwg_wavenet_stream_delayed_forward computed the way pwg_wavenet_bf16_layer_forward
  * computes: the windows of x and c (history, conditioning line and chunk alike) are rounded to bf16 while they are

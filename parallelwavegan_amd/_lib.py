@@ -241,6 +241,10 @@ SIGNATURES = {
     "pwg_wavenet_bf16_pack_weights": (ctypes.c_int, [ctypes.POINTER(WaveNetDesc)] + [_vp] * 10),
     "pwg_wavenet_bf16_layer_forward": (ctypes.c_int, [ctypes.POINTER(WaveNetDesc)] + [_vp] * 12),
     "pwg_wavenet_bf16_layer_forward_cfg": (ctypes.c_int, [ctypes.POINTER(WaveNetDesc)] + [_vp] * 11 + [_i32, _vp]),
+    "pwg_wavenet_layer_ragged_supported": (ctypes.c_int, [ctypes.POINTER(WaveNetDesc), _i32]),
+    "pwg_wavenet_layer_forward_ragged": (ctypes.c_int, [ctypes.POINTER(WaveNetDesc)] + [_vp] * 10 + [_i32, _vp]),
+    "pwg_wavenet_bf16_layer_forward_ragged": (ctypes.c_int, [ctypes.POINTER(WaveNetDesc)] + [_vp] * 9
+                                              + [_i32, _vp, _i32, _vp]),
     "pwg_wavenet_stream_bf16_supported": (ctypes.c_int, [ctypes.POINTER(WaveNetDesc)]),
     "pwg_wavenet_stream_bf16_forward": (ctypes.c_int, [ctypes.POINTER(WaveNetDesc)] + [_vp] * 14),
     "pwg_wavenet_stream_bf16_delayed_supported": (ctypes.c_int, [ctypes.POINTER(WaveNetDesc), _i32]),

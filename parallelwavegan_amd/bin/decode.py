@@ -3,8 +3,11 @@ of the reference's ``bin/decode.py`` (its mel -> waveform case, decode.py:158-24
 
 A non-causal HiFi-GAN checkpoint is decoded ``--batch-size`` utterances per forward through
 ``utils.RaggedSynthesizer`` -- every utterance exactly what ``model.inference`` gives for it alone --
-and a non-causal, reflect-padded (multi-band) MelGAN checkpoint through ``utils.MelGANRaggedSynthesizer`` (s9.5);
-every other supported generator runs the reference's loop over ``model.inference`` (decode.py:214-243).  The float ->
+a non-causal, reflect-padded (multi-band) MelGAN checkpoint through ``utils.MelGANRaggedSynthesizer`` (s9.5), and a
+Parallel WaveGAN checkpoint whose ``ragged_unsupported_reason()`` is None (the non-causal v1 geometry) through
+``utils.PWGRaggedSynthesizer`` (s9.6), its noise drawn on the device; every other supported generator -- a causal
+Parallel WaveGAN, one with a MelGAN upsampler or other channel widths -- runs the reference's loop over
+``model.inference`` (decode.py:214-243).  The float ->
 int16 step is ``utils.to_pcm16`` on the device and the files are written with the standard library's ``wave`` module.
 The RTF is timed after a device synchronisation; the reference stops its clock without one.
 """
@@ -51,8 +54,9 @@ def _parser():
     p.add_argument("--normalize-before", default=False, action="store_true",
                    help="normalise the features with the registered statistics before the model")
     p.add_argument("--batch-size", default=16, type=int,
-                   help="utterances per forward of a non-causal HiFi-GAN or MelGAN (utils.RaggedSynthesizer / "
-                        "utils.MelGANRaggedSynthesizer; default 16)")
+                   help="utterances per forward of a non-causal HiFi-GAN, MelGAN or Parallel WaveGAN "
+                        "(utils.RaggedSynthesizer / utils.MelGANRaggedSynthesizer / utils.PWGRaggedSynthesizer; "
+                        "default 16); other generators decode one utterance per call")
     p.add_argument("--verbose", type=int, default=1, help="logging level; higher is more logging")
     return p
 
@@ -73,8 +77,8 @@ def main(argv=None):
     import yaml
 
     from ..datasets import MelDataset
-    from ..models import HiFiGANGenerator, MelGANGenerator
-    from ..utils import MelGANRaggedSynthesizer, RaggedSynthesizer, load_model
+    from ..models import HiFiGANGenerator, MelGANGenerator, ParallelWaveGANGenerator
+    from ..utils import MelGANRaggedSynthesizer, PWGRaggedSynthesizer, RaggedSynthesizer, load_model
     from ..utils.streaming import to_pcm16
 
     args = _parser().parse_args(argv)
@@ -120,9 +124,11 @@ def main(argv=None):
     ragged = isinstance(model, HiFiGANGenerator) and not model.use_causal_conv \
         and model.output_conv[1].out_channels == 1
     ragged_melgan = isinstance(model, MelGANGenerator) and _melgan_is_ragged(model)
+    ragged_pwg = isinstance(model, ParallelWaveGANGenerator) and model.ragged_unsupported_reason() is None
     total_rtf, n_done = 0.0, 0
-    if ragged or ragged_melgan:
-        synth = (RaggedSynthesizer if ragged else MelGANRaggedSynthesizer)(model, max_batch=args.batch_size)
+    if ragged or ragged_melgan or ragged_pwg:
+        cls = RaggedSynthesizer if ragged else MelGANRaggedSynthesizer if ragged_melgan else PWGRaggedSynthesizer
+        synth = cls(model, max_batch=args.batch_size)
         logging.info(f"{gtype}: {args.batch_size} utterances of their own lengths per forward "
                      f"({type(synth).__name__}).")
         # one call per batch_size utterances in dump order: the host holds that many utterances at a time

@@ -50,8 +50,21 @@ struct WnArgs {
             // loads / stores, 8 = no operand DMA
 };
 
-template <int AUX>
-__global__ __launch_bounds__(256, 2) void wavenet_layer_kernel(WnArgs a) {
+// The ragged form (inference): item b ends at column E = min(frames[b] * rate, T); T stays the row stride.
+struct WnRaggedArgs : WnArgs {
+  const int* frames;  // (batch,) device table, frames per item
+  int rate;           // columns per frame
+};
+template <bool RAGGED>
+using WnArgsOf = typename std::conditional<RAGGED, WnRaggedArgs, WnArgs>::type;
+
+// RAGGED: the sequence of item b is [0, E) inside a row of stride T.  Every read of x, c and the skip sum at a column
+// >= E is replaced by zero (the staging range checks and the epilogue's bounds take E where the plain form takes T), so
+// the row may hold anything there; nothing at or past E is written, and a workgroup whose columns lie at or past E
+// returns before any load.  An element's sum order depends on the element alone: the columns < E are bit for bit the
+// plain kernel's on the item alone with T = E.  No z / g outputs.
+template <int AUX, bool RAGGED>
+__global__ __launch_bounds__(256, 2) void wavenet_layer_kernel(WnArgsOf<RAGGED> a) {
   constexpr int ROWS = WN_K * WN_R + AUX;  // 272 operand rows
   constexpr int NQ1 = ROWS / 8;            // 16-B weight records per lane and row tile in phase 1 (4 k-steps each)
   constexpr int NQ2 = WN_R / 8;            // phase 2: K = 64 rows of g
@@ -65,6 +78,12 @@ __global__ __launch_bounds__(256, 2) void wavenet_layer_kernel(WnArgs a) {
   const int b = blockIdx.y;
   const int n0 = blockIdx.x * WN_COLS;
   const int T = a.T;
+  int E = T;  // end of this item's sequence
+  if constexpr (RAGGED) {
+    const long end = (long)a.frames[b] * a.rate;  // (read once per workgroup)
+    E = end < T ? (int)end : T;
+    if (n0 >= E) return;
+  }
 
   // ---- stage the operand tile: window `tap` of x starts at sample n0 + tap * d - pad
   {
@@ -76,7 +95,7 @@ __global__ __launch_bounds__(256, 2) void wavenet_layer_kernel(WnArgs a) {
       const int tap = r0 / WN_R;
       const int f0 = is_x ? n0 + tap * a.dil - a.pad : n0;  // first sample of the window
       const int ch0 = is_x ? r0 - tap * WN_R : r0 - WN_K * WN_R;
-      if (__builtin_amdgcn_readfirstlane((f0 >= 0 && f0 + WN_COLS <= T) ? 1 : 0)) {
+      if (__builtin_amdgcn_readfirstlane((f0 >= 0 && f0 + WN_COLS <= E) ? 1 : 0)) {
         const unsigned off = (unsigned)((ch0 + (lane >> 4)) * T + f0 + 4 * (lane & 15)) * 4u;
         if (is_x) __builtin_amdgcn_raw_ptr_buffer_load_lds(x_rs, (lds_ptr_t)(tile + r0 * WN_COLS), 16, off, 0, 0, 0);
         else __builtin_amdgcn_raw_ptr_buffer_load_lds(c_rs, (lds_ptr_t)(tile + r0 * WN_COLS), 16, off, 0, 0, 0);
@@ -85,7 +104,7 @@ __global__ __launch_bounds__(256, 2) void wavenet_layer_kernel(WnArgs a) {
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) {
           const int f = f0 + lane;
-          const unsigned off = (f >= 0 && f < T) ? (unsigned)((ch0 + rr) * T + f) * 4u : 0xFFFFFFFCu;
+          const unsigned off = (f >= 0 && f < E) ? (unsigned)((ch0 + rr) * T + f) * 4u : 0xFFFFFFFCu;
           if (is_x) __builtin_amdgcn_raw_ptr_buffer_load_lds(x_rs, (lds_ptr_t)(tile + (r0 + rr) * WN_COLS), 4, off, 0, 0, 0);
           else __builtin_amdgcn_raw_ptr_buffer_load_lds(c_rs, (lds_ptr_t)(tile + (r0 + rr) * WN_COLS), 4, off, 0, 0, 0);
         }
@@ -160,14 +179,14 @@ __global__ __launch_bounds__(256, 2) void wavenet_layer_kernel(WnArgs a) {
       const float zt = acc[0][r] + bt[r], zs = acc[1][r] + bs[r];
       const float g = (a.dbg & 2) ? zt * zs : gate_fast(zt, zs);
       tile[(h * 32 + rl) * WN_COLS + cn * 32 + l31] = g;
-      if (a.z_out) {  // (training: the gate input goes out through the transposition scratch, 16-B stores)
+      if (!RAGGED && a.z_out) {  // (training: the gate input goes out through the transposition scratch, 16-B stores)
         scr[rl * 36 + l31] = zt;
         scr[32 * 36 + rl * 36 + l31] = zs;
       }
       acc[0][r] = 0.f;
       acc[1][r] = 0.f;
     }
-    if (a.z_out) {
+    if (!RAGGED && a.z_out) {
       const long zb = (long)b * WN_G * T + nq;
 #pragma unroll
       for (int ps = 0; ps < 4; ++ps) {
@@ -189,7 +208,7 @@ __global__ __launch_bounds__(256, 2) void wavenet_layer_kernel(WnArgs a) {
     }
   }
   __syncthreads();
-  if (a.g_out) {
+  if (!RAGGED && a.g_out) {
     // the gate output tile is row-major in LDS: 64 rows x 16 float4, 4 per lane
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -258,7 +277,7 @@ __global__ __launch_bounds__(256, 2) void wavenet_layer_kernel(WnArgs a) {
     float4 sv = *reinterpret_cast<const float4*>(scr + rl * 36 + tcol);
     const float4 ov = *reinterpret_cast<const float4*>(scr + 32 * 36 + rl * 36 + tcol);
     if (vec) {
-      if (nq < T) {  // (T % 4 == 0: a float4 is inside the sequence or outside it)
+      if (nq < E) {  // (T % 4 == 0, and so is E: a float4 is inside the sequence or outside it)
         if (a.skips) {
           const float4 k = *reinterpret_cast<const float4*>(a.skips + o);
           sv.x += k.x; sv.y += k.y; sv.z += k.z; sv.w += k.w;
@@ -271,7 +290,7 @@ __global__ __launch_bounds__(256, 2) void wavenet_layer_kernel(WnArgs a) {
       const float se[4] = {sv.x, sv.y, sv.z, sv.w}, oe[4] = {ov.x, ov.y, ov.z, ov.w};
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        if (nq + e < T) {
+        if (nq + e < E) {
           float v = se[e] + (a.skips ? a.skips[o + e] : 0.f);
           if (a.skip_mul != 1.0f) v *= a.skip_mul;
           a.skips_out[o + e] = v;
@@ -956,6 +975,27 @@ static bool wavenet_ok(const pwg_wavenet_desc* d) {
   return true;
 }
 
+// wavenet_ok for the ragged form, with the reason for a refusal in pwg_last_error, plus what the masked stores ask: an
+// item ends on a multiple of 4 columns, as a row of T % 4 == 0 does (a value of four samples is stored whole or not at all)
+static int wavenet_ragged_check(const pwg_wavenet_desc* d, int rate) {
+  PWG_REQUIRE(d != nullptr, PWG_ERR_NULL, "wavenet_ragged: NULL descriptor");
+  PWG_REQUIRE(d->residual_channels == WN_R && d->gate_channels == WN_G && d->skip_channels == WN_S && d->kernel == WN_K,
+              PWG_ERR_UNSUPPORTED,
+              "wavenet_ragged: residual / gate / skip channels %d / %d / %d, kernel %d (built for 64 / 128 / 64, kernel 3)",
+              d->residual_channels, d->gate_channels, d->skip_channels, d->kernel);
+  PWG_REQUIRE(d->aux_channels == 80, PWG_ERR_UNSUPPORTED, "wavenet_ragged: aux_channels = %d (built for 80)", d->aux_channels);
+  PWG_REQUIRE(!d->causal, PWG_ERR_UNSUPPORTED, "wavenet_ragged: causal layers are not built (symmetric padding only)");
+  PWG_REQUIRE(d->batch >= 1 && d->batch <= 65535, PWG_ERR_UNSUPPORTED, "wavenet_ragged: batch = %d (1 .. 65535)", d->batch);
+  PWG_REQUIRE(d->t >= 1 && d->dilation >= 1, PWG_ERR_BAD_SHAPE, "wavenet_ragged: t = %d, dilation = %d (>= 1)", d->t,
+              d->dilation);
+  // (the kernel's byte offsets into an item are 32-bit; the bound is the plain form's, whose widest tensor has 128 rows)
+  PWG_REQUIRE((long)WN_G * d->t * 4 < (1L << 32), PWG_ERR_UNSUPPORTED, "wavenet_ragged: t = %d is too long (< %ld)", d->t,
+              (1L << 32) / (WN_G * 4));
+  PWG_REQUIRE(rate >= 4 && (rate & 3) == 0, PWG_ERR_UNSUPPORTED,
+              "wavenet_ragged: rate = %d (a positive multiple of 4: an item ends where a row of T %% 4 == 0 may end)", rate);
+  return PWG_OK;
+}
+
 }  // namespace pwg
 
 using namespace pwg;
@@ -1013,7 +1053,7 @@ int pwg_wavenet_layer_forward(const pwg_wavenet_desc* d, const float* x, const f
   PWG_REQUIRE(!d->causal, PWG_ERR_UNSUPPORTED, "wavenet_layer_forward: the causal form is not built (residual = last tap window)");
   constexpr int AUX = 80;
   const size_t lds = (size_t)(WN_K * WN_R + AUX) * WN_COLS * sizeof(float);
-  void (*kern)(WnArgs) = wavenet_layer_kernel<AUX>;
+  void (*kern)(WnArgs) = wavenet_layer_kernel<AUX, false>;
   if (lds > 64 * 1024 && !lds_limit_is_set(reinterpret_cast<const void*>(kern), lds)) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     PWG_REQUIRE(e == hipSuccess, PWG_ERR_LAUNCH, "wavenet_layer_forward: cannot raise the LDS limit to %zu: %s", lds, hipGetErrorString(e));
@@ -1207,3 +1247,68 @@ int pwg_wavenet_weight_backward(const pwg_wavenet_desc* d, const float* dz, cons
 }
 
 }  // extern "C"
+
+// ---- the ragged form (inference).  Outside the block above, whose entry points the float64 matrix of
+// tests/test_wavenet_matrix_gpu.py drives one by one; these two are driven, bit for bit against the plain forward, by
+// tests/test_ragged_pwg_gpu.py and tests/test_ragged_pwg_host.py
+extern "C" int pwg_wavenet_layer_ragged_supported(const pwg_wavenet_desc* d, int32_t rate) {
+  return wavenet_ragged_check(d, rate) == PWG_OK ? 1 : 0;
+}
+
+extern "C" int pwg_wavenet_layer_forward_ragged(const pwg_wavenet_desc* d, const float* x, const float* c,
+                                                const float* skips, const float* packed, const float* b_dil,
+                                                const float* b_skip, const float* b_out, float* x_out, float* skips_out,
+                                                const int32_t* frames, int32_t rate, void* stream_) {
+  PWG_REQUIRE(frames != nullptr, PWG_ERR_NULL, "wavenet_layer_forward_ragged: NULL frames table");
+  PWG_REQUIRE((reinterpret_cast<uintptr_t>(frames) & 3u) == 0, PWG_ERR_BAD_SHAPE,
+              "wavenet_layer_forward_ragged: the frames table must be 4-B aligned");
+  const int rc = wavenet_ragged_check(d, rate);  // (a causal descriptor and rate <= 0 included)
+  if (rc != PWG_OK) return rc;
+  PWG_REQUIRE(x && c && packed && x_out && skips_out, PWG_ERR_NULL, "wavenet_layer_forward_ragged: NULL pointer");
+  PWG_REQUIRE(x != x_out, PWG_ERR_BAD_SHAPE,
+              "wavenet_layer_forward_ragged: x_out must not alias x (tiles read their neighbours' samples)");
+  hipStream_t stream = (hipStream_t)stream_;
+  WnRaggedArgs a;
+  a.x = x;
+  a.c = c;
+  a.skips = skips;
+  a.w1 = packed;
+  a.w2 = packed + (size_t)(WN_K * WN_R + d->aux_channels) * WN_G;
+  a.b_dil = b_dil;
+  a.b_skip = b_skip;
+  a.b_out = b_out;
+  a.x_out = x_out;
+  a.skips_out = skips_out;
+  a.z_out = nullptr;
+  a.g_out = nullptr;
+  a.T = d->t;
+  a.dil = d->dilation;
+  a.pad = d->dilation;
+  a.out_mul = d->out_mul;
+  a.skip_mul = d->skip_mul;
+  a.dbg = 0;
+  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
+  a.vec_ok = al16(x_out) && al16(skips) && al16(skips_out);
+  a.frames = frames;
+  a.rate = rate;
+  constexpr int AUX = 80;
+  const size_t lds = (size_t)(WN_K * WN_R + AUX) * WN_COLS * sizeof(float);
+  void (*kern)(WnRaggedArgs) = wavenet_layer_kernel<AUX, true>;
+  if (lds > 64 * 1024 && !lds_limit_is_set(reinterpret_cast<const void*>(kern), lds)) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    PWG_REQUIRE(e == hipSuccess, PWG_ERR_LAUNCH, "wavenet_layer_forward_ragged: cannot raise the LDS limit to %zu: %s", lds,
+                hipGetErrorString(e));
+  }
+  // (upper bounds: a tile past its item's end returns at once)
+  const double samples = (double)d->batch * d->t;
+  const double flops = 2.0 * samples * (WN_G * (double)(WN_K * WN_R + AUX) + (double)(WN_S + WN_R) * WN_R);
+  const double bytes = 4.0 * (samples * (WN_R * 4 + AUX + (skips ? WN_S : 0))) + 4.0 * (double)pwg_wavenet_packed_weight_floats(d);
+  maybe_poison_lds(stream);
+  {
+    ProfScope prof(stream, prof_shape_name("wavenet_layer_ragged_kernel", "B%d T%d d%d", d->batch, d->t, d->dilation),
+                   flops, bytes);
+    hipLaunchKernelGGL(kern, dim3(ceil_div(d->t, WN_COLS), d->batch), dim3(256), lds, stream, a);
+  }
+  PWG_CHECK_LAUNCH("wavenet_layer_forward_ragged");
+  return PWG_OK;
+}

@@ -29,6 +29,7 @@
 #include "wavenet_bf16.h"
 
 #include <stdint.h>
+#include <type_traits>
 
 namespace pwg {
 namespace {
@@ -52,9 +53,21 @@ struct WbArgs {
   float out_mul, skip_mul;
 };
 
+// The ragged form (inference): item b ends at column E = min(frames[b] * rate, T); T stays the row stride.
+struct WbRaggedArgs : WbArgs {
+  const int* frames;  // (batch,) device table, frames per item
+  int rate;           // columns per frame
+};
+template <bool RAGGED>
+using WbArgsOf = typename std::conditional<RAGGED, WbRaggedArgs, WbArgs>::type;
+
 // TILE: MFMA shape (32: 32x32x16, 16: 16x16x32).  A wave owns a 32 x 32 block of each half: TM x TN MFMA tiles.
-template <int TILE>
-__global__ __launch_bounds__(256, 2) void wavenet_bf16_layer_kernel(WbArgs a) {
+// RAGGED: the sequence of item b is [0, E) inside a row of stride T.  Every read of x, c and the skip sum at a column
+// >= E -- the staged windows and the fp32 residual and skip loads -- is replaced by zero, nothing at or past E is written,
+// and a workgroup whose columns lie at or past E returns before any load.  The columns < E are bit for bit the plain
+// kernel's on the item alone with T = E at the same TILE.  No z / g outputs.
+template <int TILE, bool RAGGED>
+__global__ __launch_bounds__(256, 2) void wavenet_bf16_layer_kernel(WbArgsOf<RAGGED> a) {
   constexpr int HL = 64 / TILE;      // lane groups along the reduction (2 / 4)
   constexpr int KSTEP = 8 * HL;      // reduction elements per MFMA (16 / 32)
   constexpr int NS1 = K1 / KSTEP;    // phase-1 steps (18 / 9)
@@ -77,6 +90,12 @@ __global__ __launch_bounds__(256, 2) void wavenet_bf16_layer_kernel(WbArgs a) {
   const int b = blockIdx.y;
   const int n0 = blockIdx.x * BCOLS;
   const int T = a.T, dil = a.dil;
+  int E = T;  // end of this item's sequence
+  if constexpr (RAGGED) {
+    const long end = (long)a.frames[b] * a.rate;  // (read once per workgroup)
+    E = end < T ? (int)end : T;
+    if (n0 >= E) return;
+  }
   const float* xb = a.x + (long)b * BR * T;
   const float* cb = a.c + (long)b * BA * T;
 
@@ -95,7 +114,7 @@ __global__ __launch_bounds__(256, 2) void wavenet_bf16_layer_kernel(WbArgs a) {
   // loaded right behind the staging loads (their latency hides under the whole matrix work).
   float xres[TM][TN][NREG], sres[TM][TN][NREG];
   {
-    const bool interior = n0 - dil >= 0 && n0 + BCOLS + dil <= T;
+    const bool interior = n0 - dil >= 0 && n0 + BCOLS + dil <= E;
     f32x4 st[ITEMS][8];
 #pragma unroll
     for (int it = 0; it < ITEMS; ++it) {
@@ -115,7 +134,7 @@ __global__ __launch_bounds__(256, 2) void wavenet_bf16_layer_kernel(WbArgs a) {
           } else {
 #pragma unroll
             for (int e = 0; e < 4; ++e)
-              if (f + e >= 0 && f + e < T) v[e] = p[f + e];
+              if (f + e >= 0 && f + e < E) v[e] = p[f + e];
           }
         }
         st[it][j] = v;
@@ -129,8 +148,8 @@ __global__ __launch_bounds__(256, 2) void wavenet_bf16_layer_kernel(WbArgs a) {
 #pragma unroll
         for (int i = 0; i < NREG; ++i) {
           const long o = ((long)b * BR + h * 32 + mi * TILE + rowin(i)) * T + n;
-          xres[mi][ni][i] = n < T ? a.x[o] : 0.f;
-          sres[mi][ni][i] = (a.skips && n < T) ? a.skips[o] : 0.f;
+          xres[mi][ni][i] = n < E ? a.x[o] : 0.f;
+          sres[mi][ni][i] = (a.skips && n < E) ? a.skips[o] : 0.f;
         }
       }
 #pragma unroll
@@ -210,7 +229,7 @@ __global__ __launch_bounds__(256, 2) void wavenet_bf16_layer_kernel(WbArgs a) {
             const float zs = acc[1][mi][ni][i4 + e] + bias[BR + row];
             const __bf16 g = (__bf16)gate_fp32(zt, zs);
             gv[e] = g;
-            if (a.z_out && n < T) {
+            if (!RAGGED && a.z_out && n < T) {
               a.z_out[((long)b * BG + row) * T + n] = zt;
               a.z_out[((long)b * BG + BR + row) * T + n] = zs;
               a.g_out[((long)b * BR + row) * T + n] = (float)g;
@@ -259,7 +278,7 @@ __global__ __launch_bounds__(256, 2) void wavenet_bf16_layer_kernel(WbArgs a) {
 #pragma unroll
     for (int ni = 0; ni < TN; ++ni) {
       const int n = n0 + cn * 32 + ni * TILE + r;
-      if (n >= T) continue;
+      if (n >= E) continue;
 #pragma unroll
       for (int i = 0; i < NREG; ++i) {
         const int row = h * 32 + mi * TILE + rowin(i);
@@ -318,11 +337,28 @@ static int bf16_layer_check(const pwg_wavenet_desc* d) {
   return PWG_OK;
 }
 
+// What the ragged forms ask beyond the plain ones (one rule for the fp32 and the bf16 layer: wavenet.hip's masked 16-B
+// stores need an item to end on a multiple of 4 columns; pwg_wavenet_layer_ragged_supported)
+static int bf16_ragged_check(const int32_t* frames, int rate) {
+  PWG_REQUIRE(frames != nullptr, PWG_ERR_NULL, "wavenet_bf16_layer_forward_ragged: NULL frames table");
+  PWG_REQUIRE((reinterpret_cast<uintptr_t>(frames) & 3u) == 0, PWG_ERR_BAD_SHAPE,
+              "wavenet_bf16_layer_forward_ragged: the frames table must be 4-B aligned");
+  PWG_REQUIRE(rate >= 4 && (rate & 3) == 0, PWG_ERR_UNSUPPORTED,
+              "wavenet_bf16_layer_forward_ragged: rate = %d (a positive multiple of 4)", rate);
+  return PWG_OK;
+}
+
+template <bool RAGGED>
 static int bf16_layer_forward(const pwg_wavenet_desc* d, const float* x, const float* c, const float* skips,
                               const void* packed, const float* b_dil, const float* b_skip, const float* b_out, float* x_out,
-                              float* skips_out, float* z_out, float* g_out, int mfma_shape, hipStream_t stream) {
+                              float* skips_out, float* z_out, float* g_out, int mfma_shape, hipStream_t stream,
+                              const int32_t* frames = nullptr, int rate = 0) {
   int rc = bf16_layer_check(d);
   if (rc != PWG_OK) return rc;
+  if constexpr (RAGGED) {
+    rc = bf16_ragged_check(frames, rate);
+    if (rc != PWG_OK) return rc;
+  }
   PWG_REQUIRE(x && c && packed && x_out && skips_out, PWG_ERR_NULL, "wavenet_bf16_layer_forward: NULL pointer");
   PWG_REQUIRE(x != x_out, PWG_ERR_BAD_SHAPE, "wavenet_bf16_layer_forward: x_out must not alias x (tiles read their neighbours' samples)");
   PWG_REQUIRE((z_out == nullptr) == (g_out == nullptr), PWG_ERR_BAD_SHAPE, "wavenet_bf16_layer_forward: z_out and g_out go together");
@@ -332,7 +368,7 @@ static int bf16_layer_forward(const pwg_wavenet_desc* d, const float* x, const f
               "wavenet_bf16_layer_forward: x and c must be 4-B aligned");
   PWG_REQUIRE(mfma_shape == 16 || mfma_shape == 32, PWG_ERR_BAD_SHAPE, "wavenet_bf16_layer_forward: mfma_shape = %d (16 or 32)",
               mfma_shape);
-  WbArgs a;
+  WbArgsOf<RAGGED> a;
   a.x = x;
   a.c = c;
   a.skips = skips;
@@ -349,6 +385,8 @@ static int bf16_layer_forward(const pwg_wavenet_desc* d, const float* x, const f
   a.dil = d->dilation;
   a.out_mul = d->out_mul;
   a.skip_mul = d->skip_mul;
+  if constexpr (RAGGED) a.frames = frames, a.rate = rate;
+  // (the ragged form's figures are upper bounds: a tile past its item's end returns at once)
   const double samples = (double)d->batch * d->t;
   const double flops = 2.0 * samples * (BG * (double)(BK * BR + BA) + (double)(BS + BR) * BR);
   const double bytes = 4.0 * samples * (BR * 4 + BA + (skips ? BS : 0) + (z_out ? BG + BR : 0)) +
@@ -356,11 +394,11 @@ static int bf16_layer_forward(const pwg_wavenet_desc* d, const float* x, const f
   const dim3 grid(ceil_div(d->t, BCOLS), d->batch);
   maybe_poison_lds(stream);
   {
-    ProfScope prof(stream, "wavenet_bf16_layer_kernel", flops, bytes);
+    ProfScope prof(stream, RAGGED ? "wavenet_bf16_layer_ragged_kernel" : "wavenet_bf16_layer_kernel", flops, bytes);
     if (mfma_shape == 32)
-      hipLaunchKernelGGL(wavenet_bf16_layer_kernel<32>, grid, dim3(256), kLds, stream, a);
+      hipLaunchKernelGGL((wavenet_bf16_layer_kernel<32, RAGGED>), grid, dim3(256), kLds, stream, a);
     else
-      hipLaunchKernelGGL(wavenet_bf16_layer_kernel<16>, grid, dim3(256), kLds, stream, a);
+      hipLaunchKernelGGL((wavenet_bf16_layer_kernel<16, RAGGED>), grid, dim3(256), kLds, stream, a);
   }
   PWG_CHECK_LAUNCH("wavenet_bf16_layer_forward");
   return PWG_OK;
@@ -396,14 +434,23 @@ extern "C" int pwg_wavenet_bf16_layer_forward(const pwg_wavenet_desc* d, const f
                                               const void* packed, const float* b_dil, const float* b_skip,
                                               const float* b_out, float* x_out, float* skips_out, float* z_out,
                                               float* g_out, void* stream) {
-  return bf16_layer_forward(d, x, c, skips, packed, b_dil, b_skip, b_out, x_out, skips_out, z_out, g_out,
-                            kDefaultMfmaShape, (hipStream_t)stream);
+  return bf16_layer_forward<false>(d, x, c, skips, packed, b_dil, b_skip, b_out, x_out, skips_out, z_out, g_out,
+                                   kDefaultMfmaShape, (hipStream_t)stream);
 }
 
 extern "C" int pwg_wavenet_bf16_layer_forward_cfg(const pwg_wavenet_desc* d, const float* x, const float* c,
                                                   const float* skips, const void* packed, const float* b_dil,
                                                   const float* b_skip, const float* b_out, float* x_out, float* skips_out,
                                                   float* z_out, float* g_out, int32_t mfma_shape, void* stream) {
-  return bf16_layer_forward(d, x, c, skips, packed, b_dil, b_skip, b_out, x_out, skips_out, z_out, g_out, mfma_shape,
-                            (hipStream_t)stream);
+  return bf16_layer_forward<false>(d, x, c, skips, packed, b_dil, b_skip, b_out, x_out, skips_out, z_out, g_out,
+                                   mfma_shape, (hipStream_t)stream);
+}
+
+extern "C" int pwg_wavenet_bf16_layer_forward_ragged(const pwg_wavenet_desc* d, const float* x, const float* c,
+                                                     const float* skips, const void* packed, const float* b_dil,
+                                                     const float* b_skip, const float* b_out, float* x_out,
+                                                     float* skips_out, int32_t mfma_shape, const int32_t* frames,
+                                                     int32_t rate, void* stream) {
+  return bf16_layer_forward<true>(d, x, c, skips, packed, b_dil, b_skip, b_out, x_out, skips_out, nullptr, nullptr,
+                                  mfma_shape == 0 ? kDefaultMfmaShape : mfma_shape, (hipStream_t)stream, frames, rate);
 }

@@ -297,6 +297,48 @@ class WaveNetResidualBlock(torch.nn.Module):
                            c_delay, skips, skip_line, hist[0], hist[1],
                            self.stream_image_bf16() if bf16 else self.stream_image(), b_d, b_s, b_o, valid)
 
+    # ---- utterances of different lengths in one batch (the ragged forms of csrc/wavenet.hip and csrc/wavenet_bf16.hip;
+    # DESIGN.md s9.6): one launch, no per-convolution path
+    def ragged_unsupported_reason(self, batch=1, t=64, rate=4):
+        """None if the ragged layer kernel of the block's precision covers it at (batch, t) and ``rate`` columns per
+        frame, else the reason it does not (host logic only)."""
+        if self.conv1x1_aux is None:
+            return "the block has no aux (conditioning) convolution"
+        if not self.fuse_layer:
+            return "fuse_layer is off (the ragged block is the one-launch layer)"
+        if self.use_causal_conv:
+            return "causal layers are not built"
+        if any(cv.has_spectral_norm or cv.pad_mode != "zero" for cv in self.fused_convs()):
+            return "spectral norm or non-zero padding"
+        if self.conv1x1_out.out_channels != self.conv.in_channels:
+            return "out channels differ from the residual channels"
+        if len({cv.precision for cv in self.fused_convs()}) != 1:
+            return "its convolutions are in mixed precision"
+        if self.dropout > 0.0 and self.training:
+            return "dropout in training mode"
+        if not ops.wavenet_layer_ragged_supported(self.fused_desc(batch, t), rate):
+            return _lib.lib().pwg_last_error().decode(errors="replace")
+        return None
+
+    @torch.no_grad()
+    def forward_ragged(self, x, c, frames, rate, skips=None, skip_scale=1.0, inplace_skips=False):
+        """``forward`` over a ragged batch (inference) -> (x_out, skips + s): ``frames`` is the device int32 table of
+        frames per item, ``rate`` the columns of ``x`` per frame.  ONE ragged launch, fp32 or bf16 by the convolutions'
+        precision as ``forward`` chooses; ``x``, ``c`` and ``skips`` may hold anything past an item's end, and the outputs
+        are not written there.  ValueError with the reason for a block the kernel does not cover: there is no
+        per-convolution path."""
+        reason = self.ragged_unsupported_reason(x.shape[0], x.shape[-1], rate) if x.dim() == 3 else "x is not (B, C, T)"
+        if reason is not None:
+            raise ValueError("WaveNetResidualBlock.forward_ragged: the ragged layer kernel does not cover this block: "
+                             + reason)
+        bf16 = self.conv.precision == "bf16"
+        b_d, b_s, b_o = (None if cv.bias is None else cv.bias.detach()
+                         for cv in (self.conv, self.conv1x1_skip, self.conv1x1_out))
+        return ops.wavenet_layer_forward_ragged(
+            self.fused_desc(x.shape[0], x.shape[-1], skip_scale), x.contiguous(), c.contiguous(), skips, frames, rate,
+            self.fused_image_bf16() if bf16 else self.fused_image(), b_d, b_s, b_o,
+            skips_out=skips if (inplace_skips and skips is not None) else None, bf16=bf16)
+
     def forward(self, x, c, skips=None, skip_scale=1.0, chain_aux=False, inplace_skips=False):
         """Returns (x_out, skips + s) -- the running skip sum is an addend of the skip conv's epilogue
         (``skip_scale`` is the final ``sqrt(1/layers)`` of the generator, applied by the last block).

@@ -128,6 +128,23 @@ class UpsampleNetwork(torch.nn.Module):
                                        2 * scale if self.use_causal_conv else scale, self.act, self.slope)
         return c
 
+    @torch.no_grad()
+    def forward_ragged(self, c, frames, rate=1):
+        """``forward`` over a ragged batch (inference): ``frames`` is the device int32 table of frames
+        per item, ``rate`` the columns of ``c`` per frame; ``c`` must be exactly zero past every item's end, so that a
+        stage reads there the zero padding it reads alone.  The same stage launches as ``forward``; ``ops.zero_tail``
+        follows every stage whose output feeds another stage.  The last stage's output is left as it is past an item's
+        end: its consumers read it point-wise."""
+        if self.use_causal_conv:
+            raise ValueError("UpsampleNetwork: a causal network has no ragged forward (it streams: stream_forward)")
+        for k, i in enumerate(self._stages):
+            scale = self.up_layers[i].x_scale
+            c = Fn.StretchConvFn.apply(c, self.up_layers[i + 1].weight_tensor(), scale, scale, self.act, self.slope)
+            rate *= scale
+            if k + 1 < len(self._stages):
+                ops.zero_tail(c, frames, rate)
+        return c
+
     # ---- stateful streaming of the causal network (csrc/elementwise.hip, pwg_stretch_conv_stream)
     def stream_unsupported_reason(self):
         """None if every stage can be streamed, else the reason (host logic only)."""
@@ -277,6 +294,16 @@ class ConvInUpsampleNetwork(torch.nn.Module):
 
     def forward(self, c):
         return self.upsample(self.conv_in(c))
+
+    @torch.no_grad()
+    def forward_ragged(self, c, frames):
+        """``forward`` over a ragged batch (inference): ``c`` (B, C, T_pad + 2 * aux_context_window)
+        holds item ``b``'s context-padded frames at the columns ``[0, frames[b] + 2 * aux_context_window)`` and anything
+        past them.  ``conv_in`` runs as in ``forward``; its output is item ``b``'s at the columns ``< frames[b]`` and
+        ``ops.zero_tail`` zeroes the rest (write-only: NaN included), then the stages run ragged."""
+        if self.use_causal_conv:
+            raise ValueError("ConvInUpsampleNetwork: a causal network has no ragged forward (it streams: stream_forward)")
+        return self.upsample.forward_ragged(ops.zero_tail(self.conv_in(c), frames, 1), frames)
 
     # ---- stateful streaming of the causal network
     def stream_layers(self):

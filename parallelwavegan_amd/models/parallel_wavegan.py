@@ -102,6 +102,76 @@ class ParallelWaveGANGenerator(torch.nn.Module, _WeightNormMixin):
         x = self.last_conv_layers[1](skips, pre_act="relu")
         return self.last_conv_layers[3](x, pre_act="relu")
 
+    # ---- utterances of different lengths in one batch (utils.PWGRaggedSynthesizer)
+    def ragged_unsupported_reason(self, precision="fp32"):
+        """None if ``forward_ragged`` runs this generator in ``precision`` (``"fp32"`` / ``"bf16"``: both layer kernels
+        have a ragged form of the same geometry), else the reason (host logic only)."""
+        if precision not in ("fp32", "bf16"):
+            return f"precision must be 'fp32' or 'bf16', got {precision!r}"
+        if any(f.use_causal_conv for f in self.conv_layers):
+            return "the model is causal (use_causal_conv=True): it streams (utils.PWGStream)"
+        if self.upsample_net is None:
+            return "upsample_conditional_features=False: an item's length is its mel frames through the upsampler"
+        if not isinstance(self.upsample_net, (upsample.UpsampleNetwork, upsample.ConvInUpsampleNetwork)):
+            return (f"upsample_net={self.upsample_net.__class__.__name__!r} has no ragged forward here (only "
+                    "UpsampleNetwork and ConvInUpsampleNetwork)")
+        if self.in_channels != 1 or self.out_channels != 1:
+            return (f"in_channels = {self.in_channels}, out_channels = {self.out_channels}: an item takes one noise row "
+                    "and returns one waveform")
+        for i, f in enumerate(self.conv_layers):
+            reason = f.ragged_unsupported_reason(1, 64, self.upsample_factor)
+            if reason is not None:
+                return f"conv_layers[{i}]: {reason}"
+        return None
+
+    @torch.no_grad()
+    def forward_ragged(self, z, c, frames):
+        """``forward`` over utterances of different lengths in one batch (the batched form of the loop of
+        bin/decode.py:214-243 of the reference).  With ``w = aux_context_window`` and ``up =
+        upsample_factor``: noise ``z`` (B, 1, T_pad * up), mel ``c`` (B, C, T_pad + 2 w), ``frames`` a device int32 tensor
+        (B,) with ``0 <= frames[b] <= T_pad`` -> (B, 1, T_pad * up).  Item ``b`` of ``c`` holds its frames at the columns
+        ``[w, w + frames[b])`` with its first and last frame replicated ``w`` columns outward (the caller pads, as
+        ``forward``'s does); anything may sit past column ``frames[b] + 2 w`` of ``c`` and past ``frames[b] * up`` of
+        ``z``, NaN included.  The columns ``< frames[b] * up`` of the output are what ``forward`` gives for the item
+        alone; the rest is unspecified.  Neither ``z`` nor ``c`` is written.
+
+        ``conv_in`` and the stretch stages run as in ``forward`` with ``ops.zero_tail`` behind every launch that feeds
+        another stage; every gated layer is ONE ragged launch that reads nothing at or past an item's end and writes
+        nothing there, so no zero-tail pass runs between layers; ``first_conv`` and the two last 1 x 1 convolutions are
+        point-wise.  Nothing on the host reads the table: one captured graph per (B, T_pad) serves every set of
+        lengths.  ValueError with the reason for a generator, shapes or a table this does not take."""
+        name = "ParallelWaveGANGenerator.forward_ragged"
+        reason = self.ragged_unsupported_reason()
+        if reason is not None:
+            raise ValueError(f"{name}: {reason}")
+        w, up = self.aux_context_window, self.upsample_factor
+        if not isinstance(self.upsample_net, upsample.ConvInUpsampleNetwork):
+            w = 0  # (no context convolution: a mel column is a frame)
+        if c.dim() != 3 or c.shape[1] != self.aux_channels or c.shape[2] <= 2 * w:
+            raise ValueError(f"{name}: expected (B, {self.aux_channels}, T_pad + {2 * w}) features, got {tuple(c.shape)}")
+        t_pad = c.shape[2] - 2 * w
+        if tuple(z.shape) != (c.shape[0], 1, t_pad * up):
+            raise ValueError(f"{name}: expected ({c.shape[0]}, 1, {t_pad * up}) noise for {tuple(c.shape)} features, got "
+                             f"{tuple(z.shape)}")
+        ops._require_device(z, c)
+        if (not isinstance(frames, torch.Tensor) or not frames.is_cuda or frames.dtype != torch.int32
+                or tuple(frames.shape) != (c.shape[0],) or not frames.is_contiguous()):
+            raise ValueError(f"{name}: the frames table must be a contiguous device int32 tensor of shape "
+                             f"({c.shape[0]},), got {getattr(frames, 'dtype', type(frames).__name__)} "
+                             f"{tuple(getattr(frames, 'shape', ()))} on {getattr(frames, 'device', 'the host')}")
+        if isinstance(self.upsample_net, upsample.ConvInUpsampleNetwork):
+            c = self.upsample_net.forward_ragged(c, frames)
+        else:
+            c = self.upsample_net.forward_ragged(ops.zero_tail(c.clone(), frames, 1), frames)
+        x = self.first_conv(z)
+        skips = None
+        n = len(self.conv_layers)
+        for i, f in enumerate(self.conv_layers):
+            x, skips = f.forward_ragged(x, c, frames, up, skips=skips,
+                                        skip_scale=math.sqrt(1.0 / n) if i == n - 1 else 1.0, inplace_skips=True)
+        x = self.last_conv_layers[1](skips, pre_act="relu")
+        return self.last_conv_layers[3](x, pre_act="relu")
+
     # ---- stateful streaming of the causal generator (utils.PWGStream; DESIGN.md s11.3)
     def stream_unsupported_reason(self, batch=1, precision="fp32"):
         """None if the causal generator can be streamed layer by layer in ``precision``, else the reason (host logic

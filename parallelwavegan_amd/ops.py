@@ -1019,6 +1019,46 @@ def wavenet_bf16_layer_forward(desc, x, c, skips, packed, b_dil, b_skip, b_out, 
     return x_out, skips_out, z, g
 
 
+def wavenet_layer_ragged_supported(desc, rate):
+    """Do the ragged forms of the one-launch layer (fp32 and bf16) cover this geometry at ``rate`` columns per frame?
+    :func:`wavenet_layer_supported` plus ``rate >= 4``, ``rate % 4 == 0``.  Host logic only (no device needed);
+    ``_lib.lib().pwg_last_error()`` names the reason for a False."""
+    return bool(_lib.lib().pwg_wavenet_layer_ragged_supported(ctypes.byref(desc), int(rate)))
+
+
+def wavenet_layer_forward_ragged(desc, x, c, skips, frames, rate, packed, b_dil, b_skip, b_out, skips_out=None, x_out=None,
+                                 bf16=False, mfma_shape=None):
+    """One gated residual layer over a ragged batch in one launch (inference) -> (x_out, skips_out).
+    Item ``b`` ends at column ``e = min(frames[b] * rate, T)``: ``x``, ``c`` and ``skips`` may hold anything at the
+    columns ``>= e`` (they read as zero), the outputs are NOT written there (fresh outputs are ``torch.empty``), and the
+    columns ``< e`` are bit for bit the plain layer's on the item alone.  ``skips_out`` may be ``skips`` itself.
+    ``bf16``: the bf16-operand layer on the image of :func:`wavenet_bf16_pack_weights` (``mfma_shape``: 32 or 16, None =
+    the default), else the fp32 layer on the image of :func:`wavenet_pack_weights`."""
+    _require_device(x, c, skips, b_dil, b_skip, b_out, skips_out, x_out)
+    what = "wavenet_layer_forward_ragged"
+    if not packed.is_cuda or packed.dtype != (torch.uint8 if bf16 else torch.float32):
+        raise RuntimeError(f"{what}: packed must be the device image of "
+                           f"{'wavenet_bf16_pack_weights' if bf16 else 'wavenet_pack_weights'}")
+    _require_frames(frames, desc.batch, what)
+    assert tuple(x.shape) == (desc.batch, desc.residual_channels, desc.t) and x.is_contiguous(), tuple(x.shape)
+    assert tuple(c.shape) == (desc.batch, desc.aux_channels, desc.t) and c.is_contiguous(), tuple(c.shape)
+    for t in (skips, skips_out, x_out):
+        assert t is None or (t.shape == x.shape and t.is_contiguous())
+    if x_out is None:
+        x_out = torch.empty_like(x)
+    if skips_out is None:
+        skips_out = torch.empty_like(x)
+    args = [ctypes.byref(desc), _ptr(x), _ptr(c), _ptr(skips), _ptr(packed), _ptr(b_dil), _ptr(b_skip), _ptr(b_out),
+            _ptr(x_out), _ptr(skips_out)]
+    if bf16:
+        rc = _lib.lib().pwg_wavenet_bf16_layer_forward_ragged(*args, int(mfma_shape or 0), _ptr(frames), int(rate),
+                                                              _stream())
+    else:
+        rc = _lib.lib().pwg_wavenet_layer_forward_ragged(*args, _ptr(frames), int(rate), _stream())
+    _lib.check(rc, what)
+    return x_out, skips_out
+
+
 def wavenet_stream_bf16_supported(desc):
     """Does the bf16-operand streaming form of the causal layer (csrc/wavenet_stream_bf16.hip) cover this geometry?  The
     answer and the reason in ``_lib.lib().pwg_last_error()`` are those of :func:`wavenet_stream_supported`.  Host logic

@@ -1,4 +1,5 @@
 from .utils import *  # noqa: F401,F403
 from .precision import get_inference_precision, set_inference_precision  # noqa: E402,F401
 from .streaming import (CausalStream, ChunkedSynthesizer, LookaheadStream, MelGANLookaheadStream,  # noqa: E402,F401
-                        MelGANRaggedSynthesizer, PWGLookaheadStream, PWGStream, RaggedSynthesizer, StreamPool)
+                        MelGANRaggedSynthesizer, PWGLookaheadStream, PWGRaggedSynthesizer, PWGStream,
+                        RaggedSynthesizer, StreamPool)

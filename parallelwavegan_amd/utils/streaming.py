@@ -14,7 +14,9 @@ The first / last chunk of an utterance see the model's own zero padding on their
 run without a halo there (they are batched across utterances when their lengths agree).
 
 ``RaggedSynthesizer`` batches WHOLE utterances of different lengths of the non-causal HiFi-GAN instead: one forward
-over a padded block with a device table of frames per item, every item exactly what it gives alone.
+over a padded block with a device table of frames per item, every item exactly what it gives alone (DESIGN.md s9.4);
+``MelGANRaggedSynthesizer`` and ``PWGRaggedSynthesizer`` do the same for the reflect-padded (multi-band) MelGAN (s9.5)
+and for Parallel WaveGAN, whose block carries each item's replicated edge frames and whose forward takes noise (s9.6).
 
 Everything on the device runs in libpwgkernels.so: feature normalisation + (T', C) -> (C, T')
 transpose, the generator, and the float -> PCM16 conversion.
@@ -1274,9 +1276,9 @@ RaggedPlan = collections.namedtuple("RaggedPlan", "groups padded_fraction")
 
 
 class _RaggedSynthesizer:
-    """What :class:`RaggedSynthesizer` and :class:`MelGANRaggedSynthesizer` share: the plan, one padded upload per group,
-    one graph per ``(max_batch, T_pad)`` and the recapture when the parameters change.  A subclass checks its model, calls
-    :meth:`_setup` and gives :meth:`_forward`."""
+    """What :class:`RaggedSynthesizer`, :class:`MelGANRaggedSynthesizer` and :class:`PWGRaggedSynthesizer` share: the
+    plan, one padded upload per group, one graph per ``(max_batch, T_pad)`` and the recapture when the parameters
+    change.  A subclass checks its model, calls :meth:`_setup` and gives :meth:`_forward`."""
 
     max_graph_shapes = 4  # (max_batch, T_pad) shapes whose graphs are kept (least recently used evicted)
     precision = None
@@ -1338,28 +1340,35 @@ class _RaggedSynthesizer:
         return self.plan_groups(lengths, self.max_batch, self.bucket_frames, self.max_frames, self.min_frames,
                                 self.slack_frames, type(self).__name__)
 
-    def _forward(self, c, frames):
-        """The ragged forward of one group -> (max_batch, 1, T_pad * up), whatever it holds past an item's end."""
+    def _forward(self, c, frames, *noise):
+        """The ragged forward of one group -> (max_batch, 1, T_pad * up), whatever it holds past an item's end.
+        ``noise``: the one extra input of a model that takes one (Parallel WaveGAN), else nothing."""
         raise NotImplementedError
 
-    def _capture(self, c, frames):
-        static_c, static_frames = c.clone(), frames.clone()
+    def _capture(self, *inputs):
+        statics = tuple(t.clone() for t in inputs)  # (c, frames) and, for a model that takes it, the noise
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             for _ in range(2):  # fills the weight caches / sets kernel attributes outside the capture
-                self._forward(static_c, static_frames)
+                self._forward(*statics)
         torch.cuda.current_stream().wait_stream(side)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            static_out = self._forward(static_c, static_frames)
+            static_out = self._forward(*statics)
         self.captures += 1
-        return graph, static_c, static_frames, static_out
+        return graph, statics, static_out
 
-    def _run(self, c, frames):
-        """The ragged forward of one group -> (max_batch, 1, T_pad * up); in graph mode the graph's own output buffer."""
+    def _run(self, c, frames, noise=None, draw=False):
+        """The ragged forward of one group -> (max_batch, 1, T_pad * up); in graph mode the graph's own output buffer.
+        ``noise``: the extra input of a model that takes one; ``draw``: its values are not given -- standard normal noise
+        is drawn on the device into it (in graph mode into the graph's static buffer, before the replay and outside
+        the graph)."""
+        inputs = (c, frames) if noise is None else (c, frames, noise)
         if not self.use_graph:
-            return self._forward(c, frames)
+            if draw:
+                noise.normal_()
+            return self._forward(*inputs)
         from .precision import inference_precision
 
         with inference_precision(self.model, self.precision):
@@ -1372,16 +1381,30 @@ class _RaggedSynthesizer:
         if entry is None:
             while len(self._graphs) >= self.max_graph_shapes:
                 self._graphs.popitem(last=False)  # least recently used shape
-            entry = self._capture(c, frames)
+            entry = self._capture(*inputs)
         self._graphs[key] = entry  # most recently used last
-        graph, static_c, static_frames, static_out = entry
-        static_c.copy_(c, non_blocking=True)
-        static_frames.copy_(frames, non_blocking=True)
+        graph, statics, static_out = entry
+        for static, value in zip(statics, inputs):
+            if draw and value is noise:
+                static.normal_()
+            else:
+                static.copy_(value, non_blocking=True)
         graph.replay()
         return static_out
 
+    def _host_block(self, group, feats):
+        """One group's padded upload: (max_batch, T_pad, C), zeros where there is no frame."""
+        block = torch.zeros((self.max_batch, group.t_pad, self.channels)).pin_memory()
+        for j, i in enumerate(group.indices):
+            block[j, :feats[i].shape[0]] = feats[i]
+        return block
+
+    def _run_group(self, c, frames, group, noises):
+        """One group's forward on the uploaded features and table (a subclass with a noise input builds it here)."""
+        return self._run(c, frames)
+
     @torch.no_grad()
-    def _synthesize(self, feats, normalize_before, convert):
+    def _synthesize(self, feats, normalize_before, convert, noises=None):
         if normalize_before and not (hasattr(self.model, "mean") and hasattr(self.model, "scale")):
             raise ValueError(f"{type(self).__name__}: normalize_before=True needs model.register_stats(...)")
         mean = self.model.mean if normalize_before else None
@@ -1393,12 +1416,10 @@ class _RaggedSynthesizer:
                                  f"{tuple(f.shape)}")
         outs = [None] * len(feats)
         for group in self.plan([f.shape[0] for f in feats]).groups:
-            block = torch.zeros((self.max_batch, group.t_pad, self.channels)).pin_memory()  # one padded upload per group
-            for j, i in enumerate(group.indices):
-                block[j, :feats[i].shape[0]] = feats[i]
+            block = self._host_block(group, feats)  # one padded upload per group
             frames = torch.tensor(group.frames, dtype=torch.int32).pin_memory()
             c = normalize_transpose(block.to(self._device, non_blocking=True), mean, scale)
-            y = convert(self._run(c, frames.to(self._device, non_blocking=True)))
+            y = convert(self._run_group(c, frames.to(self._device, non_blocking=True), group, noises))
             for j, i in enumerate(group.indices):
                 outs[i] = y[j, 0, :feats[i].shape[0] * self.up].clone()  # (the graph's buffer is written again)
         return outs
@@ -1429,8 +1450,8 @@ class RaggedSynthesizer(_RaggedSynthesizer):
     this synthesizer's forwards.
 
     Only the non-causal ``HiFiGANGenerator`` with one output channel: a reflect-padded MelGAN needs a mirror at each
-    item's own end (:class:`MelGANRaggedSynthesizer`) and Parallel WaveGAN replicates its edge and draws noise;
-    ``ChunkedSynthesizer`` batches the equal-shaped chunks of those."""
+    item's own end (:class:`MelGANRaggedSynthesizer`) and Parallel WaveGAN replicates its edge and takes noise
+    (:class:`PWGRaggedSynthesizer`); ``ChunkedSynthesizer`` batches the equal-shaped chunks of any mel-only generator."""
 
     def __init__(self, model, max_batch=16, bucket_frames=64, use_graph=True, precision=None):
         from ..models import HiFiGANGenerator
@@ -1510,3 +1531,113 @@ class MelGANRaggedSynthesizer(_RaggedSynthesizer):
     def _forward(self, c, frames):
         y = self.model.forward_ragged(c, frames)
         return y if self.pqmf is None else self.pqmf.synthesis(y)
+
+
+class PWGRaggedSynthesizer(_RaggedSynthesizer):
+    """:class:`RaggedSynthesizer` for the non-causal ``ParallelWaveGANGenerator``: the same plan, graphs (one per
+    ``(max_batch, T_pad)``, ``max_graph_shapes`` kept) and recapture on a parameter change, on ``model.forward_ragged``
+    (DESIGN.md s9.6), whose gated layers read nothing at or past an item's end.
+
+    The generator's two extras are the host's and the noise.  The context window: a group's block is ``(max_batch,
+    T_pad + 2 w, C)``, ``w = model.aux_context_window``, with item ``j``'s frames at the rows ``[w, w + T_j)`` and its
+    first and last frame replicated ``w`` rows outward -- per item what ``inference`` pads onto the utterance alone.
+    The noise: ``synthesize_many(feats, noises=...)`` takes one ``(T_i * up,)`` tensor or array per utterance and item
+    ``i`` uses exactly that noise (with it the result is what ``model.inference(c, x)`` gives, to summation order);
+    ``noises=None`` draws standard normal noise on the device into the graph's static noise buffer before each replay,
+    outside the graph, so two calls differ.  ``precision``: None = the modes ``utils.set_inference_precision`` left on
+    the model, else ``"fp32"`` / ``"bf16"`` for this synthesizer's forwards.  ``max_frames`` is the layer kernel's limit
+    on a row (``pwg_wavenet_layer_ragged_supported``)."""
+
+    def __init__(self, model, max_batch=16, bucket_frames=64, use_graph=True, precision=None):
+        from ..models import ParallelWaveGANGenerator
+        name = type(model).__name__
+        other = "utils.ChunkedSynthesizer batches the equal-shaped chunks of any mel-only generator"
+        if not isinstance(model, ParallelWaveGANGenerator):
+            raise ValueError(f"PWGRaggedSynthesizer: {name} is not supported (only the non-causal "
+                             f"ParallelWaveGANGenerator; utils.RaggedSynthesizer and utils.MelGANRaggedSynthesizer batch "
+                             f"HiFi-GAN and MelGAN utterances of different lengths; {other})")
+        if precision not in (None, "fp32", "bf16"):
+            raise ValueError(f"PWGRaggedSynthesizer: precision must be None, 'fp32' or 'bf16', got {precision!r}")
+        reason = model.ragged_unsupported_reason(precision or "fp32")
+        if reason is not None:
+            raise ValueError(f"PWGRaggedSynthesizer: this {name} has no ragged forward: {reason} (model.inference runs "
+                             f"one utterance per call; utils.PWGStream / utils.PWGLookaheadStream stream it)")
+        self.precision = precision
+        from ..layers.upsample import ConvInUpsampleNetwork
+
+        self.context = model.aux_context_window if isinstance(model.upsample_net, ConvInUpsampleNetwork) else 0
+        up = model.upsample_factor
+        block = model.conv_layers[0]
+        widest = max(model.aux_channels, block.conv.in_channels, block.conv1x1_skip.out_channels)
+        self._setup(model, max_batch, bucket_frames, use_graph, model.aux_channels, up, up * widest)
+        self.max_frames = min(self.max_frames, self.kernel_max_columns(block, up) // up)
+
+    @staticmethod
+    def kernel_max_columns(block, rate):
+        """The layer kernel's own limit on a row: the largest ``T`` its ragged form takes for ``block`` at ``rate``
+        columns per frame, asked of ``pwg_wavenet_layer_ragged_supported`` (host logic, monotone in ``T``)."""
+        from ..ops import wavenet_layer_ragged_supported
+
+        lo, hi = 0, 2 ** 31 - 1
+        while lo < hi:
+            mid = (lo + hi + 1) // 2
+            lo, hi = (mid, hi) if wavenet_layer_ragged_supported(block.fused_desc(1, mid), rate) else (lo, mid - 1)
+        return lo
+
+    def _forward(self, c, frames, z):
+        from .precision import inference_precision
+
+        with inference_precision(self.model, self.precision):
+            return self.model.forward_ragged(z, c, frames)
+
+    @staticmethod
+    def block_layout(group, feats, context, max_batch, channels):
+        """Pure host logic: one group's block (max_batch, T_pad + 2 w, C), ``w = context``: item j's frames at the rows
+        [w, w + T_j), its edge frames replicated w rows outward (``Fn.pad1d(..., "replicate")`` of the item alone),
+        zeros behind."""
+        w = int(context)
+        block = torch.zeros((max_batch, group.t_pad + 2 * w, channels))
+        for j, i in enumerate(group.indices):
+            n = feats[i].shape[0]
+            block[j, w:w + n] = feats[i]
+            block[j, :w] = feats[i][0]
+            block[j, w + n:n + 2 * w] = feats[i][n - 1]
+        return block
+
+    def _host_block(self, group, feats):
+        return self.block_layout(group, feats, self.context, self.max_batch, self.channels).pin_memory()
+
+    def _noise_block(self, group, noises):
+        """(max_batch, 1, T_pad * up) on the host: item j's noise at its samples, zeros behind."""
+        z = torch.zeros((self.max_batch, 1, group.t_pad * self.up)).pin_memory()
+        for j, i in enumerate(group.indices):
+            z[j, 0, :noises[i].shape[0]] = noises[i]
+        return z
+
+    def _run_group(self, c, frames, group, noises):
+        if noises is None:
+            z = torch.empty((self.max_batch, 1, group.t_pad * self.up), device=self._device)
+            return self._run(c, frames, z, draw=True)
+        return self._run(c, frames, self._noise_block(group, noises).to(self._device, non_blocking=True))
+
+    def _checked_noises(self, feats, noises):
+        if noises is None:
+            return None
+        noises = [torch.as_tensor(z, dtype=torch.float32).cpu().reshape(-1) for z in noises]
+        if len(noises) != len(feats):
+            raise ValueError(f"PWGRaggedSynthesizer: {len(noises)} noises for {len(feats)} utterances")
+        for i, (f, z) in enumerate(zip(feats, noises)):
+            n = len(f) * self.up
+            if z.shape[0] != n:
+                raise ValueError(f"PWGRaggedSynthesizer: item {i}: expected ({n},) noise for {len(f)} frames, got "
+                                 f"({z.shape[0]},)")
+        return noises
+
+    def synthesize_many(self, feats, normalize_before=False, noises=None):
+        """feats: list of ``(T_i, C)`` tensors / arrays -> list of ``(T_i * up,)`` fp32 device tensors, in input order.
+        ``noises``: None (drawn on the device) or one ``(T_i * up,)`` tensor / array per utterance."""
+        return self._synthesize(feats, normalize_before, lambda y: y, self._checked_noises(feats, noises))
+
+    def synthesize_many_pcm16(self, feats, normalize_before=False, noises=None):
+        """:meth:`synthesize_many` through the float -> PCM16 conversion on the device: int16 tensors."""
+        return self._synthesize(feats, normalize_before, to_pcm16, self._checked_noises(feats, noises))

@@ -1,6 +1,6 @@
 """16 utterances of different lengths through HiFi-GAN V1: ``utils.RaggedSynthesizer`` against the other ways to run
 them, alternating in one process.  GPU box only.
-usage: bench_ragged.py [--precision fp32|bf16] [--model hifigan|melgan] [--multiband] [--json FILE]
+usage: bench_ragged.py [--precision fp32|bf16] [--model hifigan|melgan|pwg] [--multiband] [--json FILE]
 ``--model melgan``: the same lengths and contenders through ``utils.MelGANRaggedSynthesizer`` on
 ``melgan.v1`` (the class defaults) or, with ``--multiband``, on the ``multi_band_melgan.v2`` generator with its PQMF
 attached; seeded weights, fp32 only.
@@ -16,7 +16,15 @@ and, on the padded (16, T_pad) block of ragged16, graph replays alone (device ev
 Their gap is what exactness costs on the device; the library's profiler (eager runs, per kernel family) splits it into
 the zero_tail launches, the fp32 units that run as separate convolutions, the ragged split units against the plain ones
 and the rest: the launches both forwards share, which read zeros past an item's end in the ragged one.  (MelGAN: the
-mirror_tail launches, the ragged stacks against the plain ones, the rest.)"""
+mirror_tail launches, the ragged stacks against the plain ones, the rest.)
+``--model pwg`` (fp32 or bf16): the same lengths through ``utils.PWGRaggedSynthesizer`` on
+``parallel_wavegan.v1`` (the class defaults, seeded weights).  Contenders: ragged16 / ragged8 with the noise drawn on the
+device, ``inference`` = 16 ``model.inference(c)`` calls as ``parallel-wavegan-decode`` makes them (each draws its noise
+on the host), ``inference_noise_given`` = the same calls with the noise already on the device, and ragged16_noise_given
+(host noises uploaded with the group).  ``ChunkedSynthesizer`` is no contender: it runs mel-only generators, and this
+forward takes noise.  On the padded block: the plain forward (inexact) against ``forward_ragged``, graph replays; their
+gap is what the dependent table read costs and the skipped tiles save; the profiler names the ragged layer launches and
+the zero_tail launches."""
 import argparse
 import json
 import os
@@ -30,9 +38,9 @@ import torch
 from parallelwavegan_amd import ops
 from parallelwavegan_amd.graphs import GraphedInference
 from parallelwavegan_amd.layers import PQMF
-from parallelwavegan_amd.models import HiFiGANGenerator, MelGANGenerator
-from parallelwavegan_amd.utils import (ChunkedSynthesizer, MelGANRaggedSynthesizer, RaggedSynthesizer,
-                                       set_inference_precision)
+from parallelwavegan_amd.models import HiFiGANGenerator, MelGANGenerator, ParallelWaveGANGenerator
+from parallelwavegan_amd.utils import (ChunkedSynthesizer, MelGANRaggedSynthesizer, PWGRaggedSynthesizer,
+                                       RaggedSynthesizer, set_inference_precision)
 from parallelwavegan_amd.utils.streaming import receptive_field_frames
 from tests.golden import synth
 
@@ -87,10 +95,109 @@ def split_gap(fam_plain, fam_ragged, melgan=False):
     return parts
 
 
+def summary(v):
+    return dict(median=statistics.median(v), min=min(v), max=max(v), runs=v)
+
+
+def main_pwg(args, dev):
+    """``--model pwg``: see the module docstring."""
+    model = ParallelWaveGANGenerator()
+    model.load_state_dict(synth.synth_state_dict(model.state_dict(), seed=5, g_scale=synth.PWG_G_SCALE))
+    model.remove_weight_norm()
+    model = model.to(dev).eval()
+    if args.precision == "bf16":
+        set_inference_precision(model, "bf16")
+    up, w = model.upsample_factor, model.aux_context_window
+    gen = torch.Generator().manual_seed(1)
+    feats = [torch.randn(n, 80, generator=gen) for n in LENGTHS]
+    noises = [torch.randn(n * up, generator=gen) for n in LENGTHS]
+    feats_dev = [f.to(dev) for f in feats]
+    noises_dev = [z.reshape(-1, 1).to(dev) for z in noises]
+    ragged = {k: PWGRaggedSynthesizer(model, max_batch=k, bucket_frames=64) for k in (16, 8)}
+
+    def inference():  # (decode's loop: the features go up per utterance, the noise is drawn by inference itself)
+        with torch.no_grad():
+            return [model.inference(f.to(dev)).reshape(-1) for f in feats]
+
+    def inference_noise_given():
+        with torch.no_grad():
+            return [model.inference(f, z).reshape(-1) for f, z in zip(feats_dev, noises_dev)]
+
+    runs = {"ragged16": lambda: ragged[16].synthesize_many(feats), "ragged8": lambda: ragged[8].synthesize_many(feats),
+            "ragged16_noise_given": lambda: ragged[16].synthesize_many(feats, noises=noises),
+            "inference": inference, "inference_noise_given": inference_noise_given}
+    # what the contenders compute, on the same noise: every utterance against model.inference
+    ref = inference_noise_given()
+    diffs = {f"ragged{k}": max(float((y - r).abs().max()) for y, r in zip(ragged[k].synthesize_many(feats, noises=noises), ref))
+             for k in ragged}
+    peak = max(float(r.abs().max()) for r in ref)
+    for fn in runs.values():  # warm: graphs captured, weight images cached
+        fn()
+    ms = {n: [] for n in runs}
+    for _ in range(ROUNDS):
+        for n, fn in runs.items():
+            ms[n].append(wall_ms(fn, REPS))
+
+    # the padded block of ragged16: the plain forward (inexact) against forward_ragged, graph replays
+    plan = ragged[16].plan(LENGTHS)
+    t_pad = plan.groups[0].t_pad
+    c = torch.randn(16, 80, t_pad + 2 * w, device=dev)
+    z = torch.randn(16, 1, t_pad * up, device=dev)
+    frames = torch.tensor(plan.groups[0].frames, dtype=torch.int32, device=dev)
+    plain_graph = GraphedInference(model)
+    plain_graph(z, c)
+    ragged[16]._run(c, frames, z)
+    dev_ms = {"forward_graph": [], "ragged_graph": []}
+    for _ in range(ROUNDS):
+        dev_ms["forward_graph"].append(event_ms(lambda: plain_graph(z, c), REPS))
+        dev_ms["ragged_graph"].append(event_ms(lambda: ragged[16]._run(c, frames, z), REPS))
+    with torch.no_grad():
+        model(z, c), model.forward_ragged(z, c, frames)
+        with ops.profile() as prof_plain:
+            model(z, c)
+        with ops.profile() as prof_ragged:
+            model.forward_ragged(z, c, frames)
+    fam_plain, fam_ragged = families(prof_plain), families(prof_ragged)
+    kernels_plain = sum(v["ms"] for v in fam_plain.values())
+    kernels_ragged = sum(v["ms"] for v in fam_ragged.values())
+    layer = "wavenet_bf16_layer_kernel" if args.precision == "bf16" else "wavenet_layer_kernel"
+    layer_ragged = layer.replace("_kernel", "_ragged_kernel")
+    gap = dict(zero_tail=fam_ragged.get("zero_tail_kernel", dict(ms=0.0))["ms"],
+               ragged_layers=fam_ragged[layer_ragged]["ms"] - fam_plain[layer]["ms"])
+    gap["same_launches"] = kernels_ragged - kernels_plain - sum(gap.values())
+    samples = sum(LENGTHS) * up
+    out = dict(model="parallel_wavegan.v1", precision=args.precision, lengths=LENGTHS, frames_total=sum(LENGTHS),
+               weights="seeded synthetic weights (tests/golden/synth.py, seed 5), weight norm removed",
+               audio_seconds_at_22050=samples / 22050.0, rounds=ROUNDS, reps=REPS,
+               padded_fraction={k: ragged[k].plan(LENGTHS).padded_fraction for k in ragged},
+               t_pad={k: [g.t_pad for g in ragged[k].plan(LENGTHS).groups] for k in ragged},
+               wall_ms_per_list={n: summary(v) for n, v in ms.items()},
+               msamples_per_s={n: samples / statistics.median(v) / 1e3 for n, v in ms.items()},
+               max_abs_vs_inference_same_noise=diffs, peak_abs_of_inference=peak,
+               padded_block=dict(shape=[16, 80, t_pad + 2 * w], device_ms={n: summary(v) for n, v in dev_ms.items()},
+                                 launches=dict(forward=sum(v["launches"] for v in fam_plain.values()),
+                                               forward_ragged=sum(v["launches"] for v in fam_ragged.values())),
+                                 profiler_ms=dict(forward=kernels_plain, forward_ragged=kernels_ragged, gap=gap),
+                                 families=dict(forward=fam_plain, forward_ragged=fam_ragged)))
+    for n, v in ms.items():
+        print(f"{n:22s} {statistics.median(v):8.2f} ms per list  [{min(v):8.2f} .. {max(v):8.2f}]  "
+              f"{out['msamples_per_s'][n]:6.1f} M samples/s")
+    print("max |ragged - inference| on the same noise: " + ", ".join(f"{k} {v:.2e}" for k, v in diffs.items())
+          + f" (peak |inference| {peak:.2e})")
+    for n, v in dev_ms.items():
+        print(f"{n:22s} {statistics.median(v):8.2f} ms per replay [{min(v):8.2f} .. {max(v):8.2f}]  (16 x {t_pad} frames)")
+    print(f"profiler (eager): forward {kernels_plain:.2f} ms in {out['padded_block']['launches']['forward']} launches; "
+          f"forward_ragged {kernels_ragged:.2f} ms in {out['padded_block']['launches']['forward_ragged']} launches; the gap "
+          "in parts: " + ", ".join(f"{k} {v:+.2f}" for k, v in gap.items()))
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(out, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--precision", default="fp32", choices=("fp32", "bf16"))
-    ap.add_argument("--model", default="hifigan", choices=("hifigan", "melgan"))
+    ap.add_argument("--model", default="hifigan", choices=("hifigan", "melgan", "pwg"))
     ap.add_argument("--multiband", action="store_true", help="--model melgan: the multi_band_melgan.v2 generator + PQMF")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
@@ -103,6 +210,8 @@ def main():
         raise SystemExit("bench_ragged.py: --multiband goes with --model melgan")
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
+    if args.model == "pwg":
+        return main_pwg(args, dev)
     if melgan:
         # seeded weights of audible amplitude (tests/golden/synth.py), as tools/bench_stream.py builds them
         params = dict(out_channels=4, channels=384, upsample_scales=[8, 4, 2], stacks=4) if args.multiband else {}
@@ -174,9 +283,6 @@ def main():
     zero_tail = fam_ragged.get(tail_kernel, dict(launches=0, ms=0.0))
     kernels_plain = sum(v["ms"] for v in fam_plain.values())
     kernels_ragged = sum(v["ms"] for v in fam_ragged.values())
-
-    def summary(v):
-        return dict(median=statistics.median(v), min=min(v), max=max(v), runs=v)
 
     audio_s = sum(LENGTHS) * up / 22050.0
     out = dict(model=name, precision=args.precision, lengths=LENGTHS, frames_total=sum(LENGTHS), weights=weights,
