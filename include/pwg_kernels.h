@@ -466,6 +466,17 @@ int pwg_conv1d_stream_mirrored_forward(const pwg_conv1d_desc* d, const float* x,
                                        const float* w_packed, const float* bias, float* y, int32_t in_lo, int32_t in_hi,
                                        int32_t valid_lo, int32_t valid_hi, void* stream);
 
+/* Diagnostics (host only, no launch, no device needed): the tile and grid a conv stream launch takes for `d` -- the
+ * plain, delayed, slotted and mirrored entries, fp32 and bf16 alike: they share one tile rule, evaluated here by the
+ * call the launches make.  out[5]:
+ *   out[0] tile rows (16 or 32), out[1] tile columns (16, 32 or 64: chunks of up to 16 / 32 / more columns); 32 rows
+ *          only with 64 columns and ceil(m / 32) * column tiles * batch >= 512 workgroups (m = c_out, or c_out * stride
+ *          for the transposed form)
+ *   out[2..4] grid: column tiles, row blocks, batch.
+ * Refuses what pwg_conv1d_stream_supported refuses, with the same pwg_last_error reason, and a NULL out.
+ * Purely additive -- no existing signature or behaviour changes -- so pwg_abi_version() stays 15. */
+int pwg_conv1d_stream_plan(const pwg_conv1d_desc* d, int32_t* out);
+
 /* Diagnostics (host only, no launch, no device needed): the plan pwg_conv1d_forward derives for a descriptor.
  * has_addends: 1 if add1 / add2 will be passed.  out[8]:
  *   out[0] kernel family: 0 = MFMA implicit-GEMM kernel, 1 = grouped 16x16x4 kernel, 2 = single-input-channel

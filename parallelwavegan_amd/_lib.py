@@ -162,6 +162,7 @@ SIGNATURES = {
     "pwg_conv1d_stream_supported": (ctypes.c_int, [ctypes.POINTER(ConvDesc)]),
     "pwg_conv1d_stream_hist_floats": (ctypes.c_size_t, [ctypes.POINTER(ConvDesc)]),
     "pwg_conv1d_stream_forward": (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pwg_conv1d_stream_plan": (ctypes.c_int, [ctypes.POINTER(ConvDesc), ctypes.POINTER(_i32)]),
     "pwg_conv1d_stream_bf16_supported": (ctypes.c_int, [ctypes.POINTER(ConvDesc)]),
     "pwg_conv1d_stream_bf16_forward": (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                                       _vp]),

@@ -372,6 +372,23 @@ extern "C" size_t pwg_conv1d_stream_hist_floats(const pwg_conv1d_desc* d) {
   return (size_t)d->batch * d->c_in * g.hist;
 }
 
+// Diagnostics, host only: the tile and grid every conv stream launch of `d` takes, in either precision and every form
+// (they all call stream_geometry + stream_tile as below and launch on stream_grid).  Launches nothing.
+extern "C" int pwg_conv1d_stream_plan(const pwg_conv1d_desc* d, int32_t* out) {
+  StreamGeom g;
+  const int rc = stream_geometry(d, &g);
+  if (rc != PWG_OK) return rc;
+  PWG_REQUIRE(out != nullptr, PWG_ERR_NULL, "conv1d_stream_plan: NULL out");
+  const StreamTile tile = stream_tile(d->t_in, g.m, d->batch);
+  const dim3 grid = stream_grid(tile, g.m, d->batch);
+  out[0] = 16 * tile.tm;
+  out[1] = 16 * tile.tn;
+  out[2] = (int32_t)grid.x;
+  out[3] = (int32_t)grid.y;
+  out[4] = (int32_t)grid.z;
+  return PWG_OK;
+}
+
 // The fields of the argument struct that come from the fp32 packed image -> the LDS bytes of the staged window
 static size_t fill_image_args(StreamArgs* a, const float* w_packed, const StreamGeom& g, const StreamTile& tile) {
   a->w = w_packed;

@@ -354,6 +354,11 @@ static inline StreamTile stream_tile(int n, int m, int batch) {
   return t;
 }
 
+// The grid of a launch: column tiles x row blocks x items (what pwg_conv1d_stream_plan reports)
+static inline dim3 stream_grid(const StreamTile& t, int m, int batch) {
+  return dim3(t.col_tiles, ceil_div(m, 16 * t.tm), batch);
+}
+
 // LDS of a launch: the window, or the partial tiles that reuse it
 static inline size_t stream_lds_bytes(size_t window_bytes, const StreamTile& t) {
   const size_t red = (size_t)4 * (16 * t.tm) * (16 * t.tn + 1) * sizeof(float);
@@ -452,7 +457,7 @@ static inline void stream_launch(const StreamTile& t, bool transposed, const Arg
     kern = transposed ? K<1, 4, true>::fn : K<1, 4, false>::fn;
   else
     kern = transposed ? K<2, 4, true>::fn : K<2, 4, false>::fn;
-  hipLaunchKernelGGL(kern, dim3(t.col_tiles, ceil_div(m, 16 * t.tm), batch), dim3(256), lds, stream, a);
+  hipLaunchKernelGGL(kern, stream_grid(t, m, batch), dim3(256), lds, stream, a);
 }
 
 // What a launch is accounted with (ProfScope): the contraction, and the bytes of the chunk and both histories, of the

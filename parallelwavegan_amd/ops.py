@@ -364,6 +364,15 @@ def conv1d_stream_hist_floats(desc):
     return _lib.lib().pwg_conv1d_stream_hist_floats(ctypes.byref(desc))
 
 
+def conv1d_stream_plan(desc):
+    """The tile and grid every conv stream launch of ``desc`` takes, in either precision and every form (host only: no
+    launch, no device needed): dict(tile=(rows, columns), grid=(column tiles, row blocks, batch)).  An unsupported
+    descriptor raises with the library's reason."""
+    out = (ctypes.c_int32 * 5)()
+    _lib.check(_lib.lib().pwg_conv1d_stream_plan(ctypes.byref(desc), out), "conv1d_stream_plan")
+    return dict(tile=(out[0], out[1]), grid=(out[2], out[3], out[4]))
+
+
 def _conv1d_stream_out(desc, x, hist_in, hist_out, add1, add2, out):
     """The checks the two conv stream wrappers share -> ``out`` (allocated if None)."""
     if out is None:
