@@ -851,6 +851,13 @@ size_t pwg_wavenet_weight_backward_workspace_floats(const pwg_wavenet_desc* d);
 int pwg_wavenet_weight_backward(const pwg_wavenet_desc* d, const float* dz, const float* x, const float* c, const float* gs,
                                 const float* go, const float* g, const pwg_wavenet_param_grad* grads, float* workspace,
                                 size_t workspace_floats, void* stream);
+/* Diagnostics, host only: how the two contraction launches of `d` cut the flattened (item, 32-column chunk) range into
+ * slices -- out[0..3] = {slices, chunks per slice} of the dil+aux launch, then of the skip+out launch -- by the rule the
+ * launch and the workspace query use.  The workspace holds slices0 slabs of [128][273] floats, then slices1 slabs of
+ * [128][65]: per slab row the contraction's columns ([tap0 x | tap1 x | tap2 x | c], or g) and the row sum of the
+ * 128-row operand.  Launches nothing; an unsupported descriptor is refused as pwg_wavenet_weight_backward refuses it.
+ * Purely additive -- no existing signature or behaviour changes -- so pwg_abi_version() stays 15. */
+int pwg_wavenet_weight_backward_plan(const pwg_wavenet_desc* d, int32_t out[4]);
 
 /* Old-style torch.nn.utils.weight_norm (dim=0) scale: scale[i] = g[i]/||v[i,...]||_2
  * replaces torch._weight_norm at every conv call site.

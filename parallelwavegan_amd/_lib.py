@@ -256,6 +256,7 @@ SIGNATURES = {
     "pwg_wavenet_gate_backward": (ctypes.c_int, [ctypes.POINTER(WaveNetDesc)] + [_vp] * 7),
     "pwg_wavenet_data_backward": (ctypes.c_int, [ctypes.POINTER(WaveNetDesc)] + [_vp] * 7),
     "pwg_wavenet_weight_backward_workspace_floats": (ctypes.c_size_t, [ctypes.POINTER(WaveNetDesc)]),
+    "pwg_wavenet_weight_backward_plan": (ctypes.c_int, [ctypes.POINTER(WaveNetDesc), ctypes.POINTER(_i32)]),
     "pwg_wavenet_weight_backward": (ctypes.c_int, [ctypes.POINTER(WaveNetDesc)] + [_vp] * 6
                                     + [ctypes.POINTER(WaveNetParamGrad), _vp, ctypes.c_size_t, _vp]),
     "pwg_act_backward": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _f32, _f32, _vp]),

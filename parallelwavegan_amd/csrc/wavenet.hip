@@ -1165,6 +1165,20 @@ size_t pwg_wavenet_weight_backward_workspace_floats(const pwg_wavenet_desc* d) {
   return (size_t)slices0 * WN_G * (size_t)(WN_K * WN_R + d->aux_channels + 1) + (size_t)slices1 * WN_G * (WN_R + 1);
 }
 
+// Diagnostics, host only: the slicing of the two contraction launches of `d`, from the ww_slices calls the launch and the
+// workspace query make.  Launches nothing.
+int pwg_wavenet_weight_backward_plan(const pwg_wavenet_desc* d, int32_t* out) {
+  PWG_REQUIRE(wavenet_ok(d), PWG_ERR_UNSUPPORTED, "wavenet_weight_backward_plan: unsupported layer geometry");
+  PWG_REQUIRE(out != nullptr, PWG_ERR_NULL, "wavenet_weight_backward_plan: NULL out");
+  int per, per1;
+  const int slices = ww_slices(d, &per, 1), slices1 = ww_slices(d, &per1, 3);
+  out[0] = slices;
+  out[1] = per;
+  out[2] = slices1;
+  out[3] = per1;
+  return PWG_OK;
+}
+
 int pwg_wavenet_weight_backward(const pwg_wavenet_desc* d, const float* dz, const float* x, const float* c, const float* gs,
                                 const float* go, const float* g, const pwg_wavenet_param_grad* grads, float* workspace,
                                 size_t workspace_floats, void* stream_) {

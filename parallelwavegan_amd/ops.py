@@ -1181,6 +1181,15 @@ def wavenet_data_backward(desc, dz, go, packed_bwd, need_dx=True, need_dc=True, 
     return dx, dc
 
 
+def wavenet_weight_backward_plan(desc):
+    """How the two contraction launches of ``wavenet_weight_backward`` slice the flattened (item, 32-column chunk) range
+    (host only: no launch, no device needed): dict(slices=(dil+aux, skip+out), chunks_per_slice=(dil+aux, skip+out)).
+    An unsupported descriptor raises with the library's reason."""
+    out = (ctypes.c_int32 * 4)()
+    _lib.check(_lib.lib().pwg_wavenet_weight_backward_plan(ctypes.byref(desc), out), "wavenet_weight_backward_plan")
+    return dict(slices=(out[0], out[2]), chunks_per_slice=(out[1], out[3]))
+
+
 def wavenet_weight_backward(desc, dz, x, c, gs, go, g, convs=None):
     """Parameter gradients of the layer's four convolutions (csrc/wavenet.hip: two contraction launches + one finish
     launch).  ``convs`` = four ``(v, g, has_bias)`` entries (dilated, aux, skip, out): ``v``/``g`` the weight-norm

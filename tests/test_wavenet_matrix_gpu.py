@@ -66,8 +66,10 @@ COVERED = {
     "pwg_wavenet_pack_weights_bwd": "test_backward_image",
     "pwg_wavenet_gate_backward": "test_gate_backward",
     "pwg_wavenet_data_backward": "test_data_backward",
-    "pwg_wavenet_weight_backward_workspace_floats": "tests/test_wavenet_layer_gpu.py",
-    "pwg_wavenet_weight_backward": "tests/test_wavenet_layer_gpu.py",
+    # the weight path has a matrix of its own: ``module::test``
+    "pwg_wavenet_weight_backward_workspace_floats": "tests.test_wavenet_wgrad_matrix_gpu::test_edge_grid",
+    "pwg_wavenet_weight_backward_plan": "tests.test_wavenet_wgrad_matrix_gpu::test_finish_exact_long",
+    "pwg_wavenet_weight_backward": "tests.test_wavenet_wgrad_matrix_gpu::test_edge_grid",
 }
 
 

@@ -1,7 +1,13 @@
 """CPU: the float64 references of tests/wavenet_refs.py against torch's own float64 evaluation and autograd of the
 layer written tap by tap (so that the GPU matrix of tests/test_wavenet_matrix_gpu.py is compared with something that is
 itself checked); the completeness check: every ``pwg_wavenet_*`` entry point of csrc/wavenet.hip must name, in
-``COVERED``, the test that drives it directly; and the refusal table of ``pwg_wavenet_layer_supported``."""
+``COVERED``, the test that drives it directly; and the refusal table of ``pwg_wavenet_layer_supported``.
+
+The weight path (tests/test_wavenet_wgrad_matrix_gpu.py): ``R.weight_backward`` and ``R.weight_norm_backward`` against
+autograd, the slabs against their sum, the slicing plan (``pwg_wavenet_weight_backward_plan``, answered without a device)
+at a table of shapes, and the room the data leave: over that module's grids the float32 CPU evaluation of the references
+lies at most 7.0e-7 = 0.035 of its 2e-5 bar from float64 (about 29x of room), while a reference without one column, one tap or one slice lies more than
+10 bars away at every row."""
 import ctypes
 import importlib
 import itertools
@@ -109,22 +115,26 @@ def _entry_points():
 
 def test_every_entry_point_names_the_test_that_drives_it():
     names = _entry_points()
-    assert len(names) == 10 and "pwg_wavenet_gate_backward" in names and "pwg_wavenet_layer_supported" in names, names
+    assert len(names) == 11 and "pwg_wavenet_gate_backward" in names and "pwg_wavenet_layer_supported" in names, names
+    assert "pwg_wavenet_weight_backward" in names and "pwg_wavenet_weight_backward_plan" in names, names
     gpu = importlib.import_module("tests.test_wavenet_matrix_gpu")
     missing = [n for n in names if n not in gpu.COVERED]
     assert not missing, f"entry points with no direct test: {missing}"
     stale = [n for n in gpu.COVERED if n not in names]
     assert not stale, f"COVERED names entry points that no longer exist: {stale}"
-    module_marks = getattr(gpu, "pytestmark", [])
-    module_marks = list(module_marks) if isinstance(module_marks, (list, tuple)) else [module_marks]
     for name, where in gpu.COVERED.items():
-        if where.endswith(".py"):
-            assert os.path.exists(os.path.join(ROOT, where)), f"{name}: {where} does not exist"
-        else:
-            fn = getattr(gpu, where, None)
-            assert callable(fn) and where.startswith("test_"), f"{name}: no test function {where}"
-            marks = module_marks + list(getattr(fn, "pytestmark", []))
-            assert any(m.name == "gpu" for m in marks), f"{where} is not marked gpu"
+        # ``test_name`` of the matrix itself, or ``module::test_name`` of another GPU module: a test function, never a file
+        module, _, test = where.rpartition("::")
+        mod = importlib.import_module(module) if module else gpu
+        assert os.path.basename(mod.__file__).startswith("test_"), f"{name}: {module} is not a test module"
+        fn = getattr(mod, test, None)
+        assert callable(fn) and test.startswith("test_"), f"{name}: no test function {where}"
+        module_marks = getattr(mod, "pytestmark", [])
+        module_marks = list(module_marks) if isinstance(module_marks, (list, tuple)) else [module_marks]
+        marks = module_marks + list(getattr(fn, "pytestmark", []))
+        assert any(m.name == "gpu" for m in marks), f"{where} is not marked gpu"
+    weight_path = [n for n in names if "weight_backward" in n]
+    assert len(weight_path) == 3 and all(gpu.COVERED[n].startswith("tests.test_wavenet_wgrad_matrix_gpu::") for n in weight_path)
 
 
 # ------------------------------------------------------------------------------------------------ refusal table
@@ -164,3 +174,181 @@ def test_supported_geometries_are_the_table(kwargs, supported):
         assert sizes[0] == 272 * 128 + 64 * 128 and sizes[1] == (16 * 2 + 48 * 2 + 16 * 3) * 256 and sizes[2] > 0, sizes
     else:
         assert sizes == [0, 0, 0], sizes
+
+
+# ------------------------------------------------------------------------------------------------ the weight path
+def _wgrad():
+    return importlib.import_module("tests.test_wavenet_wgrad_matrix_gpu")
+
+
+@pytest.mark.parametrize("with_go", [True, False])
+@pytest.mark.parametrize("dil", [1, 3, 64])
+@pytest.mark.parametrize("T", [1, 5, 33, 100])
+def test_weight_backward_matches_torch_autograd(T, dil, with_go):
+    """``R.weight_backward`` on ``dz``, ``gs = skip_mul * ds_out`` and ``go`` of ``R.gate_backward`` and the saved ``g``
+    against autograd of the whole layer with respect to its four weights and three biases."""
+    gen = torch.Generator().manual_seed(77 * T + dil)
+    r = lambda *s: torch.randn(*s, dtype=D, generator=gen)  # noqa: E731
+    B = 3
+    x, c, ds_out, dx_out = r(B, 64, T), r(B, AUX, T), r(B, 64, T), r(B, 64, T)
+    out_mul, skip_mul = math.sqrt(0.5), math.sqrt(1 / 30)
+    leaves = [t.requires_grad_() for t in (r(128, 64, 3) / math.sqrt(192), r(128, AUX, 1) / math.sqrt(AUX), r(64, 64, 1) / 8,
+                                           r(64, 64, 1) / 8, r(128), r(64), r(64))]
+    Wd, Wa, Ws, Wo, b_d, b_s, b_o = leaves
+    z, g, so, xo = R.layer_forward(x, c, None, Wd, Wa, Ws, Wo, b_d, b_s, b_o, dil, out_mul, skip_mul)
+    loss = (so * ds_out).sum() + ((xo * dx_out).sum() if with_go else 0.0)
+    want = torch.autograd.grad(loss, leaves, allow_unused=True)
+    with torch.no_grad():
+        dz, go = R.gate_backward(z, dx_out if with_go else None, ds_out, Ws, Wo, out_mul, skip_mul)
+        got = R.weight_backward(dz, x, c, skip_mul * ds_out, go, g, dil)
+    assert (got["dWo"] is None) == (got["db_out"] is None) == (not with_go)
+    for k, ref in zip(("dWd", "dWa", "dWs", "dWo", "db_dil", "db_skip", "db_out"), want):
+        if got[k] is None:
+            assert ref is None, k
+        else:
+            _close(got[k], ref)
+
+
+def test_weight_norm_backward_matches_torch_autograd():
+    gen = torch.Generator().manual_seed(3)
+    for shape in ((128, 64, 3), (128, AUX, 1), (64, 64, 1), (5, 1, 1)):
+        v = torch.randn(shape, dtype=D, generator=gen).requires_grad_()
+        g = (0.5 + torch.rand(shape[0], dtype=D, generator=gen)).requires_grad_()
+        dw = torch.randn(shape, dtype=D, generator=gen)
+        w = g.view(-1, 1, 1) * v / v.flatten(1).norm(dim=1).view(-1, 1, 1)
+        dv_t, dg_t = torch.autograd.grad((w * dw).sum(), (v, g))
+        dv, dg = R.weight_norm_backward(dw, v.detach(), g.detach())
+        _close(dv, dv_t)
+        _close(dg, dg_t)
+        assert R.weight_norm_backward(dw, v.detach(), g.detach().view(-1, 1, 1))[1].shape == (shape[0], 1, 1)
+
+
+# (B, T, chunks per slice of the two launches): runs that straddle items, that end on a single chunk, one chunk in total
+SLAB_PLANS = [(5, 7, (2, 2)), (3, 96, (2, 3)), (3, 95, (2, 2)), (4, 200, (3, 7)), (1, 20, (1, 1)), (2, 131, (2, 2))]
+
+
+@pytest.mark.parametrize("B,T,per", SLAB_PLANS)
+@pytest.mark.parametrize("with_go", [True, False])
+def test_slabs_sum_to_the_weight_gradients(B, T, per, with_go):
+    gen = torch.Generator().manual_seed(B * 1000 + T)
+    dil = 3
+    dz, x, c, gs, go, g = [torch.randn(B, ch, T, dtype=D, generator=gen) for ch in (128, 64, AUX, 64, 64, 64)]
+    go = go if with_go else None
+    for p in set(per):
+        ranges = R.slab_ranges(B, T, p)
+        owned = sorted((b, n) for rs in ranges for b, lo, hi in rs for n in range(lo, hi))
+        assert owned == [(b, n) for b in range(B) for n in range(T)], "every column in exactly one slice"
+        assert len(ranges) == -(-(B * -(-T // 32)) // p)
+        assert all(lo % 32 == 0 and (hi % 32 == 0 or hi == T) for rs in ranges for _, lo, hi in rs)
+    if (B, T) != (1, 20):
+        assert any(len(rs) > 1 for rs in R.slab_ranges(B, T, per[0])), "the plan straddles two items"
+    s0, s1 = R.weight_backward_slabs(dz, x, c, gs, go, g, dil, per)
+    assert s0.shape == (len(R.slab_ranges(B, T, per[0])), 128, 273) and s1.shape == (len(R.slab_ranges(B, T, per[1])), 128, 65)
+    ref = R.weight_backward(dz, x, c, gs, go, g, dil)
+    t0, t1 = s0.sum(0), s1.sum(0)
+    _close(t0[:, :192].view(128, 3, 64).permute(0, 2, 1), ref["dWd"])  # columns [tap0 x | tap1 x | tap2 x | c | row sum]
+    _close(t0[:, 192:272, None], ref["dWa"])
+    _close(t0[:, 272], ref["db_dil"])
+    _close(t1[:64, :64, None], ref["dWs"])
+    _close(t1[:64, 64], ref["db_skip"])
+    if with_go:
+        _close(t1[64:, :64, None], ref["dWo"])
+        _close(t1[64:, 64], ref["db_out"])
+    else:
+        assert float(t1[64:].abs().max()) == 0.0
+
+
+# (B, T) -> (slices0, chunks per slice 0, slices1, chunks per slice 1): one chunk in total; one chunk per item; a
+# straddling plan; at most 2 chunks per slice up to 512 (resp. 1536) chunks, 3 from the first count above it
+PLANS = [
+    ((1, 1), (1, 1, 1, 1)),
+    ((1, 32), (1, 1, 1, 1)),
+    ((1, 33), (1, 2, 1, 2)),
+    ((5, 7), (3, 2, 3, 2)),
+    ((5, 32), (3, 2, 3, 2)),
+    ((3, 95), (5, 2, 5, 2)),
+    ((1, 32 * 512), (256, 2, 256, 2)),
+    ((1, 32 * 512 + 1), (171, 3, 257, 2)),
+    ((27, 19 * 32), (171, 3, 257, 2)),
+    ((1, 32 * 1536), (256, 6, 768, 2)),
+    ((1, 32 * 1536 + 1), (220, 7, 513, 3)),
+    ((3, 5500), (172, 3, 258, 2)),
+    ((7, 7100), (222, 7, 518, 3)),
+    ((6, 25600), (253, 19, 686, 7)),  # ceil(4800 / 256) = 19, ceil(4800 / 768) = 7
+]
+
+
+@pytest.mark.parametrize("shape,plan", PLANS, ids=[f"B{b}-T{t}" for (b, t), _ in PLANS])
+def test_weight_backward_plan_is_the_table(shape, plan):
+    from parallelwavegan_amd import _lib, ops
+
+    lib = _lib.lib()
+    for dil in (1, 512):
+        d = ops.make_wavenet_desc(*shape, dil)
+        out = (ctypes.c_int32 * 4)()
+        assert lib.pwg_wavenet_weight_backward_plan(ctypes.byref(d), out) == 0
+        assert tuple(out) == plan
+        assert ops.wavenet_weight_backward_plan(d) == dict(slices=(plan[0], plan[2]), chunks_per_slice=(plan[1], plan[3]))
+        assert lib.pwg_wavenet_weight_backward_workspace_floats(ctypes.byref(d)) == plan[0] * 128 * 273 + plan[2] * 128 * 65
+        for i in (0, 2):  # the slices are the runs of R.slab_ranges
+            assert len(R.slab_ranges(*shape, plan[i + 1])) == plan[i]
+
+
+def test_weight_backward_plan_refusals():
+    from parallelwavegan_amd import _lib, ops
+
+    lib = _lib.lib()
+    out = (ctypes.c_int32 * 4)(*[-7] * 4)
+    assert lib.pwg_wavenet_weight_backward_plan(ctypes.byref(ops.make_wavenet_desc(2, 35, 3)), None) == -4  # PWG_ERR_NULL
+    assert b"NULL out" in lib.pwg_last_error()
+    for bad in (ops.make_wavenet_desc(2, 35, 3, causal=True), ops.make_wavenet_desc(2, 35, 3, aux_channels=72), None):
+        assert lib.pwg_wavenet_weight_backward_plan(None if bad is None else ctypes.byref(bad), out) == -2  # PWG_ERR_UNSUPPORTED
+        assert b"unsupported layer geometry" in lib.pwg_last_error()
+    assert list(out) == [-7] * 4
+    with pytest.raises(RuntimeError, match="unsupported layer geometry"):
+        ops.wavenet_weight_backward_plan(ops.make_wavenet_desc(2, 35, 3, kernel=5))
+
+
+def _rel(a, b):
+    return (a - b).abs().max().item() / (b.abs().max().item() + 1e-12)
+
+
+def test_float32_room_and_sensitivity():
+    """Over the GPU grids (a) and (c) of tests/test_wavenet_wgrad_matrix_gpu.py, on that module's own operands: the
+    float32 CPU evaluation of the references (final gradients and slabs) against float64, relative to the bar -- the room
+    the data leave -- and what the bar resolves: a reference without one column, one tap or one slice lies more than 10
+    bars away at every row."""
+    W = _wgrad()
+    rows = [(2, T, dil) for T, dil in W.EDGE_GRID] + list(W.SLICING_GRID)
+    worst = 0.0
+    for B, T, dil in rows:
+        ops64 = W._f64(B, T)
+        ref = R.weight_backward(*ops64, dil)
+        chunks = B * -(-T // 32)
+        per = (2, 2) if chunks >= 2 else (1, 1)
+        slabs = R.weight_backward_slabs(*ops64, dil, per)
+        ops32 = [W._data(B, T)[n] for n in W.OPERANDS]
+        f32 = R.weight_backward(*ops32, dil)
+        assert all(v.dtype == torch.float32 for v in f32.values())
+        errs = [_rel(f32[k].double(), ref[k]) for k in ref]
+        errs += [_rel(a.double(), b) for a, b in zip(R.weight_backward_slabs(*ops32, dil, per), slabs)]
+        worst = max(worst, max(errs))
+        # one column less: the last column of the last item, in both 128-row operands
+        cut = [t.clone() for t in ops64]
+        for i in (0, 3, 4):
+            cut[i][B - 1, :, T - 1] = 0
+        moved = R.weight_backward(*cut, dil)
+        for k in ref:
+            assert _rel(moved[k], ref[k]) > 10 * W.RTOL, (B, T, dil, k)
+        # one tap less (a tap that lies wholly outside the sequence, dil >= T, contributes nothing to begin with)
+        for k in range(3):
+            if k == 1 or dil < T:
+                assert ref["dWd"][:, :, k].abs().max().item() / ref["dWd"].abs().max().item() > 10 * W.RTOL, (B, T, dil, k)
+            else:
+                assert float(ref["dWd"][:, :, k].abs().max()) == 0.0
+        # one slice less
+        for s in slabs:
+            for drop in {0, s.shape[0] - 1}:
+                assert _rel(s.sum(0) - s[drop], s.sum(0)) > 10 * W.RTOL, (B, T, dil, drop)
+    print(f"float32 CPU evaluation: worst rel-to-max distance from float64 {worst:.3e} = {worst / W.RTOL:.4f} of the bar")
+    assert worst <= W.RTOL / 10, worst
