@@ -732,6 +732,30 @@ int pwg_wavenet_stream_delayed_forward(const pwg_wavenet_desc* d, const float* x
                                        float* skip_line_out, const float* hist_in, float* hist_out, const float* packed,
                                        const float* b_dil, const float* b_skip, const float* b_out, int32_t valid_lo,
                                        int32_t valid_hi, float* x_out, float* skips_out, void* stream);
+/* ---- the delayed layer with a position per item: the slotted form (csrc/wavenet_stream.hip, _bf16.hip) ----
+ * For a pool of Parallel WaveGAN look-ahead streams whose utterances start and end independently (utils.PWGStreamPool,
+ * DESIGN.md s11.11).  Replaces pwg_wavenet_stream_delayed_forward / pwg_wavenet_stream_bf16_delayed_forward of a
+ * lock-step batch: the scalar window gives way to `slots` -- the DEVICE table of pwg_conv1d_stream_slots_forward, 4 int32
+ * per item, the same rows, flags and window rule -- with the launch's `rate` (columns per frame) and output `delay`.
+ * A running item's x_out, skips_out, hist_out and skip_line_out are bit for bit what the delayed entry writes for a
+ * batch-1 launch of this item with its window; a FRESH item (slots[4b] == 0) reads hist_in, c_line and skip_line_in as
+ * NULL whatever they hold; a PAUSED item writes hist_out = hist_in and skip_line_out = skip_line_in (zeros if it is also
+ * fresh), stores 0.0f to its x_out and skips_out columns and reads none of its x, c, skips.
+ * Every other parameter and pointer rule is the delayed entry's, except that hist_in, c_line (where c_delay > 0) and,
+ * with skips, skip_line_in must be given: the start of a stream is an item's, not the launch's.  Coverage is that of
+ * pwg_wavenet_stream_delayed_supported / pwg_wavenet_stream_bf16_delayed_supported.  The bf16 entry has no z / g outputs.
+ * These two symbols are purely additive -- no existing signature or behaviour changes -- so pwg_abi_version() stays 15. */
+int pwg_wavenet_stream_slots_forward(const pwg_wavenet_desc* d, const float* x, const float* c, const float* c_line,
+                                     int32_t c_cols, int32_t c_delay, const float* skips, const float* skip_line_in,
+                                     float* skip_line_out, const float* hist_in, float* hist_out, const float* packed,
+                                     const float* b_dil, const float* b_skip, const float* b_out, const int32_t* slots,
+                                     int32_t rate, int32_t delay, float* x_out, float* skips_out, void* stream);
+int pwg_wavenet_stream_slots_forward_bf16(const pwg_wavenet_desc* d, const float* x, const float* c, const float* c_line,
+                                          int32_t c_cols, int32_t c_delay, const float* skips, const float* skip_line_in,
+                                          float* skip_line_out, const float* hist_in, float* hist_out, const void* packed,
+                                          const float* b_dil, const float* b_skip, const float* b_out,
+                                          const int32_t* slots, int32_t rate, int32_t delay, float* x_out,
+                                          float* skips_out, void* stream);
 /* ---- bf16-operand inference form of the same layer (opt-in; csrc/wavenet_bf16.hip) ----
  * The definition of the bf16-operand convolution (pwg_conv1d_bf16_*, above) applied to each of the layer's four
  * convolutions, in ONE launch:
@@ -948,6 +972,27 @@ int pwg_stretch_conv_stream_delayed(const float* x, const float* hist_in, float*
                                     int32_t valid_lo, int32_t valid_hi, void* stream);
 int pwg_delay_line_forward(const float* x, const float* line_in, float* line_out, float* delayed_out, int64_t rows,
                            int32_t n, int32_t columns, void* stream);
+/* The slotted forms of the two entries above (utils.PWGStreamPool): `items` items of `channels` rows
+ * each stand where `rows` stood, and `slots` -- the DEVICE table of pwg_conv1d_stream_slots_forward, one row per item,
+ * same flags and window rule -- stands where the window stood.
+ * pwg_stretch_conv_stream_slots replaces pwg_stretch_conv_stream_delayed: a running item is that launch of its rows with
+ * the window of (`rate` output columns per frame, output `delay`); a fresh item reads hist_in as zeros; a paused item's y
+ * columns are 0.0f and its hist_out is its hist_in (zeros if fresh).
+ * pwg_delay_line_slots_forward replaces pwg_delay_line_forward (which has no window, so this takes the table alone): a
+ * fresh item's line reads as zeros; a paused item's line is copied through and its delayed_out columns are 0.0f.
+ * pwg_slot_seed_history replaces the host-side replication of conv_in's first frame (ConvInUpsampleNetwork.
+ * lookahead_forward): every item that is fresh and not paused gets column 0 of its x (items, channels, n) in all `columns`
+ * columns of its hist (items, channels, columns); every other item's hist is left untouched.
+ * hist_in / line_in must be given (the start of a stream is an item's); up to 65535 items.  Copies and the stage's own
+ * fmaf chain: bit for bit the lock-step entries.
+ * These three symbols are purely additive -- no existing signature or behaviour changes -- so pwg_abi_version() stays 15. */
+int pwg_stretch_conv_stream_slots(const float* x, const float* hist_in, float* hist_out, const float* w, float* y,
+                                  int64_t items, int32_t channels, int32_t n, int32_t scale, int32_t freq_kernel,
+                                  int32_t act, float slope, const int32_t* slots, int32_t rate, int32_t delay, void* stream);
+int pwg_delay_line_slots_forward(const float* x, const float* line_in, float* line_out, float* delayed_out, int64_t items,
+                                 int32_t channels, int32_t n, int32_t columns, const int32_t* slots, void* stream);
+int pwg_slot_seed_history(const float* x, float* hist, int64_t items, int32_t channels, int32_t n, int32_t columns,
+                          const int32_t* slots, void* stream);
 size_t pwg_stretch_conv_backward_workspace_floats(int32_t kernel, int32_t freq_kernel);
 int pwg_stretch_conv_backward(const float* dy, const float* x, const float* w, float* dx, float* dw,
                               int64_t rows, int32_t t_in, int32_t scale, int32_t kernel, int32_t pad_left,

@@ -237,6 +237,10 @@ SIGNATURES = {
     "pwg_wavenet_stream_delayed_hist_floats": (ctypes.c_size_t, [ctypes.POINTER(WaveNetDesc)]),
     "pwg_wavenet_stream_delayed_forward": (ctypes.c_int, [ctypes.POINTER(WaveNetDesc), _vp, _vp, _vp, _i32, _i32] + [_vp] * 9
                                            + [_i32, _i32, _vp, _vp, _vp]),
+    "pwg_wavenet_stream_slots_forward": (ctypes.c_int, [ctypes.POINTER(WaveNetDesc), _vp, _vp, _vp, _i32, _i32] + [_vp] * 9
+                                         + [_vp, _i32, _i32, _vp, _vp, _vp]),
+    "pwg_wavenet_stream_slots_forward_bf16": (ctypes.c_int, [ctypes.POINTER(WaveNetDesc), _vp, _vp, _vp, _i32, _i32]
+                                              + [_vp] * 9 + [_vp, _i32, _i32, _vp, _vp, _vp]),
     "pwg_wavenet_bf16_supported": (ctypes.c_int, [ctypes.POINTER(WaveNetDesc)]),
     "pwg_wavenet_bf16_packed_weight_bytes": (ctypes.c_size_t, [ctypes.POINTER(WaveNetDesc)]),
     "pwg_wavenet_bf16_pack_weights": (ctypes.c_int, [ctypes.POINTER(WaveNetDesc)] + [_vp] * 10),
@@ -288,6 +292,10 @@ SIGNATURES = {
     "pwg_stretch_conv_stream_delayed": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _f32, _i32, _i32,
                                                        _vp]),
     "pwg_delay_line_forward": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp]),
+    "pwg_stretch_conv_stream_slots": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _f32, _vp,
+                                                     _i32, _i32, _vp]),
+    "pwg_delay_line_slots_forward": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
+    "pwg_slot_seed_history": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "pwg_stretch_conv_backward_workspace_floats": (ctypes.c_size_t, [_i32, _i32]),
     "pwg_stretch_conv_backward": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp,
                                                  ctypes.c_size_t, _vp]),

@@ -6,6 +6,7 @@
 //   delayed form          StreamDelay            addends read through a delay line, zeros stored outside a valid window
 //   window rule           stream_slot_window     the valid columns of a launch from a push-relative position
 //   slotted form          StreamSlots            the delayed form with one position per item, read from a device table
+//                         stream_slot_item       ... the row reader, shared with the slotted kernels that are no convolution
 //   mirror rule           StreamMirrorWindow::at the reflect-padded layer of a look-ahead stream: mirror, then resolve
 //   tile rule             stream_tile            column tile from n; 32-row blocks only at 2 x 256 or more workgroups
 //   coverage              stream_geometry        defined in conv1d_stream.hip; both precisions admit the same layers
@@ -159,6 +160,7 @@ __host__ __device__ static inline StreamValid stream_slot_window(int delay, int 
 // at(b) resolves the row, delayed(item) gives the item's StreamDelay: a running item IS a delayed launch with its window.
 constexpr int kStreamSlotInts = 4;
 constexpr int kStreamSlotPaused = 1, kStreamSlotLeftKnown = 2;
+
 struct StreamSlots : StreamLines {
   const int32_t* slots;  // (B, kStreamSlotInts)
   int rate, out_delay;
@@ -168,6 +170,7 @@ struct StreamSlots : StreamLines {
     int valid_lo, valid_hi;
     bool fresh, paused;
   };
+  // The row reader: workgroup-uniform; a table value reaches addressing only through the clamped window and the flags
   __device__ __forceinline__ Item at(int b, int t_out) const {
     const int32_t* __restrict__ row = slots + (size_t)b * kStreamSlotInts;
     const int before = __builtin_amdgcn_readfirstlane(row[0]), left = __builtin_amdgcn_readfirstlane(row[1]);
@@ -190,6 +193,19 @@ struct StreamSlots : StreamLines {
     return dl;
   }
 };
+
+// The same row reader for the slotted kernels that are no convolution and carry no StreamLines (the gated layer, the
+// stretch stage, the delay line and the seeding kernel of a Parallel WaveGAN pool): item b's row for a
+// launch `out_delay` columns late at `rate` columns per frame on t_out output columns
+typedef StreamSlots::Item StreamSlotItem;
+__device__ __forceinline__ StreamSlotItem stream_slot_item(const int32_t* slots, int b, int rate, int out_delay,
+                                                           int t_out) {
+  StreamSlots sl;
+  sl.slots = slots;
+  sl.rate = rate;
+  sl.out_delay = out_delay;
+  return sl.at(b, t_out);
+}
 
 __device__ __forceinline__ float stream_delayed_addend(const float* __restrict__ add, const float* __restrict__ hist,
                                                        int delay, size_t row, int t_out, int j) {

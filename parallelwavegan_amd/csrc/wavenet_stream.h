@@ -27,4 +27,11 @@ __attribute__((visibility("hidden"))) int wavenet_delayed_pointers(const char* n
                                                                    const float* skips, const float* skip_line_in,
                                                                    const float* skip_line_out, const float* skips_out);
 
+// ... and what the slotted form asks beyond them: the table, its rate and delay, and every state input the delayed form
+// may leave NULL (the start of a stream is an item's, in the table; a launch-wide NULL has no meaning)
+__attribute__((visibility("hidden"))) int wavenet_slots_pointers(const char* name, const pwg_wavenet_desc* d,
+                                                                 int32_t c_delay, const float* c_line, const float* skips,
+                                                                 const float* skip_line_in, const float* hist_in,
+                                                                 const int32_t* slots, int32_t rate, int32_t delay);
+
 }  // namespace pwg

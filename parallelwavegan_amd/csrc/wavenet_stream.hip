@@ -55,6 +55,12 @@
 // K = 64 contraction, + bias, + the skip addend / + the residual, * scale.  It depends on the layer alone: not on n, the
 // batch, the chunk's position, c_delay or its alignment, or which staging path a window took (an operand is the same
 // fp32 value through the DMA pass and through registers; the addend is the same value from the line and from the chunk).
+//
+// The slotted form (pwg_wavenet_stream_slots_forward) is the delayed form with one position per item
+// (wavenet_stream_kernel<WnSlotsArgs>): every workgroup reads its item's row of the device table of stream_common.h and
+// derives the item's valid window itself.  A running item is from there on the delayed form, the same code and the same
+// bits; a fresh item reads hist_in, c_line and skip_line_in as NULL; a paused item copies its state through, stores zeros
+// and returns in front of every barrier.
 #include "stream_common.h"
 #include "wavenet_gate.h"
 #include "wavenet_stream.h"
@@ -96,9 +102,23 @@ struct WnDelayedArgs : WnStreamArgs {
   int valid_lo, valid_hi;     // output columns (chunk-relative)
 };
 
+// The slotted form (pwg_wavenet_stream_slots_forward): the delayed form with one position per item,
+// read from the device table of stream_common.h.  A running item IS a delayed launch with its own window; a fresh one
+// reads hist_in, c_line and skip_line_in as NULL; a paused one copies its state through (the history rule with n = 0),
+// stores zeros and returns in front of every barrier, reading none of x, c, skips.
+struct WnSlotsArgs : WnStreamArgs {
+  const float* c_line;        // (B, 80, c_cols) or NULL (zeros)
+  const float* skip_line_in;  // (B, 64, d); required with skips
+  float* skip_line_out;       // (B, 64, d); unused without skips
+  int c_cols, c_delay;        // 0 <= c_delay <= c_cols
+  const int32_t* slots;       // (B, kStreamSlotInts)
+  int rate, out_delay;        // output columns per frame, delay of the output
+};
+
 template <class ARGS>
 __global__ __launch_bounds__(256, 2) void wavenet_stream_kernel(ARGS a) {
-  constexpr bool DELAYED = std::is_same<ARGS, WnDelayedArgs>::value;
+  constexpr bool SLOTTED = std::is_same<ARGS, WnSlotsArgs>::value;
+  constexpr bool DELAYED = std::is_same<ARGS, WnDelayedArgs>::value || SLOTTED;
   constexpr int NQ1 = WS_ROWS / 8;  // 16-B weight records per lane and row tile in phase 1 (4 k-steps each)
   constexpr int NQ2 = WN_R / 8;     // phase 2: K = 64 rows of g
   extern __shared__ __attribute__((aligned(16))) float tile[];  // [ROWS][64]; rows 0..63 are overwritten by g
@@ -113,14 +133,48 @@ __global__ __launch_bounds__(256, 2) void wavenet_stream_kernel(ARGS a) {
   const int H = 2 * a.dil;
   const float* __restrict__ xb = a.x + (long)b * WN_R * n;
   const float* __restrict__ cb = a.c + (long)b * WS_AUX * n;
-  const float* __restrict__ hb = a.hist_in ? a.hist_in + (long)b * WN_R * H : nullptr;
+  // SLOTTED: what this item's table row resolves to -- fresh, paused and its own window
+  [[maybe_unused]] StreamSlotItem item{};
+  bool fresh = false;
+  if constexpr (SLOTTED) {
+    item = stream_slot_item(a.slots, b, a.rate, a.out_delay, n);
+    fresh = item.fresh;
+  }
+  const float* __restrict__ hb = a.hist_in && !fresh ? a.hist_in + (long)b * WN_R * H : nullptr;
   // the aux window's past (delayed form): the conditioning line, c_cols columns; the window starts c_delay columns early
   const float* __restrict__ lb = nullptr;
+  // ... its skip line (all items'; NULL: zeros) and its valid window: the launch's, or the item's
+  [[maybe_unused]] const float* __restrict__ sli = nullptr;
+  [[maybe_unused]] int valid_lo = 0, valid_hi = 0;
   int L = 0, c_delay = 0;
   if constexpr (DELAYED) {
     L = a.c_cols;
     c_delay = a.c_delay;
-    lb = a.c_line ? a.c_line + (long)b * WS_AUX * L : nullptr;
+    lb = a.c_line && !fresh ? a.c_line + (long)b * WS_AUX * L : nullptr;
+    sli = fresh ? nullptr : a.skip_line_in;
+    if constexpr (SLOTTED) {
+      valid_lo = item.valid_lo;
+      valid_hi = item.valid_hi;
+    } else {
+      valid_lo = a.valid_lo;
+      valid_hi = a.valid_hi;
+    }
+  }
+  if constexpr (SLOTTED) {
+    if (item.paused) {  // (workgroup-uniform) state out = state in, zeros for both output tiles; in front of every barrier
+      stream_write_history<4>(xb, hb, a.hist_out + (long)b * WN_R * H, WN_R, 0, H, false, blockIdx.x, gridDim.x);
+      if (a.skips)
+        stream_write_history<4>(a.skips + (long)b * WN_S * n, sli ? sli + (long)b * WN_S * a.dil : nullptr,
+                                a.skip_line_out + (long)b * WN_S * a.dil, WN_S, 0, a.dil, false, blockIdx.x, gridDim.x);
+      for (int e = tid; e < WN_R * WN_COLS; e += 256) {
+        const int row = e / WN_COLS, j = n0 + (e - row * WN_COLS);
+        if (j >= n) continue;
+        const long o = ((long)b * WN_R + row) * n + j;
+        a.x_out[o] = 0.f;
+        a.skips_out[o] = 0.f;
+      }
+      return;
+    }
   }
 
   // ---- stage the operand tile: window `tap` of X starts at chunk-relative column n0 + (tap - 2) d, the aux window at
@@ -299,10 +353,10 @@ __global__ __launch_bounds__(256, 2) void wavenet_stream_kernel(ARGS a) {
           if (j >= n) continue;
           if (pass == 0) {
             if (a.skips)
-              e4[e] += stream_delayed_addend(a.skips, a.skip_line_in, a.dil, (size_t)b * WN_S + h * 32 + rl, n, j);
+              e4[e] += stream_delayed_addend(a.skips, sli, a.dil, (size_t)b * WN_S + h * 32 + rl, n, j);
             if (a.skip_mul != 1.0f) e4[e] *= a.skip_mul;
           }
-          if (j < a.valid_lo || j >= a.valid_hi) e4[e] = 0.f;
+          if (j < valid_lo || j >= valid_hi) e4[e] = 0.f;
           if (!vec) out[o + e] = e4[e];
         }
         if (vec && nq < n) *reinterpret_cast<float4*>(out + o) = make_float4(e4[0], e4[1], e4[2], e4[3]);
@@ -342,7 +396,7 @@ __global__ __launch_bounds__(256, 2) void wavenet_stream_kernel(ARGS a) {
   // ---- delayed form: skip_line_out = last d columns of concat(skip_line_in, skips), raw
   if constexpr (DELAYED) {
     if (a.skips)
-      stream_write_history<4>(a.skips + (long)b * WN_S * n, a.skip_line_in ? a.skip_line_in + (long)b * WN_S * a.dil : nullptr,
+      stream_write_history<4>(a.skips + (long)b * WN_S * n, sli ? sli + (long)b * WN_S * a.dil : nullptr,
                               a.skip_line_out + (long)b * WN_S * a.dil, WN_S, n, a.dil, false, blockIdx.x, gridDim.x);
   }
 }
@@ -411,6 +465,22 @@ int wavenet_delayed_pointers(const char* name, const pwg_wavenet_desc* d, const 
               "%s: skips_out must not alias skips (tiles read their neighbours' skip columns)", name);
   PWG_REQUIRE(aligned(c_line, 3) && aligned(skips, 3) && aligned(skip_line_in, 3) && aligned(skip_line_out, 3),
               PWG_ERR_BAD_SHAPE, "%s: unaligned tensor (4 B)", name);
+  return PWG_OK;
+}
+
+int wavenet_slots_pointers(const char* name, const pwg_wavenet_desc* d, int32_t c_delay, const float* c_line,
+                           const float* skips, const float* skip_line_in, const float* hist_in, const int32_t* slots,
+                           int32_t rate, int32_t delay) {
+  PWG_REQUIRE(slots != nullptr, PWG_ERR_NULL, "%s: slots is NULL", name);
+  PWG_REQUIRE(aligned(slots, 3), PWG_ERR_BAD_SHAPE, "%s: unaligned slot table", name);
+  PWG_REQUIRE(rate >= 1 && delay >= 0, PWG_ERR_BAD_SHAPE, "%s: rate = %d, delay = %d (needs rate >= 1, delay >= 0)", name,
+              rate, delay);
+  PWG_REQUIRE(hist_in != nullptr, PWG_ERR_NULL,
+              "%s: hist_in is NULL (the start of a stream is an item's, in the table)", name);
+  PWG_REQUIRE(c_line != nullptr || c_delay == 0, PWG_ERR_NULL,
+              "%s: c_line is NULL with c_delay = %d (a fresh item does not read it)", name, c_delay);
+  PWG_REQUIRE(skips == nullptr || skip_line_in != nullptr, PWG_ERR_NULL,
+              "%s: skips needs skip_line_in (%d columns; a fresh item does not read it)", name, d->dilation);
   return PWG_OK;
 }
 
@@ -525,6 +595,37 @@ extern "C" int pwg_wavenet_stream_delayed_forward(const pwg_wavenet_desc* d, con
   a.valid_lo = valid_lo;
   a.valid_hi = valid_hi;
   return wavenet_stream_launch(name, "wavenet_stream_delayed_kernel", d, a,
+                               (double)d->batch * (2.0 * WN_R * 2.0 * d->dilation + (skips ? 2.0 * WN_S * d->dilation : 0.0)),
+                               (hipStream_t)stream_);
+}
+
+// The slotted form: pwg_wavenet_stream_delayed_forward with the window replaced by the table, its rate and delay
+extern "C" int pwg_wavenet_stream_slots_forward(const pwg_wavenet_desc* d, const float* x, const float* c,
+                                                const float* c_line, int32_t c_cols, int32_t c_delay, const float* skips,
+                                                const float* skip_line_in, float* skip_line_out, const float* hist_in,
+                                                float* hist_out, const float* packed, const float* b_dil,
+                                                const float* b_skip, const float* b_out, const int32_t* slots,
+                                                int32_t rate, int32_t delay, float* x_out, float* skips_out,
+                                                void* stream_) {
+  const char* name = "wavenet_stream_slots_forward";
+  int rc = wavenet_delayed_geometry(d, c_delay);
+  if (rc != PWG_OK) return rc;
+  rc = wavenet_slots_pointers(name, d, c_delay, c_line, skips, skip_line_in, hist_in, slots, rate, delay);
+  if (rc != PWG_OK) return rc;
+  rc = wavenet_delayed_pointers(name, d, c_line, c_cols, c_delay, skips, skip_line_in, skip_line_out, skips_out);
+  if (rc != PWG_OK) return rc;
+  WnSlotsArgs a;
+  rc = wavenet_stream_fill(name, &a, d, x, c, skips, hist_in, hist_out, packed, b_dil, b_skip, b_out, x_out, skips_out);
+  if (rc != PWG_OK) return rc;
+  a.c_line = c_line;
+  a.c_cols = c_line ? c_cols : 0;
+  a.c_delay = c_delay;
+  a.skip_line_in = skips ? skip_line_in : nullptr;
+  a.skip_line_out = skips ? skip_line_out : nullptr;
+  a.slots = slots;
+  a.rate = rate;
+  a.out_delay = delay;
+  return wavenet_stream_launch(name, "wavenet_stream_slots_kernel", d, a,
                                (double)d->batch * (2.0 * WN_R * 2.0 * d->dilation + (skips ? 2.0 * WN_S * d->dilation : 0.0)),
                                (hipStream_t)stream_);
 }

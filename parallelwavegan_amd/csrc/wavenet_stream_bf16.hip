@@ -1,11 +1,13 @@
 // wavenet_stream_bf16.hip -- the streaming forms of the gated Parallel WaveGAN layer (csrc/wavenet_stream.hip) with bf16
 // operands: ONE launch per layer and chunk, computed the way wavenet_bf16_layer_kernel<32> (csrc/wavenet_bf16.hip)
-// computes.  One kernel template over its argument struct, two instantiations:
+// computes.  One kernel template over its argument struct, three instantiations:
 //
 //   causal   (WsbArgs)         X = concat(hist_in, x); taps X[n - 2d], X[n - d], X[n]; aux c[n]; residual x[n]
 //   delayed  (WsbDelayedArgs)  the NON-causal layer of a look-ahead stream on a time axis shifted by d: the same taps,
 //                              aux concat(c_line, c)[n - c_delay], residual X[n - d], skip addend
 //                              concat(skip_line_in, skips)[n], zeros STORED outside [valid_lo, valid_hi)
+//   slotted  (WsbSlotsArgs)    the delayed form with one position per item, read from the device table of
+//                              stream_common.h (a pool of streams; csrc/wavenet_stream.hip)
 //
 //     z      = W_dil (*) bf16(X) + W_aux . bf16(C) + b_dil                 (128 rows; K = 3 * 64 + 80 = 272, padded to 288)
 //     g      = bf16( tanh(z[:64]) * sigmoid(z[64:]) )                       (gate_fp32, then nearest-even)
@@ -77,9 +79,20 @@ struct WsbDelayedArgs : WsbArgs {
   int valid_lo, valid_hi;     // output columns (chunk-relative)
 };
 
+// The slotted form (csrc/wavenet_stream.hip, WnSlotsArgs): one position per item, from the table
+struct WsbSlotsArgs : WsbArgs {
+  const float* c_line;        // (B, 80, c_cols) or NULL (zeros)
+  const float* skip_line_in;  // (B, 64, d); required with skips
+  float* skip_line_out;       // (B, 64, d); unused without skips
+  int c_cols, c_delay;        // 0 <= c_delay <= c_cols
+  const int32_t* slots;       // (B, kStreamSlotInts)
+  int rate, out_delay;        // output columns per frame, delay of the output
+};
+
 template <class ARGS>
 __global__ __launch_bounds__(256, 2) void wavenet_stream_bf16_kernel(ARGS a) {
-  constexpr bool DELAYED = std::is_same<ARGS, WsbDelayedArgs>::value;
+  constexpr bool SLOTTED = std::is_same<ARGS, WsbSlotsArgs>::value;
+  constexpr bool DELAYED = std::is_same<ARGS, WsbDelayedArgs>::value || SLOTTED;
   constexpr int TILE = 32;           // v_mfma_f32_32x32x16_bf16: a wave owns one 32 x 32 tile of each half
   constexpr int HL = 64 / TILE;      // lane groups along the reduction
   constexpr int KSTEP = 8 * HL;      // reduction elements per MFMA (16)
@@ -105,14 +118,48 @@ __global__ __launch_bounds__(256, 2) void wavenet_stream_bf16_kernel(ARGS a) {
   const int H = 2 * dil;
   const float* __restrict__ xb = a.x + (long)b * BR * n;
   const float* __restrict__ cb = a.c + (long)b * BA * n;
-  const float* __restrict__ hb = a.hist_in ? a.hist_in + (long)b * BR * H : nullptr;
+  // SLOTTED: what this item's table row resolves to -- fresh, paused and its own window
+  [[maybe_unused]] StreamSlotItem item{};
+  bool fresh = false;
+  if constexpr (SLOTTED) {
+    item = stream_slot_item(a.slots, b, a.rate, a.out_delay, n);
+    fresh = item.fresh;
+  }
+  const float* __restrict__ hb = a.hist_in && !fresh ? a.hist_in + (long)b * BR * H : nullptr;
   // the aux window's past (delayed form): the conditioning line, L columns; the window starts c_delay columns early
   const float* __restrict__ lb = nullptr;
+  // ... its skip line (all items'; NULL: zeros) and its valid window: the launch's, or the item's
+  [[maybe_unused]] const float* __restrict__ sli = nullptr;
+  [[maybe_unused]] int valid_lo = 0, valid_hi = 0;
   int L = 0, c_delay = 0;
   if constexpr (DELAYED) {
     L = a.c_cols;
     c_delay = a.c_delay;
-    lb = a.c_line ? a.c_line + (long)b * BA * L : nullptr;
+    lb = a.c_line && !fresh ? a.c_line + (long)b * BA * L : nullptr;
+    sli = fresh ? nullptr : a.skip_line_in;
+    if constexpr (SLOTTED) {
+      valid_lo = item.valid_lo;
+      valid_hi = item.valid_hi;
+    } else {
+      valid_lo = a.valid_lo;
+      valid_hi = a.valid_hi;
+    }
+  }
+  if constexpr (SLOTTED) {
+    if (item.paused) {  // (workgroup-uniform) state out = state in, zeros for both output tiles; in front of every barrier
+      stream_write_history<4>(xb, hb, a.hist_out + (long)b * BR * H, BR, 0, H, false, blockIdx.x, gridDim.x);
+      if (a.skips)
+        stream_write_history<4>(a.skips + (long)b * BS * n, sli ? sli + (long)b * BS * dil : nullptr,
+                                a.skip_line_out + (long)b * BS * dil, BS, 0, dil, false, blockIdx.x, gridDim.x);
+      for (int e = tid; e < BR * BCOLS; e += 256) {
+        const int row = e / BCOLS, j = n0 + (e - row * BCOLS);
+        if (j >= n) continue;
+        const long o = ((long)b * BR + row) * n + j;
+        a.x_out[o] = 0.f;
+        a.skips_out[o] = 0.f;
+      }
+      return;
+    }
   }
 
   // accumulator element i: row h * 32 + rowin(i), column cn * 32 + r
@@ -198,7 +245,7 @@ __global__ __launch_bounds__(256, 2) void wavenet_stream_bf16_kernel(ARGS a) {
             if (kb) sres[i] = kb[o];
           }
         } else {
-          const float* __restrict__ kb = (a.skips && a.skip_line_in) ? a.skip_line_in + (long)b * BS * dil : nullptr;
+          const float* __restrict__ kb = (a.skips && sli) ? sli + (long)b * BS * dil : nullptr;
 #pragma unroll
           for (int i = 0; i < NREG; ++i) {
             const int row = row0 + rowin(i);
@@ -310,7 +357,7 @@ __global__ __launch_bounds__(256, 2) void wavenet_stream_bf16_kernel(ARGS a) {
   // delayed form stores zeros outside the valid window
   if (nc < n) {
     bool valid = true;
-    if constexpr (DELAYED) valid = nc >= a.valid_lo && nc < a.valid_hi;
+    if constexpr (DELAYED) valid = nc >= valid_lo && nc < valid_hi;
 #pragma unroll
     for (int i = 0; i < NREG; ++i) {
       const int row = h * 32 + rowin(i);
@@ -329,7 +376,7 @@ __global__ __launch_bounds__(256, 2) void wavenet_stream_bf16_kernel(ARGS a) {
   // ---- delayed form: skip_line_out = last d columns of concat(skip_line_in, skips), raw
   if constexpr (DELAYED) {
     if (a.skips)
-      stream_write_history<4>(a.skips + (long)b * BS * n, a.skip_line_in ? a.skip_line_in + (long)b * BS * dil : nullptr,
+      stream_write_history<4>(a.skips + (long)b * BS * n, sli ? sli + (long)b * BS * dil : nullptr,
                               a.skip_line_out + (long)b * BS * dil, BS, n, dil, false, blockIdx.x, gridDim.x);
   }
 }
@@ -434,6 +481,38 @@ extern "C" int pwg_wavenet_stream_bf16_delayed_forward(const pwg_wavenet_desc* d
   a.valid_lo = valid_lo;
   a.valid_hi = valid_hi;
   return stream_bf16_launch(name, "wavenet_stream_bf16_delayed_kernel", d, a,
+                            (double)d->batch * (2.0 * BR * 2.0 * d->dilation + (skips ? 2.0 * BS * d->dilation : 0.0)),
+                            (hipStream_t)stream_);
+}
+
+// The slotted form (pwg_wavenet_stream_slots_forward) under the numerical definition above; no z / g outputs
+extern "C" int pwg_wavenet_stream_slots_forward_bf16(const pwg_wavenet_desc* d, const float* x, const float* c,
+                                                     const float* c_line, int32_t c_cols, int32_t c_delay,
+                                                     const float* skips, const float* skip_line_in, float* skip_line_out,
+                                                     const float* hist_in, float* hist_out, const void* packed,
+                                                     const float* b_dil, const float* b_skip, const float* b_out,
+                                                     const int32_t* slots, int32_t rate, int32_t delay, float* x_out,
+                                                     float* skips_out, void* stream_) {
+  const char* name = "wavenet_stream_slots_forward_bf16";
+  int rc = wavenet_delayed_geometry(d, c_delay);
+  if (rc != PWG_OK) return rc;
+  rc = wavenet_slots_pointers(name, d, c_delay, c_line, skips, skip_line_in, hist_in, slots, rate, delay);
+  if (rc != PWG_OK) return rc;
+  rc = wavenet_delayed_pointers(name, d, c_line, c_cols, c_delay, skips, skip_line_in, skip_line_out, skips_out);
+  if (rc != PWG_OK) return rc;
+  WsbSlotsArgs a;
+  rc = stream_bf16_fill(name, &a, d, x, c, skips, hist_in, hist_out, packed, b_dil, b_skip, b_out, x_out, skips_out, nullptr,
+                        nullptr);
+  if (rc != PWG_OK) return rc;
+  a.c_line = c_line;
+  a.c_cols = c_line ? c_cols : 0;
+  a.c_delay = c_delay;
+  a.skip_line_in = skips ? skip_line_in : nullptr;
+  a.skip_line_out = skips ? skip_line_out : nullptr;
+  a.slots = slots;
+  a.rate = rate;
+  a.out_delay = delay;
+  return stream_bf16_launch(name, "wavenet_stream_bf16_slots_kernel", d, a,
                             (double)d->batch * (2.0 * BR * 2.0 * d->dilation + (skips ? 2.0 * BS * d->dilation : 0.0)),
                             (hipStream_t)stream_);
 }

@@ -390,11 +390,55 @@ def pwg_lookahead_state_shapes(plan, batch):
     return [(batch, ch, cols) for launch in plan for ch, cols in launch.state]
 
 
+# Where the items of a launch stand, as a slotted walk hands it out in the place of the valid window ``(lo, hi)``: the
+# device table (one row per item), the launch's rate and output delay -- the kernel derives every item's window itself
+# (utils.PWGStreamPool).  ``seed``: for ``conv_in`` with a context window the table whose fresh running
+# items get their first frame replicated into the history in front of the launch (``slots`` is then the second table,
+# in which no item is fresh); None for every other launch.
+SlotPosition = collections.namedtuple("SlotPosition", "slots rate delay seed")
+
+# ---- the rule of a Parallel WaveGAN stream launch that is no convolution, by the rule of ``_STREAM_KERNELS``: a kind's
+# row per form; the position decides the form and how it is passed -- ``valid=(lo, hi)`` or the table, rate and delay
+_PWG_STREAM_KERNELS = {
+    ("stage", "delayed"): ops.stretch_conv_stream_delayed,
+    ("stage", "slots"): ops.stretch_conv_stream_slots,
+    ("layer", "delayed", "fp32"): ops.wavenet_stream_delayed_forward,
+    ("layer", "delayed", "bf16"): ops.wavenet_stream_delayed_forward_bf16,
+    ("layer", "slots", "fp32"): ops.wavenet_stream_slots_forward,
+    ("layer", "slots", "bf16"): lambda *args, **kw: ops.wavenet_stream_slots_forward(*args, precision="bf16", **kw),
+}
+
+
+def _position(valid):
+    """``(form, keywords)`` of the position a walk handed out."""
+    if isinstance(valid, SlotPosition):
+        return "slots", {"slots": valid.slots, "rate": valid.rate, "delay": valid.delay}
+    return "delayed", {"valid": valid}
+
+
+def pwg_stream_launch(kind, valid, *args, precision=None):
+    """One launch of ``kind`` ("stage": an upsampler stage, fp32 in either precision; "layer": a gated layer, in
+    ``precision``) of the Parallel WaveGAN look-ahead walk on ``args``, what its entry takes in front of the position;
+    ``valid``: what the walk handed out, a window (lock-step) or a :class:`SlotPosition` (a pool)."""
+    form, where = _position(valid)
+    return _PWG_STREAM_KERNELS[(kind, form) if precision is None else (kind, form, precision)](*args, **where)
+
+
+def lookahead_line(x, pair, position=None, delayed=False):
+    """A delay line of the Parallel WaveGAN look-ahead walk on the chunk ``x``: ``pair = (line_in, line_out)``;
+    ``position``: what the walk handed out -- a line has no window, a slotted one reads fresh and paused from the table."""
+    if isinstance(position, SlotPosition):
+        return ops.delay_line_slots_forward(x, pair[0], pair[1], position.slots, delayed=delayed)
+    return ops.delay_line_forward(x, pair[0], pair[1], delayed=delayed)
+
+
 def lookahead_launch(cv, desc, x, hist=(None, None), valid=None, precision="fp32"):
     """One delayed launch of ``cv`` under ``desc`` without addends: the history pair and the valid window are the
-    caller's (``conv_in`` and the 1 x 1 convolutions of the Parallel WaveGAN look-ahead stream).  ``precision``, a module
-    in bf16 mode and a layer the kernel does not cover: by the rule of :func:`_launch`."""
-    return _launch("delayed", precision, cv, desc, x, hist, valid=valid)
+    caller's (``conv_in`` and the 1 x 1 convolutions of the Parallel WaveGAN look-ahead stream); a :class:`SlotPosition`
+    in the window's place: the slotted form.  ``precision``, a module in bf16 mode and a layer the kernel does not
+    cover: by the rule of :func:`_launch`."""
+    form, where = _position(valid)
+    return _launch(form, precision, cv, desc, x, hist, **where)
 
 
 def pointwise_desc(cv, batch, n, **fused):
@@ -425,3 +469,41 @@ class PWGLookaheadWalk(_Walk):
             raise RuntimeError(f"look-ahead walk out of step: the plan expects {launch.kind} {launch.module}, the model "
                                f"ran {kind} {module}")
         return launch, [self._pair() for _ in launch.state], self._window(launch, frames * launch.rate)
+
+
+def slot_table_rows_in(rows):
+    """The second table of a Parallel WaveGAN pool's step, from the rows of the first: ``(before + 1, left - 1, flags,
+    own)``.  ``conv_in``, launched with ``delay + rate`` over it, gets the windows of ``delay`` over the first --
+    ``delay + rate - (before + 1) * rate = delay - before * rate``, ``delay + rate + (left - 1) * rate = delay + left *
+    rate`` -- and no item of it is fresh, so the history the seeding kernel wrote is read."""
+    return [(before + 1, left - 1, flags, own) for before, left, flags, own in rows]
+
+
+class PWGSlotWalk(_Walk):
+    """:class:`PWGLookaheadWalk` for a batch whose items sit at different points of different utterances
+    (utils.PWGStreamPool): ``take`` has the same contract, but hands out a :class:`SlotPosition` --
+    the device table ``slots``, the launch's rate and delay -- where the lock-step walk hands out the valid window, and
+    the model launches the slotted form.  ``slots_in``: the second table (:func:`slot_table_rows_in`), which ``conv_in``
+    with a context window takes with ``delay + rate`` behind the seeding kernel; None for a plan whose ``conv_in`` keeps
+    no history.  There is no start-of-stream walk: ``state_in`` is always a half, and an item that starts an utterance
+    is fresh in the table."""
+
+    def __init__(self, plan, state_in, state_out, slots, slots_in=None, precision="fp32"):
+        if state_in is None:
+            raise ValueError("PWGSlotWalk: state_in is a ping-pong half; the start of a stream is an item's, in the table")
+        super().__init__(plan, state_in, state_out, precision=precision)
+        self.slots, self.slots_in = slots, slots_in
+
+    def take(self, kind, module, frames):
+        """The next launch of the plan, which must be ``(kind, module)`` -> ``(launch, [(state_in, state_out), ...],
+        SlotPosition)``; ``frames`` is the lock-step walk's and not needed here: the kernel knows its columns."""
+        launch = next(self._plan)
+        if launch.kind != kind or launch.module is not module:
+            raise RuntimeError(f"look-ahead walk out of step: the plan expects {launch.kind} {launch.module}, the model "
+                               f"ran {kind} {module}")
+        pairs = [self._pair() for _ in launch.state]
+        if kind == "conv_in" and pairs:
+            if self.slots_in is None:
+                raise RuntimeError("PWGSlotWalk: conv_in keeps a history and needs the second table (slots_in)")
+            return launch, pairs, SlotPosition(self.slots_in, launch.rate, launch.delay + launch.rate, self.slots)
+        return launch, pairs, SlotPosition(self.slots, launch.rate, launch.delay, None)

@@ -11,7 +11,8 @@ from .conv import Conv1d as _Conv1d
 from .conv import bf16_no_backward_error, group_image, resblock_split_admitted, resunit_split_admitted
 
 
-from .causal_conv import CausalConv1d, LookaheadLaunch, lookahead_delay  # noqa: E402  (depends on .conv only)
+from .causal_conv import (CausalConv1d, LookaheadLaunch, lookahead_delay,  # noqa: E402  (depends on .conv only)
+                          pwg_stream_launch)
 from .dropout import Dropout as _Dropout  # noqa: E402
 
 
@@ -277,7 +278,8 @@ class WaveNetResidualBlock(torch.nn.Module):
         ``dilation`` columns later than ``x``.  ``hist = (hist_in, hist_out)``: the last ``2 * dilation`` columns of the
         block's input (``hist_in`` None: start of stream); the conditioning is read ``c_delay`` columns late from
         ``concat(c_line, c)``; the running skip sum goes through ``skip_line = (line_in, line_out)`` of ``dilation``
-        columns; columns outside ``valid = (lo, hi)`` are stored as zeros.  One launch.  ``precision="bf16"``: the same
+        columns; columns outside ``valid = (lo, hi)`` are stored as zeros -- a ``causal_conv.SlotPosition`` in its place
+        (a pool's walk): the slotted launch, every item at its own position.  One launch.  ``precision="bf16"``: the same
         launch with bf16 operands (csrc/wavenet_stream_bf16.hip); history and lines stay raw fp32."""
         if self.use_causal_conv:
             raise ValueError("WaveNetResidualBlock: a causal block streams without look-ahead (stream_forward, "
@@ -292,10 +294,10 @@ class WaveNetResidualBlock(torch.nn.Module):
         with torch.no_grad():
             b_d, b_s, b_o = (None if cv.bias is None else cv.bias.detach()
                              for cv in (self.conv, self.conv1x1_skip, self.conv1x1_out))
-            forward = ops.wavenet_stream_delayed_forward_bf16 if bf16 else ops.wavenet_stream_delayed_forward
-            return forward(self.fused_desc(x.shape[0], x.shape[-1], skip_scale), x.contiguous(), c.contiguous(), c_line,
-                           c_delay, skips, skip_line, hist[0], hist[1],
-                           self.stream_image_bf16() if bf16 else self.stream_image(), b_d, b_s, b_o, valid)
+            return pwg_stream_launch("layer", valid, self.fused_desc(x.shape[0], x.shape[-1], skip_scale), x.contiguous(),
+                                     c.contiguous(), c_line, c_delay, skips, skip_line, hist[0], hist[1],
+                                     self.stream_image_bf16() if bf16 else self.stream_image(), b_d, b_s, b_o,
+                                     precision="bf16" if bf16 else "fp32")
 
     # ---- utterances of different lengths in one batch (the ragged forms of csrc/wavenet.hip and csrc/wavenet_bf16.hip;
     # DESIGN.md s9.6): one launch, no per-convolution path

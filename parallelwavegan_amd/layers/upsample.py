@@ -211,12 +211,15 @@ class UpsampleNetwork(torch.nn.Module):
     @torch.no_grad()
     def lookahead_forward(self, c, walk, frames):
         """The non-causal ``forward`` on the next chunk of a look-ahead stream (``frames`` mel frames): one delayed
-        launch per stage, state and valid window from ``walk`` (a :class:`layers.causal_conv.PWGLookaheadWalk`)."""
+        launch per stage, state and valid window from ``walk`` (a :class:`layers.causal_conv.PWGLookaheadWalk`; a
+        :class:`layers.causal_conv.PWGSlotWalk` hands out the slot table in the window's place: the slotted launch)."""
+        from .causal_conv import pwg_stream_launch
+
         for i in self._stages:
             conv, scale = self.up_layers[i + 1], self.up_layers[i].x_scale
             _, ((hist_in, hist_out),), valid = walk.take("stage", conv, frames)
-            c = ops.stretch_conv_stream_delayed(c, hist_in, hist_out, conv.weight_tensor().detach(), scale,
-                                                conv.kernel_size[0], self.act, self.slope, valid)
+            c = pwg_stream_launch("stage", valid, c, hist_in, hist_out, conv.weight_tensor().detach(), scale,
+                                  conv.kernel_size[0], self.act, self.slope)
         return c
 
 
@@ -355,13 +358,17 @@ class ConvInUpsampleNetwork(torch.nn.Module):
         """The non-causal ``forward`` on the next frames c (B, C, n) of a look-ahead stream -> (B, C, n * prod(scales)),
         late by the plan's delay.  The start of a stream replicates the first frame into ``conv_in``'s history (what
         ``inference()``'s replicate padding gives on the left); the end is the caller's: it feeds copies of the last
-        frame.  ``conv_in`` runs in the walk's precision; the stretch stages are fp32 in either."""
-        from .causal_conv import lookahead_launch
+        frame.  ``conv_in`` runs in the walk's precision; the stretch stages are fp32 in either.  A slotted walk
+        (:class:`layers.causal_conv.PWGSlotWalk`): the start of a stream is an item's, so the seeding kernel replicates
+        the first frame of the fresh running items into the input history, and ``conv_in`` runs over the second table."""
+        from .causal_conv import SlotPosition, lookahead_launch
 
         cv, w, n = self.conv_in, self.aux_context_window, c.shape[-1]
         _, pairs, valid = walk.take("conv_in", cv, n)
         hist_in, hist_out = pairs[0] if pairs else (None, None)
-        if pairs and hist_in is None:
+        if pairs and isinstance(valid, SlotPosition):
+            ops.slot_seed_history(c, hist_in, valid.seed)
+        elif pairs and hist_in is None:
             hist_in = c[:, :, :1].expand(-1, -1, 2 * w).contiguous()
         c = lookahead_launch(cv, self._lookahead_desc(c.shape[0], n), c, (hist_in, hist_out), valid, walk.precision)
         return self.upsample.lookahead_forward(c, walk, n)

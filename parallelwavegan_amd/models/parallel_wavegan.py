@@ -313,7 +313,7 @@ class ParallelWaveGANGenerator(torch.nn.Module, _WeightNormMixin):
         line, and every launch stores zeros outside the utterance.  The last block applies sqrt(1 / layers).  The walk's
         ``precision`` is the push's: ``"bf16"`` runs ``conv_in``, the 1 x 1 convolutions and the gated layers with bf16
         operands; the stretch stages, the delay lines and every state tensor stay fp32."""
-        from ..layers.causal_conv import lookahead_pointwise
+        from ..layers.causal_conv import lookahead_line, lookahead_pointwise
 
         frames, precision = c.shape[-1], walk.precision
         if isinstance(self.upsample_net, upsample.ConvInUpsampleNetwork):
@@ -321,13 +321,13 @@ class ParallelWaveGANGenerator(torch.nn.Module, _WeightNormMixin):
         else:
             c = self.upsample_net.lookahead_forward(c, walk, frames)
         assert c.size(-1) == z.size(-1)
-        _, pairs, _ = walk.take("noise", None, frames)
+        _, pairs, where = walk.take("noise", None, frames)
         if pairs:
-            z = ops.delay_line_forward(z, pairs[0][0], pairs[0][1], delayed=True)
+            z = lookahead_line(z, pairs[0], where, delayed=True)
         _, _, valid = walk.take("first_conv", self.first_conv, frames)
         x = lookahead_pointwise(self.first_conv, z, valid, precision)
-        _, ((c_line, c_line_out),), _ = walk.take("cond_line", None, frames)
-        ops.delay_line_forward(c, c_line, c_line_out)
+        _, ((c_line, c_line_out),), where = walk.take("cond_line", None, frames)
+        lookahead_line(c, (c_line, c_line_out), where)
         skips, n = None, len(self.conv_layers)
         for i, f in enumerate(self.conv_layers):
             launch, pairs, valid = walk.take("layer", f, frames)

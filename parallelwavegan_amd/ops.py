@@ -977,6 +977,103 @@ def delay_line_forward(x, line_in, line_out, delayed=False):
     return out
 
 
+# ---- the slotted forms of the four launches above (utils.PWGStreamPool): one position per item, read
+# from the device table of :func:`conv1d_stream_slots_forward`; every state input must be given
+
+def _slot_table(name, slots, batch):
+    if slots is None or not slots.is_cuda or slots.dtype != torch.int32 or not slots.is_contiguous():
+        raise RuntimeError(f"{name}: slots must be a contiguous int32 device tensor (the kernel reads it; there is no CPU "
+                           "fallback path)")
+    assert tuple(slots.shape) == (batch, SLOT_INTS), (tuple(slots.shape), batch)
+    return slots
+
+
+def wavenet_stream_slots_forward(desc, x, c, c_line, c_delay, skips, skip_line, hist_in, hist_out, packed, b_dil, b_skip,
+                                 b_out, slots=None, rate=1, delay=0, precision="fp32"):
+    """:func:`wavenet_stream_delayed_forward` (``precision="bf16"``: :func:`wavenet_stream_delayed_forward_bf16`, on that
+    image) with a position per item: the window gives way to ``slots``, the launch's ``rate`` (columns per frame) and
+    output ``delay``.  A running item is the delayed launch with its own window, a fresh one reads ``hist_in``, ``c_line``
+    and ``skip_line[0]`` as zeros, a paused one copies its state through and stores zeros.  One launch."""
+    bf16 = precision == "bf16"
+    name = "wavenet_stream_slots_forward_bf16" if bf16 else "wavenet_stream_slots_forward"
+    line_in, line_out = skip_line if skips is not None else (None, None)
+    _require_device(x, c, c_line, skips, line_in, line_out, hist_in, hist_out, b_dil, b_skip, b_out)
+    if bf16:
+        _bf16_stream_image(name, packed)
+    else:
+        _require_device(packed)
+    _slot_table(name, slots, desc.batch)
+    assert x.numel() == desc.batch * desc.residual_channels * desc.t, (tuple(x.shape), desc.batch, desc.t)
+    assert c.numel() == desc.batch * desc.aux_channels * desc.t, (tuple(c.shape), desc.batch, desc.t)
+    n_hist = wavenet_stream_delayed_hist_floats(desc)
+    for t in (hist_in, hist_out):
+        assert t is None or n_hist == 0 or t.numel() == n_hist, (tuple(t.shape), n_hist)
+    for t in (line_in, line_out):
+        assert t is None or t.numel() == desc.batch * desc.skip_channels * desc.dilation, tuple(t.shape)
+    assert skips is None or skips.numel() == x.numel()
+    c_cols = 0
+    if c_line is not None:
+        assert c_line.is_contiguous() and c_line.numel() % (desc.batch * desc.aux_channels) == 0, tuple(c_line.shape)
+        c_cols = c_line.numel() // (desc.batch * desc.aux_channels)
+    x_out, skips_out = torch.empty_like(x), torch.empty_like(x)
+    entry = _lib.lib().pwg_wavenet_stream_slots_forward_bf16 if bf16 else _lib.lib().pwg_wavenet_stream_slots_forward
+    _lib.check(entry(
+        ctypes.byref(desc), _ptr(x), _ptr(c), _ptr(c_line), c_cols, int(c_delay), _ptr(skips), _ptr(line_in), _ptr(line_out),
+        _ptr(hist_in), _ptr(hist_out), _ptr(packed), _ptr(b_dil), _ptr(b_skip), _ptr(b_out), _ptr(slots), int(rate),
+        int(delay), _ptr(x_out), _ptr(skips_out), _stream()), name)
+    return x_out, skips_out
+
+
+def stretch_conv_stream_slots(x, hist_in, hist_out, w, scale, freq_kernel=1, act=None, slope=0.0, slots=None, rate=1,
+                              delay=0):
+    """:func:`stretch_conv_stream_delayed` with a position per item (item = the leading axis of ``x``): ``slots``, ``rate``
+    (output columns per frame) and output ``delay`` stand where ``valid`` stood.  One launch."""
+    x = x.contiguous()
+    w = w.reshape(-1).contiguous()
+    _require_device(x, hist_in, hist_out, w)
+    b, ch, n = x.shape
+    _slot_table("stretch_conv_stream_slots", slots, b)
+    assert w.numel() == (2 * scale + 1) * freq_kernel, (w.numel(), scale, freq_kernel)
+    for t in (hist_in, hist_out):
+        assert t is None or (t.is_contiguous() and t.numel() == b * ch * 2), tuple(t.shape)
+    y = torch.empty((b, ch, n * scale), device=x.device, dtype=torch.float32)
+    _lib.check(_lib.lib().pwg_stretch_conv_stream_slots(_ptr(x), _ptr(hist_in), _ptr(hist_out), _ptr(w), _ptr(y), b, ch, n,
+                                                        int(scale), int(freq_kernel), ACT[act], float(slope), _ptr(slots),
+                                                        int(rate), int(delay), _stream()), "stretch_conv_stream_slots")
+    return y
+
+
+def delay_line_slots_forward(x, line_in, line_out, slots, delayed=False):
+    """:func:`delay_line_forward` with a position per item (item = the leading axis of ``x``): a fresh item's line reads
+    as zeros, a paused item's line is copied through and its delayed columns are zeros.  One launch; copies only."""
+    x = x.contiguous()
+    _require_device(x, line_in, line_out)
+    b, ch, n = x.shape
+    _slot_table("delay_line_slots_forward", slots, b)
+    L = line_out.shape[-1]
+    for t in (line_in, line_out):
+        assert t is None or (t.is_contiguous() and tuple(t.shape) == (b, ch, L)), (tuple(t.shape), (b, ch, L))
+    out = torch.empty_like(x) if delayed else None
+    _lib.check(_lib.lib().pwg_delay_line_slots_forward(_ptr(x), _ptr(line_in), _ptr(line_out), _ptr(out), b, ch, n, L,
+                                                       _ptr(slots), _stream()), "delay_line_slots_forward")
+    return out
+
+
+def slot_seed_history(x, hist, slots):
+    """Writes column 0 of ``x`` (B, C, n) into every column of ``hist`` (B, C, H), in place, for the items whose row of
+    ``slots`` says fresh and not paused; the other items' history is left as it is.  What ``conv_in`` of a Parallel
+    WaveGAN pool starts an utterance from.  One launch."""
+    x = x.contiguous()
+    _require_device(x, hist)
+    b, ch, n = x.shape
+    _slot_table("slot_seed_history", slots, b)
+    assert hist is None or (hist.is_contiguous() and tuple(hist.shape[:2]) == (b, ch)), tuple(hist.shape)
+    cols = 1 if hist is None else hist.shape[-1]
+    _lib.check(_lib.lib().pwg_slot_seed_history(_ptr(x), _ptr(hist), b, ch, n, cols, _ptr(slots), _stream()),
+               "slot_seed_history")
+    return hist
+
+
 def wavenet_bf16_supported(desc):
     """Does the bf16-operand one-launch layer (csrc/wavenet_bf16.hip) cover this geometry?  Host logic only (no device
     needed); ``_lib.lib().pwg_last_error()`` names the reason for a False."""

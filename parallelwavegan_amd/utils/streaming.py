@@ -33,6 +33,10 @@ late (3258 samples, 12.73 frames, for HiFi-GAN V1).  ``PWGLooka
 standard NON-causal Parallel WaveGAN (3921 samples, 15.3 frames, for ``parallel_wavegan.v1``), and
 ``MelGANLookaheadStream`` for the standard NON-causal, reflect-padded MelGAN and multi-band MelGAN, whose reflect-padded
 layers mirror their window on read (1425 samples for ``melgan.v1``, 2720 for ``multi_band_melgan.v2``).
+
+``StreamPool`` and ``PWGStreamPool`` run many look-ahead streams of the non-causal HiFi-GAN / Parallel WaveGAN in one
+batch whose utterances start, pause and end independently: every launch reads each item's position from a small device
+table.
 """
 import collections
 import ctypes
@@ -1112,9 +1116,133 @@ class SlotSchedule:
         return steps
 
 
-class StreamPool(_Stream):
+class _SlotPool(_Stream):
+    """What the pools share (:class:`StreamPool`, :class:`PWGStreamPool`): the schedule, the per-slot host queues and
+    ``_take``, what a step uploads -- the table first, then the model's inputs, each a device tensor with two pinned
+    twins used in turn (a twin is written again only after its copy of two steps ago has finished) --, the graph entry
+    (ONE pair of graphs, from the first step on) and the step loop.  A subclass validates its model, calls ``__init__``
+    with its plan's figures and the shapes of its inputs, and supplies ``_fill(steps, table, *hosts)``, which writes a
+    step's pinned twins, and ``_run(*inputs, state_in, state_out)``, the model on the device inputs behind the table;
+    ``_before_run(steps)`` is what a step does on the device between the upload and the launches (nothing here)."""
+
+    def __init__(self, model, slots, chunk_frames, use_graph, normalize_before, precision, up, latency_samples,
+                 settle_frames, state_shapes, table_rows, input_shapes):
+        """``table_rows``: rows of the device table (``slots``, or twice that where a second table rides behind the
+        first); ``input_shapes``: of the device inputs behind the table, the features first."""
+        from ..ops import SLOT_INTS
+
+        self.precision = precision
+        self.slots, self.chunk_frames = slots, chunk_frames
+        self.up = up
+        self.latency_samples = latency_samples
+        self._schedule = SlotSchedule(slots, chunk_frames, up, latency_samples, settle_frames)
+        super().__init__(model, [], slots, use_graph, normalize_before, state_shapes)
+        self._table = torch.zeros((table_rows, SLOT_INTS), device=self._device, dtype=torch.int32)
+        self._inputs = [torch.zeros(shape, device=self._device) for shape in input_shapes]
+        self._feats = self._inputs[0]
+        self._staging = [(torch.zeros((table_rows, SLOT_INTS), dtype=torch.int32).pin_memory(),
+                          *(torch.zeros(shape).pin_memory() for shape in input_shapes), torch.cuda.Event())
+                         for _ in range(2)]
+
+    @classmethod
+    def _checked_sizes(cls, slots, chunk_frames):
+        slots, chunk_frames = int(slots), int(chunk_frames)
+        if slots < 1:
+            raise ValueError(f"{cls.__name__}: slots must be >= 1")
+        if chunk_frames < 1:
+            raise ValueError(f"{cls.__name__}: chunk_frames must be >= 1")
+        return slots, chunk_frames
+
+    @property
+    def open_slots(self):
+        """The ids that hold an utterance, ascending."""
+        return self._schedule.open_slots
+
+    @property
+    def graphs_captured(self):
+        """How many graphs the pool holds: 0, or 2 (both directions of its one chunk size)."""
+        return sum(len(graphs) for graphs in self._graphs.values())
+
+    def reset(self):
+        """Closes every slot, dropping what is queued; the state needs no clearing (a new utterance is fresh)."""
+        self._restart()
+        self._queues = [[] for _ in range(self.batch)]
+        self._step = 0
+        self._schedule.reset()
+
+    def open(self):
+        return self._schedule.open()
+
+    def end(self, slot):
+        self._schedule.end(slot)
+
+    def _checked_frames(self, frames):
+        """What ``feed`` takes -> (n, C) fp32 on the host."""
+        frames = torch.as_tensor(frames, dtype=torch.float32).cpu()
+        if frames.dim() != 2 or frames.shape[1] != self._feats.shape[2]:
+            raise ValueError(f"{type(self).__name__}.feed: expected (n, {self._feats.shape[2]}) features, got "
+                             f"{tuple(frames.shape)}")
+        return frames
+
+    @staticmethod
+    def _take_from(queue, n, out):
+        """Moves the next ``n`` queued rows of ``queue`` (a list of host tensors) into ``out[:n]`` and zeros the rest."""
+        at = 0
+        while at < n:
+            head = queue[0]
+            k = min(n - at, head.shape[0])
+            out[at:at + k] = head[:k]
+            at += k
+            if k == head.shape[0]:
+                queue.pop(0)
+            else:
+                queue[0] = head[k:]
+        if n < out.shape[0]:
+            out[n:] = 0.0
+
+    def _take(self, slot, n, out):
+        """Moves the next ``n`` queued frames of ``slot`` into ``out[:n]`` and zeros the rest of ``out``."""
+        self._take_from(self._queues[slot], n, out)
+
+    def _before_run(self, steps):
+        """On the device, after the upload and outside the graph."""
+
+    @torch.no_grad()
+    def step(self):
+        steps = self._schedule.advance()
+        if not steps:
+            return {}
+        *hosts, copied = self._staging[self._step % 2]
+        self._step += 1
+        copied.synchronize()
+        self._fill(steps, *hosts)
+        for device, host in zip([self._table] + self._inputs, hosts):
+            device.copy_(host, non_blocking=True)
+        copied.record()
+        self._before_run(steps)
+        state_in, state_out = self._halves[self._cur], self._halves[1 - self._cur]
+        if self.use_graph:
+            graphs = self._graph_entry("pool", lambda: _capture_directions(
+                self._halves, lambda hist_in, hist_out: self._run(*self._inputs, hist_in, hist_out)))
+            graph, static_out = graphs[self._cur]
+            graph.replay()
+            y = static_out.clone()
+        else:
+            y = self._run(*self._inputs, state_in, state_out)
+        self._cur = 1 - self._cur
+        out = {}
+        for st in steps:
+            if st.action in ("run", "tail", "drain"):
+                out[st.slot] = y[st.slot, st.emit[0]:st.emit[1]]
+                self.frames_out += self.chunk_frames
+                self.samples_out += st.emit[1] - st.emit[0]
+        return out
+
+
+class StreamPool(_SlotPool):
     """``slots`` look-ahead streams of the standard NON-causal ``HiFiGANGenerator`` in one batch, whose utterances start
-    and end whenever they like: what :class:`LookaheadStream` does for ``batch`` lock-step streams, for a server.
+    and end whenever they like: what :class:`LookaheadStream` does for ``batch`` lock-step streams, for a server
+    (:class:`PWGStreamPool` is the same for the non-causal ``ParallelWaveGANGenerator``).
 
     ``open()`` -> a free slot id (RuntimeError when every slot is taken); ``feed(slot, frames)`` queues ``(n, C)``
     features, any ``n >= 0``, on the host; ``end(slot)``: no more frames.  ``step()`` is ONE set of launches over all
@@ -1151,79 +1279,31 @@ class StreamPool(_Stream):
             raise ValueError(f"StreamPool: the generator emits {out_channels} channels; a slot returns one waveform "
                              "(out_channels == 1)")
         self._refuse_bf16_model(model, precision, "look-ahead stream")
-        slots, chunk_frames = int(slots), int(chunk_frames)
-        if slots < 1:
-            raise ValueError("StreamPool: slots must be >= 1")
-        if chunk_frames < 1:
-            raise ValueError("StreamPool: chunk_frames must be >= 1")
+        slots, chunk_frames = self._checked_sizes(slots, chunk_frames)
         plan = model.lookahead_plan()  # ValueError: decreasing block delays, a layer without a causal form
         delayed = conv1d_stream_bf16_delayed_supported if precision == "bf16" else conv1d_stream_delayed_supported
         for launch in plan:  # (the slotted form covers what the delayed form covers)
             self._require_supported(delayed(launch_desc(launch, slots, chunk_frames), launch.delay1, launch.delay2),
                                     launch.conv)
-        self.precision = precision
-        self.slots, self.chunk_frames = slots, chunk_frames
-        self.up = model.upsample_factor
-        self.latency_samples = plan[-1].delay
         self._plan = plan
-        self._schedule = SlotSchedule(slots, chunk_frames, self.up, self.latency_samples, lookahead_settle_frames(plan))
-        super().__init__(model, [], slots, use_graph, normalize_before, lookahead_state_shapes(plan, slots))
-        channels = plan[0].conv.in_channels
-        from ..ops import SLOT_INTS
-
-        # what a step uploads: the table and the features, staged in two pinned buffers used in turn (a buffer is written
-        # again only after its copy of two steps ago has finished)
-        self._table = torch.zeros((slots, SLOT_INTS), device=self._device, dtype=torch.int32)
-        self._feats = torch.zeros((slots, chunk_frames, channels), device=self._device)
-        self._staging = [(torch.zeros((slots, SLOT_INTS), dtype=torch.int32).pin_memory(),
-                          torch.zeros((slots, chunk_frames, channels)).pin_memory(), torch.cuda.Event()) for _ in range(2)]
+        # what a step uploads: the table and the features
+        super().__init__(model, slots, chunk_frames, use_graph, normalize_before, precision, model.upsample_factor,
+                         plan[-1].delay, lookahead_settle_frames(plan), lookahead_state_shapes(plan, slots), slots,
+                         [(slots, chunk_frames, plan[0].conv.in_channels)])
         self._columns = torch.arange(chunk_frames, device=self._device).reshape(1, 1, -1)
 
-    @property
-    def open_slots(self):
-        """The ids that hold an utterance, ascending."""
-        return self._schedule.open_slots
-
-    @property
-    def graphs_captured(self):
-        """How many graphs the pool holds: 0, or 2 (both directions of its one chunk size)."""
-        return sum(len(graphs) for graphs in self._graphs.values())
-
-    def reset(self):
-        """Closes every slot, dropping what is queued; the state needs no clearing (a new utterance is fresh)."""
-        self._restart()
-        self._queues = [[] for _ in range(self.batch)]
-        self._step = 0
-        self._schedule.reset()
-
-    def open(self):
-        return self._schedule.open()
-
     def feed(self, slot, frames):
-        frames = torch.as_tensor(frames, dtype=torch.float32).cpu()
-        if frames.dim() != 2 or frames.shape[1] != self._feats.shape[2]:
-            raise ValueError(f"StreamPool.feed: expected (n, {self._feats.shape[2]}) features, got {tuple(frames.shape)}")
+        frames = self._checked_frames(frames)
         self._schedule.feed(slot, frames.shape[0])
         self.frames_in += frames.shape[0]
         if frames.shape[0]:
             self._queues[slot].append(frames)
 
-    def end(self, slot):
-        self._schedule.end(slot)
-
-    def _take(self, slot, n, out):
-        """Moves the next ``n`` queued frames of ``slot`` into ``out[:n]`` and zeros the rest of ``out``."""
-        queue, at = self._queues[slot], 0
-        while at < n:
-            head = queue[0]
-            k = min(n - at, head.shape[0])
-            out[at:at + k] = head[:k]
-            at += k
-            if k == head.shape[0]:
-                queue.pop(0)
-            else:
-                queue[0] = head[k:]
-        out[n:] = 0.0
+    def _fill(self, steps, table, feats):
+        table.copy_(torch.tensor([st.row for st in steps], dtype=torch.int32))
+        for st in steps:
+            if st.action in ("run", "tail", "drain"):
+                self._take(st.slot, st.take, feats[st.slot])
 
     def _run(self, feats, state_in, state_out):
         """The generator on one step's inputs, every launch slotted -> (slots, chunk_frames * up)."""
@@ -1235,38 +1315,132 @@ class StreamPool(_Stream):
         walk = SlotWalk(self._plan, state_in, state_out, self._table, self.precision)
         return self.model.lookahead_forward(c, walk).reshape(self.batch, -1)
 
-    @torch.no_grad()
-    def step(self):
-        steps = self._schedule.advance()
-        if not steps:
-            return {}
-        table, feats, copied = self._staging[self._step % 2]
-        self._step += 1
-        copied.synchronize()
-        table.copy_(torch.tensor([st.row for st in steps], dtype=torch.int32))
+
+class PWGStreamPool(_SlotPool):
+    """``slots`` look-ahead streams of the standard NON-causal ``ParallelWaveGANGenerator`` in one batch, whose
+    utterances start and end whenever they like: what :class:`PWGLookaheadStream` does for ``batch`` lock-step streams,
+    for a server.  The interface is :class:`StreamPool`'s -- ``open()``, ``feed(slot, frames, noise=None)``,
+    ``end(slot)``, ``step()`` -> ``{slot: (samples,) fp32}``, ``reset()``, ``open_slots``, ``graphs_captured``,
+    ``latency_samples``, ``state_bytes`` -- and a slot's concatenated emissions are bit for bit what
+    ``PWGLookaheadStream(model, batch=1)`` emits for the same frames and noise, pushes and flush together.
+
+    ``noise``: ``(n * up,)`` for the samples of the ``n`` frames of that ``feed`` (finite values); where none is given
+    the pool draws it with ``torch.randn`` on the device, after the step's upload and never inside a graph.  Given and
+    drawn noise may mix within a slot.  An ended slot runs on what is left, padded with copies of its last real frame
+    (kept on the host; what ``flush()`` feeds) and zero noise, then on chunks of that frame until it has emitted
+    ``frames * up`` samples; the padding is inserted before normalisation, as ``flush()`` does.
+
+    How: every launch of a step is slotted -- the gated layers (csrc/wavenet_stream.hip,
+    csrc/wavenet_stream_bf16.hip), the upsampling stages and the two delay lines (csrc/elementwise.hip), ``conv_in`` and
+    the 1 x 1 convolutions (csrc/conv1d_stream.hip) -- and reads each item's position from the device table.  ``conv_in``
+    starts an utterance from its first frame replicated: a seeding kernel writes that into the history of the fresh
+    running items, and ``conv_in`` runs with ``delay + rate`` over a second table of rows ``(before + 1, left - 1,
+    flags)``, which gives the same windows and in which no item is fresh; both tables go up in the one table upload.  A
+    step uploads the tables, the features and the noise (three copies from pinned memory), so ``use_graph`` captures ONE
+    pair of graphs and replays it from the first step on.  ``precision`` (scope: :class:`PWGLookaheadStream`; the state
+    a bf16 pool writes is the fp32 pool's bit for bit), ``normalize_before`` and the refusals are
+    :class:`PWGLookaheadStream`'s, for ``slots x chunk_frames``; ``reset()`` closes every slot."""
+
+    def __init__(self, model, slots=16, chunk_frames=8, use_graph=True, normalize_before=False, precision=None):
+        from ..layers.causal_conv import pointwise_desc, pwg_lookahead_state_shapes
+        from ..models import HiFiGANGenerator, ParallelWaveGANGenerator
+
+        precision = self._checked_precision(precision)
+        if not isinstance(model, ParallelWaveGANGenerator):
+            hint = "; the non-causal HiFiGANGenerator pools through utils.StreamPool" \
+                if isinstance(model, HiFiGANGenerator) else ""
+            raise ValueError(f"PWGStreamPool: {model.__class__.__name__} is not supported (only the non-causal "
+                             f"ParallelWaveGANGenerator{hint})")
+        slots, chunk_frames = self._checked_sizes(slots, chunk_frames)
+        reason = model.lookahead_unsupported_reason(slots, precision)
+        if reason is not None:
+            raise ValueError(f"PWGStreamPool: {reason}")
+        if model.in_channels != 1 or model.out_channels != 1:
+            raise ValueError(f"PWGStreamPool: in_channels / out_channels = {model.in_channels} / {model.out_channels} "
+                             "(a slot takes one noise row and returns one waveform)")
+        self._refuse_bf16_model(model, precision, "look-ahead stream")
+        plan = model.lookahead_plan()
+        delayed = conv1d_stream_bf16_delayed_supported if precision == "bf16" else conv1d_stream_delayed_supported
+        for launch in plan:  # (the slotted forms cover what the delayed forms cover)
+            if launch.kind == "conv_in":
+                desc = model.upsample_net._lookahead_desc(slots, chunk_frames)
+            elif launch.kind in ("first_conv", "last_conv"):
+                desc = pointwise_desc(launch.module, slots, chunk_frames * launch.rate)
+            else:
+                continue
+            self._require_supported(delayed(desc), launch.module,
+                                    " with bf16 operands" if precision == "bf16" else "")
+        self._plan = plan
+        up, latency = model.upsample_factor, plan[-1].delay
+        # conv_in with a context window keeps a history: the second table rides behind the first
+        self._two_tables = plan[0].kind == "conv_in" and bool(plan[0].state)
+        channels = model.aux_channels
+        # what a step uploads: the table(s), the features and the noise
+        super().__init__(model, slots, chunk_frames, use_graph, normalize_before, precision, up, latency,
+                         -(-latency // up), pwg_lookahead_state_shapes(plan, slots),
+                         slots * (2 if self._two_tables else 1),
+                         [(slots, chunk_frames, channels), (slots, 1, chunk_frames * up)])
+        self._noise = self._inputs[1]
+
+    @classmethod
+    def state_bytes_of(cls, model, slots):
+        """``state_bytes`` of a pool of ``slots``, from the plan's shapes alone (no device): both ping-pong halves of
+        every launch's state, fp32 in either precision."""
+        from ..layers.causal_conv import pwg_lookahead_state_shapes
+
+        return 2 * 4 * sum(b * ch * cols for b, ch, cols in pwg_lookahead_state_shapes(model.lookahead_plan(), int(slots)))
+
+    def reset(self):
+        super().reset()
+        self._noise_queues = [[] for _ in range(self.batch)]
+        self._last = [None] * self.batch  # per slot its last real frame, (C,), on the host
+
+    def feed(self, slot, frames, noise=None):
+        frames = self._checked_frames(frames)
+        n = frames.shape[0]
+        if noise is None:  # (NaN on the host: drawn on the device once it is uploaded)
+            noise = torch.full((n * self.up,), float("nan"))
+        else:
+            noise = torch.as_tensor(noise, dtype=torch.float32).cpu().reshape(-1)
+            if noise.shape[0] != n * self.up:
+                raise ValueError(f"PWGStreamPool.feed: expected ({n * self.up},) noise for {n} frame(s), got "
+                                 f"{tuple(noise.shape)}")
+            if not torch.isfinite(noise).all():
+                raise ValueError("PWGStreamPool.feed: the noise must be finite")
+        self._schedule.feed(slot, n)
+        self.frames_in += n
+        if n:
+            self._queues[slot].append(frames)
+            self._noise_queues[slot].append(noise)
+
+    def _fill(self, steps, table, feats, noise):
+        from ..layers.causal_conv import slot_table_rows_in
+
+        rows = [st.row for st in steps]
+        table.copy_(torch.tensor(rows + (slot_table_rows_in(rows) if self._two_tables else []), dtype=torch.int32))
         for st in steps:
             if st.action in ("run", "tail", "drain"):
                 self._take(st.slot, st.take, feats[st.slot])
-        self._table.copy_(table, non_blocking=True)
-        self._feats.copy_(feats, non_blocking=True)
-        copied.record()
-        state_in, state_out = self._halves[self._cur], self._halves[1 - self._cur]
-        if self.use_graph:
-            graphs = self._graph_entry("pool", lambda: _capture_directions(
-                self._halves, lambda hist_in, hist_out: self._run(self._feats, hist_in, hist_out)))
-            graph, static_out = graphs[self._cur]
-            graph.replay()
-            y = static_out.clone()
-        else:
-            y = self._run(self._feats, state_in, state_out)
-        self._cur = 1 - self._cur
-        out = {}
-        for st in steps:
-            if st.action in ("run", "tail", "drain"):
-                out[st.slot] = y[st.slot, st.emit[0]:st.emit[1]]
-                self.frames_out += self.chunk_frames
-                self.samples_out += st.emit[1] - st.emit[0]
-        return out
+                self._take_from(self._noise_queues[st.slot], st.take * self.up, noise[st.slot, 0])
+                if st.take:
+                    self._last[st.slot] = feats[st.slot, st.take - 1].clone()
+                if st.take < self.chunk_frames:
+                    feats[st.slot, st.take:] = self._last[st.slot]  # what flush() feeds: the last real frame
+
+    def _before_run(self, steps):
+        """Draws the noise nobody gave (NaN in the upload), on the device and outside the graph.  (One look at the whole
+        staged buffer: a row a paused slot left there may ask for a draw nobody reads, never the other way round.)"""
+        *_, noise, _ = self._staging[(self._step - 1) % 2]
+        if bool(torch.isnan(noise).any()):
+            self._noise.copy_(torch.where(torch.isnan(self._noise), torch.randn_like(self._noise), self._noise))
+
+    def _run(self, feats, z, state_in, state_out):
+        """The generator on one step's inputs, every launch slotted -> (slots, chunk_frames * up)."""
+        from ..layers.causal_conv import PWGSlotWalk
+
+        first, second = (self._table[:self.slots], self._table[self.slots:]) if self._two_tables else (self._table, None)
+        walk = PWGSlotWalk(self._plan, state_in, state_out, first, second, self.precision)
+        return self.model.lookahead_forward(z, self._features(feats), walk).reshape(self.batch, -1)
 
 
 RaggedGroup = collections.namedtuple("RaggedGroup", "indices frames t_pad")

@@ -59,6 +59,8 @@ whole-utterance forward (and, multi-band, ``pqmf.synthesis`` of its output) over
 generator's reach (the PQMF filter's own 31 samples are not added: the comparison leans towards the halo path).  Into
 profiles/stream_melgan_lookahead_infer.json; ``--multiband`` adds the multi-band model to the same file.
 
+``--pool --model pwg [--precision bf16]``: the same two measurements for ``utils.PWGStreamPool`` on the non-causal
+``parallel_wavegan.v1`` against ``utils.PWGLookaheadStream`` (profiles/stream_pwg_pool[_bf16]_infer.json).
 ``--pool [--precision bf16]``: ``utils.StreamPool`` on the non-causal HiFi-GAN V1 (the slotted form of the stream kernels;
 DESIGN.md s11.10).  (a) a step of 16 running slots -- every slot fed its 4 / 8 / 32 frames from the host, then ``step()``
 -- against ``LookaheadStream(batch=16).push`` of the same frames, already on the device, alternating; with the two uploads,
@@ -83,7 +85,8 @@ from parallelwavegan_amd.graphs import GraphedInference  # noqa: E402
 from parallelwavegan_amd.layers import PQMF  # noqa: E402
 from parallelwavegan_amd.models import HiFiGANGenerator, MelGANGenerator, ParallelWaveGANGenerator  # noqa: E402
 from parallelwavegan_amd.utils import (CausalStream, LookaheadStream, MelGANLookaheadStream,  # noqa: E402
-                                       PWGLookaheadStream, PWGStream, StreamPool, set_inference_precision)
+                                       PWGLookaheadStream, PWGStream, PWGStreamPool, StreamPool,
+                                       set_inference_precision)
 from parallelwavegan_amd.utils.streaming import receptive_field_frames  # noqa: E402
 from tests.golden import synth  # noqa: E402
 
@@ -200,14 +203,17 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.pool:
-        if args.model != "default" or args.multiband or args.lookahead:
-            ap.error("--pool is the stream pool of the non-causal HiFi-GAN (only --precision goes with it)")
-        args.out = args.out or os.path.join(ROOT, "profiles", "stream_pool_bf16_infer.json" if args.precision == "bf16"
-                                            else "stream_pool_infer.json")
-        rec = {"tool": "tools/bench_stream.py --pool", "device": torch.cuda.get_device_name(0), "reps": args.reps,
-               "repeats": args.repeats, "models": {}, "points": []}
-        measure_pool(rec, "hifigan_v1", build_noncausal(torch.device("cuda:0")), CHUNKS,
-                     torch.Generator(device="cpu").manual_seed(100), args, torch.device("cuda:0"))
+        if args.model == "melgan" or args.multiband or args.lookahead:
+            ap.error("--pool is the stream pool of the non-causal HiFi-GAN or (--model pwg) Parallel WaveGAN (only --precision "
+                     "goes with it)")
+        pwg = args.model == "pwg"
+        stem = "stream_pwg_pool" if pwg else "stream_pool"
+        args.out = args.out or os.path.join(ROOT, "profiles", stem + ("_bf16" if args.precision == "bf16" else "") + "_infer.json")
+        rec = {"tool": "tools/bench_stream.py --pool" + (" --model pwg" if pwg else ""),
+               "device": torch.cuda.get_device_name(0), "reps": args.reps, "repeats": args.repeats, "models": {}, "points": []}
+        dev = torch.device("cuda:0")
+        measure_pool(rec, "parallel_wavegan_v1" if pwg else "hifigan_v1", build_pwg(dev, causal=False) if pwg else
+                     build_noncausal(dev), CHUNKS, torch.Generator(device="cpu").manual_seed(100), args, dev, pwg)
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
             json.dump(rec, f, indent=1)
@@ -644,8 +650,9 @@ def measure_pwg_precision(rec, name, model, model16, lookahead, chunks, gen, arg
                                                 "layer_launch_ms")}), file=sys.stderr, flush=True)
 
 
-def measure_pool(rec, name, model, chunks, gen, args, dev):
-    """``StreamPool`` in ``args.precision``.  (a) the cost of the table: a step with all 16 slots
+def measure_pool(rec, name, model, chunks, gen, args, dev, pwg=False):
+    """``StreamPool``, or with ``pwg`` ``PWGStreamPool`` against ``PWGLookaheadStream`` (s11.11; both
+    sides get the same given noise, the pool's from the host), in ``args.precision``.  (a) the cost of the table: a step with all 16 slots
     running in steady state (every slot fed its ``n`` frames from the host, then ``step()``) against
     ``LookaheadStream(batch=16).push`` of ``n`` device-resident frames, alternating; and where a step's time goes (the two
     uploads, the replay, the output copy, each timed alone).  (b) what a server gains: 16 staggered utterances through
@@ -655,32 +662,35 @@ def measure_pool(rec, name, model, chunks, gen, args, dev):
 
     up, slots = model.upsample_factor, 16
     med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
-    probe = StreamPool(model, slots=slots, chunk_frames=8, use_graph=False, precision=args.precision)
+    pool_cls, lock_cls = (PWGStreamPool, PWGLookaheadStream) if pwg else (StreamPool, LookaheadStream)
+    probe = pool_cls(model, slots=slots, chunk_frames=8, use_graph=False, precision=args.precision)
     rec["models"][name] = {"workload": "seeded weights, weight norm removed", "precision": args.precision, "slots": slots,
                            "latency_samples": probe.latency_samples, "pool_state_bytes": probe.state_bytes}
     for n in chunks:
         host = torch.randn(slots, n, 80, generator=gen)
         feats = host.to(dev)
-        pool = StreamPool(model, slots=slots, chunk_frames=n, use_graph=True, precision=args.precision)
-        lock = LookaheadStream(model, batch=slots, use_graph=True, precision=args.precision)
+        host_z = [torch.randn(slots, n * up, generator=gen)] if pwg else []  # (the noise of a Parallel WaveGAN push)
+        z = [t.to(dev) for t in host_z]
+        pool = pool_cls(model, slots=slots, chunk_frames=n, use_graph=True, precision=args.precision)
+        lock = lock_cls(model, batch=slots, use_graph=True, precision=args.precision)
         ids = [pool.open() for _ in range(slots)]
 
         def pool_step():
             for s in ids:
-                pool.feed(s, host[s])
+                pool.feed(s, host[s], *(t[s] for t in host_z))
             pool.step()
 
         while lock.frames_in < lock.settle_frames + 4 * n:  # past every edge; both graph directions of both
-            lock.push(feats)
+            lock.push(feats, *z)
             pool_step()
         t_p, t_l = [], []
         for _ in range(args.repeats):
             t_p.append(event_ms(pool_step, args.reps))
-            t_l.append(event_ms(lambda: lock.push(feats), args.reps))
+            t_l.append(event_ms(lambda: lock.push(feats, *z), args.reps))
         graph, static_out = pool._graphs["pool"][0]
-        table, staged, _ = pool._staging[0]
-        parts = {"upload_ms": event_ms(lambda: (pool._table.copy_(table, non_blocking=True),
-                                                pool._feats.copy_(staged, non_blocking=True)), args.reps),
+        *staged, _ = pool._staging[0]
+        uploads = list(zip([pool._table] + pool._inputs, staged))  # the table(s), the features, the noise
+        parts = {"upload_ms": event_ms(lambda: [d.copy_(h, non_blocking=True) for d, h in uploads], args.reps),
                  "replay_ms": event_ms(graph.replay, args.reps),
                  "output_copy_ms": event_ms(static_out.clone, args.reps),
                  "lockstep_input_copy_ms": event_ms(lambda: feats.clone(), args.reps)}
@@ -700,9 +710,14 @@ def measure_pool(rec, name, model, chunks, gen, args, dev):
     # (b) 16 utterances of 200 .. 395 frames, one arriving every second step, 8 frames per utterance and step
     n = 8
     utts = [torch.randn(200 + 13 * i, 80, generator=gen) for i in range(slots)]
+    noises = [torch.randn(u.shape[0] * up, generator=gen) for u in utts] if pwg else None
     frames = sum(u.shape[0] for u in utts)
-    pool = StreamPool(model, slots=slots, chunk_frames=n, use_graph=True, precision=args.precision)
-    singles = [LookaheadStream(model, batch=1, use_graph=True, precision=args.precision) for _ in range(slots)]
+    pool = pool_cls(model, slots=slots, chunk_frames=n, use_graph=True, precision=args.precision)
+    singles = [lock_cls(model, batch=1, use_graph=True, precision=args.precision) for _ in range(slots)]
+
+    def inputs(i, lo):
+        """The next ``n`` frames of utterance ``i`` from frame ``lo`` (and their noise), on the host."""
+        return (utts[i][lo:lo + n],) + ((noises[i][lo * up:(lo + n) * up],) if pwg else ())
 
     def serve(open_, feed, end, step):
         """Wall-clock seconds to serve every utterance; ``step()`` -> are utterances still in flight."""
@@ -712,7 +727,7 @@ def measure_pool(rec, name, model, chunks, gen, args, dev):
             if tick % 2 == 0 and tick // 2 < slots:
                 at[tick // 2] = [open_(tick // 2), 0]
             for i, st in list(at.items()):
-                feed(st[0], utts[i][st[1]:st[1] + n])
+                feed(st[0], *inputs(i, st[1]))
                 st[1] += n
                 if st[1] >= utts[i].shape[0]:
                     end(st[0])
@@ -737,8 +752,8 @@ def measure_pool(rec, name, model, chunks, gen, args, dev):
         singles[i].reset()
         return i
 
-    def single_feed(i, f):
-        samples["singles"] += singles[i].push(f).shape[1]
+    def single_feed(i, *f):
+        samples["singles"] += singles[i].push(*f).shape[1]
 
     def single_end(i):
         samples["singles"] += singles[i].flush().shape[1]

@@ -12,7 +12,9 @@ sequence: a zero-frame push; pushes shorter than the latency (an empty, then a s
 ``flush()``; ``reset()`` and an utterance shorter than ``latency_frames``, flushed; for ``PWGStream`` ``reset(context)``
 and two more pushes.  Per utterance one line: the hash of the emitted bytes (every push's, then the flush's), of the
 tensors of ``_halves[_cur]`` and the three counters.  Noise is given explicitly; the omitted-noise path draws from the
-device generator, so a second pass records its shapes and counters only."""
+device generator, so a second pass records its shapes and counters only.
+The pools (``utils.StreamPool`` on the small non-causal HiFi-GAN, ``utils.PWGStreamPool`` on the non-causal Parallel
+WaveGAN; ``run_pool_case``) add their lines where the checkout has the class."""
 import hashlib
 import json
 import os
@@ -119,13 +121,64 @@ def run_case(out, name, cls, model, noise, graph, precision, explicit):
         out[f"{tag}/context"] = rec.line(explicit)
 
 
+POOL_LENGTHS = (2, 9, 14, 5)  # shorter than the latency, not a multiple of the chunk, more utterances than slots
+
+
+def run_pool_case(out, name, cls, model, noise, graph, precision):
+    """A pool (``utils.StreamPool`` / ``utils.PWGStreamPool``; a checkout that lacks the class has no such lines) of 3
+    slots and chunks of 4 frames over four utterances with staggered ``open()`` and irregular ``feed()`` sizes, noise
+    given: per utterance the hash of its concatenated emissions, and at the end the state's and the counters."""
+    pool = cls(model, slots=3, chunk_frames=4, use_graph=graph, precision=precision)
+    gen = torch.Generator().manual_seed(sum(map(ord, name)) * 131 + 11)
+    utts = [(torch.randn(t, 80, generator=gen), torch.randn(t * pool.up, generator=gen)) for t in POOL_LENGTHS]
+    pending, active, outs = list(range(len(utts))), {}, {i: [] for i in range(len(utts))}
+    sizes = [1, 3, 0, 6, 2]
+    for tick in range(400):
+        if not pending and not active:
+            break
+        if pending and tick % 2 == 0 and len(pool.open_slots) < pool.slots:
+            active[pool.open()] = [pending.pop(0), 0, False]
+        for k, (slot, st) in enumerate(active.items()):
+            if st[2]:
+                continue
+            f, z = utts[st[0]]
+            n = min(sizes[(tick + k) % len(sizes)], f.shape[0] - st[1])
+            args = (f[st[1]:st[1] + n], z[st[1] * pool.up:(st[1] + n) * pool.up]) if noise else (f[st[1]:st[1] + n],)
+            pool.feed(slot, *args)
+            st[1] += n
+            if st[1] == f.shape[0]:
+                pool.end(slot)
+                st[2] = True
+        for slot, y in pool.step().items():
+            outs[active[slot][0]].append(y)
+        for slot in [s for s in active if s not in pool.open_slots]:
+            del active[slot]
+    assert not pending and not active
+    torch.cuda.synchronize()
+    tag = f"{name}/{'graph' if graph else 'eager'}/{precision}"
+    for i, ys in outs.items():
+        y = torch.cat(ys).detach().cpu().contiguous()
+        out[f"{tag}/utterance{i + 1}"] = {"shape": list(y.shape), "emitted": hashlib.sha256(y.numpy().tobytes()).hexdigest()}
+    state = hashlib.sha256()
+    for t in pool._halves[pool._cur]:
+        state.update(t.detach().cpu().contiguous().numpy().tobytes())
+    out[f"{tag}/end"] = {"counters": [pool.frames_in, pool.frames_out, pool.samples_out], "state": state.hexdigest()}
+
+
 if __name__ == "__main__":
     from parallelwavegan_amd import utils
 
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     lines = {}
-    for name, (cls, model, noise) in models_under_test(dev).items():
+    under_test = models_under_test(dev)
+    for name, pool_name, noise in (("lookahead/hifigan", "StreamPool", False), ("lookahead/pwg", "PWGStreamPool", True)):
+        if hasattr(utils, pool_name):
+            for precision in ("fp32", "bf16"):
+                for graph in (False, True):
+                    run_pool_case(lines, "pool/" + name.split("/")[1], getattr(utils, pool_name), under_test[name][1], noise,
+                                  graph, precision)
+    for name, (cls, model, noise) in under_test.items():
         for precision in ("fp32",) if cls is utils.MelGANLookaheadStream else ("fp32", "bf16"):
             for graph in (False, True):
                 run_case(lines, name, cls, model, noise, graph, precision, True)
