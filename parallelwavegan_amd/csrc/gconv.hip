@@ -467,6 +467,7 @@ int gconv_forward(const pwg_conv1d_desc* d, const float* x, const float* wp, con
   const double out_elems = (double)d->batch * d->c_out * d->t_out;
   const double flops = 2.0 * out_elems * cig * d->kernel;
   const double bytes = 4.0 * ((double)d->batch * d->c_in * d->t_in + out_elems + (double)d->c_out * cig * d->kernel);
+  maybe_poison_lds(stream);
   ProfScope prof(stream, prof_shape_name("gconv_fwd_kernel", "B%d Cin%d Cout%d Tin%d Tout%d k%d s%d g%d", d->batch, d->c_in,
                                          d->c_out, d->t_in, d->t_out, d->kernel, d->stride, d->groups), flops, bytes);
   dim3 grid(ceil_div(a.total_waves, 4)), block(256);
@@ -526,6 +527,7 @@ int gconv_backward_data(const pwg_conv1d_desc* d, const float* dy, const float* 
   const double flops = 2.0 * (double)d->batch * d->c_out * d->t_out * cig * d->kernel;
   const double bytes = 4.0 * ((double)d->batch * d->c_in * d->t_in * (1 + (accum != nullptr) + (a.mask != nullptr)) +
                               (double)d->batch * d->c_out * d->t_out);
+  maybe_poison_lds(stream);
   ProfScope prof(stream, prof_shape_name("gconv_dgrad_kernel", "B%d Cin%d Cout%d Tin%d Tout%d k%d s%d g%d", d->batch, d->c_in,
                                          d->c_out, d->t_in, d->t_out, d->kernel, d->stride, d->groups), flops, bytes);
   dim3 grid(ceil_div(a.total_waves, 4)), block(256);
@@ -625,6 +627,7 @@ int gconv_backward_weight(const pwg_conv1d_desc* d, const float* x, const float*
   a.slabs = workspace;
   const double flops = 2.0 * (double)d->batch * d->c_out * d->t_out * cig * d->kernel;
   const double bytes = 4.0 * ((double)d->batch * d->c_in * d->t_in + (double)d->batch * d->c_out * d->t_out + (double)d->c_out * ncol);
+  maybe_poison_lds(stream);
   dim3 grid(ceil_div(a.total_waves, 4)), block(256);
   {
     ProfScope prof(stream, prof_shape_name("gconv_wgrad_kernel", "B%d Cin%d Cout%d Tin%d Tout%d k%d s%d g%d slices%d", d->batch,

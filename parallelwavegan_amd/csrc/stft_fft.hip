@@ -407,6 +407,7 @@ static int launch_fft(const StftFftArgs& a, int n_fft, hipStream_t stream) {
     case 10: kern = stft_fft_kernel<10, BWD>; break;
     default: kern = stft_fft_kernel<11, BWD>; break;
   }
+  maybe_poison_lds(stream);
   const double units = (double)a.batch * a.frames;
   const double nlog = 5.0 * n_fft * log2_exact(n_fft);
   ProfScope prof(stream, BWD ? "stft_fft_bwd_kernel" : "stft_fft_fwd_kernel", units * nlog * (BWD ? 2.0 : 1.0),
@@ -488,6 +489,7 @@ static int launch_mel_fft(const MelFftArgs& m, int n_fft, hipStream_t stream) {
     case 10: kern = mel_fft_kernel<10, BWD>; break;
     default: kern = mel_fft_kernel<11, BWD>; break;
   }
+  maybe_poison_lds(stream);
   const double units = (double)a.batch * a.frames;
   ProfScope prof(stream, BWD ? "mel_fft_bwd_kernel" : "mel_fft_fwd_kernel",
                  units * 5.0 * n_fft * log2_exact(n_fft) * (BWD ? 2.0 : 1.0),
