@@ -466,6 +466,30 @@ int pwg_conv1d_stream_mirrored_forward(const pwg_conv1d_desc* d, const float* x,
                                        const float* w_packed, const float* bias, float* y, int32_t in_lo, int32_t in_hi,
                                        int32_t valid_lo, int32_t valid_hi, void* stream);
 
+/* ---- the mirrored launch with a position per item: the slotted-mirrored form (fp32; csrc/conv1d_stream.hip) ----
+ * For a pool of look-ahead streams of the non-causal (multi-band) MelGAN whose utterances start and end independently
+ * (utils.MelGANStreamPool).  Replaces, chunk by chunk and item by item, the same ReflectionPad1d +
+ * Conv1d pairs of the reference generator as the mirrored entry (models/melgan.py:70-73 the first k = 7 convolution,
+ * :135-140 the last one; layers/residual_stack.py:49-52 the dilated k = 3 convolution of a stack).
+ * d, x, hist_out, w_packed, bias, y: as for pwg_conv1d_stream_mirrored_forward; there are no addends.  hist_in must be
+ *   given where the layer has history: the start of a stream is an item's, not the launch's.
+ * slots, rate, delay: the DEVICE table, the output columns per frame and the OUTPUT's delay of
+ *   pwg_conv1d_stream_slots_forward (delay >= p = (k-1)*d/2: the input is delay - p columns late).
+ * Per item b, from its row: in_lo = (delay - p) - before * rate, and in_hi = (delay - p) + left * rate if the length is
+ *   known, else unbounded; both are formed in 64 bits and saturated to [-(k-1)*d, t_in + 64] on the device, by the
+ *   statement the mirrored entry applies on the host.  A running item's y and hist_out are bit for bit what the mirrored
+ *   entry writes for a batch-1 launch of this item with [in_lo, in_hi) and [valid_lo, valid_hi) = [in_lo + p, in_hi + p)
+ *   (hist_in NULL if the item is FRESH).  A PAUSED item's hist_out is its hist_in copied through (zeros if it is fresh),
+ *   its y columns are stored as 0.0f and its x columns are not read.
+ * While an utterance's length is unknown its chunk's columns stop p short of its end, so no output that needs the
+ * right-hand mirror is computed before the table knows the length.
+ * Coverage is that of pwg_conv1d_stream_mirrored_supported (there is no query of its own); pwg_last_error names the
+ * reason for a refusal: a NULL hist_in or slots, pad_mode != PWG_PAD_REFLECT, hist_in == hist_out, delay < p.
+ * Purely additive -- no existing signature or behaviour changes -- so pwg_abi_version() stays 15. */
+int pwg_conv1d_stream_slots_mirrored_forward(const pwg_conv1d_desc* d, const float* x, const float* hist_in,
+                                             float* hist_out, const float* w_packed, const float* bias,
+                                             const int32_t* slots, int32_t rate, int32_t delay, float* y, void* stream);
+
 /* Diagnostics (host only, no launch, no device needed): the tile and grid a conv stream launch takes for `d` -- the
  * plain, delayed, slotted and mirrored entries, fp32 and bf16 alike: they share one tile rule, evaluated here by the
  * call the launches make.  out[5]:
@@ -1028,6 +1052,20 @@ int pwg_pqmf_up_stream_geometry(int32_t subbands, int32_t len, int32_t pad, int3
                                 int32_t* delay_columns);
 int pwg_pqmf_up_stream(const float* y, const float* hist_in, float* hist_out, const float* g, float* x, int32_t batch,
                        int64_t n, int64_t n_emit, int32_t subbands, int32_t len, int32_t pad, void* stream);
+
+/* pwg_pqmf_up_stream with a position per item, for a pool of multi-band MelGAN streams (utils.MelGANStreamPool,
+ * DESIGN.md s11.12; the same synthesis of layers/pqmf.py:133-149).  `slots` is the DEVICE table of
+ * pwg_conv1d_stream_slots_forward, one row per item; only "fresh" (slots[4b] == 0) and "paused" are read.  The launch
+ * always emits n_emit = n positions, the chunk positions [-D, n - D) -- every column they read lies in [-H, n) -- into
+ * x (batch, K * n).  A running item is pwg_pqmf_up_stream with n_emit = n on the item alone, bit for bit, with hist_in
+ * NULL if the item is FRESH (whatever its buffer holds).  A PAUSED item's hist_out is its hist_in copied through (zeros
+ * if it is fresh), its x columns are stored as 0.0f and its y columns are not read.  The generator stores exact zeros
+ * around each utterance, which is the padding `up` applies, so the synthesis needs no window; the first D positions of a
+ * fresh item lie before its stream and are the caller's to drop.  hist_in is required (where H > 0), hist_in and
+ * hist_out must be distinct, slots must be given.  Additive: pwg_abi_version() stays 15. */
+int pwg_pqmf_up_stream_slots(const float* y, const float* hist_in, float* hist_out, const float* g, float* x,
+                             const int32_t* slots, int32_t batch, int64_t n, int32_t subbands, int32_t len, int32_t pad,
+                             void* stream);
 
 /* ---- StyleMelGAN pieces (layers/tade_res_block.py, models/style_melgan.py) ---- */
 /* torch.nn.InstanceNorm1d(affine=False) over `rows` = B*C rows of t samples (tade_res_block.py:27,66):

@@ -179,6 +179,8 @@ SIGNATURES = {
     "pwg_conv1d_stream_mirrored_supported": (ctypes.c_int, [ctypes.POINTER(ConvDesc)]),
     "pwg_conv1d_stream_mirrored_forward": (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _i32,
                                                           _i32, _i32, _i32, _vp]),
+    "pwg_conv1d_stream_slots_mirrored_forward": (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _i32,
+                                                                _i32, _vp, _vp]),
     "pwg_conv1d_packed_weight_bwd_floats": (ctypes.c_size_t, [ctypes.POINTER(ConvDesc)]),
     "pwg_conv1d_pack_weight_bwd": (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, _vp]),
     "pwg_weight_bank_table_bytes": (ctypes.c_size_t, [_i32]),
@@ -303,6 +305,7 @@ SIGNATURES = {
     "pwg_pqmf_up": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _vp]),
     "pwg_pqmf_up_stream_geometry": (ctypes.c_int, [_i32, _i32, _i32, ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
     "pwg_pqmf_up_stream": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _vp]),
+    "pwg_pqmf_up_stream_slots": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _vp]),
     "pwg_avg_pool1d_forward": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "pwg_avg_pool1d_backward": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "pwg_pad1d_forward": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),

@@ -46,6 +46,13 @@
 // the buffers hold; a paused item copies its state through, stores zeros for y and returns in front of every barrier.
 // A running item's columns are the delayed form's with the same window, bit for bit: one launch serves items at
 // different points of different utterances, and one captured graph covers start, steady state and tail.
+//
+// Slotted-mirrored form (pwg_conv1d_stream_slots_mirrored_forward): the mirrored form with one
+// position per item, for a pool of reflect-padded (MelGAN) streams.  The item's row gives the two edges of its INPUT
+// window (StreamSlots::mirrored_at: formed in 64 bits, saturated by mirror_bound as the host does for the mirrored
+// entry); a running item then builds the StreamMirrorWindow and StreamDelay a batch-1 mirrored launch gets, and from
+// there on the code is shared; fresh and paused items are the slotted form's.  The right-hand mirror is never needed
+// before the table knows the length: while it is unknown a chunk's columns stop pad short of the utterance's end.
 #include "stream_common.h"
 
 namespace pwg {
@@ -162,7 +169,8 @@ struct StreamMirroredArgs : StreamDelayedArgs {
 
 // SLOTTED (with DELAYED): the item's position comes from the launch's table (StreamSlots); a running item is from there
 // on the delayed form with its own window, a fresh one reads no state, a paused one copies its state through, stores
-// zeros and returns.
+// zeros and returns.  With MIRRORED the row also gives the input's edges, which stand where a.in_lo / a.in_hi do; the
+// arguments are the slotted ones (a reflect-padded layer has no addends: both delay lines are zero).
 struct StreamSlotsArgs : StreamArgs {
   StreamSlots sl;
 };
@@ -175,7 +183,7 @@ using stream_args_t = std::conditional_t<
 template <int TM, int TN, bool TRANSPOSED, bool DELAYED = false, bool MIRRORED = false, bool SLOTTED = false>
 __global__ __launch_bounds__(256) void conv1d_stream_kernel(stream_args_t<DELAYED, MIRRORED, SLOTTED> a) {
   static_assert(!MIRRORED || (DELAYED && !TRANSPOSED), "the mirrored form is a delayed stride-1 convolution");
-  static_assert(!SLOTTED || (DELAYED && !MIRRORED), "the slotted form is a delayed launch with a position per item");
+  static_assert(!SLOTTED || DELAYED, "the slotted form is a delayed launch with a position per item");
   constexpr int MT = 16 * TM, NT = 16 * TN;
   extern __shared__ __attribute__((aligned(16))) float xs[];  // [SC][a.xs]; afterwards the partial tiles [4][MT][NT]
 
@@ -193,7 +201,10 @@ __global__ __launch_bounds__(256) void conv1d_stream_kernel(stream_args_t<DELAYE
   [[maybe_unused]] std::conditional_t<SLOTTED, StreamSlots::Item, StreamNoDelay> item;
   bool fresh = false;
   if constexpr (SLOTTED) {
-    item = a.sl.at(b, a.ep.t_out);
+    if constexpr (MIRRORED)
+      item = a.sl.mirrored_at(b, H, n);
+    else
+      item = a.sl.at(b, a.ep.t_out);
     fresh = item.fresh;
   }
   const float* __restrict__ hb = a.hist_in && !fresh ? a.hist_in + (size_t)b * a.c_in * H : nullptr;
@@ -267,7 +278,9 @@ __global__ __launch_bounds__(256) void conv1d_stream_kernel(stream_args_t<DELAYE
   // zero padding or past the chunk) and always loaded, so that the loads of a staging batch are issued back to back
   const StreamWindow raw_win = {xb, hb, n, H, a.pad_mode};
   const auto win = [&] {
-    if constexpr (MIRRORED)
+    if constexpr (MIRRORED && SLOTTED)
+      return StreamMirrorWindow{raw_win, item.in_lo, item.in_hi};  // (the item's own edges, saturated on the device)
+    else if constexpr (MIRRORED)
       return StreamMirrorWindow{raw_win, a.in_lo, a.in_hi};  // (the launch passes pad_mode zero: history reads raw)
     else
       return raw_win;
@@ -354,6 +367,11 @@ struct SlotsKernel {
 template <int TM, int TN, bool TRANSPOSED>
 struct MirroredKernel {
   static constexpr auto fn = conv1d_stream_kernel<TM, TN, false, true, true>;
+};
+
+template <int TM, int TN, bool TRANSPOSED>
+struct SlotsMirroredKernel {
+  static constexpr auto fn = conv1d_stream_kernel<TM, TN, false, true, true, true>;
 };
 
 }  // namespace
@@ -494,4 +512,34 @@ extern "C" int pwg_conv1d_stream_mirrored_forward(const pwg_conv1d_desc* d, cons
   return stream_run<MirroredKernel>("conv1d_stream_mirrored", "conv1d_stream_mirrored_kernel", &raw, g, tile, &a, x, hist_in,
                                     hist_out, w_packed, bias, nullptr, nullptr, y, window, 0.0, image_bytes(g),
                                     (hipStream_t)stream_);
+}
+
+// The slotted-mirrored launch: what pwg_conv1d_stream_slots_mirrored_forward (csrc/conv1d_stream_slots_mirrored.hip) is.
+// The kernel family lives here; the entry point has its own translation unit and its own tests
+// (tests/test_stream_melgan_pool_gpu.py).
+int pwg::stream_slots_mirrored_forward(const pwg_conv1d_desc* d, const float* x, const float* hist_in, float* hist_out,
+                                       const float* w_packed, const float* bias, const int32_t* slots, int32_t rate,
+                                       int32_t delay, float* y, void* stream_) {
+  StreamGeom g;
+  int rc = mirrored_geometry(d, &g);
+  if (rc != PWG_OK) return rc;
+  PWG_REQUIRE((reinterpret_cast<uintptr_t>(w_packed) & 3u) == 0, PWG_ERR_BAD_SHAPE,
+              "conv1d_stream_slots_mirrored: unaligned weight image");
+  PWG_REQUIRE(hist_in || g.hist == 0, PWG_ERR_NULL,
+              "conv1d_stream_slots_mirrored: hist_in is NULL (the start of a stream is an item's, in the table)");
+  StreamSlotsArgs a;
+  rc = stream_slot_lines("conv1d_stream_slots_mirrored", nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, slots,
+                         rate, delay, &a.sl);
+  if (rc != PWG_OK) return rc;
+  PWG_REQUIRE(delay >= g.hist / 2, PWG_ERR_BAD_SHAPE,
+              "conv1d_stream_slots_mirrored: delay = %d is less than the layer's padding %d (the input would be early)",
+              delay, g.hist / 2);
+  const StreamTile tile = stream_tile(d->t_in, g.m, d->batch);
+  const size_t window = fill_image_args(&a, w_packed, g, tile);
+  // as in the mirrored entry: the launch itself is a zero-padded one, the reflection lives in the window's mirror rule
+  pwg_conv1d_desc raw = *d;
+  raw.pad_mode = PWG_PAD_ZERO;
+  return stream_run<SlotsMirroredKernel>("conv1d_stream_slots_mirrored", "conv1d_stream_slots_mirrored_kernel", &raw, g, tile,
+                                         &a, x, hist_in, hist_out, w_packed, bias, nullptr, nullptr, y, window, 0.0,
+                                         image_bytes(g), (hipStream_t)stream_);
 }

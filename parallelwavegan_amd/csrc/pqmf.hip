@@ -12,6 +12,8 @@
 // tap read feeds 4 K FMAs.  Backward passes reuse the two kernels with the roles of the filters swapped.
 #include "common.h"
 
+#include "stream_common.h"  // the row reader of the slotted form (stream_slot_item)
+
 namespace pwg {
 
 constexpr int PQMF_NI = 4;                 // outputs (down) / input positions (up) per lane: a filter tap read from LDS
@@ -420,6 +422,84 @@ __global__ __launch_bounds__(256) void pqmf_up_stream_kernel(const float* __rest
   }
 }
 
+// ---- the slotted form (utils.MelGANStreamPool): the stream launch with one position per item, read
+// from the table of the slotted conv stream kernels (stream_common.h).  It always emits n_emit = n positions, the chunk
+// positions [-D, n - D): every column they read lies in [-hist, n).  The generator already stores exact zeros around
+// each utterance, so the synthesis needs no window -- only the two flags.  A FRESH item (row[0] == 0) reads hist_in as
+// zeros whatever it holds; a PAUSED item copies hist_in to hist_out (zeros if it is also fresh), stores 0.0f to its x
+// columns, does not read y and returns in front of every barrier (workgroup-uniform).  A running item is the launch
+// above on the item alone (hist_in NULL if fresh), chain and all.  The first D positions of a fresh item lie before its
+// late stream: they hold the sums of the zero context and the schedule never emits them.
+template <int K>
+__global__ __launch_bounds__(256) void pqmf_up_stream_slots_kernel(const float* __restrict__ y,
+                                                                   const float* __restrict__ hist_in,
+                                                                   float* __restrict__ hist_out,
+                                                                   const float* __restrict__ g, float* __restrict__ x,
+                                                                   const int32_t* __restrict__ slots, int n, int hist,
+                                                                   int len, int pad, int dlo) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int span = hist + 1;
+  const int pl = PQMF_ST + hist;
+  float* ct = lds + K * pl;
+  const int j0 = blockIdx.x * PQMF_ST;
+  const long b = blockIdx.y;
+  const StreamSlotItem item = stream_slot_item(slots, (int)b, 1, 0, n);  // (only the flags are used)
+  const float* yb = y + b * K * (long)n;
+  const float* hb = item.fresh ? nullptr : hist_in + b * K * (long)hist;
+  float* ho = hist_out + b * K * (long)hist;
+  float* xb = x + b * K * (long)n;
+  const long tbase = (long)j0 * K, t_out = (long)n * K;
+  if (item.paused) {
+    if (blockIdx.x == 0)
+      for (int idx = threadIdx.x; idx < K * hist; idx += 256) ho[idx] = hb ? hb[idx] : 0.f;
+    for (int idx = threadIdx.x; idx < PQMF_ST * K; idx += 256)
+      if (tbase + idx < t_out) xb[tbase + idx] = 0.f;
+    return;
+  }
+  // from here on pqmf_up_stream_kernel with n_emit == n, statement for statement (that kernel keeps its own text, and
+  // with it its bytes)
+  auto window = [&](int k, int w) -> float {
+    if (w < hist) return hb ? hb[k * hist + w] : 0.f;
+    return w - hist < n ? yb[k * (long)n + (w - hist)] : 0.f;
+  };
+  if (blockIdx.x == 0) {
+    for (int idx = threadIdx.x; idx < K * hist; idx += 256) {
+      const int k = idx / hist, h = idx - k * hist;
+      ho[idx] = window(k, n + h);
+    }
+  }
+  for (int idx = threadIdx.x; idx < K * pl; idx += 256) {
+    const int k = idx / pl, a = idx - k * pl;
+    lds[idx] = window(k, j0 + a);
+  }
+  for (int idx = threadIdx.x; idx < K * span * K; idx += 256) {
+    const int r = idx % K, a = (idx / K) % span, k = idx / (K * span);
+    const int m = r + pad - (dlo + a) * K;
+    ct[idx] = (m >= 0 && m < len) ? g[k * len + m] : 0.f;
+  }
+  __syncthreads();
+  float acc[K];
+#pragma unroll
+  for (int r = 0; r < K; ++r) acc[r] = 0.f;
+  const int q = threadIdx.x;
+  for (int k = 0; k < K; ++k) {
+    for (int a = 0; a < span; ++a) {
+      float cv[K];
+#pragma unroll
+      for (int r = 0; r < K; ++r) cv[r] = ct[(k * span + a) * K + r];
+      pqmf_fma_row<K>(acc, cv, lds[k * pl + q + a]);
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < K; ++r) lds[q * K + r] = acc[r];
+  __syncthreads();
+  for (int idx = threadIdx.x; idx < PQMF_ST * K; idx += 256) {
+    const long t = tbase + idx;
+    if (t < t_out) xb[t] = lds[idx];
+  }
+}
+
 // d = i - q of `up`: [dlo, dhi] = [ceil((pad - len + 1) / K), floor((K - 1 + pad) / K)]
 static inline void up_reach(int K, int len, int pad, int* dlo, int* dhi) {
   const int lo_num = pad - len + 1;  // (floor division towards -inf for the negative lower bound)
@@ -438,6 +518,19 @@ static int launch_up_stream(const float* y, const float* hist_in, float* hist_ou
   hipLaunchKernelGGL(pqmf_up_stream_kernel<K>, dim3(tiles, batch), dim3(256), lds, s, y, hist_in, hist_out, g, x, n, n_emit,
                      hist, len, pad, dlo);
   PWG_CHECK_LAUNCH("pqmf_up_stream_kernel");
+  return PWG_OK;
+}
+
+template <int K>
+static int launch_up_stream_slots(const float* y, const float* hist_in, float* hist_out, const float* g, float* x,
+                                  const int32_t* slots, int batch, int n, int len, int pad, hipStream_t s) {
+  int dlo, dhi;
+  up_reach(K, len, pad, &dlo, &dhi);
+  const int hist = dhi - dlo;
+  const size_t lds = sizeof(float) * ((size_t)K * (PQMF_ST + hist) + (size_t)K * (hist + 1) * K);  // (as launch_up_stream)
+  hipLaunchKernelGGL(pqmf_up_stream_slots_kernel<K>, dim3(ceil_div(n, PQMF_ST), batch), dim3(256), lds, s, y, hist_in,
+                     hist_out, g, x, slots, n, hist, len, pad, dlo);
+  PWG_CHECK_LAUNCH("pqmf_up_stream_slots_kernel");
   return PWG_OK;
 }
 
@@ -565,4 +658,26 @@ extern "C" int pwg_pqmf_up_stream(const float* y, const float* hist_in, float* h
   ProfScope prof(s, "pqmf_up_stream_kernel", 2.0 * batch * (double)n_emit * subbands * subbands * (hist + 1),
                  4.0 * batch * subbands * ((double)n + 2.0 * hist + (double)n_emit));
   PQMF_DISPATCH(launch_up_stream, y, hist_in, hist_out, g, x, batch, (int)n, (int)n_emit, len, pad, s);
+}
+
+extern "C" int pwg_pqmf_up_stream_slots(const float* y, const float* hist_in, float* hist_out, const float* g, float* x,
+                                        const int32_t* slots, int32_t batch, int64_t n, int32_t subbands, int32_t len,
+                                        int32_t pad, void* stream) {
+  int32_t hist = 0;
+  const int rc = pwg_pqmf_up_stream_geometry(subbands, len, pad, &hist, nullptr);
+  if (rc != PWG_OK) return rc;
+  PWG_REQUIRE(batch > 0 && batch <= 65535 && n > 0 && n * subbands < (1LL << 31), PWG_ERR_BAD_SHAPE,
+              "pqmf_up_stream_slots: bad geometry (B=%d n=%lld)", batch, (long long)n);
+  PWG_REQUIRE(y && g && x && (hist_out || hist == 0), PWG_ERR_NULL, "pqmf_up_stream_slots: NULL pointer");
+  PWG_REQUIRE(hist_in || hist == 0, PWG_ERR_NULL,
+              "pqmf_up_stream_slots: hist_in is NULL (the start of a stream is an item's, in the table)");
+  PWG_REQUIRE(slots != nullptr, PWG_ERR_NULL, "pqmf_up_stream_slots: slots is NULL");
+  PWG_REQUIRE((reinterpret_cast<uintptr_t>(slots) & 3u) == 0, PWG_ERR_BAD_SHAPE, "pqmf_up_stream_slots: unaligned slot table");
+  PWG_REQUIRE(hist == 0 || hist_in != hist_out, PWG_ERR_BAD_SHAPE,
+              "pqmf_up_stream_slots: hist_in and hist_out must be distinct buffers (other workgroups read the history)");
+  hipStream_t s = (hipStream_t)stream;
+  maybe_poison_lds(s);
+  ProfScope prof(s, "pqmf_up_stream_slots_kernel", 2.0 * batch * (double)n * subbands * subbands * (hist + 1),
+                 4.0 * batch * subbands * (2.0 * (double)n + 2.0 * hist));
+  PQMF_DISPATCH(launch_up_stream_slots, y, hist_in, hist_out, g, x, slots, batch, (int)n, len, pad, s);
 }

@@ -7,6 +7,7 @@
 //   window rule           stream_slot_window     the valid columns of a launch from a push-relative position
 //   slotted form          StreamSlots            the delayed form with one position per item, read from a device table
 //                         stream_slot_item       ... the row reader, shared with the slotted kernels that are no convolution
+//                         StreamSlots::mirrored_at ... with the input edges of a reflect-padded layer (slotted-mirrored form)
 //   mirror rule           StreamMirrorWindow::at the reflect-padded layer of a look-ahead stream: mirror, then resolve
 //   tile rule             stream_tile            column tile from n; 32-row blocks only at 2 x 256 or more workgroups
 //   coverage              stream_geometry        defined in conv1d_stream.hip; both precisions admit the same layers
@@ -90,7 +91,8 @@ struct StreamWindow {
 // column is then resolved by the start-of-stream rule above with zero padding.  A mapped column outside [-H, n) is not
 // live (it reads as zero through the staging loop's safe address): only outputs outside the valid window can depend on
 // one, and those are stored as zeros.  The host saturates in_lo / in_hi to [-H, n + kStreamMaxNt] (mirror_bound), which
-// changes no mapped column inside [-H, n) and keeps the arithmetic far from overflow.
+// changes no mapped column inside [-H, n) and keeps the arithmetic far from overflow; the slotted-mirrored form does the
+// same per item on the device (StreamSlots::mirrored_at).
 struct StreamMirrorWindow {
   StreamWindow raw;  // pad_mode == PWG_PAD_ZERO
   int in_lo, in_hi;
@@ -103,6 +105,14 @@ struct StreamMirrorWindow {
     return c;
   }
 };
+
+// An edge of the mirrored form's input window, saturated for the kernel (StreamMirrorWindow): every window column t lies
+// in [-H, n + kStreamMaxNt), so an edge at or below -H, or at or above n + kStreamMaxNt, acts as that bound does.  One
+// statement for the host (the mirrored entry's scalar edges) and the device (the slotted-mirrored form's per-item ones).
+__host__ __device__ static inline int mirror_bound(long edge, int H, int n) {
+  const long lo = -(long)H, hi = (long)n + kStreamMaxNt;
+  return (int)(edge < lo ? lo : (edge > hi ? hi : edge));
+}
 
 // ---- the fp32 epilogue of an output tile; both argument structs embed it
 struct StreamEpilogue {
@@ -165,10 +175,12 @@ struct StreamSlots : StreamLines {
   const int32_t* slots;  // (B, kStreamSlotInts)
   int rate, out_delay;
 
-  // What a kernel keeps of its item's row across its main loop: four scalars
+  // What a kernel keeps of its item's row across its main loop: four scalars, and the two saturated input edges of a
+  // reflect-padded layer (mirrored_at; 0 and never read in every other kernel)
   struct Item {
     int valid_lo, valid_hi;
     bool fresh, paused;
+    int in_lo, in_hi;
   };
   // The row reader: workgroup-uniform; a table value reaches addressing only through the clamped window and the flags
   __device__ __forceinline__ Item at(int b, int t_out) const {
@@ -176,7 +188,26 @@ struct StreamSlots : StreamLines {
     const int before = __builtin_amdgcn_readfirstlane(row[0]), left = __builtin_amdgcn_readfirstlane(row[1]);
     const int flags = __builtin_amdgcn_readfirstlane(row[2]);
     const StreamValid v = stream_slot_window(out_delay, rate, t_out, before, left, (flags & kStreamSlotLeftKnown) != 0);
-    return Item{v.lo, v.hi, before == 0, (flags & kStreamSlotPaused) != 0};
+    return Item{v.lo, v.hi, before == 0, (flags & kStreamSlotPaused) != 0, 0, 0};
+  }
+  // The row reader of the slotted-mirrored form (a reflect-padded stride-1 layer of history H = 2 * pad on a chunk of n
+  // columns).  Its input is out_delay - pad columns late, so the item's input is valid on
+  // [in_delay - before * rate, in_delay + left * rate), the right edge unbounded while the length is unknown: formed in
+  // 64 bits and saturated by mirror_bound, as the host does for the mirrored entry.  The valid window of the output is
+  // the input's shifted by pad and clamped -- the window rule's, since saturation moves an edge only outside [0, n].
+  // Workgroup-uniform like at(): a table value reaches addressing only through the saturated edges and the flags.
+  __device__ __forceinline__ Item mirrored_at(int b, int H, int n) const {
+    const int32_t* __restrict__ row = slots + (size_t)b * kStreamSlotInts;
+    const int before = __builtin_amdgcn_readfirstlane(row[0]), left = __builtin_amdgcn_readfirstlane(row[1]);
+    const int flags = __builtin_amdgcn_readfirstlane(row[2]);
+    const int pad = H / 2;
+    const long in_delay = (long)out_delay - pad;
+    const int in_lo = mirror_bound(in_delay - (long)before * rate, H, n);
+    const int in_hi = (flags & kStreamSlotLeftKnown) != 0 ? mirror_bound(in_delay + (long)left * rate, H, n)
+                                                          : n + kStreamMaxNt;
+    const int lo = in_lo + pad, hi = in_hi + pad;
+    return Item{lo < 0 ? 0 : (lo > n ? n : lo), hi < 0 ? 0 : (hi > n ? n : hi), before == 0,
+                (flags & kStreamSlotPaused) != 0, in_lo, in_hi};
   }
   // The item's delayed form, built where it is used (the launch's fields come from the kernel arguments again): the
   // launch's lines -- their inputs NULL for a fresh item -- and the item's window
@@ -338,12 +369,14 @@ __attribute__((visibility("hidden"))) int delayed_geometry(const pwg_conv1d_desc
 // history (k - 1) * d is even (symmetric padding) and fits the window.
 __attribute__((visibility("hidden"))) int mirrored_geometry(const pwg_conv1d_desc* d, StreamGeom* g);
 
-// An edge of the mirrored form's input window, saturated for the kernel (StreamMirrorWindow): every window column t lies
-// in [-H, n + kStreamMaxNt), so an edge at or below -H, or at or above n + kStreamMaxNt, acts as that bound does
-static inline int mirror_bound(long edge, int H, int n) {
-  const long lo = -(long)H, hi = (long)n + kStreamMaxNt;
-  return (int)(edge < lo ? lo : (edge > hi ? hi : edge));
-}
+// The slotted-mirrored launch (conv1d_stream.hip, where the kernel family is), behind the entry point of
+// csrc/conv1d_stream_slots_mirrored.hip: the checks, the arguments and the launch of
+// pwg_conv1d_stream_slots_mirrored_forward.
+__attribute__((visibility("hidden"))) int stream_slots_mirrored_forward(const pwg_conv1d_desc* d, const float* x,
+                                                                        const float* hist_in, float* hist_out,
+                                                                        const float* w_packed, const float* bias,
+                                                                        const int32_t* slots, int32_t rate, int32_t delay,
+                                                                        float* y, void* stream);
 
 // The fields both kernels' argument structs share
 struct StreamCommonArgs {

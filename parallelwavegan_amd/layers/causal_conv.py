@@ -131,17 +131,22 @@ _STREAM_KERNELS = {
     ("slots", "fp32"): ("slotted streaming kernel", ops.conv1d_stream_delayed_supported, ops.conv1d_stream_slots_forward),
     ("slots", "bf16"): ("slotted bf16 streaming kernel", ops.conv1d_stream_bf16_delayed_supported,
                         ops.conv1d_stream_slots_forward_bf16),
+    # (nor has the slotted-mirrored form: its coverage is the mirrored form's)
+    ("slots_mirrored", "fp32"): ("slotted mirrored streaming kernel", ops.conv1d_stream_mirrored_supported,
+                                 ops.conv1d_stream_slots_mirrored_forward),
 }
 # what an fp32 launch tells a module in bf16 mode, per form
 _LOOKAHEAD_IS_FP32 = ("the look-ahead stream is fp32 (utils.set_inference_precision(model, 'fp32'), or pass "
                       "precision='bf16' to stream with bf16 operands)")
 _FORM_IS_FP32 = {"plain": "the streaming kernel is fp32 (pass precision='bf16' to stream with bf16 operands)",
-                 "delayed": _LOOKAHEAD_IS_FP32, "mirrored": _LOOKAHEAD_IS_FP32, "slots": _LOOKAHEAD_IS_FP32}
-_FORM_IS_FP32_ONLY = {"mirrored": "a reflect-padded layer streams with a look-ahead in fp32 only"}
+                 "delayed": _LOOKAHEAD_IS_FP32, "mirrored": _LOOKAHEAD_IS_FP32, "slots": _LOOKAHEAD_IS_FP32,
+                 "slots_mirrored": _LOOKAHEAD_IS_FP32}
+_FORM_IS_FP32_ONLY = {"mirrored": "a reflect-padded layer streams with a look-ahead in fp32 only",
+                      "slots_mirrored": "a reflect-padded layer streams with a look-ahead in fp32 only"}
 
 
 def _launch(form, precision, cv, desc, x, hist, *args, delays=(), **kwargs):
-    """One launch of ``cv`` under ``desc`` through the ``form`` ("plain", "delayed", "mirrored") of the streaming kernel
+    """One launch of ``cv`` under ``desc`` through the ``form`` (a key of ``_STREAM_KERNELS``) of the streaming kernel
     on the chunk ``x`` and the history pair ``hist``; ``args`` / ``kwargs``: what the form's launch takes behind the
     bias (addends, delay lines, windows), ``delays``: what its coverage query takes behind the descriptor.  The
     precision is the call's: a bf16 call does not consult the module's own ``precision`` attribute (whole-utterance mode)
@@ -360,8 +365,9 @@ class SlotWalk(_Walk):
     (utils.StreamPool): ``run`` has the same contract, but every launch goes through the slotted form
     and derives each item's valid window itself, from ``slots`` -- the device table of ``ops.conv1d_stream_slots_forward``,
     one row per item -- and its own rate and delay.  There is no start-of-stream walk: ``state_in`` is always a half, and
-    an item that starts an utterance is fresh in the table.  Zero-padded plans only (the mirrored form needs the
-    utterance's end before its last columns)."""
+    an item that starts an utterance is fresh in the table.  A reflect-padded launch (utils.MelGANStreamPool, DESIGN.md
+    s11.12) goes through the slotted-mirrored form, which also derives each item's input edges from the table: fp32
+    only, no addends."""
 
     def __init__(self, plan, state_in, state_out, slots, precision="fp32"):
         if state_in is None:
@@ -372,7 +378,10 @@ class SlotWalk(_Walk):
     def run(self, cv, x, add1=None, add2=None, **fused):
         launch, hist, line1, line2 = self._take_conv(cv)
         if launch_is_mirrored(launch):
-            raise RuntimeError("the mirrored form of the streaming kernel has no slotted form")
+            if add1 is not None or add2 is not None or launch.delay1 or launch.delay2:
+                raise RuntimeError("the mirrored form of the streaming kernel takes no addends")
+            desc = mirrored_desc(cv, x.shape[0], x.shape[-1], **fused)
+            return _launch("slots_mirrored", self.precision, cv, desc, x, hist, self.slots, launch.rate, launch.delay)
         desc = lookahead_desc(cv, x.shape[0], x.shape[-1], **fused)
         return _launch("slots", self.precision, cv, desc, x, hist, add1, line1, launch.delay1, add2, line2, launch.delay2,
                        self.slots, launch.rate, launch.delay, delays=(launch.delay1, launch.delay2))

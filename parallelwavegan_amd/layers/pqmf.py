@@ -120,3 +120,19 @@ class PQMF(torch.nn.Module):
                                                  b, n, int(n_emit), k, self.taps + 1, self.taps // 2, _stream()),
                    "pqmf_up_stream")
         return x
+
+    @torch.no_grad()
+    def stream_synthesis_slots(self, y, hist_in, hist_out, table):
+        """:meth:`stream_synthesis` for a batch whose items sit at different points of different utterances
+        (utils.MelGANStreamPool): ``table`` is the device table of the slotted stream kernels, one row
+        per item -> (B, subbands * n) samples, always ``n_emit == n``: item ``b``'s sample ``j`` is the sample
+        ``j - stream_delay_columns * subbands`` of its chunk.  A running item is :meth:`stream_synthesis` of that item
+        alone (``hist_in`` None if it is fresh), a paused item's history is copied through and its samples are zeros.
+        ``hist_in`` is required.  Inference only."""
+        from ..ops import pqmf_up_stream_slots
+
+        b = y.shape[0]
+        assert y.shape[1] == self.subbands, (tuple(y.shape), self.subbands)
+        for t in (hist_in, hist_out):
+            assert t is None or tuple(t.shape) == self.history_shape(b), (tuple(t.shape), self.history_shape(b))
+        return pqmf_up_stream_slots(y, hist_in, hist_out, self._synthesis_weight[:, 0], table, self.taps // 2)

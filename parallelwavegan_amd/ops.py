@@ -503,6 +503,45 @@ def conv1d_stream_mirrored_forward(desc, x, hist_in, hist_out, w_packed, bias=No
     return out
 
 
+def conv1d_stream_slots_mirrored_forward(desc, x, hist_in, hist_out, w_packed, bias=None, slots=None, rate=1, delay=0,
+                                         out=None):
+    """:func:`conv1d_stream_mirrored_forward` with a position per item (utils.MelGANStreamPool):
+    ``slots`` is the device table of :func:`conv1d_stream_slots_forward`, ``rate`` the launch's output columns per frame
+    and ``delay`` its OUTPUT delay; the kernel derives each item's input window
+    (``utils.streaming.slot_mirror_window``) and valid window itself.  A running item is the mirrored launch of that item
+    alone with those windows, a fresh item reads ``hist_in`` as zeros, a paused item's history is copied through and its
+    output columns are zeros.  ``hist_in`` must be given where the layer has history.  Coverage:
+    :func:`conv1d_stream_mirrored_supported`.  One launch."""
+    _require_device(x, hist_in, hist_out, w_packed, bias, out)
+    out = _conv1d_stream_out(desc, x, hist_in, hist_out, None, None, out)
+    if slots is not None:
+        _slot_table("conv1d_stream_slots_mirrored_forward", slots, desc.batch)
+    _lib.check(_lib.lib().pwg_conv1d_stream_slots_mirrored_forward(
+        ctypes.byref(desc), _ptr(x), _ptr(hist_in), _ptr(hist_out), _ptr(w_packed), _ptr(bias), _ptr(slots), int(rate),
+        int(delay), _ptr(out), _stream()), "conv1d_stream_slots_mirrored_forward")
+    return out
+
+
+def pqmf_up_stream_slots(y, hist_in, hist_out, g, slots, pad):
+    """``pwg_pqmf_up_stream`` with a position per item (``PQMF.stream_synthesis_slots``): ``y`` (B, K, n) sub-band
+    columns, ``hist_in`` / ``hist_out`` (B, K, H), ``g`` (K, len) the synthesis taps, ``slots`` the device table of
+    :func:`conv1d_stream_slots_forward` -> (B, K * n) samples, the chunk positions ``[-D, n - D)`` of every item.  A
+    fresh item reads ``hist_in`` as zeros, a paused item's history is copied through and its samples are zeros.  One
+    launch."""
+    y = y.contiguous()
+    _require_device(y, hist_in, hist_out, g)
+    b, k, n = y.shape
+    if slots is not None:
+        _slot_table("pqmf_up_stream_slots", slots, b)
+    assert g.is_contiguous() and g.dim() == 2 and g.shape[0] == k, (tuple(g.shape), k)
+    for t in (hist_in, hist_out):
+        assert t is None or (t.is_contiguous() and tuple(t.shape[:2]) == (b, k)), (tuple(t.shape), (b, k))
+    x = torch.empty((b, k * n), device=y.device, dtype=torch.float32)
+    _lib.check(_lib.lib().pwg_pqmf_up_stream_slots(_ptr(y), _ptr(hist_in), _ptr(hist_out), _ptr(g), _ptr(x), _ptr(slots), b,
+                                                   n, k, g.shape[1], int(pad), _stream()), "pqmf_up_stream_slots")
+    return x
+
+
 def conv1d_stream_bf16_supported(desc):
     """Does the bf16-operand streaming kernel (csrc/conv1d_stream_bf16.hip) cover this descriptor?  It answers exactly
     as :func:`conv1d_stream_supported`.  Host logic only; ``_lib.lib().pwg_last_error()`` names the reason for a False."""

@@ -36,7 +36,8 @@ layers mirror their window on read (1425 samples for ``melgan.v1``, 2720 for ``m
 
 ``StreamPool`` and ``PWGStreamPool`` run many look-ahead streams of the non-causal HiFi-GAN / Parallel WaveGAN in one
 batch whose utterances start, pause and end independently: every launch reads each item's position from a small device
-table.
+table; ``MelGANStreamPool`` does the same for the reflect-padded (multi-band) MelGAN, whose
+mirrored launches also take their edges per item from the table (s11.12).
 """
 import collections
 import ctypes
@@ -1024,6 +1025,23 @@ def slot_window(delay, rate, t_out, before, left=None):
     return lo, hi
 
 
+STREAM_MAX_TILE_COLUMNS = 64  # kStreamMaxNt (csrc/stream_common.h): the widest column tile of the streaming kernel
+
+
+def slot_mirror_window(delay, pad, rate, n, before, left=None):
+    """The input edges of one item of a slotted-mirrored launch (``StreamSlots::mirrored_at``, csrc/stream_common.h),
+    restated, saturation included: a reflect-padded layer of padding ``pad`` (history ``2 * pad``) whose OUTPUT is
+    ``delay`` columns late at ``rate`` columns per frame, on a chunk of ``n`` columns that ``before`` frames went before;
+    ``left`` as in :func:`slot_window`.  The input is ``delay - pad`` columns late, so it is valid on ``[delay - pad -
+    before * rate, delay - pad + left * rate)``, unbounded on the right while ``left`` is unknown; both edges are
+    saturated to ``[-2 * pad, n + 64]`` (``mirror_bound``), which changes no column a window inside ``[-2 * pad, n)`` maps
+    to.  -> ``(in_lo, in_hi)``, what ``ops.conv1d_stream_mirrored_forward`` takes as ``in_window`` for the item alone;
+    its valid window is :func:`slot_window`'s, equal to ``(in_lo + pad, in_hi + pad)`` clamped to ``[0, n]``."""
+    bound = lambda edge: max(-2 * pad, min(n + STREAM_MAX_TILE_COLUMNS, edge))  # noqa: E731
+    in_delay = delay - pad
+    return bound(in_delay - before * rate), (n + STREAM_MAX_TILE_COLUMNS if left is None else bound(in_delay + left * rate))
+
+
 # What one slot does in one step of the pool.  ``action``: "empty" (no utterance: fresh and paused), "pause" (fewer
 # than a chunk queued, not ended), "run" (a chunk of queued frames), "tail" (ended: what is left, zero-padded) or "drain"
 # (ended: zero frames only); ``take``: queued frames it consumes; ``row``: its row of the kernels' table; ``emit``: the
@@ -1305,15 +1323,98 @@ class StreamPool(_SlotPool):
             if st.action in ("run", "tail", "drain"):
                 self._take(st.slot, st.take, feats[st.slot])
 
-    def _run(self, feats, state_in, state_out):
-        """The generator on one step's inputs, every launch slotted -> (slots, chunk_frames * up)."""
+    def _walk_run(self, feats, state_in, state_out):
+        """The generator on one step's inputs, every launch slotted -> (slots, rows, chunk_frames * rate)."""
         from ..layers.causal_conv import SlotWalk
 
         c = self._features(feats)
         if self.normalize_before:  # the padding frames are zeros AFTER normalisation (row[3]: the real frames)
             c.masked_fill_(self._columns >= self._table[:, 3].reshape(-1, 1, 1), 0.0)
         walk = SlotWalk(self._plan, state_in, state_out, self._table, self.precision)
-        return self.model.lookahead_forward(c, walk).reshape(self.batch, -1)
+        return self.model.lookahead_forward(c, walk)
+
+    def _run(self, feats, state_in, state_out):
+        """-> (slots, chunk_frames * up)."""
+        return self._walk_run(feats, state_in, state_out).reshape(self.batch, -1)
+
+
+class MelGANStreamPool(StreamPool):
+    """``slots`` look-ahead streams of the standard NON-causal, reflect-padded ``MelGANGenerator``
+    (``multi_band_melgan.v2`` included) in one batch, whose utterances start and end whenever they like: what
+    :class:`MelGANLookaheadStream` does for ``batch`` lock-step streams, for a server.  The interface is
+    :class:`StreamPool`'s -- ``open()``, ``feed(slot, frames)``, ``end(slot)``, ``step()`` -> ``{slot: (samples,) fp32}``,
+    ``reset()``, ``open_slots``, ``graphs_captured``, ``latency_samples``, ``state_bytes`` -- and a slot's concatenated
+    emissions are bit for bit what ``MelGANLookaheadStream(model, batch=1)`` emits for the same frames, pushes and flush
+    together.  ``up = upsample_factor * K`` samples per frame, ``K`` the sub-bands (1: full-band).
+
+    How: a reflect-padded launch runs the slotted-mirrored form of the streaming kernel
+    (csrc/conv1d_stream.hip), which takes both edges of each item's input window from the table; the transposed and 1 x 1
+    convolutions run the slotted form; a multi-band model's sub-bands go through the slotted PQMF synthesis
+    (csrc/pqmf.hip) in the same step, which always emits one position per column -- the schedule's emission rule, with
+    the generator's delay and the PQMF's as ``latency_samples``, picks the samples that are the utterance's.  While an
+    utterance's length is unknown its columns stop short of the end by more than any padding, so no output that needs the
+    right-hand mirror is computed before ``end(slot)`` has put the length into the table.  The padding frames of a tail
+    are zeros after normalisation; the first layer mirrors at the utterance's end and never reads them.
+
+    ``end(slot)`` on an utterance of fewer than ``min_frames`` frames (4 for a first layer of kernel 7; one without
+    frames closes silently, as in :class:`StreamPool`) raises RuntimeError, as ``flush()`` does: the slot is closed and
+    free again and has emitted nothing.  ``precision`` may be ``None`` or ``"fp32"``; ``normalize_before`` and the
+    refusals are :class:`MelGANLookaheadStream`'s, for ``slots x chunk_frames``; ``reset()`` closes every slot."""
+
+    def __init__(self, model, slots=16, chunk_frames=8, use_graph=True, normalize_before=False, precision=None):
+        from ..layers.causal_conv import lookahead_settle_frames, lookahead_state_shapes, mirrored_min_frames
+
+        precision = self._checked_precision(precision, "the mirrored form of the streaming kernel, which the reflect-padded "
+                                            "layers run, does not exist with bf16 operands yet")
+        # (MelGANLookaheadStream's checks, in its order and with its reasons, under this class's name)
+        plan, pqmf, out_channels = MelGANLookaheadStream._checked_model.__func__(type(self), model)
+        slots, chunk_frames = self._checked_sizes(slots, chunk_frames)
+        _LookaheadStream._require_plan.__func__(type(self), plan, slots, precision)
+        self._plan = plan
+        self.pqmf = pqmf
+        self.subbands = out_channels
+        up = model.upsample_factor * out_channels
+        latency = (plan[-1].delay + (pqmf.stream_delay_columns if pqmf is not None else 0)) * out_channels
+        self.min_frames = mirrored_min_frames(plan)
+        if (self.min_frames - 1) * up > latency:  # (no recipe: a first layer reaches less far than the whole generator)
+            raise ValueError(f"MelGANStreamPool: an utterance of {self.min_frames - 1} frame(s), too short for reflection, "
+                             f"would emit samples before its end is known (latency {latency} samples, {up} per frame)")
+        self.settle_frames = max(lookahead_settle_frames(plan), -(-latency // up))  # MelGANLookaheadStream.settle_frames_of
+        # what a step uploads: the table and the features; the PQMF history rides behind the plan's state
+        _SlotPool.__init__(self, model, slots, chunk_frames, use_graph, normalize_before, precision, up, latency,
+                           self.settle_frames, lookahead_state_shapes(plan, slots)
+                           + ([pqmf.history_shape(slots)] if pqmf is not None else []), slots,
+                           [(slots, chunk_frames, plan[0].conv.in_channels)])
+        self._columns = torch.arange(chunk_frames, device=self._device).reshape(1, 1, -1)
+
+    @classmethod
+    def state_bytes_of(cls, model, slots):
+        """``state_bytes`` of a pool of ``slots``, from the plan's shapes alone (no device): both ping-pong halves of
+        every launch's state and, for a multi-band model, of the PQMF history."""
+        from ..layers.causal_conv import lookahead_state_shapes
+
+        plan, pqmf, _ = MelGANLookaheadStream._checked_model.__func__(cls, model)
+        shapes = lookahead_state_shapes(plan, int(slots)) + ([pqmf.history_shape(int(slots))] if pqmf is not None else [])
+        return 2 * 4 * sum(b * ch * cols for b, ch, cols in shapes)
+
+    def end(self, slot):
+        st = self._schedule._of(slot, "end")
+        total = st[1]
+        if 0 < total < self.min_frames:  # nothing of it was emitted: (min_frames - 1) * up <= latency_samples
+            self._schedule._state[slot] = None
+            self._queues[slot] = []
+            raise RuntimeError(f"MelGANStreamPool.end: the utterance has {total} frame(s); reflection padding needs at "
+                               f"least {self.min_frames} (the whole-utterance forward cannot pad a shorter one either); "
+                               f"slot {slot} is closed and has emitted nothing")
+        self._schedule.end(slot)
+
+    def _run(self, feats, state_in, state_out):
+        """The generator on one step's inputs, every launch slotted, then the slotted PQMF synthesis of a multi-band
+        model -> (slots, chunk_frames * up)."""
+        if self.pqmf is None:
+            return self._walk_run(feats, state_in, state_out).reshape(self.batch, -1)
+        y = self._walk_run(feats, state_in[:-1], state_out[:-1])
+        return self.pqmf.stream_synthesis_slots(y, state_in[-1], state_out[-1], self._table)
 
 
 class PWGStreamPool(_SlotPool):

@@ -67,6 +67,9 @@ DESIGN.md s11.10).  (a) a step of 16 running slots -- every slot fed its 4 / 8 /
 the replay and the output copy of a step timed alone.  (b) 16 staggered utterances through the pool against the same 16
 through 16 batch-1 ``LookaheadStream``s stepped in turn, in frames per second of wall-clock time.  Into
 profiles/stream_pool_infer.json / profiles/stream_pool_bf16_infer.json.
+``--pool --model melgan [--multiband]``: the same two measurements for ``utils.MelGANStreamPool`` on the non-causal
+melgan.v1 geometry or, with ``--multiband``, multi_band_melgan.v2, against ``utils.MelGANLookaheadStream`` (fp32 only;
+DESIGN.md s11.12; profiles/stream_melgan_pool_infer.json / profiles/stream_mb_melgan_pool_infer.json).
 
 usage: python tools/bench_stream.py [--model pwg|melgan [--lookahead]] [--multiband] [--precision bf16] [--lookahead] [--pool] [--reps 200]
                                     [--repeats 3] [--out profiles/stream_infer.json]
@@ -85,8 +88,8 @@ from parallelwavegan_amd.graphs import GraphedInference  # noqa: E402
 from parallelwavegan_amd.layers import PQMF  # noqa: E402
 from parallelwavegan_amd.models import HiFiGANGenerator, MelGANGenerator, ParallelWaveGANGenerator  # noqa: E402
 from parallelwavegan_amd.utils import (CausalStream, LookaheadStream, MelGANLookaheadStream,  # noqa: E402
-                                       PWGLookaheadStream, PWGStream, PWGStreamPool, StreamPool,
-                                       set_inference_precision)
+                                       MelGANStreamPool, PWGLookaheadStream, PWGStream, PWGStreamPool,
+                                       StreamPool, set_inference_precision)
 from parallelwavegan_amd.utils.streaming import receptive_field_frames  # noqa: E402
 from tests.golden import synth  # noqa: E402
 
@@ -203,17 +206,25 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.pool:
-        if args.model == "melgan" or args.multiband or args.lookahead:
-            ap.error("--pool is the stream pool of the non-causal HiFi-GAN or (--model pwg) Parallel WaveGAN (only --precision "
-                     "goes with it)")
-        pwg = args.model == "pwg"
-        stem = "stream_pwg_pool" if pwg else "stream_pool"
+        pwg, melgan = args.model == "pwg", args.model == "melgan"
+        if args.lookahead or (args.multiband and not melgan):
+            ap.error("--pool is the stream pool of the non-causal HiFi-GAN, (--model pwg) Parallel WaveGAN (only --precision "
+                     "goes with them) or (--model melgan [--multiband]) MelGAN")
+        if melgan and args.precision != "fp32":
+            ap.error("--pool --model melgan is fp32: the mirrored form of the streaming kernel has no bf16 form")
+        stem = ("stream_mb_melgan_pool" if args.multiband else "stream_melgan_pool") if melgan else \
+            "stream_pwg_pool" if pwg else "stream_pool"
         args.out = args.out or os.path.join(ROOT, "profiles", stem + ("_bf16" if args.precision == "bf16" else "") + "_infer.json")
-        rec = {"tool": "tools/bench_stream.py --pool" + (" --model pwg" if pwg else ""),
+        rec = {"tool": "tools/bench_stream.py --pool" + (" --model " + args.model if pwg or melgan else "")
+               + (" --multiband" if args.multiband else ""),
                "device": torch.cuda.get_device_name(0), "reps": args.reps, "repeats": args.repeats, "models": {}, "points": []}
         dev = torch.device("cuda:0")
-        measure_pool(rec, "parallel_wavegan_v1" if pwg else "hifigan_v1", build_pwg(dev, causal=False) if pwg else
-                     build_noncausal(dev), CHUNKS, torch.Generator(device="cpu").manual_seed(100), args, dev, pwg)
+        if melgan:
+            name, model = ("multi_band_melgan_v2", build_multiband(dev, causal=False)) if args.multiband else \
+                ("melgan_v1", build_melgan_noncausal(dev))
+        else:
+            name, model = ("parallel_wavegan_v1", build_pwg(dev, causal=False)) if pwg else ("hifigan_v1", build_noncausal(dev))
+        measure_pool(rec, name, model, CHUNKS, torch.Generator(device="cpu").manual_seed(100), args, dev, pwg, melgan)
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
             json.dump(rec, f, indent=1)
@@ -650,9 +661,10 @@ def measure_pwg_precision(rec, name, model, model16, lookahead, chunks, gen, arg
                                                 "layer_launch_ms")}), file=sys.stderr, flush=True)
 
 
-def measure_pool(rec, name, model, chunks, gen, args, dev, pwg=False):
+def measure_pool(rec, name, model, chunks, gen, args, dev, pwg=False, melgan=False):
     """``StreamPool``, or with ``pwg`` ``PWGStreamPool`` against ``PWGLookaheadStream`` (s11.11; both
-    sides get the same given noise, the pool's from the host), in ``args.precision``.  (a) the cost of the table: a step with all 16 slots
+    sides get the same given noise, the pool's from the host), or with ``melgan`` ``MelGANStreamPool`` against
+    ``MelGANLookaheadStream`` (s11.12), in ``args.precision``.  (a) the cost of the table: a step with all 16 slots
     running in steady state (every slot fed its ``n`` frames from the host, then ``step()``) against
     ``LookaheadStream(batch=16).push`` of ``n`` device-resident frames, alternating; and where a step's time goes (the two
     uploads, the replay, the output copy, each timed alone).  (b) what a server gains: 16 staggered utterances through
@@ -660,9 +672,11 @@ def measure_pool(rec, name, model, chunks, gen, args, dev, pwg=False):
     frames per second of wall-clock time."""
     import time
 
-    up, slots = model.upsample_factor, 16
+    pqmf = getattr(model, "pqmf", None)
+    up, slots = model.upsample_factor * (pqmf.subbands if pqmf is not None else 1), 16  # samples per frame
     med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
-    pool_cls, lock_cls = (PWGStreamPool, PWGLookaheadStream) if pwg else (StreamPool, LookaheadStream)
+    pool_cls, lock_cls = (PWGStreamPool, PWGLookaheadStream) if pwg else \
+        (MelGANStreamPool, MelGANLookaheadStream) if melgan else (StreamPool, LookaheadStream)
     probe = pool_cls(model, slots=slots, chunk_frames=8, use_graph=False, precision=args.precision)
     rec["models"][name] = {"workload": "seeded weights, weight norm removed", "precision": args.precision, "slots": slots,
                            "latency_samples": probe.latency_samples, "pool_state_bytes": probe.state_bytes}

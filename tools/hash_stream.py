@@ -14,7 +14,8 @@ and two more pushes.  Per utterance one line: the hash of the emitted bytes (eve
 tensors of ``_halves[_cur]`` and the three counters.  Noise is given explicitly; the omitted-noise path draws from the
 device generator, so a second pass records its shapes and counters only.
 The pools (``utils.StreamPool`` on the small non-causal HiFi-GAN, ``utils.PWGStreamPool`` on the non-causal Parallel
-WaveGAN; ``run_pool_case``) add their lines where the checkout has the class."""
+WaveGAN, ``utils.MelGANStreamPool`` on the small non-causal MelGAN and multi-band MelGAN, fp32; ``run_pool_case``) add
+their lines where the checkout has the class."""
 import hashlib
 import json
 import os
@@ -122,15 +123,16 @@ def run_case(out, name, cls, model, noise, graph, precision, explicit):
 
 
 POOL_LENGTHS = (2, 9, 14, 5)  # shorter than the latency, not a multiple of the chunk, more utterances than slots
+MELGAN_POOL_LENGTHS = (4, 9, 14, 5)  # (reflection cannot pad fewer than 4 frames)
 
 
-def run_pool_case(out, name, cls, model, noise, graph, precision):
+def run_pool_case(out, name, cls, model, noise, graph, precision, lengths=POOL_LENGTHS):
     """A pool (``utils.StreamPool`` / ``utils.PWGStreamPool``; a checkout that lacks the class has no such lines) of 3
     slots and chunks of 4 frames over four utterances with staggered ``open()`` and irregular ``feed()`` sizes, noise
     given: per utterance the hash of its concatenated emissions, and at the end the state's and the counters."""
     pool = cls(model, slots=3, chunk_frames=4, use_graph=graph, precision=precision)
     gen = torch.Generator().manual_seed(sum(map(ord, name)) * 131 + 11)
-    utts = [(torch.randn(t, 80, generator=gen), torch.randn(t * pool.up, generator=gen)) for t in POOL_LENGTHS]
+    utts = [(torch.randn(t, 80, generator=gen), torch.randn(t * pool.up, generator=gen)) for t in lengths]
     pending, active, outs = list(range(len(utts))), {}, {i: [] for i in range(len(utts))}
     sizes = [1, 3, 0, 6, 2]
     for tick in range(400):
@@ -178,6 +180,11 @@ if __name__ == "__main__":
                 for graph in (False, True):
                     run_pool_case(lines, "pool/" + name.split("/")[1], getattr(utils, pool_name), under_test[name][1], noise,
                                   graph, precision)
+    if hasattr(utils, "MelGANStreamPool"):
+        for name in ("lookahead/melgan", "lookahead/mb_melgan"):
+            for graph in (False, True):
+                run_pool_case(lines, "pool/" + name.split("/")[1], utils.MelGANStreamPool, under_test[name][1], False, graph,
+                              "fp32", MELGAN_POOL_LENGTHS)
     for name, (cls, model, noise) in under_test.items():
         for precision in ("fp32",) if cls is utils.MelGANLookaheadStream else ("fp32", "bf16"):
             for graph in (False, True):
