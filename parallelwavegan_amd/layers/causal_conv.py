@@ -102,14 +102,34 @@ def stream_pointwise(cv, x, precision="fp32", **fused):
                            precision)
 
 
-def stream_history_pairs(layers, hist_in, hist_out):
-    """Iterator over ``(hist_in[i], hist_out[i])`` for the layers of a model's ``stream_layers()`` (``hist_in`` None, the
-    start of a stream: ``(None, hist_out[i])``).  A list of the wrong length is an error, not a shorter walk."""
-    n = len(layers)
-    if len(hist_out) != n or (hist_in is not None and len(hist_in) != n):
-        raise ValueError(f"stream_forward: hist_in / hist_out hold {None if hist_in is None else len(hist_in)} / "
-                         f"{len(hist_out)} history tensors, stream_layers() has {n}")
-    return iter(zip(hist_in if hist_in is not None else [None] * n, hist_out))
+class CausalWalk:
+    """The walk of a CAUSAL model's ``stream_layers()`` (utils.CausalStream): ``run`` has the contract of
+    :meth:`LookaheadWalk.run`, so a module runs its convolutions through either with one loop.  ``hist_in`` (None: start
+    of stream, every layer's own padding) / ``hist_out``: one history tensor per layer, a ping-pong half each -- a list of
+    the wrong length is an error, not a shorter walk; ``precision``: of every launch of the push."""
+
+    def __init__(self, layers, hist_in, hist_out, precision="fp32"):
+        n = len(layers)
+        if len(hist_out) != n or (hist_in is not None and len(hist_in) != n):
+            raise ValueError(f"stream_forward: hist_in / hist_out hold {None if hist_in is None else len(hist_in)} / "
+                             f"{len(hist_out)} history tensors, stream_layers() has {n}")
+        self.precision = precision
+        self._layers = iter(layers)
+        self._pairs = iter(zip(hist_in if hist_in is not None else [None] * n, hist_out))
+
+    def take(self, layer):
+        """The ``(hist_in, hist_out)`` pair of the next layer of ``stream_layers()``, which must be ``layer``."""
+        expected, _ = next(self._layers, (None, None))
+        if expected is not layer:
+            raise RuntimeError(f"causal walk out of step: stream_layers() expects {expected}, the model ran {layer}")
+        return next(self._pairs)
+
+    def run(self, cv, x, add1=None, add2=None, **fused):
+        """``cv`` on the chunk ``x``, one launch; fused-epilogue keywords as in ``forward``.  A causal convolution must be
+        the next layer of ``stream_layers()`` and takes its history pair; an unpadded 1 x 1 ``Conv1d`` keeps no state."""
+        if isinstance(cv, (CausalConv1d, CausalConvTranspose1d)):
+            return cv.stream_forward(x, *self.take(cv), precision=self.precision, add1=add1, add2=add2, **fused)
+        return stream_pointwise(cv, x, precision=self.precision, add1=add1, add2=add2, **fused)
 
 
 def _desc_kw(fused):
@@ -414,7 +434,7 @@ _PWG_STREAM_KERNELS = {
     ("layer", "delayed", "fp32"): ops.wavenet_stream_delayed_forward,
     ("layer", "delayed", "bf16"): ops.wavenet_stream_delayed_forward_bf16,
     ("layer", "slots", "fp32"): ops.wavenet_stream_slots_forward,
-    ("layer", "slots", "bf16"): lambda *args, **kw: ops.wavenet_stream_slots_forward(*args, precision="bf16", **kw),
+    ("layer", "slots", "bf16"): ops.wavenet_stream_slots_forward_bf16,
 }
 
 

@@ -625,7 +625,7 @@ class HiFiGANResidualBlock(torch.nn.Module):
         return x
 
     def stream_layers(self):
-        """The causal convolutions in the order :meth:`stream_forward` visits them."""
+        """The causal convolutions in the order :meth:`walk_forward` visits them."""
         out = []
         for idx in range(len(self.convs1)):
             out.append(self.convs1[idx][1])
@@ -633,29 +633,9 @@ class HiFiGANResidualBlock(torch.nn.Module):
                 out.append(self.convs2[idx][1])
         return out
 
-    def stream_forward(self, x, hist, accum=None, out_div=1.0, precision="fp32"):
-        """The causal ``forward`` on the next chunk of a stream: the same modules in the same order with the same fused
-        epilogues, every convolution through its ``stream_forward``.  ``hist``: iterator of ``(hist_in, hist_out)`` pairs,
-        one per layer of :meth:`stream_layers`; ``precision``: passed to every convolution."""
-        if not self.use_causal_conv:
-            raise ValueError("HiFiGANResidualBlock.stream_forward needs use_causal_conv=True")
-        n = len(self.convs1)
-        for idx in range(n):
-            last = idx == n - 1
-            act1, conv1 = self.convs1[idx][0], self.convs1[idx][1]
-            if self.use_additional_convs:
-                act2, conv2 = self.convs2[idx][0], self.convs2[idx][1]
-                xt = conv1.stream_forward(x, *next(hist), precision=precision, pre_act=act1.kind, pre_slope=act1.slope)
-                x = conv2.stream_forward(xt, *next(hist), precision=precision, pre_act=act2.kind, pre_slope=act2.slope,
-                                         add1=x, add2=accum if last else None, out_div=out_div if last else 1.0)
-            else:
-                x = conv1.stream_forward(x, *next(hist), precision=precision, pre_act=act1.kind, pre_slope=act1.slope,
-                                         add1=x, add2=accum if last else None, out_div=out_div if last else 1.0)
-        return x
-
     def lookahead_plan(self, delay_in, rate, delay_accum=None):
         """Delay plan of the NON-causal block streamed with a look-ahead (layers/causal_conv.py; host only) ->
-        ``(launches, delay_out)``: one :class:`LookaheadLaunch` per convolution in the order :meth:`lookahead_forward`
+        ``(launches, delay_out)``: one :class:`LookaheadLaunch` per convolution in the order :meth:`walk_forward`
         runs them.  ``delay_in``: delay of the block's input; ``rate``: its columns per mel frame; ``delay_accum``: delay
         of the MRF running sum added by the block's last launch (None: no sum yet).  The residual input of a unit is
         older than the unit's output by the paddings of its convolutions; the running sum by the difference of the block
@@ -681,10 +661,11 @@ class HiFiGANResidualBlock(torch.nn.Module):
             dx = d_out
         return launches, dx
 
-    def lookahead_forward(self, x, walk, accum=None, out_div=1.0):
-        """The NON-causal block on the next chunk of a look-ahead stream: the modules, order and fused epilogues of
-        :meth:`stream_forward`, every convolution in its causal form through ``walk`` (a
-        :class:`layers.causal_conv.LookaheadWalk` over the launches of :meth:`lookahead_plan`), which delays the addends."""
+    def walk_forward(self, x, walk, accum=None, out_div=1.0):
+        """The block on the next chunk of a stream: the modules, order and fused epilogues of ``forward``, every
+        convolution one launch through ``walk`` -- a :class:`layers.causal_conv.CausalWalk` over :meth:`stream_layers`
+        (the causal block), or a ``LookaheadWalk`` / ``SlotWalk`` over the launches of :meth:`lookahead_plan` (the
+        NON-causal block in causal form), which delays the addends."""
         n = len(self.convs1)
         for idx in range(n):
             last = idx == n - 1

@@ -6,9 +6,9 @@ import torch
 from .. import functional as Fn
 from .. import ops
 from .activation import FusedActivation
-from .causal_conv import CausalConv1d, LookaheadLaunch, lookahead_delay, mirrored_delay, stream_pointwise
+from .causal_conv import CausalConv1d, LookaheadLaunch, lookahead_delay, mirrored_delay
 from .conv import Conv1d, group_image
-from .padding import get_pad
+from .padding import FusedPad, get_pad
 
 
 class ResidualStack(torch.nn.Module):
@@ -55,9 +55,17 @@ class ResidualStack(torch.nn.Module):
             for cv in self.unit_convs():
                 cv.bank_images = False
 
+    def parts(self):
+        """``(act0, conv0, act1, conv1, skip)``: activation and dilated convolution, activation and 1 x 1 convolution, the
+        skip 1 x 1 -- in either layout (the causal ``stack`` has no pad module, hence other indices).  One pass over the
+        ``Sequential``: indexing it is several times slower, and a stream's push is host-bound."""
+        a0, conv0, a1, conv1 = (m for m in self.stack if not isinstance(m, FusedPad))
+        return a0, conv0, a1, conv1, self.skip_layer
+
     def unit_convs(self):
-        """(dilated convolution, 1x1 convolution, skip 1x1) of the non-causal form."""
-        return self.stack[2], self.stack[4], self.skip_layer
+        """(dilated convolution, 1x1 convolution, skip 1x1)."""
+        _, conv0, _, conv1, skip = self.parts()
+        return conv0, conv1, skip
 
     def unit_slope(self):
         return self.stack[0].slope
@@ -81,10 +89,11 @@ class ResidualStack(torch.nn.Module):
         """The same for the unit's data gradient (transposed weights)."""
         return group_image(self, "_unit_img_bwd", self.unit_convs(), ops.resstack_pack_weight_bwd)
 
-    def _unit_ok(self, c, a0, conv0, a1, conv1):
-        if not self.fuse_unit or self.use_causal_conv or not c.is_cuda or c.dim() != 3 or c.dtype != torch.float32:
+    def _unit_modules_ok(self):
+        """What the one-launch unit (csrc/resstack.hip) asks of the modules, whatever the input."""
+        if not self.fuse_unit or self.use_causal_conv:
             return False
-        skip = self.skip_layer
+        a0, conv0, a1, conv1, skip = self.parts()
         if any(cv.has_spectral_norm or cv.groups != 1 or cv.stride != 1 for cv in (conv0, conv1, skip)):
             return False
         if (conv0.kernel_size != 3 or conv0.pad_mode != "reflect" or conv0.padding != conv0.dilation
@@ -93,19 +102,21 @@ class ResidualStack(torch.nn.Module):
         if a0.kind != "leaky_relu" or a1.kind != "leaky_relu" or a0.slope != a1.slope or not 0.0 < a0.slope < 1.0:
             return False
         ch = conv0.in_channels
-        if any(cv.in_channels != ch or cv.out_channels != ch for cv in (conv0, conv1, skip)) or c.shape[1] != ch:
+        return all(cv.in_channels == ch and cv.out_channels == ch for cv in (conv0, conv1, skip))
+
+    def _unit_ok(self, c):
+        if not c.is_cuda or c.dim() != 3 or c.dtype != torch.float32 or not self._unit_modules_ok():
             return False
-        if not c.is_contiguous():  # (rows are staged with 16-B LDS-DMA pieces; 4-B source alignment is enough)
+        conv0 = self.parts()[1]
+        # (rows are staged with 16-B LDS-DMA pieces; 4-B source alignment is enough)
+        if c.shape[1] != conv0.in_channels or not c.is_contiguous():
             return False
-        return ops.resstack_supported(ch, c.shape[2], conv0.dilation)
+        return ops.resstack_supported(conv0.in_channels, c.shape[2], conv0.dilation)
 
     def forward(self, c):
-        if self.use_causal_conv:
-            a0, conv0, a1, conv1 = self.stack[0], self.stack[1], self.stack[2], self.stack[3]
-        else:
-            a0, conv0, a1, conv1 = self.stack[0], self.stack[2], self.stack[3], self.stack[4]
-        if self._unit_ok(c, a0, conv0, a1, conv1):
-            convs = (conv0, conv1, self.skip_layer)
+        a0, conv0, a1, conv1, skip_layer = self.parts()
+        if self._unit_ok(c):
+            convs = (conv0, conv1, skip_layer)
             bias = [None if cv.bias is None else cv.bias.detach() for cv in convs]
             needs_grad = torch.is_grad_enabled() and (c.requires_grad or any(p.requires_grad for p in self.parameters()))
             if needs_grad and self.fuse_unit_backward:
@@ -116,33 +127,20 @@ class ResidualStack(torch.nn.Module):
                 return y
             # the three layers' autograd nodes, without their launches: the values come from the one-launch unit, the
             # backward pass is the layers' own (the skip branch's value is never read: only its gradient path matters)
-            skip = self.skip_layer(c, precomputed=torch.empty_like(y))
+            skip = skip_layer(c, precomputed=torch.empty_like(y))
             t = conv0(c, pre_act=a0.kind, pre_slope=a0.slope, precomputed=h)
             return conv1(t, pre_act=a1.kind, pre_slope=a1.slope, add1=skip, precomputed=y)
-        skip = self.skip_layer(c)
+        skip = skip_layer(c)
         t = conv0(c, pre_act=a0.kind, pre_slope=a0.slope)
         return conv1(t, pre_act=a1.kind, pre_slope=a1.slope, add1=skip)
 
     # ---- utterances of different lengths in one batch (MelGANGenerator.forward_ragged)
     def ragged_fuses(self, rate):
         """Does :meth:`forward_ragged` run this stack as the ragged form of the one-launch unit at ``rate`` columns per
-        frame, for every batch of at least 64 columns?  Pure host logic over the module geometry (what ``_unit_ok`` asks
-        of the modules, and ``ops.resstack_ragged_supported`` at a covered length)."""
-        if self.use_causal_conv or not self.fuse_unit:
-            return False
-        a0, a1 = self.stack[0], self.stack[3]
-        conv0, conv1, skip = self.unit_convs()
-        if any(cv.has_spectral_norm or cv.groups != 1 or cv.stride != 1 for cv in (conv0, conv1, skip)):
-            return False
-        if (conv0.kernel_size != 3 or conv0.pad_mode != "reflect" or conv0.padding != conv0.dilation
-                or conv0.padding_right != conv0.dilation or conv1.kernel_size != 1 or skip.kernel_size != 1):
-            return False
-        if a0.kind != "leaky_relu" or a1.kind != "leaky_relu" or a0.slope != a1.slope or not 0.0 < a0.slope < 1.0:
-            return False
-        ch = conv0.in_channels
-        if any(cv.in_channels != ch or cv.out_channels != ch for cv in (conv0, conv1, skip)):
-            return False
-        return ops.resstack_ragged_supported(ch, 64, conv0.dilation, rate)
+        frame, for every batch of at least 64 columns?  Pure host logic over the module geometry (``_unit_modules_ok``,
+        and ``ops.resstack_ragged_supported`` at a covered length)."""
+        conv0 = self.parts()[1]
+        return self._unit_modules_ok() and ops.resstack_ragged_supported(conv0.in_channels, 64, conv0.dilation, rate)
 
     @torch.no_grad()
     def forward_ragged(self, x, frames, rate):
@@ -158,7 +156,7 @@ class ResidualStack(torch.nn.Module):
         slack rule of ``MelGANGenerator.forward_ragged``); ``tail`` None."""
         if self.use_causal_conv:
             raise ValueError("ResidualStack: a causal stack has no ragged forward (it streams: stream_forward)")
-        a0, conv0, a1, conv1 = self.stack[0], self.stack[2], self.stack[3], self.stack[4]
+        a0, conv0, a1, conv1, skip_layer = self.parts()
         if conv0.pad_mode != "reflect":
             raise ValueError(f"ResidualStack: pad = {self.stack[1].__class__.__name__}; only a ReflectionPad1d stack has "
                              "a ragged forward (ops.mirror_tail writes the mirror of every item's own end)")
@@ -168,30 +166,16 @@ class ResidualStack(torch.nn.Module):
             if not ops.resstack_ragged_supported(x.shape[1], x.shape[2], conv0.dilation, rate):
                 raise ValueError(f"ResidualStack.forward_ragged: {x.shape[2]} columns per item; the one-launch unit covers "
                                  "64 columns and more (below 4 GB per item): pad the batch")
-            bias = [None if cv.bias is None else cv.bias.detach() for cv in (conv0, conv1, self.skip_layer)]
+            bias = [None if cv.bias is None else cv.bias.detach() for cv in (conv0, conv1, skip_layer)]
             return ops.resstack_forward_ragged(x, frames, rate, self.unit_image(), conv0.dilation, a0.slope, *bias), 0
         ops.mirror_tail(x, frames, rate, conv0.padding)
-        skip = self.skip_layer(x)
+        skip = skip_layer(x)
         t = conv0(x, pre_act=a0.kind, pre_slope=a0.slope)
         return conv1(t, pre_act=a1.kind, pre_slope=a1.slope, add1=skip), None
 
     def stream_layers(self):
         """The causal convolutions that keep history (the 1 x 1 layers have none)."""
         return [self.stack[1]]
-
-    def stream_forward(self, c, hist, precision="fp32"):
-        """The causal ``forward`` on the next chunk of a stream; ``hist``: iterator of ``(hist_in, hist_out)`` pairs, one
-        per layer of :meth:`stream_layers`.  The skip and second 1 x 1 convolutions keep no history, but they too run
-        on the streaming kernel (``H = 0``): the general kernel picks its tile and its split of the reduction from the
-        column count and the batch, so its sums would depend on how the stream is cut into pushes.
-        ``precision``: passed to all three convolutions."""
-        if not self.use_causal_conv:
-            raise ValueError("ResidualStack.stream_forward needs use_causal_conv=True")
-        a0, conv0, a1, conv1 = self.stack[0], self.stack[1], self.stack[2], self.stack[3]
-        with torch.no_grad():
-            skip = stream_pointwise(self.skip_layer, c, precision=precision)
-            t = conv0.stream_forward(c, *next(hist), precision=precision, pre_act=a0.kind, pre_slope=a0.slope)
-            return stream_pointwise(conv1, t, precision=precision, pre_act=a1.kind, pre_slope=a1.slope, add1=skip)
 
     # ---- the NON-causal stack streamed with a fixed look-ahead (utils.MelGANLookaheadStream, DESIGN.md s11.8)
     def lookahead_plan(self, delay_in, rate):
@@ -208,11 +192,13 @@ class ResidualStack(torch.nn.Module):
         return [LookaheadLaunch(skip, rate, d_skip, 0, 0), LookaheadLaunch(conv0, rate, d0, 0, 0),
                 LookaheadLaunch(conv1, rate, d1, d1 - d_skip, 0)], d1
 
-    def lookahead_forward(self, c, walk):
-        """The non-causal ``forward`` on the next chunk of a look-ahead stream: the three launches of
-        :meth:`lookahead_plan` through ``walk`` (a :class:`layers.causal_conv.LookaheadWalk`), which delays the skip."""
-        a0, a1 = self.stack[0], self.stack[3]
-        conv0, conv1, skip_layer = self.unit_convs()
+    def walk_forward(self, c, walk):
+        """``forward`` on the next chunk of a stream, three launches through ``walk``.  A
+        :class:`layers.causal_conv.CausalWalk`: the causal stack; the skip and second 1 x 1 convolutions keep no history,
+        but they too run on the streaming kernel (``H = 0``): the general kernel picks its tile and its split of the
+        reduction from the column count and the batch, so its sums would depend on how the stream is cut into pushes.  A
+        ``LookaheadWalk`` / ``SlotWalk``: the launches of :meth:`lookahead_plan`, the walk delaying the skip."""
+        a0, conv0, a1, conv1, skip_layer = self.parts()
         skip = walk.run(skip_layer, c)
         t = walk.run(conv0, c, pre_act=a0.kind, pre_slope=a0.slope)
         return walk.run(conv1, t, add1=skip, pre_act=a1.kind, pre_slope=a1.slope)

@@ -12,8 +12,7 @@ import torch
 
 from .. import functional as Fn
 from ..layers.activation import FusedActivation, PreActivated, deferrable
-from ..layers.causal_conv import (CausalConv1d, CausalConvTranspose1d, LookaheadLaunch, lookahead_delay,
-                                  stream_history_pairs)
+from ..layers.causal_conv import CausalConv1d, CausalConvTranspose1d, CausalWalk, LookaheadLaunch, lookahead_delay
 from ..layers.conv import Conv1d, Conv2d, ConvTranspose1d, each_conv
 from ..layers.pooling import get_pooling
 from ..streams import fork_now, run_branches, run_branches_chained
@@ -154,7 +153,7 @@ class HiFiGANGenerator(torch.nn.Module):
         return ops.zero_tail(conv(c, pre_act=act.kind, pre_slope=act.slope, post_act="tanh"), frames, rate)
 
     def stream_layers(self):
-        """``(layer, rate)`` of every causal convolution in the order :meth:`stream_forward` visits them; ``rate``: the
+        """``(layer, rate)`` of every causal convolution in the order :meth:`walk_forward` visits them; ``rate``: the
         layer's input columns per mel frame."""
         if not self.use_causal_conv:
             raise ValueError("HiFiGANGenerator: streaming needs use_causal_conv=True")
@@ -171,31 +170,16 @@ class HiFiGANGenerator(torch.nn.Module):
     @torch.no_grad()
     def stream_forward(self, c, hist_in, hist_out, precision="fp32"):
         """The causal ``forward`` on the next chunk ``c`` (B, in_channels, n) of a stream -> (B, out_channels, n *
-        upsample_factor): the same modules in the same order with the same fused epilogues (MRF running sum through
-        ``accum`` / ``out_div``, residual ``add1``, the default-slope LeakyReLU in front of the output convolution,
-        tanh), one launch per convolution, no stream forking.  ``hist_in`` / ``hist_out``: one history tensor per layer
-        of :meth:`stream_layers` (``hist_in`` None: start of stream); see :class:`utils.CausalStream`.  ``precision``:
-        ``"bf16"`` runs every convolution on the bf16-operand stream kernel (the modules' own ``precision`` attributes
-        are not consulted)."""
-        hist = stream_history_pairs(self.stream_layers(), hist_in, hist_out)
-        c = self.input_conv.stream_forward(c, *next(hist), precision=precision)
-        nb = self.num_blocks
-        for i in range(self.num_upsamples):
-            act, up = self.upsamples[i][0], self.upsamples[i][1]
-            c = up.stream_forward(c, *next(hist), precision=precision, pre_act=act.kind, pre_slope=act.slope)
-            cs = None
-            for j in range(nb):
-                cs = self.blocks[i * nb + j].stream_forward(c, hist, accum=cs, out_div=float(nb) if j == nb - 1 else 1.0,
-                                                            precision=precision)
-            c = cs
-        act, conv = self.output_conv[0], self.output_conv[1]
-        return conv.stream_forward(c, *next(hist), precision=precision, pre_act=act.kind, pre_slope=act.slope,
-                                   post_act="tanh")
+        upsample_factor): :meth:`walk_forward` through a :class:`layers.causal_conv.CausalWalk`, one launch per
+        convolution.  ``hist_in`` / ``hist_out``: one history tensor per layer of :meth:`stream_layers` (``hist_in`` None:
+        start of stream); see :class:`utils.CausalStream`.  ``precision``: ``"bf16"`` runs every convolution on the
+        bf16-operand stream kernel (the modules' own ``precision`` attributes are not consulted)."""
+        return self.walk_forward(c, CausalWalk(self.stream_layers(), hist_in, hist_out, precision))
 
     def lookahead_plan(self):
         """Delay plan of the NON-causal generator streamed with a fixed look-ahead (:class:`utils.LookaheadStream`,
         DESIGN.md s11.4): one ``LookaheadLaunch(conv, rate, delay, delay1, delay2)`` per convolution in the order
-        :meth:`lookahead_forward` runs them -- output columns per mel frame, delay of the output in columns, and how much
+        :meth:`walk_forward` runs them -- output columns per mel frame, delay of the output in columns, and how much
         older its two addends are.  The last launch's delay is the stream's latency in samples.  Pure host logic over
         the module geometry.  ValueError for a causal generator and for MRF blocks whose delays decrease."""
         if self.use_causal_conv:
@@ -217,11 +201,14 @@ class HiFiGANGenerator(torch.nn.Module):
         return plan
 
     @torch.no_grad()
-    def lookahead_forward(self, c, walk):
-        """The NON-causal ``forward`` on the next chunk ``c`` (B, in_channels, n) of a look-ahead stream -> (B,
-        out_channels, n * upsample_factor), late by the plan's last delay: the modules, order and fused epilogues of
-        :meth:`stream_forward`, every convolution in its causal form through ``walk`` (a
-        :class:`layers.causal_conv.LookaheadWalk` over :meth:`lookahead_plan`)."""
+    def walk_forward(self, c, walk):
+        """``forward`` on the next chunk ``c`` (B, in_channels, n) of a stream -> (B, out_channels, n * upsample_factor):
+        the same modules in the same order with the same fused epilogues (MRF running sum through ``accum`` /
+        ``out_div``, residual ``add1``, the default-slope LeakyReLU in front of the output convolution, tanh), no stream
+        forking, every convolution one launch through ``walk``.  A :class:`layers.causal_conv.CausalWalk` over
+        :meth:`stream_layers`: the causal generator's stream; a ``LookaheadWalk`` or ``SlotWalk`` over
+        :meth:`lookahead_plan`: the NON-causal generator's, every convolution in its causal form, late by the plan's last
+        delay."""
         c = walk.run(self.input_conv, c)
         nb = self.num_blocks
         for i in range(self.num_upsamples):
@@ -229,7 +216,7 @@ class HiFiGANGenerator(torch.nn.Module):
             c = walk.run(up, c, pre_act=act.kind, pre_slope=act.slope)
             cs = None
             for j in range(nb):
-                cs = self.blocks[i * nb + j].lookahead_forward(c, walk, accum=cs, out_div=float(nb) if j == nb - 1 else 1.0)
+                cs = self.blocks[i * nb + j].walk_forward(c, walk, accum=cs, out_div=float(nb) if j == nb - 1 else 1.0)
             c = cs
         act, conv = self.output_conv[0], self.output_conv[1]
         return walk.run(conv, c, pre_act=act.kind, pre_slope=act.slope, post_act="tanh")

@@ -6,8 +6,8 @@ import numpy as np
 import torch
 
 from ..layers.activation import FusedActivation, PreActivated, deferrable
-from ..layers.causal_conv import (CausalConv1d, CausalConvTranspose1d, LookaheadLaunch, lookahead_delay, mirrored_delay,
-                                  stream_history_pairs)
+from ..layers.causal_conv import (CausalConv1d, CausalConvTranspose1d, CausalWalk, LookaheadLaunch, lookahead_delay,
+                                  mirrored_delay)
 from ..layers.conv import Conv1d, ConvTranspose1d
 from ..layers.padding import FusedPad, get_pad
 from ..layers.pooling import get_pooling
@@ -91,92 +91,75 @@ class MelGANGenerator(torch.nn.Module, _MelGANNormMixin):
         self.reset_parameters()
         self.pqmf = None
 
+    def _stages(self):
+        """``(module, pending activation, is last convolution, rate of its input)`` of the modules that compute, in
+        ``forward`` order and in either layout; a residual stack has no pending activation.  ``rate``: the module's input
+        columns per mel frame.  One pass, a list: a causal push walks it twice (``stream_layers``, ``walk_forward``)."""
+        out, act, rate, last = [], None, 1, None
+        for m in self.melgan:
+            if isinstance(m, ResidualStack):
+                out.append((m, None, False, rate))
+            elif isinstance(m, FusedActivation):
+                act = m
+            elif isinstance(m, (Conv1d, CausalConv1d, ConvTranspose1d, CausalConvTranspose1d)):
+                out.append((m, act, False, rate))  # the convolution consumes the pending activation
+                act = None
+                if isinstance(m, (ConvTranspose1d, CausalConvTranspose1d)):
+                    rate *= m.stride
+                else:
+                    last = len(out) - 1
+        out[last] = out[last][:2] + (True,) + out[last][3:]
+        return out
+
+    def _fused(self, act, last):
+        """The fused-epilogue keywords of a convolution of :meth:`_stages`."""
+        kw = dict(pre_act=act.kind, pre_slope=act.slope) if act is not None else {}
+        if last and self.use_final_nonlinear_activation:
+            kw["post_act"] = "tanh"
+        return kw
+
     def forward(self, c):
         """(B, in_channels, T) -> (B, out_channels, T * prod(upsample_scales))."""
-        mods = list(self.melgan)
         x = c
-        act = None
-        last_conv = max(i for i, m in enumerate(mods) if isinstance(m, (Conv1d, CausalConv1d)))
-        for i, m in enumerate(mods):
-            if isinstance(m, FusedActivation):
-                act = m
-            elif isinstance(m, (FusedPad, torch.nn.Identity)):
-                continue
-            elif isinstance(m, ResidualStack):
-                x = m(x)
-            else:  # Conv1d / ConvTranspose1d: consume the pending activation
-                kw = dict(pre_act=act.kind, pre_slope=act.slope) if act is not None else {}
-                if i == last_conv and self.use_final_nonlinear_activation:
-                    kw["post_act"] = "tanh"
-                x = m(x, **kw)
-                act = None
+        for m, act, last, _ in self._stages():
+            x = m(x) if isinstance(m, ResidualStack) else m(x, **self._fused(act, last))
         return x
 
-    def _stream_walk(self):
-        """``(index, module, pending activation, rate)`` of the modules that compute, in ``forward`` order."""
-        act, rate = None, 1
-        for i, m in enumerate(self.melgan):
-            if isinstance(m, FusedActivation):
-                act = m
-            elif isinstance(m, (FusedPad, torch.nn.Identity)):
-                continue
-            elif isinstance(m, ResidualStack):
-                yield i, m, None, rate
-            else:
-                yield i, m, act, rate
-                act = None
-                if isinstance(m, CausalConvTranspose1d):
-                    rate *= m.stride
-
     def stream_layers(self):
-        """``(layer, rate)`` of every causal convolution that keeps history, in the order :meth:`stream_forward` visits
+        """``(layer, rate)`` of every causal convolution that keeps history, in the order :meth:`walk_forward` visits
         them; ``rate``: the layer's input columns per mel frame."""
         if not isinstance(self.melgan[0], CausalConv1d):
             raise ValueError("MelGANGenerator: streaming needs use_causal_conv=True")
         out = []
-        for _, m, _, rate in self._stream_walk():
+        for m, _, _, rate in self._stages():
             out += [(cv, rate) for cv in (m.stream_layers() if isinstance(m, ResidualStack) else [m])]
         return out
 
     @torch.no_grad()
     def stream_forward(self, c, hist_in, hist_out, precision="fp32"):
         """The causal ``forward`` on the next chunk ``c`` (B, in_channels, n) of a stream -> (B, out_channels, n *
-        upsample_factor): the same modules in the same order with the same fused epilogues.  ``hist_in`` / ``hist_out``:
-        one history tensor per layer of :meth:`stream_layers` (``hist_in`` None: start of stream, which for the
-        reflect-padded layers needs ``utils.CausalStream.warmup_frames`` frames); see :class:`utils.CausalStream`.
+        upsample_factor): :meth:`walk_forward` through a :class:`layers.causal_conv.CausalWalk`.  ``hist_in`` /
+        ``hist_out``: one history tensor per layer of :meth:`stream_layers` (``hist_in`` None: start of stream, which for
+        the reflect-padded layers needs ``utils.CausalStream.warmup_frames`` frames); see :class:`utils.CausalStream`.
         ``precision``: ``"bf16"`` runs every convolution, the 1 x 1 ones included, on the bf16-operand stream kernel."""
-        hist = stream_history_pairs(self.stream_layers(), hist_in, hist_out)
-        walk = list(self._stream_walk())
-        last_conv = max(i for i, m, _, _ in walk if isinstance(m, CausalConv1d))
-        x = c
-        for i, m, act, _ in walk:
-            if isinstance(m, ResidualStack):
-                x = m.stream_forward(x, hist, precision=precision)
-                continue
-            kw = dict(pre_act=act.kind, pre_slope=act.slope) if act is not None else {}
-            if i == last_conv and self.use_final_nonlinear_activation:
-                kw["post_act"] = "tanh"
-            x = m.stream_forward(x, *next(hist), precision=precision, **kw)
-        return x
+        return self.walk_forward(c, CausalWalk(self.stream_layers(), hist_in, hist_out, precision))
 
-    def _lookahead_walk(self):
-        """``(module, pending activation, is last convolution)`` of the modules that compute, in ``forward`` order."""
-        mods = list(self.melgan)
-        last_conv = max(i for i, m in enumerate(mods) if isinstance(m, Conv1d))
-        act = None
-        for i, m in enumerate(mods):
-            if isinstance(m, FusedActivation):
-                act = m
-            elif isinstance(m, ResidualStack):
-                yield m, None, False
-            elif isinstance(m, (Conv1d, ConvTranspose1d)):
-                yield m, act, i == last_conv
-                act = None
+    @torch.no_grad()
+    def walk_forward(self, c, walk):
+        """``forward`` on the next chunk ``c`` (B, in_channels, n) of a stream -> (B, out_channels, n * upsample_factor):
+        the modules, order and fused epilogues of ``forward``, every convolution one launch through ``walk``.  A
+        :class:`layers.causal_conv.CausalWalk` over :meth:`stream_layers`: the causal generator's stream; a
+        ``LookaheadWalk`` or ``SlotWalk`` over :meth:`lookahead_plan`: the NON-causal generator's, every convolution in
+        its causal form, late by the plan's last delay."""
+        x = c
+        for m, act, last, _ in self._stages():
+            x = m.walk_forward(x, walk) if isinstance(m, ResidualStack) else walk.run(m, x, **self._fused(act, last))
+        return x
 
     def lookahead_plan(self):
         """Delay plan of the NON-causal generator streamed with a fixed look-ahead
         (:class:`utils.MelGANLookaheadStream`): one ``LookaheadLaunch(conv, rate, delay, delay1, delay2)``
-        per convolution in the order :meth:`lookahead_forward` runs them.  The reflect-padded convolutions (the first and
+        per convolution in the order :meth:`walk_forward` runs them.  The reflect-padded convolutions (the first and
         last one, each stack's dilated one) run the mirrored form of the streaming kernel, the transposed and 1 x 1 ones
         the delayed form; a residual stack is three launches (``ResidualStack.lookahead_plan``).  The last launch's delay
         is the generator's latency in output columns (samples, or sub-band columns of a multi-band model).  Pure host
@@ -189,40 +172,23 @@ class MelGANGenerator(torch.nn.Module, _MelGANNormMixin):
             if isinstance(m, FusedPad) and m.mode != "reflect":
                 raise ValueError(f"MelGANGenerator: pad = {m.__class__.__name__} ({m.mode}); only a ReflectionPad1d model "
                                  "streams with a look-ahead (the mirrored form of the streaming kernel)")
-        plan, delay, rate = [], 0, 1
-        for m, _, _ in self._lookahead_walk():
+        plan, delay = [], 0
+        for m, _, _, rate in self._stages():
             if isinstance(m, ResidualStack):
                 launches, delay = m.lookahead_plan(delay, rate)
                 plan += launches
                 continue
             if m.transposed:
-                delay, rate = lookahead_delay(m, delay), rate * m.stride
+                delay, rate = lookahead_delay(m, delay), rate * m.stride  # (a launch's rate is its output's)
             else:
                 delay = mirrored_delay(m, delay)
             plan.append(LookaheadLaunch(m, rate, delay, 0, 0))
         return plan
 
-    @torch.no_grad()
-    def lookahead_forward(self, c, walk):
-        """The NON-causal ``forward`` on the next chunk ``c`` (B, in_channels, n) of a look-ahead stream -> (B,
-        out_channels, n * upsample_factor), late by the plan's last delay: the modules, order and fused epilogues of
-        ``forward``, every convolution in its causal form through ``walk`` (a :class:`layers.causal_conv.LookaheadWalk`
-        over :meth:`lookahead_plan`)."""
-        x = c
-        for m, act, last in self._lookahead_walk():
-            if isinstance(m, ResidualStack):
-                x = m.lookahead_forward(x, walk)
-                continue
-            kw = dict(pre_act=act.kind, pre_slope=act.slope) if act is not None else {}
-            if last and self.use_final_nonlinear_activation:
-                kw["post_act"] = "tanh"
-            x = walk.run(m, x, **kw)
-        return x
-
     # ---- utterances of different lengths in one batch (utils.MelGANRaggedSynthesizer, DESIGN.md s9.5)
     def _ragged_walk(self):
-        """``(module, pending activation, is last convolution, rate of its input)`` of the modules that compute, in
-        ``forward`` order; ValueError for a causal generator and for a ``pad`` other than ``ReflectionPad1d``."""
+        """:meth:`_stages`; ValueError for a causal generator and for a ``pad`` other than
+        ``ReflectionPad1d``."""
         if isinstance(self.melgan[0], CausalConv1d):
             raise ValueError("MelGANGenerator: a causal generator has no ragged forward (it streams in lock step: "
                              "utils.CausalStream)")
@@ -230,12 +196,7 @@ class MelGANGenerator(torch.nn.Module, _MelGANNormMixin):
             if isinstance(m, FusedPad) and m.mode != "reflect":
                 raise ValueError(f"MelGANGenerator: pad = {m.__class__.__name__} ({m.mode}); only a ReflectionPad1d model "
                                  "has a ragged forward (ops.mirror_tail writes the mirror of every item's own end)")
-        rate, out = 1, []
-        for m, act, last in self._lookahead_walk():
-            out.append((m, act, last, rate))
-            if isinstance(m, ConvTranspose1d):
-                rate *= m.stride
-        return out
+        return self._stages()
 
     @property
     def ragged_min_frames(self):
@@ -298,10 +259,7 @@ class MelGANGenerator(torch.nn.Module, _MelGANNormMixin):
             pad = 0 if m.transposed else m.padding
             if (m.transposed or m.kernel_size > 1) and tail != pad:
                 ops.mirror_tail(x, frames, rate, pad)
-            kw = dict(pre_act=act.kind, pre_slope=act.slope) if act is not None else {}
-            if last and self.use_final_nonlinear_activation:
-                kw["post_act"] = "tanh"
-            x, tail = m(x, **kw), None
+            x, tail = m(x, **self._fused(act, last)), None
         return ops.mirror_tail(x, frames, self.upsample_factor, 0)
 
     def register_stats(self, stats):

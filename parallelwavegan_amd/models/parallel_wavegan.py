@@ -224,9 +224,11 @@ class ParallelWaveGANGenerator(torch.nn.Module, _WeightNormMixin):
         ``hist_out``: one history tensor per layer of :meth:`stream_layers` (``hist_in`` None: start of stream); see
         :class:`utils.PWGStream`.  ``precision="bf16"``: ``conv_in``, the 1 x 1 convolutions and the residual blocks run
         with bf16 operands; the stretch stages and every history stay fp32."""
-        from ..layers.causal_conv import stream_history_pairs, stream_pointwise
+        from ..layers.causal_conv import CausalWalk, stream_pointwise
 
-        hist = list(stream_history_pairs(self.stream_layers(), hist_in, hist_out))
+        layers = self.stream_layers()
+        walk = CausalWalk(layers, hist_in, hist_out, precision)  # (the lists' lengths; this model runs its layers itself)
+        hist = [walk.take(layer) for layer, _ in layers]
         n, n_up = len(self.conv_layers), len(hist) - len(self.conv_layers)
         # (the upsampler takes its layers' pairs as two lists; a None entry is its start of stream too)
         up_in, up_out = [h_in for h_in, _ in hist[:n_up]], [h_out for _, h_out in hist[:n_up]]

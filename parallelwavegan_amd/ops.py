@@ -898,14 +898,24 @@ def wavenet_stream_hist_floats(desc):
     return _lib.lib().pwg_wavenet_stream_hist_floats(ctypes.byref(desc))
 
 
-def wavenet_stream_forward(desc, x, c, skips, hist_in, hist_out, packed, b_dil, b_skip, b_out, skips_out=None):
-    """One chunk of a causal gated residual layer's stream in one launch -> (x_out, skips_out); also writes
-    ``hist_out`` = the last H columns of ``concat(hist_in, x)``.  ``hist_in`` None: start of stream (zero left context).
-    ``hist_in`` and ``hist_out`` must be distinct buffers; ``skips_out`` may be ``skips`` itself."""
-    _require_device(x, c, skips, hist_in, hist_out, packed, b_dil, b_skip, b_out, skips_out)
+def _wavenet_stream(entry, name, desc, x, c, skips, hist_in, hist_out, packed, b_dil, b_skip, b_out, bf16=False,
+                    delayed=None, valid=None, slots=None, skips_out=None, save=None):
+    """What the gated layer's stream wrappers share: the checks of every tensor and the call of the library's ``entry``.
+    ``bf16``: ``packed`` is the image of :func:`wavenet_bf16_pack_weights`; ``delayed``: None for the causal form, else
+    ``(c_line, c_delay, skip_line)`` of a delayed or slotted one, which takes its position behind the biases -- the window
+    ``valid``, or ``slots = (table, rate, delay)``; ``save``: None for an entry without the ``z`` / ``g`` outputs, else
+    whether to allocate and return them."""
+    c_line, c_delay, skip_line = (None, 0, (None, None)) if delayed is None else delayed
+    line_in, line_out = skip_line if skips is not None else (None, None)
+    _require_device(x, c, c_line, skips, line_in, line_out, hist_in, hist_out, *(() if bf16 else (packed,)), b_dil, b_skip,
+                    b_out, skips_out)
+    if bf16:
+        _bf16_stream_image(name, packed)
+    if slots is not None:
+        _slot_table(name, slots[0], desc.batch)
     assert x.numel() == desc.batch * desc.residual_channels * desc.t, (tuple(x.shape), desc.batch, desc.t)
     assert c.numel() == desc.batch * desc.aux_channels * desc.t, (tuple(c.shape), desc.batch, desc.t)
-    n_hist = wavenet_stream_hist_floats(desc)
+    n_hist = (wavenet_stream_hist_floats if delayed is None else wavenet_stream_delayed_hist_floats)(desc)
     for t in (hist_in, hist_out):
         assert t is None or n_hist == 0 or t.numel() == n_hist, (tuple(t.shape), n_hist)
     x_out = torch.empty_like(x)
@@ -913,10 +923,34 @@ def wavenet_stream_forward(desc, x, c, skips, hist_in, hist_out, packed, b_dil, 
         skips_out = torch.empty_like(x)
     for t in (skips, skips_out):
         assert t is None or t.numel() == x.numel()
-    _lib.check(_lib.lib().pwg_wavenet_stream_forward(ctypes.byref(desc), _ptr(x), _ptr(c), _ptr(skips), _ptr(hist_in),
-                                                     _ptr(hist_out), _ptr(packed), _ptr(b_dil), _ptr(b_skip), _ptr(b_out),
-                                                     _ptr(x_out), _ptr(skips_out), _stream()), "wavenet_stream_forward")
-    return x_out, skips_out
+    cond = lines = position = ()
+    if delayed is not None:
+        for t in (line_in, line_out):
+            assert t is None or t.numel() == desc.batch * desc.skip_channels * desc.dilation, tuple(t.shape)
+        c_cols = 0
+        if c_line is not None:
+            assert c_line.is_contiguous() and c_line.numel() % (desc.batch * desc.aux_channels) == 0, tuple(c_line.shape)
+            c_cols = c_line.numel() // (desc.batch * desc.aux_channels)
+        cond, lines = (_ptr(c_line), c_cols, int(c_delay)), (_ptr(line_in), _ptr(line_out))
+        if slots is None:
+            lo, hi = (0, desc.t) if valid is None else valid
+            position = (int(lo), int(hi))
+        else:
+            position = (_ptr(slots[0]), int(slots[1]), int(slots[2]))
+    z = torch.empty((x.shape[0], desc.gate_channels, x.shape[2]), device=x.device, dtype=torch.float32) if save else None
+    g = torch.empty_like(x) if save else None
+    _lib.check(entry(ctypes.byref(desc), _ptr(x), _ptr(c), *cond, _ptr(skips), *lines, _ptr(hist_in), _ptr(hist_out),
+                     _ptr(packed), _ptr(b_dil), _ptr(b_skip), _ptr(b_out), *position, _ptr(x_out), _ptr(skips_out),
+                     *(() if save is None else (_ptr(z), _ptr(g))), _stream()), name)
+    return (x_out, skips_out, z, g) if save else (x_out, skips_out)
+
+
+def wavenet_stream_forward(desc, x, c, skips, hist_in, hist_out, packed, b_dil, b_skip, b_out, skips_out=None):
+    """One chunk of a causal gated residual layer's stream in one launch -> (x_out, skips_out); also writes
+    ``hist_out`` = the last H columns of ``concat(hist_in, x)``.  ``hist_in`` None: start of stream (zero left context).
+    ``hist_in`` and ``hist_out`` must be distinct buffers; ``skips_out`` may be ``skips`` itself."""
+    return _wavenet_stream(_lib.lib().pwg_wavenet_stream_forward, "wavenet_stream_forward", desc, x, c, skips, hist_in,
+                           hist_out, packed, b_dil, b_skip, b_out, skips_out=skips_out)
 
 
 def stretch_conv_stream(x, hist_in, hist_out, w, scale, freq_kernel=1, act=None, slope=0.0):
@@ -958,27 +992,8 @@ def wavenet_stream_delayed_forward(desc, x, c, c_line, c_delay, skips, skip_line
     concatenation (``skip_line = (line_in, line_out)``, each (B, 64, dilation); ignored without ``skips``); ``hist_out`` =
     the last ``2 * dilation`` columns of ``concat(hist_in, x)``.  Columns outside ``valid = (lo, hi)`` (None: all are
     valid) are stored as exact zeros in both outputs."""
-    line_in, line_out = skip_line if skips is not None else (None, None)
-    _require_device(x, c, c_line, skips, line_in, line_out, hist_in, hist_out, packed, b_dil, b_skip, b_out)
-    assert x.numel() == desc.batch * desc.residual_channels * desc.t, (tuple(x.shape), desc.batch, desc.t)
-    assert c.numel() == desc.batch * desc.aux_channels * desc.t, (tuple(c.shape), desc.batch, desc.t)
-    n_hist = wavenet_stream_delayed_hist_floats(desc)
-    for t in (hist_in, hist_out):
-        assert t is None or n_hist == 0 or t.numel() == n_hist, (tuple(t.shape), n_hist)
-    for t in (line_in, line_out):
-        assert t is None or t.numel() == desc.batch * desc.skip_channels * desc.dilation, tuple(t.shape)
-    assert skips is None or skips.numel() == x.numel()
-    c_cols = 0
-    if c_line is not None:
-        assert c_line.is_contiguous() and c_line.numel() % (desc.batch * desc.aux_channels) == 0, tuple(c_line.shape)
-        c_cols = c_line.numel() // (desc.batch * desc.aux_channels)
-    x_out, skips_out = torch.empty_like(x), torch.empty_like(x)
-    lo, hi = (0, desc.t) if valid is None else valid
-    _lib.check(_lib.lib().pwg_wavenet_stream_delayed_forward(
-        ctypes.byref(desc), _ptr(x), _ptr(c), _ptr(c_line), c_cols, int(c_delay), _ptr(skips), _ptr(line_in), _ptr(line_out),
-        _ptr(hist_in), _ptr(hist_out), _ptr(packed), _ptr(b_dil), _ptr(b_skip), _ptr(b_out), int(lo), int(hi), _ptr(x_out),
-        _ptr(skips_out), _stream()), "wavenet_stream_delayed_forward")
-    return x_out, skips_out
+    return _wavenet_stream(_lib.lib().pwg_wavenet_stream_delayed_forward, "wavenet_stream_delayed_forward", desc, x, c, skips,
+                           hist_in, hist_out, packed, b_dil, b_skip, b_out, delayed=(c_line, c_delay, skip_line), valid=valid)
 
 
 def stretch_conv_stream_delayed(x, hist_in, hist_out, w, scale, freq_kernel=1, act=None, slope=0.0, valid=None):
@@ -1035,32 +1050,15 @@ def wavenet_stream_slots_forward(desc, x, c, c_line, c_delay, skips, skip_line, 
     and ``skip_line[0]`` as zeros, a paused one copies its state through and stores zeros.  One launch."""
     bf16 = precision == "bf16"
     name = "wavenet_stream_slots_forward_bf16" if bf16 else "wavenet_stream_slots_forward"
-    line_in, line_out = skip_line if skips is not None else (None, None)
-    _require_device(x, c, c_line, skips, line_in, line_out, hist_in, hist_out, b_dil, b_skip, b_out)
-    if bf16:
-        _bf16_stream_image(name, packed)
-    else:
-        _require_device(packed)
-    _slot_table(name, slots, desc.batch)
-    assert x.numel() == desc.batch * desc.residual_channels * desc.t, (tuple(x.shape), desc.batch, desc.t)
-    assert c.numel() == desc.batch * desc.aux_channels * desc.t, (tuple(c.shape), desc.batch, desc.t)
-    n_hist = wavenet_stream_delayed_hist_floats(desc)
-    for t in (hist_in, hist_out):
-        assert t is None or n_hist == 0 or t.numel() == n_hist, (tuple(t.shape), n_hist)
-    for t in (line_in, line_out):
-        assert t is None or t.numel() == desc.batch * desc.skip_channels * desc.dilation, tuple(t.shape)
-    assert skips is None or skips.numel() == x.numel()
-    c_cols = 0
-    if c_line is not None:
-        assert c_line.is_contiguous() and c_line.numel() % (desc.batch * desc.aux_channels) == 0, tuple(c_line.shape)
-        c_cols = c_line.numel() // (desc.batch * desc.aux_channels)
-    x_out, skips_out = torch.empty_like(x), torch.empty_like(x)
-    entry = _lib.lib().pwg_wavenet_stream_slots_forward_bf16 if bf16 else _lib.lib().pwg_wavenet_stream_slots_forward
-    _lib.check(entry(
-        ctypes.byref(desc), _ptr(x), _ptr(c), _ptr(c_line), c_cols, int(c_delay), _ptr(skips), _ptr(line_in), _ptr(line_out),
-        _ptr(hist_in), _ptr(hist_out), _ptr(packed), _ptr(b_dil), _ptr(b_skip), _ptr(b_out), _ptr(slots), int(rate),
-        int(delay), _ptr(x_out), _ptr(skips_out), _stream()), name)
-    return x_out, skips_out
+    return _wavenet_stream(getattr(_lib.lib(), "pwg_" + name), name, desc, x, c, skips, hist_in, hist_out, packed, b_dil,
+                           b_skip, b_out, bf16=bf16, delayed=(c_line, c_delay, skip_line), slots=(slots, rate, delay))
+
+
+def wavenet_stream_slots_forward_bf16(desc, x, c, c_line, c_delay, skips, skip_line, hist_in, hist_out, packed, b_dil,
+                                      b_skip, b_out, slots=None, rate=1, delay=0):
+    """:func:`wavenet_stream_slots_forward` with ``precision="bf16"``, named as the other bf16 wrappers are."""
+    return wavenet_stream_slots_forward(desc, x, c, c_line, c_delay, skips, skip_line, hist_in, hist_out, packed, b_dil,
+                                        b_skip, b_out, slots, rate, delay, precision="bf16")
 
 
 def stretch_conv_stream_slots(x, hist_in, hist_out, w, scale, freq_kernel=1, act=None, slope=0.0, slots=None, rate=1,
@@ -1228,24 +1226,8 @@ def wavenet_stream_forward_bf16(desc, x, c, skips, hist_in, hist_out, packed, b_
     """:func:`wavenet_stream_forward` with bf16 operands on the image of :func:`wavenet_bf16_pack_weights` -> (x_out,
     skips_out), with ``save`` (stage tests) -> (x_out, skips_out, z, g): the fp32 ``z`` and the bf16-rounded gate output
     (stored as fp32).  ``hist_out`` receives the same raw fp32 columns as in fp32."""
-    _require_device(x, c, skips, hist_in, hist_out, b_dil, b_skip, b_out, skips_out)
-    _bf16_stream_image("wavenet_stream_forward_bf16", packed)
-    assert x.numel() == desc.batch * desc.residual_channels * desc.t, (tuple(x.shape), desc.batch, desc.t)
-    assert c.numel() == desc.batch * desc.aux_channels * desc.t, (tuple(c.shape), desc.batch, desc.t)
-    n_hist = wavenet_stream_hist_floats(desc)
-    for t in (hist_in, hist_out):
-        assert t is None or n_hist == 0 or t.numel() == n_hist, (tuple(t.shape), n_hist)
-    x_out = torch.empty_like(x)
-    if skips_out is None:
-        skips_out = torch.empty_like(x)
-    for t in (skips, skips_out):
-        assert t is None or t.numel() == x.numel()
-    z = torch.empty((x.shape[0], desc.gate_channels, x.shape[2]), device=x.device, dtype=torch.float32) if save else None
-    g = torch.empty_like(x) if save else None
-    _lib.check(_lib.lib().pwg_wavenet_stream_bf16_forward(
-        ctypes.byref(desc), _ptr(x), _ptr(c), _ptr(skips), _ptr(hist_in), _ptr(hist_out), _ptr(packed), _ptr(b_dil),
-        _ptr(b_skip), _ptr(b_out), _ptr(x_out), _ptr(skips_out), _ptr(z), _ptr(g), _stream()), "wavenet_stream_forward_bf16")
-    return (x_out, skips_out, z, g) if save else (x_out, skips_out)
+    return _wavenet_stream(_lib.lib().pwg_wavenet_stream_bf16_forward, "wavenet_stream_forward_bf16", desc, x, c, skips,
+                           hist_in, hist_out, packed, b_dil, b_skip, b_out, bf16=True, skips_out=skips_out, save=bool(save))
 
 
 def wavenet_stream_delayed_forward_bf16(desc, x, c, c_line, c_delay, skips, skip_line, hist_in, hist_out, packed, b_dil,
@@ -1253,30 +1235,9 @@ def wavenet_stream_delayed_forward_bf16(desc, x, c, c_line, c_delay, skips, skip
     """:func:`wavenet_stream_delayed_forward` with bf16 operands on the image of :func:`wavenet_bf16_pack_weights` ->
     (x_out, skips_out), with ``save`` (stage tests) -> (x_out, skips_out, z, g); ``z`` and ``g`` are not masked by the
     valid window.  The history and the skip line receive the same raw fp32 columns as in fp32."""
-    line_in, line_out = skip_line if skips is not None else (None, None)
-    _require_device(x, c, c_line, skips, line_in, line_out, hist_in, hist_out, b_dil, b_skip, b_out)
-    _bf16_stream_image("wavenet_stream_delayed_forward_bf16", packed)
-    assert x.numel() == desc.batch * desc.residual_channels * desc.t, (tuple(x.shape), desc.batch, desc.t)
-    assert c.numel() == desc.batch * desc.aux_channels * desc.t, (tuple(c.shape), desc.batch, desc.t)
-    n_hist = wavenet_stream_delayed_hist_floats(desc)
-    for t in (hist_in, hist_out):
-        assert t is None or n_hist == 0 or t.numel() == n_hist, (tuple(t.shape), n_hist)
-    for t in (line_in, line_out):
-        assert t is None or t.numel() == desc.batch * desc.skip_channels * desc.dilation, tuple(t.shape)
-    assert skips is None or skips.numel() == x.numel()
-    c_cols = 0
-    if c_line is not None:
-        assert c_line.is_contiguous() and c_line.numel() % (desc.batch * desc.aux_channels) == 0, tuple(c_line.shape)
-        c_cols = c_line.numel() // (desc.batch * desc.aux_channels)
-    x_out, skips_out = torch.empty_like(x), torch.empty_like(x)
-    z = torch.empty((x.shape[0], desc.gate_channels, x.shape[2]), device=x.device, dtype=torch.float32) if save else None
-    g = torch.empty_like(x) if save else None
-    lo, hi = (0, desc.t) if valid is None else valid
-    _lib.check(_lib.lib().pwg_wavenet_stream_bf16_delayed_forward(
-        ctypes.byref(desc), _ptr(x), _ptr(c), _ptr(c_line), c_cols, int(c_delay), _ptr(skips), _ptr(line_in), _ptr(line_out),
-        _ptr(hist_in), _ptr(hist_out), _ptr(packed), _ptr(b_dil), _ptr(b_skip), _ptr(b_out), int(lo), int(hi), _ptr(x_out),
-        _ptr(skips_out), _ptr(z), _ptr(g), _stream()), "wavenet_stream_delayed_forward_bf16")
-    return (x_out, skips_out, z, g) if save else (x_out, skips_out)
+    return _wavenet_stream(_lib.lib().pwg_wavenet_stream_bf16_delayed_forward, "wavenet_stream_delayed_forward_bf16", desc,
+                           x, c, skips, hist_in, hist_out, packed, b_dil, b_skip, b_out, bf16=True,
+                           delayed=(c_line, c_delay, skip_line), valid=valid, save=bool(save))
 
 
 def wavenet_pack_weights_bwd(desc, w_dil, s_dil, w_aux, s_aux, w_skip, s_skip, w_out, s_out):

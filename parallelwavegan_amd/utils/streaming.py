@@ -207,6 +207,7 @@ class _Stream:
     hist_out)``, the model on one push's inputs in steady state."""
 
     max_graph_shapes = 4  # chunk sizes whose graphs are kept (least recently used evicted)
+    _pooled = False       # a pool of slots (the wording of some refusals), not lock-step streams
 
     def __init__(self, model, layers, batch, use_graph, normalize_before, extra_history=()):
         """``layers``: ``model.stream_layers()``; ``batch``: from ``_checked_batch``; ``extra_history``: shapes of
@@ -234,6 +235,11 @@ class _Stream:
         if batch < 1:
             raise ValueError(f"{cls.__name__}: batch must be >= 1")
         return batch
+
+    @classmethod
+    def _checked_sizes(cls, batch, columns=None):
+        """``(batch, columns of a launch the kernel coverage is asked about)``; a pool's are its slots and chunk."""
+        return cls._checked_batch(batch), 8
 
     @classmethod
     def _checked_precision(cls, precision, no_bf16=None):
@@ -666,6 +672,201 @@ class PWGStream(_Stream):
         return self._push_step(feats, (noise,), self._run, self.use_graph)
 
 
+# What a look-ahead stream or pool is built from, for one model, batch and precision: ``batch`` / ``columns`` from
+# ``_checked_sizes``; ``plan``: ``model.lookahead_plan()``; ``pqmf``: of a multi-band model, else None; ``up``: samples per
+# frame; ``latency_samples``: how late every sample leaves; ``settle_frames``: frames after which no launch has an edge of
+# the utterance in its window or history and nothing is trimmed; ``min_frames``: the shortest utterance; ``state_shapes``:
+# of one ping-pong half, the PQMF history last.
+StreamFigures = collections.namedtuple("StreamFigures", "batch columns plan pqmf up latency_samples settle_frames min_frames "
+                                                        "state_shapes")
+
+
+def _figures(model, plan, pqmf, batch, columns, state_shapes, settle_frames=0, min_frames=1):
+    """The figures that follow from a plan, whatever the family: ``latency_samples`` = the generator's delay times the
+    sub-band count, plus the PQMF's ``K * stream_delay_columns``; ``settle_frames``: what the plan's edges need
+    (``settle_frames``), and the latency in frames."""
+    k = pqmf.subbands if pqmf is not None else 1
+    up = model.upsample_factor * k
+    latency = (plan[-1].delay + (pqmf.stream_delay_columns if pqmf is not None else 0)) * k
+    return StreamFigures(batch, columns, plan, pqmf, up, latency, max(settle_frames, -(-latency // up)), min_frames,
+                         state_shapes + ([pqmf.history_shape(batch)] if pqmf is not None else []))
+
+
+class _Family:
+    """One family of look-ahead streaming (a generator class): whether a model can be streamed and with which figures,
+    for the lock-step class and the pool alike -- both inherit the family beside their core.  ``_streamable(model, batch,
+    columns, precision)`` runs the refusals in the family's order, under the caller's name and in its wording
+    (``_pooled``), and returns the :class:`StreamFigures`; ``_figures_of(model, batch)`` is its part that needs neither a
+    device nor a kernel, which the ``*_of`` class methods read."""
+
+    @classmethod
+    def _conv_plan_figures(cls, model, plan, pqmf, batch=1, columns=8):
+        """:func:`_figures` of a convolution plan (HiFi-GAN, MelGAN); for a plan without a reflect-padded launch
+        ``settle_frames`` is the latency in frames and ``min_frames`` 1."""
+        from ..layers.causal_conv import lookahead_settle_frames, lookahead_state_shapes, mirrored_min_frames
+
+        return _figures(model, plan, pqmf, batch, columns, lookahead_state_shapes(plan, batch),
+                        lookahead_settle_frames(plan), mirrored_min_frames(plan))
+
+    @classmethod
+    def _require_plan(cls, plan, batch, columns, precision):
+        """Every launch of a convolution plan must be one its kernel covers (the slotted forms cover what the delayed
+        and mirrored forms cover; the answer does not depend on the column count)."""
+        from ..layers.causal_conv import launch_desc, launch_is_mirrored
+
+        delayed = conv1d_stream_bf16_delayed_supported if precision == "bf16" else conv1d_stream_delayed_supported
+        for launch in plan:
+            desc = launch_desc(launch, batch, columns)
+            cls._require_supported(conv1d_stream_mirrored_supported(desc) if launch_is_mirrored(launch) else
+                                   delayed(desc, launch.delay1, launch.delay2), launch.conv)
+
+    @classmethod
+    def latency_samples_of(cls, model):
+        """Samples every output leaves late, from the module geometry alone (no device, no kernel): the generator's
+        delay times the sub-band count, plus the PQMF's ``K * stream_delay_columns`` for a multi-band model."""
+        return cls._figures_of(model).latency_samples
+
+    @classmethod
+    def settle_frames_of(cls, model):
+        """Frames after which a push has no edge of the utterance in any window or history and emits ``n * up``
+        samples, from the module geometry alone: the plan's ``lookahead_settle_frames`` and ``latency_frames``."""
+        return cls._figures_of(model).settle_frames
+
+    @classmethod
+    def min_frames_of(cls, model):
+        """The shortest utterance: what reflection can pad (``layers.causal_conv.mirrored_min_frames`` of the plan)."""
+        return cls._figures_of(model).min_frames
+
+    @classmethod
+    def state_bytes_of(cls, model, batch):
+        """``state_bytes`` for ``batch`` streams or slots, from the plan's shapes alone (no device): both ping-pong halves
+        of every launch's state and, for a multi-band model, of the PQMF history; fp32 in either precision."""
+        return 2 * 4 * sum(b * ch * cols for b, ch, cols in cls._figures_of(model, int(batch)).state_shapes)
+
+
+class _HiFiGANFamily(_Family):
+    """The standard NON-causal ``HiFiGANGenerator`` (``LookaheadStream``, ``StreamPool``)."""
+
+    @classmethod
+    def _figures_of(cls, model, batch=1):
+        return cls._conv_plan_figures(model, model.lookahead_plan(), None, batch)
+
+    @classmethod
+    def _streamable(cls, model, batch, columns, precision):
+        from ..models import HiFiGANGenerator
+
+        name, pool = cls.__name__, cls._pooled
+        if not isinstance(model, HiFiGANGenerator):
+            raise ValueError(f"{name}: {model.__class__.__name__} is not supported (only the non-causal "
+                             "HiFiGANGenerator; a non-causal MelGANGenerator streams " + ("in lock step " if pool else "")
+                             + "through utils.MelGANLookaheadStream, a ParallelWaveGANGenerator through "
+                             "utils.PWGLookaheadStream)")
+        if model.use_causal_conv:
+            raise ValueError(f"{name}: the model is causal (use_causal_conv=True) and streams "
+                             + ("in lock step, without look-ahead," if pool else "without look-ahead")
+                             + " through utils.CausalStream")
+        out_channels = model.output_conv[1].out_channels
+        if out_channels != 1:
+            raise ValueError(f"{name}: the generator emits {out_channels} channels; "
+                             + ("a slot returns one waveform" if pool else "the stream returns one waveform per stream")
+                             + " (out_channels == 1)")
+        cls._refuse_bf16_model(model, precision, "look-ahead stream")
+        batch, columns = cls._checked_sizes(batch, columns)
+        plan = model.lookahead_plan()  # ValueError: decreasing block delays, a layer without a causal form
+        cls._require_plan(plan, batch, columns, precision)
+        return cls._conv_plan_figures(model, plan, None, batch, columns)
+
+
+class _MelGANFamily(_Family):
+    """The standard NON-causal, reflect-padded ``MelGANGenerator``, multi-band included (``MelGANLookaheadStream``,
+    ``MelGANStreamPool``).  fp32 only: ``_NO_BF16`` is what ``_checked_precision`` says."""
+
+    _NO_BF16 = ("the mirrored form of the streaming kernel, which the reflect-padded layers run, does not exist with bf16 "
+                "operands yet")
+
+    @classmethod
+    def _checked_model(cls, model):
+        """The refusals that need no device, in order: the class, a causal model, the padding and the layer geometry (the
+        plan), the sub-bands, a bf16 model -> ``(plan, pqmf or None)``."""
+        from ..models import MelGANGenerator
+
+        name = cls.__name__
+        if not isinstance(model, MelGANGenerator):
+            raise ValueError(f"{name}: {model.__class__.__name__} is not supported (only the non-causal MelGANGenerator; "
+                             "HiFiGANGenerator streams through utils.LookaheadStream, ParallelWaveGANGenerator through "
+                             "utils.PWGLookaheadStream)")
+        try:
+            plan = model.lookahead_plan()  # ValueError: causal, a pad other than reflection, an even kernel
+        except ValueError as e:
+            raise ValueError(f"{name}: {e}") from None
+        pqmf = cls._checked_pqmf(model, plan[-1].conv.out_channels)
+        cls._refuse_bf16_model(model, "fp32", "look-ahead stream of a reflect-padded model", has_bf16=False)
+        return plan, pqmf
+
+    @classmethod
+    def _figures_of(cls, model, batch=1):
+        return cls._conv_plan_figures(model, *cls._checked_model(model), batch)
+
+    @classmethod
+    def _streamable(cls, model, batch, columns, precision):
+        plan, pqmf = cls._checked_model(model)
+        batch, columns = cls._checked_sizes(batch, columns)
+        cls._require_plan(plan, batch, columns, precision)
+        figures = cls._conv_plan_figures(model, plan, pqmf, batch, columns)
+        # a pool closes an utterance too short for reflection in end(): nothing of it may have left by then
+        if cls._pooled and (figures.min_frames - 1) * figures.up > figures.latency_samples:  # (no recipe: a first layer
+            # reaches less far than the whole generator)
+            raise ValueError(f"{cls.__name__}: an utterance of {figures.min_frames - 1} frame(s), too short for "
+                             f"reflection, would emit samples before its end is known (latency "
+                             f"{figures.latency_samples} samples, {figures.up} per frame)")
+        return figures
+
+
+class _PWGFamily(_Family):
+    """The standard NON-causal ``ParallelWaveGANGenerator`` (``PWGLookaheadStream``, ``PWGStreamPool``)."""
+
+    @classmethod
+    def _figures_of(cls, model, batch=1, columns=8, plan=None):
+        from ..layers.causal_conv import pwg_lookahead_state_shapes
+
+        plan = model.lookahead_plan() if plan is None else plan
+        return _figures(model, plan, None, batch, columns, pwg_lookahead_state_shapes(plan, batch))
+
+    @classmethod
+    def _streamable(cls, model, batch, columns, precision):
+        from ..layers.causal_conv import pointwise_desc
+        from ..models import HiFiGANGenerator, ParallelWaveGANGenerator
+
+        name, pool = cls.__name__, cls._pooled
+        if not isinstance(model, ParallelWaveGANGenerator):
+            other = "pools through utils.StreamPool" if pool else "streams through utils.LookaheadStream"
+            hint = f"; the non-causal HiFiGANGenerator {other}" if isinstance(model, HiFiGANGenerator) else ""
+            raise ValueError(f"{name}: {model.__class__.__name__} is not supported (only the non-causal "
+                             f"ParallelWaveGANGenerator{hint})")
+        batch, columns = cls._checked_sizes(batch, columns)
+        reason = model.lookahead_unsupported_reason(batch, precision)
+        if reason is not None:
+            raise ValueError(f"{name}: {reason}")
+        if model.in_channels != 1 or model.out_channels != 1:
+            raise ValueError(f"{name}: in_channels / out_channels = {model.in_channels} / {model.out_channels} ("
+                             + ("a slot takes one noise row and returns one waveform" if pool else
+                                "the stream takes one noise row and emits one waveform per stream") + ")")
+        cls._refuse_bf16_model(model, precision, "look-ahead stream")
+        plan = model.lookahead_plan()
+        # a bf16 stream never runs a convolution the bf16 kernel refuses in fp32 instead; a pool asks in fp32 too
+        if precision == "bf16" or pool:
+            delayed = conv1d_stream_bf16_delayed_supported if precision == "bf16" else conv1d_stream_delayed_supported
+            for launch in plan:
+                if launch.kind == "conv_in":
+                    desc = model.upsample_net._lookahead_desc(batch, columns)
+                elif launch.kind in ("first_conv", "last_conv"):
+                    desc = pointwise_desc(launch.module, batch, columns * launch.rate)
+                else:
+                    continue
+                cls._require_supported(delayed(desc), launch.module, " with bf16 operands" if precision == "bf16" else "")
+        return cls._figures_of(model, batch, columns, plan)
+
+
 class _LookaheadStream(_Stream):
     """The look-ahead streams' core: what streaming a NON-causal generator with a fixed look-ahead is, whatever the
     model.  Every layer runs in its causal form on a shifted time axis (``model.lookahead_plan()`` lists the launches and
@@ -691,53 +892,28 @@ class _LookaheadStream(_Stream):
     included, runs in it, and plan, latency, state and partition invariance do not depend on it.  ``None`` and ``"fp32"``
     are the fp32 stream, which refuses a model that ``set_inference_precision`` put in bf16 mode.
 
-    A subclass supplies its constructor (the model's checks in its own order, the plan, the state shapes), ``_run`` and
-    ``_run_tail``, what ``flush`` feeds; the ones here run a convolution plan (HiFi-GAN, MelGAN)."""
+    A subclass names its family (:class:`_Family`: the model's checks in its own order, the plan, the figures) and
+    supplies ``_run`` and ``_run_tail``, what ``flush`` feeds; the ones here run a convolution plan (HiFi-GAN, MelGAN)."""
 
     warmup_frames = 1
     _takes_noise = False  # does ``push`` take noise beside the features
     _keeps_last = False   # does ``flush`` replicate the last frame pushed (``_last``)
 
-    def __init__(self, model, plan, batch, use_graph, normalize_before, precision, state_shapes, pqmf=None, settle_frames=0,
-                 min_frames=1):
-        """``plan``: ``model.lookahead_plan()``; ``pqmf``: of a multi-band model, its history rides behind
-        ``state_shapes`` in both halves; ``settle_frames``: what the plan's edges need, if more than ``latency_frames``."""
-        k = pqmf.subbands if pqmf is not None else 1
+    def __init__(self, model, use_graph, normalize_before, precision, figures):
+        """``figures``: the family's ``_streamable(model, batch, None, precision)``.  The PQMF history of a multi-band
+        model rides behind the plan's state in both halves."""
+        pqmf = figures.pqmf
         self.precision = precision
-        self.up = model.upsample_factor * k  # samples per frame
-        self._plan = plan
+        self.up = figures.up  # samples per frame
+        self._plan = figures.plan
         self._pqmf = pqmf
-        self._hold = pqmf.stream_delay_columns * k if pqmf is not None else 0
-        self._front = plan[-1].delay * k
-        self.latency_samples = self._front + self._hold
+        self._hold = pqmf.stream_delay_columns * pqmf.subbands if pqmf is not None else 0
+        self._front = figures.latency_samples - self._hold
+        self.latency_samples = figures.latency_samples
         self.latency_frames = -(-self.latency_samples // self.up)
-        self.settle_frames = max(settle_frames, self.latency_frames)
-        self.min_frames = min_frames
-        super().__init__(model, [], batch, use_graph, normalize_before,
-                         state_shapes + ([pqmf.history_shape(batch)] if pqmf is not None else []))
-
-    @classmethod
-    def _require_plan(cls, plan, batch, precision):
-        """Every launch of a convolution plan must be one its kernel covers."""
-        from ..layers.causal_conv import launch_desc, launch_is_mirrored
-
-        delayed = conv1d_stream_bf16_delayed_supported if precision == "bf16" else conv1d_stream_delayed_supported
-        for launch in plan:
-            desc = launch_desc(launch, batch, 8)
-            cls._require_supported(conv1d_stream_mirrored_supported(desc) if launch_is_mirrored(launch) else
-                                   delayed(desc, launch.delay1, launch.delay2), launch.conv)
-
-    @classmethod
-    def _plan_of(cls, model):
-        """``(plan, pqmf or None)`` of a model, from the module geometry alone."""
-        return model.lookahead_plan(), None
-
-    @classmethod
-    def latency_samples_of(cls, model):
-        """Samples every output leaves late, from the module geometry alone (no device, no kernel): the generator's
-        delay times the sub-band count, plus the PQMF's ``K * stream_delay_columns`` for a multi-band model."""
-        plan, pqmf = cls._plan_of(model)
-        return plan[-1].delay if pqmf is None else (plan[-1].delay + pqmf.stream_delay_columns) * pqmf.subbands
+        self.settle_frames = figures.settle_frames
+        self.min_frames = figures.min_frames
+        super().__init__(model, [], figures.batch, use_graph, normalize_before, figures.state_shapes)
 
     def reset(self):
         """Back to start of stream; an unflushed tail is dropped."""
@@ -759,7 +935,7 @@ class _LookaheadStream(_Stream):
         k = len(state_out) - (self._pqmf is not None)  # (a multi-band stream's halves end with the PQMF's history)
         walk = LookaheadWalk(self._plan, None if state_in is None else state_in[:k], state_out[:k], frames_before,
                              total_frames, self.precision)
-        y = self.model.lookahead_forward(c, walk)
+        y = self.model.walk_forward(c, walk)
         if self._pqmf is None:
             return y.reshape(self.batch, -1)
         n_emit = y.shape[-1] if frames_before is None else \
@@ -824,7 +1000,7 @@ class _LookaheadStream(_Stream):
         return y
 
 
-class LookaheadStream(_LookaheadStream):
+class LookaheadStream(_HiFiGANFamily, _LookaheadStream):
     """Stateful streaming synthesis for the standard NON-causal ``HiFiGANGenerator`` (symmetric ``Conv1d``,
     ``ConvTranspose1d(padding = s//2 + s%2)``: every recipe and released checkpoint) with a fixed look-ahead.  Interface,
     emission rule, graph rule, ``flush`` / ``close`` and the precision's scope: :class:`_LookaheadStream`.
@@ -842,29 +1018,11 @@ class LookaheadStream(_LookaheadStream):
     """
 
     def __init__(self, model, batch=1, use_graph=True, normalize_before=False, precision=None):
-        from ..layers.causal_conv import lookahead_state_shapes
-        from ..models import HiFiGANGenerator
-
         precision = self._checked_precision(precision)
-        if not isinstance(model, HiFiGANGenerator):
-            raise ValueError(f"LookaheadStream: {model.__class__.__name__} is not supported (only the non-causal "
-                             "HiFiGANGenerator; a non-causal MelGANGenerator streams through "
-                             "utils.MelGANLookaheadStream, a ParallelWaveGANGenerator through utils.PWGLookaheadStream)")
-        if model.use_causal_conv:
-            raise ValueError("LookaheadStream: the model is causal (use_causal_conv=True) and streams without look-ahead "
-                             "through utils.CausalStream")
-        out_channels = model.output_conv[1].out_channels
-        if out_channels != 1:
-            raise ValueError(f"LookaheadStream: the generator emits {out_channels} channels; the stream returns one "
-                             "waveform per stream (out_channels == 1)")
-        self._refuse_bf16_model(model, precision, "look-ahead stream")
-        batch = self._checked_batch(batch)
-        plan = model.lookahead_plan()  # ValueError: decreasing block delays, a layer without a causal form
-        self._require_plan(plan, batch, precision)
-        super().__init__(model, plan, batch, use_graph, normalize_before, precision, lookahead_state_shapes(plan, batch))
+        super().__init__(model, use_graph, normalize_before, precision, self._streamable(model, batch, None, precision))
 
 
-class MelGANLookaheadStream(_LookaheadStream):
+class MelGANLookaheadStream(_MelGANFamily, _LookaheadStream):
     """Stateful streaming synthesis for the standard NON-causal ``MelGANGenerator`` (reflect padding: every recipe and
     released checkpoint, ``multi_band_melgan.v2`` included) with a fixed look-ahead.  Interface, emission rule, graph
     rule and ``flush`` / ``close``: :class:`_LookaheadStream`; the whole-utterance forward is ``forward`` /
@@ -888,61 +1046,14 @@ class MelGANLookaheadStream(_LookaheadStream):
     """
 
     def __init__(self, model, batch=1, use_graph=True, normalize_before=False, precision=None):
-        from ..layers.causal_conv import lookahead_settle_frames, lookahead_state_shapes, mirrored_min_frames
-
-        precision = self._checked_precision(precision, "the mirrored form of the streaming kernel, which the reflect-padded "
-                                            "layers run, does not exist with bf16 operands yet")
-        plan, pqmf, out_channels = self._checked_model(model)
-        batch = self._checked_batch(batch)
-        self._require_plan(plan, batch, precision)
-        self.pqmf = pqmf
-        self.subbands = out_channels
-        super().__init__(model, plan, batch, use_graph, normalize_before, precision, lookahead_state_shapes(plan, batch),
-                         pqmf, lookahead_settle_frames(plan), mirrored_min_frames(plan))
-
-    @classmethod
-    def _checked_model(cls, model):
-        """The refusals that need no device, in order: the class, a causal model, the padding and the layer geometry (the
-        plan), the sub-bands, a bf16 model -> ``(plan, pqmf or None, out_channels)``."""
-        from ..models import MelGANGenerator
-
-        name = cls.__name__
-        if not isinstance(model, MelGANGenerator):
-            raise ValueError(f"{name}: {model.__class__.__name__} is not supported (only the non-causal MelGANGenerator; "
-                             "HiFiGANGenerator streams through utils.LookaheadStream, ParallelWaveGANGenerator through "
-                             "utils.PWGLookaheadStream)")
-        try:
-            plan = model.lookahead_plan()  # ValueError: causal, a pad other than reflection, an even kernel
-        except ValueError as e:
-            raise ValueError(f"{name}: {e}") from None
-        out_channels = plan[-1].conv.out_channels
-        pqmf = cls._checked_pqmf(model, out_channels)
-        cls._refuse_bf16_model(model, "fp32", "look-ahead stream of a reflect-padded model", has_bf16=False)
-        return plan, pqmf, out_channels
-
-    @classmethod
-    def _plan_of(cls, model):
-        return cls._checked_model(model)[:2]
-
-    @classmethod
-    def settle_frames_of(cls, model):
-        """Frames after which a push has no edge of the utterance in any window or history and emits ``n * up``
-        samples, from the module geometry alone: the plan's ``lookahead_settle_frames`` and ``latency_frames``."""
-        from ..layers.causal_conv import lookahead_settle_frames
-
-        plan, _, k = cls._checked_model(model)
-        up = model.upsample_factor * k
-        return max(lookahead_settle_frames(plan), -(-cls.latency_samples_of(model) // up))
-
-    @classmethod
-    def min_frames_of(cls, model):
-        """The shortest utterance reflection can pad (``layers.causal_conv.mirrored_min_frames`` of the plan)."""
-        from ..layers.causal_conv import mirrored_min_frames
-
-        return mirrored_min_frames(cls._checked_model(model)[0])
+        precision = self._checked_precision(precision, self._NO_BF16)
+        figures = self._streamable(model, batch, None, precision)
+        self.pqmf = figures.pqmf
+        self.subbands = figures.plan[-1].conv.out_channels
+        super().__init__(model, use_graph, normalize_before, precision, figures)
 
 
-class PWGLookaheadStream(_LookaheadStream):
+class PWGLookaheadStream(_PWGFamily, _LookaheadStream):
     """Stateful streaming synthesis for the standard NON-causal ``ParallelWaveGANGenerator`` (every recipe and released
     checkpoint) with a fixed look-ahead; ``push`` also takes, optionally, the noise for the samples of its frames, and
     the whole-utterance forward is ``model.inference``.  Interface, emission rule, graph rule, ``flush`` / ``close`` and
@@ -970,35 +1081,8 @@ class PWGLookaheadStream(_LookaheadStream):
     _takes_noise = _keeps_last = True
 
     def __init__(self, model, batch=1, use_graph=True, normalize_before=False, precision=None):
-        from ..layers.causal_conv import pointwise_desc, pwg_lookahead_state_shapes
-        from ..models import HiFiGANGenerator, ParallelWaveGANGenerator
-
         precision = self._checked_precision(precision)
-        if not isinstance(model, ParallelWaveGANGenerator):
-            hint = "; the non-causal HiFiGANGenerator streams through utils.LookaheadStream" \
-                if isinstance(model, HiFiGANGenerator) else ""
-            raise ValueError(f"PWGLookaheadStream: {model.__class__.__name__} is not supported (only the non-causal "
-                             f"ParallelWaveGANGenerator{hint})")
-        batch = self._checked_batch(batch)
-        reason = model.lookahead_unsupported_reason(batch, precision)
-        if reason is not None:
-            raise ValueError(f"PWGLookaheadStream: {reason}")
-        if model.in_channels != 1 or model.out_channels != 1:
-            raise ValueError(f"PWGLookaheadStream: in_channels / out_channels = {model.in_channels} / {model.out_channels} "
-                             "(the stream takes one noise row and emits one waveform per stream)")
-        self._refuse_bf16_model(model, precision, "look-ahead stream")
-        plan = model.lookahead_plan()
-        if precision == "bf16":  # a bf16 stream never runs a convolution the bf16 kernel refuses in fp32 instead
-            for launch in plan:
-                if launch.kind == "conv_in":
-                    desc = model.upsample_net._lookahead_desc(batch, 8)
-                elif launch.kind in ("first_conv", "last_conv"):
-                    desc = pointwise_desc(launch.module, batch, 8)
-                else:
-                    continue
-                self._require_supported(conv1d_stream_bf16_delayed_supported(desc), launch.module, " with bf16 operands")
-        super().__init__(model, plan, batch, use_graph, normalize_before, precision,
-                         pwg_lookahead_state_shapes(plan, batch))
+        super().__init__(model, use_graph, normalize_before, precision, self._streamable(model, batch, None, precision))
 
     def _run(self, feats, z, state_in, state_out, frames_before=None, total_frames=None):
         """``feats``: (batch, n, C) features; ``z``: (batch, 1, n * up) noise; the rest as in the core."""
@@ -1138,23 +1222,28 @@ class _SlotPool(_Stream):
     """What the pools share (:class:`StreamPool`, :class:`PWGStreamPool`): the schedule, the per-slot host queues and
     ``_take``, what a step uploads -- the table first, then the model's inputs, each a device tensor with two pinned
     twins used in turn (a twin is written again only after its copy of two steps ago has finished) --, the graph entry
-    (ONE pair of graphs, from the first step on) and the step loop.  A subclass validates its model, calls ``__init__``
-    with its plan's figures and the shapes of its inputs, and supplies ``_fill(steps, table, *hosts)``, which writes a
-    step's pinned twins, and ``_run(*inputs, state_in, state_out)``, the model on the device inputs behind the table;
-    ``_before_run(steps)`` is what a step does on the device between the upload and the launches (nothing here)."""
+    (ONE pair of graphs, from the first step on) and the step loop.  A subclass names its family (:class:`_Family`),
+    calls ``__init__`` with the family's figures and the shapes of its inputs, and supplies ``_fill(steps, table,
+    *hosts)``, which writes a step's pinned twins, and ``_run(*inputs, state_in, state_out)``, the model on the device
+    inputs behind the table; ``_before_run(steps)`` is what a step does on the device between the upload and the launches
+    (nothing here)."""
 
-    def __init__(self, model, slots, chunk_frames, use_graph, normalize_before, precision, up, latency_samples,
-                 settle_frames, state_shapes, table_rows, input_shapes):
-        """``table_rows``: rows of the device table (``slots``, or twice that where a second table rides behind the
-        first); ``input_shapes``: of the device inputs behind the table, the features first."""
+    _pooled = True
+
+    def __init__(self, model, use_graph, normalize_before, precision, figures, table_rows, input_shapes):
+        """``figures``: the family's ``_streamable(model, slots, chunk_frames, precision)``; ``table_rows``: rows of the
+        device table (``slots``, or twice that where a second table rides behind the first); ``input_shapes``: of the
+        device inputs behind the table, the features first."""
         from ..ops import SLOT_INTS
 
         self.precision = precision
-        self.slots, self.chunk_frames = slots, chunk_frames
-        self.up = up
-        self.latency_samples = latency_samples
-        self._schedule = SlotSchedule(slots, chunk_frames, up, latency_samples, settle_frames)
-        super().__init__(model, [], slots, use_graph, normalize_before, state_shapes)
+        self.slots, self.chunk_frames = figures.batch, figures.columns
+        self._plan = figures.plan
+        self.up = figures.up
+        self.latency_samples = figures.latency_samples
+        self.settle_frames, self.min_frames = figures.settle_frames, figures.min_frames
+        self._schedule = SlotSchedule(self.slots, self.chunk_frames, self.up, self.latency_samples, self.settle_frames)
+        super().__init__(model, [], self.slots, use_graph, normalize_before, figures.state_shapes)
         self._table = torch.zeros((table_rows, SLOT_INTS), device=self._device, dtype=torch.int32)
         self._inputs = [torch.zeros(shape, device=self._device) for shape in input_shapes]
         self._feats = self._inputs[0]
@@ -1257,7 +1346,51 @@ class _SlotPool(_Stream):
         return out
 
 
-class StreamPool(_SlotPool):
+class _FeaturePool(_SlotPool):
+    """What the pools of the generators that take features alone share (:class:`StreamPool`, :class:`MelGANStreamPool`):
+    a step uploads the table and the features, the tail's padding frames are zeros after normalisation, and the model
+    runs its convolution plan through a ``SlotWalk``; the PQMF history of a multi-band model rides behind the plan's
+    state."""
+
+    def __init__(self, model, use_graph, normalize_before, precision, figures):
+        self._pqmf = figures.pqmf
+        super().__init__(model, use_graph, normalize_before, precision, figures, figures.batch,
+                         [(figures.batch, figures.columns, figures.plan[0].conv.in_channels)])
+        self._columns = torch.arange(self.chunk_frames, device=self._device).reshape(1, 1, -1)
+
+    def feed(self, slot, frames):
+        frames = self._checked_frames(frames)
+        self._schedule.feed(slot, frames.shape[0])
+        self.frames_in += frames.shape[0]
+        if frames.shape[0]:
+            self._queues[slot].append(frames)
+
+    def _fill(self, steps, table, feats):
+        table.copy_(torch.tensor([st.row for st in steps], dtype=torch.int32))
+        for st in steps:
+            if st.action in ("run", "tail", "drain"):
+                self._take(st.slot, st.take, feats[st.slot])
+
+    def _walk_run(self, feats, state_in, state_out):
+        """The generator on one step's inputs, every launch slotted -> (slots, rows, chunk_frames * rate)."""
+        from ..layers.causal_conv import SlotWalk
+
+        c = self._features(feats)
+        if self.normalize_before:  # the padding frames are zeros AFTER normalisation (row[3]: the real frames)
+            c.masked_fill_(self._columns >= self._table[:, 3].reshape(-1, 1, 1), 0.0)
+        walk = SlotWalk(self._plan, state_in, state_out, self._table, self.precision)
+        return self.model.walk_forward(c, walk)
+
+    def _run(self, feats, state_in, state_out):
+        """The generator on one step's inputs, then the slotted PQMF synthesis of a multi-band model -> (slots,
+        chunk_frames * up)."""
+        if self._pqmf is None:
+            return self._walk_run(feats, state_in, state_out).reshape(self.batch, -1)
+        y = self._walk_run(feats, state_in[:-1], state_out[:-1])
+        return self._pqmf.stream_synthesis_slots(y, state_in[-1], state_out[-1], self._table)
+
+
+class StreamPool(_HiFiGANFamily, _FeaturePool):
     """``slots`` look-ahead streams of the standard NON-causal ``HiFiGANGenerator`` in one batch, whose utterances start
     and end whenever they like: what :class:`LookaheadStream` does for ``batch`` lock-step streams, for a server
     (:class:`PWGStreamPool` is the same for the non-causal ``ParallelWaveGANGenerator``).
@@ -1281,64 +1414,12 @@ class StreamPool(_SlotPool):
     ``normalize_before`` and the refusals are :class:`LookaheadStream`'s; ``reset()`` closes every slot."""
 
     def __init__(self, model, slots=16, chunk_frames=8, use_graph=True, normalize_before=False, precision=None):
-        from ..layers.causal_conv import launch_desc, lookahead_settle_frames, lookahead_state_shapes
-        from ..models import HiFiGANGenerator
-
         precision = self._checked_precision(precision)
-        if not isinstance(model, HiFiGANGenerator):
-            raise ValueError(f"StreamPool: {model.__class__.__name__} is not supported (only the non-causal "
-                             "HiFiGANGenerator; a non-causal MelGANGenerator streams in lock step through "
-                             "utils.MelGANLookaheadStream, a ParallelWaveGANGenerator through utils.PWGLookaheadStream)")
-        if model.use_causal_conv:
-            raise ValueError("StreamPool: the model is causal (use_causal_conv=True) and streams in lock step, without "
-                             "look-ahead, through utils.CausalStream")
-        out_channels = model.output_conv[1].out_channels
-        if out_channels != 1:
-            raise ValueError(f"StreamPool: the generator emits {out_channels} channels; a slot returns one waveform "
-                             "(out_channels == 1)")
-        self._refuse_bf16_model(model, precision, "look-ahead stream")
-        slots, chunk_frames = self._checked_sizes(slots, chunk_frames)
-        plan = model.lookahead_plan()  # ValueError: decreasing block delays, a layer without a causal form
-        delayed = conv1d_stream_bf16_delayed_supported if precision == "bf16" else conv1d_stream_delayed_supported
-        for launch in plan:  # (the slotted form covers what the delayed form covers)
-            self._require_supported(delayed(launch_desc(launch, slots, chunk_frames), launch.delay1, launch.delay2),
-                                    launch.conv)
-        self._plan = plan
-        # what a step uploads: the table and the features
-        super().__init__(model, slots, chunk_frames, use_graph, normalize_before, precision, model.upsample_factor,
-                         plan[-1].delay, lookahead_settle_frames(plan), lookahead_state_shapes(plan, slots), slots,
-                         [(slots, chunk_frames, plan[0].conv.in_channels)])
-        self._columns = torch.arange(chunk_frames, device=self._device).reshape(1, 1, -1)
-
-    def feed(self, slot, frames):
-        frames = self._checked_frames(frames)
-        self._schedule.feed(slot, frames.shape[0])
-        self.frames_in += frames.shape[0]
-        if frames.shape[0]:
-            self._queues[slot].append(frames)
-
-    def _fill(self, steps, table, feats):
-        table.copy_(torch.tensor([st.row for st in steps], dtype=torch.int32))
-        for st in steps:
-            if st.action in ("run", "tail", "drain"):
-                self._take(st.slot, st.take, feats[st.slot])
-
-    def _walk_run(self, feats, state_in, state_out):
-        """The generator on one step's inputs, every launch slotted -> (slots, rows, chunk_frames * rate)."""
-        from ..layers.causal_conv import SlotWalk
-
-        c = self._features(feats)
-        if self.normalize_before:  # the padding frames are zeros AFTER normalisation (row[3]: the real frames)
-            c.masked_fill_(self._columns >= self._table[:, 3].reshape(-1, 1, 1), 0.0)
-        walk = SlotWalk(self._plan, state_in, state_out, self._table, self.precision)
-        return self.model.lookahead_forward(c, walk)
-
-    def _run(self, feats, state_in, state_out):
-        """-> (slots, chunk_frames * up)."""
-        return self._walk_run(feats, state_in, state_out).reshape(self.batch, -1)
+        super().__init__(model, use_graph, normalize_before, precision,
+                         self._streamable(model, slots, chunk_frames, precision))
 
 
-class MelGANStreamPool(StreamPool):
+class MelGANStreamPool(_MelGANFamily, _FeaturePool):
     """``slots`` look-ahead streams of the standard NON-causal, reflect-padded ``MelGANGenerator``
     (``multi_band_melgan.v2`` included) in one batch, whose utterances start and end whenever they like: what
     :class:`MelGANLookaheadStream` does for ``batch`` lock-step streams, for a server.  The interface is
@@ -1362,40 +1443,11 @@ class MelGANStreamPool(StreamPool):
     refusals are :class:`MelGANLookaheadStream`'s, for ``slots x chunk_frames``; ``reset()`` closes every slot."""
 
     def __init__(self, model, slots=16, chunk_frames=8, use_graph=True, normalize_before=False, precision=None):
-        from ..layers.causal_conv import lookahead_settle_frames, lookahead_state_shapes, mirrored_min_frames
-
-        precision = self._checked_precision(precision, "the mirrored form of the streaming kernel, which the reflect-padded "
-                                            "layers run, does not exist with bf16 operands yet")
-        # (MelGANLookaheadStream's checks, in its order and with its reasons, under this class's name)
-        plan, pqmf, out_channels = MelGANLookaheadStream._checked_model.__func__(type(self), model)
-        slots, chunk_frames = self._checked_sizes(slots, chunk_frames)
-        _LookaheadStream._require_plan.__func__(type(self), plan, slots, precision)
-        self._plan = plan
-        self.pqmf = pqmf
-        self.subbands = out_channels
-        up = model.upsample_factor * out_channels
-        latency = (plan[-1].delay + (pqmf.stream_delay_columns if pqmf is not None else 0)) * out_channels
-        self.min_frames = mirrored_min_frames(plan)
-        if (self.min_frames - 1) * up > latency:  # (no recipe: a first layer reaches less far than the whole generator)
-            raise ValueError(f"MelGANStreamPool: an utterance of {self.min_frames - 1} frame(s), too short for reflection, "
-                             f"would emit samples before its end is known (latency {latency} samples, {up} per frame)")
-        self.settle_frames = max(lookahead_settle_frames(plan), -(-latency // up))  # MelGANLookaheadStream.settle_frames_of
-        # what a step uploads: the table and the features; the PQMF history rides behind the plan's state
-        _SlotPool.__init__(self, model, slots, chunk_frames, use_graph, normalize_before, precision, up, latency,
-                           self.settle_frames, lookahead_state_shapes(plan, slots)
-                           + ([pqmf.history_shape(slots)] if pqmf is not None else []), slots,
-                           [(slots, chunk_frames, plan[0].conv.in_channels)])
-        self._columns = torch.arange(chunk_frames, device=self._device).reshape(1, 1, -1)
-
-    @classmethod
-    def state_bytes_of(cls, model, slots):
-        """``state_bytes`` of a pool of ``slots``, from the plan's shapes alone (no device): both ping-pong halves of
-        every launch's state and, for a multi-band model, of the PQMF history."""
-        from ..layers.causal_conv import lookahead_state_shapes
-
-        plan, pqmf, _ = MelGANLookaheadStream._checked_model.__func__(cls, model)
-        shapes = lookahead_state_shapes(plan, int(slots)) + ([pqmf.history_shape(int(slots))] if pqmf is not None else [])
-        return 2 * 4 * sum(b * ch * cols for b, ch, cols in shapes)
+        precision = self._checked_precision(precision, self._NO_BF16)
+        figures = self._streamable(model, slots, chunk_frames, precision)
+        self.pqmf = figures.pqmf
+        self.subbands = figures.plan[-1].conv.out_channels
+        super().__init__(model, use_graph, normalize_before, precision, figures)
 
     def end(self, slot):
         st = self._schedule._of(slot, "end")
@@ -1408,16 +1460,8 @@ class MelGANStreamPool(StreamPool):
                                f"slot {slot} is closed and has emitted nothing")
         self._schedule.end(slot)
 
-    def _run(self, feats, state_in, state_out):
-        """The generator on one step's inputs, every launch slotted, then the slotted PQMF synthesis of a multi-band
-        model -> (slots, chunk_frames * up)."""
-        if self.pqmf is None:
-            return self._walk_run(feats, state_in, state_out).reshape(self.batch, -1)
-        y = self._walk_run(feats, state_in[:-1], state_out[:-1])
-        return self.pqmf.stream_synthesis_slots(y, state_in[-1], state_out[-1], self._table)
 
-
-class PWGStreamPool(_SlotPool):
+class PWGStreamPool(_PWGFamily, _SlotPool):
     """``slots`` look-ahead streams of the standard NON-causal ``ParallelWaveGANGenerator`` in one batch, whose
     utterances start and end whenever they like: what :class:`PWGLookaheadStream` does for ``batch`` lock-step streams,
     for a server.  The interface is :class:`StreamPool`'s -- ``open()``, ``feed(slot, frames, noise=None)``,
@@ -1443,53 +1487,15 @@ class PWGStreamPool(_SlotPool):
     :class:`PWGLookaheadStream`'s, for ``slots x chunk_frames``; ``reset()`` closes every slot."""
 
     def __init__(self, model, slots=16, chunk_frames=8, use_graph=True, normalize_before=False, precision=None):
-        from ..layers.causal_conv import pointwise_desc, pwg_lookahead_state_shapes
-        from ..models import HiFiGANGenerator, ParallelWaveGANGenerator
-
         precision = self._checked_precision(precision)
-        if not isinstance(model, ParallelWaveGANGenerator):
-            hint = "; the non-causal HiFiGANGenerator pools through utils.StreamPool" \
-                if isinstance(model, HiFiGANGenerator) else ""
-            raise ValueError(f"PWGStreamPool: {model.__class__.__name__} is not supported (only the non-causal "
-                             f"ParallelWaveGANGenerator{hint})")
-        slots, chunk_frames = self._checked_sizes(slots, chunk_frames)
-        reason = model.lookahead_unsupported_reason(slots, precision)
-        if reason is not None:
-            raise ValueError(f"PWGStreamPool: {reason}")
-        if model.in_channels != 1 or model.out_channels != 1:
-            raise ValueError(f"PWGStreamPool: in_channels / out_channels = {model.in_channels} / {model.out_channels} "
-                             "(a slot takes one noise row and returns one waveform)")
-        self._refuse_bf16_model(model, precision, "look-ahead stream")
-        plan = model.lookahead_plan()
-        delayed = conv1d_stream_bf16_delayed_supported if precision == "bf16" else conv1d_stream_delayed_supported
-        for launch in plan:  # (the slotted forms cover what the delayed forms cover)
-            if launch.kind == "conv_in":
-                desc = model.upsample_net._lookahead_desc(slots, chunk_frames)
-            elif launch.kind in ("first_conv", "last_conv"):
-                desc = pointwise_desc(launch.module, slots, chunk_frames * launch.rate)
-            else:
-                continue
-            self._require_supported(delayed(desc), launch.module,
-                                    " with bf16 operands" if precision == "bf16" else "")
-        self._plan = plan
-        up, latency = model.upsample_factor, plan[-1].delay
+        figures = self._streamable(model, slots, chunk_frames, precision)
+        slots, chunk_frames, plan = figures.batch, figures.columns, figures.plan
         # conv_in with a context window keeps a history: the second table rides behind the first
         self._two_tables = plan[0].kind == "conv_in" and bool(plan[0].state)
-        channels = model.aux_channels
         # what a step uploads: the table(s), the features and the noise
-        super().__init__(model, slots, chunk_frames, use_graph, normalize_before, precision, up, latency,
-                         -(-latency // up), pwg_lookahead_state_shapes(plan, slots),
-                         slots * (2 if self._two_tables else 1),
-                         [(slots, chunk_frames, channels), (slots, 1, chunk_frames * up)])
+        super().__init__(model, use_graph, normalize_before, precision, figures, slots * (2 if self._two_tables else 1),
+                         [(slots, chunk_frames, model.aux_channels), (slots, 1, chunk_frames * figures.up)])
         self._noise = self._inputs[1]
-
-    @classmethod
-    def state_bytes_of(cls, model, slots):
-        """``state_bytes`` of a pool of ``slots``, from the plan's shapes alone (no device): both ping-pong halves of
-        every launch's state, fp32 in either precision."""
-        from ..layers.causal_conv import pwg_lookahead_state_shapes
-
-        return 2 * 4 * sum(b * ch * cols for b, ch, cols in pwg_lookahead_state_shapes(model.lookahead_plan(), int(slots)))
 
     def reset(self):
         super().reset()
