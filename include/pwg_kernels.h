@@ -1093,6 +1093,25 @@ int pwg_softmax_gate_forward(const float* z, float* y, int32_t batch, int32_t ch
                              int32_t use_softmax, void* stream);
 int pwg_softmax_gate_backward(const float* z, const float* dy, float* dz, int32_t batch, int32_t channels,
                               int64_t t, int32_t use_softmax, void* stream);
+/* The ragged forms of the four forwards above (csrc/tade_ragged.hip): the TADE stages of tade_res_block.py over a batch
+ * whose items have their own lengths, the batched form of the loop of bin/decode.py:214-243.  frames: device int32
+ * (batch,); item b ends at column e = min(frames[b] * rate, t) of its rows (rate_out and t = t_in * scale for the two
+ * that upsample: the table counts columns of the OUTPUT), t stays the row stride.  Nothing at or past e is read (NaN
+ * may sit there), every column in [e, t) is stored as +0.0f, e == 0 stores an all-zero item, a workgroup whose columns
+ * all lie at or past e only stores zeros, and the columns < e are bit for bit what the plain entry gives on the item
+ * alone, a contiguous (1, channels, e) tensor; the instance norm's statistics run over [0, e) in the plain kernel's
+ * order and it keeps no mean / rstd (forward only).  add may be NULL.  Nothing on the host depends on the table's
+ * values: a captured launch serves every set of lengths.  Refused as pwg_zero_tail refuses (a message in
+ * pwg_last_error, nothing launched): NULL or misaligned (4 B) pointers, rate <= 0, batch or channels outside
+ * 1 .. 65535, rows of 2^31 columns or more.  Additive: pwg_abi_version() stays 15. */
+int pwg_instance_norm_ragged(const float* x, float* y, const int32_t* frames, int32_t batch, int32_t channels,
+                             int32_t t, int32_t rate, float eps, void* stream);
+int pwg_upsample_nearest_ragged(const float* x, const float* add, float* y, const int32_t* frames, int32_t batch,
+                                int32_t channels, int32_t t_in, int32_t scale, int32_t rate_out, void* stream);
+int pwg_tade_modulate_ragged(const float* xn, const float* cg, float* y, const int32_t* frames, int32_t batch,
+                             int32_t channels, int32_t t_in, int32_t scale, int32_t rate_out, void* stream);
+int pwg_softmax_gate_ragged(const float* z, float* y, const int32_t* frames, int32_t batch, int32_t channels,
+                            int64_t t, int32_t rate, int32_t use_softmax, void* stream);
 
 /* ---- UHiFiGAN pieces (models/uhifigan.py) ---- */
 /* One operand of torch.cat(dim=1) (uhifigan.py:286): y (batch, c_dst, t)[:, c_off : c_off + c_src] = x

@@ -278,6 +278,10 @@ SIGNATURES = {
     "pwg_tade_modulate_backward": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "pwg_softmax_gate_forward": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i64, _i32, _vp]),
     "pwg_softmax_gate_backward": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _i64, _i32, _vp]),
+    "pwg_instance_norm_ragged": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp]),
+    "pwg_upsample_nearest_ragged": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "pwg_tade_modulate_ragged": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "pwg_softmax_gate_ragged": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _i64, _i32, _i32, _vp]),
     "pwg_gather_crop": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32,
                                        _vp]),
     "pwg_normalize_transpose": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),

@@ -5,7 +5,9 @@ A non-causal HiFi-GAN checkpoint is decoded ``--batch-size`` utterances per forw
 ``utils.RaggedSynthesizer`` -- every utterance exactly what ``model.inference`` gives for it alone --
 a non-causal, reflect-padded (multi-band) MelGAN checkpoint through ``utils.MelGANRaggedSynthesizer`` (s9.5), and a
 Parallel WaveGAN checkpoint whose ``ragged_unsupported_reason()`` is None (the non-causal v1 geometry) through
-``utils.PWGRaggedSynthesizer`` (s9.6), its noise drawn on the device; every other supported generator -- a causal
+``utils.PWGRaggedSynthesizer`` (s9.6), its noise drawn on the device, and a StyleMelGAN checkpoint with one output
+channel through ``utils.StyleMelGANRaggedSynthesizer`` (s9.7), its noise drawn on the host utterance by utterance as
+``model.inference`` draws it; every other supported generator -- a causal
 Parallel WaveGAN, one with a MelGAN upsampler or other channel widths -- runs the reference's loop over
 ``model.inference`` (decode.py:214-243).  The float ->
 int16 step is ``utils.to_pcm16`` on the device and the files are written with the standard library's ``wave`` module.
@@ -77,8 +79,9 @@ def main(argv=None):
     import yaml
 
     from ..datasets import MelDataset
-    from ..models import HiFiGANGenerator, MelGANGenerator, ParallelWaveGANGenerator
-    from ..utils import MelGANRaggedSynthesizer, PWGRaggedSynthesizer, RaggedSynthesizer, load_model
+    from ..models import HiFiGANGenerator, MelGANGenerator, ParallelWaveGANGenerator, StyleMelGANGenerator
+    from ..utils import (MelGANRaggedSynthesizer, PWGRaggedSynthesizer, RaggedSynthesizer, StyleMelGANRaggedSynthesizer,
+                         load_model)
     from ..utils.streaming import to_pcm16
 
     args = _parser().parse_args(argv)
@@ -125,9 +128,11 @@ def main(argv=None):
         and model.output_conv[1].out_channels == 1
     ragged_melgan = isinstance(model, MelGANGenerator) and _melgan_is_ragged(model)
     ragged_pwg = isinstance(model, ParallelWaveGANGenerator) and model.ragged_unsupported_reason() is None
+    ragged_style = isinstance(model, StyleMelGANGenerator) and model.output_conv[0].out_channels == 1
     total_rtf, n_done = 0.0, 0
-    if ragged or ragged_melgan or ragged_pwg:
-        cls = RaggedSynthesizer if ragged else MelGANRaggedSynthesizer if ragged_melgan else PWGRaggedSynthesizer
+    if ragged or ragged_melgan or ragged_pwg or ragged_style:
+        cls = RaggedSynthesizer if ragged else MelGANRaggedSynthesizer if ragged_melgan else \
+            PWGRaggedSynthesizer if ragged_pwg else StyleMelGANRaggedSynthesizer
         synth = cls(model, max_batch=args.batch_size)
         logging.info(f"{gtype}: {args.batch_size} utterances of their own lengths per forward "
                      f"({type(synth).__name__}).")

@@ -53,6 +53,22 @@ class TADELayer(torch.nn.Module):
         cg = self.gated_conv[0](c)
         return Fn.TadeModulateFn.apply(xn, cg, f), c
 
+    def forward_ragged(self, x, c, frames, rate):
+        """``forward`` over a ragged batch (inference): ``frames`` a device int32 (B,), ``rate`` the
+        columns of ``x`` per unit of the table, so item ``b`` of ``x`` and ``c`` ends at ``frames[b] * rate`` and of the
+        results at ``frames[b] * rate * f``.  ``x`` and ``c`` must be exactly zero from their item's end on and the
+        results are: the instance norm takes its statistics over the item alone, and ``ops.zero_tail`` runs behind
+        ``aux_conv``, whose output the zero-padded ``gated_conv`` and the next layer read past the item's end."""
+        from .. import ops
+
+        f = self.upsample_factor
+        xn = ops.instance_norm_ragged(x, frames, rate, self.norm_eps)
+        if f != 1:
+            c = ops.upsample_nearest_ragged(c, f, frames, rate * f)
+        c = ops.zero_tail(self.aux_conv[0](c), frames, rate * f)
+        cg = self.gated_conv[0](c)  # (read below the item's end only)
+        return ops.tade_modulate_ragged(xn, cg, f, frames, rate * f), c
+
 
 class TADEResBlock(torch.nn.Module):
     def __init__(self, in_channels=64, aux_channels=80, kernel_size=9, dilation=2, bias=True, upsample_factor=2,
@@ -81,3 +97,19 @@ class TADEResBlock(torch.nn.Module):
         x = Fn.SoftmaxGateFn.apply(self.gated_conv2(x), self.use_softmax)
         # upsample(residual) + x in one launch
         return Fn.UpsampleNearestFn.apply(residual, self.upsample_factor, x), c
+
+    def forward_ragged(self, x, c, frames, rate):
+        """``forward`` over a ragged batch, the same modules, order and fusions (inference).  Item ``b``
+        of ``x`` and ``c`` ends at ``frames[b] * rate`` and is exactly zero from there on, and so are the two results
+        at ``frames[b] * rate * f``: a zero-padded convolution then reads past an item's end what it reads past the
+        end of the item alone.  The outputs of ``gated_conv1`` / ``gated_conv2`` need no zero-tail pass: the ragged gate
+        reads nothing at or past an item's end and stores the zeros itself."""
+        from .. import ops
+
+        f = self.upsample_factor
+        residual = x
+        x, c = self.tade1.forward_ragged(x, c, frames, rate)
+        x = ops.softmax_gate_ragged(self.gated_conv1(x), self.use_softmax, frames, rate)
+        x, c = self.tade2.forward_ragged(x, c, frames, rate)
+        x = ops.softmax_gate_ragged(self.gated_conv2(x), self.use_softmax, frames, rate * f)
+        return ops.upsample_nearest_ragged(residual, f, frames, rate * f, add=x), c

@@ -92,6 +92,47 @@ class StyleMelGANGenerator(torch.nn.Module, _NormMixin):
             x, c = block(x, c)
         return self.output_conv[0](x, post_act="tanh")
 
+    @torch.no_grad()
+    def forward_ragged(self, c, z, segments):
+        """``forward`` over utterances of different lengths in one batch (the batched form of the loop of
+        bin/decode.py:214-243 of the reference).  The unit of length is the noise segment, ``F =
+        noise_upsample_factor`` frames: ``c`` (B, aux_channels, S_max * F), ``z`` (B, in_channels, S_max), ``segments`` a
+        device int32 tensor (B,) with ``0 <= segments[b] <= S_max`` -> (B, out_channels, S_max * F * upsample_factor) in
+        which item ``b`` holds, up to ``segments[b] * F * upsample_factor``, what ``forward(c_b, z_b)`` gives on its
+        ``segments[b] * F`` frames and ``segments[b]`` noise columns alone, and exact zeros past that (0 segments: an
+        unused item, all zeros).  ``c`` and ``z`` are not written and may hold anything past an item's end, NaN
+        included: copies are zero-tailed first.
+
+        Every ``InstanceNorm1d`` must see the item alone, so padding is not an approximation here.  Between two
+        launches an item is exactly zero from its end on: ``ops.zero_tail`` runs behind every transposed convolution
+        of the noise upsampler (its fused LeakyReLU of the bias is not zero), behind each TADE layer's ``aux_conv`` and
+        behind the output convolution; everything else is a ragged kernel of csrc/tade_ragged.hip.  Nothing on the host
+        reads the table: one captured graph per (B, S_max) serves every set of lengths."""
+        from .. import ops
+
+        name = "StyleMelGANGenerator.forward_ragged"
+        F = self.noise_upsample_factor
+        if c.dim() != 3 or z.dim() != 3 or c.shape[0] != z.shape[0]:
+            raise ValueError(f"{name}: expected (B, aux_channels, S_max * {F}) features and (B, in_channels, S_max) "
+                             f"noise, got {tuple(c.shape)} and {tuple(z.shape)}")
+        if c.shape[2] != z.shape[2] * F:
+            raise ValueError(f"{name}: {z.shape[2]} noise columns take {z.shape[2] * F} frames "
+                             f"(noise_upsample_factor = {F}), got {c.shape[2]}")
+        ops._require_device(c, z)
+        ops._require_frames(segments, c.shape[0], name)
+        rate = 1
+        x = ops.zero_tail(z.clone(), segments, rate)
+        mods = list(self.noise_upsample)
+        for i in range(0, len(mods), 2):
+            act = mods[i + 1]
+            rate *= mods[i].stride
+            x = ops.zero_tail(mods[i](x, post_act=act.kind, post_slope=act.slope), segments, rate)
+        c = ops.zero_tail(c.clone(), segments, rate)
+        for block in self.blocks:
+            x, c = block.forward_ragged(x, c, segments, rate)
+            rate *= block.upsample_factor
+        return ops.zero_tail(self.output_conv[0](x, post_act="tanh"), segments, rate)
+
     def register_stats(self, stats):
         from ..utils import load_stats
 

@@ -741,6 +741,68 @@ def mirror_tail(y, frames, rate, pad):
     return y
 
 
+def _ragged_3d(what, frames, *tensors):
+    """The checks the ragged TADE wrappers share: contiguous fp32 device (B, C, T) tensors and the table."""
+    _require_device(*tensors)
+    for t in tensors:
+        if t is not None and t.dim() != 3:
+            raise RuntimeError(f"{what}: expected a (B, C, T) tensor, got {tuple(t.shape)}")
+    _require_frames(frames, tensors[0].shape[0], what)
+
+
+def instance_norm_ragged(x, frames, rate, eps=1e-5):
+    """``InstanceNorm1d(affine=False)`` over a ragged batch (csrc/tade_ragged.hip): the statistics of item
+    ``b`` of ``x`` (B, C, T) run over its columns ``[0, e)``, ``e = min(frames[b] * rate, T)``; below ``e`` the result is
+    bit for bit the plain kernel on the item alone, at and past ``e`` it is ``+0.0`` (nothing there is read).  Forward
+    only."""
+    _ragged_3d("instance_norm_ragged", frames, x)
+    y = torch.empty_like(x)
+    b, c, t = x.shape
+    _lib.check(_lib.lib().pwg_instance_norm_ragged(_ptr(x), _ptr(y), _ptr(frames), b, c, t, int(rate), float(eps),
+                                                   _stream()), "instance_norm_ragged")
+    return y
+
+
+def upsample_nearest_ragged(x, scale, frames, rate_out, add=None):
+    """``nearest_upsample(x, scale) (+ add)`` over a ragged batch: x (B, C, T) -> (B, C, T * scale) whose item ``b``
+    ends at ``e = min(frames[b] * rate_out, T * scale)`` (``rate_out``: OUTPUT columns per frame); zeros from ``e`` on,
+    nothing of ``x`` or ``add`` read there."""
+    _ragged_3d("upsample_nearest_ragged", frames, x, add)
+    b, c, t = x.shape
+    y = torch.empty((b, c, t * int(scale)), device=x.device, dtype=torch.float32)
+    if add is not None and add.shape != y.shape:
+        raise RuntimeError(f"upsample_nearest_ragged: add must be {tuple(y.shape)}, got {tuple(add.shape)}")
+    _lib.check(_lib.lib().pwg_upsample_nearest_ragged(_ptr(x), _ptr(add), _ptr(y), _ptr(frames), b, c, t, int(scale),
+                                                      int(rate_out), _stream()), "upsample_nearest_ragged")
+    return y
+
+
+def tade_modulate_ragged(xn, cg, scale, frames, rate_out):
+    """``cg[:, :C] * nearest_upsample(xn, scale) + cg[:, C:]`` over a ragged batch: xn (B, C, T), cg (B, 2C, T * scale) ->
+    (B, C, T * scale), item ``b`` ending at ``min(frames[b] * rate_out, T * scale)``; zeros from there on."""
+    _ragged_3d("tade_modulate_ragged", frames, xn, cg)
+    b, c, t = xn.shape
+    if tuple(cg.shape) != (b, 2 * c, t * int(scale)):
+        raise RuntimeError(f"tade_modulate_ragged: cg must be {(b, 2 * c, t * int(scale))}, got {tuple(cg.shape)}")
+    y = torch.empty((b, c, t * int(scale)), device=xn.device, dtype=torch.float32)
+    _lib.check(_lib.lib().pwg_tade_modulate_ragged(_ptr(xn), _ptr(cg), _ptr(y), _ptr(frames), b, c, t, int(scale),
+                                                   int(rate_out), _stream()), "tade_modulate_ragged")
+    return y
+
+
+def softmax_gate_ragged(z, use_softmax, frames, rate):
+    """The gate of ``TADEResBlock`` over a ragged batch: z (B, 2C, T) -> (B, C, T), softmax over channels (or sigmoid) of
+    the first half x tanh of the second below ``min(frames[b] * rate, T)``, zeros from there on."""
+    _ragged_3d("softmax_gate_ragged", frames, z)
+    b, c2, t = z.shape
+    if c2 % 2:
+        raise RuntimeError(f"softmax_gate_ragged: expected an even number of channels, got {c2}")
+    y = torch.empty((b, c2 // 2, t), device=z.device, dtype=torch.float32)
+    _lib.check(_lib.lib().pwg_softmax_gate_ragged(_ptr(z), _ptr(y), _ptr(frames), b, c2 // 2, t, int(rate),
+                                                  int(bool(use_softmax)), _stream()), "softmax_gate_ragged")
+    return y
+
+
 def resunit_split_ragged_supported(desc, rate):
     """Does the ragged form of the split-operand residual unit cover this geometry at ``rate`` columns per frame?
     :func:`resunit_split_supported` plus ``rate % 4 == 0``.  Host logic only; ``_lib.lib().pwg_last_error()`` names the

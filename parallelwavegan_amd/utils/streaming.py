@@ -1922,3 +1922,114 @@ class PWGRaggedSynthesizer(_RaggedSynthesizer):
     def synthesize_many_pcm16(self, feats, normalize_before=False, noises=None):
         """:meth:`synthesize_many` through the float -> PCM16 conversion on the device: int16 tensors."""
         return self._synthesize(feats, normalize_before, to_pcm16, self._checked_noises(feats, noises))
+
+
+class StyleMelGANRaggedSynthesizer(_RaggedSynthesizer):
+    """:class:`RaggedSynthesizer` for ``StyleMelGANGenerator``: the same plan, one upload per group, graphs (one per
+    shape, ``max_graph_shapes`` kept) and recapture on a parameter change, on ``model.forward_ragged``.
+    Every TADE layer starts with an instance norm over the whole time axis, so a padded batch is another signal, not an
+    approximation; the ragged forward takes each item's statistics over the item alone.
+
+    The unit of length is the noise segment, ``F = model.noise_upsample_factor`` frames: ``inference`` runs an utterance
+    of ``T`` frames on ``ceil(T / F)`` noise columns and ``ceil(T / F) * F`` frames, the last frame replicated, and cuts
+    the audio to ``T * upsample_factor`` samples.  So the plan works in segments -- a group's ``t_pad`` is ``S_pad``, its
+    longest item's segment count rounded up to ``bucket_segments``, and its ``frames`` are segment counts --, the host
+    replicates each item's last frame up to its own segment boundary (:meth:`block_layout`) and cuts each result.
+
+    The noise: ``synthesize_many(feats, noises=...)`` takes one ``(in_channels, n_i)`` tensor or array per utterance, ``n_i
+    = ceil(T_i / F)``, and item ``i`` uses exactly that noise (``model.inference(c, z=...)`` to summation order);
+    ``noises=None`` draws on the host, per utterance in input order, with ``torch.randn(1, in_channels, n_i)`` -- the call
+    ``inference`` makes, so a seeded run reproduces a seeded loop of ``inference`` calls.  fp32 only: the modules'
+    ``precision`` is not touched."""
+
+    def __init__(self, model, max_batch=16, bucket_segments=2, use_graph=True):
+        from ..models import HiFiGANGenerator, MelGANGenerator, ParallelWaveGANGenerator, StyleMelGANGenerator
+
+        name = type(model).__name__
+        other = "utils.ChunkedSynthesizer batches the equal-shaped chunks of any mel-only generator"
+        if not isinstance(model, StyleMelGANGenerator):
+            right = {HiFiGANGenerator: "utils.RaggedSynthesizer", MelGANGenerator: "utils.MelGANRaggedSynthesizer",
+                     ParallelWaveGANGenerator: "utils.PWGRaggedSynthesizer"}
+            hint = next((f"{syn} batches its utterances of different lengths; " for cls, syn in right.items()
+                         if isinstance(model, cls)), "")
+            raise ValueError(f"StyleMelGANRaggedSynthesizer: {name} is not supported (only StyleMelGANGenerator; "
+                             f"{hint}{other})")
+        conv = model.output_conv[0]
+        if conv.out_channels != 1:
+            raise ValueError(f"StyleMelGANRaggedSynthesizer: this {name} emits {conv.out_channels} channels; an item "
+                             f"returns one waveform ({other})")
+        if int(bucket_segments) < 1:
+            raise ValueError("StyleMelGANRaggedSynthesizer: max_batch and bucket_segments must be >= 1")
+        self.segment_frames = model.noise_upsample_factor
+        self.noise_channels = model.in_channels
+        # the widest row: the 2 * channels rows of a gated convolution at the output rate
+        self._setup(model, max_batch, bucket_segments, use_graph, model.blocks[0].tade1.aux_conv[0].in_channels,
+                    model.upsample_factor, 2 * conv.in_channels * model.upsample_factor)
+        self.bucket_segments = self.bucket_frames
+
+    def segments_of(self, n_frames):
+        """Noise columns of an utterance of ``n_frames`` frames: ``ceil(n_frames / F)``, as ``inference`` draws them."""
+        return -(-int(n_frames) // self.segment_frames)
+
+    @classmethod
+    def plan_segments(cls, lengths, segment_frames, max_batch=16, bucket_segments=2, max_frames=None):
+        """Pure host logic: ``lengths`` (FRAMES per utterance) -> :meth:`plan_groups` over their segment counts
+        ``ceil(n / segment_frames)``: a group's ``frames`` are segments per item, its ``t_pad`` is ``S_pad`` and
+        ``padded_fraction`` is the share of the ``max_batch * S_pad`` segment slots that hold no segment.  ValueError
+        for an empty or over-long item, counted in frames."""
+        cls.plan_groups(lengths, 1, 1, max_frames, who=cls.__name__)  # (only its checks)
+        return cls.plan_groups([-(-int(n) // int(segment_frames)) for n in lengths], max_batch, bucket_segments,
+                               who=cls.__name__)
+
+    def plan(self, lengths):
+        """:meth:`plan_segments` with this synthesizer's ``F``, ``max_batch``, ``bucket_segments`` and ``max_frames``."""
+        return self.plan_segments(lengths, self.segment_frames, self.max_batch, self.bucket_segments, self.max_frames)
+
+    def _forward(self, c, segments, z):
+        return self.model.forward_ragged(c, z, segments)
+
+    @staticmethod
+    def block_layout(group, feats, segment_frames, max_batch, channels):
+        """Pure host logic: one group's block (max_batch, S_pad * F, C), ``F = segment_frames``: item j's frames first,
+        its last frame replicated up to its segment boundary ``segments_j * F`` (``Fn.pad1d(..., "replicate")`` of the
+        item alone in ``inference``), zeros behind."""
+        F = int(segment_frames)
+        block = torch.zeros((max_batch, group.t_pad * F, channels))
+        for j, i in enumerate(group.indices):
+            n = feats[i].shape[0]
+            block[j, :n] = feats[i]
+            block[j, n:group.frames[j] * F] = feats[i][n - 1]
+        return block
+
+    def _host_block(self, group, feats):
+        return self.block_layout(group, feats, self.segment_frames, self.max_batch, self.channels).pin_memory()
+
+    def _run_group(self, c, segments, group, noises):
+        z = torch.zeros((self.max_batch, self.noise_channels, group.t_pad)).pin_memory()
+        for j, i in enumerate(group.indices):
+            z[j, :, :noises[i].shape[1]] = noises[i]
+        return self._run(c, segments, z.to(self._device, non_blocking=True))
+
+    def _checked_noises(self, feats, noises):
+        lengths = [len(f) for f in feats]
+        if noises is None:  # inference's own draw, per utterance in input order
+            return [torch.randn(1, self.noise_channels, self.segments_of(n), dtype=torch.float)[0] for n in lengths]
+        noises = [torch.as_tensor(z, dtype=torch.float32).cpu() for z in noises]
+        if len(noises) != len(feats):
+            raise ValueError(f"StyleMelGANRaggedSynthesizer: {len(noises)} noises for {len(feats)} utterances")
+        for i, (n, z) in enumerate(zip(lengths, noises)):
+            want = (self.noise_channels, self.segments_of(n))
+            if tuple(z.shape) != want:
+                raise ValueError(f"StyleMelGANRaggedSynthesizer: item {i}: expected {want} noise for {n} frames, got "
+                                 f"{tuple(z.shape)}")
+        return noises
+
+    def synthesize_many(self, feats, normalize_before=False, noises=None):
+        """feats: list of ``(T_i, C)`` tensors / arrays -> list of ``(T_i * up,)`` fp32 device tensors, in input order.
+        ``noises``: None (drawn on the host as ``inference`` draws) or one ``(in_channels, ceil(T_i / F))`` tensor / array
+        per utterance."""
+        return self._synthesize(feats, normalize_before, lambda y: y, self._checked_noises(feats, noises))
+
+    def synthesize_many_pcm16(self, feats, normalize_before=False, noises=None):
+        """:meth:`synthesize_many` through the float -> PCM16 conversion on the device: int16 tensors."""
+        return self._synthesize(feats, normalize_before, to_pcm16, self._checked_noises(feats, noises))

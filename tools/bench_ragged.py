@@ -1,6 +1,6 @@
 """16 utterances of different lengths through HiFi-GAN V1: ``utils.RaggedSynthesizer`` against the other ways to run
 them, alternating in one process.  GPU box only.
-usage: bench_ragged.py [--precision fp32|bf16] [--model hifigan|melgan|pwg] [--multiband] [--json FILE]
+usage: bench_ragged.py [--precision fp32|bf16] [--model hifigan|melgan|pwg|style_melgan] [--multiband] [--json FILE]
 ``--model melgan``: the same lengths and contenders through ``utils.MelGANRaggedSynthesizer`` on
 ``melgan.v1`` (the class defaults) or, with ``--multiband``, on the ``multi_band_melgan.v2`` generator with its PQMF
 attached; seeded weights, fp32 only.
@@ -24,7 +24,12 @@ on the host), ``inference_noise_given`` = the same calls with the noise already 
 (host noises uploaded with the group).  ``ChunkedSynthesizer`` is no contender: it runs mel-only generators, and this
 forward takes noise.  On the padded block: the plain forward (inexact) against ``forward_ragged``, graph replays; their
 gap is what the dependent table read costs and the skipped tiles save; the profiler names the ragged layer launches and
-the zero_tail launches."""
+the zero_tail launches.
+``--model style_melgan`` (fp32): the same lengths through ``utils.StyleMelGANRaggedSynthesizer`` on the
+default ``StyleMelGANGenerator`` (seeded weights).  Contenders: ragged16 / ragged8 and ``inference`` = 16
+``model.inference(c)`` calls as ``parallel-wavegan-decode`` made them, every one drawing its noise on the host as
+``inference`` does.  On the padded block: the plain forward (inexact: its instance norms see the padding) against
+``forward_ragged``, graph replays, and the launches of one forward of each kind."""
 import argparse
 import json
 import os
@@ -38,9 +43,10 @@ import torch
 from parallelwavegan_amd import ops
 from parallelwavegan_amd.graphs import GraphedInference
 from parallelwavegan_amd.layers import PQMF
-from parallelwavegan_amd.models import HiFiGANGenerator, MelGANGenerator, ParallelWaveGANGenerator
+from parallelwavegan_amd.models import (HiFiGANGenerator, MelGANGenerator, ParallelWaveGANGenerator,
+                                        StyleMelGANGenerator)
 from parallelwavegan_amd.utils import (ChunkedSynthesizer, MelGANRaggedSynthesizer, PWGRaggedSynthesizer,
-                                       RaggedSynthesizer, set_inference_precision)
+                                       RaggedSynthesizer, StyleMelGANRaggedSynthesizer, set_inference_precision)
 from parallelwavegan_amd.utils.streaming import receptive_field_frames
 from tests.golden import synth
 
@@ -194,10 +200,96 @@ def main_pwg(args, dev):
             json.dump(out, f, indent=1)
 
 
+def main_style_melgan(args, dev):
+    """``--model style_melgan``: see the module docstring."""
+    model = StyleMelGANGenerator()
+    model.load_state_dict(synth.synth_state_dict(model.state_dict(), seed=12, g_scale=0.8))
+    model.remove_weight_norm()
+    model = model.to(dev).eval()
+    up, sf = model.upsample_factor, model.noise_upsample_factor
+    gen = torch.Generator().manual_seed(1)
+    feats = [torch.randn(n, 80, generator=gen) for n in LENGTHS]
+    noises = [torch.randn(model.in_channels, -(-n // sf), generator=gen) for n in LENGTHS]
+    ragged = {k: StyleMelGANRaggedSynthesizer(model, max_batch=k, bucket_segments=2) for k in (16, 8)}
+
+    def inference():  # (decode's loop: the features go up per utterance, the noise is drawn by inference itself)
+        with torch.no_grad():
+            return [model.inference(f.to(dev)).reshape(-1) for f in feats]
+
+    runs = {"ragged16": lambda: ragged[16].synthesize_many(feats), "ragged8": lambda: ragged[8].synthesize_many(feats),
+            "inference": inference}
+    # what the contenders compute, on the same noise: every utterance against model.inference
+    with torch.no_grad():
+        ref = [model.inference(f.to(dev), z=z.unsqueeze(0).to(dev)).reshape(-1) for f, z in zip(feats, noises)]
+    diffs = {f"ragged{k}": max(float((y - r).abs().max()) for y, r in zip(ragged[k].synthesize_many(feats, noises=noises), ref))
+             for k in ragged}
+    peak = max(float(r.abs().max()) for r in ref)
+    for fn in runs.values():  # warm: graphs captured, weight images cached
+        fn()
+    ms = {n: [] for n in runs}
+    for _ in range(ROUNDS):
+        for n, fn in runs.items():
+            ms[n].append(wall_ms(fn, REPS))
+
+    # the padded block of ragged16: the plain forward (inexact: its norms see the padding) against forward_ragged
+    plan = ragged[16].plan(LENGTHS)
+    s_pad = plan.groups[0].t_pad
+    c = torch.randn(16, 80, s_pad * sf, device=dev)
+    z = torch.randn(16, model.in_channels, s_pad, device=dev)
+    segments = torch.tensor(plan.groups[0].frames, dtype=torch.int32, device=dev)
+    plain_graph = GraphedInference(model)
+    plain_graph(c, z)
+    ragged[16]._run(c, segments, z)
+    dev_ms = {"forward_graph": [], "ragged_graph": []}
+    for _ in range(ROUNDS):
+        dev_ms["forward_graph"].append(event_ms(lambda: plain_graph(c, z), REPS))
+        dev_ms["ragged_graph"].append(event_ms(lambda: ragged[16]._run(c, segments, z), REPS))
+    with torch.no_grad():
+        model(c, z), model.forward_ragged(c, z, segments)
+        with ops.profile() as prof_plain:
+            model(c, z)
+        with ops.profile() as prof_ragged:
+            model.forward_ragged(c, z, segments)
+    fam_plain, fam_ragged = families(prof_plain), families(prof_ragged)
+    # the plain upsample / modulate / gate launches carry no profile scope (csrc/elementwise.hip): counted from
+    # TADEResBlock.forward -- two modulations, two gates, the residual upsample + add, and tade2's upsample where f != 1
+    unscoped = sum(5 + (b.upsample_factor != 1) for b in model.blocks)
+    launches = dict(forward=sum(v["launches"] for v in fam_plain.values()) + unscoped,
+                    forward_ragged=sum(v["launches"] for v in fam_ragged.values()),
+                    plain_launches_without_a_profile_scope=unscoped)
+    samples = sum(LENGTHS) * up
+    out = dict(model="style_melgan.v1 generator (the class defaults)", precision="fp32", lengths=LENGTHS,
+               frames_total=sum(LENGTHS), weights="seeded synthetic weights (tests/golden/synth.py, seed 12, g_scale 0.8), "
+               "weight norm removed", audio_seconds_at_22050=samples / 22050.0, rounds=ROUNDS, reps=REPS,
+               segment_frames=sf, segments=[-(-n // sf) for n in LENGTHS],
+               padded_fraction={k: ragged[k].plan(LENGTHS).padded_fraction for k in ragged},
+               s_pad={k: [g.t_pad for g in ragged[k].plan(LENGTHS).groups] for k in ragged},
+               wall_ms_per_list={n: summary(v) for n, v in ms.items()},
+               msamples_per_s={n: samples / statistics.median(v) / 1e3 for n, v in ms.items()},
+               max_abs_vs_inference_same_noise=diffs, peak_abs_of_inference=peak,
+               padded_block=dict(shape=[16, 80, s_pad * sf], device_ms={n: summary(v) for n, v in dev_ms.items()},
+                                 launches=launches,
+                                 profiler_ms=dict(forward_scoped_kernels_only=sum(v["ms"] for v in fam_plain.values()),
+                                                  forward_ragged=sum(v["ms"] for v in fam_ragged.values())),
+                                 families=dict(forward=fam_plain, forward_ragged=fam_ragged)))
+    for n, v in ms.items():
+        print(f"{n:13s} {statistics.median(v):8.2f} ms per list  [{min(v):8.2f} .. {max(v):8.2f}]  "
+              f"{out['msamples_per_s'][n]:6.1f} M samples/s")
+    print("max |ragged - inference| on the same noise: " + ", ".join(f"{k} {v:.2e}" for k, v in diffs.items())
+          + f" (peak |inference| {peak:.2e})")
+    for n, v in dev_ms.items():
+        print(f"{n:13s} {statistics.median(v):8.2f} ms per replay [{min(v):8.2f} .. {max(v):8.2f}]  (16 x {s_pad} segments)")
+    print(f"launches: one plain forward {launches['forward']} ({unscoped} of them counted from the code), one ragged forward "
+          f"{launches['forward_ragged']}, {fam_ragged['zero_tail_kernel']['launches']} of them zero_tail")
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(out, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--precision", default="fp32", choices=("fp32", "bf16"))
-    ap.add_argument("--model", default="hifigan", choices=("hifigan", "melgan", "pwg"))
+    ap.add_argument("--model", default="hifigan", choices=("hifigan", "melgan", "pwg", "style_melgan"))
     ap.add_argument("--multiband", action="store_true", help="--model melgan: the multi_band_melgan.v2 generator + PQMF")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
@@ -212,6 +304,10 @@ def main():
     torch.manual_seed(0)
     if args.model == "pwg":
         return main_pwg(args, dev)
+    if args.model == "style_melgan":
+        if args.precision != "fp32":
+            raise SystemExit("bench_ragged.py: the ragged StyleMelGAN forward is fp32 only")
+        return main_style_melgan(args, dev)
     if melgan:
         # seeded weights of audible amplitude (tests/golden/synth.py), as tools/bench_stream.py builds them
         params = dict(out_channels=4, channels=384, upsample_scales=[8, 4, 2], stacks=4) if args.multiband else {}
