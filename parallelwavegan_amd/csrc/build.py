@@ -22,10 +22,12 @@ EXTRA = {"conv1d.hip": ["-fno-honor-nans", "-mno-amdgpu-ieee"],
          # contracts re*re + im*im differently in the two inlined copies
          "stft_fft.hip": ["-ffp-contract=off"],
          # the 3-way operand split is exact only if v * slope (the pre-activation) is rounded to fp32 BEFORE its bf16
-         # head is subtracted: no fused multiply-subtract across the two
-         "conv1d_split.hip": ["-ffp-contract=off"],
+         # head is subtracted: no fused multiply-subtract across the two.  No SLP vectoriser: it pairs the staging's
+         # scalar fp32 multiplies and subtractions into v_pk_*_f32, which cost more beside another workgroup's MFMAs
+         # than the scalar instructions they replace (split3_pair, csrc/mfma_conv.h)
+         "conv1d_split.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
          # the same split, of lrelu(x) and of the intermediate h: bit-identical to two chained conv1d_split launches
-         "resunit_split.hip": ["-ffp-contract=off"]}
+         "resunit_split.hip": ["-ffp-contract=off", "-fno-slp-vectorize"]}
 
 
 def sources():

@@ -35,8 +35,9 @@ constexpr int PARTS = 3;
 struct SplitArgs : MfmaConvArgs {
   int plane;          // bf16 elements per LDS plane
   long part_stride;   // bf16x8 elements per weight part image
-  float pre_mul;      // pre-activation, one branch-free form for none / leaky / relu (pre_activate)
-  unsigned pre_mask;
+  float pre_mul;      // pre-activation: SplitActMasked{pre_mul, pre_mask} for none / leaky / relu, or, where pre_leaky is
+  unsigned pre_mask;  // set (leaky with 0 < slope < 1), SplitActLeaky{pre_mul}; split_staged picks the form of a launch
+  int pre_leaky;
   int wide_out;  // y / add1 / add2 are 16-B aligned and t_out % 4 == 0: 16-B accesses in the epilogue
 };
 
@@ -44,21 +45,24 @@ static int split_geometry(const pwg_conv1d_desc* d, MfmaConvGeom* g) {
   return mfma_conv_geometry("conv1d_split", PARTS, false, d, g);
 }
 
-// The pre-activation without control flow: v > 0 ? v : bits(v * mul) & mask, with (mul, mask) = (1, ~0) for none,
-// (slope, ~0) for leaky and (0, 0) for relu.  For finite v these are the bits of apply_act(): v * 1 is v, v * slope is
-// the same rounded product, and the relu's negative side is +0.0 (the mask clears the sign of v * 0).
-__device__ __forceinline__ float pre_activate(float v, float mul, unsigned mask) {
-  const float n = __uint_as_float(__float_as_uint(v * mul) & mask);
-  return v > 0.f ? v : n;
+// Run a staging site with the activation form of the launch (mfma_conv.h): wave-uniform, one branch around the site
+template <typename Site>
+__device__ __forceinline__ void split_staged(const SplitArgs& a, Site&& site) {
+  if (a.pre_leaky)
+    site(SplitActLeaky{a.pre_mul});
+  else
+    site(SplitActMasked{a.pre_mul, a.pre_mask});
 }
 
 // Vector staging of one 32-channel chunk of the x window (xc: channel 0 of the chunk, c_left channels are left).
 // item = (group of 4 columns, channel octet): 8 loads of 16 B (one per channel, lanes walk t), then per column 8 channels
 // are activated, split and written as three 16-B LDS stores (one per plane).  CHECKED (edge tiles): a load whose group
-// of columns lies outside the row or whose channel is past the end gives zeros.
-template <int NT, bool CHECKED>
+// of columns lies outside the row or whose channel is past the end gives zeros.  It reads a clamped address that is
+// always valid (the group clamped into the row, the channel to the last one) and the value is zeroed by a select, so
+// the 8 loads of an item are in flight together as in the interior copy, not one round trip each behind its own branch.
+template <int NT, bool CHECKED, typename Act>
 __device__ __forceinline__ void stage_window_vec(const SplitArgs& a, const float* __restrict__ xc, int c_left, int base,
-                                                 int ngroups, __bf16* xs, int tid) {
+                                                 int ngroups, __bf16* xs, int tid, Act act) {
   constexpr int ITEMS = window_items(NT);
   f32x4 st[ITEMS][8];
 #pragma unroll
@@ -73,11 +77,11 @@ __device__ __forceinline__ void stage_window_vec(const SplitArgs& a, const float
       }
     } else {
       const bool tin = grp < ngroups && t >= 0 && t < a.t_in;
+      const float* __restrict__ srcc = xc + min(max(t, 0), a.t_in - 4);  // t_in % 4 == 0, t_in >= 4
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (tin && oct * 8 + j < c_left) v = *reinterpret_cast<const f32x4*>(src + (size_t)j * a.t_in);
-        st[it][j] = v;
+        const f32x4 v = *reinterpret_cast<const f32x4*>(srcc + (size_t)min(oct * 8 + j, c_left - 1) * a.t_in);
+        st[it][j] = tin && oct * 8 + j < c_left ? v : f32x4{0.f, 0.f, 0.f, 0.f};
       }
     }
   }
@@ -89,7 +93,7 @@ __device__ __forceinline__ void stage_window_vec(const SplitArgs& a, const float
       for (int e = 0; e < 4; ++e) {
         float v[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = pre_activate(st[it][j][e], a.pre_mul, a.pre_mask);
+        for (int j = 0; j < 8; ++j) v[j] = act(st[it][j][e]);
         split3_store<8>(v, xs + (grp * 4 + e) * kConvRow + oct * 8, a.plane);
         // one column at a time: the scheduler otherwise interleaves all 32 splits and spills the accumulators
         __builtin_amdgcn_sched_barrier(0);
@@ -199,37 +203,41 @@ __device__ __forceinline__ void split_epilogue(const SplitArgs& a, const typenam
   }
 }
 
-// One 32-channel chunk of the x window into the three LDS planes, as conv1d_split_mfma_kernel stages it (the streamed and
-// the transposed kernel)
-template <int NT, bool VEC>
-__device__ __forceinline__ void stage_chunk(const SplitArgs& a, const MfmaConvTile& c, int chunk, __bf16* xs) {
+// One 32-channel chunk of the x window into the three LDS planes: the staging of every kernel of this file
+template <int NT, bool VEC, typename Act>
+__device__ __forceinline__ void stage_chunk(const SplitArgs& a, const MfmaConvTile& c, int chunk, __bf16* xs, Act act) {
   if (VEC) {
     const int ngroups = (c.wcols + 3) >> 2, c_left = a.c_in - chunk * KC;
     const float* __restrict__ xc = c.xb + (size_t)chunk * KC * a.t_in;
+    // an interior tile (decided once per workgroup and chunk: every staged column inside the row, a whole chunk of
+    // channels) takes unconditional loads; an edge tile checks every load
     if (c.base >= 0 && c.base + 4 * ngroups <= a.t_in && c_left >= KC)
-      stage_window_vec<NT, false>(a, xc, c_left, c.base, ngroups, xs, c.tid);
+      stage_window_vec<NT, false>(a, xc, c_left, c.base, ngroups, xs, c.tid, act);
     else
-      stage_window_vec<NT, true>(a, xc, c_left, c.base, ngroups, xs, c.tid);
+      stage_window_vec<NT, true>(a, xc, c_left, c.base, ngroups, xs, c.tid, act);
   } else {
+    // wave `wave` stages channel octet `wave` of the chunk: lanes walk the columns (coalesced fp32 rows)
     const int c_base = chunk * KC + c.wave * 8;
     const bool interior = c.base >= 0 && c.base + c.wcols <= a.t_in && c_base + 8 <= a.c_in;  // per wave and chunk
     for (int col = c.lane; col < c.wcols; col += 64) {
       const int t = c.base + col;
-      const float* __restrict__ src = c.xb + (size_t)c_base * a.t_in + t;
       float f[8];
       if (interior) {
+        const float* __restrict__ src = c.xb + (size_t)c_base * a.t_in + t;
 #pragma unroll
         for (int j = 0; j < 8; ++j) f[j] = src[(size_t)j * a.t_in];
       } else {
+        // as the CHECKED vector copy: a clamped, always valid address and a select, the 8 loads in flight together
         const bool tin = t >= 0 && t < a.t_in;
+        const float* __restrict__ srcc = c.xb + min(max(t, 0), a.t_in - 1);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-          f[j] = 0.f;
-          if (tin && c_base + j < a.c_in) f[j] = src[(size_t)j * a.t_in];
+          const float v = srcc[(size_t)min(c_base + j, a.c_in - 1) * a.t_in];
+          f[j] = tin && c_base + j < a.c_in ? v : 0.f;
         }
       }
 #pragma unroll
-      for (int j = 0; j < 8; ++j) f[j] = pre_activate(f[j], a.pre_mul, a.pre_mask);
+      for (int j = 0; j < 8; ++j) f[j] = act(f[j]);
       split3_store<8>(f, xs + col * kConvRow + c.wave * 8, a.plane);
     }
   }
@@ -254,7 +262,6 @@ conv1d_split_mfma_kernel(SplitArgs a) {
   __bf16* xs = reinterpret_cast<__bf16*>(smem);  // [part][column][ROW]
 
   const MfmaConvTile c = mfma_conv_tile<TILE, MT, NT, WAVES_M, VEC>(a);
-  const float* __restrict__ xb = c.xb;
 
   acc_t acc[TM][TN];
 #pragma unroll
@@ -266,39 +273,7 @@ conv1d_split_mfma_kernel(SplitArgs a) {
 
   for (int chunk = 0; chunk < a.cin_chunks; ++chunk) {
     if (chunk) __syncthreads();
-    if (VEC) {
-      // an interior tile (decided once per workgroup and chunk: every staged column inside the row, a whole chunk of
-      // channels) takes unconditional loads; an edge tile checks every load
-      const int ngroups = (c.wcols + 3) >> 2, c_left = a.c_in - chunk * KC;
-      const float* __restrict__ xc = xb + (size_t)chunk * KC * a.t_in;
-      if (c.base >= 0 && c.base + 4 * ngroups <= a.t_in && c_left >= KC)
-        stage_window_vec<NT, false>(a, xc, c_left, c.base, ngroups, xs, c.tid);
-      else
-        stage_window_vec<NT, true>(a, xc, c_left, c.base, ngroups, xs, c.tid);
-    } else {
-      // wave `wave` stages channel octet `wave` of the chunk: lanes walk the columns (coalesced fp32 rows)
-      const int c_base = chunk * KC + c.wave * 8;
-      const bool interior = c.base >= 0 && c.base + c.wcols <= a.t_in && c_base + 8 <= a.c_in;  // per wave and chunk
-      for (int col = c.lane; col < c.wcols; col += 64) {
-        const int t = c.base + col;
-        const float* __restrict__ src = xb + (size_t)c_base * a.t_in + t;
-        float f[8];
-        if (interior) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) f[j] = src[(size_t)j * a.t_in];
-        } else {
-          const bool tin = t >= 0 && t < a.t_in;
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            f[j] = 0.f;
-            if (tin && c_base + j < a.c_in) f[j] = src[(size_t)j * a.t_in];
-          }
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) f[j] = pre_activate(f[j], a.pre_mul, a.pre_mask);
-        split3_store<8>(f, xs + col * kConvRow + c.wave * 8, a.plane);
-      }
-    }
+    split_staged(a, [&](auto act) { stage_chunk<NT, VEC>(a, c, chunk, xs, act); });
     __syncthreads();
     for (int tap = 0; tap < a.taps; ++tap) {
 #pragma unroll
@@ -362,7 +337,7 @@ conv1d_split_streamed_mfma_kernel(SplitArgs a) {
 
   for (int chunk = 0; chunk < a.cin_chunks; ++chunk) {
     if (chunk) __syncthreads();
-    stage_chunk<NT, VEC>(a, c, chunk, xs);
+    split_staged(a, [&](auto act) { stage_chunk<NT, VEC>(a, c, chunk, xs, act); });
     __syncthreads();
 #pragma unroll 1
     for (int s = 0; s < a.taps * KSTEPS; ++s) {  // the steps of this chunk: the planes hold one chunk
@@ -420,8 +395,9 @@ __device__ __forceinline__ void request_raw_window(const float* __restrict__ xw,
 // Measured and not kept (profiles/split_window.txt): lanes that walk the COLUMNS (8 values per lane and pass, plane rows
 // 80 B apart instead of 320 B, which halves the LDS bank conflicts of this form) -- a VGPR spill in the flagship
 // instantiation, 0.97 x of the staged kernel at 16 x 800 frames where this form has 0.96 x, 0.94 x at 1 x 800.
+template <typename Act>
 __device__ __forceinline__ void split_raw_window(const SplitArgs& a, const float* raww, int ngroups, __bf16* xs, int wave,
-                                                 int lane) {
+                                                 int lane, Act act) {
   for (int grp = lane; grp < ngroups; grp += 64) {
     f32x4 st[8];
 #pragma unroll
@@ -430,7 +406,7 @@ __device__ __forceinline__ void split_raw_window(const SplitArgs& a, const float
     for (int e = 0; e < 4; ++e) {
       float v[8];
 #pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = pre_activate(st[j][e], a.pre_mul, a.pre_mask);
+      for (int j = 0; j < 8; ++j) v[j] = act(st[j][e]);
       split3_store<8>(v, xs + (grp * 4 + e) * kConvRow + wave * 8, a.plane);
       __builtin_amdgcn_sched_barrier(0);  // one column at a time, as in stage_window_vec
     }
@@ -487,9 +463,9 @@ conv1d_split_window_mfma_kernel(SplitArgs a) {
     if (chunk) __syncthreads();
     if (prefetched(chunk)) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      split_raw_window(a, raww, ngroups, xs, c.wave, c.lane);
+      split_staged(a, [&](auto act) { split_raw_window(a, raww, ngroups, xs, c.wave, c.lane, act); });
     } else {
-      stage_chunk<NT, true>(a, c, chunk, xs);
+      split_staged(a, [&](auto act) { stage_chunk<NT, true>(a, c, chunk, xs, act); });
     }
     __syncthreads();
     if (chunk + 1 < a.cin_chunks && prefetched(chunk + 1))
@@ -544,6 +520,7 @@ static void split_fill_args(SplitArgs* a, const pwg_conv1d_desc* d, const MfmaCo
   a->part_stride = image_elems(g) / 8;
   a->pre_mul = d->pre_act == PWG_ACT_LEAKY_RELU ? d->pre_slope : (d->pre_act == PWG_ACT_RELU ? 0.0f : 1.0f);
   a->pre_mask = d->pre_act == PWG_ACT_RELU ? 0u : ~0u;
+  a->pre_leaky = split_act_is_leaky(d->pre_act, d->pre_slope);
   a->wide_out = d->t_out % 4 == 0 && ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(add1) |
                                        reinterpret_cast<uintptr_t>(add2)) & 15u) == 0;
 }
@@ -827,7 +804,7 @@ convtr1d_split_mfma_kernel(ConvtrArgs a) {
 
   for (int chunk = 0; chunk < a.cin_chunks; ++chunk) {
     if (chunk) __syncthreads();
-    stage_chunk<NT, VEC>(a, c, chunk, xs);
+    split_staged(a, [&](auto act) { stage_chunk<NT, VEC>(a, c, chunk, xs, act); });
     __syncthreads();
     for (int tap = 0; tap < a.taps; ++tap) {
 #pragma unroll

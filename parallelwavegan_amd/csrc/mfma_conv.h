@@ -5,7 +5,10 @@
 //   coverage, tile rule   mfma_conv_geometry         128 / 64 / 32 rows x 128 / 128 / 256 columns from the GEMM rows
 //   weight image          image_chunks, image_m_pad, image_elems, image_decode, image_rows, mfma_conv_pack
 //                                                    [tap][ci / 8][m_pad][8] per part
-//   split arithmetic      split3, split3_store, split_product   the 3-way split of a value; N values split and stored, a
+//   split arithmetic      SplitActLeaky, SplitActMasked   the activation of a value in front of its split: max(v, v * slope)
+//                                                    for leaky with 0 < slope < 1, (mul, mask) for every other kind
+//                         split3, split3_pair, split3_store, split_product   the 3-way split of a value, of two values
+//                                                    as packed words; N values split and stored, a
 //                                                    vector per plane; one of the six part products of a row tile.
 //                                                    split_product OWNS the product order of conv1d_split.hip and
 //                                                    resunit_split.hip, which must agree to the bit
@@ -144,16 +147,68 @@ __device__ __forceinline__ void split3(float v, __bf16& hi, __bf16& mid, __bf16&
   lo = (__bf16)(r - (float)mid);
 }
 
+// The activation of a value in front of its split ("activate and split" has one owner: every staging and forming site of
+// conv1d_split.hip and resunit_split.hip applies one of the two forms below and then split3 / split3_store).  The kind is
+// fixed at launch and wave-uniform: a site is instantiated once per form and the launch's form is chosen around it.
+//
+// SplitActMasked: none / leaky / relu without control flow: v > 0 ? v : bits(v * mul) & mask, with (mul, mask) = (1, ~0)
+// for none, (slope, ~0) for leaky and (0, 0) for relu.  For finite v these are the bits of apply_act(): v * 1 is v,
+// v * slope is the same rounded product, and the relu's negative side is +0.0 (the mask clears the sign of v * 0).
+struct SplitActMasked {
+  float mul;
+  unsigned mask;
+  __device__ __forceinline__ float operator()(float v) const {
+    const float n = __uint_as_float(__float_as_uint(v * mul) & mask);
+    return v > 0.f ? v : n;
+  }
+};
+// SplitActLeaky: leaky with 0 < slope < 1 (split_act_is_leaky) as max(v, v * slope), two instructions a value.  The same
+// bits as the select for every finite v: a positive v is above its product, a negative v below the same rounded product,
+// and +-0 * slope = +-0.  The max is v_med3_f32 against FLT_MAX: under IEEE mode fmaxf grows a canonicalising v_max per
+// input that was loaded, not computed; the median of three takes the operands as they are.
+struct SplitActLeaky {
+  float slope;
+  __device__ __forceinline__ float operator()(float v) const {
+    return __builtin_amdgcn_fmed3f(v, v * slope, 3.40282347e+38f);
+  }
+};
+static inline bool split_act_is_leaky(int act, float slope) {
+  return act == PWG_ACT_LEAKY_RELU && slope > 0.f && slope < 1.f;
+}
+
 // Split N (8 or 4) fp32 values and write one N-wide vector per plane: hi at dst, mid at dst + plane, lo at
 // dst + 2 * plane.  The values are final: the caller has applied its activation.
+// The values go two at a time (split3_pair): one packed conversion per part serves both, and the arithmetic between the
+// conversions stays scalar.
+//
+// split3 of a and b, as the words (b's part << 16 | a's part): the bits of split3 -- float(hi) is hi's bits << 16 -- at
+// 11 VALU instructions a pair (3 v_cvt_pk_bf16_f32, 2 x (v_perm + v_and), 4 v_sub_f32).  a's part moves up by a byte
+// permute, not a shift: a shift is folded through the pack into a second conversion of a alone.  The subtractions stay
+// scalar because the translation units that use this are built without the SLP vectoriser (build.py): paired into
+// v_pk_add_f32 they cost more beside another workgroup's MFMAs than the two scalar ones (profiles/split_staging.txt).
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ unsigned split_pack2(float a, float b) {
+  const bf16x2 p = {(__bf16)a, (__bf16)b};
+  return __builtin_bit_cast(unsigned, p);
+}
+__device__ __forceinline__ float split_low_part(unsigned w) {  // bytes {w1, w0, 0, 0}
+  return __uint_as_float(__builtin_amdgcn_perm(w, w, 0x01000c0cu));
+}
+__device__ __forceinline__ void split3_pair(float a, float b, unsigned& hi, unsigned& mid, unsigned& lo) {
+  hi = split_pack2(a, b);
+  const float ra = a - split_low_part(hi), rb = b - __uint_as_float(hi & 0xffff0000u);
+  mid = split_pack2(ra, rb);
+  const float la = ra - split_low_part(mid), lb = rb - __uint_as_float(mid & 0xffff0000u);
+  lo = split_pack2(la, lb);
+}
 template <int N>
 __device__ __forceinline__ void split3_store(const float (&v)[N], __bf16* dst, int plane) {
-  typedef __bf16 vec_t __attribute__((ext_vector_type(N)));
+  typedef unsigned vec_t __attribute__((ext_vector_type(N / 2)));
   vec_t vh, vm, vl;
 #pragma unroll
-  for (int j = 0; j < N; ++j) {
-    __bf16 hi, mid, lo;
-    split3(v[j], hi, mid, lo);
+  for (int j = 0; j < N / 2; ++j) {
+    unsigned hi, mid, lo;
+    split3_pair(v[2 * j], v[2 * j + 1], hi, mid, lo);
     vh[j] = hi;
     vm[j] = mid;
     vl[j] = lo;

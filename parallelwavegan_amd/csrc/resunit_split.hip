@@ -83,25 +83,36 @@ struct RuSplitCfg {
 // Stage the whole C-channel window: item = (group of 4 columns, channel octet), at most two per thread: 8 loads of 16 B
 // (one per channel, along t), then per column 8 channels are activated, split and written as three 16-B LDS stores.
 // T % 4 == 0 and the first staged column is a multiple of 4: a group lies inside the row or outside it.  CHECKED (first
-// / last tiles of a row): a group outside [0, T) gives zeros = the zero padding of conv1.  behind() runs between the
+// / last tiles of a row): a group outside [0, T) gives zeros = the zero padding of conv1: it reads a clamped, always
+// valid address and is zeroed by a select (conv1d_split.hip, stage_window_vec).  behind() runs between the
 // window's loads and its LDS stores: what it requests is in flight while the window is activated and split.
 template <int C, bool CHECKED, typename Behind>
 __device__ __forceinline__ void ru_stage_window(const RuSplitArgs& a, const float* __restrict__ xb, int base, __bf16* xs,
                                                 int tid, Behind&& behind) {
   constexpr int OCTS = RuSplitCfg<C>::OCTS, ROW = RuSplitCfg<C>::ROW;
   const int nitems = (a.rows >> 2) * OCTS;
+  const SplitActLeaky act{a.slope1};  // 0 < slope < 1 (ru_split_geometry)
   f32x4 st[2][8];
 #pragma unroll
   for (int it = 0; it < 2; ++it) {
     const int idx = tid + it * 256, oct = idx % OCTS, grp = idx / OCTS;
     const int t = base + grp * 4;
-    const float* __restrict__ src = xb + (size_t)(oct * 8) * a.T + t;
     const bool in = idx < nitems && (!CHECKED || (t >= 0 && t < a.T));
+    if (!CHECKED) {
+      const float* __restrict__ src = xb + (size_t)(oct * 8) * a.T + t;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (in) v = *reinterpret_cast<const f32x4*>(src + (size_t)j * a.T);
-      st[it][j] = v;
+      for (int j = 0; j < 8; ++j) {
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (in) v = *reinterpret_cast<const f32x4*>(src + (size_t)j * a.T);
+        st[it][j] = v;
+      }
+    } else {
+      const float* __restrict__ src = xb + (size_t)(oct * 8) * a.T + min(max(t, 0), a.T - 4);  // T % 4 == 0, T >= 4
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(src + (size_t)j * a.T);
+        st[it][j] = in ? v : f32x4{0.f, 0.f, 0.f, 0.f};
+      }
     }
   }
   behind();
@@ -113,10 +124,7 @@ __device__ __forceinline__ void ru_stage_window(const RuSplitArgs& a, const floa
       for (int e = 0; e < 4; ++e) {
         float v[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const float s = st[it][j][e];
-          v[j] = s > 0.f ? s : s * a.slope1;
-        }
+        for (int j = 0; j < 8; ++j) v[j] = act(st[it][j][e]);
         split3_store<8>(v, xs + (grp * 4 + e) * ROW + oct * 8, a.plane);
         __builtin_amdgcn_sched_barrier(0);  // one column at a time (conv1d_split.hip, stage_window_vec)
       }
@@ -275,6 +283,7 @@ __global__ __launch_bounds__(256, 2) void resunit_split_kernel(RuSplitArgsOf<RAG
     __syncthreads();  // every wave has read its x columns: the h planes take their place
     // h = lrelu(acc + b1), zero outside [0, Tv) (conv2's zero padding; Tv = T in the plain form), split: a lane owns
     // channels c .. c + 3 of a column
+    const SplitActLeaky act2{a.slope2};
 #pragma unroll
     for (int mi = 0; mi < TM; ++mi)
 #pragma unroll
@@ -291,7 +300,7 @@ __global__ __launch_bounds__(256, 2) void resunit_split_kernel(RuSplitArgsOf<RAG
           for (int e = 0; e < 4; ++e) {
             v[e] = acc[mi][ni][4 * g + e];
             if (has_b1) v[e] += bias[e];
-            v[e] = v[e] > 0.f ? v[e] : v[e] * a.slope2;
+            v[e] = act2(v[e]);
             v[e] = inside ? v[e] : 0.f;
             acc[mi][ni][4 * g + e] = 0.f;
           }
@@ -610,6 +619,7 @@ __global__ __launch_bounds__(256, 2) void resblock_split_kernel(RbSplitArgs a) {
     if (last && has2) request_values(a.u.add2, ad2, true);   // (so does add2)
     __syncthreads();  // every wave has read its x columns: the h planes take their place
     // h = lrelu(acc + b1), zero outside [0, T), split: a lane owns channels c .. c + 3 of a column
+    const SplitActLeaky act2{a.slope2[u]};
 #pragma unroll
     for (int mi = 0; mi < TM; ++mi)
 #pragma unroll
@@ -626,7 +636,7 @@ __global__ __launch_bounds__(256, 2) void resblock_split_kernel(RbSplitArgs a) {
           for (int e = 0; e < 4; ++e) {
             v[e] = acc[mi][ni][4 * g + e];
             if (has_b1) v[e] += bias[e];
-            v[e] = v[e] > 0.f ? v[e] : v[e] * a.slope2[u];
+            v[e] = act2(v[e]);
             v[e] = inside ? v[e] : 0.f;
             acc[mi][ni][4 * g + e] = 0.f;
           }
@@ -641,7 +651,7 @@ __global__ __launch_bounds__(256, 2) void resblock_split_kernel(RbSplitArgs a) {
     // ---- between units: y_u = acc + b2 + x_u (the epilogue's order), zero outside [0, T); it is the next unit's
     // residual, and lrelu(y_u) with the next unit's slope1, split, is the next unit's window
     ru_request<C, TILE>(wf, a.w1[u + 1], part_stride, wrow, h);
-    const float slope = a.slope1[u + 1];
+    const SplitActLeaky act1{a.slope1[u + 1]};
     __syncthreads();  // every wave has read its h columns
 #pragma unroll
     for (int mi = 0; mi < TM; ++mi) {
@@ -662,14 +672,15 @@ __global__ __launch_bounds__(256, 2) void resblock_split_kernel(RbSplitArgs a) {
         if (!inside) v = f32x4{0.f, 0.f, 0.f, 0.f};
         res[mi][n] = v;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float s = v[e] > 0.f ? v[e] : v[e] * slope;
-          __bf16 hi, mid, lo;
-          split3(s, hi, mid, lo);
-          __bf16* dst = fr + (slot + e) * ROW + c;
-          dst[0] = hi;
-          dst[plane] = mid;
-          dst[2 * plane] = lo;
+        for (int e = 0; e < 4; e += 2) {  // two samples per split3_pair; a sample is a column: 2-byte writes
+          unsigned part[3];
+          split3_pair(act1(v[e]), act1(v[e + 1]), part[0], part[1], part[2]);
+          unsigned short* dst = reinterpret_cast<unsigned short*>(fr + (slot + e) * ROW + c);
+#pragma unroll
+          for (int q = 0; q < 3; ++q) {
+            dst[q * plane] = (unsigned short)part[q];
+            dst[q * plane + ROW] = (unsigned short)(part[q] >> 16);
+          }
         }
       }
     }
